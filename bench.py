@@ -16,9 +16,12 @@ One timed "step" = one camera frame of config[1] (EuRoC MH_01 stereo, 'accurate'
 this GPU processes in lock-step (offline batch-of-sequences mode; default 4096 = 16.5 GB of HBM per GPU):
     preprocessImage : CLAHE + device-resident pyramid (/root/reference/src/visual_front_end.cpp:1143-1177)
     kltTracking     : fbKltTracking pass A (nbpyrlvl 1, keypoints with a 3-D prior) + pass B (nbpyrlvl 3)  (:132-275)
-`value` = tracked frames/s over all sequences and ranks (max-over-ranks time), inputs resident in HBM.
+`value` = tracked frames/s over all sequences and ranks (max-over-ranks time), inputs resident in HBM; `ms_per_step` = the
+wall time of one timed step.  The inputs are seeded: the same arguments give the same inputs in every run.
+    --dump-outputs DIR  after the timed steps: what the last one computed (tracked positions, status, CLAHE'd frames) as DIR/*.npy
+    --details FILE      the full record below as JSON; the stdout line keeps the headline fields and each section's scalars
 
-The same line also carries:
+The record also carries (their scalars on the stdout line, all of it with --details):
     single_sequence : ONE camera stream through the drop-in entry (ov2_tracker_track_frame: one H2D of the frame, one
                       LK launch, one sync, hipGraph replay) -- PCIe-inclusive per-frame latency and frames/s; this is the
                       mode configs[1], [2] and [4] of BASELINE.json actually use
@@ -775,6 +778,74 @@ def ba_section(ctx):
     return out, pb, gpu_poses
 
 
+DUMP_BUDGET = 60 * 10 ** 6          # bytes of .npy data written by --dump-outputs (under 64 MB with the headers)
+DUMP_IMAGES = 8                     # sequences whose CLAHE'd level 0 is written
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+            "config")
+LINE_LIMIT = 8192                   # bytes of the stdout result line
+
+
+def dump_outputs(path, pos_d, status_d, pyr, S):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the tracked positions and the status of every
+    sequence's keypoints (a fixed, seeded sample of the sequences should they exceed the budget) -- and level 0 of the step's `cur`
+    pyramid, the CLAHE'd frame the next step and the detector read, for a fixed, seeded sample of DUMP_IMAGES sequences.  float32 /
+    float64 .npy files; the `*sequence_index` arrays say which sequences the rows are."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(2024)
+    n_img = min(DUMP_IMAGES, S)
+    img_idx = np.sort(rng.choice(S, n_img, replace=False))
+    per_seq = NKPS * 3 * 4                                       # x, y and status as float32
+    n_seq = int(min(S, (DUMP_BUDGET - n_img * W * H * 4) // per_seq))
+    seq_idx = np.arange(S) if n_seq == S else np.sort(rng.choice(S, n_seq, replace=False))
+    arrays = {"tracked_xy": pos_d.cpu().numpy()[seq_idx].astype(np.float32),
+              "status": status_d.cpu().numpy()[seq_idx].astype(np.float32),
+              "sequence_index": seq_idx.astype(np.float64),
+              "clahe_level0": np.stack([pyr.download(0, int(b))[0] for b in img_idx]).astype(np.float32),
+              "clahe_level0_sequence_index": img_idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _finite(x):
+    """NaN / inf -> None, recursively: the record stays strict JSON"""
+    if isinstance(x, float):
+        return x if np.isfinite(x) else None
+    if isinstance(x, dict):
+        return {k: _finite(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_finite(v) for v in x]
+    return x
+
+
+def result_line(out):
+    """The one JSON line on stdout: the headline fields and the config as measured, every other section cut to its scalar entries
+    (floats to 6 significant digits; of its text the short words -- units, bounds -- and errors, cut to 300 characters).  The full
+    record with its notes is --details.  A line above LINE_LIMIT bytes falls back to the headline fields alone."""
+    def short(v):
+        if isinstance(v, float):
+            return float("%.6g" % v)
+        if isinstance(v, str):
+            return v[-300:]
+        return v
+    line = {}
+    for k, v in out.items():
+        if k in HEADLINE:
+            line[k] = v
+        elif isinstance(v, dict):
+            line[k] = {kk: short(vv) for kk, vv in v.items()
+                       if isinstance(vv, (bool, int, float)) or vv is None or (isinstance(vv, str) and (len(vv) <= 64 or "error" in kk))}
+        elif isinstance(v, (list, tuple)):
+            line[k] = list(v)[:64]
+        else:
+            line[k] = short(v)
+    line = _finite(line)
+    if len(json.dumps(line)) > LINE_LIMIT:
+        line = _finite({k: out[k] for k in HEADLINE if k in out})
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -795,7 +866,15 @@ def main():
                          "retires them, which is what the lock-step batch entry points (the headline mode) exist to avoid")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the single-sequence / config-5 / BA / detect / parity sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (tracked positions, status, a seeded sample of "
+                         "CLAHE'd level-0 images) as DIR/<name>.npy, float32, at most 64 MB")
+    ap.add_argument("--details", metavar="FILE", default=None,
+                    help="write the full record (every side measurement with its notes) to FILE as JSON, e.g. bench_out/details.json; stdout "
+                         "carries its summary")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch(args))
@@ -930,6 +1009,10 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)                  # RCCL: 8 bytes, timings only
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step is i = warmup + steps - 1: its transition's priors hold the tracked positions, its `cur` pyramid the CLAHE'd frame
+        last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, pri_work[last % NT], status_d, pyrs[(last + 1) % 2], S)
     ranks_seen, bus_ids = ranks_and_devices(world, dev.index, False)     # (after the timed region: an all-reduce of ones + the PCI bus ids)
 
     # ---- the pre-processing of a step on LOW-ENTROPY frames (side measurement, rank 0): the CLAHE histogram is built with LDS atomics,
@@ -1331,7 +1414,10 @@ def main():
             except Exception:
                 import traceback
                 out["extras_error"] = traceback.format_exc()[-1500:]
-        print(json.dumps(out))
+        if args.details:
+            with open(args.details, "w") as f:
+                json.dump(_finite(out), f)
+        print(json.dumps(result_line(out), allow_nan=False))
     if world > 1:
         dist.destroy_process_group()
 
