@@ -415,6 +415,46 @@ int ov2_detect_grid_fast_batch_d(ov2_ctx *ctx, const ov2_pyr *pyr, int cell, con
 int ov2_corner_subpix(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stride,
                       float *xy_inout_h, int n, int half_win, int max_iter, double eps);
 
+/* ---- BRIEF descriptors ----------------------------------------------
+ * FeatureExtractor::describeBRIEF (src/feature_extractor.cpp:224-285): cv::xfeatures2d::BriefDescriptorExtractor with its defaults
+ * (32 bytes, use_orientation = false), called twice per keyframe from MapManager::extractKeypoints on the RAW left image.  Per point:
+ *   valid     28 <= rint(x) < w-28 and 28 <= rint(y) < h-28 (rint: half to even; NaN / inf never; w or h <= 56: none) -- the
+ *             reference's empty cv::Mat for a rejected point (:263-278) is valid = 0; its descriptor is 32 zero bytes
+ *   centre    cx = (int)(x + 0.5), cy = (int)(y + 0.5)
+ *   bit t     S(ay, ax) < S(by, bx) for test pair t = {ay, ax, by, bx} (row offset first), S(dy, dx) = sum of the 9x9 pixels centred
+ *             at (cy+dy, cx+dx); byte j = tests 8j..8j+7, the first one in the most significant bit
+ * Exact integer arithmetic: results are bit-identical whatever the call form.  Restated from the public OpenCV source (brief.cpp,
+ * keypoint.cpp), not yet confirmed against an OpenCV build (tools/ref_capture/capture_brief.cpp captures the comparison).  One case
+ * is defined differently on purpose: odd w, x == w-28.5 exactly and a +24 column offset (rows alike) make OpenCV read past its
+ * integral image; here a box only ever sums the pixels inside the image.
+ * THE PATTERN IS CONTEXT STATE.  The built-in table (ov2slam_amd/csrc/brief_pattern.hpp, tools/gen_brief_pattern.py) is NOT OpenCV's:
+ * the map only compares descriptors with each other, so any fixed table works there, but a host that mixes these descriptors with
+ * OpenCV-computed ones (the reference's loop closer) must load OpenCV's table first (tests/golden/brief_pattern_opencv.npy, recovered
+ * by tools/brief_pattern_from_probes.py).
+ * Every describe call synchronises the host once.  Scratch: the context's grow-only buffers -- device: the image (host form, rows
+ * padded to 256 B) + 41 B per point slot + 256 B per item; pinned host: 41 B per point slot.  n == 0 returns OV2_OK.            */
+#define OV2_BRIEF_BYTES 32
+/* pairs: 256 x {ay, ax, by, bx}; NULL restores the built-in table; an offset outside [-24, 24] -> OV2_EINVAL, previous table kept */
+int ov2_brief_set_pattern(ov2_ctx *ctx, const int8_t *pairs);
+int ov2_brief_get_pattern(ov2_ctx *ctx, int8_t *pairs);
+/* host image (w x h, rows `stride` bytes apart), n points (x, y) -> desc_h n x 32 bytes, valid_h n flags (0 / 1) */
+int ov2_describe_brief(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stride, const float *xy_h, int n,
+                       uint8_t *desc_h, uint8_t *valid_h);
+/* n_items device images `item_stride` bytes apart (rows `pitch` bytes apart); device points, cap slots per item, n_d[b] of them valid
+ * (n_d NULL: all cap; counts above cap are taken as cap); device outputs in the same slot layout (desc: 32 B per slot; slots past
+ * n_d[b] are not written).  n_items <= 65535.                                                                                     */
+int ov2_describe_brief_batch_d(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int pitch, size_t item_stride, int n_items,
+                               const float *xy_d, int cap, const int *n_d, uint8_t *desc_d, uint8_t *valid_d);
+/* the RAW frame of the tracker's current frame (the image given to the last preprocess / track_frame, before CLAHE -- already in HBM:
+ * no upload); valid until the next preprocess.  Needs one preprocessed frame.                                                 */
+int ov2_tracker_describe_brief(ov2_tracker *t, const float *xy_h, int n, uint8_t *desc_h, uint8_t *valid_h);
+/* the raw frames of the current lock-step step (the last ov2_btracker_track_frame), items [0, n_active) with n_active <= that step's;
+ * host points / outputs with cap slots per item (n_h[b] valid; slots past n_h[b] untouched).  OV2_EINVAL once the staging set that
+ * held those frames has been uploaded or prepared again (ov2_btracker_upload / _prepare of that set, or the next step): in the
+ * look-ahead loop, describe right after the step.                                                                                 */
+int ov2_btracker_describe_brief(ov2_btracker *t, int n_active, const float *xy_h, const int *n_h, int cap,
+                                uint8_t *desc_h, uint8_t *valid_h);
+
 /* ---- local bundle adjustment ----------------------------------------
  * Replaces the two ceres::Solve calls of Optimizer::localBA
  * (src/optimizer.cpp:479 and :618) on the anchored-inverse-depth problem built at

@@ -29,6 +29,7 @@ OV2_LK_ACC_INT64, OV2_LK_ACC_FLOAT_UI4 = 0, 1
 OV2_FAST_TIE_SCAN_ORDER, OV2_FAST_TIE_LIBSTDCXX = 0, 1
 OV2_LK_IMPL_AUTO, OV2_LK_IMPL_ROW, OV2_LK_IMPL_LANE3 = 0, 1, 2
 OV2_TRACK_IMPL_WAVE, OV2_TRACK_IMPL_ROW = 0, 1
+OV2_BRIEF_BYTES = 32
 OV2_RES_LEFT, OV2_RES_RIGHT, OV2_RES_RIGHT_ANCH, OV2_RES_PNP = 0, 1, 2, 3
 
 
@@ -216,6 +217,12 @@ SIGNATURES = {
     "ov2_detect_singlescale_batch_d": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(_i), _vp, _i, _vp, _i, _vp]),
     "ov2_detect_grid_fast_batch_d": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "ov2_corner_subpix": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _d]),
+    "ov2_brief_set_pattern": (_i, [_vp, _vp]),
+    "ov2_brief_get_pattern": (_i, [_vp, _vp]),
+    "ov2_describe_brief": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ov2_describe_brief_batch_d": (_i, [_vp, _vp, _i, _i, _i, C.c_size_t, _i, _vp, _i, _vp, _vp, _vp]),
+    "ov2_tracker_describe_brief": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "ov2_btracker_describe_brief": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "ov2_ba_default_options": (None, [C.POINTER(BAOptions)]),
     "ov2_structure_ba": (_i, [_vp, C.POINTER(SBAProblem), C.POINTER(BAOptions), C.POINTER(SBAResult)]),
     "ov2_xyz_ba_solve": (_i, [_vp, C.POINTER(XYZBAProblem), C.POINTER(BAOptions), C.POINTER(XYZBAResult)]),

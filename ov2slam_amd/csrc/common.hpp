@@ -62,6 +62,10 @@ struct ov2_ctx {
     int det_fast_tie = 1;                      // OV2_OPT_FAST_TIE: OV2_FAST_TIE_LIBSTDCXX (the reference as built with g++)
     hipStream_t det_aux_stream = nullptr; hipEvent_t det_ev[2] = {nullptr, nullptr};   // batched detectors: the passes alternate between the context's stream and this one
     int det_strip = -1;                        // OV2_OPT_DETECT_STRIP: -1 auto (batches), 0 one wavefront per cell, 1 the strip kernel
+    // BRIEF test pairs (ov2_brief_set_pattern): the caller's table when brief_custom, the built-in one otherwise; the 1 KB device copy
+    // is (re)uploaded on the stream before the next describe call after a change
+    int8_t brief_pat[256 * 4] = {};  bool brief_custom = false;
+    void *brief_pat_d = nullptr;  bool brief_pat_current = false;
     void *ba_det_pool = nullptr; size_t ba_det_bytes = 0;   // OV2_OPT_BA_DETERMINISTIC: per-work-group copies of H / F^T b / G (grow-only)
     // ov2_local_ba_batch: persistent host threads that prepare the problems of a batch (created with the first batch; ba.hip owns the type)
     void *ba_host_pool = nullptr; void (*ba_host_pool_free)(void *) = nullptr;
@@ -140,3 +144,10 @@ int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur,
                          int track_impl = OV2_TRACK_IMPL_WAVE,
                          int items = 1,    // items > 1 (trackb.hip): batch items [0, items) of both pyramids, n_max point slots and one n_dev entry per item
                          int lk_acc = OV2_LK_ACC_INT64);   // OV2_OPT_LK_ACC   // items > 1 (trackb.hip): batch items [0, items) of both pyramids, n_max point slots and one n_dev entry per item
+
+// BRIEF descriptors (brief.hip) of the points of items [0, n_items) of a device image batch (items item_stride bytes apart), from host
+// point arrays with cap slots per item (n_h[b] valid; NULL: n_h_all each) into host outputs of the same layout (slots past n_h[b]
+// untouched).  img_h != NULL: a host image of one item, uploaded to the context's scratch first (img_d is ignored).  ONE host
+// synchronisation; the kernel is enqueued on ctx->stream after everything already there (so after the frame's H2D of a tracker).
+int ov2_brief_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
+                    const float *xy_h, const int *n_h, int n_h_all, int cap, uint8_t *desc_h, uint8_t *valid_h);

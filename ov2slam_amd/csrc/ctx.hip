@@ -163,6 +163,7 @@ void ov2_ctx_destroy(ov2_ctx *ctx)
     if (ctx->stat_slots) (void)hipFree(ctx->stat_slots);
     if (ctx->ba_det_pool) (void)hipFree(ctx->ba_det_pool);
     if (ctx->ba_trace_d) (void)hipFree(ctx->ba_trace_d);
+    if (ctx->brief_pat_d) (void)hipFree(ctx->brief_pat_d);
     free(ctx->ba_trace_h);
     if (ctx->ba_host_pool && ctx->ba_host_pool_free) ctx->ba_host_pool_free(ctx->ba_host_pool);
     for (int i = 0; i < 2; i++) if (ctx->ba_ev[i]) (void)hipEventDestroy(ctx->ba_ev[i]);

@@ -295,6 +295,16 @@ uint8_t *ov2_tracker_image_buffer(ov2_tracker *t, int *stride)
 const ov2_pyr *ov2_tracker_cur_pyr(const ov2_tracker *t) { return t ? t->pyr[t->cur] : nullptr; }
 const ov2_pyr *ov2_tracker_prev_pyr(const ov2_tracker *t) { return t ? t->pyr[t->cur ^ 1] : nullptr; }
 int ov2_tracker_frames(const ov2_tracker *t) { return t ? t->frames : 0; }
+
+// describeBRIEF on the raw frame: dimg holds it from the frame's H2D (on this stream) until the next preprocess rewrites it
+int ov2_tracker_describe_brief(ov2_tracker *t, const float *xy_h, int n, uint8_t *desc_h, uint8_t *valid_h)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(n >= 0, OV2_EINVAL, "negative keypoint count");
+    if (n == 0) return OV2_OK;
+    OV2_REQUIRE(t->frames >= 1, OV2_EINVAL, "describeBRIEF needs a preprocessed frame");
+    return ov2_brief_run_h(t->ctx, nullptr, t->dimg, t->cfg.w, t->cfg.h, t->img_pitch, 0, 1, xy_h, nullptr, n, n, desc_h, valid_h);
+}
 int ov2_tracker_uses_graph(const ov2_tracker *t) { return t && t->graph_ok ? 1 : 0; }
 
 int ov2_tracker_preprocess(ov2_tracker *t, const uint8_t *img_h, int stride)

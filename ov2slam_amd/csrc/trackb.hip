@@ -66,6 +66,8 @@ struct ov2_btracker {
     float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
     // a step between ov2_btracker_track_frame_begin and _end: what _end needs to finish it
     struct Pending { bool on = false, tracked = false; int n_active = 0, use_prior = 0; const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n; } pend;
+    // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
+    int raw_which = -1, raw_n = 0;
 };
 
 static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -369,6 +371,7 @@ int ov2_btracker_upload(ov2_btracker *t, int which, int n_active)
     OV2_REQUIRE(t && which >= 0 && which < BT_IMG_SETS, OV2_EINVAL, "bad staging set");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    if (which == t->raw_which) t->raw_which = -1;                       // the current step's raw frames are overwritten
     OV2_HIP_CHECK(hipStreamWaitEvent(t->cs, t->used_ev[which], 0));      // the step that read dimg[which] last (no-op before the first record)
     OV2_HIP_CHECK(hipMemcpyAsync(t->dimg[which], t->himg[which], (size_t)n_active * t->img_bytes, hipMemcpyHostToDevice, t->cs));
     OV2_HIP_CHECK(hipEventRecord(t->up_ev[which], t->cs));
@@ -382,6 +385,7 @@ int ov2_btracker_prepare(ov2_btracker *t, int which, int n_active)
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(t->prepq.size() < 2, OV2_EINVAL, "two prepared frames are already waiting for their ov2_btracker_track_frame");
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    if (which == t->raw_which) t->raw_which = -1;
     // the frames: uploaded ahead (wait for the copy stream) or copied here, on the prep stream
     if (t->up_n[which] >= n_active) OV2_HIP_CHECK(hipStreamWaitEvent(t->ps, t->up_ev[which], 0));
     else {
@@ -435,6 +439,7 @@ int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t 
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     int which = 0;
     bool prepared = false;
+    t->raw_which = -1;                                                   // staging may rewrite any set
     int rc = stage_and_upload(t, n_active, img_h, stride, &which, &prepared);
     if (rc != OV2_OK) return rc;
     // preprocessImage: already under way on the prep stream (the context's stream waits for the pyramids' event), or in order here
@@ -447,7 +452,7 @@ int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t 
         if (rcp != OV2_OK) return rcp;
         return ov2_pyr_mark_ready(ctx, t->pyr[t->cur]);
     };
-    auto commit = [&]() { if (prepared) t->prepq.pop_front(); else t->pre_count++; t->frames++; };
+    auto commit = [&]() { if (prepared) t->prepq.pop_front(); else t->pre_count++; t->frames++; t->raw_which = which; t->raw_n = n_active; };
     t->cur = (int)(t->frames % BT_SETS);                                 // prev_pyr_.swap(cur_pyr_)  (:1169): frame k lives in set k % BT_SETS
     ov2_btracker::Pending &P = t->pend;
     P.n_active = n_active; P.use_prior = klt_use_prior; P.kps = kps_xy_h; P.has_prior = has_prior_h;
@@ -536,6 +541,20 @@ int ov2_btracker_detect_grid_fast(ov2_btracker *t, int n_active, int cell, const
 {
     OV2_REQUIRE(fast_th_inout != nullptr, OV2_EINVAL, "fast_th_inout == NULL");
     return detect_common(t, 0, n_active, cell, cur_xy_h, ncur_h, nullptr, nullptr, fast_th_inout, mask_mode, do_subpix, out_xy_h, out_cap, out_n_h);
+}
+
+int ov2_btracker_describe_brief(ov2_btracker *t, int n_active, const float *xy_h, const int *n_h, int cap, uint8_t *desc_h, uint8_t *valid_h)
+{
+    OV2_REQUIRE(t && n_h, OV2_EINVAL, "NULL argument");
+    OV2_REQUIRE(t->raw_which >= 0, OV2_EINVAL, "describeBRIEF: no current frames (no step yet, or their staging set was uploaded / prepared again)");
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->raw_n, OV2_EINVAL, "n_active exceeds the items of the current step");
+    const int which = t->raw_which;
+    const int rc = ov2_brief_run_h(t->ctx, nullptr, t->dimg[which], t->cfg.w, t->cfg.h, t->img_pitch, t->img_bytes, n_active, xy_h, n_h, 0, cap,
+                                   desc_h, valid_h);
+    if (rc != OV2_OK) return rc;
+    // a later upload of this set on the copy stream orders itself after the reads (the call has synchronised: this costs nothing)
+    OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], t->ctx->stream));
+    return OV2_OK;
 }
 
 const ov2_pyr *ov2_btracker_cur_pyr(const ov2_btracker *t) { return t ? t->pyr[t->cur] : nullptr; }

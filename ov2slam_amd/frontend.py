@@ -69,6 +69,26 @@ class Context:
                     self.set_option(ids[k], v)
         return _cm()
 
+    def set_brief_pattern(self, pairs):
+        """ov2_brief_set_pattern: the BRIEF test pairs of this context's describeBRIEF calls, (256, 4) int8 rows {ay, ax, by, bx}
+        with offsets in [-24, 24] (e.g. OpenCV's table, tests/golden/brief_pattern_opencv.npy); None restores the built-in table."""
+        if pairs is None:
+            L.check(self.lib.ov2_brief_set_pattern(self.h, None))
+            return
+        a = np.asarray(pairs)
+        if a.shape != (256, 4):
+            raise ValueError("a BRIEF pattern is 256 x 4 offsets, got shape %s" % (a.shape,))
+        if np.any(a < -24) or np.any(a > 24):      # (also checked by the library; int8 conversion would wrap first)
+            raise ValueError("BRIEF pattern offsets must lie in [-24, 24]")
+        a = np.ascontiguousarray(a, np.int8)
+        L.check(self.lib.ov2_brief_set_pattern(self.h, _ptr(a)))
+
+    def brief_pattern(self):
+        """-> (256, 4) int8: the test pairs describeBRIEF uses on this context"""
+        a = np.zeros((256, 4), np.int8)
+        L.check(self.lib.ov2_brief_get_pattern(self.h, _ptr(a)))
+        return a
+
     @property
     def stream(self):
         return self.lib.ov2_ctx_stream(self.h)
@@ -325,6 +345,15 @@ class VisualFrontEndTracker:
                                                  int(bool(klt_use_prior)), _ptr(out), _ptr(st), C.byref(p3p)))
         return out, st, bool(p3p.value)
 
+    def describeBRIEF(self, vpts):
+        """FeatureExtractor::describeBRIEF on the RAW current frame (the image of the last preprocessImage / trackFrame, before
+        CLAHE; already on the device) -> (desc (n, 32) uint8, valid (n,) bool)"""
+        pts = np.ascontiguousarray(vpts, dtype=np.float32).reshape(-1, 2)
+        n = len(pts)
+        desc = np.zeros((n, L.OV2_BRIEF_BYTES), np.uint8); valid = np.zeros(n, np.uint8)
+        L.check(self.lib.ov2_tracker_describe_brief(self.h_trk, _ptr(pts), n, _ptr(desc), _ptr(valid)))
+        return desc, valid.astype(bool)
+
     def setCalibration(self, calib):
         """calib: CameraCalibration.  From now on every kltTracking / trackFrame also computes Frame::computeKeypoint (undistorted
         pixel + bearing vector) of its output positions in the same enqueue: lastKeypoints().  Call right after construction."""
@@ -452,6 +481,23 @@ class LockstepTracker:
         bv = np.empty((n, 3), np.float64) if want_bv else None
         L.check(self.lib.ov2_btracker_last_keypoints(self.h_trk, int(item), int(n), _ptr(unpx), _ptr(bv) if want_bv else None))
         return unpx, bv
+
+    def describeBRIEF(self, n_active, pts, n):
+        """describeBRIEF on the raw frames of the current step, items [0, n_active).  pts: (>= n_active, cap, 2) float32; n: counts
+        (len n_active).  -> (desc (n_active, cap, 32) uint8, valid (n_active, cap) bool; slots past n[b] are zero).  Call it before
+        the staging set of those frames is uploaded or prepared again."""
+        na = int(n_active)
+        p = np.asarray(pts, np.float32)
+        if p.ndim != 3 or p.shape[0] < na or p.shape[2] != 2:
+            raise ValueError("pts must be (>= n_active, cap, 2)")
+        cap = p.shape[1]
+        p = np.ascontiguousarray(p[:na])
+        nn = np.ascontiguousarray(n, np.int32)
+        if len(nn) != na:
+            raise ValueError("one point count per active item")
+        desc = np.zeros((na, cap, L.OV2_BRIEF_BYTES), np.uint8); valid = np.zeros((na, cap), np.uint8)
+        L.check(self.lib.ov2_btracker_describe_brief(self.h_trk, na, _ptr(p), _ptr(nn), cap, _ptr(desc), _ptr(valid)))
+        return desc, valid.astype(bool)
 
     def detectSingleScale(self, n_active, ncellsize, cur, ncur, roi, quality, subpix=True):
         """MapManager::extractKeypoints of items [0, n_active) on their current frames.  cur: (batch, n_max, 2); ncur: counts;
@@ -595,6 +641,26 @@ class FeatureExtractor:
                                                 C.byref(th), self.mask_mode, int(bool(subpix)), _ptr(out), C.byref(n)))
         self.nfast_th_ = th.value
         return out[:n.value].copy()
+
+    def describeBRIEF(self, im, vpts):
+        """src/feature_extractor.cpp:224-285 (BriefDescriptorExtractor, 32 bytes) with the context's pattern (Context.set_brief_pattern).
+        im: (h, w) uint8, any row stride.  -> (desc (n, 32) uint8, valid (n,) bool): the reference's empty cv::Mat of a point too
+        close to the border is valid False (its row is zero)."""
+        im = np.asarray(im)
+        if im.dtype != np.uint8 or im.ndim != 2 or im.strides[1] != 1 or im.strides[0] < im.shape[1]:
+            im = np.ascontiguousarray(im, dtype=np.uint8)
+        h, w = im.shape
+        pts = np.ascontiguousarray(vpts, dtype=np.float32).reshape(-1, 2)
+        n = len(pts)
+        desc = np.zeros((n, L.OV2_BRIEF_BYTES), np.uint8); valid = np.zeros(n, np.uint8)
+        L.check(self.lib.ov2_describe_brief(self.ctx.h, _ptr(im), w, h, im.strides[0], _ptr(pts), n, _ptr(desc), _ptr(valid)))
+        return desc, valid.astype(bool)
+
+    @staticmethod
+    def describeBRIEFBatch(ctx, img_d, w, h, pitch, item_stride, n_items, xy_d, cap, n_d, desc_d, valid_d):
+        """ov2_describe_brief_batch_d: every argument a device address (int) or size; n_d may be 0 (all cap slots)."""
+        L.check(ctx.lib.ov2_describe_brief_batch_d(ctx.h, C.c_void_p(img_d), int(w), int(h), int(pitch), int(item_stride), int(n_items),
+                                                   C.c_void_p(xy_d), int(cap), C.c_void_p(n_d or None), C.c_void_p(desc_d), C.c_void_p(valid_d)))
 
     def cornerSubPix(self, im, pts, half_win=3, max_iter=30, eps=0.01):
         im = np.ascontiguousarray(im, dtype=np.uint8)

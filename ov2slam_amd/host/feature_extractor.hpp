@@ -3,6 +3,7 @@
 // Holds the same adaptive state (nfast_th_, dmaxquality_).  Errors degrade to an empty vector, like
 // the reference's empty-image path (:291-294, :446-449).
 #pragma once
+#include <array>
 #include "ov2_types.hpp"
 
 namespace ov2 {
@@ -88,6 +89,32 @@ public:
         vout_n.assign(vfast_th.size(), 0);
         if (vfast_th.empty()) return OV2_EINVAL;
         return ov2_detect_grid_fast_batch_d(ctx.get(), pyr, ncellsize, cur_xy_d, cur_cap, ncur_d, vfast_th.data(), mask_mode, 1, out_xy_d, out_cap, vout_n.data());
+    }
+
+    // reference: std::vector<cv::Mat> describeBRIEF(const cv::Mat &im, const std::vector<cv::Point2f> &vpts)  (:224-285): one 1 x 32
+    // CV_8U Mat per point, an EMPTY Mat for a point too close to the border.  Here: one 32-byte array per point and vvalid[i] = 0
+    // where the reference's Mat is empty (its bytes are 0).  The pattern is the context's (ov2_brief_set_pattern; the built-in one
+    // is NOT OpenCV's -- INTEGRATION.md).  Errors give empty vectors.
+    typedef std::array<uint8_t, OV2_BRIEF_BYTES> BriefDescriptor;
+    std::vector<BriefDescriptor> describeBRIEF(Context &ctx, const Image8 &im, const std::vector<Point2f> &vpts, std::vector<uint8_t> &vvalid)
+    {
+        std::vector<BriefDescriptor> vdesc(vpts.size());
+        vvalid.assign(vpts.size(), 0);
+        if (vpts.empty()) return vdesc;
+        const int rc = im.empty() ? OV2_EINVAL : ov2_describe_brief(ctx.get(), im.data, im.cols, im.rows, im.step, &vpts[0].x, (int)vpts.size(),
+                                                                     vdesc[0].data(), vvalid.data());
+        if (rc != OV2_OK) { vdesc.clear(); vvalid.clear(); }
+        return vdesc;
+    }
+    // the same on the RAW current frame of a FrameTracker (FrameTracker::get(): imraw, already on the device -- no upload); valid
+    // until the tracker's next frame
+    std::vector<BriefDescriptor> describeBRIEF(ov2_tracker *trk, const std::vector<Point2f> &vpts, std::vector<uint8_t> &vvalid)
+    {
+        std::vector<BriefDescriptor> vdesc(vpts.size());
+        vvalid.assign(vpts.size(), 0);
+        if (vpts.empty()) return vdesc;
+        if (ov2_tracker_describe_brief(trk, &vpts[0].x, (int)vpts.size(), vdesc[0].data(), vvalid.data()) != OV2_OK) { vdesc.clear(); vvalid.clear(); }
+        return vdesc;
     }
 
     size_t nmaxpts_, nmaxdist_;

@@ -102,6 +102,8 @@ public:
     // cur_pyr_ / prev_pyr_ for createKeyframe, stereo matching and the device-resident detectors (valid until the next frame)
     const ov2_pyr *curPyr() const { return ov2_tracker_cur_pyr(t_); }
     const ov2_pyr *prevPyr() const { return ov2_tracker_prev_pyr(t_); }
+    // the library object, e.g. for FeatureExtractor::describeBRIEF on the raw current frame
+    ov2_tracker *get() const { return t_; }
 
     // why the last kltTracking / trackFrame tracked nothing (OV2_OK when it did not fail)
     int lastError() const { return last_rc_; }
