@@ -415,6 +415,56 @@ int ov2_detect_grid_fast_batch_d(ov2_ctx *ctx, const ov2_pyr *pyr, int cell, con
 int ov2_corner_subpix(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stride,
                       float *xy_inout_h, int n, int half_win, int max_iter, double eps);
 
+/* ---- GFTT (Shi-Tomasi) detection --------------------------------------
+ * FeatureExtractor::detectGFTT (src/feature_extractor.cpp:104-221, the use_shi_tomasi branch of MapManager::extractKeypoints,
+ * src/map_manager.cpp:312-314) with its setMask helper (:575-584).  The four members it reads are passed explicitly:
+ * ov2_gftt_params_init derives nmindist = nmaxdist / 2 (truncated) and dminquality = dmaxquality / 2 like the constructor (:79-83).
+ *   1. ncur >= nmaxpts: no points.  nb2detect = nbmax != -1 ? nbmax : nmaxpts - ncur.
+ *   2. pass 1: mask = roi (all pixels when NULL), zeroed by a filled cv::circle of radius nmaxdist at cvRound of every current
+ *      keypoint; goodFeaturesToTrack(maxCorners nb2detect, quality dminquality, minDistance nmaxdist, blockSize 3, gradSize 3):
+ *        eig  = cornerMinEigenVal(im, 3, 3) over the whole image, REFLECT_101 (no blur; Sobel dy order: OV2_OPT_SOBEL_DY_ORDER)
+ *        thr  = (float)(maxVal * quality), maxVal the maximum of eig where the mask is non-zero (0 when there is no such pixel)
+ *        candidates: interior pixels (1 <= x <= w-2, 1 <= y <= h-2) with t != 0, t == 3x3 max of t and mask != 0, where
+ *              t = eig > thr ? eig : 0
+ *        order: value descending; EQUAL values: the later pixel (higher y*w + x) first -- OpenCV 4.x greaterThanPtr.  OpenCV 3.x
+ *              compares values only under an unstable std::sort; that order is not reproduced.
+ *        greedy: a candidate is dropped when an accepted point lies at dx^2 + dy^2 < minDistance^2; stop at maxCorners.
+ *      then cornerSubPix(3x3, 30 iterations, eps 0.01) when do_subpix.
+ *   3. n1 >= 0.66 * nb2detect or nb2detect < 20: done.  Otherwise pass 2 with mask = roi minus discs of radius nmindist at the
+ *      current keypoints AND the (refined) pass-1 points, quality dmaxquality, minDistance nmindist, maxCorners nb2detect - n1;
+ *      its points follow the pass-1 points.
+ * The eig map is shared by both passes.  The arithmetic is restated from the public OpenCV source and NOT pinned against an OpenCV
+ * binary (the status of detectSingleScale's response); IPP / SIMD builds of OpenCV may round differently.
+ * Arguments: nbmax -1 or >= 1 (0, which OpenCV reads as "no limit", and < -1 -> OV2_EINVAL; the reference never passes them);
+ * out_cap >= nb2detect (OV2_EINVAL), nb2detect <= 4096 and nmaxdist <= 63 (OV2_EUNSUPPORTED); images at least 16 x 16
+ * (OV2_EUNSUPPORTED); an empty image (NULL, w or h <= 0) gives 0 points.  One host synchronisation per call.
+ * Scratch: the context's grow-only device buffer, 21 B per pixel and item + the output lists (7.6 MB for 752 x 480); batches run in
+ * chunks of at most 256 MB of it (at least one item).                                                                         */
+typedef struct { int nmaxpts, nmaxdist, nmindist; double dminquality, dmaxquality; } ov2_gftt_params;
+int ov2_gftt_params_init(int nmaxpts, int nmaxdist, double dmaxquality, ov2_gftt_params *out);
+/* host image; roi_h: NULL or a w x h byte mask (rows roi_stride bytes apart, non-zero = allowed); cur_xy_h: ncur points */
+int ov2_detect_gftt(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stride, const uint8_t *roi_h, int roi_stride,
+                    const ov2_gftt_params *params, const float *cur_xy_h, int ncur, int nbmax, int do_subpix,
+                    float *out_xy_h, int out_cap, int *out_n);
+/* level 0 of batch item `item` of a device pyramid (the tracker's current CLAHE'd frame): no image upload */
+int ov2_detect_gftt_d(ov2_ctx *ctx, const ov2_pyr *pyr, int item, const uint8_t *roi_h, int roi_stride,
+                      const ov2_gftt_params *params, const float *cur_xy_h, int ncur, int nbmax, int do_subpix,
+                      float *out_xy_h, int out_cap, int *out_n);
+/* every item of the pyramid: roi_d device mask shared by all items (NULL: none); cur_xy_d cur_cap points per item, ncur_d[b] valid
+ * (NULL: none); nbmax_h host, one per item; out_xy_d out_cap points per item, out_cap >= max over items of (nbmax, or nmaxpts
+ * where nbmax is -1); out_n_h host counts.  Identical per item to the single-image forms.                                       */
+int ov2_detect_gftt_batch_d(ov2_ctx *ctx, const ov2_pyr *pyr, const uint8_t *roi_d, int roi_stride, const ov2_gftt_params *params,
+                            const float *cur_xy_d, int cur_cap, const int *ncur_d, const int *nbmax_h, int do_subpix,
+                            float *out_xy_d, int out_cap, int *out_n_h);
+/* lock-step form on the current frames of items [0, n_active) with host buffers (layout of ov2_btracker_detect_singlescale:
+ * cur_xy_h n_max slots per item, out_xy_h out_cap slots per item); roi_h as in ov2_detect_gftt, shared by all items */
+int ov2_btracker_detect_gftt(ov2_btracker *t, int n_active, const uint8_t *roi_h, int roi_stride, const ov2_gftt_params *params,
+                             const float *cur_xy_h, const int *ncur_h, const int *nbmax_h, int do_subpix,
+                             float *out_xy_h, int out_cap, int *out_n_h);
+/* FeatureExtractor::setMask on a host mask: a filled cv::circle of radius dist (value 0) at cvRound(x), cvRound(y) of each point
+ * (the pixels the kernels paint) */
+int ov2_set_mask(uint8_t *mask, int w, int h, int stride, const float *xy, int n, int dist);
+
 /* ---- BRIEF descriptors ----------------------------------------------
  * FeatureExtractor::describeBRIEF (src/feature_extractor.cpp:224-285): cv::xfeatures2d::BriefDescriptorExtractor with its defaults
  * (32 bytes, use_orientation = false), called twice per keyframe from MapManager::extractKeypoints on the RAW left image.  Per point:

@@ -130,6 +130,12 @@ class XYZBAProblem(C.Structure):
     ]
 
 
+class GfttParams(C.Structure):
+    """ov2_gftt_params: FeatureExtractor's nmaxpts_, nmaxdist_, nmindist_, dminquality_, dmaxquality_"""
+    _fields_ = [("nmaxpts", C.c_int), ("nmaxdist", C.c_int), ("nmindist", C.c_int),
+                ("dminquality", C.c_double), ("dmaxquality", C.c_double)]
+
+
 class XYZBAResult(C.Structure):
     _fields_ = [
         ("poses_out", C.POINTER(C.c_double)), ("xyz_out", C.POINTER(C.c_double)), ("chi2_last_eval", C.POINTER(C.c_double)),
@@ -217,6 +223,12 @@ SIGNATURES = {
     "ov2_detect_singlescale_batch_d": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(_i), _vp, _i, _vp, _i, _vp]),
     "ov2_detect_grid_fast_batch_d": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "ov2_corner_subpix": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _d]),
+    "ov2_gftt_params_init": (_i, [_i, _i, _d, _vp]),
+    "ov2_detect_gftt": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, C.POINTER(_i)]),
+    "ov2_detect_gftt_d": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, C.POINTER(_i)]),
+    "ov2_detect_gftt_batch_d": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "ov2_btracker_detect_gftt": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "ov2_set_mask": (_i, [_vp, _i, _i, _i, _vp, _i, _i]),
     "ov2_brief_set_pattern": (_i, [_vp, _vp]),
     "ov2_brief_get_pattern": (_i, [_vp, _vp]),
     "ov2_describe_brief": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),

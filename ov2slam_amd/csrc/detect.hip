@@ -1286,9 +1286,9 @@ __global__ __launch_bounds__(64) void k_corner_subpix(SubpixParams P, const uint
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
-static int launch_subpix(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int stride, float2 *xy_d, int n,
-                         int half_win, int max_iter, double eps, const int *n_dev = nullptr,
-                         int items = 1, long long img_item_stride = 0, int xy_item_stride = 0, int ndev_item_stride = 0)
+int launch_subpix(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int stride, float2 *xy_d, int n,
+                  int half_win, int max_iter, double eps, const int *n_dev,
+                  int items, long long img_item_stride, int xy_item_stride, int ndev_item_stride)
 {
     if (n <= 0) return OV2_OK;
     OV2_REQUIRE(half_win >= 1 && half_win <= SP_MAX_HALF, OV2_EUNSUPPORTED, "cornerSubPix half window must be in [1,5]");

@@ -64,6 +64,7 @@ struct ov2_btracker {
     // keyframe detection: device mirrors of the items' current keypoints and of the detector's output, pinned staging
     uint8_t *d_det = nullptr, *h_det = nullptr; size_t det_in_bytes = 0;
     float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
+    uint8_t *d_roi = nullptr;                     // detectGFTT: device copy of the caller's roi mask (w x h, allocated with the first one)
     // a step between ov2_btracker_track_frame_begin and _end: what _end needs to finish it
     struct Pending { bool on = false, tracked = false; int n_active = 0, use_prior = 0; const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n; } pend;
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
@@ -96,6 +97,7 @@ static void btracker_free(ov2_btracker *t)
     if (t->d_det) (void)hipFree(t->d_det);
     if (t->h_out) (void)hipHostFree(t->h_out);
     if (t->d_out) (void)hipFree(t->d_out);
+    if (t->d_roi) (void)hipFree(t->d_roi);
     delete t;
 }
 
@@ -248,13 +250,16 @@ static int apply_p3p_rule(ov2_btracker *t, int b, const float *kps, const uint8_
     return OV2_OK;
 }
 
+// mode 0: detectGridFAST, 1: detectSingleScale, 2: detectGFTT (roi_h / roi_stride / gp / nbmax_h; cell unused)
 static int detect_common(ov2_btracker *t, int mode, int n_active, int cell, const float *cur_xy_h, const int *ncur_h, const int roi[4],
-                         double *quality_inout, int *fast_th_inout, int mask_mode, int do_subpix, float *out_xy_h, int out_cap, int *out_n_h)
+                         double *quality_inout, int *fast_th_inout, int mask_mode, int do_subpix, float *out_xy_h, int out_cap, int *out_n_h,
+                         const uint8_t *roi_h = nullptr, int roi_stride = 0, const ov2_gftt_params *gp = nullptr, const int *nbmax_h = nullptr)
 {
     OV2_REQUIRE(t && out_xy_h && out_n_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(t->frames > 0, OV2_EINVAL, "no frame has been preprocessed yet");
-    OV2_REQUIRE(cell >= 8 && out_cap >= (mode == 0 ? 1 : 2) * (t->cfg.w / cell) * (t->cfg.h / cell), OV2_EINVAL, "out_cap too small for this cell size");
+    OV2_REQUIRE(mode == 2 || (cell >= 8 && out_cap >= (mode == 0 ? 1 : 2) * (t->cfg.w / cell) * (t->cfg.h / cell)), OV2_EINVAL, "out_cap too small for this cell size");
+    OV2_REQUIRE(mode != 2 || out_cap >= 1, OV2_EINVAL, "out_cap < 1");
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t nm = (size_t)t->cfg.n_max, o_cur = up256(4 * (size_t)t->batch);
@@ -278,8 +283,16 @@ static int detect_common(ov2_btracker *t, int mode, int n_active, int cell, cons
     const ov2_pyr q = prefix_of(t->pyr[t->cur], n_active);
     const float *cur_d = (const float *)(t->d_det + o_cur);
     const int *ncur_d = (const int *)t->d_det;
+    if (mode == 2 && roi_h) {
+        OV2_REQUIRE(roi_stride >= t->cfg.w, OV2_EINVAL, "roi stride < width");
+        if (!t->d_roi) OV2_HIP_CHECK(hipMalloc((void **)&t->d_roi, (size_t)t->cfg.w * t->cfg.h));
+        OV2_HIP_CHECK(hipMemcpy2DAsync(t->d_roi, (size_t)t->cfg.w, roi_h, (size_t)roi_stride, (size_t)t->cfg.w, (size_t)t->cfg.h,
+                                       hipMemcpyHostToDevice, ctx->stream));
+    }
     int rc;
-    if (mode == 0) rc = ov2_detect_grid_fast_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, fast_th_inout, mask_mode, do_subpix, t->d_out, t->out_cap, out_n_h);
+    if (mode == 2) rc = ov2_detect_gftt_batch_d(ctx, &q, roi_h ? t->d_roi : nullptr, t->cfg.w, gp, cur_d, (int)nm, ncur_d, nbmax_h, do_subpix,
+                                                t->d_out, t->out_cap, out_n_h);
+    else if (mode == 0) rc = ov2_detect_grid_fast_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, fast_th_inout, mask_mode, do_subpix, t->d_out, t->out_cap, out_n_h);
     else rc = ov2_detect_singlescale_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, roi, quality_inout, do_subpix, t->d_out, t->out_cap, out_n_h);
     if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipMemcpyAsync(t->h_out, t->d_out, 8 * (size_t)t->out_cap * n_active, hipMemcpyDeviceToHost, ctx->stream));
@@ -541,6 +554,18 @@ int ov2_btracker_detect_grid_fast(ov2_btracker *t, int n_active, int cell, const
 {
     OV2_REQUIRE(fast_th_inout != nullptr, OV2_EINVAL, "fast_th_inout == NULL");
     return detect_common(t, 0, n_active, cell, cur_xy_h, ncur_h, nullptr, nullptr, fast_th_inout, mask_mode, do_subpix, out_xy_h, out_cap, out_n_h);
+}
+
+int ov2_btracker_detect_gftt(ov2_btracker *t, int n_active, const uint8_t *roi_h, int roi_stride, const ov2_gftt_params *params,
+                             const float *cur_xy_h, const int *ncur_h, const int *nbmax_h, int do_subpix,
+                             float *out_xy_h, int out_cap, int *out_n_h)
+{
+    OV2_REQUIRE(params != nullptr && nbmax_h != nullptr, OV2_EINVAL, "params / nbmax_h == NULL");
+    OV2_REQUIRE(t && n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
+    for (int b = 0; b < n_active; b++)                 // the host list has out_cap slots per item, whatever the mirrors hold
+        OV2_REQUIRE(out_cap >= (nbmax_h[b] == -1 ? params->nmaxpts : nbmax_h[b]), OV2_EINVAL, "out_cap below nb2detect");
+    return detect_common(t, 2, n_active, 0, cur_xy_h, ncur_h, nullptr, nullptr, nullptr, 0, do_subpix, out_xy_h, out_cap, out_n_h,
+                         roi_h, roi_stride, params, nbmax_h);
 }
 
 int ov2_btracker_describe_brief(ov2_btracker *t, int n_active, const float *xy_h, const int *n_h, int cap, uint8_t *desc_h, uint8_t *valid_h)

@@ -513,6 +513,20 @@ class LockstepTracker:
                                                          1 if subpix else 0, _ptr(out), cap, _ptr(on)))
         return [out[b, :on[b]].copy() for b in range(n_active)]
 
+    def detectGFTT(self, n_active, params, cur, ncur, nbmax, roi=None, subpix=True):
+        """detectGFTT of items [0, n_active) on their current frames.  params: L.GfttParams (FeatureExtractor.gftt_params());
+        cur: (batch, n_max, 2); ncur / nbmax: one per active item; roi None or an (h, w) uint8 mask shared by the items.
+        -> list of (k, 2) arrays"""
+        cur = np.ascontiguousarray(cur, np.float32).reshape(self.batch, self.n_max, 2)
+        nc = np.zeros(self.batch, np.int32); nc[:n_active] = np.asarray(ncur, np.int32)[:n_active]
+        nb = np.ascontiguousarray(nbmax, np.int32)
+        cap = max([1] + [int(v) if v != -1 else params.nmaxpts for v in nb[:n_active]])
+        r, rp, rs = _roi_arg(roi, self.w, self.h)
+        out = np.zeros((n_active, cap, 2), np.float32); on = np.zeros(n_active, np.int32)
+        L.check(self.lib.ov2_btracker_detect_gftt(self.h_trk, int(n_active), rp, rs, C.byref(params), _ptr(cur), _ptr(nc), _ptr(nb),
+                                                  1 if subpix else 0, _ptr(out), cap, _ptr(on)))
+        return [out[b, :on[b]].copy() for b in range(n_active)]
+
     def detectGridFAST(self, n_active, ncellsize, cur, ncur, fast_th, mask_mode=L.OV2_MASK_AS_EXECUTED, subpix=True):
         cap = max(1, (self.w // ncellsize) * (self.h // ncellsize))
         cur = np.ascontiguousarray(cur, np.float32).reshape(self.batch, self.n_max, 2)
@@ -550,15 +564,106 @@ class LockstepTracker:
             pass
 
 
+def _gftt_params(nmaxpts, nmaxdist, nmindist, dminquality, dmaxquality):
+    return L.GfttParams(int(nmaxpts), int(nmaxdist), int(nmindist), float(dminquality), float(dmaxquality))
+
+
+def _roi_arg(roi, w, h):
+    """roi: None or an (h, w) uint8 mask (any row stride) -> (array or None, pointer, stride)"""
+    if roi is None:
+        return None, None, 0
+    r = np.asarray(roi)
+    if r.dtype != np.uint8 or r.ndim != 2 or r.strides[1] != 1 or r.strides[0] < r.shape[1]:
+        r = np.ascontiguousarray(r, dtype=np.uint8)
+    if r.shape != (h, w):
+        raise ValueError("roi must be an (h, w) uint8 mask")
+    return r, _ptr(r), r.strides[0]
+
+
+def set_mask(mask, vpts, dist):
+    """FeatureExtractor::setMask (src/feature_extractor.cpp:575-584) in place on an (h, w) uint8 mask: a filled disc of radius dist
+    (value 0) at cvRound of every point."""
+    if mask.dtype != np.uint8 or mask.ndim != 2 or mask.strides[1] != 1:
+        raise ValueError("mask must be a 2-D uint8 array with unit column stride")
+    pts = np.ascontiguousarray(vpts, dtype=np.float32).reshape(-1, 2)
+    h, w = mask.shape
+    L.check(L.load().ov2_set_mask(mask.ctypes.data_as(C.c_void_p), w, h, mask.strides[0], _ptr(pts), len(pts), int(dist)))
+    return mask
+
+
 class FeatureExtractor:
     """Mirror of /root/reference/include/feature_extractor.hpp:30-54: holds the
-    adaptive thresholds nfast_th_ and dmaxquality_ that the two grid detectors update."""
+    adaptive thresholds nfast_th_ and dmaxquality_ that the two grid detectors update, and detectGFTT's
+    nmaxpts_ / nmaxdist_ / nmindist_ / dminquality_ (derived like the constructor, :79-83, unless given)."""
 
-    def __init__(self, ctx, nfast_th=10, dmaxquality=0.001, mask_mode=L.OV2_MASK_AS_EXECUTED):
+    def __init__(self, ctx, nfast_th=10, dmaxquality=0.001, mask_mode=L.OV2_MASK_AS_EXECUTED, nmaxpts=300, nmaxdist=35,
+                 nmindist=None, dminquality=None):
         self.ctx, self.lib = ctx, ctx.lib
         self.nfast_th_ = int(nfast_th)
         self.dmaxquality_ = float(dmaxquality)
         self.mask_mode = mask_mode
+        self.nmaxpts_ = int(nmaxpts)
+        self.nmaxdist_ = int(nmaxdist)
+        self.nmindist_ = int(nmaxdist) // 2 if nmindist is None else int(nmindist)
+        self.dminquality_ = float(dmaxquality) / 2. if dminquality is None else float(dminquality)
+
+    def gftt_params(self):
+        return _gftt_params(self.nmaxpts_, self.nmaxdist_, self.nmindist_, self.dminquality_, self.dmaxquality_)
+
+    def _gftt_cap(self, ncur, nbmax):
+        return max(1, int(nbmax) if nbmax != -1 else self.nmaxpts_ - ncur)
+
+    def detectGFTT(self, im, vcurkps, roi=None, nbmax=-1, subpix=True):
+        """src/feature_extractor.cpp:104-221 on a host image (any row stride).  roi: None or an (h, w) uint8 mask."""
+        im = np.asarray(im)
+        if im.dtype != np.uint8 or im.ndim != 2 or im.strides[1] != 1 or im.strides[0] < im.shape[1]:
+            im = np.ascontiguousarray(im, dtype=np.uint8)
+        if im.size == 0:
+            return np.zeros((0, 2), np.float32)
+        h, w = im.shape
+        cur = np.ascontiguousarray(vcurkps, dtype=np.float32).reshape(-1, 2)
+        r, rp, rs = _roi_arg(roi, w, h)
+        cap = self._gftt_cap(len(cur), nbmax)
+        out = np.zeros((cap, 2), np.float32)
+        n = C.c_int(0)
+        p = self.gftt_params()
+        L.check(self.lib.ov2_detect_gftt(self.ctx.h, _ptr(im), w, h, im.strides[0], rp, rs, C.byref(p), _ptr(cur), len(cur),
+                                         int(nbmax), int(bool(subpix)), _ptr(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def detectGFTTPyr(self, pyr, vcurkps, roi=None, nbmax=-1, subpix=True, item=0):
+        """detectGFTT on level 0 of a device-resident pyramid (the CLAHE'd cur_img_ of the keyframe) -- no image upload."""
+        cur = np.ascontiguousarray(vcurkps, dtype=np.float32).reshape(-1, 2)
+        w, h = pyr.level_size(0)
+        r, rp, rs = _roi_arg(roi, w, h)
+        cap = self._gftt_cap(len(cur), nbmax)
+        out = np.zeros((cap, 2), np.float32)
+        n = C.c_int(0)
+        p = self.gftt_params()
+        L.check(self.lib.ov2_detect_gftt_d(self.ctx.h, pyr.h_pyr, int(item), rp, rs, C.byref(p), _ptr(cur), len(cur),
+                                           int(nbmax), int(bool(subpix)), _ptr(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    @staticmethod
+    def detectGFTTBatch(ctx, pyr, roi_d, roi_stride, params, cur_xy_d, cur_cap, ncur_d, nbmax, out_xy_d, out_cap, subpix=True):
+        """ov2_detect_gftt_batch_d: detectGFTT on EVERY batch item of `pyr`.  roi_d / cur_xy_d / ncur_d / out_xy_d are device
+        addresses (ints; 0 = NULL for the first three); params an L.GfttParams (FeatureExtractor.gftt_params()); nbmax one int
+        per item.  Returns the per-item point counts (int32 array)."""
+        nb = np.ascontiguousarray(nbmax, np.int32)
+        if len(nb) != pyr.batch:
+            raise ValueError("one nbmax per batch item")
+        n = np.zeros(pyr.batch, np.int32)
+        L.check(ctx.lib.ov2_detect_gftt_batch_d(ctx.h, pyr.h_pyr, C.c_void_p(roi_d or None), int(roi_stride), C.byref(params),
+                                                C.c_void_p(cur_xy_d or None), int(cur_cap), C.c_void_p(ncur_d or None), _ptr(nb),
+                                                1 if subpix else 0, C.c_void_p(out_xy_d), int(out_cap), n.ctypes.data_as(C.c_void_p)))
+        return n
+
+    def setMask(self, im, vpts, dist, mask=None):
+        """src/feature_extractor.cpp:575-584: mask None -> a new all-255 (h, w) mask; returns the mask."""
+        if mask is None:
+            h, w = np.asarray(im).shape[:2]
+            mask = np.full((h, w), 255, np.uint8)
+        return set_mask(mask, vpts, dist)
 
     def detectGridFAST(self, im, ncellsize, vcurkps, roi=None, subpix=True):
         """src/feature_extractor.cpp:443-570 (roi is unused there too)."""

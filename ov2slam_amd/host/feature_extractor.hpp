@@ -1,7 +1,7 @@
 // feature_extractor.hpp -- C++ adapter with the signatures of the reference's FeatureExtractor grid
 // detectors (/root/reference/include/feature_extractor.hpp:40-46, src/feature_extractor.cpp:288-570).
-// Holds the same adaptive state (nfast_th_, dmaxquality_).  Errors degrade to an empty vector, like
-// the reference's empty-image path (:291-294, :446-449).
+// Holds the same adaptive state (nfast_th_, dmaxquality_) and detectGFTT's nmindist_ / dminquality_ (derived like the reference's
+// constructor, :79-83).  Errors degrade to an empty vector, like the reference's empty-image path (:291-294, :446-449).
 #pragma once
 #include <array>
 #include "ov2_types.hpp"
@@ -12,7 +12,53 @@ class FeatureExtractor {
 public:
     // reference: FeatureExtractor(size_t nmaxpts, size_t nmaxdist, double dmaxquality, int nfast_th)
     FeatureExtractor(size_t nmaxpts, size_t nmaxdist, double dmaxquality, int nfast_th, int mask_mode = OV2_MASK_AS_EXECUTED)
-        : nmaxpts_(nmaxpts), nmaxdist_(nmaxdist), dmaxquality_(dmaxquality), nfast_th_(nfast_th), mask_mode_(mask_mode) {}
+        : nmaxpts_(nmaxpts), nmaxdist_(nmaxdist), dmaxquality_(dmaxquality), nfast_th_(nfast_th), mask_mode_(mask_mode)
+    {
+        nmindist_ = nmaxdist / 2;          // size_t = double: truncated (:81)
+        dminquality_ = dmaxquality / 2.;   // :82
+    }
+    // reference: FeatureExtractor() {} (its members stay uninitialised there; zero here)
+    FeatureExtractor() : FeatureExtractor(0, 0, 0.0, 0) {}
+
+    // the members detectGFTT reads, as the C ABI takes them
+    ov2_gftt_params gfttParams() const
+    {
+        ov2_gftt_params p;
+        p.nmaxpts = (int)nmaxpts_; p.nmaxdist = (int)nmaxdist_; p.nmindist = (int)nmindist_;
+        p.dminquality = dminquality_; p.dmaxquality = dmaxquality_;
+        return p;
+    }
+
+    // reference: std::vector<cv::Point2f> detectGFTT(const cv::Mat &im, const std::vector<cv::Point2f> &vcurkps,
+    //                const cv::Mat &roi, int nbmax = -1) const   (:104-221; roi empty = no roi)
+    std::vector<Point2f> detectGFTT(Context &ctx, const Image8 &im, const std::vector<Point2f> &vcurkps, const Image8 &roi,
+                                    int nbmax = -1) const
+    {
+        const size_t cap = gfttCapacity(vcurkps.size(), nbmax);
+        if (im.empty() || cap == 0) return std::vector<Point2f>();
+        std::vector<Point2f> out(cap);
+        int n = 0;
+        const ov2_gftt_params p = gfttParams();
+        const int rc = ov2_detect_gftt(ctx.get(), im.data, im.cols, im.rows, im.step, roi.empty() ? nullptr : roi.data, roi.step, &p,
+                                       vcurkps.empty() ? nullptr : &vcurkps[0].x, (int)vcurkps.size(), nbmax, 1, &out[0].x, (int)cap, &n);
+        out.resize(rc == OV2_OK ? (size_t)n : 0);
+        return out;
+    }
+    // the same on level 0 of a device-resident pyramid (FrameTracker::curPyr(): the CLAHE'd cur_img_ of the keyframe,
+    // src/map_manager.cpp:312-314) -- no image upload
+    std::vector<Point2f> detectGFTT(Context &ctx, const ov2_pyr *pyr, const std::vector<Point2f> &vcurkps, const Image8 &roi,
+                                    int nbmax = -1) const
+    {
+        const size_t cap = gfttCapacity(vcurkps.size(), nbmax);
+        if (!pyr || cap == 0) return std::vector<Point2f>();
+        std::vector<Point2f> out(cap);
+        int n = 0;
+        const ov2_gftt_params p = gfttParams();
+        const int rc = ov2_detect_gftt_d(ctx.get(), pyr, 0, roi.empty() ? nullptr : roi.data, roi.step, &p,
+                                         vcurkps.empty() ? nullptr : &vcurkps[0].x, (int)vcurkps.size(), nbmax, 1, &out[0].x, (int)cap, &n);
+        out.resize(rc == OV2_OK ? (size_t)n : 0);
+        return out;
+    }
 
     // reference: std::vector<cv::Point2f> detectGridFAST(const cv::Mat &im, const int ncellsize,
     //                const std::vector<cv::Point2f> &vcurkps, const cv::Rect &roi)
@@ -121,6 +167,16 @@ public:
     double dmaxquality_;       // feature_extractor.hpp:50
     int nfast_th_;             // feature_extractor.hpp:52
     int mask_mode_;
+    size_t nmindist_;          // detectGFTT's pass-2 distance and quality
+    double dminquality_;
+
+private:
+    // points the output list needs: nbmax, or nmaxpts_ - ncur where nbmax is -1; 0 = the reference's early return (:108-111)
+    size_t gfttCapacity(size_t ncur, int nbmax) const
+    {
+        if (ncur >= nmaxpts_) return 0;
+        return nbmax != -1 ? (size_t)(nbmax > 0 ? nbmax : 1) : nmaxpts_ - ncur;
+    }
 };
 
 }  // namespace ov2

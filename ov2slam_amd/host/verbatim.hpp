@@ -5,6 +5,8 @@
 //                                                              std::vector<cv::Point2f> &vpriorkps, std::vector<bool> &vkpstatus) const
 //     /root/reference/include/feature_extractor.hpp:40-46  std::vector<cv::Point2f> detectGridFAST / detectSingleScale(const cv::Mat &im, const int ncellsize,
 //                                                              const std::vector<cv::Point2f> &vcurkps, const cv::Rect &roi)
+//     /root/reference/include/feature_extractor.hpp:34-37  FeatureExtractor(); std::vector<cv::Point2f> detectGFTT(const cv::Mat &im,
+//                                                              const std::vector<cv::Point2f> &vcurkps, const cv::Mat &roi, int nbmax=-1) const
 // The adapters of feature_tracker.hpp / feature_extractor.hpp take an ov2::Context and device pyramids -- the fast route, wired by
 // integration/ov2slam_hip.patch.  Here the context is the calling thread's own (created on first use) and the device pyramid of a
 // std::vector<cv::Mat> is found in a small per-thread cache:
@@ -124,7 +126,14 @@ private:
 // ---- FeatureExtractor with the reference's signatures (the adaptive nfast_th_ / dmaxquality_ are the members of the same names) ---------
 class FeatureExtractor {
 public:
+    FeatureExtractor() {}
     FeatureExtractor(size_t nmaxpts, size_t nmaxdist, double dmaxquality, int nfast_th) : impl_(nmaxpts, nmaxdist, dmaxquality, nfast_th) {}
+
+    // cur_img_ is a host Mat here: it is uploaded (the patched route reads the tracker's pyramid instead); an empty roi = none
+    std::vector<cv::Point2f> detectGFTT(const cv::Mat &im, const std::vector<cv::Point2f> &vcurkps, const cv::Mat &roi, int nbmax = -1) const
+    {
+        return impl_.detectGFTT(threadContext(), Image8(im), vcurkps, roi.empty() ? Image8() : Image8(roi), nbmax);
+    }
 
     std::vector<cv::Point2f> detectGridFAST(const cv::Mat &im, const int ncellsize, const std::vector<cv::Point2f> &vcurkps, const cv::Rect &roi)
     {
@@ -136,6 +145,10 @@ public:
     }
     double &dmaxquality() { return impl_.dmaxquality_; }
     int &nfast_th() { return impl_.nfast_th_; }
+    size_t &nmaxpts() { return impl_.nmaxpts_; }
+    size_t &nmaxdist() { return impl_.nmaxdist_; }
+    size_t &nmindist() { return impl_.nmindist_; }
+    double &dminquality() { return impl_.dminquality_; }
 private:
     ov2::FeatureExtractor impl_;
 };
