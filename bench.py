@@ -20,8 +20,11 @@ this GPU processes in lock-step (offline batch-of-sequences mode; default 4096 =
 wall time of one timed step.  The inputs are seeded: the same arguments give the same inputs in every run.
     --dump-outputs DIR  after the timed steps: what the last one computed (tracked positions, status, CLAHE'd frames) as DIR/*.npy
     --details FILE      the full record below as JSON; the stdout line keeps the headline fields and each section's scalars
+    --full              also run every side measurement below; without it a run sets up, warms up, times the steps and reports
+                        the headline, with the roofline figures of those steps
 
-The record also carries (their scalars on the stdout line, all of it with --details):
+With --full the record also carries (their scalars on the stdout line, all of it with --details), besides
+variants of the step (low-entropy frames, one content in every sequence, two streams, keyframe detection):
     single_sequence : ONE camera stream through the drop-in entry (ov2_tracker_track_frame: one H2D of the frame, one
                       LK launch, one sync, hipGraph replay) -- PCIe-inclusive per-frame latency and frames/s; this is the
                       mode configs[1], [2] and [4] of BASELINE.json actually use
@@ -65,7 +68,9 @@ def make_inputs(seqs, seed, uniform=False):
     levels) -- and per-sequence keypoints / priors from the ground-truth flow of the sequence's set (sequence s shows set s % 64).
     Round 5 showed the same seven views to every sequence, band-limited noise stretched to 0..255: the friendliest input there is.
     Returns (views (sets, NF+1, H, W) uint8, kps, pri (2 NF, seqs, NKPS, 2) float32); with uniform=True also the priors of the same
-    keypoints when EVERY sequence shows set 0 (round 5's input, kept as a side measurement of the bench)."""
+    keypoints when EVERY sequence shows set 0 (round 5's input, kept as a side measurement of the bench).
+    The keypoints and priors take `rng`'s draws in the order of a per-sequence loop (tests/test_bench_inputs.py holds that loop and
+    checks the arrays bit for bit); the arithmetic on the draws runs for all sequences of a transition at once."""
     from ov2slam_amd import synth
     rng = np.random.default_rng(seed)
     n_sets = max(1, min(N_VIEW_SETS, seqs))
@@ -101,15 +106,24 @@ def make_inputs(seqs, seed, uniform=False):
         sel = rng.uniform(size=views[k].shape) < 0.8
         views[k] = np.where(sel, views[k] // 32, views[k] // 4).astype(np.uint8)
 
-    def flow(offs, pts, a, b):
-        (ox0, oy0, t0), (ox1, oy1, t1) = offs[a], offs[b]
-        dx, dy = pts[:, 0] - cx, pts[:, 1] - cy
-        c, s = np.cos(t0), np.sin(t0)
-        tx, ty = c * dx - s * dy + cx + ox0, s * dx + c * dy + cy + oy0
+    def flow(sets, pts, a, b):
+        # ground-truth flow of view a -> b for pts (seqs, NKPS, 2) of sequences showing view sets `sets`; the sines and cosines
+        # are taken one angle at a time, as numpy's scalar path computes them
+        def col(fn):
+            return np.array([fn(offs_of[j]) for j in range(n_sets)])[sets][:, None]
+        ox0, oy0, c0, s0 = col(lambda o: o[a][0]), col(lambda o: o[a][1]), col(lambda o: np.cos(o[a][2])), col(lambda o: np.sin(o[a][2]))
+        ox1, oy1, c1, s1 = col(lambda o: o[b][0]), col(lambda o: o[b][1]), col(lambda o: np.cos(-o[b][2])), col(lambda o: np.sin(-o[b][2]))
+        dx, dy = pts[..., 0] - cx, pts[..., 1] - cy
+        tx, ty = c0 * dx - s0 * dy + cx + ox0, s0 * dx + c0 * dy + cy + oy0
         dx, dy = tx - cx - ox1, ty - cy - oy1
-        c, s = np.cos(-t1), np.sin(-t1)
-        return np.stack([c * dx - s * dy + cx, s * dx + c * dy + cy], 1)
+        return np.stack([c1 * dx - s1 * dy + cx, s1 * dx + c1 * dy + cy], -1)
 
+    # per sequence: synth.grid_keypoints(W, H, CELL, rng) (one point per cell, jittered), cut or topped up to NKPS with uniform
+    # points, shuffled, and the priors = ground-truth flow + N(0, 1.5) noise
+    xs, ys = (np.arange(W // CELL) + 0.5) * CELL, (np.arange(H // CELL) + 0.5) * CELL
+    grid = np.stack(np.meshgrid(xs, ys), -1).reshape(-1, 2)
+    n_fill = max(0, NKPS - len(grid))
+    sets = np.arange(seqs) % n_sets
     # transition t of the ping-pong walk over the views (0 -> 1 -> ... -> NF -> NF-1 -> ... -> 0 -> ...): 2*NF transitions per cycle,
     # every frame's `prev` pyramid is the previous step's `cur` -- no view is ever pre-processed twice in a row
     kps = np.zeros((2 * NF, seqs, NKPS, 2), np.float32)
@@ -117,17 +131,26 @@ def make_inputs(seqs, seed, uniform=False):
     pri_u = np.zeros_like(kps) if uniform else None
     for f in range(2 * NF):
         va, vb = walk_view(f), walk_view(f + 1)
+        jit = np.empty((seqs,) + grid.shape)
+        fill = np.empty((seqs, n_fill, 2))
+        perm = np.tile(np.arange(NKPS), (seqs, 1))
+        noise = np.empty((seqs, NKPS, 2))
         for s in range(seqs):
-            k = synth.grid_keypoints(W, H, CELL, rng)[:NKPS]
-            if len(k) < NKPS:
-                extra = np.stack([rng.uniform(20, W - 20, NKPS - len(k)), rng.uniform(20, H - 20, NKPS - len(k))], 1)
-                k = np.concatenate([k, extra.astype(np.float32)])
-            rng.shuffle(k)
-            kps[f, s] = k
-            noise = rng.normal(0, 1.5, k.shape)
-            pri[f, s] = flow(offs_of[s % n_sets], k.astype(np.float64), va, vb) + noise
-            if uniform:
-                pri_u[f, s] = flow(offs_of[0], k.astype(np.float64), va, vb) + noise
+            jit[s] = rng.uniform(-0.45, 0.45, grid.shape)
+            if n_fill:
+                fill[s, :, 0] = rng.uniform(20, W - 20, n_fill)
+                fill[s, :, 1] = rng.uniform(20, H - 20, n_fill)
+            rng.shuffle(perm[s])                                      # the permutation a shuffle of the NKPS rows would apply
+            noise[s] = rng.normal(0, 1.5, (NKPS, 2))
+        g = grid + jit * CELL
+        g[..., 0] = np.clip(g[..., 0], 6, W - 7)
+        g[..., 1] = np.clip(g[..., 1], 6, H - 7)
+        k = np.concatenate([g.astype(np.float32)[:, :NKPS], fill.astype(np.float32)], 1)
+        k = np.take_along_axis(k, perm[..., None], 1)
+        kps[f] = k
+        pri[f] = flow(sets, k.astype(np.float64), va, vb) + noise
+        if uniform:
+            pri_u[f] = flow(np.zeros_like(sets), k.astype(np.float64), va, vb) + noise
     return (views, kps, pri, pri_u) if uniform else (views, kps, pri)
 
 
@@ -864,14 +887,17 @@ def main():
                          "(tools/r4_conc.py, profiles/archive/r4_stream_concurrency.txt): 1 stream 4.4 k frames/s, 2 streams 7.3 k, 4 streams 6.4 k, 8 streams "
                          "5.9 k -- the streams are chains of small launches and the aggregate is bound by the rate the GPU's command processor "
                          "retires them, which is what the lock-step batch entry points (the headline mode) exist to avoid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-sequence / config-5 / BA / detect / parity sections")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement as well (CPU baseline, parity vs the oracle, single-sequence, "
+                         "config 5, BA, detection, stereo, variants of the step): the full record")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements after all (the plain run)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (tracked positions, status, a seeded sample of "
                          "CLAHE'd level-0 images) as DIR/<name>.npy, float32, at most 64 MB")
     ap.add_argument("--details", metavar="FILE", default=None,
-                    help="write the full record (every side measurement with its notes) to FILE as JSON, e.g. bench_out/details.json; stdout "
-                         "carries its summary")
+                    help="write the whole record (with --full every side measurement with its notes) to FILE as JSON, e.g. "
+                         "bench_out/details.json; stdout carries its summary")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -924,7 +950,10 @@ def main():
     dev = torch.device("cuda", local_rank if world > 1 else 0)
 
     S = args.seqs
-    view_sets, kps, pri, pri_uniform = make_inputs(S, seed=1234 + rank, uniform=True)      # every rank owns different sequences; sequence s shows view set s % 64
+    side = args.full and not args.no_extras                     # the side measurements after the headline
+    # every rank owns different sequences; sequence s shows view set s % 64 (with the side measurements, also round 5's priors)
+    inputs = make_inputs(S, seed=1234 + rank, uniform=side and rank == 0)
+    view_sets, kps, pri = inputs[:3]
     views = view_sets[0]                                        # the single-sequence sections below run sequence 0
     n_sets = int(view_sets.shape[0])
 
@@ -1019,7 +1048,7 @@ def main():
     # and the bench frames (band-limited noise stretched to 0..255) are the friendliest input there is -- a constant, an over- or an
     # under-exposed frame puts a wavefront's 64 adds on a handful of bins (round 4's kernel: 3.0x slower on a constant frame)
     pre_entropy = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and side:
         try:
             ev = lambda: torch.cuda.Event(enable_timing=True)
             rngp = np.random.default_rng(5)
@@ -1089,7 +1118,7 @@ def main():
     # event per tracking step orders consumer -> the producer that overwrites the buffer two steps later.  The headline `value`
     # and `roofline` stay the serial ones above: a kernel's launch time measured while it shares the CUs says nothing about it.
     pipelined = None
-    if not args.no_extras and world == 1:
+    if side and world == 1:
       try:
         s_pre = torch.cuda.Stream(device=dev)
         ctx_pre = ov2slam_amd.Context(dev.index, stream=s_pre.cuda_stream)
@@ -1130,7 +1159,7 @@ def main():
     # free the batch buffers before the single-sequence / BA sections
     # ---- keyframe detection for the whole batch: every sequence's detector on level 0 of its pyramid, one call -------------
     det_batch = None
-    if not args.no_extras and world == 1:
+    if side and world == 1:
       try:
         ncells = (W // CELL) * (H // CELL)
         cap = 2 * ncells
@@ -1196,11 +1225,11 @@ def main():
     # same work shape; what differs is how much the Gauss-Newton trip counts of a wavefront's twenty keypoints spread (the kernel idles
     # in lock step behind its slowest keypoint) -- the only link between the 0.28 of rounds 3-5 and this round's figure on 64 contents
     uniform = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and side:
         try:
             for f in range(NF + 1):
                 frames_d[f].copy_(frames_d[f, 0:1].expand(S, H, PITCH))
-            pri_d.copy_(torch.from_numpy(pri_uniform).to(dev))
+            pri_d.copy_(torch.from_numpy(inputs[3]).to(dev))
             lk_events.clear(); stats_d.zero_()
             preprocess(hp[0], a_img[walk_view(0)])
             nu = min(args.steps, 20)
@@ -1227,7 +1256,7 @@ def main():
     torch.cuda.empty_cache()
 
     c5 = None
-    if not args.no_extras and args.workload == "euroc":
+    if side and args.workload == "euroc":
         try:
             ctx5 = ov2slam_amd.Context(dev.index)
             c5 = run_config5(ctx5, rank, world, args.config5_scale, device=dev.index, concurrency=args.config5_concurrency, stream_scale=args.config5_stream_scale)
@@ -1408,7 +1437,7 @@ def main():
             if "speedup_vs_cpu_pipeline_bound" in c2:
                 out["combined_speedup_vs_cpu"] = c2["speedup_vs_cpu_pipeline_bound"]
                 out["combined_speedup_vs_cpu_serial_cpu"] = c2["speedup_vs_cpu_serial"]
-        if world == 1 and not args.no_extras:
+        if world == 1 and side:
             try:
                 extras()
             except Exception:

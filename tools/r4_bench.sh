@@ -1,7 +1,7 @@
 #!/bin/bash
 # bench line on the GPU box (+ optional extra arguments), printed compactly
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; O=$ROOT/gpurun_out/r4b; mkdir -p $O; cd $ROOT
-t0=$(date +%s); timeout 900 python bench.py "$@" > $O/bench.json 2> $O/bench.err; echo "bench rc $? $(( $(date +%s) - t0 )) s"; tail -3 $O/bench.err
+t0=$(date +%s); timeout 900 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err; echo "bench rc $? $(( $(date +%s) - t0 )) s"; tail -3 $O/bench.err
 python - <<'PY'
 import json, os
 O = os.path.join(os.environ.get("GRAFT_REPO_ROOT", "."), "gpurun_out", "r4b")

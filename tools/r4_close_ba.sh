@@ -5,7 +5,7 @@ for c in config4_mono config4_stereo window; do bash tools/ba_kstats.sh $c > $O/
 for c in config4_mono window; do bash tools/ba_timeline.sh $c > $O/tl_$c.log 2>&1; cp gpurun_out/batl_$c/timeline.txt $O/timeline_$c.txt; find gpurun_out/batl_$c -name "*kernel_trace.csv" -delete; done
 bash tools/ba_ticks.sh > $O/ba_ticks.log 2>&1; tail -2 $O/ba_ticks.log
 python tools/ba_iter_time.py > $O/ba_iter_time.txt 2>&1; tail -3 $O/ba_iter_time.txt
-t0=$(date +%s); timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $? $(( $(date +%s) - t0 )) s"
+t0=$(date +%s); timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $? $(( $(date +%s) - t0 )) s"
 python - <<'PY'
 import json, os
 O = os.path.join(os.environ.get("GRAFT_REPO_ROOT", "."), "gpurun_out", "r4c")

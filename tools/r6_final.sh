@@ -22,9 +22,9 @@ cp gpurun_out/prof_$TAG/summary.json $O/${TAG}_rocprof_summary_seqs4096.json
 cp gpurun_out/prof_$TAG/trace_kernel_stats.csv $O/${TAG}_kernel_stats_seqs4096.csv 2>/dev/null
 cp profiles/lk_traffic.json $O/lk_traffic.json
 # --- the bench lines (they now find counters whose kernel-source hashes match the tree)
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 # the driver's command line (20 timed steps after 5: boost clocks, no thermal steady state)
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err; echo "bench (driver args) rc $?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err; echo "bench (driver args) rc $?"
 timeout 600 python bench.py --workload kitti --no-cpu-baseline --no-extras > $O/bench_kitti.json 2> $O/bench_kitti.err; echo "kitti rc $?"
 python - <<PY
 import json
