@@ -15,11 +15,16 @@
 //     on exact integer partial sums (16-bit halves), so results stay bit-identical to the oracle.
 //   * Forward levels and the backward level run through ONE inlined instance of the level body
 //     (a small step machine) to keep the code inside the instruction cache.
+//   * Four wavefronts per SIMD: at most 128 VGPRs without scratch (tests/test_lk3_resources.py).  What held registers
+//     for nothing is gone from them: the v_perm selectors ride in SGPRs, the keypoint and the forward result wait in LDS
+//     (`keep`) while the levels run, lane-derived offsets are formed where they are used, and the template build has a
+//     straight-line instance with and one without the border masks.
 #include "common.hpp"
 #include "xcd_map.hpp"
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -40,12 +45,13 @@ struct LK3Params {
 #define L3_WAVES 1                    // wavefronts per workgroup (no workgroup-level cooperation: small groups balance best)
 #endif
 #ifndef L3_MIN_WAVES_PER_EU
-#define L3_MIN_WAVES_PER_EU 3
+#define L3_MIN_WAVES_PER_EU 4
 #endif
 #define L3_KPB (L3_KPW * L3_WAVES)     // keypoints per workgroup
 #define L3_IROWS (L3_WIN + 3)         // template neighbourhood rows  (12)
 #define L3_JROWS 16                   // search neighbourhood rows
 #define L3_NBH_R 3                    // (16 - (WIN+1)) / 2
+#define L3_KEEP 8                     // dwords per keypoint of the kernel's LDS `keep` (kp, forward result and counters)
 #define L3_STRIDE 116                 // dwords per keypoint slot: 48 (I) + 64 (J) + 4 pad; 16-byte multiple so that rows move as b128
 
 struct L3Lv { int w, h, img_pitch, pady; long long img_roi; };      // the level fields this kernel needs (kept in SGPRs)
@@ -98,13 +104,17 @@ __device__ __forceinline__ int dot2h(uint32_t a, uint32_t b)
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
     return r;
 }
+// A v_perm_b32 selector in a scalar register: VOP3 takes no literal here, and left to itself the compiler keeps each selector
+// in a VGPR for the whole kernel (four of them -- registers the 4-wavefront budget of 128 does not have).
+template <uint32_t K>
+__device__ __forceinline__ uint32_t l3_sel() { uint32_t r; asm("s_mov_b32 %0, %1" : "=s"(r) : "i"(K)); return r; }
 // (S0 >> 16, S1 >> 16) of two signed sums as an i16 pair: their high halves, one byte permute
-__device__ __forceinline__ uint32_t hi16_pair(int s0, int s1) { return __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x07060302u); }
+__device__ __forceinline__ uint32_t hi16_pair(int s0, int s1) { return __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, l3_sel<0x07060302u>()); }
 // (S0 >> 9, S1 >> 9) as two u16 for sums 0 <= S < 2^24 that already hold their rounding constant: bytes 1-2 of each
 // (S >> 8, 16 bits) by one byte permute, then one packed shift
 __device__ __forceinline__ uint32_t shr9_pair(int s0, int s1)
 {
-    const uint32_t hi8 = __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x06050201u);
+    const uint32_t hi8 = __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, l3_sel<0x06050201u>());
     return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, hi8) >> (unsigned short)1));
 }
 __device__ __forceinline__ uint32_t pack_lo16(int lo, int hi) { return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u); }   // (lo & 0xFFFF) | (hi << 16)
@@ -113,12 +123,12 @@ __device__ __forceinline__ uint32_t pack_lo16(int lo, int hi) { return __builtin
 // the two accumulator initialisations (v_dot2c needs its rounding constant moved into the destination first)
 __device__ __forceinline__ uint32_t round9_pair(int s0, int s1)
 {
-    const uint32_t hi8 = __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, 0x06050201u);
+    const uint32_t hi8 = __builtin_amdgcn_perm((uint32_t)s1, (uint32_t)s0, l3_sel<0x06050201u>());
     return __builtin_bit_cast(uint32_t, (u16x2)((__builtin_bit_cast(u16x2, hi8) + (unsigned short)1) >> (unsigned short)1));
 }
 __device__ __forceinline__ uint32_t odd_pair(uint32_t e_next, uint32_t e) { return __builtin_amdgcn_alignbyte(e_next, e, 2); }             // (e.hi, e_next.lo)
-__device__ __forceinline__ uint32_t bytes01(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0c010c00u); }                                 // (b0, b1) as two u16
-__device__ __forceinline__ uint32_t bytes23(uint32_t w) { return __builtin_amdgcn_perm(0u, w, 0x0c030c02u); }                                 // (b2, b3)
+__device__ __forceinline__ uint32_t bytes01(uint32_t w) { return __builtin_amdgcn_perm(0u, w, l3_sel<0x0c010c00u>()); }        // (b0, b1) as two u16
+__device__ __forceinline__ uint32_t bytes23(uint32_t w) { return __builtin_amdgcn_perm(0u, w, l3_sel<0x0c030c02u>()); }        // (b2, b3)
 
 template <int CTRL>
 __device__ __forceinline__ int l3_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
@@ -157,6 +167,9 @@ __device__ __forceinline__ float l3_sum3_f32(int p, int sub)
 __device__ __forceinline__ int l3_round(float v) { return __float2int_rn(v); }
 __device__ __forceinline__ int l3_floor(float v) { return (int)floorf(v); }
 __device__ __forceinline__ int l3_m24(int a, int b) { return __mul24(a, b); }
+// a per-lane value the compiler must take as produced here: what is derived from it is computed where it is used, not
+// hoisted into the kernel prologue and held (or spilled) across every level and Gauss-Newton trip
+__device__ __forceinline__ int l3_pin(int v) { asm volatile("" : "+v"(v)); return v; }
 
 __device__ __forceinline__ void l3_lds_sync()
 {
@@ -175,6 +188,7 @@ __device__ __forceinline__ void l3_lds_sync()
 template <bool CLAMP>
 __device__ __forceinline__ void l3_fetch_J_rows(uint32_t *slot, const uint8_t *jroi, const L3Lv &LJ, int xa, uint32_t sh, int jy0, int sub)
 {
+    sub = l3_pin(sub);
     const uint8_t *p0 = jroi + (long long)(jy0 + sub) * LJ.img_pitch + xa;
     const long long step = 3LL * LJ.img_pitch;
     uint32_t *dst = slot + 48 + 4 * sub;
@@ -234,8 +248,9 @@ struct L3Slot { int ax0, ay0, bx0, by0; };
 __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, const L3Lv &LI,
                                          const uint8_t *__restrict__ itemJ, const L3Lv &LJ,
                                          const LK3Params &prm, int level, bool scale_from_input, bool reuse,
-                                         float px0, float py0, int sub, uint32_t *slot, L3State &st, L3Slot &sl)
+                                         float px0, float py0, int sub_, uint32_t *slot, L3State &st, L3Slot &sl)
 {
+    const int sub = sub_;
     constexpr int WIN = L3_WIN;
     const float halfWin = (float)(WIN - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (float)(1 << 20);
@@ -267,6 +282,7 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
     const uint8_t *iroi = itemI + LI.img_roi, *jroi = itemJ + LJ.img_roi;
     // 12 rows, one 16-byte request each, rows sub + 3k from one base pointer (clamp only near the image border)
     auto fetch_I = [&](uint32_t *dst, int ixa) {
+        const int sub = l3_pin(sub_);
         const bool outside = ipy - 1 < -LI.pady || ipy - 1 + L3_IROWS - 1 > LI.h + LI.pady - 1;
         const bool clamp_rows = __builtin_amdgcn_ballot_w64(outside) != 0;
         const uint8_t *p0 = iroi + (long long)(ipy - 1 + sub) * LI.img_pitch + ixa;
@@ -325,7 +341,7 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
     T.cIX = 0; T.cIY = 0;
     int s11 = 0, s12 = 0, s22 = 0;
     {
-        const int r0 = 3 * sub;
+        const int r0 = 3 * l3_pin(sub);
         // Streaming order (keeps ~100 VGPRs live instead of ~140): image rows are unpacked from LDS as they are
         // needed, derivative row d is formed from image rows d, d+1, d+2, and window row j = d-1 is finished as
         // soon as derivative rows j, j+1 exist.  E[m][i] = (p[2i], p[2i+1]) of image row m;
@@ -343,7 +359,7 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
         // derivative positions outside the image are 0 (rare: only for windows overlapping the image border)
         const bool border = ipx < 0 || ipx + WIN >= LI.w || ipy + r0 < 0 || ipy + r0 + 3 >= LI.h;
         const bool any_border = __builtin_amdgcn_ballot_w64(border) != 0;
-        auto deriv_row = [&](int d, const uint32_t (&ea)[6], const uint32_t (&eb)[6], const uint32_t (&ec)[6], uint32_t (&dx)[5], uint32_t (&dy)[5]) {
+        auto deriv_row = [&](auto border_tag, int d, const uint32_t (&ea)[6], const uint32_t (&eb)[6], const uint32_t (&ec)[6], uint32_t (&dx)[5], uint32_t (&dy)[5]) {
             uint32_t T0[6], T1[6];
 #pragma unroll
             // The derivatives are produced with a factor 4 (Scharr weights 12 / 40 instead of 3 / 10: |4 d| <= 16320 still fits 16
@@ -358,13 +374,14 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 dx[i] = pk_sub(T0[i + 1], T0[i]);
                 dy[i] = pk_add(pk_mul(pk_add(T1[i], T1[i + 1]), 12), pk_mul(odd_pair(T1[i + 1], T1[i]), 40));
             }
-            if (any_border) {
+            if constexpr (decltype(border_tag)::value) {
                 const int Yd = ipy + r0 + d;
                 const bool yin = Yd >= 0 && Yd < LI.h;
+                const uint32_t mlo = (uint32_t)l3_pin(0x0000FFFF), mhi = (uint32_t)l3_pin((int)0xFFFF0000u);   // (made here, not held from the prologue)
 #pragma unroll
                 for (int i = 0; i < 5; i++) {
                     const int X = ipx + 2 * i;
-                    const uint32_t mk = ((yin && X >= 0 && X < LI.w) ? 0x0000FFFFu : 0u) | ((yin && X + 1 >= 0 && X + 1 < LI.w) ? 0xFFFF0000u : 0u);
+                    const uint32_t mk = ((yin && X >= 0 && X < LI.w) ? mlo : 0u) | ((yin && X + 1 >= 0 && X + 1 < LI.w) ? mhi : 0u);
                     dx[i] &= mk; dy[i] &= mk;
                 }
             }
@@ -405,17 +422,23 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
             for (int j = 0; j < L3_RPL; j++) for (int t = 0; t < 5; t++) { T.X[j][t] = slot[4 * r0 + j * 5 + t] >> 1; T.Y[j][t] = T.X[j][t] >> 1; }
             s11 = s22 = 1 << 28; s12 = 0;
         } else {
+        // two straight-line instances, with and without the border masks: a border branch inside every derivative row
+        // let the window rows sink below the last of them, which held all four derivative rows and the image rows at once
+        auto build = [&](auto bt) {
         load_row(0, E0); load_row(1, E1); load_row(2, E2);
-        deriv_row(0, E0, E1, E2, DXa, DYa);
+        deriv_row(bt, 0, E0, E1, E2, DXa, DYa);
         load_row(3, E3);
-        deriv_row(1, E1, E2, E3, DXb, DYb);
+        deriv_row(bt, 1, E1, E2, E3, DXb, DYb);
         window_row(0, E1, E2, DXa, DYa, DXb, DYb);                  // window row 0: image rows 1, 2; derivative rows 0, 1
         load_row(4, E0);                                            // E0 <- image row 4
-        deriv_row(2, E2, E3, E0, DXa, DYa);
+        deriv_row(bt, 2, E2, E3, E0, DXa, DYa);
         window_row(1, E2, E3, DXb, DYb, DXa, DYa);                  // image rows 2, 3; derivative rows 1, 2
         load_row(5, E1);                                            // E1 <- image row 5
-        deriv_row(3, E3, E0, E1, DXb, DYb);
+        deriv_row(bt, 3, E3, E0, E1, DXb, DYb);
         window_row(2, E3, E0, DXa, DYa, DXb, DYb);                  // image rows 3, 4; derivative rows 2, 3
+        };
+        if (any_border) build(std::true_type());
+        else build(std::false_type());
         }
     }
     // per-lane partials: 27 * 4080^2 = 4.5e8 < 2^31
@@ -523,6 +546,7 @@ __global__ __launch_bounds__(64 * L3_WAVES, L3_MIN_WAVES_PER_EU) void k_fb_klt3(
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[L3_KPB * L3_STRIDE];
     __shared__ unsigned int s_stats[2];
+    __shared__ __attribute__((aligned(16))) float keep[L3_KPB * L3_KEEP];
     // XCD-aware work-group -> (batch item, keypoint block) map: the dispatcher deals consecutive work-group
     // ids round-robin over the 8 XCDs, each with its own L2.  All blocks of one item (one image pair) are
     // given ids of the same residue mod 8 and consecutive rank, so the image lines they share are fetched
@@ -540,34 +564,42 @@ __global__ __launch_bounds__(64 * L3_WAVES, L3_MIN_WAVES_PER_EU) void k_fb_klt3(
     }
     if (l16 < 15 && i < n) {                                     // the 3 lanes of a keypoint take the same side
         uint32_t *slot = lds + kslot * L3_STRIDE;
-        const long long gi = (long long)b * prm.n_max + i;
+        // What only the end of the walk needs -- the keypoint, and after the forward pass its result and counters -- waits in
+        // LDS, written by lane 0 of the group, instead of in registers through every level: 4 wavefronts per SIMD leave 128
+        // VGPRs, and the template build of a level needs nearly all of them.
+        float *kk = keep + kslot * L3_KEEP;
         const uint8_t *itemP = P.base + (long long)b * P.item_stride;
         const uint8_t *itemC = C.base + (long long)b * C.item_stride;
-        const float2 kp = kps[gi];
-        const float2 pr = priors[gi];
         L3State st;
-        st.nx = (prm.flags & OV2_LK_USE_INITIAL_FLOW) ? pr.x : kp.x;
-        st.ny = (prm.flags & OV2_LK_USE_INITIAL_FLOW) ? pr.y : kp.y;
+        {
+            const long long gi = (long long)b * prm.n_max + i;
+            const float2 kp = kps[gi];
+            const float2 pr = priors[gi];
+            st.nx = (prm.flags & OV2_LK_USE_INITIAL_FLOW) ? pr.x : kp.x;
+            st.ny = (prm.flags & OV2_LK_USE_INITIAL_FLOW) ? pr.y : kp.y;
+            if (sub == 0) { kk[0] = kp.x; kk[1] = kp.y; }
+        }
         st.status = 1; st.err = 0.f; st.iters = 0; st.visits = 0;
         L3Slot sl = {0, 0, 0, 0};
-        int ok = 1;
         float fx = 0.f, fy = 0.f;
-        int acc_iters = 0, acc_visits = 0;
-        float err_fwd = 0.f;
         // step machine: steps 0..max_level = forward levels max_level..0, step max_level+1 = backward level 0
         const int nsteps = prm.max_level + 1 + (prm.do_fb ? 1 : 0);
         for (int step = 0; step < nsteps; step++) {
             const bool bwd = step > prm.max_level;
+            l3_lds_sync();                                          // kk[] written by lane 0 of the group
             if (bwd) {
                 // forward pass finished: filter (feature_tracker.cpp:79-101), then set up the backward track (:113-116)
                 fx = st.nx; fy = st.ny;
-                ok = st.status;
+                int ok = st.status;
                 if (ok && st.err > prm.err_th) ok = 0;
-                const float W0 = (float)C.lv[0].w, H0 = (float)C.lv[0].h;
+                const float W0 = (float)l3_pin(C.lv[0].w), H0 = (float)l3_pin(C.lv[0].h);
                 if (ok && !(1.f <= fx && fx < W0 - 1.f && 1.f <= fy && fy < H0 - 1.f)) ok = 0;       // inBorder :216-221
-                acc_iters = st.iters; acc_visits = st.visits; err_fwd = st.err;
+                if (sub == 0) {
+                    kk[2] = fx; kk[3] = fy; kk[4] = st.err;
+                    ((int *)kk)[5] = st.iters; ((int *)kk)[6] = st.visits; ((int *)kk)[7] = ok;
+                }
                 if (!ok) break;
-                st.nx = kp.x; st.ny = kp.y; st.status = 1; st.err = 0.f; st.iters = 0; st.visits = 0;
+                st.nx = kk[0]; st.ny = kk[1]; st.status = 1; st.err = 0.f; st.iters = 0; st.visits = 0;
                 // (sl.ax0 .. sl.by0 keep describing the slot: forward level 0 staged both regions, or ok would be 0)
             }
             const int level = bwd ? 0 : prm.max_level - step;
@@ -581,23 +613,32 @@ __global__ __launch_bounds__(64 * L3_WAVES, L3_MIN_WAVES_PER_EU) void k_fb_klt3(
                 LJ.w = bwd ? a.w : c.w; LJ.h = bwd ? a.h : c.h; LJ.img_pitch = bwd ? a.img_pitch : c.img_pitch;
                 LJ.pady = bwd ? a.pady : c.pady; LJ.img_roi = bwd ? a.img_roi : c.img_roi;
             }
-            l3_level(itemI, LI, itemJ, LJ, prm, level, top, bwd, bwd ? fx : kp.x, bwd ? fy : kp.y, sub, slot, st, sl);
+            l3_level(itemI, LI, itemJ, LJ, prm, level, top, bwd, bwd ? fx : kk[0], bwd ? fy : kk[1], sub, slot, st, sl);
         }
-        if (prm.do_fb) {
-            if (ok) {
-                acc_iters += st.iters; acc_visits += st.visits;
-                if (!st.status) ok = 0;
-                else {
-                    const float ddx = kp.x - st.nx, ddy = kp.y - st.ny;      // cv::norm(Point2f) (:128)
-                    const double nrm = sqrt((double)ddx * (double)ddx + (double)ddy * (double)ddy);
-                    if (nrm > (double)prm.fb_dist) ok = 0;
-                }
-            }
-        } else {
-            fx = st.nx; fy = st.ny; ok = st.status; acc_iters = st.iters; acc_visits = st.visits; err_fwd = st.err;
-        }
+        l3_lds_sync();
         if (sub == 0) {
-            priors[gi] = make_float2(fx, fy);
+            float ofx, ofy, err_fwd;
+            int ok, acc_iters, acc_visits;
+            if (prm.do_fb) {
+                ofx = kk[2]; ofy = kk[3]; err_fwd = kk[4];
+                acc_iters = ((const int *)kk)[5]; acc_visits = ((const int *)kk)[6]; ok = ((const int *)kk)[7];
+                if (ok) {
+                    acc_iters += st.iters; acc_visits += st.visits;
+                    if (!st.status) ok = 0;
+                    else {
+                        const float ddx = kk[0] - st.nx, ddy = kk[1] - st.ny;      // cv::norm(Point2f) (:128)
+                        const double nrm = sqrt((double)ddx * (double)ddx + (double)ddy * (double)ddy);
+                        if (nrm > (double)prm.fb_dist) ok = 0;
+                    }
+                }
+            } else {
+                ofx = st.nx; ofy = st.ny; ok = st.status; acc_iters = st.iters; acc_visits = st.visits; err_fwd = st.err;
+            }
+            // the keypoint's index once more from the lane id (held since the prologue, it would cost registers for the whole walk)
+            const int tid = l3_pin((int)threadIdx.x);
+            const int kslot_e = (tid >> 6) * L3_KPW + ((tid & 63) >> 4) * 5 + (tid & 15) / 3;
+            const long long gi = (long long)b * prm.n_max + bx * L3_KPB + kslot_e;
+            priors[gi] = make_float2(ofx, ofy);
             status[gi] = (uint8_t)ok;
             if (err_out) err_out[gi] = err_fwd;
             if (iters_out) iters_out[gi] = acc_iters;
