@@ -812,6 +812,80 @@ int ov2_stereo_match_batch(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *rig
                            const double *D, int nD, int n_max, const float *kps_px_h, const float *kps_unpx_h, const float *priors3d_h,
                            const uint8_t *has_prior3d_h, const int *n_h, float *right_px_h, uint8_t *stereo_ok_h);
 
+/* ------------------------------------------------------------------ */
+/* Keyframe triangulation (Mapper::triangulateStereo +                  */
+/* Mapper::triangulateTemporal, src/mapper.cpp:191-461)                 */
+/* ------------------------------------------------------------------ */
+/* The mapper's two triangulation loops for a new keyframe (called back to back under map_mutex_, src/mapper.cpp:97, :120) in ONE
+ * staging upload, ONE launch, ONE download and ONE synchronisation per call, one lane per keypoint in fp64 (csrc/triangulate.hip):
+ *   stereo      keypoints with is_stereo[i] != 0 (the caller flags is_stereo_ && !is3d_ keypoints, :388-395):
+ *               rect:  disp = unpx.x - runpx.x in float; disp < 0 rejects; z = (float)(K[0] |Tcic0.t| / fabs(disp));
+ *                      left = z * iK * (unpx.x, unpx.y, 1)  (disp == 0 passes and gives a NaN point, accepted like the reference)
+ *               else:  left = triangulate2(Tlr, bv, rbv)
+ *               rejected if left.z < 0.1 or (Tlr^-1 left).z < 0.1, or if |proj_K(left) - unpx| or |proj_Kr(Tcic0 left) - runpx|
+ *               exceeds fmax_reproj_err (cv::Point2f projections, cv::norm, float); otherwise wpt = Twc left, invdepth = 1 / left.z
+ *   temporal    keypoints with src[i] >= 0 that the stereo pass did not make 3-D.  The host decides eligibility from the map
+ *               (:243-295: the map point exists, is not 3-D, has >= 2 observers, its first observer ci is not this keyframe and
+ *               holds the keypoint) and passes ci's row of the source table and ci's keypoint (src_unpx, src_bv):
+ *               Tcicj = Tcw[ci] Twc; in stereo mode |Tcicj.t| < 0.01 skips (OV2_TRI_NO_MOTION); left = triangulate2(Tcicj,
+ *               src_bv, bv), right = Tcicj^-1 left; the same depth and reprojection gates (left K on both sides); a rejection
+ *               with rotation-compensated parallax > 20 px asks for removeMapPointObs; otherwise wpt = Twc[ci] left.
+ * triangulate2 is OpenGV's closed-form midpoint (the USE_OPENGV build, src/multi_view_geometry.cpp:53-100, the one the paper's
+ * results used); the OpenCV fallback (cv::triangulatePoints) is not provided.  Poses are [tx ty tz qx qy qz qw] taken as held by
+ * the Frame / CameraCalibration (no renormalisation); the library inverts only where the reference does (Trl :379, Tcjci :280).
+ * Status bits per keypoint (what a caller needs to replay every map mutation in the reference's order: the stereo keypoints in
+ * order, then the temporal ones):
+ *   STEREO_TRIED && !STEREO_OK   removeStereoKeypointById(lmid)
+ *   STEREO_OK / TEMPORAL_OK      updateMapPoint(lmid, wpt, invdepth)   (anchor: this keyframe / the source keyframe)
+ *   TEMPORAL_TRIED               counted in the reference's `candidates`
+ *   NO_MOTION                    skipped, no mutation
+ *   REMOVE_OBS                   removeMapPointObs(lmid, this keyframe's id)
+ * wpt / invdepth are 0 where no point was created.  OV2_EINVAL: NULL ctx / params / buffers, n or n_src < 0, n_items < 0, a source
+ * index outside [-1, n_src), a point flagged stereo without runpx / rbv or in mono mode, a temporal point without src_unpx /
+ * src_bv; nothing is modified then.  */
+enum {
+    OV2_TRI_STEREO_TRIED = 1, OV2_TRI_STEREO_OK = 2, OV2_TRI_TEMPORAL_TRIED = 4, OV2_TRI_TEMPORAL_OK = 8,
+    OV2_TRI_NO_MOTION = 16, OV2_TRI_REMOVE_OBS = 32
+};
+typedef struct {
+    int stereo;                  /* pslamstate_->stereo_ (the no-motion skip, :287)                                          */
+    int rect;                    /* bdo_stereo_rect_ (:410)                                                                  */
+    float fmax_reproj_err;       /* fmax_reproj_err_                                                                         */
+    double K[4];                 /* left fx fy cx cy (projCamToImage)                                                        */
+    double iK[9];                /* left iK_, row-major (the rectified branch)                                               */
+    double Kr[4];                /* right fx fy cx cy (projCamToRightImage)                                                  */
+    double Tlr[7];               /* pcalib_rightcam_->getExtrinsic() (Tc0ci_)                                                */
+    double Tcic0[7];             /* pcalib_rightcam_->Tcic0_ as held                                                         */
+} ov2_tri_params;
+typedef struct {
+    int n;                       /* keypoints of the new keyframe                                                            */
+    const double *Twc;           /* 7: the new keyframe's Twc_                                                               */
+    const float *unpx;           /* 2n                                                                                       */
+    const double *bv;            /* 3n                                                                                       */
+    const uint8_t *is_stereo;    /* n or NULL (no stereo keypoint)                                                           */
+    const float *runpx;          /* 2n, needed when a point is flagged stereo                                                */
+    const double *rbv;           /* 3n, likewise                                                                             */
+    const int *src;              /* n or NULL: row of the source table, -1 = no temporal candidate                           */
+    const float *src_unpx;       /* 2n: the source keyframe's keypoint of the same map point (needed where src[i] >= 0)      */
+    const double *src_bv;        /* 3n                                                                                       */
+    int n_src;                   /* rows of the source table                                                                 */
+    const double *src_Twc;       /* 7 n_src: Twc_ of each source keyframe                                                    */
+    const double *src_Tcw;       /* 7 n_src: Tcw_ of each source keyframe, as held                                           */
+} ov2_tri_keyframe;
+typedef struct {
+    uint8_t *status;             /* n: OV2_TRI_* bits                                                                        */
+    double *wpt;                 /* 3n                                                                                       */
+    double *invdepth;            /* n                                                                                        */
+    int n_stereo, n_stereo_good; /* the reference's nbstereo / good of the stereo pass                                       */
+    int n_candidates, n_temporal_good;   /* candidates / good of the temporal pass                                           */
+} ov2_tri_result;
+/* one keyframe: the batch form with one item, through the same code path */
+int ov2_triangulate_keyframe(ov2_ctx *ctx, const ov2_tri_params *params, const ov2_tri_keyframe *kf, ov2_tri_result *result);
+/* the keyframes of a lock-step batch, items [0, n_items) with shared params (one grid, grid.y = item; n_items <= 65535, else
+ * OV2_EUNSUPPORTED).  Per item the result equals ov2_triangulate_keyframe on that item; an item with n == 0 is allowed. */
+int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, int n_items, const ov2_tri_keyframe *kfs,
+                                   ov2_tri_result *results);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ OV2_LK_IMPL_AUTO, OV2_LK_IMPL_ROW, OV2_LK_IMPL_LANE3 = 0, 1, 2
 OV2_TRACK_IMPL_WAVE, OV2_TRACK_IMPL_ROW = 0, 1
 OV2_BRIEF_BYTES = 32
 OV2_RES_LEFT, OV2_RES_RIGHT, OV2_RES_RIGHT_ANCH, OV2_RES_PNP = 0, 1, 2, 3
+OV2_TRI_STEREO_TRIED, OV2_TRI_STEREO_OK, OV2_TRI_TEMPORAL_TRIED, OV2_TRI_TEMPORAL_OK, OV2_TRI_NO_MOTION, OV2_TRI_REMOVE_OBS = 1, 2, 4, 8, 16, 32
 
 
 class Ov2Error(RuntimeError):
@@ -134,6 +135,26 @@ class GfttParams(C.Structure):
     """ov2_gftt_params: FeatureExtractor's nmaxpts_, nmaxdist_, nmindist_, dminquality_, dmaxquality_"""
     _fields_ = [("nmaxpts", C.c_int), ("nmaxdist", C.c_int), ("nmindist", C.c_int),
                 ("dminquality", C.c_double), ("dmaxquality", C.c_double)]
+
+
+class TriParams(C.Structure):
+    """ov2_tri_params (Mapper::triangulateStereo / triangulateTemporal)"""
+    _fields_ = [("stereo", C.c_int), ("rect", C.c_int), ("fmax_reproj_err", C.c_float), ("K", C.c_double * 4),
+                ("iK", C.c_double * 9), ("Kr", C.c_double * 4), ("Tlr", C.c_double * 7), ("Tcic0", C.c_double * 7)]
+
+
+class TriKeyframe(C.Structure):
+    """ov2_tri_keyframe"""
+    _fields_ = [("n", C.c_int), ("Twc", C.POINTER(C.c_double)), ("unpx", C.POINTER(C.c_float)), ("bv", C.POINTER(C.c_double)),
+                ("is_stereo", C.POINTER(C.c_uint8)), ("runpx", C.POINTER(C.c_float)), ("rbv", C.POINTER(C.c_double)),
+                ("src", C.POINTER(C.c_int)), ("src_unpx", C.POINTER(C.c_float)), ("src_bv", C.POINTER(C.c_double)),
+                ("n_src", C.c_int), ("src_Twc", C.POINTER(C.c_double)), ("src_Tcw", C.POINTER(C.c_double))]
+
+
+class TriResult(C.Structure):
+    """ov2_tri_result"""
+    _fields_ = [("status", C.POINTER(C.c_uint8)), ("wpt", C.POINTER(C.c_double)), ("invdepth", C.POINTER(C.c_double)),
+                ("n_stereo", C.c_int), ("n_stereo_good", C.c_int), ("n_candidates", C.c_int), ("n_temporal_good", C.c_int)]
 
 
 class XYZBAResult(C.Structure):
@@ -246,6 +267,8 @@ SIGNATURES = {
     "ov2_local_ba_default_options": (None, [C.POINTER(LocalBAOptions)]),
     "ov2_local_ba": (_i, [_vp, C.POINTER(BAProblem), C.POINTER(LocalBAOptions), C.POINTER(LocalBAResult)]),
     "ov2_local_ba_batch": (_i, [_vp, _i, C.POINTER(BAProblem), C.POINTER(LocalBAOptions), C.POINTER(LocalBAResult), C.POINTER(_i)]),
+    "ov2_triangulate_keyframe": (_i, [_vp, C.POINTER(TriParams), C.POINTER(TriKeyframe), C.POINTER(TriResult)]),
+    "ov2_triangulate_keyframe_batch": (_i, [_vp, C.POINTER(TriParams), _i, C.POINTER(TriKeyframe), C.POINTER(TriResult)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

@@ -5,4 +5,5 @@
 #include "camera_calibration.hpp"
 #include "visual_front_end.hpp"
 #include "slam_gpu.hpp"
+#include "mapper.hpp"
 int main() { return 0; }
