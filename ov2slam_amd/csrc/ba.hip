@@ -38,9 +38,6 @@
 #include <chrono>
 #include <thread>
 
-#ifndef BA_KO
-#define BA_KO 0      // knock-out timing of the lineariser: 1 no global Hao atomics, 2 no LDS atomics, 4 no wave sums, 8 no landmark pairs
-#endif
 #pragma clang fp contract(fast)   // BA parity is 1e-4 relative in fp64: FMA contraction is fine here
 
 #define BA_TILE 32
@@ -555,7 +552,7 @@ __device__ __forceinline__ void block_reduce3(double &a, double &b, double &c, d
 // H is stored as its UPPER triangle only (row <= col).
 // The 35 per-landmark sums over the residual lanes (Haa[21], F_a^T b [6], E^T F_a [6], E^T E, E^T b) go through a
 // per-wave 35 x 33 LDS transpose -- every lane parks its partials, lane q adds up row q -- instead of 35 six-step
-// shuffle butterflies (420 ds_bpermute per landmark: a third of this kernel, knock-out timing BA_KO=4); lane q keeps
+// shuffle butterflies (420 ds_bpermute per landmark: a third of this kernel by knock-out timing); lane q keeps
 // the running anchor sums q < 27 in ONE register until the anchor changes.
 // dynamic LDS: 8*nfp (two W rows per wavefront) + n_opt*27 + 4*n_opt*21 + 4*LIN_RED doubles
 #define LIN_NRED 35
@@ -619,12 +616,10 @@ __device__ __forceinline__ void b_ba_linearize(const BADev &D, const int *__rest
                 int t = e - ob * 21, c = 0, d = 0;
                 for (c = 0; c < 6; c++) { if (t < 6 - c) { d = c + t; break; } t -= 6 - c; }
                 atomicAdd(&Hoo[e], v);                                               // block-shared observer blocks (same indexing)
-#if !(BA_KO & 1)
                 if (ca >= 0) {
                     h_add_upper(Hout, D.nfp, ca + d, ob * 6 + c, -v);
                     if (d != c) h_add_upper(Hout, D.nfp, ca + c, ob * 6 + d, -v);
                 }
-#endif
                 Hao[e] = 0;
             }
         }
@@ -660,7 +655,7 @@ __device__ __forceinline__ void b_ba_linearize(const BADev &D, const int *__rest
     // passes deliver the two landmarks' sums.  Anything else (more blocks, a change of anchor, the sparse-W path) goes singly.
     LmHdr hq0, hq1, hq2, hq3;                                       // headers of the landmarks idx .. idx + 3
     ResRec r_cur;
-    auto pairable = [&](const LmHdr &x, const LmHdr &y, int ix) { return !(BA_KO & 8) && !BIG && ix + 1 < i1 && x.a == y.a && x.end - x.beg <= 32 && y.end - y.beg <= 32; };
+    auto pairable = [&](const LmHdr &x, const LmHdr &y, int ix) { return !BIG && ix + 1 < i1 && x.a == y.a && x.end - x.beg <= 32 && y.end - y.beg <= 32; };
     bool pair_cur = false;
     if (i0 < i1) {
         hq0 = load_hdr(i0); hq1 = load_hdr(i0 + 1); hq2 = load_hdr(i0 + 2); hq3 = load_hdr(i0 + 3);
@@ -742,22 +737,17 @@ __device__ __forceinline__ void b_ba_linearize(const BADev &D, const int *__rest
                 if (co >= 0) {
                     const int ob = co / 6;
                     int t = 0;
-#if !(BA_KO & 2)
                     for (int c = 0; c < 6; c++) {
                         atomicAdd(&my_wrow[co + c], Jl[0] * Jo[c] + Jl[1] * Jo[6 + c]);   // LDS fp64 atomics
                         atomicAdd(&bo[ob * 6 + c], Jo[c] * r[0] + Jo[6 + c] * r[1]);
                         for (int d = c; d < 6; d++) atomicAdd(&Hao[ob * 21 + t++], Jo[c] * Jo[d] + Jo[6 + c] * Jo[6 + d]);
                     }
-#else
-                    if (Jo[0] == 1.2345) my_wrow[co] = Jo[1] + Ja[3] + (double)ob + (double)t;
-#endif
                 }
             }
         }
         // transpose-reduce: slots 0..20 Haa, 21..26 ba, 27..32 wa, 33 E^T E, 34 E^T b; pass p takes the lanes 32 p .. 32 p + 31: the
         // second landmark of a pair, or the blocks 32 .. 63 of a single landmark with more than 32 of them
         double tot = 0, totB = 0;
-#if !(BA_KO & 4)
         for (int p = 0; p < ((pair_cur || hq0.end - hq0.beg > 32) ? 2 : 1); p++) {
             if ((lane >> 5) == p) {
                 double *col = red + (lane & 31);
@@ -777,9 +767,6 @@ __device__ __forceinline__ void b_ba_linearize(const BADev &D, const int *__rest
             }
             wave_lds_sync();
         }
-#else
-        tot = Haa[lane % 21] + ba[lane % 6] + wa[lane % 6] + ete + etb;
-#endif
         if (ca >= 0 && lane < 27) dacc += tot + totB;
         if (lane == 33) { D.ete[lm0] = tot; if (pair_cur) D.ete[lm1] = totB; }
         if (lane == 34) { D.etb[lm0] = tot; if (pair_cur) D.etb[lm1] = totB; gmax_w = fmax(gmax_w, fmax(fabs(tot), fabs(totB))); }
@@ -1160,13 +1147,10 @@ __global__ __launch_bounds__(256) void k_ba_schur_gemm_B(const BADev *__restrict
 // below it is solved row-per-thread against that block and parked in LDS, and the trailing update
 // reads the panel from LDS only (each S entry is touched once per panel).
 #define CH_NB 32
-#ifndef CH_GRP
 #define CH_GRP 8           // columns of the diagonal block published per work-group barrier (pipelined panel solve): 2 / 4 / 8 -> 102 / 89 / 87 us
-#endif
 #define CH_LDP 33          // padded leading dimension (doubles) of the LDS panel rows
-// CH_EXP (undefined in the product): knock-out timing of k_ba_cholesky's phases (tools/build_variant.sh ... -DCH_EXP=<bits>,
-// profiles/archive/r4_ba_dead_ends.txt): trailing update 1 no MFMA, 2 no loads of the old tile values, 4 no tile stores, 8 no LDS operand
-// reads; 16 the panel solve does a quarter of its terms.  Any value switches the positive-pivot test off (the factor is garbage).
+// knock-out timings of k_ba_cholesky's phases (no MFMA, no loads of the old tile values, no tile stores, no LDS operand reads, a
+// quarter of the panel solve's terms): profiles/archive/r4_ba_dead_ends.txt
 #define CH_MAX_LDS_N 415   // k_ba_cholesky (512 threads, six panel wavefronts): the right-hand side rides as a panel row, n - 32 + 1 <= 384; larger: HBM path
 // dynamic LDS of k_ba_cholesky: diagonal block, solution vector, panel (rows rounded up to whole 16-row MFMA tiles: the trailing
 // update reads its operand rows unpredicated)
@@ -1449,9 +1433,7 @@ __device__ __forceinline__ void b_ba_cholesky(const BADev &D)
 #pragma unroll
                     for (int k = kmin; k < c; k++) pnext -= a[k] * L11[(c + 1) * CH_LDP + k];
                 }
-#ifndef CH_EXP
                 if (!(d > 0.0) || !isfinite(d)) fail = true;
-#endif
                 // pivot through 1/sqrt(d): v_rsq_f64 seed (~2^-26) + two Newton steps, then L[c][c] = d r with one Heron
                 // correction and L[i][c] = sacc r -- 9 dependent instructions instead of the ~25 of sqrt() followed by a
                 // division, 32 times per block on the kernel's longest serial chain (and 15 KB less unrolled code)
@@ -1513,13 +1495,8 @@ __device__ __forceinline__ void b_ba_cholesky(const BADev &D)
                     __syncthreads();                           // columns j .. j+3 of L11 and their reciprocal pivots are there
                 }
                 double acc = x[j];
-#if defined(CH_EXP) && (CH_EXP & 16)
-#pragma unroll
-                for (int k = 0; k < j; k += 4) acc -= x[k] * L11[j * CH_LDP + k];
-#else
 #pragma unroll
                 for (int k = 0; k < j; k++) acc -= x[k] * L11[j * CH_LDP + k];
-#endif
                 x[j] = acc * s_rdiag[j];
             }
             if (has) {
@@ -1596,12 +1573,7 @@ __device__ __forceinline__ void b_ba_cholesky(const BADev &D)
             auto fetch = [&](int bi, int bj, bool has, double (&o)[4]) {
                 const double *c = corner(bi, bj);
 #pragma unroll
-#if defined(CH_EXP) && (CH_EXP & 2)
-                for (int r = 0; r < 4; r++) o[r] = (has && okmask(bi, bj, r)) ? (double)lo[r] : 0.0;
-                (void)c;
-#else
                 for (int r = 0; r < 4; r++) o[r] = (has && okmask(bi, bj, r)) ? c[lo[r]] : 0.0;
-#endif
             };
             int bi0 = 0, bj0 = 0, bi1, bj1;
             advance(bi0, bj0, wv);
@@ -1622,28 +1594,14 @@ __device__ __forceinline__ void b_ba_cholesky(const BADev &D)
                 d4 c0 = {0., 0., 0., 0.}, c1 = {0., 0., 0., 0.};
 #pragma unroll
                 for (int kk = 0; kk < CH_NB / 4; kk++) {
-#if defined(CH_EXP) && (CH_EXP & 1)
-                    c0[0] += pa0[4 * kk] * pb0[4 * kk]; c1[0] += pa1[4 * kk] * pb1[4 * kk];
-#else
-#if defined(CH_EXP) && (CH_EXP & 8)
-                    c0 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)(bi0 + kk), (double)(bj0 - kk), c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f64_16x16x4f64((double)(bi1 * kk), (double)(bj1 + lk), c1, 0, 0, 0);
-#else
                     c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa0[4 * kk], pb0[4 * kk], c0, 0, 0, 0);
                     c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa1[4 * kk], pb1[4 * kk], c1, 0, 0, 0);
-#endif
-#endif
                 }
                 double *q0 = corner(bi0, bj0), *q1 = corner(bi1, bj1);
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-#if defined(CH_EXP) && (CH_EXP & 4)
-                    if (okmask(bi0, bj0, r) && c0[r] == 1.2345) q0[lo[r]] = old0[r] - c0[r];
-                    if (has1 && okmask(bi1, bj1, r) && c1[r] == 1.2345) q1[lo[r]] = old1[r] - c1[r];
-#else
                     if (okmask(bi0, bj0, r)) q0[lo[r]] = old0[r] - c0[r];
                     if (has1 && okmask(bi1, bj1, r)) q1[lo[r]] = old1[r] - c1[r];
-#endif
                 }
                 bi0 = nbi0; bj0 = nbj0; bi1 = nbi1; bj1 = nbj1;
 #pragma unroll

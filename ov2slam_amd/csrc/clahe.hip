@@ -61,15 +61,10 @@ __device__ __forceinline__ void clahe_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#ifndef CLAHE_KO
-#define CLAHE_KO 0        // knock-out timing experiments. lut: 1 loads hit one line, 2 no ds_add, 4 no clip/scan tail;
-#endif                    // apply: 8 loads hit, 16 no stores, 32 no LUT look-ups, 64 no blend
 #define CH_WAVE_DW 256               // dwords of a one-copy histogram
 #define CH_CSTRIDE 264               // dwords between the copies of a multi-copy histogram: bin b of copy c sits in LDS bank (b + 8 c) % 64
-#ifndef CH_NCOPY
 #define CH_NCOPY 4                   // copies of the wavefronts that histogram most tiles (k_clahe_lut; the LUT wavefronts of the fused kernel)
-#endif
-                                     // (A/B builds: tools/build_variant.sh .. -DCH_NCOPY=..; profiles/r5_clahe_histogram_variants.txt)
+                                     // (other copy counts: profiles/r5_clahe_histogram_variants.txt)
 #define CH_MULTI_DW (CH_NCOPY * CH_CSTRIDE)
 typedef uint32_t c_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -110,7 +105,7 @@ __device__ __forceinline__ void clahe_lut_tiles(const ClaheParams &P, const uint
     auto tile_load = [&](int t, uint32_t (&vv)[16], uint32_t &phs) {
         const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
         const int x_begin = tx * P.tw;
-        if (SRC_ALIGNED && !(CLAHE_KO & 1) && (ty * P.th + 64 <= P.h) && (long long)P.h * P.stride < (1ll << 31)) {
+        if (SRC_ALIGNED && (ty * P.th + 64 <= P.h) && (long long)P.h * P.stride < (1ll << 31)) {
             // all 64 candidate rows lie inside the image: one scalar base, one 32-bit lane offset, no per-row tests
             // (rows >= th are fetched and ignored; lanes right of the tile stay masked: the row may end there)
             const uint32_t ph = (uint32_t)(x_begin & 3);
@@ -136,8 +131,6 @@ __device__ __forceinline__ void clahe_lut_tiles(const ClaheParams &P, const uint
             if (SRC_ALIGNED) {
                 const uint32_t ph = (uint32_t)(x_begin & 3);          // rows and base aligned: the phase is the tile's column phase
                 phs |= ph << (2 * i);
-                if (CLAHE_KO & 1) { if (4 * i + sub < P.th && 4 * l16 < P.tw + (int)ph && (x_begin & ~3) + 4 * l16 < P.w) v = *(const uint32_t *)(img + 4 * l16); }
-                else
                 if (4 * i + sub < P.th && 4 * l16 < P.tw + (int)ph && (x_begin & ~3) + 4 * l16 < P.w) v = *(const uint32_t *)(img + y * P.stride + (x_begin & ~3) + 4 * l16);
             } else {
                 const uint8_t *rp = img + (long long)y * P.stride + x_begin;
@@ -182,7 +175,6 @@ __device__ __forceinline__ void clahe_lut_tiles(const ClaheParams &P, const uint
                 }
                 if (mine && 4 * i + sub < P.th) {
                     const uint32_t v = cur[i];
-                    if (CLAHE_KO & 2) { if (v == 0x12345678u) hw[0] = 1; continue; }
                     atomicAdd(&hist[v & 0xFF], w0);
                     atomicAdd(&hist[(v >> 8) & 0xFF], w1);
                     atomicAdd(&hist[(v >> 16) & 0xFF], w2);
@@ -217,7 +209,7 @@ __device__ __forceinline__ void clahe_lut_tiles(const ClaheParams &P, const uint
             histogram(tn);
             if (tn + tstride < ntiles && tile_fast(tn + tstride)) tile_load(tn + tstride, cur, cur_ph);
         }
-        if (P.clip > 0 && !(CLAHE_KO & 4)) {
+        if (P.clip > 0) {
             int over = 0;
 #pragma unroll
             for (int k = 0; k < 4; k++) { over += max(hv[k] - P.clip, 0); hv[k] = min(hv[k], P.clip); }
@@ -350,8 +342,6 @@ __global__ __launch_bounds__(512) void k_clahe_apply(ClaheParams P, const uint8_
                 const int y = min(yb + u, y1 - 1);
                 const uint8_t *sp = simg + (long long)y * P.stride + xb;
                 uint32_t in = 0;
-                if (CLAHE_KO & 8) in = *(const uint32_t *)(simg + (tid & 15) * 4);
-                else
                 // aligned rows: the dword at xb lies inside the row's stride even when w % 4 != 0 (stride % 4 == 0 > w); no
                 // branch here, so that the compiler can count the loads in flight (vmcnt(CA_UNROLL) instead of vmcnt(0))
                 if (src_aligned) in = *(const uint32_t *)sp;
@@ -379,9 +369,7 @@ __global__ __launch_bounds__(512) void k_clahe_apply(ClaheParams P, const uint8_
                 const c_f32x2 YA = {ya, ya}, YB = {ya1, ya1};
                 uint8_t *drow = dimg + y * P.dst_stride;
                 const uint32_t in = inr[u];
-                uint32_t q0, q1, q2, q3;
-                if (CLAHE_KO & 32) { q0 = in; q1 = in >> 1; q2 = in >> 2; q3 = in >> 3; }
-                else { q0 = lutc[0][in & 0xFF]; q1 = lutc[1][(in >> 8) & 0xFF]; q2 = lutc[2][(in >> 16) & 0xFF]; q3 = lutc[3][in >> 24]; }
+                const uint32_t q0 = lutc[0][in & 0xFF], q1 = lutc[1][(in >> 8) & 0xFF], q2 = lutc[2][(in >> 16) & 0xFF], q3 = lutc[3][in >> 24];
                 // res = (l11 * xa1 + l12 * xa) * ya1 + (l21 * xa1 + l22 * xa) * ya, pixels (0,1) and (2,3) side by side
                 const c_f32x2 A11 = {c_ub(q0, 0), c_ub(q1, 0)}, A12 = {c_ub(q0, 1), c_ub(q1, 1)}, A21 = {c_ub(q0, 2), c_ub(q1, 2)}, A22 = {c_ub(q0, 3), c_ub(q1, 3)};
                 const c_f32x2 B11 = {c_ub(q2, 0), c_ub(q3, 0)}, B12 = {c_ub(q2, 1), c_ub(q3, 1)}, B21 = {c_ub(q2, 2), c_ub(q3, 2)}, B22 = {c_ub(q2, 3), c_ub(q3, 3)};
@@ -392,8 +380,6 @@ __global__ __launch_bounds__(512) void k_clahe_apply(ClaheParams P, const uint8_
                 out = __builtin_amdgcn_cvt_pk_u8_f32(rintf(r01.y), 1, out);
                 out = __builtin_amdgcn_cvt_pk_u8_f32(rintf(r23.x), 2, out);
                 out = __builtin_amdgcn_cvt_pk_u8_f32(rintf(r23.y), 3, out);
-                if (CLAHE_KO & 64) out = q0 ^ q1 ^ q2 ^ q3;
-                if ((CLAHE_KO & 16) && out != 0x12345678u) continue;
                 if (full) *(uint32_t *)(drow + xb) = out;
                 else for (int k = 0; k < 4; k++) if (xb + k < P.w) drow[xb + k] = (uint8_t)(out >> (8 * k));
             }
@@ -454,17 +440,13 @@ __global__ __launch_bounds__(512) void k_clahe_apply(ClaheParams P, const uint8_
 // may be unaligned (hardware handles unaligned dword loads).
 // Geometry: dword-aligned destinations, h >= 8, at most CS_MAX_STRIPS strips, tiles_x + 1 <= 40 (host-checked; anything else takes
 // the separate kernels).  tests/test_gpu_clahe.py: named geometries vs the oracle + a random sweep vs the
-// separate kernels.
+// separate kernels.  Knock-out timings of its parts: profiles/archive/r4_strip_kernel_knockouts.txt.
 __device__ __forceinline__ uint32_t c_wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true); }   // lane i <- lane i-1
 __device__ __forceinline__ uint32_t c_wave_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true); }   // lane i <- lane i+1
 
 #define CS_UNROLL 6
-#ifndef CS_KO
-#define CS_KO 0           // knock-out timing experiments (tools/build_variant.sh; profiles/archive/r4_strip_kernel_knockouts.txt): 1 loads hit one
-#endif                    // row, 2 no level-0 stores, 4 no level-1 stores, 8 no LUT look-ups, 16 no blend, 32 no pyrDown sums / level-1
-                          // rows, 64 / 128 no border stores of level 0 / 1, 256 distinct slack dwords, 512 / 1024 (fused form) the LUT
-                          // wavefront / the shared first row of tiles computes nothing
 #define CS_MAX_STRIPS 8
+#define CS_LUT_PRIO 3     // s_setprio of the fused kernel's LUT wavefront
 // UNAL: w % 4 != 0 or an odd level-1 width (the generic right edge); false keeps the w % 4 == 0 instance free of its per-lane
 // selectors (they cost three spilled registers at this kernel's 80-VGPR budget)
 // FUSED (round 4): the work-group has one more wavefront, which computes the tile LUTs (clahe_lut_tiles: histogram, clip, scan) of the
@@ -516,16 +498,13 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         __syncthreads();
     };
     if (FUSED) {
-        if (!(CS_KO & 1024)) lut_row(0, s, P.nstrips + P.nlut);              // the first row of tiles: all wavefronts
+        lut_row(0, s, P.nstrips + P.nlut);                              // the first row of tiles: all wavefronts
         if (s >= P.nstrips) {                                           // the LUT wavefront: one row of tiles ahead of the strips
             const int n_cell_rows = cell_row(P.h - 1) + 1;              // (the strips stage every row of cells once, in order)
-#ifndef CS_LUT_PRIO
-#define CS_LUT_PRIO 3
-#endif
             __builtin_amdgcn_s_setprio(CS_LUT_PRIO);                    // one wavefront against 3: it must not wait for issue slots
             for (int c = 0; c < n_cell_rows; c++) {
                 build(c);
-                if (c + 1 < P.tiles_y && !(CS_KO & 512)) lut_row(c + 1, s - P.nstrips, P.nlut);
+                if (c + 1 < P.tiles_y) lut_row(c + 1, s - P.nstrips, P.nlut);
             }
             return;
         }
@@ -567,7 +546,7 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     const bool dup = d_raw > ndw - 1;                                   // lanes beyond the image recompute the last column: their stores go to the slack
     const uint32_t pad0 = 4u * nb0, pad1 = 2u * nb1;
     // stores of lanes without a border column: the alignment slack right of the border (never consumed, inside the row pitch)
-    const uint32_t slack0 = pad0 + 4u * (uint32_t)((P.w + win + 3) >> 2) + ((CS_KO & 256) ? 4u * lane : 0u), slack1 = pad1 + 2u * (uint32_t)((P.l1_w + win + 3) >> 1) + ((CS_KO & 256) ? 2u * lane : 0u);
+    const uint32_t slack0 = pad0 + 4u * (uint32_t)((P.w + win + 3) >> 2), slack1 = pad1 + 2u * (uint32_t)((P.l1_w + win + 3) >> 1);
     const uint32_t o0 = dup ? slack0 : pad0 + 4u * d;
     // right border dword of this lane: pixels p[top], p[top-1], p[top-2], p[top-3] at x0 = 2 (w - 1) - top, top = xb + 2 (w even)
     // or xb (w odd): the choice that makes x0 a multiple of 4; both windows lie inside (left neighbour's dword, own dword)
@@ -592,11 +571,6 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         y_switch = yn;
         build(cy);
     };
-    // a level-0 row: every lane's dword and, in the edge strips, the border dword
-#ifndef CS_BUF
-#define CS_BUF 1          // 0: 64-bit lane addresses (the form the CS_KO store knock-outs are written for)
-#endif
-#if CS_BUF
     // buffer addressing (round 4): one descriptor per image, the row as a scalar offset, the lane's column as a 32-bit offset -- no
     // 64-bit address arithmetic per store (the kernel's time is within noise of the pointer form, 1 % in the median; it needs 6-8
     // registers less, and the instance for unaligned widths no longer spills)
@@ -604,35 +578,23 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     const __amdgpu_buffer_rsrc_t rs_dst = __builtin_amdgcn_make_buffer_rsrc(dbase, 0, 0x7fffffff, 0x00020000);
     const uint8_t *sbase = src + (long long)b * P.src_item_stride;
     const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void *)sbase, 0, 0x7fffffff, 0x00020000);
+    // a level-0 row: every lane's dword and, in the edge strips, the border dword
     auto put0 = [&](uint8_t *row, uint32_t v, uint32_t bv) {
         const int so = (int)(row - dbase);
         __builtin_amdgcn_raw_buffer_store_b32(v, rs_dst, (int)o0, so, 0);
         if (edge_strip) __builtin_amdgcn_raw_buffer_store_b32(bv, rs_dst, (int)o0b, so, 0);
     };
-    auto put1 = [&](uint8_t *row, uint32_t v, uint32_t bv) {
+    auto put1 = [&](uint8_t *row, uint32_t v, uint32_t bv) {               // a level-1 row: pixel pairs
         const int so = (int)(row - dbase);
         __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, rs_dst, (int)o1, so, 0);
         if (edge_strip) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bv, rs_dst, (int)o1b, so, 0);
     };
-#else
-    auto put0 = [&](uint8_t *row, uint32_t v, uint32_t bv) {
-        if ((CS_KO & 2) && v != 0x12345678u) return;
-        *(uint32_t *)(row + o0) = v;
-        if (edge_strip && !(CS_KO & 64)) *(uint32_t *)(row + o0b) = bv;
-    };
-    auto put1 = [&](uint8_t *row, uint32_t v, uint32_t bv) {               // a level-1 row: pixel pairs
-        if ((CS_KO & 4) && v != 0x12345678u) return;
-        *(uint16_t *)(row + o1) = (uint16_t)v;
-        if (edge_strip && !(CS_KO & 128)) *(uint16_t *)(row + o1b) = (uint16_t)bv;
-    };
-#endif
     typedef unsigned short cu16x2 __attribute__((ext_vector_type(2)));
     uint8_t *r1 = d1m;                                                  // level-1 row of the next emit
     // level-1 row Y from the horizontal sums of level-0 rows 2Y-2 .. 2Y+2 (packed pairs, <= 16 * 255 each); rows are emitted in order.
     // The REFLECT_101 border mirrors rows 1 .. win above the image and rows h1-1-win .. h1-2 below it: the same stores once more
     auto emit = [&](int Y, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4, auto mirror_c) {
         constexpr bool MIRROR = decltype(mirror_c)::value;
-        if (CS_KO & 32) { if (c4 == 0x12345678u) *(uint32_t *)r1 = c4; return; }
         const cu16x2 s0 = __builtin_bit_cast(cu16x2, c0), s1 = __builtin_bit_cast(cu16x2, c1), s2 = __builtin_bit_cast(cu16x2, c2),
                      s3 = __builtin_bit_cast(cu16x2, c3), s4 = __builtin_bit_cast(cu16x2, c4);
         const cu16x2 v = (s2 * (unsigned short)6 + (s1 + s3) * (unsigned short)4 + s0 + s4 + (unsigned short)128) >> (unsigned short)8;
@@ -664,9 +626,7 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         const float tyf = (float)y * P.inv_th - 0.5f;
         const float ya = tyf - (float)(cy - 1), ya1 = 1.0f - ya;
         const c_f32x2 YA = {ya, ya}, YB = {ya1, ya1};
-        uint32_t q0, q1, q2, q3;
-        if (CS_KO & 8) { q0 = in * 0x01010101u; q1 = in ^ 0x55u; q2 = in + 0x01020304u; q3 = in >> 3; }
-        else { q0 = lutc[0][in & 0xFF]; q1 = lutc[1][(in >> 8) & 0xFF]; q2 = lutc[2][(in >> 16) & 0xFF]; q3 = lutc[3][in >> 24]; }
+        const uint32_t q0 = lutc[0][in & 0xFF], q1 = lutc[1][(in >> 8) & 0xFF], q2 = lutc[2][(in >> 16) & 0xFF], q3 = lutc[3][in >> 24];
         const c_f32x2 A11 = {c_ub(q0, 0), c_ub(q1, 0)}, A12 = {c_ub(q0, 1), c_ub(q1, 1)}, A21 = {c_ub(q0, 2), c_ub(q1, 2)}, A22 = {c_ub(q0, 3), c_ub(q1, 3)};
         const c_f32x2 B11 = {c_ub(q2, 0), c_ub(q3, 0)}, B12 = {c_ub(q2, 1), c_ub(q3, 1)}, B21 = {c_ub(q2, 2), c_ub(q3, 2)}, B22 = {c_ub(q2, 3), c_ub(q3, 3)};
         const c_f32x2 r01 = (A11 * XB01 + A12 * XA01) * YB + (A21 * XB01 + A22 * XA01) * YA;
@@ -678,7 +638,6 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         const uint32_t u0 = __builtin_bit_cast(uint32_t, (float)m01.x), u1 = __builtin_bit_cast(uint32_t, (float)m01.y);
         const uint32_t u2 = __builtin_bit_cast(uint32_t, (float)m23.x), u3 = __builtin_bit_cast(uint32_t, (float)m23.y);
         uint32_t out = __builtin_amdgcn_perm(__builtin_amdgcn_perm(u3, u2, 0x0c0c0400u), __builtin_amdgcn_perm(u1, u0, 0x0c0c0400u), 0x05040100u);
-        if (CS_KO & 16) out = q0 + q1 + q2 + q3;
         // neighbours: pixels xb-2, xb-1 (left lane's bytes 2, 3) and xb+4 (right lane's byte 0); REFLECT_101 at the image edge
         uint32_t lf = c_wave_shr1(out), rt = c_wave_shl1(out);
         if (first_col) lf = __builtin_amdgcn_perm(out, out, 0x01020000u);      // (.., .., p2, p1)
@@ -697,7 +656,6 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
             if (y >= P.h - 1 - win && y <= P.h - 2) put0(d0m + (long long)(2 * (P.h - 1) - y) * P.dst_stride, out, bv);
         }
         // pyrDown, horizontal: sums centred on pixels xb and xb + 2
-        if (CS_KO & 32) { hE += out; return; }
         const uint32_t l0 = __builtin_amdgcn_alignbyte(out, lf, 2);
         const uint32_t h0 = __builtin_amdgcn_udot4(l0, 0x04060401u, __builtin_amdgcn_udot4(out, 0x00010000u, 0u, false), false);
         const uint32_t h1 = __builtin_amdgcn_udot4(out, 0x04060401u, __builtin_amdgcn_udot4(rt, 0x00000001u, 0u, false), false);
@@ -710,11 +668,7 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     for (int yb = 0; yb < P.h; yb += CS_UNROLL) {
         if (yb + 2 * CS_UNROLL <= P.h) {
 #pragma unroll
-#if CS_BUF
             for (int u = 0; u < CS_UNROLL; u++) { nxt[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_src, (int)xo, (int)(srow - sbase), 0) >> (UNAL ? in_sh : 0u); srow += P.stride; }
-#else
-            for (int u = 0; u < CS_UNROLL; u++) { nxt[u] = *(const cs_u32_a1 *)(srow + xo) >> (UNAL ? in_sh : 0u); if (!(CS_KO & 1)) srow += P.stride; }
-#endif
         } else {
 #pragma unroll
             for (int u = 0; u < CS_UNROLL; u++)

@@ -28,12 +28,7 @@
 #pragma clang fp contract(off)
 
 #define DET_MAX_CELL 64
-#ifndef DET_TWO_STREAMS
-#define DET_TWO_STREAMS 1
-#endif
-#ifndef DET_CHUNK
 #define DET_CHUNK 1024     // images per pass of the batch entry points (the response maps of a pass live in the scratch: 1.3 MB per EuRoC image)
-#endif
 
 __device__ __forceinline__ int d_reflect101(int p, int len)
 {
@@ -713,12 +708,8 @@ __device__ void d_fk_std_sort(int *first, int n, int *stk)
     else d_fk_insertion_sort(first, first + n);
 }
 #undef FK_LESS
-#ifndef DET_SEL_THREADS_BATCH
 #define DET_SEL_THREADS_BATCH 512
-#endif
-#ifndef DET_SEL_MIN_WAVES
 #define DET_SEL_MIN_WAVES 4          // wavefronts per SIMD the batch instance is compiled for (register cap 512 / this)
-#endif
 #define DET_SORT_CAP 512        // corners of a cell that can enter the emulated sort (non-adjacent after NMS: <= 32 x 32 / 2 for cs = 64, halved again by N3)
 
 // MODE 0 = FAST scores (bytes), 1 = min-eigenvalue (floats); a cell row (<= MAXROW * CHUNKS columns) is held in registers
@@ -1590,7 +1581,7 @@ static int detect_batch(ov2_ctx *ctx, int mode, const ov2_pyr *pyr, int cell, co
     // Passes of `chunk` images share the response / candidate scratch.  More than one pass: TWO scratch sets of half a chunk, the passes
     // alternating between the context's stream and an auxiliary one -- the selection sweep of a pass (a dependency chain: two work-groups
     // per CU, the vector units nearly idle) then runs beside the response kernel of the next pass (issue-bound) instead of between two of them
-    const bool two = DET_TWO_STREAMS && items > DET_CHUNK / 2;
+    const bool two = items > DET_CHUNK / 2;
     const int chunk = two ? DET_CHUNK / 2 : std::min(items, DET_CHUNK);
     const size_t map_bytes = (size_t)ncells * npx * (mode == 0 ? 1 : 4);
     const size_t set_bytes = (((size_t)chunk * map_bytes + 255) & ~(size_t)255) +

@@ -26,9 +26,7 @@
 #define GFTT_MAX_CORNERS 4096          // points one pass may accept (the walk's LDS list); nb2detect above -> OV2_EUNSUPPORTED
 #define GFTT_GRID_MAX 8192             // cells of the walk's LDS grid (the cell side grows past minDistance until it fits)
 #define GFTT_MAX_RADIUS 63             // d_circle_halfwidths' table
-#ifndef GFTT_SCRATCH_BUDGET
 #define GFTT_SCRATCH_BUDGET (256ull << 20)    // bytes of per-item scratch a chunk may use (at least one item)
-#endif
 
 // per item, per call (device)
 struct GfttItem {

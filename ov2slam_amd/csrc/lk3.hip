@@ -41,12 +41,8 @@ struct LK3Params {
 #define L3_WIN 9
 #define L3_RPL 3                      // window rows per lane
 #define L3_KPW 20                     // keypoints per wavefront
-#ifndef L3_WAVES
 #define L3_WAVES 1                    // wavefronts per workgroup (no workgroup-level cooperation: small groups balance best)
-#endif
-#ifndef L3_MIN_WAVES_PER_EU
 #define L3_MIN_WAVES_PER_EU 4
-#endif
 #define L3_KPB (L3_KPW * L3_WAVES)     // keypoints per workgroup
 #define L3_IROWS (L3_WIN + 3)         // template neighbourhood rows  (12)
 #define L3_JROWS 16                   // search neighbourhood rows
@@ -62,13 +58,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // global_load_dwordx4 needs dword alignment only
 // LDS reads at BYTE granularity (gfx950 serves unaligned ds_read_b96): the twelve bytes p[0..11] of a staged row from the window's
 // own first column -- no v_alignbyte to shift the row into place, one LDS instruction per row instead of two
-#ifndef L3_UNALIGNED_LDS
-#define L3_UNALIGNED_LDS 1
-#endif
 typedef uint32_t u32x3_a1 __attribute__((ext_vector_type(3), aligned(1)));
-#ifndef L3_UNALIGNED_GLOBAL
-#define L3_UNALIGNED_GLOBAL 1
-#endif
 typedef uint32_t u32x4_a1 __attribute__((ext_vector_type(4), aligned(1)));
 
 // ---- packed 16-bit helpers (carrier type: uint32_t = two 16-bit fields, element 0 in the low half) ----
@@ -90,18 +80,6 @@ __device__ __forceinline__ int dot2r(uint32_t a, uint32_t b)
     int r;
     const int c256 = __builtin_amdgcn_readfirstlane(256);
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c256));
-    return r;
-}
-#ifndef L3_DOT2H_ASM
-#define L3_DOT2H_ASM 0
-#endif
-#define DOT2H(a, b) (L3_DOT2H_ASM ? dot2h((a), (b)) : dot2((a), (b), 1 << 15))
-// a.lo * b.lo + a.hi * b.hi + 2^15 (scalar-register accumulator like dot2r): the derivative taps, whose inputs carry a factor 4
-__device__ __forceinline__ int dot2h(uint32_t a, uint32_t b)
-{
-    int r;
-    const int c = __builtin_amdgcn_readfirstlane(1 << 15);
-    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
     return r;
 }
 // A v_perm_b32 selector in a scalar register: VOP3 takes no literal here, and left to itself the compiler keeps each selector
@@ -182,9 +160,6 @@ __device__ __forceinline__ void l3_lds_sync()
 // One row = one 16-byte + one 4-byte request (a lane's row never coalesces with its neighbours': the number of
 // L1 line look-ups, not bytes, bounds this phase).  Rows are addressed from one 64-bit base with a constant
 // stride; the clamp into the padded buffer is only evaluated when some keypoint of the wavefront needs it.
-#ifndef OV2_LK3_KO
-#define OV2_LK3_KO 0
-#endif
 template <bool CLAMP>
 __device__ __forceinline__ void l3_fetch_J_rows(uint32_t *slot, const uint8_t *jroi, const L3Lv &LJ, int xa, uint32_t sh, int jy0, int sub)
 {
@@ -201,19 +176,9 @@ __device__ __forceinline__ void l3_fetch_J_rows(uint32_t *slot, const uint8_t *j
                 y = y < -LJ.pady ? -LJ.pady : (y > LJ.h + LJ.pady - 1 ? LJ.h + LJ.pady - 1 : y);   // rows beyond the buffer are never consumed
                 p = jroi + (long long)y * LJ.img_pitch + xa;
             }
-            if (OV2_LK3_KO & 2) p = jroi + sub * 64 + k * 32;
-#if L3_UNALIGNED_GLOBAL
             // the row's sixteen bytes from its own first column: ONE request at byte granularity (the memory pipeline serves
             // unaligned dwordx4), nothing to shift
             *(u32x4 *)(dst + 12 * k) = *(const u32x4_a1 *)(p + sh);
-#else
-            const u32x4 lo = *(const u32x4_a4 *)p;
-            const uint32_t hi = *(const uint32_t *)(p + 16);
-            u32x4 o;
-            o.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, sh); o.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, sh);
-            o.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, sh); o.w = __builtin_amdgcn_alignbyte(hi, lo.w, sh);
-            *(u32x4 *)(dst + 12 * k) = o;
-#endif
         }
     }
 }
@@ -223,7 +188,6 @@ __device__ __forceinline__ void l3_fetch_J(uint32_t *slot, const uint8_t *jroi, 
     const int xa = jx0 & ~3;
     const uint32_t sh = (uint32_t)(jx0 - xa);
     const bool outside = jy0 < -LJ.pady || jy0 + L3_JROWS - 1 > LJ.h + LJ.pady - 1;
-    if (OV2_LK3_KO & 16) return;
     if (__builtin_amdgcn_ballot_w64(outside) == 0) l3_fetch_J_rows<false>(slot, jroi, LJ, xa, sh, jy0, sub);
     else l3_fetch_J_rows<true>(slot, jroi, LJ, xa, sh, jy0, sub);
 }
@@ -295,8 +259,7 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 y = y < -LI.pady ? -LI.pady : (y > LI.h + LI.pady - 1 ? LI.h + LI.pady - 1 : y);     // only feeds derivatives of out-of-image rows (= 0)
                 p = iroi + (long long)y * LI.img_pitch + ixa;
             }
-            if (OV2_LK3_KO & 1) p = iroi + sub * 64 + k * 16;
-            if (!(OV2_LK3_KO & 8)) *(u32x4 *)(dst + 4 * sub + 12 * k) = *(const u32x4_a4 *)p;
+            *(u32x4 *)(dst + 4 * sub + 12 * k) = *(const u32x4_a4 *)p;
         }
     };
     const uint32_t *tsrc;                                           // template source rows (16 B each), first needed byte at `ish`
@@ -347,13 +310,8 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
         // soon as derivative rows j, j+1 exist.  E[m][i] = (p[2i], p[2i+1]) of image row m;
         // DX[d][i] = (dx[2i], dx[2i+1]) with column c <-> ipx + c.
         auto load_row = [&](int m, uint32_t (&e)[6]) {
-#if L3_UNALIGNED_LDS
             const u32x3_a1 w = *(const u32x3_a1 *)((const uint8_t *)(tsrc + 4 * (r0 + m)) + ish);
             const uint32_t d0 = w.x, d1 = w.y, d2 = w.z;
-#else
-            const u32x4 w = *(const u32x4 *)(tsrc + 4 * (r0 + m));
-            const uint32_t d0 = __builtin_amdgcn_alignbyte(w.y, w.x, ish), d1 = __builtin_amdgcn_alignbyte(w.z, w.y, ish), d2 = __builtin_amdgcn_alignbyte(w.w, w.z, ish);
-#endif
             e[0] = bytes01(d0); e[1] = bytes23(d0); e[2] = bytes01(d1); e[3] = bytes23(d1); e[4] = bytes01(d2); e[5] = bytes23(d2);
         };
         // derivative positions outside the image are 0 (rare: only for windows overlapping the image border)
@@ -399,8 +357,8 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 const uint32_t xb = (x & 1) ? odd_pair(dxb[(x >> 1) + 1], dxb[x >> 1]) : dxb[x >> 1];
                 const uint32_t yt = (x & 1) ? odd_pair(dyt[(x >> 1) + 1], dyt[x >> 1]) : dyt[x >> 1];
                 const uint32_t yb = (x & 1) ? odd_pair(dyb[(x >> 1) + 1], dyb[x >> 1]) : dyb[x >> 1];
-                xv = dot2(xt, W01, DOT2H(xb, W23));                 // 4 S + 2^15: descaled by hi16_pair
-                yv = dot2(yt, W01, DOT2H(yb, W23));
+                xv = dot2(xt, W01, dot2(xb, W23, 1 << 15));         // 4 S + 2^15: descaled by hi16_pair
+                yv = dot2(yt, W01, dot2(yb, W23, 1 << 15));
             };
 #pragma unroll
             for (int t = 0; t < 5; t++) {
@@ -418,10 +376,6 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
             }
         };
         uint32_t E0[6], E1[6], E2[6], E3[6], DXa[5], DYa[5], DXb[5], DYb[5];
-        if (OV2_LK3_KO & 4) {
-            for (int j = 0; j < L3_RPL; j++) for (int t = 0; t < 5; t++) { T.X[j][t] = slot[4 * r0 + j * 5 + t] >> 1; T.Y[j][t] = T.X[j][t] >> 1; }
-            s11 = s22 = 1 << 28; s12 = 0;
-        } else {
         // two straight-line instances, with and without the border masks: a border branch inside every derivative row
         // let the window rows sink below the last of them, which held all four derivative rows and the image rows at once
         auto build = [&](auto bt) {
@@ -439,7 +393,6 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
         };
         if (any_border) build(std::true_type());
         else build(std::false_type());
-        }
     }
     // per-lane partials: 27 * 4080^2 = 4.5e8 < 2^31
     const float A11 = l3_sum3_f32(s11, sub) * FLT_SCALE;
@@ -485,21 +438,11 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 }
                 // source rows iny + 3 sub + m (m = 0..3), bytes [inx, inx + WIN]
                 uint32_t P[4][9];                                              // P[m][x] = (p[x], p[x+1])
-#if L3_UNALIGNED_LDS
                 const uint8_t *s0 = (const uint8_t *)(slot + jb + 4 * (oy + 3 * sub)) + ox;
-#else
-                const uint32_t sh = (uint32_t)(ox & 3);
-                const uint32_t *s0 = slot + jb + 4 * (oy + 3 * sub) + (ox >> 2);
-#endif
 #pragma unroll
                 for (int m = 0; m < 4; m++) {
-#if L3_UNALIGNED_LDS
                     const u32x3_a1 w = *(const u32x3_a1 *)(s0 + 16 * m);
                     const uint32_t d0 = w.x, d1 = w.y, d2 = w.z;
-#else
-                    const uint32_t a0 = s0[4 * m], a1 = s0[4 * m + 1], a2 = s0[4 * m + 2], a3 = s0[4 * m + 3];
-                    const uint32_t d0 = __builtin_amdgcn_alignbyte(a1, a0, sh), d1 = __builtin_amdgcn_alignbyte(a2, a1, sh), d2 = __builtin_amdgcn_alignbyte(a3, a2, sh);
-#endif
                     P[m][0] = bytes01(d0); P[m][2] = bytes23(d0); P[m][4] = bytes01(d1); P[m][6] = bytes23(d1); P[m][8] = bytes01(d2);
                     P[m][1] = odd_pair(P[m][2], P[m][0]); P[m][3] = odd_pair(P[m][4], P[m][2]);
                     P[m][5] = odd_pair(P[m][6], P[m][4]); P[m][7] = odd_pair(P[m][8], P[m][6]);

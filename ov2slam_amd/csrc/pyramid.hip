@@ -33,13 +33,10 @@ __device__ __forceinline__ int reflect101(int p, int len)
 // Only ROI pixels are written here; the REFLECT_101 borders are filled by k_pyr_border (tiny).
 // HBM traffic per level-0 pixel: 1 B read, 1 B + 0.25 B written -- the reference's pyramid also
 // stores 4 B/px of derivatives, which this design never materialises.
-// Knock-out timing (PYR_KO) of the first version (128x32 tiles, 4x4 pixels per thread, 2-byte stores) showed
+// Knock-out timing of the first version (128x32 tiles, 4x4 pixels per thread, 2-byte stores) showed
 // three additive costs -- load misses 80 us, 2-byte stores 50 us, LDS traffic + launch 46 us of 176 us at
 // 1024 x 752x480 -- and no arithmetic cost at all: a latency-bound kernel.  Hence wider work per thread (twice
 // the bytes in flight, dword stores, 3.5 instead of 5.25 LDS dwords per output).
-#ifndef PYR_KO
-#define PYR_KO 0                     // knock-out timing experiments (1: loads hit one line, 2: no stores, 4: no arithmetic)
-#endif
 #define PT_W 256
 #define PT_H 32                      // (64 = two row sets per thread, twice the bytes in flight: measured 3 % slower)
 #define PT_LDS_DW 66                 // (PT_W + 8) / 4 dwords per tile row: columns x0-4 .. x0+259
@@ -100,8 +97,7 @@ __global__ __launch_bounds__(256) void k_pyr_level(PyrDesc P, int level, const u
                 // the stencils reach 2 columns / rows past the ROI, the clamps start at win >= 3)
                 const int cy = min(max(gy, -P.win), L.h + P.win - 1);
                 const int cx = min(gx, L.w + P.win) & ~3;                       // [cx, cx+8) stays inside the row (pitch slack 8)
-                if (PYR_KO & 1) v = *(const pyr_u32x2_a4 *)(src + (tid & 15) * 8);
-                else v = *(const pyr_u32x2_a4 *)(src + cy * L.img_pitch + cx);
+                v = *(const pyr_u32x2_a4 *)(src + cy * L.img_pitch + cx);
             }
         }
         stage[i] = v;
@@ -163,8 +159,8 @@ __global__ __launch_bounds__(256) void k_pyr_level(PyrDesc P, int level, const u
             const uint32_t h1 = __builtin_amdgcn_udot4(q0, 0x04060401u, __builtin_amdgcn_udot4(q1, 0x00000001u, 0u, false), false);
             const uint32_t h2 = __builtin_amdgcn_udot4(l2, 0x04060401u, __builtin_amdgcn_udot4(q1, 0x00010000u, 0u, false), false);
             const uint32_t h3 = __builtin_amdgcn_udot4(q1, 0x04060401u, __builtin_amdgcn_udot4(c, 0x00000001u, 0u, false), false);
-            hp[r][0] = (PYR_KO & 4) ? q0 : (h0 | (h1 << 16));
-            hp[r][1] = (PYR_KO & 4) ? q1 : (h2 | (h3 << 16));
+            hp[r][0] = h0 | (h1 << 16);
+            hp[r][1] = h2 | (h3 << 16);
         }
         typedef unsigned short pu16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -177,11 +173,10 @@ __global__ __launch_bounds__(256) void k_pyr_level(PyrDesc P, int level, const u
                 const pu16x2 c2 = __builtin_bit_cast(pu16x2, hp[r + 2][k]), c1 = __builtin_bit_cast(pu16x2, hp[r + 1][k]), c3 = __builtin_bit_cast(pu16x2, hp[r + 3][k]);
                 const pu16x2 c0 = __builtin_bit_cast(pu16x2, hp[r][k]), c4 = __builtin_bit_cast(pu16x2, hp[r + 4][k]);
                 const pu16x2 v = (c2 * (unsigned short)6 + (c1 + c3) * (unsigned short)4 + c0 + c4 + (unsigned short)128) >> (unsigned short)8;
-                vv[k] = (PYR_KO & 4) ? hp[r][k] ^ hp[r + 4][k] : __builtin_bit_cast(uint32_t, v);
+                vv[k] = __builtin_bit_cast(uint32_t, v);
             }
             const uint32_t out = __builtin_amdgcn_perm(vv[1], vv[0], 0x06040200u);    // bytes (v0, v1, v2, v3)
             if (FUSE_BORDER) otile[2 * ty + oy][tx] = out;
-            if ((PYR_KO & 2) && out != 0x12345678u) continue;
             uint8_t *d = nroi + (Y + oy) * N.img_pitch + X;                         // X % 4 == 0, ROI origin 16-byte aligned
             if (X + 3 < N.w) {
                 *(uint32_t *)d = out;
