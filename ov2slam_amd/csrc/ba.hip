@@ -25,49 +25,27 @@
 //   * Step acceptance, radius update, tolerances and the "last evaluated point" bookkeeping
 //     (chi2err_/isdepthpositive_ caching) follow Ceres exactly (k_ba_iter_begin,
 //     k_ba_candidate, k_ba_decide).
+//
+// Parts (one translation unit): ba_core.hpp -- the control block and the trust-region rules, shared with struct_ba.hip;
+// ba_chol.hpp -- the Cholesky kernels of the reduced system; ba_problem.hpp -- the device-resident problem (ba_create).
+// This file: the kernels of the LM loop, the host LM driver (ba_lm_loop, ba_run, ba_run_batch), the localBA protocol.
 #include "common.hpp"
 #include <math.h>
 #include <float.h>
 #include <algorithm>
 #include <stdlib.h>
 #include <vector>
-#include <atomic>
-#include <condition_variable>
 #include <functional>
 #include <mutex>
 #include <chrono>
-#include <thread>
 
 #pragma clang fp contract(fast)   // BA parity is 1e-4 relative in fp64: FMA contraction is fine here
+#include "ba_core.hpp"           // (after the pragma: the shared functions are compiled with contraction here)
 
 #define BA_TILE 32
 #define BA_MAX_NFP 6144     // 1024 optimised keyframes: H, G, S are dense nfp x nfp doubles (302 MB each at the cap)
 
 #define BA_PART_MAX 2048
-#define BA_TRACE_CAP 64
-typedef ov2_ba_iter BAIterRec;   // the iteration summary Ceres pushes into Solver::Summary::iterations (OV2_OPT_BA_TRACE)
-struct BACtl {
-    // accumulators
-    double cost_acc;
-    double acc1, acc2, acc3;      // sum_l y_l g'_l ; sum_l (2 y_l s_l t_l + s_l^2 ete_l y_l^2) ; sum_l c_l t_l^2
-    double acc_sn, acc_xn;        // landmark part of |x - candidate|^2 and |candidate|^2 (k_ba_backsub, inverse-depth form)
-    int bad_step;                 // a non-finite landmark step (k_ba_backsub)
-    int reuse_now;                // reuse_diag as this iteration found it (k_ba_iter_begin sets reuse_diag = 1 when it is done)
-    unsigned long long dbg[8];    // phase clocks of the last k_ba_cholesky (wall_clock64 ticks)
-    // LM / TR state
-    double radius, decrease_factor;
-    double x_cost, cand_cost, model_cost_change, x_norm, minimum_cost, initial_cost, gmax;
-    double ev_min, ev_cur, ev_ref, ev_cand, ev_acc_ref, ev_acc_cand;
-    int ev_nonmono;
-    int reuse_diag;
-    int iteration, n_steps, n_success, num_invalid, termination, done;
-    int need_lin, fresh_lin, step_successful, step_valid, lin_fail, scaled;
-    // OV2_OPT_BA_TRACE: the summary of the iteration under way and where finished ones go (NULL: no trace)
-    BAIterRec cur;
-    BAIterRec *trace;
-    int n_trace;
-};
-
 struct BADev {                    // device pointers + sizes (passed by value to kernels)
     int n_kf, n_lm, n_act, nf, nfp;
     int *flag_h;                  // pinned host word: 2 * (iteration whose outcome is known) + done, written by k_ba_decide
@@ -177,135 +155,7 @@ __device__ __forceinline__ double d_lm_c(const BADev &D, int l, double radius, i
     return s * s / (s * s * e + dg / radius);
 }
 
-struct BAOpt {
-    int max_iter;
-    double ftol, gtol, ptol, max_radius, min_radius, min_diag, max_diag, min_rel_decrease;
-    int jacobi, max_invalid;
-};
-
-// ---------------------------------------------------------------------------------- trust-region bookkeeping (one thread)
-// The three scalar state machines of Ceres' TrustRegionMinimizer as pure functions on the control block, shared by the
-// multi-kernel solver (k_ba_iter_begin / k_ba_candidate / k_ba_decide) and the single-kernel pose-only solver (k_pnp_solve).
-__device__ __forceinline__ void d_ctl_iter_begin(BACtl &cl, const BAOpt &O, int fresh, double gmax)
-{
-    BACtl *ctl = &cl;
-    if (fresh) {
-        ctl->gmax = gmax;
-        ctl->x_cost = ctl->cost_acc;
-        ctl->cost_acc = 0;
-        if (!ctl->scaled) {             // iteration zero
-            ctl->scaled = 1;
-            ctl->initial_cost = ctl->x_cost; ctl->minimum_cost = ctl->x_cost;
-            ctl->ev_min = ctl->ev_cur = ctl->ev_ref = ctl->ev_cand = ctl->x_cost;
-            ctl->ev_acc_ref = ctl->ev_acc_cand = 0; ctl->ev_nonmono = 0;
-        }
-        ctl->fresh_lin = 0;
-        ctl->reuse_diag = 0;
-        // IterationZero / HandleSuccessfulStep -> EvaluateGradientAndJacobian: cost and gradient norm of the new point
-        ctl->cur.cost = ctl->x_cost; ctl->cur.gradient_max_norm = gmax;
-        if (ctl->cur.iteration == 0) { ctl->cur.step_is_valid = 1; ctl->cur.step_is_successful = 1; }
-    }
-    // FinalizeIterationAndCheckIfMinimizerCanContinue
-    if (ctl->step_successful) {
-        ctl->n_success++;
-        if (ctl->x_cost < ctl->minimum_cost) ctl->minimum_cost = ctl->x_cost;
-    }
-    ctl->cur.trust_region_radius = ctl->radius;
-    if (ctl->trace) { if (ctl->n_trace < BA_TRACE_CAP) ctl->trace[ctl->n_trace] = ctl->cur; ctl->n_trace++; }
-    if (ctl->iteration >= O.max_iter) { ctl->termination = OV2_TERM_NO_CONVERGENCE; ctl->done = 1; }
-    else if (ctl->step_successful && ctl->gmax <= O.gtol) { ctl->termination = OV2_TERM_GRADIENT_TOL; ctl->done = 1; }
-    else if (ctl->radius <= O.min_radius) { ctl->termination = OV2_TERM_MIN_RADIUS; ctl->done = 1; }
-    else {
-        ctl->iteration++;
-        ctl->step_successful = 0;
-        ctl->step_valid = 0;
-        ctl->lin_fail = 0;
-        ctl->n_steps++;
-        ctl->acc1 = 0; ctl->acc2 = 0; ctl->acc3 = 0; ctl->acc_sn = 0; ctl->acc_xn = 0; ctl->bad_step = 0;
-        // the next summary: iteration number, the gradient norm of the last accepted point (trust_region_minimizer.cc:87-93, :124-126)
-        ctl->cur.iteration = ctl->iteration; ctl->cur.step_is_valid = 0; ctl->cur.step_is_successful = 0;
-        ctl->cur.cost = 0; ctl->cur.cost_change = 0; ctl->cur.step_norm = 0; ctl->cur.relative_decrease = 0;
-    }
-}
-
-// returns 1 when the step is valid (model cost change > 0); P1 = y . g'_f, P2 = y^T H'_pp y of the pose part
-__device__ __forceinline__ int d_ctl_candidate(BACtl &cl, const BAOpt &O, int ok, double P1, double P2)
-{
-    BACtl *ctl = &cl;
-    int valid = 0;
-    if (ok) {
-        // model_cost_change = -(J step).(r + J step / 2) with step = -y  ==  y.g' - y^T H' y / 2
-        const double mcc = (P1 + ctl->acc1) - 0.5 * (P2 + ctl->acc3 + ctl->acc2);
-        ctl->model_cost_change = mcc;
-        valid = mcc > 0.0;
-    }
-    if (!valid) {
-        // HandleInvalidStep (trust_region_minimizer.cc:436-459)
-        if (++ctl->num_invalid >= O.max_invalid) { ctl->termination = OV2_TERM_INVALID_STEPS; ctl->done = 1; }
-        else { ctl->radius = ctl->radius / ctl->decrease_factor; ctl->decrease_factor *= 2.0; ctl->reuse_diag = 1; }
-        ctl->step_valid = 0;
-        ctl->cur.cost = ctl->x_cost;                       // "a step of length zero and no progress" (:476-484)
-    } else {
-        ctl->num_invalid = 0;
-        ctl->step_valid = 1;
-        ctl->cur.step_is_valid = 1;
-    }
-    return valid;
-}
-
-// returns 1 when the candidate is accepted; SN = |x - candidate|^2, XN = |candidate|^2 over the variable blocks
-__device__ __forceinline__ int d_ctl_decide(BACtl &cl, const BAOpt &O, double SN, double XN)
-{
-    BACtl *ctl = &cl;
-    int accept = 0;
-    const double cand = ctl->cost_acc;
-    ctl->cost_acc = 0;
-    ctl->cand_cost = cand;
-    ctl->cur.step_norm = sqrt(SN); ctl->cur.cost_change = ctl->x_cost - cand;
-    if (sqrt(SN) <= O.ptol * (ctl->x_norm + O.ptol)) { ctl->termination = OV2_TERM_PARAMETER_TOL; ctl->done = 1; }
-    else if (fabs(ctl->x_cost - cand) <= O.ftol * ctl->x_cost) { ctl->termination = OV2_TERM_FUNCTION_TOL; ctl->done = 1; }
-    else {
-        const double mcc = ctl->model_cost_change;
-        const double r1 = (ctl->ev_cur - cand) / mcc, r2 = (ctl->ev_ref - cand) / (ctl->ev_acc_ref + mcc);
-        const double rel = fmax(r1, r2);
-        ctl->cur.relative_decrease = rel;
-        if (rel > O.min_rel_decrease) {
-            accept = 1;
-            ctl->cur.step_is_successful = 1;               // (cost and gradient norm: the next k_ba_iter_begin, from the fresh linearisation)
-            ctl->x_norm = sqrt(XN);
-            ctl->step_successful = 1;
-            ctl->need_lin = 1;
-            // LevenbergMarquardtStrategy::StepAccepted
-            const double t = 2.0 * rel - 1.0;
-            ctl->radius = fmin(O.max_radius, ctl->radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-            ctl->decrease_factor = 2.0; ctl->reuse_diag = 0;
-            // TrustRegionStepEvaluator::StepAccepted (max_consecutive_nonmonotonic_steps = 0)
-            ctl->ev_cur = cand; ctl->ev_acc_cand += mcc; ctl->ev_acc_ref += mcc;
-            if (ctl->ev_cur < ctl->ev_min) { ctl->ev_min = ctl->ev_cur; ctl->ev_nonmono = 0; ctl->ev_cand = ctl->ev_cur; ctl->ev_acc_cand = 0; }
-            else { ctl->ev_nonmono++; if (ctl->ev_cur > ctl->ev_cand) { ctl->ev_cand = ctl->ev_cur; ctl->ev_acc_cand = 0; } }
-            if (ctl->ev_nonmono == 0) { ctl->ev_ref = ctl->ev_cand; ctl->ev_acc_ref = ctl->ev_acc_cand; }
-        } else {
-            ctl->radius = ctl->radius / ctl->decrease_factor; ctl->decrease_factor *= 2.0; ctl->reuse_diag = 1;
-            ctl->cur.cost = cand;                          // the rejected candidate's cost (:119-127)
-        }
-    }
-    return accept;
-}
-
 // ---------------------------------------------------------------------------------- algebra
-__device__ __forceinline__ void d_quat_to_R(const double *q, double *R)
-{
-    double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double n = sqrt(x * x + y * y + z * z + w * w);
-    x /= n; y /= n; z /= n; w /= n;
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
 // T' = Exp(delta) * T   (se3left_parametrization.hpp:45-57, Sophus se3.hpp:763-784, so3.hpp:585-621)
 __device__ void d_se3_left_plus(const double *pose, const double *a, double *out)
 {
@@ -351,22 +201,6 @@ __device__ void d_se3_left_plus(const double *pose, const double *a, double *out
         out[i] = V[3 * i] * a[0] + V[3 * i + 1] * a[1] + V[3 * i + 2] * a[2] +
                  Re[3 * i] * pose[0] + Re[3 * i + 1] * pose[1] + Re[3 * i + 2] * pose[2];
     out[3] = r[0] / rn; out[4] = r[1] / rn; out[5] = r[2] / rn; out[6] = r[3] / rn;
-}
-
-__device__ __forceinline__ void d_pose_to_RT(const double *pose, double *RT)
-{
-    d_quat_to_R(pose + 3, RT);
-    RT[9] = pose[0]; RT[10] = pose[1]; RT[11] = pose[2];
-}
-
-// Huber (loss_function.cc:48-62) -> (rho, rho')
-__device__ __forceinline__ void d_huber(double a, double s, double &rho0, double &rho1)
-{
-    if (a > 0 && s > a * a) {
-        const double r = sqrt(s);
-        rho0 = 2.0 * a * r - a * a;
-        rho1 = fmax(DBL_MIN, a / r);
-    } else { rho0 = s; rho1 = 1.0; }
 }
 
 // One residual block.  RTa / RTo: anchor / observer (Rwc | t).  Returns the depth-positive flag.
@@ -499,26 +333,6 @@ __device__ __forceinline__ int d_residual_xyz(const BADev &D, int type, const do
         Jp[6 * i + 5] = a * X[1] - b * X[0];
     }
     return dp;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup (<= 16 wavefronts); result valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *s_part)
-{
-    v = wave_sum(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
-    if (lane == 0) s_part[wave] = v;
-    __syncthreads();
-    double t = 0;
-    if (threadIdx.x == 0) for (int w = 0; w < nw; w++) t += s_part[w];
-    return t;
 }
 
 // three sums (or, MAX = true, maxima) over the workgroup with two barriers; results valid in thread 0.  The
@@ -1141,178 +955,7 @@ __device__ __forceinline__ void b_ba_schur_gemm(const BADev &D, int ntiles, int 
 __global__ __launch_bounds__(256) void k_ba_schur_gemm(BADev D, int ntiles, int lm_per_split) { b_ba_schur_gemm(D, ntiles, lm_per_split); }
 __global__ __launch_bounds__(256) void k_ba_schur_gemm_B(const BADev *__restrict__ arr) { const BADev &D = arr[blockIdx.z]; if ((int)blockIdx.x >= D.g_nupper || (int)blockIdx.y >= D.g_ksplit) return; b_ba_schur_gemm(D, D.g_ntiles, D.g_lmps); }
 
-// ---------------------------------------------------------------------------------- reduced system (1 block)
-// S = s_i s_j (H_ij - G_ij) + delta_ij diag_i / radius ; rhs = s_i (b_i - v_i); blocked Cholesky; solve.
-// Right-looking, 32-wide panels: the diagonal block is factored in LDS by one wavefront, the panel
-// below it is solved row-per-thread against that block and parked in LDS, and the trailing update
-// reads the panel from LDS only (each S entry is touched once per panel).
-#define CH_NB 32
-#define CH_GRP 8           // columns of the diagonal block published per work-group barrier (pipelined panel solve): 2 / 4 / 8 -> 102 / 89 / 87 us
-#define CH_LDP 33          // padded leading dimension (doubles) of the LDS panel rows
-// knock-out timings of k_ba_cholesky's phases (no MFMA, no loads of the old tile values, no tile stores, no LDS operand reads, a
-// quarter of the panel solve's terms): profiles/archive/r4_ba_dead_ends.txt
-#define CH_MAX_LDS_N 415   // k_ba_cholesky (512 threads, six panel wavefronts): the right-hand side rides as a panel row, n - 32 + 1 <= 384; larger: HBM path
-// dynamic LDS of k_ba_cholesky: diagonal block, solution vector, panel (rows rounded up to whole 16-row MFMA tiles: the trailing
-// update reads its operand rows unpredicated)
-static inline size_t chol_lds_bytes(int nf, int nfp) { return 8 * ((size_t)CH_NB * CH_LDP + 2 * (size_t)nfp + (size_t)((std::max(0, nf - CH_NB) + 15) & ~15) * CH_LDP) + 64; }
-
-// The two triangular solves L y = rhs, L^T x = y on the factor in S (HBM) with the inverse diagonal blocks in Linv; yv (LDS, nfp
-// doubles) holds rhs on entry and x on return, L11 is a CH_NB x CH_LDP LDS scratch.  One work-group.
-__device__ __forceinline__ void chol_trisolve(const BADev &D, double *L11, double *yv, double (*s_red)[33], bool forward_done = false)
-{
-    const int n = D.nf, ld = D.nfp, tid = threadIdx.x, nt = blockDim.x;
-    const double *S = D.S, *Linv = D.Linv;
-    // forward substitution  L y = rhs, left-looking by blocks:  y_blk = Linv_blk (b_blk - L[blk, 0:k0] y[0:k0])
-    // (forward_done: yv already holds y -- k_ba_cholesky carries the right-hand side through the factorisation as one more panel row)
-    const int tr = tid >> 5, tcn = tid & 31, ngr = nt >> 5;  // ngr groups of 32 partial-sum threads
-    for (int k0 = 0; k0 < n && !forward_done; k0 += CH_NB) {
-        const int nb = min(CH_NB, n - k0);
-        for (int r = tr; r < CH_NB; r += ngr) {
-            double part = 0;
-            if (r < nb) for (int k = tcn; k < k0; k += 32) part += S[(long long)(k0 + r) * ld + k] * yv[k];
-            s_red[r][tcn] = part;
-        }
-        for (int e = tid; e < CH_NB * CH_NB; e += nt) L11[(e >> 5) * CH_LDP + (e & 31)] = Linv[(long long)(k0 / CH_NB) * CH_NB * CH_NB + e];
-        __syncthreads();
-        if (tid < CH_NB) {
-            double r = 0;
-            for (int q = 0; q < 32; q++) r += s_red[tid][q];
-            s_red[tid][32] = tid < nb ? yv[k0 + tid] - r : 0.0;
-        }
-        __syncthreads();
-        if (tid < nb) {
-            double r = 0;
-            for (int k = 0; k <= tid; k++) r += L11[tid * CH_LDP + k] * s_red[k][32];
-            yv[k0 + tid] = r;
-        }
-        __syncthreads();
-    }
-    // backward substitution  L^T x = y, right-looking by blocks, last block first:  x_blk = Linv_blk^T y_blk, then
-    // y[0:k0] -= L[blk, 0:k0]^T x_blk.  Nothing the loop loads depends on x: thread t keeps column t of the block row L[blk, 0:k0]
-    // (32 doubles, coalesced over t) and its share of Linv_blk in registers, requested one block ahead, so that a block costs two
-    // barriers and 2 x 32 FMAs instead of a dependent walk over L in L2 with three barriers (round 4: 44 -> ~12 us at n = 300).
-    if (n <= nt && nt >= 256) {
-        const int nblk = (n + CH_NB - 1) / CH_NB;
-        constexpr int NINV = CH_NB * CH_NB / 256;                // Linv doubles per thread at the smallest work-group (256)
-        double cur[CH_NB], nxt[CH_NB], winv[NINV], ninv[NINV];
-        auto load_rows = [&](int k0, int nb, double (&v)[CH_NB]) {
-#pragma unroll
-            for (int i = 0; i < CH_NB; i++) v[i] = (tid < k0 && i < nb) ? S[(long long)(k0 + i) * ld + tid] : 0.0;
-        };
-        auto load_inv = [&](int blk, double (&w)[NINV]) {
-#pragma unroll
-            for (int u = 0; u < NINV; u++) { const int e = tid + u * nt; w[u] = e < CH_NB * CH_NB ? Linv[(long long)blk * CH_NB * CH_NB + e] : 0.0; }
-        };
-        load_rows((nblk - 1) * CH_NB, n - (nblk - 1) * CH_NB, cur);
-        load_inv(nblk - 1, winv);
-        for (int blk = nblk - 1; blk >= 0; blk--) {
-            const int k0 = blk * CH_NB, nb = min(CH_NB, n - k0);
-#pragma unroll
-            for (int u = 0; u < NINV; u++) { const int e = tid + u * nt; if (e < CH_NB * CH_NB) L11[(e >> 5) * CH_LDP + (e & 31)] = winv[u]; }
-            if (blk > 0) { load_rows(k0 - CH_NB, CH_NB, nxt); load_inv(blk - 1, ninv); }
-            __syncthreads();                                     // the inverse block is staged, y carries every later block's update
-            if (tid < CH_NB) {
-                double r = 0;
-                for (int k = tid; k < nb; k++) r += L11[k * CH_LDP + tid] * yv[k0 + k];     // Linv^T
-                s_red[tid][32] = tid < nb ? r : 0.0;
-            }
-            __syncthreads();
-            if (tid < nb) yv[k0 + tid] = s_red[tid][32];
-            if (tid < k0) {
-                double acc = yv[tid];
-#pragma unroll
-                for (int i = 0; i < CH_NB; i++) acc -= cur[i] * s_red[i][32];
-                yv[tid] = acc;
-            }
-#pragma unroll
-            for (int i = 0; i < CH_NB; i++) cur[i] = nxt[i];
-#pragma unroll
-            for (int u = 0; u < NINV; u++) winv[u] = ninv[u];
-        }
-        __syncthreads();
-        return;
-    }
-    // (systems wider than the work-group: the large-problem path) left-looking, x_blk = Linv_blk^T (y_blk - L[below, blk]^T x[below])
-    for (int k0 = ((n - 1) / CH_NB) * CH_NB; k0 >= 0; k0 -= CH_NB) {
-        const int nb = min(CH_NB, n - k0);
-        // lanes along the block's columns (coalesced), thread groups along the rows below
-        for (int g = tr; g < 32; g += ngr) {
-            double part = 0;
-            if (tcn < nb) for (int i = k0 + nb + g; i < n; i += 32) part += S[(long long)i * ld + k0 + tcn] * yv[i];
-            s_red[tcn][g] = part;
-        }
-        for (int e = tid; e < CH_NB * CH_NB; e += nt) L11[(e >> 5) * CH_LDP + (e & 31)] = Linv[(long long)(k0 / CH_NB) * CH_NB * CH_NB + e];
-        __syncthreads();
-        if (tid < CH_NB) {
-            double r = 0;
-            for (int q = 0; q < 32; q++) r += s_red[tid][q];
-            s_red[tid][32] = tid < nb ? yv[k0 + tid] - r : 0.0;
-        }
-        __syncthreads();
-        if (tid < nb) {
-            double r = 0;
-            for (int k = tid; k < nb; k++) r += L11[k * CH_LDP + tid] * s_red[k][32];     // Linv^T
-            yv[k0 + tid] = r;
-        }
-        __syncthreads();
-    }
-}
-
-// Backward substitution  L^T x = y  on the factor in S WITHOUT inverse diagonal blocks (k_ba_cholesky, round 4): right-looking by
-// blocks, last block first.  Wavefront 0 solves the block itself -- lane j keeps column j of the 32 x 32 diagonal block in registers
-// and the 32 unknowns go by, last first: x_i = y_i / L_ii in lane i, broadcast by v_readlane, y_j -= L_ij x_i in the lanes j < i --;
-// the other wavefronts then take the block's unknowns out of everything above: thread t keeps column t of the block row L[blk, 0:k0]
-// in registers.  Nothing that is loaded depends on x: both register sets are requested one block ahead.  yv holds y on entry and x on
-// return; rd_all = 1 / L_ii of all n unknowns (kept from the factorisation); needs n - 32 <= blockDim - 64.
-__device__ __forceinline__ void chol_backward_blocks(const BADev &D, double *yv, const double *rd_all, double *s_x)
-{
-    const int n = D.nf, ld = D.nfp, tid = threadIdx.x, lane = tid & 63, t = tid - 64;
-    const bool w0 = tid < 64;
-    const double *S = D.S;
-    const int nblk = (n + CH_NB - 1) / CH_NB;
-    double cur[CH_NB], nxt[CH_NB], nx2[CH_NB];                   // two blocks ahead: a block's own work is ~1 us, its 32 loads per thread ~3 us
-    auto load = [&](int k0, int nb, double (&v)[CH_NB]) {
-        const double *col = S + (long long)k0 * ld + (w0 ? k0 + lane : t);
-        const bool mine = w0 ? lane < nb : t < k0;
-#pragma unroll
-        for (int i = 0; i < CH_NB; i++) v[i] = (mine && i < nb && (!w0 || i > lane)) ? col[(long long)i * ld] : 0.0;   // w0: L[i][lane] of the diagonal block; else L[k0 + i][t]
-    };
-    load((nblk - 1) * CH_NB, n - (nblk - 1) * CH_NB, cur);
-#pragma unroll
-    for (int i = 0; i < CH_NB; i++) nxt[i] = 0.0;
-    if (nblk > 1) load((nblk - 2) * CH_NB, CH_NB, nxt);
-    for (int blk = nblk - 1; blk >= 0; blk--) {
-        const int k0 = blk * CH_NB, nb = min(CH_NB, n - k0);
-#pragma unroll
-        for (int i = 0; i < CH_NB; i++) nx2[i] = 0.0;
-        if (blk > 1) load(k0 - 2 * CH_NB, CH_NB, nx2);
-        __syncthreads();                                         // y carries every later block's update
-        if (w0) {
-            double y = lane < nb ? yv[k0 + lane] : 0.0;
-            const double rd = lane < nb ? rd_all[k0 + lane] : 0.0;
-            int ln = lane;
-            asm volatile("" : "+v"(ln));                             // (keeps the 64 lane masks below out of spilled scalar registers)
-#pragma unroll
-            for (int i = CH_NB - 1; i >= 0; i--) {
-                const double xl = y * rd;
-                const double xi = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xl), i), __builtin_amdgcn_readlane(__double2loint(xl), i));
-                y = ln == i ? xi : (ln < i ? y - cur[i] * xi : y);
-            }
-            if (lane < CH_NB) s_x[lane] = y;
-            if (lane < nb) yv[k0 + lane] = y;
-        }
-        __syncthreads();
-        if (!w0 && t < k0) {
-            double acc = yv[t];
-#pragma unroll
-            for (int i = 0; i < CH_NB; i++) acc -= cur[i] * s_x[i];
-            yv[t] = acc;
-        }
-#pragma unroll
-        for (int i = 0; i < CH_NB; i++) { cur[i] = nxt[i]; nxt[i] = nx2[i]; }
-    }
-    __syncthreads();
-}
+#include "ba_chol.hpp"          // the LDS-panel Cholesky (k_ba_cholesky) and the multi-kernel Cholesky on HBM (k_chol_*)
 
 // lower triangle of S, one thread per entry, many workgroups (latency-bound gathers from H and G)
 __device__ __forceinline__ void b_ba_assemble(const BADev &D)
@@ -1335,297 +978,6 @@ __device__ __forceinline__ void b_ba_assemble(const BADev &D)
 }
 __global__ __launch_bounds__(256) void k_ba_assemble(BADev D) { b_ba_assemble(D); }
 __global__ __launch_bounds__(256) void k_ba_assemble_B(const BADev *__restrict__ arr) { const BADev &D = arr[blockIdx.z]; if ((int)blockIdx.y >= D.nf) return; b_ba_assemble(D); }
-
-__device__ __forceinline__ void b_ba_cholesky(const BADev &D)
-{
-    BACtl *ctl = D.ctl;
-    if (ctl->done) return;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    double *L11 = (double *)smem_raw;                       // CH_NB x CH_LDP : diagonal block / its inverse
-    double *yv = L11 + CH_NB * CH_LDP;                      // nfp
-    double *P = yv + D.nfp;                                 // (n - CH_NB) x CH_LDP : panel below the diagonal block
-    double *rd_all = P + (size_t)((max(0, D.nf - CH_NB) + 15) & ~15) * CH_LDP;   // nfp: reciprocal pivots of all unknowns (backward substitution)
-    const int n = D.nf, ld = D.nfp, tid = threadIdx.x, nt = blockDim.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    __shared__ int s_fail;
-    __shared__ double s_red[32][33];
-    __shared__ double s_rdiag[CH_NB];                        // 1 / L11[j][j] of the current diagonal block
-    __shared__ double s_yk[CH_NB];                           // the block's part of the forward solution (the right-hand side as a panel row)
-    double *S = D.S;
-    // The right-hand side rides through the factorisation as one more row of the panel: solving its block against L11 IS the
-    // forward substitution of that block, and its trailing update (rhs_rest -= P y_blk) replaces the forward pass of the
-    // triangular solves (ten blocks of partial sums over L in L2, three barriers each).  Needs a free panel thread.
-    const bool rhs_row = n - CH_NB + 1 <= nt - 128;
-    // (S was assembled by k_ba_assemble: in here, one workgroup walking the n^2 entries took 85 us of latency)
-    for (int i = tid; i < D.nfp; i += nt) yv[i] = i < n ? D.scale_f[i] * (D.bf[i] - D.v[i]) : 0.0;
-    if (tid == 0) s_fail = 0;
-    __syncthreads();
-
-    unsigned long long tk[6] = {0, 0, 0, 0, 0, 0}, tc = wall_clock64();
-#define CH_TICK(i) do { const unsigned long long t_ = wall_clock64(); tk[i] += t_ - tc; tc = t_; } while (0)
-    for (int k0 = 0; k0 < n; k0 += CH_NB) {
-        const int nb = min(CH_NB, n - k0);
-        const int m = n - k0 - nb;                          // rows below the diagonal block
-        // (a) diagonal block -> LDS (identity padding when nb < 32), panel rows -> LDS (coalesced)
-        for (int e = tid; e < CH_NB * CH_NB; e += nt) {
-            const int i = e >> 5, j = e & 31;
-            double v = (i == j) ? 1.0 : 0.0;
-            if (i < nb && j <= i) v = S[(long long)(k0 + i) * ld + k0 + j];
-            L11[i * CH_LDP + j] = v;
-        }
-        // (eight loads in flight per thread: a load -> LDS store loop pays one L2 round trip per element)
-        for (int e0 = tid; e0 < m * CH_NB; e0 += 8 * nt) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int e = e0 + u * nt, t = e >> 5, j = e & 31;
-                v[u] = (e < m * CH_NB && j < nb) ? S[(long long)(k0 + nb + t) * ld + k0 + j] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int e = e0 + u * nt;
-                if (e < m * CH_NB) P[(e >> 5) * CH_LDP + (e & 31)] = v[u];
-            }
-        }
-        __syncthreads();
-        CH_TICK(0);
-        // (b) + (c), pipelined through LDS.  Wavefront 0 factors the diagonal block (left-looking, lane i owns row i in
-        //     registers, one LDS sync per column) and PUBLISHES its columns in groups of four (L11[.][c], the reciprocal pivots,
-        //     then a work-group barrier; a per-column flag with spinning consumers made the register allocator spill the row
-        //     arrays).  The other wavefronts solve the panel X L11^T = A21 one row per thread and trail the
-        //     factorisation by one column instead of waiting for all 32: the panel solve (9 us per panel as a phase of its own)
-        //     hides behind the 5 us pivot chain.
-        if (wave == 0) {
-            double a[CH_NB];
-#pragma unroll
-            for (int j = 0; j < CH_NB; j++) a[j] = lane < CH_NB ? L11[lane * CH_LDP + j] : 0.0;
-            bool fail = false;
-            // (the lane index of THIS panel step: compared against the 32 column numbers below.  Without the laundering the compiler
-            // hoists all 64 lane masks out of the panel loop and parks them in spilled scalar registers -- 470 v_writelane / 1000
-            // v_readlane with their wait states, on the one wavefront everybody waits for)
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-            // Column c needs  a[c] - sum_{k<c} a[k] L[c][k]  of every row.  Round 4: the terms of the columns published two
-            // barriers ago and earlier (k < 4 (c/4 - 1)) are taken out of the future columns by the HELPER wavefront below, in LDS,
-            // while this wavefront works on the current group of four -- it had 90 instructions per column at c = 20, two thirds of
-            // them those terms, and every other wavefront of the kernel waits for it.  What stays here: the 4 .. 7 terms of the last
-            // two groups (this wavefront's own registers), the same order k = 0, 1, .. as ever (bit-identical factor).  All of them
-            // but the last (k = c-1) are known one column earlier and are accumulated while the previous pivot's rsqrt chain is in
-            // flight -- except for the first column of a group, whose LDS value is final only after the barrier just passed.
-            double pnext = a[0];
-#pragma unroll
-            for (int c = 0; c < CH_NB; c++) {
-                double sacc;
-                if ((c & (CH_GRP - 1)) == 0 && c >= 2 * CH_GRP) {
-#pragma unroll
-                    for (int q = 0; q < CH_GRP; q++) a[c + q] = ln < CH_NB ? L11[ln * CH_LDP + c + q] : 0.0;   // with the helper's terms
-                    sacc = a[c];
-#pragma unroll
-                    for (int k = c - CH_GRP; k < c; k++) sacc -= a[k] * L11[c * CH_LDP + k];
-                } else {
-                    sacc = pnext;
-                    if (c > 0) sacc -= a[c - 1] * L11[c * CH_LDP + c - 1];          // row c of L, final for k < c (broadcast read)
-                }
-                const double d = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(sacc), c), __builtin_amdgcn_readlane(__double2loint(sacc), c));
-                if (c + 1 < CH_NB && !(((c + 1) & (CH_GRP - 1)) == 0 && c + 1 >= 2 * CH_GRP)) {
-                    const int kmin = (c + 1) / CH_GRP >= 1 ? CH_GRP * ((c + 1) / CH_GRP - 1) : 0;
-                    pnext = a[c + 1];
-#pragma unroll
-                    for (int k = kmin; k < c; k++) pnext -= a[k] * L11[(c + 1) * CH_LDP + k];
-                }
-                if (!(d > 0.0) || !isfinite(d)) fail = true;
-                // pivot through 1/sqrt(d): v_rsq_f64 seed (~2^-26) + two Newton steps, then L[c][c] = d r with one Heron
-                // correction and L[i][c] = sacc r -- 9 dependent instructions instead of the ~25 of sqrt() followed by a
-                // division, 32 times per block on the kernel's longest serial chain (and 15 KB less unrolled code)
-                double r = __builtin_amdgcn_rsq(d);
-                r = fma(0.5 * r, fma(-(d * r), r, 1.0), r);
-                r = fma(0.5 * r, fma(-(d * r), r, 1.0), r);
-                double dj = d * r;
-                dj = fma(0.5 * r, fma(-dj, dj, d), dj);
-                const double l = ln == c ? dj : sacc * r;
-                a[c] = ln >= c ? l : 0.0;
-                if (ln < CH_NB) L11[ln * CH_LDP + c] = a[c];                 // (lanes < c write the 0 of the upper triangle: never read)
-                // reciprocal pivot 1 / L[c][c]: r refined by one Newton step of the reciprocal (two FMAs, no division)
-                if (ln == c) { const double rc = fma(r, fma(-dj, r, 1.0), r); s_rdiag[c] = rc; rd_all[k0 + c] = rc; }
-                wave_lds_sync();
-                if ((c & (CH_GRP - 1)) == CH_GRP - 1) __syncthreads();   // columns c-CH_GRP+1 .. c are published: the panel wavefronts may use them
-            }
-            if (fail && lane == 0) s_fail = 1;
-        } else if (wave == 4) {
-            // the helper (same SIMD as wavefront 0, no panel rows): before barrier g the columns of the groups < g are published; it
-            // takes the terms of group g-1 out of the columns of the groups > g (row per lane, two columns at a time), in place
-            const int hi = lane & 31, hh = lane >> 5;
-#pragma unroll
-            for (int g = 0; g < CH_NB / CH_GRP; g++) {
-                if (g >= 1) {
-                    const int kb = CH_GRP * (g - 1);
-                    double lk4[CH_GRP];
-#pragma unroll
-                    for (int q = 0; q < CH_GRP; q++) lk4[q] = L11[hi * CH_LDP + kb + q];
-#pragma unroll
-                    for (int jj = CH_GRP * (g + 1); jj < CH_NB; jj += 2) {
-                        const int j = jj + hh;
-                        double acc = L11[hi * CH_LDP + j];
-#pragma unroll
-                        for (int q = 0; q < CH_GRP; q++) acc -= lk4[q] * L11[j * CH_LDP + kb + q];
-                        L11[hi * CH_LDP + j] = acc;
-                    }
-                }
-                __syncthreads();
-            }
-        } else {
-            // left-looking per row (x[32] in registers, row j of L read as one contiguous LDS row).  Every panel wavefront
-            // passes the same 8 work-group barriers as wavefront 0, whether its threads own a row or not.
-            // (wavefronts 1-3 and 5-7 take rows 0 .. 383; two rows per thread on three wavefronts would halve the broadcast reads of
-            // L11 -- 1 KB comes back per ds_read_b128 whatever the number of rows it serves -- but x and z together need more
-            // than the 256 registers the kernel has: measured with spills, 202 us against 89)
-            const int t = wave < 4 ? tid - 64 : tid - 128;
-            const bool has = t < m;
-            const bool rhs = rhs_row && t == m;                 // the thread after the last panel row takes the right-hand side
-            double x[CH_NB];
-#pragma unroll
-            for (int j = 0; j < CH_NB; j++) x[j] = has ? P[t * CH_LDP + j] : (rhs ? yv[k0 + j] : 0.0);
-#pragma unroll
-            for (int j = 0; j < CH_NB; j++) {
-                if ((j & (CH_GRP - 1)) == 0) {
-                    // x[j-1] must be finished BEFORE the barrier: without this artificial use the scheduler drains all eight
-                    // barriers first -- loading the whole block into registers (992 VGPRs: spills) -- and computes afterwards,
-                    // which also serialises the panel solve behind the factorisation again
-                    if (j > 0) asm volatile("" ::"v"(x[j - 1]) : "memory");
-                    __syncthreads();                           // columns j .. j+3 of L11 and their reciprocal pivots are there
-                }
-                double acc = x[j];
-#pragma unroll
-                for (int k = 0; k < j; k++) acc -= x[k] * L11[j * CH_LDP + k];
-                x[j] = acc * s_rdiag[j];
-            }
-            if (has) {
-#pragma unroll
-                for (int j = 0; j < CH_NB; j++) P[t * CH_LDP + j] = x[j];
-            }
-            if (rhs) {
-#pragma unroll
-                for (int j = 0; j < CH_NB; j++) { s_yk[j] = x[j]; if (j < nb) yv[k0 + j] = x[j]; }
-            }
-        }
-        __syncthreads();
-        // rows beyond the pipelined ones (only for reduced systems of more than ~480 unknowns): plain pass on the LDS rows, the
-        // block is complete.  Rolled on purpose: an unrolled copy of the 496-term row solve is 12 KB of code, and this kernel has
-        // to stay inside the 64 KB instruction cache (round 4: at 77 KB every panel step re-fetched its code from L2).
-        for (int t = tid + 384; t < m; t += nt) {
-            double *xr = P + t * CH_LDP;
-#pragma nounroll
-            for (int j = 0; j < CH_NB; j++) {
-                double acc = xr[j];
-#pragma nounroll
-                for (int k = 0; k < j; k++) acc -= xr[k] * L11[j * CH_LDP + k];
-                xr[j] = acc * s_rdiag[j];
-            }
-        }
-        __syncthreads();
-        if (rhs_row) {
-            // trailing update of the right-hand side: rhs[below] -= P y_blk
-            for (int i = tid; i < m; i += nt) {
-                double acc = yv[k0 + nb + i];
-#pragma unroll
-                for (int j = 0; j < CH_NB; j++) acc -= P[i * CH_LDP + j] * s_yk[j];
-                yv[k0 + nb + i] = acc;
-            }
-        }
-        CH_TICK(1);
-        if (s_fail) break;
-        // factored block and panel back to HBM (coalesced)
-        for (int e = tid; e < nb * nb; e += nt) {
-            const int i = e / nb, j = e - i * nb;
-            if (j <= i) S[(long long)(k0 + i) * ld + k0 + j] = L11[i * CH_LDP + j];
-        }
-        for (int e = tid; e < m * CH_NB; e += nt) {
-            const int t = e >> 5, j = e & 31;
-            if (j < nb) S[(long long)(k0 + nb + t) * ld + k0 + j] = P[t * CH_LDP + j];
-        }
-        CH_TICK(2);
-        // (d) trailing update  A22 -= P P^T  (lower triangle) on the fp64 matrix cores: one wavefront per 16x16 tile,
-        //     8 x v_mfma_f64_16x16x4_f64 over the 32 panel columns.  Operand layout (cdna_hip_programming.md, f64 MFMA):
-        //     A: lane holds A[lane & 15][lane >> 4], B: lane holds B[lane >> 4][lane & 15] -- both are rows of the LDS
-        //     panel --, C/D: col = lane & 15, row = (lane >> 4) + 4 * reg.  S stays in HBM/L2; a tile is read, updated
-        //     and written once per panel step.
-        {
-            typedef double d4 __attribute__((ext_vector_type(4)));
-            const int mb = (m + 15) >> 4, nwv = nt >> 6;
-            const int lr = lane & 15, lk = lane >> 4;
-            // A wavefront takes the tiles wv, wv + nwv, .. of the row-major lower-triangle enumeration, two at a time (two
-            // independent MFMA chains).  Round 4: the phase was a SUM of its parts (knock-outs: 24 us of tile bookkeeping -- a
-            // double-precision sqrt per tile index, 64-bit multiplies per element address, four predicates per element --, 31 us of
-            // MFMA, 9 us of loads, 6 us of LDS reads, 4 us of stores; two wavefronts per SIMD overlap little).  Now the tile
-            // walk is integer arithmetic on the scalar unit (wave-uniform), an element's address is a uniform base + one of four
-            // per-lane constants, operand rows are read unpredicated (garbage rows >= m only reach rows / columns that are not
-            // stored), and the old values of the next pair are requested before the chains of the current pair run.
-            const int ntile = mb * (mb + 1) / 2;
-            const int wv = __builtin_amdgcn_readfirstlane(wave);
-            auto advance = [&](int &bi, int &bj, int step) { bj += step; while (bj > bi) { bj -= bi + 1; bi++; } };
-            int lo[4];                                              // element (lk + 4 r, lr) of a tile, in doubles from the tile's corner
-#pragma unroll
-            for (int r = 0; r < 4; r++) lo[r] = (lk + 4 * r) * ld + lr;
-            double *Sc = S + (long long)(k0 + nb) * ld + k0 + nb;      // corner of the trailing matrix
-            const double *Pl = P + lr * CH_LDP + lk;                   // this lane's operand element of tile row 0
-            auto corner = [&](int bi, int bj) { return Sc + ((long long)bi * ld + bj) * 16; };
-            auto okmask = [&](int bi, int bj, int r) { return (16 * bi + lk + 4 * r < m) && (bi != bj || lr <= lk + 4 * r); };
-            auto fetch = [&](int bi, int bj, bool has, double (&o)[4]) {
-                const double *c = corner(bi, bj);
-#pragma unroll
-                for (int r = 0; r < 4; r++) o[r] = (has && okmask(bi, bj, r)) ? c[lo[r]] : 0.0;
-            };
-            int bi0 = 0, bj0 = 0, bi1, bj1;
-            advance(bi0, bj0, wv);
-            bi1 = bi0; bj1 = bj0; advance(bi1, bj1, nwv);
-            double old0[4], old1[4];
-            fetch(bi0, bj0, wv < ntile, old0);
-            fetch(bi1, bj1, wv + nwv < ntile, old1);
-            for (int t0 = wv; t0 < ntile; t0 += 2 * nwv) {
-                const bool has1 = t0 + nwv < ntile;
-                int nbi0 = bi1, nbj0 = bj1, nbi1, nbj1;
-                advance(nbi0, nbj0, nwv);
-                nbi1 = nbi0; nbj1 = nbj0; advance(nbi1, nbj1, nwv);
-                double nold0[4], nold1[4];
-                fetch(nbi0, nbj0, t0 + 2 * nwv < ntile, nold0);
-                fetch(nbi1, nbj1, t0 + 3 * nwv < ntile, nold1);
-                const double *pa0 = Pl + bi0 * (16 * CH_LDP), *pb0 = Pl + bj0 * (16 * CH_LDP);
-                const double *pa1 = Pl + (has1 ? bi1 : bi0) * (16 * CH_LDP), *pb1 = Pl + (has1 ? bj1 : bj0) * (16 * CH_LDP);
-                d4 c0 = {0., 0., 0., 0.}, c1 = {0., 0., 0., 0.};
-#pragma unroll
-                for (int kk = 0; kk < CH_NB / 4; kk++) {
-                    c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa0[4 * kk], pb0[4 * kk], c0, 0, 0, 0);
-                    c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa1[4 * kk], pb1[4 * kk], c1, 0, 0, 0);
-                }
-                double *q0 = corner(bi0, bj0), *q1 = corner(bi1, bj1);
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    if (okmask(bi0, bj0, r)) q0[lo[r]] = old0[r] - c0[r];
-                    if (has1 && okmask(bi1, bj1, r)) q1[lo[r]] = old1[r] - c1[r];
-                }
-                bi0 = nbi0; bj0 = nbj0; bi1 = nbi1; bj1 = nbj1;
-#pragma unroll
-                for (int r = 0; r < 4; r++) { old0[r] = nold0[r]; old1[r] = nold1[r]; }
-            }
-        }
-        __syncthreads();
-        CH_TICK(3);
-    }
-    if (s_fail) { if (tid == 0) ctl->lin_fail = 1; return; }
-
-    CH_TICK(4);
-    // forward substitution rode along as a panel row (rhs_row: the host sends systems of more than 479 unknowns to the HBM path);
-    // backward substitution from the factor itself -- no inverse diagonal blocks (rounds 1-3 computed them here: 20 us and 12 KB of
-    // unrolled code in a kernel that has to fit the instruction cache)
-    chol_backward_blocks(D, yv, rd_all, &s_red[0][0]);
-
-    for (int i = tid; i < n; i += nt) D.yf[i] = yv[i];
-    CH_TICK(5);
-    if (tid == 0) for (int i = 0; i < 6; i++) ctl->dbg[i] = tk[i];
-#undef CH_TICK
-}
-__global__ __launch_bounds__(512) void k_ba_cholesky(BADev D) { b_ba_cholesky(D); }
-__global__ __launch_bounds__(512) void k_ba_cholesky_B(const BADev *__restrict__ arr) { const BADev &D = arr[blockIdx.z]; b_ba_cholesky(D); }
 
 // ================================================================================== pose-only problems in ONE kernel
 // MultiViewGeometry::ceresPnP (src/multi_view_geometry.cpp:492-586): one free pose, a few hundred fixed world points.  The
@@ -1747,7 +1099,7 @@ __global__ __launch_bounds__(256) void k_ba_pose_only(BADev D, BAOpt O, BACtl ct
                         P1 += yi * si * s_b[i];
                         P2 += yi * si * s_b[i] - (s_diag[i] / cl.radius) * yi * yi;
                     }
-                const int valid = d_ctl_candidate(cl, O, ok, P1, P2);
+                const int valid = d_ctl_candidate(cl, O, ok, d_ctl_schur_model_cost_change(cl, P1, P2));
                 if (valid) {
                     double d[6], out[7];
                     for (int c = 0; c < 6; c++) d[c] = -s_y[c] * s_scale[c];
@@ -1878,159 +1230,6 @@ __global__ __launch_bounds__(64 * SS_WAVES) void k_ba_schur_sparse(BADev D, int 
     if (threadIdx.x < 6 && vacc[threadIdx.x] != 0.0) atomicAdd(&D.v[ci + threadIdx.x], vacc[threadIdx.x]);
 }
 
-// Blocked right-looking Cholesky of the reduced system on HBM, three kernels per 32-column panel:
-//   k_chol_diag  (1 wavefront): factor the diagonal block in LDS (same register-row algorithm as k_ba_cholesky), write it back, and
-//                its inverse (for the triangular solves) to Linv
-//   k_chol_panel (64 rows per work-group): X L11^T = A21 by substitution, one row per thread
-//   k_chol_trail (one 32 x 32 tile per work-group, lower triangle): A22 -= X X^T
-// then k_chol_solve (1 work-group): the two triangular solves.  ~3 * nf / 32 launches per LM iteration: this path is for the
-// loop-closure / offline BAs (hundreds of keyframes), where a solve takes milliseconds either way.
-__global__ __launch_bounds__(64) void k_chol_diag(BADev D, int k0)
-{
-    BACtl *ctl = D.ctl;
-    if (ctl->done || ctl->lin_fail) return;
-    __shared__ double L11[CH_NB * CH_LDP];
-    const int n = D.nf, ld = D.nfp, lane = threadIdx.x;
-    const int nb = min(CH_NB, n - k0);
-    double *S = D.S;
-    for (int e = lane; e < CH_NB * CH_NB; e += 64) {
-        const int i = e >> 5, j = e & 31;
-        double v = (i == j) ? 1.0 : 0.0;
-        if (i < nb && j <= i) v = S[(long long)(k0 + i) * ld + k0 + j];
-        L11[i * CH_LDP + j] = v;
-    }
-    wave_lds_sync();
-    double a[CH_NB];
-#pragma unroll
-    for (int j = 0; j < CH_NB; j++) a[j] = lane < CH_NB ? L11[lane * CH_LDP + j] : 0.0;
-    bool fail = false;
-    double pnext = a[0];
-#pragma unroll
-    for (int c = 0; c < CH_NB; c++) {
-        double sacc = pnext;
-        if (c > 0) sacc -= a[c - 1] * L11[c * CH_LDP + c - 1];
-        const double d = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(sacc), c), __builtin_amdgcn_readlane(__double2loint(sacc), c));
-        if (c + 1 < CH_NB) {
-            pnext = a[c + 1];
-#pragma unroll
-            for (int k = 0; k < c; k++) pnext -= a[k] * L11[(c + 1) * CH_LDP + k];
-        }
-        if (!(d > 0.0) || !isfinite(d)) fail = true;
-        double r = __builtin_amdgcn_rsq(d);
-        r = fma(0.5 * r, fma(-(d * r), r, 1.0), r);
-        r = fma(0.5 * r, fma(-(d * r), r, 1.0), r);
-        double dj = d * r;
-        dj = fma(0.5 * r, fma(-dj, dj, d), dj);
-        const double l = lane == c ? dj : sacc * r;
-        a[c] = lane >= c ? l : 0.0;
-        if (lane >= c && lane < CH_NB) L11[lane * CH_LDP + c] = a[c];
-        if (lane == c) L11[c * CH_LDP + CH_NB] = fma(r, fma(-dj, r, 1.0), r);          // reciprocal pivot in the padding column
-        wave_lds_sync();
-    }
-    if (__builtin_amdgcn_ballot_w64(fail) != 0) { if (lane == 0) ctl->lin_fail = 1; return; }
-    for (int e = lane; e < nb * nb; e += 64) {
-        const int i = e / nb, j = e - i * nb;
-        if (j <= i) S[(long long)(k0 + i) * ld + k0 + j] = L11[i * CH_LDP + j];
-    }
-    if (lane < CH_NB) {                                                 // inverse block: lane j solves L x = e_j
-        double x[CH_NB];
-#pragma unroll
-        for (int i = 0; i < CH_NB; i++) {
-            double acc = (i == lane) ? 1.0 : 0.0;
-#pragma unroll
-            for (int k = 0; k < i; k++) acc -= L11[i * CH_LDP + k] * x[k];
-            x[i] = i < lane ? 0.0 : acc * L11[i * CH_LDP + CH_NB];
-        }
-        double *dst = D.Linv + (long long)(k0 / CH_NB) * CH_NB * CH_NB;
-#pragma unroll
-        for (int i = 0; i < CH_NB; i++) dst[i * CH_NB + lane] = x[i];
-    }
-}
-
-__global__ __launch_bounds__(64) void k_chol_panel(BADev D, int k0)
-{
-    const BACtl *ctl = D.ctl;
-    if (ctl->done || ctl->lin_fail) return;
-    __shared__ double L11[CH_NB * CH_LDP];
-    __shared__ double X[64 * CH_LDP];                                   // the work-group's 64 panel rows (a thread's row stays in LDS: the fully
-                                                                        // unrolled register version made the scheduler hoist all 496 loads of L11
-                                                                        // -- 512 VGPRs, 624 spills -- and miscomputed from column 12 on)
-    const int n = D.nf, ld = D.nfp, lane = threadIdx.x;
-    const int nb = min(CH_NB, n - k0), m = n - k0 - nb;
-    double *S = D.S;
-    for (int e = lane; e < CH_NB * CH_NB; e += 64) {
-        const int i = e >> 5, j = e & 31;
-        double v = (i == j) ? 1.0 : 0.0;
-        if (i < nb && j <= i) v = S[(long long)(k0 + i) * ld + k0 + j];
-        L11[i * CH_LDP + j] = v;
-    }
-    const int t0 = blockIdx.x * 64;
-    for (int e = lane; e < 64 * CH_NB; e += 64) {                       // coalesced: 32 consecutive columns of one row per half wavefront
-        const int r = e >> 5, j = e & 31;
-        X[r * CH_LDP + j] = (t0 + r < m && j < nb) ? S[(long long)(k0 + nb + t0 + r) * ld + k0 + j] : 0.0;
-    }
-    __syncthreads();
-    double *x = X + lane * CH_LDP;
-    for (int j = 0; j < CH_NB; j++) {
-        double acc = x[j];
-        const double *lr = L11 + j * CH_LDP;
-        for (int k = 0; k < j; k++) acc -= x[k] * lr[k];
-        x[j] = acc / lr[j];
-    }
-    __syncthreads();
-    for (int e = lane; e < 64 * CH_NB; e += 64) {
-        const int r = e >> 5, j = e & 31;
-        if (t0 + r < m && j < nb) S[(long long)(k0 + nb + t0 + r) * ld + k0 + j] = X[r * CH_LDP + j];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_chol_trail(BADev D, int k0)
-{
-    const BACtl *ctl = D.ctl;
-    if (ctl->done || ctl->lin_fail) return;
-    __shared__ double A[32][33], B[32][33];
-    const int n = D.nf, ld = D.nfp, tid = threadIdx.x;
-    const int nb = min(CH_NB, n - k0), m = n - k0 - nb;
-    // lower-triangular tile index -> (bi, bj), bj <= bi
-    int t = blockIdx.x, bi = 0;
-    while (t > bi) { t -= bi + 1; bi++; }
-    const int bj = t;
-    double *S = D.S;
-    for (int e = tid; e < 32 * 32; e += 256) {
-        const int r = e >> 5, c = e & 31;
-        const int ia = bi * 32 + r, ib = bj * 32 + r;
-        A[r][c] = (ia < m && c < nb) ? S[(long long)(k0 + nb + ia) * ld + k0 + c] : 0.0;
-        B[r][c] = (ib < m && c < nb) ? S[(long long)(k0 + nb + ib) * ld + k0 + c] : 0.0;
-    }
-    __syncthreads();
-    const int r0 = (tid >> 4) * 2, c0 = (tid & 15) * 2;                 // 2 x 2 outputs per thread
-    double acc[2][2] = {{0, 0}, {0, 0}};
-    for (int k = 0; k < 32; k++) {
-        const double a0 = A[r0][k], a1 = A[r0 + 1][k], b0 = B[c0][k], b1 = B[c0 + 1][k];
-        acc[0][0] += a0 * b0; acc[0][1] += a0 * b1; acc[1][0] += a1 * b0; acc[1][1] += a1 * b1;
-    }
-    for (int i = 0; i < 2; i++)
-        for (int j = 0; j < 2; j++) {
-            const int gi = bi * 32 + r0 + i, gj = bj * 32 + c0 + j;
-            if (gi < m && gj <= gi) S[(long long)(k0 + nb + gi) * ld + k0 + nb + gj] -= acc[i][j];
-        }
-}
-
-__global__ __launch_bounds__(512) void k_chol_solve(BADev D)
-{
-    const BACtl *ctl = D.ctl;
-    if (ctl->done || ctl->lin_fail) return;
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    double *L11 = (double *)smem_raw;                       // CH_NB x CH_LDP
-    double *yv = L11 + CH_NB * CH_LDP;                      // nfp
-    __shared__ double s_red[32][33];
-    const int n = D.nf, tid = threadIdx.x, nt = blockDim.x;
-    for (int i = tid; i < D.nfp; i += nt) yv[i] = i < n ? D.scale_f[i] * (D.bf[i] - D.v[i]) : 0.0;
-    __syncthreads();
-    chol_trisolve(D, L11, yv, s_red);
-    for (int i = tid; i < n; i += nt) D.yf[i] = yv[i];
-}
-
 // ---------------------------------------------------------------------------------- back substitution
 // one wavefront per landmark: t_l = W_l . (s .* yf); y_l = s_l (etb_l - t_l) / etep_l
 __device__ __forceinline__ void b_ba_backsub(const BADev &D)
@@ -2150,7 +1349,7 @@ __device__ __forceinline__ void b_ba_candidate(const BADev &D, BAOpt O)
     if (tid == 0) {
         BACtl cl = *ctl;
         if (D.ldim == 1 && D.n_lm > 0) { cl.acc1 += A1; cl.acc2 += A2; cl.acc3 += A3; }
-        s_flag = d_ctl_candidate(cl, O, ok, P1, P2);
+        s_flag = d_ctl_candidate(cl, O, ok, d_ctl_schur_model_cost_change(cl, P1, P2));
         *D.ctl = cl;
     }
     __syncthreads();
@@ -2338,23 +1537,6 @@ __global__ __launch_bounds__(256) void k_ba_linearize_xyz(BADev D)
     if (threadIdx.x == 0 && cost != 0.0) atomicAdd(&ctl->cost_acc, cost);
 }
 
-// lower Cholesky factor of the symmetric 3x3 (a0 a1 a2; . a3 a4; . . a5); returns false if not positive definite
-__device__ __forceinline__ bool d_chol3(const double a[6], double L[6])      // L: (l00, l10, l11, l20, l21, l22)
-{
-    if (!(a[0] > 0.0)) return false;
-    L[0] = sqrt(a[0]);
-    L[1] = a[1] / L[0];
-    const double d1 = a[3] - L[1] * L[1];
-    if (!(d1 > 0.0)) return false;
-    L[2] = sqrt(d1);
-    L[3] = a[2] / L[0];
-    L[4] = (a[4] - L[3] * L[1]) / L[2];
-    const double d2 = a[5] - L[3] * L[3] - L[4] * L[4];
-    if (!(d2 > 0.0)) return false;
-    L[5] = sqrt(d2);
-    return true;
-}
-
 // one wavefront per point (see the block comment above)
 __global__ __launch_bounds__(256) void k_ba_xyz_prep(BADev D)
 {
@@ -2538,471 +1720,7 @@ __device__ __forceinline__ void b_ba_lm_live(const BADev &D)
 __global__ __launch_bounds__(256) void k_ba_lm_live(BADev D) { b_ba_lm_live(D); }
 __global__ __launch_bounds__(256) void k_ba_lm_live_B(const BADev *__restrict__ arr) { const BADev &D = arr[blockIdx.z]; if (D.skip2) return; b_ba_lm_live(D); }
 
-struct ov2_ba_dev {
-    BADev D;
-    void *pool = nullptr; size_t pool_bytes = 0;
-    bool pool_owned = true;             // false: the pool lives in the context's grow-only device scratch (transient small problems)
-    int n_res = 0;
-    int *lm_order = nullptr;            // landmarks sorted by anchor keyframe (device)
-    std::vector<double> h_poses0, h_lam0;
-    int device = 0;
-};
-
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-static void ba_destroy(ov2_ba_dev *dev);
-
-// lock-step batch (ov2_local_ba_batch): the problems' pools and staging mirrors are consecutive slices of ONE device / pinned block
-struct BASlice { uint8_t *dev_base; size_t dev_cap, dev_used; uint8_t *host_base; size_t host_cap, host_used; std::mutex m; };      // (the problems of a batch are prepared on several host threads)
-#define BA_SLICE_FULL (-12345)          // (internal: the caller grows the blocks and starts over)
-
-// persistent host threads of a context (ov2_ctx::ba_host_pool): the problems of a batch are prepared on them (spawning sixteen threads per
-// batch was 0.3 ms of its first millisecond), and so are the slices of one large problem's sort (ba_create)
-struct BAHostPool {
-    std::vector<std::thread> th; std::mutex m; std::condition_variable cv_go, cv_done;
-    const std::function<void(int)> *fn = nullptr; int n = 0, gen = 0, busy = 0; std::atomic<int> next{0}; bool quit = false;
-    explicit BAHostPool(int nt)
-    {
-        try { spawn(nt); }
-        catch (...) { { std::lock_guard<std::mutex> l(m); quit = true; } cv_go.notify_all(); for (auto &t : th) t.join(); th.clear(); throw; }
-    }
-    void spawn(int nt)
-    {
-        for (int t = 0; t < nt; t++)
-            th.emplace_back([this] {
-                int seen = 0;
-                for (;;) {
-                    { std::unique_lock<std::mutex> l(m); cv_go.wait(l, [&] { return quit || gen != seen; }); if (quit) return; seen = gen; }
-                    for (int i; (i = next.fetch_add(1)) < n;) (*fn)(i);
-                    { std::lock_guard<std::mutex> l(m); busy--; }
-                    cv_done.notify_one();
-                }
-            });
-    }
-    ~BAHostPool() { { std::lock_guard<std::mutex> l(m); quit = true; } cv_go.notify_all(); for (auto &t : th) t.join(); }
-    void run(int count, const std::function<void(int)> &f)              // f(0 .. count-1); the caller takes part
-    {
-        if (th.empty() || count <= 1) { for (int i = 0; i < count; i++) f(i); return; }
-        { std::lock_guard<std::mutex> l(m); fn = &f; n = count; next.store(0); busy = (int)th.size(); gen++; }
-        cv_go.notify_all();
-        for (int i; (i = next.fetch_add(1)) < count;) f(i);
-        std::unique_lock<std::mutex> l(m); cv_done.wait(l, [&] { return busy == 0; });
-    }
-};
-
-static BAHostPool *ba_host_pool_of(ov2_ctx *ctx)
-{
-    if (!ctx->ba_host_pool) {
-        try { ctx->ba_host_pool = new BAHostPool(15); }               // (no threads to be had: the caller works serially)
-        catch (...) { ctx->ba_host_pool = nullptr; }
-        ctx->ba_host_pool_free = [](void *q) { delete (BAHostPool *)q; };
-    }
-    return (BAHostPool *)ctx->ba_host_pool;
-}
-
-// transient: the problem lives for one ov2_ba_solve call -- small pools then come out of the context's device scratch instead of
-// a hipMalloc / hipFree pair (~100 us, more than a whole ceresPnP solve)
-static int ba_create(ov2_ctx *ctx, const ov2_ba_problem *p, ov2_ba_dev **out, bool transient = false, BASlice *ext = nullptr)
-{
-    OV2_REQUIRE(p && out, OV2_EINVAL, "NULL problem");
-    OV2_REQUIRE(p->n_kf > 0 && p->n_lm >= 0 && p->n_res >= 0, OV2_EINVAL, "bad problem sizes");
-    OV2_REQUIRE(p->poses && p->kf_const, OV2_EINVAL, "NULL pose arrays");
-    OV2_REQUIRE(p->n_lm == 0 || (p->invdepth && p->lm_anchor_kf && p->lm_anchor_uv), OV2_EINVAL, "NULL landmark arrays");
-    OV2_REQUIRE(p->n_res == 0 || (p->res_type && p->res_kf && p->res_lm && p->res_uv && p->res_sigma), OV2_EINVAL, "NULL residual arrays");
-    // validate + landmark-sorted order of the active residual blocks (a STABLE counting sort: blocks of a landmark keep the
-    // caller's order); pose-only blocks (OV2_RES_PNP) go to their own list.  Large problems (a 590 k-block localBA: 3.8 ms of the
-    // call were this sort and the staging fill) split the residual range over a few host threads: per-thread counts, offsets
-    // = landmark prefix + the counts of the lower-numbered threads, so the result is identical to the serial sort.
-    // (a 25-KF window of 69 k blocks: 2 threads; the problems of a batch are prepared side by side already: one thread each)
-    int NT = (p->n_res >= (1 << 16) && !ext) ? std::min(8, p->n_res >> 15) : 1;
-    BAHostPool *hpool = NT > 1 ? ba_host_pool_of(ctx) : nullptr;
-    if (!hpool) NT = 1;
-    const bool dbg_laps = ctx->debug != 0 && !ext;
-    const auto tc0 = std::chrono::steady_clock::now();
-    auto clap = [&](const char *what) {
-        if (dbg_laps) fprintf(stderr, "[ov2 ba_create] %-34s %8.3f ms since entry\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count());
-    };
-    std::vector<std::vector<int>> cntT((size_t)NT, std::vector<int>((size_t)p->n_lm + 1, 0));
-    std::vector<int> nactT((size_t)NT, 0), npoT((size_t)NT, 0);
-    std::vector<const char *> errT((size_t)NT, nullptr);
-    auto range_of = [&](int t, int &b, int &e) { b = (int)((long long)p->n_res * t / NT); e = (int)((long long)p->n_res * (t + 1) / NT); };
-    auto run_threads = [&](auto &&fn) {
-        if (NT == 1) { fn(0); return; }
-        const std::function<void(int)> f = fn;                          // (the context's persistent threads: two spawns per call were 0.1 - 0.3 ms)
-        hpool->run(NT, f);
-    };
-    run_threads([&](int t) {
-        int b, e; range_of(t, b, e);
-        std::vector<int> &cn = cntT[(size_t)t];
-        int na_t = 0, np_t = 0;
-        const char *err = nullptr;
-        for (int i = b; i < e && !err; i++) {
-            if (p->res_active && !p->res_active[i]) continue;
-            if (p->res_type[i] > OV2_RES_PNP) { err = "unknown residual type"; break; }
-            if (!(p->res_sigma[i] > 0)) { err = "res_sigma must be positive"; break; }
-            if (p->res_type[i] == OV2_RES_PNP) {
-                if (!p->res_xyz) { err = "OV2_RES_PNP blocks need res_xyz"; break; }
-                if (p->res_kf[i] < 0 || p->res_kf[i] >= p->n_kf) { err = "res_kf out of range"; break; }
-                np_t++;
-                continue;
-            }
-            const int lm = p->res_lm[i];
-            if (lm < 0 || lm >= p->n_lm) { err = "res_lm out of range"; break; }
-            if (p->res_type[i] != OV2_RES_RIGHT_ANCH && (p->res_kf[i] < 0 || p->res_kf[i] >= p->n_kf)) { err = "res_kf out of range"; break; }
-            // The observer of a LEFT / RIGHT block is never the landmark's anchor keyframe (the reference skips the anchor's own
-            // mono observation, src/optimizer.cpp:290-296, and gives its right-camera observation the RIGHT_ANCH factor): the lineariser
-            // relies on it (J_observer = -J_anchor serves both the observer's diagonal block and the anchor-observer block)
-            if (p->res_type[i] != OV2_RES_RIGHT_ANCH && p->res_kf[i] == p->lm_anchor_kf[lm]) { err = "a LEFT / RIGHT block observes its landmark from the anchor keyframe (use OV2_RES_RIGHT_ANCH)"; break; }
-            cn[lm]++; na_t++;
-        }
-        nactT[(size_t)t] = na_t; npoT[(size_t)t] = np_t; errT[(size_t)t] = err;
-    });
-    for (int t = 0; t < NT; t++) OV2_REQUIRE(errT[(size_t)t] == nullptr, OV2_EINVAL, errT[(size_t)t]);
-    clap("validate + count");
-    std::vector<int> cnt(p->n_lm + 1, 0);                              // cnt[l] = first sorted index of landmark l (CSR)
-    int n_act = 0, n_po = 0;
-    for (int t = 0; t < NT; t++) { n_act += nactT[(size_t)t]; n_po += npoT[(size_t)t]; }
-    {
-        int run = 0;
-        for (int l = 0; l < p->n_lm; l++) {
-            OV2_REQUIRE(p->lm_anchor_kf[l] >= 0 && p->lm_anchor_kf[l] < p->n_kf, OV2_EINVAL, "lm_anchor_kf out of range");
-            cnt[l] = run;
-            for (int t = 0; t < NT; t++) { const int c = cntT[(size_t)t][l]; cntT[(size_t)t][l] = run; run += c; }   // cntT becomes the thread's fill cursor
-        }
-        cnt[p->n_lm] = run;
-    }
-    std::vector<int> pose_col(p->n_kf);
-    int n_opt = 0;
-    for (int k = 0; k < p->n_kf; k++) pose_col[k] = p->kf_const[k] ? -1 : 6 * n_opt++;
-    const int nf = 6 * n_opt, nfp = std::max(BA_TILE, (nf + BA_TILE - 1) / BA_TILE * BA_TILE);
-    OV2_REQUIRE(nfp <= BA_MAX_NFP, OV2_EUNSUPPORTED, "more than 1024 optimised keyframes: dense reduced system too large");
-    // the per-residual upload arrays are filled straight into the context's PINNED host scratch: the H2D copies below are then
-    // real asynchronous DMA (from pageable std::vectors every copy went through the runtime's staging buffer, ~2.5 ms for the
-    // 20 MB of a 590 k-block problem) and no 20 MB of vectors is allocated and zeroed per call
-    int *res_kf, *res_orig, *po_kf, *po_orig;
-    uint8_t *res_type;
-    double *res_uv, *res_sigma, *po_xyz, *po_uv, *po_sigma;
-    // Round 3: the staging buffer MIRRORS the first eleven arrays of the device pool (same offsets), so that everything a solve
-    // needs from the host goes up in ONE copy instead of eleven (each ~15 us of launch overhead: a third of ba_create on a
-    // 69 k-block window)
-    const size_t nl = (size_t)std::max(1, p->n_lm), na = (size_t)std::max(1, n_act), nr = (size_t)std::max(1, p->n_res);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
-    const size_t o_pose_col = take(4 * (size_t)p->n_kf), o_lm_ptr = take(4 * (nl + 1)), o_lm_anchor = take(4 * nl), o_lm_auv = take(16 * nl);
-    const size_t o_res_type = take(na), o_res_kf = take(4 * na), o_res_orig = take(4 * na), o_res_uv = take(16 * na), o_res_sigma = take(8 * na);
-    const size_t o_lm_order = take(4 * nl), o_lm_live = take(nl);
-    const size_t o_pose0 = take(56 * (size_t)p->n_kf), o_lam0 = take(8 * nl);      // initial parameters (the batch's reset kernel copies them on the device)
-    const size_t up_bytes = off;                                       // [0, up_bytes) of the pool = the staging buffer
-    uint8_t *hs = nullptr;
-    {
-        const size_t np_h = (size_t)std::max(1, n_po);
-        size_t hoff = up_bytes;
-        auto htake = [&](size_t bytes) { const size_t o = hoff; hoff += (bytes + 255) & ~(size_t)255; return o; };
-        const size_t h6 = htake(4 * np_h), h7 = htake(4 * np_h), h8 = htake(24 * np_h), h9 = htake(16 * np_h), h10 = htake(8 * np_h);
-        if (ext) {
-            std::lock_guard<std::mutex> l(ext->m);
-            if (ext->host_used + hoff > ext->host_cap) { ext->host_used += al256(hoff); return BA_SLICE_FULL; }    // (keeps counting: the caller learns the total)
-            hs = ext->host_base + ext->host_used; ext->host_used += al256(hoff);
-        } else {
-        const int rch = ctx->reserve_host(hoff);
-        if (rch != OV2_OK) return rch;
-        hs = (uint8_t *)ctx->h_scratch;
-        }
-        res_kf = (int *)(hs + o_res_kf); res_orig = (int *)(hs + o_res_orig); res_type = hs + o_res_type; res_uv = (double *)(hs + o_res_uv); res_sigma = (double *)(hs + o_res_sigma);
-        po_kf = (int *)(hs + h6); po_orig = (int *)(hs + h7); po_xyz = (double *)(hs + h8); po_uv = (double *)(hs + h9); po_sigma = (double *)(hs + h10);
-    }
-    std::vector<int> poStart((size_t)NT + 1, 0);
-    for (int t = 0; t < NT; t++) poStart[(size_t)t + 1] = poStart[(size_t)t] + npoT[(size_t)t];
-    run_threads([&](int t) {
-        int b, e; range_of(t, b, e);
-        std::vector<int> &fill = cntT[(size_t)t];
-        int kp = poStart[(size_t)t];
-        for (int i = b; i < e; i++) {
-            if (p->res_active && !p->res_active[i]) continue;
-            if (p->res_type[i] == OV2_RES_PNP) {
-                po_kf[kp] = p->res_kf[i]; po_orig[kp] = i; po_sigma[kp] = p->res_sigma[i];
-                po_uv[2 * kp] = p->res_uv[2 * i]; po_uv[2 * kp + 1] = p->res_uv[2 * i + 1];
-                for (int c = 0; c < 3; c++) po_xyz[3 * kp + c] = p->res_xyz[3 * i + c];
-                kp++;
-                continue;
-            }
-            const int k = fill[p->res_lm[i]]++;
-            res_type[k] = p->res_type[i]; res_kf[k] = p->res_type[i] == OV2_RES_RIGHT_ANCH ? p->lm_anchor_kf[p->res_lm[i]] : p->res_kf[i];
-            res_orig[k] = i; res_uv[2 * k] = p->res_uv[2 * i]; res_uv[2 * k + 1] = p->res_uv[2 * i + 1]; res_sigma[k] = p->res_sigma[i];
-        }
-    });
-
-    clap("fill staging (sorted blocks)");
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    ov2_ba_dev *dev = new (std::nothrow) ov2_ba_dev();
-    OV2_REQUIRE(dev != nullptr, OV2_ENOMEM, "out of host memory");
-    dev->device = ctx->device; dev->n_res = p->n_res;
-    if (!ext) dev->h_poses0.assign(p->poses, p->poses + 7 * (size_t)p->n_kf);
-    if (!ext) dev->h_lam0.assign(p->invdepth, p->invdepth + (p->n_lm > 0 ? p->n_lm : 0));
-    BADev &D = dev->D;
-    memset(&D, 0, sizeof(D));
-    D.n_kf = p->n_kf; D.n_lm = p->n_lm; D.n_act = n_act; D.nf = nf; D.nfp = nfp; D.n_po = n_po; D.ldim = 1; D.n_res = p->n_res;
-    {   // beyond what the LDS-resident lineariser / Cholesky hold (~90 optimised keyframes): sparse W + HBM Cholesky (BADev::big)
-        const size_t lin_lds = 8 * (8 * (size_t)nfp + (size_t)n_opt * 27 + 4 * (size_t)n_opt * 21 + 4 * (size_t)LIN_RED) + 64;
-        const size_t chol_lds = chol_lds_bytes(nf, nfp);
-        D.big = (lin_lds > 159 * 1024 || chol_lds > 150 * 1024 || nf > CH_MAX_LDS_N) ? 1 : 0;
-        if (ctx->ba_force_large) D.big = 1;                                    // OV2_OPT_BA_FORCE_LARGE: the path on small problems (tests)
-        // beyond ~570 optimised keyframes the big-path linearisers cannot pre-aggregate the observer blocks in LDS either
-        D.lin_direct = (D.big && 8 * ((size_t)n_opt * 27 + 4 * (size_t)LIN_RED) + 64 > 159 * 1024) ? 1 : 0;
-        if (ctx->ba_lin_direct && D.big) D.lin_direct = 1;                     // OV2_OPT_BA_LIN_DIRECT (tests: force it on small problems)
-        D.chol_hbm = D.big; D.lin_waves = 4;
-    }
-    // big path: the slots of the sparse W (one per landmark and optimised keyframe seeing or anchoring it) and their per-keyframe lists
-    std::vector<int> cw_ptr(p->n_lm + 1, 0), cw_col, cw_lm, res_cw, lm_cwa, kfl_ptr(n_opt + 1, 0), kfl_idx;
-    if (D.big) {
-        res_cw.assign(std::max(1, n_act), -1); lm_cwa.assign(std::max(1, p->n_lm), -1);
-        std::vector<int> slot_of(std::max(1, n_opt), -1), touched;
-        for (int l = 0; l < p->n_lm; l++) {
-            cw_ptr[l] = (int)cw_col.size();
-            touched.clear();
-            auto get = [&](int col) {
-                const int ob = col / 6;
-                if (slot_of[ob] < 0) { slot_of[ob] = (int)cw_col.size(); cw_col.push_back(col); cw_lm.push_back(l); touched.push_back(ob); }
-                return slot_of[ob];
-            };
-            if (cnt[l] != cnt[l + 1]) {
-                const int ca = pose_col[p->lm_anchor_kf[l]];
-                if (ca >= 0) lm_cwa[l] = get(ca);
-                for (int k = cnt[l]; k < cnt[l + 1]; k++) {
-                    if (res_type[k] == OV2_RES_RIGHT_ANCH) continue;
-                    const int co = pose_col[res_kf[k]];
-                    if (co >= 0) res_cw[k] = get(co);
-                }
-            }
-            for (int ob : touched) slot_of[ob] = -1;
-        }
-        cw_ptr[p->n_lm] = (int)cw_col.size();
-        for (int c : cw_col) kfl_ptr[c / 6 + 1]++;
-        for (int k = 0; k < n_opt; k++) kfl_ptr[k + 1] += kfl_ptr[k];
-        kfl_idx.resize(cw_col.size());
-        std::vector<int> kfill(kfl_ptr.begin(), kfl_ptr.end() - 1);
-        for (size_t j = 0; j < cw_col.size(); j++) kfl_idx[kfill[cw_col[j] / 6]++] = (int)j;
-    }
-    D.n_cw = (int)cw_col.size();
-    const size_t ncw = (size_t)std::max(1, D.n_cw);
-    const size_t o_x_pose = take(56 * (size_t)p->n_kf), o_c_pose = take(56 * (size_t)p->n_kf), o_x_RT = take(96 * (size_t)p->n_kf), o_c_RT = take(96 * (size_t)p->n_kf);
-    const size_t o_x_lam = take(8 * nl), o_c_lam = take(8 * nl), o_scale_f = take(8 * (size_t)nfp), o_diag_f = take(8 * (size_t)nfp);
-    const size_t o_scale_l = take(8 * nl), o_diag_l = take(8 * nl), o_ete = take(8 * nl), o_etb = take(8 * nl), o_cl = take(8 * nl), o_ce = take(8 * nl);
-    const size_t o_W = take(D.big ? 256 : 8 * nl * nfp), o_H = take(8 * (size_t)nfp * nfp), o_G = take(8 * (size_t)nfp * nfp), o_S = take(8 * (size_t)nfp * nfp);
-    const size_t o_cww = take(48 * ncw), o_cw_ptr = take(4 * (nl + 1)), o_cw_col = take(4 * ncw), o_cw_lm = take(4 * ncw);
-    const size_t o_res_cw = take(4 * na), o_lm_cwa = take(4 * nl), o_kfl_ptr = take(4 * ((size_t)n_opt + 1)), o_kfl_idx = take(4 * ncw);
-    const size_t o_bf = take(8 * (size_t)nfp), o_v = take(8 * (size_t)nfp), o_yf = take(8 * (size_t)nfp), o_yl = take(8 * nl);
-    const size_t o_Linv = take(8 * (size_t)nfp * 32);
-    const size_t o_chi2 = take(8 * nr), o_dpos = take(nr), o_ctl = take(sizeof(BACtl));
-    const size_t o_res_off = take(na), o_bad_obs = take(nr), o_lba_cnt = take(64), o_part = take(8 * 7 * BA_PART_MAX);
-    const size_t npo = (size_t)std::max(1, n_po);
-    const size_t o_po_kf = take(4 * npo), o_po_orig = take(4 * npo), o_po_xyz = take(24 * npo), o_po_uv = take(16 * npo), o_po_sigma = take(8 * npo);
-    dev->pool_bytes = off;
-    if (ext) {
-        std::lock_guard<std::mutex> l(ext->m);
-        if (ext->dev_used + off > ext->dev_cap) { ext->dev_used += al256(off); delete dev; return BA_SLICE_FULL; }
-        dev->pool = ext->dev_base + ext->dev_used; dev->pool_owned = false; ext->dev_used += al256(off);
-    } else if (transient && off <= ((size_t)64 << 20)) {               // (the context keeps the largest pool it has seen: grow-only scratch)
-        const int rcs = ctx->reserve_device(off);
-        if (rcs != OV2_OK) { delete dev; return rcs; }
-        dev->pool = ctx->d_scratch; dev->pool_owned = false;
-    } else {
-        hipError_t e = hipMalloc(&dev->pool, dev->pool_bytes);
-        if (e != hipSuccess) { delete dev; ov2_set_error("hipMalloc(%zu): %s", off, hipGetErrorString(e)); return OV2_ENOMEM; }
-    }
-    uint8_t *b = (uint8_t *)dev->pool;
-    D.pose_col = (int *)(b + o_pose_col); D.lm_ptr = (int *)(b + o_lm_ptr); D.lm_anchor = (int *)(b + o_lm_anchor); D.lm_auv = (double *)(b + o_lm_auv);
-    D.res_type = b + o_res_type; D.res_kf = (int *)(b + o_res_kf); D.res_orig = (int *)(b + o_res_orig); D.res_uv = (double *)(b + o_res_uv); D.res_sigma = (double *)(b + o_res_sigma);
-    D.x_pose = (double *)(b + o_x_pose); D.c_pose = (double *)(b + o_c_pose); D.x_RT = (double *)(b + o_x_RT); D.c_RT = (double *)(b + o_c_RT);
-    D.x_lam = (double *)(b + o_x_lam); D.c_lam = (double *)(b + o_c_lam); D.scale_f = (double *)(b + o_scale_f); D.diag_f = (double *)(b + o_diag_f);
-    D.scale_l = (double *)(b + o_scale_l); D.diag_l = (double *)(b + o_diag_l); D.ete = (double *)(b + o_ete); D.etb = (double *)(b + o_etb);
-    D.part = (double *)(b + o_part);
-    D.cl = (double *)(b + o_cl); D.ce = (double *)(b + o_ce); D.W = (double *)(b + o_W); D.H = (double *)(b + o_H); D.G = (double *)(b + o_G); D.S = (double *)(b + o_S);
-    D.Linv = (double *)(b + o_Linv);
-    D.cww = (double *)(b + o_cww); D.cw_ptr = (int *)(b + o_cw_ptr); D.cw_col = (int *)(b + o_cw_col); D.cw_lm = (int *)(b + o_cw_lm);
-    D.res_cw = (int *)(b + o_res_cw); D.lm_cwa = (int *)(b + o_lm_cwa); D.kfl_ptr = (int *)(b + o_kfl_ptr); D.kfl_idx = (int *)(b + o_kfl_idx);
-    D.bf = (double *)(b + o_bf); D.v = (double *)(b + o_v); D.yf = (double *)(b + o_yf); D.yl = (double *)(b + o_yl);
-    D.chi2 = (double *)(b + o_chi2); D.dpos = b + o_dpos; D.ctl = (BACtl *)(b + o_ctl);
-    dev->lm_order = (int *)(b + o_lm_order);
-    D.lm_order_b = dev->lm_order; D.pose0 = (const double *)(b + o_pose0); D.lam0 = (const double *)(b + o_lam0);
-    D.res_off = b + o_res_off; D.lm_live = b + o_lm_live; D.bad_obs = b + o_bad_obs; D.lba_cnt = (int *)(b + o_lba_cnt);
-    D.po_kf = (int *)(b + o_po_kf); D.po_orig = (int *)(b + o_po_orig); D.po_xyz = (double *)(b + o_po_xyz); D.po_uv = (double *)(b + o_po_uv); D.po_sigma = (double *)(b + o_po_sigma);
-    for (int i = 0; i < 4; i++) { D.calib_l[i] = p->calib_l[i]; D.calib_r[i] = p->calib_r[i]; }
-    {   // Trl: normalised quaternion -> R (host)
-        double q[4] = {p->T_rl[3], p->T_rl[4], p->T_rl[5], p->T_rl[6]};
-        const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        if (n > 0) { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; } else { q[0] = q[1] = q[2] = 0; q[3] = 1; }
-        const double x = q[0], y = q[1], z = q[2], w = q[3];
-        D.Rrl[0] = 1 - 2 * (y * y + z * z); D.Rrl[1] = 2 * (x * y - z * w); D.Rrl[2] = 2 * (x * z + y * w);
-        D.Rrl[3] = 2 * (x * y + z * w); D.Rrl[4] = 1 - 2 * (x * x + z * z); D.Rrl[5] = 2 * (y * z - x * w);
-        D.Rrl[6] = 2 * (x * z - y * w); D.Rrl[7] = 2 * (y * z + x * w); D.Rrl[8] = 1 - 2 * (x * x + y * y);
-        D.trl[0] = p->T_rl[0]; D.trl[1] = p->T_rl[1]; D.trl[2] = p->T_rl[2];
-    }
-    hipStream_t s = ctx->stream;
-#define UP(dst, src, bytes) do { if ((bytes) > 0) { hipError_t _e = hipMemcpyAsync((void *)(dst), (src), (bytes), hipMemcpyHostToDevice, s); \
-        if (_e != hipSuccess) { if (dev->pool_owned) (void)hipFree(dev->pool); delete dev; ov2_set_error("H2D: %s", hipGetErrorString(_e)); return OV2_EHIP; } } } while (0)
-    {   // the small arrays join the residual arrays in the staging mirror; landmarks are processed anchor by anchor (lm_order)
-        int *lm_order = (int *)(hs + o_lm_order);
-        {   // stable counting sort by anchor keyframe (a std::stable_sort of 3000 landmarks was 60 us of a 0.45 ms call)
-            std::vector<int> first((size_t)p->n_kf + 1, 0);
-            for (int l = 0; l < p->n_lm; l++) first[(size_t)p->lm_anchor_kf[l] + 1]++;
-            for (int k = 0; k < p->n_kf; k++) first[(size_t)k + 1] += first[(size_t)k];
-            for (int l = 0; l < p->n_lm; l++) lm_order[first[(size_t)p->lm_anchor_kf[l]]++] = l;
-        }
-        uint8_t *lm_live = hs + o_lm_live;
-        for (int l = 0; l < p->n_lm; l++) lm_live[l] = cnt[l] != cnt[l + 1];
-        memcpy(hs + o_pose_col, pose_col.data(), 4 * (size_t)p->n_kf);
-        memcpy(hs + o_lm_ptr, cnt.data(), 4 * ((size_t)p->n_lm + 1));
-        if (p->n_lm > 0) { memcpy(hs + o_lm_anchor, p->lm_anchor_kf, 4 * (size_t)p->n_lm); memcpy(hs + o_lm_auv, p->lm_anchor_uv, 16 * (size_t)p->n_lm); }
-        memcpy(hs + o_pose0, p->poses, 56 * (size_t)p->n_kf);
-        if (p->n_lm > 0) memcpy(hs + o_lam0, p->invdepth, 8 * (size_t)p->n_lm);
-    }
-    clap("views + small arrays + lm_order");
-    UP(b, hs, up_bytes);                                               // ONE copy: pose_col .. lam0
-    if (!ext) {                                                        // (batch: k_ba_reset_B clears them)
-        hipError_t em = hipMemsetAsync(D.res_off, 0, na, s);
-        if (em == hipSuccess) em = hipMemsetAsync(D.bad_obs, 0, nr, s);
-        if (em == hipSuccess) em = hipMemsetAsync(D.lba_cnt, 0, 64, s);
-        if (em != hipSuccess) { ov2_set_error("hipMemsetAsync: %s", hipGetErrorString(em)); ba_destroy(dev); return OV2_EHIP; }
-    }
-    UP(D.po_kf, po_kf, 4 * (size_t)n_po); UP(D.po_orig, po_orig, 4 * (size_t)n_po);
-    UP(D.po_xyz, po_xyz, 24 * (size_t)n_po); UP(D.po_uv, po_uv, 16 * (size_t)n_po); UP(D.po_sigma, po_sigma, 8 * (size_t)n_po);
-    if (D.big) {
-        UP(D.cw_ptr, cw_ptr.data(), 4 * ((size_t)p->n_lm + 1)); UP(D.cw_col, cw_col.data(), 4 * (size_t)D.n_cw); UP(D.cw_lm, cw_lm.data(), 4 * (size_t)D.n_cw);
-        UP(D.res_cw, res_cw.data(), 4 * (size_t)n_act); UP(D.lm_cwa, lm_cwa.data(), 4 * (size_t)p->n_lm);
-        UP(D.kfl_ptr, kfl_ptr.data(), 4 * ((size_t)n_opt + 1)); UP(D.kfl_idx, kfl_idx.data(), 4 * (size_t)D.n_cw);
-    }
-#undef UP
-    // the staging vectors die at return: make sure the copies are done (a batch slice's staging lives until the batch is through)
-    if (!ext || D.big) {
-        const hipError_t es = hipStreamSynchronize(s);
-        if (es != hipSuccess) { ov2_set_error("hipStreamSynchronize: %s", hipGetErrorString(es)); ba_destroy(dev); return OV2_EHIP; }
-    }
-    clap("upload enqueued + synchronised");
-    *out = dev;
-    return OV2_OK;
-}
-
-// 3-D point landmarks with variable poses (ldim = 3): same device object, point-sorted residual blocks
-static int xyzba_create(ov2_ctx *ctx, const ov2_xyzba_problem *p, ov2_ba_dev **out)
-{
-    OV2_REQUIRE(p && out, OV2_EINVAL, "NULL problem");
-    OV2_REQUIRE(p->n_kf > 0 && p->n_pts >= 0 && p->n_res >= 0, OV2_EINVAL, "bad problem sizes");
-    OV2_REQUIRE(p->poses, OV2_EINVAL, "NULL pose array");
-    OV2_REQUIRE(p->n_pts == 0 || p->xyz, OV2_EINVAL, "NULL point array");
-    OV2_REQUIRE(p->n_res == 0 || (p->res_type && p->res_kf && p->res_pt && p->res_uv && p->res_sigma), OV2_EINVAL, "NULL residual arrays");
-    std::vector<int> cnt(p->n_pts + 1, 0);
-    int n_act = 0;
-    for (int i = 0; i < p->n_res; i++) {
-        if (p->res_active && !p->res_active[i]) continue;
-        OV2_REQUIRE(p->res_type[i] <= OV2_XYZ_RIGHT, OV2_EINVAL, "unknown residual type");
-        OV2_REQUIRE(p->res_sigma[i] > 0, OV2_EINVAL, "res_sigma must be positive");
-        OV2_REQUIRE(p->res_pt[i] >= 0 && p->res_pt[i] < p->n_pts, OV2_EINVAL, "res_pt out of range");
-        OV2_REQUIRE(p->res_kf[i] >= 0 && p->res_kf[i] < p->n_kf, OV2_EINVAL, "res_kf out of range");
-        cnt[p->res_pt[i] + 1]++; n_act++;
-    }
-    for (int l = 0; l < p->n_pts; l++) cnt[l + 1] += cnt[l];
-    std::vector<int> pose_col(p->n_kf);
-    int n_opt = 0;
-    for (int k = 0; k < p->n_kf; k++) pose_col[k] = (p->kf_const && p->kf_const[k]) ? -1 : 6 * n_opt++;
-    const int nf = 6 * n_opt, nfp = std::max(BA_TILE, (nf + BA_TILE - 1) / BA_TILE * BA_TILE);
-    // Size limits BEFORE anything is allocated or uploaded (W and W' alone are 2 x 24 n_pts nfp bytes).  The 3-D point form keeps
-    // W dense: its lineariser holds 3 rows of it per wavefront in LDS next to the observer blocks (4 wavefronts per work-group up
-    // to ~200 optimised keyframes, then 2, then 1: ~450), and beyond ~90 keyframes the reduced system is factored by the
-    // multi-kernel Cholesky on HBM instead of the one-work-group LDS kernel.
-    int lin_waves = 0;
-    for (int nw = 4; nw >= 1 && !lin_waves; nw >>= 1)
-        if (8 * (3 * (size_t)nw * nfp + (size_t)n_opt * 27) + 64 <= 159 * 1024) lin_waves = nw;
-    if (ctx->ba_xyz_lin_waves == 1 || ctx->ba_xyz_lin_waves == 2) lin_waves = lin_waves ? std::min(lin_waves, ctx->ba_xyz_lin_waves) : 0;   // OV2_OPT_BA_XYZ_LIN_WAVES (tests)
-    if (!lin_waves || nfp > BA_MAX_NFP) {
-        ov2_set_error("too many optimised keyframes (%d) for the 3-D point form (limit ~450: dense W rows in LDS)", n_opt);
-        return OV2_EUNSUPPORTED;
-    }
-    const size_t chol_lds_res = chol_lds_bytes(nf, nfp);
-    int chol_hbm = (chol_lds_res > 150 * 1024 || nf > CH_MAX_LDS_N) ? 1 : 0;
-    if (ctx->ba_force_large) chol_hbm = 1;                                      // OV2_OPT_BA_FORCE_LARGE (tests: the HBM factorisation on small problems)
-    std::vector<int> fill(cnt.begin(), cnt.end() - 1), res_kf(n_act), res_orig(n_act);
-    std::vector<uint8_t> res_type(n_act);
-    std::vector<double> res_uv(2 * (size_t)n_act), res_sigma(n_act);
-    for (int i = 0; i < p->n_res; i++) {
-        if (p->res_active && !p->res_active[i]) continue;
-        const int k = fill[p->res_pt[i]]++;
-        res_type[k] = p->res_type[i]; res_kf[k] = p->res_kf[i]; res_orig[k] = i;
-        res_uv[2 * k] = p->res_uv[2 * i]; res_uv[2 * k + 1] = p->res_uv[2 * i + 1]; res_sigma[k] = p->res_sigma[i];
-    }
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    ov2_ba_dev *dev = new (std::nothrow) ov2_ba_dev();
-    OV2_REQUIRE(dev != nullptr, OV2_ENOMEM, "out of host memory");
-    dev->device = ctx->device; dev->n_res = p->n_res;
-    dev->h_poses0.assign(p->poses, p->poses + 7 * (size_t)p->n_kf);
-    dev->h_lam0.assign(p->xyz, p->xyz + 3 * (size_t)(p->n_pts > 0 ? p->n_pts : 0));
-    BADev &D = dev->D;
-    memset(&D, 0, sizeof(D));
-    D.n_kf = p->n_kf; D.n_lm = p->n_pts; D.n_act = n_act; D.nf = nf; D.nfp = nfp; D.n_po = 0; D.ldim = 3;
-    D.chol_hbm = chol_hbm; D.lin_waves = lin_waves;
-    const size_t nl = (size_t)std::max(1, p->n_pts), na = (size_t)std::max(1, n_act), nr = (size_t)std::max(1, p->n_res);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
-    const size_t o_pose_col = take(4 * (size_t)p->n_kf), o_lm_ptr = take(4 * (nl + 1));
-    const size_t o_res_type = take(na), o_res_kf = take(4 * na), o_res_orig = take(4 * na), o_res_uv = take(16 * na), o_res_sigma = take(8 * na);
-    const size_t o_x_pose = take(56 * (size_t)p->n_kf), o_c_pose = take(56 * (size_t)p->n_kf), o_x_RT = take(96 * (size_t)p->n_kf), o_c_RT = take(96 * (size_t)p->n_kf);
-    const size_t o_x_lam = take(24 * nl), o_c_lam = take(24 * nl), o_scale_f = take(8 * (size_t)nfp), o_diag_f = take(8 * (size_t)nfp);
-    const size_t o_scale_l = take(24 * nl), o_diag_l = take(24 * nl), o_etb = take(24 * nl), o_yl = take(24 * nl), o_ep = take(24 * nl), o_ones = take(24 * nl);
-    const size_t o_ete6 = take(48 * nl), o_minv6 = take(48 * nl);
-    const size_t o_W = take(24 * nl * nfp), o_Wp = take(24 * nl * nfp);
-    const size_t o_H = take(8 * (size_t)nfp * nfp), o_G = take(8 * (size_t)nfp * nfp), o_S = take(8 * (size_t)nfp * nfp);
-    const size_t o_bf = take(8 * (size_t)nfp), o_v = take(8 * (size_t)nfp), o_yf = take(8 * (size_t)nfp), o_Linv = take(8 * (size_t)nfp * 32);
-    const size_t o_chi2 = take(8 * nr), o_dpos = take(nr), o_ctl = take(sizeof(BACtl));
-    dev->pool_bytes = off;
-    hipError_t e = hipMalloc(&dev->pool, dev->pool_bytes);
-    if (e != hipSuccess) { delete dev; ov2_set_error("hipMalloc(%zu): %s", off, hipGetErrorString(e)); return OV2_ENOMEM; }
-    uint8_t *b = (uint8_t *)dev->pool;
-    D.pose_col = (int *)(b + o_pose_col); D.lm_ptr = (int *)(b + o_lm_ptr);
-    D.res_type = b + o_res_type; D.res_kf = (int *)(b + o_res_kf); D.res_orig = (int *)(b + o_res_orig); D.res_uv = (double *)(b + o_res_uv); D.res_sigma = (double *)(b + o_res_sigma);
-    D.x_pose = (double *)(b + o_x_pose); D.c_pose = (double *)(b + o_c_pose); D.x_RT = (double *)(b + o_x_RT); D.c_RT = (double *)(b + o_c_RT);
-    D.x_lam = (double *)(b + o_x_lam); D.c_lam = (double *)(b + o_c_lam); D.scale_f = (double *)(b + o_scale_f); D.diag_f = (double *)(b + o_diag_f);
-    D.scale_l = (double *)(b + o_scale_l); D.diag_l = (double *)(b + o_diag_l); D.etb = (double *)(b + o_etb); D.yl = (double *)(b + o_yl);
-    D.ep = (double *)(b + o_ep); D.ones = (double *)(b + o_ones); D.ete6 = (double *)(b + o_ete6); D.minv6 = (double *)(b + o_minv6);
-    D.W = (double *)(b + o_W); D.Wp = (double *)(b + o_Wp); D.H = (double *)(b + o_H); D.G = (double *)(b + o_G); D.S = (double *)(b + o_S);
-    D.bf = (double *)(b + o_bf); D.v = (double *)(b + o_v); D.yf = (double *)(b + o_yf); D.Linv = (double *)(b + o_Linv);
-    D.chi2 = (double *)(b + o_chi2); D.dpos = b + o_dpos; D.ctl = (BACtl *)(b + o_ctl);
-    D.cl = D.ones; D.ce = D.ep; D.ete = D.ete6;              // (scalar-landmark views, unused when ldim == 3)
-    for (int i = 0; i < 4; i++) { D.calib_l[i] = p->calib_l[i]; D.calib_r[i] = p->calib_r[i]; }
-    {
-        double q[4] = {p->T_rl[3], p->T_rl[4], p->T_rl[5], p->T_rl[6]};
-        const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        if (n > 0) { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; } else { q[0] = q[1] = q[2] = 0; q[3] = 1; }
-        const double x = q[0], y = q[1], z = q[2], w = q[3];
-        D.Rrl[0] = 1 - 2 * (y * y + z * z); D.Rrl[1] = 2 * (x * y - z * w); D.Rrl[2] = 2 * (x * z + y * w);
-        D.Rrl[3] = 2 * (x * y + z * w); D.Rrl[4] = 1 - 2 * (x * x + z * z); D.Rrl[5] = 2 * (y * z - x * w);
-        D.Rrl[6] = 2 * (x * z - y * w); D.Rrl[7] = 2 * (y * z + x * w); D.Rrl[8] = 1 - 2 * (x * x + y * y);
-        D.trl[0] = p->T_rl[0]; D.trl[1] = p->T_rl[1]; D.trl[2] = p->T_rl[2];
-    }
-    hipStream_t s = ctx->stream;
-#define UPX(dst, src, bytes) do { if ((bytes) > 0) { hipError_t _e = hipMemcpyAsync((void *)(dst), (src), (bytes), hipMemcpyHostToDevice, s); \
-        if (_e != hipSuccess) { (void)hipFree(dev->pool); delete dev; ov2_set_error("H2D: %s", hipGetErrorString(_e)); return OV2_EHIP; } } } while (0)
-    UPX(D.pose_col, pose_col.data(), 4 * (size_t)p->n_kf);
-    UPX(D.lm_ptr, cnt.data(), 4 * ((size_t)p->n_pts + 1));
-    UPX(D.res_type, res_type.data(), (size_t)n_act);
-    UPX(D.res_kf, res_kf.data(), 4 * (size_t)n_act);
-    UPX(D.res_orig, res_orig.data(), 4 * (size_t)n_act);
-    UPX(D.res_uv, res_uv.data(), 16 * (size_t)n_act);
-    UPX(D.res_sigma, res_sigma.data(), 8 * (size_t)n_act);
-#undef UPX
-    {
-        const hipError_t es = hipStreamSynchronize(s);
-        if (es != hipSuccess) { ov2_set_error("hipStreamSynchronize: %s", hipGetErrorString(es)); ba_destroy(dev); return OV2_EHIP; }
-    }
-    *out = dev;
-    return OV2_OK;
-}
-
-static void ba_destroy(ov2_ba_dev *dev)
-{
-    if (!dev) return;
-    (void)hipSetDevice(dev->device);
-    if (dev->pool && dev->pool_owned) (void)hipFree(dev->pool);
-    delete dev;
-}
+#include "ba_problem.hpp"       // ov2_ba_dev, ba_create / xyzba_create / ba_destroy, the batch slices and the host thread pool
 
 // state reset of a solve in ONE launch (round 5; single problems: it replaces two pageable H2D copies of the initial parameters, six
 // memsets and the upload of the control block -- 60-80 us of host time per pass): x = initial parameters, chi2 = "never evaluated",
@@ -3028,23 +1746,98 @@ __device__ __forceinline__ void b_ba_reset(const BADev &D, const BACtl &ctl0, in
 __global__ __launch_bounds__(256) void k_ba_reset(BADev D, BACtl ctl0, int keep_state, int host_chi2) { b_ba_reset(D, ctl0, keep_state, host_chi2); }
 __global__ __launch_bounds__(256) void k_ba_reset_B(const BADev *__restrict__ arr, BACtl ctl0, int keep_state) { b_ba_reset(arr[blockIdx.z], ctl0, keep_state, 0); }
 
+// ---------------------------------------------------------------------------------- host LM driver (single solve and lock-step batch)
+static int ba_check_options(const ov2_ba_options *o)
+{
+    OV2_REQUIRE(o->max_iter >= 0 && o->initial_radius > 0 && o->min_lm_diagonal > 0 && o->min_lm_diagonal <= o->max_lm_diagonal,
+                OV2_EINVAL, "bad solver options");
+    return OV2_OK;
+}
+
+// Waits until the outcome of iteration `it` of all n problems is known: k_ba_decide stores 2 * iteration + done into each problem's
+// pinned word (a finished problem reports `done` on its way out).  *all_done: every problem has terminated.
+static int ba_wait_outcome(hipStream_t s, const volatile int *flag, int n, int it, bool *all_done)
+{
+    for (unsigned spins = 0;;) {
+        int known = 0, done = 0;
+        for (int i = 0; i < n; i++) { const int f = flag[i]; known += f >= 2 * it; done += f >= 0 && (f & 1); }
+        *all_done = done == n;
+        if (known == n) return OV2_OK;
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
+        __builtin_ia32_pause();                                               // the estimator thread shares its core's siblings with the SLAM / mapper threads
+#endif
+        if ((++spins & 0x3FFFFFu) == 0) {                                 // (a watchdog, ~every 0.3 s: a query per wait put a 6 us bubble in front of the next launch)
+            const hipError_t q = hipStreamQuery(s);
+            if (q == hipSuccess) {                                    // everything enqueued has run: the words are final
+                done = 0;
+                for (int i = 0; i < n; i++) done += flag[i] >= 0 && (flag[i] & 1);
+                *all_done = done == n;
+                return OV2_OK;
+            }
+            if (q != hipErrorNotReady) OV2_HIP_CHECK(q);
+        }
+    }
+}
+
+// The LM loop, enqueued half an iteration ahead.  The first half of iteration `it` (bookkeeping, Schur complement, factorisation:
+// ~265 us of config 4's ~385) goes into the stream BEFORE the outcome of iteration it - 1 is known; k_ba_decide stores that outcome
+// into pinned host memory, and the second half (back-substitution .. decision, re-linearisation) follows when the host has seen
+// it -- while the GPU is still busy with the first half, so the stream never drains.  A solve that converges pays four empty
+// launches (every kernel starts with `if (ctl->done) return`): the two-iteration chunks of rounds 2-3 paid 18 plus a 4-byte
+// device-to-host copy + event per chunk, a whole iteration of look-ahead 9.
+// first_half(it), second_half(it): the caller's launches; bookkeeping(O): its k_ba_iter_begin launch outside an iteration.
+template <class F1, class F2, class FB>
+static int ba_lm_loop(hipStream_t s, const ov2_ba_options *o, const BAOpt &O, const volatile int *flag, int n, F1 first_half, F2 second_half, FB bookkeeping)
+{
+    const auto t_start = std::chrono::steady_clock::now();
+    for (int it = 0; it < o->max_iter; it++) {
+        if (it > 0 && o->max_solver_time_s > 0.0) {
+            // Ceres tests total_time >= max_solver_time_in_seconds at the top of every iteration; here against the time the DEVICE
+            // has actually spent (wait for the previous iteration first, otherwise only the enqueue is timed)
+            OV2_HIP_CHECK(hipStreamSynchronize(s));
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() >= o->max_solver_time_s) {
+                // the regular per-iteration bookkeeping with an iteration budget of zero: it finalises the last step (successful
+                // step count, minimum cost, cost of a fresh linearisation) and terminates with NO_CONVERGENCE
+                BAOpt Ostop = O;
+                Ostop.max_iter = 0;
+                bookkeeping(Ostop);
+                break;
+            }
+        }
+        first_half(it);
+        if (it >= 1) {
+            bool all_done = false;
+            const int rc = ba_wait_outcome(s, flag, n, it - 1, &all_done);
+            if (rc != OV2_OK) return rc;
+            if (all_done) break;
+        }
+        second_half(it);
+    }
+    bookkeeping(O);                                        // final bookkeeping
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
+static void ba_fill_result(ov2_ba_result *r, const BACtl &c, float ms)
+{
+    r->iterations = c.n_steps; r->num_successful_steps = c.n_success; r->termination = c.termination;
+    r->initial_cost = c.initial_cost; r->final_cost = c.minimum_cost; r->solve_ms = ms;
+}
+
 // keep_state: continue from the parameters and the cached chi2 / depth flags that are on the device (second pass of
 // ov2_local_ba) instead of resetting to the problem's initial values
 static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba_result *r,
                   const double *chi2_init, const uint8_t *dpos_init, bool keep_state = false)
 {
     OV2_REQUIRE(o && r, OV2_EINVAL, "NULL options/result");
-    OV2_REQUIRE(o->max_iter >= 0 && o->initial_radius > 0 && o->min_lm_diagonal > 0 && o->min_lm_diagonal <= o->max_lm_diagonal,
-                OV2_EINVAL, "bad solver options");
+    const int rc_o = ba_check_options(o);
+    if (rc_o != OV2_OK) return rc_o;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     BADev D = dev->D;
     D.huber = o->huber_delta;
     D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
     hipStream_t s = ctx->stream;
-    BAOpt O;
-    O.max_iter = o->max_iter; O.ftol = o->function_tolerance; O.gtol = o->gradient_tolerance; O.ptol = o->parameter_tolerance;
-    O.max_radius = o->max_radius; O.min_radius = o->min_radius; O.min_diag = o->min_lm_diagonal; O.max_diag = o->max_lm_diagonal;
-    O.min_rel_decrease = o->min_relative_decrease; O.jacobi = o->jacobi_scaling; O.max_invalid = o->max_consecutive_invalid_steps;
+    const BAOpt O = ba_opt_from(*o);
 
     // size limits first: nothing is created or enqueued for a problem this path cannot solve
     const int n_opt = D.nf / 6;
@@ -3105,18 +1898,13 @@ static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba
     else OV2_HIP_CHECK(hipMemsetAsync(D.dpos, 0, (size_t)std::max(1, dev->n_res), s));
     }
     OV2_HIP_CHECK(hipEventRecord(e0, s));
-    BACtl h_ctl;
-    memset(&h_ctl, 0, sizeof(h_ctl));
-    h_ctl.radius = o->initial_radius; h_ctl.decrease_factor = 2.0; h_ctl.x_norm = -1.0;
-    h_ctl.need_lin = 1; h_ctl.step_successful = 1;
-    h_ctl.termination = OV2_TERM_NO_CONVERGENCE;
-    h_ctl.cur.gradient_norm = NAN;                          // (the device forms the max norm only)
     ctx->ba_trace_n = 0;
     if (ctx->ba_trace) {
         if (!ctx->ba_trace_d) OV2_HIP_CHECK(hipMalloc(&ctx->ba_trace_d, sizeof(BAIterRec) * BA_TRACE_CAP));
         if (!ctx->ba_trace_h) { ctx->ba_trace_h = malloc(sizeof(BAIterRec) * BA_TRACE_CAP); OV2_REQUIRE(ctx->ba_trace_h, OV2_ENOMEM, "trace buffer"); }
-        h_ctl.trace = (BAIterRec *)ctx->ba_trace_d;
     }
+    BACtl h_ctl;
+    ba_ctl_init(h_ctl, o->initial_radius, ctx->ba_trace ? (BAIterRec *)ctx->ba_trace_d : nullptr);
     // one optimised pose, pose-only residual blocks, no landmarks (ceresPnP): the whole loop in one kernel (OV2_OPT_BA_POSE_ONLY_FUSED
     // = 0 keeps the multi-kernel path for A/B runs)
     const bool fused_po = fused_po_path;
@@ -3203,12 +1991,6 @@ static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba
     };
     linearize();
     if (!one_reset) OV2_HIP_CHECK(hipMemsetAsync(D.G, 0, 8 * (size_t)D.nfp * D.nfp, s));    // (every later iteration: cleared by the back-substitution kernel)
-    // The LM loop is enqueued half an iteration ahead.  The first half of iteration `it` (bookkeeping, Schur complement, factorisation:
-    // ~265 us of config 4's ~385) goes into the stream BEFORE the outcome of iteration it - 1 is known; k_ba_decide stores that outcome
-    // into pinned host memory, and the second half (back-substitution .. decision, re-linearisation) follows when the host has seen
-    // it -- while the GPU is still busy with the first half, so the stream never drains.  A solve that converges pays four empty
-    // launches (every kernel starts with `if (ctl->done) return`): the two-iteration chunks of rounds 2-3 paid 18 plus a 4-byte
-    // device-to-host copy + event per chunk, a whole iteration of look-ahead 9.
     int rc_h = ctx->reserve_host(64);
     if (rc_h != OV2_OK) return rc_h;
     volatile int *flag_h = (volatile int *)ctx->h_scratch;
@@ -3244,42 +2026,9 @@ static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba
         hipLaunchKernelGGL(k_ba_decide, dim3(1), dim3(1024), 0, s, D, O, it);
         linearize();
     };
-    const auto t_start = std::chrono::steady_clock::now();
-    for (int it = 0; it < o->max_iter; it++) {
-        if (it > 0 && o->max_solver_time_s > 0.0) {
-            // Ceres tests total_time >= max_solver_time_in_seconds at the top of every iteration; here against the time the DEVICE
-            // has actually spent (wait for the previous iteration first, otherwise only the enqueue is timed)
-            OV2_HIP_CHECK(hipStreamSynchronize(s));
-            const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-            if (el >= o->max_solver_time_s) {
-                // the regular per-iteration bookkeeping with an iteration budget of zero: it finalises the last step (successful
-                // step count, minimum cost, cost of a fresh linearisation) and terminates with NO_CONVERGENCE
-                BAOpt Ostop = O;
-                Ostop.max_iter = 0;
-                hipLaunchKernelGGL(k_ba_iter_begin, dim3(1), dim3(1024), 0, s, D, Ostop, -1);
-                break;
-            }
-        }
-        first_half(it);
-        if (it >= 1) {
-            // outcome of iteration it - 1 (k_ba_decide of that iteration)
-            unsigned spins = 0;
-            while (flag_h[0] < 2 * (it - 1)) {
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
-                __builtin_ia32_pause();                                               // the estimator thread shares its core's siblings with the SLAM / mapper threads
-#endif
-                if ((++spins & 0x3FFFFFu) == 0) {                                 // (a watchdog, ~every 0.3 s: a query per wait put a 6 us bubble in front of the next launch)
-                    const hipError_t q = hipStreamQuery(s);
-                    if (q == hipSuccess) break;                               // everything enqueued has run: the word is final
-                    if (q != hipErrorNotReady) OV2_HIP_CHECK(q);
-                }
-            }
-            if (flag_h[0] >= 0 && (flag_h[0] & 1)) break;
-        }
-        second_half(it);
-    }
-    hipLaunchKernelGGL(k_ba_iter_begin, dim3(1), dim3(1024), 0, s, D, O, -1);    // final bookkeeping
-    OV2_HIP_CHECK(hipGetLastError());
+    const int rc_l = ba_lm_loop(s, o, O, flag_h, 1, first_half, second_half,
+                                [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin, dim3(1), dim3(1024), 0, s, D, Ob, -1); });
+    if (rc_l != OV2_OK) return rc_l;
     }
     OV2_HIP_CHECK(hipEventRecord(e1, s));
     // results
@@ -3296,9 +2045,7 @@ static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba
     }
     float ms = 0;
     OV2_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    r->iterations = h_ctl.n_steps; r->num_successful_steps = h_ctl.n_success;
-    r->initial_cost = h_ctl.initial_cost; r->final_cost = h_ctl.minimum_cost; r->termination = h_ctl.termination;
-    r->solve_ms = ms;
+    ba_fill_result(r, h_ctl, ms);
     if (ctx->debug)
         fprintf(stderr, "[ov2 ba] cholesky ticks (100MHz): copy-in %llu pivot+panel %llu write-back %llu trailing %llu block inverses %llu solves %llu\n",
                 h_ctl.dbg[0], h_ctl.dbg[1], h_ctl.dbg[2], h_ctl.dbg[3], h_ctl.dbg[4], h_ctl.dbg[5]);
@@ -3353,14 +2100,11 @@ struct BABatch {
 // one LM solve of every problem of the batch (ba_run's loop on batched launches); skip[i]: the problem sits this pass out
 static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const double *huber, const uint8_t *skip, bool keep_state, float *ms_out)
 {
-    OV2_REQUIRE(o->max_iter >= 0 && o->initial_radius > 0 && o->min_lm_diagonal > 0 && o->min_lm_diagonal <= o->max_lm_diagonal,
-                OV2_EINVAL, "bad solver options");
+    const int rc_o = ba_check_options(o);
+    if (rc_o != OV2_OK) return rc_o;
     const int N = (int)B.devs.size();
     hipStream_t s = ctx->stream;
-    BAOpt O;
-    O.max_iter = o->max_iter; O.ftol = o->function_tolerance; O.gtol = o->gradient_tolerance; O.ptol = o->parameter_tolerance;
-    O.max_radius = o->max_radius; O.min_radius = o->min_radius; O.min_diag = o->min_lm_diagonal; O.max_diag = o->max_lm_diagonal;
-    O.min_rel_decrease = o->min_relative_decrease; O.jacobi = o->jacobi_scaling; O.max_invalid = o->max_consecutive_invalid_steps;
+    const BAOpt O = ba_opt_from(*o);
     int lin_blocks = 1, bs_blocks = 1, cost_blocks = 1, nupper = 1, ksplit_max = 1, nf_max = 0, nfp_max = 0, reset_blocks = 1, init_blocks = 1;
     size_t lin_lds = 0, chol_lds = 0;
     // a single problem spreads over the whole chip for latency (16 landmarks per lineariser work-group, 1024 Schur work-groups); a batch
@@ -3403,9 +2147,7 @@ static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const
     struct { hipEvent_t e0, e1; } ev{ctx->ba_ev[0], ctx->ba_ev[1]};
     OV2_HIP_CHECK(hipEventRecord(ev.e0, s));
     BACtl c0;
-    memset(&c0, 0, sizeof(c0));
-    c0.radius = o->initial_radius; c0.decrease_factor = 2.0; c0.x_norm = -1.0;
-    c0.need_lin = 1; c0.step_successful = 1; c0.termination = OV2_TERM_NO_CONVERGENCE;
+    ba_ctl_init(c0, o->initial_radius, nullptr);
     const BADev *A = B.d_arr;
     const unsigned Z = (unsigned)N;
     if (B.lm_live_first) {
@@ -3430,51 +2172,47 @@ static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const
         linearize();
     };
     linearize();
-    const auto t_start = std::chrono::steady_clock::now();
-    for (int it = 0; it < o->max_iter; it++) {
-        if (it > 0 && o->max_solver_time_s > 0.0) {
-            // (the budget of ba_run, against the time the device has spent on the batch)
-            OV2_HIP_CHECK(hipStreamSynchronize(s));
-            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() >= o->max_solver_time_s) {
-                BAOpt Ostop = O;
-                Ostop.max_iter = 0;
-                hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, Ostop, -1);
-                break;
-            }
-        }
-        first_half(it);
-        if (it >= 1) {
-            // the outcome of iteration it - 1 of EVERY problem (a finished problem's k_ba_decide reports `done` on its way out)
-            unsigned spins = 0;
-            bool all_done = false;
-            for (;;) {
-                int known = 0, done = 0;
-                for (int i = 0; i < N; i++) { const int f = B.h_flag[i]; known += f >= 2 * (it - 1); done += f >= 0 && (f & 1); }
-                if (known == N) { all_done = done == N; break; }
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
-                __builtin_ia32_pause();
-#endif
-                if ((++spins & 0xFFFFFu) == 0) {
-                    const hipError_t q = hipStreamQuery(s);
-                    if (q == hipSuccess) {
-                        all_done = true;
-                        for (int i = 0; i < N; i++) all_done = all_done && B.h_flag[i] >= 0 && (B.h_flag[i] & 1);
-                        break;
-                    }
-                    if (q != hipErrorNotReady) OV2_HIP_CHECK(q);
-                }
-            }
-            if (all_done) break;
-        }
-        second_half(it);
-    }
-    hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O, -1);    // final bookkeeping
-    OV2_HIP_CHECK(hipGetLastError());
+    const int rc_l = ba_lm_loop(s, o, O, B.h_flag, N, first_half, second_half,
+                                [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, Ob, -1); });
+    if (rc_l != OV2_OK) return rc_l;
     OV2_HIP_CHECK(hipEventRecord(ev.e1, s));
     OV2_HIP_CHECK(hipMemcpyAsync(B.h_ctl, B.d_ctl, sizeof(BACtl) * (size_t)N, hipMemcpyDeviceToHost, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));
     OV2_HIP_CHECK(hipEventElapsedTime(ms_out, ev.e0, ev.e1));
     return OV2_OK;
+}
+
+// ---------------------------------------------------------------------------------- the two-pass localBA protocol (single and batch)
+static void local_ba_clear_result(ov2_local_ba_result &r)
+{
+    r.l2_done = 0; r.pass2_error = OV2_OK; r.n_bad_pass1 = 0; r.n_bad_total = 0; r.status = OV2_OK;
+    for (int q = 0; q < 2; q++) { r.iterations[q] = 0; r.num_successful_steps[q] = 0; r.termination[q] = OV2_TERM_NO_CONVERGENCE; r.initial_cost[q] = r.final_cost[q] = 0; r.solve_ms[q] = 0; }
+}
+
+// the summary of a finished pass (q = 0, 1) into its slot
+static void local_ba_store_pass(ov2_local_ba_result &r, int q, const ov2_ba_result &b)
+{
+    r.iterations[q] = b.iterations; r.num_successful_steps[q] = b.num_successful_steps; r.termination[q] = b.termination;
+    r.initial_cost[q] = b.initial_cost; r.final_cost[q] = b.final_cost; r.solve_ms[q] = b.solve_ms;
+}
+static void local_ba_store_pass(ov2_local_ba_result &r, int q, const BACtl &c, float ms)
+{
+    ov2_ba_result b;
+    ba_fill_result(&b, c, ms);
+    local_ba_store_pass(r, q, b);
+}
+
+// Huber's delta of the first pass (<= 0: trivial loss)
+static double local_ba_huber(const ov2_local_ba_options &o) { return o.use_robust_cost ? sqrt(o.robust_mono_th) : -1.0; }
+
+// The decision after the first outlier test (src/optimizer.cpp:603-608): is there a second pass, and with which loss?  stopLocalBA()
+// is evaluated HERE, after the first solve: a keyframe that arrived while pass 1 ran skips pass 2.  The loss is reset to L2 only
+// when both residual lists are still non-empty (mono runs keep Huber!).
+static bool local_ba_second_pass(const ov2_local_ba_options &o, int n_bad, int left_remaining, int right_remaining, double *huber2)
+{
+    const bool stop = o.stop_requested || (o.stop_flag && *o.stop_flag);
+    *huber2 = (left_remaining && right_remaining) ? -1.0 : local_ba_huber(o);
+    return o.apply_l2_after_robust && o.use_robust_cost && !stop && n_bad > 0;
 }
 
 static bool same_solver_options(const ov2_ba_options &a, const ov2_ba_options &b)
@@ -3495,9 +2233,7 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
         OV2_REQUIRE(o[i].robust_mono_th == o[0].robust_mono_th && o[i].use_robust_cost == o[0].use_robust_cost && o[i].apply_l2_after_robust == o[0].apply_l2_after_robust &&
                     same_solver_options(o[i].pass1, o[0].pass1) && same_solver_options(o[i].pass2, o[0].pass2), OV2_EINVAL,
                     "ov2_local_ba_batch: the problems of a batch share the protocol and solver options (only the stop request is per problem)");
-        ov2_local_ba_result &ri = r[i];
-        ri.l2_done = 0; ri.pass2_error = OV2_OK; ri.n_bad_pass1 = 0; ri.n_bad_total = 0; ri.status = OV2_OK;
-        for (int q = 0; q < 2; q++) { ri.iterations[q] = 0; ri.num_successful_steps[q] = 0; ri.termination[q] = OV2_TERM_NO_CONVERGENCE; ri.initial_cost[q] = ri.final_cost[q] = 0; ri.solve_ms[q] = 0; }
+        local_ba_clear_result(r[i]);
     }
     // which problems can share launches: inverse-depth problems of the LDS-resident path with landmarks and optimised keyframes
     std::vector<int> idx;                                   // batch slot -> problem
@@ -3510,11 +2246,7 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
     }
     BABatch B;
     int N = (int)idx.size();
-    const bool dbg = ctx->debug != 0;
-    const auto tw0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (dbg) fprintf(stderr, "[ov2 local_ba_batch] %-28s %8.3f ms since entry (%d problems)\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count(), N);
-    };
+    const BALap lap{"local_ba_batch", ctx->debug != 0};
     size_t out_base = 0, out_total = 0;                     // the batch's result block (k_ba_gather_B) inside the header
     std::vector<size_t> out_off;
     if (N > 0) {
@@ -3584,8 +2316,7 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
     lap("sort + upload (ba_create)");
     if (N > 0) {
         const ov2_local_ba_options &o0 = o[0];
-        const double hub = o0.use_robust_cost ? sqrt(o0.robust_mono_th) : -1.0;
-        std::vector<double> huber((size_t)N, hub);
+        std::vector<double> huber((size_t)N, local_ba_huber(o0));
         std::vector<uint8_t> skip((size_t)N, 0);
         OV2_HIP_CHECK(hipMemsetAsync(B.d_cnt, 0, 64 * (size_t)N, s));
         ov2_ba_options o1 = o0.pass1;
@@ -3593,12 +2324,7 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
         int rc = ba_run_batch(ctx, B, &o1, huber.data(), nullptr, false, &ms);
         if (rc != OV2_OK) return rc;
         lap("pass 1");
-        for (int k = 0; k < N; k++) {
-            ov2_local_ba_result &ri = r[idx[(size_t)k]];
-            const BACtl &c = B.h_ctl[k];
-            ri.iterations[0] = c.n_steps; ri.num_successful_steps[0] = c.n_success; ri.termination[0] = c.termination;
-            ri.initial_cost[0] = c.initial_cost; ri.final_cost[0] = c.minimum_cost; ri.solve_ms[0] = ms;
-        }
+        for (int k = 0; k < N; k++) local_ba_store_pass(r[idx[(size_t)k]], 0, B.h_ctl[k], ms);
         int mk_blocks = 1;
         for (int k = 0; k < N; k++) mk_blocks = std::max(mk_blocks, std::min(1024, (B.devs[(size_t)k]->D.n_act + 255) / 256));
         hipLaunchKernelGGL(k_ba_mark_outliers_B, dim3(mk_blocks, 1, (unsigned)N), dim3(256), 0, s, (const BADev *)B.d_arr, o0.robust_mono_th, o0.apply_l2_after_robust ? 1 : 0, (uint8_t *)nullptr);
@@ -3611,18 +2337,15 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
         }
         OV2_HIP_CHECK(hipStreamSynchronize(s));
         lap("outlier test 1");
-        // the stop request of each problem is read HERE, after its first solve (src/optimizer.cpp:603-604)
+        // (only the stop request is per problem: the other options are the batch's)
         int n_pass2 = 0;
         std::vector<int> bad1((size_t)N, 0);
         for (int k = 0; k < N; k++) {
-            const ov2_local_ba_options &ok = o[idx[(size_t)k]];
             ov2_local_ba_result &ri = r[idx[(size_t)k]];
-            const int nbbad = B.h_cnt[16 * k], left = B.h_cnt[16 * k + 1], right = B.h_cnt[16 * k + 2];
+            const int nbbad = B.h_cnt[16 * k];
             bad1[(size_t)k] = nbbad; ri.n_bad_pass1 = nbbad; ri.n_bad_total = nbbad;
-            const bool stop = ok.stop_requested || (ok.stop_flag && *ok.stop_flag);
-            const bool go = o0.apply_l2_after_robust && o0.use_robust_cost && !stop && nbbad > 0;
+            const bool go = local_ba_second_pass(o[idx[(size_t)k]], nbbad, B.h_cnt[16 * k + 1], B.h_cnt[16 * k + 2], &huber[(size_t)k]);
             skip[(size_t)k] = go ? 0 : 1;
-            huber[(size_t)k] = (left && right) ? -1.0 : hub;                   // (:606-608: mono runs keep Huber)
             n_pass2 += go;
         }
         if (n_pass2 > 0) {
@@ -3638,11 +2361,8 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
             } else {
                 for (int k = 0; k < N; k++) {
                     if (skip[(size_t)k]) continue;
-                    ov2_local_ba_result &ri = r[idx[(size_t)k]];
-                    const BACtl &c = B.h_ctl[k];
-                    ri.l2_done = 1;
-                    ri.iterations[1] = c.n_steps; ri.num_successful_steps[1] = c.n_success; ri.termination[1] = c.termination;
-                    ri.initial_cost[1] = c.initial_cost; ri.final_cost[1] = c.minimum_cost; ri.solve_ms[1] = ms;
+                    r[idx[(size_t)k]].l2_done = 1;
+                    local_ba_store_pass(r[idx[(size_t)k]], 1, B.h_ctl[k], ms);
                 }
                 hipLaunchKernelGGL(k_ba_mark_outliers_B, dim3(mk_blocks, 1, (unsigned)N), dim3(256), 0, s, (const BADev *)B.d_arr, o0.robust_mono_th, 0, (uint8_t *)nullptr);
                 OV2_HIP_CHECK(hipGetLastError());
@@ -3760,14 +2480,9 @@ int ov2_local_ba(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_optio
 static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r)
 {
     OV2_REQUIRE(o->robust_mono_th > 0, OV2_EINVAL, "robust_mono_th must be positive");
-    r->l2_done = 0; r->pass2_error = OV2_OK; r->n_bad_pass1 = 0; r->n_bad_total = 0;
-    for (int i = 0; i < 2; i++) { r->iterations[i] = 0; r->num_successful_steps[i] = 0; r->termination[i] = OV2_TERM_NO_CONVERGENCE; r->initial_cost[i] = r->final_cost[i] = 0; r->solve_ms[i] = 0; }
+    local_ba_clear_result(*r);
     ov2_ba_dev *dev = nullptr;
-    const bool dbg = ctx->debug != 0;
-    const auto tw0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (dbg) fprintf(stderr, "[ov2 local_ba] %-28s %8.3f ms since entry\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count());
-    };
+    const BALap lap{"local_ba", ctx->debug != 0};
     int rc = ba_create(ctx, p, &dev, /*transient*/ true);       // the pool lives in the context's scratch through both passes
     if (rc != OV2_OK) return rc;
     lap("sort + upload (ba_create)");
@@ -3775,16 +2490,14 @@ static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_b
     if (dev->D.n_po > 0) { ov2_set_error("ov2_local_ba: problems with OV2_RES_PNP blocks go through ov2_ba_solve"); return OV2_EUNSUPPORTED; }
     BADev &D = dev->D;
     hipStream_t s = ctx->stream;
-    const double huber = o->use_robust_cost ? sqrt(o->robust_mono_th) : -1.0;
     // pass 1 (:436-485)
-    ov2_ba_options o1 = o->pass1;
-    o1.huber_delta = huber;
+    ov2_ba_options o1 = o->pass1, o2 = o->pass2;
+    o1.huber_delta = local_ba_huber(*o);
     ov2_ba_result br;
     memset(&br, 0, sizeof(br));
     rc = ba_run(ctx, dev, &o1, &br, nullptr, nullptr);
     if (rc != OV2_OK) return rc;
-    r->iterations[0] = br.iterations; r->num_successful_steps[0] = br.num_successful_steps; r->termination[0] = br.termination; r->initial_cost[0] = br.initial_cost;
-    r->final_cost[0] = br.final_cost; r->solve_ms[0] = br.solve_ms;
+    local_ba_store_pass(*r, 0, br);
     lap("pass 1");
     // outlier test on the values cached by the last Evaluate of pass 1 (:492-594)
     rc = ctx->reserve_host(64);
@@ -3797,14 +2510,9 @@ static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_b
     if (r->bad_after_pass1 && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->bad_after_pass1, D.bad_obs, (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));
     lap("outlier test 1");
-    const int nbbad = cnt_h[0], left_remaining = cnt_h[1], right_remaining = cnt_h[2];
+    const int nbbad = cnt_h[0];
     r->n_bad_pass1 = nbbad; r->n_bad_total = nbbad;
-    // stopLocalBA() is evaluated HERE, after the first solve (:603-604): a keyframe that arrived while pass 1 ran skips pass 2
-    const bool stop = o->stop_requested || (o->stop_flag && *o->stop_flag);
-    if (o->apply_l2_after_robust && o->use_robust_cost && !stop && nbbad > 0) {          // :603-604
-        // the loss is reset to L2 only when both residual lists are still non-empty (:606-608: mono runs keep Huber!)
-        ov2_ba_options o2 = o->pass2;
-        o2.huber_delta = (left_remaining && right_remaining) ? -1.0 : huber;
+    if (local_ba_second_pass(*o, nbbad, cnt_h[1], cnt_h[2], &o2.huber_delta)) {
         hipLaunchKernelGGL(k_ba_lm_live, dim3(std::max(1, std::min(512, (D.n_lm + 3) / 4))), dim3(256), 0, s, D);
         OV2_HIP_CHECK(hipMemsetAsync(D.lba_cnt, 0, 16, s));
         rc = ba_run(ctx, dev, &o2, &br, nullptr, nullptr, /*keep_state*/ true);
@@ -3815,8 +2523,7 @@ static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_b
             goto download;
         }
         r->l2_done = 1;
-        r->iterations[1] = br.iterations; r->num_successful_steps[1] = br.num_successful_steps; r->termination[1] = br.termination; r->initial_cost[1] = br.initial_cost;
-        r->final_cost[1] = br.final_cost; r->solve_ms[1] = br.solve_ms;
+        local_ba_store_pass(*r, 1, br);
         lap("pass 2");
         // second outlier test on the residual blocks that are still in the problem (:637-735)
         hipLaunchKernelGGL(k_ba_mark_outliers, dim3(mk_blocks), dim3(256), 0, s, D, o->robust_mono_th, 0, (uint8_t *)nullptr);

@@ -14,10 +14,9 @@
 // src/loop_closer.cpp:353) has 10^2..10^4 points: latency, not throughput, is what matters, and a single
 // launch with no host round trips is the shortest path.
 #include "common.hpp"
-#include <float.h>
-#include <math.h>
 
 #pragma clang fp contract(off)
+#include "ba_core.hpp"            // (after the pragma: the shared functions are compiled without contraction here)
 
 struct SbaOut { int iterations, num_successful_steps, termination, pad; double initial_cost, final_cost; };
 
@@ -33,18 +32,9 @@ struct SbaDev {
     double *jr;                   // 8 per CSR slot: corrected (scaled) Jacobian 2x3 + corrected residual
     double *chi2; uint8_t *dpos;  // n_res
     double calib_l[4], calib_r[4], Rrl[9], trl[3];
-    ov2_ba_options o;
+    BAOpt O; double huber, initial_radius;
     SbaOut *out;
 };
-
-__device__ __forceinline__ void sba_quat_to_R(const double *q, double *R)
-{
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double x = q[0] / n, y = q[1] / n, z = q[2] / n, w = q[3] / n;
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
-    R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-    R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
-}
 
 // one residual block; J = d r / d X (2x3) when JAC
 template <bool JAC>
@@ -76,28 +66,7 @@ __device__ __forceinline__ int sba_residual(const SbaDev &D, int type, const dou
     return c[2] > 0;
 }
 
-__device__ __forceinline__ void sba_huber(double a, double s, double &rho0, double &rho1)
-{
-    if (a > 0 && s > a * a) {
-        const double r = sqrt(s);
-        rho0 = 2.0 * a * r - a * a;
-        rho1 = fmax(DBL_MIN, a / r);
-    } else { rho0 = s; rho1 = 1.0; }
-}
-
-// deterministic workgroup reductions (result in every thread)
-__device__ __forceinline__ double sba_block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double t = 0;
-    for (int w = 0; w < nw; w++) t += sh[w];
-    return t;
-}
+// deterministic workgroup maximum (result in every thread: the per-point code asks "did any point fail")
 __device__ __forceinline__ double sba_block_max(double v, double *sh)
 {
 #pragma unroll
@@ -128,7 +97,7 @@ __device__ __forceinline__ double sba_evaluate(const SbaDev &D, const double *x)
             const double sq = r[0] * r[0] + r[1] * r[1];
             D.chi2[i] = sq; D.dpos[i] = (uint8_t)dp;
             double rho0, rho1;
-            sba_huber(D.o.huber_delta, sq, rho0, rho1);
+            d_huber(D.huber, sq, rho0, rho1);
             cost += 0.5 * rho0;
             if (JAC) {
                 const double k = sqrt(rho1);            // corrector.cc: rho'' <= 0 for Huber / trivial loss
@@ -158,12 +127,13 @@ __device__ __forceinline__ void sba_colnorm(const SbaDev &D, int pt, double n[3]
 __global__ __launch_bounds__(1024) void k_structure_ba(SbaDev D)
 {
     __shared__ double sh[16];
-    const ov2_ba_options &o = D.o;
+    __shared__ BACtl cl;                                   // the trust-region state: thread 0 runs the d_ctl_* rules, every thread reads the verdict
+    const BAOpt &O = D.O;
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int k = tid; k < D.n_kf; k += nt) {
         double Rwc[9];
         const double *p = D.poses + 7 * k;
-        sba_quat_to_R(p + 3, Rwc);
+        d_quat_to_R(p + 3, Rwc);
         double *rt = D.kf_rt + 12 * k;
         for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) rt[3 * i + j] = Rwc[3 * j + i];
         for (int i = 0; i < 3; i++) rt[9 + i] = -(rt[3 * i] * p[0] + rt[3 * i + 1] * p[1] + rt[3 * i + 2] * p[2]);
@@ -176,10 +146,16 @@ __global__ __launch_bounds__(1024) void k_structure_ba(SbaDev D)
         for (int pt = tid; pt < D.n_pts; pt += nt) if (in_program(pt)) for (int c = 0; c < 3; c++) m = fmax(m, fabs(D.g[3 * pt + c]));
         return sba_block_max(m, sh);
     };
+    // cost, corrected Jacobians and gradient at x: "a fresh linearisation" for the next d_ctl_iter_begin
+    auto linearize = [&]() {
+        const double cost = block_sum(sba_evaluate<true>(D, D.x), sh);
+        if (tid == 0) { cl.cost_acc = cost; cl.need_lin = 0; cl.fresh_lin = 1; }
+    };
 
     // iteration 0
-    double x_cost = sba_block_sum(sba_evaluate<true>(D, D.x), sh);
-    if (o.jacobi_scaling) {
+    if (tid == 0) ba_ctl_init(cl, D.initial_radius, nullptr);
+    linearize();
+    if (O.jacobi) {
         for (int pt = tid; pt < D.n_pts; pt += nt) {
             double n[3];
             sba_colnorm(D, pt, n);
@@ -190,28 +166,22 @@ __global__ __launch_bounds__(1024) void k_structure_ba(SbaDev D)
             }
         }
     }
-    const double initial_cost = x_cost;
-    double minimum_cost = x_cost, x_norm = -1.0, radius = o.initial_radius, decrease_factor = 2.0;
-    int reuse_diagonal = 0, num_invalid = 0;
-    double ev_min = x_cost, ev_cur = x_cost, ev_ref = x_cost, ev_cand = x_cost, ev_acc_ref = 0, ev_acc_cand = 0;
-    int ev_nonmono = 0, iteration = 0, step_successful = 1, term = OV2_TERM_NO_CONVERGENCE, n_success = 0, n_steps = 0;
     double gmax = grad_max();
 
-    for (;;) {                                         // every scalar below is identical in all threads
-        if (step_successful) { n_success++; if (x_cost < minimum_cost) minimum_cost = x_cost; }
-        if (iteration >= o.max_iter) { term = OV2_TERM_NO_CONVERGENCE; break; }
-        if (step_successful && gmax <= o.gradient_tolerance) { term = OV2_TERM_GRADIENT_TOL; break; }
-        if (radius <= o.min_radius) { term = OV2_TERM_MIN_RADIUS; break; }
-        iteration++;
-        step_successful = 0;
-        n_steps++;
+    for (;;) {
+        __syncthreads();                                   // every thread has read the last verdict
+        if (tid == 0) d_ctl_iter_begin(cl, O, cl.fresh_lin, gmax);
+        __syncthreads();
+        if (cl.done) break;
+        const double radius = cl.radius;
+        const int reuse_diagonal = cl.reuse_diag;
         // LM diagonal, block-diagonal solve and the model cost change, all per point
         double mcc = 0, bad = 0;
         for (int pt = tid; pt < D.n_pts; pt += nt) {
             if (!reuse_diagonal) {
                 double n[3];
                 sba_colnorm(D, pt, n);
-                for (int c = 0; c < 3; c++) D.diag[3 * pt + c] = fmin(fmax(n[c], o.min_lm_diagonal), o.max_lm_diagonal);
+                for (int c = 0; c < 3; c++) D.diag[3 * pt + c] = fmin(fmax(n[c], O.min_diag), O.max_diag);
             }
             if (!in_program(pt)) { D.y[3 * pt] = D.y[3 * pt + 1] = D.y[3 * pt + 2] = 0; continue; }
             double A[9] = {0}, b[3] = {0, 0, 0};
@@ -223,22 +193,12 @@ __global__ __launch_bounds__(1024) void k_structure_ba(SbaDev D)
                 }
             }
             for (int a = 0; a < 3; a++) { const double d = sqrt(D.diag[3 * pt + a] / radius); A[4 * a] += d * d; }
-            double L[9] = {0};
-            bool ok = true;
-            for (int j = 0; j < 3 && ok; j++) {
-                double d = A[4 * j];
-                for (int k = 0; k < j; k++) d -= L[3 * j + k] * L[3 * j + k];
-                if (!(d > 0.0) || !isfinite(d)) { ok = false; break; }
-                L[4 * j] = sqrt(d);
-                for (int i = j + 1; i < 3; i++) {
-                    double s = A[3 * i + j];
-                    for (int k = 0; k < j; k++) s -= L[3 * i + k] * L[3 * j + k];
-                    L[3 * i + j] = s / L[4 * j];
-                }
-            }
+            const double a6[6] = {A[0], A[1], A[2], A[4], A[5], A[8]};
+            double L[6];
+            bool ok = d_chol3(a6, L) && isfinite(L[0]) && isfinite(L[2]) && isfinite(L[5]);     // (a pivot that is not finite fails too)
             if (ok) {
-                for (int i = 0; i < 3; i++) { double s = b[i]; for (int k = 0; k < i; k++) s -= L[3 * i + k] * b[k]; b[i] = s / L[4 * i]; }
-                for (int i = 2; i >= 0; i--) { double s = b[i]; for (int k = i + 1; k < 3; k++) s -= L[3 * k + i] * b[k]; b[i] = s / L[4 * i]; }
+                b[0] = b[0] / L[0]; b[1] = (b[1] - L[1] * b[0]) / L[2]; b[2] = (b[2] - L[3] * b[0] - L[4] * b[1]) / L[5];
+                b[2] = b[2] / L[5]; b[1] = (b[1] - L[4] * b[2]) / L[2]; b[0] = (b[0] - L[1] * b[1] - L[3] * b[2]) / L[0];
                 for (int c = 0; c < 3; c++) { if (!isfinite(b[c])) ok = false; b[c] = -b[c]; }
             }
             if (!ok) { bad = 1; continue; }
@@ -249,54 +209,34 @@ __global__ __launch_bounds__(1024) void k_structure_ba(SbaDev D)
                 mcc -= m0 * (r[0] + m0 / 2.0) + m1 * (r[1] + m1 / 2.0);
             }
         }
-        reuse_diagonal = 1;
         const bool lin_ok = sba_block_max(bad, sh) == 0;
-        const double model_cost_change = sba_block_sum(mcc, sh);
-        if (!(lin_ok && model_cost_change > 0.0)) {
-            if (++num_invalid >= o.max_consecutive_invalid_steps) { term = OV2_TERM_INVALID_STEPS; break; }
-            radius = radius / decrease_factor; decrease_factor *= 2.0;
-            continue;
-        }
-        num_invalid = 0;
-        double step_sq = 0;
+        mcc = block_sum(mcc, sh);
+        if (tid == 0) d_ctl_candidate(cl, O, lin_ok, mcc);
+        __syncthreads();
+        if (cl.done) break;
+        if (!cl.step_valid) continue;
+        double step_sq = 0, xn = 0;
         for (int pt = tid; pt < D.n_pts; pt += nt)
             for (int c = 0; c < 3; c++) {
                 const double xv = D.x[3 * pt + c], cv = xv + D.y[3 * pt + c] * D.scale[3 * pt + c];
                 D.cand[3 * pt + c] = cv;
-                if (in_program(pt)) step_sq += (xv - cv) * (xv - cv);
+                if (in_program(pt)) { step_sq += (xv - cv) * (xv - cv); xn += cv * cv; }
             }
-        const double cand_cost = sba_block_sum(sba_evaluate<false>(D, D.cand), sh);
-        step_sq = sba_block_sum(step_sq, sh);
-        if (sqrt(step_sq) <= o.parameter_tolerance * (x_norm + o.parameter_tolerance)) { term = OV2_TERM_PARAMETER_TOL; break; }
-        if (fabs(x_cost - cand_cost) <= o.function_tolerance * x_cost) { term = OV2_TERM_FUNCTION_TOL; break; }
-        const double r1 = (ev_cur - cand_cost) / model_cost_change, r2 = (ev_ref - cand_cost) / (ev_acc_ref + model_cost_change);
-        const double rel = r1 > r2 ? r1 : r2;
-        if (rel > o.min_relative_decrease) {
-            double xn = 0;
-            for (int pt = tid; pt < D.n_pts; pt += nt)
-                for (int c = 0; c < 3; c++) { const double v = D.cand[3 * pt + c]; D.x[3 * pt + c] = v; if (in_program(pt)) xn += v * v; }
-            x_norm = sqrt(sba_block_sum(xn, sh));
-            x_cost = sba_block_sum(sba_evaluate<true>(D, D.x), sh);          // stores the Jacobians already column-scaled
+        const double cand_cost = block_sum(sba_evaluate<false>(D, D.cand), sh);
+        step_sq = block_sum(step_sq, sh);
+        xn = block_sum(xn, sh);
+        if (tid == 0) { cl.cost_acc = cand_cost; d_ctl_decide(cl, O, step_sq, xn); }
+        __syncthreads();
+        if (cl.done) break;
+        if (cl.step_successful) {
+            for (int pt = tid; pt < D.n_pts; pt += nt) for (int c = 0; c < 3; c++) D.x[3 * pt + c] = D.cand[3 * pt + c];   // (a thread's own points: no barrier)
+            linearize();                                   // stores the Jacobians already column-scaled
             gmax = grad_max();
-            step_successful = 1;
-            const double t3 = 2.0 * rel - 1.0;
-            double d = 1.0 - t3 * t3 * t3;
-            if (d < 1.0 / 3.0) d = 1.0 / 3.0;
-            radius = radius / d;
-            if (radius > o.max_radius) radius = o.max_radius;
-            decrease_factor = 2.0;
-            reuse_diagonal = 0;
-            ev_cur = cand_cost; ev_acc_cand += model_cost_change; ev_acc_ref += model_cost_change;
-            if (ev_cur < ev_min) { ev_min = ev_cur; ev_nonmono = 0; ev_cand = ev_cur; ev_acc_cand = 0; }
-            else { ev_nonmono++; if (ev_cur > ev_cand) { ev_cand = ev_cur; ev_acc_cand = 0; } }
-            if (ev_nonmono == 0) { ev_ref = ev_cand; ev_acc_ref = ev_acc_cand; }
-        } else {
-            radius = radius / decrease_factor; decrease_factor *= 2.0;
         }
     }
     if (tid == 0) {
-        D.out->iterations = n_steps; D.out->num_successful_steps = n_success; D.out->termination = term;
-        D.out->initial_cost = initial_cost; D.out->final_cost = minimum_cost;
+        D.out->iterations = cl.n_steps; D.out->num_successful_steps = cl.n_success; D.out->termination = cl.termination;
+        D.out->initial_cost = cl.initial_cost; D.out->final_cost = cl.minimum_cost;
     }
 }
 
@@ -363,17 +303,9 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
     D.diag = (double *)(ds + o_diag); D.y = (double *)(ds + o_y); D.jr = (double *)(ds + o_jr);
     D.chi2 = (double *)(ds + o_chi2); D.dpos = ds + o_dpos; D.out = (SbaOut *)(ds + o_out);
     for (int i = 0; i < 4; i++) { D.calib_l[i] = p->calib_l[i]; D.calib_r[i] = p->calib_r[i]; }
-    {
-        const double *q = p->T_rl + 3;
-        const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        const double x = q[0] / n, y = q[1] / n, z = q[2] / n, w = q[3] / n;
-        double *R = D.Rrl;
-        R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w);     R[2] = 2 * (x * z + y * w);
-        R[3] = 2 * (x * y + z * w);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-        R[6] = 2 * (x * z - y * w);     R[7] = 2 * (y * z + x * w);     R[8] = 1 - 2 * (x * x + y * y);
-        D.trl[0] = p->T_rl[0]; D.trl[1] = p->T_rl[1]; D.trl[2] = p->T_rl[2];
-    }
-    D.o = *opt;
+    d_quat_to_R(p->T_rl + 3, D.Rrl);
+    D.trl[0] = p->T_rl[0]; D.trl[1] = p->T_rl[1]; D.trl[2] = p->T_rl[2];
+    D.O = ba_opt_from(*opt); D.huber = opt->huber_delta; D.initial_radius = opt->initial_radius;
     hipEvent_t e0, e1;
     OV2_HIP_CHECK(hipEventCreate(&e0)); OV2_HIP_CHECK(hipEventCreate(&e1));
     OV2_HIP_CHECK(hipEventRecord(e0, ctx->stream));
