@@ -886,6 +886,109 @@ int ov2_triangulate_keyframe(ov2_ctx *ctx, const ov2_tri_params *params, const o
 int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, int n_items, const ov2_tri_keyframe *kfs,
                                    ov2_tri_result *results);
 
+/* ------------------------------------------------------------------ */
+/* Local-map matching (Mapper::matchToMap, src/mapper.cpp:576-774)      */
+/* ------------------------------------------------------------------ */
+/* The loop that Mapper::matchingToLocalMap runs after the triangulation: every 3-D point of the local map is projected into the
+ * new keyframe and compared, by descriptor, with the map points of the keypoints around its projection; a match says "this
+ * keypoint's map point is a re-detection of that local map point" (mergeMatches).  One wavefront per local map point
+ * (csrc/match.hip), ONE staging upload, the launches, ONE download and ONE synchronisation per call.
+ *
+ * Thresholds, once per call on the host in float as the reference writes them: vfov = 0.5 img_h / fy, hfov = 0.5 img_w / fx,
+ * view_th = cos(atan(max(hfov, vfov))); dmaxpxdist = fmax_proj_pxdist, doubled when nb3dkps < 30; mindist = (float)(desc_bytes *
+ * fmax_desc_dist * 8.).
+ * Per local map point l, in the caller's order, with wpt = lm_wpt[l] and A = lm_mp[l] (its row of the map-point table):
+ *   campt = Tcw wpt (Sophus SE3d * Vector3d, the pose as held); campt.z < 0.1 -> BEHIND; view_angle = (float)(campt.z / |campt|),
+ *   fabs(view_angle) < view_th -> OUT_OF_FOV; projpx = projectCamToImageDist(campt) (below); outside [0, img_w) x [0, img_h) (or
+ *   NaN) -> OUT_OF_IMAGE.
+ *   Candidates: the keypoints of cells r in {rkp-1, rkp}, c in {ckp-1, ckp}, rkp = floor(projpx.y / ncellsize), ckp alike (a 2x2
+ *   block as the reference's loop bounds give it, not 3x3; r < 0 or c < 0 skipped), cell index r * ceil(img_w / ncellsize) + c, in
+ *   that order and inside a cell in the order of cell_kp.  A candidate keypoint k with B = kp_mp[k] >= 0 and B holding a descriptor:
+ *     pxdist = (float)cv::norm(projpx - kp_px[k]) > dmaxpxdist                       -> skipped
+ *     A and B share an observing keyframe id (obs_kfid; stale observations count)     -> skipped
+ *     coprojpx (float) += cv::norm(obs_px - projWorldToImageDist_kf(wpt)) over B's observations with obs_kf >= 0, in ascending
+ *     keyframe id; coprojpx / count > dmaxpxdist -> skipped (count == 0: NaN, the candidate passes; no depth check here)
+ *     dist = the minimum Hamming distance over all (descriptor of A, descriptor of B) pairs, start value 1000
+ *     dist <= bestdist: best -> second, k -> best;  else dist <= secdist: k -> second   (both start at mindist, id -1)
+ *   best and second both set and 0.9 * secdist < bestdist -> RATIO_REJECTED; no best -> NO_CANDIDATE; otherwise BEST: the point
+ *   proposes keypoint lm_kp[l] at lm_dist[l].
+ * Per keypoint the proposing point with the smallest distance wins, among equals the one listed LAST in the local map (the
+ * reference's `<=`): kp_lm[k] / kp_dist[k]; kp_lm is the reference's map_previd_newid as (keypoint row -> local-map index).
+ * The pick is a 64-bit atomic minimum on (distance, reversed index), so a call's bytes do not depend on scheduling.
+ * lm_projpx is (0, 0) for BEHIND / OUT_OF_FOV points; lm_dist is the final bestdist (mindist when nothing qualified) and 0 for
+ * points that a gate removed; lm_kp is -1 unless BEST.
+ *
+ * projectCamToImageDist (src/camera_calibration.cpp:254-281): x = X / z, y = Y / z in double through invz = 1 / z; nD == 0:
+ * Point2f(fx x + cx, fy y + cy).  Otherwise x, y are first rounded to float (cv::Point3f / Point2f) and run, in double, through
+ * cv::projectPoints with zero rotation and translation (OV2_CAM_PINHOLE, k1 k2 p1 p2 [k3 [k4 k5 k6 [s1 s2 s3 s4]]], nD = 4 / 5 / 8
+ * / 12) or cv::fisheye::distortPoints (OV2_CAM_FISHEYE, nD = 4); the result is rounded to float.  Both are restated from the
+ * published models, not pinned against an OpenCV build.
+ *
+ * What stays on the host: choosing the local map, the filters that need the map's hash tables (isObservingKp, missing / 2-D /
+ * descriptor-less points, :613-623), mergeMatches, and the map clean-up the reference does in passing (:678-681, :708-713).
+ * DEVIATION (snapshot): the caller marks a stale observation (its keyframe is gone or no longer holds the keypoint) with
+ * obs_kf = -1 when it flattens the map.  Such an observation still counts in the shared-observer test and is left out of the
+ * re-projection sum, as in the reference the first time it is met; the reference then removes it from the map, so a LATER local
+ * map point of the same call would see the cleaned set.  Without stale observations the two agree exactly.
+ *
+ * OV2_EINVAL: NULL params / keyframe / result / ctx, a negative count, a NULL array with a non-zero count, kp_mp / lm_mp / obs_kf
+ * / cell_kp outside its table, offsets (cell_start, obs_start, desc_start) that do not start at 0 or decrease, obs_kfid not strictly
+ * ascending inside a row, img_w / img_h / ncellsize not positive.  OV2_EUNSUPPORTED: desc_bytes != 32, a coefficient count the model
+ * does not take, more than 65535 items, more than 2^31 - 1 elements of one kind in a call.  All of it is checked on the host
+ * before any device work (the inputs before the context, so a malformed input is reported without a device); nothing is
+ * modified then. */
+enum {
+    OV2_MATCH_BEHIND = 1, OV2_MATCH_OUT_OF_FOV = 2, OV2_MATCH_OUT_OF_IMAGE = 4, OV2_MATCH_NO_CANDIDATE = 8,
+    OV2_MATCH_RATIO_REJECTED = 16, OV2_MATCH_BEST = 32
+};
+typedef struct {
+    int model;                   /* OV2_CAM_PINHOLE / OV2_CAM_FISHEYE                                                        */
+    double K[4];                 /* fx fy cx cy                                                                              */
+    const double *D;             /* nD distortion coefficients (NULL when nD == 0)                                           */
+    int nD;
+    double img_w, img_h;         /* pcalib_leftcam_->img_w_ / img_h_                                                         */
+    int ncellsize;               /* Frame::ncellsize_                                                                        */
+    float fmax_proj_pxdist;      /* fmaxprojerr                                                                              */
+    float fmax_desc_dist;        /* fdistratio                                                                               */
+    int desc_bytes;              /* desc_.cols: 32                                                                           */
+} ov2_match_params;
+typedef struct {
+    const double *Tcw;           /* 7: the keyframe's Tcw_ as held                                                           */
+    int nb3dkps;                 /* frame.nb3dkps_                                                                           */
+    int n_kp;                    /* keypoints                                                                                */
+    const float *kp_px;          /* 2 n_kp: px_                                                                              */
+    const int *kp_mp;            /* n_kp: row of the map-point table, -1 = no usable map point                               */
+    const int *cell_start;       /* ncells + 1 offsets into cell_kp, ncells = ceil(img_w / ncellsize) * ceil(img_h / ncellsize) */
+    const int *cell_kp;          /* keypoint rows, per cell in vgridkps_ order                                               */
+    int n_mp;                    /* rows of the map-point table (local map points and the keypoints' map points alike)       */
+    const int *obs_start;        /* n_mp + 1                                                                                 */
+    const int *obs_kfid;         /* per observation: keyframe id, strictly ascending inside a row                            */
+    const int *obs_kf;           /* per observation: row of the pose table, -1 = stale                                       */
+    const float *obs_px;         /* 2 per observation: the observing keyframe's px_ of that map point                        */
+    const int *desc_start;       /* n_mp + 1                                                                                 */
+    const uint8_t *desc;         /* desc_bytes per descriptor: the map point's map_kf_desc_, any order                       */
+    int n_kf;                    /* rows of the pose table                                                                   */
+    const double *kf_Tcw;        /* 7 n_kf, as held                                                                          */
+    int n_lm;                    /* local map points, in the caller's iteration order                                        */
+    const int *lm_mp;            /* n_lm: row of the map-point table                                                         */
+    const double *lm_wpt;        /* 3 n_lm                                                                                   */
+} ov2_match_keyframe;
+typedef struct {
+    uint8_t *lm_status;          /* n_lm: OV2_MATCH_* bits                                                                   */
+    int *lm_kp;                  /* n_lm: proposed keypoint row or -1                                                        */
+    float *lm_dist;              /* n_lm                                                                                     */
+    float *lm_projpx;            /* 2 n_lm                                                                                   */
+    int *kp_lm;                  /* n_kp: the winning local-map index or -1                                                  */
+    float *kp_dist;              /* n_kp: its distance (0 where kp_lm == -1)                                                 */
+    int n_matches;               /* keypoints with kp_lm >= 0                                                                */
+} ov2_match_result;
+/* one keyframe: the batch form with one item, through the same code path */
+int ov2_match_to_map(ov2_ctx *ctx, const ov2_match_params *params, const ov2_match_keyframe *kf, ov2_match_result *result);
+/* the keyframes of a lock-step batch, items [0, n_items) with shared params (grid.y = item).  Per item the result equals
+ * ov2_match_to_map on that item; an item without local map points or without keypoints is allowed. */
+int ov2_match_to_map_batch(ov2_ctx *ctx, const ov2_match_params *params, int n_items, const ov2_match_keyframe *kfs,
+                           ov2_match_result *results);
+
 #ifdef __cplusplus
 }
 #endif

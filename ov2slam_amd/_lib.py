@@ -32,6 +32,7 @@ OV2_TRACK_IMPL_WAVE, OV2_TRACK_IMPL_ROW = 0, 1
 OV2_BRIEF_BYTES = 32
 OV2_RES_LEFT, OV2_RES_RIGHT, OV2_RES_RIGHT_ANCH, OV2_RES_PNP = 0, 1, 2, 3
 OV2_TRI_STEREO_TRIED, OV2_TRI_STEREO_OK, OV2_TRI_TEMPORAL_TRIED, OV2_TRI_TEMPORAL_OK, OV2_TRI_NO_MOTION, OV2_TRI_REMOVE_OBS = 1, 2, 4, 8, 16, 32
+OV2_MATCH_BEHIND, OV2_MATCH_OUT_OF_FOV, OV2_MATCH_OUT_OF_IMAGE, OV2_MATCH_NO_CANDIDATE, OV2_MATCH_RATIO_REJECTED, OV2_MATCH_BEST = 1, 2, 4, 8, 16, 32
 
 
 class Ov2Error(RuntimeError):
@@ -157,6 +158,30 @@ class TriResult(C.Structure):
                 ("n_stereo", C.c_int), ("n_stereo_good", C.c_int), ("n_candidates", C.c_int), ("n_temporal_good", C.c_int)]
 
 
+class MatchParams(C.Structure):
+    """ov2_match_params (Mapper::matchToMap)"""
+    _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
+                ("img_h", C.c_double), ("ncellsize", C.c_int), ("fmax_proj_pxdist", C.c_float), ("fmax_desc_dist", C.c_float),
+                ("desc_bytes", C.c_int)]
+
+
+class MatchKeyframe(C.Structure):
+    """ov2_match_keyframe"""
+    _fields_ = [("Tcw", C.POINTER(C.c_double)), ("nb3dkps", C.c_int), ("n_kp", C.c_int), ("kp_px", C.POINTER(C.c_float)),
+                ("kp_mp", C.POINTER(C.c_int)), ("cell_start", C.POINTER(C.c_int)), ("cell_kp", C.POINTER(C.c_int)),
+                ("n_mp", C.c_int), ("obs_start", C.POINTER(C.c_int)), ("obs_kfid", C.POINTER(C.c_int)),
+                ("obs_kf", C.POINTER(C.c_int)), ("obs_px", C.POINTER(C.c_float)), ("desc_start", C.POINTER(C.c_int)),
+                ("desc", C.POINTER(C.c_uint8)), ("n_kf", C.c_int), ("kf_Tcw", C.POINTER(C.c_double)), ("n_lm", C.c_int),
+                ("lm_mp", C.POINTER(C.c_int)), ("lm_wpt", C.POINTER(C.c_double))]
+
+
+class MatchResult(C.Structure):
+    """ov2_match_result"""
+    _fields_ = [("lm_status", C.POINTER(C.c_uint8)), ("lm_kp", C.POINTER(C.c_int)), ("lm_dist", C.POINTER(C.c_float)),
+                ("lm_projpx", C.POINTER(C.c_float)), ("kp_lm", C.POINTER(C.c_int)), ("kp_dist", C.POINTER(C.c_float)),
+                ("n_matches", C.c_int)]
+
+
 class XYZBAResult(C.Structure):
     _fields_ = [
         ("poses_out", C.POINTER(C.c_double)), ("xyz_out", C.POINTER(C.c_double)), ("chi2_last_eval", C.POINTER(C.c_double)),
@@ -269,6 +294,8 @@ SIGNATURES = {
     "ov2_local_ba_batch": (_i, [_vp, _i, C.POINTER(BAProblem), C.POINTER(LocalBAOptions), C.POINTER(LocalBAResult), C.POINTER(_i)]),
     "ov2_triangulate_keyframe": (_i, [_vp, C.POINTER(TriParams), C.POINTER(TriKeyframe), C.POINTER(TriResult)]),
     "ov2_triangulate_keyframe_batch": (_i, [_vp, C.POINTER(TriParams), _i, C.POINTER(TriKeyframe), C.POINTER(TriResult)]),
+    "ov2_match_to_map": (_i, [_vp, C.POINTER(MatchParams), C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
+    "ov2_match_to_map_batch": (_i, [_vp, C.POINTER(MatchParams), _i, C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

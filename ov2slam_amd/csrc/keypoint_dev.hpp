@@ -66,6 +66,35 @@ __device__ __forceinline__ bool kp_undistort_fisheye(const KpCalib &c, double u,
 // host: validate and pack the calibration (defined in keypoint.hip)
 int ov2_kp_calib(int model, const double K[4], const double *D, int nD, const double iK[9], KpCalib &c);
 
+// The forward model: CameraCalibration::projectCamToImageDist (src/camera_calibration.cpp:254-281) of a camera-frame point.
+// x = X / z, y = Y / z in double through invz; without coefficients Point2f(fx x + cx, fy y + cy).  With coefficients x, y are
+// first rounded to float (cv::Point3f / cv::Point2f), then cv::projectPoints with zero rotation and translation (pinhole: the
+// radial-tangential-rational-thin-prism model, k = k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4, absent ones 0) or
+// cv::fisheye::distortPoints, both in double, and the pixel is rounded to float.
+__device__ __forceinline__ float2 kp_project_dist(const KpCalib &c, double X, double Y, double Z)
+{
+    const double invz = 1. / Z;
+    double x = X * invz, y = Y * invz;
+    if (c.nD <= 0) return make_float2((float)(c.fx * x + c.cx), (float)(c.fy * y + c.cy));
+    x = (double)(float)x; y = (double)(float)y;
+    const double *k = c.k;
+    if (c.model == OV2_CAM_FISHEYE) {
+        const double r = sqrt(x * x + y * y);
+        const double theta = atan(r);
+        const double theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta4 * theta4;
+        const double theta_d = theta * (1 + k[0] * theta2 + k[1] * theta4 + k[2] * theta6 + k[3] * theta8);
+        const double cdist = r > 1e-8 ? theta_d * (1.0 / r) : 1;
+        return make_float2((float)((x * cdist) * c.fx + c.cx), (float)((y * cdist) * c.fy + c.cy));
+    }
+    const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    const double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+    const double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+    const double icdist2 = 1. / (1 + k[5] * r2 + k[6] * r4 + k[7] * r6);
+    const double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2 + k[8] * r2 + k[9] * r4;
+    const double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1 + k[10] * r2 + k[11] * r4;
+    return make_float2((float)(xd * c.fx + c.cx), (float)(yd * c.fy + c.cy));
+}
+
 // undistortImagePoint on a float pixel: `return pt` when there is no distortion vector
 __device__ __forceinline__ float2 kp_undistort_image_point(const KpCalib &c, float2 p)
 {
