@@ -989,6 +989,81 @@ int ov2_match_to_map(ov2_ctx *ctx, const ov2_match_params *params, const ov2_mat
 int ov2_match_to_map_batch(ov2_ctx *ctx, const ov2_match_params *params, int n_items, const ov2_match_keyframe *kfs,
                            ov2_match_result *results);
 
+/* ==================================================================== */
+/* Absolute pose from 2D-3D matches (MultiViewGeometry::p3pRansac,      */
+/* src/multi_view_geometry.cpp:144-343, USE_OPENGV)                     */
+/* ==================================================================== */
+/* What VisualFrontEnd::computePose runs when the motion model is wrong (the p3p_req of the trackers) and what the loop closer
+ * runs per candidate: Kneip's P3P on three matches of a sample row, the row's fourth match picks among its solutions, and the
+ * hypotheses are searched as OpenGV's sac::Lmeds (smallest median of sqrt(1 - cos)) or sac::Ransac (largest inlier count, adaptive
+ * iteration bound) would.  fp64 (csrc/p3p.hip): ONE staging upload, three launches, ONE download, ONE synchronisation per call.
+ *
+ * The sample table is an INPUT (n_rows x 4 indices), so the result is a deterministic function of the arguments: hypotheses are
+ * evaluated in parallel, the winner is chosen exactly as the sequential loop over the rows in order would choose it.  A row with
+ * a repeated or out-of-range index, without a solution (an accepted root of the quartic whose pose reproduces the row's own
+ * three bearings to d <= 1e-12) or with a non-finite model is skipped WITHOUT counting an
+ * iteration; the search stops when its loop ends or the rows run out.  ov2_p3p_draw_samples fills a table (a caller draws
+ * 2 x max_iterations rows so that skipped rows do not shorten the search).
+ *   LMedS   while iterations < max_iterations: a strictly smaller penalty becomes the best; ++iterations.  The penalty is the exact
+ *           median of sqrt(d): sqrt(d[n/2]) for odd n, the mean of the two middle square roots for even n.
+ *   RANSAC  k = 1; while iterations < k: a strictly larger inlier count (d < threshold) becomes the best and sets
+ *           k = log(1 - probability) / log(1 - (count / n)^4) (the argument clamped to [DBL_EPSILON, 1 - DBL_EPSILON]); ++iterations;
+ *           stop once iterations > max_iterations.
+ * d_i = max(0, 1 - bv_i . v / |v|), v = Rwc^T (X_i - twc).  After either loop the outliers of the best model are the points with
+ * d_i >= threshold, ascending.  The full specification is tests/p3p_ref.py; OpenGV itself is not available to this project, so the
+ * solver and the loops are restated and nothing is pinned against an OpenGV binary.
+ *
+ * status: OV2_P3P_TOO_FEW_POINTS (n < 4: nothing else is set or searched), OV2_P3P_NO_MODEL (no valid row was reached; comes with
+ * OV2_P3P_FEW_INLIERS), OV2_P3P_FEW_INLIERS (fewer than 5), OV2_P3P_NOT_ORTHOGONAL (Sophus::isOrthogonal fails on Rwc).  The
+ * reference returns false on any of them.  model, score, best_row and the outlier list describe the best model whenever there is
+ * one (best_row >= 0), whatever the status; without one they are 0 / -1 / empty.
+ *
+ * Capacity: OV2_P3P_MAX_POINTS points and OV2_P3P_MAX_ROWS rows per problem, 65535 problems per call.  OV2_EINVAL: NULL params /
+ * problem / result / ctx, a NULL array with a non-zero count, a negative count, a non-finite bearing or point, threshold <= 0 or
+ * not finite, probability outside (0, 1), max_iterations < 0, an unknown mode, boptimize != 0 (OpenGV's non-linear refinement is
+ * not provided: refine with ov2_ba_solve / ov2::ceresPnP, as LoopCloser::computePnP does right after), anything beyond the
+ * capacity.  All of it is checked on the host before any device work, the inputs before the context. */
+enum { OV2_P3P_LMEDS = 0, OV2_P3P_RANSAC = 1 };
+enum { OV2_P3P_TOO_FEW_POINTS = 1, OV2_P3P_NO_MODEL = 2, OV2_P3P_FEW_INLIERS = 4, OV2_P3P_NOT_ORTHOGONAL = 8 };
+#define OV2_P3P_MAX_POINTS 2048
+#define OV2_P3P_MAX_ROWS 4096
+typedef struct {
+    int mode;                    /* OV2_P3P_LMEDS / OV2_P3P_RANSAC                                                            */
+    int max_iterations;          /* nmaxiter                                                                                 */
+    double threshold;            /* 1 - cos(atan(errth / focal))                                                             */
+    double probability;          /* 0.99                                                                                     */
+    int boptimize;               /* must be 0                                                                                */
+} ov2_p3p_params;
+typedef struct {
+    int n;                       /* matches                                                                                  */
+    const double *bv;            /* 3 n: unit bearing vectors, camera frame                                                  */
+    const double *X;             /* 3 n: world points                                                                        */
+    int n_rows;                  /* rows of the sample table                                                                 */
+    const int *samples;          /* 4 n_rows                                                                                 */
+} ov2_p3p_problem;
+typedef struct {
+    double model[12];            /* Rwc row-major (9), twc (3)                                                               */
+    double score;                /* the best row's penalty (LMedS) or inlier count (RANSAC)                                  */
+    int best_row;                /* -1: no model                                                                             */
+    int iterations;              /* rows that counted                                                                        */
+    int rows_consumed;           /* rows the loop took from the table, skipped ones included                                 */
+    int status;                  /* OV2_P3P_* bits, 0 = the reference returns true                                           */
+    int n_inliers, n_outliers;
+    int *outliers;               /* n slots; the first n_outliers are written, ascending                                     */
+    uint8_t *trace_valid;        /* optional (NULL or n_rows): 1 where the row gave a hypothesis                             */
+    double *trace_score;         /* optional (NULL or n_rows): every row's penalty or count, 0 for an invalid row            */
+} ov2_p3p_result;
+/* one problem: the batch form with one item, through the same code path */
+int ov2_p3p_ransac(ov2_ctx *ctx, const ov2_p3p_params *params, const ov2_p3p_problem *problem, ov2_p3p_result *result);
+/* the problems of a lock-step batch, items [0, n_items) with shared params (the problem is a grid axis: each kernel is launched
+ * once).  Per item the result equals ov2_p3p_ransac on that item bit for bit; sizes may differ, empty problems are allowed. */
+int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems,
+                         ov2_p3p_result *results);
+/* Host only: rows x 4 indices of [0, n), distinct inside a row.  Draw j of the stream is splitmix64's output for the state
+ * seed + (j + 1) * 0x9E3779B97F4A7C15, reduced modulo n; a slot that repeats an earlier slot of its row is drawn again.  Stands in
+ * for OpenGV's rand()-driven drawIndexSample.  OV2_EINVAL: n < 4, rows < 0, NULL out with rows > 0. */
+int ov2_p3p_draw_samples(unsigned long long seed, int n, int rows, int *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,9 @@ OV2_BRIEF_BYTES = 32
 OV2_RES_LEFT, OV2_RES_RIGHT, OV2_RES_RIGHT_ANCH, OV2_RES_PNP = 0, 1, 2, 3
 OV2_TRI_STEREO_TRIED, OV2_TRI_STEREO_OK, OV2_TRI_TEMPORAL_TRIED, OV2_TRI_TEMPORAL_OK, OV2_TRI_NO_MOTION, OV2_TRI_REMOVE_OBS = 1, 2, 4, 8, 16, 32
 OV2_MATCH_BEHIND, OV2_MATCH_OUT_OF_FOV, OV2_MATCH_OUT_OF_IMAGE, OV2_MATCH_NO_CANDIDATE, OV2_MATCH_RATIO_REJECTED, OV2_MATCH_BEST = 1, 2, 4, 8, 16, 32
+OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
+OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
+OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
 
 
 class Ov2Error(RuntimeError):
@@ -182,6 +185,25 @@ class MatchResult(C.Structure):
                 ("n_matches", C.c_int)]
 
 
+class P3PParams(C.Structure):
+    """ov2_p3p_params"""
+    _fields_ = [("mode", C.c_int), ("max_iterations", C.c_int), ("threshold", C.c_double), ("probability", C.c_double),
+                ("boptimize", C.c_int)]
+
+
+class P3PProblem(C.Structure):
+    """ov2_p3p_problem"""
+    _fields_ = [("n", C.c_int), ("bv", C.POINTER(C.c_double)), ("X", C.POINTER(C.c_double)), ("n_rows", C.c_int),
+                ("samples", C.POINTER(C.c_int))]
+
+
+class P3PResult(C.Structure):
+    """ov2_p3p_result"""
+    _fields_ = [("model", C.c_double * 12), ("score", C.c_double), ("best_row", C.c_int), ("iterations", C.c_int),
+                ("rows_consumed", C.c_int), ("status", C.c_int), ("n_inliers", C.c_int), ("n_outliers", C.c_int),
+                ("outliers", C.POINTER(C.c_int)), ("trace_valid", C.POINTER(C.c_uint8)), ("trace_score", C.POINTER(C.c_double))]
+
+
 class XYZBAResult(C.Structure):
     _fields_ = [
         ("poses_out", C.POINTER(C.c_double)), ("xyz_out", C.POINTER(C.c_double)), ("chi2_last_eval", C.POINTER(C.c_double)),
@@ -296,6 +318,9 @@ SIGNATURES = {
     "ov2_triangulate_keyframe_batch": (_i, [_vp, C.POINTER(TriParams), _i, C.POINTER(TriKeyframe), C.POINTER(TriResult)]),
     "ov2_match_to_map": (_i, [_vp, C.POINTER(MatchParams), C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
     "ov2_match_to_map_batch": (_i, [_vp, C.POINTER(MatchParams), _i, C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
+    "ov2_p3p_ransac": (_i, [_vp, C.POINTER(P3PParams), C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
+    "ov2_p3p_ransac_batch": (_i, [_vp, C.POINTER(P3PParams), _i, C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
+    "ov2_p3p_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

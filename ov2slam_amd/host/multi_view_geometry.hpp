@@ -8,7 +8,12 @@
 //   pass 2    loss reset to L2, same options, only if bapply_l2_after_robust and outliers were found               (:567-570)
 // The reference function is static and is called from two threads: the caller passes the context of ITS thread
 // (ov2::SlamGpu::threadContext()).
+//
+// ov2::p3pRansac -- MultiViewGeometry::p3pRansac in its USE_OPENGV form (:144-343): Kneip's P3P under OpenGV's LMedS (the front end,
+// src/visual_front_end.cpp:729-742) or RANSAC loop (the loop closer, src/loop_closer.cpp:817) on the device (ov2_p3p_ransac,
+// csrc/p3p.hip).  OpenGV's solver and loops are restated, not linked: same algorithm, another random stream (see below).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include "ov2_types.hpp"
 
@@ -71,6 +76,74 @@ inline bool ceresPnP(Context &ctx, const double *vunkps, const double *vwpts, co
     }
     for (int i = 0; i < 7; i++) Twc[i] = pose_out[i];                                           // :572
     return termination != OV2_TERM_FAILURE;                                                    // Summary::IsSolutionUsable (:574)
+}
+
+// bvs / vwpts: n x 3 unit bearing vectors (camera frame) and world points.  Twc: [tx ty tz qx qy qz qw], written only when the
+// function returns true (translation = the model's last column, rotation through Sophus::SE3d::setRotationMatrix: Eigen's
+// Quaterniond(R), normalised).  voutliersidx receives every index that is not an inlier, ascending, only when the function returns
+// true -- the reference returns before it touches either on its false paths (n < 4, fewer than 5 inliers, rotation not orthogonal).
+// seed: the sample table is drawn from it (ov2_p3p_draw_samples, 2 x nmaxiter rows so that skipped rows do not shorten the
+// search, at most OV2_P3P_MAX_ROWS), so a call is a deterministic function of its arguments; the reference draws from rand(), seeded
+// by the clock when bdorandom -- which the shipped parameter files set -- so its own result differs from run to run.  bdorandom is
+// accepted for the signature and not read: pass a varying seed for the same effect.
+// boptimize (OpenGV's non-linear refinement on the inliers) is not provided: the call fails (*library_ok = false).  Refine the pose
+// with ov2::ceresPnP, as LoopCloser::computePnP does right after.
+inline bool p3pRansac(Context &ctx, const double *bvs, const double *vwpts, size_t n, int nmaxiter, float errth, bool boptimize,
+                      bool bdorandom, float fx, float fy, double Twc[7], std::vector<int> &voutliersidx, bool use_lmeds,
+                      unsigned long long seed, bool *library_ok = nullptr, std::string *error = nullptr)
+{
+    (void)bdorandom;
+    if (library_ok) *library_ok = true;
+    if (n < 4) return false;                                                                   // :178-180
+    float focal = fx + fy;                                                                     // :209-213
+    focal /= 2.;
+    // The reference writes (1.0 - cos(atan(errth/focal))) with unqualified names: a build whose headers bring std::cos / std::atan
+    // into scope resolves the float overloads (the threshold is then a float difference), one that sees only C's ::cos / ::atan
+    // evaluates in double.  This adapter evaluates in double.
+    ov2_p3p_params P{};
+    P.mode = use_lmeds ? OV2_P3P_LMEDS : OV2_P3P_RANSAC;
+    P.max_iterations = nmaxiter;
+    P.threshold = 1.0 - std::cos(std::atan((double)(errth / focal)));
+    P.probability = 0.99;
+    P.boptimize = boptimize ? 1 : 0;
+    const int rows = (int)std::min<long long>(2LL * std::max(nmaxiter, 0), OV2_P3P_MAX_ROWS);
+    std::vector<int> samples(4 * (size_t)rows), outliers(n);
+    ov2_p3p_problem pb{};
+    pb.n = (int)n; pb.bv = bvs; pb.X = vwpts; pb.n_rows = rows; pb.samples = samples.data();
+    ov2_p3p_result r{};
+    r.outliers = outliers.data();
+    if (ov2_p3p_draw_samples(seed, (int)n, rows, samples.data()) != OV2_OK || ov2_p3p_ransac(ctx.get(), &P, &pb, &r) != OV2_OK) {
+        if (library_ok) *library_ok = false;
+        if (error) *error = ov2_last_error();
+        return false;
+    }
+    if (r.status != 0) return false;                                                           // :220-226
+    const double *m = r.model;                                                                 // Rwc row-major, twc
+    double q[4];                                                                               // x y z w: Eigen::Quaterniond(R)
+    double t = m[0] + m[4] + m[8];
+    if (t > 0.) {
+        t = std::sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+    const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);         // SO3::setQuaternion normalises
+    Twc[0] = m[9]; Twc[1] = m[10]; Twc[2] = m[11];
+    for (int i = 0; i < 4; i++) Twc[3 + i] = q[i] / qn;
+    voutliersidx.reserve(n);                                                                   // :241-251
+    voutliersidx.insert(voutliersidx.end(), outliers.begin(), outliers.begin() + r.n_outliers);
+    return true;
 }
 
 }  // namespace ov2
