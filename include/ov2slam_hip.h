@@ -1064,6 +1064,78 @@ int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items
  * for OpenGV's rand()-driven drawIndexSample.  OV2_EINVAL: n < 4, rows < 0, NULL out with rows > 0. */
 int ov2_p3p_draw_samples(unsigned long long seed, int n, int rows, int *out);
 
+/* ==================================================================== */
+/* Relative pose from 2D-2D matches (MultiViewGeometry::                */
+/* compute5ptEssentialMatrix, src/multi_view_geometry.cpp:594-696,      */
+/* USE_OPENGV)                                                          */
+/* ==================================================================== */
+/* What VisualFrontEnd::epipolar2d2dFiltering runs per frame, the initialisation once and the loop closer per candidate: Nister's
+ * five-point solver on the first five matches of a sample row, all EIGHT matches of the row pick among its solutions (real roots
+ * of the degree-10 polynomial x four decompositions), and the hypotheses are searched as OpenGV's sac::Ransac (largest inlier
+ * count, adaptive iteration bound with a sample size of 8) would.  fp64 (csrc/fivept.hip): ONE staging upload, three launches, ONE
+ * download, ONE synchronisation per call.
+ *
+ * The model is [R | t] with x1 = R x2 + t (the reference's Rwc, twc), |t| = 1: bv1^T [t]x R bv2 = 0.  The sample table is an
+ * INPUT (n_rows x 8 indices), so the result is a deterministic function of the arguments.  A row with a repeated or out-of-range
+ * index, without a real root or without a finite candidate is skipped WITHOUT counting an iteration.
+ *   RANSAC  k = 1; while iterations < k: a strictly larger inlier count (d < threshold) becomes the best and sets
+ *           k = log(1 - probability) / log(1 - (count / n)^8) (the argument clamped to [DBL_EPSILON, 1 - DBL_EPSILON]); ++iterations;
+ *           stop once iterations > max_iterations.
+ * d_i = (1 - bv1_i . p / |p|) + (1 - bv2_i . r / |r|), p the midpoint triangulation of the two rays (triangulate2), r = R^T (p - t).
+ * After the loop the outliers of the best model are the points with d_i >= threshold (or d_i not a number), ascending.  The full
+ * specification is tests/fivept_ref.py; OpenGV itself is not available to this project, so the solver and the loop are restated and
+ * nothing is pinned against an OpenGV binary.
+ *
+ * status: OV2_EPI_TOO_FEW_POINTS (n < 8: nothing else is set or searched), OV2_EPI_NO_MODEL (no valid row was reached; comes with
+ * OV2_EPI_FEW_INLIERS), OV2_EPI_FEW_INLIERS (fewer than 10, :665).  The reference returns false on any of them.
+ *
+ * boptimize must be 0: OpenGV's non-linear refinement (optimizeModelCoefficients on the inliers) is not provided.  The front end
+ * asks for it only in the mono branch when tracking is poor (src/visual_front_end.cpp:440-660); every other caller passes false.
+ *
+ * Capacity: OV2_EPI_MAX_POINTS points and OV2_EPI_MAX_ROWS rows per problem, 65535 problems per call.  OV2_EINVAL: NULL params /
+ * problem / result / ctx, a NULL array with a non-zero count, a negative count, a non-finite bearing, threshold <= 0 or not finite,
+ * probability outside (0, 1), max_iterations < 0, boptimize != 0, anything beyond the capacity.  All of it is checked on the host
+ * before any device work, the inputs before the context; a rejected call writes nothing. */
+enum { OV2_EPI_TOO_FEW_POINTS = 1, OV2_EPI_NO_MODEL = 2, OV2_EPI_FEW_INLIERS = 4 };
+#define OV2_EPI_MAX_POINTS 2048
+#define OV2_EPI_MAX_ROWS 4096
+typedef struct {
+    int max_iterations;          /* nmaxiter                                                                                 */
+    double threshold;            /* 2 (1 - cos(atan(errth / focal)))                                                         */
+    double probability;          /* 0.99                                                                                     */
+    int boptimize;               /* must be 0                                                                                */
+} ov2_epipolar_params;
+typedef struct {
+    int n;                       /* matches                                                                                  */
+    const double *bv1;           /* 3 n: unit bearing vectors of the keyframe                                                */
+    const double *bv2;           /* 3 n: unit bearing vectors of the current frame                                           */
+    int n_rows;                  /* rows of the sample table                                                                 */
+    const int *samples;          /* 8 n_rows                                                                                 */
+} ov2_epipolar_problem;
+typedef struct {
+    double model[12];            /* R row-major (9), t (3)                                                                   */
+    double score;                /* the best row's inlier count                                                              */
+    int best_row;                /* -1: no model                                                                             */
+    int iterations;              /* rows that counted                                                                        */
+    int rows_consumed;           /* rows the loop took from the table, skipped ones included                                 */
+    int status;                  /* OV2_EPI_* bits, 0 = the reference returns true                                           */
+    int n_inliers, n_outliers;
+    int *outliers;               /* n slots; the first n_outliers are written, ascending                                     */
+    uint8_t *trace_valid;        /* optional (NULL or n_rows): 1 where the row gave a hypothesis                             */
+    double *trace_score;         /* optional (NULL or n_rows): every row's inlier count, 0 for an invalid row                */
+    double *trace_model;         /* optional (NULL or 12 n_rows): every row's model, zeros for an invalid row                */
+} ov2_epipolar_result;
+/* one problem: the batch form with one item, through the same code path */
+int ov2_epipolar_ransac(ov2_ctx *ctx, const ov2_epipolar_params *params, const ov2_epipolar_problem *problem,
+                        ov2_epipolar_result *result);
+/* the problems of a lock-step batch, items [0, n_items) with shared params (the problem is a grid axis: each kernel is launched
+ * once).  Per item the result equals ov2_epipolar_ransac on that item bit for bit; sizes may differ, empty problems are allowed. */
+int ov2_epipolar_ransac_batch(ov2_ctx *ctx, const ov2_epipolar_params *params, int n_items, const ov2_epipolar_problem *problems,
+                              ov2_epipolar_result *results);
+/* Host only: rows x 8 indices of [0, n), distinct inside a row, from the stream of ov2_p3p_draw_samples.  OV2_EINVAL: n < 8,
+ * rows < 0, NULL out with rows > 0. */
+int ov2_epipolar_draw_samples(unsigned long long seed, int n, int rows, int *out);
+
 #ifdef __cplusplus
 }
 #endif

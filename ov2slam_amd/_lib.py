@@ -36,6 +36,8 @@ OV2_MATCH_BEHIND, OV2_MATCH_OUT_OF_FOV, OV2_MATCH_OUT_OF_IMAGE, OV2_MATCH_NO_CAN
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
+OV2_EPI_TOO_FEW_POINTS, OV2_EPI_NO_MODEL, OV2_EPI_FEW_INLIERS = 1, 2, 4
+OV2_EPI_MAX_POINTS, OV2_EPI_MAX_ROWS = 2048, 4096
 
 
 class Ov2Error(RuntimeError):
@@ -204,6 +206,25 @@ class P3PResult(C.Structure):
                 ("outliers", C.POINTER(C.c_int)), ("trace_valid", C.POINTER(C.c_uint8)), ("trace_score", C.POINTER(C.c_double))]
 
 
+class EpipolarParams(C.Structure):
+    """ov2_epipolar_params"""
+    _fields_ = [("max_iterations", C.c_int), ("threshold", C.c_double), ("probability", C.c_double), ("boptimize", C.c_int)]
+
+
+class EpipolarProblem(C.Structure):
+    """ov2_epipolar_problem"""
+    _fields_ = [("n", C.c_int), ("bv1", C.POINTER(C.c_double)), ("bv2", C.POINTER(C.c_double)), ("n_rows", C.c_int),
+                ("samples", C.POINTER(C.c_int))]
+
+
+class EpipolarResult(C.Structure):
+    """ov2_epipolar_result"""
+    _fields_ = [("model", C.c_double * 12), ("score", C.c_double), ("best_row", C.c_int), ("iterations", C.c_int),
+                ("rows_consumed", C.c_int), ("status", C.c_int), ("n_inliers", C.c_int), ("n_outliers", C.c_int),
+                ("outliers", C.POINTER(C.c_int)), ("trace_valid", C.POINTER(C.c_uint8)), ("trace_score", C.POINTER(C.c_double)),
+                ("trace_model", C.POINTER(C.c_double))]
+
+
 class XYZBAResult(C.Structure):
     _fields_ = [
         ("poses_out", C.POINTER(C.c_double)), ("xyz_out", C.POINTER(C.c_double)), ("chi2_last_eval", C.POINTER(C.c_double)),
@@ -321,6 +342,9 @@ SIGNATURES = {
     "ov2_p3p_ransac": (_i, [_vp, C.POINTER(P3PParams), C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_ransac_batch": (_i, [_vp, C.POINTER(P3PParams), _i, C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),
+    "ov2_epipolar_ransac": (_i, [_vp, C.POINTER(EpipolarParams), C.POINTER(EpipolarProblem), C.POINTER(EpipolarResult)]),
+    "ov2_epipolar_ransac_batch": (_i, [_vp, C.POINTER(EpipolarParams), _i, C.POINTER(EpipolarProblem), C.POINTER(EpipolarResult)]),
+    "ov2_epipolar_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

@@ -10,4 +10,5 @@
 // the adapters that are free functions: taking their addresses keeps their signatures checked
 static auto *const check_ceres_pnp = &ov2::ceresPnP;
 static auto *const check_p3p_ransac = &ov2::p3pRansac;
-int main() { return check_ceres_pnp && check_p3p_ransac ? 0 : 1; }
+static auto *const check_5pt = &ov2::compute5ptEssentialMatrix;
+int main() { return check_ceres_pnp && check_p3p_ransac && check_5pt ? 0 : 1; }

@@ -12,6 +12,11 @@
 // ov2::p3pRansac -- MultiViewGeometry::p3pRansac in its USE_OPENGV form (:144-343): Kneip's P3P under OpenGV's LMedS (the front end,
 // src/visual_front_end.cpp:729-742) or RANSAC loop (the loop closer, src/loop_closer.cpp:817) on the device (ov2_p3p_ransac,
 // csrc/p3p.hip).  OpenGV's solver and loops are restated, not linked: same algorithm, another random stream (see below).
+//
+// ov2::compute5ptEssentialMatrix -- MultiViewGeometry::compute5ptEssentialMatrix in its USE_OPENGV form (:594-696): Nister's five-point
+// solver under OpenGV's RANSAC loop (the epipolar filter of the front end, src/visual_front_end.cpp:440-660, the initialisation, :946,
+// and the loop closer, src/loop_closer.cpp:483) on the device (ov2_epipolar_ransac, csrc/fivept.hip).  Restated like the P3P search,
+// not pinned against an OpenGV binary.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -142,6 +147,48 @@ inline bool p3pRansac(Context &ctx, const double *bvs, const double *vwpts, size
     Twc[0] = m[9]; Twc[1] = m[10]; Twc[2] = m[11];
     for (int i = 0; i < 4; i++) Twc[3 + i] = q[i] / qn;
     voutliersidx.reserve(n);                                                                   // :241-251
+    voutliersidx.insert(voutliersidx.end(), outliers.begin(), outliers.begin() + r.n_outliers);
+    return true;
+}
+
+// bvs1 / bvs2: n x 3 unit bearing vectors of the keyframe and of the current frame.  Rwc (row-major 3 x 3), twc and voutliersidx are
+// written only when the function returns true, as the reference returns before it touches them on its false paths (n < 8, fewer
+// than 10 inliers).  The model is x1 = Rwc x2 + twc with |twc| = 1.
+// bdorandom selects the seed policy of the sample table (ov2_epipolar_draw_samples, 2 x nmaxiter rows so that skipped rows do not
+// shorten the search, at most OV2_EPI_MAX_ROWS): false = the fixed seed 0, so that two calls on the same matches agree, as OpenGV's
+// constant srand does; true = the caller's `seed`, which the caller varies, standing in for OpenGV's clock-seeded rand().
+// boptimize (OpenGV's non-linear refinement on the inliers; the front end asks for it only in the mono branch when tracking is
+// poor) is not provided: the call fails (*library_ok = false).
+inline bool compute5ptEssentialMatrix(Context &ctx, const double *bvs1, const double *bvs2, size_t n, int nmaxiter, float errth,
+                                      bool boptimize, bool bdorandom, float fx, float fy, double Rwc[9], double twc[3],
+                                      std::vector<int> &voutliersidx, unsigned long long seed = 0, bool *library_ok = nullptr,
+                                      std::string *error = nullptr)
+{
+    if (library_ok) *library_ok = true;
+    if (n < 8) return false;                                                                   // :624-626
+    float focal = fx + fy;                                                                     // :654-658
+    focal /= 2.;
+    ov2_epipolar_params P{};
+    P.max_iterations = nmaxiter;
+    P.threshold = 2.0 * (1.0 - std::cos(std::atan((double)(errth / focal))));
+    P.probability = 0.99;
+    P.boptimize = boptimize ? 1 : 0;
+    const int rows = (int)std::min<long long>(2LL * std::max(nmaxiter, 0), OV2_EPI_MAX_ROWS);
+    std::vector<int> samples(8 * (size_t)rows), outliers(n);
+    ov2_epipolar_problem pb{};
+    pb.n = (int)n; pb.bv1 = bvs1; pb.bv2 = bvs2; pb.n_rows = rows; pb.samples = samples.data();
+    ov2_epipolar_result r{};
+    r.outliers = outliers.data();
+    if (ov2_epipolar_draw_samples(bdorandom ? seed : 0ull, (int)n, rows, samples.data()) != OV2_OK ||
+        ov2_epipolar_ransac(ctx.get(), &P, &pb, &r) != OV2_OK) {
+        if (library_ok) *library_ok = false;
+        if (error) *error = ov2_last_error();
+        return false;
+    }
+    if (r.status != 0) return false;                                                           // :665-667
+    for (int i = 0; i < 9; i++) Rwc[i] = r.model[i];                                            // :669-670
+    for (int i = 0; i < 3; i++) twc[i] = r.model[9 + i];
+    voutliersidx.reserve(n);                                                                   // :683-693
     voutliersidx.insert(voutliersidx.end(), outliers.begin(), outliers.begin() + r.n_outliers);
     return true;
 }
