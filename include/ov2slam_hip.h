@@ -1136,6 +1136,85 @@ int ov2_epipolar_ransac_batch(ov2_ctx *ctx, const ov2_epipolar_params *params, i
  * rows < 0, NULL out with rows > 0. */
 int ov2_epipolar_draw_samples(unsigned long long seed, int n, int rows, int *out);
 
+/* ==================================================================== */
+/* Pose-graph optimisation (Optimizer::localPoseGraph,                  */
+/* src/optimizer.cpp:2346-2591, and Optimizer::fullPoseGraph,           */
+/* :2783-2865)                                                          */
+/* ==================================================================== */
+/* One ceres::Solve over SE(3) poses Twc ([tx ty tz qx qy qz qw], SE3LeftParameterization: T <- Exp(delta) T) tied by
+ * LeftSE3RelativePoseError blocks (src/ceres_parametrization.cpp:30-102): for an edge (i, j) with measurement Tc_i c_j
+ *   err = Twc_j^-1 Twc_i Tc_i c_j,   r = (1 / sigma) log(err)   (Sophus SE(3) log, [rho; omega]),
+ * with the reference's approximate Jacobians as written there ("adapted from Strasdat"), not the derivative of r.
+ * fp64 (csrc/posegraph.hip): ONE staging upload, ONE launch that runs the whole Levenberg-Marquardt loop (one work-group per
+ * problem, the trust-region rules of the other device solvers), ONE download, ONE synchronisation per call.
+ *
+ * The two option sets of the reference, both SPARSE_NORMAL_CHOLESKY / LM without a loss function and Ceres' defaults elsewhere
+ * (ov2_ba_default_options, then):
+ *   localPoseGraph  max_iter 10,  function_tolerance 1e-4, huber_delta 0   (:2441-2446)
+ *   fullPoseGraph   max_iter 100, function_tolerance 1e-6, huber_delta 0   (:2820-2825)
+ * huber_delta > 0 is OV2_EUNSUPPORTED (the reference passes no loss function).  max_solver_time_s > 0 is OV2_EUNSUPPORTED too: the
+ * loop runs inside one launch and, like ov2_structure_ba, has no clock to stop it (that solver ignores the field; this one
+ * refuses it, so a caller does not believe in a limit that is not there).
+ *
+ * Structure.  Order the variable poses (pose_const[i] == 0) by their index.  An edge may join a variable pose and a constant
+ * one, or two variable poses that are NEIGHBOURS in that order, in either direction and any number of times (with two poses the
+ * chain edge and the loop edge of localPoseGraph are the same pair).  The normal matrix is then block-tridiagonal with 6x6
+ * blocks and falls into independent segments wherever two neighbours share no edge; SPARSE_NORMAL_CHOLESKY's exact solve of
+ * (J^T J + D^2) y = J^T r is a block Cholesky recurrence along each segment.  Both problems of the reference have this form.  An
+ * edge between two variable poses that are not neighbours is OV2_EUNSUPPORTED (the message names the edge), i == j is
+ * OV2_EINVAL; nothing is enqueued.
+ *
+ * Deviation from Ceres: an edge whose two ends are constant (two consecutive keyframes in fullPoseGraph) takes no part in the
+ * program and none in initial_cost / final_cost.  Ceres would add it to both as "fixed cost", which nobody reads.  A variable
+ * pose without an edge is not in the program either (as in Ceres) and comes back unchanged.
+ *
+ * A problem without a variable pose, or without an edge that touches one, returns OV2_OK with poses_out = poses, iterations = 0
+ * and termination = OV2_TERM_FUNCTION_TOL (Ceres: "no non-constant parameter blocks").  A block factorisation that meets a
+ * non-positive or non-finite pivot is an invalid step (the radius shrinks); a solve whose run of max_consecutive_invalid_steps
+ * invalid steps ends on such a failure reports OV2_TERM_FAILURE and returns its INPUT poses (Ceres does not write back an unusable
+ * solution).
+ *
+ * With OV2_OPT_BA_TRACE = 1, ov2_pose_graph_solve fills the context's iteration trace (ov2_ba_get_trace), with the meaning it has
+ * for ov2_ba_solve.  A batch call records none, unless it has exactly one item.
+ *
+ * Capacity: OV2_PG_MAX_POSES poses and OV2_PG_MAX_EDGES edges per problem, 65535 problems per call.  OV2_EINVAL: a NULL
+ * argument or array, a negative count, anything beyond the capacity, a pose / measurement / sigma that is not finite, a zero
+ * quaternion, sigma <= 0, an edge index out of range, i == j, max_iter < 0.  Everything is checked on the host before the context
+ * is looked at; a rejected call writes none of its outputs. */
+#define OV2_PG_MAX_POSES 16384
+#define OV2_PG_MAX_EDGES 32768
+typedef struct {
+    int n_poses;
+    const double *poses;         /* 7 n_poses: Twc                                                                            */
+    const uint8_t *pose_const;   /* n_poses: 1 = constant block (the loop keyframe; the keyframes of fullPoseGraph)           */
+    int n_edges;
+    const int *edge_i, *edge_j;  /* n_edges each                                                                              */
+    const double *edge_T;        /* 7 n_edges: Tc_i c_j                                                                       */
+    const double *edge_sigma;    /* n_edges, or NULL = 1 (both call sites of the reference)                                   */
+} ov2_pg_problem;
+typedef struct {
+    double *poses_out;           /* 7 n_poses                                                                                 */
+    int iterations, num_successful_steps;
+    double initial_cost, final_cost;
+    int termination;             /* OV2_TERM_*                                                                                */
+    double solve_ms;             /* device time of the launch (the batch: of the whole batch)                                 */
+} ov2_pg_result;
+int ov2_pose_graph_solve(ov2_ctx *ctx, const ov2_pg_problem *p, const ov2_ba_options *o, ov2_pg_result *r);
+/* n_items independent problems with shared options, one work-group each in the same launch.  Per item the result equals
+ * ov2_pose_graph_solve on that item bit for bit; an item that fails (OV2_TERM_FAILURE) does not disturb the others. */
+int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *p, const ov2_ba_options *o, ov2_pg_result *r);
+/* What localPoseGraph does with the solution (:2476-2585), k_pg_apply.  win_old / win_new: the n_win window keyframes before and
+ * after the solve.  Every younger keyframe and the current frame (young_old, n_young poses) get
+ *   young_new = newopt_Twc (ini_Tcw young_old),
+ * and every 3-D point moves rigidly with the keyframe it is anchored in (pt_kf in [0, n_win + n_young), the younger ones after
+ * the window): xyz_out = Twc_new (Tcw_old xyz).  Quaternions are renormalised after each product, as Sophus::SE3d does.  The
+ * 0.3 m test on the optimised pose of the new keyframe (:2467-2474, stereo only) is the caller's.  OV2_EINVAL: NULL array with a
+ * non-zero count, negative count, n_win + n_young = 0 with n_pts > 0, pt_kf out of range, a pose that is not finite or has a
+ * zero quaternion, more than 2^24 keyframes or 2^27 points. */
+int ov2_pose_graph_apply(ov2_ctx *ctx, int n_win, const double *win_old, const double *win_new, const double ini_Tcw[7],
+                         const double newopt_Twc[7], int n_young, const double *young_old, double *young_new, int n_pts,
+                         const double *xyz, const int *pt_kf, double *xyz_out);
+
 #ifdef __cplusplus
 }
 #endif

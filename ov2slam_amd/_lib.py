@@ -38,6 +38,9 @@ OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHO
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
 OV2_EPI_TOO_FEW_POINTS, OV2_EPI_NO_MODEL, OV2_EPI_FEW_INLIERS = 1, 2, 4
 OV2_EPI_MAX_POINTS, OV2_EPI_MAX_ROWS = 2048, 4096
+OV2_PG_MAX_POSES, OV2_PG_MAX_EDGES = 16384, 32768
+OV2_TERM_NO_CONVERGENCE, OV2_TERM_FUNCTION_TOL, OV2_TERM_PARAMETER_TOL, OV2_TERM_GRADIENT_TOL = 0, 1, 2, 3
+OV2_TERM_MIN_RADIUS, OV2_TERM_INVALID_STEPS, OV2_TERM_FAILURE = 4, 5, 6
 
 
 class Ov2Error(RuntimeError):
@@ -225,6 +228,19 @@ class EpipolarResult(C.Structure):
                 ("trace_model", C.POINTER(C.c_double))]
 
 
+class PGProblem(C.Structure):
+    """ov2_pg_problem"""
+    _fields_ = [("n_poses", C.c_int), ("poses", C.POINTER(C.c_double)), ("pose_const", C.POINTER(C.c_uint8)), ("n_edges", C.c_int),
+                ("edge_i", C.POINTER(C.c_int)), ("edge_j", C.POINTER(C.c_int)), ("edge_T", C.POINTER(C.c_double)),
+                ("edge_sigma", C.POINTER(C.c_double))]
+
+
+class PGResult(C.Structure):
+    """ov2_pg_result"""
+    _fields_ = [("poses_out", C.POINTER(C.c_double)), ("iterations", C.c_int), ("num_successful_steps", C.c_int),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("termination", C.c_int), ("solve_ms", C.c_double)]
+
+
 class XYZBAResult(C.Structure):
     _fields_ = [
         ("poses_out", C.POINTER(C.c_double)), ("xyz_out", C.POINTER(C.c_double)), ("chi2_last_eval", C.POINTER(C.c_double)),
@@ -345,6 +361,9 @@ SIGNATURES = {
     "ov2_epipolar_ransac": (_i, [_vp, C.POINTER(EpipolarParams), C.POINTER(EpipolarProblem), C.POINTER(EpipolarResult)]),
     "ov2_epipolar_ransac_batch": (_i, [_vp, C.POINTER(EpipolarParams), _i, C.POINTER(EpipolarProblem), C.POINTER(EpipolarResult)]),
     "ov2_epipolar_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),
+    "ov2_pose_graph_solve": (_i, [_vp, C.POINTER(PGProblem), C.POINTER(BAOptions), C.POINTER(PGResult)]),
+    "ov2_pose_graph_solve_batch": (_i, [_vp, _i, C.POINTER(PGProblem), C.POINTER(BAOptions), C.POINTER(PGResult)]),
+    "ov2_pose_graph_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

@@ -80,6 +80,18 @@ struct FlatXYZProblem : FlatStructureProblem {
     }
 };
 
+// Flat form of the ceres::Problem of Optimizer::localPoseGraph (src/optimizer.cpp:2373-2424) and fullPoseGraph (:2794-2814):
+// SE(3) poses (SE3LeftParameterization) and LeftSE3RelativePoseError blocks.
+struct FlatPoseGraph {
+    std::vector<double> poses;          // 7 per pose: Twc
+    std::vector<uint8_t> pose_const;    // SetParameterBlockConstant
+    std::vector<int> edge_i, edge_j;
+    std::vector<double> edge_T;         // 7 per edge: Tc_i c_j
+
+    int addPose(const double pose[7], bool constant) { poses.insert(poses.end(), pose, pose + 7); pose_const.push_back(constant); return (int)pose_const.size() - 1; }
+    void addEdge(int i, int j, const double Tcicj[7]) { edge_i.push_back(i); edge_j.push_back(j); edge_T.insert(edge_T.end(), Tcicj, Tcicj + 7); }
+};
+
 struct LocalBAResult {
     bool ok = false, l2_done = false;
     // why a solve was skipped (ok == false): the library's return code and message, e.g. OV2_EUNSUPPORTED "reduced system too
@@ -189,6 +201,39 @@ public:
         ov2_sba_result res{};
         res.xyz_out = xyz_out.data();
         return ov2_structure_ba(ctx.get(), &p, &opt, &res) == OV2_OK;
+    }
+
+    // The ceres::Solve of Optimizer::localPoseGraph (src/optimizer.cpp:2441-2451: 10 iterations, function_tolerance 1e-4) or, with
+    // full, of fullPoseGraph (:2820-2830: 100 iterations, 1e-6); no loss function.  On success `poses_out` holds every pose, the
+    // constant ones unchanged.  What follows in localPoseGraph is the caller's: reject the solution when the optimised new keyframe
+    // lies more than 0.3 m from newTwc in stereo (:2467-2474), else applyPoseGraph.  termination (or NULL): OV2_TERM_*; a solve
+    // that ends with OV2_TERM_FAILURE returns false and the input poses.
+    bool solvePoseGraph(Context &ctx, const FlatPoseGraph &pg, bool full, std::vector<double> &poses_out, int *termination = nullptr) const
+    {
+        ov2_pg_problem p{};
+        p.n_poses = (int)pg.pose_const.size(); p.poses = pg.poses.data(); p.pose_const = pg.pose_const.data();
+        p.n_edges = (int)pg.edge_i.size(); p.edge_i = pg.edge_i.data(); p.edge_j = pg.edge_j.data(); p.edge_T = pg.edge_T.data();
+        p.edge_sigma = nullptr;
+        ov2_ba_options opt; ov2_ba_default_options(&opt);
+        opt.max_iter = full ? 100 : 10; opt.function_tolerance = full ? 1e-6 : 1e-4; opt.huber_delta = 0.0;
+        poses_out.assign(pg.poses.size(), 0.0);
+        ov2_pg_result res{};
+        res.poses_out = poses_out.data();
+        if (ov2_pose_graph_solve(ctx.get(), &p, &opt, &res) != OV2_OK) return false;
+        if (termination) *termination = res.termination;
+        return res.termination != OV2_TERM_FAILURE;
+    }
+
+    // What localPoseGraph does with its solution (src/optimizer.cpp:2476-2585): the younger keyframes and the current frame
+    // (young_old, 7 each) get newopt_Twc (ini_Tcw young_old), every 3-D point moves with the keyframe it is anchored in
+    // (pt_kf: window keyframes first, then the younger ones).
+    bool applyPoseGraph(Context &ctx, const std::vector<double> &win_old, const std::vector<double> &win_new, const double ini_Tcw[7],
+                        const double newopt_Twc[7], const std::vector<double> &young_old, std::vector<double> &young_new,
+                        const std::vector<double> &xyz, const std::vector<int> &pt_kf, std::vector<double> &xyz_out) const
+    {
+        young_new.assign(young_old.size(), 0.0); xyz_out.assign(xyz.size(), 0.0);
+        return ov2_pose_graph_apply(ctx.get(), (int)win_old.size() / 7, win_old.data(), win_new.data(), ini_Tcw, newopt_Twc, (int)young_old.size() / 7,
+                                    young_old.data(), young_new.data(), (int)xyz.size() / 3, xyz.data(), pt_kf.data(), xyz_out.data()) == OV2_OK;
     }
 
     // Optimizer::looseBA (src/optimizer.cpp:900-1672): same residual blocks, ONE solve (5 it, function_tolerance

@@ -170,6 +170,137 @@ def structure_only_ba(ctx, prob, opts=None, res_active=None):
                 termination=R.termination, solve_ms=R.solve_ms)
 
 
+def _pg_pack(prob, want_out=True):
+    """dict(poses (n, 7) Twc, pose_const (n), edge_i, edge_j (m), edge_T (m, 7) Tc_i c_j[, edge_sigma (m)]) ->
+    (PGProblem, PGResult, poses_out, keep-alive list)"""
+    keep = []
+
+    def arr(v, dt):
+        a = np.ascontiguousarray(v, dt); keep.append(a)
+        return a
+
+    P = L.PGProblem()
+    poses = arr(prob["poses"], np.float64).reshape(-1, 7)
+    ei = arr(prob["edge_i"], np.int32)
+    P.n_poses, P.n_edges = len(poses), len(ei)
+    P.poses = _dp(poses); P.pose_const = _u8p(arr(prob["pose_const"], np.uint8))
+    P.edge_i = _ip(ei); P.edge_j = _ip(arr(prob["edge_j"], np.int32)); P.edge_T = _dp(arr(prob["edge_T"], np.float64))
+    if prob.get("edge_sigma") is not None:
+        P.edge_sigma = _dp(arr(prob["edge_sigma"], np.float64))
+    out = np.zeros((max(1, P.n_poses), 7))
+    R = L.PGResult()
+    R.poses_out = _dp(out)
+    return P, R, out, keep
+
+
+def pose_graph_options(lib, full=False, **kw):
+    """the reference's two option sets: localPoseGraph (src/optimizer.cpp:2441-2446) or, full=True, fullPoseGraph (:2820-2825)"""
+    o = dict(max_iter=100, function_tolerance=1e-6) if full else dict(max_iter=10, function_tolerance=1e-4)
+    o.update(huber_delta=0.0)
+    o.update(kw)
+    return default_options(lib, **o)
+
+
+def _pg_result(P, R, out):
+    return dict(poses=out[:P.n_poses], iterations=R.iterations, num_successful_steps=R.num_successful_steps, initial_cost=R.initial_cost,
+                final_cost=R.final_cost, termination=R.termination, solve_ms=R.solve_ms)
+
+
+def pose_graph(ctx, prob, opts=None, trace=False):
+    """One ceres::Solve of a pose graph (ov2_pose_graph_solve).  opts: default = localPoseGraph's.  trace: with the iteration
+    summaries under "trace"."""
+    if trace:
+        prev = ctx.get_option(L.OV2_OPT_BA_TRACE)
+        ctx.set_option(L.OV2_OPT_BA_TRACE, 1)
+        try:
+            d = pose_graph(ctx, prob, opts)
+            d["trace"] = last_trace(ctx)
+        finally:
+            ctx.set_option(L.OV2_OPT_BA_TRACE, prev)
+        return d
+    opts = opts or pose_graph_options(ctx.lib)
+    P, R, out, keep = _pg_pack(prob)
+    L.check(ctx.lib.ov2_pose_graph_solve(ctx.h, C.byref(P), C.byref(opts), C.byref(R)))
+    return _pg_result(P, R, out)
+
+
+def pose_graph_batch(ctx, probs, opts=None):
+    """Independent pose graphs in one launch (ov2_pose_graph_solve_batch): a list of dicts as pose_graph returns them."""
+    opts = opts or pose_graph_options(ctx.lib)
+    n = len(probs)
+    PA = (L.PGProblem * max(1, n))(); RA = (L.PGResult * max(1, n))()
+    packed = [_pg_pack(p) for p in probs]
+    for i, (P, R, out, keep) in enumerate(packed):
+        PA[i] = P; RA[i] = R
+    L.check(ctx.lib.ov2_pose_graph_solve_batch(ctx.h, n, PA, C.byref(opts), RA))
+    return [_pg_result(PA[i], RA[i], packed[i][2]) for i in range(n)]
+
+
+def pose_graph_apply(ctx, win_old, win_new, ini_Tcw, newopt_Twc, young_old, xyz, pt_kf):
+    """What localPoseGraph does with its solution (ov2_pose_graph_apply, src/optimizer.cpp:2476-2585): (young_new, xyz_out)."""
+    wo = np.ascontiguousarray(win_old, np.float64).reshape(-1, 7); wn = np.ascontiguousarray(win_new, np.float64).reshape(-1, 7)
+    yo = np.ascontiguousarray(young_old, np.float64).reshape(-1, 7); X = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    kf = np.ascontiguousarray(pt_kf, np.int32)
+    ini = np.ascontiguousarray(ini_Tcw, np.float64); new = np.ascontiguousarray(newopt_Twc, np.float64)
+    yn = np.zeros((max(1, len(yo)), 7)); Xo = np.zeros((max(1, len(X)), 3))
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    L.check(ctx.lib.ov2_pose_graph_apply(ctx.h, len(wo), vp(wo), vp(wn), vp(ini), vp(new), len(yo), vp(yo), vp(yn), len(X), vp(X), vp(kf), vp(Xo)))
+    return yn[:len(yo)], Xo[:len(X)]
+
+
+def inv_pose(T):
+    """[t q] of T^-1 (float64, unit quaternion assumed up to normalisation)"""
+    T = np.asarray(T, np.float64)
+    q = T[3:] / np.linalg.norm(T[3:])
+    x, y, z, w = q
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    return np.concatenate([-(R.T @ T[:3]), [-x, -y, -z, w]])
+
+
+def mul_pose(A, B):
+    """[t q] of A B"""
+    A = np.asarray(A, np.float64); B = np.asarray(B, np.float64)
+    ax, ay, az, aw = A[3:] / np.linalg.norm(A[3:]); bx, by, bz, bw = B[3:] / np.linalg.norm(B[3:])
+    q = np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                  aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz])
+    q /= np.linalg.norm(q)
+    x, y, z, w = ax, ay, az, aw
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    return np.concatenate([A[:3] + R @ B[:3], q])
+
+
+def local_pose_graph_problem(poses, loop_edge_T):
+    """Optimizer::localPoseGraph's problem (src/optimizer.cpp:2373-2424).  poses: Twc of the keyframes that exist between the loop
+    keyframe (first, constant) and the new keyframe (last), one entry per keyframe id, None where the map has no keyframe of that
+    id (skipped, :2391-2396; a missing new keyframe: None is returned where the reference returns false); loop_edge_T = Tcw_loop
+    newTwc.  One edge between consecutive keyframes measuring their current relative pose, then the loop edge from the first to
+    the last."""
+    if not isinstance(poses, np.ndarray):
+        if poses[-1] is None:
+            return None
+        poses = [p for p in poses if p is not None]
+    poses = np.asarray(poses, np.float64).reshape(-1, 7)
+    n = len(poses)
+    chain = [mul_pose(inv_pose(poses[k - 1]), poses[k]) for k in range(1, n)]
+    const = np.zeros(n, np.uint8); const[0] = 1
+    return dict(poses=poses, pose_const=const, edge_i=np.array(list(range(n - 1)) + [0], np.int32),
+                edge_j=np.array(list(range(1, n)) + [n - 1], np.int32),
+                edge_T=np.array(chain + [np.asarray(loop_edge_T, np.float64)]).reshape(-1, 7))
+
+
+def full_pose_graph_problem(vTwc, vTpc, viskf):
+    """Optimizer::fullPoseGraph's problem (src/optimizer.cpp:2794-2814): every frame a pose, keyframes constant, an edge
+    (i - 1, i) measuring vTpc[i] for i >= 1 (vTpc[0] is not used)."""
+    vTwc = np.asarray(vTwc, np.float64).reshape(-1, 7); vTpc = np.asarray(vTpc, np.float64).reshape(-1, 7)
+    n = len(vTwc)
+    return dict(poses=vTwc, pose_const=np.asarray(viskf, bool).astype(np.uint8), edge_i=np.arange(0, max(0, n - 1), dtype=np.int32),
+                edge_j=np.arange(1, max(1, n), dtype=np.int32), edge_T=vTpc[1:])
+
+
 class ResidentProblem:
     """ov2_ba_create / ov2_ba_solve_resident: the problem stays in HBM between solves."""
 
@@ -206,8 +337,8 @@ class ResidentProblem:
 
 
 class Optimizer:
-    """Mirror of /root/reference/include/optimizer.hpp:36-60: localBA, looseBA, fullBA (structureOnlyBA: see
-    structure_only_ba below; the two pose-graph solvers are out of scope).
+    """Mirror of /root/reference/include/optimizer.hpp:36-60: localBA, looseBA, fullBA, structureOnlyBA (see
+    structure_only_ba above), localPoseGraph and fullPoseGraph (pose_graph above).
 
     localBA(problem, buse_robust_cost) runs optimizer.cpp:436-627 on a flat problem:
       pass 1  Huber(sqrt(robust_mono_th)), 5 iterations, function_tolerance 1e-3          (:436-485)
@@ -368,6 +499,20 @@ class Optimizer:
         function_tolerance 1e-3; the map points take the optimised positions (:2768-2779), no outlier handling."""
         return structure_only_ba(self.ctx, prob, default_options(self.ctx.lib, max_iter=10, function_tolerance=1e-3,
                                                                  huber_delta=math.sqrt(self.robust_mono_th)))
+
+    def localPoseGraph(self, poses, loop_edge_T):
+        """Optimizer::localPoseGraph's solve (src/optimizer.cpp:2373-2457): `poses` = Twc of the keyframes from the loop keyframe
+        (constant) to the new one, loop_edge_T = Tcw_loop newTwc; 10 iterations, function_tolerance 1e-4.  The caller rejects the
+        result when poses[-1] lies more than 0.3 m from newTwc in stereo (:2467-2474) and otherwise moves the map with
+        pose_graph_apply (:2476-2585).  Entries of `poses` may be None for keyframe ids the map no longer has (:2391-2396)."""
+        prob = local_pose_graph_problem(poses, loop_edge_T)
+        if prob is None:                                        # the new keyframe is not in the map: the reference returns false (:2392-2393)
+            return None
+        return pose_graph(self.ctx, prob, pose_graph_options(self.ctx.lib, full=False))
+
+    def fullPoseGraph(self, vTwc, vTpc, viskf):
+        """Optimizer::fullPoseGraph's solve (src/optimizer.cpp:2794-2830): 100 iterations, function_tolerance 1e-6."""
+        return pose_graph(self.ctx, full_pose_graph_problem(vTwc, vTpc, viskf), pose_graph_options(self.ctx.lib, full=True))
 
     def looseBA(self, prob, buse_robust_cost=True):
         """Optimizer::looseBA (src/optimizer.cpp:900-1672) on a flat problem -- the loop-closure BA over the KFs
