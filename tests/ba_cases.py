@@ -1,0 +1,284 @@
+"""Bundle-adjustment problems of IRREGULAR structure (plain numpy), in the layouts of ov2slam_amd.synth.make_ba_problem /
+make_xyz_ba_problem / make_structure_problem -- what the oracle and ov2slam_amd.optimizer take.
+
+synth's generators give every landmark the same number of residual blocks, hand the blocks over landmark by landmark, weigh them
+all alike and use one calibration and an unrotated stereo pair.  Here the caller states the number of residual blocks of every
+landmark, and everything else varies too:
+  * a stereo observer contributes LEFT + RIGHT, a share of the observers LEFT only or RIGHT only; RIGHT_ANCH on some landmarks,
+  * few anchor keyframes; constant keyframes anywhere; one free keyframe that no block touches,
+  * res_sigma in 1.2^{0..3}, calib_r != calib_l, T_rl with a rotation of half a degree,
+  * gross outliers: a few percent of the blocks, and EVERY block of the `dead` landmarks (they lose all blocks in localBA's pass 1),
+  * a seeded permutation of the block order (shuffle_blocks); the landmark-sorted problem and the permutation stay available.
+The scene is shared by the three forms: keyframes on a 10 m arc, 1 degree apart, looking at the volume around the centre, so that
+every keyframe of a 70-keyframe window sees every landmark."""
+import numpy as np
+
+from ov2slam_amd.synth import _quat_from_R, _so3_exp
+
+LEFT, RIGHT, RIGHT_ANCH = 0, 1, 2
+CALIB_L = np.array([458.654, 457.296, 367.215, 248.375])
+CALIB_R = np.array([457.587, 456.134, 379.999, 255.238])
+T_RL_ROT = np.array([0.004, -0.006, 0.005])                      # |w| = 0.0088 rad = 0.50 degrees
+T_RL = np.concatenate([[-0.11, 0.002, -0.001], _quat_from_R(_so3_exp(T_RL_ROT))])
+SIGMAS = 1.2 ** np.arange(4)
+
+# the count patterns of standard_layout: name -> the counts of eight consecutive landmarks of one anchor
+RUN_PATTERNS = {"all 32": [32] * 8, "32/33": [32, 33] * 4, "0/5": [0, 5] * 4, "1/31": [1, 31] * 4, "all 33": [33] * 8,
+                "all 64": [64] * 8, "all 65": [65] * 8}
+
+
+class _Scene:
+    def __init__(self, n_kf):
+        th = np.deg2rad(1.0) * np.arange(n_kf)
+        self.t = 10.0 * np.stack([np.cos(th), np.sin(th), np.zeros(n_kf)], 1)
+        zc = -np.stack([np.cos(th), np.sin(th), np.zeros(n_kf)], 1)
+        yc = np.tile(np.array([0, 0, -1.0]), (n_kf, 1))
+        self.R = np.stack([np.cross(yc, zc), yc, zc], 2)          # (n_kf, 3, 3) Rwc: columns = camera axes
+        self.poses = np.zeros((n_kf, 7))
+        self.poses[:, :3] = self.t
+        for k in range(n_kf):
+            self.poses[k, 3:] = _quat_from_R(self.R[k])
+        self.R_rl = _so3_exp(T_RL_ROT)
+
+    def project(self, kf, X, right):
+        """pixel and depth of the world point X in the left / right camera of keyframe kf"""
+        pc = self.R[kf].T @ (X - self.t[kf])
+        K = CALIB_L
+        if right:
+            pc = self.R_rl @ pc + T_RL[:3]
+            K = CALIB_R
+        return np.array([K[0] * pc[0] / pc[2] + K[2], K[1] * pc[1] / pc[2] + K[3]]), pc[2]
+
+    def noisy_poses(self, rng, kf_const, pose_noise):
+        p = self.poses.copy()
+        for k in range(len(p)):
+            dt = rng.normal(0, pose_noise[0], 3); dw = rng.normal(0, pose_noise[1], 3)
+            if not kf_const[k]:
+                p[k, :3] += dt
+                p[k, 3:] = _quat_from_R(_so3_exp(dw) @ self.R[k])
+        return p
+
+
+def _observers(c_obs, avail, rng, single_share, all_single=False):
+    """c_obs LEFT / RIGHT blocks of one landmark -> [(keyframe, type)] in keyframe order: stereo observers give LEFT then RIGHT,
+    as many as possible; about `single_share` of the observers (and one more where c_obs is odd) give one block only"""
+    if c_obs == 0:
+        return []
+    odd = c_obs & 1
+    s = c_obs if all_single else odd + 2 * int(rng.binomial(c_obs // 2, 0.5 * single_share))
+    s = min(s, c_obs, 2 * len(avail) - c_obs)
+    if s < odd:
+        raise ValueError("%d blocks need more than the %d keyframes available" % (c_obs, len(avail)))
+    n_obs = (c_obs + s) // 2
+    kfs = np.sort(rng.choice(avail, n_obs, replace=False))
+    single = np.zeros(n_obs, bool); single[rng.choice(n_obs, s, replace=False)] = True
+    out = []
+    for k, one in zip(kfs, single):
+        out += [(int(k), int(rng.integers(0, 2)))] if one else [(int(k), LEFT), (int(k), RIGHT)]
+    return out
+
+
+def _noise(rng, sigma, gross, px_noise, k=None):
+    """pixel noise of one block; gross: 30 .. 60 sigma, in a random direction or, for block k of a dead landmark, within 20
+    degrees of the image's vertical with alternating sign: the keyframes move horizontally, so neither the depth of the landmark
+    nor a stereo pair's disparity can absorb it (the landmark stays where it is and every block of it stays an outlier)"""
+    if not gross:
+        return sigma * rng.normal(0, px_noise, 2)
+    a = rng.uniform(0, 2 * np.pi) if k is None else 0.5 * np.pi + rng.uniform(-0.35, 0.35) + np.pi * (k & 1)
+    return sigma * rng.uniform(30, 60) * np.array([np.cos(a), np.sin(a)])
+
+
+def _kf_const(n_kf, const_kfs):
+    c = np.zeros(n_kf, np.uint8); c[list(const_kfs)] = 1
+    return c
+
+
+def make_invdepth_problem(counts, anchors, n_kf, const_kfs=(0,), empty_kf=None, dead=(), seed=1, px_noise=1.0, outlier_frac=0.03,
+                          single_share=0.25, anch_share=0.5, pose_noise=(0.02, np.deg2rad(0.5)), invdepth_noise=0.05):
+    """Anchored inverse-depth problem (make_ba_problem layout): landmark l has exactly counts[l] residual blocks and the anchor
+    keyframe anchors[l]; no block observes from `empty_kf`; every block of the landmarks in `dead` is a gross outlier.
+    Blocks come landmark by landmark -- [RIGHT_ANCH], then per observer in keyframe order [LEFT][RIGHT] -- see shuffle_blocks."""
+    rng = np.random.default_rng(seed)
+    sc = _Scene(n_kf)
+    counts = np.asarray(counts, int); anchors = np.asarray(anchors, np.int32)
+    n_lm = len(counts)
+    kf_const = _kf_const(n_kf, const_kfs)
+    X = np.stack([rng.uniform(-3, 3, n_lm), rng.uniform(-3, 3, n_lm), rng.uniform(-2, 2, n_lm)], 1)
+    auv = np.zeros((n_lm, 2)); lam = np.zeros(n_lm)
+    rt, rk, rl, ruv, rs, rout = [], [], [], [], [], []
+    dead = set(int(d) for d in dead)
+    for l in range(n_lm):
+        a, c = int(anchors[l]), int(counts[l])
+        auv[l], z = sc.project(a, X[l], False)
+        lam[l] = 1.0 / z
+        avail = np.array([k for k in range(n_kf) if k != a and k != empty_kf])
+        ra = int(c > 0 and rng.random() < anch_share)
+        if (c - ra + 1) // 2 > len(avail):
+            ra = 1
+        blocks = [(a, RIGHT_ANCH)] * ra + _observers(c - ra, avail, rng, single_share)
+        assert len(blocks) == c
+        for k, (kf, typ) in enumerate(blocks):
+            sigma = float(rng.choice(SIGMAS))
+            gross = l in dead or (typ != RIGHT_ANCH and rng.random() < outlier_frac)
+            uv, _ = sc.project(kf, X[l], typ != LEFT)
+            rt.append(typ); rk.append(kf); rl.append(l); rs.append(sigma); rout.append(gross)
+            ruv.append(uv + _noise(rng, sigma, gross, px_noise, k if l in dead else None))
+    n_res = len(rt)
+    return dict(n_kf=n_kf, n_lm=n_lm, n_res=n_res, poses=sc.noisy_poses(rng, kf_const, pose_noise), kf_const=kf_const,
+                invdepth=lam * (1 + rng.normal(0, invdepth_noise, n_lm)), lm_anchor_kf=anchors, lm_anchor_uv=auv,
+                res_type=np.array(rt, np.uint8), res_kf=np.array(rk, np.int32), res_lm=np.array(rl, np.int32),
+                res_uv=np.array(ruv, np.float64).reshape(-1, 2), res_sigma=np.array(rs, np.float64),
+                calib_l=CALIB_L.copy(), calib_r=CALIB_R.copy(), T_rl=T_RL.copy(), poses_gt=sc.poses, invdepth_gt=lam,
+                is_outlier=np.array(rout, bool), counts=counts, empty_kf=empty_kf, dead=np.array(sorted(dead), int))
+
+
+def make_xyz_problem(counts, n_kf, const_kfs=(0,), empty_kf=None, dead=(), seed=1, px_noise=1.0, outlier_frac=0.03,
+                     single_share=0.25, pose_noise=(0.02, np.deg2rad(0.5)), xyz_noise=0.1):
+    """3-D points and variable poses (make_xyz_ba_problem layout): point l has exactly counts[l] residual blocks.  The blocks of a
+    dead point come from different keyframes: a stereo pair's opposite vertical errors would send a free 3-D point sideways without
+    end through the roll of T_rl, and a point on its way to infinity is no test of anything."""
+    rng = np.random.default_rng(seed)
+    sc = _Scene(n_kf)
+    counts = np.asarray(counts, int)
+    n_pts = len(counts)
+    kf_const = _kf_const(n_kf, const_kfs)
+    X = np.stack([rng.uniform(-3, 3, n_pts), rng.uniform(-3, 3, n_pts), rng.uniform(-2, 2, n_pts)], 1)
+    avail = np.array([k for k in range(n_kf) if k != empty_kf])
+    rt, rk, rp, ruv, rs, rout = [], [], [], [], [], []
+    dead = set(int(d) for d in dead)
+    for l in range(n_pts):
+        for k, (kf, typ) in enumerate(_observers(int(counts[l]), avail, rng, single_share, l in dead)):
+            sigma = float(rng.choice(SIGMAS))
+            gross = l in dead or rng.random() < outlier_frac
+            uv, _ = sc.project(kf, X[l], typ == RIGHT)
+            rt.append(typ); rk.append(kf); rp.append(l); rs.append(sigma); rout.append(gross)
+            ruv.append(uv + _noise(rng, sigma, gross, px_noise, k if l in dead else None))
+    return dict(n_kf=n_kf, n_pts=n_pts, n_res=len(rt), poses=sc.noisy_poses(rng, kf_const, pose_noise), kf_const=kf_const,
+                xyz=X + rng.normal(0, xyz_noise, X.shape), xyz_gt=X, res_type=np.array(rt, np.uint8), res_kf=np.array(rk, np.int32),
+                res_pt=np.array(rp, np.int32), res_uv=np.array(ruv, np.float64).reshape(-1, 2), res_sigma=np.array(rs, np.float64),
+                calib_l=CALIB_L.copy(), calib_r=CALIB_R.copy(), T_rl=T_RL.copy(), poses_gt=sc.poses,
+                is_outlier=np.array(rout, bool), counts=counts, empty_kf=empty_kf, dead=np.array(sorted(dead), int))
+
+
+def make_structure_problem(counts, n_kf, seed=1, **kw):
+    """Structure-only problem (make_structure_problem layout): make_xyz_problem's blocks on the exact, constant keyframe poses."""
+    pb = make_xyz_problem(counts, n_kf, const_kfs=range(n_kf), seed=seed, **kw)
+    del pb["kf_const"]
+    return pb
+
+
+def shuffle_blocks(pb, seed=1):
+    """The same problem with its residual blocks in a seeded random order: block j of the result is block perm[j] of `pb`
+    (the permutation is returned under "perm")."""
+    perm = np.random.default_rng(seed).permutation(int(pb["n_res"]))
+    out = dict(pb)
+    for k, v in pb.items():
+        if k.startswith("res_") or k == "is_outlier":
+            out[k] = np.ascontiguousarray(np.asarray(v)[perm])
+    out["perm"] = perm
+    return out
+
+
+def unshuffle(values, perm):
+    """per-block values of a shuffled problem -> in the block order of the problem it was shuffled from"""
+    out = np.empty_like(values)
+    out[perm] = values
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the standard irregular cases
+N_KF = 70
+CONST_KFS = (0, 35, 69)                                           # start, middle, end
+ANCHOR_KFS = (0, 9, 22, 35, 48, 61)                               # two of them constant
+EMPTY_KF = 41                                                     # free, and no block observes from it
+
+
+def standard_layout(seed=1):
+    """(counts, anchors, dead) of the standard irregular problem: per anchor keyframe, in landmark order, runs of eight landmarks
+    with the patterns of RUN_PATTERNS, one landmark each of 128 and 129 blocks, landmarks of 1 .. 12 blocks in between and a few
+    `dead` landmarks of 1 or 2 blocks; the landmarks of the anchors are interleaved, so landmark order is not anchor order."""
+    rng = np.random.default_rng(seed)
+    small = lambda: [int(c) for c in rng.integers(1, 13, int(rng.integers(6, 11)))]
+    P = RUN_PATTERNS
+    per_anchor = [
+        P["0/5"] + small() + P["all 64"] + [-1],                          # (constant anchor)     -1 / -2: a dead landmark of 1 / 2 blocks
+        P["all 32"] + small() + [-2] + P["1/31"] + [0, 0],
+        P["32/33"] + small() + [128, 129] + [-1],
+        P["all 33"] + small() + P["1/31"] + [-2],                         # (constant anchor)
+        P["all 65"] + [-2] + small() + P["0/5"] + [63, 32],
+        small() + P["all 32"][:3] + [64, 0, 33, 2, 1] + small(),
+    ]
+    cursor = [0] * len(per_anchor)
+    counts, anchors, dead = [], [], []
+    while True:
+        left = [i for i, seq in enumerate(per_anchor) if cursor[i] < len(seq)]
+        if not left:
+            break
+        i = int(rng.choice(left))
+        c = per_anchor[i][cursor[i]]; cursor[i] += 1
+        if c < 0:
+            dead.append(len(counts)); c = -c
+        counts.append(c); anchors.append(ANCHOR_KFS[i])
+    return np.array(counts), np.array(anchors, np.int32), np.array(dead)
+
+
+def irregular_invdepth(seed=1, shuffle=True):
+    counts, anchors, dead = standard_layout(seed)
+    pb = make_invdepth_problem(counts, anchors, N_KF, CONST_KFS, EMPTY_KF, dead, seed=seed)
+    return shuffle_blocks(pb, seed) if shuffle else pb
+
+
+XYZ_COUNTS = (1, 2, 63, 64, 65, 129)
+
+
+def irregular_xyz_counts(seed=1):
+    """points of 1, 2, 63, 64, 65 and 129 blocks (three of each) among points of 2 .. 12 blocks; two dead points"""
+    rng = np.random.default_rng(seed)
+    counts = np.concatenate([np.repeat(XYZ_COUNTS, 3), rng.integers(2, 13, 60), [0, 2, 2]])
+    order = rng.permutation(len(counts))
+    dead = np.nonzero(order >= len(counts) - 2)[0]
+    return counts[order], dead
+
+
+def irregular_xyz(seed=1, shuffle=True):
+    counts, dead = irregular_xyz_counts(seed)
+    pb = make_xyz_problem(counts, N_KF, CONST_KFS, EMPTY_KF, dead, seed=seed)
+    return shuffle_blocks(pb, seed) if shuffle else pb
+
+
+def irregular_structure(seed=1, shuffle=True):
+    counts, dead = irregular_xyz_counts(seed)
+    pb = make_structure_problem(counts, N_KF, seed=seed, dead=dead)
+    return shuffle_blocks(pb, seed) if shuffle else pb
+
+
+SWEEP_COUNTS = (1, 2, 31, 32, 33, 63, 64, 65, 128, 129)
+
+
+def count_sweep_problem(c, seed=1):
+    """24 landmarks on two anchor keyframes, all with c residual blocks; 10 keyframes plus as many as c observers need.
+    Keyframe 0 is constant; with one or two blocks per landmark the blocks cannot carry nine free keyframes, so the number of free
+    keyframes is limited to a quarter of (residuals - landmarks) / 6: 2 at c = 1, 6 at c = 2, all but keyframe 0 from c = 3 --
+    and to 64, so that the largest counts still run on the solver's small-problem path by default (up to 69 free keyframes)."""
+    n_kf = 10 + c // 2
+    n_free = min(n_kf - 1, 64, (48 * c - 24) // 12)
+    by_priority = [2, 6, 1, 3, 4, 5, 7, 8, 9] + list(range(10, n_kf))       # the two anchors are free first
+    const = [0] + by_priority[n_free:]
+    pb = make_invdepth_problem([c] * 24, [2, 6] * 12, n_kf, const, seed=100 * seed + c)
+    return shuffle_blocks(pb, seed)
+
+
+def random_case(rng):
+    """A random irregular inverse-depth problem (tools/fuzz_parity.py): counts in 0 .. 140, a random constant set, shuffled."""
+    n_kf = 75
+    n_lm = int(rng.integers(40, 160))
+    heavy = rng.random(n_lm) < 0.15
+    counts = np.where(heavy, rng.integers(0, 141, n_lm), rng.integers(0, 34, n_lm))
+    anchor_kfs = rng.choice(n_kf, int(rng.integers(2, 9)), replace=False)
+    anchors = np.sort(rng.choice(anchor_kfs, n_lm)).astype(np.int32)
+    anchors = anchors[np.argsort(rng.integers(0, 4, n_lm), kind="stable")]   # runs of one anchor, interleaved
+    const = set(int(k) for k in rng.choice(n_kf, int(rng.integers(1, 6)), replace=False))
+    free = [k for k in range(n_kf) if k not in const and k not in anchor_kfs]
+    seed = int(rng.integers(1 << 30))
+    pb = make_invdepth_problem(counts, anchors, n_kf, sorted(const), int(rng.choice(free)), seed=seed)
+    return shuffle_blocks(pb, seed)

@@ -397,3 +397,28 @@ def test_device_residuals_match_the_reference_source(ref, gpu_ctx):
         assert bool(g["depthpos"][i]) == dp
         n += 1
     assert n > 2000
+
+
+@pytest.mark.gpu
+def test_device_residuals_match_the_reference_source_on_an_irregular_problem(ref, gpu_ctx):
+    """The same zero-iteration check on the irregular problem of tests/ba_cases.py, EVERY block: per-block sigma, calib_r != calib_l
+    and a rotated T_rl on the device against the reference's Evaluate, no oracle in between -- and, the blocks being shuffled and the
+    device working on its own landmark-sorted copy, the way back to the caller's block indices (res_orig)."""
+    from ov2slam_amd import optimizer
+    from tests import ba_cases
+    pb = ba_cases.irregular_invdepth()
+    o = optimizer.default_options(gpu_ctx.lib)
+    o.max_iter = 0
+    g = optimizer.solve(gpu_ctx, pb, o)
+    poses, auvs, uvs = pb["poses"], pb["lm_anchor_uv"], pb["res_uv"]
+    cl, cr, T = pb["calib_l"], pb["calib_r"], pb["T_rl"]
+    n_right = 0
+    for i in range(int(pb["n_res"])):
+        t, kf, lm = int(pb["res_type"][i]), int(pb["res_kf"][i]), int(pb["res_lm"][i])
+        anchor = poses[int(pb["lm_anchor_kf"][lm])]; lam = np.array([float(pb["invdepth"][lm])])
+        blocks = {0: [cl, anchor, poses[kf], lam], 1: [cl, cr, anchor, poses[kf], T, lam], 2: [cl, cr, T, lam]}[t]
+        _, _, chi2, dp = ref_eval(ref, t, blocks, uvs[i], auvs[lm], float(pb["res_sigma"][i]), want_jac=False)
+        assert abs(g["chi2"][i] - chi2) <= 1e-10 * max(1.0, chi2), (i, t, g["chi2"][i], chi2)
+        assert bool(g["depthpos"][i]) == dp
+        n_right += t != 0
+    assert n_right > 1000 and len(set(pb["res_sigma"])) == 4

@@ -3,13 +3,16 @@
 Every case draws an image size, content, window / cell / tile parameters and point sets (including points on and
 beyond the borders) and demands bit-exact agreement for the integer/float32 front-end paths; every few cases the
 single-sequence tracker (ov2_tracker_*: preprocessImage + kltTracking), the pyramid-resident detectors and random bundle
-adjustments (inverse depth, 3-D points, the large-problem path) are compared as well (BA: the tolerances of tests/test_gpu_ba.py)."""
+adjustments (inverse depth, 3-D points, the large-problem path) are compared as well (BA: the tolerances of tests/test_gpu_ba.py);
+every other inverse-depth problem is an irregular one (tests/ba_cases.py: 0 .. 140 blocks per landmark, random constant keyframes,
+shuffled blocks)."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import ov2slam_amd
 from ov2slam_amd import synth, _lib as L
 from oracle import oracle as O
+from tests import ba_cases
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -225,7 +228,12 @@ for case in range(N):
                 out["dcost"] = max(out["dcost"], abs(r2["final_cost"] - r0["final_cost"]))
             floor_cache[key] = out
             return out
-        pb = synth.make_ba_problem(n_kf, n_lm, min(obs, n_kf), stereo=stereo, seed=bseed)
+        irregular = case % 8 == 4                                           # every other BA case: tests/ba_cases.py's random draw
+        if irregular:
+            pb = ba_cases.random_case(np.random.default_rng(bseed))
+            binfo.update(irregular=True, n_kf=pb["n_kf"], n_lm=pb["n_lm"], n_res=pb["n_res"], max_count=int(pb["counts"].max()))
+        else:
+            pb = synth.make_ba_problem(n_kf, n_lm, min(obs, n_kf), stereo=stereo, seed=bseed)
         r = O.ba_solve(pb, O.ba_default_options(**kw))
         for big in (0, 1):
             ctx.set_option(L.OV2_OPT_BA_FORCE_LARGE, big)
