@@ -27,6 +27,7 @@
 //     k_ba_candidate, k_ba_decide).
 //
 // Parts (one translation unit): ba_core.hpp -- the control block and the trust-region rules, shared with struct_ba.hip;
+// ba_geom.hpp -- constants, the kernels' dynamic-LDS sizes, path choice and launch geometry (plain C++, the one owner of each);
 // ba_chol.hpp -- the Cholesky kernels of the reduced system; ba_problem.hpp -- the device-resident problem (ba_create).
 // This file: the kernels of the LM loop, the host LM driver (ba_lm_loop, ba_run, ba_run_batch), the localBA protocol.
 #include "common.hpp"
@@ -42,8 +43,7 @@
 #pragma clang fp contract(fast)   // BA parity is 1e-4 relative in fp64: FMA contraction is fine here
 #include "ba_core.hpp"           // (after the pragma: the shared functions are compiled with contraction here)
 
-#define BA_TILE 32
-#define BA_MAX_NFP 6144     // 1024 optimised keyframes: H, G, S are dense nfp x nfp doubles (302 MB each at the cap)
+#include "ba_geom.hpp"           // tile / panel constants, the kernels' dynamic-LDS sizes, path choice, launch geometry
 
 #define BA_PART_MAX 2048
 struct BADev {                    // device pointers + sizes (passed by value to kernels)
@@ -63,7 +63,7 @@ struct BADev {                    // device pointers + sizes (passed by value to
     // (buse_inv_depth: 0, optimizer.cpp:207-209 / :333-384).  Per-landmark state arrays (x_lam, c_lam, scale_l, diag_l, etb,
     // yl) hold ldim entries per landmark, W holds ldim rows per landmark; the 3x3 e-block data is in ete6 / minv6.
     int ldim;
-    // big = 1: more optimised keyframes than the LDS-resident path holds (~90).  W = E^T F is then kept SPARSE: one 6-double
+    // big = 1: more optimised keyframes than the LDS-resident path holds (69: ba_small_path).  W = E^T F is then kept SPARSE: one 6-double
     // "slot" per (landmark, optimised keyframe that sees or anchors it) in cww -- the anchor block and the left / right observer
     // blocks of one keyframe share a slot -- instead of a dense n_lm x nfp matrix.  The anchor-observer blocks of H go to HBM with
     // global atomics, the Schur complement is accumulated row block by row block in LDS from per-keyframe slot lists
@@ -71,9 +71,9 @@ struct BADev {                    // device pointers + sizes (passed by value to
     int big, n_cw;
     int chol_hbm;                 // reduced system factored by the multi-kernel Cholesky on HBM (k_chol_*): always with big, and for 3-D point
                                   // problems (dense W, k_ba_schur_gemm) whose reduced system outgrows the one-work-group LDS kernel
-    int lin_waves;                // 3-D point lineariser: wavefronts per work-group (each keeps 3 rows of W in LDS: 4 up to ~200 keyframes, 2, 1 up to ~450)
+    int lin_waves;                // 3-D point lineariser: wavefronts per work-group (each keeps 3 rows of W in LDS: ba_xyz_lin_waves)
     int lin_direct;               // big path with more optimised keyframes than the work-group's LDS can pre-aggregate (n_opt x 27 doubles:
-                                  // ~570): observer diagonal blocks and F^T b go to H / bf with global atomics as well
+                                  // ba_lin_direct): observer diagonal blocks and F^T b go to H / bf with global atomics as well
     double *cww;                  // 6*n_cw   slot values (zeroed by k_ba_zero_lin, filled by the lineariser)          [big]
     int *cw_ptr;                  // n_lm+1   slots of a landmark                                                      [big]
     int *cw_col;                  // n_cw     pose column of the slot
@@ -368,9 +368,7 @@ __device__ __forceinline__ void block_reduce3(double &a, double &b, double &c, d
 // per-wave 35 x 33 LDS transpose -- every lane parks its partials, lane q adds up row q -- instead of 35 six-step
 // shuffle butterflies (420 ds_bpermute per landmark: a third of this kernel by knock-out timing); lane q keeps
 // the running anchor sums q < 27 in ONE register until the anchor changes.
-// dynamic LDS: 8*nfp (two W rows per wavefront) + n_opt*27 + 4*n_opt*21 + 4*LIN_RED doubles
-#define LIN_NRED 35
-#define LIN_RED (LIN_NRED * 33)
+// dynamic LDS: 8*nfp (two W rows per wavefront) + n_opt*27 + 4*n_opt*21 + 4*LIN_RED doubles (lin_lds_bytes, ba_geom.hpp)
 __device__ __forceinline__ void h_add_upper(double *H, int ld, int r, int c, double v)
 {
     if (r <= c) atomicAdd(&H[(long long)r * ld + c], v); else atomicAdd(&H[(long long)c * ld + r], v);
@@ -1168,7 +1166,6 @@ __global__ __launch_bounds__(256) void k_ba_zero_lin(BADev D)
 // longest first).  nsplit > 1 (few keyframes): several work-groups share a row block and flush it with global atomics.
 // First version: one wavefront per landmark, lane per entry, 36 E^2 GLOBAL atomics per landmark -- 44 ms per iteration on the
 // 50 KF x 10 k x 30 stereo problem, 50 ms at 300 KF (profiles/archive/r2_ba_big_*).
-#define SS_WAVES 8
 // Beyond 341 keyframes the row block no longer fits the LDS: blockIdx.y walks over column chunks of `ncol` columns (a multiple of
 // 6: pose blocks never straddle a chunk); a work-group accumulates the part [col0, col0 + ncol) of its row block only, and the
 // chunk that holds no column >= cmin exits at once.
@@ -1824,234 +1821,244 @@ static void ba_fill_result(ov2_ba_result *r, const BACtl &c, float ms)
     r->initial_cost = c.initial_cost; r->final_cost = c.minimum_cost; r->solve_ms = ms;
 }
 
-// keep_state: continue from the parameters and the cached chi2 / depth flags that are on the device (second pass of
-// ov2_local_ba) instead of resetting to the problem's initial values
-static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba_result *r,
-                  const double *chi2_init, const uint8_t *dpos_init, bool keep_state = false)
+// Dynamic-LDS limits are per-function, process-wide attributes: raised once to the hardware maximum (two contexts solving problems
+// of different size on two threads would otherwise race on them).  The list is every kernel that is launched with dynamic LDS;
+// what each asks for is its function in ba_geom.hpp.
+static int ba_raise_lds_limits()
 {
-    OV2_REQUIRE(o && r, OV2_EINVAL, "NULL options/result");
-    const int rc_o = ba_check_options(o);
-    if (rc_o != OV2_OK) return rc_o;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    BADev D = dev->D;
-    D.huber = o->huber_delta;
-    D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
-    hipStream_t s = ctx->stream;
-    const BAOpt O = ba_opt_from(*o);
+    static std::once_flag attr_once;
+    static hipError_t attr_err = hipSuccess;
+    std::call_once(attr_once, [] {
+        const void *const fns[] = {
+            (const void *)k_ba_linearize<false>, (const void *)k_chol_solve, (const void *)k_ba_linearize<true>,        // lin_lds_bytes, chol_solve_lds_bytes, lin_big_lds_bytes
+            (const void *)k_ba_schur_sparse, (const void *)k_ba_linearize_xyz, (const void *)k_ba_cholesky,             // schur_sparse_lds_bytes, lin_xyz_lds_bytes, chol_lds_bytes
+            (const void *)k_ba_linearize_po, (const void *)k_ba_linearize_B, (const void *)k_ba_cholesky_B,             // lin_po_lds_bytes, lin_lds_bytes, chol_lds_bytes
+            (const void *)k_ba_backsub, (const void *)k_ba_backsub_xyz, (const void *)k_ba_backsub_B};                  // backsub_lds_bytes
+        // the attribute bounds static + dynamic LDS together: leave room for each kernel's __shared__ arrays
+        auto raise = [](const void *fn) {
+            hipFuncAttributes fa;
+            hipError_t e = hipFuncGetAttributes(&fa, fn);
+            if (e != hipSuccess) return e;
+            for (int kb = 160; kb >= 64; kb -= 32) {             // 160 KB per work-group on gfx950; smaller steps only if refused
+                e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kb * 1024 - (int)fa.sharedSizeBytes);
+                if (e == hipSuccess) return e;
+                (void)hipGetLastError();
+            }
+            return e;
+        };
+        for (const void *fn : fns) if ((attr_err = raise(fn)) != hipSuccess) return;
+    });
+    OV2_HIP_CHECK(attr_err);
+    return OV2_OK;
+}
 
-    // size limits first: nothing is created or enqueued for a problem this path cannot solve
-    const int n_opt = D.nf / 6;
-    const size_t lin_lds = D.big ? 8 * ((D.lin_direct ? 0 : (size_t)(D.nf / 6) * 27) + 4 * (size_t)LIN_RED) + 64
-                         : D.ldim == 3 ? 8 * (3 * (size_t)D.lin_waves * D.nfp + (size_t)n_opt * 27) + 64
-                                       : 8 * (8 * (size_t)D.nfp + (size_t)n_opt * 27 + 4 * (size_t)n_opt * 21 + 4 * (size_t)LIN_RED) + 64;
-    const size_t chol_lds = D.chol_hbm ? 8 * ((size_t)CH_NB * CH_LDP + (size_t)D.nfp) + 64  // k_chol_solve: scratch block + the solution vector
-                                  : chol_lds_bytes(D.nf, D.nfp);
-    OV2_REQUIRE(lin_lds <= 159 * 1024, OV2_EUNSUPPORTED, "too many optimised keyframes for the LDS-aggregating lineariser");
-    OV2_REQUIRE(chol_lds <= 150 * 1024, OV2_EUNSUPPORTED, "reduced system too large for the LDS-panel Cholesky");
-    {   // dynamic-LDS limits are per-function, process-wide attributes: raise them once to the hardware maximum (two
-        // contexts solving problems of different size on two threads would otherwise race on them)
-        static std::once_flag attr_once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(attr_once, [] {
-            // the attribute bounds static + dynamic LDS together: leave room for each kernel's __shared__ arrays
-            auto raise = [](const void *fn) {
-                hipFuncAttributes fa;
-                hipError_t e = hipFuncGetAttributes(&fa, fn);
-                if (e != hipSuccess) return e;
-                for (int kb = 160; kb >= 64; kb -= 32) {             // 160 KB per work-group on gfx950; smaller steps only if refused
-                    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kb * 1024 - (int)fa.sharedSizeBytes);
-                    if (e == hipSuccess) return e;
-                    (void)hipGetLastError();
-                }
-                return e;
-            };
-            attr_err = raise((const void *)k_ba_linearize<false>);
-            if (attr_err == hipSuccess) attr_err = raise((const void *)k_chol_solve);
-            if (attr_err == hipSuccess) attr_err = raise((const void *)k_ba_linearize<true>);
-            if (attr_err == hipSuccess) attr_err = raise((const void *)k_ba_schur_sparse);
-            if (attr_err == hipSuccess) attr_err = raise((const void *)k_ba_linearize_xyz);
-            if (attr_err == hipSuccess) attr_err = raise((const void *)k_ba_cholesky);
-            if (attr_err == hipSuccess) attr_err = raise((const void *)k_ba_linearize_po);
-        });
-        OV2_HIP_CHECK(attr_err);
+// What the host supplies to a fresh solve, before its clock starts.  one_reset: k_ba_reset copies the initial parameters and clears
+// chi2 / depth flags on the device (b_ba_reset) -- only a caller's own seed of those two goes up; else everything is copied / set here
+static int ba_upload_initial(hipStream_t s, const ov2_ba_dev *dev, bool one_reset, const double *chi2_init, const uint8_t *dpos_init)
+{
+    const BADev &D = dev->D;
+    const size_t nr = (size_t)dev->n_res, nr1 = (size_t)std::max(1, dev->n_res);
+    if (!one_reset) {
+        OV2_HIP_CHECK(hipMemcpyAsync(D.x_pose, dev->h_poses0.data(), 56 * (size_t)D.n_kf, hipMemcpyHostToDevice, s));
+        if (D.n_lm > 0) OV2_HIP_CHECK(hipMemcpyAsync(D.x_lam, dev->h_lam0.data(), 8 * (size_t)D.n_lm * D.ldim, hipMemcpyHostToDevice, s));
     }
-    for (int i = 0; i < 2; i++) if (!ctx->ba_ev[i]) OV2_HIP_CHECK(hipEventCreate(&ctx->ba_ev[i]));      // (the context's: destroyed with it)
-    hipEvent_t e0 = ctx->ba_ev[0], e1 = ctx->ba_ev[1];
-    // state reset: x = initial parameters, everything else zero, scales one
-    const size_t NL = (size_t)D.n_lm * D.ldim;               // per-landmark state entries (1 inverse depth or 3 coordinates each)
-    // small inverse-depth problems: one reset kernel instead of the copies / memsets below (b_ba_reset); pose-only fused solves and the
-    // other forms keep the round-1 sequence
-    const bool fused_po_path = D.n_lm == 0 && D.n_po > 0 && D.nf == 6 && D.ldim == 1 && ctx->ba_pose_only_fused && !(o->max_solver_time_s > 0.0) && !ctx->ba_deterministic;
-    const bool one_reset = D.ldim == 1 && !D.big && D.pose0 != nullptr && !fused_po_path;
-    if (!keep_state && one_reset) {
-        if (chi2_init) OV2_HIP_CHECK(hipMemcpyAsync(D.chi2, chi2_init, 8 * (size_t)dev->n_res, hipMemcpyHostToDevice, s));
-        else if (dpos_init) OV2_HIP_CHECK(hipMemsetAsync(D.chi2, 0xFF, 8 * (size_t)std::max(1, dev->n_res), s));
-        if (dpos_init) OV2_HIP_CHECK(hipMemcpyAsync(D.dpos, dpos_init, (size_t)dev->n_res, hipMemcpyHostToDevice, s));
-        else if (chi2_init) OV2_HIP_CHECK(hipMemsetAsync(D.dpos, 0, (size_t)std::max(1, dev->n_res), s));
-    }
-    if (!keep_state && !one_reset) {
-    OV2_HIP_CHECK(hipMemcpyAsync(D.x_pose, dev->h_poses0.data(), 56 * (size_t)D.n_kf, hipMemcpyHostToDevice, s));
-    if (D.n_lm > 0) OV2_HIP_CHECK(hipMemcpyAsync(D.x_lam, dev->h_lam0.data(), 8 * NL, hipMemcpyHostToDevice, s));
-    if (chi2_init) OV2_HIP_CHECK(hipMemcpyAsync(D.chi2, chi2_init, 8 * (size_t)dev->n_res, hipMemcpyHostToDevice, s));
-    else OV2_HIP_CHECK(hipMemsetAsync(D.chi2, 0xFF, 8 * (size_t)std::max(1, dev->n_res), s));     // NaN pattern
-    if (dpos_init) OV2_HIP_CHECK(hipMemcpyAsync(D.dpos, dpos_init, (size_t)dev->n_res, hipMemcpyHostToDevice, s));
-    else OV2_HIP_CHECK(hipMemsetAsync(D.dpos, 0, (size_t)std::max(1, dev->n_res), s));
-    }
-    OV2_HIP_CHECK(hipEventRecord(e0, s));
-    ctx->ba_trace_n = 0;
-    if (ctx->ba_trace) {
-        if (!ctx->ba_trace_d) OV2_HIP_CHECK(hipMalloc(&ctx->ba_trace_d, sizeof(BAIterRec) * BA_TRACE_CAP));
-        if (!ctx->ba_trace_h) { ctx->ba_trace_h = malloc(sizeof(BAIterRec) * BA_TRACE_CAP); OV2_REQUIRE(ctx->ba_trace_h, OV2_ENOMEM, "trace buffer"); }
-    }
-    BACtl h_ctl;
-    ba_ctl_init(h_ctl, o->initial_radius, ctx->ba_trace ? (BAIterRec *)ctx->ba_trace_d : nullptr);
-    // one optimised pose, pose-only residual blocks, no landmarks (ceresPnP): the whole loop in one kernel (OV2_OPT_BA_POSE_ONLY_FUSED
-    // = 0 keeps the multi-kernel path for A/B runs)
-    const bool fused_po = fused_po_path;
-    if (fused_po) {
-        hipLaunchKernelGGL(k_ba_pose_only, dim3(1), dim3(256), 0, s, D, O, h_ctl);
-        OV2_HIP_CHECK(hipGetLastError());
-    } else {
+    if (chi2_init) OV2_HIP_CHECK(hipMemcpyAsync(D.chi2, chi2_init, 8 * nr, hipMemcpyHostToDevice, s));
+    else if (dpos_init || !one_reset) OV2_HIP_CHECK(hipMemsetAsync(D.chi2, 0xFF, 8 * nr1, s));       // NaN pattern: never evaluated
+    if (dpos_init) OV2_HIP_CHECK(hipMemcpyAsync(D.dpos, dpos_init, nr, hipMemcpyHostToDevice, s));
+    else if (chi2_init || !one_reset) OV2_HIP_CHECK(hipMemsetAsync(D.dpos, 0, nr1, s));
+    return OV2_OK;
+}
+
+// the control block and the zeroed normal equations: one kernel (small inverse-depth problems, see b_ba_reset) or the round-1 sequence
+static int ba_reset_system(hipStream_t s, const BADev &D, const BAGeom &G, const BACtl &h_ctl, bool one_reset, bool keep_state, bool host_chi2)
+{
     if (one_reset) {
-        const int rb = (int)std::min<size_t>(256, ((size_t)std::max(std::max(D.n_res, D.nfp * D.nfp), D.n_lm) + 1023) / 1024);
-        hipLaunchKernelGGL(k_ba_reset, dim3(std::max(1, rb)), dim3(256), 0, s, D, h_ctl, keep_state ? 1 : 0, (chi2_init || dpos_init) ? 1 : 0);
-    } else {
+        hipLaunchKernelGGL(k_ba_reset, dim3(G.reset_blocks), dim3(256), 0, s, D, h_ctl, keep_state ? 1 : 0, host_chi2 ? 1 : 0);
+        return OV2_OK;
+    }
     OV2_HIP_CHECK(hipMemcpyAsync(D.ctl, &h_ctl, sizeof(h_ctl), hipMemcpyHostToDevice, s));
     OV2_HIP_CHECK(hipMemsetAsync(D.H, 0, 8 * (size_t)D.nfp * D.nfp, s));
     OV2_HIP_CHECK(hipMemsetAsync(D.bf, 0, 8 * (size_t)D.nfp, s));
     OV2_HIP_CHECK(hipMemsetAsync(D.yf, 0, 8 * (size_t)D.nfp, s));
-    }
-    // poses -> R | t, scales = 1 (round 1 filled the scales through a host staging vector: three copies and a synchronisation)
-    hipLaunchKernelGGL(k_ba_init, dim3((int)std::min<size_t>(1024, (std::max<size_t>(std::max<size_t>(D.n_kf, D.nfp), NL) + 255) / 256)), dim3(256), 0, s, D);
+    return OV2_OK;
+}
 
-    const int lin_blocks = std::max(1, std::min(256, (D.n_lm + 15) / 16));   // (512: two workgroups per CU -- measured 15 % slower)
-    const int ntiles = D.nfp / BA_TILE, n_upper = ntiles * (ntiles + 1) / 2;
+// OV2_OPT_BA_DETERMINISTIC (BADev::det): one-wavefront lineariser work-groups with their own copies of H / F^T b / cost, one copy
+// of W^T C W / v per landmark split; everything else of the solver is already a fixed-order computation.  The copies live in the
+// CONTEXT (grow-only, like d_scratch): ov2_local_ba / ov2_ba_solve create a transient problem per call.  DG: k_ba_schur_gemm's view.
+static int ba_det_setup(ov2_ctx *ctx, BADev &D, BADev &DG, const BAGeom &G)
+{
+    OV2_REQUIRE(D.ldim == 1 && !D.big, OV2_EUNSUPPORTED, "OV2_OPT_BA_DETERMINISTIC covers the inverse-depth form on the LDS-resident path only");
+    hipStream_t s = ctx->stream;
+    const size_t nn = (size_t)D.nfp * D.nfp, ncopy = (size_t)G.det_lin + G.det_po;
+    const size_t b_H = al256(8 * ncopy * nn), b_bf = al256(8 * ncopy * D.nfp), b_c = al256(8 * std::max<size_t>(1, ncopy));
+    const size_t b_G = al256(8 * (size_t)G.ksplit * nn), b_v = al256(8 * (size_t)G.ksplit * D.nfp);
+    const size_t need = b_H + b_bf + b_c + b_G + b_v;
+    if (need > ctx->ba_det_bytes) {
+        if (ctx->ba_det_pool) { OV2_HIP_CHECK(hipStreamSynchronize(s)); (void)hipFree(ctx->ba_det_pool); ctx->ba_det_pool = nullptr; ctx->ba_det_bytes = 0; }
+        hipError_t e = hipMalloc(&ctx->ba_det_pool, need);
+        if (e != hipSuccess) { ov2_set_error("hipMalloc(%zu) for the deterministic mode: %s", need, hipGetErrorString(e)); return OV2_ENOMEM; }
+        ctx->ba_det_bytes = need;
+    }
+    uint8_t *q = (uint8_t *)ctx->ba_det_pool;
+    D.det = 1; D.det_lin = G.det_lin; D.det_po = G.det_po; D.det_ksplit = G.ksplit;
+    D.Hpart = (double *)q; D.bfpart = (double *)(q + b_H); D.costpart = (double *)(q + b_H + b_bf);
+    D.Gpart = (double *)(q + b_H + b_bf + b_c); D.vpart = (double *)(q + b_H + b_bf + b_c + b_G);
+    OV2_HIP_CHECK(hipMemsetAsync(ctx->ba_det_pool, 0, b_H + b_bf + b_c, s));      // (the copies are clean between linearisations: k_ba_det_reduce clears as it reads)
+    D.lin_blocks = G.det_lin;
+    DG.det = 1; DG.det_ksplit = G.ksplit; DG.Gpart = D.Gpart; DG.vpart = D.vpart;
+    return OV2_OK;
+}
+
+// the multi-kernel solve of one problem: state reset, first linearisation, the LM loop (D by value: the launches' view of the problem)
+static int ba_enqueue_solve(ov2_ctx *ctx, const ov2_ba_dev *dev, BADev D, const BAGeom &G, const ov2_ba_options *o, const BAOpt &O,
+                            const BACtl &h_ctl, bool one_reset, bool keep_state, bool host_chi2)
+{
+    hipStream_t s = ctx->stream;
+    const int n_opt = D.nf / 6;
+    int rc = ba_reset_system(s, D, G, h_ctl, one_reset, keep_state, host_chi2);
+    if (rc != OV2_OK) return rc;
+    // poses -> R | t, scales = 1 (round 1 filled the scales through a host staging vector: three copies and a synchronisation)
+    hipLaunchKernelGGL(k_ba_init, dim3(G.init_blocks), dim3(256), 0, s, D);
+    D.bs_blocks = G.bs_blocks; D.cost_blocks = G.cost_blocks; D.lin_blocks = G.lin_blocks;
     // rows of the W^T C W contraction: landmarks, or the 3 pseudo-rows per point of Wp (ldim 3)
     BADev DG = D;
     if (D.ldim == 3) { DG.W = D.Wp; DG.n_lm = 3 * D.n_lm; DG.cl = D.ones; DG.etb = D.ep; }
-    int ksplit = std::max(1, std::min(64, (1024 + n_upper - 1) / n_upper));
-    int lm_per_split = std::max(BA_TILE, ((DG.n_lm + ksplit - 1) / ksplit + BA_TILE - 1) / BA_TILE * BA_TILE);
-    ksplit = std::max(1, (DG.n_lm + lm_per_split - 1) / lm_per_split);
-    const int ws_blocks = std::max(1, std::min(512, std::max((D.n_lm + 3) / 4, (D.n_po + 255) / 256)));
-    // inverse-depth form: 16 landmarks per work-group pass in the back-substitution, 8 in the cost kernel -- one pass each when the grid allows
-    const int bs_blocks = std::max(1, std::min(2048, (D.n_lm + 15) / 16));
-    const int cost_blocks = std::max(1, std::min(2048, std::max((D.n_lm + 7) / 8, (D.n_po + 255) / 256)));
-    D.bs_blocks = bs_blocks; D.cost_blocks = cost_blocks; D.lin_blocks = lin_blocks;
-    // OV2_OPT_BA_DETERMINISTIC (BADev::det): one-wavefront lineariser work-groups with their own copies of H / F^T b / cost, one copy
-    // of W^T C W / v per landmark split; everything else of the solver is already a fixed-order computation
-    int det_lin = 0, det_po = 0;
     if (ctx->ba_deterministic) {
-        OV2_REQUIRE(D.ldim == 1 && !D.big, OV2_EUNSUPPORTED, "OV2_OPT_BA_DETERMINISTIC covers the inverse-depth form on the LDS-resident path only");
-        det_lin = D.n_lm > 0 ? std::max(1, std::min(128, (D.n_lm + 15) / 16)) : 0;
-        det_po = D.n_po > 0 ? std::max(1, std::min(32, (D.n_po + 63) / 64)) : 0;
-        const size_t nn = (size_t)D.nfp * D.nfp, ncopy = (size_t)det_lin + det_po;
-        const size_t b_H = al256(8 * ncopy * nn), b_bf = al256(8 * ncopy * D.nfp), b_c = al256(8 * std::max<size_t>(1, ncopy));
-        const size_t b_G = al256(8 * (size_t)ksplit * nn), b_v = al256(8 * (size_t)ksplit * D.nfp);
-        const size_t need = b_H + b_bf + b_c + b_G + b_v;
-        // the copies live in the CONTEXT (grow-only, like d_scratch): ov2_local_ba / ov2_ba_solve create a transient problem per call
-        if (need > ctx->ba_det_bytes) {
-            if (ctx->ba_det_pool) { OV2_HIP_CHECK(hipStreamSynchronize(s)); (void)hipFree(ctx->ba_det_pool); ctx->ba_det_pool = nullptr; ctx->ba_det_bytes = 0; }
-            hipError_t e = hipMalloc(&ctx->ba_det_pool, need);
-            if (e != hipSuccess) { ov2_set_error("hipMalloc(%zu) for the deterministic mode: %s", need, hipGetErrorString(e)); return OV2_ENOMEM; }
-            ctx->ba_det_bytes = need;
-        }
-        uint8_t *q = (uint8_t *)ctx->ba_det_pool;
-        D.det = 1; D.det_lin = det_lin; D.det_po = det_po; D.det_ksplit = ksplit;
-        D.Hpart = (double *)q; D.bfpart = (double *)(q + b_H); D.costpart = (double *)(q + b_H + b_bf);
-        D.Gpart = (double *)(q + b_H + b_bf + b_c); D.vpart = (double *)(q + b_H + b_bf + b_c + b_G);
-        OV2_HIP_CHECK(hipMemsetAsync(ctx->ba_det_pool, 0, b_H + b_bf + b_c, s));      // (the copies are clean between linearisations: k_ba_det_reduce clears as it reads)
-        D.lin_blocks = det_lin;
-        DG.det = 1; DG.det_ksplit = ksplit; DG.Gpart = D.Gpart; DG.vpart = D.vpart;
+        rc = ba_det_setup(ctx, D, DG, G);
+        if (rc != OV2_OK) return rc;
     }
-    const int po_blocks = std::max(1, std::min(256, (D.n_po + 255) / 256));
-    // k_ba_schur_sparse: ~512 work-groups; row block + per-wavefront staging (64 slot blocks + columns)
-    const int ss_split = std::max(1, (512 + std::max(1, n_opt) - 1) / std::max(1, n_opt));
-    // column chunk of the row block kept in LDS: all of it up to 2040 columns (340 pose blocks), else that many per chunk
-    int ss_ncol = D.nfp <= 2048 ? D.nfp : 2040;
-    if (ctx->ba_schur_chunk >= 6) ss_ncol = std::min(ss_ncol, ctx->ba_schur_chunk / 6 * 6);                                     // OV2_OPT_BA_SCHUR_CHUNK (tests)
-    const int ss_chunks = (D.nfp + ss_ncol - 1) / ss_ncol;
-    const size_t ss_lds = 8 * (6 * (size_t)ss_ncol + (size_t)SS_WAVES * 64 * 6) + 4 * (size_t)SS_WAVES * 64 + 64;
 
     auto linearize = [&]() {
-        if (D.n_lm > 0 && D.ldim == 3) hipLaunchKernelGGL(k_ba_linearize_xyz, dim3(lin_blocks * (4 / D.lin_waves)), dim3(64 * D.lin_waves), lin_lds, s, D);
+        if (D.n_lm > 0 && D.ldim == 3) hipLaunchKernelGGL(k_ba_linearize_xyz, dim3(G.lin_blocks * (4 / D.lin_waves)), dim3(64 * D.lin_waves), G.lin_lds, s, D);
         else if (D.big) {
             // (k_ba_decide leaves H, F^T b and the W slots to this kernel on the large path: also for pose-only problems)
             if (D.n_lm > 0 || D.n_po > 0) hipLaunchKernelGGL(k_ba_zero_lin, dim3(1024), dim3(256), 0, s, D);
-            if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_linearize<true>, dim3(lin_blocks), dim3(256), lin_lds, s, D, dev->lm_order);
+            if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_linearize<true>, dim3(G.lin_blocks), dim3(256), G.lin_lds, s, D, dev->lm_order);
         }
         else if (D.det) {
             // one wavefront per work-group, each with its own copy of H / F^T b; then the copies in order
-            if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_linearize<false>, dim3(det_lin), dim3(64), lin_lds, s, D, dev->lm_order);
-            if (D.n_po > 0) hipLaunchKernelGGL(k_ba_linearize_po, dim3(det_po), dim3(64), (size_t)n_opt * 27 * 8 + 16, s, D);
+            if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_linearize<false>, dim3(G.det_lin), dim3(64), G.lin_lds, s, D, dev->lm_order);
+            if (D.n_po > 0) hipLaunchKernelGGL(k_ba_linearize_po, dim3(G.det_po), dim3(64), G.po_lds, s, D);
             hipLaunchKernelGGL(k_ba_det_reduce, dim3(256), dim3(256), 0, s, D);
             return;
         }
-        else if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_linearize<false>, dim3(lin_blocks), dim3(256), lin_lds, s, D, dev->lm_order);
-        if (D.n_po > 0) hipLaunchKernelGGL(k_ba_linearize_po, dim3(po_blocks), dim3(256), (D.big && D.lin_direct ? 0 : (size_t)n_opt * 27 * 8) + 16, s, D);
+        else if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_linearize<false>, dim3(G.lin_blocks), dim3(256), G.lin_lds, s, D, dev->lm_order);
+        if (D.n_po > 0) hipLaunchKernelGGL(k_ba_linearize_po, dim3(G.po_blocks), dim3(256), G.po_lds, s, D);
     };
     linearize();
     if (!one_reset) OV2_HIP_CHECK(hipMemsetAsync(D.G, 0, 8 * (size_t)D.nfp * D.nfp, s));    // (every later iteration: cleared by the back-substitution kernel)
-    int rc_h = ctx->reserve_host(64);
-    if (rc_h != OV2_OK) return rc_h;
+    rc = ctx->reserve_host(64);
+    if (rc != OV2_OK) return rc;
     volatile int *flag_h = (volatile int *)ctx->h_scratch;
     flag_h[0] = -1;
     D.flag_h = (int *)ctx->h_scratch;
     DG.flag_h = D.flag_h;
     auto first_half = [&](int it) {
         hipLaunchKernelGGL(k_ba_iter_begin, dim3(1), dim3(1024), 0, s, D, O, it);
-        if (D.ldim == 3 && D.n_lm > 0) hipLaunchKernelGGL(k_ba_xyz_prep, dim3(ws_blocks), dim3(256), 0, s, D);
-        if (D.n_lm > 0 && D.big) hipLaunchKernelGGL(k_ba_schur_sparse, dim3(n_opt * ss_split, ss_chunks), dim3(64 * SS_WAVES), ss_lds, s, D, ss_split, ss_ncol);
-        else if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_schur_gemm, dim3(n_upper, ksplit), dim3(256), 0, s, DG, ntiles, lm_per_split);
+        if (D.ldim == 3 && D.n_lm > 0) hipLaunchKernelGGL(k_ba_xyz_prep, dim3(G.ws_blocks), dim3(256), 0, s, D);
+        if (D.n_lm > 0 && D.big) hipLaunchKernelGGL(k_ba_schur_sparse, dim3(n_opt * G.ss_split, G.ss_chunks), dim3(64 * SS_WAVES), G.ss_lds, s, D, G.ss_split, G.ss_ncol);
+        else if (D.n_lm > 0) hipLaunchKernelGGL(k_ba_schur_gemm, dim3(G.n_upper, G.ksplit), dim3(256), 0, s, DG, G.ntiles, G.lm_per_split);
         if (D.nf > 0) hipLaunchKernelGGL(k_ba_assemble, dim3((D.nf + 255) / 256, D.nf), dim3(256), 0, s, D);   // (structure-only problems: no reduced system)
-        if (D.chol_hbm) {
-            for (int k0 = 0; k0 < D.nf; k0 += CH_NB) {
-                const int m = D.nf - k0 - std::min(CH_NB, D.nf - k0);
-                hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(64), 0, s, D, k0);
-                if (m > 0) {
-                    const int mb = (m + 31) / 32;
-                    hipLaunchKernelGGL(k_chol_panel, dim3((m + 63) / 64), dim3(64), 0, s, D, k0);
-                    hipLaunchKernelGGL(k_chol_trail, dim3(mb * (mb + 1) / 2), dim3(256), 0, s, D, k0);
-                }
+        if (!D.chol_hbm) { hipLaunchKernelGGL(k_ba_cholesky, dim3(1), dim3(512), G.chol_lds, s, D); return; }
+        for (int k0 = 0; k0 < D.nf; k0 += CH_NB) {
+            const int m = D.nf - k0 - std::min(CH_NB, D.nf - k0);
+            hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(64), 0, s, D, k0);
+            if (m > 0) {
+                const int mb = (m + 31) / 32;
+                hipLaunchKernelGGL(k_chol_panel, dim3((m + 63) / 64), dim3(64), 0, s, D, k0);
+                hipLaunchKernelGGL(k_chol_trail, dim3(mb * (mb + 1) / 2), dim3(256), 0, s, D, k0);
             }
-            hipLaunchKernelGGL(k_chol_solve, dim3(1), dim3(512), chol_lds, s, D);
-        } else
-        hipLaunchKernelGGL(k_ba_cholesky, dim3(1), dim3(512), chol_lds, s, D);
+        }
+        hipLaunchKernelGGL(k_chol_solve, dim3(1), dim3(512), G.chol_lds, s, D);
     };
     auto second_half = [&](int it) {
-        if (D.ldim == 3) hipLaunchKernelGGL(k_ba_backsub_xyz, dim3(ws_blocks), dim3(256), (size_t)D.nfp * 8, s, D);
-        else hipLaunchKernelGGL(k_ba_backsub, dim3(bs_blocks), dim3(256), (size_t)D.nfp * 8, s, D);
+        if (D.ldim == 3) hipLaunchKernelGGL(k_ba_backsub_xyz, dim3(G.ws_blocks), dim3(256), G.bs_lds, s, D);
+        else hipLaunchKernelGGL(k_ba_backsub, dim3(G.bs_blocks), dim3(256), G.bs_lds, s, D);
         hipLaunchKernelGGL(k_ba_candidate, dim3(1), dim3(1024), 0, s, D, O);
-        if (D.ldim == 3) hipLaunchKernelGGL(k_ba_cost_xyz, dim3(ws_blocks), dim3(256), 0, s, D);
-        else hipLaunchKernelGGL(k_ba_cost, dim3(cost_blocks), dim3(256), 0, s, D);
+        if (D.ldim == 3) hipLaunchKernelGGL(k_ba_cost_xyz, dim3(G.ws_blocks), dim3(256), 0, s, D);
+        else hipLaunchKernelGGL(k_ba_cost, dim3(G.cost_blocks), dim3(256), 0, s, D);
         hipLaunchKernelGGL(k_ba_decide, dim3(1), dim3(1024), 0, s, D, O, it);
         linearize();
     };
-    const int rc_l = ba_lm_loop(s, o, O, flag_h, 1, first_half, second_half,
-                                [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin, dim3(1), dim3(1024), 0, s, D, Ob, -1); });
-    if (rc_l != OV2_OK) return rc_l;
+    return ba_lm_loop(s, o, O, flag_h, 1, first_half, second_half,
+                      [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin, dim3(1), dim3(1024), 0, s, D, Ob, -1); });
+}
+
+// the result copies of a solve, asynchronous on s (a NULL destination is skipped)
+static int ba_download(hipStream_t s, const ov2_ba_dev *dev, double *poses, double *lam, uint8_t *bad_obs, double *chi2, uint8_t *dpos)
+{
+    const BADev &D = dev->D;
+    const size_t nr = (size_t)dev->n_res;
+    if (poses) OV2_HIP_CHECK(hipMemcpyAsync(poses, D.x_pose, 56 * (size_t)D.n_kf, hipMemcpyDeviceToHost, s));
+    if (lam && D.n_lm > 0) OV2_HIP_CHECK(hipMemcpyAsync(lam, D.x_lam, 8 * (size_t)D.n_lm * D.ldim, hipMemcpyDeviceToHost, s));
+    if (bad_obs && nr > 0) OV2_HIP_CHECK(hipMemcpyAsync(bad_obs, D.bad_obs, nr, hipMemcpyDeviceToHost, s));
+    if (chi2 && nr > 0) OV2_HIP_CHECK(hipMemcpyAsync(chi2, D.chi2, 8 * nr, hipMemcpyDeviceToHost, s));
+    if (dpos && nr > 0) OV2_HIP_CHECK(hipMemcpyAsync(dpos, D.dpos, nr, hipMemcpyDeviceToHost, s));
+    return OV2_OK;
+}
+
+// keep_state: continue from the parameters and the cached chi2 / depth flags that are on the device (second pass of
+// ov2_local_ba) instead of resetting to the problem's initial values
+static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba_result *r,
+                  const double *chi2_init, const uint8_t *dpos_init, bool keep_state = false)
+{
+    OV2_REQUIRE(o && r, OV2_EINVAL, "NULL options/result");
+    int rc = ba_check_options(o);
+    if (rc != OV2_OK) return rc;
+    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    BADev D = dev->D;
+    D.huber = o->huber_delta;
+    D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
+    hipStream_t s = ctx->stream;
+    const BAOpt O = ba_opt_from(*o);
+    // a problem alone spreads over the whole chip: up to 256 lineariser work-groups, ~1024 for the Schur complement
+    const BAGeom G = ba_geom(D, 256, 1024, ctx->ba_schur_chunk);
+    // size limits first: nothing is created or enqueued for a problem this path cannot solve
+    OV2_REQUIRE(G.lin_lds <= BA_LIN_LDS_MAX, OV2_EUNSUPPORTED, "too many optimised keyframes for the LDS-aggregating lineariser");
+    OV2_REQUIRE(G.chol_lds <= BA_CHOL_LDS_MAX, OV2_EUNSUPPORTED, "reduced system too large for the LDS-panel Cholesky");
+    rc = ba_raise_lds_limits();
+    if (rc == OV2_OK) rc = ba_events(ctx);
+    if (rc != OV2_OK) return rc;
+    // one optimised pose, pose-only residual blocks, no landmarks (ceresPnP): the whole loop in one kernel (OV2_OPT_BA_POSE_ONLY_FUSED
+    // = 0 keeps the multi-kernel path for A/B runs)
+    const bool fused_po = D.n_lm == 0 && D.n_po > 0 && D.nf == 6 && D.ldim == 1 && ctx->ba_pose_only_fused && !(o->max_solver_time_s > 0.0) && !ctx->ba_deterministic;
+    // small inverse-depth problems: one reset kernel instead of copies and memsets; pose-only fused solves and the other forms keep the round-1 sequence
+    const bool one_reset = D.ldim == 1 && !D.big && D.pose0 != nullptr && !fused_po;
+    if (!keep_state) {
+        rc = ba_upload_initial(s, dev, one_reset, chi2_init, dpos_init);
+        if (rc != OV2_OK) return rc;
     }
-    OV2_HIP_CHECK(hipEventRecord(e1, s));
-    // results
+    OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[0], s));
+    BAIterRec *trace = nullptr;
+    rc = ba_trace_begin(ctx, ctx->ba_trace != 0, &trace);
+    if (rc != OV2_OK) return rc;
+    BACtl h_ctl;
+    ba_ctl_init(h_ctl, o->initial_radius, trace);
+    if (fused_po) {
+        hipLaunchKernelGGL(k_ba_pose_only, dim3(1), dim3(256), 0, s, D, O, h_ctl);
+        OV2_HIP_CHECK(hipGetLastError());
+    } else {
+        rc = ba_enqueue_solve(ctx, dev, D, G, o, O, h_ctl, one_reset, keep_state, chi2_init || dpos_init);
+        if (rc != OV2_OK) return rc;
+    }
+    OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[1], s));
     OV2_HIP_CHECK(hipMemcpyAsync(&h_ctl, D.ctl, sizeof(h_ctl), hipMemcpyDeviceToHost, s));
-    if (r->poses_out) OV2_HIP_CHECK(hipMemcpyAsync(r->poses_out, D.x_pose, 56 * (size_t)D.n_kf, hipMemcpyDeviceToHost, s));
-    if (r->invdepth_out && D.n_lm > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->invdepth_out, D.x_lam, 8 * NL, hipMemcpyDeviceToHost, s));
-    if (r->chi2_last_eval && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->chi2_last_eval, D.chi2, 8 * (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
-    if (r->depthpos_last_eval && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->depthpos_last_eval, D.dpos, (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
+    rc = ba_download(s, dev, r->poses_out, r->invdepth_out, nullptr, r->chi2_last_eval, r->depthpos_last_eval);
+    if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipStreamSynchronize(s));
     if (h_ctl.trace) {
-        ctx->ba_trace_n = h_ctl.n_trace;
-        const int nrec = std::min(h_ctl.n_trace, BA_TRACE_CAP);
-        if (nrec > 0) OV2_HIP_CHECK(hipMemcpy(ctx->ba_trace_h, ctx->ba_trace_d, sizeof(BAIterRec) * (size_t)nrec, hipMemcpyDeviceToHost));
+        rc = ba_trace_fetch(ctx, h_ctl.n_trace);
+        if (rc != OV2_OK) return rc;
     }
     float ms = 0;
-    OV2_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    OV2_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ba_ev[0], ctx->ba_ev[1]));
     ba_fill_result(r, h_ctl, ms);
     if (ctx->debug)
         fprintf(stderr, "[ov2 ba] cholesky ticks (100MHz): copy-in %llu pivot+panel %llu write-back %llu trailing %llu block inverses %llu solves %llu\n",
                 h_ctl.dbg[0], h_ctl.dbg[1], h_ctl.dbg[2], h_ctl.dbg[3], h_ctl.dbg[4], h_ctl.dbg[5]);
     return OV2_OK;
 }
-
 
 // ================================================================================== lock-step batch of local-BA problems
 // BASELINE configs[4]: eleven sequences advance in lock step on one GPU (ov2_btracker_*), their keyframes arrive together -- and
@@ -2080,13 +2087,6 @@ __global__ __launch_bounds__(256) void k_ba_gather_B(const BADev *__restrict__ a
     if (D.out_flags & 2) for (long long e = i0; e < D.n_res; e += stride) o[e] = D.dpos[e];
 }
 
-static bool ba_small_path(int n_opt)
-{
-    const int nf = 6 * n_opt, nfp = std::max(BA_TILE, (nf + BA_TILE - 1) / BA_TILE * BA_TILE);
-    const size_t lin_lds = 8 * (8 * (size_t)nfp + (size_t)n_opt * 27 + 4 * (size_t)n_opt * 21 + 4 * (size_t)LIN_RED) + 64;
-    return !(lin_lds > 159 * 1024 || chol_lds_bytes(nf, nfp) > 150 * 1024 || nf > CH_MAX_LDS_N);
-}
-
 struct BABatch {
     std::vector<ov2_ba_dev *> devs;
     BADev *h_arr = nullptr, *d_arr = nullptr;           // the problems' device views: pinned staging / device copy
@@ -2100,42 +2100,32 @@ struct BABatch {
 // one LM solve of every problem of the batch (ba_run's loop on batched launches); skip[i]: the problem sits this pass out
 static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const double *huber, const uint8_t *skip, bool keep_state, float *ms_out)
 {
-    const int rc_o = ba_check_options(o);
-    if (rc_o != OV2_OK) return rc_o;
+    int rc = ba_check_options(o);
+    if (rc != OV2_OK) return rc;
     const int N = (int)B.devs.size();
     hipStream_t s = ctx->stream;
     const BAOpt O = ba_opt_from(*o);
-    int lin_blocks = 1, bs_blocks = 1, cost_blocks = 1, nupper = 1, ksplit_max = 1, nf_max = 0, nfp_max = 0, reset_blocks = 1, init_blocks = 1;
-    size_t lin_lds = 0, chol_lds = 0;
     // a single problem spreads over the whole chip for latency (16 landmarks per lineariser work-group, 1024 Schur work-groups); a batch
     // fills it anyway: ~768 lineariser and ~2048 Schur work-groups over ALL problems -- fewer flushes of the LDS aggregates and fewer
     // atomic adds into G per problem (eleven windows: 2.31 -> 2.07 ms of device time; tools/r5_ba_batch_grid.sh swept 512 .. 4096 / 1024 .. 16384)
     const int lin_total = 768, schur_total = 2048;
     const int lin_cap = std::max(16, std::min(256, (lin_total + N - 1) / N));
     const int schur_wgs = std::max(64, std::min(1024, (schur_total + N - 1) / N));
-    for (int i = 0; i < N; i++) {
-        const BADev &D = B.devs[(size_t)i]->D;
-        const int n_opt = D.nf / 6;
-        lin_lds = std::max(lin_lds, 8 * (8 * (size_t)D.nfp + (size_t)n_opt * 27 + 4 * (size_t)n_opt * 21 + 4 * (size_t)LIN_RED) + 64);
-        chol_lds = std::max(chol_lds, chol_lds_bytes(D.nf, D.nfp));
-        lin_blocks = std::max(lin_blocks, std::min(lin_cap, (D.n_lm + 15) / 16));
-        bs_blocks = std::max(bs_blocks, std::min(2048, (D.n_lm + 15) / 16));
-        cost_blocks = std::max(cost_blocks, std::min(2048, (D.n_lm + 7) / 8));
-        nf_max = std::max(nf_max, D.nf); nfp_max = std::max(nfp_max, D.nfp);
-        reset_blocks = std::max(reset_blocks, (int)std::min<size_t>(256, ((size_t)std::max(D.n_res, D.nfp * D.nfp) + 1023) / 1024));
-        init_blocks = std::max(init_blocks, (int)std::min<size_t>(1024, ((size_t)std::max(std::max(D.n_kf, D.nfp), D.n_lm) + 255) / 256));
-    }
-    OV2_REQUIRE(lin_lds <= 159 * 1024 && chol_lds <= 150 * 1024, OV2_EUNSUPPORTED, "a problem of the batch is too large for the LDS-resident path");
+    // grids and LDS bytes: the largest any problem needs; the Schur split is each problem's own (into its view)
+    std::vector<BAGeom> each((size_t)N);
+    for (int i = 0; i < N; i++) each[(size_t)i] = ba_geom(B.devs[(size_t)i]->D, lin_cap, schur_wgs);
+    BAGeom G = each[0];
+    for (int i = 1; i < N; i++) ba_geom_max(G, each[(size_t)i]);
+    OV2_REQUIRE(G.lin_lds <= BA_LIN_LDS_MAX && G.chol_lds <= BA_CHOL_LDS_MAX, OV2_EUNSUPPORTED, "a problem of the batch is too large for the LDS-resident path");
+    rc = ba_raise_lds_limits();
+    if (rc == OV2_OK) rc = ba_events(ctx);
+    if (rc != OV2_OK) return rc;
     for (int i = 0; i < N; i++) {
         BADev D = B.devs[(size_t)i]->D;
+        const BAGeom &g = each[(size_t)i];
         D.huber = huber[i]; D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
-        D.bs_blocks = bs_blocks; D.cost_blocks = cost_blocks; D.lin_blocks = lin_blocks;
-        const int ntiles = D.nfp / BA_TILE, n_upper = ntiles * (ntiles + 1) / 2;
-        int ksplit = std::max(1, std::min(64, (schur_wgs + n_upper - 1) / n_upper));
-        const int lmps = std::max(BA_TILE, ((D.n_lm + ksplit - 1) / ksplit + BA_TILE - 1) / BA_TILE * BA_TILE);
-        ksplit = std::max(1, (D.n_lm + lmps - 1) / lmps);
-        D.g_ntiles = ntiles; D.g_nupper = n_upper; D.g_lmps = lmps; D.g_ksplit = ksplit;
-        nupper = std::max(nupper, n_upper); ksplit_max = std::max(ksplit_max, ksplit);
+        D.bs_blocks = G.bs_blocks; D.cost_blocks = G.cost_blocks; D.lin_blocks = G.lin_blocks;
+        D.g_ntiles = g.ntiles; D.g_nupper = g.n_upper; D.g_lmps = g.lm_per_split; D.g_ksplit = g.ksplit;
         D.skip2 = skip && skip[i] ? 1 : 0;
         D.flag_h = (int *)(B.h_flag + i);
         D.ctl = B.d_ctl + i; D.lba_cnt = B.d_cnt + 16 * i;
@@ -2143,9 +2133,7 @@ static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const
         B.h_flag[i] = -1;
     }
     OV2_HIP_CHECK(hipMemcpyAsync(B.d_arr, B.h_arr, sizeof(BADev) * (size_t)N, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < 2; i++) if (!ctx->ba_ev[i]) OV2_HIP_CHECK(hipEventCreate(&ctx->ba_ev[i]));
-    struct { hipEvent_t e0, e1; } ev{ctx->ba_ev[0], ctx->ba_ev[1]};
-    OV2_HIP_CHECK(hipEventRecord(ev.e0, s));
+    OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[0], s));
     BACtl c0;
     ba_ctl_init(c0, o->initial_radius, nullptr);
     const BADev *A = B.d_arr;
@@ -2155,30 +2143,30 @@ static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const
         for (int i = 0; i < N; i++) ll = std::max(ll, std::min(512, (B.devs[(size_t)i]->D.n_lm + 3) / 4));
         hipLaunchKernelGGL(k_ba_lm_live_B, dim3(ll, 1, Z), dim3(256), 0, s, A);
     }
-    hipLaunchKernelGGL(k_ba_reset_B, dim3(reset_blocks, 1, Z), dim3(256), 0, s, A, c0, keep_state ? 1 : 0);
-    hipLaunchKernelGGL(k_ba_init_B, dim3(init_blocks, 1, Z), dim3(256), 0, s, A);
-    auto linearize = [&]() { hipLaunchKernelGGL(k_ba_linearize_B, dim3(lin_blocks, 1, Z), dim3(256), lin_lds, s, A); };
+    hipLaunchKernelGGL(k_ba_reset_B, dim3(G.reset_blocks_B, 1, Z), dim3(256), 0, s, A, c0, keep_state ? 1 : 0);
+    hipLaunchKernelGGL(k_ba_init_B, dim3(G.init_blocks, 1, Z), dim3(256), 0, s, A);
+    auto linearize = [&]() { hipLaunchKernelGGL(k_ba_linearize_B, dim3(G.lin_blocks, 1, Z), dim3(256), G.lin_lds, s, A); };
     auto first_half = [&](int it) {
         hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O, it);
-        hipLaunchKernelGGL(k_ba_schur_gemm_B, dim3(nupper, ksplit_max, Z), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(k_ba_assemble_B, dim3((nf_max + 255) / 256, nf_max, Z), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(k_ba_cholesky_B, dim3(1, 1, Z), dim3(512), chol_lds, s, A);
+        hipLaunchKernelGGL(k_ba_schur_gemm_B, dim3(G.n_upper, G.ksplit, Z), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(k_ba_assemble_B, dim3((G.nf + 255) / 256, G.nf, Z), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(k_ba_cholesky_B, dim3(1, 1, Z), dim3(512), G.chol_lds, s, A);
     };
     auto second_half = [&](int it) {
-        hipLaunchKernelGGL(k_ba_backsub_B, dim3(bs_blocks, 1, Z), dim3(256), (size_t)nfp_max * 8, s, A);
+        hipLaunchKernelGGL(k_ba_backsub_B, dim3(G.bs_blocks, 1, Z), dim3(256), G.bs_lds, s, A);
         hipLaunchKernelGGL(k_ba_candidate_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O);
-        hipLaunchKernelGGL(k_ba_cost_B, dim3(cost_blocks, 1, Z), dim3(256), 0, s, A);
+        hipLaunchKernelGGL(k_ba_cost_B, dim3(G.cost_blocks, 1, Z), dim3(256), 0, s, A);
         hipLaunchKernelGGL(k_ba_decide_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O, it);
         linearize();
     };
     linearize();
-    const int rc_l = ba_lm_loop(s, o, O, B.h_flag, N, first_half, second_half,
-                                [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, Ob, -1); });
-    if (rc_l != OV2_OK) return rc_l;
-    OV2_HIP_CHECK(hipEventRecord(ev.e1, s));
+    rc = ba_lm_loop(s, o, O, B.h_flag, N, first_half, second_half,
+                    [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, Ob, -1); });
+    if (rc != OV2_OK) return rc;
+    OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[1], s));
     OV2_HIP_CHECK(hipMemcpyAsync(B.h_ctl, B.d_ctl, sizeof(BACtl) * (size_t)N, hipMemcpyDeviceToHost, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));
-    OV2_HIP_CHECK(hipEventElapsedTime(ms_out, ev.e0, ev.e1));
+    OV2_HIP_CHECK(hipEventElapsedTime(ms_out, ctx->ba_ev[0], ctx->ba_ev[1]));
     return OV2_OK;
 }
 
@@ -2531,11 +2519,8 @@ static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_b
         OV2_HIP_CHECK(hipMemcpyAsync(cnt_h, D.lba_cnt, 16, hipMemcpyDeviceToHost, s));
     }
 download:
-    if (r->poses_out) OV2_HIP_CHECK(hipMemcpyAsync(r->poses_out, D.x_pose, 56 * (size_t)D.n_kf, hipMemcpyDeviceToHost, s));
-    if (r->invdepth_out && D.n_lm > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->invdepth_out, D.x_lam, 8 * (size_t)D.n_lm, hipMemcpyDeviceToHost, s));
-    if (r->bad_obs && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->bad_obs, D.bad_obs, (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
-    if (r->chi2_last_eval && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->chi2_last_eval, D.chi2, 8 * (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
-    if (r->depthpos_last_eval && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->depthpos_last_eval, D.dpos, (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
+    rc = ba_download(s, dev, r->poses_out, r->invdepth_out, r->bad_obs, r->chi2_last_eval, r->depthpos_last_eval);
+    if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipStreamSynchronize(s));
     if (r->l2_done) r->n_bad_total = nbbad + cnt_h[0];
     lap("outlier test 2 + download");

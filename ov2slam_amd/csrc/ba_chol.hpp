@@ -8,15 +8,10 @@
 // Right-looking, 32-wide panels: the diagonal block is factored in LDS by one wavefront, the panel
 // below it is solved row-per-thread against that block and parked in LDS, and the trailing update
 // reads the panel from LDS only (each S entry is touched once per panel).
-#define CH_NB 32
+// (CH_NB, CH_LDP, CH_MAX_LDS_N and the kernels' dynamic-LDS sizes, chol_lds_bytes / chol_solve_lds_bytes: ba_geom.hpp)
 #define CH_GRP 8           // columns of the diagonal block published per work-group barrier (pipelined panel solve): 2 / 4 / 8 -> 102 / 89 / 87 us
-#define CH_LDP 33          // padded leading dimension (doubles) of the LDS panel rows
 // knock-out timings of k_ba_cholesky's phases (no MFMA, no loads of the old tile values, no tile stores, no LDS operand reads, a
 // quarter of the panel solve's terms): profiles/archive/r4_ba_dead_ends.txt
-#define CH_MAX_LDS_N 415   // k_ba_cholesky (512 threads, six panel wavefronts): the right-hand side rides as a panel row, n - 32 + 1 <= 384; larger: HBM path
-// dynamic LDS of k_ba_cholesky: diagonal block, solution vector, panel (rows rounded up to whole 16-row MFMA tiles: the trailing
-// update reads its operand rows unpredicated)
-static inline size_t chol_lds_bytes(int nf, int nfp) { return 8 * ((size_t)CH_NB * CH_LDP + 2 * (size_t)nfp + (size_t)((std::max(0, nf - CH_NB) + 15) & ~15) * CH_LDP) + 64; }
 
 // The two triangular solves L y = rhs, L^T x = y on the factor in S (HBM) with the inverse diagonal blocks in Linv; yv (LDS, nfp
 // doubles) holds rhs on entry and x on return, L11 is a CH_NB x CH_LDP LDS scratch.  One work-group.

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include <math.h>
 #include <float.h>
+#include <stdlib.h>
 
 #define BA_TRACE_CAP 64
 typedef ov2_ba_iter BAIterRec;   // the iteration summary Ceres pushes into Solver::Summary::iterations (OV2_OPT_BA_TRACE)
@@ -58,6 +59,35 @@ __host__ __device__ inline void ba_ctl_init(BACtl &c, double initial_radius, BAI
     c.termination = OV2_TERM_NO_CONVERGENCE;
     c.cur.gradient_norm = NAN;                              // (the device forms the max norm only)
     c.trace = trace;
+}
+
+// ---------------------------------------------------------------------------------- host scaffolding of a solve
+// the context's two timing events (ov2_ctx::ba_ev), created with the first solve and destroyed with the context: a pair per
+// pass was 25 us
+static inline int ba_events(ov2_ctx *ctx)
+{
+    for (int i = 0; i < 2; i++) if (!ctx->ba_ev[i]) OV2_HIP_CHECK(hipEventCreate(&ctx->ba_ev[i]));
+    return OV2_OK;
+}
+
+// OV2_OPT_BA_TRACE.  Begin: no record yet; on: the buffers exist (allocated with the first traced solve) and *trace is the
+// device one for the control block, else NULL.  Fetch (after the solve's synchronisation): the n_trace records the device wrote.
+static inline int ba_trace_begin(ov2_ctx *ctx, bool on, BAIterRec **trace)
+{
+    ctx->ba_trace_n = 0;
+    *trace = nullptr;
+    if (!on) return OV2_OK;
+    if (!ctx->ba_trace_d) OV2_HIP_CHECK(hipMalloc(&ctx->ba_trace_d, sizeof(BAIterRec) * BA_TRACE_CAP));
+    if (!ctx->ba_trace_h) { ctx->ba_trace_h = malloc(sizeof(BAIterRec) * BA_TRACE_CAP); OV2_REQUIRE(ctx->ba_trace_h, OV2_ENOMEM, "trace buffer"); }
+    *trace = (BAIterRec *)ctx->ba_trace_d;
+    return OV2_OK;
+}
+static inline int ba_trace_fetch(ov2_ctx *ctx, int n_trace)
+{
+    ctx->ba_trace_n = n_trace;
+    const int nrec = n_trace < BA_TRACE_CAP ? n_trace : BA_TRACE_CAP;
+    if (nrec > 0) OV2_HIP_CHECK(hipMemcpy(ctx->ba_trace_h, ctx->ba_trace_d, sizeof(BAIterRec) * (size_t)nrec, hipMemcpyDeviceToHost));
+    return OV2_OK;
 }
 
 // ---------------------------------------------------------------------------------- trust-region bookkeeping (one thread)

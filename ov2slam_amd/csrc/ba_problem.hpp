@@ -1,6 +1,6 @@
 // ba_problem.hpp -- the device-resident BA problem (ov2_ba_dev): validation, the landmark sort, the pool layout and the upload
 // (ba_create, xyzba_create), the slices of a lock-step batch and the context's host thread pool.  A part of ba.hip (same
-// translation unit): included there after BADev and the Cholesky's size limits.
+// translation unit): included there after BADev; sizes and path decisions come from ba_geom.hpp.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -171,7 +171,7 @@ static int ba_create(ov2_ctx *ctx, const ov2_ba_problem *p, ov2_ba_dev **out, bo
     std::vector<int> pose_col(p->n_kf);
     int n_opt = 0;
     for (int k = 0; k < p->n_kf; k++) pose_col[k] = p->kf_const[k] ? -1 : 6 * n_opt++;
-    const int nf = 6 * n_opt, nfp = std::max(BA_TILE, (nf + BA_TILE - 1) / BA_TILE * BA_TILE);
+    const int nf = 6 * n_opt, nfp = ba_nfp(n_opt);
     OV2_REQUIRE(nfp <= BA_MAX_NFP, OV2_EUNSUPPORTED, "more than 1024 optimised keyframes: dense reduced system too large");
     // the per-residual upload arrays are filled straight into the context's PINNED host scratch: the H2D copies below are then
     // real asynchronous DMA (from pageable std::vectors every copy went through the runtime's staging buffer, ~2.5 ms for the
@@ -239,16 +239,11 @@ static int ba_create(ov2_ctx *ctx, const ov2_ba_problem *p, ov2_ba_dev **out, bo
     BADev &D = dev->D;
     memset(&D, 0, sizeof(D));
     D.n_kf = p->n_kf; D.n_lm = p->n_lm; D.n_act = n_act; D.nf = nf; D.nfp = nfp; D.n_po = n_po; D.ldim = 1; D.n_res = p->n_res;
-    {   // beyond what the LDS-resident lineariser / Cholesky hold (~90 optimised keyframes): sparse W + HBM Cholesky (BADev::big)
-        const size_t lin_lds = 8 * (8 * (size_t)nfp + (size_t)n_opt * 27 + 4 * (size_t)n_opt * 21 + 4 * (size_t)LIN_RED) + 64;
-        const size_t chol_lds = chol_lds_bytes(nf, nfp);
-        D.big = (lin_lds > 159 * 1024 || chol_lds > 150 * 1024 || nf > CH_MAX_LDS_N) ? 1 : 0;
-        if (ctx->ba_force_large) D.big = 1;                                    // OV2_OPT_BA_FORCE_LARGE: the path on small problems (tests)
-        // beyond ~570 optimised keyframes the big-path linearisers cannot pre-aggregate the observer blocks in LDS either
-        D.lin_direct = (D.big && 8 * ((size_t)n_opt * 27 + 4 * (size_t)LIN_RED) + 64 > 159 * 1024) ? 1 : 0;
-        if (ctx->ba_lin_direct && D.big) D.lin_direct = 1;                     // OV2_OPT_BA_LIN_DIRECT (tests: force it on small problems)
-        D.chol_hbm = D.big; D.lin_waves = 4;
-    }
+    // beyond what the LDS-resident lineariser / Cholesky hold (69 optimised keyframes): sparse W + HBM Cholesky (BADev::big); from 583
+    // the big-path linearisers cannot pre-aggregate the observer blocks in LDS either.  The decisions are ba_geom.hpp's.
+    D.big = !ba_small_path(n_opt) || ctx->ba_force_large;                      // OV2_OPT_BA_FORCE_LARGE: the path on small problems (tests)
+    D.lin_direct = D.big && (ba_lin_direct(n_opt) || ctx->ba_lin_direct);      // OV2_OPT_BA_LIN_DIRECT (tests: force it on small problems)
+    D.chol_hbm = D.big; D.lin_waves = 4;
     // big path: the slots of the sparse W (one per landmark and optimised keyframe seeing or anchoring it) and their per-keyframe lists
     std::vector<int> cw_ptr(p->n_lm + 1, 0), cw_col, cw_lm, res_cw, lm_cwa, kfl_ptr(n_opt + 1, 0), kfl_idx;
     if (D.big) {
@@ -390,22 +385,18 @@ static int xyzba_create(ov2_ctx *ctx, const ov2_xyzba_problem *p, ov2_ba_dev **o
     std::vector<int> pose_col(p->n_kf);
     int n_opt = 0;
     for (int k = 0; k < p->n_kf; k++) pose_col[k] = (p->kf_const && p->kf_const[k]) ? -1 : 6 * n_opt++;
-    const int nf = 6 * n_opt, nfp = std::max(BA_TILE, (nf + BA_TILE - 1) / BA_TILE * BA_TILE);
+    const int nf = 6 * n_opt, nfp = ba_nfp(n_opt);
     // Size limits BEFORE anything is allocated or uploaded (W and W' alone are 2 x 24 n_pts nfp bytes).  The 3-D point form keeps
     // W dense: its lineariser holds 3 rows of it per wavefront in LDS next to the observer blocks (4 wavefronts per work-group up
-    // to ~200 optimised keyframes, then 2, then 1: ~450), and beyond ~90 keyframes the reduced system is factored by the
-    // multi-kernel Cholesky on HBM instead of the one-work-group LDS kernel.
-    int lin_waves = 0;
-    for (int nw = 4; nw >= 1 && !lin_waves; nw >>= 1)
-        if (8 * (3 * (size_t)nw * nfp + (size_t)n_opt * 27) + 64 <= 159 * 1024) lin_waves = nw;
+    // to 202 optimised keyframes, then 2 up to 320, then 1 up to 451: ba_xyz_lin_waves), and beyond 69 keyframes the reduced system is
+    // factored by the multi-kernel Cholesky on HBM instead of the one-work-group LDS kernel (ba_chol_hbm).
+    int lin_waves = ba_xyz_lin_waves(n_opt, nfp);
     if (ctx->ba_xyz_lin_waves == 1 || ctx->ba_xyz_lin_waves == 2) lin_waves = lin_waves ? std::min(lin_waves, ctx->ba_xyz_lin_waves) : 0;   // OV2_OPT_BA_XYZ_LIN_WAVES (tests)
     if (!lin_waves || nfp > BA_MAX_NFP) {
-        ov2_set_error("too many optimised keyframes (%d) for the 3-D point form (limit ~450: dense W rows in LDS)", n_opt);
+        ov2_set_error("too many optimised keyframes (%d) for the 3-D point form (limit 451: dense W rows in LDS)", n_opt);
         return OV2_EUNSUPPORTED;
     }
-    const size_t chol_lds_res = chol_lds_bytes(nf, nfp);
-    int chol_hbm = (chol_lds_res > 150 * 1024 || nf > CH_MAX_LDS_N) ? 1 : 0;
-    if (ctx->ba_force_large) chol_hbm = 1;                                      // OV2_OPT_BA_FORCE_LARGE (tests: the HBM factorisation on small problems)
+    const int chol_hbm = ba_chol_hbm(n_opt, nfp) || ctx->ba_force_large;         // OV2_OPT_BA_FORCE_LARGE (tests: the HBM factorisation on small problems)
     std::vector<int> fill(cnt.begin(), cnt.end() - 1), res_kf(n_act), res_orig(n_act);
     std::vector<uint8_t> res_type(n_act);
     std::vector<double> res_uv(2 * (size_t)n_act), res_sigma(n_act);

@@ -895,15 +895,13 @@ int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *
     float ms = 0;
     const uint8_t *hs_c = nullptr;
     const bool trace = n_items == 1 && ctx->ba_trace;      // ov2_pose_graph_solve (a batch call with one item is the same call)
-    ctx->ba_trace_n = 0;
+    BAIterRec *trace_d = nullptr;
+    ctx->ba_trace_n = 0;                                   // (also when nothing is solved)
     if (any) {
         OV2_HIP_CHECK(hipSetDevice(ctx->device));
         rc = ctx->reserve_device(total);  if (rc) return rc;
         rc = ctx->reserve_host(up_end);   if (rc) return rc;
-        if (trace) {
-            if (!ctx->ba_trace_d) OV2_HIP_CHECK(hipMalloc(&ctx->ba_trace_d, sizeof(BAIterRec) * BA_TRACE_CAP));
-            if (!ctx->ba_trace_h) { ctx->ba_trace_h = malloc(sizeof(BAIterRec) * BA_TRACE_CAP); OV2_REQUIRE(ctx->ba_trace_h, OV2_ENOMEM, "trace buffer"); }
-        }
+        rc = ba_trace_begin(ctx, trace, &trace_d);  if (rc) return rc;
         uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
         memset(hs, 0, up_end);
         for (size_t b = 0; b < B; b++) {
@@ -928,8 +926,8 @@ int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *
         PgArgs a;
         a.arena = ds; a.items = (const PgItem *)ds; a.out = (PgOut *)(ds + o_out);
         a.O = ba_opt_from(*opt); a.initial_radius = opt->initial_radius;
-        a.trace = trace ? (BAIterRec *)ctx->ba_trace_d : nullptr;
-        for (int i = 0; i < 2; i++) if (!ctx->ba_ev[i]) OV2_HIP_CHECK(hipEventCreate(&ctx->ba_ev[i]));      // (the context's: destroyed with it)
+        a.trace = trace_d;
+        rc = ba_events(ctx);  if (rc) return rc;
         OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[0], ctx->stream));
         hipLaunchKernelGGL(k_pg_solve, dim3(n_items), dim3(PG_THREADS), 0, ctx->stream, a);
         OV2_HIP_CHECK(hipGetLastError());
@@ -955,11 +953,7 @@ int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *
         else memcpy(r.poses_out, hs_c + items[b].o_x, bytes);
         r.iterations = o.iterations; r.num_successful_steps = o.num_successful_steps; r.initial_cost = o.initial_cost;
         r.final_cost = o.final_cost; r.termination = o.termination;
-        if (trace) {
-            ctx->ba_trace_n = o.n_trace;
-            const int nrec = o.n_trace < BA_TRACE_CAP ? o.n_trace : BA_TRACE_CAP;
-            if (nrec > 0) OV2_HIP_CHECK(hipMemcpy(ctx->ba_trace_h, ctx->ba_trace_d, sizeof(BAIterRec) * (size_t)nrec, hipMemcpyDeviceToHost));
-        }
+        if (trace) { rc = ba_trace_fetch(ctx, o.n_trace);  if (rc) return rc; }
     }
     return OV2_OK;
 }

@@ -306,8 +306,8 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
     d_quat_to_R(p->T_rl + 3, D.Rrl);
     D.trl[0] = p->T_rl[0]; D.trl[1] = p->T_rl[1]; D.trl[2] = p->T_rl[2];
     D.O = ba_opt_from(*opt); D.huber = opt->huber_delta; D.initial_radius = opt->initial_radius;
-    hipEvent_t e0, e1;
-    OV2_HIP_CHECK(hipEventCreate(&e0)); OV2_HIP_CHECK(hipEventCreate(&e1));
+    rc = ba_events(ctx);  if (rc) return rc;             // (the context's pair: nothing to release on the error returns below)
+    hipEvent_t e0 = ctx->ba_ev[0], e1 = ctx->ba_ev[1];
     OV2_HIP_CHECK(hipEventRecord(e0, ctx->stream));
     hipLaunchKernelGGL(k_structure_ba, dim3(1), dim3(1024), 0, ctx->stream, D);
     OV2_HIP_CHECK(hipGetLastError());
@@ -317,7 +317,6 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     float ms = 0;
     OV2_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (res->xyz_out && n_pts) memcpy(res->xyz_out, hs + o_x, 24 * (size_t)n_pts);
     if (res->chi2_last_eval && n_res) memcpy(res->chi2_last_eval, hs + o_chi2, 8 * (size_t)n_res);
     if (res->depthpos_last_eval && n_res) memcpy(res->depthpos_last_eval, hs + o_dpos, (size_t)n_res);

@@ -106,6 +106,18 @@ def test_batch_falls_back_for_problems_it_does_not_cover(gpu_ctx):
         ov2slam_amd.Optimizer(gpu_ctx).localBA_batch([small, bad])
 
 
+def test_batch_splits_at_the_path_boundary(gpu_ctx):
+    """70 and 69 optimised keyframes (one keyframe of the stereo form is constant): the first is laid out for the sparse path and is
+    solved alone, the second is the largest problem that shares launches (ba_small_path, csrc/ba_geom.hpp) -- ba_create and the
+    batch's choice of who may share launches must agree on it."""
+    large, small = synth.make_ba_problem(71, 600, 6, stereo=True, seed=5), synth.make_ba_problem(70, 600, 6, stereo=True, seed=5)
+    assert [int((pb["kf_const"] == 0).sum()) for pb in (large, small)] == [70, 69]
+    res, nb = ov2slam_amd.Optimizer(gpu_ctx).localBA_batch([large, small])
+    assert nb == 1
+    _same(res[0], ov2slam_amd.Optimizer(gpu_ctx).localBA(large), tight=1e-6)
+    _same(res[1], ov2slam_amd.Optimizer(gpu_ctx).localBA(small))
+
+
 def test_batch_reports_a_status_per_problem(gpu_ctx):
     """a left-out problem that ov2_local_ba rejects (OV2_RES_PNP blocks: OV2_EUNSUPPORTED) must neither hide the valid
     results of the others nor stop the left-out problems after it (include/ov2slam_hip.h ov2_local_ba_result::status)."""
