@@ -190,6 +190,46 @@ int ov2_pyr_build_clahe_h(ov2_ctx *ctx, ov2_pyr *p, const uint8_t *img_h, int st
  * (src/mapper.cpp:74-81 per keyframe).  clip_limit < 0: no CLAHE (use_clahe: 0).  Asynchronous like ov2_pyr_build_clahe_h.        */
 int ov2_pyr_build_clahe_hb(ov2_ctx *ctx, ov2_pyr *p, int n_items, const uint8_t *const *img_h, int stride, double clip_limit, int tiles_x, int tiles_y);
 
+/* ---- image rectification: CameraCalibration::rectifyImage ----------------------------------------
+ * cv::remap(img, rect, undist_map_x_, undist_map_y_, cv::INTER_LINEAR) of src/camera_calibration.cpp:233-241, which
+ * SlamManager::addNewMonoImage / addNewStereoImages run on every frame, left and right, before preprocessImage whenever
+ * bdo_undist / bdo_stereo_rect is set (src/ov2slam.cpp:239-265).  CV_8UC1, INTER_LINEAR, BORDER_CONSTANT 0: OpenCV's own C++
+ * path RESTATED (tests/remap_ref.py), not pinned against an OpenCV build; IPP's remap, which stock builds disable, is not the
+ * canonical form.  The two map forms are the two the reference creates:
+ *   OV2_MAP_F32    setUndistMap (:92 / :97), a CV_32FC1 pair: map1[y*w+x] = source x, map2[y*w+x] = source y (float).  Per
+ *                  pixel sx = cvRound(x * 32.f), sy likewise (ties to even); ix = saturate_cast<short>(sx >> 5), a = sx & 31,
+ *                  iy / b from sy (arithmetic shift, two's complement: negative coordinates floor).
+ *   OV2_MAP_FIXED  setUndistStereoMap (:141 / :145), type 11: map1 = (ix, iy) int16 pairs (CV_16SC2), map2 = b * 32 + a as
+ *                  uint16 (CV_16UC1).
+ * With p00, p01, p10, p11 the source pixels at (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1), every tap outside the image 0:
+ *   out = (p00*(32-a)*(32-b)*32 + p01*a*(32-b)*32 + p10*(32-a)*b*32 + p11*a*b*32 + (1 << 14)) >> 15
+ * (OpenCV's BilinearTab_i; at (a, b) = (0, 0) its short table holds 32767 + a fix-up, which gives p00 for 8-bit pixels too).
+ * ov2_rectmap_create checks the contract -- w, h in [2, 32767]; OV2_MAP_F32 values finite with |v| * 32 < 2^31; OV2_MAP_FIXED
+ * map2 values < 1024: OV2_EINVAL otherwise -- and normalises either form, once, on the host, to one device representation
+ * (6 B per pixel): there is one kernel path.  The handle is opaque and immutable; the caller's arrays are free on return.
+ * A map must OUTLIVE every tracker it is set on (ov2_*_set_rectification) and every call it was passed to that is still in
+ * flight: destroy it after them (or after ov2_*_set_rectification(t, NULL) / a synchronisation).  Computing the maps
+ * (cv::initUndistortRectifyMap, cv::stereoRectify) happens once at start-up and stays with the caller.                     */
+#define OV2_MAP_F32   0
+#define OV2_MAP_FIXED 1
+typedef struct ov2_rectmap ov2_rectmap;
+int  ov2_rectmap_create(ov2_ctx *ctx, int w, int h, int form, const void *map1, const void *map2, ov2_rectmap **out);
+void ov2_rectmap_destroy(ov2_rectmap *map);
+/* rectifyImage on host buffers (rows src_stride / dst_stride bytes apart; only w bytes of a dst row are written): one H2D, the
+ * kernel, one D2H, synchronising.  dst_h == src_h is allowed (the reference rectifies in place).                          */
+int ov2_rectify_h(ov2_ctx *ctx, const ov2_rectmap *map, const uint8_t *src_h, int src_stride, uint8_t *dst_h, int dst_stride);
+/* n_items device images `src_item_stride` bytes apart (rows src_pitch apart) -> dst likewise; the map entries are read once per
+ * work-group and reused for its items.  Asynchronous on ctx's stream; src and dst must not overlap.  Whole-dword stores when
+ * dst_d, dst_pitch and dst_item_stride are multiples of 4 (byte stores otherwise, same result).                           */
+int ov2_rectify_d(ov2_ctx *ctx, const ov2_rectmap *map, const uint8_t *src_d, size_t src_pitch, size_t src_item_stride, int n_items,
+                  uint8_t *dst_d, size_t dst_pitch, size_t dst_item_stride);
+/* The right image(s) of a stereo keyframe (src/ov2slam.cpp:255-256, then src/mapper.cpp:74-81): n_items RAW host images (one
+ * pointer each, rows `stride` apart) into items [0, n_items) of `p` -- ONE H2D, the remap, then what ov2_pyr_build_clahe_h /
+ * _hb (use_clahe != 0) or ov2_pyr_build_h (use_clahe == 0: clip_limit / tiles ignored) do with the rectified frames.
+ * Asynchronous like those; OV2_EINVAL when map and pyramid differ in size.                                                 */
+int ov2_pyr_build_rect_h(ov2_ctx *ctx, ov2_pyr *p, const ov2_rectmap *map, int n_items, const uint8_t *const *img_h, int stride,
+                         int use_clahe, double clip_limit, int tiles_x, int tiles_y);
+
 /* ---- Lucas-Kanade --------------------------------------------------
  * ov2_lk_track replaces one cv::calcOpticalFlowPyrLK(prevPyr, nextPyr, prevPts,
  * nextPts, status, err, Size(win,win), max_level, TermCriteria(COUNT+EPS,
@@ -288,6 +328,14 @@ int  ov2_tracker_track_frame(ov2_tracker *t, const uint8_t *img_h, int stride, c
  * ov2_tracker_klt / _track_frame call (entries of untracked keypoints are computed from their last forward position).   */
 int  ov2_tracker_set_calibration(ov2_tracker *t, int model, const double K[4], const double *D, int nD, const double iK[9]);
 int  ov2_tracker_last_keypoints(const ov2_tracker *t, int n, float *unpx_xy_h, double *bv_xyz_h);
+/* Optional: rectifyImage inside the per-frame enqueue.  From this call on the frames handed to ov2_tracker_preprocess /
+ * _track_frame are RAW (distorted): each is uploaded to a buffer of its own (allocated by the first such call) and remapped, as
+ * one more kernel of the same enqueue -- one more node of the captured graph, the chain stays linear -- before CLAHE / level 0.
+ * The tracker's device frame then holds the RECTIFIED image: ov2_tracker_describe_brief and the detectors on the tracker's
+ * pyramid see what the reference's imraw / im hold after rectifyImage.  map == NULL switches it off again (the frames are then
+ * taken as they come, and every call enqueues exactly what it did before).  The map must match the tracker's w x h
+ * (OV2_EINVAL) and outlive its use here.  Synchronises and re-captures the graphs like ov2_tracker_set_calibration.        */
+int  ov2_tracker_set_rectification(ov2_tracker *t, const ov2_rectmap *map);
 /* the tracker's pyramids (valid until the next preprocess), e.g. for createKeyframe / stereo matching / detection */
 const ov2_pyr *ov2_tracker_cur_pyr(const ov2_tracker *t);
 const ov2_pyr *ov2_tracker_prev_pyr(const ov2_tracker *t);
@@ -333,6 +381,13 @@ int  ov2_btracker_prepare(ov2_btracker *t, int which, int n_active);
 /* Frame::computeKeypoint inside the per-step enqueue, as ov2_tracker_set_calibration (one calibration: the sequences of a batch
  * come from one camera rig)                                                                                            */
 int  ov2_btracker_set_calibration(ov2_btracker *t, int model, const double K[4], const double *D, int nD, const double iK[9]);
+/* rectifyImage inside the per-step enqueue, as ov2_tracker_set_rectification (one map: the sequences of a batch come from one
+ * camera rig): the frames of ov2_btracker_track_frame / _upload / _prepare are RAW from this call on.  They are uploaded to a set
+ * of three raw buffers (allocated by the first such call) and remapped for all active items in one launch before CLAHE / level 0 --
+ * on the prep stream for ov2_btracker_prepare, on the context's stream otherwise; ov2_btracker_describe_brief then reads the
+ * RECTIFIED frames.  map == NULL switches it off.  Call it between steps: it synchronises the tracker's streams, voids
+ * uploads started ahead (they are repeated in order) and returns OV2_EINVAL while prepared frames wait or a step is open.   */
+int  ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map);
 /* preprocessImage + kltTracking of items [0, n_active): the lock-step form of ov2_tracker_track_frame, same per-item semantics
  * (first frame: pyramids only; has_prior_h / klt_use_prior / status bits / p3p_req[b] as there, the "motion model is wrong" retry
  * of visual_front_end.cpp:225-230 included).  Blocking: one synchronisation.                                             */
@@ -496,7 +551,7 @@ int ov2_describe_brief(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int str
 int ov2_describe_brief_batch_d(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int pitch, size_t item_stride, int n_items,
                                const float *xy_d, int cap, const int *n_d, uint8_t *desc_d, uint8_t *valid_d);
 /* the RAW frame of the tracker's current frame (the image given to the last preprocess / track_frame, before CLAHE -- already in HBM:
- * no upload); valid until the next preprocess.  Needs one preprocessed frame.                                                 */
+ * no upload; after ov2_tracker_set_rectification: that image rectified); valid until the next preprocess.  Needs one preprocessed frame. */
 int ov2_tracker_describe_brief(ov2_tracker *t, const float *xy_h, int n, uint8_t *desc_h, uint8_t *valid_h);
 /* the raw frames of the current lock-step step (the last ov2_btracker_track_frame), items [0, n_active) with n_active <= that step's;
  * host points / outputs with cap slots per item (n_h[b] valid; slots past n_h[b] untouched).  OV2_EINVAL once the staging set that

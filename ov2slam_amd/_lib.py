@@ -30,6 +30,7 @@ OV2_FAST_TIE_SCAN_ORDER, OV2_FAST_TIE_LIBSTDCXX = 0, 1
 OV2_LK_IMPL_AUTO, OV2_LK_IMPL_ROW, OV2_LK_IMPL_LANE3 = 0, 1, 2
 OV2_TRACK_IMPL_WAVE, OV2_TRACK_IMPL_ROW = 0, 1
 OV2_BRIEF_BYTES = 32
+OV2_MAP_F32, OV2_MAP_FIXED = 0, 1
 OV2_RES_LEFT, OV2_RES_RIGHT, OV2_RES_RIGHT_ANCH, OV2_RES_PNP = 0, 1, 2, 3
 OV2_TRI_STEREO_TRIED, OV2_TRI_STEREO_OK, OV2_TRI_TEMPORAL_TRIED, OV2_TRI_TEMPORAL_OK, OV2_TRI_NO_MOTION, OV2_TRI_REMOVE_OBS = 1, 2, 4, 8, 16, 32
 OV2_MATCH_BEHIND, OV2_MATCH_OUT_OF_FOV, OV2_MATCH_OUT_OF_IMAGE, OV2_MATCH_NO_CANDIDATE, OV2_MATCH_RATIO_REJECTED, OV2_MATCH_BEST = 1, 2, 4, 8, 16, 32
@@ -286,6 +287,11 @@ SIGNATURES = {
     "ov2_pyr_build_clahe_d": (_i, [_vp, _vp, _vp, _i, C.c_size_t, _d, _i, _i]),
     "ov2_pyr_build_clahe_h": (_i, [_vp, _vp, _vp, _i, _d, _i, _i]),
     "ov2_pyr_build_clahe_hb": (_i, [_vp, _vp, _i, _vp, _i, _d, _i, _i]),
+    "ov2_rectmap_create": (_i, [_vp, _i, _i, _i, _vp, _vp, _pp]),
+    "ov2_rectmap_destroy": (None, [_vp]),
+    "ov2_rectify_h": (_i, [_vp, _vp, _vp, _i, _vp, _i]),
+    "ov2_rectify_d": (_i, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _i, _vp, C.c_size_t, C.c_size_t]),
+    "ov2_pyr_build_rect_h": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _d, _i, _i]),
     "ov2_stereo_match_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ov2_tracker_create": (_i, [_vp, C.POINTER(TrackerConfig), _pp]),
     "ov2_tracker_destroy": (None, [_vp]),
@@ -295,6 +301,7 @@ SIGNATURES = {
     "ov2_tracker_track_frame": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, C.POINTER(_i)]),
     "ov2_tracker_set_calibration": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
     "ov2_tracker_last_keypoints": (_i, [_vp, _i, _vp, _vp]),
+    "ov2_tracker_set_rectification": (_i, [_vp, _vp]),
     "ov2_tracker_cur_pyr": (_vp, [_vp]),
     "ov2_tracker_prev_pyr": (_vp, [_vp]),
     "ov2_tracker_frames": (_i, [_vp]),
@@ -307,6 +314,7 @@ SIGNATURES = {
     "ov2_btracker_upload": (_i, [_vp, _i, _i]),
     "ov2_btracker_prepare": (_i, [_vp, _i, _i]),
     "ov2_btracker_set_calibration": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
+    "ov2_btracker_set_rectification": (_i, [_vp, _vp]),
     "ov2_btracker_track_frame": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "ov2_btracker_track_frame_begin": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "ov2_btracker_track_frame_end": (_i, [_vp, _vp, _vp, _vp]),

@@ -129,7 +129,19 @@ struct ov2_pyr {
 int ov2_pyr_mark_ready(ov2_ctx *ctx, ov2_pyr *p);              // after the last kernel of a build was enqueued
 int ov2_pyr_wait_ready(ov2_ctx *ctx, const ov2_pyr *p);        // before the first kernel of a consumer
 
+// ---- rectification map (rectify.hip) -----------------------------------------
+// Both map forms of ov2_rectmap_create normalised to one device representation; immutable after creation.
+struct ov2_rectmap {
+    int device = 0, w = 0, h = 0;
+    int pitch = 0;              // map entries per row: w rounded up to 4 (the kernel's vector loads stay aligned)
+    uint32_t *ixy = nullptr;    // (uint16)ix | (uint16)iy << 16
+    uint16_t *ab = nullptr;     // b * 32 + a
+};
+
 // kernels' host launchers (defined in the .hip files)
+// cv::remap (INTER_LINEAR, BORDER_CONSTANT 0) of n_items device images through `m` (k_remap): src and dst must not overlap
+int ov2_launch_remap(hipStream_t stream, const ov2_rectmap *m, const uint8_t *src_d, size_t src_pitch, size_t src_item, int n_items,
+                     uint8_t *dst_d, size_t dst_pitch, size_t dst_item);
 // from_level = 1: levels 0 and 1 (borders included) are already in place (k_clahe_apply_pyr)
 int ov2_launch_pyr_build(ov2_ctx *ctx, ov2_pyr *p, const uint8_t *img_d, int stride, size_t img_batch_stride, int from_level = 0);
 // cv::CLAHE::apply on `batch` device images; border > 0: dst is a padded pyramid level, its REFLECT_101 border is written too

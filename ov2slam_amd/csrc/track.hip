@@ -7,6 +7,7 @@
 //   H2D keypoint block (one copy: n, keypoints, priors, flags) -> k_track_klt (both fbKltTracking calls of the
 //   reference and the retry of lost prior tracks in one launch, lk.hip) -> D2H result block (one copy) -> ONE sync.
 // With use_graph the whole sequence is captured once per pyramid parity and replayed with hipGraphLaunch.
+// ov2_tracker_set_rectification: the H2D goes to a raw buffer and k_remap (rectify.hip) follows it, before k_clahe_lut.
 #include "common.hpp"
 #include "keypoint_dev.hpp"
 #include <new>
@@ -22,6 +23,9 @@ struct ov2_tracker {
     int frames = 0;
     // pinned host / device mirrors
     uint8_t *himg = nullptr, *dimg = nullptr; size_t img_pitch = 0, img_bytes = 0;
+    // ov2_tracker_set_rectification: the frame's H2D goes to draw, k_remap writes the rectified frame to dimg
+    const ov2_rectmap *rect = nullptr;
+    uint8_t *draw = nullptr;       // allocated by the first ov2_tracker_set_rectification
     uint8_t *lut = nullptr;
     uint8_t *hblk = nullptr, *dblk = nullptr;
     uint8_t *kblk = nullptr;       // what the LK kernel dereferences: dblk, or the device alias of the pinned block (zero_copy)
@@ -40,12 +44,17 @@ struct ov2_tracker {
 
 static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-// preprocessImage body for pyramid `dst` (no swap, no event): frame H2D + CLAHE / level-0 copy + coarser levels
+// preprocessImage body for pyramid `dst` (no swap, no event): frame H2D (+ rectifyImage) + CLAHE / level-0 copy + coarser levels
 static int enqueue_preprocess(ov2_tracker *t, ov2_pyr *dst)
 {
     ov2_ctx *ctx = t->ctx;
     const ov2_tracker_config &c = t->cfg;
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dimg, t->himg, t->img_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (t->rect) {
+        OV2_HIP_CHECK(hipMemcpyAsync(t->draw, t->himg, t->img_bytes, hipMemcpyHostToDevice, ctx->stream));
+        const int rcr = ov2_launch_remap(ctx->stream, t->rect, t->draw, t->img_pitch, 0, 1, t->dimg, t->img_pitch, 0);
+        if (rcr != OV2_OK) return rcr;
+    } else
+        OV2_HIP_CHECK(hipMemcpyAsync(t->dimg, t->himg, t->img_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (c.use_clahe) {
         const PyrLevelDesc &L0 = dst->d.lv[0];
         int rc = ov2_launch_clahe(ctx, t->dimg, c.w, c.h, (int)t->img_pitch, 0, 1, c.clahe_clip, c.tiles_x, c.tiles_y,
@@ -178,6 +187,7 @@ static void tracker_free(ov2_tracker *t)
     if (t->himg) (void)hipHostFree(t->himg);
     if (t->hblk) (void)hipHostFree(t->hblk);
     if (t->dimg) (void)hipFree(t->dimg);
+    if (t->draw) (void)hipFree(t->draw);
     if (t->dblk) (void)hipFree(t->dblk);
     if (t->lut) (void)hipFree(t->lut);
     delete t;
@@ -276,6 +286,28 @@ int ov2_tracker_set_calibration(ov2_tracker *t, int model, const double K[4], co
     return OV2_OK;
 }
 
+int ov2_tracker_set_rectification(ov2_tracker *t, const ov2_rectmap *map)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!map || (map->w == t->cfg.w && map->h == t->cfg.h), OV2_EINVAL, "map and tracker differ in size");
+    OV2_REQUIRE(!map || map->device == t->ctx->device, OV2_EINVAL, "the map lives on another device");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    if (map && !t->draw) {
+        OV2_HIP_CHECK(hipMalloc((void **)&t->draw, t->img_bytes + 256));
+        OV2_HIP_CHECK(hipMemset(t->draw, 0, t->img_bytes + 256));
+    }
+    t->rect = map;
+    // the per-frame enqueue gained / lost a kernel and reads another buffer: the captured graphs are stale
+    for (int i = 0; i < 2; i++) if (t->gexec[i]) { (void)hipGraphExecDestroy(t->gexec[i]); t->gexec[i] = nullptr; }
+    for (int parity = 0; parity < 2 && t->graph_ok; parity++) {
+        const int rcg = capture_graph(t, parity);
+        if (rcg == OV2_EUNSUPPORTED) t->graph_ok = false;
+        else if (rcg != OV2_OK) return rcg;
+    }
+    return OV2_OK;
+}
+
 int ov2_tracker_last_keypoints(const ov2_tracker *t, int n, float *unpx_xy_h, double *bv_xyz_h)
 {
     OV2_REQUIRE(t && t->has_calib, OV2_EINVAL, "no calibration set on this tracker");
@@ -296,7 +328,8 @@ const ov2_pyr *ov2_tracker_cur_pyr(const ov2_tracker *t) { return t ? t->pyr[t->
 const ov2_pyr *ov2_tracker_prev_pyr(const ov2_tracker *t) { return t ? t->pyr[t->cur ^ 1] : nullptr; }
 int ov2_tracker_frames(const ov2_tracker *t) { return t ? t->frames : 0; }
 
-// describeBRIEF on the raw frame: dimg holds it from the frame's H2D (on this stream) until the next preprocess rewrites it
+// describeBRIEF on the raw frame: dimg holds it from the frame's H2D (on this stream; rectified there when a map is set) until the
+// next preprocess rewrites it
 int ov2_tracker_describe_brief(ov2_tracker *t, const float *xy_h, int n, uint8_t *desc_h, uint8_t *valid_h)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");

@@ -43,6 +43,12 @@ struct ov2_btracker {
     // frames: pinned staging sets + their device mirrors; a copy stream for uploads and a stream for pre-processing started ahead
     uint8_t *himg[BT_IMG_SETS] = {nullptr, nullptr, nullptr}, *dimg[BT_IMG_SETS] = {nullptr, nullptr, nullptr};
     size_t img_pitch = 0, img_bytes = 0;          // per item (img_bytes a multiple of 256)
+    // ov2_btracker_set_rectification: the uploads of set `which` go to draw[which]; the pre-processing of the set starts with k_remap
+    // draw[which] -> dimg[which], so dimg holds the RECTIFIED frames.  used_ev[which] is recorded behind that pre-processing: it covers
+    // the remap's reads of draw[which] as it covers the reads of dimg[which]
+    const ov2_rectmap *rect = nullptr;
+    uint8_t *draw[BT_IMG_SETS] = {nullptr, nullptr, nullptr};      // allocated by the first ov2_btracker_set_rectification
+    uint8_t *upload_dst(int which) const { return rect ? draw[which] : dimg[which]; }
     hipStream_t cs = nullptr, ps = nullptr;
     ov2_ctx side;                                 // what the launchers of clahe.hip / pyramid.hip see when they enqueue on `ps`
     uint8_t *lut = nullptr;                       // CLAHE tables of a step (the context's scratch is busy with the detector on the main stream)
@@ -90,6 +96,7 @@ static void btracker_free(ov2_btracker *t)
         if (t->used_ev[i]) (void)hipEventDestroy(t->used_ev[i]);
         if (t->himg[i]) (void)hipHostFree(t->himg[i]);
         if (t->dimg[i]) (void)hipFree(t->dimg[i]);
+        if (t->draw[i]) (void)hipFree(t->draw[i]);
     }
     if (t->hblk) (void)hipHostFree(t->hblk);
     if (t->dblk) (void)hipFree(t->dblk);
@@ -111,6 +118,10 @@ static int enqueue_preprocess(ov2_btracker *t, ov2_ctx *on, ov2_pyr *dst, int wh
     const ov2_tracker_config &c = t->cfg;
     ov2_pyr q = prefix_of(dst, n);
     int rc;
+    if (t->rect) {                                                       // rectifyImage of the n raw frames, one launch
+        rc = ov2_launch_remap(on->stream, t->rect, t->draw[which], t->img_pitch, t->img_bytes, n, t->dimg[which], t->img_pitch, t->img_bytes);
+        if (rc != OV2_OK) return rc;
+    }
     if (c.use_clahe) {
         const PyrLevelDesc &L0 = q.d.lv[0];
         int l1_done = 0;
@@ -182,7 +193,7 @@ static int stage_and_upload(ov2_btracker *t, int n, const uint8_t *const *img_h,
     if (in_place && t->up_n[which] >= n) OV2_HIP_CHECK(hipStreamWaitEvent(t->ctx->stream, t->up_ev[which], 0));
     else {
         if (t->up_n[which]) OV2_HIP_CHECK(hipStreamWaitEvent(t->ctx->stream, t->up_ev[which], 0));     // a shorter look-ahead copy: order after it
-        OV2_HIP_CHECK(hipMemcpyAsync(t->dimg[which], t->himg[which], (size_t)n * t->img_bytes, hipMemcpyHostToDevice, t->ctx->stream));
+        OV2_HIP_CHECK(hipMemcpyAsync(t->upload_dst(which), t->himg[which], (size_t)n * t->img_bytes, hipMemcpyHostToDevice, t->ctx->stream));
     }
     t->up_n[which] = 0;
     *which_out = which;
@@ -386,7 +397,7 @@ int ov2_btracker_upload(ov2_btracker *t, int which, int n_active)
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
     if (which == t->raw_which) t->raw_which = -1;                       // the current step's raw frames are overwritten
     OV2_HIP_CHECK(hipStreamWaitEvent(t->cs, t->used_ev[which], 0));      // the step that read dimg[which] last (no-op before the first record)
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dimg[which], t->himg[which], (size_t)n_active * t->img_bytes, hipMemcpyHostToDevice, t->cs));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->upload_dst(which), t->himg[which], (size_t)n_active * t->img_bytes, hipMemcpyHostToDevice, t->cs));
     OV2_HIP_CHECK(hipEventRecord(t->up_ev[which], t->cs));
     t->up_n[which] = n_active;
     return OV2_OK;
@@ -404,7 +415,7 @@ int ov2_btracker_prepare(ov2_btracker *t, int which, int n_active)
     else {
         if (t->up_n[which]) OV2_HIP_CHECK(hipStreamWaitEvent(t->ps, t->up_ev[which], 0));
         OV2_HIP_CHECK(hipStreamWaitEvent(t->ps, t->used_ev[which], 0));
-        OV2_HIP_CHECK(hipMemcpyAsync(t->dimg[which], t->himg[which], (size_t)n_active * t->img_bytes, hipMemcpyHostToDevice, t->ps));
+        OV2_HIP_CHECK(hipMemcpyAsync(t->upload_dst(which), t->himg[which], (size_t)n_active * t->img_bytes, hipMemcpyHostToDevice, t->ps));
     }
     t->up_n[which] = 0;
     // target: the pyramid set of frame pre_count.  Its last readers on the context's stream -- the tracking kernels of the step that
@@ -428,6 +439,28 @@ int ov2_btracker_set_calibration(ov2_btracker *t, int model, const double K[4], 
     const int rc = ov2_kp_calib(model, K, D, nD, iK, c);
     if (rc != OV2_OK) return rc;
     t->calib = c; t->has_calib = true;
+    return OV2_OK;
+}
+
+int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!map || (map->w == t->cfg.w && map->h == t->cfg.h), OV2_EINVAL, "map and tracker differ in size");
+    OV2_REQUIRE(!map || map->device == t->ctx->device, OV2_EINVAL, "the map lives on another device");
+    OV2_REQUIRE(t->prepq.empty() && !t->pend.on, OV2_EINVAL, "ov2_btracker_set_rectification between steps only: prepared frames wait or a step is open");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    OV2_HIP_CHECK(hipStreamSynchronize(t->cs));
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ps));
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    for (int i = 0; i < BT_IMG_SETS && map; i++)
+        if (!t->draw[i]) {
+            OV2_HIP_CHECK(hipMalloc((void **)&t->draw[i], t->img_bytes * t->batch + 256));
+            OV2_HIP_CHECK(hipMemset(t->draw[i], 0, t->img_bytes * t->batch + 256));
+        }
+    // an upload started ahead went where the old setting put it: void it (the pinned slots still hold the frames; the step or the
+    // prepare call that consumes them copies them again, in order)
+    for (int i = 0; i < BT_IMG_SETS; i++) t->up_n[i] = 0;
+    t->rect = map;
     return OV2_OK;
 }
 

@@ -163,6 +163,25 @@ class Pyramid:
         L.check(self.lib.ov2_pyr_build_clahe_hb(self.ctx.h, self.h_pyr, len(imgs), ptrs, self.w, float(clip_limit), int(tiles_x), int(tiles_y)))
         return self
 
+    def build_rect(self, rmap, imgs, use_clahe=True, clip_limit=3.0, tiles_x=None, tiles_y=None):
+        """The right image(s) of a stereo keyframe from RAW host frames (ov2_pyr_build_rect_h): upload, rectifyImage through `rmap`
+        (a RectifyMap), then build_clahe / build_clahe_batch (use_clahe) or build of the rectified frames, into items
+        [0, len(imgs)).  imgs: one (h, >= w) uint8 array or a list of them with one common row pitch."""
+        if isinstance(imgs, np.ndarray) and imgs.ndim == 2:
+            imgs = [imgs]
+        imgs = [im if im.dtype == np.uint8 and im.ndim == 2 and im.strides[1] == 1 else np.ascontiguousarray(im, np.uint8) for im in imgs]
+        stride = imgs[0].strides[0]
+        for im in imgs:
+            if im.ndim != 2 or im.shape[0] != self.h or im.shape[1] < self.w or im.strides[0] != stride:
+                raise ValueError("frames must be %d rows of >= %d bytes with one common row pitch" % (self.h, self.w))
+        self._keep = imgs
+        ptrs = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        tx = self.w // 50 if tiles_x is None else int(tiles_x)
+        ty = self.h // 50 if tiles_y is None else int(tiles_y)
+        L.check(self.lib.ov2_pyr_build_rect_h(self.ctx.h, self.h_pyr, rmap.h_map, len(imgs), ptrs, stride, int(bool(use_clahe)),
+                                              float(clip_limit), tx, ty))
+        return self
+
     def build_clahe_from_device(self, dev_ptr, clip_limit, tiles_x, tiles_y, stride=None, batch_stride=None):
         """preprocessImage: CLAHE written straight into level 0, then the coarser levels (one call)."""
         stride = stride or self.w
@@ -189,6 +208,61 @@ class Pyramid:
         if getattr(self, "h_pyr", None):
             self.lib.ov2_pyr_destroy(self.h_pyr)
             self.h_pyr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RectifyMap:
+    """Device form of the pair (undist_map_x_, undist_map_y_) a CameraCalibration holds after setUndistMap / setUndistStereoMap
+    (the reference's src/camera_calibration.cpp:92-97, :141-145): ov2_rectmap.  form "f32": map1 = source x, map2 = source y, (h, w)
+    float32 each (CV_32FC1); form "fixed": map1 (h, w, 2) int16 = (ix, iy) (CV_16SC2), map2 (h, w) uint16 = b * 32 + a (CV_16UC1).
+    Immutable; keep it alive while a tracker uses it."""
+
+    FORMS = {"f32": L.OV2_MAP_F32, "fixed": L.OV2_MAP_FIXED}
+
+    def __init__(self, ctx, form, map1, map2):
+        self.ctx, self.lib = ctx, ctx.lib
+        f = self.FORMS[form] if isinstance(form, str) else int(form)
+        if f == L.OV2_MAP_F32:
+            m1 = np.ascontiguousarray(map1, np.float32); m2 = np.ascontiguousarray(map2, np.float32)
+            if m1.ndim != 2 or m1.shape != m2.shape:
+                raise ValueError("an f32 map is two (h, w) float32 arrays")
+        else:
+            m1 = np.ascontiguousarray(map1, np.int16); m2 = np.ascontiguousarray(map2, np.uint16)
+            if m1.ndim != 3 or m1.shape[2] != 2 or m1.shape[:2] != m2.shape:
+                raise ValueError("a fixed-point map is (h, w, 2) int16 + (h, w) uint16")
+        self.h, self.w = int(m2.shape[0]), int(m2.shape[1])
+        hm = C.c_void_p()
+        L.check(self.lib.ov2_rectmap_create(ctx.h, self.w, self.h, f, _ptr(m1), _ptr(m2), C.byref(hm)))
+        self.h_map = hm
+        ctx._children.add(self)
+
+    def rectify(self, img, out=None):
+        """rectifyImage of an (h, >= w) uint8 host image (any row stride) -> the rectified (h, w) image; out: the array to write
+        (may be img itself: the reference rectifies in place)"""
+        img = img if img.dtype == np.uint8 and img.ndim == 2 and img.strides[1] == 1 else np.ascontiguousarray(img, np.uint8)
+        if img.shape[0] != self.h or img.shape[1] < self.w:
+            raise ValueError("image shape %s does not match the map's %dx%d" % (img.shape, self.w, self.h))
+        if out is None:
+            out = np.empty((self.h, self.w), np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 2 or out.strides[1] != 1 or out.shape[0] != self.h or out.shape[1] < self.w:
+            raise ValueError("out must be an (h, >= w) uint8 array with unit column stride")
+        L.check(self.lib.ov2_rectify_h(self.ctx.h, self.h_map, _ptr(img), img.strides[0], _ptr(out), out.strides[0]))
+        return out
+
+    def rectify_device(self, src_d, src_pitch, src_item_stride, n_items, dst_d, dst_pitch, dst_item_stride):
+        """ov2_rectify_d: device addresses (ints), asynchronous on the context's stream"""
+        L.check(self.lib.ov2_rectify_d(self.ctx.h, self.h_map, C.c_void_p(src_d), int(src_pitch), int(src_item_stride), int(n_items),
+                                       C.c_void_p(dst_d), int(dst_pitch), int(dst_item_stride)))
+
+    def close(self):
+        if getattr(self, "h_map", None):
+            self.lib.ov2_rectmap_destroy(self.h_map)
+            self.h_map = None
 
     def __del__(self):
         try:
@@ -360,6 +434,12 @@ class VisualFrontEndTracker:
         L.check(self.lib.ov2_tracker_set_calibration(self.h_trk, calib.model, _ptr(calib.K), _ptr(calib.D) if calib.D is not None else None,
                                                      0 if calib.D is None else len(calib.D), _ptr(calib.iK)))
 
+    def setRectification(self, rmap):
+        """rmap: RectifyMap or None.  From now on preprocessImage / trackFrame take RAW frames and run CameraCalibration::rectifyImage
+        inside the same enqueue; describeBRIEF and the detectors on cur_pyr then see the rectified frame.  None switches it off."""
+        L.check(self.lib.ov2_tracker_set_rectification(self.h_trk, rmap.h_map if rmap is not None else None))
+        self._rmap = rmap                                    # the map must outlive its use by the tracker
+
     def lastKeypoints(self, n, want_bv=True):
         """(unpx (n,2) float32, bv (n,3) float64 or None) of the n keypoints of the last kltTracking / trackFrame call."""
         unpx = np.empty((n, 2), np.float32)
@@ -422,6 +502,12 @@ class LockstepTracker:
     def setCalibration(self, calib):
         L.check(self.lib.ov2_btracker_set_calibration(self.h_trk, calib.model, _ptr(calib.K), _ptr(calib.D) if calib.D is not None else None,
                                                       0 if calib.D is None else len(calib.D), _ptr(calib.iK)))
+
+    def setRectification(self, rmap):
+        """rmap: RectifyMap or None: the frames of trackFrame / upload / prepare are RAW from now on (rectified in the same enqueue,
+        before CLAHE).  Between steps only."""
+        L.check(self.lib.ov2_btracker_set_rectification(self.h_trk, rmap.h_map if rmap is not None else None))
+        self._rmap = rmap
 
     def upload(self, which, n_active):
         """start the H2D of staging set `which` (already filled through image_buffers[which]) on the copy stream"""
@@ -806,3 +892,17 @@ class CameraCalibration:
 
     def undistortImagePoint(self, pt):
         return self.computeKeypoints(np.asarray(pt, np.float32).reshape(1, 2), want_bv=False)[0][0]
+
+    def setRectifyMaps(self, form, map1, map2):
+        """The maps of setUndistMap ("f32") / setUndistStereoMap ("fixed") (src/camera_calibration.cpp:92-97, :141-145), computed by the
+        caller once at start-up; as there, the calibration is the rectified one from then on (D_ empty).  -> the RectifyMap"""
+        self.rectify_map = RectifyMap(self.ctx, form, map1, map2)
+        self.D = None
+        return self.rectify_map
+
+    def rectifyImage(self, img, out=None):
+        """src/camera_calibration.cpp:233-241: cv::remap through the maps when they are set, the image itself otherwise"""
+        rm = getattr(self, "rectify_map", None)
+        if rm is None:
+            return img
+        return rm.rectify(img, out)

@@ -11,4 +11,9 @@
 static auto *const check_ceres_pnp = &ov2::ceresPnP;
 static auto *const check_p3p_ransac = &ov2::p3pRansac;
 static auto *const check_5pt = &ov2::compute5ptEssentialMatrix;
-int main() { return check_ceres_pnp && check_p3p_ransac && check_5pt ? 0 : 1; }
+// the rectification adapters (CameraCalibration, FrameTracker), by address too
+static auto const check_undist_maps = &ov2::CameraCalibration::setUndistMaps;
+static auto const check_rectify = &ov2::CameraCalibration::rectifyImage;
+static auto const check_rect_map = &ov2::CameraCalibration::rectMap;
+static auto const check_set_rect = &ov2::FrameTracker::setRectification;
+int main() { return check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }

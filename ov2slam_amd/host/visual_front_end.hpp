@@ -93,6 +93,10 @@ public:
     {
         return ov2_tracker_set_calibration(t_, model, K, D, nD, iK) == OV2_OK;
     }
+    // CameraCalibration::rectifyImage (src/ov2slam.cpp:242 / :255) inside the per-frame enqueue: from this call on preprocessImage /
+    // trackFrame take the RAW frame and remap it on the device before CLAHE.  map: CameraCalibration::rectMap (it must outlive its
+    // use here); nullptr switches it off.  Call it right after construction, like setCalibration (the graphs are re-captured).
+    bool setRectification(const ov2_rectmap *map) { return ov2_tracker_set_rectification(t_, map) == OV2_OK; }
     bool lastKeypoints(size_t n, std::vector<Point2f> &vunpx, std::vector<double> &vbv) const
     {
         vunpx.resize(n); vbv.resize(3 * n);
