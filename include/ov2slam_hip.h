@@ -1044,6 +1044,58 @@ int ov2_match_to_map(ov2_ctx *ctx, const ov2_match_params *params, const ov2_mat
 int ov2_match_to_map_batch(ov2_ctx *ctx, const ov2_match_params *params, int n_items, const ov2_match_keyframe *kfs,
                            ov2_match_result *results);
 
+/* ------------------------------------------------------------------ */
+/* Descriptor kNN matching (LoopCloser::knnMatching,                    */
+/* src/loop_closer.cpp:378-459)                                         */
+/* ------------------------------------------------------------------ */
+/* The first stage of LoopCloser::processLoopCandidate: cv::BFMatcher(cv::NORM_HAMMING).knnMatch(query, train, vmatches, 2) and
+ * the loop :432-449 that keeps a query row when it has fewer than two neighbours, or when d0 <= maxdist && d0 <= d1 * 0.85.  One
+ * lane per query row (csrc/knn.hip); ONE staging upload, the launches, ONE download and ONE synchronisation per call.  A call with
+ * few items and many train rows spreads ranges of train rows over more work-groups and merges their candidates on the device;
+ * the order-free definition below makes the result the same bytes either way.
+ *
+ * Per query row q the two neighbours are the two smallest (Hamming distance, train row) pairs in lexicographic order: among equal
+ * distances the lower train row comes first, which is what OpenCV's batchDistance produces by visiting the train rows in ascending
+ * order with strict comparisons.  idx[2q], idx[2q+1] are their train rows (-1: no such neighbour), dist[2q], dist[2q+1] their
+ * distances as int (what DMatch::distance holds as a float; -1 where idx is -1).
+ *   good[q] = idx0 >= 0 && (idx1 < 0 || (d0 <= max_dist && (double)d0 <= (double)d1 * ratio))     (fp64, no contraction)
+ * so a train set of ONE row makes every query good whatever its distance (the reference's m.size() < 2), and an empty train set
+ * or an empty query set gives no pairs (the reference returns before it matches, :422-424).  There is no cross-check: several
+ * queries may take the same train row.  pair_query / pair_train list (q, idx0) of the good rows in query order, n_pairs of them:
+ * the reference appends (vkpids[q], vlmids[idx0]) for exactly these.  The reference's settings are desc_bytes = 32,
+ * max_dist = (int)(desc_bytes * 0.5 * 8.) = 128, ratio = 0.85.
+ * BFMatcher::knnMatch is restated from OpenCV's published source, not pinned against an OpenCV build.
+ *
+ * What stays on the host: the two frame walks that collect the rows and their ids (:391-420).
+ *
+ * OV2_EINVAL: NULL params / item / result / ctx, a negative count, a NULL array with a non-zero count, max_dist < 0, ratio negative
+ * or not finite.  OV2_EUNSUPPORTED: desc_bytes != 32, more than 65535 items, more than 2^31 - 1 query or train rows in a call.
+ * All of it is checked on the host before any device work (the inputs before the context, so a malformed input is reported
+ * without a device); nothing is modified then. */
+typedef struct {
+    int desc_bytes;              /* query.cols: 32                                                                           */
+    int max_dist;                /* maxdist: (int)(desc_bytes * 0.5 * 8.)                                                    */
+    double ratio;                /* 0.85                                                                                     */
+} ov2_knn_params;
+typedef struct {
+    int n_query, n_train;
+    const uint8_t *query;        /* desc_bytes per row                                                                       */
+    const uint8_t *train;
+} ov2_knn_item;
+typedef struct {
+    int *idx;                    /* 2 n_query: train rows of the nearest and the second nearest, -1 = none                   */
+    int *dist;                   /* 2 n_query: their Hamming distances, -1 where idx is -1                                   */
+    uint8_t *good;               /* n_query                                                                                  */
+    int *pair_query;             /* capacity n_query: the good query rows, ascending                                         */
+    int *pair_train;             /* capacity n_query: their nearest train rows                                               */
+    int n_pairs;
+} ov2_knn_result;
+/* one query / train pair: the batch form with one item, through the same code path */
+int ov2_knn_match(ov2_ctx *ctx, const ov2_knn_params *params, const ov2_knn_item *item, ov2_knn_result *result);
+/* items [0, n_items) with shared params (grid.y = item).  Per item the result equals ov2_knn_match on that item; an item with
+ * n_query == 0 or n_train == 0 is allowed and has n_pairs = 0. */
+int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items, const ov2_knn_item *items, ov2_knn_result *results);
+
 /* ==================================================================== */
 /* Absolute pose from 2D-3D matches (MultiViewGeometry::p3pRansac,      */
 /* src/multi_view_geometry.cpp:144-343, USE_OPENGV)                     */

@@ -191,6 +191,22 @@ class MatchResult(C.Structure):
                 ("n_matches", C.c_int)]
 
 
+class KnnParams(C.Structure):
+    """ov2_knn_params (LoopCloser::knnMatching)"""
+    _fields_ = [("desc_bytes", C.c_int), ("max_dist", C.c_int), ("ratio", C.c_double)]
+
+
+class KnnItem(C.Structure):
+    """ov2_knn_item"""
+    _fields_ = [("n_query", C.c_int), ("n_train", C.c_int), ("query", C.POINTER(C.c_uint8)), ("train", C.POINTER(C.c_uint8))]
+
+
+class KnnResult(C.Structure):
+    """ov2_knn_result"""
+    _fields_ = [("idx", C.POINTER(C.c_int)), ("dist", C.POINTER(C.c_int)), ("good", C.POINTER(C.c_uint8)),
+                ("pair_query", C.POINTER(C.c_int)), ("pair_train", C.POINTER(C.c_int)), ("n_pairs", C.c_int)]
+
+
 class P3PParams(C.Structure):
     """ov2_p3p_params"""
     _fields_ = [("mode", C.c_int), ("max_iterations", C.c_int), ("threshold", C.c_double), ("probability", C.c_double),
@@ -363,6 +379,8 @@ SIGNATURES = {
     "ov2_triangulate_keyframe_batch": (_i, [_vp, C.POINTER(TriParams), _i, C.POINTER(TriKeyframe), C.POINTER(TriResult)]),
     "ov2_match_to_map": (_i, [_vp, C.POINTER(MatchParams), C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
     "ov2_match_to_map_batch": (_i, [_vp, C.POINTER(MatchParams), _i, C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
+    "ov2_knn_match": (_i, [_vp, C.POINTER(KnnParams), C.POINTER(KnnItem), C.POINTER(KnnResult)]),
+    "ov2_knn_match_batch": (_i, [_vp, C.POINTER(KnnParams), _i, C.POINTER(KnnItem), C.POINTER(KnnResult)]),
     "ov2_p3p_ransac": (_i, [_vp, C.POINTER(P3PParams), C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_ransac_batch": (_i, [_vp, C.POINTER(P3PParams), _i, C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),

@@ -7,6 +7,7 @@
 #include "slam_gpu.hpp"
 #include "mapper.hpp"
 #include "multi_view_geometry.hpp"
+#include "loop_closer.hpp"
 // the adapters that are free functions: taking their addresses keeps their signatures checked
 static auto *const check_ceres_pnp = &ov2::ceresPnP;
 static auto *const check_p3p_ransac = &ov2::p3pRansac;
@@ -16,4 +17,9 @@ static auto const check_undist_maps = &ov2::CameraCalibration::setUndistMaps;
 static auto const check_rectify = &ov2::CameraCalibration::rectifyImage;
 static auto const check_rect_map = &ov2::CameraCalibration::rectMap;
 static auto const check_set_rect = &ov2::FrameTracker::setRectification;
-int main() { return check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
+// the loop closer's descriptor matching, both overloads
+static int (ov2::LoopCloser::*const check_knn)(ov2::Context &, const std::vector<uint8_t> &, const std::vector<int> &, const std::vector<uint8_t> &,
+                                               const std::vector<int> &, std::vector<std::pair<int, int>> &) const = &ov2::LoopCloser::knnMatching;
+static int (ov2::LoopCloser::*const check_knn_batch)(ov2::Context &, const std::vector<ov2::KnnMatchingInput> &,
+                                                     std::vector<std::vector<std::pair<int, int>>> &) const = &ov2::LoopCloser::knnMatching;
+int main() { return check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
