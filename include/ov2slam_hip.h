@@ -130,6 +130,8 @@ void *ov2_ctx_stream(ov2_ctx *ctx);        /* the hipStream_t, for event timing 
 #define OV2_LK_ACC_FLOAT_UI4       1
 #define OV2_OPT_BA_TRACE           13   /* 1: ov2_ba_solve / ov2_ba_solve_resident / ov2_xyz_ba_solve / each pass of ov2_local_ba record the
                                            iteration summaries of the solve (ov2_ba_get_trace); the batch entry point does not */
+#define OV2_OPT_LCKF_SCRATCH_KB    16   /* ov2_lckf_prepare*: device scratch (KiB) the batch forms may hold at a time; items are walked in chunks
+                                           that fit (at least one item per chunk).  Default 262144 (256 MiB); >= 1 */
 int  ov2_ctx_set_option(ov2_ctx *ctx, int option, int value);
 int  ov2_ctx_get_option(ov2_ctx *ctx, int option, int *value);
 
@@ -1095,6 +1097,80 @@ int ov2_knn_match(ov2_ctx *ctx, const ov2_knn_params *params, const ov2_knn_item
 /* items [0, n_items) with shared params (grid.y = item).  Per item the result equals ov2_knn_match on that item; an item with
  * n_query == 0 or n_train == 0 is allowed and has n_pairs = 0. */
 int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items, const ov2_knn_item *items, ov2_knn_result *results);
+
+/* ------------------------------------------------------------------ */
+/* Loop-closure keyframe preparation (LoopCloser::run,                  */
+/* src/loop_closer.cpp:86-144)                                          */
+/* ------------------------------------------------------------------ */
+/* What LoopCloser::run does with every new keyframe before the place recogniser sees it: a mask that is 255 everywhere with a
+ * cv::circle(mask, kp.px_, 2., 0, -1) at each keypoint whose map point already has a descriptor, FastFeatureDetector::create(20)
+ * ->detect on the whole raw left image under that mask, KeyPointsFilter::retainBest(vaddkps, 300), and BriefDescriptorExtractor::
+ * compute on what is left.  Integers throughout; every output is the same bytes whatever the call form and from run to run.
+ * Per item: a u8 image w x h, n_excl float points excl_xy (x, y), and the parameters below.
+ *   1 FAST    cv::FAST(img, threshold, nonmaxSuppression = true, TYPE_9_16).  threshold is clamped to [0, 255].  Candidates are
+ *             3 <= x < w-3, 3 <= y < h-3 (none when w < 7 or h < 7); a candidate is a corner when 9 contiguous pixels of its
+ *             16-pixel ring are all < v - threshold or all > v + threshold; its score is cornerScore<16>.  A corner survives when
+ *             its score is strictly greater than the scores of its eight neighbours (not a corner / outside the candidate range:
+ *             0).  The response is the score, 1 .. 255.
+ *   2 mask    a corner at (x, y) is dropped when the filled circle of some exclusion point covers the pixel: centre
+ *             (rint(px), rint(py)) (half to even), radius excl_radius, OpenCV's midpoint circle clipped to the image -- the pixels
+ *             ov2_set_mask paints.  A point with a non-finite coordinate paints nothing.
+ *   3 retain  KeyPointsFilter::retainBest(retain): retain < 0 keeps every corner, retain == 0 none; at most `retain` corners
+ *             left: all are kept (cut = 0); otherwise cut = the retain-th largest response and EVERY corner with response >= cut
+ *             is kept (std::nth_element + std::partition(>= ambiguous_response) as a set): ties at the cut are the normal case,
+ *             so n_kept > retain is.
+ *   4 BRIEF   compute() first removes keypoints outside [28, w-28) x [28, h-28) (runByImageBorder) -- AFTER retainBest, so fewer
+ *             than `retain` descriptors is normal -- and describes the rest with the context's pattern, exactly as
+ *             ov2_describe_brief does on the same image and integer points: kept_valid is that call's valid, kept_desc its rows
+ *             (32 zero bytes where valid == 0).
+ *   5 order   both lists are in raster order (y ascending, then x).  The reference's order is whatever libstdc++'s nth_element /
+ *             partition leave: a permutation of the same set (ov2slam_amd/host/loop_closer.hpp reproduces it on the host).
+ * Truncation is not an error: a list is cut at its capacity in raster order, the counts stay the true ones, and a slot's
+ * descriptor is written only when the slot exists.  Slots past min(count, capacity) are not written.
+ *
+ * What stays on the host: the frame walk that collects the exclusion points and the existing descriptors, and the cv::vconcat
+ * of the two descriptor sets.  The ORB fallback of a build without OPENCV_CONTRIB (cv::ORB::create(500, 1., 0)) is not covered.
+ * cv::FAST, KeyPointsFilter and BriefDescriptorExtractor::compute restated from OpenCV's published source, not pinned against an
+ * OpenCV build.
+ *
+ * The host forms do ONE staging upload, the launches, ONE download and ONE synchronisation.  Device scratch per item (the
+ * context's grow-only buffer): a u8 score map (w rounded up to 64, times h), a bit mask (w / 8 bytes per row), 16 B per row, a
+ * 1 KB histogram and 8 B per kept slot; the batch forms walk the items in chunks that fit OV2_OPT_LCKF_SCRATCH_KB (same bytes
+ * whatever the chunk size; still one synchronisation).
+ *
+ * OV2_EINVAL: a NULL argument (a list pointer may be NULL when its capacity or count is 0), a negative count or capacity,
+ * w or h < 1, stride < w, item_stride smaller than one image, excl_radius outside [0, 64] (the half-width table of the painter).
+ * OV2_EUNSUPPORTED: an image side of 2^15 or more (int16 coordinates), more than 65535 items.  All of it is checked on the host,
+ * the inputs before the context or the tracker's state; nothing is written then. */
+typedef struct { int threshold, retain, excl_radius; } ov2_lckf_params;      /* reference: 20, 300, 2 */
+int ov2_lckf_params_init(ov2_lckf_params *out);
+typedef struct {
+    int n_all;            /* corners after NMS and mask filter (true count, may exceed all_cap)           */
+    int cut;              /* the retain-th largest response, 0 when nothing was cut                        */
+    int n_kept;           /* retained corners (true count, may exceed kept_cap)                            */
+    int n_desc;           /* of those, inside the BRIEF border (valid == 1)                                */
+    int16_t *all_xy; uint8_t *all_resp; int all_cap;      /* optional (NULL / 0): the pre-retain list, raster order */
+    int16_t *kept_xy; uint8_t *kept_resp; uint8_t *kept_valid; uint8_t *kept_desc; int kept_cap;  /* 32 B per slot */
+} ov2_lckf_result;
+/* host image (w x h, rows `stride` bytes apart), n_excl host points (x, y) */
+int ov2_lckf_prepare(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stride, const ov2_lckf_params *params,
+                     const float *excl_xy_h, int n_excl, ov2_lckf_result *result);
+/* the RAW frame of the tracker's current frame, the one ov2_tracker_describe_brief reads: no image upload */
+int ov2_tracker_lckf_prepare(ov2_tracker *t, const ov2_lckf_params *params, const float *excl_xy_h, int n_excl,
+                             ov2_lckf_result *result);
+/* n_items device images `item_stride` bytes apart (rows `pitch` bytes apart); device exclusion points, excl_cap slots per item,
+ * n_excl_d[b] of them valid (counts above excl_cap are taken as excl_cap; n_excl_d may be NULL when excl_cap == 0); device outputs
+ * in slot layouts: all_* all_cap slots per item (may be NULL / 0), kept_* kept_cap slots per item, counts_d 4 ints per item
+ * {n_all, cut, n_kept, n_desc}.  Synchronises once. */
+int ov2_lckf_prepare_batch_d(ov2_ctx *ctx, const ov2_lckf_params *params, const uint8_t *img_d, int w, int h, int pitch,
+                             size_t item_stride, int n_items, const float *excl_xy_d, int excl_cap, const int *n_excl_d,
+                             int16_t *all_xy_d, uint8_t *all_resp_d, int all_cap, int16_t *kept_xy_d, uint8_t *kept_resp_d,
+                             uint8_t *kept_valid_d, uint8_t *kept_desc_d, int kept_cap, int *counts_d);
+/* the raw frames of the current lock-step step, items [0, n_active): host exclusion points with excl_cap slots per item
+ * (n_excl_h[b] valid), one result per item (capacities may differ).  OV2_EINVAL once the staging set that held those frames has
+ * been uploaded or prepared again, as for ov2_btracker_describe_brief: in the look-ahead loop, call right after the step. */
+int ov2_btracker_lckf_prepare(ov2_btracker *t, int n_active, const ov2_lckf_params *params, const float *excl_xy_h,
+                              const int *n_excl_h, int excl_cap, ov2_lckf_result *results);
 
 /* ==================================================================== */
 /* Absolute pose from 2D-3D matches (MultiViewGeometry::p3pRansac,      */

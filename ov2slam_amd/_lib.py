@@ -25,6 +25,7 @@ OV2_OPT_FAST_TIE = 12
 OV2_OPT_BA_TRACE = 13
 OV2_OPT_LK_ACC = 14
 OV2_OPT_DETECT_STRIP = 15
+OV2_OPT_LCKF_SCRATCH_KB = 16
 OV2_LK_ACC_INT64, OV2_LK_ACC_FLOAT_UI4 = 0, 1
 OV2_FAST_TIE_SCAN_ORDER, OV2_FAST_TIE_LIBSTDCXX = 0, 1
 OV2_LK_IMPL_AUTO, OV2_LK_IMPL_ROW, OV2_LK_IMPL_LANE3 = 0, 1, 2
@@ -207,6 +208,19 @@ class KnnResult(C.Structure):
                 ("pair_query", C.POINTER(C.c_int)), ("pair_train", C.POINTER(C.c_int)), ("n_pairs", C.c_int)]
 
 
+class LckfParams(C.Structure):
+    """ov2_lckf_params (LoopCloser::run's keyframe preparation)"""
+    _fields_ = [("threshold", C.c_int), ("retain", C.c_int), ("excl_radius", C.c_int)]
+
+
+class LckfResult(C.Structure):
+    """ov2_lckf_result"""
+    _fields_ = [("n_all", C.c_int), ("cut", C.c_int), ("n_kept", C.c_int), ("n_desc", C.c_int),
+                ("all_xy", C.POINTER(C.c_int16)), ("all_resp", C.POINTER(C.c_uint8)), ("all_cap", C.c_int),
+                ("kept_xy", C.POINTER(C.c_int16)), ("kept_resp", C.POINTER(C.c_uint8)), ("kept_valid", C.POINTER(C.c_uint8)),
+                ("kept_desc", C.POINTER(C.c_uint8)), ("kept_cap", C.c_int)]
+
+
 class P3PParams(C.Structure):
     """ov2_p3p_params"""
     _fields_ = [("mode", C.c_int), ("max_iterations", C.c_int), ("threshold", C.c_double), ("probability", C.c_double),
@@ -381,6 +395,12 @@ SIGNATURES = {
     "ov2_match_to_map_batch": (_i, [_vp, C.POINTER(MatchParams), _i, C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
     "ov2_knn_match": (_i, [_vp, C.POINTER(KnnParams), C.POINTER(KnnItem), C.POINTER(KnnResult)]),
     "ov2_knn_match_batch": (_i, [_vp, C.POINTER(KnnParams), _i, C.POINTER(KnnItem), C.POINTER(KnnResult)]),
+    "ov2_lckf_params_init": (_i, [C.POINTER(LckfParams)]),
+    "ov2_lckf_prepare": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LckfParams), _vp, _i, C.POINTER(LckfResult)]),
+    "ov2_tracker_lckf_prepare": (_i, [_vp, C.POINTER(LckfParams), _vp, _i, C.POINTER(LckfResult)]),
+    "ov2_lckf_prepare_batch_d": (_i, [_vp, C.POINTER(LckfParams), _vp, _i, _i, _i, C.c_size_t, _i, _vp, _i, _vp,
+                                      _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ov2_btracker_lckf_prepare": (_i, [_vp, _i, C.POINTER(LckfParams), _vp, _vp, _i, C.POINTER(LckfResult)]),
     "ov2_p3p_ransac": (_i, [_vp, C.POINTER(P3PParams), C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_ransac_batch": (_i, [_vp, C.POINTER(P3PParams), _i, C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),

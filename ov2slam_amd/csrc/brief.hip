@@ -122,8 +122,8 @@ static int brief_pattern_d(ov2_ctx *ctx, const int **out)
     return OV2_OK;
 }
 
-static int brief_launch(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
-                        const float *xy_d, int cap, const int *n_d, int n_all, uint8_t *desc_d, uint8_t *valid_d)
+int ov2_brief_launch_d(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
+                       const float *xy_d, int cap, const int *n_d, int n_all, uint8_t *desc_d, uint8_t *valid_d)
 {
     const int *pat = nullptr;
     int rc = brief_pattern_d(ctx, &pat);
@@ -178,7 +178,7 @@ int ov2_brief_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, in
         memcpy(hblk + o_xy + 8 * (size_t)b * cap, xy_h + 2 * (size_t)b * cap, 8 * (size_t)nn[b]);
     }
     OV2_HIP_CHECK(hipMemcpyAsync(dblk, hblk, o_desc, hipMemcpyHostToDevice, ctx->stream));
-    rc = brief_launch(ctx, img_d, w, h, pitch, item_stride, n_items, (const float *)(dblk + o_xy), cap, (const int *)(dblk + o_n), 0,
+    rc = ov2_brief_launch_d(ctx, img_d, w, h, pitch, item_stride, n_items, (const float *)(dblk + o_xy), cap, (const int *)(dblk + o_n), 0,
                       dblk + o_desc, dblk + o_valid);
     if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipMemcpyAsync(hblk + o_desc, dblk + o_desc, blk - o_desc, hipMemcpyDeviceToHost, ctx->stream));
@@ -230,7 +230,7 @@ int ov2_describe_brief_batch_d(ov2_ctx *ctx, const uint8_t *img_d, int w, int h,
     if (cap == 0) return OV2_OK;
     OV2_REQUIRE(img_d && xy_d && desc_d && valid_d, OV2_EINVAL, "NULL device buffer");
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = brief_launch(ctx, img_d, w, h, (size_t)pitch, item_stride, n_items, xy_d, cap, n_d, cap, desc_d, valid_d);
+    rc = ov2_brief_launch_d(ctx, img_d, w, h, (size_t)pitch, item_stride, n_items, xy_d, cap, n_d, cap, desc_d, valid_d);
     if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return OV2_OK;

@@ -70,6 +70,7 @@ struct ov2_ctx {
     // ov2_local_ba_batch: persistent host threads that prepare the problems of a batch (created with the first batch; ba.hip owns the type)
     void *ba_host_pool = nullptr; void (*ba_host_pool_free)(void *) = nullptr;
     hipEvent_t ba_ev[2] = {nullptr, nullptr};              // the two timing events of a solve (created with the first one: a pair per pass was 25 us)
+    int lckf_scratch_kb = 256 * 1024;          // OV2_OPT_LCKF_SCRATCH_KB: device scratch one chunk of ov2_lckf_prepare* items may take
     int debug = 0;                             // OV2_OPT_DEBUG; initial value: environment OV2_DEBUG, read once by ov2_ctx_create
     // pinned staging of host images on their way to the device: its own buffer (h_scratch is rewritten by the next call's small
     // arrays while an asynchronous image upload may still be in flight) and an event that says when it may be refilled
@@ -163,6 +164,17 @@ int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur,
 // synchronisation; the kernel is enqueued on ctx->stream after everything already there (so after the frame's H2D of a tracker).
 int ov2_brief_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
                     const float *xy_h, const int *n_h, int n_h_all, int cap, uint8_t *desc_h, uint8_t *valid_h);
+
+// k_brief32 on device points, enqueued on ctx->stream with no synchronisation (the context's pattern: uploaded first when it changed):
+// n_items images item_stride apart, cap point slots per item, n_d[b] of them live (NULL: n_all each)
+int ov2_brief_launch_d(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
+                       const float *xy_d, int cap, const int *n_d, int n_all, uint8_t *desc_d, uint8_t *valid_d);
+
+// the loop closer's keyframe preparation (lckf.hip) on items [0, n_items) of a device image batch, or on one host image (img_h != NULL:
+// uploaded to the context's scratch first, img_d is ignored): host exclusion points with excl_cap slots per item, one result per item.
+// ONE upload, ONE download, ONE host synchronisation; the inputs are checked before the context is touched.
+int ov2_lckf_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
+                   const ov2_lckf_params *params, const float *excl_xy_h, const int *n_excl_h, int excl_cap, ov2_lckf_result *results);
 
 // cv::cornerSubPix (detect.hip, k_corner_subpix) on device points, one wavefront per point slot: `items` images img_item_stride bytes
 // apart, n slots per item xy_item_stride points apart; n_dev (ints ndev_item_stride apart) holds each item's live count on the

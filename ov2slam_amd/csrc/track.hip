@@ -338,6 +338,14 @@ int ov2_tracker_describe_brief(ov2_tracker *t, const float *xy_h, int n, uint8_t
     OV2_REQUIRE(t->frames >= 1, OV2_EINVAL, "describeBRIEF needs a preprocessed frame");
     return ov2_brief_run_h(t->ctx, nullptr, t->dimg, t->cfg.w, t->cfg.h, t->img_pitch, 0, 1, xy_h, nullptr, n, n, desc_h, valid_h);
 }
+// LoopCloser::run's keyframe preparation on the same raw frame
+int ov2_tracker_lckf_prepare(ov2_tracker *t, const ov2_lckf_params *params, const float *excl_xy_h, int n_excl, ov2_lckf_result *result)
+{
+    OV2_REQUIRE(t && result, OV2_EINVAL, "NULL tracker / result");
+    OV2_REQUIRE(n_excl >= 0, OV2_EINVAL, "negative count (n_excl)");
+    OV2_REQUIRE(t->frames >= 1, OV2_EINVAL, "the keyframe preparation needs a preprocessed frame");
+    return ov2_lckf_run_h(t->ctx, nullptr, t->dimg, t->cfg.w, t->cfg.h, t->img_pitch, 0, 1, params, excl_xy_h, &n_excl, n_excl, result);
+}
 int ov2_tracker_uses_graph(const ov2_tracker *t) { return t && t->graph_ok ? 1 : 0; }
 
 int ov2_tracker_preprocess(ov2_tracker *t, const uint8_t *img_h, int stride)

@@ -615,6 +615,21 @@ int ov2_btracker_describe_brief(ov2_btracker *t, int n_active, const float *xy_h
     return OV2_OK;
 }
 
+int ov2_btracker_lckf_prepare(ov2_btracker *t, int n_active, const ov2_lckf_params *params, const float *excl_xy_h, const int *n_excl_h,
+                              int excl_cap, ov2_lckf_result *results)
+{
+    OV2_REQUIRE(t && n_excl_h && results, OV2_EINVAL, "NULL argument");
+    OV2_REQUIRE(t->raw_which >= 0, OV2_EINVAL, "keyframe preparation: no current frames (no step yet, or their staging set was uploaded / prepared again)");
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->raw_n, OV2_EINVAL, "n_active exceeds the items of the current step");
+    const int which = t->raw_which;
+    const int rc = ov2_lckf_run_h(t->ctx, nullptr, t->dimg[which], t->cfg.w, t->cfg.h, t->img_pitch, t->img_bytes, n_active, params, excl_xy_h,
+                                  n_excl_h, excl_cap, results);
+    if (rc != OV2_OK) return rc;
+    // a later upload of this set on the copy stream orders itself after the reads (the call has synchronised: this costs nothing)
+    OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], t->ctx->stream));
+    return OV2_OK;
+}
+
 const ov2_pyr *ov2_btracker_cur_pyr(const ov2_btracker *t) { return t ? t->pyr[t->cur] : nullptr; }
 const ov2_pyr *ov2_btracker_prev_pyr(const ov2_btracker *t) { return t ? t->pyr[t->prev()] : nullptr; }
 int ov2_btracker_pyramid_sets(const ov2_btracker *t) { return t ? BT_SETS : 0; }

@@ -22,4 +22,10 @@ static int (ov2::LoopCloser::*const check_knn)(ov2::Context &, const std::vector
                                                const std::vector<int> &, std::vector<std::pair<int, int>> &) const = &ov2::LoopCloser::knnMatching;
 static int (ov2::LoopCloser::*const check_knn_batch)(ov2::Context &, const std::vector<ov2::KnnMatchingInput> &,
                                                      std::vector<std::vector<std::pair<int, int>>> &) const = &ov2::LoopCloser::knnMatching;
-int main() { return check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
+// the keyframe preparation, host image and tracker forms, and the host-side order helper
+static int (ov2::LoopCloser::*const check_lckf)(ov2::Context &, const ov2::Image8 &, const std::vector<ov2::Point2f> &, std::vector<ov2::Point2f> &,
+                                                std::vector<float> &, std::vector<uint8_t> &, ov2::LoopCloser::Order) const = &ov2::LoopCloser::detectAdditionalKeypoints;
+static int (ov2::LoopCloser::*const check_lckf_trk)(ov2_tracker *, const std::vector<ov2::Point2f> &, std::vector<ov2::Point2f> &,
+                                                    std::vector<float> &, std::vector<uint8_t> &, ov2::LoopCloser::Order) const = &ov2::LoopCloser::detectAdditionalKeypoints;
+static auto *const check_retain_order = &ov2::retainBestReferenceOrder;
+int main() { return check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
