@@ -1099,6 +1099,101 @@ int ov2_knn_match(ov2_ctx *ctx, const ov2_knn_params *params, const ov2_knn_item
 int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items, const ov2_knn_item *items, ov2_knn_result *results);
 
 /* ------------------------------------------------------------------ */
+/* Loop local-map tracking (LoopCloser::trackLoopLocalMap /             */
+/* LoopCloser::matchToMap, src/loop_closer.cpp:502-763)                 */
+/* ------------------------------------------------------------------ */
+/* The fourth stage of LoopCloser::processLoopCandidate: once P3P has put the new keyframe into the loop keyframe's frame, the 3-D
+ * points of the loop keyframe's neighbourhood are projected into the new keyframe and matched, by descriptor, with the map points
+ * of the keypoints around their projections.  A cousin of ov2_match_to_map with other gates and other arithmetic -- a different
+ * function of the reference, not a mode of that one.  One wavefront per local map point (csrc/loopmap.hip), ONE staging upload,
+ * two launches, ONE download and ONE synchronisation per call.
+ *
+ * Thresholds, once per call on the host in float as the reference writes them (:595-607, :656): hfov = (float)(0.5 * img_w * fx)
+ * -- MULTIPLIED by the focal length, and atan(hfov) in both branches of the reference's `if`, so vfov is never used --,
+ * view_th = (float)cos((float)atan(hfov)), each step taken in double and rounded to float (EuRoC: 5.797544e-06, i.e. the cone
+ * removes next to nothing); dmaxpxdist = fmax_proj_pxdist as given (the reference passes 10.); mindist = (float)(desc_bytes *
+ * fmax_desc_dist * 8.) (the reference passes fmax_desc_dist_ * 1.5 as a float).
+ * Per local map point l, in the caller's order, with wpt = lm_wpt[l] and A = lm_mp[l] (its row of the map-point table):
+ *   campt = Tcw wpt (Sophus SE3d * Vector3d; Tcw is the caller's Twc.inverse(), the P3P / PnP result, not the frame's pose);
+ *   campt.z < 0.1 -> BEHIND; view_angle = (float)(campt.z / |campt|), fabs(view_angle) < view_th -> OUT_OF_FOV; projpx =
+ *   projectCamToImageDist(campt) (as for ov2_match_to_map); outside [0, img_w) x [0, img_h) (or NaN) -> OUT_OF_IMAGE.
+ *   Candidates: the keypoints of cells r in {rkp-1, rkp}, c in {ckp-1, ckp}, rkp = floor(projpx.y / ncellsize), ckp alike (the 2x2
+ *   block of Frame::getSurroundingKeypoints(cv::Point2f); r < 0 or c < 0 skipped), cell index r * ceil(img_w / ncellsize) + c, in
+ *   that order and inside a cell in the order of cell_kp.  A candidate keypoint k is skipped when
+ *     kp_matched[k] != 0 (its lmid_ is in vmatchedkpids, :672-675), or kp_mp[k] < 0 or B = kp_mp[k] holds no descriptor, or
+ *     pxdist = (float)cv::norm(projpx - kp_px[k]) > dmaxpxdist, or
+ *     A and B share an observing keyframe id (obs_kfid).
+ *   Otherwise dist = the minimum Hamming distance over all (descriptor of A, descriptor of B) pairs, start value 1000;
+ *     dist <= bestdist: best -> second, k -> best;  else dist <= secdist: k -> second   (both start at mindist, id -1)
+ *   best and second both set and 0.9 * secdist < bestdist -> RATIO_REJECTED; no best -> NO_CANDIDATE; otherwise BEST: the point
+ *   proposes keypoint lm_kp[l] at lm_dist[l].
+ * There is no re-projection into the candidate's observers, no pose table, and the loop only reads the map: the flat form and the
+ * reference agree without any deviation.
+ * Per keypoint the proposing point with the smallest distance wins, among equals the one listed LAST in the local map (the
+ * reference's `<=`): kp_lm[k] / kp_dist[k]; kp_lm is the reference's map_previd_newid as (keypoint row -> local-map index).
+ * The pick is a 64-bit atomic minimum on (distance, reversed index), so a call's bytes do not depend on scheduling.
+ * lm_projpx is (0, 0) for BEHIND / OUT_OF_FOV points; lm_dist is the final bestdist (mindist when nothing qualified) and 0 for
+ * points that a gate removed; lm_kp is -1 unless BEST.
+ *
+ * What stays on the host: the covisible-keyframe walk that builds the local set and vmatchedkpids (:505-562; ov2slam_amd/host/
+ * loop_closer.hpp has it as loopLocalMapReferenceOrder), the filters that need the map's hash tables (isObservingKp, missing / 2-D
+ * / bad / descriptor-less points, :614-631), and appending the matches to vkplmids (:576-582).
+ *
+ * OV2_EINVAL: NULL params / item / result / ctx, a negative count, a NULL array with a non-zero count, kp_mp / lm_mp / cell_kp
+ * outside its table, offsets (cell_start, obs_start, desc_start) that do not start at 0 or decrease, obs_kfid not strictly
+ * ascending inside a row, img_w / img_h / ncellsize not positive.  OV2_EUNSUPPORTED: desc_bytes != 32, a coefficient count the model
+ * does not take, more than 65535 items, more than 2^31 - 1 elements of one kind in a call.  All of it is checked on the host
+ * before any device work (the inputs before the context, so a malformed input is reported without a device); nothing is
+ * modified then. */
+enum {
+    OV2_LOOPMAP_BEHIND = 1, OV2_LOOPMAP_OUT_OF_FOV = 2, OV2_LOOPMAP_OUT_OF_IMAGE = 4, OV2_LOOPMAP_NO_CANDIDATE = 8,
+    OV2_LOOPMAP_RATIO_REJECTED = 16, OV2_LOOPMAP_BEST = 32
+};
+typedef struct {
+    int model;                   /* OV2_CAM_PINHOLE / OV2_CAM_FISHEYE                                                        */
+    double K[4];                 /* fx fy cx cy                                                                              */
+    const double *D;             /* nD distortion coefficients (NULL when nD == 0)                                           */
+    int nD;
+    double img_w, img_h;         /* pcalib_leftcam_->img_w_ / img_h_                                                         */
+    int ncellsize;               /* Frame::ncellsize_                                                                        */
+    float fmax_proj_pxdist;      /* fmaxprojerr: the reference passes 10.                                                    */
+    float fmax_desc_dist;        /* fdistratio: the reference passes fmax_desc_dist_ * 1.5                                   */
+    int desc_bytes;              /* desc_.cols: 32                                                                           */
+} ov2_loopmap_params;
+typedef struct {
+    const double *Tcw;           /* 7: Twc.inverse() of the P3P / PnP result                                                 */
+    int n_kp;                    /* keypoints of the new keyframe                                                            */
+    const float *kp_px;          /* 2 n_kp: px_                                                                              */
+    const int *kp_mp;            /* n_kp: row of the map-point table, -1 = no usable map point                               */
+    const uint8_t *kp_matched;   /* n_kp: non-zero = the keypoint's lmid_ is in vmatchedkpids                                */
+    const int *cell_start;       /* ncells + 1 offsets into cell_kp, ncells = ceil(img_w / ncellsize) * ceil(img_h / ncellsize) */
+    const int *cell_kp;          /* keypoint rows, per cell in vgridkps_ order                                               */
+    int n_mp;                    /* rows of the map-point table (local map points and the keypoints' map points alike)       */
+    const int *obs_start;        /* n_mp + 1                                                                                 */
+    const int *obs_kfid;         /* per observation: keyframe id, strictly ascending inside a row                            */
+    const int *desc_start;       /* n_mp + 1                                                                                 */
+    const uint8_t *desc;         /* desc_bytes per descriptor: the map point's map_kf_desc_, any order                       */
+    int n_lm;                    /* local map points, in the caller's iteration order                                        */
+    const int *lm_mp;            /* n_lm: row of the map-point table                                                         */
+    const double *lm_wpt;        /* 3 n_lm                                                                                   */
+} ov2_loopmap_item;
+typedef struct {
+    uint8_t *lm_status;          /* n_lm: OV2_LOOPMAP_* bits                                                                 */
+    int *lm_kp;                  /* n_lm: proposed keypoint row or -1                                                        */
+    float *lm_dist;              /* n_lm                                                                                     */
+    float *lm_projpx;            /* 2 n_lm                                                                                   */
+    int *kp_lm;                  /* n_kp: the winning local-map index or -1                                                  */
+    float *kp_dist;              /* n_kp: its distance (0 where kp_lm == -1)                                                 */
+    int n_matches;               /* keypoints with kp_lm >= 0                                                                */
+} ov2_loopmap_result;
+/* one loop candidate: the batch form with one item, through the same code path */
+int ov2_loop_match_to_map(ov2_ctx *ctx, const ov2_loopmap_params *params, const ov2_loopmap_item *item, ov2_loopmap_result *result);
+/* items [0, n_items) with shared params (grid.y = item).  Per item the result equals ov2_loop_match_to_map on that item; an item
+ * without local map points or without keypoints is allowed. */
+int ov2_loop_match_to_map_batch(ov2_ctx *ctx, const ov2_loopmap_params *params, int n_items, const ov2_loopmap_item *items,
+                                ov2_loopmap_result *results);
+
+/* ------------------------------------------------------------------ */
 /* Loop-closure keyframe preparation (LoopCloser::run,                  */
 /* src/loop_closer.cpp:86-144)                                          */
 /* ------------------------------------------------------------------ */

@@ -35,6 +35,8 @@ OV2_MAP_F32, OV2_MAP_FIXED = 0, 1
 OV2_RES_LEFT, OV2_RES_RIGHT, OV2_RES_RIGHT_ANCH, OV2_RES_PNP = 0, 1, 2, 3
 OV2_TRI_STEREO_TRIED, OV2_TRI_STEREO_OK, OV2_TRI_TEMPORAL_TRIED, OV2_TRI_TEMPORAL_OK, OV2_TRI_NO_MOTION, OV2_TRI_REMOVE_OBS = 1, 2, 4, 8, 16, 32
 OV2_MATCH_BEHIND, OV2_MATCH_OUT_OF_FOV, OV2_MATCH_OUT_OF_IMAGE, OV2_MATCH_NO_CANDIDATE, OV2_MATCH_RATIO_REJECTED, OV2_MATCH_BEST = 1, 2, 4, 8, 16, 32
+OV2_LOOPMAP_BEHIND, OV2_LOOPMAP_OUT_OF_FOV, OV2_LOOPMAP_OUT_OF_IMAGE = 1, 2, 4
+OV2_LOOPMAP_NO_CANDIDATE, OV2_LOOPMAP_RATIO_REJECTED, OV2_LOOPMAP_BEST = 8, 16, 32
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -206,6 +208,29 @@ class KnnResult(C.Structure):
     """ov2_knn_result"""
     _fields_ = [("idx", C.POINTER(C.c_int)), ("dist", C.POINTER(C.c_int)), ("good", C.POINTER(C.c_uint8)),
                 ("pair_query", C.POINTER(C.c_int)), ("pair_train", C.POINTER(C.c_int)), ("n_pairs", C.c_int)]
+
+
+class LoopMapParams(C.Structure):
+    """ov2_loopmap_params (LoopCloser::matchToMap)"""
+    _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
+                ("img_h", C.c_double), ("ncellsize", C.c_int), ("fmax_proj_pxdist", C.c_float), ("fmax_desc_dist", C.c_float),
+                ("desc_bytes", C.c_int)]
+
+
+class LoopMapItem(C.Structure):
+    """ov2_loopmap_item"""
+    _fields_ = [("Tcw", C.POINTER(C.c_double)), ("n_kp", C.c_int), ("kp_px", C.POINTER(C.c_float)), ("kp_mp", C.POINTER(C.c_int)),
+                ("kp_matched", C.POINTER(C.c_uint8)), ("cell_start", C.POINTER(C.c_int)), ("cell_kp", C.POINTER(C.c_int)),
+                ("n_mp", C.c_int), ("obs_start", C.POINTER(C.c_int)), ("obs_kfid", C.POINTER(C.c_int)),
+                ("desc_start", C.POINTER(C.c_int)), ("desc", C.POINTER(C.c_uint8)), ("n_lm", C.c_int),
+                ("lm_mp", C.POINTER(C.c_int)), ("lm_wpt", C.POINTER(C.c_double))]
+
+
+class LoopMapResult(C.Structure):
+    """ov2_loopmap_result"""
+    _fields_ = [("lm_status", C.POINTER(C.c_uint8)), ("lm_kp", C.POINTER(C.c_int)), ("lm_dist", C.POINTER(C.c_float)),
+                ("lm_projpx", C.POINTER(C.c_float)), ("kp_lm", C.POINTER(C.c_int)), ("kp_dist", C.POINTER(C.c_float)),
+                ("n_matches", C.c_int)]
 
 
 class LckfParams(C.Structure):
@@ -395,6 +420,8 @@ SIGNATURES = {
     "ov2_match_to_map_batch": (_i, [_vp, C.POINTER(MatchParams), _i, C.POINTER(MatchKeyframe), C.POINTER(MatchResult)]),
     "ov2_knn_match": (_i, [_vp, C.POINTER(KnnParams), C.POINTER(KnnItem), C.POINTER(KnnResult)]),
     "ov2_knn_match_batch": (_i, [_vp, C.POINTER(KnnParams), _i, C.POINTER(KnnItem), C.POINTER(KnnResult)]),
+    "ov2_loop_match_to_map": (_i, [_vp, C.POINTER(LoopMapParams), C.POINTER(LoopMapItem), C.POINTER(LoopMapResult)]),
+    "ov2_loop_match_to_map_batch": (_i, [_vp, C.POINTER(LoopMapParams), _i, C.POINTER(LoopMapItem), C.POINTER(LoopMapResult)]),
     "ov2_lckf_params_init": (_i, [C.POINTER(LckfParams)]),
     "ov2_lckf_prepare": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LckfParams), _vp, _i, C.POINTER(LckfResult)]),
     "ov2_tracker_lckf_prepare": (_i, [_vp, C.POINTER(LckfParams), _vp, _i, C.POINTER(LckfResult)]),

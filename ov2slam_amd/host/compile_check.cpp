@@ -28,4 +28,12 @@ static int (ov2::LoopCloser::*const check_lckf)(ov2::Context &, const ov2::Image
 static int (ov2::LoopCloser::*const check_lckf_trk)(ov2_tracker *, const std::vector<ov2::Point2f> &, std::vector<ov2::Point2f> &,
                                                     std::vector<float> &, std::vector<uint8_t> &, ov2::LoopCloser::Order) const = &ov2::LoopCloser::detectAdditionalKeypoints;
 static auto *const check_retain_order = &ov2::retainBestReferenceOrder;
-int main() { return check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
+// the loop local-map tracking, both overloads, its settings and the host-side walk
+static int (ov2::LoopCloser::*const check_loopmap)(ov2::Context &, const ov2::LoopMapInput &, std::vector<std::pair<int, int>> &,
+                                                   ov2::LoopMapOutput *) const = &ov2::LoopCloser::trackLoopLocalMap;
+static int (ov2::LoopCloser::*const check_loopmap_batch)(ov2::Context &, const std::vector<ov2::LoopMapInput> &,
+                                                         std::vector<std::vector<std::pair<int, int>>> &,
+                                                         std::vector<ov2::LoopMapOutput> *) const = &ov2::LoopCloser::trackLoopLocalMap;
+static auto const check_set_loopmap = &ov2::LoopCloser::setLoopMapMatching;
+static auto *const check_loopmap_order = &ov2::loopLocalMapReferenceOrder;
+int main() { return check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }

@@ -11,8 +11,20 @@
 // filter, with their descriptors.  The library's lists are in raster order; Order::Reference reorders them on the host with the
 // literal std::nth_element / std::partition of KeyPointsFilter::retainBest (retainBestReferenceOrder below), which gives the
 // reference's keypoint order when both are built with the same libstdc++.
+//
+// And for the local-map tracking behind P3P (LoopCloser::trackLoopLocalMap / matchToMap, src/loop_closer.cpp:502-763) over
+// ov2_loop_match_to_map[_batch]: the caller flattens the new keyframe's keypoints and the local map (LoopMapInput), the call appends
+// (keypoint's lmid, local map point's lmid) of the matches to vkplmids in ascending keypoint id, exactly what :576-582 appends.  The
+// covisible-keyframe walk in front of it (:505-562) needs no device: loopLocalMapReferenceOrder below does it with literal
+// std::unordered_set inserts and erases, so the local map comes out in the iteration order the reference walks it in when both are
+// built with the same libstdc++ -- the order that decides which of two equally distant points keeps a keypoint.
 #pragma once
 #include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <unordered_set>
 #include "ov2_types.hpp"
 
 namespace ov2 {
@@ -40,6 +52,84 @@ inline void retainBestReferenceOrder(std::vector<LckfCorner> &keypoints, int n_p
                                             [ambiguous_response](const LckfCorner &k) { return k.response >= ambiguous_response; });
         keypoints.resize((size_t)(new_end - keypoints.begin()));
     }
+}
+
+// LoopCloser::matchToMap: the arrays of ov2_loopmap_item (include/ov2slam_hip.h) plus the ids the rows stand for
+struct LoopMapInput {
+    double Tcw[7] = {0, 0, 0, 0, 0, 0, 1};  // Twc.inverse() of the P3P / PnP result
+    std::vector<int> kp_lmid;           // n_kp: the keypoints' lmid_ (the keys of map_previd_newid)
+    std::vector<Point2f> kp_px;         // n_kp
+    std::vector<int> kp_mp;             // n_kp: row of the map-point table, -1 = no usable map point
+    std::vector<uint8_t> kp_matched;    // n_kp: non-zero = the keypoint's lmid_ is in vmatchedkpids
+    std::vector<int> cell_start, cell_kp;   // ncells + 1 offsets; keypoint rows per cell in vgridkps_ order
+    std::vector<int> obs_start;         // n_mp + 1
+    std::vector<int> obs_kfid;          // per observation: keyframe id, ascending inside a row
+    std::vector<int> desc_start;        // n_mp + 1
+    std::vector<uint8_t> desc;          // 32 per descriptor
+    std::vector<int> lm_lmid;           // n_lm: the local map points' ids, in iteration order (the values of map_previd_newid)
+    std::vector<int> lm_mp;             // n_lm: row of the map-point table
+    std::vector<double> lm_wpt;         // 3 n_lm
+};
+
+struct LoopMapOutput {
+    std::vector<uint8_t> lm_status;     // n_lm: OV2_LOOPMAP_* bits
+    std::vector<int> lm_kp;             // n_lm: proposed keypoint row or -1
+    std::vector<float> lm_dist, lm_projpx;   // n_lm, 2 n_lm
+    std::vector<int> kp_lm;             // n_kp: winning local-map index or -1
+    std::vector<float> kp_dist;         // n_kp
+    std::map<int, int> map_previd_newid;    // keypoint's lmid -> local map point's lmid
+};
+
+// one entry of lckf.getCovisibleKfMap() as the walk meets it: the keyframe id and the lmid_ of its getKeypoints3d(), in order;
+// kp3d_lmids == nullptr stands for pmap_->getKeyframe(kfid) == nullptr
+struct LoopCovisibleKeyframe { int kfid; const std::vector<int> *kp3d_lmids; };
+
+// The set-building walk of LoopCloser::trackLoopLocalMap (:505-562), literally: lccov in ascending keyframe id (std::map order;
+// the loop keyframe's own entry included, which the reference adds at :509), newkf_observes = newkf.isObservingKp.  Appends the
+// (lmid, lmid) pairs to vkplmids, fills vmatchedkpids (if given) and returns set_local_lmids in its iteration order.  Needs no device.
+inline std::vector<int> loopLocalMapReferenceOrder(int lckf_kfid, const std::vector<LoopCovisibleKeyframe> &lccov,
+                                                   const std::function<bool(int)> &newkf_observes,
+                                                   std::vector<std::pair<int, int>> &vkplmids, std::vector<int> *vmatchedkpids = nullptr)
+{
+    std::unordered_set<int> set_local_lmids, set_checked_kpids;
+    for (const LoopCovisibleKeyframe &cokf : lccov) {
+        const int kfid = cokf.kfid;
+        if (kfid < lckf_kfid - 15) {
+            continue;
+        } else if (kfid > lckf_kfid + 15) {
+            break;
+        }
+        if (cokf.kp3d_lmids == nullptr) {
+            continue;
+        }
+        for (const int lmid : *cokf.kp3d_lmids) {
+            auto it = set_checked_kpids.find(lmid);
+            if (it == set_checked_kpids.end()) {
+                set_checked_kpids.insert(lmid);
+                if (newkf_observes(lmid)) {
+                    std::pair<int, int> kplmid(lmid, lmid);
+                    auto kpit = std::find(vkplmids.begin(), vkplmids.end(), kplmid);
+                    if (kpit == vkplmids.end()) {
+                        vkplmids.push_back(kplmid);
+                    }
+                } else {
+                    set_local_lmids.insert(lmid);
+                }
+            }
+        }
+    }
+    if (vmatchedkpids) {
+        vmatchedkpids->clear();
+        vmatchedkpids->reserve(vkplmids.size());
+    }
+    for (const auto &kplmid : vkplmids) {
+        if (vmatchedkpids) vmatchedkpids->push_back(kplmid.first);
+        set_local_lmids.erase(kplmid.second);
+    }
+    std::vector<int> order;
+    order.reserve(set_local_lmids.size());
+    for (const int lmid : set_local_lmids) order.push_back(lmid);
+    return order;
 }
 
 class LoopCloser {
@@ -98,9 +188,106 @@ public:
     // the settings of FastFeatureDetector::create(20), retainBest(vaddkps, 300) and cv::circle(mask, px, 2., 0, -1)
     void setKeyframePreparation(int threshold, int retain, int excl_radius) { lp_.threshold = threshold; lp_.retain = retain; lp_.excl_radius = excl_radius; }
 
+    // what trackLoopLocalMap needs: the left camera's model (OV2_CAM_*) / K / distortion vector / image size, Frame::ncellsize_, and
+    // maxdist / ratio as processLoopCandidate passes them (10. and (float)(fmax_desc_dist_ * 1.5), fmax_desc_dist_ = 0.2 by default)
+    void setLoopMapMatching(int model, const double K[4], const double *D, int nD, double img_w, double img_h, int ncellsize,
+                            float fmaxprojerr = 10.f, float fdistratio = (float)(0.2 * 1.5))
+    {
+        std::memset(&mp_, 0, sizeof(mp_));
+        mp_.model = model; std::memcpy(mp_.K, K, sizeof(mp_.K));
+        md_.assign(D, D + (nD > 0 ? nD : 0));
+        mp_.nD = nD; mp_.img_w = img_w; mp_.img_h = img_h; mp_.ncellsize = ncellsize;
+        mp_.fmax_proj_pxdist = fmaxprojerr; mp_.fmax_desc_dist = fdistratio; mp_.desc_bytes = 32;
+        has_loopmap_ = true;
+    }
+    // LoopCloser::matchToMap of one loop candidate and the append :576-582 (one upload, one synchronisation): (kp_lmid, lm_lmid) of
+    // the matches go to the end of vkplmids in ascending keypoint id.  OV2_OK or the library's error (OV2_EINVAL before
+    // setLoopMapMatching), in which case vkplmids and *out are left as they were.
+    int trackLoopLocalMap(Context &ctx, const LoopMapInput &in, std::vector<std::pair<int, int>> &vkplmids, LoopMapOutput *out = nullptr) const
+    {
+        std::vector<LoopMapOutput> o(1);
+        const int rc = runLoopMap(ctx, &in, 1, o.data());
+        if (rc != OV2_OK) return rc;
+        for (const auto &e : o[0].map_previd_newid) vkplmids.emplace_back(e.first, e.second);
+        if (out) *out = std::move(o[0]);
+        return OV2_OK;
+    }
+    // several candidates in one call: vkplmids[b] is appended to as the single form does for item b (the vector is grown to
+    // in.size() entries)
+    int trackLoopLocalMap(Context &ctx, const std::vector<LoopMapInput> &in, std::vector<std::vector<std::pair<int, int>>> &vkplmids,
+                          std::vector<LoopMapOutput> *out = nullptr) const
+    {
+        std::vector<LoopMapOutput> o(in.size());
+        const int rc = runLoopMap(ctx, in.data(), in.size(), o.data());
+        if (rc != OV2_OK) return rc;
+        if (vkplmids.size() < in.size()) vkplmids.resize(in.size());
+        for (size_t b = 0; b < in.size(); b++)
+            for (const auto &e : o[b].map_previd_newid) vkplmids[b].emplace_back(e.first, e.second);
+        if (out) *out = std::move(o);
+        return OV2_OK;
+    }
+
 private:
     ov2_knn_params kp_ = {};
     ov2_lckf_params lp_ = {20, 300, 2};
+    ov2_loopmap_params mp_ = {};
+    std::vector<double> md_;
+    bool has_loopmap_ = false;
+
+    static const float *fp(const std::vector<Point2f> &v) { return v.empty() ? nullptr : &v[0].x; }
+    template <class T> static const T *dp(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+
+    static bool loopmap_sizes_ok(const LoopMapInput &k)
+    {
+        const size_t n_kp = k.kp_lmid.size(), n_lm = k.lm_lmid.size();
+        if (k.kp_px.size() != n_kp || k.kp_mp.size() != n_kp || k.kp_matched.size() != n_kp) return false;
+        if (k.lm_mp.size() != n_lm || k.lm_wpt.size() != 3 * n_lm || k.obs_start.size() != k.desc_start.size()) return false;
+        if (!k.obs_start.empty() && (k.obs_start.back() < 0 || k.desc_start.back() < 0)) return false;
+        const size_t n_ob = k.obs_start.empty() ? 0 : (size_t)k.obs_start.back(), n_de = k.desc_start.empty() ? 0 : (size_t)k.desc_start.back();
+        if (k.obs_kfid.size() != n_ob || k.desc.size() != 32 * n_de) return false;
+        if (!k.cell_start.empty() && (k.cell_start.back() < 0 || k.cell_kp.size() != (size_t)k.cell_start.back())) return false;
+        return n_kp <= 0x7fffffff && n_lm <= 0x7fffffff && k.obs_start.size() <= 0x7fffffff;
+    }
+
+    int runLoopMap(Context &ctx, const LoopMapInput *in, size_t n_items, LoopMapOutput *out) const
+    {
+        static_assert(sizeof(Point2f) == 2 * sizeof(float), "Point2f must be two packed floats");
+        if (!has_loopmap_ || n_items > 0x7fffffff) return OV2_EINVAL;
+        ov2_loopmap_params mp = mp_;
+        mp.D = md_.empty() ? nullptr : md_.data();
+        std::vector<ov2_loopmap_item> items(n_items);
+        std::vector<ov2_loopmap_result> res(n_items);
+        for (size_t b = 0; b < n_items; b++) {
+            const LoopMapInput &k = in[b];
+            if (!loopmap_sizes_ok(k)) return OV2_EINVAL;
+            // the library reads ncells + 1 offsets: a cell table of another length is the caller's error, not a read past the end
+            const size_t nbw = (size_t)std::ceil((float)mp.img_w / (float)mp.ncellsize), nbh = (size_t)std::ceil((float)mp.img_h / (float)mp.ncellsize);
+            if (!k.cell_start.empty() && k.cell_start.size() != nbw * nbh + 1) return OV2_EINVAL;
+            if (k.cell_start.empty() && !k.kp_lmid.empty()) return OV2_EINVAL;
+            ov2_loopmap_item &s = items[b];
+            s.Tcw = k.Tcw;
+            s.n_kp = (int)k.kp_lmid.size(); s.kp_px = fp(k.kp_px); s.kp_mp = dp(k.kp_mp); s.kp_matched = dp(k.kp_matched);
+            s.cell_start = dp(k.cell_start); s.cell_kp = dp(k.cell_kp);
+            s.n_mp = k.obs_start.empty() ? 0 : (int)k.obs_start.size() - 1;
+            s.obs_start = dp(k.obs_start); s.obs_kfid = dp(k.obs_kfid); s.desc_start = dp(k.desc_start); s.desc = dp(k.desc);
+            s.n_lm = (int)k.lm_lmid.size(); s.lm_mp = dp(k.lm_mp); s.lm_wpt = dp(k.lm_wpt);
+            LoopMapOutput &o = out[b];
+            const size_t n_lm = k.lm_lmid.size(), n_kp = k.kp_lmid.size();
+            o.lm_status.assign(n_lm, 0); o.lm_kp.assign(n_lm, -1); o.lm_dist.assign(n_lm, 0.f); o.lm_projpx.assign(2 * n_lm, 0.f);
+            o.kp_lm.assign(n_kp, -1); o.kp_dist.assign(n_kp, 0.f);
+            ov2_loopmap_result &r = res[b];
+            r.lm_status = o.lm_status.data(); r.lm_kp = o.lm_kp.data(); r.lm_dist = o.lm_dist.data(); r.lm_projpx = o.lm_projpx.data();
+            r.kp_lm = o.kp_lm.data(); r.kp_dist = o.kp_dist.data(); r.n_matches = 0;
+        }
+        const int rc = ov2_loop_match_to_map_batch(ctx.get(), &mp, (int)n_items, items.data(), res.data());
+        if (rc != OV2_OK) return rc;
+        for (size_t b = 0; b < n_items; b++) {                      // :743-760: keypoint's map point -> local map point, a std::map
+            out[b].map_previd_newid.clear();
+            for (size_t i = 0; i < in[b].kp_lmid.size(); i++)
+                if (out[b].kp_lm[i] >= 0) out[b].map_previd_newid.emplace(in[b].kp_lmid[i], in[b].lm_lmid[(size_t)out[b].kp_lm[i]]);
+        }
+        return OV2_OK;
+    }
 
     template <class Call>
     int lckf(Order order, std::vector<Point2f> &out_px, std::vector<float> &out_resp, std::vector<uint8_t> &out_desc, Call call) const
