@@ -75,6 +75,14 @@ void *ov2_ctx_stream(ov2_ctx *ctx);        /* the hipStream_t, for event timing 
  * (its entry points are called from several threads of a host process that may call setenv concurrently).
  * OV2_OPT_LK_IMPL           ov2_fb_klt* / ov2_lk_track with the reference's window (9): AUTO picks the 3-lanes-per-keypoint kernel
  *                           (lk3.hip) from 65536 points per call on, the row-per-lane kernel (lk.hip) below
+ * OV2_OPT_LK_PERSIST        the 3-lanes-per-keypoint kernel's launch form.  -1 (default): launches of more keypoint blocks than the device
+ *                           holds work-groups at once run persistent -- a small kernel lists the (item, block) pairs that hold a
+ *                           keypoint, and one round of resident work-groups pulls them until none is left; smaller launches keep
+ *                           one work-group per block.  0: always one work-group per block.  N > 0: always persistent, with exactly N
+ *                           work-groups (tests, A/B measurements).  Results do not depend on it
+ *                           The unit lists live in a buffer of the context that grows (is freed and allocated again) when a
+ *                           launch needs more room than any before it.  A captured graph keeps the pointer it was captured with:
+ *                           make the largest launch once BEFORE capturing, as for every grow-only buffer of a context
  * OV2_OPT_TRACK_IMPL        ov2_tracker_* / ov2_stereo_match, window 9: wavefront per keypoint (lkw.hip, default) or row per lane
  * OV2_OPT_CLAHE_STRIPS      ov2_pyr_build_clahe_*: the one-walk strip kernel (CLAHE apply + level 1 + borders): -1 auto (batch x
  *                           strips >= 1024: the fused form), 0 never, 1 whenever the geometry allows, after the LUT kernel,
@@ -109,6 +117,7 @@ void *ov2_ctx_stream(ov2_ctx *ctx);        /* the hipStream_t, for event timing 
 #define OV2_LK_IMPL_AUTO           0
 #define OV2_LK_IMPL_ROW            1
 #define OV2_LK_IMPL_LANE3          2
+#define OV2_OPT_LK_PERSIST         17
 #define OV2_OPT_TRACK_IMPL         3
 #define OV2_TRACK_IMPL_WAVE        0
 #define OV2_TRACK_IMPL_ROW         1

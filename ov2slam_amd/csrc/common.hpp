@@ -44,10 +44,15 @@ struct ov2_ctx {
     // (same-address device atomics retire at ~6 ns each: 2 per work-group on one address would put a
     // 200 us floor under a 16k-work-group launch); a one-block kernel folds the lines into the caller's pair.
     unsigned long long *stat_slots = nullptr;
+    // persistent k_fb_klt3 (lk3.hip): pull counters, list lengths and unit lists of one launch (lk_plan.hpp; grow-only, re-made by every
+    // launch on the stream) and the number of work-groups the device holds at once (0: not queried yet)
+    int *lk_plan = nullptr;  size_t lk_plan_ints = 0;
+    int lk_resident_wgs = 0;
     int sobel_dy_order = OV2_SOBEL_DY_OPENCV_ROWFILTER;   // ov2_ctx_set_option(OV2_OPT_SOBEL_DY_ORDER)
     // Path selection / test forcing (ov2_ctx_set_option, OV2_OPT_*).  The library reads NO environment variable after
     // ov2_ctx_create: the entry points are called from several threads of a host that may setenv() concurrently.
     int lk_impl = OV2_LK_IMPL_AUTO;            // OV2_OPT_LK_IMPL
+    int lk_persist = -1;                       // OV2_OPT_LK_PERSIST: -1 auto, 0 one work-group per keypoint block, N > 0 persistent with N work-groups
     int track_impl = OV2_TRACK_IMPL_WAVE;      // OV2_OPT_TRACK_IMPL
     int lk_acc = OV2_LK_ACC_INT64;             // OV2_OPT_LK_ACC
     int clahe_strips = -1;                     // OV2_OPT_CLAHE_STRIPS: -1 auto, 0 never, 1 whenever the geometry allows
@@ -79,6 +84,7 @@ struct ov2_ctx {
     int reserve_device(size_t bytes);
     int reserve_host(size_t bytes);
     int reserve_stat_slots();
+    int reserve_lk_plan(size_t ints);
     // host image (any row stride, pageable or pinned) -> device buffer with pitch dst_pitch, asynchronous on the stream; the
     // caller's buffer is free again when this returns
     int upload_image(void *dst_d, size_t dst_pitch, const uint8_t *src_h, size_t src_stride, size_t w, size_t h);

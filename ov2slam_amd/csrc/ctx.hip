@@ -145,6 +145,16 @@ int ov2_ctx::reserve_stat_slots()
     return OV2_OK;
 }
 
+int ov2_ctx::reserve_lk_plan(size_t ints)
+{
+    if (ints <= lk_plan_ints) return OV2_OK;
+    if (lk_plan) { OV2_HIP_CHECK(hipStreamSynchronize(stream)); OV2_HIP_CHECK(hipFree(lk_plan)); lk_plan = nullptr; lk_plan_ints = 0; }
+    const size_t cap = ints + ints / 2 + 1024;
+    OV2_HIP_CHECK(hipMalloc((void **)&lk_plan, cap * sizeof(int)));
+    lk_plan_ints = cap;
+    return OV2_OK;
+}
+
 int ov2_ctx_create(int device, ov2_ctx **out) { return ctx_create_common(device, nullptr, true, out); }
 
 int ov2_ctx_create_with_priority(int device, int priority, ov2_ctx **out) { return ctx_create_common(device, nullptr, true, out, priority); }
@@ -161,6 +171,7 @@ void ov2_ctx_destroy(ov2_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->stat_slots) (void)hipFree(ctx->stat_slots);
+    if (ctx->lk_plan) (void)hipFree(ctx->lk_plan);
     if (ctx->ba_det_pool) (void)hipFree(ctx->ba_det_pool);
     if (ctx->ba_trace_d) (void)hipFree(ctx->ba_trace_d);
     if (ctx->brief_pat_d) (void)hipFree(ctx->brief_pat_d);
@@ -194,6 +205,9 @@ int ov2_ctx_set_option(ov2_ctx *ctx, int option, int value)
     case OV2_OPT_LK_IMPL:
         OV2_REQUIRE(value >= OV2_LK_IMPL_AUTO && value <= OV2_LK_IMPL_LANE3, OV2_EINVAL, "unknown LK kernel choice");
         ctx->lk_impl = value; return OV2_OK;
+    case OV2_OPT_LK_PERSIST:
+        OV2_REQUIRE(value >= -1, OV2_EINVAL, "OV2_OPT_LK_PERSIST takes -1, 0 or a number of work-groups");
+        ctx->lk_persist = value; return OV2_OK;
     case OV2_OPT_TRACK_IMPL:
         OV2_REQUIRE(value == OV2_TRACK_IMPL_WAVE || value == OV2_TRACK_IMPL_ROW, OV2_EINVAL, "unknown tracker kernel choice");
         ctx->track_impl = value; return OV2_OK;
@@ -236,6 +250,7 @@ int ov2_ctx_get_option(ov2_ctx *ctx, int option, int *value)
     switch (option) {
     case OV2_OPT_SOBEL_DY_ORDER:     *value = ctx->sobel_dy_order; return OV2_OK;
     case OV2_OPT_LK_IMPL:            *value = ctx->lk_impl; return OV2_OK;
+    case OV2_OPT_LK_PERSIST:         *value = ctx->lk_persist; return OV2_OK;
     case OV2_OPT_TRACK_IMPL:         *value = ctx->track_impl; return OV2_OK;
     case OV2_OPT_CLAHE_STRIPS:       *value = ctx->clahe_strips; return OV2_OK;
     case OV2_OPT_BA_FORCE_LARGE:     *value = ctx->ba_force_large; return OV2_OK;

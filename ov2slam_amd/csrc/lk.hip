@@ -582,7 +582,7 @@ __global__ __launch_bounds__(LK_STAT_SLOTS) void k_lk_stats_fold(unsigned long l
 
 // ---- host side -------------------------------------------------------------------
 // lk3.hip: 3-lanes-per-keypoint kernel for the reference's window (9)
-int ov2_launch_fb_klt3(hipStream_t s, const PyrDesc &P, const PyrDesc &C, int max_level, int max_iter, double eps2,
+int ov2_launch_fb_klt3(ov2_ctx *ctx, const PyrDesc &P, const PyrDesc &C, int max_level, int max_iter, double eps2,
                        float min_eig_th, int flags, float err_th, float fb_dist, int do_fb, int n_max,
                        const float2 *kps, float2 *priors, uint8_t *status, float *err, int *iters,
                        const int *n_per_item, unsigned long long *stat_slots);
@@ -626,8 +626,8 @@ static int lk_dispatch(ov2_ctx *ctx, const ov2_pyr *prev, const ov2_pyr *cur, LK
     }
     // (the float-accumulator mode lives in the row kernel: the 3-lanes-per-keypoint kernel sums exact integers only)
     if (prm.win == 9 && ctx->lk_acc == OV2_LK_ACC_INT64 && !lk_use_row_kernel(ctx, (long long)prm.n_max * P.batch)) {
-        ov2_launch_fb_klt3(ctx->stream, P, C, prm.max_level, prm.max_iter, prm.eps2, prm.min_eig_th, prm.flags, prm.err_th,
-                           prm.fb_dist, prm.do_fb, prm.n_max, kps_d, priors_d, status_d, err_d, iters_d, n_per_item_d, slots);
+        if (int rc = ov2_launch_fb_klt3(ctx, P, C, prm.max_level, prm.max_iter, prm.eps2, prm.min_eig_th, prm.flags, prm.err_th,
+                                        prm.fb_dist, prm.do_fb, prm.n_max, kps_d, priors_d, status_d, err_d, iters_d, n_per_item_d, slots)) return rc;
         if (slots) hipLaunchKernelGGL(k_lk_stats_fold, dim3(1), dim3(LK_STAT_SLOTS), 0, ctx->stream, slots, stats_d);
         OV2_HIP_CHECK(hipGetLastError());
         return OV2_OK;

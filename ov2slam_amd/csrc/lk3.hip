@@ -19,8 +19,13 @@
 //     for nothing is gone from them: the v_perm selectors ride in SGPRs, the keypoint and the forward result wait in LDS
 //     (`keep`) while the levels run, lane-derived offsets are formed where they are used, and the template build has a
 //     straight-line instance with and one without the border masks.
+//   * Launches larger than one round of resident work-groups run PERSISTENT: k_lk_plan lists the (item, keypoint block) units
+//     that hold a keypoint (lk_plan.hpp), and as many work-groups as the GPU holds at once pull units from the list of their
+//     XCD until all lists are empty.  No work-group is launched for a block without keypoints, and the launch, the kernel
+//     arguments and the statistics' global atomics are paid once per resident slot instead of once per block.
 #include "common.hpp"
 #include "xcd_map.hpp"
+#include "lk_plan.hpp"
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
@@ -481,30 +486,105 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
     sl.bx0 = jx0; sl.by0 = jy0;
 }
 
+// work-group-wide hand-over of LDS values (one wavefront per work-group: no s_barrier)
+__device__ __forceinline__ void l3_wg_sync()
+{
+    if (L3_WAVES == 1) l3_lds_sync();
+    else __syncthreads();
+}
+
+// The unit plan of a persistent launch (lk_plan.hpp): one work-group per list, one thread per entry, a prefix sum over the
+// entries' unit counts.  Also resets the list's pull counter.
+__global__ __launch_bounds__(256) void k_lk_plan(const int *__restrict__ n_per_item, int n_all, int batch, int nbx, int *__restrict__ plan)
+{
+    __shared__ int s_wave[4];
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int *list = plan + OV2_LKP_UNITS + (long long)r * ov2_lkp_list_cap(batch, nbx);
+    const int entries = ov2_lkp_entries(batch);
+    int base = 0;
+    for (int j0 = 0; j0 < entries; j0 += 256) {
+        const int j = j0 + (int)threadIdx.x;
+        ov2_lkp_entry e = {0, 0, 1, 0};
+        if (j < entries) {
+            const int item = ov2_lkp_item(r, j, batch);
+            e = ov2_lkp_entry_of(r, j, batch, nbx, L3_KPB, n_per_item ? n_per_item[item] : n_all);
+        }
+        int incl = e.count;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int off = base + incl - e.count;
+        for (int w = 0; w < 4; w++) {
+            if (w < wave) off += s_wave[w];
+            base += s_wave[w];
+        }
+        for (int t = 0; t < e.count; t++) list[off + t] = ov2_lkp_pack(e.item, e.first + t * e.step, nbx);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { plan[OV2_LKP_LEN + r] = base; plan[r * OV2_LKP_CTR_STRIDE] = 0; }
+}
+
+// plan == nullptr: the direct form, work-group id -> unit through ov2_xcd_map, one unit per work-group (gridDim.x = nbx * batch).
+// Otherwise persistent: any number of work-groups, each pulling units (lk_plan.hpp) until every list is empty.
 __global__ __launch_bounds__(64 * L3_WAVES, L3_MIN_WAVES_PER_EU) void k_fb_klt3(PyrDesc P, PyrDesc C, LK3Params prm, int nbx,
                                                  const float2 *__restrict__ kps, float2 *__restrict__ priors,
                                                  uint8_t *__restrict__ status, float *__restrict__ err_out,
                                                  int *__restrict__ iters_out, const int *__restrict__ n_per_item,
-                                                 unsigned long long *__restrict__ stats)
+                                                 unsigned long long *__restrict__ stats, int *plan)
 {
     __shared__ __attribute__((aligned(16))) uint32_t lds[L3_KPB * L3_STRIDE];
-    __shared__ unsigned int s_stats[2];
+    __shared__ unsigned long long s_stats[2];                     // 64 bits: a persistent work-group adds up any number of units
+    __shared__ int s_pull;
     __shared__ __attribute__((aligned(16))) float keep[L3_KPB * L3_KEEP];
-    // XCD-aware work-group -> (batch item, keypoint block) map: the dispatcher deals consecutive work-group
-    // ids round-robin over the 8 XCDs, each with its own L2.  All blocks of one item (one image pair) are
-    // given ids of the same residue mod 8 and consecutive rank, so the image lines they share are fetched
-    // into one L2 only, and at about the same time.
-    int b, bx;
-    ov2_xcd_map(blockIdx.x, nbx, P.batch, &b, &bx);
-    const int n = n_per_item ? n_per_item[b] : prm.n_max;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l16 = lane & 15, g = l16 / 3, sub = l16 - 3 * g;
     const int kslot = wave * L3_KPW + (lane >> 4) * 5 + g;
-    const int i = bx * L3_KPB + kslot;
     if (stats) {
         if (threadIdx.x < 2) s_stats[threadIdx.x] = 0;
         __syncthreads();
     }
+    // Persistent form: work-group ids are dealt round-robin over the 8 XCDs, so list blockIdx.x & 7 is the one whose image
+    // lines this XCD's L2 holds; when it is exhausted the work-group takes from the following lists, so that ragged counts
+    // do not leave one XCD finishing alone.  `hop` (lists given up so far) and the unit are wave-uniform and live in SGPRs.
+    int hop = 0;
+    for (int round = 0;; round++) {
+    int b, bx;
+    if (plan) {
+        const int cap = ov2_lkp_list_cap(P.batch, nbx);
+        int unit = -1;
+        while (hop < OV2_LKP_LISTS) {
+            const int q = (blockIdx.x + hop) & (OV2_LKP_LISTS - 1);
+            int *ctr = plan + q * OV2_LKP_CTR_STRIDE;
+            const int len = plan[OV2_LKP_LEN + q];
+            // Thread 0 pulls and hands the index to the whole work-group through LDS (every wavefront then takes the same side).
+            // Another XCD's list gets a look before the pull -- a counter only grows, so a list seen exhausted stays exhausted --
+            // which spares the tail of the launch seven failing atomics per work-group; the own list is pulled straight away.
+            if (threadIdx.x == 0) {
+                int u = len;
+                if (hop == 0 || __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < len) u = (int)atomicAdd((unsigned int *)ctr, 1u);
+                s_pull = u;
+            }
+            l3_wg_sync();
+            const int u = __builtin_amdgcn_readfirstlane(s_pull);
+            l3_wg_sync();
+            if (u < len) { unit = plan[OV2_LKP_UNITS + (long long)q * cap + u]; break; }
+            hop++;
+        }
+        if (unit < 0) break;
+        ov2_lkp_unpack(unit, nbx, &b, &bx);
+    } else {
+        // XCD-aware work-group -> (batch item, keypoint block) map: the dispatcher deals consecutive work-group
+        // ids round-robin over the 8 XCDs, each with its own L2.  All blocks of one item (one image pair) are
+        // given ids of the same residue mod 8 and consecutive rank, so the image lines they share are fetched
+        // into one L2 only, and at about the same time.
+        if (round) break;
+        ov2_xcd_map(blockIdx.x, nbx, P.batch, &b, &bx);
+    }
+    const int n = n_per_item ? n_per_item[b] : prm.n_max;
+    const int i = bx * L3_KPB + kslot;
     if (l16 < 15 && i < n) {                                     // the 3 lanes of a keypoint take the same side
         uint32_t *slot = lds + kslot * L3_STRIDE;
         // What only the end of the walk needs -- the keypoint, and after the forward pass its result and counters -- waits in
@@ -586,20 +666,24 @@ __global__ __launch_bounds__(64 * L3_WAVES, L3_MIN_WAVES_PER_EU) void k_fb_klt3(
             if (err_out) err_out[gi] = err_fwd;
             if (iters_out) iters_out[gi] = acc_iters;
             if (stats) {
-                atomicAdd(&s_stats[0], (unsigned int)acc_iters);
-                atomicAdd(&s_stats[1], (unsigned int)acc_visits);
+                atomicAdd(&s_stats[0], (unsigned long long)acc_iters);
+                atomicAdd(&s_stats[1], (unsigned long long)acc_visits);
             }
         }
     }
+    l3_wg_sync();                                                  // the next unit's walk reuses lds[] and keep[]
+    }
+    // a work-group's statistics: accumulated over its units, two global atomics at its end
     if (stats) {
         __syncthreads();
         if (threadIdx.x < 2 && s_stats[threadIdx.x])
-            atomicAdd(&stats[(blockIdx.x & (LK_STAT_SLOTS - 1)) * LK_STAT_STRIDE + threadIdx.x], (unsigned long long)s_stats[threadIdx.x]);
+            atomicAdd(&stats[(blockIdx.x & (LK_STAT_SLOTS - 1)) * LK_STAT_STRIDE + threadIdx.x], s_stats[threadIdx.x]);
     }
 }
 
-// launcher used by lk.hip's dispatch for WIN == 9
-int ov2_launch_fb_klt3(hipStream_t s, const PyrDesc &P, const PyrDesc &C, int max_level, int max_iter, double eps2,
+// launcher used by lk.hip's dispatch for WIN == 9.  ctx->lk_persist (OV2_OPT_LK_PERSIST): -1 the persistent form for launches of
+// more than one round of resident work-groups, 0 never, N > 0 always, with N work-groups.
+int ov2_launch_fb_klt3(ov2_ctx *ctx, const PyrDesc &P, const PyrDesc &C, int max_level, int max_iter, double eps2,
                        float min_eig_th, int flags, float err_th, float fb_dist, int do_fb, int n_max,
                        const float2 *kps, float2 *priors, uint8_t *status, float *err, int *iters,
                        const int *n_per_item, unsigned long long *stats)
@@ -608,7 +692,28 @@ int ov2_launch_fb_klt3(hipStream_t s, const PyrDesc &P, const PyrDesc &C, int ma
     prm.max_level = max_level; prm.max_iter = max_iter; prm.eps2 = eps2; prm.min_eig_th = min_eig_th; prm.flags = flags;
     prm.err_th = err_th; prm.fb_dist = fb_dist; prm.do_fb = do_fb; prm.n_max = n_max;
     const int nbx = (n_max + L3_KPB - 1) / L3_KPB;
-    dim3 grid(nbx * P.batch);
-    hipLaunchKernelGGL(k_fb_klt3, grid, dim3(64 * L3_WAVES), 0, s, P, C, prm, nbx, kps, priors, status, err, iters, n_per_item, stats);
-    return 0;
+    const long long units = (long long)nbx * P.batch;
+    OV2_REQUIRE(units <= 0x7FFFFFFF, OV2_EINVAL, "LK launch has more than 2^31 - 1 keypoint blocks");
+    hipStream_t s = ctx->stream;
+    int grid = (int)units, *plan = nullptr;
+    bool persist = ctx->lk_persist > 0;
+    if (persist) grid = ctx->lk_persist;
+    else if (ctx->lk_persist < 0) {
+        if (!ctx->lk_resident_wgs) {                                // work-groups the device holds at once, queried once
+            int per_cu = 0, cus = 0;
+            OV2_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fb_klt3, 64 * L3_WAVES, 0));
+            OV2_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+            OV2_REQUIRE(per_cu > 0 && cus > 0, OV2_EHIP, "k_fb_klt3 does not fit the device");
+            ctx->lk_resident_wgs = per_cu * cus;
+        }
+        persist = units > ctx->lk_resident_wgs;
+        if (persist) grid = ctx->lk_resident_wgs;
+    }
+    if (persist) {
+        if (int rc = ctx->reserve_lk_plan((size_t)ov2_lkp_ints(P.batch, nbx))) return rc;
+        plan = ctx->lk_plan;
+        hipLaunchKernelGGL(k_lk_plan, dim3(OV2_LKP_LISTS), dim3(256), 0, s, n_per_item, n_max, P.batch, nbx, plan);
+    }
+    hipLaunchKernelGGL(k_fb_klt3, dim3(grid), dim3(64 * L3_WAVES), 0, s, P, C, prm, nbx, kps, priors, status, err, iters, n_per_item, stats, plan);
+    return OV2_OK;
 }
