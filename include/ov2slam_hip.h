@@ -1502,6 +1502,117 @@ int ov2_pose_graph_apply(ov2_ctx *ctx, int n_win, const double *win_old, const d
                          const double newopt_Twc[7], int n_young, const double *young_old, double *young_new, int n_pts,
                          const double *xyz, const int *pt_kf, double *xyz_out);
 
+/* ---- frame versus previous keyframe (fkf.hip): the per-frame keypoint passes of src/visual_front_end.cpp -------------------
+ *   ov2_parallax           VisualFrontEnd::computeParallax (:1066-1141) in the arithmetic of each of its three call sites
+ *   ov2_kf_decision        VisualFrontEnd::checkNewKfReq (:986-1061): the rule on parallax, occupied cells and 3-D counts
+ *   ov2_sampson_filter_2d  the Sampson pass over the 2-D keypoints after the 5-point search (:610-652)
+ * One item describes the current frame and the previous keyframe from host arrays.  Frame::getKeypointById is a device-side
+ * binary search of cur_lmid[i] in kf_lmid, which therefore has to be STRICTLY ASCENDING (the host does not join); landmark ids
+ * are non-negative in the reference, and a current id that the keyframe does not hold has "no counterpart".
+ * Poses are [tx ty tz qx qy qz qw] as the Frame holds them: kf_Tcw is the keyframe's own Tcw_, not re-derived from its Twc_.
+ *
+ * Parallax, for each current keypoint IN ARRAY ORDER (mapkps_ is an unordered_map: the caller's order is the only one there is):
+ *   skipped by the filter (ONLY_2D: :1096; ONLY_3D: :494-498) or without counterpart (:1104 / :505): continue;
+ *   unrot:  u = projectCamToImage(R bv) (camera_calibration.cpp:243-252), R = matrix(q of kf_Tcw) matrix(q of cur_Twc) (:1082-1084),
+ *           both by Eigen's toRotationMatrix from the quaternions as held, sums of three products serial ((a0 + a1) + a2);
+ *   else    u = cur_unpx[i];
+ *   d = cv::norm(u - kf_unpx[j]): the difference in float, sqrt((double)dx dx + (double)dy dy);
+ *   OV2_FKF_AVG / OV2_FKF_MEDIAN (:1117-1118): p = (float)d, sum += p in float;
+ *   OV2_FKF_AVG_WIDE (:517): sum = (float)((double)sum + d) -- it differs from the former in the last bit.
+ * The sum is serial in array order, not a tree.  Result: the averages are sum / (float)n, with n == 0 giving 0 (:1126) for AVG and
+ * MEDIAN and the 0.f / 0 NaN of :528 for AVG_WIDE.  MEDIAN: the reference inserts into a std::set<float>, so it is the element
+ * at index n_distinct / 2 of the DISTINCT values in ascending order, not the middle of the multiset.  n_distinct is 0 for the
+ * averages (the set stays empty).  A non-finite p is undefined behaviour in the reference's set: here it is counted in
+ * n_nonfinite, stays out of the distinct values, and with n_nonfinite > 0 the median is NaN; the averages carry the non-finite
+ * value through the float sum like the reference.
+ *
+ * Decision: parallax with (unrot = 1, OV2_FKF_ALL, OV2_FKF_MEDIAN).  nb3dkps / noccupcells of the item, or with -1 counted here:
+ * the cur_is3d flags set, and the distinct Frame::getKeypointCellIdx(cur_px) (frame.cpp:587-592: float division by ncellsize,
+ * floor, r nbwcells + c).  An index outside [0, nbwcells nbhcells) would make the reference's vgridkps_.at() throw: it is not
+ * counted and reported in n_out_of_grid (as is a row or column beyond +-2^20, or not finite).  The comparisons of :1005-1045 are
+ * the reference's, in double against its size_t / int / float operands.  `reason`: the early return that fired (OV2_KF_RET_*),
+ * or the bits of the final expression (c0 || c1 || c2) && cx.  With n_nonfinite > 0 the decision is 0 and reason
+ * OV2_KF_NONFINITE.
+ *
+ * Sampson pass: for every current keypoint with is3d == 0, err = computeSampsonDistance(Fkfcur, cur_unpx, kf_unpx) with the
+ * current point as leftpt, bad = err > fransac_err; 3-D keypoints get err = 0, bad = 0.  The reference does NOT check that the
+ * keyframe holds the keypoint (:633): a missing counterpart is scored against Keypoint()'s unpx_ = (0, 0), and so it is here.
+ * Fkfcur is the caller's (computeFundamentalMat12 in its own Eigen), row-major like the Frl of ov2_stereo_epipolar_check.
+ *
+ * Capacity: OV2_FKF_MAX_POINTS keypoints on either side, OV2_FKF_MAX_CELLS grid cells, 65535 items (OV2_EUNSUPPORTED beyond).
+ * OV2_EINVAL: a NULL argument or array (cur_px / cur_bv / cur_Twc / kf_Tcw are not read by the Sampson pass and may be NULL
+ * there), a negative count, kf_lmid not strictly ascending, ncellsize / nbwcells / nbhcells not positive (decision only).
+ * All of it is checked on the host before the context is touched; a rejected call writes nothing.  Each call is one upload, one
+ * launch, one download, one host synchronisation. */
+#define OV2_FKF_MAX_POINTS 2048
+#define OV2_FKF_MAX_CELLS 65536
+enum { OV2_FKF_ALL = 0, OV2_FKF_ONLY_2D = 1, OV2_FKF_ONLY_3D = 2 };
+enum { OV2_FKF_AVG = 0, OV2_FKF_MEDIAN = 1, OV2_FKF_AVG_WIDE = 2 };
+enum {
+    OV2_KF_C0 = 1, OV2_KF_C1 = 2, OV2_KF_C2 = 4, OV2_KF_CX = 8,     /* the final expression, :1036-1045                      */
+    OV2_KF_RET_FEW_CELLS = 16,                                      /* :1008, true                                           */
+    OV2_KF_RET_FEW_3D = 32,                                         /* :1015, true                                           */
+    OV2_KF_RET_MANY_3D = 64,                                        /* :1021, false                                          */
+    OV2_KF_RET_TIME = 128,                                          /* :1030, true                                           */
+    OV2_KF_NONFINITE = 256
+};
+typedef struct {
+    double K[4];                 /* fx fy cx cy of the left camera                                                           */
+    int ncellsize, nbwcells, nbhcells;   /* the Frame's grid (frame.cpp:66-69)                                               */
+    int nbmaxkps;                /* SlamParams::nbmaxkps_                                                                    */
+    float finit_parallax;        /* SlamParams::finit_parallax_                                                              */
+    int stereo;                  /* SlamParams::stereo_                                                                      */
+} ov2_fkf_params;
+typedef struct {
+    int n_cur;
+    const int *cur_lmid;         /* n_cur                                                                                    */
+    const float *cur_px;         /* 2 n_cur: Keypoint::px_                                                                   */
+    const float *cur_unpx;       /* 2 n_cur: Keypoint::unpx_                                                                 */
+    const double *cur_bv;        /* 3 n_cur: Keypoint::bv_                                                                   */
+    const uint8_t *cur_is3d;     /* n_cur                                                                                    */
+    const double *cur_Twc;       /* 7                                                                                        */
+    int n_kf;
+    const int *kf_lmid;          /* n_kf, strictly ascending                                                                 */
+    const float *kf_unpx;        /* 2 n_kf                                                                                   */
+    const double *kf_Tcw;        /* 7                                                                                        */
+    int cur_id, kf_id;           /* Frame::id_                                                                               */
+    double cur_time, kf_time;    /* Frame::img_time_                                                                         */
+    int kf_nb3dkps;              /* pkf->nb3dkps_                                                                            */
+    int localba_is_on;           /* SlamParams::blocalba_is_on_                                                              */
+    int noccupcells, nb3dkps;    /* of the current frame; -1: counted on the device from cur_px / cur_is3d                   */
+} ov2_fkf_item;
+typedef struct {
+    float parallax;
+    int n;                       /* keypoints that entered the statistic                                                     */
+    int n_distinct;              /* size of the reference's set (MEDIAN), 0 otherwise                                        */
+    int n_nonfinite;
+} ov2_parallax_result;
+typedef struct {
+    float parallax;
+    int n, n_distinct, n_nonfinite;
+    int noccupcells, nb3dkps;    /* as used by the rule: the item's, or counted                                              */
+    int n_out_of_grid;           /* 0 unless noccupcells was counted                                                         */
+    int decision;                /* 0 / 1: checkNewKfReq's return value                                                      */
+    int reason;                  /* OV2_KF_* bits                                                                            */
+} ov2_kf_decision_result;
+typedef struct {
+    float *err;                  /* n_cur                                                                                    */
+    uint8_t *bad;                /* n_cur                                                                                    */
+    int n_bad;
+} ov2_sampson2d_result;
+int ov2_parallax(ov2_ctx *ctx, const ov2_fkf_params *params, const ov2_fkf_item *item, int unrot, int filter, int stat,
+                 ov2_parallax_result *result);
+int ov2_parallax_batch(ov2_ctx *ctx, const ov2_fkf_params *params, int n_items, const ov2_fkf_item *items, int unrot, int filter,
+                       int stat, ov2_parallax_result *results);
+int ov2_kf_decision(ov2_ctx *ctx, const ov2_fkf_params *params, const ov2_fkf_item *item, ov2_kf_decision_result *result);
+int ov2_kf_decision_batch(ov2_ctx *ctx, const ov2_fkf_params *params, int n_items, const ov2_fkf_item *items,
+                          ov2_kf_decision_result *results);
+/* one Fkfcur (9 doubles, row-major) per item */
+int ov2_sampson_filter_2d(ov2_ctx *ctx, const ov2_fkf_item *item, const double Fkfcur[9], float fransac_err,
+                          ov2_sampson2d_result *result);
+int ov2_sampson_filter_2d_batch(ov2_ctx *ctx, int n_items, const ov2_fkf_item *items, const double *Fkfcur, float fransac_err,
+                                ov2_sampson2d_result *results);
+
 #ifdef __cplusplus
 }
 #endif

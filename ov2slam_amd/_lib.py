@@ -38,6 +38,12 @@ OV2_TRI_STEREO_TRIED, OV2_TRI_STEREO_OK, OV2_TRI_TEMPORAL_TRIED, OV2_TRI_TEMPORA
 OV2_MATCH_BEHIND, OV2_MATCH_OUT_OF_FOV, OV2_MATCH_OUT_OF_IMAGE, OV2_MATCH_NO_CANDIDATE, OV2_MATCH_RATIO_REJECTED, OV2_MATCH_BEST = 1, 2, 4, 8, 16, 32
 OV2_LOOPMAP_BEHIND, OV2_LOOPMAP_OUT_OF_FOV, OV2_LOOPMAP_OUT_OF_IMAGE = 1, 2, 4
 OV2_LOOPMAP_NO_CANDIDATE, OV2_LOOPMAP_RATIO_REJECTED, OV2_LOOPMAP_BEST = 8, 16, 32
+# frame versus keyframe (fkf.hip)
+OV2_FKF_MAX_POINTS, OV2_FKF_MAX_CELLS = 2048, 65536
+OV2_FKF_ALL, OV2_FKF_ONLY_2D, OV2_FKF_ONLY_3D = 0, 1, 2
+OV2_FKF_AVG, OV2_FKF_MEDIAN, OV2_FKF_AVG_WIDE = 0, 1, 2
+OV2_KF_C0, OV2_KF_C1, OV2_KF_C2, OV2_KF_CX = 1, 2, 4, 8
+OV2_KF_RET_FEW_CELLS, OV2_KF_RET_FEW_3D, OV2_KF_RET_MANY_3D, OV2_KF_RET_TIME, OV2_KF_NONFINITE = 16, 32, 64, 128, 256
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -306,6 +312,39 @@ class XYZBAResult(C.Structure):
     ]
 
 
+class FkfParams(C.Structure):
+    """ov2_fkf_params"""
+    _fields_ = [("K", C.c_double * 4), ("ncellsize", C.c_int), ("nbwcells", C.c_int), ("nbhcells", C.c_int), ("nbmaxkps", C.c_int),
+                ("finit_parallax", C.c_float), ("stereo", C.c_int)]
+
+
+class FkfItem(C.Structure):
+    """ov2_fkf_item"""
+    _fields_ = [("n_cur", C.c_int), ("cur_lmid", C.POINTER(C.c_int)), ("cur_px", C.POINTER(C.c_float)),
+                ("cur_unpx", C.POINTER(C.c_float)), ("cur_bv", C.POINTER(C.c_double)), ("cur_is3d", C.POINTER(C.c_uint8)),
+                ("cur_Twc", C.POINTER(C.c_double)), ("n_kf", C.c_int), ("kf_lmid", C.POINTER(C.c_int)),
+                ("kf_unpx", C.POINTER(C.c_float)), ("kf_Tcw", C.POINTER(C.c_double)), ("cur_id", C.c_int), ("kf_id", C.c_int),
+                ("cur_time", C.c_double), ("kf_time", C.c_double), ("kf_nb3dkps", C.c_int), ("localba_is_on", C.c_int),
+                ("noccupcells", C.c_int), ("nb3dkps", C.c_int)]
+
+
+class ParallaxResult(C.Structure):
+    """ov2_parallax_result"""
+    _fields_ = [("parallax", C.c_float), ("n", C.c_int), ("n_distinct", C.c_int), ("n_nonfinite", C.c_int)]
+
+
+class KfDecisionResult(C.Structure):
+    """ov2_kf_decision_result"""
+    _fields_ = [("parallax", C.c_float), ("n", C.c_int), ("n_distinct", C.c_int), ("n_nonfinite", C.c_int),
+                ("noccupcells", C.c_int), ("nb3dkps", C.c_int), ("n_out_of_grid", C.c_int), ("decision", C.c_int),
+                ("reason", C.c_int)]
+
+
+class Sampson2dResult(C.Structure):
+    """ov2_sampson2d_result"""
+    _fields_ = [("err", C.POINTER(C.c_float)), ("bad", C.POINTER(C.c_uint8)), ("n_bad", C.c_int)]
+
+
 _vp, _i, _f, _d = C.c_void_p, C.c_int, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 
@@ -438,6 +477,12 @@ SIGNATURES = {
     "ov2_pose_graph_solve": (_i, [_vp, C.POINTER(PGProblem), C.POINTER(BAOptions), C.POINTER(PGResult)]),
     "ov2_pose_graph_solve_batch": (_i, [_vp, _i, C.POINTER(PGProblem), C.POINTER(BAOptions), C.POINTER(PGResult)]),
     "ov2_pose_graph_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ov2_parallax": (_i, [_vp, C.POINTER(FkfParams), C.POINTER(FkfItem), _i, _i, _i, C.POINTER(ParallaxResult)]),
+    "ov2_parallax_batch": (_i, [_vp, C.POINTER(FkfParams), _i, C.POINTER(FkfItem), _i, _i, _i, C.POINTER(ParallaxResult)]),
+    "ov2_kf_decision": (_i, [_vp, C.POINTER(FkfParams), C.POINTER(FkfItem), C.POINTER(KfDecisionResult)]),
+    "ov2_kf_decision_batch": (_i, [_vp, C.POINTER(FkfParams), _i, C.POINTER(FkfItem), C.POINTER(KfDecisionResult)]),
+    "ov2_sampson_filter_2d": (_i, [_vp, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
+    "ov2_sampson_filter_2d_batch": (_i, [_vp, _i, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

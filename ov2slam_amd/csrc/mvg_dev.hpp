@@ -1,0 +1,57 @@
+// mvg_dev.hpp -- small fp64 geometry shared by triangulate.hip, stereo.hip and fkf.hip: Eigen's quaternion-to-matrix, a serial
+// 3x3 matrix-vector product, CameraCalibration::projectCamToImage, cv::norm of a Point2f difference and
+// MultiViewGeometry::computeSampsonDistance.  Sums of three products run serially.
+#pragma once
+#include "common.hpp"
+
+#pragma clang fp contract(off)
+
+struct TriD3 { double x, y, z; };
+struct TriQ { double x, y, z, w; };
+
+// Eigen's toRotationMatrix, no renormalisation (row-major)
+__device__ __forceinline__ void tri_rotmat(TriQ q, double R[9])
+{
+    const double tx = 2. * q.x, ty = 2. * q.y, tz = 2. * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    R[0] = 1. - (tyy + tzz); R[1] = txy - twz;        R[2] = txz + twy;
+    R[3] = txy + twz;        R[4] = 1. - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy;        R[7] = tyz + twx;        R[8] = 1. - (txx + tyy);
+}
+__device__ __forceinline__ TriD3 tri_matvec(const double R[9], TriD3 v)
+{
+    return TriD3{(R[0] * v.x + R[1] * v.y) + R[2] * v.z, (R[3] * v.x + R[4] * v.y) + R[5] * v.z, (R[6] * v.x + R[7] * v.y) + R[8] * v.z};
+}
+// CameraCalibration::projectCamToImage (src/camera_calibration.cpp:243-252): double math, cv::Point2f result
+__device__ __forceinline__ float2 tri_project(const double K[4], TriD3 p)
+{
+    const double invz = 1. / p.z;
+    const double x = p.x * invz, y = p.y * invz;
+    return make_float2((float)(K[0] * x + K[2]), (float)(K[1] * y + K[3]));
+}
+// cv::norm(a - b) of two cv::Point2f: the difference in float, the norm in double
+__device__ __forceinline__ double tri_pdist(float2 a, float2 b)
+{
+    const float dx = a.x - b.x, dy = a.y - b.y;
+    return sqrt((double)dx * (double)dx + (double)dy * (double)dy);
+}
+
+// float Sampson distance exactly as MultiViewGeometry::computeSampsonDistance narrows its doubles
+__device__ __forceinline__ float sampson(const double *F, float lx, float ly, float rx, float ry)
+{
+    const double l[3] = {(double)lx, (double)ly, 1.}, r[3] = {(double)rx, (double)ry, 1.};
+    double rtF[3], Fl[3], Ftr[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) rtF[j] = (r[0] * F[j] + r[1] * F[3 + j]) + r[2] * F[6 + j];
+    float num = (float)((rtF[0] * l[0] + rtF[1] * l[1]) + rtF[2] * l[2]);
+    num *= num;
+#pragma unroll
+    for (int k = 0; k < 3; k++) Fl[k] = (F[3 * k] * l[0] + F[3 * k + 1] * l[1]) + F[3 * k + 2] * l[2];
+#pragma unroll
+    for (int j = 0; j < 3; j++) Ftr[j] = (F[j] * r[0] + F[3 + j] * r[1]) + F[6 + j] * r[2];
+    const float x1 = (float)Ftr[0], x2 = (float)Fl[0], y1 = (float)Ftr[1], y2 = (float)Fl[1];
+    const float den = x1 * x1 + y1 * y1 + x2 * x2 + y2 * y2;
+    return sqrtf(num / den);
+}

@@ -11,6 +11,7 @@
 // replicated border with the vertical-only weights b1/b2 outside the columns (adjustRect) -- integers,
 // bit-exact against the oracle.
 #include "keypoint_dev.hpp"
+#include "mvg_dev.hpp"
 
 #pragma clang fp contract(off)
 
@@ -118,24 +119,6 @@ __global__ __launch_bounds__(256) void k_line_min_sad(PyrDesc PL, PyrDesc PR, in
         }
     }
     if (lane == 0) { xprior[i] = best_c; l1err[i] = best_e; }
-}
-
-// float Sampson distance exactly as MultiViewGeometry::computeSampsonDistance narrows its doubles
-__device__ __forceinline__ float sampson(const double *F, float lx, float ly, float rx, float ry)
-{
-    const double l[3] = {(double)lx, (double)ly, 1.}, r[3] = {(double)rx, (double)ry, 1.};
-    double rtF[3], Fl[3], Ftr[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) rtF[j] = (r[0] * F[j] + r[1] * F[3 + j]) + r[2] * F[6 + j];
-    float num = (float)((rtF[0] * l[0] + rtF[1] * l[1]) + rtF[2] * l[2]);
-    num *= num;
-#pragma unroll
-    for (int k = 0; k < 3; k++) Fl[k] = (F[3 * k] * l[0] + F[3 * k + 1] * l[1]) + F[3 * k + 2] * l[2];
-#pragma unroll
-    for (int j = 0; j < 3; j++) Ftr[j] = (F[j] * r[0] + F[3 + j] * r[1]) + F[6 + j] * r[2];
-    const float x1 = (float)Ftr[0], x2 = (float)Fl[0], y1 = (float)Ftr[1], y2 = (float)Fl[1];
-    const float den = x1 * x1 + y1 * y1 + x2 * x2 + y2 * y2;
-    return sqrtf(num / den);
 }
 
 struct EpiParams { double F[9]; int rect; };

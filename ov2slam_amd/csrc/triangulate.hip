@@ -9,14 +9,12 @@
 // run serially.  tests/tri_ref.py is the same arithmetic in numpy.
 // Layout: per-point fields one array each (float2 pixels, 3-double bearings, contiguous records), so a wavefront's loads of
 // one field cover consecutive bytes; grid.y = batch item.
-#include "common.hpp"
+#include "mvg_dev.hpp"
 
 #pragma clang fp contract(off)
 
 #define TRI_BLOCK 64
 
-struct TriD3 { double x, y, z; };
-struct TriQ { double x, y, z, w; };
 struct TriSE3 { TriD3 t; TriQ q; };
 
 struct TriParams {
@@ -66,21 +64,6 @@ __device__ __host__ __forceinline__ TriSE3 tri_load(const double *T)   // [tx ty
 {
     return TriSE3{TriD3{T[0], T[1], T[2]}, TriQ{T[3], T[4], T[5], T[6]}};
 }
-// Eigen's toRotationMatrix, no renormalisation (row-major)
-__device__ __forceinline__ void tri_rotmat(TriQ q, double R[9])
-{
-    const double tx = 2. * q.x, ty = 2. * q.y, tz = 2. * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0] = 1. - (tyy + tzz); R[1] = txy - twz;        R[2] = txz + twy;
-    R[3] = txy + twz;        R[4] = 1. - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;        R[7] = tyz + twx;        R[8] = 1. - (txx + tyy);
-}
-__device__ __forceinline__ TriD3 tri_matvec(const double R[9], TriD3 v)
-{
-    return TriD3{(R[0] * v.x + R[1] * v.y) + R[2] * v.z, (R[3] * v.x + R[4] * v.y) + R[5] * v.z, (R[6] * v.x + R[7] * v.y) + R[8] * v.z};
-}
 // opengv::triangulation::triangulate2 with (R12, t12) = the Tlr handed to MultiViewGeometry::triangulate (:85-100)
 __device__ __forceinline__ TriD3 tri_triangulate2(const double R12[9], TriD3 t12, TriD3 f1, TriD3 f2)
 {
@@ -93,20 +76,6 @@ __device__ __forceinline__ TriD3 tri_triangulate2(const double R12[9], TriD3 t12
     const double l0 = i00 * b0 + i01 * b1, l1 = i10 * b0 + i11 * b1;
     return TriD3{(l0 * f1.x + (t12.x + l1 * f2u.x)) / 2., (l0 * f1.y + (t12.y + l1 * f2u.y)) / 2., (l0 * f1.z + (t12.z + l1 * f2u.z)) / 2.};
 }
-// CameraCalibration::projectCamToImage (src/camera_calibration.cpp:243-252): double math, cv::Point2f result
-__device__ __forceinline__ float2 tri_project(const double K[4], TriD3 p)
-{
-    const double invz = 1. / p.z;
-    const double x = p.x * invz, y = p.y * invz;
-    return make_float2((float)(K[0] * x + K[2]), (float)(K[1] * y + K[3]));
-}
-// cv::norm(a - b) of two cv::Point2f: the difference in float, the norm in double
-__device__ __forceinline__ double tri_pdist(float2 a, float2 b)
-{
-    const float dx = a.x - b.x, dy = a.y - b.y;
-    return sqrt((double)dx * (double)dx + (double)dy * (double)dy);
-}
-
 // items[b] = {first point slot, point count, first row of the source table, 0}; twc: 7 doubles per item; srcT: 14 doubles per source
 // keyframe (Twc, Tcw).  Outputs: status / wpt / invdepth per point slot (zeros where no point was created).
 __global__ __launch_bounds__(TRI_BLOCK) void k_triangulate(TriParams P, const int4 *__restrict__ items, const double *__restrict__ twc,

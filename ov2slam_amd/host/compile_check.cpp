@@ -36,4 +36,16 @@ static int (ov2::LoopCloser::*const check_loopmap_batch)(ov2::Context &, const s
                                                          std::vector<ov2::LoopMapOutput> *) const = &ov2::LoopCloser::trackLoopLocalMap;
 static auto const check_set_loopmap = &ov2::LoopCloser::setLoopMapMatching;
 static auto *const check_loopmap_order = &ov2::loopLocalMapReferenceOrder;
-int main() { return check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
+// frame versus previous keyframe: computeParallax / checkNewKfReq / epipolarFilter2d, single and batch
+static int (*const check_parallax)(ov2::Context &, const ov2::KfReqParams &, const ov2::FrameVsKeyframe &, bool, int, int, ov2_parallax_result &) = &ov2::computeParallax;
+static int (*const check_parallax_batch)(ov2::Context &, const ov2::KfReqParams &, const std::vector<ov2::FrameVsKeyframe> &, bool, int, int,
+                                         std::vector<ov2_parallax_result> &) = &ov2::computeParallax;
+static int (*const check_kfreq)(ov2::Context &, const ov2::KfReqParams &, const ov2::FrameVsKeyframe &, ov2_kf_decision_result &) = &ov2::checkNewKfReq;
+static int (*const check_kfreq_batch)(ov2::Context &, const ov2::KfReqParams &, const std::vector<ov2::FrameVsKeyframe> &,
+                                      std::vector<ov2_kf_decision_result> &) = &ov2::checkNewKfReq;
+static int (*const check_epi2d)(ov2::Context &, const ov2::FrameVsKeyframe &, const double *, float, std::vector<int> &, std::vector<float> *) = &ov2::epipolarFilter2d;
+static int (*const check_epi2d_batch)(ov2::Context &, const std::vector<ov2::FrameVsKeyframe> &, const std::vector<double> &, float,
+                                      std::vector<std::vector<int>> &, std::vector<std::vector<float>> *) = &ov2::epipolarFilter2d;
+static auto const check_kf_sort = &ov2::detail::sortKeyframeByLmid;
+
+int main() { return check_parallax && check_parallax_batch && check_kfreq && check_kfreq_batch && check_epi2d && check_epi2d_batch && check_kf_sort && check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }

@@ -3,6 +3,7 @@
 // The reference's members prev_pyr_ / cur_pyr_ live inside the tracker object; kltTracking's two fbKltTracking calls, the
 // retry of lost prior tracks and the bp3preq_ rule are reproduced by the library (include/ov2slam_hip.h).
 #pragma once
+#include <algorithm>
 #include "ov2_types.hpp"
 
 namespace ov2 {
@@ -118,5 +119,173 @@ private:
     int last_rc_ = OV2_OK;
     std::string last_msg_;
 };
+
+// ---- frame versus previous keyframe: computeParallax (:1066-1141), checkNewKfReq (:986-1061) and the Sampson pass over the 2-D
+// keypoints of epipolar2d2dFiltering (:610-652) on ov2_parallax / ov2_kf_decision / ov2_sampson_filter_2d.  The caller hands over
+// what the reference's maps hold: the current frame's keypoints in the iteration order of pcurframe_->mapkps_ (the float sums run
+// in that order) and the keyframe's in any order -- the adapter sorts them by lmid, the library joins on the device.
+struct KfReqParams {
+    double K[4] = {0, 0, 0, 0};                               // pcalib_leftcam_: fx_, fy_, cx_, cy_
+    int ncellsize = 0, nbwcells = 0, nbhcells = 0;            // Frame: ncellsize_, nbwcells_, nbhcells_
+    int nbmaxkps = 0;                                         // SlamParams: nbmaxkps_, finit_parallax_, stereo_
+    float finit_parallax = 0.f;
+    bool stereo = false;
+};
+struct FrameVsKeyframe {
+    std::vector<int> cur_lmid;                                // Keypoint::lmid_, px_, unpx_, bv_ (3 doubles each), is3d_
+    std::vector<Point2f> cur_px, cur_unpx;
+    std::vector<double> cur_bv;
+    std::vector<uint8_t> cur_is3d;
+    double cur_Twc[7] = {0, 0, 0, 0, 0, 0, 1};                // pcurframe_->getTwc(): [t q]
+    std::vector<int> kf_lmid;                                 // pkf->mapkps_, any order
+    std::vector<Point2f> kf_unpx;
+    double kf_Tcw[7] = {0, 0, 0, 0, 0, 0, 1};                 // pkf->getTcw(), as held
+    int cur_id = 0, kf_id = 0;                                // Frame::id_
+    double cur_time = 0., kf_time = 0.;                       // Frame::img_time_
+    int kf_nb3dkps = 0;                                       // pkf->nb3dkps_
+    bool localba_is_on = false;                               // pslamstate_->blocalba_is_on_
+    int noccupcells = -1, nb3dkps = -1;                       // pcurframe_->noccupcells_ / nb3dkps_; -1: counted on the device
+};
+
+namespace detail {
+// the keyframe side in ascending lmid order (what ov2_fkf_item asks for); false when the arrays differ in length or an id repeats
+inline bool sortKeyframeByLmid(const std::vector<int> &lmid, const std::vector<Point2f> &unpx, std::vector<int> &lmid_sorted,
+                               std::vector<float> &unpx_sorted)
+{
+    const size_t m = lmid.size();
+    lmid_sorted.clear(); unpx_sorted.clear();
+    if (unpx.size() != m) return false;
+    std::vector<std::pair<int, size_t>> order(m);
+    for (size_t i = 0; i < m; i++) order[i] = std::make_pair(lmid[i], i);
+    std::sort(order.begin(), order.end());
+    lmid_sorted.resize(m); unpx_sorted.resize(2 * m);
+    for (size_t i = 0; i < m; i++) {
+        if (i > 0 && order[i].first == order[i - 1].first) return false;
+        lmid_sorted[i] = order[i].first;
+        unpx_sorted[2 * i] = unpx[order[i].second].x; unpx_sorted[2 * i + 1] = unpx[order[i].second].y;
+    }
+    return true;
+}
+struct FkfPacked { std::vector<int> kf_lmid; std::vector<float> kf_unpx; ov2_fkf_item item; };
+inline bool packFkf(const FrameVsKeyframe &f, FkfPacked &p)
+{
+    const size_t n = f.cur_lmid.size();
+    if (f.cur_px.size() != n || f.cur_unpx.size() != n || f.cur_bv.size() != 3 * n || f.cur_is3d.size() != n) return false;
+    if (!sortKeyframeByLmid(f.kf_lmid, f.kf_unpx, p.kf_lmid, p.kf_unpx)) return false;
+    static const float none_f[2] = {0.f, 0.f}; static const double none_d[3] = {0., 0., 0.}; static const int none_i = 0; static const uint8_t none_b = 0;
+    ov2_fkf_item &it = p.item;
+    it.n_cur = (int)n;
+    it.cur_lmid = n ? f.cur_lmid.data() : &none_i; it.cur_px = n ? &f.cur_px[0].x : none_f; it.cur_unpx = n ? &f.cur_unpx[0].x : none_f;
+    it.cur_bv = n ? f.cur_bv.data() : none_d; it.cur_is3d = n ? f.cur_is3d.data() : &none_b; it.cur_Twc = f.cur_Twc;
+    it.n_kf = (int)p.kf_lmid.size();
+    it.kf_lmid = it.n_kf ? p.kf_lmid.data() : &none_i; it.kf_unpx = it.n_kf ? p.kf_unpx.data() : none_f; it.kf_Tcw = f.kf_Tcw;
+    it.cur_id = f.cur_id; it.kf_id = f.kf_id; it.cur_time = f.cur_time; it.kf_time = f.kf_time; it.kf_nb3dkps = f.kf_nb3dkps;
+    it.localba_is_on = f.localba_is_on ? 1 : 0; it.noccupcells = f.noccupcells; it.nb3dkps = f.nb3dkps;
+    return true;
+}
+inline ov2_fkf_params fkfParams(const KfReqParams &k)
+{
+    ov2_fkf_params p{};
+    for (int j = 0; j < 4; j++) p.K[j] = k.K[j];
+    p.ncellsize = k.ncellsize; p.nbwcells = k.nbwcells; p.nbhcells = k.nbhcells; p.nbmaxkps = k.nbmaxkps;
+    p.finit_parallax = k.finit_parallax; p.stereo = k.stereo ? 1 : 0;
+    return p;
+}
+inline bool packFkfBatch(const std::vector<FrameVsKeyframe> &fs, std::vector<FkfPacked> &packed, std::vector<ov2_fkf_item> &items)
+{
+    packed.resize(fs.size()); items.resize(fs.size());
+    for (size_t b = 0; b < fs.size(); b++) {
+        if (!packFkf(fs[b], packed[b])) return false;
+        items[b] = packed[b].item;
+    }
+    return true;
+}
+}  // namespace detail
+
+// computeParallax(kfid, do_unrot, bmedian, b2donly) is (do_unrot, b2donly ? OV2_FKF_ONLY_2D : OV2_FKF_ALL, bmedian ? OV2_FKF_MEDIAN :
+// OV2_FKF_AVG); the gate ahead of the 5-point search (:488-535) is (true, epifrom3dkps ? OV2_FKF_ONLY_3D : OV2_FKF_ALL, OV2_FKF_AVG_WIDE).
+// Returns OV2_OK or the library's code (ov2_last_error() says why); OV2_EINVAL for arrays that differ in length or a repeated keyframe id.
+inline int computeParallax(Context &ctx, const KfReqParams &params, const FrameVsKeyframe &f, bool do_unrot, int filter, int stat,
+                           ov2_parallax_result &out)
+{
+    detail::FkfPacked p;
+    if (!detail::packFkf(f, p)) return OV2_EINVAL;
+    const ov2_fkf_params fp = detail::fkfParams(params);
+    return ov2_parallax(ctx.get(), &fp, &p.item, do_unrot ? 1 : 0, filter, stat, &out);
+}
+inline int computeParallax(Context &ctx, const KfReqParams &params, const std::vector<FrameVsKeyframe> &fs, bool do_unrot, int filter,
+                           int stat, std::vector<ov2_parallax_result> &out)
+{
+    std::vector<detail::FkfPacked> packed;
+    std::vector<ov2_fkf_item> items;
+    if (!detail::packFkfBatch(fs, packed, items)) return OV2_EINVAL;
+    out.assign(fs.size(), ov2_parallax_result{});
+    const ov2_fkf_params fp = detail::fkfParams(params);
+    return ov2_parallax_batch(ctx.get(), &fp, (int)fs.size(), items.data(), do_unrot ? 1 : 0, filter, stat, out.data());
+}
+
+// checkNewKfReq: out.decision is its return value, out.reason says which line decided
+inline int checkNewKfReq(Context &ctx, const KfReqParams &params, const FrameVsKeyframe &f, ov2_kf_decision_result &out)
+{
+    detail::FkfPacked p;
+    if (!detail::packFkf(f, p)) return OV2_EINVAL;
+    const ov2_fkf_params fp = detail::fkfParams(params);
+    return ov2_kf_decision(ctx.get(), &fp, &p.item, &out);
+}
+inline int checkNewKfReq(Context &ctx, const KfReqParams &params, const std::vector<FrameVsKeyframe> &fs, std::vector<ov2_kf_decision_result> &out)
+{
+    std::vector<detail::FkfPacked> packed;
+    std::vector<ov2_fkf_item> items;
+    if (!detail::packFkfBatch(fs, packed, items)) return OV2_EINVAL;
+    out.assign(fs.size(), ov2_kf_decision_result{});
+    const ov2_fkf_params fp = detail::fkfParams(params);
+    return ov2_kf_decision_batch(ctx.get(), &fp, (int)fs.size(), items.data(), out.data());
+}
+
+// the loop of :624-644: vbadkpids in the order of the current frame's keypoints (the caller removes them, :646-648); verr (optional):
+// the Sampson distance per current keypoint, 0 for 3-D keypoints.  Fkfcur: computeFundamentalMat12(Tidentity, Tkfcur, K_), row-major.
+inline int epipolarFilter2d(Context &ctx, const FrameVsKeyframe &f, const double Fkfcur[9], float fransac_err, std::vector<int> &vbadkpids,
+                            std::vector<float> *verr = nullptr)
+{
+    vbadkpids.clear();
+    detail::FkfPacked p;
+    if (!detail::packFkf(f, p)) return OV2_EINVAL;
+    const size_t n = f.cur_lmid.size();
+    std::vector<float> err(n ? n : 1);
+    std::vector<uint8_t> bad(n ? n : 1);
+    ov2_sampson2d_result r{err.data(), bad.data(), 0};
+    const int rc = ov2_sampson_filter_2d(ctx.get(), &p.item, Fkfcur, fransac_err, &r);
+    if (rc != OV2_OK) return rc;
+    for (size_t i = 0; i < n; i++) if (bad[i]) vbadkpids.push_back(f.cur_lmid[i]);
+    if (verr) { err.resize(n); verr->swap(err); }
+    return OV2_OK;
+}
+// one Fkfcur (9 doubles) per item in vF
+inline int epipolarFilter2d(Context &ctx, const std::vector<FrameVsKeyframe> &fs, const std::vector<double> &vF, float fransac_err,
+                            std::vector<std::vector<int>> &vbadkpids, std::vector<std::vector<float>> *verr = nullptr)
+{
+    vbadkpids.assign(fs.size(), std::vector<int>());
+    if (vF.size() != 9 * fs.size()) return OV2_EINVAL;
+    std::vector<detail::FkfPacked> packed;
+    std::vector<ov2_fkf_item> items;
+    if (!detail::packFkfBatch(fs, packed, items)) return OV2_EINVAL;
+    std::vector<std::vector<float>> err(fs.size());
+    std::vector<std::vector<uint8_t>> bad(fs.size());
+    std::vector<ov2_sampson2d_result> rs(fs.size());
+    for (size_t b = 0; b < fs.size(); b++) {
+        const size_t n = fs[b].cur_lmid.size();
+        err[b].resize(n ? n : 1); bad[b].resize(n ? n : 1);
+        rs[b] = ov2_sampson2d_result{err[b].data(), bad[b].data(), 0};
+    }
+    const int rc = ov2_sampson_filter_2d_batch(ctx.get(), (int)fs.size(), items.data(), vF.data(), fransac_err, rs.data());
+    if (rc != OV2_OK) return rc;
+    for (size_t b = 0; b < fs.size(); b++) {
+        const size_t n = fs[b].cur_lmid.size();
+        for (size_t i = 0; i < n; i++) if (bad[b][i]) vbadkpids[b].push_back(fs[b].cur_lmid[i]);
+        err[b].resize(n);
+    }
+    if (verr) verr->swap(err);
+    return OV2_OK;
+}
 
 }  // namespace ov2

@@ -1,0 +1,152 @@
+"""Host-side mirror of the per-frame "frame versus previous keyframe" passes of the reference's src/visual_front_end.cpp on top
+of the C ABI (ov2_parallax / ov2_kf_decision / ov2_sampson_filter_2d and their batch forms, csrc/fkf.hip):
+
+    parallax            VisualFrontEnd::computeParallax (:1066-1141) in the arithmetic of each of its three call sites
+    kf_decision         VisualFrontEnd::checkNewKfReq (:986-1061)
+    sampson_filter_2d   the Sampson pass over the 2-D keypoints after the 5-point search (:610-652)
+
+An item is a dict named like the fields of ov2_fkf_item (the counts follow from the array lengths): cur_lmid (n,), cur_px (n,2),
+cur_unpx (n,2), cur_bv (n,3), cur_is3d (n,), cur_Twc (7,), kf_lmid (m,) strictly ascending, kf_unpx (m,2), kf_Tcw (7,), and the
+scalars cur_id, kf_id, cur_time, kf_time, kf_nb3dkps, localba_is_on, noccupcells, nb3dkps (-1 or absent: counted on the device).
+Poses are [tx ty tz qx qy qz qw], as held by the Frame.  The join by landmark id runs on the device."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+
+ALL, ONLY_2D, ONLY_3D = L.OV2_FKF_ALL, L.OV2_FKF_ONLY_2D, L.OV2_FKF_ONLY_3D
+AVG, MEDIAN, AVG_WIDE = L.OV2_FKF_AVG, L.OV2_FKF_MEDIAN, L.OV2_FKF_AVG_WIDE
+
+_FKF_FIELDS = (("cur_lmid", np.int32, C.c_int, 1), ("cur_px", np.float32, C.c_float, 2), ("cur_unpx", np.float32, C.c_float, 2),
+               ("cur_bv", np.float64, C.c_double, 3), ("cur_is3d", np.uint8, C.c_uint8, 1), ("kf_lmid", np.int32, C.c_int, 1),
+               ("kf_unpx", np.float32, C.c_float, 2))
+_FKF_SCALARS = (("cur_id", 0), ("kf_id", 0), ("kf_nb3dkps", 0), ("localba_is_on", 0), ("noccupcells", -1), ("nb3dkps", -1))
+
+
+def fkf_params(K, *, ncellsize, nbwcells, nbhcells, nbmaxkps, finit_parallax, stereo):
+    """ov2_fkf_params: left K (fx fy cx cy), the Frame's grid (ncellsize_, nbwcells_, nbhcells_) and the SlamParams' nbmaxkps_,
+    finit_parallax_ and stereo_"""
+    p = L.FkfParams()
+    p.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(4)]
+    p.ncellsize, p.nbwcells, p.nbhcells, p.nbmaxkps = int(ncellsize), int(nbwcells), int(nbhcells), int(nbmaxkps)
+    p.finit_parallax, p.stereo = float(finit_parallax), int(bool(stereo))
+    return p
+
+
+def _as_fkf_params(params):
+    if isinstance(params, L.FkfParams):
+        return params
+    return fkf_params(params["K"], ncellsize=params["ncellsize"], nbwcells=params["nbwcells"], nbhcells=params["nbhcells"],
+                      nbmaxkps=params["nbmaxkps"], finit_parallax=params["finit_parallax"], stereo=params["stereo"])
+
+
+def _fkf_item(item):
+    """(ov2_fkf_item, the arrays it points into)"""
+    keep = {}
+    s = L.FkfItem()
+    for name, dt, ct, width in _FKF_FIELDS:
+        a = item.get(name)
+        a = np.zeros(0, dt) if a is None else np.ascontiguousarray(a, dtype=dt)
+        keep[name] = a
+        setattr(s, name, a.ctypes.data_as(C.POINTER(ct)))
+    s.n_cur, s.n_kf = keep["cur_lmid"].size, keep["kf_lmid"].size
+    for name, dt, ct, width in _FKF_FIELDS:
+        if keep[name].size != width * (s.n_cur if name.startswith("cur_") else s.n_kf):
+            raise ValueError("frame versus keyframe: %s has %d elements, not %d per keypoint" % (name, keep[name].size, width))
+    for name in ("cur_Twc", "kf_Tcw"):
+        a = np.ascontiguousarray(item.get(name, (0, 0, 0, 0, 0, 0, 1)), np.float64).reshape(7)
+        keep[name] = a
+        setattr(s, name, a.ctypes.data_as(C.POINTER(C.c_double)))
+    for name, default in _FKF_SCALARS:
+        setattr(s, name, int(item.get(name, default)))
+    s.cur_time, s.kf_time = float(item.get("cur_time", 0.)), float(item.get("kf_time", 0.))
+    return s, keep
+
+
+def _parallax_dict(r):
+    return dict(parallax=np.float32(r.parallax), n=r.n, n_distinct=r.n_distinct, n_nonfinite=r.n_nonfinite)
+
+
+def _decision_dict(r):
+    d = _parallax_dict(r)
+    d.update(noccupcells=r.noccupcells, nb3dkps=r.nb3dkps, n_out_of_grid=r.n_out_of_grid, decision=r.decision, reason=r.reason)
+    return d
+
+
+def _items(items):
+    items = list(items)
+    S = (L.FkfItem * max(1, len(items)))()
+    keep = []
+    for b, it in enumerate(items):
+        S[b], k = _fkf_item(it)
+        keep.append(k)
+    return items, S, keep
+
+
+def parallax(ctx, params, item, *, unrot, filter=ALL, stat=AVG):
+    """ov2_parallax: computeParallax(kfid, do_unrot, bmedian, b2donly) is (unrot, ONLY_2D if b2donly else ALL, MEDIAN if bmedian
+    else AVG); the gate ahead of the 5-point search is (1, ONLY_3D if epifrom3dkps else ALL, AVG_WIDE).  Returns a dict with
+    parallax (np.float32), n, n_distinct, n_nonfinite."""
+    s, keep = _fkf_item(item)
+    r = L.ParallaxResult()
+    L.check(ctx.lib.ov2_parallax(ctx.h, C.byref(_as_fkf_params(params)), C.byref(s), int(unrot), int(filter), int(stat), C.byref(r)))
+    return _parallax_dict(r)
+
+
+def parallax_batch(ctx, params, items, *, unrot, filter=ALL, stat=AVG):
+    """ov2_parallax_batch: the frames of a lock-step batch in one launch (shared params and form); one dict per item"""
+    items, S, keep = _items(items)
+    R = (L.ParallaxResult * max(1, len(items)))()
+    L.check(ctx.lib.ov2_parallax_batch(ctx.h, C.byref(_as_fkf_params(params)), len(items), S, int(unrot), int(filter), int(stat), R))
+    return [_parallax_dict(R[b]) for b in range(len(items))]
+
+
+def kf_decision(ctx, params, item):
+    """ov2_kf_decision: checkNewKfReq.  Returns the parallax fields plus noccupcells, nb3dkps (as used by the rule), n_out_of_grid,
+    decision (0 / 1) and reason (OV2_KF_* bits)."""
+    s, keep = _fkf_item(item)
+    r = L.KfDecisionResult()
+    L.check(ctx.lib.ov2_kf_decision(ctx.h, C.byref(_as_fkf_params(params)), C.byref(s), C.byref(r)))
+    return _decision_dict(r)
+
+
+def kf_decision_batch(ctx, params, items):
+    """ov2_kf_decision_batch: one small record per item comes back; one dict per item"""
+    items, S, keep = _items(items)
+    R = (L.KfDecisionResult * max(1, len(items)))()
+    L.check(ctx.lib.ov2_kf_decision_batch(ctx.h, C.byref(_as_fkf_params(params)), len(items), S, R))
+    return [_decision_dict(R[b]) for b in range(len(items))]
+
+
+def _sampson_result(n):
+    out = dict(err=np.zeros(n, np.float32), bad=np.zeros(n, np.uint8))
+    r = L.Sampson2dResult()
+    r.err, r.bad = out["err"].ctypes.data_as(C.POINTER(C.c_float)), out["bad"].ctypes.data_as(C.POINTER(C.c_uint8))
+    return r, out
+
+
+def sampson_filter_2d(ctx, item, Fkfcur, fransac_err):
+    """ov2_sampson_filter_2d: err (n,) float32 and bad (n,) uint8 per current keypoint (0 for 3-D keypoints), n_bad.  A 2-D
+    keypoint the keyframe does not hold is scored against (0, 0), as the reference does."""
+    s, keep = _fkf_item(item)
+    r, out = _sampson_result(s.n_cur)
+    F = np.ascontiguousarray(Fkfcur, np.float64).reshape(9)
+    L.check(ctx.lib.ov2_sampson_filter_2d(ctx.h, C.byref(s), F.ctypes.data_as(C.POINTER(C.c_double)), float(fransac_err), C.byref(r)))
+    out["n_bad"] = r.n_bad
+    return out
+
+
+def sampson_filter_2d_batch(ctx, items, Fkfcur, fransac_err):
+    """ov2_sampson_filter_2d_batch: Fkfcur is (n_items, 9); one dict per item"""
+    items, S, keep = _items(items)
+    F = np.ascontiguousarray(Fkfcur, np.float64).reshape(len(items), 9)
+    R = (L.Sampson2dResult * max(1, len(items)))()
+    outs = []
+    for b in range(len(items)):
+        R[b], out = _sampson_result(S[b].n_cur)
+        outs.append(out)
+    L.check(ctx.lib.ov2_sampson_filter_2d_batch(ctx.h, len(items), S, F.ctypes.data_as(C.POINTER(C.c_double)), float(fransac_err), R))
+    for b, out in enumerate(outs):
+        out["n_bad"] = R[b].n_bad
+    return outs
