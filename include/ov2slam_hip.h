@@ -958,7 +958,7 @@ int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, i
 /* The loop that Mapper::matchingToLocalMap runs after the triangulation: every 3-D point of the local map is projected into the
  * new keyframe and compared, by descriptor, with the map points of the keypoints around its projection; a match says "this
  * keypoint's map point is a re-detection of that local map point" (mergeMatches).  One wavefront per local map point
- * (csrc/match.hip), ONE staging upload, the launches, ONE download and ONE synchronisation per call.
+ * (csrc/mapmatch.hip), ONE staging upload, the launches, ONE download and ONE synchronisation per call.
  *
  * Thresholds, once per call on the host in float as the reference writes them: vfov = 0.5 img_h / fy, hfov = 0.5 img_w / fx,
  * view_th = cos(atan(max(hfov, vfov))); dmaxpxdist = fmax_proj_pxdist, doubled when nb3dkps < 30; mindist = (float)(desc_bytes *
@@ -1114,7 +1114,7 @@ int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items,
 /* The fourth stage of LoopCloser::processLoopCandidate: once P3P has put the new keyframe into the loop keyframe's frame, the 3-D
  * points of the loop keyframe's neighbourhood are projected into the new keyframe and matched, by descriptor, with the map points
  * of the keypoints around their projections.  A cousin of ov2_match_to_map with other gates and other arithmetic -- a different
- * function of the reference, not a mode of that one.  One wavefront per local map point (csrc/loopmap.hip), ONE staging upload,
+ * function of the reference, not a mode of that one.  One wavefront per local map point (csrc/mapmatch.hip), ONE staging upload,
  * two launches, ONE download and ONE synchronisation per call.
  *
  * Thresholds, once per call on the host in float as the reference writes them (:595-607, :656): hfov = (float)(0.5 * img_w * fx)

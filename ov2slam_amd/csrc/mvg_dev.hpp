@@ -1,5 +1,6 @@
-// mvg_dev.hpp -- small fp64 geometry shared by triangulate.hip, stereo.hip and fkf.hip: Eigen's quaternion-to-matrix, a serial
-// 3x3 matrix-vector product, CameraCalibration::projectCamToImage, cv::norm of a Point2f difference and
+// mvg_dev.hpp -- small fp64 geometry shared by triangulate.hip, mapmatch.hip, stereo.hip and fkf.hip: Sophus' SO3 / SE3 products
+// and actions on a pose as held (restated from the vendored so3.hpp, se3.hpp), Eigen's quaternion-to-matrix, a serial 3x3
+// matrix-vector product, CameraCalibration::projectCamToImage, cv::norm of a Point2f difference and
 // MultiViewGeometry::computeSampsonDistance.  Sums of three products run serially.
 #pragma once
 #include "common.hpp"
@@ -8,6 +9,48 @@
 
 struct TriD3 { double x, y, z; };
 struct TriQ { double x, y, z, w; };
+struct TriSE3 { TriD3 t; TriQ q; };      // a pose as held: [tx ty tz qx qy qz qw]
+
+__device__ __forceinline__ double tri_dot(TriD3 a, TriD3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ TriD3 tri_cross(TriD3 a, TriD3 b)       // Eigen's cross
+{
+    return TriD3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+// SO3's constructor normalises (so3.hpp:297-303, :483-489); squaredNorm in serial order
+__device__ __forceinline__ TriQ tri_qnormalize(double x, double y, double z, double w)
+{
+    const double n = sqrt(((x * x + y * y) + z * z) + w * w);
+    return TriQ{x / n, y / n, z / n, w / n};
+}
+__device__ __forceinline__ TriQ tri_qmul(TriQ a, TriQ b)           // so3.hpp:329-343
+{
+    return tri_qnormalize(a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
+                          a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
+                          a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x,
+                          a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z);
+}
+__device__ __forceinline__ TriD3 tri_qact(TriQ q, TriD3 p)         // so3.hpp:362-371
+{
+    const TriD3 qv{q.x, q.y, q.z};
+    TriD3 uv = tri_cross(qv, p);
+    uv = TriD3{uv.x + uv.x, uv.y + uv.y, uv.z + uv.z};
+    const TriD3 c = tri_cross(qv, uv);
+    return TriD3{(p.x + q.w * uv.x) + c.x, (p.y + q.w * uv.y) + c.y, (p.z + q.w * uv.z) + c.z};
+}
+__device__ __forceinline__ TriD3 tri_act(const TriSE3 &T, TriD3 p)   // se3.hpp:325-328
+{
+    const TriD3 r = tri_qact(T.q, p);
+    return TriD3{r.x + T.t.x, r.y + T.t.y, r.z + T.t.z};
+}
+__device__ __forceinline__ TriSE3 tri_mul(const TriSE3 &A, const TriSE3 &B)   // se3.hpp:308-312
+{
+    const TriD3 r = tri_qact(A.q, B.t);
+    return TriSE3{TriD3{A.t.x + r.x, A.t.y + r.y, A.t.z + r.z}, tri_qmul(A.q, B.q)};
+}
+__device__ __host__ __forceinline__ TriSE3 tri_load(const double *T)   // [tx ty tz qx qy qz qw] as held, no renormalisation
+{
+    return TriSE3{TriD3{T[0], T[1], T[2]}, TriQ{T[3], T[4], T[5], T[6]}};
+}
 
 // Eigen's toRotationMatrix, no renormalisation (row-major)
 __device__ __forceinline__ void tri_rotmat(TriQ q, double R[9])

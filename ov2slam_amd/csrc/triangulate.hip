@@ -15,8 +15,6 @@
 
 #define TRI_BLOCK 64
 
-struct TriSE3 { TriD3 t; TriQ q; };
-
 struct TriParams {
     int stereo, rect;
     float emax;
@@ -24,46 +22,6 @@ struct TriParams {
     TriSE3 Tlr, Trl, Tcic0;
 };
 
-__device__ __forceinline__ double tri_dot(TriD3 a, TriD3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ TriD3 tri_cross(TriD3 a, TriD3 b)       // Eigen's cross
-{
-    return TriD3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-// SO3's constructor normalises (so3.hpp:297-303, :483-489); squaredNorm in serial order
-__device__ __forceinline__ TriQ tri_qnormalize(double x, double y, double z, double w)
-{
-    const double n = sqrt(((x * x + y * y) + z * z) + w * w);
-    return TriQ{x / n, y / n, z / n, w / n};
-}
-__device__ __forceinline__ TriQ tri_qmul(TriQ a, TriQ b)           // so3.hpp:329-343
-{
-    return tri_qnormalize(a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-                          a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
-                          a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x,
-                          a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z);
-}
-__device__ __forceinline__ TriD3 tri_qact(TriQ q, TriD3 p)         // so3.hpp:362-371
-{
-    const TriD3 qv{q.x, q.y, q.z};
-    TriD3 uv = tri_cross(qv, p);
-    uv = TriD3{uv.x + uv.x, uv.y + uv.y, uv.z + uv.z};
-    const TriD3 c = tri_cross(qv, uv);
-    return TriD3{(p.x + q.w * uv.x) + c.x, (p.y + q.w * uv.y) + c.y, (p.z + q.w * uv.z) + c.z};
-}
-__device__ __forceinline__ TriD3 tri_act(const TriSE3 &T, TriD3 p)   // se3.hpp:325-328
-{
-    const TriD3 r = tri_qact(T.q, p);
-    return TriD3{r.x + T.t.x, r.y + T.t.y, r.z + T.t.z};
-}
-__device__ __forceinline__ TriSE3 tri_mul(const TriSE3 &A, const TriSE3 &B)   // se3.hpp:308-312
-{
-    const TriD3 r = tri_qact(A.q, B.t);
-    return TriSE3{TriD3{A.t.x + r.x, A.t.y + r.y, A.t.z + r.z}, tri_qmul(A.q, B.q)};
-}
-__device__ __host__ __forceinline__ TriSE3 tri_load(const double *T)   // [tx ty tz qx qy qz qw] as held, no renormalisation
-{
-    return TriSE3{TriD3{T[0], T[1], T[2]}, TriQ{T[3], T[4], T[5], T[6]}};
-}
 // opengv::triangulation::triangulate2 with (R12, t12) = the Tlr handed to MultiViewGeometry::triangulate (:85-100)
 __device__ __forceinline__ TriD3 tri_triangulate2(const double R12[9], TriD3 t12, TriD3 f1, TriD3 f2)
 {

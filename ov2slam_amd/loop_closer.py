@@ -14,7 +14,7 @@ kept_valid (n,) uint8, kept_desc (n, 32) uint8 in raster order (y, then x) and, 
 retainBest.  The frame walk that collects the exclusion points and the vconcat with the existing descriptors stay with the caller.
 
 And of the local-map tracking behind P3P (LoopCloser::trackLoopLocalMap / matchToMap, src/loop_closer.cpp:502-763) on top of
-ov2_loop_match_to_map[_batch] (csrc/loopmap.hip): loopmap_params(), loop_match_to_map(), loop_match_to_map_batch().  An item is a dict
+ov2_loop_match_to_map[_batch] (csrc/mapmatch.hip): loopmap_params(), loop_match_to_map(), loop_match_to_map_batch().  An item is a dict
 of numpy arrays named like the fields of ov2_loopmap_item (the counts are taken from the array lengths); a result is a dict with
 lm_status (n_lm,) uint8 (OV2_LOOPMAP_* bits), lm_kp, lm_dist, lm_projpx (n_lm, 2), kp_lm (n_kp,), kp_dist, n_matches.  The
 covisible-keyframe walk that builds the local set and the flattening of the map stay with the caller."""
@@ -23,6 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _mapmatch
 
 
 def knn_params(desc_bytes=32, max_dist=None, ratio=0.85):
@@ -314,97 +315,35 @@ def lckf_prepare_batch_d(ctx, params, img_d, w, h, pitch, item_stride, n_items, 
                                              v(kept_xy_d), v(kept_resp_d), v(kept_valid_d), v(kept_desc_d), int(kept_cap), v(counts_d)))
 
 
-# ---- local-map tracking of a loop candidate --------------------------------------------------------------------------------------
+# ---- local-map tracking of a loop candidate (the plumbing is _mapmatch's, shared with mapper.py) ------------------------------------
 LOOPMAP_BEHIND, LOOPMAP_OUT_OF_FOV, LOOPMAP_OUT_OF_IMAGE = L.OV2_LOOPMAP_BEHIND, L.OV2_LOOPMAP_OUT_OF_FOV, L.OV2_LOOPMAP_OUT_OF_IMAGE
 LOOPMAP_NO_CANDIDATE, LOOPMAP_RATIO_REJECTED, LOOPMAP_BEST = L.OV2_LOOPMAP_NO_CANDIDATE, L.OV2_LOOPMAP_RATIO_REJECTED, L.OV2_LOOPMAP_BEST
-_CAM_MODELS = {"pinhole": L.OV2_CAM_PINHOLE, "fisheye": L.OV2_CAM_FISHEYE}
+
+_LOOPMAP_FIELDS = (("kp_px", np.float32, C.c_float), ("kp_mp", np.int32, C.c_int), ("kp_matched", np.uint8, C.c_uint8),
+                   ("cell_start", np.int32, C.c_int), ("cell_kp", np.int32, C.c_int), ("obs_start", np.int32, C.c_int),
+                   ("obs_kfid", np.int32, C.c_int), ("desc_start", np.int32, C.c_int), ("desc", np.uint8, C.c_uint8),
+                   ("lm_mp", np.int32, C.c_int), ("lm_wpt", np.float64, C.c_double))
+_LOOPMAP = _mapmatch.Family("loop_match_to_map", "ov2_loop_match_to_map", "ov2_loop_match_to_map_batch", L.LoopMapParams, L.LoopMapItem,
+                            L.LoopMapResult, _LOOPMAP_FIELDS, defaults=dict(fmax_proj_pxdist=10.0))
 
 
 def loopmap_params(K, D, *, model="pinhole", img_w, img_h, ncellsize, fmax_proj_pxdist=10.0, fmax_desc_dist, desc_bytes=32):
     """ov2_loopmap_params: the left camera's model / K (fx fy cx cy) / distortion vector (None or empty: none) / image size, the
     Frame's ncellsize_, and maxdist / ratio as LoopCloser::processLoopCandidate passes them (10. and fmax_desc_dist_ * 1.5).
     The returned struct keeps its distortion array alive."""
-    p = L.LoopMapParams()
-    p.model = _CAM_MODELS[model] if isinstance(model, str) else int(model)
-    p.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(4)]
-    d = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
-    p._D = d
-    p.D, p.nD = (_p(d, C.c_double) if d.size else None), int(d.size)
-    p.img_w, p.img_h, p.ncellsize = float(img_w), float(img_h), int(ncellsize)
-    p.fmax_proj_pxdist, p.fmax_desc_dist, p.desc_bytes = float(fmax_proj_pxdist), float(fmax_desc_dist), int(desc_bytes)
-    return p
+    return _LOOPMAP.params(K, D, model, img_w, img_h, ncellsize, fmax_proj_pxdist, fmax_desc_dist, desc_bytes)
 
 
-def _as_loopmap_params(params):
-    if isinstance(params, L.LoopMapParams):
-        return params
-    return loopmap_params(params["K"], params.get("D"), model=params.get("model", "pinhole"), img_w=params["img_w"],
-                          img_h=params["img_h"], ncellsize=params["ncellsize"], fmax_proj_pxdist=params.get("fmax_proj_pxdist", 10.0),
-                          fmax_desc_dist=params["fmax_desc_dist"], desc_bytes=params.get("desc_bytes", 32))
-
-
-_LOOPMAP_FIELDS = (("kp_px", np.float32, C.c_float), ("kp_mp", np.int32, C.c_int), ("kp_matched", np.uint8, C.c_uint8),
-                   ("cell_start", np.int32, C.c_int), ("cell_kp", np.int32, C.c_int), ("obs_start", np.int32, C.c_int),
-                   ("obs_kfid", np.int32, C.c_int), ("desc_start", np.int32, C.c_int), ("desc", np.uint8, C.c_uint8),
-                   ("lm_mp", np.int32, C.c_int), ("lm_wpt", np.float64, C.c_double))
-
-
-def _loopmap_item(item):
-    """(ov2_loopmap_item, the arrays it points into, n_lm, n_kp)"""
-    t = np.ascontiguousarray(item["Tcw"], dtype=np.float64)
-    if t.shape != (7,):
-        raise ValueError("loop_match_to_map: Tcw must hold 7 doubles (translation, then the quaternion x y z w)")
-    keep = dict(Tcw=t)
-    s = L.LoopMapItem()
-    s.Tcw = _p(t, C.c_double)
-    for name, dt, ct in _LOOPMAP_FIELDS:
-        a = item.get(name)
-        a = None if a is None else np.ascontiguousarray(a, dtype=dt)
-        keep[name] = a
-        setattr(s, name, _p(a, ct) if a is not None and a.size else None)
-    size = lambda n: 0 if keep[n] is None else keep[n].size
-    s.n_kp, s.n_lm = size("kp_mp"), size("lm_mp")
-    s.n_mp = max(size("obs_start") - 1, 0)
-    if size("kp_px") != 2 * s.n_kp or size("kp_matched") != s.n_kp or size("lm_wpt") != 3 * s.n_lm or size("desc_start") != size("obs_start"):
-        raise ValueError("loop_match_to_map: array lengths disagree (kp_px / kp_mp / kp_matched, lm_wpt / lm_mp, obs_start / desc_start)")
-    if s.n_mp and (size("obs_kfid") != keep["obs_start"][-1] or size("desc") != 32 * keep["desc_start"][-1]):
-        raise ValueError("loop_match_to_map: the observation / descriptor arrays are not as long as their offsets say")
-    if size("cell_start") and size("cell_kp") != keep["cell_start"][-1]:
-        raise ValueError("loop_match_to_map: cell_kp is not as long as cell_start says")
-    return s, keep, s.n_lm, s.n_kp
-
-
-def _loopmap_result(n_lm, n_kp):
-    out = dict(lm_status=np.zeros(n_lm, np.uint8), lm_kp=np.full(n_lm, -1, np.int32), lm_dist=np.zeros(n_lm, np.float32),
-               lm_projpx=np.zeros((n_lm, 2), np.float32), kp_lm=np.full(n_kp, -1, np.int32), kp_dist=np.zeros(n_kp, np.float32))
-    r = L.LoopMapResult()
-    r.lm_status = _p(out["lm_status"], C.c_uint8)
-    r.lm_kp, r.kp_lm = _p(out["lm_kp"], C.c_int), _p(out["kp_lm"], C.c_int)
-    r.lm_dist, r.lm_projpx, r.kp_dist = _p(out["lm_dist"], C.c_float), _p(out["lm_projpx"], C.c_float), _p(out["kp_dist"], C.c_float)
-    return r, out
+_as_loopmap_params = _LOOPMAP.as_params
+_loopmap_item = _LOOPMAP.item        # (ov2_loopmap_item, the arrays it points into, n_lm, n_kp)
+_loopmap_result = _LOOPMAP.result    # (ov2_loopmap_result, the dict of arrays it points into)
 
 
 def loop_match_to_map(ctx, params, item):
     """ov2_loop_match_to_map: LoopCloser::matchToMap for one loop candidate.  Returns the result arrays as a dict (module docstring)."""
-    s, keep, n_lm, n_kp = _loopmap_item(item)
-    r, out = _loopmap_result(n_lm, n_kp)
-    L.check(ctx.lib.ov2_loop_match_to_map(ctx.h, C.byref(_as_loopmap_params(params)), C.byref(s), C.byref(r)))
-    out["n_matches"] = r.n_matches
-    return out
+    return _LOOPMAP.call(ctx, params, item)
 
 
 def loop_match_to_map_batch(ctx, params, items):
     """ov2_loop_match_to_map_batch: several candidates in one call (shared params).  Returns one dict per item, as loop_match_to_map."""
-    items = list(items)
-    S = (L.LoopMapItem * max(1, len(items)))()
-    R = (L.LoopMapResult * max(1, len(items)))()
-    keep, outs = [], []
-    for b, item in enumerate(items):
-        s, k, n_lm, n_kp = _loopmap_item(item)
-        r, out = _loopmap_result(n_lm, n_kp)
-        S[b], R[b] = s, r
-        keep.append(k); outs.append(out)
-    L.check(ctx.lib.ov2_loop_match_to_map_batch(ctx.h, C.byref(_as_loopmap_params(params)), len(items), S, R))
-    for b, out in enumerate(outs):
-        out["n_matches"] = R[b].n_matches
-    return outs
+    return _LOOPMAP.call_batch(ctx, params, items)

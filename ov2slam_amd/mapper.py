@@ -13,7 +13,7 @@ A keyframe is a dict of numpy arrays named like the fields of ov2_tri_keyframe: 
 is_stereo (n,), runpx (n,2), rbv (n,3), src (n,) int (-1: no candidate), src_unpx (n,2), src_bv (n,3), src_Twc (m,7), src_Tcw (m,7).
 Poses are [tx ty tz qx qy qz qw], as held by the Frame.
 
-Local-map matching (Mapper::matchToMap, src/mapper.cpp:576-774; ov2_match_to_map[_batch], csrc/match.hip): match_params(),
+Local-map matching (Mapper::matchToMap, src/mapper.cpp:576-774; ov2_match_to_map[_batch], csrc/mapmatch.hip): match_params(),
 match_to_map(), match_to_map_batch().  A keyframe is a dict of numpy arrays named like the fields of ov2_match_keyframe (the
 counts follow from the array lengths): Tcw (7,), nb3dkps, kp_px (n_kp,2), kp_mp (n_kp,), cell_start (ncells+1,), cell_kp,
 obs_start (n_mp+1,), obs_kfid, obs_kf, obs_px (n_obs,2), desc_start (n_mp+1,), desc (n_desc,32) uint8, kf_Tcw (n_kf,7),
@@ -23,6 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _mapmatch
 
 STEREO_TRIED, STEREO_OK = L.OV2_TRI_STEREO_TRIED, L.OV2_TRI_STEREO_OK
 TEMPORAL_TRIED, TEMPORAL_OK = L.OV2_TRI_TEMPORAL_TRIED, L.OV2_TRI_TEMPORAL_OK
@@ -124,98 +125,38 @@ def triangulate_keyframe_batch(ctx, params, kfs):
     return [_finish(R[b], outs[b]) for b in range(len(kfs))]
 
 
-# ---- local-map matching ------------------------------------------------------------------------------------------------------------
+# ---- local-map matching (the plumbing is _mapmatch's, shared with loop_closer.py) ---------------------------------------------------
 MATCH_BEHIND, MATCH_OUT_OF_FOV, MATCH_OUT_OF_IMAGE = L.OV2_MATCH_BEHIND, L.OV2_MATCH_OUT_OF_FOV, L.OV2_MATCH_OUT_OF_IMAGE
 MATCH_NO_CANDIDATE, MATCH_RATIO_REJECTED, MATCH_BEST = L.OV2_MATCH_NO_CANDIDATE, L.OV2_MATCH_RATIO_REJECTED, L.OV2_MATCH_BEST
-_CAM_MODELS = {"pinhole": L.OV2_CAM_PINHOLE, "fisheye": L.OV2_CAM_FISHEYE}
-
-
-def match_params(K, D, *, model="pinhole", img_w, img_h, ncellsize, fmax_proj_pxdist, fmax_desc_dist, desc_bytes=32):
-    """ov2_match_params: the left camera's model / K (fx fy cx cy) / distortion vector (None or empty: none) / image size, the
-    Frame's ncellsize_, and the SlamParams' fmax_proj_pxdist_ and fmax_desc_dist_ as Mapper::matchingToLocalMap passes them.
-    The returned struct keeps its distortion array alive."""
-    p = L.MatchParams()
-    p.model = _CAM_MODELS[model] if isinstance(model, str) else int(model)
-    p.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(4)]
-    d = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
-    p._D = d
-    p.D, p.nD = (_p(d, C.c_double) if d.size else None), int(d.size)
-    p.img_w, p.img_h, p.ncellsize = float(img_w), float(img_h), int(ncellsize)
-    p.fmax_proj_pxdist, p.fmax_desc_dist, p.desc_bytes = float(fmax_proj_pxdist), float(fmax_desc_dist), int(desc_bytes)
-    return p
-
-
-def _as_match_params(params):
-    if isinstance(params, L.MatchParams):
-        return params
-    return match_params(params["K"], params.get("D"), model=params.get("model", "pinhole"), img_w=params["img_w"],
-                        img_h=params["img_h"], ncellsize=params["ncellsize"], fmax_proj_pxdist=params["fmax_proj_pxdist"],
-                        fmax_desc_dist=params["fmax_desc_dist"], desc_bytes=params.get("desc_bytes", 32))
-
 
 _MATCH_FIELDS = (("kp_px", np.float32, C.c_float), ("kp_mp", np.int32, C.c_int), ("cell_start", np.int32, C.c_int),
                  ("cell_kp", np.int32, C.c_int), ("obs_start", np.int32, C.c_int), ("obs_kfid", np.int32, C.c_int),
                  ("obs_kf", np.int32, C.c_int), ("obs_px", np.float32, C.c_float), ("desc_start", np.int32, C.c_int),
                  ("desc", np.uint8, C.c_uint8), ("kf_Tcw", np.float64, C.c_double), ("lm_mp", np.int32, C.c_int),
                  ("lm_wpt", np.float64, C.c_double))
+_MATCH = _mapmatch.Family("match_to_map", "ov2_match_to_map", "ov2_match_to_map_batch", L.MatchParams, L.MatchKeyframe, L.MatchResult,
+                          _MATCH_FIELDS, scalars=("nb3dkps",))
 
 
-def _match_keyframe(kf):
-    """(ov2_match_keyframe, the arrays it points into, n_lm, n_kp)"""
-    keep = dict(Tcw=_arr(kf["Tcw"], np.float64, (7,)))
-    s = L.MatchKeyframe()
-    s.Tcw, s.nb3dkps = _p(keep["Tcw"], C.c_double), int(kf["nb3dkps"])
-    for name, dt, ct in _MATCH_FIELDS:
-        a = kf.get(name)
-        a = None if a is None else np.ascontiguousarray(a, dtype=dt)
-        keep[name] = a
-        setattr(s, name, _p(a, ct) if a is not None and a.size else None)
-    size = lambda n: 0 if keep[n] is None else keep[n].size
-    s.n_kp, s.n_kf, s.n_lm = size("kp_mp"), size("kf_Tcw") // 7, size("lm_mp")
-    s.n_mp = max(size("obs_start") - 1, 0)
-    if size("kp_px") != 2 * s.n_kp or size("lm_wpt") != 3 * s.n_lm or size("desc_start") != size("obs_start"):
-        raise ValueError("match_to_map: array lengths disagree (kp_px / kp_mp, lm_wpt / lm_mp, obs_start / desc_start)")
-    if s.n_mp and (size("obs_kfid") != keep["obs_start"][-1] or size("obs_kf") != size("obs_kfid") or
-                   size("obs_px") != 2 * size("obs_kfid") or size("desc") != 32 * keep["desc_start"][-1]):
-        raise ValueError("match_to_map: the observation / descriptor arrays are not as long as their offsets say")
-    if size("cell_start") and size("cell_kp") != keep["cell_start"][-1]:
-        raise ValueError("match_to_map: cell_kp is not as long as cell_start says")
-    return s, keep, s.n_lm, s.n_kp
+def match_params(K, D, *, model="pinhole", img_w, img_h, ncellsize, fmax_proj_pxdist, fmax_desc_dist, desc_bytes=32):
+    """ov2_match_params: the left camera's model / K (fx fy cx cy) / distortion vector (None or empty: none) / image size, the
+    Frame's ncellsize_, and the SlamParams' fmax_proj_pxdist_ and fmax_desc_dist_ as Mapper::matchingToLocalMap passes them.
+    The returned struct keeps its distortion array alive."""
+    return _MATCH.params(K, D, model, img_w, img_h, ncellsize, fmax_proj_pxdist, fmax_desc_dist, desc_bytes)
 
 
-def _match_result(n_lm, n_kp):
-    out = dict(lm_status=np.zeros(n_lm, np.uint8), lm_kp=np.full(n_lm, -1, np.int32), lm_dist=np.zeros(n_lm, np.float32),
-               lm_projpx=np.zeros((n_lm, 2), np.float32), kp_lm=np.full(n_kp, -1, np.int32), kp_dist=np.zeros(n_kp, np.float32))
-    r = L.MatchResult()
-    r.lm_status = _p(out["lm_status"], C.c_uint8)
-    r.lm_kp, r.kp_lm = _p(out["lm_kp"], C.c_int), _p(out["kp_lm"], C.c_int)
-    r.lm_dist, r.lm_projpx, r.kp_dist = _p(out["lm_dist"], C.c_float), _p(out["lm_projpx"], C.c_float), _p(out["kp_dist"], C.c_float)
-    return r, out
+_as_match_params = _MATCH.as_params
+_match_keyframe = _MATCH.item        # (ov2_match_keyframe, the arrays it points into, n_lm, n_kp)
+_match_result = _MATCH.result        # (ov2_match_result, the dict of arrays it points into)
 
 
 def match_to_map(ctx, params, kf):
     """ov2_match_to_map: Mapper::matchToMap for one keyframe.  Returns a dict with lm_status (n_lm,) uint8 (OV2_MATCH_* bits),
     lm_kp, lm_dist, lm_projpx (n_lm,2), kp_lm (n_kp,) (the winning local-map index per keypoint, -1: none), kp_dist, n_matches."""
-    s, keep, n_lm, n_kp = _match_keyframe(kf)
-    r, out = _match_result(n_lm, n_kp)
-    L.check(ctx.lib.ov2_match_to_map(ctx.h, C.byref(_as_match_params(params)), C.byref(s), C.byref(r)))
-    out["n_matches"] = r.n_matches
-    return out
+    return _MATCH.call(ctx, params, kf)
 
 
 def match_to_map_batch(ctx, params, kfs):
     """ov2_match_to_map_batch: the keyframes of a lock-step batch in one call (shared params).  Returns one dict per keyframe,
     as match_to_map."""
-    kfs = list(kfs)
-    S = (L.MatchKeyframe * max(1, len(kfs)))()
-    R = (L.MatchResult * max(1, len(kfs)))()
-    keep, outs = [], []
-    for b, kf in enumerate(kfs):
-        s, k, n_lm, n_kp = _match_keyframe(kf)
-        r, out = _match_result(n_lm, n_kp)
-        S[b], R[b] = s, r
-        keep.append(k); outs.append(out)
-    L.check(ctx.lib.ov2_match_to_map_batch(ctx.h, C.byref(_as_match_params(params)), len(kfs), S, R))
-    for b, out in enumerate(outs):
-        out["n_matches"] = R[b].n_matches
-    return outs
+    return _MATCH.call_batch(ctx, params, kfs)

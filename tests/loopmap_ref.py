@@ -7,8 +7,8 @@ Two independent forms:
   replay()    the two reference functions statement by statement over a dict-based toy map: the covisible-keyframe walk that
               builds set_local_lmids and appends the (lmid, lmid) pairs, vmatchedkpids, the loop over the local set with its
               `continue`s, the pick, and the matches appended to vkplmids in std::map order;
-  flat()      the per-local-map-point form over the flattened arrays of ov2_loopmap_item, i.e. what k_loop_match (csrc/loopmap.hip)
-              computes.
+  flat()      the per-local-map-point form over the flattened arrays of ov2_loopmap_item, i.e. what k_map_match<true>
+              (csrc/mapmatch.hip) computes.
 flatten() turns a toy map into those arrays (what the host does before the call); tests/test_loopmap_reference.py checks
 replay == flat o flatten on every output field, bit for bit.  The loop only reads the map, so there is no deviation to document.
 

@@ -5,7 +5,7 @@ CameraCalibration::projectCamToImageDist (src/camera_calibration.cpp:254-281) an
 Two independent forms:
   replay()    the reference loop statement by statement over a dict-based toy map (map points with set_kfids_ / map_kf_desc_,
               keyframes with mapkps_, the frame with mapkps_ / vgridkps_), `continue`s and the map clean-up included;
-  flat()      the per-map-point form over the flattened arrays of ov2_match_keyframe, i.e. what k_match (csrc/match.hip) computes.
+  flat()      the per-map-point form over the flattened arrays of ov2_match_keyframe, i.e. what k_map_match<false> (csrc/mapmatch.hip) computes.
 flatten() turns a toy map into those arrays (what the host does before the call); tests/test_match_reference.py checks
 replay == flat o flatten on every output field, bit for bit.
 

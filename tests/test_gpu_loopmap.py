@@ -1,8 +1,9 @@
-"""Loop local-map tracking on the GPU (csrc/loopmap.hip, ov2_loop_match_to_map[_batch]) against the numpy specification
+"""Loop local-map tracking on the GPU (k_map_match<true>, csrc/mapmatch.hip, ov2_loop_match_to_map[_batch]) against the numpy specification
 (tests/loopmap_ref.py, flat()): every output array bit-exact for the undistorted and the radial-tangential calibrations -- status
 bytes, indices, the float distances and projections --, the crafted shapes at which the kernel takes another path, the batch form
 against single calls, an EuRoC-sized candidate with byte-identical repeats, the fisheye model to 1 float ulp of the projection on
-margin-filtered scenes, rejected calls, and the C++ adapter (ov2slam_amd/host/loop_closer.hpp) against the literal replay."""
+margin-filtered scenes, rejected calls, the C++ adapter (ov2slam_amd/host/loop_closer.hpp) against the literal replay, and the
+mapper's call (the kernel's other instantiation) on a scene where the two reference functions coincide."""
 import ctypes as C
 import os
 import struct
@@ -13,7 +14,9 @@ import pytest
 
 from ov2slam_amd import _lib as L
 from ov2slam_amd import loop_closer as LC
+from ov2slam_amd import mapper
 from tests import loopmap_ref as R
+from tests import match_ref as MR
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,6 +62,34 @@ def test_crafted_cases_bit_exact(gpu_ctx, case):
     assert [int(s) for s in got["lm_status"]] == status
     assert [int(k) for k in got["lm_kp"]] == lm_kp
     _check(got, R.flat(M["params"], item))
+
+
+@pytest.mark.parametrize("calib", list(CALIBS))
+def test_agrees_with_the_mappers_call_where_the_functions_coincide(gpu_ctx, calib):
+    """The device form of test_loopmap_reference's side-by-side test: no matched flags, nb3dkps >= 30, equal fmaxprojerr / fdistratio,
+    every observation stale (the Mapper's re-projection gate then passes by its NaN rule), and without the points the Mapper's
+    narrower viewing cone removes.  ov2_match_to_map and ov2_loop_match_to_map then return the same arrays, those of the
+    specification: what the kernel's two instantiations share has stayed shared."""
+    P = MR.make_params(fmax_proj_pxdist=10.0, fmax_desc_dist=R.FDISTRATIO, **CALIBS[calib])
+    M = MR.make_scene(P, np.random.default_rng(5), n_kp=120, n_lm=261, nb3dkps=100)
+    kf, _ = MR.flatten(M)
+    kf["obs_kf"] = np.full_like(kf["obs_kf"], -1)
+    kf["obs_px"] = np.zeros_like(kf["obs_px"])
+    keep = MR.flat(P, kf)["lm_status"] != MR.OUT_OF_FOV
+    assert 0 < (~keep).sum() < len(keep)
+    kf["lm_mp"], kf["lm_wpt"] = kf["lm_mp"][keep], kf["lm_wpt"][keep]
+    want = MR.flat(P, kf)
+    item = {k: kf[k] for k in ("Tcw", "kp_px", "kp_mp", "cell_start", "cell_kp", "obs_start", "obs_kfid", "desc_start", "desc", "lm_mp", "lm_wpt")}
+    item["kp_matched"] = np.zeros(len(kf["kp_mp"]), np.uint8)
+    _check(R.flat(P, item), want)
+    as_mapper = mapper.match_to_map(gpu_ctx, P, kf)
+    as_loop = LC.loop_match_to_map(gpu_ctx, P, item)
+    for f in FIELDS:
+        assert np.asarray(as_mapper[f]).tobytes() == np.asarray(as_loop[f]).tobytes(), f
+    assert as_mapper["n_matches"] == as_loop["n_matches"]
+    _check(as_mapper, want)
+    _check(as_loop, want)
+    assert want["n_matches"] > 5 and (want["lm_status"] == R.RATIO_REJECTED).any() and not (as_loop["lm_status"] == R.OUT_OF_FOV).any()
 
 
 def _empty_item(P):

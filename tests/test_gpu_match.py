@@ -1,5 +1,5 @@
-"""Local-map matching on the GPU (csrc/match.hip, ov2_match_to_map[_batch]) against the numpy specification (tests/match_ref.py,
-flat()): every output array bit-exact for the undistorted and the radial-tangential calibrations -- status bytes, indices, the
+"""Local-map matching on the GPU (k_map_match<false>, csrc/mapmatch.hip, ov2_match_to_map[_batch]) against the numpy specification
+(tests/match_ref.py, flat()): every output array bit-exact for the undistorted and the radial-tangential calibrations -- status bytes, indices, the
 float distances and projections --, the crafted quirks, the batch form against single calls, an EuRoC-sized keyframe whose rows
 exceed 64 observers, byte-identical repeats, the fisheye model to 1 float ulp of the projection on margin-filtered scenes, and the
 C++ adapter (ov2slam_amd/host/mapper.hpp) against the Python form."""

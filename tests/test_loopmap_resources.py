@@ -1,38 +1,12 @@
-"""k_loop_match / k_loop_pick (ov2slam_amd/csrc/loopmap.hip): a device-only compile for gfx950 shows no scratch and at most 128 VGPRs
-(four wavefronts per SIMD), and the C ABI of the loop local-map tracking rejects bad arguments and every class of malformed input
-without a GPU (the inputs are checked before the context is touched)."""
+"""The C ABI of the loop local-map tracking (k_map_match<true> / k_map_pick, ov2slam_amd/csrc/mapmatch.hip) rejects bad arguments and
+every class of malformed input without a GPU (the inputs are checked before the context is touched).  The kernels' resources are
+checked in tests/test_match_resources.py."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import loopmap_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_k_loop_kernels_use_no_scratch_and_128_vgprs(tmp_path):
-    src = os.path.join(ROOT, "ov2slam_amd", "csrc", "loopmap.hip")
-    out = str(tmp_path / "loopmap.s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                    "--cuda-device-only", "-S", src, "-o", out], check=True, capture_output=True)
-    txt = open(out).read()
-    res = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S):
-        res[m.group(1)] = {k: int(v) for k, v in re.findall(r"\.amdhsa_(\w+) (\d+)\s", m.group(2))}
-    names = [n for n in res if "k_loop_" in n]
-    assert len(names) == 2, names
-    for n in names:
-        print(n, "vgpr", res[n]["next_free_vgpr"], "sgpr", res[n]["next_free_sgpr"], "lds", res[n]["group_segment_fixed_size"])
-        assert res[n]["private_segment_fixed_size"] == 0, (n, res[n])
-        assert res[n]["next_free_vgpr"] <= 128, (n, res[n])
-        assert res[n]["group_segment_fixed_size"] == 0, (n, res[n])
 
 
 def _lib():

@@ -1,5 +1,5 @@
 """The specification of the local-map matching (tests/match_ref.py) against itself: the literal replay of the reference loop
-(Mapper::matchToMap, src/mapper.cpp:576-774) and the flattened per-map-point form that k_match implements agree bit for bit on
+(Mapper::matchToMap, src/mapper.cpp:576-774) and the flattened per-map-point form that k_map_match<false> implements agree bit for bit on
 randomised scenes that make the interesting paths common, the crafted quirks behave as the header says, and the forward
 distortion model agrees with the published model evaluated in extended precision.  No GPU."""
 import copy

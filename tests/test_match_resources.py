@@ -1,5 +1,6 @@
-"""k_match / k_match_pick (ov2slam_amd/csrc/match.hip): a device-only compile for gfx950 shows no scratch and at most 128 VGPRs
-(four wavefronts per SIMD), and the C ABI of the local-map matching rejects bad arguments and every class of malformed input
+"""k_map_match<false / true> / k_map_pick (ov2slam_amd/csrc/mapmatch.hip): a device-only compile for gfx950 shows no scratch, no LDS,
+at most 128 VGPRs (four wavefronts per SIMD) and no more VGPRs per instantiation than the mapper's and the loop closer's kernels took
+as separate files, and the C ABI of the local-map matching rejects bad arguments and every class of malformed input
 without a GPU (the inputs are checked before the context is touched)."""
 import ctypes as C
 import os
@@ -17,20 +18,28 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_k_match_kernels_use_no_scratch_and_128_vgprs(tmp_path):
-    src = os.path.join(ROOT, "ov2slam_amd", "csrc", "match.hip")
-    out = str(tmp_path / "match.s")
+def test_k_map_kernels_use_no_scratch_no_lds_and_their_vgpr_budgets(tmp_path):
+    src = os.path.join(ROOT, "ov2slam_amd", "csrc", "mapmatch.hip")
+    out = str(tmp_path / "mapmatch.s")
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
                     "--cuda-device-only", "-S", src, "-o", out], check=True, capture_output=True)
     txt = open(out).read()
     res = {}
     for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S):
         res[m.group(1)] = {k: int(v) for k, v in re.findall(r"\.amdhsa_(\w+) (\d+)\s", m.group(2))}
-    names = [n for n in res if "k_match" in n]
-    assert len(names) == 2, names
-    for n in names:
+    # exactly three kernels: the two instantiations of k_map_match (Itanium mangling: ILb0E = <false>, ILb1E = <true>) and k_map_pick
+    assert len(res) == 3, sorted(res)
+    mapper = [n for n in res if "k_map_match" in n and "ILb0E" in n]
+    loop = [n for n in res if "k_map_match" in n and "ILb1E" in n]
+    pick = [n for n in res if "k_map_pick" in n]
+    assert len(mapper) == len(loop) == len(pick) == 1, sorted(res)
+    for n in res:
+        print(n, "vgpr", res[n]["next_free_vgpr"], "sgpr", res[n]["next_free_sgpr"], "lds", res[n]["group_segment_fixed_size"])
         assert res[n]["private_segment_fixed_size"] == 0, (n, res[n])
+        assert res[n]["group_segment_fixed_size"] == 0, (n, res[n])
         assert res[n]["next_free_vgpr"] <= 128, (n, res[n])
+    assert res[mapper[0]]["next_free_vgpr"] <= 115, res[mapper[0]]       # what the mapper's kernel took in a file of its own
+    assert res[loop[0]]["next_free_vgpr"] <= 72, res[loop[0]]            # what the loop closer's kernel took in a file of its own
 
 
 def _lib():
@@ -109,12 +118,14 @@ MALFORMED = [
     ("lm_mp_negative", lambda kf: _mod(kf, "lm_mp", lambda a: a.__setitem__(0, -1)), b"lm_mp"),
     ("obs_kf_outside", lambda kf: _mod(kf, "obs_kf", lambda a: a.__setitem__(0, len(kf["kf_Tcw"]))), b"obs_kf"),
     ("cell_kp_outside", lambda kf: _mod(kf, "cell_kp", lambda a: a.__setitem__(0, len(kf["kp_mp"]))), b"cell_kp"),
+    ("cell_kp_negative", lambda kf: _mod(kf, "cell_kp", lambda a: a.__setitem__(0, -1)), b"cell_kp"),
     ("obs_kfid_unsorted", lambda kf: _mod(kf, "obs_kfid", lambda a: a.__setitem__(kf["obs_start"][_first_row_with_two_obs(kf)] + 1,
                                                                                    a[kf["obs_start"][_first_row_with_two_obs(kf)]])), b"unsorted"),
     ("obs_start_decreases", lambda kf: _mod(kf, "obs_start", lambda a: a.__setitem__(1, a[2] + 1)), b"obs_start"),
     ("desc_start_decreases", lambda kf: _mod(kf, "desc_start", lambda a: a.__setitem__(1, a[2] + 1)), b"desc_start"),
     ("cell_start_decreases", lambda kf: _mod(kf, "cell_start", lambda a: a.__setitem__(1, a[-1] + 1)), b"cell_start"),
     ("obs_start_not_from_zero", lambda kf: _mod(kf, "obs_start", lambda a: a.__setitem__(0, -1)), b"obs_start"),
+    ("cell_start_not_from_zero", lambda kf: _mod(kf, "cell_start", lambda a: a.__setitem__(0, 1)), b"cell_start"),
 ]
 
 
@@ -159,17 +170,19 @@ def test_negative_counts_and_null_arrays():
         r, out = mapper._match_result(n_lm, n_kp)
         assert lib.ov2_match_to_map(None, C.byref(_params()), C.byref(s), C.byref(r)) == L.OV2_EINVAL
         assert b"negative count" in lib.ov2_last_error()
-    for field in ("Tcw", "kp_px", "kp_mp", "cell_start", "obs_start", "desc", "kf_Tcw", "lm_wpt"):
+    for field in ("Tcw", "kp_px", "kp_mp", "cell_start", "cell_kp", "obs_start", "obs_kfid", "obs_kf", "obs_px", "desc_start", "desc", "kf_Tcw",
+                  "lm_mp", "lm_wpt"):
         s, keep, n_lm, n_kp = mapper._match_keyframe(kf)
         setattr(s, field, None)
         r, out = mapper._match_result(n_lm, n_kp)
         assert lib.ov2_match_to_map(None, C.byref(_params()), C.byref(s), C.byref(r)) == L.OV2_EINVAL, field
         assert b"NULL" in lib.ov2_last_error() and b"NULL context" not in lib.ov2_last_error(), field
-    s, keep, n_lm, n_kp = mapper._match_keyframe(kf)
-    r, out = mapper._match_result(n_lm, n_kp)
-    r.lm_dist = None
-    assert lib.ov2_match_to_map(None, C.byref(_params()), C.byref(s), C.byref(r)) == L.OV2_EINVAL
-    assert b"result buffer" in lib.ov2_last_error()
+    for field in ("lm_status", "lm_kp", "lm_dist", "lm_projpx", "kp_lm", "kp_dist"):
+        s, keep, n_lm, n_kp = mapper._match_keyframe(kf)
+        r, out = mapper._match_result(n_lm, n_kp)
+        setattr(r, field, None)
+        assert lib.ov2_match_to_map(None, C.byref(_params()), C.byref(s), C.byref(r)) == L.OV2_EINVAL, field
+        assert b"result buffer" in lib.ov2_last_error(), field
 
 
 def test_unsupported_parameters():

@@ -1,7 +1,7 @@
-"""Wall time of the loop local-map tracking on the GPU (csrc/loopmap.hip), host synchronisation included:
+"""Wall time of the loop local-map tracking on the GPU (csrc/mapmatch.hip), host synchronisation included:
 
     python tools/loopmap_time.py [reps] [batch sizes, default 11,4096] [output.json]
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/loopmap_time.py --one 11 5   (device time of k_loop_match / k_loop_pick
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/loopmap_time.py --one 11 5   (device time of k_map_match<true> / k_map_pick
                                                                   per launch; --one B REPS measures one size in this process, B = 0:
                                                                   single, B = -1: ov2_match_to_map on the same scene)
 

@@ -1,7 +1,7 @@
-"""Wall time of the local-map matching on the GPU (csrc/match.hip), host synchronisation included:
+"""Wall time of the local-map matching on the GPU (csrc/mapmatch.hip), host synchronisation included:
 
     python tools/match_time.py [reps] [batch sizes, default 11,4096] [output.json]
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/match_time.py --one 11 5     (device time of k_match / k_match_pick per
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/match_time.py --one 11 5     (device time of k_map_match<false> / k_map_pick per
                                                                   launch; --one B REPS measures one size in this process, B = 0: single)
 
 Prints one JSON line (and writes it to output.json when given): medians after one warm-up call, in us, of ov2_match_to_map for one
