@@ -447,6 +447,8 @@ __device__ __forceinline__ uint32_t c_wave_shl1(uint32_t v) { return (uint32_t)_
 #define CS_UNROLL 6
 #define CS_MAX_STRIPS 8
 #define CS_LUT_PRIO 3     // s_setprio of the fused kernel's LUT wavefront
+enum { CS_MID = 0, CS_EDGE = 1, CS_ANY = 2 };      // what a strip holds of the image's edges (compile-time tag of a row)
+template <int E> using cs_tag = std::integral_constant<int, E>;
 // UNAL: w % 4 != 0 or an odd level-1 width (the generic right edge); false keeps the w % 4 == 0 instance free of its per-lane
 // selectors (they cost three spilled registers at this kernel's 80-VGPR budget)
 // FUSED (round 4): the work-group has one more wavefront, which computes the tile LUTs (clahe_lut_tiles: histogram, clip, scan) of the
@@ -564,11 +566,22 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     const uint32_t xo = (d == ndw - 1 && wr) ? (uint32_t)(P.w - 4) : (uint32_t)xb;
     const uint32_t in_sh = (d == ndw - 1 && wr) ? 8u * (4u - (uint32_t)wr) : 0u;
 
+    // The vertical weights ya, 1 - ya of a row are wave-uniform: lane i holds those of row y_tab + i (the same float expression a
+    // row evaluated for itself, so the same bits), and a row fetches its pair with two v_readlane_b32 into scalar registers --
+    // the packed blend takes them as its scalar operand.  64 rows per table: a taller row of cells refills it on the way.
+    int y_tab = 0;
+    float wya = 0.f, wyb = 0.f;
+    auto ytab = [&](int y) {
+        y_tab = y;
+        const float tyf = (float)(y + lane) * P.inv_th - 0.5f;
+        wya = tyf - (float)(cy - 1); wyb = 1.0f - wya;
+    };
     auto stage = [&](int y) {
         cy = cell_row(y);
         int yn = max(y + 1, (int)(((float)cy + 0.5f) * (float)P.th) - 2);
         while (yn < P.h && cell_row(yn) == cy) yn++;
         y_switch = yn;
+        ytab(y);
         build(cy);
     };
     // buffer addressing (round 4): one descriptor per image, the row as a scalar offset, the lane's column as a 32-bit offset -- no
@@ -578,53 +591,59 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     const __amdgpu_buffer_rsrc_t rs_dst = __builtin_amdgcn_make_buffer_rsrc(dbase, 0, 0x7fffffff, 0x00020000);
     const uint8_t *sbase = src + (long long)b * P.src_item_stride;
     const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void *)sbase, 0, 0x7fffffff, 0x00020000);
+    // Rows are 32-bit byte offsets into the descriptor (one scalar register each, one scalar add per row; the 64-bit row pointers
+    // they replace were spilled and reloaded in every row).  EDGE (compile time) says what the strip holds of the image's edges:
+    // CS_MID nothing -- no first / last column, no border lane, so rows without any of that code; CS_EDGE border lanes for certain
+    // (their stores need no test); CS_ANY whatever edge_strip, first_col and last_col say at run time (the rolled rows).
+    const int so_d0 = (int)(d0m - dbase), so_d1 = (int)(d1m - dbase);
+    const bool mid_strip = !edge_strip && d_first > 0 && d_first + 63 < ndw - 1;    // (uniform) no first / last column, no border lane
+    auto cs_edge = [&](auto edge_c) { return decltype(edge_c)::value == CS_EDGE || (decltype(edge_c)::value == CS_ANY && edge_strip); };
     // a level-0 row: every lane's dword and, in the edge strips, the border dword
-    auto put0 = [&](uint8_t *row, uint32_t v, uint32_t bv) {
-        const int so = (int)(row - dbase);
+    auto put0 = [&](int so, uint32_t v, uint32_t bv, auto edge_c) {
         __builtin_amdgcn_raw_buffer_store_b32(v, rs_dst, (int)o0, so, 0);
-        if (edge_strip) __builtin_amdgcn_raw_buffer_store_b32(bv, rs_dst, (int)o0b, so, 0);
+        if (cs_edge(edge_c)) __builtin_amdgcn_raw_buffer_store_b32(bv, rs_dst, (int)o0b, so, 0);
     };
-    auto put1 = [&](uint8_t *row, uint32_t v, uint32_t bv) {               // a level-1 row: pixel pairs
-        const int so = (int)(row - dbase);
+    auto put1 = [&](int so, uint32_t v, uint32_t bv, auto edge_c) {         // a level-1 row: pixel pairs
         __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, rs_dst, (int)o1, so, 0);
-        if (edge_strip) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bv, rs_dst, (int)o1b, so, 0);
+        if (cs_edge(edge_c)) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bv, rs_dst, (int)o1b, so, 0);
     };
     typedef unsigned short cu16x2 __attribute__((ext_vector_type(2)));
-    uint8_t *r1 = d1m;                                                  // level-1 row of the next emit
+    int r1 = so_d1;                                                     // level-1 row of the next emit
     // level-1 row Y from the horizontal sums of level-0 rows 2Y-2 .. 2Y+2 (packed pairs, <= 16 * 255 each); rows are emitted in order.
     // The REFLECT_101 border mirrors rows 1 .. win above the image and rows h1-1-win .. h1-2 below it: the same stores once more
-    auto emit = [&](int Y, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4, auto mirror_c) {
+    auto emit = [&](int Y, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4, auto mirror_c, auto edge_c) {
         constexpr bool MIRROR = decltype(mirror_c)::value;
         const cu16x2 s0 = __builtin_bit_cast(cu16x2, c0), s1 = __builtin_bit_cast(cu16x2, c1), s2 = __builtin_bit_cast(cu16x2, c2),
                      s3 = __builtin_bit_cast(cu16x2, c3), s4 = __builtin_bit_cast(cu16x2, c4);
         const cu16x2 v = (s2 * (unsigned short)6 + (s1 + s3) * (unsigned short)4 + s0 + s4 + (unsigned short)128) >> (unsigned short)8;
         uint32_t o = __builtin_amdgcn_perm(0u, __builtin_bit_cast(uint32_t, v), 0x0c0c0200u);       // (v0, v1) as two bytes
         uint32_t bv = 0;
-        if (edge_strip) {
+        if (cs_edge(edge_c)) {
             bv = __builtin_amdgcn_perm(c_wave_shr1(o), o, 0x0c0c0500u);    // border pair: (own first pixel, left neighbour's second)
             if (UNAL && fix1) o = bv;                                              // odd level-1 width: the last pair's second pixel is border
         }
-        put1(r1, o, bv);
+        put1(r1, o, bv, edge_c);
         r1 += P.l1_pitch;
         if (MIRROR) {
-            if (Y >= 1 && Y <= win) put1(d1m - (long long)Y * P.l1_pitch, o, bv);
-            if (Y >= P.l1_h - 1 - win && Y <= P.l1_h - 2) put1(d1m + (long long)(2 * (P.l1_h - 1) - Y) * P.l1_pitch, o, bv);
+            if (Y >= 1 && Y <= win) put1(so_d1 - Y * P.l1_pitch, o, bv, edge_c);
+            if (Y >= P.l1_h - 1 - win && Y <= P.l1_h - 2) put1(so_d1 + (2 * (P.l1_h - 1) - Y) * P.l1_pitch, o, bv, edge_c);
         }
     };
 
     uint32_t hA = 0, hB = 0, hC = 0, hD = 0, hE = 0;                      // horizontal sums of rows y-4 .. y
     const uint8_t *srow = src + (long long)b * P.src_item_stride;        // (uniform) source row of the next prefetch
-    uint8_t *r0 = d0m;                                                  // level-0 row of the next store
+    int r0 = so_d0;                                                     // level-0 row of the next store
     uint32_t inr[CS_UNROLL], nxt[CS_UNROLL];
 #pragma unroll
     for (int u = 0; u < CS_UNROLL; u++) inr[u] = *(const cs_u32_a1 *)(srow + (long long)min(u, P.h - 1) * P.stride + xo) >> (UNAL ? in_sh : 0u);
     srow += (long long)CS_UNROLL * P.stride;
     // one row: CLAHE blend of the lane's four pixels, level-0 stores, horizontal pyrDown sums into the rolling window.
     // MIRROR: the row may be one the REFLECT_101 border mirrors (-y for 1 <= y <= win, 2 (h-1) - y for h-1-win <= y <= h-2)
-    auto do_row = [&](int y, uint32_t in, auto mirror_c) {
+    auto do_row = [&](int y, uint32_t in, auto mirror_c, auto edge_c) {
         constexpr bool MIRROR = decltype(mirror_c)::value;
-        const float tyf = (float)y * P.inv_th - 0.5f;
-        const float ya = tyf - (float)(cy - 1), ya1 = 1.0f - ya;
+        constexpr int EDGE = decltype(edge_c)::value;
+        const float ya = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wya), y - y_tab));
+        const float ya1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wyb), y - y_tab));
         const c_f32x2 YA = {ya, ya}, YB = {ya1, ya1};
         const uint32_t q0 = lutc[0][in & 0xFF], q1 = lutc[1][(in >> 8) & 0xFF], q2 = lutc[2][(in >> 16) & 0xFF], q3 = lutc[3][in >> 24];
         const c_f32x2 A11 = {c_ub(q0, 0), c_ub(q1, 0)}, A12 = {c_ub(q0, 1), c_ub(q1, 1)}, A21 = {c_ub(q0, 2), c_ub(q1, 2)}, A22 = {c_ub(q0, 3), c_ub(q1, 3)};
@@ -640,20 +659,22 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         uint32_t out = __builtin_amdgcn_perm(__builtin_amdgcn_perm(u3, u2, 0x0c0c0400u), __builtin_amdgcn_perm(u1, u0, 0x0c0c0400u), 0x05040100u);
         // neighbours: pixels xb-2, xb-1 (left lane's bytes 2, 3) and xb+4 (right lane's byte 0); REFLECT_101 at the image edge
         uint32_t lf = c_wave_shr1(out), rt = c_wave_shl1(out);
-        if (first_col) lf = __builtin_amdgcn_perm(out, out, 0x01020000u);      // (.., .., p2, p1)
-        if (edge_strip) {
-            if (UNAL) out = __builtin_amdgcn_perm(out, lf, sel_fix);           // (identity except in the last column of a width % 4 != 0)
-        }
-        if (UNAL) { if (last_col) rt = __builtin_amdgcn_perm(out, lf, sel_rt); }   // p[xb + 4] mirrored about w - 1
-        else if (last_col) rt = out >> 16;                                      // p(w) = p(w-2)
         uint32_t bv = 0;                                                        // border dword of the edge lanes:
-        if (edge_strip)                                                         // (p[4d+4], p[4d+3], p[4d+2], p[4d+1]) left, p[top .. top-3] right
-            bv = bl0 ? __builtin_amdgcn_perm(out, rt, 0x05060700u) : __builtin_amdgcn_perm(out, lf, sel_br);
-        put0(r0, out, bv);
+        if (EDGE != CS_MID) {
+            if (first_col) lf = __builtin_amdgcn_perm(out, out, 0x01020000u);      // (.., .., p2, p1)
+            if (cs_edge(edge_c)) {
+                if (UNAL) out = __builtin_amdgcn_perm(out, lf, sel_fix);           // (identity except in the last column of a width % 4 != 0)
+            }
+            if (UNAL) { if (last_col) rt = __builtin_amdgcn_perm(out, lf, sel_rt); }   // p[xb + 4] mirrored about w - 1
+            else if (last_col) rt = out >> 16;                                      // p(w) = p(w-2)
+            if (cs_edge(edge_c))                                                    // (p[4d+4], p[4d+3], p[4d+2], p[4d+1]) left, p[top .. top-3] right
+                bv = bl0 ? __builtin_amdgcn_perm(out, rt, 0x05060700u) : __builtin_amdgcn_perm(out, lf, sel_br);
+        }
+        put0(r0, out, bv, edge_c);
         r0 += P.dst_stride;
         if (MIRROR) {
-            if (y >= 1 && y <= win) put0(d0m - (long long)y * P.dst_stride, out, bv);
-            if (y >= P.h - 1 - win && y <= P.h - 2) put0(d0m + (long long)(2 * (P.h - 1) - y) * P.dst_stride, out, bv);
+            if (y >= 1 && y <= win) put0(so_d0 - y * P.dst_stride, out, bv, edge_c);
+            if (y >= P.h - 1 - win && y <= P.h - 2) put0(so_d0 + (2 * (P.h - 1) - y) * P.dst_stride, out, bv, edge_c);
         }
         // pyrDown, horizontal: sums centred on pixels xb and xb + 2
         const uint32_t l0 = __builtin_amdgcn_alignbyte(out, lf, 2);
@@ -665,6 +686,8 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     // table of its row of cells is already staged, all six rows exist -- straight-line code, so that the look-ups and loads of
     // one row overlap the arithmetic of another.  The few others (top / bottom of the image, a switch of tables inside the
     // group) take the rolled loop below with every test per row.
+    // yb < fast_end: yb + CS_UNROLL - 1 < h - 1 - win, yb + CS_UNROLL - 4 < 2 (l1_h - 1 - win) and yb + CS_UNROLL <= h in one bound
+    const int fast_end = min(min(P.h - win - CS_UNROLL, 2 * (P.l1_h - 1 - win) - CS_UNROLL + 4), P.h - CS_UNROLL + 1);
     for (int yb = 0; yb < P.h; yb += CS_UNROLL) {
         if (yb + 2 * CS_UNROLL <= P.h) {
 #pragma unroll
@@ -676,24 +699,34 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         }
         if (yb == y_switch) stage(yb);
         // (level-0 rows yb .. yb+5 and the level-1 rows (yb-2)/2 .. (yb+2)/2 they complete are not mirrored by a border)
-        const bool fast = yb > 2 * win + 2 && yb + CS_UNROLL - 1 < P.h - 1 - win && yb + CS_UNROLL - 4 < 2 * (P.l1_h - 1 - win) &&
-                          y_switch >= yb + CS_UNROLL && yb + CS_UNROLL <= P.h;
+        const bool fast = yb > 2 * win + 2 && yb < fast_end && y_switch >= yb + CS_UNROLL;
         if (fast) {
+            if (yb + CS_UNROLL > y_tab + 64) ytab(yb);
+            auto group = [&](auto edge_c) {
+                // The instances start with the same code (index extraction and table addresses of all six rows), which the compiler
+                // would hoist above the choice between them -- 24 registers held across the whole group, and spills.  The rows'
+                // inputs pass through an empty statement that differs per instance, so nothing of them is common.
+                asm volatile("; strip kind %6" : "+v"(inr[0]), "+v"(inr[1]), "+v"(inr[2]), "+v"(inr[3]), "+v"(inr[4]), "+v"(inr[5]) : "i"(decltype(edge_c)::value));
 #pragma unroll
-            for (int u = 0; u < CS_UNROLL; u++) {
-                do_row(yb + u, inr[u], std::false_type());
-                if ((u & 1) == 0) emit((yb + u - 2) >> 1, hA, hB, hC, hD, hE, std::false_type());   // yb is even, > 2
-            }
+                for (int u = 0; u < CS_UNROLL; u++) {
+                    do_row(yb + u, inr[u], std::false_type(), edge_c);
+                    if ((u & 1) == 0) emit((yb + u - 2) >> 1, hA, hB, hC, hD, hE, std::false_type(), edge_c);   // yb is even, > 2
+                }
+            };
+            if (mid_strip) group(cs_tag<CS_MID>());
+            else if (edge_strip) group(cs_tag<CS_EDGE>());
+            else group(cs_tag<CS_ANY>());
         } else {
 #pragma nounroll
             for (int u = 0; u < CS_UNROLL; u++) {
                 const int y = yb + u;
                 if (y >= P.h) break;
                 if (y == y_switch) stage(y);
-                do_row(y, inr[0], std::true_type());
+                if (y >= y_tab + 64) ytab(y);
+                do_row(y, inr[0], std::true_type(), cs_tag<CS_ANY>());
                 if (!(y & 1)) {
-                    if (y == 2) emit(0, hE, hD, hC, hD, hE, std::true_type());        // rows -2, -1 mirror rows 2, 1
-                    else if (y > 2) emit((y - 2) >> 1, hA, hB, hC, hD, hE, std::true_type());
+                    if (y == 2) emit(0, hE, hD, hC, hD, hE, std::true_type(), cs_tag<CS_ANY>());        // rows -2, -1 mirror rows 2, 1
+                    else if (y > 2) emit((y - 2) >> 1, hA, hB, hC, hD, hE, std::true_type(), cs_tag<CS_ANY>());
                 }
 #pragma unroll
                 for (int k = 0; k + 1 < CS_UNROLL; k++) inr[k] = inr[k + 1];
@@ -703,8 +736,8 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         for (int u = 0; u < CS_UNROLL; u++) inr[u] = nxt[u];
     }
     // the last level-1 row: its window hangs over the bottom edge (row h mirrors h-2, row h+1 mirrors h-3)
-    if (P.h & 1) emit((P.h - 1) >> 1, hC, hD, hE, hD, hC, std::true_type());
-    else emit((P.h - 2) >> 1, hB, hC, hD, hE, hD, std::true_type());
+    if (P.h & 1) emit((P.h - 1) >> 1, hC, hD, hE, hD, hC, std::true_type(), cs_tag<CS_ANY>());
+    else emit((P.h - 2) >> 1, hB, hC, hD, hE, hD, std::true_type(), cs_tag<CS_ANY>());
 }
 
 int ov2_launch_clahe(ov2_ctx *ctx, const uint8_t *src_d, int w, int h, int stride, size_t src_batch_stride, int batch,

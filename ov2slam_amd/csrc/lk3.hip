@@ -87,6 +87,17 @@ __device__ __forceinline__ int dot2r(uint32_t a, uint32_t b)
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c256));
     return r;
 }
+// a.lo * b.lo + a.hi * b.hi + 2^15, the rounding constant of the derivative taps, likewise (the two-address form loads it into
+// the destination with a v_mov first: 54 of them per template build)
+__device__ __forceinline__ int dot2h(uint32_t a, uint32_t b)
+{
+    int r;
+    const int c32k = __builtin_amdgcn_readfirstlane(1 << 15);
+    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c32k));
+    return r;
+}
+// a.lo * b.lo + a.hi * b.hi + c into a register of its own (the two-address form copies c first where c lives on)
+__device__ __forceinline__ int dot2a(uint32_t a, uint32_t b, int c) { int r; asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 // A v_perm_b32 selector in a scalar register: VOP3 takes no literal here, and left to itself the compiler keeps each selector
 // in a VGPR for the whole kernel (four of them -- registers the 4-wavefront budget of 128 does not have).
 template <uint32_t K>
@@ -362,8 +373,8 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 const uint32_t xb = (x & 1) ? odd_pair(dxb[(x >> 1) + 1], dxb[x >> 1]) : dxb[x >> 1];
                 const uint32_t yt = (x & 1) ? odd_pair(dyt[(x >> 1) + 1], dyt[x >> 1]) : dyt[x >> 1];
                 const uint32_t yb = (x & 1) ? odd_pair(dyb[(x >> 1) + 1], dyb[x >> 1]) : dyb[x >> 1];
-                xv = dot2(xt, W01, dot2(xb, W23, 1 << 15));         // 4 S + 2^15: descaled by hi16_pair
-                yv = dot2(yt, W01, dot2(yb, W23, 1 << 15));
+                xv = dot2(xt, W01, dot2h(xb, W23));                 // 4 S + 2^15: descaled by hi16_pair
+                yv = dot2(yt, W01, dot2h(yb, W23));
             };
 #pragma unroll
             for (int t = 0; t < 5; t++) {
@@ -373,6 +384,14 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 const uint32_t Ipair = shr9_pair(i0, i1);
                 T.X[j][t] = hi16_pair(x0, x1);
                 T.Y[j][t] = hi16_pair(y0, y1);
+                if (j == 0 && t == 0) {                             // the first products start the sums: no accumulator to clear
+                    s11 = dot2z(T.X[j][t], T.X[j][t]);
+                    s12 = dot2z(T.X[j][t], T.Y[j][t]);
+                    s22 = dot2z(T.Y[j][t], T.Y[j][t]);
+                    T.cIX = dot2z(Ipair, T.X[j][t]);
+                    T.cIY = dot2z(Ipair, T.Y[j][t]);
+                    continue;
+                }
                 s11 = dot2(T.X[j][t], T.X[j][t], s11);
                 s12 = dot2(T.X[j][t], T.Y[j][t], s12);
                 s22 = dot2(T.Y[j][t], T.Y[j][t], s22);
@@ -454,7 +473,9 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
                 }
                 // sum (J - I) dI = sum J dI - sum I dI: the accumulators start at minus the template's constants; every partial
                 // sum is  sum_done (J - I) dI - sum_rest I dI,  |.| <= 27 * 8160 * 4080 = 9e8 < 2^30
-                int sb1 = -T.cIX, sb2 = -T.cIY;
+                // (the first product takes the start value as a third operand: accumulating in place would copy it in every trip)
+                const int nIX = -T.cIX, nIY = -T.cIY;
+                int sb1, sb2;
 #pragma unroll
                 for (int j = 0; j < L3_RPL; j++) {
                     int v[WIN + 1];
@@ -464,8 +485,8 @@ __device__ __forceinline__ void l3_level(const uint8_t *__restrict__ itemI, cons
 #pragma unroll
                     for (int t = 0; t < 5; t++) {
                         const uint32_t Jpair = shr9_pair(v[2 * t], v[2 * t + 1]);
-                        sb1 = dot2(Jpair, T.X[j][t], sb1);
-                        sb2 = dot2(Jpair, T.Y[j][t], sb2);
+                        sb1 = (j == 0 && t == 0) ? dot2a(Jpair, T.X[j][t], nIX) : dot2(Jpair, T.X[j][t], sb1);
+                        sb2 = (j == 0 && t == 0) ? dot2a(Jpair, T.Y[j][t], nIY) : dot2(Jpair, T.Y[j][t], sb2);
                     }
                 }
                 const float b1 = l3_sum3_f32(sb1, sub) * FLT_SCALE;
