@@ -1613,6 +1613,121 @@ int ov2_sampson_filter_2d(ov2_ctx *ctx, const ov2_fkf_item *item, const double F
 int ov2_sampson_filter_2d_batch(ov2_ctx *ctx, int n_items, const ov2_fkf_item *items, const double *Fkfcur, float fransac_err,
                                 ov2_sampson2d_result *results);
 
+/* ---- tracking priors (priors.hip): where the reference derives the priors that its KLT calls start from ----------------------
+ *   ov2_klt_priors      VisualFrontEnd::kltTracking (src/visual_front_end.cpp:156-184): the map point of every 3-D keypoint
+ *                       projected with the predicted pose (Frame::projWorldToImageDist, Frame::isInImage)
+ *   ov2_stereo_priors   MapManager::stereoMatching (src/map_manager.cpp:396-489): the map point projected into the right image
+ *                       (projWorldToRightImageDist, isInRightImage) and, without rectification (:438-484), the inverse-distance-
+ *                       weighted depth of the 3-D neighbours of Frame::getSurroundingKeypoints(const Keypoint&) (frame.cpp:594-622)
+ *                       pushed through projCamToRightImageDist
+ * One lane per keypoint, fp64 without contraction; poses are [tx ty tz qx qy qz qw] as held.  The caller passes the predicted
+ * pose: MotionModel is not part of this.
+ *
+ * Frame form, per keypoint:
+ *   campt  = Tcw * wpt                          (Sophus SE3d * Vector3d; Tcw = the predicted Twc, inverted by the caller)
+ *   projpx = projectCamToImageDist(campt)       (camera_calibration.cpp:254-281, as ov2_match_to_map)
+ *   has_prior = klt_use_prior && is3d && projpx in [0, img_w) x [0, img_h);  prior = has_prior ? projpx : px
+ * THERE IS NO DEPTH GATE, as there is none in the reference: a point behind the camera may project into the image and then
+ * carries a prior.  NaN / infinity fails isInImage.  wpt is not read where is3d == 0.
+ *
+ * Stereo form, per keypoint, by `state` (0 = 2-D; 1 = 3-D with a live map point; 2 = 3-D whose map point is gone: the reference
+ * removes the observation and `continue`s, :415-418):
+ *   state 2   has_prior = 0, skip = 1
+ *   state 1   projpt = rightcam.projectCamToImageDist(Tcic0 * (Tcw * wpt)); in the right image: has_prior = 1, done;
+ *             else it falls through to the neighbour branch, as in the reference
+ *   rect != 0 stop: the SAD prior lives inside ov2_stereo_match
+ *   neighbours  rkp / ckp = floor(px.y / ncellsize) / floor(px.x / ncellsize) (float division); cells (rkp-1, ckp-1),
+ *             (rkp-1, ckp), (rkp, ckp-1), (rkp, ckp) in that order, r < 0 / c < 0 skipped, cell_kp order inside a cell; the
+ *             keypoint itself excluded; neighbours with state == 1 kept.  Per kept neighbour, in that order, double accumulators:
+ *                coef = 1. / cv::norm(cokp.unpx - kp.unpx)   (difference in float, norm in double)
+ *                weights += coef;  mean_z += coef * (Tcw * wpt_co).z
+ *             With at least one: mean_z /= weights; pred = mean_z * (bv / bv.z) (component-wise division first);
+ *             projpt = rightcam.projectCamToImageDist(Tcic0 * pred); in the right image: has_prior = 2.
+ *             A coincident neighbour gives coef = inf, hence NaN, hence no prior, as in the reference.
+ *   A row or column of the 2 x 2 block that lies outside the grid (px outside the image, or not finite) is skipped where the
+ *   reference's vgridkps_.at() would throw or wrap.  The grid is ceil(img_w / ncellsize) x ceil(img_h / ncellsize) in float
+ *   (frame.cpp:41-43): the two cameras of a rig share one image size.
+ * Outputs: prior (px where there is none), has_prior (0 / 1 / 2), skip.  prior and has_prior ARE EXACTLY what
+ * ov2_stereo_match[_batch] takes as priors3d_h and has_prior3d_h: non-zero means a prior (both kinds join v3dpriors, :411 / :477).
+ *
+ * OV2_EINVAL: a NULL argument, a negative count, a NULL array with a non-zero count, cell_kp outside its table, cell_start that
+ * does not start at 0 or decreases, img_w / img_h / ncellsize not positive, state > 2.  OV2_EUNSUPPORTED: a coefficient count the
+ * model does not take (pinhole 0 / 4 / 5 / 8 / 12, fisheye 0 / 4), more than 65535 items, more than 2^31 - 1 elements of one kind.
+ * All of it is checked on the host before the context is touched; a rejected call writes nothing.  An item without keypoints is
+ * allowed.  Each call is one upload, one launch, one download, one host synchronisation. */
+typedef struct {
+    int model;                   /* OV2_CAM_PINHOLE / OV2_CAM_FISHEYE: the left camera                                       */
+    double K[4];                 /* fx fy cx cy                                                                              */
+    const double *D;             /* nD distortion coefficients (NULL when nD == 0)                                           */
+    int nD;
+    double img_w, img_h;         /* pcalib_leftcam_->img_w_ / img_h_                                                         */
+    int klt_use_prior;           /* SlamParams::klt_use_prior_                                                               */
+} ov2_klt_priors_params;
+typedef struct {
+    const double *Tcw;           /* 7: the predicted pose, already inverted                                                  */
+    int n;
+    const float *px;             /* 2 n: Keypoint::px_                                                                       */
+    const uint8_t *is3d;         /* n                                                                                        */
+    const double *wpt;           /* 3 n: the map point (not read where is3d == 0)                                            */
+} ov2_klt_priors_item;
+typedef struct {
+    float *prior;                /* 2 n                                                                                      */
+    uint8_t *has_prior;          /* n: 0 / 1                                                                                 */
+    int n_prior;                 /* keypoints with a prior                                                                   */
+} ov2_klt_priors_result;
+typedef struct {
+    int model;                   /* the RIGHT camera                                                                         */
+    double K[4];
+    const double *D;
+    int nD;
+    double img_w, img_h;         /* pcalib_rightcam_->img_w_ / img_h_; also the size behind the keypoint grid                */
+    double Tcic0[7];             /* pcalib_rightcam_->Tcic0_                                                                 */
+    int ncellsize;               /* Frame::ncellsize_                                                                        */
+    int rect;                    /* SlamParams::bdo_stereo_rect_                                                             */
+} ov2_stereo_priors_params;
+typedef struct {
+    const double *Tcw;           /* 7: the keyframe's Tcw_                                                                   */
+    int n;
+    const float *px;             /* 2 n: px_                                                                                 */
+    const float *unpx;           /* 2 n: unpx_                                                                               */
+    const double *bv;            /* 3 n: bv_                                                                                 */
+    const double *wpt;           /* 3 n: the map point (read where state == 1)                                               */
+    const uint8_t *state;        /* n: 0 / 1 / 2                                                                             */
+    const int *cell_start;       /* ncells + 1 offsets into cell_kp, as in ov2_match_keyframe (may be NULL when rect != 0)   */
+    const int *cell_kp;          /* keypoint rows, per cell in vgridkps_ order                                               */
+} ov2_stereo_priors_item;
+typedef struct {
+    float *prior;                /* 2 n: priors3d_h of ov2_stereo_match                                                      */
+    uint8_t *has_prior;          /* n: 0, 1 (map point) or 2 (neighbours): has_prior3d_h of ov2_stereo_match                 */
+    uint8_t *skip;               /* n: 1 = the reference drops the keypoint from the matching (state 2)                      */
+    int n_prior3d, n_prior_nb, n_skip;
+} ov2_stereo_priors_result;
+/* one frame / keyframe: the batch form with one item, through the same code path */
+int ov2_klt_priors(ov2_ctx *ctx, const ov2_klt_priors_params *params, const ov2_klt_priors_item *item, ov2_klt_priors_result *result);
+int ov2_klt_priors_batch(ov2_ctx *ctx, const ov2_klt_priors_params *params, int n_items, const ov2_klt_priors_item *items,
+                         ov2_klt_priors_result *results);
+int ov2_stereo_priors(ov2_ctx *ctx, const ov2_stereo_priors_params *params, const ov2_stereo_priors_item *item,
+                      ov2_stereo_priors_result *result);
+int ov2_stereo_priors_batch(ov2_ctx *ctx, const ov2_stereo_priors_params *params, int n_items, const ov2_stereo_priors_item *items,
+                            ov2_stereo_priors_result *results);
+
+/* The lock-step step with the frame form fused in: ov2_btracker_track_frame[_begin] with prior_xy_h / has_prior_h replaced by
+ * the map points (wpt_h: 3 doubles per slot, is3d_h: one byte per slot, both n_max slots per item) and the predicted poses
+ * (Tcw_h: 7 doubles per item).  k_prior_frame writes the prior and flag slots of the tracker's point block on the context's
+ * stream ahead of the tracking kernels: the priors never visit the host on the way in.  They come back with the results, so
+ * the p3p rule runs on the flags the device set; ov2_btracker_track_frame_end finishes either kind of step, and
+ * ov2_btracker_last_priors returns what was used.  The camera is the one of ov2_btracker_set_calibration (OV2_EINVAL without
+ * one; the image size is the tracker's).  First frame, n_total == 0, the look-ahead calls and every result are as for
+ * ov2_btracker_track_frame fed the output of ov2_klt_priors_batch (tests/test_gpu_priors_lockstep.py). */
+int  ov2_btracker_track_frame_map_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                        const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h,
+                                        int klt_use_prior);
+int  ov2_btracker_track_frame_map(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                  const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior,
+                                  float *out_xy_h, uint8_t *status_h, int *p3p_req);
+/* prior (2 floats) / has_prior of the first n keypoints of item `item` as the LAST step used them (either form) */
+int  ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *prior_xy_h, uint8_t *has_prior_h);
+
 #ifdef __cplusplus
 }
 #endif

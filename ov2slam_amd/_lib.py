@@ -345,6 +345,42 @@ class Sampson2dResult(C.Structure):
     _fields_ = [("err", C.POINTER(C.c_float)), ("bad", C.POINTER(C.c_uint8)), ("n_bad", C.c_int)]
 
 
+class KltPriorsParams(C.Structure):
+    """ov2_klt_priors_params"""
+    _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
+                ("img_h", C.c_double), ("klt_use_prior", C.c_int)]
+
+
+class KltPriorsItem(C.Structure):
+    """ov2_klt_priors_item"""
+    _fields_ = [("Tcw", C.POINTER(C.c_double)), ("n", C.c_int), ("px", C.POINTER(C.c_float)), ("is3d", C.POINTER(C.c_uint8)),
+                ("wpt", C.POINTER(C.c_double))]
+
+
+class KltPriorsResult(C.Structure):
+    """ov2_klt_priors_result"""
+    _fields_ = [("prior", C.POINTER(C.c_float)), ("has_prior", C.POINTER(C.c_uint8)), ("n_prior", C.c_int)]
+
+
+class StereoPriorsParams(C.Structure):
+    """ov2_stereo_priors_params"""
+    _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
+                ("img_h", C.c_double), ("Tcic0", C.c_double * 7), ("ncellsize", C.c_int), ("rect", C.c_int)]
+
+
+class StereoPriorsItem(C.Structure):
+    """ov2_stereo_priors_item"""
+    _fields_ = [("Tcw", C.POINTER(C.c_double)), ("n", C.c_int), ("px", C.POINTER(C.c_float)), ("unpx", C.POINTER(C.c_float)),
+                ("bv", C.POINTER(C.c_double)), ("wpt", C.POINTER(C.c_double)), ("state", C.POINTER(C.c_uint8)),
+                ("cell_start", C.POINTER(C.c_int)), ("cell_kp", C.POINTER(C.c_int))]
+
+
+class StereoPriorsResult(C.Structure):
+    """ov2_stereo_priors_result"""
+    _fields_ = [("prior", C.POINTER(C.c_float)), ("has_prior", C.POINTER(C.c_uint8)), ("skip", C.POINTER(C.c_uint8)),
+                ("n_prior3d", C.c_int), ("n_prior_nb", C.c_int), ("n_skip", C.c_int)]
+
+
 _vp, _i, _f, _d = C.c_void_p, C.c_int, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 
@@ -483,6 +519,13 @@ SIGNATURES = {
     "ov2_kf_decision_batch": (_i, [_vp, C.POINTER(FkfParams), _i, C.POINTER(FkfItem), C.POINTER(KfDecisionResult)]),
     "ov2_sampson_filter_2d": (_i, [_vp, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
     "ov2_sampson_filter_2d_batch": (_i, [_vp, _i, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
+    "ov2_klt_priors": (_i, [_vp, C.POINTER(KltPriorsParams), C.POINTER(KltPriorsItem), C.POINTER(KltPriorsResult)]),
+    "ov2_klt_priors_batch": (_i, [_vp, C.POINTER(KltPriorsParams), _i, C.POINTER(KltPriorsItem), C.POINTER(KltPriorsResult)]),
+    "ov2_stereo_priors": (_i, [_vp, C.POINTER(StereoPriorsParams), C.POINTER(StereoPriorsItem), C.POINTER(StereoPriorsResult)]),
+    "ov2_stereo_priors_batch": (_i, [_vp, C.POINTER(StereoPriorsParams), _i, C.POINTER(StereoPriorsItem), C.POINTER(StereoPriorsResult)]),
+    "ov2_btracker_track_frame_map_begin": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "ov2_btracker_track_frame_map": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ov2_btracker_last_priors": (_i, [_vp, _i, _i, _vp, _vp]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

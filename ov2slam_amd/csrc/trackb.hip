@@ -23,6 +23,10 @@
 #include <vector>
 
 int ov2_launch_compute_keypoints(hipStream_t s, const KpCalib &c, const float *px_d, int n_max, const int *n_dev, float *unpx_d, double *bv_d, int items = 1);
+// priors.hip: k_prior_frame on device arrays with n_max point slots per item
+int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double img_h, int use_prior, const void *items_d,
+                           const double *Tcw_d, const float *px_d, const uint8_t *is3d_d, const double *wpt_d, float *prior_d,
+                           uint8_t *has_prior_d, int n_max, int n_items);
 
 #define BT_SETS 8       // pyramid sets in rotation: cur, prev, the one being prepared for the next frame, five of slack for the mapper
                         // context (a keyframe's pyramids outlive it by BT_SETS - 1 steps: the keyframe period of the shipped parameter files)
@@ -67,6 +71,11 @@ struct ov2_btracker {
     bool has_calib = false;
     KpCalib calib;
     std::vector<int> last_n;           // per item: keypoints of the last track_frame (0 before / after a call that tracked nothing)
+    std::vector<int> last_pn;          // the same whether or not a calibration is set (ov2_btracker_last_priors)
+    // ov2_btracker_track_frame_map: the map side of a step -- [items 16 B][Tcw 56 B] per item, [wpt 24][is3d 1] per slot --, allocated
+    // by the first such step; pinned + mapped or mirrored on the device like the keypoint block
+    uint8_t *hmap = nullptr, *dmap = nullptr, *kmap = nullptr;
+    size_t m_it = 0, m_T = 0, m_w = 0, m_3d = 0, map_bytes = 0;
     // keyframe detection: device mirrors of the items' current keypoints and of the detector's output, pinned staging
     uint8_t *d_det = nullptr, *h_det = nullptr; size_t det_in_bytes = 0;
     float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
@@ -100,6 +109,8 @@ static void btracker_free(ov2_btracker *t)
     }
     if (t->hblk) (void)hipHostFree(t->hblk);
     if (t->dblk) (void)hipFree(t->dblk);
+    if (t->hmap) (void)hipHostFree(t->hmap);
+    if (t->dmap) (void)hipFree(t->dmap);
     if (t->h_det) (void)hipHostFree(t->h_det);
     if (t->d_det) (void)hipFree(t->d_det);
     if (t->h_out) (void)hipHostFree(t->h_out);
@@ -137,12 +148,21 @@ static int enqueue_preprocess(ov2_btracker *t, ov2_ctx *on, ov2_pyr *dst, int wh
 }
 
 // kltTracking of items [0, n): keypoint block in, the fused LK launch, computeKeypoint, result block out
-static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur, int n)
+// map_use_prior >= 0 (ov2_btracker_track_frame_map): k_prior_frame fills the prior and flag slots from the map side first
+static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur, int n, int map_use_prior = -1)
 {
     ov2_ctx *ctx = t->ctx;
     const ov2_tracker_config &c = t->cfg;
     if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->dblk, t->hblk, t->in_bytes, hipMemcpyHostToDevice, ctx->stream));
     uint8_t *k = t->kblk;
+    if (map_use_prior >= 0) {
+        if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->dmap, t->hmap, t->map_bytes, hipMemcpyHostToDevice, ctx->stream));
+        const uint8_t *m = t->kmap;
+        const int rcp = ov2_launch_prior_frame(ctx->stream, t->calib, (double)c.w, (double)c.h, map_use_prior, m + t->m_it,
+                                               (const double *)(m + t->m_T), (const float *)(k + t->o_kps), m + t->m_3d,
+                                               (const double *)(m + t->m_w), (float *)(k + t->o_pri), k + t->o_flg, c.n_max, n);
+        if (rcp != OV2_OK) return rcp;
+    }
     int rc = ov2_launch_track_klt(ctx->stream, prev, cur, c.win, c.prior_pyr_lvl, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist,
                                   c.n_max, (const int *)(k + t->o_n), (const float *)(k + t->o_kps), (const float *)(k + t->o_pri),
                                   k + t->o_flg, (float *)(k + t->o_out), k + t->o_st, nullptr, nullptr, 0.f, ctx->track_impl, n, ctx->lk_acc);
@@ -154,6 +174,8 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
     }
     if (!t->zero_copy)
         OV2_HIP_CHECK(hipMemcpyAsync(t->hblk + t->o_out, t->dblk + t->o_out, t->blk_bytes - t->o_out, hipMemcpyDeviceToHost, ctx->stream));
+    if (!t->zero_copy && map_use_prior >= 0)                            // the priors and flags the device set come back with the results
+        OV2_HIP_CHECK(hipMemcpyAsync(t->hblk + t->o_pri, t->dblk + t->o_pri, t->in_bytes - t->o_pri, hipMemcpyDeviceToHost, ctx->stream));
     return OV2_OK;
 }
 
@@ -200,6 +222,43 @@ static int stage_and_upload(ov2_btracker *t, int n, const uint8_t *const *img_h,
     return OV2_OK;
 }
 
+// the map side of a step into hmap (allocated here by the first such step)
+static int stage_map(ov2_btracker *t, int n_active, const double *wpt, const uint8_t *is3d, const double *Tcw, const int *n_h)
+{
+    const size_t nm = (size_t)t->cfg.n_max;
+    if (!t->hmap) {
+        const size_t slots = nm * (size_t)t->batch;
+        t->m_it = 0; t->m_T = up256(16 * (size_t)t->batch); t->m_w = up256(t->m_T + 56 * (size_t)t->batch); t->m_3d = up256(t->m_w + 24 * slots);
+        t->map_bytes = up256(t->m_3d + slots);
+        uint8_t *h = nullptr, *d = nullptr;
+        hipError_t e = hipHostMalloc((void **)&h, t->map_bytes, hipHostMallocMapped);
+        if (e == hipSuccess && !t->zero_copy) e = hipMalloc((void **)&d, t->map_bytes);
+        void *alias = d;
+        if (e == hipSuccess && t->zero_copy) e = hipHostGetDevicePointer(&alias, h, 0);
+        if (e != hipSuccess || !alias) {
+            if (h) (void)hipHostFree(h);
+            if (d) (void)hipFree(d);
+            (void)hipGetLastError();
+            ov2_set_error("ov2_btracker_track_frame_map: %s", hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        memset(h, 0, t->map_bytes);
+        t->hmap = h; t->dmap = d; t->kmap = (uint8_t *)alias;
+    }
+    int *it = (int *)(t->hmap + t->m_it);
+    for (int b = 0; b < t->batch; b++) {
+        it[4 * b] = (int)((size_t)b * nm); it[4 * b + 1] = b < n_active ? n_h[b] : 0; it[4 * b + 2] = it[4 * b + 3] = 0;
+    }
+    memcpy(t->hmap + t->m_T, Tcw, 56 * (size_t)n_active);
+    for (int b = 0; b < n_active; b++) {
+        const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
+        if (!n) continue;
+        memcpy(t->hmap + t->m_w + 24 * o, wpt + 3 * o, 24 * n);
+        memcpy(t->hmap + t->m_3d + o, is3d + o, n);
+    }
+    return OV2_OK;
+}
+
 static void stage_points(ov2_btracker *t, int n_active, const float *kps, const float *pri, const uint8_t *has_prior, const int *n_h, int use_prior)
 {
     const size_t nm = (size_t)t->cfg.n_max;
@@ -209,6 +268,7 @@ static void stage_points(ov2_btracker *t, int n_active, const float *kps, const 
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
         if (!n) continue;
         memcpy(t->hblk + t->o_kps + 8 * o, kps + 2 * o, 8 * n);
+        if (!pri) continue;                                              // the map form: k_prior_frame writes both
         memcpy(t->hblk + t->o_pri + 8 * o, pri + 2 * o, 8 * n);
         uint8_t *f = t->hblk + t->o_flg + o;
         if (use_prior && has_prior) for (size_t i = 0; i < n; i++) f[i] = has_prior[o + i] ? 1 : 0;
@@ -327,6 +387,7 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     OV2_REQUIRE(t != nullptr, OV2_ENOMEM, "out of host memory");
     t->ctx = ctx; t->cfg = *cfg; t->batch = batch;
     t->last_n.assign((size_t)batch, 0);
+    t->last_pn.assign((size_t)batch, 0);
     int rc = OV2_OK;
     for (int i = 0; i < BT_SETS && rc == OV2_OK; i++) {
         rc = ov2_pyr_create(ctx, cfg->w, cfg->h, cfg->win, cfg->nklt_pyr_lvl, batch, &t->pyr[i]);
@@ -464,10 +525,15 @@ int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
     return OV2_OK;
 }
 
-int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
-                                   const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior)
+} // extern "C"
+
+// both forms of the step's first half.  map: the priors come from the device (wpt_h / is3d_h / Tcw_h), prior_xy_h / has_prior_h are unused
+static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                             const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior, bool map,
+                             const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h)
 {
     OV2_REQUIRE(t && img_h, OV2_EINVAL, "NULL argument");
+    OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(stride >= t->cfg.w, OV2_EINVAL, "stride < width");
@@ -479,8 +545,9 @@ int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t 
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
         n_total += n;
     }
-    OV2_REQUIRE(n_total == 0 || (kps_xy_h && prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
-    for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = 0;
+    if (map) OV2_REQUIRE(n_total == 0 || (kps_xy_h && wpt_h && is3d_h && Tcw_h && n_h), OV2_EINVAL, "NULL point buffer");
+    else OV2_REQUIRE(n_total == 0 || (kps_xy_h && prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
+    for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = t->last_pn[(size_t)b] = 0;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     int which = 0;
@@ -512,13 +579,32 @@ int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t 
         P.tracked = false; P.on = true;
         return OV2_OK;
     }
-    stage_points(t, n_active, kps_xy_h, prior_xy_h, has_prior_h, n_h, klt_use_prior);
+    if (map) {
+        rc = stage_map(t, n_active, wpt_h, is3d_h, Tcw_h, n_h);
+        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
+        P.has_prior = t->hblk + t->o_flg;                                // the flags the device sets: same slots as the caller's array
+    }
+    stage_points(t, n_active, kps_xy_h, map ? nullptr : prior_xy_h, has_prior_h, n_h, klt_use_prior);
     rc = preprocess();
-    if (rc == OV2_OK) rc = enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], n_active);
+    if (rc == OV2_OK) rc = enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], n_active, map ? (klt_use_prior ? 1 : 0) : -1);
     if (rc != OV2_OK) { t->cur = old_cur; return rc; }
     commit();
     P.tracked = true; P.on = true;
     return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                   const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior)
+{
+    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, prior_xy_h, has_prior_h, n_h, klt_use_prior, false, nullptr, nullptr, nullptr);
+}
+
+int ov2_btracker_track_frame_map_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                       const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior)
+{
+    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h);
 }
 
 int ov2_btracker_track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req)
@@ -546,6 +632,7 @@ int ov2_btracker_track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *stat
                                       status_h + o, p3p_req ? p3p_req + b : nullptr);
         if (rc != OV2_OK) return rc;
         if (t->has_calib) t->last_n[(size_t)b] = (int)n;
+        t->last_pn[(size_t)b] = (int)n;
     }
     return OV2_OK;
 }
@@ -562,6 +649,31 @@ int ov2_btracker_track_frame(ov2_btracker *t, int n_active, const uint8_t *const
     const int rc = ov2_btracker_track_frame_begin(t, n_active, img_h, stride, kps_xy_h, prior_xy_h, has_prior_h, n_h, klt_use_prior);
     if (rc != OV2_OK) return rc;
     return ov2_btracker_track_frame_end(t, out_xy_h, status_h, p3p_req);
+}
+
+int ov2_btracker_track_frame_map(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                 const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior,
+                                 float *out_xy_h, uint8_t *status_h, int *p3p_req)
+{
+    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // as ov2_btracker_track_frame: the result buffers before anything is enqueued
+        int n_total = 0;
+        for (int b = 0; b < n_active; b++) n_total += n_h[b] > 0 ? n_h[b] : 0;
+        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
+    }
+    const int rc = ov2_btracker_track_frame_map_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior);
+    if (rc != OV2_OK) return rc;
+    return ov2_btracker_track_frame_end(t, out_xy_h, status_h, p3p_req);
+}
+
+int ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *prior_xy_h, uint8_t *has_prior_h)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(n >= 0 && n <= t->last_pn[(size_t)item], OV2_EINVAL, "more keypoints than the last tracking call returned for this item");
+    const size_t o = (size_t)item * t->cfg.n_max;
+    if (prior_xy_h) memcpy(prior_xy_h, t->hblk + t->o_pri + 8 * o, 8 * (size_t)n);
+    if (has_prior_h) memcpy(has_prior_h, t->hblk + t->o_flg + o, (size_t)n);
+    return OV2_OK;
 }
 
 int ov2_btracker_last_keypoints(const ov2_btracker *t, int item, int n, float *unpx_xy_h, double *bv_xyz_h)

@@ -562,6 +562,50 @@ class LockstepTracker:
         self._pending = None
         return out, st, p3p.astype(bool)
 
+    def _map_args(self, imgs, kps, wpt, is3d, Tcw, n):
+        na = len(imgs)
+        imgs = [im if im.dtype == np.uint8 and im.strides[1] == 1 else np.ascontiguousarray(im, np.uint8) for im in imgs]
+        stride = imgs[0].strides[0]
+        for im in imgs:
+            if im.ndim != 2 or im.shape[0] != self.h or im.shape[1] < self.w or im.strides[0] != stride:
+                raise ValueError("frames must be %d rows of >= %d bytes with one common row pitch" % (self.h, self.w))
+        ptrs = (C.c_void_p * na)(*[im.ctypes.data for im in imgs])
+        kps = np.ascontiguousarray(kps, np.float32).reshape(self.batch, self.n_max, 2)
+        wpt = np.ascontiguousarray(wpt, np.float64).reshape(self.batch, self.n_max, 3)
+        is3d = np.ascontiguousarray(is3d, np.uint8).reshape(self.batch, self.n_max)
+        Tcw = np.ascontiguousarray(Tcw, np.float64).reshape(-1, 7)
+        nn = np.ascontiguousarray(n, np.int32)
+        if len(nn) != na or len(Tcw) < na:
+            raise ValueError("one keypoint count and one predicted pose per active item")
+        return na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn
+
+    def trackFrameMap(self, imgs, kps, wpt, is3d, Tcw, n, klt_use_prior=True):
+        """trackFrame with the priors derived on the device (ov2_btracker_track_frame_map): wpt (batch, n_max, 3) float64 map points,
+        is3d (batch, n_max) uint8, Tcw (>= n_active, 7) the predicted poses [t q], already inverted.  Needs setCalibration.
+        -> (out, status bits, p3p_req) as trackFrame; lastPriors returns the priors that were used."""
+        na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
+        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
+        p3p = np.zeros(na, np.int32)
+        L.check(self.lib.ov2_btracker_track_frame_map(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw), _ptr(nn),
+                                                      int(bool(klt_use_prior)), _ptr(out), _ptr(st), _ptr(p3p)))
+        return out, st, p3p.astype(bool)
+
+    track_frame_map = trackFrameMap
+
+    def trackFrameMapBegin(self, imgs, kps, wpt, is3d, Tcw, n, klt_use_prior=True):
+        """first half of trackFrameMap; trackFrameEnd finishes it"""
+        na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
+        self._pending = (imgs, kps, wpt, is3d, nn)                                # (kps is re-read by trackFrameEnd: keep it alive)
+        L.check(self.lib.ov2_btracker_track_frame_map_begin(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw),
+                                                            _ptr(nn), int(bool(klt_use_prior))))
+
+    def lastPriors(self, item, n):
+        """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
+        pri = np.empty((n, 2), np.float32)
+        hp = np.empty(n, np.uint8)
+        L.check(self.lib.ov2_btracker_last_priors(self.h_trk, int(item), int(n), _ptr(pri), _ptr(hp)))
+        return pri, hp
+
     def lastKeypoints(self, item, n, want_bv=True):
         unpx = np.empty((n, 2), np.float32)
         bv = np.empty((n, 3), np.float64) if want_bv else None

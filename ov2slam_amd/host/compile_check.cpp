@@ -47,5 +47,17 @@ static int (*const check_epi2d)(ov2::Context &, const ov2::FrameVsKeyframe &, co
 static int (*const check_epi2d_batch)(ov2::Context &, const std::vector<ov2::FrameVsKeyframe> &, const std::vector<double> &, float,
                                       std::vector<std::vector<int>> &, std::vector<std::vector<float>> *) = &ov2::epipolarFilter2d;
 static auto const check_kf_sort = &ov2::detail::sortKeyframeByLmid;
+// the tracking priors: kltPriors / stereoPriors, single and batch, and their host-only helpers
+static int (*const check_klt_priors)(ov2::Context &, const ov2::ProjectionCamera &, bool, const ov2::KltPriorsInput &, std::vector<ov2::Point2f> &,
+                                     std::vector<uint8_t> &) = &ov2::kltPriors;
+static int (*const check_klt_priors_batch)(ov2::Context &, const ov2::ProjectionCamera &, bool, const std::vector<ov2::KltPriorsInput> &,
+                                           std::vector<std::vector<ov2::Point2f>> &, std::vector<std::vector<uint8_t>> &) = &ov2::kltPriors;
+static int (*const check_stereo_priors)(ov2::Context &, const ov2::StereoPriorsParams &, const ov2::StereoPriorsInput &, std::vector<ov2::Point2f> &,
+                                        std::vector<uint8_t> &, std::vector<uint8_t> &) = &ov2::stereoPriors;
+static int (*const check_stereo_priors_batch)(ov2::Context &, const ov2::StereoPriorsParams &, const std::vector<ov2::StereoPriorsInput> &,
+                                              std::vector<std::vector<ov2::Point2f>> &, std::vector<std::vector<uint8_t>> &,
+                                              std::vector<std::vector<uint8_t>> &) = &ov2::stereoPriors;
+static auto const check_cell_table = &ov2::detail::buildCellTable;
+static auto const check_pack_klt = &ov2::detail::packKltPriors;
 
-int main() { return check_parallax && check_parallax_batch && check_kfreq && check_kfreq_batch && check_epi2d && check_epi2d_batch && check_kf_sort && check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
+int main() { return check_klt_priors && check_klt_priors_batch && check_stereo_priors && check_stereo_priors_batch && check_cell_table && check_pack_klt && check_parallax && check_parallax_batch && check_kfreq && check_kfreq_batch && check_epi2d && check_epi2d_batch && check_kf_sort && check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }

@@ -102,4 +102,13 @@ private:
     int win_ = 0, max_level_ = -1;
 };
 
+// the forward model of one camera as the prior passes take it (ov2::kltPriors: the left camera, ov2::stereoPriors: the right one):
+// CameraCalibration's model (OV2_CAM_PINHOLE / OV2_CAM_FISHEYE), fx_ fy_ cx_ cy_, Dcv_ (empty: none), img_w_ / img_h_
+struct ProjectionCamera {
+    int model = OV2_CAM_PINHOLE;
+    double K[4] = {0, 0, 0, 0};
+    std::vector<double> D;
+    double img_w = 0., img_h = 0.;
+};
+
 }  // namespace ov2

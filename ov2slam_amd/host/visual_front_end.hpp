@@ -288,4 +288,72 @@ inline int epipolarFilter2d(Context &ctx, const std::vector<FrameVsKeyframe> &fs
     return OV2_OK;
 }
 
+// ---- the priors of kltTracking (:156-184) on ov2_klt_priors: every 3-D keypoint's map point projected with the predicted pose
+// (projWorldToImageDist), a prior where it lands in the image (isInImage) and kp.px_ otherwise.  The caller hands over the
+// keypoints in the iteration order of pcurframe_->mapkps_ with the map point of each 3-D one (pmap_->map_plms_.at(lmid)->getPoint();
+// not read for 2-D keypoints) and the predicted pose inverted (Tcw = [t q]).  MotionModel itself stays with the caller.
+struct KltPriorsInput {
+    std::vector<Point2f> px;                                  // Keypoint::px_
+    std::vector<uint8_t> is3d;                                // Keypoint::is3d_
+    std::vector<double> wpt;                                  // 3 doubles per keypoint
+    double Tcw[7] = {0, 0, 0, 0, 0, 0, 1};
+};
+
+namespace detail {
+// false when the arrays differ in length; an empty frame gets non-NULL arrays
+inline bool packKltPriors(const KltPriorsInput &f, ov2_klt_priors_item &it)
+{
+    const size_t n = f.px.size();
+    if (f.is3d.size() != n || f.wpt.size() != 3 * n || n > 0x7fffffffu) return false;
+    static const float none_f[2] = {0.f, 0.f}; static const double none_d[3] = {0., 0., 0.}; static const uint8_t none_b = 0;
+    it.Tcw = f.Tcw; it.n = (int)n;
+    it.px = n ? &f.px[0].x : none_f; it.is3d = n ? f.is3d.data() : &none_b; it.wpt = n ? f.wpt.data() : none_d;
+    return true;
+}
+inline ov2_klt_priors_params kltPriorsParams(const ProjectionCamera &cam, bool klt_use_prior)
+{
+    ov2_klt_priors_params p{};
+    p.model = cam.model;
+    for (int j = 0; j < 4; j++) p.K[j] = cam.K[j];
+    p.D = cam.D.empty() ? nullptr : cam.D.data(); p.nD = (int)cam.D.size();
+    p.img_w = cam.img_w; p.img_h = cam.img_h; p.klt_use_prior = klt_use_prior ? 1 : 0;
+    return p;
+}
+}  // namespace detail
+
+// vpriors[i] / vhasprior[i] are what FrameTracker::kltTracking / trackFrame take.  Returns OV2_OK or the library's code
+// (ov2_last_error() says why); OV2_EINVAL for arrays that differ in length.
+inline int kltPriors(Context &ctx, const ProjectionCamera &cam, bool klt_use_prior, const KltPriorsInput &f, std::vector<Point2f> &vpriors,
+                     std::vector<uint8_t> &vhasprior)
+{
+    ov2_klt_priors_item it{};
+    if (!detail::packKltPriors(f, it)) return OV2_EINVAL;
+    const size_t n = f.px.size();
+    vpriors.assign(n ? n : 1, Point2f()); vhasprior.assign(n ? n : 1, 0);
+    ov2_klt_priors_result r{&vpriors[0].x, vhasprior.data(), 0};
+    const ov2_klt_priors_params p = detail::kltPriorsParams(cam, klt_use_prior);
+    const int rc = ov2_klt_priors(ctx.get(), &p, &it, &r);
+    vpriors.resize(n); vhasprior.resize(n);
+    return rc;
+}
+// the frames of a lock-step batch in one launch
+inline int kltPriors(Context &ctx, const ProjectionCamera &cam, bool klt_use_prior, const std::vector<KltPriorsInput> &fs,
+                     std::vector<std::vector<Point2f>> &vpriors, std::vector<std::vector<uint8_t>> &vhasprior)
+{
+    const size_t B = fs.size();
+    std::vector<ov2_klt_priors_item> items(B);
+    std::vector<ov2_klt_priors_result> rs(B);
+    vpriors.assign(B, std::vector<Point2f>()); vhasprior.assign(B, std::vector<uint8_t>());
+    for (size_t b = 0; b < B; b++) {
+        if (!detail::packKltPriors(fs[b], items[b])) return OV2_EINVAL;
+        const size_t n = fs[b].px.size();
+        vpriors[b].assign(n ? n : 1, Point2f()); vhasprior[b].assign(n ? n : 1, 0);
+        rs[b] = ov2_klt_priors_result{&vpriors[b][0].x, vhasprior[b].data(), 0};
+    }
+    const ov2_klt_priors_params p = detail::kltPriorsParams(cam, klt_use_prior);
+    const int rc = ov2_klt_priors_batch(ctx.get(), &p, (int)B, items.data(), rs.data());
+    for (size_t b = 0; b < B; b++) { vpriors[b].resize(fs[b].px.size()); vhasprior[b].resize(fs[b].px.size()); }
+    return rc;
+}
+
 }  // namespace ov2

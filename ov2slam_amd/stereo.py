@@ -7,7 +7,8 @@
     gate     right keypoint undistorted, |dy| or Sampson distance <= 2 (:568-590)
 
 The map look-ups around it (projecting map points, surrounding-keypoint depth priors, updateKeypointStereo)
-stay on the host in the reference and are inputs / outputs here."""
+stay on the host in the reference and are inputs / outputs here; the two kinds of prior have a device form of their own
+(ov2slam_amd/priors.py: stereo_priors, whose prior / has_prior are the priors3d_xy / has_prior3d of stereo_match_arrays)."""
 import numpy as np
 
 from . import _lib as L
