@@ -287,7 +287,8 @@ int ov2_stereo_match(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, in
 
 // ov2_stereo_match for the keyframes of a lock-step batch (all sequences of a rank reach their keyframes together): items [0, n_items)
 // of two batch pyramids, n_max point slots per item, ONE enqueue and ONE synchronisation for all of them -- the same three kernels with
-// the grid extended by the item.  Per item the results are those of ov2_stereo_match on that item (tests/test_gpu_stereo.py).
+// the grid extended by the item.  Per item the results are those of ov2_stereo_match on that item (tests/test_gpu_lockstep.py:
+// test_item_view_in_stereo_matching) and the oracle's on that item (tests/test_gpu_stereo_cases.py: test_batch_form_against_the_oracle).
 int ov2_stereo_match_batch(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, int n_items, int nklt_win_size, int nklt_pyr_lvl, int max_iter,
                            float eps, float nklt_err, float fmax_fbklt_dist, int rect, const double Frl[9], int model, const double K[4],
                            const double *D, int nD, int n_max, const float *kps_px_h, const float *kps_unpx_h, const float *priors3d_h,

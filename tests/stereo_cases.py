@@ -1,0 +1,206 @@
+"""Stereo-matching scenes (plain numpy + the CPU oracle) built to populate every branch of MapManager::stereoMatching's data path:
+what tests/test_stereo_cases.py checks on the oracle alone and tests/test_gpu_stereo_cases.py runs through the HIP kernels.
+
+A scene is a left / right pair cut from one texture at a horizontal disparity, with
+  * a vertical band of the right image rolled 3 rows down: tracks that land in it end off their row and the epipolar gate rejects them,
+  * keypoints in the interior AND within 28 px of every border, permuted so that both kinds share wavefronts and work-groups: on the
+    SAD level the border keypoints walk through getLineMinSAD's `halfwin += ...` adjustments (half window 0, shrunk, grown),
+  * 3-D priors on about 35 % of the keypoints, about 30 % of those far off: lost by the one-level pass and retried on the full pyramid.
+All keypoints lie inside the image (the contract of ov2_line_min_sad).  Pinhole only: every comparison against the device is exact."""
+import numpy as np
+
+from ov2slam_amd import synth
+
+RADTAN = (-0.05, 0.01, 1e-4, -1e-4)
+F_XTRANS = np.array([[0, 0, 0], [0, 0, -1.0], [0, 1.0, 0]])       # identical pinhole cameras, pure x-translation: rows are epipolar lines
+SAD_WIN = 7                                                        # map_manager.cpp:431
+
+# name -> w, h, disparity, interior / border keypoints, LK windows, nklt_pyr_lvl, rectified, distortion
+SPECS = {
+    "euroc_half":        dict(w=376, h=240, disp=12, n_inner=70, n_edge=60, wins=(9,), lvl=3, rect=True, D=None),
+    "euroc_half_unrect": dict(w=376, h=240, disp=12, n_inner=70, n_edge=60, wins=(9,), lvl=3, rect=False, D=RADTAN),
+    "odd_w7":            dict(w=333, h=131, disp=10, n_inner=60, n_edge=60, wins=(7,), lvl=2, rect=True, D=RADTAN),
+    "odd_w11_unrect":    dict(w=161, h=121, disp=6, n_inner=40, n_edge=40, wins=(11,), lvl=1, rect=False, D=RADTAN),
+    "flat_strip":        dict(w=264, h=100, disp=8, n_inner=50, n_edge=50, wins=(9,), lvl=3, rect=True, D=None),
+    "w5_w13":            dict(w=161, h=121, disp=6, n_inner=40, n_edge=40, wins=(5, 13), lvl=3, rect=True, D=None),
+}
+NAMES = tuple(SPECS)
+CASE_WINS = tuple((name, win) for name in NAMES for win in SPECS[name]["wins"])
+MAX_LEVEL = 3                                                      # every shape above gives a four-level pyramid
+
+
+def gain(im):
+    """contrast x 5 about mid-grey: with the soft synthetic texture every LK sum stays below 2^24 and float accumulation is exact
+    (tests/test_gpu_frontend.py: test_fbklt_float_accumulators_as_executed_on_x86)"""
+    return np.clip((im.astype(np.float32) - 128.0) * 5.0 + 128.0, 0, 255).astype(np.uint8)
+
+
+def images(w, h, disp, seed):
+    tex = synth.base_texture(max(w, h) + 400, seed)
+    l = tex[50:50 + h, 100:100 + w].astype(np.uint8)
+    r = tex[50:50 + h, 100 + disp:100 + disp + w].astype(np.uint8)
+    c0, c1 = w // 3, w // 3 + w // 4
+    r[:, c0:c1] = np.roll(r[:, c0:c1], 3, axis=0)
+    return l, r
+
+
+def keypoints(w, h, n_inner, n_edge, rng):
+    inner = np.stack([rng.uniform(30, w - 1 - 30, n_inner), rng.uniform(30, h - 1 - 30, n_inner)], 1)
+    d = rng.uniform(0, 28, n_edge)
+    d[:4] = 0.0                                                    # one keypoint exactly on each border
+    along_x, along_y = rng.uniform(0, w - 1, n_edge), rng.uniform(0, h - 1, n_edge)
+    edge = np.empty((n_edge, 2))
+    for i in range(n_edge):
+        edge[i] = [(d[i], along_y[i]), (w - 1 - d[i], along_y[i]), (along_x[i], d[i]), (along_x[i], h - 1 - d[i])][i % 4]
+    kps = np.concatenate([inner, edge]).astype(np.float32)
+    kps[:, 0] = np.clip(kps[:, 0], 0, w - 1); kps[:, 1] = np.clip(kps[:, 1], 0, h - 1)
+    return kps[rng.permutation(len(kps))]
+
+
+def priors_3d(kps, disp, rng):
+    n = len(kps)
+    has = rng.random(n) < 0.35
+    far = has & (rng.random(n) < 0.30)
+    p = kps.astype(np.float64) + np.stack([-disp + rng.normal(0, 1.0, n), rng.normal(0, 0.3, n)], 1)
+    p[far] += np.stack([rng.uniform(8, 16, n), -rng.uniform(5, 10, n)], 1)[far]
+    return {int(i): (np.float32(p[i, 0]), np.float32(p[i, 1])) for i in np.nonzero(has)[0]}
+
+
+def half_window(x, y, w, h, nwinsize=SAD_WIN):
+    """getLineMinSAD's half window after its four `halfwin += <float>` adjustments (feature_tracker.cpp:154-161, oracle/stereo.c):
+    each sum is formed in float32 and truncated toward zero"""
+    f = np.float32
+    x, y, hw = f(x), f(y), nwinsize // 2
+    if x - f(hw) < 0: hw = int(f(hw) + (x - f(hw)))
+    if x + f(hw) >= w: hw = int(f(hw) + (x + f(hw) - f(w) - f(1)))
+    if y - f(hw) < 0: hw = int(f(hw) + (y - f(hw)))
+    if y + f(hw) >= h: hw = int(f(hw) + (y + f(hw) - f(h) - f(1)))
+    return hw
+
+
+def half_windows(pts, w, h, nwinsize=SAD_WIN):
+    return np.array([half_window(x, y, w, h, nwinsize) for x, y in np.asarray(pts, np.float32).reshape(-1, 2)], int)
+
+
+_cache = {}
+
+
+def case(name, win=None, seed=None, contrast=False):
+    """The scene `name` (SPECS) for one of its LK windows (default: the first), as a dict: left / right (uint8), kps, kps_unpx,
+    priors3d {index: (x, y)}, K, D, rect, Frl, win, nklt_pyr_lvl, the oracle's pyramids opl / opr and its results ok / right_px.
+    seed: texture and keypoint seed (default w + h); contrast: images through gain().  Cached: treat the arrays as read-only."""
+    from oracle import oracle as O
+    s = SPECS[name]
+    win = s["wins"][0] if win is None else win
+    assert win in s["wins"]
+    w, h = s["w"], s["h"]
+    seed = w + h if seed is None else seed
+    key = (name, win, seed, contrast)
+    if key in _cache:
+        return _cache[key]
+    l, r = images(w, h, s["disp"], seed)
+    if contrast:
+        l, r = gain(l), gain(r)
+    rng = np.random.default_rng(seed)
+    kps = keypoints(w, h, s["n_inner"], s["n_edge"], rng)
+    K = (0.61 * w, 0.608 * w, 0.488 * w, 0.517 * h)
+    iK = np.linalg.inv(np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1.0]]))
+    c = dict(name=name, w=w, h=h, disp=s["disp"], left=l, right=r, kps=kps, priors3d=priors_3d(kps, s["disp"], rng), K=K, D=s["D"],
+             rect=s["rect"], Frl=None if s["rect"] else F_XTRANS.copy(), win=win, nklt_pyr_lvl=s["lvl"], _runs={})
+    c["kps_unpx"] = O.compute_keypoints(O.CAM_PINHOLE, K, s["D"], iK, kps)[0]
+    c["opl"], c["opr"] = O.Pyramid(l, win, MAX_LEVEL), O.Pyramid(r, win, MAX_LEVEL)
+    assert c["opl"].levels == MAX_LEVEL + 1
+    c["ok"], c["right_px"] = oracle_run(c)
+    _cache[key] = c
+    return c
+
+
+def prefix_priors(c, n):
+    return {i: p for i, p in c["priors3d"].items() if i < n}
+
+
+def oracle_run(c, n=None, nklt_pyr_lvl=None, float_acc=False):
+    """oracle.stereo_matching on the first n keypoints of the case (default: all), at another nklt_pyr_lvl, or with the float
+    accumulators of an x86 OpenCV 4.x build.  -> (stereo_ok, right_px), cached."""
+    from oracle import oracle as O
+    n = len(c["kps"]) if n is None else n
+    lvl = c["nklt_pyr_lvl"] if nklt_pyr_lvl is None else nklt_pyr_lvl
+    key = (n, lvl, float_acc)
+    if key not in c["_runs"]:
+        with O.lk_acc_mode(O.LK_ACC_FLOAT_UI4 if float_acc else O.LK_ACC_INT64):
+            c["_runs"][key] = O.stereo_matching(c["opl"], c["opr"], c["kps"][:n], c["kps_unpx"][:n], O.CAM_PINHOLE, c["K"], c["D"], c["rect"],
+                                                Frl=c["Frl"], win=c["win"], nklt_pyr_lvl=lvl, priors3d=prefix_priors(c, n))
+    return c["_runs"][key]
+
+
+def stages(c):
+    """The stages of the flow per keypoint, from the oracle's own entry points: sad_xp (getLineMinSAD on the SAD level, for every
+    keypoint), halfwin, has3d, first_ok (the one-level pass succeeded), retried, tracked, ok.  Cached."""
+    from oracle import oracle as O
+    if "_stages" in c:
+        return c["_stages"]
+    kps, n, lvl, win = c["kps"], len(c["kps"]), c["nklt_pyr_lvl"], c["win"]
+    up = np.float32(2.0 ** lvl); down = np.float32(1.0) / up
+    il, ir = c["opl"].level(lvl)[0], c["opr"].level(lvl)[0]
+    lh, lw = il.shape
+    top = kps * down
+    sad_xp = O.line_min_sad(il, ir, top, SAD_WIN, True)[0]
+    has3d = np.zeros(n, bool); has3d[sorted(c["priors3d"])] = True
+    pri = kps.copy()
+    if c["rect"]:
+        x = sad_xp * up
+        use = (x >= 0) & (x <= kps[:, 0])
+        pri[use, 0] = x[use]
+    first_ok = np.zeros(n, bool); tracked = np.zeros(n, bool)
+    i3 = np.nonzero(has3d)[0]
+    if len(i3):
+        out, st, _ = O.fb_klt(c["opl"], c["opr"], win, 1, 30., 0.5, kps[i3], np.array([c["priors3d"][i] for i in i3], np.float32))
+        first_ok[i3] = st
+        pri[i3] = out
+    retried = has3d & ~first_ok
+    i2 = np.nonzero(~has3d | retried)[0]
+    out, st, _ = O.fb_klt(c["opl"], c["opr"], win, lvl, 30., 0.5, kps[i2], pri[i2])
+    tracked[i2] = st
+    tracked |= first_ok
+    # a retry that started from the 3-D prior itself instead of the one-level pass's forward result (map_manager.cpp:533-538)
+    ir_ = np.nonzero(retried)[0]
+    wrong, wst, _ = O.fb_klt(c["opl"], c["opr"], win, lvl, 30., 0.5, kps[ir_], np.array([c["priors3d"][i] for i in ir_], np.float32))
+    sel = np.isin(i2, ir_)
+    retry_distinct = (wst != st[sel]) | ((wrong.view(np.uint32) != out[sel].view(np.uint32)).any(axis=1) & wst & st[sel])
+    c["_stages"] = dict(retry_distinct=retry_distinct,sad_xp=sad_xp, halfwin=half_windows(top, lw, lh), has3d=has3d, first_ok=first_ok, retried=retried, tracked=tracked,
+                        ok=c["ok"], gate_rejected=tracked & ~c["ok"])
+    return c["_stages"]
+
+
+def counts(c):
+    """the branch-population figures of one case, as the log and the test use them"""
+    s = stages(c)
+    return dict(n=len(c["kps"]), sad_none=int((s["sad_xp"] == -1).sum()), halfwin=sorted(set(int(v) for v in s["halfwin"])),
+                with_3d=int(s["has3d"].sum()), first_ok=int(s["first_ok"].sum()), retried=int(s["retried"].sum()), retry_distinct=int(s["retry_distinct"].sum()),
+                tracked=int(s["tracked"].sum()), untracked=int((~s["tracked"]).sum()), gate_rejected=int(s["gate_rejected"].sum()),
+                ok=int(s["ok"].sum()))
+
+
+def sad_points(lw, lh, rng, pow2_right=False):
+    """Points for getLineMinSAD on a level of lw x lh pixels: 400 within 6 px of the four borders (the corners and (lw - 1, lh - 1)
+    included), 200 in the interior; pow2_right: points whose rightward scan crosses 4 .. 128 from just below / above, low mantissa bits set"""
+    f = np.float32
+    d = rng.uniform(0, 6, 400)
+    ax, ay = rng.uniform(0, lw - 1, 400), rng.uniform(0, lh - 1, 400)
+    edge = np.array([[(d[i], ay[i]), (lw - 1 - d[i], ay[i]), (ax[i], d[i]), (ax[i], lh - 1 - d[i])][i % 4] for i in range(400)])
+    edge[:4] = [(0, 0), (lw - 1, 0), (0, lh - 1), (lw - 1, lh - 1)]
+    # exactly on the last row / column: the only in-image places where window 7 grows (3 -> 4); the last row can still be scanned
+    edge[4:12, 1] = lh - 1
+    edge[12:16, 0] = lw - 1
+    x1, y1 = max(6.0, lw - 7.0), max(6.0, lh - 7.0)
+    inner = np.stack([rng.uniform(min(6.0, x1), x1, 200), rng.uniform(min(6.0, y1), y1, 200)], 1)
+    pts = [edge, inner]
+    if pow2_right:
+        xs = []
+        for p in (4, 8, 16, 32, 64, 128):
+            xs += [np.nextafter(f(p), f(0)), np.nextafter(f(p), f(1e9)), f(p) + f(2.0 ** -17), f(p) - f(1) + f(2.0 ** -17), f(p - 0.7)]
+        xs = np.array(xs, np.float64)
+        pts.append(np.stack([np.tile(xs, 2), np.concatenate([rng.uniform(12, lh - 13, len(xs)), rng.uniform(0, 3, len(xs))])], 1))
+    pts = np.concatenate(pts).astype(np.float32)
+    pts[:, 0] = np.clip(pts[:, 0], 0, lw - 1); pts[:, 1] = np.clip(pts[:, 1], 0, lh - 1)
+    return pts
