@@ -1306,6 +1306,7 @@ int launch_subpix(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int stride, 
     return OV2_OK;
 }
 
+static int g_strip_static_lds = 0;                               // k_mineig_strip's static LDS, read where the limits are raised
 // The dynamic-LDS limit is a per-function, process-wide attribute: raise it ONCE for every instance to the hardware maximum
 // (less the kernel's static LDS) instead of per call to that call's need -- two contexts on two threads would race on it.
 static hipError_t det_raise_lds_limits()
@@ -1317,6 +1318,7 @@ static hipError_t det_raise_lds_limits()
             hipFuncAttributes fa;
             hipError_t e = hipFuncGetAttributes(&fa, fn);
             if (e != hipSuccess) return e;
+            if (fn == (const void *)k_mineig_strip) g_strip_static_lds = (int)fa.sharedSizeBytes;
             return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
         };
         const void *fns[] = {(const void *)k_mineig_cells, (const void *)k_mineig_strip,
@@ -1362,17 +1364,22 @@ static int enqueue_detect(ov2_ctx *ctx, int mode, const uint8_t *im, int w, int 
         hipLaunchKernelGGL(k_fast_cells, dim3(ncells * items), dim3(256), 0, ctx->stream, im, w, h, im_stride, cell, nw, th, maps_d, mask_mode, cand_d, B);
     } else if (ctx->det_strip == 1 || (ctx->det_strip < 0 && (long long)ncells * items >= 2048)) {
         // batches: the free cells of an image side by side, several per work-group (k_mineig_strip); the cells per group / wavefronts
-        // per group that leave the fewest lanes idle: a wavefront owns at most 60 of its 64 columns
-        int best_n = 1, best_k = (cell + 59) / 60;
-        double best_e = (double)cell / (64.0 * best_k);
-        for (int nc = 2; nc <= STRIP_MAX_CELLS; nc++) {
+        // per group that leave the fewest lanes idle: a wavefront owns at most 60 of its 64 columns.  Only what fits the LDS is a
+        // choice: at cell 64 the densest packing (7 cells on 8 wavefronts) needs 165888 bytes, so (6, 7) runs
+        auto strip_lds = [cell](int k) { return (((size_t)cell * 64 * k + 15) & ~(size_t)15) + (size_t)k * cell * 65 * 4; };
+        const size_t lds_limit = (size_t)160 * 1024 - (size_t)g_strip_static_lds;
+        int best_n = 0, best_k = 0;
+        double best_e = 0.0;
+        for (int nc = 1; nc <= STRIP_MAX_CELLS; nc++) {
             const int k = (nc * cell + 59) / 60;
             if (k > 8) break;
+            if (strip_lds(k) > lds_limit) continue;
             const double e = (double)nc * cell / (64.0 * k);
-            if (e > best_e + 1e-9) { best_e = e; best_n = nc; best_k = k; }
+            if (best_n == 0 || e > best_e + 1e-9) { best_e = e; best_n = nc; best_k = k; }
         }
+        OV2_REQUIRE(best_n > 0, OV2_EUNSUPPORTED, "no strip geometry of this cell size fits the LDS");
         const int owned = (best_n * cell + best_k - 1) / best_k;
-        const size_t lds = (((size_t)cell * 64 * best_k + 15) & ~(size_t)15) + (size_t)best_k * cell * 65 * 4;
+        const size_t lds = strip_lds(best_k);
         int *free_d = (int *)(cand_d + (size_t)items * ncells);          // (the callers reserve it behind the candidates)
         hipLaunchKernelGGL(k_free_cells, dim3(items), dim3(64), (size_t)(ncells + 31) / 32 * 4, ctx->stream, cell, nw, B, free_d);
         hipLaunchKernelGGL(k_mineig_strip, dim3((ncells + best_n - 1) / best_n, items), dim3(64 * best_k), lds, ctx->stream, im, w, h, im_stride, cell, nw,

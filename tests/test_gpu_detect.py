@@ -88,7 +88,7 @@ def test_grid_fast_ties_among_equal_responses(gpu_ctx, oracle, tie):
 
 
 @pytest.mark.parametrize("name", [n for n, _ in IMAGES])
-@pytest.mark.parametrize("cell", [35, 45, 53, 58])
+@pytest.mark.parametrize("cell", [35, 45, 53, 58, 63, 64])
 def test_singlescale_bit_exact(gpu_ctx, oracle, name, cell):
     img = dict(IMAGES)[name]
     h, w = img.shape
@@ -220,7 +220,7 @@ sys.path.insert(0, sys.argv[1])
 import ov2slam_amd
 from ov2slam_amd import synth
 ctx = ov2slam_amd.Context(0)
-B, W, H, CELL, NCUR = 11, 376, 240, 35, 48            # 11 items; with chunk = 256 one chunk -- OV2 tests the chunk loop below with B > 256
+B, W, H, CELL, NCUR = 11, 376, 240, 35, 48            # 11 items: one pass (DET_CHUNK = 1024 items, in two sets of 512) -- the pass loop runs below with 1100 items
 rng = np.random.default_rng(5)
 imgs, curs, ncur = [], np.zeros((B, NCUR, 2), np.float32), np.zeros(B, np.int32)
 for b in range(B):
