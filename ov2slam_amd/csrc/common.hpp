@@ -184,7 +184,7 @@ int ov2_lckf_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int
 
 // cv::cornerSubPix (detect.hip, k_corner_subpix) on device points, one wavefront per point slot: `items` images img_item_stride bytes
 // apart, n slots per item xy_item_stride points apart; n_dev (ints ndev_item_stride apart) holds each item's live count on the
-// device (NULL: n).  Asynchronous on ctx->stream; used by the detectors of detect.hip and gftt.hip.
-int launch_subpix(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int stride, float2 *xy_d, int n,
+// device (NULL: n).  Asynchronous on `stream`; used by the detectors of detect.hip and gftt.hip.
+int launch_subpix(hipStream_t stream, const uint8_t *img_d, int w, int h, int stride, float2 *xy_d, int n,
                   int half_win, int max_iter, double eps, const int *n_dev = nullptr,
                   int items = 1, long long img_item_stride = 0, int xy_item_stride = 0, int ndev_item_stride = 0);

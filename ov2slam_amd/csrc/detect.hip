@@ -19,6 +19,7 @@
 //      Bit-identical results to the serial raster order.
 //   3. k_corner_subpix : cv::cornerSubPix, one wavefront per point (parallel patch, ordered accumulation).
 #include "common.hpp"
+#include "detect_plan.hpp"        // size constants, launch geometry, LDS bytes, scratch layouts, adaptation rules, geometry check
 #include <limits.h>
 #include <float.h>
 #include <math.h>
@@ -26,9 +27,6 @@
 #include <mutex>
 
 #pragma clang fp contract(off)
-
-#define DET_MAX_CELL 64
-#define DET_CHUNK 1024     // images per pass of the batch entry points (the response maps of a pass live in the scratch: 1.3 MB per EuRoC image)
 
 __device__ __forceinline__ int d_reflect101(int p, int len)
 {
@@ -48,6 +46,7 @@ __device__ __forceinline__ int d_reflect101(int p, int len)
 // still set when the sweep reaches the cell, it IS the masked arg-max -- the sweep then costs two LDS bit tests per cell instead
 // of a load batch and two arg-max passes, and falls back to the full scan otherwise.
 struct CellCand { int p1; float v1; int p2; float v2; };      // p = lx | ly << 16 (cell-local pixel), -1: none
+static_assert(sizeof(CellCand) == DET_CAND_BYTES, "detect_plan.hpp lays out the scratch with this size");
 
 // Batched launches (one image per batch item of a pyramid, ov2_detect_*_batch_d): per-item strides and parameters; everything
 // zero / NULL for a single image.  The cell kernels run ncells work-groups per item, the selection one work-group per item,
@@ -396,7 +395,6 @@ __device__ __forceinline__ float d_argmax_key_value(unsigned long long k)
     return __uint_as_float(u);
 }
 
-#define STRIP_MAX_CELLS 8
 // the free cells of every image in raster order (the reference's loops `continue` on cells that hold a current keypoint, :296-319):
 // free_list[item * (ncells + 1)] = count, then the cell indices.  One wavefront per image.
 __global__ __launch_bounds__(64) void k_free_cells(int cs, int nwcells, DetBatch B, int *__restrict__ free_list)
@@ -615,6 +613,7 @@ struct SelectOut {
     int nslow, pad_;             // cells of the sweep that needed the full masked scan (a candidate was hit by a neighbour's disc)
     unsigned long long dbg[4];   // wall_clock64 ticks (100 MHz): init, prologue, sweep, compaction
 };
+static_assert(sizeof(SelectOut) == DET_SELECT_OUT_BYTES, "detect_plan.hpp lays out the scratch with this size");
 
 __device__ __forceinline__ void mask_clear_span(unsigned *mask, int wpr, int y, int xa, int xb)
 {
@@ -708,9 +707,7 @@ __device__ void d_fk_std_sort(int *first, int n, int *stk)
     else d_fk_insertion_sort(first, first + n);
 }
 #undef FK_LESS
-#define DET_SEL_THREADS_BATCH 512
 #define DET_SEL_MIN_WAVES 4          // wavefronts per SIMD the batch instance is compiled for (register cap 512 / this)
-#define DET_SORT_CAP 512        // corners of a cell that can enter the emulated sort (non-adjacent after NMS: <= 32 x 32 / 2 for cs = 64, halved again by N3)
 
 // MODE 0 = FAST scores (bytes), 1 = min-eigenvalue (floats); a cell row (<= MAXROW * CHUNKS columns) is held in registers
 // MAXROW columns at a time: (36,1) and (52,1) cover the reference cell sizes with compile-time column indices, (32,2) the rest
@@ -1277,7 +1274,7 @@ __global__ __launch_bounds__(64) void k_corner_subpix(SubpixParams P, const uint
 // ---------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------
-int launch_subpix(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int stride, float2 *xy_d, int n,
+int launch_subpix(hipStream_t stream, const uint8_t *img_d, int w, int h, int stride, float2 *xy_d, int n,
                   int half_win, int max_iter, double eps, const int *n_dev,
                   int items, long long img_item_stride, int xy_item_stride, int ndev_item_stride)
 {
@@ -1295,127 +1292,85 @@ int launch_subpix(ov2_ctx *ctx, const uint8_t *img_d, int w, int h, int stride, 
         P.e[i] = expf(-x * x);
     }
     dim3 grid(n, items), block(64);                           // one wavefront per point (and batch item)
-    switch (half_win) {
-    case 1: hipLaunchKernelGGL(k_corner_subpix<1>, grid, block, 0, ctx->stream, P, img_d, xy_d, n_dev); break;
-    case 2: hipLaunchKernelGGL(k_corner_subpix<2>, grid, block, 0, ctx->stream, P, img_d, xy_d, n_dev); break;
-    case 3: hipLaunchKernelGGL(k_corner_subpix<3>, grid, block, 0, ctx->stream, P, img_d, xy_d, n_dev); break;
-    case 4: hipLaunchKernelGGL(k_corner_subpix<4>, grid, block, 0, ctx->stream, P, img_d, xy_d, n_dev); break;
-    default: hipLaunchKernelGGL(k_corner_subpix<5>, grid, block, 0, ctx->stream, P, img_d, xy_d, n_dev); break;
-    }
+    static void (*const subpix[SP_MAX_HALF])(SubpixParams, const uint8_t *, float2 *, const int *) = {k_corner_subpix<1>, k_corner_subpix<2>, k_corner_subpix<3>,
+                                                                                                      k_corner_subpix<4>, k_corner_subpix<5>};
+    hipLaunchKernelGGL(subpix[half_win - 1], grid, block, 0, stream, P, img_d, xy_d, n_dev);
     OV2_HIP_CHECK(hipGetLastError());
     return OV2_OK;
 }
 
-static int g_strip_static_lds = 0;                               // k_mineig_strip's static LDS, read where the limits are raised
+// The twelve k_grid_select instances, [mode][class of the cell size (det_select_class)][0: 1024 threads, 1: DET_SEL_THREADS_BATCH].
+// The launch and det_raise_lds_limits both read this table: no instance can run without its limit raised.
+typedef void (*select_kernel)(SelectParams, const float2 *, const uint8_t *, const float *, const CellCand *, float2 *, SelectOut *, DetBatch);
+template <int MODE, int C, int NT> static constexpr select_kernel sel() { return k_grid_select<MODE, DET_SELECT_CLASS[C].maxrow, DET_SELECT_CLASS[C].chunks, NT>; }
+static const select_kernel g_select[2][3][2] = {
+    {{sel<0, 0, 1024>(), sel<0, 0, DET_SEL_THREADS_BATCH>()}, {sel<0, 1, 1024>(), sel<0, 1, DET_SEL_THREADS_BATCH>()}, {sel<0, 2, 1024>(), sel<0, 2, DET_SEL_THREADS_BATCH>()}},
+    {{sel<1, 0, 1024>(), sel<1, 0, DET_SEL_THREADS_BATCH>()}, {sel<1, 1, 1024>(), sel<1, 1, DET_SEL_THREADS_BATCH>()}, {sel<1, 2, 1024>(), sel<1, 2, DET_SEL_THREADS_BATCH>()}}};
+
 // The dynamic-LDS limit is a per-function, process-wide attribute: raise it ONCE for every instance to the hardware maximum
 // (less the kernel's static LDS) instead of per call to that call's need -- two contexts on two threads would race on it.
-static hipError_t det_raise_lds_limits()
+struct DetLimits { hipError_t err; int strip_static_lds; };         // k_mineig_strip's static LDS: what its geometry has to leave free
+static const DetLimits &det_raise_lds_limits()
 {
     static std::once_flag once;
-    static hipError_t err = hipSuccess;
+    static DetLimits L = {hipSuccess, 0};
     std::call_once(once, [] {
-        auto raise = [](const void *fn) {
+        auto raise = [](const void *fn, int *static_lds) {
             hipFuncAttributes fa;
             hipError_t e = hipFuncGetAttributes(&fa, fn);
             if (e != hipSuccess) return e;
-            if (fn == (const void *)k_mineig_strip) g_strip_static_lds = (int)fa.sharedSizeBytes;
-            return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
+            if (static_lds) *static_lds = (int)fa.sharedSizeBytes;
+            return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DET_LDS_BYTES - (int)fa.sharedSizeBytes);
         };
-        const void *fns[] = {(const void *)k_mineig_cells, (const void *)k_mineig_strip,
-                             (const void *)k_grid_select<0, 36, 1, 1024>, (const void *)k_grid_select<0, 52, 1, 1024>, (const void *)k_grid_select<0, 32, 2, 1024>,
-                             (const void *)k_grid_select<1, 36, 1, 1024>, (const void *)k_grid_select<1, 52, 1, 1024>, (const void *)k_grid_select<1, 32, 2, 1024>,
-                             (const void *)k_grid_select<0, 36, 1, DET_SEL_THREADS_BATCH>, (const void *)k_grid_select<0, 52, 1, DET_SEL_THREADS_BATCH>,
-                             (const void *)k_grid_select<0, 32, 2, DET_SEL_THREADS_BATCH>, (const void *)k_grid_select<1, 36, 1, DET_SEL_THREADS_BATCH>,
-                             (const void *)k_grid_select<1, 52, 1, DET_SEL_THREADS_BATCH>, (const void *)k_grid_select<1, 32, 2, DET_SEL_THREADS_BATCH>};
-        for (const void *fn : fns) if (err == hipSuccess) err = raise(fn);
+        L.err = raise((const void *)k_mineig_cells, nullptr);
+        if (L.err == hipSuccess) L.err = raise((const void *)k_mineig_strip, &L.strip_static_lds);
+        for (auto &mode : g_select) for (auto &cls : mode) for (select_kernel fn : cls) if (L.err == hipSuccess) L.err = raise((const void *)fn, nullptr);
     });
-    return err;
+    return L;
 }
 
-// Dynamic LDS of k_grid_select: exclusion mask + cell tables (+ the sort areas of the libstdc++ tie order, FAST only).
-// *slots = sort areas that fit (<= 16); returns 0 when the image does not fit at all.
-static size_t det_select_lds(int w, int h, int cell, int mode, int fast_tie, int *slots)
-{
-    const int nw = w / cell, nh = h / cell, ncells = nw * nh, wpr = (w + 31) / 32;
-    const size_t base = (size_t)h * wpr * 4 + 64 * 4 + (size_t)ncells * 16 + (size_t)nh * 4 + (((size_t)(nh + 1) * (nw + 1) + 3) & ~(size_t)3) + (size_t)ncells * 8;
-    const size_t limit = 160 * 1024 - 256;                           // less the kernel's static LDS (locks, counters)
-    *slots = 0;
-    if (base > limit) return 0;
-    if (mode != 0 || fast_tie != OV2_FAST_TIE_LIBSTDCXX) return base;
-    const size_t area = (size_t)(DET_SORT_CAP + 72) * 4;
-    const size_t fit = (limit - base) / area;
-    if (fit == 0) return 0;
-    *slots = fit > 16 ? 16 : (int)fit;
-    return base + (size_t)*slots * area;
-}
+// what det_check_geometry refused, as the entry points report it (OV2_EUNSUPPORTED each)
+static const char *const det_check_msg[] = {"", "cell size must be in [8,64]", "image too large", "image too large for the LDS-resident exclusion mask"};
 
 // The three launches of a detection (response + candidates per cell, selection, sub-pixel refinement) for `items` images
-// that lie `B.img_stride` bytes apart; every pointer addresses item 0.  Asynchronous on the context's stream.
-static int enqueue_detect(ov2_ctx *ctx, int mode, const uint8_t *im, int w, int h, int im_stride, int cell, int items, DetBatch B,
+// that lie `B.img_stride` bytes apart; every pointer addresses item 0.  Asynchronous on `stream`; the context gives the options only.
+static int enqueue_detect(const ov2_ctx *ctx, hipStream_t stream, int mode, const uint8_t *im, int w, int h, int im_stride, int cell, int items, DetBatch B,
                           int fast_th, int mask_mode, const int roi[4], double quality, int ncur, const float2 *cur_d,
-                          uint8_t *maps_d, CellCand *cand_d, float2 *out_d, SelectOut *so_d, int do_subpix)
+                          uint8_t *maps_d, CellCand *cand_d, int *free_d, float2 *out_d, SelectOut *so_d, int do_subpix)
 {
-    const int nw = w / cell, nh = h / cell, ncells = nw * nh, npx = cell * cell, wpr = (w + 31) / 32;
+    const int nw = w / cell, nh = h / cell, ncells = nw * nh;
     int sort_slots = 0;
-    const size_t sel_lds = det_select_lds(w, h, cell, mode, ctx->det_fast_tie, &sort_slots);
+    const size_t sel_lds = det_select_lds(w, h, cell, mode, ctx->det_fast_tie == OV2_FAST_TIE_LIBSTDCXX, &sort_slots);
     B.ncells = ncells; B.cur = cur_d; B.ncur_all = ncur;
     if (mode == 0) {
         int th = fast_th < 0 ? 0 : (fast_th > 255 ? 255 : fast_th);
-        hipLaunchKernelGGL(k_fast_cells, dim3(ncells * items), dim3(256), 0, ctx->stream, im, w, h, im_stride, cell, nw, th, maps_d, mask_mode, cand_d, B);
-    } else if (ctx->det_strip == 1 || (ctx->det_strip < 0 && (long long)ncells * items >= 2048)) {
-        // batches: the free cells of an image side by side, several per work-group (k_mineig_strip); the cells per group / wavefronts
-        // per group that leave the fewest lanes idle: a wavefront owns at most 60 of its 64 columns.  Only what fits the LDS is a
-        // choice: at cell 64 the densest packing (7 cells on 8 wavefronts) needs 165888 bytes, so (6, 7) runs
-        auto strip_lds = [cell](int k) { return (((size_t)cell * 64 * k + 15) & ~(size_t)15) + (size_t)k * cell * 65 * 4; };
-        const size_t lds_limit = (size_t)160 * 1024 - (size_t)g_strip_static_lds;
-        int best_n = 0, best_k = 0;
-        double best_e = 0.0;
-        for (int nc = 1; nc <= STRIP_MAX_CELLS; nc++) {
-            const int k = (nc * cell + 59) / 60;
-            if (k > 8) break;
-            if (strip_lds(k) > lds_limit) continue;
-            const double e = (double)nc * cell / (64.0 * k);
-            if (best_n == 0 || e > best_e + 1e-9) { best_e = e; best_n = nc; best_k = k; }
-        }
-        OV2_REQUIRE(best_n > 0, OV2_EUNSUPPORTED, "no strip geometry of this cell size fits the LDS");
-        const int owned = (best_n * cell + best_k - 1) / best_k;
-        const size_t lds = strip_lds(best_k);
-        int *free_d = (int *)(cand_d + (size_t)items * ncells);          // (the callers reserve it behind the candidates)
-        hipLaunchKernelGGL(k_free_cells, dim3(items), dim3(64), (size_t)(ncells + 31) / 32 * 4, ctx->stream, cell, nw, B, free_d);
-        hipLaunchKernelGGL(k_mineig_strip, dim3((ncells + best_n - 1) / best_n, items), dim3(64 * best_k), lds, ctx->stream, im, w, h, im_stride, cell, nw,
-                           (float *)maps_d, ctx->sobel_dy_order, cell / 4, cand_d, B, best_n, owned, (const int *)free_d);
+        hipLaunchKernelGGL(k_fast_cells, dim3(ncells * items), dim3(256), 0, stream, im, w, h, im_stride, cell, nw, th, maps_d, mask_mode, cand_d, B);
+    } else if (det_use_strip(ctx->det_strip, ncells, items)) {
+        // batches: the free cells of an image side by side, several per work-group (k_mineig_strip)
+        const DetStrip g = det_strip_geometry(cell, det_raise_lds_limits().strip_static_lds);
+        OV2_REQUIRE(g.cells > 0, OV2_EUNSUPPORTED, "no strip geometry of this cell size fits the LDS");
+        hipLaunchKernelGGL(k_free_cells, dim3(items), dim3(64), (size_t)(ncells + 31) / 32 * 4, stream, cell, nw, B, free_d);
+        hipLaunchKernelGGL(k_mineig_strip, dim3((ncells + g.cells - 1) / g.cells, items), dim3(64 * g.waves), g.lds, stream, im, w, h, im_stride, cell, nw,
+                           (float *)maps_d, ctx->sobel_dy_order, cell / 4, cand_d, B, g.cells, g.owned, (const int *)free_d);
     } else {
-        const size_t lds = (size_t)npx * 5 + 16;                      // lambda_min (float) + blurred cell (byte) per pixel
-        hipLaunchKernelGGL(k_mineig_cells, dim3(ncells * items), dim3(64), lds, ctx->stream, im, w, h, im_stride, cell, nw, (float *)maps_d, ctx->sobel_dy_order, cell / 4, cand_d, B);
+        const size_t lds = (size_t)cell * cell * 5 + 16;              // lambda_min (float) + blurred cell (byte) per pixel
+        hipLaunchKernelGGL(k_mineig_cells, dim3(ncells * items), dim3(64), lds, stream, im, w, h, im_stride, cell, nw, (float *)maps_d, ctx->sobel_dy_order, cell / 4, cand_d, B);
     }
     SelectParams P;
-    P.w = w; P.h = h; P.cs = cell; P.nwcells = nw; P.nhcells = nh; P.radius = cell / 4; P.mask_words_per_row = wpr;
+    P.w = w; P.h = h; P.cs = cell; P.nwcells = nw; P.nhcells = nh; P.radius = cell / 4; P.mask_words_per_row = (w + 31) / 32;
     P.mode = mode; P.mask_mode = mask_mode; P.ncur = ncur;
     P.fast_tie = ctx->det_fast_tie; P.sort_slots = sort_slots > 0 ? sort_slots : 1;
     P.roi_x = roi ? roi[0] : 0; P.roi_y = roi ? roi[1] : 0; P.roi_w = roi ? roi[2] : w; P.roi_h = roi ? roi[3] : h;
     P.quality = quality;
-    // One image: sixteen wavefronts, a row of cells each (latency).  Batches: EIGHT (rows w, w + 8 -- the anti-diagonal dependence keeps
-    // at most nwcells / 2 rows busy at a time anyway), so that two work-groups share a CU's sixteen wavefront slots (106 VGPRs: four
-    // per SIMD) instead of one
-    const bool sel_batch = items >= 64;
-#define OV2_LAUNCH_SELECT(MD, MR, CH)                                                                                               \
-    do { if (sel_batch) hipLaunchKernelGGL((k_grid_select<MD, MR, CH, DET_SEL_THREADS_BATCH>), dim3(items), dim3(DET_SEL_THREADS_BATCH), sel_lds, ctx->stream, P, cur_d, \
-                       (const uint8_t *)maps_d, (const float *)maps_d, (const CellCand *)cand_d, out_d, so_d, B);                   \
-         else hipLaunchKernelGGL((k_grid_select<MD, MR, CH, 1024>), dim3(items), dim3(1024), sel_lds, ctx->stream, P, cur_d, (const uint8_t *)maps_d,     \
-                       (const float *)maps_d, (const CellCand *)cand_d, out_d, so_d, B); } while (0)
-    if (mode == 0) { if (cell <= 36) OV2_LAUNCH_SELECT(0, 36, 1); else if (cell <= 52) OV2_LAUNCH_SELECT(0, 52, 1); else OV2_LAUNCH_SELECT(0, 32, 2); }
-    else { if (cell <= 36) OV2_LAUNCH_SELECT(1, 36, 1); else if (cell <= 52) OV2_LAUNCH_SELECT(1, 52, 1); else OV2_LAUNCH_SELECT(1, 32, 2); }
-#undef OV2_LAUNCH_SELECT
+    const int nt = det_select_threads(items);
+    const select_kernel select = g_select[mode][det_select_class(cell)][nt != 1024];
+    hipLaunchKernelGGL(select, dim3(items), dim3(nt), sel_lds, stream, P, cur_d, (const uint8_t *)maps_d, (const float *)maps_d, (const CellCand *)cand_d, out_d, so_d, B);
     OV2_HIP_CHECK(hipGetLastError());
+    if (!do_subpix) return OV2_OK;
     // sub-pixel refinement over the CAPACITY of the output list (the kernel reads the count on the device and the
     // surplus wavefronts leave at once)
-    if (do_subpix) {
-        const int cap = mode == 0 ? ncells : 2 * ncells;
-        const int rc = launch_subpix(ctx, im, w, h, im_stride, out_d, cap, 3, 30, 0.01, (const int *)so_d,
-                                     items, B.img_stride, B.out_stride, (int)(sizeof(SelectOut) / sizeof(int)));
-        if (rc) return rc;
-    }
-    return OV2_OK;
+    return launch_subpix(stream, im, w, h, im_stride, out_d, det_out_cap(mode, ncells), 3, 30, 0.01, (const int *)so_d,
+                         items, B.img_stride, B.out_stride, (int)(sizeof(SelectOut) / sizeof(int)));
 }
 
 // img_h: host image (uploaded first) -- or img_d: an image already in HBM (pyramid level 0: no upload), row pitch `stride`
@@ -1428,53 +1383,64 @@ static int detect_common(ov2_ctx *ctx, int mode, const uint8_t *img_h, const uin
     memset(so_h, 0, sizeof(*so_h));
     if ((!img_h && !img_d) || w <= 0 || h <= 0) return OV2_OK;            // empty image -> empty vector (:291-294 / :446-449)
     OV2_REQUIRE(stride >= w, OV2_EINVAL, "stride < width");
-    OV2_REQUIRE(cell >= 8 && cell <= DET_MAX_CELL, OV2_EUNSUPPORTED, "cell size must be in [8,64]");
+    const DetCheck chk = det_check_geometry(w, h, cell, mode, ctx->det_fast_tie == OV2_FAST_TIE_LIBSTDCXX);
+    OV2_REQUIRE(chk == DET_CHECK_OK, OV2_EUNSUPPORTED, det_check_msg[chk]);
     OV2_REQUIRE(ncur >= 0 && (ncur == 0 || cur_xy_h), OV2_EINVAL, "bad current keypoints");
-    OV2_REQUIRE(w < 65536 && h < 32768, OV2_EUNSUPPORTED, "image too large");
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    OV2_HIP_CHECK(det_raise_lds_limits());
-    const int nw = w / cell, nh = h / cell, ncells = nw * nh;
+    OV2_HIP_CHECK(det_raise_lds_limits().err);
+    const int ncells = (w / cell) * (h / cell);
     if (ncells == 0) return OV2_OK;
-    const int npx = cell * cell;
-    { int slots_; OV2_REQUIRE(det_select_lds(w, h, cell, mode, ctx->det_fast_tie, &slots_) != 0, OV2_EUNSUPPORTED, "image too large for the LDS-resident exclusion mask"); }
-
-    // device scratch: [img w*h][maps][cur 8*ncur][out 8*2*ncells][SelectOut]
-    const size_t o_img = 0;
-    const size_t map_bytes = (size_t)ncells * npx * (mode == 0 ? 1 : 4);
-    const size_t o_map = img_d ? 0 : (((size_t)w * h + 255) & ~(size_t)255);
-    const size_t o_cur = (o_map + map_bytes + 255) & ~(size_t)255;
-    const size_t o_out = (o_cur + 8 * (size_t)(ncur > 0 ? ncur : 1) + 255) & ~(size_t)255;
-    const size_t o_so = o_out + 16 * (size_t)ncells;
-    const size_t o_cand = (o_so + sizeof(SelectOut) + 255) & ~(size_t)255;
-    const size_t total = o_cand + sizeof(CellCand) * (size_t)ncells + 4 * ((size_t)ncells + 1);        // candidates, then the free-cell list (k_free_cells)
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(16 * (size_t)ncells + sizeof(SelectOut)); if (rc) return rc;
+    const DetScratch S = det_scratch(w, h, cell, mode, ncur, !img_d);
+    const size_t out_bytes = S.so + sizeof(SelectOut) - S.out;       // the points and, right behind them, the counters
+    int rc = ctx->reserve_device(S.total);  if (rc) return rc;
+    rc = ctx->reserve_host(out_bytes); if (rc) return rc;
     uint8_t *ds = (uint8_t *)ctx->d_scratch;
     const uint8_t *im = img_d;                                  // what the kernels read, and its pitch
     int im_stride = stride;
     if (!img_d) {
-        rc = ctx->upload_image(ds + o_img, (size_t)w, img_h, (size_t)stride, (size_t)w, (size_t)h);
+        rc = ctx->upload_image(ds + S.img, (size_t)w, img_h, (size_t)stride, (size_t)w, (size_t)h);
         if (rc) return rc;
-        im = ds + o_img; im_stride = w;
+        im = ds + S.img; im_stride = w;
     }
-    if (ncur > 0) OV2_HIP_CHECK(hipMemcpyAsync(ds + o_cur, cur_xy_h, 8 * (size_t)ncur, hipMemcpyHostToDevice, ctx->stream));
+    if (ncur > 0) OV2_HIP_CHECK(hipMemcpyAsync(ds + S.cur, cur_xy_h, 8 * (size_t)ncur, hipMemcpyHostToDevice, ctx->stream));
 
-    DetBatch B;
-    memset(&B, 0, sizeof(B));
-    rc = enqueue_detect(ctx, mode, im, w, h, im_stride, cell, 1, B, fast_th, mask_mode, roi, quality, ncur, (const float2 *)(ds + o_cur),
-                        ds + o_map, (CellCand *)(ds + o_cand), (float2 *)(ds + o_out), (SelectOut *)(ds + o_so), do_subpix);
+    DetBatch B = {};
+    rc = enqueue_detect(ctx, ctx->stream, mode, im, w, h, im_stride, cell, 1, B, fast_th, mask_mode, roi, quality, ncur, (const float2 *)(ds + S.cur),
+                        ds + S.map, (CellCand *)(ds + S.cand), (int *)(ds + S.free_list), (float2 *)(ds + S.out), (SelectOut *)(ds + S.so), do_subpix);
     if (rc) return rc;
     // ONE copy of (points, counters) and ONE synchronisation
     uint8_t *hs = (uint8_t *)ctx->h_scratch;
-    OV2_HIP_CHECK(hipMemcpyAsync(hs, ds + o_out, 16 * (size_t)ncells + sizeof(SelectOut), hipMemcpyDeviceToHost, ctx->stream));
+    OV2_HIP_CHECK(hipMemcpyAsync(hs, ds + S.out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    memcpy(so_h, hs + 16 * (size_t)ncells, sizeof(SelectOut));
+    memcpy(so_h, hs + (S.so - S.out), sizeof(SelectOut));
     if (ctx->debug)
         fprintf(stderr, "[ov2 det] select ticks (100MHz): init %llu prologue %llu sweep %llu compaction %llu; cells on the full-scan path: %d\n",
                 so_h->dbg[0], so_h->dbg[1], so_h->dbg[2], so_h->dbg[3], so_h->nslow);
     const int n = so_h->n;
     if (n > 0) memcpy(out_xy_h, hs, 8 * (size_t)n);
     *out_n = n;
+    return OV2_OK;
+}
+
+// detectGridFAST / detectSingleScale on one image, host or device, with the reference's adaptation of the threshold / the quality
+// behind it (an empty image adapts nothing); the public forms have checked their pointers
+static int detect_fast_one(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int w, int h, int stride, int cell, const float *cur_xy_h, int ncur,
+                           int *fast_th_inout, int mask_mode, int do_subpix, float *out_xy_h, int *out_n)
+{
+    SelectOut so;
+    const int rc = detect_common(ctx, 0, img_h, img_d, w, h, stride, cell, cur_xy_h, ncur, *fast_th_inout, mask_mode, nullptr, 0.0, do_subpix, out_xy_h, out_n, &so);
+    if (rc != OV2_OK || (!img_h && !img_d) || w <= 0 || h <= 0) return rc;
+    *fast_th_inout = det_adapt_fast_th(*fast_th_inout, so.nbkps, so.nbempty);
+    return OV2_OK;
+}
+
+static int detect_singlescale_one(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int w, int h, int stride, int cell, const float *cur_xy_h, int ncur,
+                                  const int roi[4], double *quality_inout, int do_subpix, float *out_xy_h, int *out_n)
+{
+    SelectOut so;
+    const int rc = detect_common(ctx, 1, img_h, img_d, w, h, stride, cell, cur_xy_h, ncur, 0, 0, roi, *quality_inout, do_subpix, out_xy_h, out_n, &so);
+    if (rc != OV2_OK || (!img_h && !img_d) || w <= 0 || h <= 0) return rc;
+    *quality_inout = det_adapt_quality(*quality_inout, so.n, (w / cell) * (h / cell), so.nboccup);
     return OV2_OK;
 }
 
@@ -1486,16 +1452,7 @@ int ov2_detect_grid_fast(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int s
 {
     OV2_REQUIRE(fast_th_inout != nullptr, OV2_EINVAL, "fast_th_inout == NULL");
     OV2_REQUIRE(mask_mode == OV2_MASK_AS_EXECUTED || mask_mode == OV2_MASK_INTENDED, OV2_EINVAL, "bad mask_mode");
-    SelectOut so;
-    const int th = *fast_th_inout;
-    const int rc = detect_common(ctx, 0, img_h, nullptr, w, h, stride, cell, cur_xy_h, ncur, th, mask_mode, nullptr, 0.0,
-                                 do_subpix, out_xy_h, out_n, &so);
-    if (rc != OV2_OK) return rc;
-    if (!img_h || w <= 0 || h <= 0) return OV2_OK;
-    // threshold adaptation (:546-552), int *= double truncates
-    if ((double)so.nbkps < 0.5 * (double)so.nbempty && so.nbempty > 10) *fast_th_inout = (int)(th * 0.66);
-    else if (so.nbkps == so.nbempty) *fast_th_inout = (int)(th * 1.5);
-    return OV2_OK;
+    return detect_fast_one(ctx, img_h, nullptr, w, h, stride, cell, cur_xy_h, ncur, fast_th_inout, mask_mode, do_subpix, out_xy_h, out_n);
 }
 
 int ov2_detect_singlescale(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stride, int cell,
@@ -1503,17 +1460,7 @@ int ov2_detect_singlescale(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int
                            int do_subpix, float *out_xy_h, int *out_n)
 {
     OV2_REQUIRE(quality_inout != nullptr && roi != nullptr, OV2_EINVAL, "quality_inout / roi == NULL");
-    SelectOut so;
-    const double q = *quality_inout;
-    const int rc = detect_common(ctx, 1, img_h, nullptr, w, h, stride, cell, cur_xy_h, ncur, 0, 0, roi, q,
-                                 do_subpix, out_xy_h, out_n, &so);
-    if (rc != OV2_OK) return rc;
-    if (!img_h || w <= 0 || h <= 0) return OV2_OK;
-    // :418-423 (nbkps there is the size after the secondary top-up)
-    const int ncells = (w / cell) * (h / cell);
-    if ((double)so.n < 0.33 * (double)(ncells - so.nboccup)) *quality_inout = q / 2.;
-    else if ((double)so.n > 0.9 * (double)(ncells - so.nboccup)) *quality_inout = q * 1.5;
-    return OV2_OK;
+    return detect_singlescale_one(ctx, img_h, nullptr, w, h, stride, cell, cur_xy_h, ncur, roi, quality_inout, do_subpix, out_xy_h, out_n);
 }
 
 // Device-resident forms: the image is level 0 of batch item `item` of a pyramid that is already in HBM -- the (equalised)
@@ -1535,15 +1482,8 @@ int ov2_detect_grid_fast_d(ov2_ctx *ctx, const ov2_pyr *pyr, int item, int cell,
     OV2_REQUIRE(fast_th_inout != nullptr, OV2_EINVAL, "fast_th_inout == NULL");
     OV2_REQUIRE(mask_mode == OV2_MASK_AS_EXECUTED || mask_mode == OV2_MASK_INTENDED, OV2_EINVAL, "bad mask_mode");
     const uint8_t *img; int w, h, stride;
-    int rc = pyr_level0(ctx, pyr, item, &img, &w, &h, &stride);
-    if (rc != OV2_OK) return rc;
-    SelectOut so;
-    const int th = *fast_th_inout;
-    rc = detect_common(ctx, 0, nullptr, img, w, h, stride, cell, cur_xy_h, ncur, th, mask_mode, nullptr, 0.0, do_subpix, out_xy_h, out_n, &so);
-    if (rc != OV2_OK) return rc;
-    if ((double)so.nbkps < 0.5 * (double)so.nbempty && so.nbempty > 10) *fast_th_inout = (int)(th * 0.66);     // :546-552
-    else if (so.nbkps == so.nbempty) *fast_th_inout = (int)(th * 1.5);
-    return OV2_OK;
+    const int rc = pyr_level0(ctx, pyr, item, &img, &w, &h, &stride);
+    return rc != OV2_OK ? rc : detect_fast_one(ctx, nullptr, img, w, h, stride, cell, cur_xy_h, ncur, fast_th_inout, mask_mode, do_subpix, out_xy_h, out_n);
 }
 
 int ov2_detect_singlescale_d(ov2_ctx *ctx, const ov2_pyr *pyr, int item, int cell, const float *cur_xy_h, int ncur,
@@ -1551,20 +1491,12 @@ int ov2_detect_singlescale_d(ov2_ctx *ctx, const ov2_pyr *pyr, int item, int cel
 {
     OV2_REQUIRE(quality_inout != nullptr && roi != nullptr, OV2_EINVAL, "quality_inout / roi == NULL");
     const uint8_t *img; int w, h, stride;
-    int rc = pyr_level0(ctx, pyr, item, &img, &w, &h, &stride);
-    if (rc != OV2_OK) return rc;
-    SelectOut so;
-    const double q = *quality_inout;
-    rc = detect_common(ctx, 1, nullptr, img, w, h, stride, cell, cur_xy_h, ncur, 0, 0, roi, q, do_subpix, out_xy_h, out_n, &so);
-    if (rc != OV2_OK) return rc;
-    const int ncells = (w / cell) * (h / cell);
-    if ((double)so.n < 0.33 * (double)(ncells - so.nboccup)) *quality_inout = q / 2.;                         // :418-423
-    else if ((double)so.n > 0.9 * (double)(ncells - so.nboccup)) *quality_inout = q * 1.5;
-    return OV2_OK;
+    const int rc = pyr_level0(ctx, pyr, item, &img, &w, &h, &stride);
+    return rc != OV2_OK ? rc : detect_singlescale_one(ctx, nullptr, img, w, h, stride, cell, cur_xy_h, ncur, roi, quality_inout, do_subpix, out_xy_h, out_n);
 }
 
-// Batched device-resident detection: every batch item of the pyramid in ONE call (chunks of 256 items share the response /
-// candidate scratch; launches of successive chunks are stream-ordered, one host synchronisation at the end).
+// Batched device-resident detection: every batch item of the pyramid in ONE call (the passes of DetBatchScratch share the response /
+// candidate scratch; launches of successive passes are stream-ordered, one host synchronisation at the end).
 static int detect_batch(ov2_ctx *ctx, int mode, const ov2_pyr *pyr, int cell, const float *cur_xy_d, int cur_cap, const int *ncur_d,
                         int *fast_th_inout, int mask_mode, const int roi[4], double *quality_inout, int do_subpix,
                         float *out_xy_d, int out_cap, int *out_n_h)
@@ -1574,55 +1506,39 @@ static int detect_batch(ov2_ctx *ctx, int mode, const ov2_pyr *pyr, int cell, co
     int rc = pyr_level0(ctx, pyr, 0, &img, &w, &h, &stride);
     if (rc != OV2_OK) return rc;
     const int items = pyr->d.batch;
-    OV2_REQUIRE(cell >= 8 && cell <= DET_MAX_CELL, OV2_EUNSUPPORTED, "cell size must be in [8,64]");
-    OV2_REQUIRE(w < 65536 && h < 32768, OV2_EUNSUPPORTED, "image too large");
+    const DetCheck chk = det_check_geometry(w, h, cell, mode, ctx->det_fast_tie == OV2_FAST_TIE_LIBSTDCXX);
+    OV2_REQUIRE(chk == DET_CHECK_OK, OV2_EUNSUPPORTED, det_check_msg[chk]);
     OV2_REQUIRE(cur_cap >= 0 && (ncur_d == nullptr || cur_xy_d != nullptr), OV2_EINVAL, "bad current keypoints");
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    OV2_HIP_CHECK(det_raise_lds_limits());
-    const int nw = w / cell, nh = h / cell, ncells = nw * nh, npx = cell * cell;
+    OV2_HIP_CHECK(det_raise_lds_limits().err);
+    const int ncells = (w / cell) * (h / cell);
     for (int i = 0; i < items; i++) out_n_h[i] = 0;
     if (ncells == 0) return OV2_OK;
-    const int cap = mode == 0 ? ncells : 2 * ncells;
-    OV2_REQUIRE(out_cap >= cap, OV2_EINVAL, "out_cap too small: (w/cell)*(h/cell) points per item for FAST, twice that for single scale");
-    { int slots_; OV2_REQUIRE(det_select_lds(w, h, cell, mode, ctx->det_fast_tie, &slots_) != 0, OV2_EUNSUPPORTED, "image too large for the LDS-resident exclusion mask"); }
-    // Passes of `chunk` images share the response / candidate scratch.  More than one pass: TWO scratch sets of half a chunk, the passes
-    // alternating between the context's stream and an auxiliary one -- the selection sweep of a pass (a dependency chain: two work-groups
-    // per CU, the vector units nearly idle) then runs beside the response kernel of the next pass (issue-bound) instead of between two of them
-    const bool two = items > DET_CHUNK / 2;
-    const int chunk = two ? DET_CHUNK / 2 : std::min(items, DET_CHUNK);
-    const size_t map_bytes = (size_t)ncells * npx * (mode == 0 ? 1 : 4);
-    const size_t set_bytes = (((size_t)chunk * map_bytes + 255) & ~(size_t)255) +
-                             (((size_t)chunk * (ncells * sizeof(CellCand) + 4 * ((size_t)ncells + 1)) + 255) & ~(size_t)255);   // maps; candidates + free-cell lists
-    const size_t o_cand_in_set = ((size_t)chunk * map_bytes + 255) & ~(size_t)255;
-    const size_t o_so = (two ? 2 : 1) * set_bytes;
-    const size_t o_par = (o_so + (size_t)items * sizeof(SelectOut) + 255) & ~(size_t)255;       // per-item threshold / quality
-    const size_t total = o_par + (size_t)items * 8;
-    rc = ctx->reserve_device(total); if (rc) return rc;
+    OV2_REQUIRE(out_cap >= det_out_cap(mode, ncells), OV2_EINVAL, "out_cap too small: (w/cell)*(h/cell) points per item for FAST, twice that for single scale");
+    const DetBatchScratch S = det_batch_scratch(cell, ncells, mode, items);
+    const bool two = S.sets == 2;
+    rc = ctx->reserve_device(S.total); if (rc) return rc;
     rc = ctx->reserve_host((size_t)items * sizeof(SelectOut)); if (rc) return rc;
     uint8_t *ds = (uint8_t *)ctx->d_scratch;
-    if (mode == 0) OV2_HIP_CHECK(hipMemcpyAsync(ds + o_par, fast_th_inout, 4 * (size_t)items, hipMemcpyHostToDevice, ctx->stream));
-    else OV2_HIP_CHECK(hipMemcpyAsync(ds + o_par, quality_inout, 8 * (size_t)items, hipMemcpyHostToDevice, ctx->stream));
-    hipStream_t main_stream = ctx->stream;
+    const hipStream_t main_stream = ctx->stream;
+    OV2_HIP_CHECK(hipMemcpyAsync(ds + S.par, mode == 0 ? (const void *)fast_th_inout : (const void *)quality_inout, (mode == 0 ? 4 : 8) * (size_t)items,
+                                 hipMemcpyHostToDevice, main_stream));
     if (two) {
         if (!ctx->det_aux_stream) OV2_HIP_CHECK(hipStreamCreateWithFlags(&ctx->det_aux_stream, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) if (!ctx->det_ev[i]) OV2_HIP_CHECK(hipEventCreateWithFlags(&ctx->det_ev[i], hipEventDisableTiming));
         OV2_HIP_CHECK(hipEventRecord(ctx->det_ev[0], main_stream));                     // what precedes this call on the context's stream (the pyramid, the parameters)
         OV2_HIP_CHECK(hipStreamWaitEvent(ctx->det_aux_stream, ctx->det_ev[0], 0));
     }
-    int pass = 0;
-    for (int c0 = 0; c0 < items; c0 += chunk, pass++) {
-        const int n = std::min(chunk, items - c0);
-        const size_t o_set = two ? (size_t)(pass & 1) * set_bytes : 0;
-        DetBatch B;
-        memset(&B, 0, sizeof(B));
+    for (int c0 = 0, pass = 0; c0 < items; c0 += S.chunk, pass++) {
+        const int n = std::min(S.chunk, items - c0);
+        uint8_t *set = ds + (size_t)(pass & 1) * (two ? S.set_bytes : 0);              // odd passes: the second scratch set, on the auxiliary stream
+        DetBatch B = {};
         B.img_stride = (long long)pyr->d.item_stride; B.cur_stride = cur_cap; B.out_stride = out_cap;
         B.ncur = ncur_d ? ncur_d + c0 : nullptr;
-        if (mode == 0) B.fast_th = (const int *)(ds + o_par) + c0; else B.quality = (const double *)(ds + o_par) + c0;
-        if (two && (pass & 1)) ctx->stream = ctx->det_aux_stream;                       // (the launchers enqueue on the context's stream; a context belongs to one thread)
-        rc = enqueue_detect(ctx, mode, img + (long long)c0 * pyr->d.item_stride, w, h, stride, cell, n, B, 0, mask_mode, roi, 0.0, 0,
-                            (const float2 *)cur_xy_d + (long long)c0 * cur_cap, ds + o_set, (CellCand *)(ds + o_set + o_cand_in_set),
-                            (float2 *)out_xy_d + (long long)c0 * out_cap, (SelectOut *)(ds + o_so) + c0, do_subpix);
-        ctx->stream = main_stream;
+        if (mode == 0) B.fast_th = (const int *)(ds + S.par) + c0; else B.quality = (const double *)(ds + S.par) + c0;
+        rc = enqueue_detect(ctx, two && (pass & 1) ? ctx->det_aux_stream : main_stream, mode, img + (long long)c0 * pyr->d.item_stride, w, h, stride, cell, n, B,
+                            0, mask_mode, roi, 0.0, 0, (const float2 *)cur_xy_d + (long long)c0 * cur_cap, set + S.map, (CellCand *)(set + S.cand),
+                            (int *)(set + S.free_list), (float2 *)out_xy_d + (long long)c0 * out_cap, (SelectOut *)(ds + S.so) + c0, do_subpix);
         if (rc) break;
     }
     if (two) {                                                                          // join (also on an error: nothing of this call may outlive it on the auxiliary stream)
@@ -1632,19 +1548,12 @@ static int detect_batch(ov2_ctx *ctx, int mode, const ov2_pyr *pyr, int cell, co
     }
     if (rc) return rc;
     SelectOut *so = (SelectOut *)ctx->h_scratch;
-    OV2_HIP_CHECK(hipMemcpyAsync(so, ds + o_so, (size_t)items * sizeof(SelectOut), hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    OV2_HIP_CHECK(hipMemcpyAsync(so, ds + S.so, (size_t)items * sizeof(SelectOut), hipMemcpyDeviceToHost, main_stream));
+    OV2_HIP_CHECK(hipStreamSynchronize(main_stream));
     for (int i = 0; i < items; i++) {
         out_n_h[i] = so[i].n;
-        if (mode == 0) {                                                 // threshold adaptation (:546-552), int *= double truncates
-            const int th = fast_th_inout[i];
-            if ((double)so[i].nbkps < 0.5 * (double)so[i].nbempty && so[i].nbempty > 10) fast_th_inout[i] = (int)(th * 0.66);
-            else if (so[i].nbkps == so[i].nbempty) fast_th_inout[i] = (int)(th * 1.5);
-        } else {                                                         // :418-423
-            const double q = quality_inout[i];
-            if ((double)so[i].n < 0.33 * (double)(ncells - so[i].nboccup)) quality_inout[i] = q / 2.;
-            else if ((double)so[i].n > 0.9 * (double)(ncells - so[i].nboccup)) quality_inout[i] = q * 1.5;
-        }
+        if (mode == 0) fast_th_inout[i] = det_adapt_fast_th(fast_th_inout[i], so[i].nbkps, so[i].nbempty);
+        else quality_inout[i] = det_adapt_quality(quality_inout[i], so[i].n, ncells, so[i].nboccup);
     }
     return OV2_OK;
 }
@@ -1676,7 +1585,7 @@ int ov2_corner_subpix(ov2_ctx *ctx, const uint8_t *img_h, int w, int h, int stri
     uint8_t *ds = (uint8_t *)ctx->d_scratch;
     rc = ctx->upload_image(ds, (size_t)w, img_h, (size_t)stride, (size_t)w, (size_t)h); if (rc) return rc;
     OV2_HIP_CHECK(hipMemcpyAsync(ds + o_xy, xy_inout_h, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_subpix(ctx, ds, w, h, w, (float2 *)(ds + o_xy), n, half_win, max_iter, eps);
+    rc = launch_subpix(ctx->stream, ds, w, h, w, (float2 *)(ds + o_xy), n, half_win, max_iter, eps);
     if (rc) return rc;
     OV2_HIP_CHECK(hipMemcpyAsync(xy_inout_h, ds + o_xy, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));

@@ -575,7 +575,7 @@ static int gftt_enqueue(ov2_ctx *ctx, const uint8_t *img, int w, int h, int stri
             hipLaunchKernelGGL(k_gftt_walk, dim3(n), dim3(64), ps == 0 ? walk_lds0 : walk_lds1, ctx->stream, A, ps, G[ps], gw[ps], gh[ps], cap);
             OV2_HIP_CHECK(hipGetLastError());
             if (do_subpix) {
-                const int rc = launch_subpix(ctx, A.img, w, h, stride, ps == 0 ? A.out : A.out2, out_cap, 3, 30, 0.01,
+                const int rc = launch_subpix(ctx->stream, A.img, w, h, stride, ps == 0 ? A.out : A.out2, out_cap, 3, 30, 0.01,
                                              ps == 0 ? &it[0].n1 : &it[0].n2, n, img_item_stride, out_cap, (int)(sizeof(GfttItem) / sizeof(int)));
                 if (rc) return rc;
             }

@@ -112,16 +112,28 @@ def test_every_geometry_and_select_instance_is_reached():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_strip_kernel_static_lds_is_what_the_geometries_assume(tmp_path):
     """a device-only compile of detect.hip for gfx950: k_mineig_strip's static LDS is DC.STRIP_STATIC_LDS, with which cell 63 still fits
-    7 cells on 8 wavefronts and cell 64 does not"""
-    src = os.path.join(ROOT, "ov2slam_amd", "csrc", "detect.hip")
+    7 cells on 8 wavefronts and cell 64 does not; and each of the twelve k_grid_select instances stays within the static LDS that
+    detect_plan.hpp's det_select_lds leaves free for it (the bound is printed from the header by a g++ program, not restated here)"""
+    csrc = os.path.join(ROOT, "ov2slam_amd", "csrc")
+    src = os.path.join(csrc, "detect.hip")
     out = str(tmp_path / "detect.s")
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "--cuda-device-only", "-S", src, "-o", out],
                    check=True, capture_output=True)
-    blocks = re.findall(r"\.amdhsa_kernel (\S*k_mineig_strip\S*)(.*?)\.end_amdhsa_kernel", open(out).read(), re.S)
+    kernels = re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", open(out).read(), re.S)
+    fixed = {name: int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1)) for name, body in kernels}
+    blocks = [name for name in fixed if "k_mineig_strip" in name]
     assert len(blocks) == 1
-    static = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", blocks[0][1]).group(1))
+    static = fixed[blocks[0]]
     assert static == DC.STRIP_STATIC_LDS
     assert DC.strip_lds(63, 8) + static <= 160 * 1024 < DC.strip_lds(64, 8) + static
+    (tmp_path / "bound.cpp").write_text('#include <cstdio>\n#include "detect_plan.hpp"\nint main() { printf("%d\\n", DET_SELECT_STATIC_LDS); return 0; }\n')
+    subprocess.check_call(["g++", "-std=c++17", "-I", csrc, str(tmp_path / "bound.cpp"), "-o", str(tmp_path / "bound")])
+    bound = int(subprocess.run([str(tmp_path / "bound")], capture_output=True, text=True, check=True).stdout)
+    select = {name: b for name, b in fixed.items() if "k_grid_select" in name}
+    # <MODE, MAXROW, CHUNKS, NT> as the mangled name spells it: ILi0ELi36ELi1ELi1024EE
+    inst = {tuple(int(v) for v in re.search(r"k_grid_selectILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EE", name).groups()) for name in select}
+    assert inst == {DC.select_instance(m, c, i) for m in (0, 1) for c in DC.CELLS for i in (1, 64)} and len(select) == 12
+    assert all(0 < b <= bound for b in select.values()), (select, bound)
 
 
 @pytest.mark.parametrize("cell", DC.BORDER_CELLS)
