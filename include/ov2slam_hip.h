@@ -1352,6 +1352,117 @@ int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items
 int ov2_p3p_draw_samples(unsigned long long seed, int n, int rows, int *out);
 
 /* ==================================================================== */
+/* Per-frame pose (f15): MultiViewGeometry::ceresPnP in one launch      */
+/* (src/multi_view_geometry.cpp:492-586) and VisualFrontEnd::computePose */
+/* as one device-resident chain (src/visual_front_end.cpp:659-851)      */
+/* ==================================================================== */
+/* ov2_ceres_pnp[_batch]: the WHOLE two-pass protocol of ceresPnP in one kernel (csrc/pnp.hip, k_pnp_solve: one work-group per
+ * problem, blockIdx.x = item; fp64), one upload, one launch, one download, one synchronisation per call:
+ *   pass 1    Huber(sqrt(chi2th)) unless !use_robust, nmaxiter iterations, function_tolerance 1e-3, every other solver setting as
+ *             ov2_ba_default_options gives it (Jacobi scaling, the LM diagonal bounds, radius 1e4 ...)
+ *   outliers  block i is bad when chi2_i > chi2th or its depth is not positive, on the values of the LAST Evaluate of pass 1 (the
+ *             candidate evaluation overwrites them whether or not the step is accepted), ascending
+ *   all bad   (or n == 0) success = 0 with the pose of pass 1, no pass 2
+ *   pass 2    only if apply_l2_after_robust and some block is bad: a fresh solve with the trivial loss over the remaining blocks,
+ *             from the pose of pass 1
+ *   success   Summary::IsSolutionUsable of the last solve that ran (termination OV2_TERM_NO_CONVERGENCE .. OV2_TERM_MIN_RADIUS)
+ * The outlier list is that of the first test only.  The reference's max_solver_time_in_seconds = 0.005 has no counterpart: the
+ * result never depends on machine load.  Every sum over the blocks (J^T J, J^T r, the cost) is formed in a fixed order, so a problem
+ * gives the same bits from run to run, as item b of any batch, and inside ov2_compute_pose as here.  The trust-region rules are
+ * those of ov2_ba_solve's pose-only kernel (csrc/ba_core.hpp); that kernel and the route through ov2_ba_solve are unchanged.
+ *
+ * ov2_compute_pose[_batch]: per item ONE upload, the three launches of ov2_p3p_ransac_batch, a gather launch, the k_pnp_solve launch,
+ * a decision launch, ONE download, ONE synchronisation:
+ *   1  n < 4: action OV2_POSE_TOO_FEW; Twc_out = Twc, p3p_req_out = p3p_req, nothing removed, nothing else ran (:667).
+ *   2  do_p3p (the caller's bp3preq_ || dop3p_): the search of ov2_p3p_ransac_batch on bv / wpt / samples with params->p3p.  Status != 0,
+ *      fewer than 5 inliers or a non-finite translation: action OV2_POSE_P3P_RESET, Twc_out = Twc, p3p_req_out = p3p_req (:750-761).
+ *   3  otherwise P3P's outliers leave unpx / wpt / scale, the order of the rest kept (:769-778); P3P's pose (Rwc as the unit
+ *      quaternion of ov2_pose_from_model) becomes the frame pose AND the start of PnP (:766).
+ *   4  ceresPnP as above on the m remaining blocks.
+ *   5  rejected when !success, or m - n_out < 5, or (double)n_out > 0.5 * (double)m, or the translation is not finite (:809-813):
+ *        without P3P             OV2_POSE_PNP_REQ_P3P, p3p_req_out = 1, Twc_out = Twc
+ *        with P3P and mono       OV2_POSE_PNP_RESET   } p3p_req_out = p3p_req, Twc_out = P3P's pose, P3P's removals stand,
+ *        with P3P and stereo     OV2_POSE_PNP_KEEP    } PnP's do not
+ *      accepted: OV2_POSE_OK, Twc_out = PnP's pose, p3p_req_out = 0, PnP's outliers are removed as well.
+ *   removed[i], i in the caller's index space: 0 kept, 1 removed after P3P, 2 removed after an accepted PnP.
+ * The chain gives, bit for bit, what ov2_p3p_ransac followed by ov2_ceres_pnp on the host-compacted arrays gives.
+ *
+ * Capacity: OV2_P3P_MAX_POINTS points and OV2_P3P_MAX_ROWS rows per item, 65535 items per call.  Items of a batch share params;
+ * sizes may differ, empty items are allowed; the single forms are the batch forms with one item.  OV2_EINVAL: a NULL params /
+ * problem / result / ctx, a NULL array with a non-zero count (bv and samples only where do_p3p), a negative count, a non-finite
+ * input value, |scale| > 60, chi2th <= 0 or not finite, nmaxiter < 0, K not finite or fx / fy == 0, whatever ov2_p3p_ransac_batch
+ * refuses in params->p3p, anything beyond the capacity.  All of it is checked on the host, the inputs before the context; a
+ * rejected call leaves its outputs untouched. */
+enum { OV2_POSE_TOO_FEW = 0, OV2_POSE_OK = 1, OV2_POSE_PNP_REQ_P3P = 2, OV2_POSE_P3P_RESET = 3, OV2_POSE_PNP_RESET = 4, OV2_POSE_PNP_KEEP = 5 };
+typedef struct {
+    int nmaxiter;                /* 5 in computePose                                                                         */
+    double chi2th;               /* robust_mono_th (5.9915)                                                                  */
+    int use_robust;              /* buse_robust                                                                              */
+    int apply_l2_after_robust;   /* bapply_l2_after_robust                                                                   */
+    double K[4];                 /* fx fy cx cy of the left camera                                                           */
+} ov2_pnp_params;
+typedef struct {
+    int n;                       /* residual blocks                                                                          */
+    const double *unpx;          /* 2 n: undistorted pixels                                                                  */
+    const double *wpt;           /* 3 n: world points                                                                        */
+    const int *scale;            /* n: pyramid level of the keypoint, sigma = 2^scale                                        */
+    const double *Twc;           /* 7: [t q(xyzw)], the start                                                                */
+} ov2_pnp_problem;
+typedef struct {
+    int ran;                     /* 0: the pass did not run (the other fields are 0 then)                                    */
+    int iterations;              /* as ov2_ba_result                                                                         */
+    int num_successful_steps;
+    int termination;             /* OV2_TERM_*                                                                               */
+    double initial_cost, final_cost;
+} ov2_pnp_pass;
+typedef struct {
+    int success;
+    int n_outliers;
+    double Twc[7];
+    int *outliers;               /* n slots; the first n_outliers are written, ascending                                     */
+    ov2_pnp_pass pass[2];
+} ov2_pnp_result;
+int ov2_ceres_pnp(ov2_ctx *ctx, const ov2_pnp_params *params, const ov2_pnp_problem *problem, ov2_pnp_result *result);
+int ov2_ceres_pnp_batch(ov2_ctx *ctx, const ov2_pnp_params *params, int n_items, const ov2_pnp_problem *problems,
+                        ov2_pnp_result *results);
+
+typedef struct {
+    ov2_pnp_params pnp;
+    ov2_p3p_params p3p;          /* the front end searches with OV2_P3P_LMEDS                                                */
+    int mono;                    /* pslamstate_->mono_                                                                       */
+} ov2_pose_params;
+typedef struct {
+    int n;                       /* 3-D keypoints of the frame (the packed arrays of :675-712)                               */
+    const double *unpx;          /* 2 n                                                                                      */
+    const double *wpt;           /* 3 n                                                                                      */
+    const int *scale;            /* n                                                                                        */
+    const double *Twc;           /* 7: the frame's pose                                                                      */
+    const double *bv;            /* 3 n unit bearings; read only where do_p3p                                                */
+    int do_p3p;                  /* bp3preq_ || dop3p_                                                                       */
+    int p3p_req;                 /* bp3preq_                                                                                 */
+    int n_rows;                  /* rows of the sample table; read only where do_p3p                                         */
+    const int *samples;          /* 4 n_rows                                                                                 */
+} ov2_pose_problem;
+typedef struct {
+    double Twc[7];
+    int action;                  /* OV2_POSE_*                                                                               */
+    int p3p_req_out;             /* the next frame's bp3preq_                                                                */
+    int n_removed_p3p, n_outliers_pnp;   /* P3P's outliers (0 unless P3P succeeded); PnP's first-test outliers, accepted or not */
+    int ran_p3p;                 /* the search ran for this item (do_p3p and n >= 4); pass[q].ran says the same of the PnP passes */
+    int p3p_status, p3p_best_row, p3p_iterations, p3p_rows_consumed;   /* as ov2_p3p_result; 0 / -1 / 0 / 0 when it did not run */
+    double p3p_score;
+    uint8_t *removed;            /* n bytes                                                                                  */
+    ov2_pnp_pass pass[2];
+} ov2_pose_result;
+int ov2_compute_pose(ov2_ctx *ctx, const ov2_pose_params *params, const ov2_pose_problem *problem, ov2_pose_result *result);
+int ov2_compute_pose_batch(ov2_ctx *ctx, const ov2_pose_params *params, int n_items, const ov2_pose_problem *problems,
+                           ov2_pose_result *results);
+/* Host only: the pose [t q(xyzw)] of a P3P model (Rwc row-major, twc), with the very arithmetic the chain uses on the device
+ * (Eigen's matrix-to-quaternion branches, then a normalisation), so that a caller who runs ov2_p3p_ransac and ov2_ceres_pnp
+ * directly starts PnP from the same bits.  OV2_EINVAL: a NULL pointer. */
+int ov2_pose_from_model(const double *model12, double *Twc7);
+
+/* ==================================================================== */
 /* Relative pose from 2D-2D matches (MultiViewGeometry::                */
 /* compute5ptEssentialMatrix, src/multi_view_geometry.cpp:594-696,      */
 /* USE_OPENGV)                                                          */

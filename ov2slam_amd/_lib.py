@@ -47,6 +47,7 @@ OV2_KF_RET_FEW_CELLS, OV2_KF_RET_FEW_3D, OV2_KF_RET_MANY_3D, OV2_KF_RET_TIME, OV
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
+OV2_POSE_TOO_FEW, OV2_POSE_OK, OV2_POSE_PNP_REQ_P3P, OV2_POSE_P3P_RESET, OV2_POSE_PNP_RESET, OV2_POSE_PNP_KEEP = 0, 1, 2, 3, 4, 5
 OV2_EPI_TOO_FEW_POINTS, OV2_EPI_NO_MODEL, OV2_EPI_FEW_INLIERS = 1, 2, 4
 OV2_EPI_MAX_POINTS, OV2_EPI_MAX_ROWS = 2048, 4096
 OV2_PG_MAX_POSES, OV2_PG_MAX_EDGES = 16384, 32768
@@ -270,6 +271,50 @@ class P3PResult(C.Structure):
     _fields_ = [("model", C.c_double * 12), ("score", C.c_double), ("best_row", C.c_int), ("iterations", C.c_int),
                 ("rows_consumed", C.c_int), ("status", C.c_int), ("n_inliers", C.c_int), ("n_outliers", C.c_int),
                 ("outliers", C.POINTER(C.c_int)), ("trace_valid", C.POINTER(C.c_uint8)), ("trace_score", C.POINTER(C.c_double))]
+
+
+class PnPParams(C.Structure):
+    """ov2_pnp_params"""
+    _fields_ = [("nmaxiter", C.c_int), ("chi2th", C.c_double), ("use_robust", C.c_int), ("apply_l2_after_robust", C.c_int),
+                ("K", C.c_double * 4)]
+
+
+class PnPProblem(C.Structure):
+    """ov2_pnp_problem"""
+    _fields_ = [("n", C.c_int), ("unpx", C.POINTER(C.c_double)), ("wpt", C.POINTER(C.c_double)), ("scale", C.POINTER(C.c_int)),
+                ("Twc", C.POINTER(C.c_double))]
+
+
+class PnPPass(C.Structure):
+    """ov2_pnp_pass"""
+    _fields_ = [("ran", C.c_int), ("iterations", C.c_int), ("num_successful_steps", C.c_int), ("termination", C.c_int),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+
+class PnPResult(C.Structure):
+    """ov2_pnp_result"""
+    _fields_ = [("success", C.c_int), ("n_outliers", C.c_int), ("Twc", C.c_double * 7), ("outliers", C.POINTER(C.c_int)),
+                ("passes", PnPPass * 2)]
+
+
+class PoseParams(C.Structure):
+    """ov2_pose_params"""
+    _fields_ = [("pnp", PnPParams), ("p3p", P3PParams), ("mono", C.c_int)]
+
+
+class PoseProblem(C.Structure):
+    """ov2_pose_problem"""
+    _fields_ = [("n", C.c_int), ("unpx", C.POINTER(C.c_double)), ("wpt", C.POINTER(C.c_double)), ("scale", C.POINTER(C.c_int)),
+                ("Twc", C.POINTER(C.c_double)), ("bv", C.POINTER(C.c_double)), ("do_p3p", C.c_int), ("p3p_req", C.c_int),
+                ("n_rows", C.c_int), ("samples", C.POINTER(C.c_int))]
+
+
+class PoseResult(C.Structure):
+    """ov2_pose_result"""
+    _fields_ = [("Twc", C.c_double * 7), ("action", C.c_int), ("p3p_req_out", C.c_int), ("n_removed_p3p", C.c_int),
+                ("n_outliers_pnp", C.c_int), ("ran_p3p", C.c_int), ("p3p_status", C.c_int), ("p3p_best_row", C.c_int),
+                ("p3p_iterations", C.c_int), ("p3p_rows_consumed", C.c_int), ("p3p_score", C.c_double),
+                ("removed", C.POINTER(C.c_uint8)), ("passes", PnPPass * 2)]
 
 
 class EpipolarParams(C.Structure):
@@ -507,6 +552,11 @@ SIGNATURES = {
     "ov2_p3p_ransac": (_i, [_vp, C.POINTER(P3PParams), C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_ransac_batch": (_i, [_vp, C.POINTER(P3PParams), _i, C.POINTER(P3PProblem), C.POINTER(P3PResult)]),
     "ov2_p3p_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),
+    "ov2_ceres_pnp": (_i, [_vp, C.POINTER(PnPParams), C.POINTER(PnPProblem), C.POINTER(PnPResult)]),
+    "ov2_ceres_pnp_batch": (_i, [_vp, C.POINTER(PnPParams), _i, C.POINTER(PnPProblem), C.POINTER(PnPResult)]),
+    "ov2_compute_pose": (_i, [_vp, C.POINTER(PoseParams), C.POINTER(PoseProblem), C.POINTER(PoseResult)]),
+    "ov2_compute_pose_batch": (_i, [_vp, C.POINTER(PoseParams), _i, C.POINTER(PoseProblem), C.POINTER(PoseResult)]),
+    "ov2_pose_from_model": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ov2_epipolar_ransac": (_i, [_vp, C.POINTER(EpipolarParams), C.POINTER(EpipolarProblem), C.POINTER(EpipolarResult)]),
     "ov2_epipolar_ransac_batch": (_i, [_vp, C.POINTER(EpipolarParams), _i, C.POINTER(EpipolarProblem), C.POINTER(EpipolarResult)]),
     "ov2_epipolar_draw_samples": (_i, [C.c_ulonglong, _i, _i, C.POINTER(_i)]),

@@ -16,6 +16,7 @@
 // No atomics, no result that depends on scheduling.  Every pointer and size is validated on the host before any device work; the
 // kernels check every sample index against the problem's point count before they read through it.
 #include "common.hpp"
+#include "p3p_dev.hpp"                 // P3Item, P3Out and the host steps (plan, stage, enqueue) that pnp.hip chains as well
 #include <cmath>
 #include <cfloat>
 
@@ -48,10 +49,6 @@ __device__ __forceinline__ double p3_dist(const P3Model &m, P3V bv, P3V X)
     const double d = 1.0 - p3_dot(bv, v);
     return d > 0.0 ? d : 0.0;
 }
-
-struct P3Item { int n, S, pt0, row0; };
-struct P3Out { double model[12]; double score; int best_row, iterations, rows_consumed, status, n_inliers, n_outliers; };
-static_assert(sizeof(P3Out) == 128, "P3Out layout");
 
 struct P3Args {
     const P3Item *items; const double *bv; const double *X; const int4 *samples;
@@ -467,12 +464,11 @@ int ov2_p3p_draw_samples(unsigned long long seed, int n, int rows, int *out)
     return OV2_OK;
 }
 
-int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems, ov2_p3p_result *results)
+int p3p_plan(const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems, const ov2_p3p_result *results, P3Plan *plan)
 {
-    // the inputs first, the context last: a malformed input is reported without a device
     OV2_REQUIRE(params, OV2_EINVAL, "NULL params");
     OV2_REQUIRE(n_items >= 0, OV2_EINVAL, "n_items < 0");
-    OV2_REQUIRE(n_items == 0 || (problems && results), OV2_EINVAL, "NULL problem / result array");
+    OV2_REQUIRE(n_items == 0 || problems, OV2_EINVAL, "NULL problem / result array");
     OV2_REQUIRE(n_items <= 65535, OV2_EINVAL, "more than 65535 problems in one call");
     OV2_REQUIRE(params->mode == OV2_P3P_LMEDS || params->mode == OV2_P3P_RANSAC, OV2_EINVAL, "mode is neither OV2_P3P_LMEDS nor OV2_P3P_RANSAC");
     OV2_REQUIRE(!params->boptimize, OV2_EINVAL, "boptimize is not provided: refine the pose with ov2_ba_solve (ov2::ceresPnP) afterwards");
@@ -484,76 +480,103 @@ int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items
     bool trace = false;
     for (int b = 0; b < n_items; b++) {
         const ov2_p3p_problem &p = problems[b];
-        const ov2_p3p_result &r = results[b];
         OV2_REQUIRE(p.n >= 0 && p.n_rows >= 0, OV2_EINVAL, "negative count (n / n_rows)");
         OV2_REQUIRE(p.n <= P3_MAX_POINTS, OV2_EINVAL, "capacity: more than 2048 points in one problem");
         OV2_REQUIRE(p.n_rows <= P3_MAX_ROWS, OV2_EINVAL, "capacity: more than 4096 sample rows in one problem");
         OV2_REQUIRE(p.n == 0 || (p.bv && p.X), OV2_EINVAL, "NULL bv / X");
         OV2_REQUIRE(p.n_rows == 0 || p.samples, OV2_EINVAL, "NULL samples");
-        OV2_REQUIRE(p.n == 0 || r.outliers, OV2_EINVAL, "NULL result buffer (outliers)");
+        if (results) {
+            const ov2_p3p_result &r = results[b];
+            OV2_REQUIRE(p.n == 0 || r.outliers, OV2_EINVAL, "NULL result buffer (outliers)");
+            trace = trace || r.trace_valid || r.trace_score;
+        }
         for (size_t i = 0; i < 3 * (size_t)p.n; i++)
             OV2_REQUIRE(std::isfinite(p.bv[i]) && std::isfinite(p.X[i]), OV2_EINVAL, "bv / X not finite");
-        trace = trace || r.trace_valid || r.trace_score;
         NP += (size_t)p.n; NR += (size_t)p.n_rows;
         n_max = p.n > n_max ? p.n : n_max; s_max = p.n_rows > s_max ? p.n_rows : s_max;
     }
     OV2_REQUIRE(NP <= 0x7fffffff && NR <= 0x7fffffff, OV2_EINVAL, "capacity: more than 2^31 - 1 points or rows in one call");
+    P3Plan &pl = *plan;
+    const size_t B = (size_t)n_items;
+    pl.B = B; pl.NP = NP; pl.NR = NR; pl.n_max = n_max; pl.s_max = s_max; pl.trace = trace;
+    pl.o_it = 0; pl.o_bv = p3_al(pl.o_it + sizeof(P3Item) * B); pl.o_X = p3_al(pl.o_bv + 24 * NP); pl.o_sm = p3_al(pl.o_X + 24 * NP);
+    pl.o_out = p3_al(pl.o_sm + 16 * NR); pl.o_ol = p3_al(pl.o_out + sizeof(P3Out) * B); pl.o_va = p3_al(pl.o_ol + 4 * NP);
+    pl.o_sc = p3_al(pl.o_va + NR); pl.o_md = p3_al(pl.o_sc + 8 * NR); pl.total = p3_al(pl.o_md + 96 * NR);
+    return OV2_OK;
+}
+
+void p3p_stage(const P3Plan &pl, const ov2_p3p_problem *problems, uint8_t *hs)
+{
+    size_t pt0 = 0, row0 = 0;
+    for (size_t b = 0; b < pl.B; b++) {
+        const ov2_p3p_problem &p = problems[b];
+        const P3Item it{p.n, p.n_rows, (int)pt0, (int)row0};
+        memcpy(hs + pl.o_it + sizeof(P3Item) * b, &it, sizeof(P3Item));
+        if (p.n) {
+            memcpy(hs + pl.o_bv + 24 * pt0, p.bv, 24 * (size_t)p.n);
+            memcpy(hs + pl.o_X + 24 * pt0, p.X, 24 * (size_t)p.n);
+        }
+        if (p.n_rows) memcpy(hs + pl.o_sm + 16 * row0, p.samples, 16 * (size_t)p.n_rows);
+        pt0 += (size_t)p.n; row0 += (size_t)p.n_rows;
+    }
+}
+
+int p3p_enqueue(hipStream_t s, const ov2_p3p_params *params, const P3Plan &pl, uint8_t *ds)
+{
+    const int n_items = (int)pl.B;
+    P3Args a;
+    a.items = (const P3Item *)(ds + pl.o_it); a.bv = (const double *)(ds + pl.o_bv); a.X = (const double *)(ds + pl.o_X);
+    a.samples = (const int4 *)(ds + pl.o_sm); a.models = (double *)(ds + pl.o_md); a.valid = ds + pl.o_va; a.score = (double *)(ds + pl.o_sc);
+    a.out = (P3Out *)(ds + pl.o_out); a.outliers = (int *)(ds + pl.o_ol);
+    a.mode = params->mode; a.max_iterations = params->max_iterations; a.threshold = params->threshold; a.probability = params->probability;
+    if (pl.s_max > 0) {
+        hipLaunchKernelGGL(k_p3p_solve, dim3((pl.s_max + 63) / 64, n_items), dim3(64), 0, s, a);
+        OV2_HIP_CHECK(hipGetLastError());
+        const size_t lds = (a.mode == OV2_P3P_LMEDS && pl.n_max > P3_REG * 64) ? 8 * 64 * (size_t)((pl.n_max + 63) / 64) : 0;
+        hipLaunchKernelGGL(k_p3p_score, dim3(pl.s_max, n_items), dim3(64), lds, s, a);
+        OV2_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_p3p_pick, dim3(n_items), dim3(64), 0, s, a);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
+int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems, ov2_p3p_result *results)
+{
+    // the inputs first, the context last: a malformed input is reported without a device
+    OV2_REQUIRE(params, OV2_EINVAL, "NULL params");
+    OV2_REQUIRE(n_items >= 0, OV2_EINVAL, "n_items < 0");
+    OV2_REQUIRE(n_items == 0 || (problems && results), OV2_EINVAL, "NULL problem / result array");
+    P3Plan pl;
+    int rc = p3p_plan(params, n_items, problems, results, &pl);
+    if (rc) return rc;
     OV2_REQUIRE(ctx, OV2_EINVAL, "NULL context");
     if (n_items == 0) return OV2_OK;
 
-    // staging: [items 16 B][bv 24][X 24][samples 16] up, [out 128][outliers 4][valid 1][score 8] down (the last two only for a
-    // trace), [models 96] device only; every section 16-byte aligned
-    const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_bv = p3_al(o_it + sizeof(P3Item) * B), o_X = p3_al(o_bv + 24 * NP), o_sm = p3_al(o_X + 24 * NP);
-    const size_t o_out = p3_al(o_sm + 16 * NR), o_ol = p3_al(o_out + sizeof(P3Out) * B), o_va = p3_al(o_ol + 4 * NP);
-    const size_t o_sc = p3_al(o_va + NR), o_md = p3_al(o_sc + 8 * NR), total = p3_al(o_md + 96 * NR);
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(o_md);         if (rc) return rc;
+    rc = ctx->reserve_device(pl.total);  if (rc) return rc;
+    rc = ctx->reserve_host(pl.o_md);     if (rc) return rc;
     uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
-    size_t pt0 = 0, row0 = 0;
-    for (int b = 0; b < n_items; b++) {
-        const ov2_p3p_problem &p = problems[b];
-        const P3Item it{p.n, p.n_rows, (int)pt0, (int)row0};
-        memcpy(hs + o_it + sizeof(P3Item) * b, &it, sizeof(P3Item));
-        if (p.n) {
-            memcpy(hs + o_bv + 24 * pt0, p.bv, 24 * (size_t)p.n);
-            memcpy(hs + o_X + 24 * pt0, p.X, 24 * (size_t)p.n);
-        }
-        if (p.n_rows) memcpy(hs + o_sm + 16 * row0, p.samples, 16 * (size_t)p.n_rows);
-        pt0 += (size_t)p.n; row0 += (size_t)p.n_rows;
-    }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
-    P3Args a;
-    a.items = (const P3Item *)(ds + o_it); a.bv = (const double *)(ds + o_bv); a.X = (const double *)(ds + o_X);
-    a.samples = (const int4 *)(ds + o_sm); a.models = (double *)(ds + o_md); a.valid = ds + o_va; a.score = (double *)(ds + o_sc);
-    a.out = (P3Out *)(ds + o_out); a.outliers = (int *)(ds + o_ol);
-    a.mode = params->mode; a.max_iterations = params->max_iterations; a.threshold = params->threshold; a.probability = params->probability;
-    if (s_max > 0) {
-        hipLaunchKernelGGL(k_p3p_solve, dim3((s_max + 63) / 64, n_items), dim3(64), 0, ctx->stream, a);
-        OV2_HIP_CHECK(hipGetLastError());
-        const size_t lds = (a.mode == OV2_P3P_LMEDS && n_max > P3_REG * 64) ? 8 * 64 * (size_t)((n_max + 63) / 64) : 0;
-        hipLaunchKernelGGL(k_p3p_score, dim3(s_max, n_items), dim3(64), lds, ctx->stream, a);
-        OV2_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_p3p_pick, dim3(n_items), dim3(64), 0, ctx->stream, a);
-    OV2_HIP_CHECK(hipGetLastError());
-    const size_t down_end = (trace && NR > 0) ? o_md : o_va;
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, down_end - o_out, hipMemcpyDeviceToHost, ctx->stream));
+    p3p_stage(pl, problems, hs);
+    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, pl.o_out, hipMemcpyHostToDevice, ctx->stream));
+    rc = p3p_enqueue(ctx->stream, params, pl, ds);
+    if (rc) return rc;
+    const size_t down_end = (pl.trace && pl.NR > 0) ? pl.o_md : pl.o_va;
+    OV2_HIP_CHECK(hipMemcpyAsync(hs + pl.o_out, ds + pl.o_out, down_end - pl.o_out, hipMemcpyDeviceToHost, ctx->stream));
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    pt0 = row0 = 0;
+    size_t pt0 = 0, row0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_p3p_problem &p = problems[b];
         ov2_p3p_result &r = results[b];
         P3Out o;
-        memcpy(&o, hs + o_out + sizeof(P3Out) * b, sizeof(P3Out));
+        memcpy(&o, hs + pl.o_out + sizeof(P3Out) * b, sizeof(P3Out));
         memcpy(r.model, o.model, sizeof(o.model));
         r.score = o.score; r.best_row = o.best_row; r.iterations = o.iterations; r.rows_consumed = o.rows_consumed;
         r.status = o.status; r.n_inliers = o.n_inliers; r.n_outliers = o.n_outliers;
-        if (o.n_outliers > 0) memcpy(r.outliers, hs + o_ol + 4 * pt0, 4 * (size_t)o.n_outliers);
+        if (o.n_outliers > 0) memcpy(r.outliers, hs + pl.o_ol + 4 * pt0, 4 * (size_t)o.n_outliers);
         if (p.n_rows) {
-            if (r.trace_valid) memcpy(r.trace_valid, hs + o_va + row0, (size_t)p.n_rows);
-            if (r.trace_score) memcpy(r.trace_score, hs + o_sc + 8 * row0, 8 * (size_t)p.n_rows);
+            if (r.trace_valid) memcpy(r.trace_valid, hs + pl.o_va + row0, (size_t)p.n_rows);
+            if (r.trace_score) memcpy(r.trace_score, hs + pl.o_sc + 8 * row0, 8 * (size_t)p.n_rows);
         }
         pt0 += (size_t)p.n; row0 += (size_t)p.n_rows;
     }

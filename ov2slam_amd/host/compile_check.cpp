@@ -10,6 +10,8 @@
 #include "loop_closer.hpp"
 // the adapters that are free functions: taking their addresses keeps their signatures checked
 static auto *const check_ceres_pnp = &ov2::ceresPnP;
+static auto *const check_ceres_pnp_fused = &ov2::ceresPnPFused;
+static int (*const check_compute_pose)(ov2::Context &, const ov2::ComputePoseParams &, const ov2::ComputePoseInput &, ov2::ComputePoseOutput &) = &ov2::computePose;
 static auto *const check_p3p_ransac = &ov2::p3pRansac;
 static auto *const check_5pt = &ov2::compute5ptEssentialMatrix;
 // the rectification adapters (CameraCalibration, FrameTracker), by address too

@@ -83,6 +83,37 @@ inline bool ceresPnP(Context &ctx, const double *vunkps, const double *vwpts, co
     return termination != OV2_TERM_FAILURE;                                                    // Summary::IsSolutionUsable (:574)
 }
 
+// ceresPnP's whole protocol in ONE launch (ov2_ceres_pnp, csrc/pnp.hip): one upload, one kernel, one download, one synchronisation
+// instead of the two blocking solves above, and sums formed in a fixed order (the same bits in every run).  Arguments as ceresPnP;
+// Twc is written whenever the library ran, also on a false return (the pose of pass 1 when every observation is bad).  There is
+// no time limit.  ceresPnP above keeps its route through ov2_ba_solve.
+inline bool ceresPnPFused(Context &ctx, const double *vunkps, const double *vwpts, const int *vscales, size_t n, double Twc[7], int nmaxiter,
+                          float chi2th, bool buse_robust, bool bapply_l2_after_robust, float fx, float fy, float cx, float cy,
+                          std::vector<int> &voutliersidx, bool *library_ok = nullptr, std::string *error = nullptr,
+                          ov2_pnp_result *summary = nullptr)
+{
+    if (library_ok) *library_ok = true;
+    if (n == 0) return false;
+    const std::vector<int> zeros(vscales ? 0 : n, 0);
+    std::vector<int> outliers(n);
+    ov2_pnp_params P{};
+    P.nmaxiter = nmaxiter; P.chi2th = (double)chi2th; P.use_robust = buse_robust ? 1 : 0; P.apply_l2_after_robust = bapply_l2_after_robust ? 1 : 0;
+    P.K[0] = fx; P.K[1] = fy; P.K[2] = cx; P.K[3] = cy;
+    ov2_pnp_problem pb{};
+    pb.n = (int)n; pb.unpx = vunkps; pb.wpt = vwpts; pb.scale = vscales ? vscales : zeros.data(); pb.Twc = Twc;
+    ov2_pnp_result r{};
+    r.outliers = outliers.data();
+    if (n > 0x7fffffffu || ov2_ceres_pnp(ctx.get(), &P, &pb, &r) != OV2_OK) {
+        if (library_ok) *library_ok = false;
+        if (error) *error = ov2_last_error();
+        return false;
+    }
+    voutliersidx.insert(voutliersidx.end(), outliers.begin(), outliers.begin() + r.n_outliers);
+    for (int i = 0; i < 7; i++) Twc[i] = r.Twc[i];
+    if (summary) { *summary = r; summary->outliers = nullptr; }
+    return r.success != 0;
+}
+
 // bvs / vwpts: n x 3 unit bearing vectors (camera frame) and world points.  Twc: [tx ty tz qx qy qz qw], written only when the
 // function returns true (translation = the model's last column, rotation through Sophus::SE3d::setRotationMatrix: Eigen's
 // Quaterniond(R), normalised).  voutliersidx receives every index that is not an inlier, ascending, only when the function returns

@@ -4,6 +4,7 @@
 // retry of lost prior tracks and the bp3preq_ rule are reproduced by the library (include/ov2slam_hip.h).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include "ov2_types.hpp"
 
 namespace ov2 {
@@ -353,6 +354,98 @@ inline int kltPriors(Context &ctx, const ProjectionCamera &cam, bool klt_use_pri
     const ov2_klt_priors_params p = detail::kltPriorsParams(cam, klt_use_prior);
     const int rc = ov2_klt_priors_batch(ctx.get(), &p, (int)B, items.data(), rs.data());
     for (size_t b = 0; b < B; b++) { vpriors[b].resize(fs[b].px.size()); vhasprior[b].resize(fs[b].px.size()); }
+    return rc;
+}
+
+// ---- computePose (:659-851) on ov2_compute_pose: P3P -> removal of its outliers -> ceresPnP -> the acceptance test as ONE
+// device-resident chain with one synchronisation.  The caller hands over the packed arrays the reference builds at :675-712, in
+// the iteration order of pcurframe_->mapkps_ over the 3-D keypoints with a live map point, and acts on the result:
+//   OV2_POSE_TOO_FEW       return (:667)
+//   OV2_POSE_P3P_RESET     resetFrame() (:758)
+//   OV2_POSE_OK            setTwc(Twc), bp3preq_ = p3p_req_out (false), removeObsFromCurFrameById(lmid[i]) where removed[i] != 0
+//   OV2_POSE_PNP_REQ_P3P   bp3preq_ = p3p_req_out (true) (:817)
+//   OV2_POSE_PNP_RESET     setTwc(Twc) (P3P's, :766), remove where removed[i] == 1, then resetFrame() (:824)
+//   OV2_POSE_PNP_KEEP      setTwc(Twc) (P3P's), remove where removed[i] == 1
+struct ComputePoseInput {
+    std::vector<double> unpx;                                 // 2 per keypoint: Keypoint::unpx_
+    std::vector<double> wpt;                                  // 3 per keypoint: MapPoint::getPoint()
+    std::vector<int> scale;                                   // Keypoint::scale_
+    std::vector<double> bv;                                   // 3 per keypoint: Keypoint::bv_ (read only where do_p3p)
+    double Twc[7] = {0, 0, 0, 0, 0, 0, 1};                    // pcurframe_->getTwc()
+    bool p3p_req = false;                                     // bp3preq_
+    bool do_p3p = false;                                      // bp3preq_ || pslamstate_->dop3p_
+    unsigned long long seed = 0;                              // the sample table is drawn from it (see ov2::p3pRansac)
+};
+struct ComputePoseParams {
+    int nransac_iter = 100; float fransac_err = 3.f;          // pslamstate_->nransac_iter_, fransac_err_
+    float robust_mono_th = 5.9915f;
+    bool apply_l2_after_robust = true, mono = false;
+    float fx = 0, fy = 0, cx = 0, cy = 0;
+};
+struct ComputePoseOutput { ov2_pose_result r; std::vector<uint8_t> removed; };
+
+namespace detail {
+inline ov2_pose_params poseParams(const ComputePoseParams &c)
+{
+    ov2_pose_params p{};
+    p.pnp.nmaxiter = 5; p.pnp.chi2th = (double)c.robust_mono_th; p.pnp.use_robust = 1; p.pnp.apply_l2_after_robust = c.apply_l2_after_robust ? 1 : 0;
+    p.pnp.K[0] = c.fx; p.pnp.K[1] = c.fy; p.pnp.K[2] = c.cx; p.pnp.K[3] = c.cy;
+    float focal = c.fx + c.fy;                                // multi_view_geometry.cpp:209-213, as ov2::p3pRansac
+    focal /= 2.;
+    p.p3p.mode = OV2_P3P_LMEDS; p.p3p.max_iterations = c.nransac_iter;
+    p.p3p.threshold = 1.0 - std::cos(std::atan((double)(c.fransac_err / focal)));
+    p.p3p.probability = 0.99; p.p3p.boptimize = 0;
+    p.mono = c.mono ? 1 : 0;
+    return p;
+}
+// false when the arrays differ in length; the sample table of a searching frame is drawn into `samples`
+inline bool packPose(const ComputePoseInput &f, int nransac_iter, std::vector<int> &samples, ComputePoseOutput &out, ov2_pose_problem &it)
+{
+    const size_t n = f.scale.size();
+    if (f.unpx.size() != 2 * n || f.wpt.size() != 3 * n || (f.do_p3p && f.bv.size() != 3 * n) || n > 0x7fffffffu) return false;
+    it = ov2_pose_problem{};
+    it.n = (int)n; it.unpx = f.unpx.data(); it.wpt = f.wpt.data(); it.scale = f.scale.data(); it.Twc = f.Twc;
+    it.do_p3p = f.do_p3p ? 1 : 0; it.p3p_req = f.p3p_req ? 1 : 0;
+    if (f.do_p3p && n >= 4) {
+        const int rows = (int)std::min<long long>(2LL * std::max(nransac_iter, 0), OV2_P3P_MAX_ROWS);
+        samples.assign(4 * (size_t)rows, 0);
+        if (ov2_p3p_draw_samples(f.seed, (int)n, rows, samples.data()) != OV2_OK) return false;
+        it.bv = f.bv.data(); it.n_rows = rows; it.samples = samples.data();
+    }
+    out.removed.assign(n ? n : 1, 0);
+    out.r = ov2_pose_result{};
+    out.r.removed = out.removed.data();
+    return true;
+}
+}  // namespace detail
+
+// Returns OV2_OK or the library's code (ov2_last_error() says why); OV2_EINVAL for arrays that differ in length.
+inline int computePose(Context &ctx, const ComputePoseParams &params, const ComputePoseInput &f, ComputePoseOutput &out)
+{
+    std::vector<int> samples;
+    ov2_pose_problem it;
+    if (!detail::packPose(f, params.nransac_iter, samples, out, it)) return OV2_EINVAL;
+    const ov2_pose_params p = detail::poseParams(params);
+    const int rc = ov2_compute_pose(ctx.get(), &p, &it, &out.r);
+    out.removed.resize(f.scale.size());
+    out.r.removed = out.removed.data();
+    return rc;
+}
+// the frames of a lock-step batch in one call
+inline int computePose(Context &ctx, const ComputePoseParams &params, const std::vector<ComputePoseInput> &fs, std::vector<ComputePoseOutput> &out)
+{
+    const size_t B = fs.size();
+    std::vector<std::vector<int>> samples(B);
+    std::vector<ov2_pose_problem> items(B);
+    std::vector<ov2_pose_result> rs(B);
+    out.assign(B, ComputePoseOutput());
+    for (size_t b = 0; b < B; b++) {
+        if (!detail::packPose(fs[b], params.nransac_iter, samples[b], out[b], items[b])) return OV2_EINVAL;
+        rs[b] = out[b].r;
+    }
+    const ov2_pose_params p = detail::poseParams(params);
+    const int rc = ov2_compute_pose_batch(ctx.get(), &p, (int)B, items.data(), rs.data());
+    for (size_t b = 0; b < B; b++) { out[b].r = rs[b]; out[b].removed.resize(fs[b].scale.size()); out[b].r.removed = out[b].removed.data(); }
     return rc;
 }
 

@@ -192,3 +192,159 @@ def epipolar_ransac_batch(ctx, params, problems, trace=False):
         keeps.append(k)
     L.check(ctx.lib.ov2_epipolar_ransac_batch(ctx.h, C.byref(_epi_as_params(params)), len(problems), S, R))
     return [_epi_finish(R[b], keeps[b], trace) for b in range(len(problems))]
+
+
+# ---- the per-frame pose (f15): ceresPnP in one launch and computePose as one device-resident chain (csrc/pnp.hip) -----------------
+# MultiViewGeometry::ceresPnP (src/multi_view_geometry.cpp:492-586) and VisualFrontEnd::computePose (src/visual_front_end.cpp:659-851).
+# A PnP problem is a dict: unpx (n,2) undistorted pixels, wpt (n,3) world points, scale (n,) int pyramid levels (sigma = 2^scale;
+# omitted: zeros), Twc (7,) [t q(xyzw)].  A pose problem adds bv (n,3), do_p3p, p3p_req and samples (rows,4) (read only where do_p3p).
+TOO_FEW, POSE_OK, PNP_REQ_P3P = L.OV2_POSE_TOO_FEW, L.OV2_POSE_OK, L.OV2_POSE_PNP_REQ_P3P
+P3P_RESET, PNP_RESET, PNP_KEEP = L.OV2_POSE_P3P_RESET, L.OV2_POSE_PNP_RESET, L.OV2_POSE_PNP_KEEP
+ACTION_NAMES = {TOO_FEW: "TOO_FEW", POSE_OK: "POSE_OK", PNP_REQ_P3P: "PNP_REQ_P3P", P3P_RESET: "P3P_RESET", PNP_RESET: "PNP_RESET",
+                PNP_KEEP: "PNP_KEEP"}
+
+
+def pnp_params(nmaxiter, chi2th, use_robust, apply_l2_after_robust, K):
+    p = L.PnPParams()
+    p.nmaxiter, p.chi2th, p.use_robust, p.apply_l2_after_robust = int(nmaxiter), float(chi2th), int(bool(use_robust)), int(bool(apply_l2_after_robust))
+    p.K[:] = [float(v) for v in K]
+    return p
+
+
+def _as_pnp_params(params):
+    if isinstance(params, L.PnPParams):
+        return params
+    return pnp_params(params.get("nmaxiter", 5), params["chi2th"], params.get("use_robust", True),
+                      params.get("apply_l2_after_robust", True), params["K"])
+
+
+def pose_params(pnp, p3p, mono):
+    p = L.PoseParams()
+    p.pnp, p.p3p, p.mono = _as_pnp_params(pnp), _as_params(p3p), int(bool(mono))
+    return p
+
+
+def _as_pose_params(params):
+    if isinstance(params, L.PoseParams):
+        return params
+    return pose_params(params["pnp"], params["p3p"], params.get("mono", False))
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _pnp_arrays(pb, who):
+    unpx = np.ascontiguousarray(pb["unpx"], np.float64).reshape(-1, 2)
+    wpt = np.ascontiguousarray(pb["wpt"], np.float64).reshape(-1, 3)
+    n = len(unpx)
+    scale = np.ascontiguousarray(pb["scale"] if pb.get("scale") is not None else np.zeros(n), np.int32).reshape(-1)
+    Twc = np.ascontiguousarray(pb["Twc"], np.float64).reshape(-1)
+    if len(wpt) != n or len(scale) != n or len(Twc) != 7:
+        raise ValueError("%s: %d pixels, %d world points, %d scales, %d pose entries" % (who, n, len(wpt), len(scale), len(Twc)))
+    return n, unpx, wpt, scale, Twc
+
+
+def _passes(r):
+    return [dict(ran=bool(q.ran), iterations=q.iterations, num_successful_steps=q.num_successful_steps, termination=q.termination,
+                 initial_cost=q.initial_cost, final_cost=q.final_cost) for q in r.passes]
+
+
+def _pnp_problem(pb):
+    n, unpx, wpt, scale, Twc = _pnp_arrays(pb, "ceres_pnp")
+    keep = dict(unpx=unpx, wpt=wpt, scale=scale, Twc=Twc, outliers=np.zeros(max(n, 1), np.int32))
+    s = L.PnPProblem()
+    s.n, s.Twc = n, _dp(Twc)
+    s.unpx, s.wpt = (_dp(unpx), _dp(wpt)) if n else (None, None)
+    s.scale = scale.ctypes.data_as(C.POINTER(C.c_int)) if n else None
+    r = L.PnPResult()
+    r.outliers = keep["outliers"].ctypes.data_as(C.POINTER(C.c_int))
+    return s, r, keep
+
+
+def _pnp_finish(r, keep):
+    return dict(success=bool(r.success), Twc=np.array(r.Twc[:], np.float64), outliers=keep["outliers"][:r.n_outliers].copy(),
+                passes=_passes(r))
+
+
+def ceres_pnp(ctx, params, problem):
+    """ov2_ceres_pnp: the two-pass protocol of ceresPnP in one launch.  Returns a dict: success, Twc (7,), outliers (ascending int32,
+    the first test's) and passes (two dicts: ran, iterations, num_successful_steps, termination, initial_cost, final_cost)."""
+    s, r, keep = _pnp_problem(problem)
+    L.check(ctx.lib.ov2_ceres_pnp(ctx.h, C.byref(_as_pnp_params(params)), C.byref(s), C.byref(r)))
+    return _pnp_finish(r, keep)
+
+
+def ceres_pnp_batch(ctx, params, problems):
+    """ov2_ceres_pnp_batch: the problems of a lock-step batch in one launch (shared params, sizes may differ); one dict per problem,
+    bit for bit what ceres_pnp gives on it."""
+    problems = list(problems)
+    S = (L.PnPProblem * max(1, len(problems)))()
+    R = (L.PnPResult * max(1, len(problems)))()
+    keeps = []
+    for b, pb in enumerate(problems):
+        S[b], R[b], k = _pnp_problem(pb)
+        keeps.append(k)
+    L.check(ctx.lib.ov2_ceres_pnp_batch(ctx.h, C.byref(_as_pnp_params(params)), len(problems), S, R))
+    return [_pnp_finish(R[b], keeps[b]) for b in range(len(problems))]
+
+
+def _pose_problem(pb):
+    n, unpx, wpt, scale, Twc = _pnp_arrays(pb, "compute_pose")
+    do_p3p = bool(pb.get("do_p3p", False))
+    keep = dict(unpx=unpx, wpt=wpt, scale=scale, Twc=Twc, removed=np.zeros(max(n, 1), np.uint8))
+    s = L.PoseProblem()
+    s.n, s.Twc, s.do_p3p, s.p3p_req = n, _dp(Twc), int(do_p3p), int(bool(pb.get("p3p_req", False)))
+    s.unpx, s.wpt = (_dp(unpx), _dp(wpt)) if n else (None, None)
+    s.scale = scale.ctypes.data_as(C.POINTER(C.c_int)) if n else None
+    if do_p3p:
+        bv = np.ascontiguousarray(pb["bv"], np.float64).reshape(-1, 3)
+        sm = np.ascontiguousarray(pb["samples"], np.int32).reshape(-1, 4)
+        if len(bv) != n:
+            raise ValueError("compute_pose: %d bearing vectors, %d keypoints" % (len(bv), n))
+        keep["bv"], keep["samples"] = bv, sm
+        s.bv = _dp(bv) if n else None
+        s.n_rows = len(sm)
+        s.samples = sm.ctypes.data_as(C.POINTER(C.c_int)) if len(sm) else None
+    r = L.PoseResult()
+    r.removed = keep["removed"].ctypes.data_as(C.POINTER(C.c_uint8))
+    return s, r, keep
+
+
+def _pose_finish(r, keep):
+    n = len(keep["unpx"])
+    return dict(Twc=np.array(r.Twc[:], np.float64), action=r.action, p3p_req_out=bool(r.p3p_req_out), removed=keep["removed"][:n].copy(),
+                n_removed_p3p=r.n_removed_p3p, n_outliers_pnp=r.n_outliers_pnp, ran_p3p=bool(r.ran_p3p),
+                p3p=dict(status=r.p3p_status, best_row=r.p3p_best_row, iterations=r.p3p_iterations, rows_consumed=r.p3p_rows_consumed,
+                         score=r.p3p_score), passes=_passes(r))
+
+
+def compute_pose(ctx, params, problem):
+    """ov2_compute_pose: VisualFrontEnd::computePose as one device-resident chain (P3P -> compaction -> ceresPnP -> decision), one
+    synchronisation.  Returns a dict: Twc (7,), action (OV2_POSE_*), p3p_req_out, removed (n,) uint8 (0 kept, 1 after P3P, 2 after an
+    accepted PnP), n_removed_p3p, n_outliers_pnp, ran_p3p, p3p (status, best_row, iterations, rows_consumed, score), passes."""
+    s, r, keep = _pose_problem(problem)
+    L.check(ctx.lib.ov2_compute_pose(ctx.h, C.byref(_as_pose_params(params)), C.byref(s), C.byref(r)))
+    return _pose_finish(r, keep)
+
+
+def compute_pose_batch(ctx, params, problems):
+    """ov2_compute_pose_batch: the frames of a lock-step batch in one call (shared params, sizes and do_p3p may differ); one dict
+    per frame, bit for bit what compute_pose gives on it."""
+    problems = list(problems)
+    S = (L.PoseProblem * max(1, len(problems)))()
+    R = (L.PoseResult * max(1, len(problems)))()
+    keeps = []
+    for b, pb in enumerate(problems):
+        S[b], R[b], k = _pose_problem(pb)
+        keeps.append(k)
+    L.check(ctx.lib.ov2_compute_pose_batch(ctx.h, C.byref(_as_pose_params(params)), len(problems), S, R))
+    return [_pose_finish(R[b], keeps[b]) for b in range(len(problems))]
+
+
+def pose_from_model(model):
+    """ov2_pose_from_model (host only): [t q(xyzw)] of a P3P model (Rwc row-major, twc), with the arithmetic the chain uses"""
+    m = np.ascontiguousarray(model, np.float64).reshape(12)
+    out = np.zeros(7, np.float64)
+    L.check(L.load().ov2_pose_from_model(_dp(m), _dp(out)))
+    return out
