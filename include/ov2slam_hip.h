@@ -1839,6 +1839,71 @@ int  ov2_btracker_track_frame_map(ov2_btracker *t, int n_active, const uint8_t *
 /* prior (2 floats) / has_prior of the first n keypoints of item `item` as the LAST step used them (either form) */
 int  ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *prior_xy_h, uint8_t *has_prior_h);
 
+/* The lock-step step with the per-frame pose fused in (f16): ov2_btracker_track_frame_map[_begin] followed, on the same stream and
+ * with no host round trip in between, by ov2_compute_pose's chain on the frame's 3-D keypoints (VisualFrontEnd::trackMono,
+ * src/visual_front_end.cpp:86-116 with doepipolar_ == 0, then computePose, :659-851).  One enqueue, one synchronisation (in _end).
+ * Per active item b:
+ *   tracking   exactly ov2_btracker_track_frame_map: Tcw_h is the predicted pose INVERTED by the caller, input->Twc_h the same pose
+ *              NOT inverted (pcurframe_->getTwc() after the motion model); the library inverts nothing.
+ *   pose set   the slots i < n_h[b] with (status[i] & 3) == 1 && is3d[i], in slot order; m of them (mapkps_ after kltTracking removed
+ *              the lost keypoints, restricted to is3d_).  k_pose_select writes that predicate as one byte per slot and k_pose_pack
+ *              reads the byte (csrc/framepose.hip).
+ *   inputs     of the chain, packed: unpx = the float unpx of the step's computeKeypoint widened to double, wpt = the slot's map
+ *              point, scale = input->scale_h (NULL: all 0), bv = the step's bearing, Twc = input->Twc_h, p3p_req =
+ *              input->p3p_req_h[b] || the step's own 33 % rule (:225-230), do_p3p = p3p_req || params->dop3p, samples = the table
+ *              ov2_p3p_draw_samples(input->seed_h[b], m, params->n_rows, .) gives, drawn ON THE DEVICE, when do_p3p && m >= 4 (no
+ *              table otherwise).
+ *   result     results[b] is, to the last bit, what ov2_compute_pose returns on those inputs, EXCEPT that results[b].removed holds
+ *              n_h[b] bytes IN SLOT SPACE: removed[i] speaks of slot i (0 kept or not in the pose set, 1 removed after P3P, 2
+ *              removed after an accepted PnP).  results[b].removed must be non-NULL where n_h[b] > 0.
+ *   nothing    On the first frame of a tracker and on a step where nothing is tracked (n_total == 0) no chain runs: action =
+ *   ran        OV2_POSE_TOO_FEW, Twc = Twc_h, p3p_req_out = p3p_req_h[b], every other field (and removed) 0.
+ * The 33 % rule stays on the host: it re-tracks the item's prior keypoints (ov2_fb_klt), which changes that item's positions and
+ * status AFTER the device chain has run.  For an item where the rule fires, _end discards the device pose, rebuilds the pose set
+ * from the final status / unpx / bv and runs ov2_compute_pose_batch over just those items with do_p3p = p3p_req = 1 and a table drawn
+ * from the new m: a second submission with its own upload, six launches and synchronisation (the cost of one ov2_compute_pose_batch
+ * call over the items concerned, on top of the retry's own ov2_fb_klt calls).  It is the rare path: a frame whose motion model
+ * failed.
+ * ov2_btracker_track_frame_end on a step begun with _pose_begin finishes the tracking half and drops the pose.
+ *
+ * NOT in the step: epipolar2d2dFiltering between tracking and pose (the shipped parameter files set doepipolar: 1; a caller with it
+ * on keeps the route of separate calls), checkNewKfReq, the motion model, kltTrackingFromKF.
+ *
+ * OV2_EINVAL, checked on the host before anything is enqueued (the tracker stays where it was; the same frames can be passed
+ * again): everything ov2_btracker_track_frame_map refuses; no calibration; NULL params / input / Twc_h / p3p_req_h / seed_h;
+ * whatever ov2_compute_pose_batch refuses in params->pose; n_rows < 0 or > OV2_P3P_MAX_ROWS; cfg.n_max > OV2_P3P_MAX_POINTS;
+ * |scale| > 60; a non-finite Twc_h; a non-finite wpt on an is3d slot of an active item.  unpx and bv are produced on the device
+ * and CANNOT be checked on the host: the chain's own finiteness tests decide for them (k_pose_gather rejects a search whose
+ * translation is not finite, k_pose_decide a PnP pose whose translation is not finite; the trust-region loop fails on a non-finite
+ * step), so a non-finite bearing yields a refused pose, never an error code.
+ * The pose buffers belong to the tracker: allocated by the first pose step (about 142 B per point slot and 121 B per sample row
+ * of the whole batch), freed with the tracker. */
+typedef struct {
+    ov2_pose_params pose;        /* exactly what ov2_compute_pose takes (pnp, p3p, mono)                                     */
+    int dop3p;                   /* SlamParams::dop3p_                                                                       */
+    int n_rows;                  /* rows of the sample table drawn for an item that searches                                 */
+} ov2_frame_pose_params;
+typedef struct {                 /* per step; items / slots laid out like the map form's arrays                              */
+    const double *Twc_h;         /* 7 per item: pcurframe_->getTwc() after the motion model                                  */
+    const int *scale_h;          /* n_max per item: Keypoint::scale_; NULL = all 0                                           */
+    const uint8_t *p3p_req_h;    /* 1 per item: bp3preq_ as it stands before this frame                                      */
+    const unsigned long long *seed_h;  /* 1 per item: seed of the sample table                                               */
+} ov2_frame_pose_input;
+int  ov2_btracker_track_frame_pose_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                         const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h,
+                                         int klt_use_prior, const ov2_frame_pose_params *params, const ov2_frame_pose_input *input);
+/* results: n_active of them (those of the step begun); p3p_req: the rule's flags as ov2_btracker_track_frame_end returns them */
+int  ov2_btracker_track_frame_pose_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results);
+int  ov2_btracker_track_frame_pose(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                   const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior,
+                                   const ov2_frame_pose_params *params, const ov2_frame_pose_input *input,
+                                   float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results);
+/* What the last pose step fed the chain for `item` (for an item the rule re-ran: what the second run used): *m, the slot of each
+ * packed point (m ints; slot_idx may be NULL), the sample table actually used (4 * *n_rows_used ints; samples may be NULL; 0 rows
+ * when the item did not search).  slot_idx needs cfg.n_max ints of room, samples 4 * n_rows.  Reads the tracker's device buffers:
+ * a diagnostic, not a per-frame call.  OV2_EINVAL before the first finished pose step. */
+int  ov2_btracker_last_pose_inputs(const ov2_btracker *t, int item, int *m, int *slot_idx, int *samples, int *n_rows_used);
+
 #ifdef __cplusplus
 }
 #endif

@@ -317,6 +317,17 @@ class PoseResult(C.Structure):
                 ("removed", C.POINTER(C.c_uint8)), ("passes", PnPPass * 2)]
 
 
+class FramePoseParams(C.Structure):
+    """ov2_frame_pose_params"""
+    _fields_ = [("pose", PoseParams), ("dop3p", C.c_int), ("n_rows", C.c_int)]
+
+
+class FramePoseInput(C.Structure):
+    """ov2_frame_pose_input"""
+    _fields_ = [("Twc_h", C.POINTER(C.c_double)), ("scale_h", C.POINTER(C.c_int)), ("p3p_req_h", C.POINTER(C.c_uint8)),
+                ("seed_h", C.POINTER(C.c_ulonglong))]
+
+
 class EpipolarParams(C.Structure):
     """ov2_epipolar_params"""
     _fields_ = [("max_iterations", C.c_int), ("threshold", C.c_double), ("probability", C.c_double), ("boptimize", C.c_int)]
@@ -576,6 +587,12 @@ SIGNATURES = {
     "ov2_btracker_track_frame_map_begin": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "ov2_btracker_track_frame_map": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "ov2_btracker_last_priors": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ov2_btracker_track_frame_pose_begin": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FramePoseParams),
+                                                 C.POINTER(FramePoseInput)]),
+    "ov2_btracker_track_frame_pose_end": (_i, [_vp, _vp, _vp, _vp, C.POINTER(PoseResult)]),
+    "ov2_btracker_track_frame_pose": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FramePoseParams),
+                                           C.POINTER(FramePoseInput), _vp, _vp, _vp, C.POINTER(PoseResult)]),
+    "ov2_btracker_last_pose_inputs": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

@@ -464,6 +464,14 @@ int ov2_p3p_draw_samples(unsigned long long seed, int n, int rows, int *out)
     return OV2_OK;
 }
 
+static void p3p_plan_fill(P3Plan &pl, size_t B, size_t NP, size_t NR, int n_max, int s_max, bool trace)
+{
+    pl.B = B; pl.NP = NP; pl.NR = NR; pl.n_max = n_max; pl.s_max = s_max; pl.trace = trace;
+    pl.o_it = 0; pl.o_bv = p3_al(pl.o_it + sizeof(P3Item) * B); pl.o_X = p3_al(pl.o_bv + 24 * NP); pl.o_sm = p3_al(pl.o_X + 24 * NP);
+    pl.o_out = p3_al(pl.o_sm + 16 * NR); pl.o_ol = p3_al(pl.o_out + sizeof(P3Out) * B); pl.o_va = p3_al(pl.o_ol + 4 * NP);
+    pl.o_sc = p3_al(pl.o_va + NR); pl.o_md = p3_al(pl.o_sc + 8 * NR); pl.total = p3_al(pl.o_md + 96 * NR);
+}
+
 int p3p_plan(const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems, const ov2_p3p_result *results, P3Plan *plan)
 {
     OV2_REQUIRE(params, OV2_EINVAL, "NULL params");
@@ -496,12 +504,18 @@ int p3p_plan(const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *p
         n_max = p.n > n_max ? p.n : n_max; s_max = p.n_rows > s_max ? p.n_rows : s_max;
     }
     OV2_REQUIRE(NP <= 0x7fffffff && NR <= 0x7fffffff, OV2_EINVAL, "capacity: more than 2^31 - 1 points or rows in one call");
-    P3Plan &pl = *plan;
-    const size_t B = (size_t)n_items;
-    pl.B = B; pl.NP = NP; pl.NR = NR; pl.n_max = n_max; pl.s_max = s_max; pl.trace = trace;
-    pl.o_it = 0; pl.o_bv = p3_al(pl.o_it + sizeof(P3Item) * B); pl.o_X = p3_al(pl.o_bv + 24 * NP); pl.o_sm = p3_al(pl.o_X + 24 * NP);
-    pl.o_out = p3_al(pl.o_sm + 16 * NR); pl.o_ol = p3_al(pl.o_out + sizeof(P3Out) * B); pl.o_va = p3_al(pl.o_ol + 4 * NP);
-    pl.o_sc = p3_al(pl.o_va + NR); pl.o_md = p3_al(pl.o_sc + 8 * NR); pl.total = p3_al(pl.o_md + 96 * NR);
+    p3p_plan_fill(*plan, (size_t)n_items, NP, NR, n_max, s_max, trace);
+    return OV2_OK;
+}
+
+int p3p_plan_capacity(int n_items, int n_max, int n_rows, P3Plan *plan)
+{
+    OV2_REQUIRE(n_items >= 0 && n_items <= 65535, OV2_EINVAL, "more than 65535 problems in one call");
+    OV2_REQUIRE(n_max >= 0 && n_max <= P3_MAX_POINTS, OV2_EINVAL, "capacity: more than 2048 points in one problem");
+    OV2_REQUIRE(n_rows >= 0 && n_rows <= P3_MAX_ROWS, OV2_EINVAL, "capacity: more than 4096 sample rows in one problem");
+    const size_t NP = (size_t)n_items * (size_t)n_max, NR = (size_t)n_items * (size_t)n_rows;
+    OV2_REQUIRE(NP <= 0x7fffffff && NR <= 0x7fffffff, OV2_EINVAL, "capacity: more than 2^31 - 1 points or rows in one call");
+    p3p_plan_fill(*plan, (size_t)n_items, NP, NR, n_max, n_rows, false);
     return OV2_OK;
 }
 

@@ -19,6 +19,11 @@ struct P3Plan {
 
 // the checks of ov2_p3p_ransac_batch on params and problems (results may be NULL: then no result buffer is looked at), and the plan
 int p3p_plan(const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems, const ov2_p3p_result *results, P3Plan *plan);
+// The plan in its capacity form, for a block whose items are written on the device: problem b owns n_max points at b * n_max and
+// n_rows rows at b * n_rows.  The grids and the LDS size of p3p_enqueue follow these bounds; every kernel takes the real counts from
+// the P3Item it reads (a problem's bits do not depend on the bounds: the LDS path is chosen by its own n).  No trace.  OV2_EINVAL
+// beyond the capacity of ov2_p3p_ransac_batch.
+int p3p_plan_capacity(int n_items, int n_max, int n_rows, P3Plan *plan);
 // fills [0, o_out) of the host block
 void p3p_stage(const P3Plan &pl, const ov2_p3p_problem *problems, uint8_t *hs);
 // the three launches on the device block (whose [0, o_out) holds what p3p_stage wrote); results stay in HBM: P3Out per problem at

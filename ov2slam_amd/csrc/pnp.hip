@@ -14,6 +14,7 @@
 // item's point count by construction (P3P's outlier indices are checked against it all the same).
 #include "common.hpp"
 #include "p3p_dev.hpp"
+#include "pose_dev.hpp"               // PnPItem, PnPOut, PoseItem, PoseOut; the chain as host steps (trackb.hip runs it too)
 #include <cmath>
 #include <cfloat>
 #include <vector>
@@ -29,13 +30,6 @@
 #define PNP_WAVES (PNP_THREADS / 64)
 #define PNP_MAX_POINTS OV2_P3P_MAX_POINTS
 static_assert(PNP_THREADS == 64 || PNP_THREADS == 128 || PNP_THREADS == 256, "PNP_THREADS");
-
-struct PnPItem { int n, pt0, pad0, pad1; };
-struct PnPOut {
-    double pose[7], initial_cost[2], final_cost[2];
-    int success, n_out, ran[2], iterations[2], n_success[2], termination[2];
-};
-static_assert(sizeof(PnPOut) == 128, "PnPOut layout");
 
 struct PnPArgs {
     const PnPItem *items;
@@ -272,14 +266,6 @@ __host__ __device__ static inline void pose_from_model(const double *m, double *
 
 enum { POSE_ST_TOO_FEW = 0, POSE_ST_P3P_FAIL = 1, POSE_ST_PNP = 2, POSE_ST_P3P_PNP = 3 };   // what k_pose_gather found
 
-struct PoseItem { int n, pt0, do_p3p, p3p_req; };
-struct PoseOut {
-    double Twc[7], p3p_score, initial_cost[2], final_cost[2];
-    int action, p3p_req_out, n_removed_p3p, n_outliers_pnp, ran_p3p, p3p_status, p3p_best_row, p3p_iterations, p3p_rows_consumed;
-    int ran[2], iterations[2], n_success[2], termination[2], pad;
-};
-static_assert(sizeof(PoseOut) == 168, "PoseOut layout");
-
 struct PoseArgs {
     const PoseItem *items;
     const double *Twc, *unpx, *wpt, *sigma;            // the caller's arrays (7 per item; 2, 3, 1 per point)
@@ -425,6 +411,59 @@ static void pnp_fill_args(PnPArgs &a, const ov2_pnp_params *p)
 static void pnp_store_pass(ov2_pnp_pass &d, int ran, int it, int ns, int term, double ic, double fc)
 {
     d.ran = ran; d.iterations = it; d.num_successful_steps = ns; d.termination = term; d.initial_cost = ic; d.final_cost = fc;
+}
+
+// ---- the chain on a block at capacity (pose_dev.hpp): the lock-step tracker's pose step ---------------------------------------------
+int pose_check_params(const ov2_pose_params *params)
+{
+    OV2_REQUIRE(params, OV2_EINVAL, "NULL params");
+    const int rc = pnp_check_params(&params->pnp);  if (rc) return rc;
+    P3Plan pl;
+    return p3p_plan(&params->p3p, 0, nullptr, nullptr, &pl);
+}
+
+int pose_layout(int n_items, int n_max, int n_rows, PoseLayout *L)
+{
+    const int rc = p3p_plan_capacity(n_items, n_max, n_rows, &L->pl);  if (rc) return rc;
+    const size_t B = (size_t)n_items, NP = L->pl.NP;
+    L->B = B; L->n_max = n_max; L->n_rows = n_rows;
+    L->o_it = 0; L->o_px = pn_al(L->o_it + sizeof(PoseItem) * B); L->o_sg = pn_al(L->o_px + 16 * NP); L->o_p3 = pn_al(L->o_sg + 8 * NP);
+    L->o_cx = pn_al(L->o_p3 + L->pl.total); L->o_cw = pn_al(L->o_cx + 16 * NP); L->o_cs = pn_al(L->o_cw + 24 * NP); L->o_ix = pn_al(L->o_cs + 8 * NP);
+    L->o_pi = pn_al(L->o_ix + 4 * NP); L->o_q0 = pn_al(L->o_pi + sizeof(PnPItem) * B); L->o_st = pn_al(L->o_q0 + 56 * B);
+    L->o_po = pn_al(L->o_st + 4 * B); L->o_pl = pn_al(L->o_po + sizeof(PnPOut) * B); L->o_rm = pn_al(L->o_pl + 4 * NP);
+    L->total = pn_al(L->o_rm + NP);
+    return OV2_OK;
+}
+
+int pose_chain_enqueue(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, uint8_t *ds, const double *Twc_d, PoseOut *out_d,
+                       int n_items, bool search)
+{
+    if (n_items <= 0) return OV2_OK;
+    P3Plan pl = L.pl;
+    pl.B = (size_t)n_items;                                         // the grids cover the active items; the offsets are the block's
+    uint8_t *p3 = ds + L.o_p3;
+    if (search) { const int rc = p3p_enqueue(s, &params->p3p, pl, p3);  if (rc) return rc; }
+    PoseArgs g;
+    g.items = (const PoseItem *)(ds + L.o_it); g.Twc = Twc_d; g.unpx = (const double *)(ds + L.o_px);
+    g.wpt = (const double *)(p3 + pl.o_X); g.sigma = (const double *)(ds + L.o_sg);
+    g.p3items = search ? (const P3Item *)(p3 + pl.o_it) : nullptr;
+    g.p3out = search ? (const P3Out *)(p3 + pl.o_out) : nullptr;
+    g.p3ol = search ? (const int *)(p3 + pl.o_ol) : nullptr;
+    g.c_unpx = (double *)(ds + L.o_cx); g.c_wpt = (double *)(ds + L.o_cw); g.c_sigma = (double *)(ds + L.o_cs); g.idx = (int *)(ds + L.o_ix);
+    g.pnp_items = (PnPItem *)(ds + L.o_pi); g.pose0 = (double *)(ds + L.o_q0); g.stage = (int *)(ds + L.o_st);
+    g.pnp_out = (const PnPOut *)(ds + L.o_po); g.pnp_ol = (const int *)(ds + L.o_pl);
+    g.out = out_d; g.removed = ds + L.o_rm; g.mono = params->mono != 0;
+    hipLaunchKernelGGL(k_pose_gather, dim3(n_items), dim3(64), 0, s, g);
+    OV2_HIP_CHECK(hipGetLastError());
+    PnPArgs a;
+    pnp_fill_args(a, &params->pnp);
+    a.items = g.pnp_items; a.pose0 = g.pose0; a.unpx = g.c_unpx; a.wpt = g.c_wpt; a.sigma = g.c_sigma;
+    a.out = (PnPOut *)(ds + L.o_po); a.outliers = (int *)(ds + L.o_pl);
+    hipLaunchKernelGGL(k_pnp_solve, dim3(n_items), dim3(PNP_THREADS), 0, s, a);
+    OV2_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_pose_decide, dim3(n_items), dim3(64), 0, s, g);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
 }
 
 extern "C" {

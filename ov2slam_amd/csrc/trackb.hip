@@ -16,8 +16,13 @@
 // with three pinned staging sets and eight pyramid sets in rotation; events order producer -> consumer and consumer -> the producer
 // that reuses a buffer.  A caller that uses neither look-ahead call gets the same results from the plain in-order enqueue.
 // Results per item are bit-identical to an ov2_tracker fed the same frames and keypoints (tests/test_gpu_lockstep.py).
+// ov2_btracker_track_frame_pose puts computePose behind the step's kernels on the context's stream (framepose.hip: the pose set and
+// P3P's sample table; pose_dev.hpp: the chain of pnp.hip on a block at capacity): tracking results and the per-frame pose with the
+// one synchronisation, byte-equal to ov2_btracker_track_frame_map followed by ov2_compute_pose_batch (tests/test_gpu_framepose.py).
 #include "common.hpp"
 #include "keypoint_dev.hpp"
+#include "pose_dev.hpp"
+#include <cmath>
 #include <deque>
 #include <new>
 #include <vector>
@@ -27,6 +32,14 @@ int ov2_launch_compute_keypoints(hipStream_t s, const KpCalib &c, const float *p
 int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double img_h, int use_prior, const void *items_d,
                            const double *Tcw_d, const float *px_d, const uint8_t *is3d_d, const double *wpt_d, float *prior_d,
                            uint8_t *has_prior_d, int n_max, int n_items);
+
+// framepose.hip: the pose set, computePose's chain and the removal bytes in slot space, behind k_compute_keypoints
+int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search,
+                          const int *n_d, const uint8_t *status_d, const float *unpx_d, const double *bv_d, const double *wpt_d,
+                          const uint8_t *is3d_d, const double *Twc_d, const int *scale_d, const uint8_t *flags_d,
+                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d);
+size_t ov2_frame_pose_work_bytes(const PoseLayout &L);
+size_t ov2_frame_pose_slot_offset(const PoseLayout &L);
 
 #define BT_SETS 8       // pyramid sets in rotation: cur, prev, the one being prepared for the next frame, five of slack for the mapper
                         // context (a keyframe's pyramids outlive it by BT_SETS - 1 steps: the keyframe period of the shipped parameter files)
@@ -76,12 +89,28 @@ struct ov2_btracker {
     // by the first such step; pinned + mapped or mirrored on the device like the keypoint block
     uint8_t *hmap = nullptr, *dmap = nullptr, *kmap = nullptr;
     size_t m_it = 0, m_T = 0, m_w = 0, m_3d = 0, map_bytes = 0;
+    // ov2_btracker_track_frame_pose: the pose side of a step, allocated by the first such step.  hpose, pinned + mapped or mirrored
+    // like the keypoint block: [Twc 56][seed 8][flags 1] per item and [scale 4] per slot go up; [PoseOut 168][m, rows 8] per item and
+    // [removed 1] per slot come down.  dwork: the chain's block at capacity and the pack's lists (device only; not the context's
+    // scratch, which other calls use on the same stream)
+    uint8_t *hpose = nullptr, *dpose = nullptr, *kpose = nullptr, *dwork = nullptr;
+    size_t q_T = 0, q_seed = 0, q_fl = 0, q_sc = 0, q_in = 0, q_out = 0, q_ms = 0, q_rm = 0, pose_bytes = 0, work_bytes = 0;
+    // ov2_btracker_last_pose_inputs: the layout of the last finished pose step; per item m and rows; for an item the rule re-ran, the
+    // slot list and the table of the second run (the device block still holds those of the first)
+    bool lp_on = false, lp_chain = false;
+    PoseLayout lp_L;
+    std::vector<int> lp_m, lp_rows;
+    std::vector<std::vector<int>> lp_slot, lp_samples;
+    std::vector<uint8_t> lp_host;
     // keyframe detection: device mirrors of the items' current keypoints and of the detector's output, pinned staging
     uint8_t *d_det = nullptr, *h_det = nullptr; size_t det_in_bytes = 0;
     float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
     uint8_t *d_roi = nullptr;                     // detectGFTT: device copy of the caller's roi mask (w x h, allocated with the first one)
     // a step between ov2_btracker_track_frame_begin and _end: what _end needs to finish it
-    struct Pending { bool on = false, tracked = false; int n_active = 0, use_prior = 0; const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n; } pend;
+    struct Pending { bool on = false, tracked = false; int n_active = 0, use_prior = 0; const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n;
+                     // a pose step (ov2_btracker_track_frame_pose_begin): its settings and the per-item inputs _end needs again
+                     bool pose = false; ov2_frame_pose_params pp; PoseLayout L; std::vector<double> Twc; std::vector<uint8_t> req;
+                     std::vector<unsigned long long> seed; } pend;
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
 };
@@ -111,6 +140,9 @@ static void btracker_free(ov2_btracker *t)
     if (t->dblk) (void)hipFree(t->dblk);
     if (t->hmap) (void)hipHostFree(t->hmap);
     if (t->dmap) (void)hipFree(t->dmap);
+    if (t->hpose) (void)hipHostFree(t->hpose);
+    if (t->dpose) (void)hipFree(t->dpose);
+    if (t->dwork) (void)hipFree(t->dwork);
     if (t->h_det) (void)hipHostFree(t->h_det);
     if (t->d_det) (void)hipFree(t->d_det);
     if (t->h_out) (void)hipHostFree(t->h_out);
@@ -149,7 +181,9 @@ static int enqueue_preprocess(ov2_btracker *t, ov2_ctx *on, ov2_pyr *dst, int wh
 
 // kltTracking of items [0, n): keypoint block in, the fused LK launch, computeKeypoint, result block out
 // map_use_prior >= 0 (ov2_btracker_track_frame_map): k_prior_frame fills the prior and flag slots from the map side first
-static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur, int n, int map_use_prior = -1)
+// pose (ov2_btracker_track_frame_pose): the pose set, computePose's chain and the removal bytes follow k_compute_keypoints
+static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur, int n, int map_use_prior = -1,
+                       const ov2_btracker::Pending *pose = nullptr)
 {
     ov2_ctx *ctx = t->ctx;
     const ov2_tracker_config &c = t->cfg;
@@ -171,6 +205,21 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
         rc = ov2_launch_compute_keypoints(ctx->stream, t->calib, (const float *)(k + t->o_out), c.n_max, (const int *)(k + t->o_n),
                                           (float *)(k + t->o_unpx), (double *)(k + t->o_bv), n);
         if (rc != OV2_OK) return rc;
+    }
+    if (pose) {
+        if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->dpose, t->hpose, t->q_in, hipMemcpyHostToDevice, ctx->stream));
+        uint8_t *q = t->kpose;
+        const uint8_t *m = t->kmap;
+        bool search = pose->pp.dop3p != 0;
+        for (int b = 0; b < n; b++) search = search || pose->req[(size_t)b];
+        rc = ov2_launch_frame_pose(ctx->stream, &pose->pp.pose, pose->L, n, search, (const int *)(k + t->o_n), k + t->o_st,
+                                   (const float *)(k + t->o_unpx), (const double *)(k + t->o_bv), (const double *)(m + t->m_w), m + t->m_3d,
+                                   (const double *)(q + t->q_T), (const int *)(q + t->q_sc), q + t->q_fl,
+                                   (const unsigned long long *)(q + t->q_seed), t->dwork, (PoseOut *)(q + t->q_out), (int *)(q + t->q_ms),
+                                   q + t->q_rm);
+        if (rc != OV2_OK) return rc;
+        if (!t->zero_copy)
+            OV2_HIP_CHECK(hipMemcpyAsync(t->hpose + t->q_out, t->dpose + t->q_out, t->pose_bytes - t->q_out, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (!t->zero_copy)
         OV2_HIP_CHECK(hipMemcpyAsync(t->hblk + t->o_out, t->dblk + t->o_out, t->blk_bytes - t->o_out, hipMemcpyDeviceToHost, ctx->stream));
@@ -255,6 +304,78 @@ static int stage_map(ov2_btracker *t, int n_active, const double *wpt, const uin
         if (!n) continue;
         memcpy(t->hmap + t->m_w + 24 * o, wpt + 3 * o, 24 * n);
         memcpy(t->hmap + t->m_3d + o, is3d + o, n);
+    }
+    return OV2_OK;
+}
+
+// what a pose step refuses beyond the map form's checks (n_active and the counts are known to be in range); *L: the chain's layout
+static int check_pose(const ov2_btracker *t, int n_active, const double *wpt, const uint8_t *is3d, const int *n_h,
+                      const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, PoseLayout *L)
+{
+    OV2_REQUIRE(pp && in, OV2_EINVAL, "ov2_btracker_track_frame_pose: NULL params / input");
+    OV2_REQUIRE(in->Twc_h && in->p3p_req_h && in->seed_h, OV2_EINVAL, "ov2_btracker_track_frame_pose: NULL Twc_h / p3p_req_h / seed_h");
+    int rc = pose_check_params(&pp->pose);  if (rc) return rc;
+    OV2_REQUIRE(pp->n_rows >= 0, OV2_EINVAL, "negative count (n_rows)");
+    OV2_REQUIRE(pp->n_rows <= OV2_P3P_MAX_ROWS, OV2_EINVAL, "capacity: more than 4096 sample rows in one problem");
+    OV2_REQUIRE(t->cfg.n_max <= OV2_P3P_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds the 2048 points of one pose problem");
+    rc = pose_layout(t->batch, t->cfg.n_max, pp->n_rows, L);  if (rc) return rc;
+    const size_t nm = (size_t)t->cfg.n_max;
+    for (int b = 0; b < n_active; b++) {
+        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(in->Twc_h[7 * (size_t)b + c]), OV2_EINVAL, "Twc not finite");
+        const size_t n = (size_t)(n_h ? n_h[b] : 0), o = (size_t)b * nm;
+        for (size_t i = 0; i < n; i++) {
+            if (in->scale_h) OV2_REQUIRE(in->scale_h[o + i] >= -60 && in->scale_h[o + i] <= 60, OV2_EINVAL, "|scale| > 60");
+            if (is3d && wpt && is3d[o + i]) {
+                const double *w = wpt + 3 * (o + i);
+                OV2_REQUIRE(std::isfinite(w[0]) && std::isfinite(w[1]) && std::isfinite(w[2]), OV2_EINVAL, "wpt not finite on a 3-D slot");
+            }
+        }
+    }
+    return OV2_OK;
+}
+
+// the pose inputs of a step into hpose (the pose buffers are allocated here by the first pose step, and grown when a step asks for
+// more sample rows than any before it)
+static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, const int *n_h,
+                      const PoseLayout &L)
+{
+    const size_t nm = (size_t)t->cfg.n_max, B = (size_t)t->batch, slots = nm * B;
+    if (!t->hpose) {
+        t->q_T = 0; t->q_seed = up256(56 * B); t->q_fl = up256(t->q_seed + 8 * B); t->q_sc = up256(t->q_fl + B); t->q_in = up256(t->q_sc + 4 * slots);
+        t->q_out = t->q_in; t->q_ms = up256(t->q_out + sizeof(PoseOut) * B); t->q_rm = up256(t->q_ms + 8 * B); t->pose_bytes = up256(t->q_rm + slots);
+        uint8_t *h = nullptr, *d = nullptr;
+        hipError_t e = hipHostMalloc((void **)&h, t->pose_bytes, hipHostMallocMapped);
+        if (e == hipSuccess && !t->zero_copy) e = hipMalloc((void **)&d, t->pose_bytes);
+        void *alias = d;
+        if (e == hipSuccess && t->zero_copy) e = hipHostGetDevicePointer(&alias, h, 0);
+        if (e != hipSuccess || !alias) {
+            if (h) (void)hipHostFree(h);
+            if (d) (void)hipFree(d);
+            (void)hipGetLastError();
+            ov2_set_error("ov2_btracker_track_frame_pose: %s", hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        memset(h, 0, t->pose_bytes);
+        t->hpose = h; t->dpose = d; t->kpose = (uint8_t *)alias;
+    }
+    const size_t need = ov2_frame_pose_work_bytes(L);
+    if (need > t->work_bytes) {
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (the previous step's chain has long finished: _end waited for it)
+        if (t->dwork) (void)hipFree(t->dwork);
+        t->dwork = nullptr; t->work_bytes = 0; t->lp_on = false;         // the lists of the last step go with the block
+        const hipError_t e = hipMalloc((void **)&t->dwork, need);
+        if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("ov2_btracker_track_frame_pose: %s", hipGetErrorString(e)); return OV2_ENOMEM; }
+        t->work_bytes = need;
+    }
+    memcpy(t->hpose + t->q_T, in->Twc_h, 56 * (size_t)n_active);
+    memcpy(t->hpose + t->q_seed, in->seed_h, 8 * (size_t)n_active);
+    uint8_t *fl = t->hpose + t->q_fl;
+    for (int b = 0; b < n_active; b++) {
+        const int req = in->p3p_req_h[b] != 0;
+        fl[b] = (uint8_t)(req | ((req || pp->dop3p) ? 2 : 0));
+        const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
+        int *sc = (int *)(t->hpose + t->q_sc) + o;
+        if (in->scale_h) memcpy(sc, in->scale_h + o, 4 * n); else memset(sc, 0, 4 * n);
     }
     return OV2_OK;
 }
@@ -527,10 +648,12 @@ int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
 
 } // extern "C"
 
-// both forms of the step's first half.  map: the priors come from the device (wpt_h / is3d_h / Tcw_h), prior_xy_h / has_prior_h are unused
+// the forms of the step's first half.  map: the priors come from the device (wpt_h / is3d_h / Tcw_h), prior_xy_h / has_prior_h are unused;
+// pose (a map form): the pose of ov2_btracker_track_frame_pose follows in the same enqueue
 static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
                              const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior, bool map,
-                             const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h)
+                             const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, bool pose = false,
+                             const ov2_frame_pose_params *pp = nullptr, const ov2_frame_pose_input *pin = nullptr)
 {
     OV2_REQUIRE(t && img_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
@@ -547,6 +670,8 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
     }
     if (map) OV2_REQUIRE(n_total == 0 || (kps_xy_h && wpt_h && is3d_h && Tcw_h && n_h), OV2_EINVAL, "NULL point buffer");
     else OV2_REQUIRE(n_total == 0 || (kps_xy_h && prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
+    PoseLayout poseL;
+    if (pose) { const int rcp = check_pose(t, n_active, wpt_h, is3d_h, n_h, pp, pin, &poseL);  if (rcp != OV2_OK) return rcp; }
     for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = t->last_pn[(size_t)b] = 0;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
@@ -571,6 +696,13 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
     P.n_active = n_active; P.use_prior = klt_use_prior; P.kps = kps_xy_h; P.has_prior = has_prior_h;
     P.n.assign((size_t)n_active, 0);
     if (n_h) for (int b = 0; b < n_active; b++) P.n[(size_t)b] = n_h[b];
+    P.pose = pose;
+    if (pose) {
+        P.pp = *pp; P.L = poseL;
+        P.Twc.assign(pin->Twc_h, pin->Twc_h + 7 * (size_t)n_active);
+        P.req.assign(pin->p3p_req_h, pin->p3p_req_h + n_active);
+        P.seed.assign(pin->seed_h, pin->seed_h + n_active);
+    }
     if (t->frames == 0 || n_total == 0) {
         // first frame (trackMono returns right after preprocessImage) or nothing to track anywhere
         rc = preprocess();
@@ -584,9 +716,13 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
         if (rc != OV2_OK) { t->cur = old_cur; return rc; }
         P.has_prior = t->hblk + t->o_flg;                                // the flags the device sets: same slots as the caller's array
     }
+    if (pose) {
+        rc = stage_pose(t, n_active, pp, pin, n_h, poseL);
+        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
+    }
     stage_points(t, n_active, kps_xy_h, map ? nullptr : prior_xy_h, has_prior_h, n_h, klt_use_prior);
     rc = preprocess();
-    if (rc == OV2_OK) rc = enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], n_active, map ? (klt_use_prior ? 1 : 0) : -1);
+    if (rc == OV2_OK) rc = enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], n_active, map ? (klt_use_prior ? 1 : 0) : -1, pose ? &P : nullptr);
     if (rc != OV2_OK) { t->cur = old_cur; return rc; }
     commit();
     P.tracked = true; P.on = true;
@@ -607,12 +743,107 @@ int ov2_btracker_track_frame_map_begin(ov2_btracker *t, int n_active, const uint
     return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h);
 }
 
-int ov2_btracker_track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req)
+} // extern "C"
+
+static void pose_store(ov2_pose_result &r, const PoseOut &o)
+{
+    memcpy(r.Twc, o.Twc, 56);
+    r.action = o.action; r.p3p_req_out = o.p3p_req_out; r.n_removed_p3p = o.n_removed_p3p; r.n_outliers_pnp = o.n_outliers_pnp;
+    r.ran_p3p = o.ran_p3p; r.p3p_status = o.p3p_status; r.p3p_best_row = o.p3p_best_row; r.p3p_iterations = o.p3p_iterations;
+    r.p3p_rows_consumed = o.p3p_rows_consumed; r.p3p_score = o.p3p_score;
+    for (int q = 0; q < 2; q++) {
+        ov2_pnp_pass &d = r.pass[q];
+        d.ran = o.ran[q]; d.iterations = o.iterations[q]; d.num_successful_steps = o.n_success[q]; d.termination = o.termination[q];
+        d.initial_cost = o.initial_cost[q]; d.final_cost = o.final_cost[q];
+    }
+}
+
+// The items where the 33 % rule fired (`redo`), after their retry: the pose set from the final status, the step's unpx / bv as the
+// retry left them, a table drawn from the new m, and ov2_compute_pose_batch over just those items with do_p3p = p3p_req = 1
+static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_t *status_h, ov2_pose_result *results)
+{
+    const ov2_btracker::Pending &P = t->pend;
+    const size_t nm = (size_t)t->cfg.n_max, R = redo.size();
+    std::vector<std::vector<double>> unpx(R), wpt(R), bv(R);
+    std::vector<std::vector<int>> scale(R);
+    std::vector<std::vector<uint8_t>> rm(R);
+    std::vector<ov2_pose_problem> pb(R);
+    std::vector<ov2_pose_result> rs(R);
+    for (size_t k = 0; k < R; k++) {
+        const int b = redo[k];
+        const size_t o = (size_t)b * nm;
+        const int n = P.n[(size_t)b];
+        const float *un = (const float *)(t->hblk + t->o_unpx) + 2 * o;
+        const double *bvs = (const double *)(t->hblk + t->o_bv) + 3 * o, *w = (const double *)(t->hmap + t->m_w) + 3 * o;
+        const uint8_t *d3 = t->hmap + t->m_3d + o;
+        const int *sc = (const int *)(t->hpose + t->q_sc) + o;
+        std::vector<int> &slot = t->lp_slot[(size_t)b];
+        slot.clear();
+        for (int i = 0; i < n; i++)
+            if ((status_h[o + i] & 3) == 1 && d3[i]) {
+                slot.push_back(i);
+                unpx[k].push_back((double)un[2 * i]); unpx[k].push_back((double)un[2 * i + 1]);
+                for (int c = 0; c < 3; c++) { wpt[k].push_back(w[3 * i + c]); bv[k].push_back(bvs[3 * i + c]); }
+                scale[k].push_back(sc[i]);
+            }
+        const int m = (int)slot.size();
+        std::vector<int> &tab = t->lp_samples[(size_t)b];
+        tab.clear();
+        if (m >= 4 && P.pp.n_rows > 0) {
+            tab.resize(4 * (size_t)P.pp.n_rows);
+            const int rc = ov2_p3p_draw_samples(P.seed[(size_t)b], m, P.pp.n_rows, tab.data());
+            if (rc != OV2_OK) return rc;
+        }
+        rm[k].assign((size_t)(m > 0 ? m : 1), 0);
+        ov2_pose_problem &q = pb[k];
+        q.n = m; q.unpx = unpx[k].data(); q.wpt = wpt[k].data(); q.scale = scale[k].data(); q.Twc = P.Twc.data() + 7 * (size_t)b;
+        q.bv = bv[k].data(); q.do_p3p = 1; q.p3p_req = 1; q.n_rows = m >= 4 ? P.pp.n_rows : 0; q.samples = tab.empty() ? nullptr : tab.data();
+        rs[k].removed = rm[k].data();
+        t->lp_m[(size_t)b] = m; t->lp_rows[(size_t)b] = q.n_rows; t->lp_host[(size_t)b] = 1;
+    }
+    const int rc = ov2_compute_pose_batch(t->ctx, &P.pp.pose, (int)R, pb.data(), rs.data());
+    if (rc != OV2_OK) return rc;
+    for (size_t k = 0; k < R; k++) {
+        const int b = redo[k];
+        ov2_pose_result &r = results[b];
+        uint8_t *removed = r.removed;
+        r = rs[k];
+        r.removed = removed;
+        if (P.n[(size_t)b] > 0) memset(removed, 0, (size_t)P.n[(size_t)b]);
+        const std::vector<int> &slot = t->lp_slot[(size_t)b];
+        for (size_t j = 0; j < slot.size(); j++) removed[slot[j]] = rm[k][j];
+    }
+    return OV2_OK;
+}
+
+// both forms of the step's second half.  results != NULL: the step was begun with ov2_btracker_track_frame_pose_begin and its
+// poses are wanted; NULL: the tracking half only (a pose the step computed is dropped)
+static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     ov2_btracker::Pending &P = t->pend;
     OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_track_frame_end without ov2_btracker_track_frame_begin");
+    OV2_REQUIRE(!results || P.pose, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was not begun with ov2_btracker_track_frame_pose_begin");
+    if (results)
+        for (int b = 0; b < P.n_active; b++)
+            OV2_REQUIRE(P.n[(size_t)b] == 0 || results[b].removed, OV2_EINVAL, "NULL result buffer (removed)");
     P.on = false;
+    if (results) {
+        const size_t B = (size_t)t->batch;
+        t->lp_on = true; t->lp_chain = P.tracked; t->lp_L = P.L;
+        t->lp_m.assign(B, 0); t->lp_rows.assign(B, 0); t->lp_host.assign(B, 0);
+        t->lp_slot.resize(B); t->lp_samples.resize(B);
+        if (!P.tracked)                                                  // first frame / nothing tracked: no chain ran
+            for (int b = 0; b < P.n_active; b++) {
+                ov2_pose_result &r = results[b];
+                uint8_t *removed = r.removed;
+                memset(&r, 0, sizeof(r));
+                r.removed = removed;
+                if (P.n[(size_t)b] > 0) memset(removed, 0, (size_t)P.n[(size_t)b]);
+                memcpy(r.Twc, P.Twc.data() + 7 * (size_t)b, 56);
+                r.action = OV2_POSE_TOO_FEW; r.p3p_req_out = P.req[(size_t)b] != 0;
+            }
+    }
     const size_t nm = (size_t)t->cfg.n_max;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
@@ -623,17 +854,97 @@ int ov2_btracker_track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *stat
     }
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     OV2_REQUIRE(out_xy_h && status_h, OV2_EINVAL, "NULL result buffer");
+    std::vector<int> rule((size_t)P.n_active, 0);
     for (int b = 0; b < P.n_active; b++) {
         const size_t n = (size_t)P.n[(size_t)b], o = nm * (size_t)b;
         if (!n) continue;
         memcpy(out_xy_h + 2 * o, t->hblk + t->o_out + 8 * o, 8 * n);
         memcpy(status_h + o, t->hblk + t->o_st + o, n);
         const int rc = apply_p3p_rule(t, b, P.kps + 2 * o, P.has_prior ? P.has_prior + o : nullptr, P.use_prior, (int)n, out_xy_h + 2 * o,
-                                      status_h + o, p3p_req ? p3p_req + b : nullptr);
+                                      status_h + o, &rule[(size_t)b]);
         if (rc != OV2_OK) return rc;
+        if (p3p_req) p3p_req[b] = rule[(size_t)b];
         if (t->has_calib) t->last_n[(size_t)b] = (int)n;
         t->last_pn[(size_t)b] = (int)n;
     }
+    if (!results) return OV2_OK;
+    std::vector<int> redo;
+    for (int b = 0; b < P.n_active; b++) {
+        const size_t n = (size_t)P.n[(size_t)b], o = nm * (size_t)b;
+        int ms[2];
+        memcpy(ms, t->hpose + t->q_ms + 8 * (size_t)b, 8);
+        t->lp_m[(size_t)b] = ms[0]; t->lp_rows[(size_t)b] = ms[1];
+        if (n && rule[(size_t)b]) { redo.push_back(b); continue; }
+        PoseOut po;
+        memcpy(&po, t->hpose + t->q_out + sizeof(PoseOut) * (size_t)b, sizeof(PoseOut));
+        pose_store(results[b], po);
+        if (n) memcpy(results[b].removed, t->hpose + t->q_rm + o, n);
+    }
+    if (!redo.empty()) return pose_redo(t, redo, status_h, results);
+    return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req)
+{
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, nullptr);
+}
+
+int ov2_btracker_track_frame_pose_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                        const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h,
+                                        int klt_use_prior, const ov2_frame_pose_params *params, const ov2_frame_pose_input *input)
+{
+    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h,
+                             true, params, input);
+}
+
+int ov2_btracker_track_frame_pose_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results)
+{
+    OV2_REQUIRE(results, OV2_EINVAL, "NULL result array");
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, results);
+}
+
+int ov2_btracker_track_frame_pose(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                  const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior,
+                                  const ov2_frame_pose_params *params, const ov2_frame_pose_input *input,
+                                  float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results)
+{
+    OV2_REQUIRE(results, OV2_EINVAL, "NULL result array");
+    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // as ov2_btracker_track_frame: the result buffers before anything is enqueued
+        int n_total = 0;
+        for (int b = 0; b < n_active; b++) {
+            n_total += n_h[b] > 0 ? n_h[b] : 0;
+            OV2_REQUIRE(n_h[b] <= 0 || results[b].removed, OV2_EINVAL, "NULL result buffer (removed)");
+        }
+        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
+    }
+    const int rc = ov2_btracker_track_frame_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
+    if (rc != OV2_OK) return rc;
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, results);
+}
+
+int ov2_btracker_last_pose_inputs(const ov2_btracker *t, int item, int *m, int *slot_idx, int *samples, int *n_rows_used)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(t->lp_on, OV2_EINVAL, "ov2_btracker_last_pose_inputs: no pose step has been finished on this tracker");
+    const size_t b = (size_t)item;
+    const int mm = t->lp_m[b], rows = t->lp_rows[b];
+    if (m) *m = mm;
+    if (n_rows_used) *n_rows_used = rows;
+    if (t->lp_host[b]) {
+        if (slot_idx && mm > 0) memcpy(slot_idx, t->lp_slot[b].data(), 4 * (size_t)mm);
+        if (samples && rows > 0) memcpy(samples, t->lp_samples[b].data(), 16 * (size_t)rows);
+        return OV2_OK;
+    }
+    if (!t->lp_chain || (mm <= 0 && rows <= 0)) return OV2_OK;
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const PoseLayout &L = t->lp_L;
+    if (slot_idx && mm > 0)
+        OV2_HIP_CHECK(hipMemcpy(slot_idx, t->dwork + ov2_frame_pose_slot_offset(L) + 4 * b * (size_t)L.n_max, 4 * (size_t)mm, hipMemcpyDeviceToHost));
+    if (samples && rows > 0)
+        OV2_HIP_CHECK(hipMemcpy(samples, t->dwork + L.o_p3 + L.pl.o_sm + 16 * b * (size_t)L.n_rows, 16 * (size_t)rows, hipMemcpyDeviceToHost));
     return OV2_OK;
 }
 

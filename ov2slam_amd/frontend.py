@@ -599,6 +599,80 @@ class LockstepTracker:
         L.check(self.lib.ov2_btracker_track_frame_map_begin(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw),
                                                             _ptr(nn), int(bool(klt_use_prior))))
 
+    def _pose_args(self, na, nn, params, Twc, p3p_req, seed, scale, dop3p, n_rows):
+        from . import pose as _pose
+        fp = L.FramePoseParams()
+        fp.pose, fp.dop3p, fp.n_rows = _pose._as_pose_params(params), int(bool(dop3p)), int(n_rows)
+        self._pose_rows = max(0, int(n_rows))                                     # (the room lastPoseInputs gives the table)
+        Twc = np.ascontiguousarray(Twc, np.float64).reshape(-1, 7)
+        req = np.ascontiguousarray(p3p_req, np.uint8).reshape(-1)
+        seed = np.ascontiguousarray(seed, np.uint64).reshape(-1)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.int32).reshape(self.batch, self.n_max)
+        if len(Twc) < na or len(req) < na or len(seed) < na:
+            raise ValueError("one pose, one p3p request and one seed per active item")
+        fi = L.FramePoseInput()
+        fi.Twc_h = Twc.ctypes.data_as(C.POINTER(C.c_double))
+        fi.scale_h = None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_int))
+        fi.p3p_req_h = req.ctypes.data_as(C.POINTER(C.c_uint8))
+        fi.seed_h = seed.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        return fp, fi, (Twc, req, seed, sc)
+
+    def _pose_results(self, na, nn):
+        R = (L.PoseResult * max(1, na))()
+        removed = np.zeros((max(1, na), self.n_max), np.uint8)
+        for b in range(na):
+            R[b].removed = removed[b].ctypes.data_as(C.POINTER(C.c_uint8))
+        return R, removed
+
+    def _pose_dicts(self, R, removed, nn):
+        from . import pose as _pose
+        return [_pose._pose_finish(R[b], dict(unpx=removed[b, :int(nn[b])], removed=removed[b])) for b in range(len(nn))]
+
+    def trackFramePose(self, imgs, kps, wpt, is3d, Tcw, n, params, Twc, p3p_req, seed, scale=None, dop3p=False, n_rows=0,
+                       klt_use_prior=True):
+        """trackFrameMap and the per-frame pose in one enqueue and one synchronisation (ov2_btracker_track_frame_pose).  params: as
+        pose.compute_pose takes them; Twc (>= n_active, 7): the predicted poses NOT inverted (Tcw: the same, inverted); p3p_req, seed:
+        one per item; scale (batch, n_max) int or None; dop3p, n_rows: SlamParams::dop3p_ and the rows of the table drawn for an item
+        that searches.  -> (out, status bits, p3p_req, poses): poses[b] as pose.compute_pose returns it, with removed (n[b],) IN SLOT
+        SPACE."""
+        na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
+        fp, fi, keep = self._pose_args(na, nn, params, Twc, p3p_req, seed, scale, dop3p, n_rows)
+        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
+        p3p = np.zeros(na, np.int32)
+        R, removed = self._pose_results(na, nn)
+        L.check(self.lib.ov2_btracker_track_frame_pose(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw), _ptr(nn),
+                                                       int(bool(klt_use_prior)), C.byref(fp), C.byref(fi), _ptr(out), _ptr(st), _ptr(p3p), R))
+        return out, st, p3p.astype(bool), self._pose_dicts(R, removed, nn)
+
+    def trackFramePoseBegin(self, imgs, kps, wpt, is3d, Tcw, n, params, Twc, p3p_req, seed, scale=None, dop3p=False, n_rows=0,
+                            klt_use_prior=True):
+        """first half of trackFramePose; trackFramePoseEnd finishes it (trackFrameEnd finishes the tracking half and drops the pose)"""
+        na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
+        fp, fi, keep = self._pose_args(na, nn, params, Twc, p3p_req, seed, scale, dop3p, n_rows)
+        L.check(self.lib.ov2_btracker_track_frame_pose_begin(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw),
+                                                             _ptr(nn), int(bool(klt_use_prior)), C.byref(fp), C.byref(fi)))
+        self._pending = (imgs, kps, wpt, is3d, nn)                                # (kps is re-read by the end half: keep it alive)
+
+    def trackFramePoseEnd(self):
+        """second half of trackFramePose -> (out, status bits, p3p_req, poses)"""
+        nn = self._pending[4]
+        na = len(nn)
+        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
+        p3p = np.zeros(na, np.int32)
+        R, removed = self._pose_results(na, nn)
+        L.check(self.lib.ov2_btracker_track_frame_pose_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p), R))
+        self._pending = None
+        return out, st, p3p.astype(bool), self._pose_dicts(R, removed, nn)
+
+    def lastPoseInputs(self, item):
+        """what the last pose step fed the chain for `item` -> (m, slots (m,) int32, samples (rows used, 4) int32)"""
+        m, rows = C.c_int(), C.c_int()
+        slot = np.zeros(self.n_max, np.int32)
+        tab = np.zeros((max(1, self._pose_rows), 4), np.int32)
+        L.check(self.lib.ov2_btracker_last_pose_inputs(self.h_trk, int(item), C.byref(m), slot.ctypes.data_as(C.POINTER(C.c_int)),
+                                                       tab.ctypes.data_as(C.POINTER(C.c_int)), C.byref(rows)))
+        return m.value, slot[:m.value].copy(), tab[:rows.value].copy()
+
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
         pri = np.empty((n, 2), np.float32)
