@@ -141,6 +141,9 @@ void *ov2_ctx_stream(ov2_ctx *ctx);        /* the hipStream_t, for event timing 
                                            iteration summaries of the solve (ov2_ba_get_trace); the batch entry point does not */
 #define OV2_OPT_LCKF_SCRATCH_KB    16   /* ov2_lckf_prepare*: device scratch (KiB) the batch forms may hold at a time; items are walked in chunks
                                            that fit (at least one item per chunk).  Default 262144 (256 MiB); >= 1 */
+#define OV2_OPT_EPIF_CAPACITY      18   /* test forcing: 1 makes ov2_epipolar_filter[_batch] stage its device block in the CAPACITY form (every item
+                                           owns as many keypoint / keyframe slots as the largest item of the call), the form a fused step
+                                           will use; the results do not depend on it.  Default 0: packed to the items' sizes */
 int  ov2_ctx_set_option(ov2_ctx *ctx, int option, int value);
 int  ov2_ctx_get_option(ov2_ctx *ctx, int option, int *value);
 
@@ -1724,6 +1727,101 @@ int ov2_sampson_filter_2d(ov2_ctx *ctx, const ov2_fkf_item *item, const double F
 int ov2_sampson_filter_2d_batch(ov2_ctx *ctx, int n_items, const ov2_fkf_item *items, const double *Fkfcur, float fransac_err,
                                 ov2_sampson2d_result *results);
 
+/* ---- epipolar2d2dFiltering (epifilter.hip): VisualFrontEnd::epipolar2d2dFiltering, src/visual_front_end.cpp:440-656 -----------
+ * The whole per-frame function as ONE device chain: the join against the previous keyframe, the parallax gate, the 5-point search
+ * over a sample table drawn on the device, the 50 % rule, the removals, the mono pose, computeFundamentalMat12 and the Sampson pass
+ * over the 2-D keypoints.  One upload, five launches (k_epif_gather, k_e5_solve, k_e5_score, k_e5_pick, k_epif_decide), one
+ * download, ONE synchronisation per call.  The arithmetic is that of the three separate calls: the parallax IS ov2_parallax(unrot =
+ * 1, ONLY_3D or ALL, OV2_FKF_AVG_WIDE), the search IS ov2_epipolar_ransac on the packed bearings with the table of
+ * ov2_epipolar_draw_samples(seed, m, n_rows), the pass IS ov2_sampson_filter_2d -- bit for bit.
+ *
+ *   :462   n_cur < 8: OV2_EPIF_TOO_FEW_KPS.  (m, parallax, epifrom3dkps and nb3dkps are still reported; nothing is searched.)
+ *   :484   epifrom3dkps = stereo && nb3dkps > 30; nb3dkps is the item's, or with -1 the cur_is3d flags set.
+ *   :492   the join: the current keypoints IN ARRAY ORDER, only the 3-D ones under epifrom3dkps; the counterpart by binary search in
+ *          the strictly ascending kf_lmid, a keypoint without one is skipped.  Match k (k < m) is current keypoint pair_cur[k] and
+ *          keyframe slot j: bv1[k] = kf_bv[j], bv2[k] = cur_bv[pair_cur[k]].
+ *   :528   parallax = sum / (float)m, the sum serial in array order as OV2_FKF_AVG_WIDE; m == 0 gives the reference's 0.f / 0 NaN.
+ *   :530   (double)parallax < 2. * (double)fransac_err: OV2_EPIF_LOW_PARALLAX.  A NaN parallax does not return here.
+ *   :540   do_optimize = mono && nbkfs > 2 && nb3dkps < 30.
+ *   :559   the search (epi.max_iterations / threshold / probability), over n_rows rows when m >= 8 and without a table otherwise.
+ *   :574   any OV2_EPI_* bit in its status (m < 8 included): OV2_EPIF_NO_MODEL.
+ *   :580   (double)n_outliers > 0.5 * (double)m: OV2_EPIF_DEGENERATE, nothing is removed.
+ *   :587   removed[pair_cur[outliers[k]]] = 1.
+ *   :594   do_optimize: see "Mono" below.
+ *   :611   epifrom3dkps: F = K^-T hat(t) R' K^-1 with t = model t, R' = toRotationMatrix of the quaternion of model R (the reference
+ *          goes through Sophus::SE3d(Rkfc, tkfc) and back: Eigen's matrix-to-quaternion branches, a normalisation), K^-1 and K^-T
+ *          in closed form for the upper-triangular K ([1/fx 0 -cx/fx; 0 1/fy -cy/fy; 0 0 1]), the products from left to right as
+ *          full 3 x 3 products, each sum of three terms serial.  Then for every keypoint with is3d == 0 the rule of
+ *          ov2_sampson_filter_2d (the current point as leftpt, a missing counterpart scored against (0, 0)):
+ *          err > fransac_err gives removed = 2.  F is restated, not pinned against an Eigen / Sophus build.
+ *          OV2_EPIF_FILTERED.
+ *
+ * Mono.  boptimize changes only Rwc / twc in the reference's search, never its outlier list (src/multi_view_geometry.cpp:669-693),
+ * so every decision and every removal above is the reference's in this branch too.  The REFINED pose is not available (OpenGV's
+ * non-linear refinement has no device form; epi.boptimize must be 0).  Where do_optimize holds and the filter reached :594 the
+ * chain sets pose_from_model = 1 and writes
+ *   Twc_model = kf_Twc * SE3(Rkfc, scale * tkfc / |tkfc|),   scale = |(kf_Tcw * cur_Twc).translation()|,
+ * from the UNREFINED model in Sophus' arithmetic (SE3(R, t): the quaternion of ov2_pose_from_model; the product: quaternion product
+ * with renormalisation plus the rotated translation, as ov2_pose_graph_apply).  This is NOT the reference's pose until a
+ * refinement exists: the chain never overwrites the caller's pose, and what to do with Twc_model is the caller's decision.
+ *
+ * Device draw.  The table is drawn by k_epif_gather because m exists only on the device in a fused step; it equals
+ * ov2_epipolar_draw_samples(seed, m, n_rows) integer for integer.  The kernel evaluates the stream in windows of 2048 draws; a row
+ * that needed more than a WHOLE window by itself (2048 draws: a chance below 2^-380 at m = 8, where a row is a permutation and
+ * misses a given value for 2048 draws with probability (7/8)^2048) ends the draw, and the remaining rows are filled with
+ * -1, which the search skips.
+ *
+ * Capacity: OV2_FKF_MAX_POINTS keypoints on either side, OV2_EPI_MAX_ROWS rows, 65535 items.  OV2_EINVAL, all of it checked on the
+ * host before the context is touched (a rejected call writes nothing): everything ov2_parallax and ov2_epipolar_ransac_batch refuse
+ * for these inputs (NULL arguments or arrays with a non-zero count, negative counts, kf_lmid not strictly ascending, threshold,
+ * probability, max_iterations, boptimize != 0), a NULL kf_bv / kf_Twc with n_kf > 0, a NULL `removed` with n_cur > 0, bearings,
+ * poses or K that are not finite, n_rows outside [0, OV2_EPI_MAX_ROWS], n_cur / n_kf beyond OV2_FKF_MAX_POINTS, more than 65535
+ * items. */
+enum { OV2_EPIF_TOO_FEW_KPS = 0, OV2_EPIF_LOW_PARALLAX = 1, OV2_EPIF_NO_MODEL = 2, OV2_EPIF_DEGENERATE = 3, OV2_EPIF_FILTERED = 4 };
+typedef struct {
+    ov2_fkf_params fkf;          /* K and stereo are read                                                                    */
+    ov2_epipolar_params epi;     /* nransac_iter_, the bearing threshold of fransac_err_, 0.99; boptimize must be 0          */
+    float fransac_err;           /* SlamParams::fransac_err_ (pixels): the gate and the Sampson pass                         */
+    int mono;                    /* SlamParams::mono_                                                                        */
+    int n_rows;                  /* rows of the sample table drawn per item that searches                                    */
+} ov2_epifilter_params;
+typedef struct {
+    ov2_fkf_item fkf;            /* the item of ov2_parallax / ov2_sampson_filter_2d; nb3dkps: pcurframe_->nb3dkps_ or -1    */
+    const double *kf_bv;         /* 3 n_kf: the keyframe's Keypoint::bv_, in the order of kf_lmid                            */
+    const double *kf_Twc;        /* 7: pkf->getTwc() as held                                                                 */
+    int nbkfs;                   /* pmap_->nbkfs_                                                                            */
+    unsigned long long seed;     /* of the sample table                                                                      */
+} ov2_epifilter_item;
+typedef struct {
+    int action;                  /* OV2_EPIF_*                                                                               */
+    int m;                       /* matches that entered the search                                                          */
+    int epifrom3dkps, do_optimize;
+    int nb3dkps;                 /* as used: the item's, or counted                                                          */
+    float parallax;              /* :528; NaN when m == 0                                                                    */
+    int status, best_row, iterations, rows_consumed;   /* the search's, as ov2_epipolar_result; 0 / -1 / 0 / 0 when it did not run */
+    double score;
+    int n_inliers, n_outliers;
+    double model[12];            /* Rkfc row-major, tkfc; zeros without a model                                              */
+    double F[9];                 /* row-major; zeros unless the Sampson pass ran                                             */
+    int n_removed_ransac, n_removed_sampson;
+    uint8_t *removed;            /* n_cur bytes: 0 kept, 1 removed as a RANSAC outlier, 2 removed by the Sampson pass        */
+    int *pair_cur;               /* optional (NULL or n_cur ints of room): the current index of packed match k, k < m        */
+    float *err;                  /* optional (NULL or n_cur): the Sampson error, 0 where the pass did not score              */
+    int pose_from_model;         /* 1: Twc_model is set (mono, see above)                                                    */
+    double Twc_model[7];
+    int *trace_samples;          /* optional diagnostic (NULL or 8 n_rows): the table the device drew; untouched without a search */
+} ov2_epifilter_result;
+/* The four pointers of the result (removed, pair_cur, err, trace_samples) are INPUTS of the call, read on entry: the caller sets
+ * each of them to a buffer or to NULL before the call (zero-initialise the struct, then set `removed`); every other field is
+ * written by the call.  trace_samples is not part of the reference's function: it exists so that the table drawn on the device can
+ * be compared with ov2_epipolar_draw_samples. */
+/* one frame: the batch form with one item, through the same code path */
+int ov2_epipolar_filter(ov2_ctx *ctx, const ov2_epifilter_params *params, const ov2_epifilter_item *item, ov2_epifilter_result *result);
+/* the frames of a lock-step batch with shared params (the item is a grid axis: each kernel is launched once).  Per item the result
+ * equals ov2_epipolar_filter on that item bit for bit; sizes may differ, empty frames are allowed. */
+int ov2_epipolar_filter_batch(ov2_ctx *ctx, const ov2_epifilter_params *params, int n_items, const ov2_epifilter_item *items,
+                              ov2_epifilter_result *results);
+
 /* ---- tracking priors (priors.hip): where the reference derives the priors that its KLT calls start from ----------------------
  *   ov2_klt_priors      VisualFrontEnd::kltTracking (src/visual_front_end.cpp:156-184): the map point of every 3-D keypoint
  *                       projected with the predicted pose (Frame::projWorldToImageDist, Frame::isInImage)
@@ -1867,7 +1965,9 @@ int  ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *pri
  * ov2_btracker_track_frame_end on a step begun with _pose_begin finishes the tracking half and drops the pose.
  *
  * NOT in the step: epipolar2d2dFiltering between tracking and pose (the shipped parameter files set doepipolar: 1; a caller with it
- * on keeps the route of separate calls), checkNewKfReq, the motion model, kltTrackingFromKF.
+ * on keeps the route of separate calls: tracking, ov2_epipolar_filter_batch -- the function as one device chain, built on a
+ * caller-owned block so that it can go between the select and the pack later --, ov2_compute_pose_batch), checkNewKfReq, the motion
+ * model, kltTrackingFromKF.
  *
  * OV2_EINVAL, checked on the host before anything is enqueued (the tracker stays where it was; the same frames can be passed
  * again): everything ov2_btracker_track_frame_map refuses; no calibration; NULL params / input / Twc_h / p3p_req_h / seed_h;

@@ -27,6 +27,7 @@ OV2_OPT_LK_ACC = 14
 OV2_OPT_DETECT_STRIP = 15
 OV2_OPT_LCKF_SCRATCH_KB = 16
 OV2_OPT_LK_PERSIST = 17
+OV2_OPT_EPIF_CAPACITY = 18
 OV2_LK_ACC_INT64, OV2_LK_ACC_FLOAT_UI4 = 0, 1
 OV2_FAST_TIE_SCAN_ORDER, OV2_FAST_TIE_LIBSTDCXX = 0, 1
 OV2_LK_IMPL_AUTO, OV2_LK_IMPL_ROW, OV2_LK_IMPL_LANE3 = 0, 1, 2
@@ -50,6 +51,7 @@ OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
 OV2_POSE_TOO_FEW, OV2_POSE_OK, OV2_POSE_PNP_REQ_P3P, OV2_POSE_P3P_RESET, OV2_POSE_PNP_RESET, OV2_POSE_PNP_KEEP = 0, 1, 2, 3, 4, 5
 OV2_EPI_TOO_FEW_POINTS, OV2_EPI_NO_MODEL, OV2_EPI_FEW_INLIERS = 1, 2, 4
 OV2_EPI_MAX_POINTS, OV2_EPI_MAX_ROWS = 2048, 4096
+OV2_EPIF_TOO_FEW_KPS, OV2_EPIF_LOW_PARALLAX, OV2_EPIF_NO_MODEL, OV2_EPIF_DEGENERATE, OV2_EPIF_FILTERED = 0, 1, 2, 3, 4
 OV2_PG_MAX_POSES, OV2_PG_MAX_EDGES = 16384, 32768
 OV2_TERM_NO_CONVERGENCE, OV2_TERM_FUNCTION_TOL, OV2_TERM_PARAMETER_TOL, OV2_TERM_GRADIENT_TOL = 0, 1, 2, 3
 OV2_TERM_MIN_RADIUS, OV2_TERM_INVALID_STEPS, OV2_TERM_FAILURE = 4, 5, 6
@@ -401,6 +403,27 @@ class Sampson2dResult(C.Structure):
     _fields_ = [("err", C.POINTER(C.c_float)), ("bad", C.POINTER(C.c_uint8)), ("n_bad", C.c_int)]
 
 
+class EpifilterParams(C.Structure):
+    """ov2_epifilter_params"""
+    _fields_ = [("fkf", FkfParams), ("epi", EpipolarParams), ("fransac_err", C.c_float), ("mono", C.c_int), ("n_rows", C.c_int)]
+
+
+class EpifilterItem(C.Structure):
+    """ov2_epifilter_item"""
+    _fields_ = [("fkf", FkfItem), ("kf_bv", C.POINTER(C.c_double)), ("kf_Twc", C.POINTER(C.c_double)), ("nbkfs", C.c_int),
+                ("seed", C.c_ulonglong)]
+
+
+class EpifilterResult(C.Structure):
+    """ov2_epifilter_result"""
+    _fields_ = [("action", C.c_int), ("m", C.c_int), ("epifrom3dkps", C.c_int), ("do_optimize", C.c_int), ("nb3dkps", C.c_int),
+                ("parallax", C.c_float), ("status", C.c_int), ("best_row", C.c_int), ("iterations", C.c_int),
+                ("rows_consumed", C.c_int), ("score", C.c_double), ("n_inliers", C.c_int), ("n_outliers", C.c_int),
+                ("model", C.c_double * 12), ("F", C.c_double * 9), ("n_removed_ransac", C.c_int), ("n_removed_sampson", C.c_int),
+                ("removed", C.POINTER(C.c_uint8)), ("pair_cur", C.POINTER(C.c_int)), ("err", C.POINTER(C.c_float)),
+                ("pose_from_model", C.c_int), ("Twc_model", C.c_double * 7), ("trace_samples", C.POINTER(C.c_int))]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -580,6 +603,8 @@ SIGNATURES = {
     "ov2_kf_decision_batch": (_i, [_vp, C.POINTER(FkfParams), _i, C.POINTER(FkfItem), C.POINTER(KfDecisionResult)]),
     "ov2_sampson_filter_2d": (_i, [_vp, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
     "ov2_sampson_filter_2d_batch": (_i, [_vp, _i, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
+    "ov2_epipolar_filter": (_i, [_vp, C.POINTER(EpifilterParams), C.POINTER(EpifilterItem), C.POINTER(EpifilterResult)]),
+    "ov2_epipolar_filter_batch": (_i, [_vp, C.POINTER(EpifilterParams), _i, C.POINTER(EpifilterItem), C.POINTER(EpifilterResult)]),
     "ov2_klt_priors": (_i, [_vp, C.POINTER(KltPriorsParams), C.POINTER(KltPriorsItem), C.POINTER(KltPriorsResult)]),
     "ov2_klt_priors_batch": (_i, [_vp, C.POINTER(KltPriorsParams), _i, C.POINTER(KltPriorsItem), C.POINTER(KltPriorsResult)]),
     "ov2_stereo_priors": (_i, [_vp, C.POINTER(StereoPriorsParams), C.POINTER(StereoPriorsItem), C.POINTER(StereoPriorsResult)]),

@@ -76,6 +76,7 @@ struct ov2_ctx {
     void *ba_host_pool = nullptr; void (*ba_host_pool_free)(void *) = nullptr;
     hipEvent_t ba_ev[2] = {nullptr, nullptr};              // the two timing events of a solve (created with the first one: a pair per pass was 25 us)
     int lckf_scratch_kb = 256 * 1024;          // OV2_OPT_LCKF_SCRATCH_KB: device scratch one chunk of ov2_lckf_prepare* items may take
+    int epif_capacity = 0;                     // OV2_OPT_EPIF_CAPACITY: ov2_epipolar_filter_batch stages its block in the capacity form
     int debug = 0;                             // OV2_OPT_DEBUG; initial value: environment OV2_DEBUG, read once by ov2_ctx_create
     // pinned staging of host images on their way to the device: its own buffer (h_scratch is rewritten by the next call's small
     // arrays while an asynchronous image upload may still be in flight) and an event that says when it may be refilled

@@ -234,6 +234,7 @@ int ov2_ctx_set_option(ov2_ctx *ctx, int option, int value)
     case OV2_OPT_LCKF_SCRATCH_KB:
         OV2_REQUIRE(value >= 1, OV2_EINVAL, "OV2_OPT_LCKF_SCRATCH_KB takes >= 1 KiB");
         ctx->lckf_scratch_kb = value; return OV2_OK;
+    case OV2_OPT_EPIF_CAPACITY:      ctx->epif_capacity = value != 0; return OV2_OK;
     case OV2_OPT_DEBUG:              ctx->debug = value != 0; return OV2_OK;
     case OV2_OPT_FAST_TIE:
         OV2_REQUIRE(value == OV2_FAST_TIE_SCAN_ORDER || value == OV2_FAST_TIE_LIBSTDCXX, OV2_EINVAL, "OV2_OPT_FAST_TIE takes 0 or 1");
@@ -263,6 +264,7 @@ int ov2_ctx_get_option(ov2_ctx *ctx, int option, int *value)
     case OV2_OPT_DETECT_STRIP:       *value = ctx->det_strip; return OV2_OK;
     case OV2_OPT_LK_ACC:             *value = ctx->lk_acc; return OV2_OK;
     case OV2_OPT_LCKF_SCRATCH_KB:    *value = ctx->lckf_scratch_kb; return OV2_OK;
+    case OV2_OPT_EPIF_CAPACITY:      *value = ctx->epif_capacity; return OV2_OK;
     case OV2_OPT_DEBUG:              *value = ctx->debug; return OV2_OK;
     case OV2_OPT_FAST_TIE:           *value = ctx->det_fast_tie; return OV2_OK;
     default:

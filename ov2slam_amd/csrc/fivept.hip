@@ -18,6 +18,7 @@
 // No atomics, no result that depends on scheduling.  Every pointer and size is validated on the host before any device work; the
 // solve kernel checks every sample index against the problem's point count before it reads through it.
 #include "common.hpp"
+#include "fivept_dev.hpp"              // E5Item, E5Out, E5Args and the host step (e5_enqueue) that epifilter.hip chains as well
 #include <cmath>
 #include <cfloat>
 
@@ -59,17 +60,6 @@ __device__ __forceinline__ double e5_dist(const E5Model &m, E5V f1, E5V f2)
     const E5V r{(q.x * R[0] + q.y * R[3]) + q.z * R[6], (q.x * R[1] + q.y * R[4]) + q.z * R[7], (q.x * R[2] + q.y * R[5]) + q.z * R[8]};
     return (1. - e5_dot(f1, p) / sqrt(e5_dot(p, p))) + (1. - e5_dot(f2, r) / sqrt(e5_dot(r, r)));
 }
-
-struct E5Item { int n, S, pt0, row0; };
-struct E5Out { double model[12]; double score; int best_row, iterations, rows_consumed, status, n_inliers, n_outliers; };
-static_assert(sizeof(E5Out) == 128, "E5Out layout");
-
-struct E5Args {
-    const E5Item *items; const double *bv1; const double *bv2; const int4 *samples;
-    double *models; uint8_t *valid; double *score;
-    E5Out *out; int *outliers;
-    int max_iterations; double threshold, probability;
-};
 
 // ---- polynomials in (x, y, z): variables 0 = x, 1 = y, 2 = z, 3 = 1; monomials are sorted tuples in lexicographic order ----
 __device__ __forceinline__ constexpr int e5_qidx(int i, int j) { return i * 4 - i * (i - 1) / 2 + (j - i); }               // i <= j
@@ -571,12 +561,18 @@ __global__ __launch_bounds__(64) void k_e5_pick(E5Args a)
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static inline size_t e5_al(size_t x) { return (x + 15) & ~(size_t)15; }
 
-static inline unsigned long long e5_splitmix64(unsigned long long seed, unsigned long long j)
+int e5_enqueue(hipStream_t s, const E5Args &a, int n_items, int s_max)
 {
-    unsigned long long z = seed + (j + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
+    if (n_items <= 0) return OV2_OK;
+    if (s_max > 0) {
+        hipLaunchKernelGGL(k_e5_solve, dim3((s_max + E5_LANES - 1) / E5_LANES, n_items), dim3(E5_LANES), 0, s, a);
+        OV2_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_e5_score, dim3(s_max, n_items), dim3(64), 0, s, a);
+        OV2_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_e5_pick, dim3(n_items), dim3(64), 0, s, a);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
 }
 
 int ov2_epipolar_draw_samples(unsigned long long seed, int n, int rows, int *out)
@@ -659,14 +655,8 @@ int ov2_epipolar_ransac_batch(ov2_ctx *ctx, const ov2_epipolar_params *params, i
     a.samples = (const int4 *)(ds + o_sm); a.models = (double *)(ds + o_md); a.valid = ds + o_va; a.score = (double *)(ds + o_sc);
     a.out = (E5Out *)(ds + o_out); a.outliers = (int *)(ds + o_ol);
     a.max_iterations = params->max_iterations; a.threshold = params->threshold; a.probability = params->probability;
-    if (s_max > 0) {
-        hipLaunchKernelGGL(k_e5_solve, dim3((s_max + E5_LANES - 1) / E5_LANES, n_items), dim3(E5_LANES), 0, ctx->stream, a);
-        OV2_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_e5_score, dim3(s_max, n_items), dim3(64), 0, ctx->stream, a);
-        OV2_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_e5_pick, dim3(n_items), dim3(64), 0, ctx->stream, a);
-    OV2_HIP_CHECK(hipGetLastError());
+    rc = e5_enqueue(ctx->stream, a, n_items, s_max);
+    if (rc) return rc;
     OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, down_end - o_out, hipMemcpyDeviceToHost, ctx->stream));
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     pt0 = row0 = 0;

@@ -8,7 +8,7 @@
 //                    bitonic sort padded with +inf, run heads flagged, scanned, the head of rank n_distinct / 2 picked.
 //   k_fkf_sampson    the Sampson pass over the 2-D keypoints after the 5-point search (:610-652), one lane per keypoint.
 // include/ov2slam_hip.h states the arithmetic; tests/kfreq_ref.py is the same in numpy.
-#include "mvg_dev.hpp"
+#include "fkf_dev.hpp"                 // the join, the rotation, the distance and the widened sum: epifilter.hip uses them too
 
 #pragma clang fp contract(off)
 
@@ -30,17 +30,6 @@ struct FkfItemD {
     double cur_Twc[7], kf_Tcw[7];
 };
 #define FKF_OUT_INTS 12       // per item: parallax bits, n, n_distinct, n_nonfinite, noccupcells, nb3dkps, n_out_of_grid, decision, reason
-
-// Frame::getKeypointById on ascending ids: the slot of `id`, -1 when the keyframe does not hold it
-__device__ __forceinline__ int fkf_find(const int *kf, int n, int id)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (kf[mid] < id) lo = mid + 1; else hi = mid;
-    }
-    return (lo < n && kf[lo] == id) ? lo : -1;
-}
 
 __global__ __launch_bounds__(FKF_THREADS) void k_fkf_parallax(FkfParamsD P, const FkfItemD *__restrict__ items, const int *__restrict__ cur_lmid,
                                                               const float2 *__restrict__ cur_px, const float2 *__restrict__ cur_unpx,
@@ -66,15 +55,7 @@ __global__ __launch_bounds__(FKF_THREADS) void k_fkf_parallax(FkfParamsD P, cons
     __syncthreads();
 
     double R[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
-    if (P.unrot) {                                      // Rkfcur = Rkfw * Rwcur, :1082-1084
-        double A[9], B[9];
-        tri_rotmat(TriQ{it.kf_Tcw[3], it.kf_Tcw[4], it.kf_Tcw[5], it.kf_Tcw[6]}, A);
-        tri_rotmat(TriQ{it.cur_Twc[3], it.cur_Twc[4], it.cur_Twc[5], it.cur_Twc[6]}, B);
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) R[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
-    }
+    if (P.unrot) fkf_rkfcur(it.kf_Tcw, it.cur_Twc, R);  // Rkfcur = Rkfw * Rwcur, :1082-1084
     int my_n = 0, my_nf = 0, my_3d = 0, my_oog = 0;
     for (int i = t; i < n_cur; i += FKF_THREADS) {
         const int g = cur0 + i;
@@ -96,10 +77,8 @@ __global__ __launch_bounds__(FKF_THREADS) void k_fkf_parallax(FkfParamsD P, cons
         const bool skip = (P.filter == OV2_FKF_ONLY_2D && is3d) || (P.filter == OV2_FKF_ONLY_3D && !is3d);
         const int j = skip ? -1 : fkf_find(s_k, n_kf, cur_lmid[g]);
         if (j >= 0) {
-            float2 u;
-            if (P.unrot) u = tri_project(P.K, tri_matvec(R, TriD3{cur_bv[3 * (size_t)g], cur_bv[3 * (size_t)g + 1], cur_bv[3 * (size_t)g + 2]}));
-            else u = cur_unpx[g];
-            d = tri_pdist(u, kf_unpx[kf0 + j]);
+            if (P.unrot) d = fkf_unrot_dist(P.K, R, cur_bv + 3 * (size_t)g, kf_unpx[kf0 + j]);
+            else d = tri_pdist(cur_unpx[g], kf_unpx[kf0 + j]);
             my_n++;
             const float p = (float)d;
             if (!(fabsf(p) <= 3.402823466e+38f)) my_nf++;
@@ -127,10 +106,7 @@ __global__ __launch_bounds__(FKF_THREADS) void k_fkf_parallax(FkfParamsD P, cons
             if (__ballot(d != -1.) == 0ull) continue;
             if (d == -1.) d = 0.;
             if (P.stat == OV2_FKF_AVG_WIDE) {
-                const int lo = __double2loint(d), hi = __double2hiint(d);
-#pragma unroll
-                for (int l = 0; l < 64; l++)                                                    // :517
-                    sum = (float)((double)sum + __hiloint2double(__builtin_amdgcn_readlane(hi, l), __builtin_amdgcn_readlane(lo, l)));
+                sum = fkf_wide_add64(sum, d);                                                   // :517
             } else {
                 const int p = __float_as_int((float)d);
 #pragma unroll
@@ -253,7 +229,7 @@ __global__ __launch_bounds__(FKF_THREADS) void k_fkf_sampson(const FkfItemD *__r
 static inline size_t fkf_al(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // every input check of the three entry points, before the context is looked at; full: the arrays the parallax / decision kernel reads
-static int fkf_check_items(int n_items, const ov2_fkf_item *items, bool full, size_t *N, size_t *M, int *n_max)
+int fkf_check_items(int n_items, const ov2_fkf_item *items, bool full, size_t *N, size_t *M, int *n_max)
 {
     OV2_REQUIRE(n_items <= 65535, OV2_EUNSUPPORTED, "more than 65535 items in one call");
     *N = *M = 0; *n_max = 0;

@@ -1,7 +1,8 @@
 // mvg_dev.hpp -- small fp64 geometry shared by triangulate.hip, mapmatch.hip, stereo.hip and fkf.hip: Sophus' SO3 / SE3 products
 // and actions on a pose as held (restated from the vendored so3.hpp, se3.hpp), Eigen's quaternion-to-matrix, a serial 3x3
-// matrix-vector product, CameraCalibration::projectCamToImage, cv::norm of a Point2f difference and
-// MultiViewGeometry::computeSampsonDistance.  Sums of three products run serially.
+// matrix-vector product, CameraCalibration::projectCamToImage, cv::norm of a Point2f difference,
+// MultiViewGeometry::computeSampsonDistance and the pose of a model (Eigen's matrix-to-quaternion branches; pnp.hip and epifilter.hip).
+// Sums of three products run serially.
 #pragma once
 #include "common.hpp"
 
@@ -97,4 +98,29 @@ __device__ __forceinline__ float sampson(const double *F, float lx, float ly, fl
     const float x1 = (float)Ftr[0], x2 = (float)Fl[0], y1 = (float)Ftr[1], y2 = (float)Fl[1];
     const float den = x1 * x1 + y1 * y1 + x2 * x2 + y2 * y2;
     return sqrtf(num / den);
+}
+
+// [t q] of (Rwc row-major | twc): Eigen's QuaternionBase::operator=(Matrix3) branches, then a normalisation
+__host__ __device__ static inline void pose_from_model(const double *m, double *p)
+{
+    const double t = (m[0] + m[4]) + m[8];
+    double q[4];                                                    // x y z w
+    if (t > 0.0) {
+        double s = sqrt(t + 1.0);
+        q[3] = 0.5 * s; s = 0.5 / s;
+        q[0] = (m[7] - m[5]) * s; q[1] = (m[2] - m[6]) * s; q[2] = (m[3] - m[1]) * s;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        double s = sqrt(((m[4 * i] - m[4 * j]) - m[4 * k]) + 1.0);
+        q[i] = 0.5 * s; s = 0.5 / s;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * s;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * s;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * s;
+    }
+    const double nq = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    p[0] = m[9]; p[1] = m[10]; p[2] = m[11];
+    p[3] = q[0] / nq; p[4] = q[1] / nq; p[5] = q[2] / nq; p[6] = q[3] / nq;
 }

@@ -14,6 +14,7 @@
 // item's point count by construction (P3P's outlier indices are checked against it all the same).
 #include "common.hpp"
 #include "p3p_dev.hpp"
+#include "mvg_dev.hpp"                // pose_from_model (epifilter.hip builds the mono pose from it too)
 #include "pose_dev.hpp"               // PnPItem, PnPOut, PoseItem, PoseOut; the chain as host steps (trackb.hip runs it too)
 #include <cmath>
 #include <cfloat>
@@ -238,31 +239,6 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_solve(PnPArgs a)
 
 // ================================================================================== the chain around it
 #pragma clang fp contract(off)    // from here on every expression rounds as written (the host form of pose_from_model must agree)
-
-// [t q] of (Rwc row-major | twc): Eigen's QuaternionBase::operator=(Matrix3) branches, then a normalisation
-__host__ __device__ static inline void pose_from_model(const double *m, double *p)
-{
-    const double t = (m[0] + m[4]) + m[8];
-    double q[4];                                                    // x y z w
-    if (t > 0.0) {
-        double s = sqrt(t + 1.0);
-        q[3] = 0.5 * s; s = 0.5 / s;
-        q[0] = (m[7] - m[5]) * s; q[1] = (m[2] - m[6]) * s; q[2] = (m[3] - m[1]) * s;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        double s = sqrt(((m[4 * i] - m[4 * j]) - m[4 * k]) + 1.0);
-        q[i] = 0.5 * s; s = 0.5 / s;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * s;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * s;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * s;
-    }
-    const double nq = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
-    p[0] = m[9]; p[1] = m[10]; p[2] = m[11];
-    p[3] = q[0] / nq; p[4] = q[1] / nq; p[5] = q[2] / nq; p[6] = q[3] / nq;
-}
 
 enum { POSE_ST_TOO_FEW = 0, POSE_ST_P3P_FAIL = 1, POSE_ST_PNP = 2, POSE_ST_P3P_PNP = 3 };   // what k_pose_gather found
 

@@ -49,6 +49,10 @@ static int (*const check_epi2d)(ov2::Context &, const ov2::FrameVsKeyframe &, co
 static int (*const check_epi2d_batch)(ov2::Context &, const std::vector<ov2::FrameVsKeyframe> &, const std::vector<double> &, float,
                                       std::vector<std::vector<int>> &, std::vector<std::vector<float>> *) = &ov2::epipolarFilter2d;
 static auto const check_kf_sort = &ov2::detail::sortKeyframeByLmid;
+// epipolar2d2dFiltering as one device chain, single and batch
+static int (*const check_epif)(ov2::Context &, const ov2::EpipolarFilterParams &, const ov2::EpipolarFilterInput &, ov2::EpipolarFilterOutput &) = &ov2::epipolar2d2dFiltering;
+static int (*const check_epif_batch)(ov2::Context &, const ov2::EpipolarFilterParams &, const std::vector<ov2::EpipolarFilterInput> &,
+                                     std::vector<ov2::EpipolarFilterOutput> &) = &ov2::epipolar2d2dFiltering;
 // the tracking priors: kltPriors / stereoPriors, single and batch, and their host-only helpers
 static int (*const check_klt_priors)(ov2::Context &, const ov2::ProjectionCamera &, bool, const ov2::KltPriorsInput &, std::vector<ov2::Point2f> &,
                                      std::vector<uint8_t> &) = &ov2::kltPriors;

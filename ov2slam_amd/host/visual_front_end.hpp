@@ -150,12 +150,16 @@ struct FrameVsKeyframe {
 
 namespace detail {
 // the keyframe side in ascending lmid order (what ov2_fkf_item asks for); false when the arrays differ in length or an id repeats
+// bv / bv_sorted (optional, both or none): the bearings (3 doubles each) carried along, for epipolar2d2dFiltering
 inline bool sortKeyframeByLmid(const std::vector<int> &lmid, const std::vector<Point2f> &unpx, std::vector<int> &lmid_sorted,
-                               std::vector<float> &unpx_sorted)
+                               std::vector<float> &unpx_sorted, const std::vector<double> *bv = nullptr,
+                               std::vector<double> *bv_sorted = nullptr)
 {
     const size_t m = lmid.size();
     lmid_sorted.clear(); unpx_sorted.clear();
     if (unpx.size() != m) return false;
+    if ((bv != nullptr) != (bv_sorted != nullptr) || (bv && bv->size() != 3 * m)) return false;
+    if (bv_sorted) bv_sorted->assign(3 * m, 0.);
     std::vector<std::pair<int, size_t>> order(m);
     for (size_t i = 0; i < m; i++) order[i] = std::make_pair(lmid[i], i);
     std::sort(order.begin(), order.end());
@@ -164,15 +168,19 @@ inline bool sortKeyframeByLmid(const std::vector<int> &lmid, const std::vector<P
         if (i > 0 && order[i].first == order[i - 1].first) return false;
         lmid_sorted[i] = order[i].first;
         unpx_sorted[2 * i] = unpx[order[i].second].x; unpx_sorted[2 * i + 1] = unpx[order[i].second].y;
+        if (bv)
+            for (int c = 0; c < 3; c++) (*bv_sorted)[3 * i + c] = (*bv)[3 * order[i].second + c];
     }
     return true;
 }
 struct FkfPacked { std::vector<int> kf_lmid; std::vector<float> kf_unpx; ov2_fkf_item item; };
-inline bool packFkf(const FrameVsKeyframe &f, FkfPacked &p)
+// kf_bv / kf_bv_sorted (optional, both or none): the keyframe's bearings, sorted along with its ids
+inline bool packFkf(const FrameVsKeyframe &f, FkfPacked &p, const std::vector<double> *kf_bv = nullptr,
+                    std::vector<double> *kf_bv_sorted = nullptr)
 {
     const size_t n = f.cur_lmid.size();
     if (f.cur_px.size() != n || f.cur_unpx.size() != n || f.cur_bv.size() != 3 * n || f.cur_is3d.size() != n) return false;
-    if (!sortKeyframeByLmid(f.kf_lmid, f.kf_unpx, p.kf_lmid, p.kf_unpx)) return false;
+    if (!sortKeyframeByLmid(f.kf_lmid, f.kf_unpx, p.kf_lmid, p.kf_unpx, kf_bv, kf_bv_sorted)) return false;
     static const float none_f[2] = {0.f, 0.f}; static const double none_d[3] = {0., 0., 0.}; static const int none_i = 0; static const uint8_t none_b = 0;
     ov2_fkf_item &it = p.item;
     it.n_cur = (int)n;
@@ -286,6 +294,104 @@ inline int epipolarFilter2d(Context &ctx, const std::vector<FrameVsKeyframe> &fs
         err[b].resize(n);
     }
     if (verr) verr->swap(err);
+    return OV2_OK;
+}
+
+// ---- epipolar2d2dFiltering (:440-656) as one device chain on ov2_epipolar_filter: the join, the parallax gate, the 5-point search
+// over a table drawn on the device from `seed`, the 50 % rule, the removals and the Sampson pass over the 2-D keypoints.  The frame is
+// a FrameVsKeyframe (the current keypoints in the iteration order of pcurframe_->mapkps_, the keyframe's in any order) plus the
+// keyframe's bearings and Twc.  vremove: the lmids the reference hands to removeObsFromCurFrameById, in its order -- the RANSAC
+// outliers ascending in join order (:587-590), then the 2-D keypoints in array order (:646-648).  out.r.Twc_model (where
+// out.r.pose_from_model) is the pose of the UNREFINED model: the reference refines it first (OpenGV, not provided), so it is the
+// caller's decision whether to setTwc() with it.
+struct EpipolarFilterParams {
+    KfReqParams kf;                                           // K and stereo are read
+    int nransac_iter = 100;                                   // SlamParams: nransac_iter_, fransac_err_, mono_
+    float fransac_err = 3.f;
+    bool mono = false;
+    double threshold = 0.;                                    // 0: 2 (1 - cos(atan(fransac_err / focal))) from K, as the reference
+    double probability = 0.99;
+    int n_rows = 200;                                         // rows of the sample table per frame
+};
+struct EpipolarFilterInput {
+    FrameVsKeyframe f;
+    std::vector<double> kf_bv;                                // pkf's Keypoint::bv_, 3 doubles each, in the order of f.kf_lmid
+    double kf_Twc[7] = {0, 0, 0, 0, 0, 0, 1};                 // pkf->getTwc()
+    int nbkfs = 0;                                            // pmap_->nbkfs_
+    unsigned long long seed = 0;
+};
+struct EpipolarFilterOutput {
+    ov2_epifilter_result r;
+    std::vector<uint8_t> removed;
+    std::vector<int> pair_cur;
+    std::vector<float> err;
+    std::vector<int> vremove;
+};
+namespace detail {
+struct EpifPacked { FkfPacked fkf; std::vector<double> kf_bv; ov2_epifilter_item item; };
+inline bool packEpif(const EpipolarFilterInput &in, EpifPacked &p, EpipolarFilterOutput &out)
+{
+    const size_t n = in.f.cur_lmid.size();
+    if (!packFkf(in.f, p.fkf, &in.kf_bv, &p.kf_bv)) return false;          // one sort: ids, pixels and bearings together
+    static const double none_d[3] = {0., 0., 0.};
+    p.item.fkf = p.fkf.item;
+    p.item.kf_bv = p.kf_bv.empty() ? none_d : p.kf_bv.data();
+    p.item.kf_Twc = in.kf_Twc; p.item.nbkfs = in.nbkfs; p.item.seed = in.seed;
+    out.removed.assign(n ? n : 1, 0); out.pair_cur.assign(n ? n : 1, 0); out.err.assign(n ? n : 1, 0.f); out.vremove.clear();
+    out.r = ov2_epifilter_result{};
+    out.r.removed = out.removed.data(); out.r.pair_cur = out.pair_cur.data(); out.r.err = out.err.data();
+    return true;
+}
+inline ov2_epifilter_params epifParams(const EpipolarFilterParams &c)
+{
+    ov2_epifilter_params p{};
+    p.fkf = fkfParams(c.kf);
+    p.epi.max_iterations = c.nransac_iter; p.epi.probability = c.probability; p.epi.boptimize = 0;
+    if (c.threshold > 0.) p.epi.threshold = c.threshold;
+    else {                                                    // src/multi_view_geometry.cpp:640-641
+        const float focal = (float)((double)((float)c.kf.K[0] + (float)c.kf.K[1]) / 2.);
+        p.epi.threshold = 2.0 * (1.0 - std::cos(std::atan((double)(c.fransac_err / focal))));
+    }
+    p.fransac_err = c.fransac_err; p.mono = c.mono ? 1 : 0; p.n_rows = c.n_rows;
+    return p;
+}
+inline void finishEpif(const EpipolarFilterInput &in, EpipolarFilterOutput &out)
+{
+    const size_t n = in.f.cur_lmid.size();
+    out.removed.resize(n); out.err.resize(n);
+    out.pair_cur.resize((size_t)(out.r.m > 0 ? out.r.m : 0));
+    for (int idx : out.pair_cur) if (out.removed[(size_t)idx] == 1) out.vremove.push_back(in.f.cur_lmid[(size_t)idx]);
+    for (size_t i = 0; i < n; i++) if (out.removed[i] == 2) out.vremove.push_back(in.f.cur_lmid[i]);
+    out.r.removed = out.removed.data(); out.r.pair_cur = out.pair_cur.data(); out.r.err = out.err.data();
+}
+}  // namespace detail
+
+inline int epipolar2d2dFiltering(Context &ctx, const EpipolarFilterParams &params, const EpipolarFilterInput &in, EpipolarFilterOutput &out)
+{
+    detail::EpifPacked p;
+    if (!detail::packEpif(in, p, out)) return OV2_EINVAL;
+    const ov2_epifilter_params ep = detail::epifParams(params);
+    const int rc = ov2_epipolar_filter(ctx.get(), &ep, &p.item, &out.r);
+    if (rc != OV2_OK) return rc;
+    detail::finishEpif(in, out);
+    return OV2_OK;
+}
+// the frames of a lock-step batch in one chain
+inline int epipolar2d2dFiltering(Context &ctx, const EpipolarFilterParams &params, const std::vector<EpipolarFilterInput> &ins,
+                                 std::vector<EpipolarFilterOutput> &outs)
+{
+    std::vector<detail::EpifPacked> packed(ins.size());
+    std::vector<ov2_epifilter_item> items(ins.size());
+    std::vector<ov2_epifilter_result> rs(ins.size());
+    outs.assign(ins.size(), EpipolarFilterOutput());
+    for (size_t b = 0; b < ins.size(); b++) {
+        if (!detail::packEpif(ins[b], packed[b], outs[b])) return OV2_EINVAL;
+        items[b] = packed[b].item; rs[b] = outs[b].r;
+    }
+    const ov2_epifilter_params ep = detail::epifParams(params);
+    const int rc = ov2_epipolar_filter_batch(ctx.get(), &ep, (int)ins.size(), items.data(), rs.data());
+    if (rc != OV2_OK) return rc;
+    for (size_t b = 0; b < ins.size(); b++) { outs[b].r = rs[b]; detail::finishEpif(ins[b], outs[b]); }
     return OV2_OK;
 }
 

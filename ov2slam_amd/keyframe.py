@@ -4,6 +4,7 @@ of the C ABI (ov2_parallax / ov2_kf_decision / ov2_sampson_filter_2d and their b
     parallax            VisualFrontEnd::computeParallax (:1066-1141) in the arithmetic of each of its three call sites
     kf_decision         VisualFrontEnd::checkNewKfReq (:986-1061)
     sampson_filter_2d   the Sampson pass over the 2-D keypoints after the 5-point search (:610-652)
+    epipolar_filter     VisualFrontEnd::epipolar2d2dFiltering (:440-656) as one device chain (ov2_epipolar_filter, csrc/epifilter.hip)
 
 An item is a dict named like the fields of ov2_fkf_item (the counts follow from the array lengths): cur_lmid (n,), cur_px (n,2),
 cur_unpx (n,2), cur_bv (n,3), cur_is3d (n,), cur_Twc (7,), kf_lmid (m,) strictly ascending, kf_unpx (m,2), kf_Tcw (7,), and the
@@ -17,6 +18,8 @@ from . import _lib as L
 
 ALL, ONLY_2D, ONLY_3D = L.OV2_FKF_ALL, L.OV2_FKF_ONLY_2D, L.OV2_FKF_ONLY_3D
 AVG, MEDIAN, AVG_WIDE = L.OV2_FKF_AVG, L.OV2_FKF_MEDIAN, L.OV2_FKF_AVG_WIDE
+EPIF_TOO_FEW_KPS, EPIF_LOW_PARALLAX, EPIF_NO_MODEL, EPIF_DEGENERATE, EPIF_FILTERED = (
+    L.OV2_EPIF_TOO_FEW_KPS, L.OV2_EPIF_LOW_PARALLAX, L.OV2_EPIF_NO_MODEL, L.OV2_EPIF_DEGENERATE, L.OV2_EPIF_FILTERED)
 
 _FKF_FIELDS = (("cur_lmid", np.int32, C.c_int, 1), ("cur_px", np.float32, C.c_float, 2), ("cur_unpx", np.float32, C.c_float, 2),
                ("cur_bv", np.float64, C.c_double, 3), ("cur_is3d", np.uint8, C.c_uint8, 1), ("kf_lmid", np.int32, C.c_int, 1),
@@ -150,3 +153,91 @@ def sampson_filter_2d_batch(ctx, items, Fkfcur, fransac_err):
     for b, out in enumerate(outs):
         out["n_bad"] = R[b].n_bad
     return outs
+
+
+# ---- epipolar2d2dFiltering ----------------------------------------------------------------------------------------------------------
+def epifilter_params(fkf, *, max_iterations, threshold, fransac_err, mono, n_rows, probability=0.99, boptimize=False):
+    """ov2_epifilter_params: the ov2_fkf_params (or the dict of them; K and stereo are read), the search's nransac_iter_ and bearing
+    threshold, SlamParams::fransac_err_ (pixels) and mono_, and the rows of the sample table drawn per item"""
+    p = L.EpifilterParams()
+    p.fkf = _as_fkf_params(fkf)
+    p.epi.max_iterations, p.epi.threshold, p.epi.probability = int(max_iterations), float(threshold), float(probability)
+    p.epi.boptimize = int(bool(boptimize))
+    p.fransac_err, p.mono, p.n_rows = float(fransac_err), int(bool(mono)), int(n_rows)
+    return p
+
+
+def _as_epifilter_params(params):
+    if isinstance(params, L.EpifilterParams):
+        return params
+    return epifilter_params(params["fkf"], max_iterations=params["max_iterations"], threshold=params["threshold"],
+                            fransac_err=params["fransac_err"], mono=params["mono"], n_rows=params["n_rows"],
+                            probability=params.get("probability", 0.99), boptimize=params.get("boptimize", False))
+
+
+def _epifilter_item(item):
+    """(ov2_epifilter_item, the arrays it points into): the ov2_fkf_item dict plus kf_bv (m, 3), kf_Twc (7,), nbkfs, seed"""
+    s = L.EpifilterItem()
+    s.fkf, keep = _fkf_item(item)
+    a = item.get("kf_bv")
+    a = np.zeros(0, np.float64) if a is None else np.ascontiguousarray(a, np.float64)
+    if a.size != 3 * s.fkf.n_kf:
+        raise ValueError("frame versus keyframe: kf_bv has %d elements, not 3 per keypoint" % a.size)
+    keep["kf_bv"] = a
+    keep["kf_Twc"] = np.ascontiguousarray(item.get("kf_Twc", (0, 0, 0, 0, 0, 0, 1)), np.float64).reshape(7)
+    s.kf_bv, s.kf_Twc = (keep[k].ctypes.data_as(C.POINTER(C.c_double)) for k in ("kf_bv", "kf_Twc"))
+    s.nbkfs, s.seed = int(item.get("nbkfs", 0)), int(item.get("seed", 0)) & ((1 << 64) - 1)
+    return s, keep
+
+
+def _epifilter_result(n, n_rows, trace):
+    out = dict(removed=np.zeros(n, np.uint8), pair_cur=np.zeros(n, np.int32), err=np.zeros(n, np.float32))
+    r = L.EpifilterResult()
+    r.removed = out["removed"].ctypes.data_as(C.POINTER(C.c_uint8))
+    r.pair_cur = out["pair_cur"].ctypes.data_as(C.POINTER(C.c_int))
+    r.err = out["err"].ctypes.data_as(C.POINTER(C.c_float))
+    if trace:
+        out["samples"] = np.full((n_rows, 8), -1, np.int32)
+        r.trace_samples = out["samples"].ctypes.data_as(C.POINTER(C.c_int))
+    return r, out
+
+
+def _epifilter_dict(r, out):
+    out.update(action=r.action, m=r.m, epifrom3dkps=r.epifrom3dkps, do_optimize=r.do_optimize, nb3dkps=r.nb3dkps,
+               parallax=np.float32(r.parallax), status=r.status, best_row=r.best_row, iterations=r.iterations,
+               rows_consumed=r.rows_consumed, score=np.float64(r.score), n_inliers=r.n_inliers, n_outliers=r.n_outliers,
+               model=np.array(r.model[:], np.float64), F=np.array(r.F[:], np.float64), n_removed_ransac=r.n_removed_ransac,
+               n_removed_sampson=r.n_removed_sampson, pose_from_model=r.pose_from_model, Twc_model=np.array(r.Twc_model[:], np.float64))
+    out["pair_cur"] = out["pair_cur"][:max(r.m, 0)]
+    if "samples" in out and not (r.action >= EPIF_NO_MODEL and r.m >= 8):
+        out["samples"] = None                                      # no table was drawn
+    return out
+
+
+def epipolar_filter(ctx, params, item, *, trace_samples=False):
+    """ov2_epipolar_filter: epipolar2d2dFiltering of one frame.  Returns a dict named like ov2_epifilter_result: action (EPIF_*), m,
+    epifrom3dkps, do_optimize, nb3dkps, parallax (np.float32), the search's status / best_row / iterations / rows_consumed / score /
+    n_inliers / n_outliers / model (12,), F (9,), n_removed_ransac, n_removed_sampson, removed (n,) uint8 (0 kept, 1 RANSAC outlier,
+    2 Sampson pass), pair_cur (m,), err (n,) float32, pose_from_model, Twc_model (7,); with trace_samples the table the device drew
+    (n_rows, 8), None where the item did not search."""
+    p = _as_epifilter_params(params)
+    s, keep = _epifilter_item(item)
+    r, out = _epifilter_result(s.fkf.n_cur, p.n_rows, trace_samples)
+    L.check(ctx.lib.ov2_epipolar_filter(ctx.h, C.byref(p), C.byref(s), C.byref(r)))
+    return _epifilter_dict(r, out)
+
+
+def epipolar_filter_batch(ctx, params, items, *, trace_samples=False):
+    """ov2_epipolar_filter_batch: the frames of a lock-step batch in one chain (shared params); one dict per item"""
+    p = _as_epifilter_params(params)
+    items = list(items)
+    S = (L.EpifilterItem * max(1, len(items)))()
+    R = (L.EpifilterResult * max(1, len(items)))()
+    keep, outs = [], []
+    for b, it in enumerate(items):
+        S[b], k = _epifilter_item(it)
+        R[b], out = _epifilter_result(S[b].fkf.n_cur, p.n_rows, trace_samples)
+        keep.append(k)
+        outs.append(out)
+    L.check(ctx.lib.ov2_epipolar_filter_batch(ctx.h, C.byref(p), len(items), S, R))
+    return [_epifilter_dict(R[b], outs[b]) for b in range(len(items))]
