@@ -1967,7 +1967,8 @@ int  ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *pri
  * NOT in the step: epipolar2d2dFiltering between tracking and pose (the shipped parameter files set doepipolar: 1; a caller with it
  * on keeps the route of separate calls: tracking, ov2_epipolar_filter_batch -- the function as one device chain, built on a
  * caller-owned block so that it can go between the select and the pack later --, ov2_compute_pose_batch), checkNewKfReq, the motion
- * model, kltTrackingFromKF.
+ * model, kltTrackingFromKF.  (Since f18 the filter has a step of its own form: ov2_btracker_track_frame_epi_pose below puts that
+ * chain between the select and the pack; this step is unchanged and remains the one for doepipolar: 0.)
  *
  * OV2_EINVAL, checked on the host before anything is enqueued (the tracker stays where it was; the same frames can be passed
  * again): everything ov2_btracker_track_frame_map refuses; no calibration; NULL params / input / Twc_h / p3p_req_h / seed_h;
@@ -2003,6 +2004,88 @@ int  ov2_btracker_track_frame_pose(ov2_btracker *t, int n_active, const uint8_t 
  * when the item did not search).  slot_idx needs cfg.n_max ints of room, samples 4 * n_rows.  Reads the tracker's device buffers:
  * a diagnostic, not a per-frame call.  OV2_EINVAL before the first finished pose step. */
 int  ov2_btracker_last_pose_inputs(const ov2_btracker *t, int item, int *m, int *slot_idx, int *samples, int *n_rows_used);
+
+/* The lock-step step with epipolar2d2dFiltering AND the per-frame pose fused in (f18): what VisualFrontEnd::trackMono does per frame
+ * with doepipolar_ == 1 (src/visual_front_end.cpp:86-116: kltTracking, epipolar2d2dFiltering, computePose), one enqueue and one
+ * synchronisation (in _end), nothing visiting the host between tracking and pose.  A caller whose parameter file sets doepipolar: 1
+ * -- every shipped one -- takes this step in place of the three separate calls.
+ *
+ * The keyframe the filter joins against (pmap_->map_pkfs_.at(pcurframe_->kfid_)) is RESIDENT ON THE DEVICE: it changes only when a
+ * keyframe is created and does not travel with the steps.  ov2_btracker_set_keyframe gives item `item` its keyframe: kf_lmid
+ * (n_kf, strictly ascending), kf_unpx (2 per entry), kf_bv (3 per entry), kf_Twc[7] -- the keyframe fields of ov2_epifilter_item,
+ * validated on the host as ov2_epipolar_filter_batch validates them (NULL arrays with n_kf > 0, n_kf < 0, unsorted ids, bearings or
+ * a pose that are not finite), plus n_kf <= cfg.n_max.  kf_Tcw is kf_Twc inverted on the host by ov2_se3_inverse (below); a caller
+ * of the separate route that wants the step's bits passes that inverse as ov2_fkf_item.kf_Tcw.  The call copies on the context's
+ * stream into the tracker's epipolar block and returns when the copy is done; it keeps a host copy (the rare path below reads it).
+ * n_kf == 0 (kf_Twc may then be NULL) takes the keyframe away.  OV2_EINVAL between _begin and _end of any step.  An item without a
+ * keyframe behaves as n_kf = 0: empty join, NaN parallax, OV2_EPIF_NO_MODEL, nothing removed (the reference returns early on a null
+ * keyframe).  The block is allocated by the first set_keyframe or the first such step and freed with the tracker (about 119 B per
+ * point slot -- 98 in the filter's block, 8 for the pack's lists, 13 pinned --, 36 B per keyframe slot, 137 B per sample row, 0.9 KB
+ * per item); the context's scratch is not used.
+ *
+ * Per active item b, behind k_compute_keypoints on the context's stream:
+ *   k_pose_select   as f16.
+ *   k_epif_pack     (csrc/frameepi.hip) the slots i < n_h[b] with (status[i] & 3) == 1, in slot order -- the frame's keypoints after
+ *                   kltTracking removed the lost ones -- into the filter's current-frame arrays: lmid = input->lmid_h, unpx = the
+ *                   step's float unpx, bv = the step's bearing, is3d = the step's is3d_h; the item's record with nb3dkps = -1 (the
+ *                   chain counts the flags of the packed frame: pcurframe_->nb3dkps_ after the removals), nbkfs and seed from the
+ *                   input, cur_Twc = input->pose.Twc_h, the keyframe from the resident header.
+ *   the chain       of ov2_epipolar_filter, its five launches untouched.
+ *   k_epif_apply    removed (0 / 1 / 2), err and pair_cur from packed space to SLOT SPACE, and the select byte of every removed slot
+ *                   cleared: the reference erases the RANSAC outliers from the frame before computePose reads it (:587-590; the
+ *                   Sampson removals are 2-D keypoints and never were in the pose set).
+ *   k_pose_pack, computePose's chain, k_pose_unpack   as f16: the pose set, m, the m >= 4 test and P3P's table are those of the
+ *                   frame AFTER the filter.
+ * epi_results[b] is, bit for bit, what ov2_epipolar_filter returns for those inputs, EXCEPT that removed holds n_h[b] bytes in slot
+ * space, and err (n_h[b] floats) and pair_cur (pair_cur[k]: the slot of match k), where non-NULL, are in slot space too.
+ * trace_samples must be NULL (ov2_btracker_last_epi_inputs fetches the table).  pose_results[b] is what ov2_compute_pose returns on
+ * the filtered set, removed in slot space as f16.  status_h and out_xy_h are the tracking's, untouched by the filter.
+ * On the first frame of a tracker and on a step where nothing is tracked no chain runs: the epipolar record is action =
+ * OV2_EPIF_TOO_FEW_KPS with every other field (and removed, err) 0, the pose record is f16's.
+ *
+ * The 33 % rule stays on the host as in f16: for an item where it fires, _end discards BOTH device results, rebuilds the frame from
+ * the final status / unpx / bv and runs ov2_epipolar_filter_batch (with the keyframe's host copy) and then ov2_compute_pose_batch
+ * (do_p3p = p3p_req = 1) over just those items.
+ * THE ONE DEVIATION from the reference: the mono branch do_optimize (:594).  pose_from_model and Twc_model are reported from the
+ * UNREFINED model as ov2_epipolar_filter reports them, and the pose chain starts from the caller's Twc_h, never from Twc_model:
+ * OpenGV's non-linear refinement has no device form.  Everything else is the reference's per-frame sequence.
+ * ov2_btracker_track_frame_end on such a step finishes the tracking half and drops both results.
+ *
+ * OV2_EINVAL, checked on the host before anything is enqueued: everything ov2_btracker_track_frame_pose_begin refuses; whatever
+ * ov2_epipolar_filter_batch refuses in params->epi (boptimize != 0 included); NULL lmid_h / nbkfs_h / epi_seed_h; epi.n_rows
+ * outside [0, OV2_EPI_MAX_ROWS]; cfg.n_max > OV2_FKF_MAX_POINTS.  In _end: a NULL result array, a NULL `removed` where n_h[b] > 0, a
+ * non-NULL trace_samples, a step that was not begun with _epi_pose_begin. */
+typedef struct {
+    ov2_frame_pose_params pose;  /* as f16                                                                                   */
+    ov2_epifilter_params  epi;   /* as ov2_epipolar_filter_batch; epi.epi.boptimize must be 0                                */
+} ov2_frame_epi_pose_params;
+typedef struct {
+    ov2_frame_pose_input pose;   /* as f16                                                                                   */
+    const int *lmid_h;           /* n_max per item: Keypoint::lmid_ of each slot                                             */
+    const int *nbkfs_h;          /* 1 per item: pmap_->nbkfs_                                                                */
+    const unsigned long long *epi_seed_h;   /* 1 per item: seed of the 5-point sample table                                  */
+} ov2_frame_epi_pose_input;
+int  ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf_lmid, const float *kf_unpx, const double *kf_bv,
+                               const double *kf_Twc);
+int  ov2_btracker_track_frame_epi_pose_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride,
+                                             const float *kps_xy_h, const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h,
+                                             const int *n_h, int klt_use_prior, const ov2_frame_epi_pose_params *params,
+                                             const ov2_frame_epi_pose_input *input);
+int  ov2_btracker_track_frame_epi_pose_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req,
+                                           ov2_epifilter_result *epi_results, ov2_pose_result *pose_results);
+int  ov2_btracker_track_frame_epi_pose(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                       const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h,
+                                       int klt_use_prior, const ov2_frame_epi_pose_params *params,
+                                       const ov2_frame_epi_pose_input *input, float *out_xy_h, uint8_t *status_h, int *p3p_req,
+                                       ov2_epifilter_result *epi_results, ov2_pose_result *pose_results);
+/* What the last such step fed the filter for `item` (for an item the rule re-ran: what the second run used): *n_cur and the slot of
+ * each keypoint of the packed frame (n_cur ints; slot_idx may be NULL, else cfg.n_max ints of room), *m matches, the sample table
+ * the search used (8 * *n_rows_used ints; samples may be NULL, else 8 * epi.n_rows ints of room; 0 rows when the item did not
+ * search).  Reads the tracker's device buffers: a diagnostic, not a per-frame call.  OV2_EINVAL before the first finished step. */
+int  ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, int *slot_idx, int *m, int *samples, int *n_rows_used);
+/* out = the inverse of the transform T, both [tx ty tz qx qy qz qw]: the conjugate quaternion and minus the rotated translation, the
+ * rotation matrix of the conjugate written out, each sum of three terms serial.  Host arithmetic, no context. */
+int  ov2_se3_inverse(const double T[7], double out[7]);
 
 #ifdef __cplusplus
 }

@@ -424,6 +424,17 @@ class EpifilterResult(C.Structure):
                 ("pose_from_model", C.c_int), ("Twc_model", C.c_double * 7), ("trace_samples", C.POINTER(C.c_int))]
 
 
+class FrameEpiPoseParams(C.Structure):
+    """ov2_frame_epi_pose_params"""
+    _fields_ = [("pose", FramePoseParams), ("epi", EpifilterParams)]
+
+
+class FrameEpiPoseInput(C.Structure):
+    """ov2_frame_epi_pose_input"""
+    _fields_ = [("pose", FramePoseInput), ("lmid_h", C.POINTER(C.c_int)), ("nbkfs_h", C.POINTER(C.c_int)),
+                ("epi_seed_h", C.POINTER(C.c_ulonglong))]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -618,6 +629,15 @@ SIGNATURES = {
     "ov2_btracker_track_frame_pose": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FramePoseParams),
                                            C.POINTER(FramePoseInput), _vp, _vp, _vp, C.POINTER(PoseResult)]),
     "ov2_btracker_last_pose_inputs": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "ov2_btracker_set_keyframe": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "ov2_btracker_track_frame_epi_pose_begin": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FrameEpiPoseParams),
+                                                     C.POINTER(FrameEpiPoseInput)]),
+    "ov2_btracker_track_frame_epi_pose_end": (_i, [_vp, _vp, _vp, _vp, C.POINTER(EpifilterResult), C.POINTER(PoseResult)]),
+    "ov2_btracker_track_frame_epi_pose": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(FrameEpiPoseParams),
+                                               C.POINTER(FrameEpiPoseInput), _vp, _vp, _vp, C.POINTER(EpifilterResult),
+                                               C.POINTER(PoseResult)]),
+    "ov2_btracker_last_epi_inputs": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "ov2_se3_inverse": (_i, [_vp, _vp]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

@@ -126,11 +126,13 @@ __global__ __launch_bounds__(256) void k_pose_unpack(FpArgs a)
 
 // The pose half of a lock-step step behind k_compute_keypoints on `s`.  blk: the tracker's point block (n at o_n, status, unpx, bv),
 // map: its map block (wpt, is3d), in / out: the step's pose inputs and results (the caller's pointers into its pinned or mirrored
-// block), work: [PoseLayout L][sel 1][slot 4][rank 4 per slot].
+// block), work: [PoseLayout L][sel 1][slot 4][rank 4 per slot].  hook (frameepi.hip, or none): what a step enqueues between the
+// select and the pack -- it may clear select bytes; without one the launches are the four below.
 int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search,
                           const int *n_d, const uint8_t *status_d, const float *unpx_d, const double *bv_d, const double *wpt_d,
                           const uint8_t *is3d_d, const double *Twc_d, const int *scale_d, const uint8_t *flags_d,
-                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d)
+                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d,
+                          int (*hook)(hipStream_t, uint8_t *, void *), void *hook_arg)
 {
     const size_t NP = L.pl.NP;
     uint8_t *x = work + L.total;
@@ -146,6 +148,7 @@ int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const Po
     const dim3 slots((L.n_max + 255) / 256, n_active);
     hipLaunchKernelGGL(k_pose_select, slots, dim3(256), 0, s, a);
     OV2_HIP_CHECK(hipGetLastError());
+    if (hook) { const int rch = hook(s, a.sel, hook_arg);  if (rch != OV2_OK) return rch; }
     hipLaunchKernelGGL(k_pose_pack, dim3(n_active), dim3(64), 0, s, a);
     OV2_HIP_CHECK(hipGetLastError());
     const int rc = pose_chain_enqueue(s, params, L, work, Twc_d, out_d, n_active, search);

@@ -19,9 +19,14 @@
 // ov2_btracker_track_frame_pose puts computePose behind the step's kernels on the context's stream (framepose.hip: the pose set and
 // P3P's sample table; pose_dev.hpp: the chain of pnp.hip on a block at capacity): tracking results and the per-frame pose with the
 // one synchronisation, byte-equal to ov2_btracker_track_frame_map followed by ov2_compute_pose_batch (tests/test_gpu_framepose.py).
+// ov2_btracker_track_frame_epi_pose is that step with epipolar2d2dFiltering between the select and the pack (frameepi.hip: the frame
+// packed into the epipolar block, the chain of epifilter.hip on it, the removals applied to the select bytes), against a keyframe
+// that ov2_btracker_set_keyframe keeps on the device: trackMono's per-frame sequence with doepipolar_ == 1 in one enqueue, byte-equal
+// to the three separate calls (tests/test_gpu_frameepi.py).
 #include "common.hpp"
 #include "keypoint_dev.hpp"
 #include "pose_dev.hpp"
+#include "frameepi_dev.hpp"
 #include <cmath>
 #include <deque>
 #include <new>
@@ -37,7 +42,8 @@ int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double
 int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search,
                           const int *n_d, const uint8_t *status_d, const float *unpx_d, const double *bv_d, const double *wpt_d,
                           const uint8_t *is3d_d, const double *Twc_d, const int *scale_d, const uint8_t *flags_d,
-                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d);
+                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d,
+                          ov2_fp_hook hook = nullptr, void *hook_arg = nullptr);
 size_t ov2_frame_pose_work_bytes(const PoseLayout &L);
 size_t ov2_frame_pose_slot_offset(const PoseLayout &L);
 
@@ -102,6 +108,26 @@ struct ov2_btracker {
     std::vector<int> lp_m, lp_rows;
     std::vector<std::vector<int>> lp_slot, lp_samples;
     std::vector<uint8_t> lp_host;
+    // ov2_btracker_track_frame_epi_pose / ov2_btracker_set_keyframe: the epipolar side, allocated by the first of either.
+    //   depi   the filter's block (EpifLayout at capacity: batch x n_max slots, batch x n_rows rows; device only).  Its inputs
+    //          [0, o_up) do not depend on n_rows, so the resident keyframe arrays stay where they are when a step asks for more rows
+    //          and the block is grown (they are then copied again from kf_host).
+    //   dfx    [FeKfHdr 120 per item][slot 4][rank 4 per slot] (device only)
+    //   hepi   pinned + mapped or mirrored like the keypoint block: [lmid 4 per slot][nbkfs 4][seed 8 per item] go up;
+    //          [EpifOut 304][n_cur 4 per item][removed 1][err 4][pair 4 per slot] come down
+    uint8_t *depi = nullptr, *dfx = nullptr, *hepi = nullptr, *depi_io = nullptr, *kepi = nullptr;
+    size_t depi_bytes = 0, x_slot = 0, x_rank = 0, e_lm = 0, e_nk = 0, e_sd = 0, e_in = 0, e_out = 0, e_nc = 0, e_rm = 0, e_er = 0, e_pc = 0,
+           epi_bytes = 0;
+    EpifLayout eL0;                                   // the layout with no rows: where the keyframe arrays lie
+    std::vector<uint8_t> kf_host;                     // host copy of the block's [o_kl, o_up)
+    std::vector<FeKfHdr> kf_hdr;
+    FeStep fe;                                        // the arguments of the step being enqueued
+    // ov2_btracker_last_epi_inputs: as lp_* above
+    bool le_on = false, le_chain = false;
+    EpifLayout le_L;
+    std::vector<int> le_ncur, le_m, le_rows;
+    std::vector<std::vector<int>> le_slot, le_samples;
+    std::vector<uint8_t> le_host;
     // keyframe detection: device mirrors of the items' current keypoints and of the detector's output, pinned staging
     uint8_t *d_det = nullptr, *h_det = nullptr; size_t det_in_bytes = 0;
     float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
@@ -110,7 +136,10 @@ struct ov2_btracker {
     struct Pending { bool on = false, tracked = false; int n_active = 0, use_prior = 0; const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n;
                      // a pose step (ov2_btracker_track_frame_pose_begin): its settings and the per-item inputs _end needs again
                      bool pose = false; ov2_frame_pose_params pp; PoseLayout L; std::vector<double> Twc; std::vector<uint8_t> req;
-                     std::vector<unsigned long long> seed; } pend;
+                     std::vector<unsigned long long> seed;
+                     // an epipolar + pose step (ov2_btracker_track_frame_epi_pose_begin): the filter's settings (its per-item inputs
+                     // stay in hepi, which the device only reads)
+                     bool epi = false; ov2_epifilter_params ep; EpifLayout eL; } pend;
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
 };
@@ -143,6 +172,10 @@ static void btracker_free(ov2_btracker *t)
     if (t->hpose) (void)hipHostFree(t->hpose);
     if (t->dpose) (void)hipFree(t->dpose);
     if (t->dwork) (void)hipFree(t->dwork);
+    if (t->depi) (void)hipFree(t->depi);
+    if (t->dfx) (void)hipFree(t->dfx);
+    if (t->hepi) (void)hipHostFree(t->hepi);
+    if (t->depi_io) (void)hipFree(t->depi_io);
     if (t->h_det) (void)hipHostFree(t->h_det);
     if (t->d_det) (void)hipFree(t->d_det);
     if (t->h_out) (void)hipHostFree(t->h_out);
@@ -212,14 +245,39 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
         const uint8_t *m = t->kmap;
         bool search = pose->pp.dop3p != 0;
         for (int b = 0; b < n; b++) search = search || pose->req[(size_t)b];
+        ov2_fp_hook hook = nullptr;
+        if (pose->epi) {                                                // the filter between the select and the pack (frameepi.hip)
+            if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->depi_io, t->hepi, t->e_in, hipMemcpyHostToDevice, ctx->stream));
+            uint8_t *e = t->kepi, *d = t->depi;
+            const EpifLayout &EL = pose->eL;
+            FeStep &fe = t->fe;
+            FeArgs &a = fe.a;
+            a.n_dev = (const int *)(k + t->o_n); a.status = k + t->o_st; a.is3d = m + t->m_3d;
+            a.unpx = (const float2 *)(k + t->o_unpx); a.bv = (const double *)(k + t->o_bv);
+            a.lmid = (const int *)(e + t->e_lm); a.nbkfs = (const int *)(e + t->e_nk); a.seed = (const unsigned long long *)(e + t->e_sd);
+            a.Twc = (const double *)(q + t->q_T); a.hdr = (const FeKfHdr *)t->dfx;
+            a.items = (EpifItem *)(d + EL.o_it); a.c_lmid = (int *)(d + EL.o_lm); a.c_unpx = (float2 *)(d + EL.o_un);
+            a.c_bv = (double *)(d + EL.o_bv); a.c_is3d = d + EL.o_3d;
+            a.slot = (int *)(t->dfx + t->x_slot); a.rank = (int *)(t->dfx + t->x_rank);
+            a.out = (const EpifOut *)(d + EL.o_out); a.removed = d + EL.o_rm; a.err = (const float *)(d + EL.o_er);
+            a.pair_cur = (const int *)(d + EL.o_pc);
+            a.sel = nullptr;
+            a.out_io = (EpifOut *)(e + t->e_out); a.ncur_io = (int *)(e + t->e_nc); a.removed_io = e + t->e_rm;
+            a.err_io = (float *)(e + t->e_er); a.pair_io = (int *)(e + t->e_pc);
+            a.n_max = c.n_max; a.n_rows = pose->ep.n_rows;
+            fe.params = &pose->ep; fe.L = EL; fe.block = d; fe.n_active = n;
+            hook = ov2_frame_epi_hook;
+        }
         rc = ov2_launch_frame_pose(ctx->stream, &pose->pp.pose, pose->L, n, search, (const int *)(k + t->o_n), k + t->o_st,
                                    (const float *)(k + t->o_unpx), (const double *)(k + t->o_bv), (const double *)(m + t->m_w), m + t->m_3d,
                                    (const double *)(q + t->q_T), (const int *)(q + t->q_sc), q + t->q_fl,
                                    (const unsigned long long *)(q + t->q_seed), t->dwork, (PoseOut *)(q + t->q_out), (int *)(q + t->q_ms),
-                                   q + t->q_rm);
+                                   q + t->q_rm, hook, &t->fe);
         if (rc != OV2_OK) return rc;
         if (!t->zero_copy)
             OV2_HIP_CHECK(hipMemcpyAsync(t->hpose + t->q_out, t->dpose + t->q_out, t->pose_bytes - t->q_out, hipMemcpyDeviceToHost, ctx->stream));
+        if (!t->zero_copy && pose->epi)
+            OV2_HIP_CHECK(hipMemcpyAsync(t->hepi + t->e_out, t->depi_io + t->e_out, t->epi_bytes - t->e_out, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (!t->zero_copy)
         OV2_HIP_CHECK(hipMemcpyAsync(t->hblk + t->o_out, t->dblk + t->o_out, t->blk_bytes - t->o_out, hipMemcpyDeviceToHost, ctx->stream));
@@ -378,6 +436,81 @@ static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params
         if (in->scale_h) memcpy(sc, in->scale_h + o, 4 * n); else memset(sc, 0, 4 * n);
     }
     return OV2_OK;
+}
+
+// what an epipolar + pose step refuses beyond the pose step's checks; *L: the filter's layout at capacity
+static int check_epi(const ov2_btracker *t, const ov2_frame_epi_pose_params *pp, const ov2_frame_epi_pose_input *in, EpifLayout *L)
+{
+    OV2_REQUIRE(pp && in, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
+    OV2_REQUIRE(in->lmid_h && in->nbkfs_h && in->epi_seed_h, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL lmid_h / nbkfs_h / epi_seed_h");
+    const int rc = epif_check_params(&pp->epi);  if (rc) return rc;
+    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    return epif_layout_capacity(t->batch, t->cfg.n_max, pp->epi.n_rows, L);
+}
+
+// The epipolar side's buffers (allocated by the first call) and the filter's block, grown to hold layout L.  The keyframe arrays lie
+// in the block's input section, whose offsets do not depend on the rows: a grown block gets them again from the host copy.
+static int ensure_epi(ov2_btracker *t, const EpifLayout *L)
+{
+    const size_t nm = (size_t)t->cfg.n_max, B = (size_t)t->batch, slots = nm * B;
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    if (!t->hepi) {
+        EpifLayout L0;
+        const int rc = epif_layout_capacity(t->batch, t->cfg.n_max, 0, &L0);  if (rc) return rc;
+        t->e_lm = 0; t->e_nk = up256(4 * slots); t->e_sd = up256(t->e_nk + 4 * B); t->e_in = up256(t->e_sd + 8 * B);
+        t->e_out = t->e_in; t->e_nc = up256(t->e_out + sizeof(EpifOut) * B); t->e_rm = up256(t->e_nc + 4 * B);
+        t->e_er = up256(t->e_rm + slots); t->e_pc = up256(t->e_er + 4 * slots); t->epi_bytes = up256(t->e_pc + 4 * slots);
+        t->x_slot = up256(sizeof(FeKfHdr) * B); t->x_rank = t->x_slot + 4 * slots;
+        const size_t fx_bytes = t->x_rank + 4 * slots;
+        uint8_t *h = nullptr, *d = nullptr, *fx = nullptr;
+        hipError_t e = hipHostMalloc((void **)&h, t->epi_bytes, hipHostMallocMapped);
+        if (e == hipSuccess && !t->zero_copy) e = hipMalloc((void **)&d, t->epi_bytes);
+        void *alias = d;
+        if (e == hipSuccess && t->zero_copy) e = hipHostGetDevicePointer(&alias, h, 0);
+        if (e == hipSuccess) e = hipMalloc((void **)&fx, fx_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(fx, 0, fx_bytes, t->ctx->stream);       // no item has a keyframe yet
+        if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+        if (e != hipSuccess || !alias) {
+            if (h) (void)hipHostFree(h);
+            if (d) (void)hipFree(d);
+            if (fx) (void)hipFree(fx);
+            (void)hipGetLastError();
+            ov2_set_error("ov2_btracker_track_frame_epi_pose: %s", hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        memset(h, 0, t->epi_bytes);
+        t->hepi = h; t->depi_io = d; t->kepi = (uint8_t *)alias; t->dfx = fx;
+        t->eL0 = L0;
+        t->kf_host.assign(L0.o_up - L0.o_kl, 0);
+        t->kf_hdr.assign(B, FeKfHdr());
+    }
+    const size_t need = L ? L->total : t->eL0.total;
+    if (!t->depi || need > t->depi_bytes) {
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (the previous step's chain has long finished: _end waited for it)
+        uint8_t *nd = nullptr;
+        hipError_t e = hipMalloc((void **)&nd, need);
+        if (e == hipSuccess) e = hipMemset(nd, 0, need);
+        if (e == hipSuccess) e = hipMemcpy(nd + t->eL0.o_kl, t->kf_host.data(), t->kf_host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (nd) (void)hipFree(nd);
+            (void)hipGetLastError();
+            ov2_set_error("ov2_btracker_track_frame_epi_pose: %s", hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        if (t->depi) (void)hipFree(t->depi);
+        t->depi = nd; t->depi_bytes = need; t->le_on = false;           // the lists of the last step go with the block
+    }
+    return OV2_OK;
+}
+
+// the filter's inputs of a step into hepi
+static void stage_epi(ov2_btracker *t, int n_active, const ov2_frame_epi_pose_input *in, const int *n_h)
+{
+    const size_t nm = (size_t)t->cfg.n_max;
+    for (int b = 0; b < n_active; b++)
+        if (n_h[b] > 0) memcpy(t->hepi + t->e_lm + 4 * nm * (size_t)b, in->lmid_h + nm * (size_t)b, 4 * (size_t)n_h[b]);
+    memcpy(t->hepi + t->e_nk, in->nbkfs_h, 4 * (size_t)n_active);
+    memcpy(t->hepi + t->e_sd, in->epi_seed_h, 8 * (size_t)n_active);
 }
 
 static void stage_points(ov2_btracker *t, int n_active, const float *kps, const float *pri, const uint8_t *has_prior, const int *n_h, int use_prior)
@@ -653,7 +786,8 @@ int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
 static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
                              const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior, bool map,
                              const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, bool pose = false,
-                             const ov2_frame_pose_params *pp = nullptr, const ov2_frame_pose_input *pin = nullptr)
+                             const ov2_frame_pose_params *pp = nullptr, const ov2_frame_pose_input *pin = nullptr, bool epi = false,
+                             const ov2_frame_epi_pose_params *epp = nullptr, const ov2_frame_epi_pose_input *ein = nullptr)
 {
     OV2_REQUIRE(t && img_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
@@ -671,7 +805,13 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
     if (map) OV2_REQUIRE(n_total == 0 || (kps_xy_h && wpt_h && is3d_h && Tcw_h && n_h), OV2_EINVAL, "NULL point buffer");
     else OV2_REQUIRE(n_total == 0 || (kps_xy_h && prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
     PoseLayout poseL;
+    EpifLayout epiL;
+    if (epi) {                                                           // (pp / pin: the pose halves of epp / ein, or NULL with them)
+        OV2_REQUIRE(epp && ein, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
+        pp = &epp->pose; pin = &ein->pose;
+    }
     if (pose) { const int rcp = check_pose(t, n_active, wpt_h, is3d_h, n_h, pp, pin, &poseL);  if (rcp != OV2_OK) return rcp; }
+    if (epi) { const int rce = check_epi(t, epp, ein, &epiL);  if (rce != OV2_OK) return rce; }
     for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = t->last_pn[(size_t)b] = 0;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
@@ -703,6 +843,8 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
         P.req.assign(pin->p3p_req_h, pin->p3p_req_h + n_active);
         P.seed.assign(pin->seed_h, pin->seed_h + n_active);
     }
+    P.epi = epi;
+    if (epi) { P.ep = epp->epi; P.eL = epiL; }
     if (t->frames == 0 || n_total == 0) {
         // first frame (trackMono returns right after preprocessImage) or nothing to track anywhere
         rc = preprocess();
@@ -719,6 +861,11 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
     if (pose) {
         rc = stage_pose(t, n_active, pp, pin, n_h, poseL);
         if (rc != OV2_OK) { t->cur = old_cur; return rc; }
+    }
+    if (epi) {
+        rc = ensure_epi(t, &epiL);
+        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
+        stage_epi(t, n_active, ein, n_h);
     }
     stage_points(t, n_active, kps_xy_h, map ? nullptr : prior_xy_h, has_prior_h, n_h, klt_use_prior);
     rc = preprocess();
@@ -760,7 +907,9 @@ static void pose_store(ov2_pose_result &r, const PoseOut &o)
 
 // The items where the 33 % rule fired (`redo`), after their retry: the pose set from the final status, the step's unpx / bv as the
 // retry left them, a table drawn from the new m, and ov2_compute_pose_batch over just those items with do_p3p = p3p_req = 1
-static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_t *status_h, ov2_pose_result *results)
+// excl (or NULL): one byte per slot, laid out like status_h -- a slot the filter removed is not in the pose set
+static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_t *status_h, ov2_pose_result *results,
+                     const uint8_t *excl = nullptr)
 {
     const ov2_btracker::Pending &P = t->pend;
     const size_t nm = (size_t)t->cfg.n_max, R = redo.size();
@@ -780,7 +929,7 @@ static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_
         std::vector<int> &slot = t->lp_slot[(size_t)b];
         slot.clear();
         for (int i = 0; i < n; i++)
-            if ((status_h[o + i] & 3) == 1 && d3[i]) {
+            if ((status_h[o + i] & 3) == 1 && d3[i] && !(excl && excl[o + i])) {
                 slot.push_back(i);
                 unpx[k].push_back((double)un[2 * i]); unpx[k].push_back((double)un[2 * i + 1]);
                 for (int c = 0; c < 3; c++) { wpt[k].push_back(w[3 * i + c]); bv[k].push_back(bvs[3 * i + c]); }
@@ -816,9 +965,106 @@ static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_
     return OV2_OK;
 }
 
+// the record of the chain into the caller's result (its four pointers are the caller's and stay), as ov2_epipolar_filter_batch does
+static void epi_store(ov2_epifilter_result &r, const EpifOut &o)
+{
+    r.action = o.action; r.m = o.m; r.epifrom3dkps = o.epifrom3dkps; r.do_optimize = o.do_optimize; r.nb3dkps = o.nb3dkps;
+    r.parallax = o.parallax; r.status = o.status; r.best_row = o.best_row; r.iterations = o.iterations;
+    r.rows_consumed = o.rows_consumed; r.score = o.score; r.n_inliers = o.n_inliers; r.n_outliers = o.n_outliers;
+    memcpy(r.model, o.model, sizeof o.model); memcpy(r.F, o.F, sizeof o.F); memcpy(r.Twc_model, o.Twc_model, sizeof o.Twc_model);
+    r.n_removed_ransac = o.n_removed_ransac; r.n_removed_sampson = o.n_removed_sampson; r.pose_from_model = o.pose_from_model;
+}
+
+// rows of the table the filter's search used: it ran (the action is past the two early returns) over at least eight matches
+static inline int epi_rows_used(int action, int m, int n_rows) { return action >= OV2_EPIF_NO_MODEL && m >= 8 ? n_rows : 0; }
+
+// The items where the 33 % rule fired, after their retry: the frame from the final status, the step's unpx / bv as the retry left them,
+// ov2_epipolar_filter_batch against the keyframes' host copy over just those items, the results to slot space; excl (laid out like
+// status_h) gets a byte per slot the filter removed, for the pose set of pose_redo.
+static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *out_xy_h, const uint8_t *status_h,
+                    ov2_epifilter_result *results, std::vector<uint8_t> &excl)
+{
+    const ov2_btracker::Pending &P = t->pend;
+    const size_t nm = (size_t)t->cfg.n_max, R = redo.size();
+    const int n_rows = P.ep.n_rows;
+    const EpifLayout &L0 = t->eL0;
+    const uint8_t *kh = t->kf_host.data();
+    const int *lmid_h = (const int *)(t->hepi + t->e_lm), *nbkfs_h = (const int *)(t->hepi + t->e_nk);    // as the step staged them
+    const unsigned long long *seed_h = (const unsigned long long *)(t->hepi + t->e_sd);
+    std::vector<std::vector<int>> lmid(R), pair(R);
+    std::vector<std::vector<float>> px(R), unpx(R), err(R);
+    std::vector<std::vector<double>> bv(R);
+    std::vector<std::vector<uint8_t>> d3(R), rm(R);
+    std::vector<ov2_epifilter_item> items(R);
+    std::vector<ov2_epifilter_result> rs(R);
+    excl.assign(nm * (size_t)P.n_active, 0);
+    for (size_t k = 0; k < R; k++) {
+        const int b = redo[k];
+        const size_t o = (size_t)b * nm;
+        const int n = P.n[(size_t)b];
+        const float *un = (const float *)(t->hblk + t->o_unpx) + 2 * o;
+        const double *bvs = (const double *)(t->hblk + t->o_bv) + 3 * o;
+        const uint8_t *f3 = t->hmap + t->m_3d + o;
+        std::vector<int> &slot = t->le_slot[(size_t)b];
+        slot.clear();
+        for (int i = 0; i < n; i++)
+            if ((status_h[o + i] & 3) == 1) {
+                slot.push_back(i);
+                lmid[k].push_back(lmid_h[o + i]);
+                px[k].push_back(out_xy_h[2 * (o + i)]); px[k].push_back(out_xy_h[2 * (o + i) + 1]);
+                unpx[k].push_back(un[2 * i]); unpx[k].push_back(un[2 * i + 1]);
+                for (int c = 0; c < 3; c++) bv[k].push_back(bvs[3 * i + c]);
+                d3[k].push_back(f3[i]);
+            }
+        const int nc = (int)slot.size();
+        const size_t room = (size_t)(nc > 0 ? nc : 1);
+        lmid[k].resize(room); px[k].resize(2 * room); unpx[k].resize(2 * room); bv[k].resize(3 * room); d3[k].resize(room);
+        rm[k].assign(room, 0); pair[k].assign(room, 0); err[k].assign(room, 0.f);
+        std::vector<int> &tab = t->le_samples[(size_t)b];
+        tab.assign(8 * (size_t)(n_rows > 0 ? n_rows : 1), -1);
+        const FeKfHdr &h = t->kf_hdr[(size_t)b];
+        ov2_epifilter_item &q = items[k];
+        memset(&q, 0, sizeof q);
+        q.fkf.n_cur = nc; q.fkf.cur_lmid = lmid[k].data(); q.fkf.cur_px = px[k].data(); q.fkf.cur_unpx = unpx[k].data();
+        q.fkf.cur_bv = bv[k].data(); q.fkf.cur_is3d = d3[k].data(); q.fkf.cur_Twc = P.Twc.data() + 7 * (size_t)b;
+        q.fkf.n_kf = h.n_kf; q.fkf.kf_lmid = (const int *)kh + o; q.fkf.kf_unpx = (const float *)(kh + (L0.o_ku - L0.o_kl)) + 2 * o;
+        q.fkf.kf_Tcw = h.kf_Tcw; q.fkf.noccupcells = -1; q.fkf.nb3dkps = -1;
+        q.kf_bv = (const double *)(kh + (L0.o_kb - L0.o_kl)) + 3 * o; q.kf_Twc = h.kf_Twc; q.nbkfs = nbkfs_h[b]; q.seed = seed_h[b];
+        ov2_epifilter_result &r = rs[k];
+        memset(&r, 0, sizeof r);
+        r.removed = rm[k].data(); r.pair_cur = pair[k].data(); r.err = err[k].data(); r.trace_samples = n_rows > 0 ? tab.data() : nullptr;
+    }
+    const int rc = ov2_epipolar_filter_batch(t->ctx, &P.ep, (int)R, items.data(), rs.data());
+    if (rc != OV2_OK) return rc;
+    for (size_t k = 0; k < R; k++) {
+        const int b = redo[k];
+        const size_t o = (size_t)b * nm;
+        const int n = P.n[(size_t)b];
+        const std::vector<int> &slot = t->le_slot[(size_t)b];
+        ov2_epifilter_result &r = results[b], keep = results[b];
+        r = rs[k];
+        r.removed = keep.removed; r.pair_cur = keep.pair_cur; r.err = keep.err; r.trace_samples = nullptr;
+        if (n > 0) memset(r.removed, 0, (size_t)n);
+        if (r.err && n > 0) memset(r.err, 0, 4 * (size_t)n);
+        for (size_t j = 0; j < slot.size(); j++) {
+            r.removed[slot[j]] = rm[k][j];
+            if (r.err) r.err[slot[j]] = err[k][j];
+            if (rm[k][j]) excl[o + (size_t)slot[j]] = 1;
+        }
+        if (r.pair_cur)
+            for (int j = 0; j < r.m && j < (int)slot.size(); j++)
+                r.pair_cur[j] = (unsigned)pair[k][(size_t)j] < slot.size() ? slot[(size_t)pair[k][(size_t)j]] : -1;
+        t->le_ncur[(size_t)b] = (int)slot.size(); t->le_m[(size_t)b] = r.m;
+        t->le_rows[(size_t)b] = epi_rows_used(r.action, r.m, n_rows); t->le_host[(size_t)b] = 1;
+    }
+    return OV2_OK;
+}
+
 // both forms of the step's second half.  results != NULL: the step was begun with ov2_btracker_track_frame_pose_begin and its
 // poses are wanted; NULL: the tracking half only (a pose the step computed is dropped)
-static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results)
+// eres != NULL (with results): the step was begun with ov2_btracker_track_frame_epi_pose_begin and the filter's records are wanted too
+static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results,
+                           ov2_epifilter_result *eres = nullptr)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     ov2_btracker::Pending &P = t->pend;
@@ -827,6 +1073,13 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
     if (results)
         for (int b = 0; b < P.n_active; b++)
             OV2_REQUIRE(P.n[(size_t)b] == 0 || results[b].removed, OV2_EINVAL, "NULL result buffer (removed)");
+    OV2_REQUIRE(!eres || P.epi, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose_end: the step was not begun with ov2_btracker_track_frame_epi_pose_begin");
+    OV2_REQUIRE(!results || !P.epi || eres, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was begun with ov2_btracker_track_frame_epi_pose_begin");
+    if (eres)
+        for (int b = 0; b < P.n_active; b++) {
+            OV2_REQUIRE(P.n[(size_t)b] == 0 || eres[b].removed, OV2_EINVAL, "NULL result buffer (removed) of the filter");
+            OV2_REQUIRE(!eres[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
+        }
     P.on = false;
     if (results) {
         const size_t B = (size_t)t->batch;
@@ -842,6 +1095,21 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
                 if (P.n[(size_t)b] > 0) memset(removed, 0, (size_t)P.n[(size_t)b]);
                 memcpy(r.Twc, P.Twc.data() + 7 * (size_t)b, 56);
                 r.action = OV2_POSE_TOO_FEW; r.p3p_req_out = P.req[(size_t)b] != 0;
+            }
+    }
+    if (eres) {
+        const size_t B = (size_t)t->batch;
+        t->le_on = true; t->le_chain = P.tracked; t->le_L = P.eL;
+        t->le_ncur.assign(B, 0); t->le_m.assign(B, 0); t->le_rows.assign(B, 0); t->le_host.assign(B, 0);
+        t->le_slot.resize(B); t->le_samples.resize(B);
+        if (!P.tracked)                                                  // first frame / nothing tracked: no chain ran
+            for (int b = 0; b < P.n_active; b++) {
+                ov2_epifilter_result &r = eres[b], keep = eres[b];
+                memset(&r, 0, sizeof(r));
+                r.removed = keep.removed; r.pair_cur = keep.pair_cur; r.err = keep.err;
+                r.action = OV2_EPIF_TOO_FEW_KPS;
+                if (P.n[(size_t)b] > 0) memset(r.removed, 0, (size_t)P.n[(size_t)b]);
+                if (P.n[(size_t)b] > 0 && r.err) memset(r.err, 0, 4 * (size_t)P.n[(size_t)b]);
             }
     }
     const size_t nm = (size_t)t->cfg.n_max;
@@ -875,10 +1143,29 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
         memcpy(ms, t->hpose + t->q_ms + 8 * (size_t)b, 8);
         t->lp_m[(size_t)b] = ms[0]; t->lp_rows[(size_t)b] = ms[1];
         if (n && rule[(size_t)b]) { redo.push_back(b); continue; }
+        if (eres) {
+            ov2_epifilter_result &r = eres[b];
+            EpifOut eo;
+            memcpy(&eo, t->hepi + t->e_out + sizeof(EpifOut) * (size_t)b, sizeof(EpifOut));
+            epi_store(r, eo);
+            memcpy(&t->le_ncur[(size_t)b], t->hepi + t->e_nc + 4 * (size_t)b, 4);
+            t->le_m[(size_t)b] = eo.m; t->le_rows[(size_t)b] = epi_rows_used(eo.action, eo.m, P.ep.n_rows);
+            if (n) {
+                memcpy(r.removed, t->hepi + t->e_rm + o, n);
+                if (r.pair_cur && eo.m > 0) memcpy(r.pair_cur, t->hepi + t->e_pc + 4 * o, 4 * (size_t)(eo.m < (int)n ? eo.m : (int)n));
+                if (r.err) memcpy(r.err, t->hepi + t->e_er + 4 * o, 4 * n);
+            }
+        }
         PoseOut po;
         memcpy(&po, t->hpose + t->q_out + sizeof(PoseOut) * (size_t)b, sizeof(PoseOut));
         pose_store(results[b], po);
         if (n) memcpy(results[b].removed, t->hpose + t->q_rm + o, n);
+    }
+    if (!redo.empty() && eres) {
+        std::vector<uint8_t> excl;
+        const int rc = epi_redo(t, redo, out_xy_h, status_h, eres, excl);
+        if (rc != OV2_OK) return rc;
+        return pose_redo(t, redo, status_h, results, excl.data());
     }
     if (!redo.empty()) return pose_redo(t, redo, status_h, results);
     return OV2_OK;
@@ -945,6 +1232,111 @@ int ov2_btracker_last_pose_inputs(const ov2_btracker *t, int item, int *m, int *
         OV2_HIP_CHECK(hipMemcpy(slot_idx, t->dwork + ov2_frame_pose_slot_offset(L) + 4 * b * (size_t)L.n_max, 4 * (size_t)mm, hipMemcpyDeviceToHost));
     if (samples && rows > 0)
         OV2_HIP_CHECK(hipMemcpy(samples, t->dwork + L.o_p3 + L.pl.o_sm + 16 * b * (size_t)L.n_rows, 16 * (size_t)rows, hipMemcpyDeviceToHost));
+    return OV2_OK;
+}
+
+int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf_lmid, const float *kf_unpx, const double *kf_bv,
+                              const double *kf_Twc)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(n_kf >= 0, OV2_EINVAL, "negative count (n_kf)");
+    OV2_REQUIRE(n_kf <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "more than OV2_FKF_MAX_POINTS (2048) keypoints in the keyframe");
+    OV2_REQUIRE(n_kf <= t->cfg.n_max, OV2_EINVAL, "the keyframe carries more keypoints than cfg.n_max slots");
+    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    OV2_REQUIRE(n_kf == 0 || (kf_lmid && kf_unpx), OV2_EINVAL, "NULL array of the keyframe (kf_lmid / kf_unpx)");
+    OV2_REQUIRE(n_kf == 0 || (kf_bv && kf_Twc), OV2_EINVAL, "NULL kf_bv / kf_Twc");
+    for (int i = 1; i < n_kf; i++) OV2_REQUIRE(kf_lmid[i - 1] < kf_lmid[i], OV2_EINVAL, "kf_lmid unsorted: not strictly ascending");
+    FeKfHdr h = FeKfHdr();
+    h.n_kf = n_kf;
+    if (kf_Twc) {
+        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(kf_Twc[c]), OV2_EINVAL, "pose not finite (kf_Twc)");
+        memcpy(h.kf_Twc, kf_Twc, 56);
+        ov2_fe_invert(kf_Twc, h.kf_Tcw);
+        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(h.kf_Tcw[c]), OV2_EINVAL, "pose not finite (the inverse of kf_Twc)");
+    }
+    for (size_t i = 0; i < 3 * (size_t)n_kf; i++) OV2_REQUIRE(std::isfinite(kf_bv[i]), OV2_EINVAL, "kf_bv not finite");
+    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_set_keyframe between steps only: a step is open");
+    const int rc = ensure_epi(t, nullptr);
+    if (rc != OV2_OK) return rc;
+    const EpifLayout &L0 = t->eL0;
+    const size_t o = (size_t)item * (size_t)t->cfg.n_max, n = (size_t)n_kf;
+    uint8_t *kh = t->kf_host.data();
+    hipStream_t s = t->ctx->stream;
+    if (n) {
+        memcpy(kh + 4 * o, kf_lmid, 4 * n);
+        memcpy(kh + (L0.o_ku - L0.o_kl) + 8 * o, kf_unpx, 8 * n);
+        memcpy(kh + (L0.o_kb - L0.o_kl) + 24 * o, kf_bv, 24 * n);
+        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kl + 4 * o, kh + 4 * o, 4 * n, hipMemcpyHostToDevice, s));
+        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_ku + 8 * o, kh + (L0.o_ku - L0.o_kl) + 8 * o, 8 * n, hipMemcpyHostToDevice, s));
+        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kb + 24 * o, kh + (L0.o_kb - L0.o_kl) + 24 * o, 24 * n, hipMemcpyHostToDevice, s));
+    }
+    t->kf_hdr[(size_t)item] = h;
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dfx + sizeof(FeKfHdr) * (size_t)item, &t->kf_hdr[(size_t)item], sizeof(FeKfHdr), hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipStreamSynchronize(s));                              // the host copy may be rewritten by the next call
+    return OV2_OK;
+}
+
+int ov2_btracker_track_frame_epi_pose_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                            const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h,
+                                            int klt_use_prior, const ov2_frame_epi_pose_params *params,
+                                            const ov2_frame_epi_pose_input *input)
+{
+    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h,
+                             true, nullptr, nullptr, true, params, input);
+}
+
+int ov2_btracker_track_frame_epi_pose_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req,
+                                          ov2_epifilter_result *epi_results, ov2_pose_result *pose_results)
+{
+    OV2_REQUIRE(epi_results && pose_results, OV2_EINVAL, "NULL result array");
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results);
+}
+
+int ov2_btracker_track_frame_epi_pose(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                      const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior,
+                                      const ov2_frame_epi_pose_params *params, const ov2_frame_epi_pose_input *input,
+                                      float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_epifilter_result *epi_results,
+                                      ov2_pose_result *pose_results)
+{
+    OV2_REQUIRE(epi_results && pose_results, OV2_EINVAL, "NULL result array");
+    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // as ov2_btracker_track_frame: the result buffers before anything is enqueued
+        int n_total = 0;
+        for (int b = 0; b < n_active; b++) {
+            n_total += n_h[b] > 0 ? n_h[b] : 0;
+            OV2_REQUIRE(n_h[b] <= 0 || (pose_results[b].removed && epi_results[b].removed), OV2_EINVAL, "NULL result buffer (removed)");
+            OV2_REQUIRE(!epi_results[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
+        }
+        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
+    }
+    const int rc = ov2_btracker_track_frame_epi_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
+    if (rc != OV2_OK) return rc;
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results);
+}
+
+int ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, int *slot_idx, int *m, int *samples, int *n_rows_used)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(t->le_on, OV2_EINVAL, "ov2_btracker_last_epi_inputs: no epipolar step has been finished on this tracker");
+    const size_t b = (size_t)item;
+    const int nc = t->le_ncur[b], rows = t->le_rows[b];
+    if (n_cur) *n_cur = nc;
+    if (m) *m = t->le_m[b];
+    if (n_rows_used) *n_rows_used = rows;
+    if (t->le_host[b]) {
+        if (slot_idx && nc > 0) memcpy(slot_idx, t->le_slot[b].data(), 4 * (size_t)nc);
+        if (samples && rows > 0) memcpy(samples, t->le_samples[b].data(), 32 * (size_t)rows);
+        return OV2_OK;
+    }
+    if (!t->le_chain || (nc <= 0 && rows <= 0)) return OV2_OK;
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const EpifLayout &L = t->le_L;
+    const size_t nm = (size_t)t->cfg.n_max;
+    if (slot_idx && nc > 0 && (size_t)nc <= nm)
+        OV2_HIP_CHECK(hipMemcpy(slot_idx, t->dfx + t->x_slot + 4 * b * nm, 4 * (size_t)nc, hipMemcpyDeviceToHost));
+    if (samples && rows > 0)
+        OV2_HIP_CHECK(hipMemcpy(samples, t->depi + L.o_sm + 32 * b * (size_t)L.s_max, 32 * (size_t)rows, hipMemcpyDeviceToHost));
     return OV2_OK;
 }
 

@@ -673,6 +673,100 @@ class LockstepTracker:
                                                        tab.ctypes.data_as(C.POINTER(C.c_int)), C.byref(rows)))
         return m.value, slot[:m.value].copy(), tab[:rows.value].copy()
 
+    def setKeyframe(self, item, kf_lmid, kf_unpx, kf_bv, kf_Twc):
+        """the keyframe item `item` is filtered against from now on (ov2_btracker_set_keyframe): kf_lmid (m,) strictly ascending,
+        kf_unpx (m, 2), kf_bv (m, 3), kf_Twc (7,); it stays on the device until it is replaced.  m == 0 takes it away.  Between
+        steps only."""
+        lm = np.ascontiguousarray(kf_lmid, np.int32).reshape(-1)
+        un = np.ascontiguousarray(kf_unpx, np.float32).reshape(-1, 2)
+        bv = np.ascontiguousarray(kf_bv, np.float64).reshape(-1, 3)
+        if len(un) != len(lm) or len(bv) != len(lm):
+            raise ValueError("one unpx and one bearing per keyframe id")
+        T = None if kf_Twc is None else np.ascontiguousarray(kf_Twc, np.float64).reshape(7)
+        L.check(self.lib.ov2_btracker_set_keyframe(self.h_trk, int(item), len(lm), _ptr(lm), _ptr(un), _ptr(bv), _ptr(T)))
+
+    def _epi_args(self, na, nn, params, epi_params, Twc, p3p_req, seed, lmid, nbkfs, epi_seed, scale, dop3p, n_rows):
+        from . import keyframe as _kf
+        fp, fi, keep = self._pose_args(na, nn, params, Twc, p3p_req, seed, scale, dop3p, n_rows)
+        ep = L.FrameEpiPoseParams()
+        ep.pose, ep.epi = fp, _kf._as_epifilter_params(epi_params)
+        self._epi_rows = max(0, int(ep.epi.n_rows))                               # (the room lastEpiInputs gives the table)
+        lm = np.ascontiguousarray(lmid, np.int32).reshape(self.batch, self.n_max)
+        nk = np.ascontiguousarray(nbkfs, np.int32).reshape(-1)
+        es = np.ascontiguousarray(epi_seed, np.uint64).reshape(-1)
+        if len(nk) < na or len(es) < na:
+            raise ValueError("one nbkfs and one epipolar seed per active item")
+        ei = L.FrameEpiPoseInput()
+        ei.pose = fi
+        ei.lmid_h = lm.ctypes.data_as(C.POINTER(C.c_int))
+        ei.nbkfs_h = nk.ctypes.data_as(C.POINTER(C.c_int))
+        ei.epi_seed_h = es.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        return ep, ei, keep + (lm, nk, es)
+
+    def _epi_results(self, na):
+        R = (L.EpifilterResult * max(1, na))()
+        bufs = dict(removed=np.zeros((max(1, na), self.n_max), np.uint8), pair_cur=np.zeros((max(1, na), self.n_max), np.int32),
+                    err=np.zeros((max(1, na), self.n_max), np.float32))
+        for b in range(na):
+            R[b].removed = bufs["removed"][b].ctypes.data_as(C.POINTER(C.c_uint8))
+            R[b].pair_cur = bufs["pair_cur"][b].ctypes.data_as(C.POINTER(C.c_int))
+            R[b].err = bufs["err"][b].ctypes.data_as(C.POINTER(C.c_float))
+        return R, bufs
+
+    def _epi_dicts(self, R, bufs, nn):
+        from . import keyframe as _kf
+        return [_kf._epifilter_dict(R[b], dict(removed=bufs["removed"][b, :int(nn[b])], pair_cur=bufs["pair_cur"][b],
+                                               err=bufs["err"][b, :int(nn[b])])) for b in range(len(nn))]
+
+    def trackFrameEpiPose(self, imgs, kps, wpt, is3d, Tcw, n, params, epi_params, Twc, p3p_req, seed, lmid, nbkfs, epi_seed,
+                          scale=None, dop3p=False, n_rows=0, klt_use_prior=True):
+        """trackFrameMap, epipolar2d2dFiltering against the resident keyframes (setKeyframe) and the per-frame pose in one enqueue and
+        one synchronisation (ov2_btracker_track_frame_epi_pose): trackMono's per-frame sequence with doepipolar_ == 1.  As
+        trackFramePose, plus epi_params (as keyframe.epipolar_filter takes them; boptimize False), lmid (batch, n_max) int32, nbkfs
+        and epi_seed one per item.  -> (out, status bits, p3p_req, epis, poses): epis[b] as keyframe.epipolar_filter returns it with
+        removed / err (n[b],) and pair_cur (m,) IN SLOT SPACE; poses[b] as trackFramePose, on the frame after the filter."""
+        na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
+        ep, ei, keep = self._epi_args(na, nn, params, epi_params, Twc, p3p_req, seed, lmid, nbkfs, epi_seed, scale, dop3p, n_rows)
+        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
+        p3p = np.zeros(na, np.int32)
+        R, removed = self._pose_results(na, nn)
+        E, bufs = self._epi_results(na)
+        L.check(self.lib.ov2_btracker_track_frame_epi_pose(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw),
+                                                           _ptr(nn), int(bool(klt_use_prior)), C.byref(ep), C.byref(ei), _ptr(out),
+                                                           _ptr(st), _ptr(p3p), E, R))
+        return out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn), self._pose_dicts(R, removed, nn)
+
+    def trackFrameEpiPoseBegin(self, imgs, kps, wpt, is3d, Tcw, n, params, epi_params, Twc, p3p_req, seed, lmid, nbkfs, epi_seed,
+                               scale=None, dop3p=False, n_rows=0, klt_use_prior=True):
+        """first half of trackFrameEpiPose; trackFrameEpiPoseEnd finishes it (trackFrameEnd finishes the tracking half and drops both
+        results)"""
+        na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
+        ep, ei, keep = self._epi_args(na, nn, params, epi_params, Twc, p3p_req, seed, lmid, nbkfs, epi_seed, scale, dop3p, n_rows)
+        L.check(self.lib.ov2_btracker_track_frame_epi_pose_begin(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw),
+                                                                 _ptr(nn), int(bool(klt_use_prior)), C.byref(ep), C.byref(ei)))
+        self._pending = (imgs, kps, wpt, is3d, nn)                                # (kps is re-read by the end half: keep it alive)
+
+    def trackFrameEpiPoseEnd(self):
+        """second half of trackFrameEpiPose -> (out, status bits, p3p_req, epis, poses)"""
+        nn = self._pending[4]
+        na = len(nn)
+        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
+        p3p = np.zeros(na, np.int32)
+        R, removed = self._pose_results(na, nn)
+        E, bufs = self._epi_results(na)
+        L.check(self.lib.ov2_btracker_track_frame_epi_pose_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p), E, R))
+        self._pending = None
+        return out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn), self._pose_dicts(R, removed, nn)
+
+    def lastEpiInputs(self, item):
+        """what the last epipolar step fed the filter for `item` -> (n_cur, slots (n_cur,) int32, m, samples (rows used, 8) int32)"""
+        nc, m, rows = C.c_int(), C.c_int(), C.c_int()
+        slot = np.zeros(self.n_max, np.int32)
+        tab = np.zeros((max(1, self._epi_rows), 8), np.int32)
+        L.check(self.lib.ov2_btracker_last_epi_inputs(self.h_trk, int(item), C.byref(nc), slot.ctypes.data_as(C.POINTER(C.c_int)),
+                                                      C.byref(m), tab.ctypes.data_as(C.POINTER(C.c_int)), C.byref(rows)))
+        return nc.value, slot[:nc.value].copy(), m.value, tab[:rows.value].copy()
+
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
         pri = np.empty((n, 2), np.float32)

@@ -155,6 +155,15 @@ def sampson_filter_2d_batch(ctx, items, Fkfcur, fransac_err):
     return outs
 
 
+def se3_inverse(T):
+    """ov2_se3_inverse: [t q] of the inverse of the transform [t q] in the library's host arithmetic -- the kf_Tcw that
+    LockstepTracker.setKeyframe derives from kf_Twc, bit for bit"""
+    T = np.ascontiguousarray(T, np.float64).reshape(7)
+    out = np.zeros(7, np.float64)
+    L.check(L.load().ov2_se3_inverse(T.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 # ---- epipolar2d2dFiltering ----------------------------------------------------------------------------------------------------------
 def epifilter_params(fkf, *, max_iterations, threshold, fransac_err, mono, n_rows, probability=0.99, boptimize=False):
     """ov2_epifilter_params: the ov2_fkf_params (or the dict of them; K and stereo are read), the search's nransac_iter_ and bearing
