@@ -164,6 +164,14 @@ int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur,
                          int track_impl = OV2_TRACK_IMPL_WAVE,
                          int items = 1,    // items > 1 (trackb.hip): batch items [0, items) of both pyramids, n_max point slots and one n_dev entry per item
                          int lk_acc = OV2_LK_ACC_INT64);   // OV2_OPT_LK_ACC   // items > 1 (trackb.hip): batch items [0, items) of both pyramids, n_max point slots and one n_dev entry per item
+// The cross-keypoint rule of visual_front_end.cpp:225-230 over the n results of one frame (track.hip; both trackers call it): when
+// fewer than 33 % of the prior tracks are good, the lost ones are run again from their keypoints between the two pyramids (one item
+// each), out_xy / status take the new results and *p3p_req (may be NULL) is set.  calib != NULL: unpx (2 per keypoint) and bv (3 per
+// keypoint) of the re-run keypoints follow their new positions.
+struct KpCalib;
+struct P3pRuleFrame { const float *kps; const uint8_t *has_prior; int use_prior, n; float *out_xy; uint8_t *status; float *unpx; double *bv; };
+int ov2_apply_p3p_rule(ov2_ctx *ctx, const ov2_tracker_config &cfg, const ov2_pyr *prev, const ov2_pyr *cur, const KpCalib *calib,
+                       const P3pRuleFrame &f, int *p3p_req);
 
 // BRIEF descriptors (brief.hip) of the points of items [0, n_items) of a device image batch (items item_stride bytes apart), from host
 // point arrays with cap slots per item (n_h[b] valid; NULL: n_h_all each) into host outputs of the same layout (slots past n_h[b]

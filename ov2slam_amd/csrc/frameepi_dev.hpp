@@ -4,6 +4,7 @@
 #pragma once
 #include "common.hpp"
 #include "epif_dev.hpp"
+#include "pose_dev.hpp"
 
 // 120 bytes per item, device resident: written by ov2_btracker_set_keyframe, read by k_epif_pack.  All zero: no keyframe.
 struct FeKfHdr {
@@ -35,7 +36,6 @@ struct FeStep {
     uint8_t *block;                                     // the epipolar block
     int n_active;
 };
-typedef int (*ov2_fp_hook)(hipStream_t s, uint8_t *sel, void *arg);
-int ov2_frame_epi_hook(hipStream_t s, uint8_t *sel, void *arg);     // arg: FeStep *
+int ov2_frame_epi_hook(hipStream_t s, uint8_t *sel, void *arg);     // an ov2_fp_hook (pose_dev.hpp); arg: FeStep *
 // [t q] of the inverse of the transform [t q] (Sophus' SE3::inverse: the conjugate, and minus the rotated translation)
 void ov2_fe_invert(const double T[7], double out[7]);

@@ -124,26 +124,21 @@ __global__ __launch_bounds__(256) void k_pose_unpack(FpArgs a)
     a.removed_slot[o + i] = (r >= 0 && r < a.n_max) ? a.removed[o + (size_t)r] : (uint8_t)0;
 }
 
-// The pose half of a lock-step step behind k_compute_keypoints on `s`.  blk: the tracker's point block (n at o_n, status, unpx, bv),
-// map: its map block (wpt, is3d), in / out: the step's pose inputs and results (the caller's pointers into its pinned or mirrored
-// block), work: [PoseLayout L][sel 1][slot 4][rank 4 per slot].  hook (frameepi.hip, or none): what a step enqueues between the
-// select and the pack -- it may clear select bytes; without one the launches are the four below.
-int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search,
-                          const int *n_d, const uint8_t *status_d, const float *unpx_d, const double *bv_d, const double *wpt_d,
-                          const uint8_t *is3d_d, const double *Twc_d, const int *scale_d, const uint8_t *flags_d,
-                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d,
-                          int (*hook)(hipStream_t, uint8_t *, void *), void *hook_arg)
+// The pose half of a lock-step step behind k_compute_keypoints on `s` (pose_dev.hpp: FramePoseIo).  Without a hook the launches are
+// the four below.
+int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search, const FramePoseIo &io,
+                          ov2_fp_hook hook, void *hook_arg)
 {
     const size_t NP = L.pl.NP;
-    uint8_t *x = work + L.total;
+    uint8_t *work = io.work, *x = work + L.total;
     FpArgs a;
-    a.n_dev = n_d; a.status = status_d; a.is3d = is3d_d; a.unpx = unpx_d; a.bv = bv_d; a.wpt = wpt_d;
-    a.scale = scale_d; a.flags = flags_d; a.seed = seed_d;
-    a.sel = x; a.slot = (int *)(x + ((NP + 15) & ~(size_t)15)); a.rank = a.slot + NP; a.ms = (int2 *)ms_d;
+    a.n_dev = io.n_dev; a.status = io.status; a.is3d = io.is3d; a.unpx = io.unpx; a.bv = io.bv; a.wpt = io.wpt;
+    a.scale = io.scale; a.flags = io.flags; a.seed = io.seed;
+    a.sel = x; a.slot = (int *)(x + ((NP + 15) & ~(size_t)15)); a.rank = a.slot + NP; a.ms = (int2 *)io.ms;
     uint8_t *p3 = work + L.o_p3;
     a.items = (PoseItem *)(work + L.o_it); a.c_unpx = (double *)(work + L.o_px); a.c_sigma = (double *)(work + L.o_sg);
     a.p3items = (P3Item *)(p3 + L.pl.o_it); a.p3bv = (double *)(p3 + L.pl.o_bv); a.p3X = (double *)(p3 + L.pl.o_X); a.samples = (int4 *)(p3 + L.pl.o_sm);
-    a.removed = work + L.o_rm; a.removed_slot = removed_slot_d;
+    a.removed = work + L.o_rm; a.removed_slot = io.removed_slot;
     a.n_max = L.n_max; a.n_rows = L.n_rows;
     const dim3 slots((L.n_max + 255) / 256, n_active);
     hipLaunchKernelGGL(k_pose_select, slots, dim3(256), 0, s, a);
@@ -151,13 +146,12 @@ int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const Po
     if (hook) { const int rch = hook(s, a.sel, hook_arg);  if (rch != OV2_OK) return rch; }
     hipLaunchKernelGGL(k_pose_pack, dim3(n_active), dim3(64), 0, s, a);
     OV2_HIP_CHECK(hipGetLastError());
-    const int rc = pose_chain_enqueue(s, params, L, work, Twc_d, out_d, n_active, search);
+    const int rc = pose_chain_enqueue(s, params, L, work, io.Twc, io.out, n_active, search);
     if (rc != OV2_OK) return rc;
     hipLaunchKernelGGL(k_pose_unpack, slots, dim3(256), 0, s, a);
     OV2_HIP_CHECK(hipGetLastError());
     return OV2_OK;
 }
 
-// bytes of the work block for layout L, and where the slot list of the packed points lies in it
 size_t ov2_frame_pose_work_bytes(const PoseLayout &L) { return L.total + ((L.pl.NP + 15) & ~(size_t)15) + 8 * L.pl.NP + 16; }
 size_t ov2_frame_pose_slot_offset(const PoseLayout &L) { return L.total + ((L.pl.NP + 15) & ~(size_t)15); }

@@ -65,6 +65,12 @@ __device__ __forceinline__ bool kp_undistort_fisheye(const KpCalib &c, double u,
 
 // host: validate and pack the calibration (defined in keypoint.hip)
 int ov2_kp_calib(int model, const double K[4], const double *D, int nD, const double iK[9], KpCalib &c);
+// keypoint.hip: k_compute_keypoints on device arrays, `items` items of n_max point slots and one n_dev entry each
+int ov2_launch_compute_keypoints(hipStream_t s, const KpCalib &c, const float *px_d, int n_max, const int *n_dev, float *unpx_d, double *bv_d, int items = 1);
+// priors.hip: k_prior_frame on device arrays with n_max point slots per item
+int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double img_h, int use_prior, const void *items_d,
+                           const double *Tcw_d, const float *px_d, const uint8_t *is3d_d, const double *wpt_d, float *prior_d,
+                           uint8_t *has_prior_d, int n_max, int n_items);
 
 // The forward model: CameraCalibration::projectCamToImageDist (src/camera_calibration.cpp:254-281) of a camera-frame point.
 // x = X / z, y = Y / z in double through invz; without coefficients Point2f(fx x + cx, fy y + cy).  With coefficients x, y are

@@ -40,3 +40,20 @@ int pose_layout(int n_items, int n_max, int n_rows, PoseLayout *L);
 // b's at b * n_max) are left at o_rm.
 int pose_chain_enqueue(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, uint8_t *ds, const double *Twc_d, PoseOut *out_d,
                        int n_items, bool search);
+
+// framepose.hip: the pose set, computePose's chain and the removal bytes in slot space, behind k_compute_keypoints.  The device
+// pointers of a step, named as the kernels' FpArgs names them: the tracker's point block (n_dev, status, unpx, bv) and map block
+// (wpt, is3d); the step's pose inputs (Twc, scale, flags, seed) and results (out, ms, removed_slot) in its pinned or mirrored block;
+// work: [PoseLayout L][sel 1][slot 4][rank 4 per slot].
+struct FramePoseIo {
+    const int *n_dev; const uint8_t *status; const float *unpx; const double *bv, *wpt; const uint8_t *is3d;
+    const double *Twc; const int *scale; const uint8_t *flags; const unsigned long long *seed;
+    uint8_t *work; PoseOut *out; int *ms; uint8_t *removed_slot;
+};
+// what a step enqueues between the select and the pack (frameepi.hip: ov2_frame_epi_hook, or none): it may clear select bytes
+typedef int (*ov2_fp_hook)(hipStream_t s, uint8_t *sel, void *arg);
+int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search, const FramePoseIo &io,
+                          ov2_fp_hook hook, void *hook_arg);
+// bytes of the work block for layout L, and where the slot list of the packed points lies in it
+size_t ov2_frame_pose_work_bytes(const PoseLayout &L);
+size_t ov2_frame_pose_slot_offset(const PoseLayout &L);

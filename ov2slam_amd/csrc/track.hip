@@ -13,8 +13,6 @@
 #include <new>
 #include <vector>
 
-int ov2_launch_compute_keypoints(hipStream_t s, const KpCalib &c, const float *px_d, int n_max, const int *n_dev, float *unpx_d, double *bv_d, int items = 1);
-
 struct ov2_tracker {
     ov2_ctx *ctx = nullptr;
     ov2_tracker_config cfg;
@@ -134,49 +132,57 @@ static int klt_overflow_chunks(ov2_tracker *t, const float *kps, const float *pr
     return OV2_OK;
 }
 
-// the cross-keypoint rule of visual_front_end.cpp:225-230 over all n results
-static int apply_p3p_rule(ov2_tracker *t, const float *kps, const uint8_t *has_prior, int use_prior, int n, float *out_xy,
-                          uint8_t *status, int *p3p_req)
+// the cross-keypoint rule of visual_front_end.cpp:225-230 over all n results (common.hpp)
+int ov2_apply_p3p_rule(ov2_ctx *ctx, const ov2_tracker_config &c, const ov2_pyr *prev, const ov2_pyr *cur, const KpCalib *calib,
+                       const P3pRuleFrame &f, int *p3p_req)
 {
+    const int n = f.n;
     size_t nbkps = 0, nbgood = 0;
-    if (use_prior && has_prior)
-        for (int i = 0; i < n; i++) if (has_prior[i]) { nbkps++; if ((status[i] & 3) == 1) nbgood++; }
+    if (f.use_prior && f.has_prior)
+        for (int i = 0; i < n; i++) if (f.has_prior[i]) { nbkps++; if ((f.status[i] & 3) == 1) nbgood++; }
     int p3p = 0;
     if (nbkps > 0 && (double)nbgood < 0.33 * (double)nbkps) {
         // "Motion model might be quite wrong": vpriors = vkps for the second call (:229) -- only the lost prior
         // tracks had a prior different from their keypoint, so only they are re-run, from the keypoints themselves
         p3p = 1;
         std::vector<int> idx;
-        for (int i = 0; i < n; i++) if (status[i] & 2) idx.push_back(i);
+        for (int i = 0; i < n; i++) if (f.status[i] & 2) idx.push_back(i);
         if (!idx.empty()) {
             const int m = (int)idx.size();
             std::vector<float> k2(2 * (size_t)m), p2(2 * (size_t)m);
             std::vector<uint8_t> s2((size_t)m);
-            for (int j = 0; j < m; j++) { k2[2 * j] = p2[2 * j] = kps[2 * idx[j]]; k2[2 * j + 1] = p2[2 * j + 1] = kps[2 * idx[j] + 1]; }
-            const ov2_tracker_config &c = t->cfg;
-            const int rc = ov2_fb_klt(t->ctx, t->pyr[t->cur ^ 1], t->pyr[t->cur], c.win, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th,
-                                      c.fb_dist, k2.data(), p2.data(), m, s2.data(), nullptr);
+            for (int j = 0; j < m; j++) { k2[2 * j] = p2[2 * j] = f.kps[2 * idx[j]]; k2[2 * j + 1] = p2[2 * j + 1] = f.kps[2 * idx[j] + 1]; }
+            const int rc = ov2_fb_klt(ctx, prev, cur, c.win, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist, k2.data(), p2.data(), m,
+                                      s2.data(), nullptr);
             if (rc != OV2_OK) return rc;
             for (int j = 0; j < m; j++) {
-                out_xy[2 * idx[j]] = p2[2 * j]; out_xy[2 * idx[j] + 1] = p2[2 * j + 1];
-                status[idx[j]] = (uint8_t)(2 | (s2[j] ? 1 : 0));
+                f.out_xy[2 * idx[j]] = p2[2 * j]; f.out_xy[2 * idx[j] + 1] = p2[2 * j + 1];
+                f.status[idx[j]] = (uint8_t)(2 | (s2[j] ? 1 : 0));
             }
-            if (t->has_calib) {                                        // their undistorted pixels / bearings follow the new positions
+            if (calib) {                                               // their undistorted pixels / bearings follow the new positions
                 std::vector<float> u2(2 * (size_t)m);
                 std::vector<double> b2(3 * (size_t)m);
-                const KpCalib &kc = t->calib;
+                const KpCalib &kc = *calib;
                 const double Kk[4] = {kc.fx, kc.fy, kc.cx, kc.cy};
-                const int rck = ov2_compute_keypoints(t->ctx, kc.model, Kk, kc.nD ? kc.k : nullptr, kc.nD, kc.iK, p2.data(), m, u2.data(), b2.data());
+                const int rck = ov2_compute_keypoints(ctx, kc.model, Kk, kc.nD ? kc.k : nullptr, kc.nD, kc.iK, p2.data(), m, u2.data(), b2.data());
                 if (rck != OV2_OK) return rck;
                 for (int j = 0; j < m; j++) {
-                    memcpy(&t->last_unpx[2 * (size_t)idx[j]], &u2[2 * (size_t)j], 8);
-                    memcpy(&t->last_bv[3 * (size_t)idx[j]], &b2[3 * (size_t)j], 24);
+                    memcpy(f.unpx + 2 * (size_t)idx[j], &u2[2 * (size_t)j], 8);
+                    memcpy(f.bv + 3 * (size_t)idx[j], &b2[3 * (size_t)j], 24);
                 }
             }
         }
     }
     if (p3p_req) *p3p_req = p3p;
     return OV2_OK;
+}
+
+// the rule on the tracker's own pyramids; the re-derived unpx / bv go to last_unpx / last_bv
+static int apply_p3p_rule(ov2_tracker *t, const float *kps, const uint8_t *has_prior, int use_prior, int n, float *out_xy,
+                          uint8_t *status, int *p3p_req)
+{
+    const P3pRuleFrame f = {kps, has_prior, use_prior, n, out_xy, status, t->last_unpx.data(), t->last_bv.data()};
+    return ov2_apply_p3p_rule(t->ctx, t->cfg, t->pyr[t->cur ^ 1], t->pyr[t->cur], t->has_calib ? &t->calib : nullptr, f, p3p_req);
 }
 
 static void tracker_free(ov2_tracker *t)

@@ -27,29 +27,90 @@
 #include "keypoint_dev.hpp"
 #include "pose_dev.hpp"
 #include "frameepi_dev.hpp"
+#include "trackb_layout.hpp"
 #include <cmath>
 #include <deque>
 #include <new>
 #include <vector>
 
-int ov2_launch_compute_keypoints(hipStream_t s, const KpCalib &c, const float *px_d, int n_max, const int *n_dev, float *unpx_d, double *bv_d, int items = 1);
-// priors.hip: k_prior_frame on device arrays with n_max point slots per item
-int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double img_h, int use_prior, const void *items_d,
-                           const double *Tcw_d, const float *px_d, const uint8_t *is3d_d, const double *wpt_d, float *prior_d,
-                           uint8_t *has_prior_d, int n_max, int n_items);
-
-// framepose.hip: the pose set, computePose's chain and the removal bytes in slot space, behind k_compute_keypoints
-int ov2_launch_frame_pose(hipStream_t s, const ov2_pose_params *params, const PoseLayout &L, int n_active, bool search,
-                          const int *n_d, const uint8_t *status_d, const float *unpx_d, const double *bv_d, const double *wpt_d,
-                          const uint8_t *is3d_d, const double *Twc_d, const int *scale_d, const uint8_t *flags_d,
-                          const unsigned long long *seed_d, uint8_t *work, PoseOut *out_d, int *ms_d, uint8_t *removed_slot_d,
-                          ov2_fp_hook hook = nullptr, void *hook_arg = nullptr);
-size_t ov2_frame_pose_work_bytes(const PoseLayout &L);
-size_t ov2_frame_pose_slot_offset(const PoseLayout &L);
-
 #define BT_SETS 8       // pyramid sets in rotation: cur, prev, the one being prepared for the next frame, five of slack for the mapper
                         // context (a keyframe's pyramids outlive it by BT_SETS - 1 steps: the keyframe period of the shipped parameter files)
 #define BT_IMG_SETS 3   // staging sets: frame f (read by its pre-processing), f + 1 (arriving), f + 2 (being filled by the host)
+
+static_assert(sizeof(PoseOut) == BT_POSE_OUT_BYTES, "trackb_layout.hpp: the pose block's record");
+static_assert(sizeof(EpifOut) == BT_EPIF_OUT_BYTES, "trackb_layout.hpp: the epipolar block's record");
+static_assert(sizeof(FeKfHdr) == BT_KF_HDR_BYTES, "trackb_layout.hpp: the index block's header");
+
+// A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
+// (zero copy), or mirrored on the device with a copy up before the kernels and a copy down behind them.
+struct IoBlock {
+    uint8_t *h = nullptr, *d = nullptr, *k = nullptr;    // the pinned block; its device mirror (NULL with zero copy); what the kernels dereference
+    size_t bytes = 0;
+    // decide: the tracker's first block takes the alias when there is one and sets zero_copy; the later blocks follow it
+    int alloc(size_t n, bool &zero_copy, bool decide, const char *who)
+    {
+        hipError_t e = hipHostMalloc((void **)&h, n, hipHostMallocMapped);
+        void *alias = nullptr;
+        if (e == hipSuccess && decide) {
+            zero_copy = hipHostGetDevicePointer(&alias, h, 0) == hipSuccess && alias;
+            if (!zero_copy) (void)hipGetLastError();
+        }
+        if (e == hipSuccess && !zero_copy) { e = hipMalloc((void **)&d, n); alias = d; }
+        else if (e == hipSuccess && !decide) e = hipHostGetDevicePointer(&alias, h, 0);
+        if (e != hipSuccess || !alias) {
+            release();
+            (void)hipGetLastError();
+            ov2_set_error("%s: %s", who, hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        memset(h, 0, n);
+        k = (uint8_t *)alias; bytes = n;
+        return OV2_OK;
+    }
+    void release()
+    {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        h = d = k = nullptr; bytes = 0;
+    }
+    // [0, n) up, [from, to) down: nothing to do when the kernels work on the pinned block itself
+    int upload(hipStream_t s, size_t n) const { if (d) OV2_HIP_CHECK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)); return OV2_OK; }
+    int download(hipStream_t s, size_t from, size_t to) const
+    {
+        if (d) OV2_HIP_CHECK(hipMemcpyAsync(h + from, d + from, to - from, hipMemcpyDeviceToHost, s));
+        return OV2_OK;
+    }
+};
+
+// One step as its _begin call describes it.  Each form includes the one before it: map -- the priors come from the device (wpt_h /
+// is3d_h / Tcw_h; prior_xy_h / has_prior_h are unused); pose -- the pose of ov2_btracker_track_frame_pose follows in the same
+// enqueue; epi -- the filter of ov2_btracker_track_frame_epi_pose runs between the pose's select and its pack.
+enum StepForm { STEP_PLAIN = 0, STEP_MAP, STEP_POSE, STEP_EPI };
+struct StepArgs {
+    StepForm form = STEP_PLAIN;
+    int n_active = 0, stride = 0, klt_use_prior = 0;
+    const uint8_t *const *img_h = nullptr;
+    const float *kps_xy_h = nullptr; const int *n_h = nullptr;
+    const float *prior_xy_h = nullptr; const uint8_t *has_prior_h = nullptr;                               // plain
+    const double *wpt_h = nullptr; const uint8_t *is3d_h = nullptr; const double *Tcw_h = nullptr;         // map and later
+    const ov2_frame_pose_params *pp = nullptr; const ov2_frame_pose_input *pin = nullptr;                  // pose (epi: the pose halves of epp / ein)
+    const ov2_frame_epi_pose_params *epp = nullptr; const ov2_frame_epi_pose_input *ein = nullptr;         // epi
+};
+
+// ov2_btracker_last_pose_inputs / ov2_btracker_last_epi_inputs: what the last finished step of the kind fed its chain.  Per item the
+// counts (ncur: entries of the slot list -- the filter's packed frame; the pose set, so m again) and, for an item the 33 % rule
+// re-ran (host), the slot list and the table of the second run -- the device block still holds those of the first
+struct LastInputs {
+    bool on = false, chain = false;                  // a step has been finished; its chain ran (not a first frame / nothing tracked)
+    std::vector<int> ncur, m, rows;
+    std::vector<std::vector<int>> slot, samples;
+    std::vector<uint8_t> host;
+    void open(size_t B, bool tracked)
+    {
+        on = true; chain = tracked;
+        ncur.assign(B, 0); m.assign(B, 0); rows.assign(B, 0); host.assign(B, 0); slot.resize(B); samples.resize(B);
+    }
+};
 
 struct ov2_btracker {
     ov2_ctx *ctx = nullptr;
@@ -65,7 +126,7 @@ struct ov2_btracker {
     long frames = 0;
     // frames: pinned staging sets + their device mirrors; a copy stream for uploads and a stream for pre-processing started ahead
     uint8_t *himg[BT_IMG_SETS] = {nullptr, nullptr, nullptr}, *dimg[BT_IMG_SETS] = {nullptr, nullptr, nullptr};
-    size_t img_pitch = 0, img_bytes = 0;          // per item (img_bytes a multiple of 256)
+    size_t img_pitch = 0, img_bytes = 0;          // per item (trackb_layout.hpp)
     // ov2_btracker_set_rectification: the uploads of set `which` go to draw[which]; the pre-processing of the set starts with k_remap
     // draw[which] -> dimg[which], so dimg holds the RECTIFIED frames.  used_ev[which] is recorded behind that pre-processing: it covers
     // the remap's reads of draw[which] as it covers the reads of dimg[which]
@@ -83,69 +144,49 @@ struct ov2_btracker {
     struct Prep { int which, n, set; };
     std::deque<Prep> prepq;
     long pre_count = 0;
-    // keypoint block: pinned + mapped (the kernels read / write it through its device alias) or mirrored on the device
-    uint8_t *hblk = nullptr, *dblk = nullptr, *kblk = nullptr;
+    // the four blocks the host and the kernels share (IoBlock; their sections: trackb_layout.hpp).  The point block decides zero_copy
+    // for all of them; the map, pose and epipolar blocks are allocated by the first step of their form
+    IoBlock pt, map, pose, epi;
     bool zero_copy = false;
-    size_t o_n = 0, o_kps = 0, o_pri = 0, o_flg = 0, in_bytes = 0, o_out = 0, o_st = 0, o_unpx = 0, o_bv = 0, blk_bytes = 0;
+    BtPointLayout pl; BtMapLayout ml; BtPoseLayout ql; BtEpiLayout el;
     bool has_calib = false;
     KpCalib calib;
     std::vector<int> last_n;           // per item: keypoints of the last track_frame (0 before / after a call that tracked nothing)
     std::vector<int> last_pn;          // the same whether or not a calibration is set (ov2_btracker_last_priors)
-    // ov2_btracker_track_frame_map: the map side of a step -- [items 16 B][Tcw 56 B] per item, [wpt 24][is3d 1] per slot --, allocated
-    // by the first such step; pinned + mapped or mirrored on the device like the keypoint block
-    uint8_t *hmap = nullptr, *dmap = nullptr, *kmap = nullptr;
-    size_t m_it = 0, m_T = 0, m_w = 0, m_3d = 0, map_bytes = 0;
-    // ov2_btracker_track_frame_pose: the pose side of a step, allocated by the first such step.  hpose, pinned + mapped or mirrored
-    // like the keypoint block: [Twc 56][seed 8][flags 1] per item and [scale 4] per slot go up; [PoseOut 168][m, rows 8] per item and
-    // [removed 1] per slot come down.  dwork: the chain's block at capacity and the pack's lists (device only; not the context's
+    // ov2_btracker_track_frame_pose: the chain's block at capacity and the pack's lists (device only, grow-only; not the context's
     // scratch, which other calls use on the same stream)
-    uint8_t *hpose = nullptr, *dpose = nullptr, *kpose = nullptr, *dwork = nullptr;
-    size_t q_T = 0, q_seed = 0, q_fl = 0, q_sc = 0, q_in = 0, q_out = 0, q_ms = 0, q_rm = 0, pose_bytes = 0, work_bytes = 0;
-    // ov2_btracker_last_pose_inputs: the layout of the last finished pose step; per item m and rows; for an item the rule re-ran, the
-    // slot list and the table of the second run (the device block still holds those of the first)
-    bool lp_on = false, lp_chain = false;
-    PoseLayout lp_L;
-    std::vector<int> lp_m, lp_rows;
-    std::vector<std::vector<int>> lp_slot, lp_samples;
-    std::vector<uint8_t> lp_host;
+    uint8_t *dwork = nullptr;
+    size_t work_bytes = 0;
+    LastInputs lp;
+    PoseLayout lp_L;                                  // the chain's layout in the last finished pose step
     // ov2_btracker_track_frame_epi_pose / ov2_btracker_set_keyframe: the epipolar side, allocated by the first of either.
-    //   depi   the filter's block (EpifLayout at capacity: batch x n_max slots, batch x n_rows rows; device only).  Its inputs
-    //          [0, o_up) do not depend on n_rows, so the resident keyframe arrays stay where they are when a step asks for more rows
-    //          and the block is grown (they are then copied again from kf_host).
-    //   dfx    [FeKfHdr 120 per item][slot 4][rank 4 per slot] (device only)
-    //   hepi   pinned + mapped or mirrored like the keypoint block: [lmid 4 per slot][nbkfs 4][seed 8 per item] go up;
-    //          [EpifOut 304][n_cur 4 per item][removed 1][err 4][pair 4 per slot] come down
-    uint8_t *depi = nullptr, *dfx = nullptr, *hepi = nullptr, *depi_io = nullptr, *kepi = nullptr;
-    size_t depi_bytes = 0, x_slot = 0, x_rank = 0, e_lm = 0, e_nk = 0, e_sd = 0, e_in = 0, e_out = 0, e_nc = 0, e_rm = 0, e_er = 0, e_pc = 0,
-           epi_bytes = 0;
+    //   depi   the filter's block (EpifLayout at capacity: batch x n_max slots, batch x n_rows rows; device only, grow-only).  Its
+    //          inputs [0, o_up) do not depend on n_rows, so the resident keyframe arrays stay where they are when a step asks for
+    //          more rows and the block is grown (they are then copied again from kf_host).
+    //   dfx    the index block (device only)
+    uint8_t *depi = nullptr, *dfx = nullptr;
+    size_t depi_bytes = 0;
     EpifLayout eL0;                                   // the layout with no rows: where the keyframe arrays lie
     std::vector<uint8_t> kf_host;                     // host copy of the block's [o_kl, o_up)
     std::vector<FeKfHdr> kf_hdr;
     FeStep fe;                                        // the arguments of the step being enqueued
-    // ov2_btracker_last_epi_inputs: as lp_* above
-    bool le_on = false, le_chain = false;
-    EpifLayout le_L;
-    std::vector<int> le_ncur, le_m, le_rows;
-    std::vector<std::vector<int>> le_slot, le_samples;
-    std::vector<uint8_t> le_host;
+    LastInputs le;
+    EpifLayout le_L;                                  // the filter's layout in the last finished epipolar step
     // keyframe detection: device mirrors of the items' current keypoints and of the detector's output, pinned staging
     uint8_t *d_det = nullptr, *h_det = nullptr; size_t det_in_bytes = 0;
     float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
     uint8_t *d_roi = nullptr;                     // detectGFTT: device copy of the caller's roi mask (w x h, allocated with the first one)
     // a step between ov2_btracker_track_frame_begin and _end: what _end needs to finish it
-    struct Pending { bool on = false, tracked = false; int n_active = 0, use_prior = 0; const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n;
-                     // a pose step (ov2_btracker_track_frame_pose_begin): its settings and the per-item inputs _end needs again
-                     bool pose = false; ov2_frame_pose_params pp; PoseLayout L; std::vector<double> Twc; std::vector<uint8_t> req;
+    struct Pending { bool on = false, tracked = false; StepForm form = STEP_PLAIN; int n_active = 0, use_prior = 0;
+                     const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n;
+                     // pose and epi: the settings and the per-item inputs _end needs again (the filter's per-item inputs stay in the
+                     // epipolar block, which the device only reads)
+                     ov2_frame_pose_params pp; PoseLayout L; std::vector<double> Twc; std::vector<uint8_t> req;
                      std::vector<unsigned long long> seed;
-                     // an epipolar + pose step (ov2_btracker_track_frame_epi_pose_begin): the filter's settings (its per-item inputs
-                     // stay in hepi, which the device only reads)
-                     bool epi = false; ov2_epifilter_params ep; EpifLayout eL; } pend;
+                     ov2_epifilter_params ep; EpifLayout eL; } pend;
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
 };
-
-static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static void btracker_free(ov2_btracker *t)
 {
@@ -165,17 +206,10 @@ static void btracker_free(ov2_btracker *t)
         if (t->dimg[i]) (void)hipFree(t->dimg[i]);
         if (t->draw[i]) (void)hipFree(t->draw[i]);
     }
-    if (t->hblk) (void)hipHostFree(t->hblk);
-    if (t->dblk) (void)hipFree(t->dblk);
-    if (t->hmap) (void)hipHostFree(t->hmap);
-    if (t->dmap) (void)hipFree(t->dmap);
-    if (t->hpose) (void)hipHostFree(t->hpose);
-    if (t->dpose) (void)hipFree(t->dpose);
+    for (IoBlock *b : {&t->pt, &t->map, &t->pose, &t->epi}) b->release();
     if (t->dwork) (void)hipFree(t->dwork);
     if (t->depi) (void)hipFree(t->depi);
     if (t->dfx) (void)hipFree(t->dfx);
-    if (t->hepi) (void)hipHostFree(t->hepi);
-    if (t->depi_io) (void)hipFree(t->depi_io);
     if (t->h_det) (void)hipHostFree(t->h_det);
     if (t->d_det) (void)hipFree(t->d_det);
     if (t->h_out) (void)hipHostFree(t->h_out);
@@ -212,78 +246,81 @@ static int enqueue_preprocess(ov2_btracker *t, ov2_ctx *on, ov2_pyr *dst, int wh
     return OV2_OK;
 }
 
-// kltTracking of items [0, n): keypoint block in, the fused LK launch, computeKeypoint, result block out
-// map_use_prior >= 0 (ov2_btracker_track_frame_map): k_prior_frame fills the prior and flag slots from the map side first
-// pose (ov2_btracker_track_frame_pose): the pose set, computePose's chain and the removal bytes follow k_compute_keypoints
-static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur, int n, int map_use_prior = -1,
-                       const ov2_btracker::Pending *pose = nullptr)
+// kltTracking of items [0, P.n_active) for the step P describes: keypoint block in, the fused LK launch, computeKeypoint, result block out
+// map form: k_prior_frame fills the prior and flag slots from the map side first
+// pose form: the pose set, computePose's chain and the removal bytes follow k_compute_keypoints; epi form: with the filter's hook
+static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur, const ov2_btracker::Pending &P)
 {
     ov2_ctx *ctx = t->ctx;
     const ov2_tracker_config &c = t->cfg;
-    if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->dblk, t->hblk, t->in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    uint8_t *k = t->kblk;
-    if (map_use_prior >= 0) {
-        if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->dmap, t->hmap, t->map_bytes, hipMemcpyHostToDevice, ctx->stream));
-        const uint8_t *m = t->kmap;
-        const int rcp = ov2_launch_prior_frame(ctx->stream, t->calib, (double)c.w, (double)c.h, map_use_prior, m + t->m_it,
-                                               (const double *)(m + t->m_T), (const float *)(k + t->o_kps), m + t->m_3d,
-                                               (const double *)(m + t->m_w), (float *)(k + t->o_pri), k + t->o_flg, c.n_max, n);
-        if (rcp != OV2_OK) return rcp;
-    }
-    int rc = ov2_launch_track_klt(ctx->stream, prev, cur, c.win, c.prior_pyr_lvl, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist,
-                                  c.n_max, (const int *)(k + t->o_n), (const float *)(k + t->o_kps), (const float *)(k + t->o_pri),
-                                  k + t->o_flg, (float *)(k + t->o_out), k + t->o_st, nullptr, nullptr, 0.f, ctx->track_impl, n, ctx->lk_acc);
-    if (rc != OV2_OK) return rc;
-    if (t->has_calib) {
-        rc = ov2_launch_compute_keypoints(ctx->stream, t->calib, (const float *)(k + t->o_out), c.n_max, (const int *)(k + t->o_n),
-                                          (float *)(k + t->o_unpx), (double *)(k + t->o_bv), n);
+    const hipStream_t s = ctx->stream;
+    const int n = P.n_active;
+    const BtPointLayout &pl = t->pl;
+    const BtMapLayout &ml = t->ml;
+    uint8_t *k = t->pt.k;
+    const uint8_t *m = t->map.k;
+    int rc = t->pt.upload(s, pl.in_bytes);  if (rc) return rc;
+    if (P.form >= STEP_MAP) {
+        rc = t->map.upload(s, ml.map_bytes);  if (rc) return rc;
+        rc = ov2_launch_prior_frame(s, t->calib, (double)c.w, (double)c.h, P.use_prior ? 1 : 0, m + ml.m_it, (const double *)(m + ml.m_T),
+                                    (const float *)(k + pl.o_kps), m + ml.m_3d, (const double *)(m + ml.m_w), (float *)(k + pl.o_pri),
+                                    k + pl.o_flg, c.n_max, n);
         if (rc != OV2_OK) return rc;
     }
-    if (pose) {
-        if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->dpose, t->hpose, t->q_in, hipMemcpyHostToDevice, ctx->stream));
-        uint8_t *q = t->kpose;
-        const uint8_t *m = t->kmap;
-        bool search = pose->pp.dop3p != 0;
-        for (int b = 0; b < n; b++) search = search || pose->req[(size_t)b];
+    rc = ov2_launch_track_klt(s, prev, cur, c.win, c.prior_pyr_lvl, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist,
+                              c.n_max, (const int *)(k + pl.o_n), (const float *)(k + pl.o_kps), (const float *)(k + pl.o_pri),
+                              k + pl.o_flg, (float *)(k + pl.o_out), k + pl.o_st, nullptr, nullptr, 0.f, ctx->track_impl, n, ctx->lk_acc);
+    if (rc != OV2_OK) return rc;
+    if (t->has_calib) {
+        rc = ov2_launch_compute_keypoints(s, t->calib, (const float *)(k + pl.o_out), c.n_max, (const int *)(k + pl.o_n),
+                                          (float *)(k + pl.o_unpx), (double *)(k + pl.o_bv), n);
+        if (rc != OV2_OK) return rc;
+    }
+    if (P.form >= STEP_POSE) {
+        const BtPoseLayout &ql = t->ql;
+        rc = t->pose.upload(s, ql.q_in);  if (rc) return rc;
+        uint8_t *q = t->pose.k;
+        bool search = P.pp.dop3p != 0;
+        for (int b = 0; b < n; b++) search = search || P.req[(size_t)b];
         ov2_fp_hook hook = nullptr;
-        if (pose->epi) {                                                // the filter between the select and the pack (frameepi.hip)
-            if (!t->zero_copy) OV2_HIP_CHECK(hipMemcpyAsync(t->depi_io, t->hepi, t->e_in, hipMemcpyHostToDevice, ctx->stream));
-            uint8_t *e = t->kepi, *d = t->depi;
-            const EpifLayout &EL = pose->eL;
+        if (P.form == STEP_EPI) {                                       // the filter between the select and the pack (frameepi.hip)
+            const BtEpiLayout &el = t->el;
+            rc = t->epi.upload(s, el.e_in);  if (rc) return rc;
+            uint8_t *e = t->epi.k, *d = t->depi;
+            const EpifLayout &EL = P.eL;
             FeStep &fe = t->fe;
             FeArgs &a = fe.a;
-            a.n_dev = (const int *)(k + t->o_n); a.status = k + t->o_st; a.is3d = m + t->m_3d;
-            a.unpx = (const float2 *)(k + t->o_unpx); a.bv = (const double *)(k + t->o_bv);
-            a.lmid = (const int *)(e + t->e_lm); a.nbkfs = (const int *)(e + t->e_nk); a.seed = (const unsigned long long *)(e + t->e_sd);
-            a.Twc = (const double *)(q + t->q_T); a.hdr = (const FeKfHdr *)t->dfx;
+            a.n_dev = (const int *)(k + pl.o_n); a.status = k + pl.o_st; a.is3d = m + ml.m_3d;
+            a.unpx = (const float2 *)(k + pl.o_unpx); a.bv = (const double *)(k + pl.o_bv);
+            a.lmid = (const int *)(e + el.e_lm); a.nbkfs = (const int *)(e + el.e_nk); a.seed = (const unsigned long long *)(e + el.e_sd);
+            a.Twc = (const double *)(q + ql.q_T); a.hdr = (const FeKfHdr *)t->dfx;
             a.items = (EpifItem *)(d + EL.o_it); a.c_lmid = (int *)(d + EL.o_lm); a.c_unpx = (float2 *)(d + EL.o_un);
             a.c_bv = (double *)(d + EL.o_bv); a.c_is3d = d + EL.o_3d;
-            a.slot = (int *)(t->dfx + t->x_slot); a.rank = (int *)(t->dfx + t->x_rank);
+            a.slot = (int *)(t->dfx + el.x_slot); a.rank = (int *)(t->dfx + el.x_rank);
             a.out = (const EpifOut *)(d + EL.o_out); a.removed = d + EL.o_rm; a.err = (const float *)(d + EL.o_er);
             a.pair_cur = (const int *)(d + EL.o_pc);
             a.sel = nullptr;
-            a.out_io = (EpifOut *)(e + t->e_out); a.ncur_io = (int *)(e + t->e_nc); a.removed_io = e + t->e_rm;
-            a.err_io = (float *)(e + t->e_er); a.pair_io = (int *)(e + t->e_pc);
-            a.n_max = c.n_max; a.n_rows = pose->ep.n_rows;
-            fe.params = &pose->ep; fe.L = EL; fe.block = d; fe.n_active = n;
+            a.out_io = (EpifOut *)(e + el.e_out); a.ncur_io = (int *)(e + el.e_nc); a.removed_io = e + el.e_rm;
+            a.err_io = (float *)(e + el.e_er); a.pair_io = (int *)(e + el.e_pc);
+            a.n_max = c.n_max; a.n_rows = P.ep.n_rows;
+            fe.params = &P.ep; fe.L = EL; fe.block = d; fe.n_active = n;
             hook = ov2_frame_epi_hook;
         }
-        rc = ov2_launch_frame_pose(ctx->stream, &pose->pp.pose, pose->L, n, search, (const int *)(k + t->o_n), k + t->o_st,
-                                   (const float *)(k + t->o_unpx), (const double *)(k + t->o_bv), (const double *)(m + t->m_w), m + t->m_3d,
-                                   (const double *)(q + t->q_T), (const int *)(q + t->q_sc), q + t->q_fl,
-                                   (const unsigned long long *)(q + t->q_seed), t->dwork, (PoseOut *)(q + t->q_out), (int *)(q + t->q_ms),
-                                   q + t->q_rm, hook, &t->fe);
+        FramePoseIo io;
+        io.n_dev = (const int *)(k + pl.o_n); io.status = k + pl.o_st; io.unpx = (const float *)(k + pl.o_unpx); io.bv = (const double *)(k + pl.o_bv);
+        io.wpt = (const double *)(m + ml.m_w); io.is3d = m + ml.m_3d;
+        io.Twc = (const double *)(q + ql.q_T); io.scale = (const int *)(q + ql.q_sc); io.flags = q + ql.q_fl;
+        io.seed = (const unsigned long long *)(q + ql.q_seed);
+        io.work = t->dwork; io.out = (PoseOut *)(q + ql.q_out); io.ms = (int *)(q + ql.q_ms); io.removed_slot = q + ql.q_rm;
+        rc = ov2_launch_frame_pose(s, &P.pp.pose, P.L, n, search, io, hook, &t->fe);
         if (rc != OV2_OK) return rc;
-        if (!t->zero_copy)
-            OV2_HIP_CHECK(hipMemcpyAsync(t->hpose + t->q_out, t->dpose + t->q_out, t->pose_bytes - t->q_out, hipMemcpyDeviceToHost, ctx->stream));
-        if (!t->zero_copy && pose->epi)
-            OV2_HIP_CHECK(hipMemcpyAsync(t->hepi + t->e_out, t->depi_io + t->e_out, t->epi_bytes - t->e_out, hipMemcpyDeviceToHost, ctx->stream));
+        rc = t->pose.download(s, ql.q_out, ql.pose_bytes);
+        if (rc == OV2_OK && P.form == STEP_EPI) rc = t->epi.download(s, t->el.e_out, t->el.epi_bytes);
+        if (rc != OV2_OK) return rc;
     }
-    if (!t->zero_copy)
-        OV2_HIP_CHECK(hipMemcpyAsync(t->hblk + t->o_out, t->dblk + t->o_out, t->blk_bytes - t->o_out, hipMemcpyDeviceToHost, ctx->stream));
-    if (!t->zero_copy && map_use_prior >= 0)                            // the priors and flags the device set come back with the results
-        OV2_HIP_CHECK(hipMemcpyAsync(t->hblk + t->o_pri, t->dblk + t->o_pri, t->in_bytes - t->o_pri, hipMemcpyDeviceToHost, ctx->stream));
-    return OV2_OK;
+    rc = t->pt.download(s, pl.o_out, pl.blk_bytes);
+    if (rc == OV2_OK && P.form >= STEP_MAP) rc = t->pt.download(s, pl.o_pri, pl.in_bytes);   // the priors and flags the device set come back with the results
+    return rc;
 }
 
 // Frames of items [0, n) -> dimg[which] on the main stream, `which` = the staging set the step reads.  Frames that already sit in
@@ -333,42 +370,25 @@ static int stage_and_upload(ov2_btracker *t, int n, const uint8_t *const *img_h,
 static int stage_map(ov2_btracker *t, int n_active, const double *wpt, const uint8_t *is3d, const double *Tcw, const int *n_h)
 {
     const size_t nm = (size_t)t->cfg.n_max;
-    if (!t->hmap) {
-        const size_t slots = nm * (size_t)t->batch;
-        t->m_it = 0; t->m_T = up256(16 * (size_t)t->batch); t->m_w = up256(t->m_T + 56 * (size_t)t->batch); t->m_3d = up256(t->m_w + 24 * slots);
-        t->map_bytes = up256(t->m_3d + slots);
-        uint8_t *h = nullptr, *d = nullptr;
-        hipError_t e = hipHostMalloc((void **)&h, t->map_bytes, hipHostMallocMapped);
-        if (e == hipSuccess && !t->zero_copy) e = hipMalloc((void **)&d, t->map_bytes);
-        void *alias = d;
-        if (e == hipSuccess && t->zero_copy) e = hipHostGetDevicePointer(&alias, h, 0);
-        if (e != hipSuccess || !alias) {
-            if (h) (void)hipHostFree(h);
-            if (d) (void)hipFree(d);
-            (void)hipGetLastError();
-            ov2_set_error("ov2_btracker_track_frame_map: %s", hipGetErrorString(e));
-            return OV2_ENOMEM;
-        }
-        memset(h, 0, t->map_bytes);
-        t->hmap = h; t->dmap = d; t->kmap = (uint8_t *)alias;
-    }
-    int *it = (int *)(t->hmap + t->m_it);
+    if (!t->map.h) { const int rc = t->map.alloc(t->ml.map_bytes, t->zero_copy, false, "ov2_btracker_track_frame_map");  if (rc) return rc; }
+    uint8_t *hmap = t->map.h;
+    const BtMapLayout &ml = t->ml;
+    int *it = (int *)(hmap + ml.m_it);
     for (int b = 0; b < t->batch; b++) {
         it[4 * b] = (int)((size_t)b * nm); it[4 * b + 1] = b < n_active ? n_h[b] : 0; it[4 * b + 2] = it[4 * b + 3] = 0;
     }
-    memcpy(t->hmap + t->m_T, Tcw, 56 * (size_t)n_active);
+    memcpy(hmap + ml.m_T, Tcw, 56 * (size_t)n_active);
     for (int b = 0; b < n_active; b++) {
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
         if (!n) continue;
-        memcpy(t->hmap + t->m_w + 24 * o, wpt + 3 * o, 24 * n);
-        memcpy(t->hmap + t->m_3d + o, is3d + o, n);
+        memcpy(hmap + ml.m_w + 24 * o, wpt + 3 * o, 24 * n);
+        memcpy(hmap + ml.m_3d + o, is3d + o, n);
     }
     return OV2_OK;
 }
 
 // what a pose step refuses beyond the map form's checks (n_active and the counts are known to be in range); *L: the chain's layout
-static int check_pose(const ov2_btracker *t, int n_active, const double *wpt, const uint8_t *is3d, const int *n_h,
-                      const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, PoseLayout *L)
+static int check_pose(const ov2_btracker *t, const StepArgs &A, const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, PoseLayout *L)
 {
     OV2_REQUIRE(pp && in, OV2_EINVAL, "ov2_btracker_track_frame_pose: NULL params / input");
     OV2_REQUIRE(in->Twc_h && in->p3p_req_h && in->seed_h, OV2_EINVAL, "ov2_btracker_track_frame_pose: NULL Twc_h / p3p_req_h / seed_h");
@@ -378,13 +398,13 @@ static int check_pose(const ov2_btracker *t, int n_active, const double *wpt, co
     OV2_REQUIRE(t->cfg.n_max <= OV2_P3P_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds the 2048 points of one pose problem");
     rc = pose_layout(t->batch, t->cfg.n_max, pp->n_rows, L);  if (rc) return rc;
     const size_t nm = (size_t)t->cfg.n_max;
-    for (int b = 0; b < n_active; b++) {
+    for (int b = 0; b < A.n_active; b++) {
         for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(in->Twc_h[7 * (size_t)b + c]), OV2_EINVAL, "Twc not finite");
-        const size_t n = (size_t)(n_h ? n_h[b] : 0), o = (size_t)b * nm;
+        const size_t n = (size_t)(A.n_h ? A.n_h[b] : 0), o = (size_t)b * nm;
         for (size_t i = 0; i < n; i++) {
             if (in->scale_h) OV2_REQUIRE(in->scale_h[o + i] >= -60 && in->scale_h[o + i] <= 60, OV2_EINVAL, "|scale| > 60");
-            if (is3d && wpt && is3d[o + i]) {
-                const double *w = wpt + 3 * (o + i);
+            if (A.is3d_h && A.wpt_h && A.is3d_h[o + i]) {
+                const double *w = A.wpt_h + 3 * (o + i);
                 OV2_REQUIRE(std::isfinite(w[0]) && std::isfinite(w[1]) && std::isfinite(w[2]), OV2_EINVAL, "wpt not finite on a 3-D slot");
             }
         }
@@ -397,42 +417,27 @@ static int check_pose(const ov2_btracker *t, int n_active, const double *wpt, co
 static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, const int *n_h,
                       const PoseLayout &L)
 {
-    const size_t nm = (size_t)t->cfg.n_max, B = (size_t)t->batch, slots = nm * B;
-    if (!t->hpose) {
-        t->q_T = 0; t->q_seed = up256(56 * B); t->q_fl = up256(t->q_seed + 8 * B); t->q_sc = up256(t->q_fl + B); t->q_in = up256(t->q_sc + 4 * slots);
-        t->q_out = t->q_in; t->q_ms = up256(t->q_out + sizeof(PoseOut) * B); t->q_rm = up256(t->q_ms + 8 * B); t->pose_bytes = up256(t->q_rm + slots);
-        uint8_t *h = nullptr, *d = nullptr;
-        hipError_t e = hipHostMalloc((void **)&h, t->pose_bytes, hipHostMallocMapped);
-        if (e == hipSuccess && !t->zero_copy) e = hipMalloc((void **)&d, t->pose_bytes);
-        void *alias = d;
-        if (e == hipSuccess && t->zero_copy) e = hipHostGetDevicePointer(&alias, h, 0);
-        if (e != hipSuccess || !alias) {
-            if (h) (void)hipHostFree(h);
-            if (d) (void)hipFree(d);
-            (void)hipGetLastError();
-            ov2_set_error("ov2_btracker_track_frame_pose: %s", hipGetErrorString(e));
-            return OV2_ENOMEM;
-        }
-        memset(h, 0, t->pose_bytes);
-        t->hpose = h; t->dpose = d; t->kpose = (uint8_t *)alias;
-    }
+    const size_t nm = (size_t)t->cfg.n_max;
+    if (!t->pose.h) { const int rc = t->pose.alloc(t->ql.pose_bytes, t->zero_copy, false, "ov2_btracker_track_frame_pose");  if (rc) return rc; }
     const size_t need = ov2_frame_pose_work_bytes(L);
     if (need > t->work_bytes) {
         OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (the previous step's chain has long finished: _end waited for it)
         if (t->dwork) (void)hipFree(t->dwork);
-        t->dwork = nullptr; t->work_bytes = 0; t->lp_on = false;         // the lists of the last step go with the block
+        t->dwork = nullptr; t->work_bytes = 0; t->lp.on = false;         // the lists of the last step go with the block
         const hipError_t e = hipMalloc((void **)&t->dwork, need);
         if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("ov2_btracker_track_frame_pose: %s", hipGetErrorString(e)); return OV2_ENOMEM; }
         t->work_bytes = need;
     }
-    memcpy(t->hpose + t->q_T, in->Twc_h, 56 * (size_t)n_active);
-    memcpy(t->hpose + t->q_seed, in->seed_h, 8 * (size_t)n_active);
-    uint8_t *fl = t->hpose + t->q_fl;
+    uint8_t *hpose = t->pose.h;
+    const BtPoseLayout &ql = t->ql;
+    memcpy(hpose + ql.q_T, in->Twc_h, 56 * (size_t)n_active);
+    memcpy(hpose + ql.q_seed, in->seed_h, 8 * (size_t)n_active);
+    uint8_t *fl = hpose + ql.q_fl;
     for (int b = 0; b < n_active; b++) {
         const int req = in->p3p_req_h[b] != 0;
         fl[b] = (uint8_t)(req | ((req || pp->dop3p) ? 2 : 0));
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
-        int *sc = (int *)(t->hpose + t->q_sc) + o;
+        int *sc = (int *)(hpose + ql.q_sc) + o;
         if (in->scale_h) memcpy(sc, in->scale_h + o, 4 * n); else memset(sc, 0, 4 * n);
     }
     return OV2_OK;
@@ -452,37 +457,27 @@ static int check_epi(const ov2_btracker *t, const ov2_frame_epi_pose_params *pp,
 // in the block's input section, whose offsets do not depend on the rows: a grown block gets them again from the host copy.
 static int ensure_epi(ov2_btracker *t, const EpifLayout *L)
 {
-    const size_t nm = (size_t)t->cfg.n_max, B = (size_t)t->batch, slots = nm * B;
+    const char *who = "ov2_btracker_track_frame_epi_pose";
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    if (!t->hepi) {
+    if (!t->epi.h) {
         EpifLayout L0;
-        const int rc = epif_layout_capacity(t->batch, t->cfg.n_max, 0, &L0);  if (rc) return rc;
-        t->e_lm = 0; t->e_nk = up256(4 * slots); t->e_sd = up256(t->e_nk + 4 * B); t->e_in = up256(t->e_sd + 8 * B);
-        t->e_out = t->e_in; t->e_nc = up256(t->e_out + sizeof(EpifOut) * B); t->e_rm = up256(t->e_nc + 4 * B);
-        t->e_er = up256(t->e_rm + slots); t->e_pc = up256(t->e_er + 4 * slots); t->epi_bytes = up256(t->e_pc + 4 * slots);
-        t->x_slot = up256(sizeof(FeKfHdr) * B); t->x_rank = t->x_slot + 4 * slots;
-        const size_t fx_bytes = t->x_rank + 4 * slots;
-        uint8_t *h = nullptr, *d = nullptr, *fx = nullptr;
-        hipError_t e = hipHostMalloc((void **)&h, t->epi_bytes, hipHostMallocMapped);
-        if (e == hipSuccess && !t->zero_copy) e = hipMalloc((void **)&d, t->epi_bytes);
-        void *alias = d;
-        if (e == hipSuccess && t->zero_copy) e = hipHostGetDevicePointer(&alias, h, 0);
-        if (e == hipSuccess) e = hipMalloc((void **)&fx, fx_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(fx, 0, fx_bytes, t->ctx->stream);       // no item has a keyframe yet
+        int rc = epif_layout_capacity(t->batch, t->cfg.n_max, 0, &L0);  if (rc) return rc;
+        rc = t->epi.alloc(t->el.epi_bytes, t->zero_copy, false, who);  if (rc) return rc;
+        uint8_t *fx = nullptr;
+        hipError_t e = hipMalloc((void **)&fx, t->el.fx_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(fx, 0, t->el.fx_bytes, t->ctx->stream);       // no item has a keyframe yet
         if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
-        if (e != hipSuccess || !alias) {
-            if (h) (void)hipHostFree(h);
-            if (d) (void)hipFree(d);
+        if (e != hipSuccess) {
+            t->epi.release();
             if (fx) (void)hipFree(fx);
             (void)hipGetLastError();
-            ov2_set_error("ov2_btracker_track_frame_epi_pose: %s", hipGetErrorString(e));
+            ov2_set_error("%s: %s", who, hipGetErrorString(e));
             return OV2_ENOMEM;
         }
-        memset(h, 0, t->epi_bytes);
-        t->hepi = h; t->depi_io = d; t->kepi = (uint8_t *)alias; t->dfx = fx;
+        t->dfx = fx;
         t->eL0 = L0;
         t->kf_host.assign(L0.o_up - L0.o_kl, 0);
-        t->kf_hdr.assign(B, FeKfHdr());
+        t->kf_hdr.assign((size_t)t->batch, FeKfHdr());
     }
     const size_t need = L ? L->total : t->eL0.total;
     if (!t->depi || need > t->depi_bytes) {
@@ -494,11 +489,11 @@ static int ensure_epi(ov2_btracker *t, const EpifLayout *L)
         if (e != hipSuccess) {
             if (nd) (void)hipFree(nd);
             (void)hipGetLastError();
-            ov2_set_error("ov2_btracker_track_frame_epi_pose: %s", hipGetErrorString(e));
+            ov2_set_error("%s: %s", who, hipGetErrorString(e));
             return OV2_ENOMEM;
         }
         if (t->depi) (void)hipFree(t->depi);
-        t->depi = nd; t->depi_bytes = need; t->le_on = false;           // the lists of the last step go with the block
+        t->depi = nd; t->depi_bytes = need; t->le.on = false;           // the lists of the last step go with the block
     }
     return OV2_OK;
 }
@@ -508,71 +503,28 @@ static void stage_epi(ov2_btracker *t, int n_active, const ov2_frame_epi_pose_in
 {
     const size_t nm = (size_t)t->cfg.n_max;
     for (int b = 0; b < n_active; b++)
-        if (n_h[b] > 0) memcpy(t->hepi + t->e_lm + 4 * nm * (size_t)b, in->lmid_h + nm * (size_t)b, 4 * (size_t)n_h[b]);
-    memcpy(t->hepi + t->e_nk, in->nbkfs_h, 4 * (size_t)n_active);
-    memcpy(t->hepi + t->e_sd, in->epi_seed_h, 8 * (size_t)n_active);
+        if (n_h[b] > 0) memcpy(t->epi.h + t->el.e_lm + 4 * nm * (size_t)b, in->lmid_h + nm * (size_t)b, 4 * (size_t)n_h[b]);
+    memcpy(t->epi.h + t->el.e_nk, in->nbkfs_h, 4 * (size_t)n_active);
+    memcpy(t->epi.h + t->el.e_sd, in->epi_seed_h, 8 * (size_t)n_active);
 }
 
 static void stage_points(ov2_btracker *t, int n_active, const float *kps, const float *pri, const uint8_t *has_prior, const int *n_h, int use_prior)
 {
     const size_t nm = (size_t)t->cfg.n_max;
-    int *nd = (int *)(t->hblk + t->o_n);
+    uint8_t *hblk = t->pt.h;
+    const BtPointLayout &pl = t->pl;
+    int *nd = (int *)(hblk + pl.o_n);
     for (int b = 0; b < t->batch; b++) nd[b] = b < n_active ? n_h[b] : 0;
     for (int b = 0; b < n_active; b++) {
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
         if (!n) continue;
-        memcpy(t->hblk + t->o_kps + 8 * o, kps + 2 * o, 8 * n);
+        memcpy(hblk + pl.o_kps + 8 * o, kps + 2 * o, 8 * n);
         if (!pri) continue;                                              // the map form: k_prior_frame writes both
-        memcpy(t->hblk + t->o_pri + 8 * o, pri + 2 * o, 8 * n);
-        uint8_t *f = t->hblk + t->o_flg + o;
+        memcpy(hblk + pl.o_pri + 8 * o, pri + 2 * o, 8 * n);
+        uint8_t *f = hblk + pl.o_flg + o;
         if (use_prior && has_prior) for (size_t i = 0; i < n; i++) f[i] = has_prior[o + i] ? 1 : 0;
         else memset(f, 0, n);
     }
-}
-
-// the cross-keypoint rule of visual_front_end.cpp:225-230 for item b (same as track.hip: apply_p3p_rule), on the item's views
-static int apply_p3p_rule(ov2_btracker *t, int b, const float *kps, const uint8_t *has_prior, int use_prior, int n, float *out_xy,
-                          uint8_t *status, int *p3p_req)
-{
-    size_t nbkps = 0, nbgood = 0;
-    if (use_prior && has_prior)
-        for (int i = 0; i < n; i++) if (has_prior[i]) { nbkps++; if ((status[i] & 3) == 1) nbgood++; }
-    int p3p = 0;
-    if (nbkps > 0 && (double)nbgood < 0.33 * (double)nbkps) {
-        p3p = 1;                                                        // vpriors = vkps for the second call (:229)
-        std::vector<int> idx;
-        for (int i = 0; i < n; i++) if (status[i] & 2) idx.push_back(i);
-        if (!idx.empty()) {
-            const int m = (int)idx.size();
-            std::vector<float> k2(2 * (size_t)m), p2(2 * (size_t)m);
-            std::vector<uint8_t> s2((size_t)m);
-            for (int j = 0; j < m; j++) { k2[2 * j] = p2[2 * j] = kps[2 * idx[j]]; k2[2 * j + 1] = p2[2 * j + 1] = kps[2 * idx[j] + 1]; }
-            const ov2_tracker_config &c = t->cfg;
-            const int rc = ov2_fb_klt(t->ctx, t->view[t->prev()][b], t->view[t->cur][b], c.win, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th,
-                                      c.fb_dist, k2.data(), p2.data(), m, s2.data(), nullptr);
-            if (rc != OV2_OK) return rc;
-            for (int j = 0; j < m; j++) {
-                out_xy[2 * idx[j]] = p2[2 * j]; out_xy[2 * idx[j] + 1] = p2[2 * j + 1];
-                status[idx[j]] = (uint8_t)(2 | (s2[j] ? 1 : 0));
-            }
-            if (t->has_calib) {                                        // their undistorted pixels / bearings follow the new positions
-                std::vector<float> u2(2 * (size_t)m);
-                std::vector<double> b2(3 * (size_t)m);
-                const KpCalib &kc = t->calib;
-                const double Kk[4] = {kc.fx, kc.fy, kc.cx, kc.cy};
-                const int rck = ov2_compute_keypoints(t->ctx, kc.model, Kk, kc.nD ? kc.k : nullptr, kc.nD, kc.iK, p2.data(), m, u2.data(), b2.data());
-                if (rck != OV2_OK) return rck;
-                float *un = (float *)(t->hblk + t->o_unpx) + 2 * (size_t)b * t->cfg.n_max;
-                double *bv = (double *)(t->hblk + t->o_bv) + 3 * (size_t)b * t->cfg.n_max;
-                for (int j = 0; j < m; j++) {
-                    memcpy(un + 2 * (size_t)idx[j], &u2[2 * (size_t)j], 8);
-                    memcpy(bv + 3 * (size_t)idx[j], &b2[3 * (size_t)j], 24);
-                }
-            }
-        }
-    }
-    if (p3p_req) *p3p_req = p3p;
-    return OV2_OK;
 }
 
 // mode 0: detectGridFAST, 1: detectSingleScale, 2: detectGFTT (roi_h / roi_stride / gp / nbmax_h; cell unused)
@@ -652,12 +604,11 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
         }
     }
     if (rc != OV2_OK) { btracker_free(t); return rc; }
-    t->img_pitch = up16((size_t)cfg->w);
-    t->img_bytes = up256(t->img_pitch * (size_t)cfg->h);
-    const size_t nm = (size_t)cfg->n_max * (size_t)batch;
-    t->o_n = 0; t->o_kps = up256(4 * (size_t)batch); t->o_pri = t->o_kps + 8 * nm; t->o_flg = t->o_pri + 8 * nm; t->in_bytes = up256(t->o_flg + nm);
-    t->o_out = t->in_bytes; t->o_st = t->o_out + 8 * nm; t->o_unpx = up256(t->o_st + nm); t->o_bv = up256(t->o_unpx + 8 * nm); t->blk_bytes = t->o_bv + 24 * nm;
-    t->det_in_bytes = up256(4 * (size_t)batch) + 8 * nm;
+    t->img_pitch = bt_img_pitch(cfg->w);
+    t->img_bytes = bt_img_bytes(cfg->w, cfg->h);
+    t->pl = bt_point_layout(batch, cfg->n_max); t->ml = bt_map_layout(batch, cfg->n_max);
+    t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max);
+    t->det_in_bytes = bt_det_in_bytes(batch, cfg->n_max);
     hipError_t e = hipSuccess;
     for (int i = 0; i < BT_IMG_SETS && e == hipSuccess; i++) {
         e = hipHostMalloc((void **)&t->himg[i], t->img_bytes * batch + 256, hipHostMallocDefault);
@@ -674,22 +625,15 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&t->ps, hipStreamNonBlocking, prio);
     }
     if (e == hipSuccess) e = hipMalloc((void **)&t->lut, (size_t)batch * (cfg->use_clahe ? (size_t)cfg->tiles_x * cfg->tiles_y : 1) * 256 + 256);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&t->hblk, t->blk_bytes, hipHostMallocMapped);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->dblk, t->blk_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(t->dblk, 0, t->blk_bytes, ctx->stream);
+    // the kernels read / write the pinned point block through its device alias (no staging copies); a device mirror is the fallback
+    if (e == hipSuccess && (rc = t->pt.alloc(t->pl.blk_bytes, t->zero_copy, true, "ov2_btracker_create")) != OV2_OK) { btracker_free(t); return rc; }
+    if (e == hipSuccess && t->pt.d) e = hipMemsetAsync(t->pt.d, 0, t->pl.blk_bytes, ctx->stream);
     if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_det, t->det_in_bytes, hipHostMallocDefault);
     if (e == hipSuccess) e = hipMalloc((void **)&t->d_det, t->det_in_bytes);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { ov2_set_error("ov2_btracker_create: %s", hipGetErrorString(e)); btracker_free(t); return OV2_ENOMEM; }
-    memset(t->hblk, 0, t->blk_bytes);
     memset(t->h_det, 0, t->det_in_bytes);
     t->side.device = ctx->device; t->side.stream = t->ps; t->side.owns_stream = false;
-    t->kblk = t->dblk;
-    {   // the kernels read / write the pinned block through its device alias (no staging copies); the device block is the fallback
-        void *alias = nullptr;
-        if (hipHostGetDevicePointer(&alias, t->hblk, 0) == hipSuccess && alias) { t->kblk = (uint8_t *)alias; t->zero_copy = true; }
-        else (void)hipGetLastError();
-    }
     *out = t;
     return OV2_OK;
 }
@@ -781,44 +725,44 @@ int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
 
 } // extern "C"
 
-// the forms of the step's first half.  map: the priors come from the device (wpt_h / is3d_h / Tcw_h), prior_xy_h / has_prior_h are unused;
-// pose (a map form): the pose of ov2_btracker_track_frame_pose follows in the same enqueue
-static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
-                             const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior, bool map,
-                             const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, bool pose = false,
-                             const ov2_frame_pose_params *pp = nullptr, const ov2_frame_pose_input *pin = nullptr, bool epi = false,
-                             const ov2_frame_epi_pose_params *epp = nullptr, const ov2_frame_epi_pose_input *ein = nullptr)
+// the step's first half, for every form (StepArgs)
+static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
 {
-    OV2_REQUIRE(t && img_h, OV2_EINVAL, "NULL argument");
+    const int n_active = A.n_active;
+    const int *n_h = A.n_h;
+    const bool map = A.form >= STEP_MAP, pose = A.form >= STEP_POSE, epi = A.form == STEP_EPI;
+    OV2_REQUIRE(t && A.img_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
-    OV2_REQUIRE(stride >= t->cfg.w, OV2_EINVAL, "stride < width");
+    OV2_REQUIRE(A.stride >= t->cfg.w, OV2_EINVAL, "stride < width");
     const size_t nm = (size_t)t->cfg.n_max;
     int n_total = 0;
     for (int b = 0; b < n_active; b++) {
-        OV2_REQUIRE(img_h[b] != nullptr, OV2_EINVAL, "NULL frame of an active item");
+        OV2_REQUIRE(A.img_h[b] != nullptr, OV2_EINVAL, "NULL frame of an active item");
         const int n = n_h ? n_h[b] : 0;
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
         n_total += n;
     }
-    if (map) OV2_REQUIRE(n_total == 0 || (kps_xy_h && wpt_h && is3d_h && Tcw_h && n_h), OV2_EINVAL, "NULL point buffer");
-    else OV2_REQUIRE(n_total == 0 || (kps_xy_h && prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
+    if (map) OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.wpt_h && A.is3d_h && A.Tcw_h && n_h), OV2_EINVAL, "NULL point buffer");
+    else OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
+    const ov2_frame_pose_params *pp = A.pp;
+    const ov2_frame_pose_input *pin = A.pin;
     PoseLayout poseL;
     EpifLayout epiL;
-    if (epi) {                                                           // (pp / pin: the pose halves of epp / ein, or NULL with them)
-        OV2_REQUIRE(epp && ein, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
-        pp = &epp->pose; pin = &ein->pose;
+    if (epi) {                                                           // (pp / pin: the pose halves of epp / ein)
+        OV2_REQUIRE(A.epp && A.ein, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
+        pp = &A.epp->pose; pin = &A.ein->pose;
     }
-    if (pose) { const int rcp = check_pose(t, n_active, wpt_h, is3d_h, n_h, pp, pin, &poseL);  if (rcp != OV2_OK) return rcp; }
-    if (epi) { const int rce = check_epi(t, epp, ein, &epiL);  if (rce != OV2_OK) return rce; }
+    if (pose) { const int rcp = check_pose(t, A, pp, pin, &poseL);  if (rcp != OV2_OK) return rcp; }
+    if (epi) { const int rce = check_epi(t, A.epp, A.ein, &epiL);  if (rce != OV2_OK) return rce; }
     for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = t->last_pn[(size_t)b] = 0;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     int which = 0;
     bool prepared = false;
     t->raw_which = -1;                                                   // staging may rewrite any set
-    int rc = stage_and_upload(t, n_active, img_h, stride, &which, &prepared);
+    int rc = stage_and_upload(t, n_active, A.img_h, A.stride, &which, &prepared);
     if (rc != OV2_OK) return rc;
     // preprocessImage: already under way on the prep stream (the context's stream waits for the pyramids' event), or in order here
     const int old_cur = t->cur;
@@ -833,46 +777,54 @@ static int track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const
     auto commit = [&]() { if (prepared) t->prepq.pop_front(); else t->pre_count++; t->frames++; t->raw_which = which; t->raw_n = n_active; };
     t->cur = (int)(t->frames % BT_SETS);                                 // prev_pyr_.swap(cur_pyr_)  (:1169): frame k lives in set k % BT_SETS
     ov2_btracker::Pending &P = t->pend;
-    P.n_active = n_active; P.use_prior = klt_use_prior; P.kps = kps_xy_h; P.has_prior = has_prior_h;
+    P.form = A.form; P.n_active = n_active; P.use_prior = A.klt_use_prior; P.kps = A.kps_xy_h; P.has_prior = A.has_prior_h;
     P.n.assign((size_t)n_active, 0);
     if (n_h) for (int b = 0; b < n_active; b++) P.n[(size_t)b] = n_h[b];
-    P.pose = pose;
     if (pose) {
         P.pp = *pp; P.L = poseL;
         P.Twc.assign(pin->Twc_h, pin->Twc_h + 7 * (size_t)n_active);
         P.req.assign(pin->p3p_req_h, pin->p3p_req_h + n_active);
         P.seed.assign(pin->seed_h, pin->seed_h + n_active);
     }
-    P.epi = epi;
-    if (epi) { P.ep = epp->epi; P.eL = epiL; }
-    if (t->frames == 0 || n_total == 0) {
-        // first frame (trackMono returns right after preprocessImage) or nothing to track anywhere
-        rc = preprocess();
-        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
-        commit();
-        P.tracked = false; P.on = true;
-        return OV2_OK;
-    }
-    if (map) {
-        rc = stage_map(t, n_active, wpt_h, is3d_h, Tcw_h, n_h);
-        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
-        P.has_prior = t->hblk + t->o_flg;                                // the flags the device sets: same slots as the caller's array
-    }
-    if (pose) {
-        rc = stage_pose(t, n_active, pp, pin, n_h, poseL);
-        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
-    }
-    if (epi) {
-        rc = ensure_epi(t, &epiL);
-        if (rc != OV2_OK) { t->cur = old_cur; return rc; }
-        stage_epi(t, n_active, ein, n_h);
-    }
-    stage_points(t, n_active, kps_xy_h, map ? nullptr : prior_xy_h, has_prior_h, n_h, klt_use_prior);
-    rc = preprocess();
-    if (rc == OV2_OK) rc = enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], n_active, map ? (klt_use_prior ? 1 : 0) : -1, pose ? &P : nullptr);
+    if (epi) { P.ep = A.epp->epi; P.eL = epiL; }
+    // the step proper: the form's blocks staged (and allocated or grown by the first step that needs them), then the enqueue
+    auto track = [&]() -> int {
+        int r = OV2_OK;
+        if (map) {
+            r = stage_map(t, n_active, A.wpt_h, A.is3d_h, A.Tcw_h, n_h);  if (r) return r;
+            P.has_prior = t->pt.h + t->pl.o_flg;                         // the flags the device sets: same slots as the caller's array
+        }
+        if (pose) { r = stage_pose(t, n_active, pp, pin, n_h, poseL);  if (r) return r; }
+        if (epi) {
+            r = ensure_epi(t, &epiL);  if (r) return r;
+            stage_epi(t, n_active, A.ein, n_h);
+        }
+        stage_points(t, n_active, A.kps_xy_h, map ? nullptr : A.prior_xy_h, A.has_prior_h, n_h, A.klt_use_prior);
+        r = preprocess();
+        return r ? r : enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], P);
+    };
+    // the first frame (trackMono returns right after preprocessImage) and a step with nothing to track anywhere only pre-process
+    const bool tracked = t->frames > 0 && n_total > 0;
+    rc = tracked ? track() : preprocess();
     if (rc != OV2_OK) { t->cur = old_cur; return rc; }
     commit();
-    P.tracked = true; P.on = true;
+    P.tracked = tracked; P.on = true;
+    return OV2_OK;
+}
+
+// What the one-call forms check before anything is enqueued: the result buffers.  pose / epi: the result arrays of those forms (or
+// NULL).  Arguments that track_frame_begin refuses are left to it.
+static int check_outputs(const ov2_btracker *t, int n_active, const int *n_h, const float *out_xy_h, const uint8_t *status_h,
+                         const ov2_pose_result *pose, const ov2_epifilter_result *epi)
+{
+    if (!(t && n_active >= 1 && n_active <= t->batch && n_h)) return OV2_OK;
+    int n_total = 0;
+    for (int b = 0; b < n_active; b++) {
+        n_total += n_h[b] > 0 ? n_h[b] : 0;
+        if (pose) OV2_REQUIRE(n_h[b] <= 0 || (pose[b].removed && (!epi || epi[b].removed)), OV2_EINVAL, "NULL result buffer (removed)");
+        if (epi) OV2_REQUIRE(!epi[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
+    }
+    OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
     return OV2_OK;
 }
 
@@ -881,16 +833,40 @@ extern "C" {
 int ov2_btracker_track_frame_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
                                    const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior)
 {
-    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, prior_xy_h, has_prior_h, n_h, klt_use_prior, false, nullptr, nullptr, nullptr);
+    StepArgs A;
+    A.n_active = n_active; A.img_h = img_h; A.stride = stride; A.kps_xy_h = kps_xy_h; A.n_h = n_h; A.klt_use_prior = klt_use_prior;
+    A.prior_xy_h = prior_xy_h; A.has_prior_h = has_prior_h;
+    return track_frame_begin(t, A);
 }
 
 int ov2_btracker_track_frame_map_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
                                        const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior)
 {
-    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h);
+    StepArgs A;
+    A.form = STEP_MAP; A.n_active = n_active; A.img_h = img_h; A.stride = stride; A.kps_xy_h = kps_xy_h; A.n_h = n_h; A.klt_use_prior = klt_use_prior;
+    A.wpt_h = wpt_h; A.is3d_h = is3d_h; A.Tcw_h = Tcw_h;
+    return track_frame_begin(t, A);
 }
 
 } // extern "C"
+
+// A query of the last inputs of item b: the slot list and the table's rows (row_bytes each: 16 the pose, 32 the
+// filter), from the host lists where the rule re-ran the item, else from the device block (slot_d / tab_d: the item's)
+static int last_inputs_fetch(const ov2_btracker *t, const LastInputs &r, size_t b, int *slot_idx, int *samples, const uint8_t *slot_d,
+                             const uint8_t *tab_d, size_t row_bytes)
+{
+    const int n = r.ncur[b], rows = r.rows[b];
+    if (r.host[b]) {
+        if (slot_idx && n > 0) memcpy(slot_idx, r.slot[b].data(), 4 * (size_t)n);
+        if (samples && rows > 0) memcpy(samples, r.samples[b].data(), row_bytes * (size_t)rows);
+        return OV2_OK;
+    }
+    if (!r.chain || (n <= 0 && rows <= 0)) return OV2_OK;
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    if (slot_idx && n > 0 && n <= t->cfg.n_max) OV2_HIP_CHECK(hipMemcpy(slot_idx, slot_d, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    if (samples && rows > 0) OV2_HIP_CHECK(hipMemcpy(samples, tab_d, row_bytes * (size_t)rows, hipMemcpyDeviceToHost));
+    return OV2_OK;
+}
 
 static void pose_store(ov2_pose_result &r, const PoseOut &o)
 {
@@ -905,13 +881,34 @@ static void pose_store(ov2_pose_result &r, const PoseOut &o)
     }
 }
 
+// a result as a step leaves it where no chain ran: the caller's pointers kept, their n bytes / values and everything else cleared
+static void pose_reset(ov2_pose_result &r, int n, const double *Twc, int req)
+{
+    uint8_t *removed = r.removed;
+    memset(&r, 0, sizeof(r));
+    r.removed = removed;
+    if (n > 0) memset(removed, 0, (size_t)n);
+    memcpy(r.Twc, Twc, 56);
+    r.action = OV2_POSE_TOO_FEW; r.p3p_req_out = req != 0;
+}
+
+static void epi_reset(ov2_epifilter_result &r, int n)
+{
+    const ov2_epifilter_result keep = r;
+    memset(&r, 0, sizeof(r));
+    r.removed = keep.removed; r.pair_cur = keep.pair_cur; r.err = keep.err;
+    r.action = OV2_EPIF_TOO_FEW_KPS;
+    if (n > 0) memset(r.removed, 0, (size_t)n);
+    if (n > 0 && r.err) memset(r.err, 0, 4 * (size_t)n);
+}
+
 // The items where the 33 % rule fired (`redo`), after their retry: the pose set from the final status, the step's unpx / bv as the
 // retry left them, a table drawn from the new m, and ov2_compute_pose_batch over just those items with do_p3p = p3p_req = 1
 // excl (or NULL): one byte per slot, laid out like status_h -- a slot the filter removed is not in the pose set
-static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_t *status_h, ov2_pose_result *results,
-                     const uint8_t *excl = nullptr)
+static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_t *status_h, ov2_pose_result *results, const uint8_t *excl)
 {
     const ov2_btracker::Pending &P = t->pend;
+    const uint8_t *hblk = t->pt.h, *hmap = t->map.h;
     const size_t nm = (size_t)t->cfg.n_max, R = redo.size();
     std::vector<std::vector<double>> unpx(R), wpt(R), bv(R);
     std::vector<std::vector<int>> scale(R);
@@ -922,11 +919,11 @@ static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_
         const int b = redo[k];
         const size_t o = (size_t)b * nm;
         const int n = P.n[(size_t)b];
-        const float *un = (const float *)(t->hblk + t->o_unpx) + 2 * o;
-        const double *bvs = (const double *)(t->hblk + t->o_bv) + 3 * o, *w = (const double *)(t->hmap + t->m_w) + 3 * o;
-        const uint8_t *d3 = t->hmap + t->m_3d + o;
-        const int *sc = (const int *)(t->hpose + t->q_sc) + o;
-        std::vector<int> &slot = t->lp_slot[(size_t)b];
+        const float *un = (const float *)(hblk + t->pl.o_unpx) + 2 * o;
+        const double *bvs = (const double *)(hblk + t->pl.o_bv) + 3 * o, *w = (const double *)(hmap + t->ml.m_w) + 3 * o;
+        const uint8_t *d3 = hmap + t->ml.m_3d + o;
+        const int *sc = (const int *)(t->pose.h + t->ql.q_sc) + o;
+        std::vector<int> &slot = t->lp.slot[(size_t)b];
         slot.clear();
         for (int i = 0; i < n; i++)
             if ((status_h[o + i] & 3) == 1 && d3[i] && !(excl && excl[o + i])) {
@@ -936,7 +933,7 @@ static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_
                 scale[k].push_back(sc[i]);
             }
         const int m = (int)slot.size();
-        std::vector<int> &tab = t->lp_samples[(size_t)b];
+        std::vector<int> &tab = t->lp.samples[(size_t)b];
         tab.clear();
         if (m >= 4 && P.pp.n_rows > 0) {
             tab.resize(4 * (size_t)P.pp.n_rows);
@@ -948,19 +945,18 @@ static int pose_redo(ov2_btracker *t, const std::vector<int> &redo, const uint8_
         q.n = m; q.unpx = unpx[k].data(); q.wpt = wpt[k].data(); q.scale = scale[k].data(); q.Twc = P.Twc.data() + 7 * (size_t)b;
         q.bv = bv[k].data(); q.do_p3p = 1; q.p3p_req = 1; q.n_rows = m >= 4 ? P.pp.n_rows : 0; q.samples = tab.empty() ? nullptr : tab.data();
         rs[k].removed = rm[k].data();
-        t->lp_m[(size_t)b] = m; t->lp_rows[(size_t)b] = q.n_rows; t->lp_host[(size_t)b] = 1;
+        t->lp.ncur[(size_t)b] = t->lp.m[(size_t)b] = m; t->lp.rows[(size_t)b] = q.n_rows; t->lp.host[(size_t)b] = 1;
     }
     const int rc = ov2_compute_pose_batch(t->ctx, &P.pp.pose, (int)R, pb.data(), rs.data());
     if (rc != OV2_OK) return rc;
     for (size_t k = 0; k < R; k++) {
         const int b = redo[k];
         ov2_pose_result &r = results[b];
-        uint8_t *removed = r.removed;
+        pose_reset(r, P.n[(size_t)b], P.Twc.data() + 7 * (size_t)b, 1);
+        rs[k].removed = r.removed;                                       // the second run's record, the caller's (cleared) bytes
         r = rs[k];
-        r.removed = removed;
-        if (P.n[(size_t)b] > 0) memset(removed, 0, (size_t)P.n[(size_t)b]);
-        const std::vector<int> &slot = t->lp_slot[(size_t)b];
-        for (size_t j = 0; j < slot.size(); j++) removed[slot[j]] = rm[k][j];
+        const std::vector<int> &slot = t->lp.slot[(size_t)b];
+        for (size_t j = 0; j < slot.size(); j++) r.removed[slot[j]] = rm[k][j];
     }
     return OV2_OK;
 }
@@ -989,8 +985,8 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
     const int n_rows = P.ep.n_rows;
     const EpifLayout &L0 = t->eL0;
     const uint8_t *kh = t->kf_host.data();
-    const int *lmid_h = (const int *)(t->hepi + t->e_lm), *nbkfs_h = (const int *)(t->hepi + t->e_nk);    // as the step staged them
-    const unsigned long long *seed_h = (const unsigned long long *)(t->hepi + t->e_sd);
+    const int *lmid_h = (const int *)(t->epi.h + t->el.e_lm), *nbkfs_h = (const int *)(t->epi.h + t->el.e_nk);    // as the step staged them
+    const unsigned long long *seed_h = (const unsigned long long *)(t->epi.h + t->el.e_sd);
     std::vector<std::vector<int>> lmid(R), pair(R);
     std::vector<std::vector<float>> px(R), unpx(R), err(R);
     std::vector<std::vector<double>> bv(R);
@@ -1002,10 +998,10 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
         const int b = redo[k];
         const size_t o = (size_t)b * nm;
         const int n = P.n[(size_t)b];
-        const float *un = (const float *)(t->hblk + t->o_unpx) + 2 * o;
-        const double *bvs = (const double *)(t->hblk + t->o_bv) + 3 * o;
-        const uint8_t *f3 = t->hmap + t->m_3d + o;
-        std::vector<int> &slot = t->le_slot[(size_t)b];
+        const float *un = (const float *)(t->pt.h + t->pl.o_unpx) + 2 * o;
+        const double *bvs = (const double *)(t->pt.h + t->pl.o_bv) + 3 * o;
+        const uint8_t *f3 = t->map.h + t->ml.m_3d + o;
+        std::vector<int> &slot = t->le.slot[(size_t)b];
         slot.clear();
         for (int i = 0; i < n; i++)
             if ((status_h[o + i] & 3) == 1) {
@@ -1020,7 +1016,7 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
         const size_t room = (size_t)(nc > 0 ? nc : 1);
         lmid[k].resize(room); px[k].resize(2 * room); unpx[k].resize(2 * room); bv[k].resize(3 * room); d3[k].resize(room);
         rm[k].assign(room, 0); pair[k].assign(room, 0); err[k].assign(room, 0.f);
-        std::vector<int> &tab = t->le_samples[(size_t)b];
+        std::vector<int> &tab = t->le.samples[(size_t)b];
         tab.assign(8 * (size_t)(n_rows > 0 ? n_rows : 1), -1);
         const FeKfHdr &h = t->kf_hdr[(size_t)b];
         ov2_epifilter_item &q = items[k];
@@ -1040,12 +1036,11 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
         const int b = redo[k];
         const size_t o = (size_t)b * nm;
         const int n = P.n[(size_t)b];
-        const std::vector<int> &slot = t->le_slot[(size_t)b];
-        ov2_epifilter_result &r = results[b], keep = results[b];
-        r = rs[k];
-        r.removed = keep.removed; r.pair_cur = keep.pair_cur; r.err = keep.err; r.trace_samples = nullptr;
-        if (n > 0) memset(r.removed, 0, (size_t)n);
-        if (r.err && n > 0) memset(r.err, 0, 4 * (size_t)n);
+        const std::vector<int> &slot = t->le.slot[(size_t)b];
+        ov2_epifilter_result &r = results[b];
+        epi_reset(r, n);
+        rs[k].removed = r.removed; rs[k].pair_cur = r.pair_cur; rs[k].err = r.err; rs[k].trace_samples = nullptr;
+        r = rs[k];                                                       // the second run's record, the caller's (cleared) arrays
         for (size_t j = 0; j < slot.size(); j++) {
             r.removed[slot[j]] = rm[k][j];
             if (r.err) r.err[slot[j]] = err[k][j];
@@ -1054,8 +1049,8 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
         if (r.pair_cur)
             for (int j = 0; j < r.m && j < (int)slot.size(); j++)
                 r.pair_cur[j] = (unsigned)pair[k][(size_t)j] < slot.size() ? slot[(size_t)pair[k][(size_t)j]] : -1;
-        t->le_ncur[(size_t)b] = (int)slot.size(); t->le_m[(size_t)b] = r.m;
-        t->le_rows[(size_t)b] = epi_rows_used(r.action, r.m, n_rows); t->le_host[(size_t)b] = 1;
+        t->le.ncur[(size_t)b] = (int)slot.size(); t->le.m[(size_t)b] = r.m;
+        t->le.rows[(size_t)b] = epi_rows_used(r.action, r.m, n_rows); t->le.host[(size_t)b] = 1;
     }
     return OV2_OK;
 }
@@ -1064,54 +1059,30 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
 // poses are wanted; NULL: the tracking half only (a pose the step computed is dropped)
 // eres != NULL (with results): the step was begun with ov2_btracker_track_frame_epi_pose_begin and the filter's records are wanted too
 static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results,
-                           ov2_epifilter_result *eres = nullptr)
+                           ov2_epifilter_result *eres)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     ov2_btracker::Pending &P = t->pend;
     OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_track_frame_end without ov2_btracker_track_frame_begin");
-    OV2_REQUIRE(!results || P.pose, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was not begun with ov2_btracker_track_frame_pose_begin");
+    OV2_REQUIRE(!results || P.form >= STEP_POSE, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was not begun with ov2_btracker_track_frame_pose_begin");
     if (results)
         for (int b = 0; b < P.n_active; b++)
             OV2_REQUIRE(P.n[(size_t)b] == 0 || results[b].removed, OV2_EINVAL, "NULL result buffer (removed)");
-    OV2_REQUIRE(!eres || P.epi, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose_end: the step was not begun with ov2_btracker_track_frame_epi_pose_begin");
-    OV2_REQUIRE(!results || !P.epi || eres, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was begun with ov2_btracker_track_frame_epi_pose_begin");
+    OV2_REQUIRE(!eres || P.form == STEP_EPI, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose_end: the step was not begun with ov2_btracker_track_frame_epi_pose_begin");
+    OV2_REQUIRE(!results || P.form != STEP_EPI || eres, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was begun with ov2_btracker_track_frame_epi_pose_begin");
     if (eres)
         for (int b = 0; b < P.n_active; b++) {
             OV2_REQUIRE(P.n[(size_t)b] == 0 || eres[b].removed, OV2_EINVAL, "NULL result buffer (removed) of the filter");
             OV2_REQUIRE(!eres[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
         }
     P.on = false;
-    if (results) {
-        const size_t B = (size_t)t->batch;
-        t->lp_on = true; t->lp_chain = P.tracked; t->lp_L = P.L;
-        t->lp_m.assign(B, 0); t->lp_rows.assign(B, 0); t->lp_host.assign(B, 0);
-        t->lp_slot.resize(B); t->lp_samples.resize(B);
-        if (!P.tracked)                                                  // first frame / nothing tracked: no chain ran
-            for (int b = 0; b < P.n_active; b++) {
-                ov2_pose_result &r = results[b];
-                uint8_t *removed = r.removed;
-                memset(&r, 0, sizeof(r));
-                r.removed = removed;
-                if (P.n[(size_t)b] > 0) memset(removed, 0, (size_t)P.n[(size_t)b]);
-                memcpy(r.Twc, P.Twc.data() + 7 * (size_t)b, 56);
-                r.action = OV2_POSE_TOO_FEW; r.p3p_req_out = P.req[(size_t)b] != 0;
-            }
-    }
-    if (eres) {
-        const size_t B = (size_t)t->batch;
-        t->le_on = true; t->le_chain = P.tracked; t->le_L = P.eL;
-        t->le_ncur.assign(B, 0); t->le_m.assign(B, 0); t->le_rows.assign(B, 0); t->le_host.assign(B, 0);
-        t->le_slot.resize(B); t->le_samples.resize(B);
-        if (!P.tracked)                                                  // first frame / nothing tracked: no chain ran
-            for (int b = 0; b < P.n_active; b++) {
-                ov2_epifilter_result &r = eres[b], keep = eres[b];
-                memset(&r, 0, sizeof(r));
-                r.removed = keep.removed; r.pair_cur = keep.pair_cur; r.err = keep.err;
-                r.action = OV2_EPIF_TOO_FEW_KPS;
-                if (P.n[(size_t)b] > 0) memset(r.removed, 0, (size_t)P.n[(size_t)b]);
-                if (P.n[(size_t)b] > 0 && r.err) memset(r.err, 0, 4 * (size_t)P.n[(size_t)b]);
-            }
-    }
+    if (results) { t->lp.open((size_t)t->batch, P.tracked); t->lp_L = P.L; }
+    if (eres) { t->le.open((size_t)t->batch, P.tracked); t->le_L = P.eL; }
+    if (!P.tracked)                                                      // first frame / nothing tracked: no chain ran
+        for (int b = 0; b < P.n_active; b++) {
+            if (results) pose_reset(results[b], P.n[(size_t)b], P.Twc.data() + 7 * (size_t)b, P.req[(size_t)b]);
+            if (eres) epi_reset(eres[b], P.n[(size_t)b]);
+        }
     const size_t nm = (size_t)t->cfg.n_max;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
@@ -1122,14 +1093,19 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
     }
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     OV2_REQUIRE(out_xy_h && status_h, OV2_EINVAL, "NULL result buffer");
+    uint8_t *hblk = t->pt.h;
+    const BtPointLayout &pl = t->pl;
     std::vector<int> rule((size_t)P.n_active, 0);
     for (int b = 0; b < P.n_active; b++) {
         const size_t n = (size_t)P.n[(size_t)b], o = nm * (size_t)b;
         if (!n) continue;
-        memcpy(out_xy_h + 2 * o, t->hblk + t->o_out + 8 * o, 8 * n);
-        memcpy(status_h + o, t->hblk + t->o_st + o, n);
-        const int rc = apply_p3p_rule(t, b, P.kps + 2 * o, P.has_prior ? P.has_prior + o : nullptr, P.use_prior, (int)n, out_xy_h + 2 * o,
-                                      status_h + o, &rule[(size_t)b]);
+        memcpy(out_xy_h + 2 * o, hblk + pl.o_out + 8 * o, 8 * n);
+        memcpy(status_h + o, hblk + pl.o_st + o, n);
+        // the rule on the item's views; the re-derived unpx / bv go to the item's rows of the point block
+        const P3pRuleFrame f = {P.kps + 2 * o, P.has_prior ? P.has_prior + o : nullptr, P.use_prior, (int)n, out_xy_h + 2 * o, status_h + o,
+                                (float *)(hblk + pl.o_unpx) + 2 * o, (double *)(hblk + pl.o_bv) + 3 * o};
+        const int rc = ov2_apply_p3p_rule(ctx, t->cfg, t->view[t->prev()][b], t->view[t->cur][b], t->has_calib ? &t->calib : nullptr, f,
+                                          &rule[(size_t)b]);
         if (rc != OV2_OK) return rc;
         if (p3p_req) p3p_req[b] = rule[(size_t)b];
         if (t->has_calib) t->last_n[(size_t)b] = (int)n;
@@ -1137,59 +1113,59 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
     }
     if (!results) return OV2_OK;
     std::vector<int> redo;
+    const uint8_t *hpose = t->pose.h, *hepi = t->epi.h;
+    const BtEpiLayout &el = t->el;
     for (int b = 0; b < P.n_active; b++) {
         const size_t n = (size_t)P.n[(size_t)b], o = nm * (size_t)b;
         int ms[2];
-        memcpy(ms, t->hpose + t->q_ms + 8 * (size_t)b, 8);
-        t->lp_m[(size_t)b] = ms[0]; t->lp_rows[(size_t)b] = ms[1];
+        memcpy(ms, hpose + t->ql.q_ms + 8 * (size_t)b, 8);
+        t->lp.ncur[(size_t)b] = t->lp.m[(size_t)b] = ms[0]; t->lp.rows[(size_t)b] = ms[1];
         if (n && rule[(size_t)b]) { redo.push_back(b); continue; }
         if (eres) {
             ov2_epifilter_result &r = eres[b];
             EpifOut eo;
-            memcpy(&eo, t->hepi + t->e_out + sizeof(EpifOut) * (size_t)b, sizeof(EpifOut));
+            memcpy(&eo, hepi + el.e_out + sizeof(EpifOut) * (size_t)b, sizeof(EpifOut));
             epi_store(r, eo);
-            memcpy(&t->le_ncur[(size_t)b], t->hepi + t->e_nc + 4 * (size_t)b, 4);
-            t->le_m[(size_t)b] = eo.m; t->le_rows[(size_t)b] = epi_rows_used(eo.action, eo.m, P.ep.n_rows);
+            memcpy(&t->le.ncur[(size_t)b], hepi + el.e_nc + 4 * (size_t)b, 4);
+            t->le.m[(size_t)b] = eo.m; t->le.rows[(size_t)b] = epi_rows_used(eo.action, eo.m, P.ep.n_rows);
             if (n) {
-                memcpy(r.removed, t->hepi + t->e_rm + o, n);
-                if (r.pair_cur && eo.m > 0) memcpy(r.pair_cur, t->hepi + t->e_pc + 4 * o, 4 * (size_t)(eo.m < (int)n ? eo.m : (int)n));
-                if (r.err) memcpy(r.err, t->hepi + t->e_er + 4 * o, 4 * n);
+                memcpy(r.removed, hepi + el.e_rm + o, n);
+                if (r.pair_cur && eo.m > 0) memcpy(r.pair_cur, hepi + el.e_pc + 4 * o, 4 * (size_t)(eo.m < (int)n ? eo.m : (int)n));
+                if (r.err) memcpy(r.err, hepi + el.e_er + 4 * o, 4 * n);
             }
         }
         PoseOut po;
-        memcpy(&po, t->hpose + t->q_out + sizeof(PoseOut) * (size_t)b, sizeof(PoseOut));
+        memcpy(&po, hpose + t->ql.q_out + sizeof(PoseOut) * (size_t)b, sizeof(PoseOut));
         pose_store(results[b], po);
-        if (n) memcpy(results[b].removed, t->hpose + t->q_rm + o, n);
+        if (n) memcpy(results[b].removed, hpose + t->ql.q_rm + o, n);
     }
-    if (!redo.empty() && eres) {
-        std::vector<uint8_t> excl;
-        const int rc = epi_redo(t, redo, out_xy_h, status_h, eres, excl);
-        if (rc != OV2_OK) return rc;
-        return pose_redo(t, redo, status_h, results, excl.data());
-    }
-    if (!redo.empty()) return pose_redo(t, redo, status_h, results);
-    return OV2_OK;
+    if (redo.empty()) return OV2_OK;
+    std::vector<uint8_t> excl;
+    if (eres) { const int rc = epi_redo(t, redo, out_xy_h, status_h, eres, excl);  if (rc != OV2_OK) return rc; }
+    return pose_redo(t, redo, status_h, results, eres ? excl.data() : nullptr);
 }
 
 extern "C" {
 
 int ov2_btracker_track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req)
 {
-    return track_frame_end(t, out_xy_h, status_h, p3p_req, nullptr);
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, nullptr, nullptr);
 }
 
 int ov2_btracker_track_frame_pose_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
                                         const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h,
                                         int klt_use_prior, const ov2_frame_pose_params *params, const ov2_frame_pose_input *input)
 {
-    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h,
-                             true, params, input);
+    StepArgs A;
+    A.form = STEP_POSE; A.n_active = n_active; A.img_h = img_h; A.stride = stride; A.kps_xy_h = kps_xy_h; A.n_h = n_h; A.klt_use_prior = klt_use_prior;
+    A.wpt_h = wpt_h; A.is3d_h = is3d_h; A.Tcw_h = Tcw_h; A.pp = params; A.pin = input;
+    return track_frame_begin(t, A);
 }
 
 int ov2_btracker_track_frame_pose_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results)
 {
     OV2_REQUIRE(results, OV2_EINVAL, "NULL result array");
-    return track_frame_end(t, out_xy_h, status_h, p3p_req, results);
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, results, nullptr);
 }
 
 int ov2_btracker_track_frame_pose(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
@@ -1198,41 +1174,24 @@ int ov2_btracker_track_frame_pose(ov2_btracker *t, int n_active, const uint8_t *
                                   float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results)
 {
     OV2_REQUIRE(results, OV2_EINVAL, "NULL result array");
-    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // as ov2_btracker_track_frame: the result buffers before anything is enqueued
-        int n_total = 0;
-        for (int b = 0; b < n_active; b++) {
-            n_total += n_h[b] > 0 ? n_h[b] : 0;
-            OV2_REQUIRE(n_h[b] <= 0 || results[b].removed, OV2_EINVAL, "NULL result buffer (removed)");
-        }
-        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
-    }
-    const int rc = ov2_btracker_track_frame_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
+    int rc = check_outputs(t, n_active, n_h, out_xy_h, status_h, results, nullptr);
+    if (rc == OV2_OK) rc = ov2_btracker_track_frame_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
     if (rc != OV2_OK) return rc;
-    return track_frame_end(t, out_xy_h, status_h, p3p_req, results);
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, results, nullptr);
 }
 
 int ov2_btracker_last_pose_inputs(const ov2_btracker *t, int item, int *m, int *slot_idx, int *samples, int *n_rows_used)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(t->lp_on, OV2_EINVAL, "ov2_btracker_last_pose_inputs: no pose step has been finished on this tracker");
+    OV2_REQUIRE(t->lp.on, OV2_EINVAL, "ov2_btracker_last_pose_inputs: no pose step has been finished on this tracker");
     const size_t b = (size_t)item;
-    const int mm = t->lp_m[b], rows = t->lp_rows[b];
-    if (m) *m = mm;
-    if (n_rows_used) *n_rows_used = rows;
-    if (t->lp_host[b]) {
-        if (slot_idx && mm > 0) memcpy(slot_idx, t->lp_slot[b].data(), 4 * (size_t)mm);
-        if (samples && rows > 0) memcpy(samples, t->lp_samples[b].data(), 16 * (size_t)rows);
-        return OV2_OK;
-    }
-    if (!t->lp_chain || (mm <= 0 && rows <= 0)) return OV2_OK;
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    if (m) *m = t->lp.m[b];
+    if (n_rows_used) *n_rows_used = t->lp.rows[b];
     const PoseLayout &L = t->lp_L;
-    if (slot_idx && mm > 0)
-        OV2_HIP_CHECK(hipMemcpy(slot_idx, t->dwork + ov2_frame_pose_slot_offset(L) + 4 * b * (size_t)L.n_max, 4 * (size_t)mm, hipMemcpyDeviceToHost));
-    if (samples && rows > 0)
-        OV2_HIP_CHECK(hipMemcpy(samples, t->dwork + L.o_p3 + L.pl.o_sm + 16 * b * (size_t)L.n_rows, 16 * (size_t)rows, hipMemcpyDeviceToHost));
-    return OV2_OK;
+    const uint8_t *w = t->lp.chain ? t->dwork : nullptr;
+    return last_inputs_fetch(t, t->lp, b, slot_idx, samples, w ? w + ov2_frame_pose_slot_offset(L) + 4 * b * (size_t)L.n_max : nullptr,
+                             w ? w + L.o_p3 + L.pl.o_sm + 16 * b * (size_t)L.n_rows : nullptr, 16);
 }
 
 int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf_lmid, const float *kf_unpx, const double *kf_bv,
@@ -1282,8 +1241,10 @@ int ov2_btracker_track_frame_epi_pose_begin(ov2_btracker *t, int n_active, const
                                             int klt_use_prior, const ov2_frame_epi_pose_params *params,
                                             const ov2_frame_epi_pose_input *input)
 {
-    return track_frame_begin(t, n_active, img_h, stride, kps_xy_h, nullptr, nullptr, n_h, klt_use_prior, true, wpt_h, is3d_h, Tcw_h,
-                             true, nullptr, nullptr, true, params, input);
+    StepArgs A;
+    A.form = STEP_EPI; A.n_active = n_active; A.img_h = img_h; A.stride = stride; A.kps_xy_h = kps_xy_h; A.n_h = n_h; A.klt_use_prior = klt_use_prior;
+    A.wpt_h = wpt_h; A.is3d_h = is3d_h; A.Tcw_h = Tcw_h; A.epp = params; A.ein = input;
+    return track_frame_begin(t, A);
 }
 
 int ov2_btracker_track_frame_epi_pose_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req,
@@ -1300,16 +1261,8 @@ int ov2_btracker_track_frame_epi_pose(ov2_btracker *t, int n_active, const uint8
                                       ov2_pose_result *pose_results)
 {
     OV2_REQUIRE(epi_results && pose_results, OV2_EINVAL, "NULL result array");
-    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // as ov2_btracker_track_frame: the result buffers before anything is enqueued
-        int n_total = 0;
-        for (int b = 0; b < n_active; b++) {
-            n_total += n_h[b] > 0 ? n_h[b] : 0;
-            OV2_REQUIRE(n_h[b] <= 0 || (pose_results[b].removed && epi_results[b].removed), OV2_EINVAL, "NULL result buffer (removed)");
-            OV2_REQUIRE(!epi_results[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
-        }
-        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
-    }
-    const int rc = ov2_btracker_track_frame_epi_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
+    int rc = check_outputs(t, n_active, n_h, out_xy_h, status_h, pose_results, epi_results);
+    if (rc == OV2_OK) rc = ov2_btracker_track_frame_epi_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
     if (rc != OV2_OK) return rc;
     return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results);
 }
@@ -1318,38 +1271,23 @@ int ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, in
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(t->le_on, OV2_EINVAL, "ov2_btracker_last_epi_inputs: no epipolar step has been finished on this tracker");
+    OV2_REQUIRE(t->le.on, OV2_EINVAL, "ov2_btracker_last_epi_inputs: no epipolar step has been finished on this tracker");
     const size_t b = (size_t)item;
-    const int nc = t->le_ncur[b], rows = t->le_rows[b];
-    if (n_cur) *n_cur = nc;
-    if (m) *m = t->le_m[b];
-    if (n_rows_used) *n_rows_used = rows;
-    if (t->le_host[b]) {
-        if (slot_idx && nc > 0) memcpy(slot_idx, t->le_slot[b].data(), 4 * (size_t)nc);
-        if (samples && rows > 0) memcpy(samples, t->le_samples[b].data(), 32 * (size_t)rows);
-        return OV2_OK;
-    }
-    if (!t->le_chain || (nc <= 0 && rows <= 0)) return OV2_OK;
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    if (n_cur) *n_cur = t->le.ncur[b];
+    if (m) *m = t->le.m[b];
+    if (n_rows_used) *n_rows_used = t->le.rows[b];
     const EpifLayout &L = t->le_L;
-    const size_t nm = (size_t)t->cfg.n_max;
-    if (slot_idx && nc > 0 && (size_t)nc <= nm)
-        OV2_HIP_CHECK(hipMemcpy(slot_idx, t->dfx + t->x_slot + 4 * b * nm, 4 * (size_t)nc, hipMemcpyDeviceToHost));
-    if (samples && rows > 0)
-        OV2_HIP_CHECK(hipMemcpy(samples, t->depi + L.o_sm + 32 * b * (size_t)L.s_max, 32 * (size_t)rows, hipMemcpyDeviceToHost));
-    return OV2_OK;
+    const bool dev = t->le.chain;
+    return last_inputs_fetch(t, t->le, b, slot_idx, samples, dev ? t->dfx + t->el.x_slot + 4 * b * (size_t)t->cfg.n_max : nullptr,
+                             dev ? t->depi + L.o_sm + 32 * b * (size_t)L.s_max : nullptr, 32);
 }
 
 int ov2_btracker_track_frame(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
                              const float *prior_xy_h, const uint8_t *has_prior_h, const int *n_h, int klt_use_prior,
                              float *out_xy_h, uint8_t *status_h, int *p3p_req)
 {
-    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // (the one-call form checks its result buffers before anything is enqueued)
-        int n_total = 0;
-        for (int b = 0; b < n_active; b++) n_total += n_h[b] > 0 ? n_h[b] : 0;
-        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
-    }
-    const int rc = ov2_btracker_track_frame_begin(t, n_active, img_h, stride, kps_xy_h, prior_xy_h, has_prior_h, n_h, klt_use_prior);
+    int rc = check_outputs(t, n_active, n_h, out_xy_h, status_h, nullptr, nullptr);
+    if (rc == OV2_OK) rc = ov2_btracker_track_frame_begin(t, n_active, img_h, stride, kps_xy_h, prior_xy_h, has_prior_h, n_h, klt_use_prior);
     if (rc != OV2_OK) return rc;
     return ov2_btracker_track_frame_end(t, out_xy_h, status_h, p3p_req);
 }
@@ -1358,12 +1296,8 @@ int ov2_btracker_track_frame_map(ov2_btracker *t, int n_active, const uint8_t *c
                                  const double *wpt_h, const uint8_t *is3d_h, const double *Tcw_h, const int *n_h, int klt_use_prior,
                                  float *out_xy_h, uint8_t *status_h, int *p3p_req)
 {
-    if (t && n_active >= 1 && n_active <= t->batch && n_h) {              // as ov2_btracker_track_frame: the result buffers before anything is enqueued
-        int n_total = 0;
-        for (int b = 0; b < n_active; b++) n_total += n_h[b] > 0 ? n_h[b] : 0;
-        OV2_REQUIRE(n_total == 0 || (out_xy_h && status_h), OV2_EINVAL, "NULL point buffer");
-    }
-    const int rc = ov2_btracker_track_frame_map_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior);
+    int rc = check_outputs(t, n_active, n_h, out_xy_h, status_h, nullptr, nullptr);
+    if (rc == OV2_OK) rc = ov2_btracker_track_frame_map_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior);
     if (rc != OV2_OK) return rc;
     return ov2_btracker_track_frame_end(t, out_xy_h, status_h, p3p_req);
 }
@@ -1374,8 +1308,8 @@ int ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *prio
     OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
     OV2_REQUIRE(n >= 0 && n <= t->last_pn[(size_t)item], OV2_EINVAL, "more keypoints than the last tracking call returned for this item");
     const size_t o = (size_t)item * t->cfg.n_max;
-    if (prior_xy_h) memcpy(prior_xy_h, t->hblk + t->o_pri + 8 * o, 8 * (size_t)n);
-    if (has_prior_h) memcpy(has_prior_h, t->hblk + t->o_flg + o, (size_t)n);
+    if (prior_xy_h) memcpy(prior_xy_h, t->pt.h + t->pl.o_pri + 8 * o, 8 * (size_t)n);
+    if (has_prior_h) memcpy(has_prior_h, t->pt.h + t->pl.o_flg + o, (size_t)n);
     return OV2_OK;
 }
 
@@ -1385,8 +1319,8 @@ int ov2_btracker_last_keypoints(const ov2_btracker *t, int item, int n, float *u
     OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
     OV2_REQUIRE(n >= 0 && n <= t->last_n[(size_t)item], OV2_EINVAL, "more keypoints than the last tracking call returned for this item");
     const size_t o = (size_t)item * t->cfg.n_max;
-    if (unpx_xy_h) memcpy(unpx_xy_h, t->hblk + t->o_unpx + 8 * o, 8 * (size_t)n);
-    if (bv_xyz_h) memcpy(bv_xyz_h, t->hblk + t->o_bv + 24 * o, 24 * (size_t)n);
+    if (unpx_xy_h) memcpy(unpx_xy_h, t->pt.h + t->pl.o_unpx + 8 * o, 8 * (size_t)n);
+    if (bv_xyz_h) memcpy(bv_xyz_h, t->pt.h + t->pl.o_bv + 24 * o, 24 * (size_t)n);
     return OV2_OK;
 }
 

@@ -1,0 +1,70 @@
+// trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
+// point block, the map block, the pose block, the epipolar I/O block and the filter's device-only index block, each computed by one
+// function of (batch, n_max).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
+// it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
+#pragma once
+#include <stddef.h>
+
+#define BT_POSE_OUT_BYTES 168       // sizeof(PoseOut), sizeof(EpifOut), sizeof(FeKfHdr): trackb.hip asserts all three
+#define BT_EPIF_OUT_BYTES 304
+#define BT_KF_HDR_BYTES 120
+
+static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// frames: row pitch and bytes of one item in the staging sets
+static inline size_t bt_img_pitch(int w) { return up16((size_t)w); }
+static inline size_t bt_img_bytes(int w, int h) { return up256(bt_img_pitch(w) * (size_t)h); }
+// keyframe detection: [n 4 per item][current keypoints 8 per slot]
+static inline size_t bt_det_in_bytes(int batch, int n_max) { return up256(4 * (size_t)batch) + 8 * (size_t)n_max * (size_t)batch; }
+
+// The point block.  [n 4 per item][kps 8][prior 8][flag 1 per slot] go up (in_bytes; o_pri and o_flg follow their predecessor
+// directly); [out 8][status 1 per slot (o_st follows o_out directly)][unpx 8][bv 24 per slot] come down.
+struct BtPointLayout { size_t o_n, o_kps, o_pri, o_flg, in_bytes, o_out, o_st, o_unpx, o_bv, blk_bytes; };
+static inline BtPointLayout bt_point_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    BtPointLayout L;
+    L.o_n = 0; L.o_kps = up256(4 * B); L.o_pri = L.o_kps + 8 * slots; L.o_flg = L.o_pri + 8 * slots; L.in_bytes = up256(L.o_flg + slots);
+    L.o_out = L.in_bytes; L.o_st = L.o_out + 8 * slots; L.o_unpx = up256(L.o_st + slots); L.o_bv = up256(L.o_unpx + 8 * slots);
+    L.blk_bytes = L.o_bv + 24 * slots;
+    return L;
+}
+
+// The map block: [items 16][Tcw 56 per item][wpt 24][is3d 1 per slot], all of it goes up.
+struct BtMapLayout { size_t m_it, m_T, m_w, m_3d, map_bytes; };
+static inline BtMapLayout bt_map_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    BtMapLayout L;
+    L.m_it = 0; L.m_T = up256(16 * B); L.m_w = up256(L.m_T + 56 * B); L.m_3d = up256(L.m_w + 24 * slots);
+    L.map_bytes = up256(L.m_3d + slots);
+    return L;
+}
+
+// The pose block: [Twc 56][seed 8][flags 1 per item][scale 4 per slot] go up (q_in); [PoseOut 168][m, rows 8 per item]
+// [removed 1 per slot] come down.
+struct BtPoseLayout { size_t q_T, q_seed, q_fl, q_sc, q_in, q_out, q_ms, q_rm, pose_bytes; };
+static inline BtPoseLayout bt_pose_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    BtPoseLayout L;
+    L.q_T = 0; L.q_seed = up256(56 * B); L.q_fl = up256(L.q_seed + 8 * B); L.q_sc = up256(L.q_fl + B); L.q_in = up256(L.q_sc + 4 * slots);
+    L.q_out = L.q_in; L.q_ms = up256(L.q_out + BT_POSE_OUT_BYTES * B); L.q_rm = up256(L.q_ms + 8 * B); L.pose_bytes = up256(L.q_rm + slots);
+    return L;
+}
+
+// The epipolar blocks.  I/O block: [lmid 4 per slot][nbkfs 4][seed 8 per item] go up (e_in); [EpifOut 304][n_cur 4 per item]
+// [removed 1][err 4][pair 4 per slot] come down.  Index block (device only): [FeKfHdr 120 per item][slot 4][rank 4 per slot (x_rank
+// follows x_slot directly)].
+struct BtEpiLayout { size_t e_lm, e_nk, e_sd, e_in, e_out, e_nc, e_rm, e_er, e_pc, epi_bytes, x_slot, x_rank, fx_bytes; };
+static inline BtEpiLayout bt_epi_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    BtEpiLayout L;
+    L.e_lm = 0; L.e_nk = up256(4 * slots); L.e_sd = up256(L.e_nk + 4 * B); L.e_in = up256(L.e_sd + 8 * B);
+    L.e_out = L.e_in; L.e_nc = up256(L.e_out + BT_EPIF_OUT_BYTES * B); L.e_rm = up256(L.e_nc + 4 * B);
+    L.e_er = up256(L.e_rm + slots); L.e_pc = up256(L.e_er + 4 * slots); L.epi_bytes = up256(L.e_pc + 4 * slots);
+    L.x_slot = up256(BT_KF_HDR_BYTES * B); L.x_rank = L.x_slot + 4 * slots; L.fx_bytes = L.x_rank + 4 * slots;
+    return L;
+}

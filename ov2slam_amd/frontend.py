@@ -517,25 +517,32 @@ class LockstepTracker:
         """preprocessImage of staging set `which` for the NEXT trackFrame, on the tracker's prep stream"""
         L.check(self.lib.ov2_btracker_prepare(self.h_trk, int(which), int(n_active)))
 
-    def trackFrame(self, imgs, kps, pri, hasprior, n, klt_use_prior=True):
-        """imgs: list of n_active (h, >=w) uint8 arrays of one row pitch (or pinned slots of one staging set); kps / pri:
-        (batch, n_max, 2) float32; hasprior: (batch, n_max) uint8 or None; n: per-item counts (len n_active).
-        -> (out (batch, n_max, 2), status bits (batch, n_max), p3p_req (n_active,) bool)"""
-        na = len(imgs)
+    def _frames(self, imgs):
+        """the frames of a step -> (contiguous list, common row pitch, pointer array); refuses a wrong shape or mixed pitches"""
         imgs = [im if im.dtype == np.uint8 and im.strides[1] == 1 else np.ascontiguousarray(im, np.uint8) for im in imgs]
         stride = imgs[0].strides[0]
         for im in imgs:
             if im.ndim != 2 or im.shape[0] != self.h or im.shape[1] < self.w or im.strides[0] != stride:
                 raise ValueError("frames must be %d rows of >= %d bytes with one common row pitch" % (self.h, self.w))
-        ptrs = (C.c_void_p * na)(*[im.ctypes.data for im in imgs])
+        return imgs, stride, (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+
+    def _outputs(self, na):
+        """the result arrays of a step: out (batch, n_max, 2), status bits (batch, n_max), p3p_req (na,)"""
+        return np.zeros((self.batch, self.n_max, 2), np.float32), np.zeros((self.batch, self.n_max), np.uint8), np.zeros(na, np.int32)
+
+    def trackFrame(self, imgs, kps, pri, hasprior, n, klt_use_prior=True):
+        """imgs: list of n_active (h, >=w) uint8 arrays of one row pitch (or pinned slots of one staging set); kps / pri:
+        (batch, n_max, 2) float32; hasprior: (batch, n_max) uint8 or None; n: per-item counts (len n_active).
+        -> (out (batch, n_max, 2), status bits (batch, n_max), p3p_req (n_active,) bool)"""
+        na = len(imgs)
+        imgs, stride, ptrs = self._frames(imgs)
         kps = np.ascontiguousarray(kps, np.float32).reshape(self.batch, self.n_max, 2)
         pri = np.ascontiguousarray(pri, np.float32).reshape(self.batch, self.n_max, 2)
         hp = None if hasprior is None else np.ascontiguousarray(hasprior, np.uint8).reshape(self.batch, self.n_max)
         nn = np.ascontiguousarray(n, np.int32)
         if len(nn) != na:
             raise ValueError("one keypoint count per active item")
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         L.check(self.lib.ov2_btracker_track_frame(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(pri), _ptr(hp), _ptr(nn),
                                                   int(bool(klt_use_prior)), _ptr(out), _ptr(st), _ptr(p3p)))
         return out, st, p3p.astype(bool)
@@ -543,9 +550,7 @@ class LockstepTracker:
     def trackFrameBegin(self, imgs, kps, pri, hasprior, n, klt_use_prior=True):
         """first half of trackFrame: enqueue the step and return (upload / prepare of the frames to come go between the halves)"""
         na = len(imgs)
-        imgs = [im if im.dtype == np.uint8 and im.strides[1] == 1 else np.ascontiguousarray(im, np.uint8) for im in imgs]
-        stride = imgs[0].strides[0]
-        ptrs = (C.c_void_p * na)(*[im.ctypes.data for im in imgs])
+        imgs, stride, ptrs = self._frames(imgs)
         kps = np.ascontiguousarray(kps, np.float32).reshape(self.batch, self.n_max, 2)
         pri = np.ascontiguousarray(pri, np.float32).reshape(self.batch, self.n_max, 2)
         hp = None if hasprior is None else np.ascontiguousarray(hasprior, np.uint8).reshape(self.batch, self.n_max)
@@ -556,20 +561,14 @@ class LockstepTracker:
     def trackFrameEnd(self):
         """second half: wait, results, p3p rule -> (out, status bits, p3p_req) as trackFrame"""
         na = len(self._pending[0])
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         L.check(self.lib.ov2_btracker_track_frame_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p)))
         self._pending = None
         return out, st, p3p.astype(bool)
 
     def _map_args(self, imgs, kps, wpt, is3d, Tcw, n):
         na = len(imgs)
-        imgs = [im if im.dtype == np.uint8 and im.strides[1] == 1 else np.ascontiguousarray(im, np.uint8) for im in imgs]
-        stride = imgs[0].strides[0]
-        for im in imgs:
-            if im.ndim != 2 or im.shape[0] != self.h or im.shape[1] < self.w or im.strides[0] != stride:
-                raise ValueError("frames must be %d rows of >= %d bytes with one common row pitch" % (self.h, self.w))
-        ptrs = (C.c_void_p * na)(*[im.ctypes.data for im in imgs])
+        imgs, stride, ptrs = self._frames(imgs)
         kps = np.ascontiguousarray(kps, np.float32).reshape(self.batch, self.n_max, 2)
         wpt = np.ascontiguousarray(wpt, np.float64).reshape(self.batch, self.n_max, 3)
         is3d = np.ascontiguousarray(is3d, np.uint8).reshape(self.batch, self.n_max)
@@ -584,8 +583,7 @@ class LockstepTracker:
         is3d (batch, n_max) uint8, Tcw (>= n_active, 7) the predicted poses [t q], already inverted.  Needs setCalibration.
         -> (out, status bits, p3p_req) as trackFrame; lastPriors returns the priors that were used."""
         na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         L.check(self.lib.ov2_btracker_track_frame_map(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw), _ptr(nn),
                                                       int(bool(klt_use_prior)), _ptr(out), _ptr(st), _ptr(p3p)))
         return out, st, p3p.astype(bool)
@@ -637,8 +635,7 @@ class LockstepTracker:
         SPACE."""
         na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
         fp, fi, keep = self._pose_args(na, nn, params, Twc, p3p_req, seed, scale, dop3p, n_rows)
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         R, removed = self._pose_results(na, nn)
         L.check(self.lib.ov2_btracker_track_frame_pose(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw), _ptr(nn),
                                                        int(bool(klt_use_prior)), C.byref(fp), C.byref(fi), _ptr(out), _ptr(st), _ptr(p3p), R))
@@ -657,8 +654,7 @@ class LockstepTracker:
         """second half of trackFramePose -> (out, status bits, p3p_req, poses)"""
         nn = self._pending[4]
         na = len(nn)
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         R, removed = self._pose_results(na, nn)
         L.check(self.lib.ov2_btracker_track_frame_pose_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p), R))
         self._pending = None
@@ -727,8 +723,7 @@ class LockstepTracker:
         removed / err (n[b],) and pair_cur (m,) IN SLOT SPACE; poses[b] as trackFramePose, on the frame after the filter."""
         na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = self._map_args(imgs, kps, wpt, is3d, Tcw, n)
         ep, ei, keep = self._epi_args(na, nn, params, epi_params, Twc, p3p_req, seed, lmid, nbkfs, epi_seed, scale, dop3p, n_rows)
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         R, removed = self._pose_results(na, nn)
         E, bufs = self._epi_results(na)
         L.check(self.lib.ov2_btracker_track_frame_epi_pose(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(Tcw),
@@ -750,8 +745,7 @@ class LockstepTracker:
         """second half of trackFrameEpiPose -> (out, status bits, p3p_req, epis, poses)"""
         nn = self._pending[4]
         na = len(nn)
-        out = np.zeros((self.batch, self.n_max, 2), np.float32); st = np.zeros((self.batch, self.n_max), np.uint8)
-        p3p = np.zeros(na, np.int32)
+        out, st, p3p = self._outputs(na)
         R, removed = self._pose_results(na, nn)
         E, bufs = self._epi_results(na)
         L.check(self.lib.ov2_btracker_track_frame_epi_pose_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p), E, R))

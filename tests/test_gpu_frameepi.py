@@ -51,6 +51,9 @@ def _epi_params(stereo, mono, n_rows=EPI_ROWS):
 #           1  dop3p under RANSAC, nbkfs 2 on one item
 #           2  the wrong motion model: the rule fires
 #           3  the third item has ended; p3p_req on one item
+#   grow:   the pose's sample rows go 7, 40 and the filter's (epi_rows) 8, 48 on one tracker, P3P and the five-point search running in
+#           both steps: the second step grows the chain's work block and the filter's block behind a finished step, and the filter's
+#           block gets the resident keyframe arrays again from the host copy
 STEREO = [dict(counts=[64, 37, 0], swap3=[2, 1, 0], swap2=[2, 0, 0], scale=True),
           dict(counts=[20, 20, 6], n3d=[5, 5, 3], point3=[2, 1, 0], req=[1, 1, 1], n_rows=40, exact=True),
           dict(counts=[64, 37, 0], kf=["same", "same", "same"], repeat=True),
@@ -59,7 +62,10 @@ MONO = [dict(counts=[64, 37, 0], n3d=[20, 10, 0], point3=[3, 2, 0], dop3p=True, 
         dict(counts=[37, 0, 64], n3d=[12, 0, 25], swap3=[1, 0, 2], dop3p=True, n_rows=40, mode=pose.RANSAC, nbkfs=[3, 3, 2]),
         dict(counts=[0, 64, 37], wrong_pose=True, n_rows=40, swap3=[0, 2, 1]),
         dict(counts=[64, 37], req=[0, 1], n_rows=7, scale=True, swap3=[1, 1])]
-SPECS = dict(stereo=(STEREO, dict(stereo=True, mono=False)), mono=(MONO, dict(stereo=False, mono=True)))
+GROW = [dict(counts=[64, 37, 0], n3d=[20, 10, 0], point3=[3, 2, 0], dop3p=True, n_rows=7, epi_rows=8),
+        dict(counts=[37, 20, 64], n3d=[12, 8, 25], swap3=[1, 0, 2], dop3p=True, n_rows=40, epi_rows=48)]
+SPECS = dict(stereo=(STEREO, dict(stereo=True, mono=False)), mono=(MONO, dict(stereo=False, mono=True)),
+             grow=(GROW, dict(stereo=False, mono=True)))
 
 _SEQS, _RUNS = {}, {}
 
@@ -161,7 +167,7 @@ def _inputs(name, cal):
                           epi_seed=rng.integers(0, 1 << 63, BATCH).astype(np.uint64) * np.uint64(2) + np.uint64(1),
                           lmid=lmid, nbkfs=nbkfs, keyframes=kfs,
                           scale=rng.integers(0, 4, (BATCH, N_MAX)).astype(np.int32) if sp.get("scale") else None,
-                          params=_params(sp.get("mode", pose.LMEDS), cfg["mono"]), epi_params=_epi_params(cfg["stereo"], cfg["mono"]),
+                          params=_params(sp.get("mode", pose.LMEDS), cfg["mono"]), epi_params=_epi_params(cfg["stereo"], cfg["mono"], sp.get("epi_rows", EPI_ROWS)),
                           dop3p=sp.get("dop3p", False), n_rows=sp.get("n_rows", 0), klt_use_prior=True))
         prev_idx = cur_idx
     return steps
@@ -314,6 +320,12 @@ def test_the_route_exercises_what_the_cases_are_for(gpu_ctx):
     assert all(p["ran_p3p"] for p in M[2]["poses"][1:]) and all(e["m"] >= 8 for e in M[2]["epis"][1:])
     # an item that has ended, p3p_req on one of the others
     assert len(M[3]["epis"]) == 2 and [p["ran_p3p"] for p in M[3]["poses"]] == [False, True]
+    # grow: both searches run in both steps, on tables of 7 / 8 rows and then of 40 / 48
+    G = _play(gpu_ctx, "grow", "route")
+    _show("grow", G)
+    for g, (prow, erow) in zip(G, ((7, 8), (40, 48))):
+        assert sum(bool(p["ran_p3p"]) and len(i[2]) == prow for p, i in zip(g["poses"], g["inputs"])) >= 2
+        assert sum(e["action"] == keyframe.EPIF_FILTERED and len(ei[3]) == erow for e, ei in zip(g["epis"], g["einputs"])) >= 2
     # every action and both removal codes were seen; removed speaks of slots of the frame, the pose's of slots of the filtered frame
     seen = {e["action"] for run in (S, M) for s in run for e in s["epis"]}
     assert seen == {keyframe.EPIF_TOO_FEW_KPS, keyframe.EPIF_LOW_PARALLAX, keyframe.EPIF_NO_MODEL, keyframe.EPIF_DEGENERATE, keyframe.EPIF_FILTERED}
@@ -336,9 +348,10 @@ def test_last_epi_inputs_are_the_packed_frame_and_the_host_draw(gpu_ctx):
                 want = R.frame_set(r["st"][b], int(s["n"][b]))
                 assert n_cur == len(want) and np.array_equal(slots, want) and m == r["epis"][b]["m"], (name, f, b)
                 search = r["epis"][b]["action"] >= keyframe.EPIF_NO_MODEL and m >= 8
-                assert len(tab) == (EPI_ROWS if search else 0), (name, f, b)
+                rows = s["epi_params"]["n_rows"]                   # (EPI_ROWS wherever the spec does not say otherwise)
+                assert len(tab) == (rows if search else 0), (name, f, b)
                 if search:
-                    assert np.array_equal(tab, pose.epipolar_draw_samples(int(s["epi_seed"][b]), m, EPI_ROWS)), (name, f, b)
+                    assert np.array_equal(tab, pose.epipolar_draw_samples(int(s["epi_seed"][b]), m, rows)), (name, f, b)
                 seen += bool(search)
     assert seen >= 10
 
