@@ -1668,7 +1668,9 @@ enum {
     OV2_KF_RET_FEW_3D = 32,                                         /* :1015, true                                           */
     OV2_KF_RET_MANY_3D = 64,                                        /* :1021, false                                          */
     OV2_KF_RET_TIME = 128,                                          /* :1030, true                                           */
-    OV2_KF_NONFINITE = 256
+    OV2_KF_NONFINITE = 256,
+    OV2_KF_FIRST_FRAME = 512,                                       /* ov2_btracker_track_mono: trackMono :77, true          */
+    OV2_KF_NO_KEYFRAME = 1024                                       /* ov2_btracker_track_mono: no keyframe (info), :994     */
 };
 typedef struct {
     double K[4];                 /* fx fy cx cy of the left camera                                                           */
@@ -1968,7 +1970,8 @@ int  ov2_btracker_last_priors(const ov2_btracker *t, int item, int n, float *pri
  * on keeps the route of separate calls: tracking, ov2_epipolar_filter_batch -- the function as one device chain, built on a
  * caller-owned block so that it can go between the select and the pack later --, ov2_compute_pose_batch), checkNewKfReq, the motion
  * model, kltTrackingFromKF.  (Since f18 the filter has a step of its own form: ov2_btracker_track_frame_epi_pose below puts that
- * chain between the select and the pack; this step is unchanged and remains the one for doepipolar: 0.)
+ * chain between the select and the pack; this step is unchanged and remains the one for doepipolar: 0.  Since f19 the motion model
+ * and checkNewKfReq run around either step in ov2_btracker_track_mono, at the end of this header.)
  *
  * OV2_EINVAL, checked on the host before anything is enqueued (the tracker stays where it was; the same frames can be passed
  * again): everything ov2_btracker_track_frame_map refuses; no calibration; NULL params / input / Twc_h / p3p_req_h / seed_h;
@@ -2086,6 +2089,123 @@ int  ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, i
 /* out = the inverse of the transform T, both [tx ty tz qx qy qz qw]: the conjugate quaternion and minus the rotated translation, the
  * rotation matrix of the conjugate written out, each sum of three terms serial.  Host arithmetic, no context. */
 int  ov2_se3_inverse(const double T[7], double out[7]);
+
+/* The constant-velocity MotionModel of the reference (include/visual_front_end.hpp:38-90) on the device (f19, csrc/motion.hip): the
+ * two lines of VisualFrontEnd::trackMono that stand in front of and behind the per-frame step.  Fp64, one lane per item, Sophus'
+ * SE(3) product, inverse, log and exp in the one device copy the pose-graph solver uses (csrc/se3_dev.hpp).  Poses are
+ * [tx ty tz qx qy qz qw]; a pose is read as Sophus::SE3d(q, t) reads it (the quaternion normalised) and copied as it is given.
+ *
+ * The state is MotionModel's three members.  reset(): prev_time = -1, log_relT = 0 (prevTwc any finite pose).
+ *
+ * ov2_motion_apply: applyMotionModel(Twc, time) (:43-58).
+ *   prev_time > 0:  d = (Twc * prevTwc^-1).log(); if NOT every |d_k| <= 1e-5 (Eigen's isZero(1.e-5) per coefficient; a NaN
+ *                   coefficient is "not zero"), state_out.prevTwc = Twc_in and *resynced = 1 -- the estimator or the loop closer
+ *                   moved the frame since the last update.  Twc_out = Twc * exp(log_relT * (time - prev_time)).
+ *   otherwise:      Twc_out = Twc_in, *resynced = 0.
+ *   state_out is state_in but for that prevTwc.  Tcw_out is Twc_out inverted in the arithmetic of ov2_se3_inverse -- products, sums
+ *   and negations, compiled without contraction on both sides --, so it equals ov2_se3_inverse(Twc_out) BIT FOR BIT.
+ * ov2_motion_update: updateMotionModel(Twc, time) (:60-78).
+ *   prev_time < 0:  only stores: prev_time = time, prevTwc = Twc.
+ *   otherwise:      log_relT = (prevTwc^-1 * Twc).log() / (time - prev_time), prev_time = time, prevTwc = Twc.
+ * (prev_time == 0 is the reference's own gap between "> 0" and "< 0": apply leaves the pose, update takes the second branch.)
+ * Device sin / cos / atan are not libm's: against tests/motion_ref.py the doubles agree to rounding (tests/test_gpu_motion.py holds
+ * them to the rule of the pose-graph tests), resynced exactly wherever no |d_k| sits on the threshold.
+ *
+ * The batch forms take n items (state_in, time: n; Twc: 7 n; resynced: n bytes) in one upload, one launch, one download and one
+ * synchronisation on the context's stream; the single forms are the batch of one.  Outputs may alias the inputs.  n == 0: OV2_OK.
+ * OV2_EINVAL, checked on the host before the context is touched, nothing written: n < 0; a NULL array; a state, pose or time that is
+ * not finite; prev_time >= 0 && time <= prev_time (the reference exits on dt < 0 and divides by zero on dt == 0: both are refused,
+ * by apply as by update).  Finite inputs with dt > 0 give a finite log and exp, so the outputs are finite. */
+typedef struct {
+    double prev_time;            /* MotionModel::prev_time_; < 0: no pose stored yet                                         */
+    double prevTwc[7];           /* MotionModel::prevTwc_                                                                    */
+    double log_relT[6];          /* MotionModel::log_relT_: [upsilon; omega] per second                                      */
+} ov2_motion_state;
+int  ov2_motion_apply(ov2_ctx *ctx, const ov2_motion_state *state_in, const double Twc_in[7], double time,
+                      ov2_motion_state *state_out, double Twc_out[7], double Tcw_out[7], uint8_t *resynced);
+int  ov2_motion_apply_batch(ov2_ctx *ctx, int n, const ov2_motion_state *state_in, const double *Twc_in, const double *time,
+                            ov2_motion_state *state_out, double *Twc_out, double *Tcw_out, uint8_t *resynced);
+int  ov2_motion_update(ov2_ctx *ctx, const ov2_motion_state *state_in, const double Twc[7], double time, ov2_motion_state *state_out);
+int  ov2_motion_update_batch(ov2_ctx *ctx, int n, const ov2_motion_state *state_in, const double *Twc, const double *time,
+                             ov2_motion_state *state_out);
+
+/* The lock-step step that IS VisualFrontEnd::trackMono after initialisation (f19; src/visual_front_end.cpp:65-128): the motion model
+ * in front of the step of f18 (doepipolar: 1) or f16 (doepipolar: 0), and behind it updateMotionModel and checkNewKfReq, one enqueue
+ * and one synchronisation.  The caller hands over images, keypoints, map points and a timestamp and gets the tracked frame, the
+ * filter's record, the pose and the keyframe request; it does no pose arithmetic.  What remains with it per frame is the map (which
+ * slots exist) and createKeyframe.
+ *
+ * RESIDENT ON THE DEVICE per item, mirrored on the host: the frame pose (pcurframe_->Twc_; the identity at first), the
+ * ov2_motion_state (reset() at first) and the keyframe's id_, img_time_ and nb3dkps_ next to the keyframe arrays of
+ * ov2_btracker_set_keyframe.  ov2_btracker_set_pose: the estimator or the loop closer moved the frame -- the case applyMotionModel's
+ * resync exists for; a non-finite pose is refused.  ov2_btracker_reset_motion: MotionModel::reset().  ov2_btracker_set_keyframe_info:
+ * call it with ov2_btracker_set_keyframe.  The get_ calls return the mirrors.  All five return OV2_EINVAL between _begin and _end.
+ *
+ * params: the ov2_frame_epi_pose_params as they are (step.epi.fkf carries ncellsize, nbwcells, nbhcells, nbmaxkps, finit_parallax
+ * and stereo for the decision) plus doepipolar; with doepipolar == 0 step.epi's search settings are not read, the filter is skipped
+ * and epi_results must be NULL.  input: the ov2_frame_epi_pose_input with step.pose.Twc_h == NULL (there is no Tcw_h argument
+ * either), plus time_h, frame_id_h and localba_is_on_h (NULL: all 0) per item; nbkfs_h / epi_seed_h may be NULL with doepipolar == 0.
+ *
+ * On the context's stream, nothing visiting the host:
+ *   k_mono_apply    (csrc/mono.hip) ov2_motion_apply on the resident pose and state: the predicted Twc into the pose block, its
+ *                   inverse into the map block -- behind those blocks' uploads, ahead of k_prior_frame.
+ *   the step        of f18 (or f16), untouched: same kernels, same launches.
+ *   k_mono_pack     the frame checkNewKfReq sees, in slot order: the slots with (status & 3) == 1 whose filter `removed` byte (either
+ *                   kind) and pose `removed` byte are 0 -- none where the pose's action is OV2_POSE_P3P_RESET or OV2_POSE_PNP_RESET
+ *                   (resetFrame(), :1181-1203) --, with lmid, the tracked px, unpx, bv and is3d; the item's record: cur_Twc = the pose
+ *                   record's Twc, the keyframe's fields from the resident block, kf_Tcw the one set_keyframe derived, noccupcells =
+ *                   nb3dkps = -1.  Its thread 0 runs ov2_motion_update on the pose record's Twc and stores the new resident pose
+ *                   (that Twc) and state.
+ *   k_fkf_parallax  itself (csrc/fkf.hip), as ov2_kf_decision_batch launches it.
+ * Everything ov2_btracker_track_frame_epi_pose_end returns is returned as there; mono_results[b] adds the predicted Twc, resynced,
+ * the state after the update and the decision -- byte for byte what ov2_motion_apply_batch, the step with that pose,
+ * ov2_motion_update_batch and ov2_kf_decision_batch on the frame above return (tests/test_gpu_trackmono.py).
+ * The tracker's first frame: nothing runs, as in f18; the pose record carries the resident pose, the decision record is zero with
+ * decision = 1 and reason = OV2_KF_FIRST_FRAME (:77), the motion state is untouched.  Any later step: the motion model and the
+ * decision run for every active item, also where an item or the whole step has no keypoints (computePose returns at :667, the
+ * update stores, nb3dkps_ = 0 decides).  An item without a keyframe (n_kf == 0) or without keyframe info: the decision record is
+ * zero with decision = 0 and reason = OV2_KF_NO_KEYFRAME (:994).
+ * The 33 % rule stays on the host as in f16 / f18: for an item where it fires, _end re-runs the filter and the pose as there, then
+ * ov2_motion_update_batch and ov2_kf_decision_batch over just those items from the state BEFORE the step's update, and writes the
+ * corrected pose and state back into the resident block.  After _end the resident pose and state of every item are the route's.
+ * ov2_btracker_track_frame_end on such a step gives the tracking half, drops the rest and puts the resident pose and state back.
+ *
+ * OV2_EINVAL, checked on the host before anything is enqueued: everything the step of f18 (f16) refuses except Twc_h / Tcw_h, which
+ * are gone (a non-NULL Twc_h is refused); NULL lmid_h / time_h / frame_id_h; a time that is not finite or not after the item's
+ * prev_time where that is >= 0; no calibration; the grid ov2_kf_decision refuses; cfg.n_max > OV2_FKF_MAX_POINTS.  A predicted pose
+ * cannot be checked on the host any more; it is finite because the resident values are (set_pose refuses anything else, the
+ * chain's own tests refuse a non-finite pose) and dt > 0, which give a finite log and exp. */
+typedef struct {
+    ov2_frame_epi_pose_params step;   /* as f18                                                                              */
+    int doepipolar;                   /* SlamParams::doepipolar_: 1 the step of f18, 0 the step of f16                       */
+} ov2_track_mono_params;
+typedef struct {
+    ov2_frame_epi_pose_input step;    /* as f18; step.pose.Twc_h must be NULL                                                */
+    const double *time_h;             /* 1 per item: pcurframe_->img_time_                                                   */
+    const int *frame_id_h;            /* 1 per item: pcurframe_->id_                                                         */
+    const uint8_t *localba_is_on_h;   /* 1 per item: pslamstate_->blocalba_is_on_; NULL = all 0                              */
+} ov2_track_mono_input;
+typedef struct {
+    double Twc_pred[7];               /* the pose after applyMotionModel: what tracking and the pose chain started from      */
+    int resynced;                     /* applyMotionModel moved prevTwc_ to the frame pose                                   */
+    ov2_motion_state state;           /* after updateMotionModel                                                             */
+    ov2_kf_decision_result kf;        /* checkNewKfReq                                                                       */
+} ov2_track_mono_result;
+int  ov2_btracker_set_pose(ov2_btracker *t, int item, const double Twc[7]);
+int  ov2_btracker_get_pose(ov2_btracker *t, int item, double Twc[7]);
+int  ov2_btracker_reset_motion(ov2_btracker *t, int item);
+int  ov2_btracker_get_motion(ov2_btracker *t, int item, ov2_motion_state *state);
+int  ov2_btracker_set_keyframe_info(ov2_btracker *t, int item, int kf_id, double kf_time, int kf_nb3dkps);
+int  ov2_btracker_track_mono_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                   const double *wpt_h, const uint8_t *is3d_h, const int *n_h, int klt_use_prior,
+                                   const ov2_track_mono_params *params, const ov2_track_mono_input *input);
+int  ov2_btracker_track_mono_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_epifilter_result *epi_results,
+                                 ov2_pose_result *pose_results, ov2_track_mono_result *mono_results);
+int  ov2_btracker_track_mono(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                             const double *wpt_h, const uint8_t *is3d_h, const int *n_h, int klt_use_prior,
+                             const ov2_track_mono_params *params, const ov2_track_mono_input *input, float *out_xy_h, uint8_t *status_h,
+                             int *p3p_req, ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
+                             ov2_track_mono_result *mono_results);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ OV2_FKF_ALL, OV2_FKF_ONLY_2D, OV2_FKF_ONLY_3D = 0, 1, 2
 OV2_FKF_AVG, OV2_FKF_MEDIAN, OV2_FKF_AVG_WIDE = 0, 1, 2
 OV2_KF_C0, OV2_KF_C1, OV2_KF_C2, OV2_KF_CX = 1, 2, 4, 8
 OV2_KF_RET_FEW_CELLS, OV2_KF_RET_FEW_3D, OV2_KF_RET_MANY_3D, OV2_KF_RET_TIME, OV2_KF_NONFINITE = 16, 32, 64, 128, 256
+OV2_KF_FIRST_FRAME, OV2_KF_NO_KEYFRAME = 512, 1024      # ov2_btracker_track_mono
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -435,6 +436,27 @@ class FrameEpiPoseInput(C.Structure):
                 ("epi_seed_h", C.POINTER(C.c_ulonglong))]
 
 
+class MotionState(C.Structure):
+    """ov2_motion_state"""
+    _fields_ = [("prev_time", C.c_double), ("prevTwc", C.c_double * 7), ("log_relT", C.c_double * 6)]
+
+
+class TrackMonoParams(C.Structure):
+    """ov2_track_mono_params"""
+    _fields_ = [("step", FrameEpiPoseParams), ("doepipolar", C.c_int)]
+
+
+class TrackMonoInput(C.Structure):
+    """ov2_track_mono_input"""
+    _fields_ = [("step", FrameEpiPoseInput), ("time_h", C.POINTER(C.c_double)), ("frame_id_h", C.POINTER(C.c_int)),
+                ("localba_is_on_h", C.POINTER(C.c_uint8))]
+
+
+class TrackMonoResult(C.Structure):
+    """ov2_track_mono_result"""
+    _fields_ = [("Twc_pred", C.c_double * 7), ("resynced", C.c_int), ("state", MotionState), ("kf", KfDecisionResult)]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -638,6 +660,19 @@ SIGNATURES = {
                                                C.POINTER(PoseResult)]),
     "ov2_btracker_last_epi_inputs": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "ov2_se3_inverse": (_i, [_vp, _vp]),
+    "ov2_motion_apply": (_i, [_vp, C.POINTER(MotionState), _vp, _d, C.POINTER(MotionState), _vp, _vp, _vp]),
+    "ov2_motion_apply_batch": (_i, [_vp, _i, C.POINTER(MotionState), _vp, _vp, C.POINTER(MotionState), _vp, _vp, _vp]),
+    "ov2_motion_update": (_i, [_vp, C.POINTER(MotionState), _vp, _d, C.POINTER(MotionState)]),
+    "ov2_motion_update_batch": (_i, [_vp, _i, C.POINTER(MotionState), _vp, _vp, C.POINTER(MotionState)]),
+    "ov2_btracker_set_pose": (_i, [_vp, _i, _vp]),
+    "ov2_btracker_get_pose": (_i, [_vp, _i, _vp]),
+    "ov2_btracker_reset_motion": (_i, [_vp, _i]),
+    "ov2_btracker_get_motion": (_i, [_vp, _i, C.POINTER(MotionState)]),
+    "ov2_btracker_set_keyframe_info": (_i, [_vp, _i, _i, _d, _i]),
+    "ov2_btracker_track_mono_begin": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(TrackMonoParams), C.POINTER(TrackMonoInput)]),
+    "ov2_btracker_track_mono_end": (_i, [_vp, _vp, _vp, _vp, C.POINTER(EpifilterResult), C.POINTER(PoseResult), C.POINTER(TrackMonoResult)]),
+    "ov2_btracker_track_mono": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(TrackMonoParams), C.POINTER(TrackMonoInput),
+                                     _vp, _vp, _vp, C.POINTER(EpifilterResult), C.POINTER(PoseResult), C.POINTER(TrackMonoResult)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

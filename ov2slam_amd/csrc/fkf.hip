@@ -15,21 +15,7 @@
 #define FKF_THREADS 256
 #define FKF_INF_BITS 0x7f800000
 
-struct FkfParamsD {
-    double K[4];
-    int ncellsize, nbwcells, nbhcells, nbmaxkps;
-    float finit_parallax;
-    int stereo, unrot, filter, stat, decide;
-};
-// 176 bytes, 16-byte aligned sections in the staging buffer
-struct FkfItemD {
-    int cur0, n_cur, kf0, n_kf;
-    int cur_id, kf_id, kf_nb3dkps, localba_is_on;
-    int noccupcells, nb3dkps, pad0, pad1;
-    double cur_time, kf_time;
-    double cur_Twc[7], kf_Tcw[7];
-};
-#define FKF_OUT_INTS 12       // per item: parallax bits, n, n_distinct, n_nonfinite, noccupcells, nb3dkps, n_out_of_grid, decision, reason
+// FkfParamsD, FkfItemD, FKF_OUT_INTS: fkf_dev.hpp (the lock-step step fills the item records on the device)
 
 __global__ __launch_bounds__(FKF_THREADS) void k_fkf_parallax(FkfParamsD P, const FkfItemD *__restrict__ items, const int *__restrict__ cur_lmid,
                                                               const float2 *__restrict__ cur_px, const float2 *__restrict__ cur_unpx,
@@ -226,6 +212,32 @@ __global__ __launch_bounds__(FKF_THREADS) void k_fkf_sampson(const FkfItemD *__r
     bad[g] = e > thr ? 1 : 0;                                                      // :641
 }
 
+// k_fkf_parallax as ov2_kf_decision_batch launches it (unrot = 1, OV2_FKF_ALL, OV2_FKF_MEDIAN, decide = 1) on a caller-owned device
+// block: the lock-step step (trackb.hip) puts it behind its own kernels.  params must have passed fkf_check_decide.
+int ov2_launch_kf_decision(hipStream_t s, const ov2_fkf_params *params, int n_items, const FkfItemD *items_d, const int *cur_lmid,
+                           const float2 *cur_px, const float2 *cur_unpx, const double *cur_bv, const uint8_t *cur_is3d, const int *kf_lmid,
+                           const float2 *kf_unpx, int *out_d)
+{
+    FkfParamsD P;
+    for (int j = 0; j < 4; j++) P.K[j] = params->K[j];
+    P.ncellsize = params->ncellsize; P.nbwcells = params->nbwcells; P.nbhcells = params->nbhcells; P.nbmaxkps = params->nbmaxkps;
+    P.finit_parallax = params->finit_parallax; P.stereo = params->stereo ? 1 : 0;
+    P.unrot = 1; P.filter = OV2_FKF_ALL; P.stat = OV2_FKF_MEDIAN; P.decide = 1;
+    hipLaunchKernelGGL(k_fkf_parallax, dim3(n_items), dim3(FKF_THREADS), 0, s, P, items_d, cur_lmid, cur_px, cur_unpx, cur_bv, cur_is3d,
+                       kf_lmid, kf_unpx, out_d);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
+int fkf_check_decide(const ov2_fkf_params *params)
+{
+    OV2_REQUIRE(params->ncellsize > 0 && params->nbwcells > 0 && params->nbhcells > 0, OV2_EINVAL,
+                "ncellsize / nbwcells / nbhcells not positive");
+    OV2_REQUIRE((long long)params->nbwcells * params->nbhcells <= OV2_FKF_MAX_CELLS, OV2_EUNSUPPORTED,
+                "more than OV2_FKF_MAX_CELLS (65536) grid cells");
+    return OV2_OK;
+}
+
 static inline size_t fkf_al(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // every input check of the three entry points, before the context is looked at; full: the arrays the parallax / decision kernel reads
@@ -273,12 +285,7 @@ static int fkf_run(ov2_ctx *ctx, const ov2_fkf_params *params, int n_items, cons
     OV2_REQUIRE(unrot == 0 || unrot == 1, OV2_EINVAL, "unrot is not 0 or 1");
     OV2_REQUIRE(filter == OV2_FKF_ALL || filter == OV2_FKF_ONLY_2D || filter == OV2_FKF_ONLY_3D, OV2_EINVAL, "unknown filter");
     OV2_REQUIRE(stat == OV2_FKF_AVG || stat == OV2_FKF_MEDIAN || stat == OV2_FKF_AVG_WIDE, OV2_EINVAL, "unknown stat");
-    if (decide) {
-        OV2_REQUIRE(params->ncellsize > 0 && params->nbwcells > 0 && params->nbhcells > 0, OV2_EINVAL,
-                    "ncellsize / nbwcells / nbhcells not positive");
-        OV2_REQUIRE((long long)params->nbwcells * params->nbhcells <= OV2_FKF_MAX_CELLS, OV2_EUNSUPPORTED,
-                    "more than OV2_FKF_MAX_CELLS (65536) grid cells");
-    }
+    if (decide) { const int rcd = fkf_check_decide(params);  if (rcd) return rcd; }
     size_t N = 0, M = 0;
     int n_max = 0;
     int rc = fkf_check_items(n_items, items, true, &N, &M, &n_max);

@@ -49,3 +49,28 @@ __device__ __forceinline__ float fkf_wide_add64(float sum, double d)
 // every input check fkf.hip makes on its items (full: the arrays the parallax / decision kernel reads); N / M: the keypoints of all
 // frames / keyframes, n_max: the largest frame
 int fkf_check_items(int n_items, const ov2_fkf_item *items, bool full, size_t *N, size_t *M, int *n_max);
+
+// the kernels' parameter block, the item record and the result ints of fkf.hip: the lock-step step (mono.hip) fills the records on
+// the device and reads the ints
+struct FkfParamsD {
+    double K[4];
+    int ncellsize, nbwcells, nbhcells, nbmaxkps;
+    float finit_parallax;
+    int stereo, unrot, filter, stat, decide;
+};
+// 176 bytes, 16-byte aligned sections in the staging buffer
+struct FkfItemD {
+    int cur0, n_cur, kf0, n_kf;
+    int cur_id, kf_id, kf_nb3dkps, localba_is_on;
+    int noccupcells, nb3dkps, pad0, pad1;
+    double cur_time, kf_time;
+    double cur_Twc[7], kf_Tcw[7];
+};
+#define FKF_OUT_INTS 12       // per item: parallax bits, n, n_distinct, n_nonfinite, noccupcells, nb3dkps, n_out_of_grid, decision, reason
+
+// what ov2_kf_decision refuses in its params (the grid)
+int fkf_check_decide(const ov2_fkf_params *params);
+// k_fkf_parallax in the form of ov2_kf_decision_batch on a caller-owned device block (fkf.hip)
+int ov2_launch_kf_decision(hipStream_t s, const ov2_fkf_params *params, int n_items, const FkfItemD *items_d, const int *cur_lmid,
+                           const float2 *cur_px, const float2 *cur_unpx, const double *cur_bv, const uint8_t *cur_is3d, const int *kf_lmid,
+                           const float2 *kf_unpx, int *out_d);

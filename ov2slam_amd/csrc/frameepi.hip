@@ -102,12 +102,7 @@ int ov2_frame_epi_hook(hipStream_t s, uint8_t *sel, void *arg)
 
 void ov2_fe_invert(const double T[7], double out[7])
 {
-    const double x = -T[3], y = -T[4], z = -T[5], w = T[6];        // the conjugate
-    const double R[9] = {1. - 2. * (y * y + z * z), 2. * (x * y - z * w), 2. * (x * z + y * w),
-                         2. * (x * y + z * w), 1. - 2. * (x * x + z * z), 2. * (y * z - x * w),
-                         2. * (x * z - y * w), 2. * (y * z + x * w), 1. - 2. * (x * x + y * y)};
-    for (int r = 0; r < 3; r++) out[r] = -((R[3 * r] * T[0] + R[3 * r + 1] * T[1]) + R[3 * r + 2] * T[2]);
-    out[3] = x; out[4] = y; out[5] = z; out[6] = w;
+    fe_invert_hd(T, out);
 }
 
 extern "C" int ov2_se3_inverse(const double T[7], double out[7])

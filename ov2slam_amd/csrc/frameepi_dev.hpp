@@ -37,5 +37,15 @@ struct FeStep {
     int n_active;
 };
 int ov2_frame_epi_hook(hipStream_t s, uint8_t *sel, void *arg);     // an ov2_fp_hook (pose_dev.hpp); arg: FeStep *
-// [t q] of the inverse of the transform [t q] (Sophus' SE3::inverse: the conjugate, and minus the rotated translation)
+// [t q] of the inverse of the transform [t q] (Sophus' SE3::inverse: the conjugate, and minus the rotated translation).  Products,
+// sums and negations only, compiled without contraction: host and device (motion.hip) give the same bits.  out may not alias T.
+__host__ __device__ inline void fe_invert_hd(const double *T, double *out)
+{
+    const double x = -T[3], y = -T[4], z = -T[5], w = T[6];        // the conjugate
+    const double R[9] = {1. - 2. * (y * y + z * z), 2. * (x * y - z * w), 2. * (x * z + y * w),
+                         2. * (x * y + z * w), 1. - 2. * (x * x + z * z), 2. * (y * z - x * w),
+                         2. * (x * z - y * w), 2. * (y * z + x * w), 1. - 2. * (x * x + y * y)};
+    for (int r = 0; r < 3; r++) out[r] = -((R[3 * r] * T[0] + R[3 * r + 1] * T[1]) + R[3 * r + 2] * T[2]);
+    out[3] = x; out[4] = y; out[5] = z; out[6] = w;
+}
 void ov2_fe_invert(const double T[7], double out[7]);

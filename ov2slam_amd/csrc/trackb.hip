@@ -23,10 +23,15 @@
 // packed into the epipolar block, the chain of epifilter.hip on it, the removals applied to the select bytes), against a keyframe
 // that ov2_btracker_set_keyframe keeps on the device: trackMono's per-frame sequence with doepipolar_ == 1 in one enqueue, byte-equal
 // to the three separate calls (tests/test_gpu_frameepi.py).
+// ov2_btracker_track_mono is trackMono after initialisation: that step (or the pose step, doepipolar_ == 0) between the motion model
+// and the keyframe decision (mono.hip: k_mono_apply in front, k_mono_pack and fkf.hip's k_fkf_parallax behind), the frame pose, the
+// motion state and the keyframe's id / time / nb3dkps resident on the device with host mirrors; byte-equal to ov2_motion_apply_batch,
+// the step, ov2_motion_update_batch and ov2_kf_decision_batch (tests/test_gpu_trackmono.py).
 #include "common.hpp"
 #include "keypoint_dev.hpp"
 #include "pose_dev.hpp"
 #include "frameepi_dev.hpp"
+#include "mono_dev.hpp"
 #include "trackb_layout.hpp"
 #include <cmath>
 #include <deque>
@@ -40,6 +45,8 @@
 static_assert(sizeof(PoseOut) == BT_POSE_OUT_BYTES, "trackb_layout.hpp: the pose block's record");
 static_assert(sizeof(EpifOut) == BT_EPIF_OUT_BYTES, "trackb_layout.hpp: the epipolar block's record");
 static_assert(sizeof(FeKfHdr) == BT_KF_HDR_BYTES, "trackb_layout.hpp: the index block's header");
+static_assert(sizeof(ov2_motion_state) == BT_MOTION_STATE_BYTES, "trackb_layout.hpp: the mono blocks' state");
+static_assert(sizeof(FkfItemD) == BT_FKF_ITEM_BYTES && 4 * FKF_OUT_INTS == BT_KF_DEC_BYTES, "trackb_layout.hpp: the mono blocks' records");
 
 // A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
 // (zero copy), or mirrored on the device with a copy up before the kernels and a copy down behind them.
@@ -85,7 +92,9 @@ struct IoBlock {
 // One step as its _begin call describes it.  Each form includes the one before it: map -- the priors come from the device (wpt_h /
 // is3d_h / Tcw_h; prior_xy_h / has_prior_h are unused); pose -- the pose of ov2_btracker_track_frame_pose follows in the same
 // enqueue; epi -- the filter of ov2_btracker_track_frame_epi_pose runs between the pose's select and its pack.
-enum StepForm { STEP_PLAIN = 0, STEP_MAP, STEP_POSE, STEP_EPI };
+// mono -- ov2_btracker_track_mono: the epi form (or, with doepipolar == 0, the pose form) between the motion model and the keyframe
+// decision; track_frame_begin resolves it to that inner form plus Pending::mono.
+enum StepForm { STEP_PLAIN = 0, STEP_MAP, STEP_POSE, STEP_EPI, STEP_MONO };
 struct StepArgs {
     StepForm form = STEP_PLAIN;
     int n_active = 0, stride = 0, klt_use_prior = 0;
@@ -95,6 +104,7 @@ struct StepArgs {
     const double *wpt_h = nullptr; const uint8_t *is3d_h = nullptr; const double *Tcw_h = nullptr;         // map and later
     const ov2_frame_pose_params *pp = nullptr; const ov2_frame_pose_input *pin = nullptr;                  // pose (epi: the pose halves of epp / ein)
     const ov2_frame_epi_pose_params *epp = nullptr; const ov2_frame_epi_pose_input *ein = nullptr;         // epi
+    const ov2_track_mono_params *mp = nullptr; const ov2_track_mono_input *min = nullptr;                  // mono (epp / ein: their step halves)
 };
 
 // ov2_btracker_last_pose_inputs / ov2_btracker_last_epi_inputs: what the last finished step of the kind fed its chain.  Per item the
@@ -146,9 +156,15 @@ struct ov2_btracker {
     long pre_count = 0;
     // the four blocks the host and the kernels share (IoBlock; their sections: trackb_layout.hpp).  The point block decides zero_copy
     // for all of them; the map, pose and epipolar blocks are allocated by the first step of their form
-    IoBlock pt, map, pose, epi;
+    IoBlock pt, map, pose, epi, mono;
     bool zero_copy = false;
-    BtPointLayout pl; BtMapLayout ml; BtPoseLayout ql; BtEpiLayout el;
+    BtPointLayout pl; BtMapLayout ml; BtPoseLayout ql; BtEpiLayout el; BtMonoLayout nl;
+    // ov2_btracker_track_mono: the resident block (frame pose, motion state, keyframe info per item) with its host mirrors, and the
+    // work block of k_mono_pack / k_fkf_parallax (both device only), allocated by the first setter or step of the kind
+    uint8_t *dres = nullptr, *dmw = nullptr;
+    std::vector<double> res_T, res_kt;
+    std::vector<ov2_motion_state> res_st;
+    std::vector<MonoKfInfo> res_ki;
     bool has_calib = false;
     KpCalib calib;
     std::vector<int> last_n;           // per item: keypoints of the last track_frame (0 before / after a call that tracked nothing)
@@ -183,7 +199,10 @@ struct ov2_btracker {
                      // epipolar block, which the device only reads)
                      ov2_frame_pose_params pp; PoseLayout L; std::vector<double> Twc; std::vector<uint8_t> req;
                      std::vector<unsigned long long> seed;
-                     ov2_epifilter_params ep; EpifLayout eL; } pend;
+                     ov2_epifilter_params ep; EpifLayout eL;
+                     // mono: the step runs between the motion model and the decision; ran: not the tracker's first frame
+                     bool mono = false, mono_ran = false; ov2_fkf_params fkf; std::vector<double> time;
+                     std::vector<int> frame_id, localba; } pend;
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
 };
@@ -206,7 +225,9 @@ static void btracker_free(ov2_btracker *t)
         if (t->dimg[i]) (void)hipFree(t->dimg[i]);
         if (t->draw[i]) (void)hipFree(t->draw[i]);
     }
-    for (IoBlock *b : {&t->pt, &t->map, &t->pose, &t->epi}) b->release();
+    for (IoBlock *b : {&t->pt, &t->map, &t->pose, &t->epi, &t->mono}) b->release();
+    if (t->dres) (void)hipFree(t->dres);
+    if (t->dmw) (void)hipFree(t->dmw);
     if (t->dwork) (void)hipFree(t->dwork);
     if (t->depi) (void)hipFree(t->depi);
     if (t->dfx) (void)hipFree(t->dfx);
@@ -246,6 +267,9 @@ static int enqueue_preprocess(ov2_btracker *t, ov2_ctx *on, ov2_pyr *dst, int wh
     return OV2_OK;
 }
 
+static MonoArgs mono_args(ov2_btracker *t, const ov2_btracker::Pending &P, bool chain);           // (below, with the mono side's staging)
+static int enqueue_mono_tail(ov2_btracker *t, const ov2_btracker::Pending &P, bool chain);
+
 // kltTracking of items [0, P.n_active) for the step P describes: keypoint block in, the fused LK launch, computeKeypoint, result block out
 // map form: k_prior_frame fills the prior and flag slots from the map side first
 // pose form: the pose set, computePose's chain and the removal bytes follow k_compute_keypoints; epi form: with the filter's hook
@@ -262,6 +286,15 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
     int rc = t->pt.upload(s, pl.in_bytes);  if (rc) return rc;
     if (P.form >= STEP_MAP) {
         rc = t->map.upload(s, ml.map_bytes);  if (rc) return rc;
+        if (P.mono) {
+            // the motion model, behind the uploads of the two blocks it writes into (a mirrored block's upload would overwrite it)
+            // and ahead of k_prior_frame; the filter's inputs travel here when the inner step does not take them (lmid is needed)
+            rc = t->pose.upload(s, t->ql.q_in);  if (rc) return rc;
+            rc = t->mono.upload(s, t->nl.n_in);  if (rc) return rc;
+            if (P.form != STEP_EPI) { rc = t->epi.upload(s, t->el.e_in);  if (rc) return rc; }
+            rc = ov2_launch_mono_apply(s, mono_args(t, P, true), n);
+            if (rc != OV2_OK) return rc;
+        }
         rc = ov2_launch_prior_frame(s, t->calib, (double)c.w, (double)c.h, P.use_prior ? 1 : 0, m + ml.m_it, (const double *)(m + ml.m_T),
                                     (const float *)(k + pl.o_kps), m + ml.m_3d, (const double *)(m + ml.m_w), (float *)(k + pl.o_pri),
                                     k + pl.o_flg, c.n_max, n);
@@ -278,7 +311,7 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
     }
     if (P.form >= STEP_POSE) {
         const BtPoseLayout &ql = t->ql;
-        rc = t->pose.upload(s, ql.q_in);  if (rc) return rc;
+        if (!P.mono) { rc = t->pose.upload(s, ql.q_in);  if (rc) return rc; }
         uint8_t *q = t->pose.k;
         bool search = P.pp.dop3p != 0;
         for (int b = 0; b < n; b++) search = search || P.req[(size_t)b];
@@ -316,6 +349,7 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
         if (rc != OV2_OK) return rc;
         rc = t->pose.download(s, ql.q_out, ql.pose_bytes);
         if (rc == OV2_OK && P.form == STEP_EPI) rc = t->epi.download(s, t->el.e_out, t->el.epi_bytes);
+        if (rc == OV2_OK && P.mono) rc = enqueue_mono_tail(t, P, true);
         if (rc != OV2_OK) return rc;
     }
     rc = t->pt.download(s, pl.o_out, pl.blk_bytes);
@@ -377,7 +411,7 @@ static int stage_map(ov2_btracker *t, int n_active, const double *wpt, const uin
     for (int b = 0; b < t->batch; b++) {
         it[4 * b] = (int)((size_t)b * nm); it[4 * b + 1] = b < n_active ? n_h[b] : 0; it[4 * b + 2] = it[4 * b + 3] = 0;
     }
-    memcpy(hmap + ml.m_T, Tcw, 56 * (size_t)n_active);
+    if (Tcw) memcpy(hmap + ml.m_T, Tcw, 56 * (size_t)n_active);      // (mono: k_mono_apply writes the inverse of the predicted pose)
     for (int b = 0; b < n_active; b++) {
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
         if (!n) continue;
@@ -388,10 +422,14 @@ static int stage_map(ov2_btracker *t, int n_active, const double *wpt, const uin
 }
 
 // what a pose step refuses beyond the map form's checks (n_active and the counts are known to be in range); *L: the chain's layout
-static int check_pose(const ov2_btracker *t, const StepArgs &A, const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, PoseLayout *L)
+// mono: the pose comes from the device (Twc_h must be NULL)
+static int check_pose(const ov2_btracker *t, const StepArgs &A, const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, PoseLayout *L,
+                      bool mono)
 {
     OV2_REQUIRE(pp && in, OV2_EINVAL, "ov2_btracker_track_frame_pose: NULL params / input");
-    OV2_REQUIRE(in->Twc_h && in->p3p_req_h && in->seed_h, OV2_EINVAL, "ov2_btracker_track_frame_pose: NULL Twc_h / p3p_req_h / seed_h");
+    OV2_REQUIRE((mono ? !in->Twc_h : in->Twc_h != nullptr) && in->p3p_req_h && in->seed_h, OV2_EINVAL,
+                mono ? "ov2_btracker_track_mono: Twc_h must be NULL (the pose is resident), p3p_req_h / seed_h must not"
+                     : "ov2_btracker_track_frame_pose: NULL Twc_h / p3p_req_h / seed_h");
     int rc = pose_check_params(&pp->pose);  if (rc) return rc;
     OV2_REQUIRE(pp->n_rows >= 0, OV2_EINVAL, "negative count (n_rows)");
     OV2_REQUIRE(pp->n_rows <= OV2_P3P_MAX_ROWS, OV2_EINVAL, "capacity: more than 4096 sample rows in one problem");
@@ -399,7 +437,7 @@ static int check_pose(const ov2_btracker *t, const StepArgs &A, const ov2_frame_
     rc = pose_layout(t->batch, t->cfg.n_max, pp->n_rows, L);  if (rc) return rc;
     const size_t nm = (size_t)t->cfg.n_max;
     for (int b = 0; b < A.n_active; b++) {
-        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(in->Twc_h[7 * (size_t)b + c]), OV2_EINVAL, "Twc not finite");
+        for (int c = 0; c < 7 && !mono; c++) OV2_REQUIRE(std::isfinite(in->Twc_h[7 * (size_t)b + c]), OV2_EINVAL, "Twc not finite");
         const size_t n = (size_t)(A.n_h ? A.n_h[b] : 0), o = (size_t)b * nm;
         for (size_t i = 0; i < n; i++) {
             if (in->scale_h) OV2_REQUIRE(in->scale_h[o + i] >= -60 && in->scale_h[o + i] <= 60, OV2_EINVAL, "|scale| > 60");
@@ -430,7 +468,7 @@ static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params
     }
     uint8_t *hpose = t->pose.h;
     const BtPoseLayout &ql = t->ql;
-    memcpy(hpose + ql.q_T, in->Twc_h, 56 * (size_t)n_active);
+    if (in->Twc_h) memcpy(hpose + ql.q_T, in->Twc_h, 56 * (size_t)n_active);     // (mono: k_mono_apply writes the predicted pose)
     memcpy(hpose + ql.q_seed, in->seed_h, 8 * (size_t)n_active);
     uint8_t *fl = hpose + ql.q_fl;
     for (int b = 0; b < n_active; b++) {
@@ -504,8 +542,115 @@ static void stage_epi(ov2_btracker *t, int n_active, const ov2_frame_epi_pose_in
     const size_t nm = (size_t)t->cfg.n_max;
     for (int b = 0; b < n_active; b++)
         if (n_h[b] > 0) memcpy(t->epi.h + t->el.e_lm + 4 * nm * (size_t)b, in->lmid_h + nm * (size_t)b, 4 * (size_t)n_h[b]);
-    memcpy(t->epi.h + t->el.e_nk, in->nbkfs_h, 4 * (size_t)n_active);
-    memcpy(t->epi.h + t->el.e_sd, in->epi_seed_h, 8 * (size_t)n_active);
+    if (in->nbkfs_h) memcpy(t->epi.h + t->el.e_nk, in->nbkfs_h, 4 * (size_t)n_active);         // (NULL: mono without the filter)
+    if (in->epi_seed_h) memcpy(t->epi.h + t->el.e_sd, in->epi_seed_h, 8 * (size_t)n_active);
+}
+
+// the host mirrors of items [b0, b1) to the resident block, on the context's stream; returns when the copies are done
+static int mono_push(ov2_btracker *t, int b0, int b1)
+{
+    const BtMonoLayout &nl = t->nl;
+    const size_t o = (size_t)b0, n = (size_t)(b1 - b0);
+    hipStream_t s = t->ctx->stream;
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_T + 56 * o, t->res_T.data() + 7 * o, 56 * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_st + sizeof(ov2_motion_state) * o, t->res_st.data() + o, sizeof(ov2_motion_state) * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_kt + 8 * o, t->res_kt.data() + o, 8 * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_ki + sizeof(MonoKfInfo) * o, t->res_ki.data() + o, sizeof(MonoKfInfo) * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipStreamSynchronize(s));
+    return OV2_OK;
+}
+
+// The mono side's buffers, allocated by the first setter or step of the kind: the I/O block, the resident block with its host mirrors
+// (pose: the identity; state: reset(); no keyframe info) and the work block
+static int ensure_mono(ov2_btracker *t)
+{
+    if (t->dres) return OV2_OK;
+    const char *who = "ov2_btracker_track_mono";
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const size_t B = (size_t)t->batch;
+    if (!t->mono.h) { const int rc = t->mono.alloc(t->nl.mono_bytes, t->zero_copy, false, who);  if (rc) return rc; }
+    uint8_t *res = nullptr, *w = nullptr;
+    hipError_t e = hipMalloc((void **)&res, t->nl.res_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&w, t->nl.work_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(res, 0, t->nl.res_bytes, t->ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w, 0, t->nl.work_bytes, t->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+    if (e != hipSuccess) {
+        if (res) (void)hipFree(res);
+        if (w) (void)hipFree(w);
+        (void)hipGetLastError();
+        ov2_set_error("%s: %s", who, hipGetErrorString(e));
+        return OV2_ENOMEM;
+    }
+    ov2_motion_state s0;
+    memset(&s0, 0, sizeof s0);
+    s0.prev_time = -1.; s0.prevTwc[6] = 1.;
+    t->res_st.assign(B, s0);
+    t->res_T.assign(7 * B, 0.);
+    for (size_t b = 0; b < B; b++) t->res_T[7 * b + 6] = 1.;
+    t->res_kt.assign(B, 0.);
+    t->res_ki.assign(B, MonoKfInfo{0, 0, 0, 0});
+    t->dres = res; t->dmw = w;
+    return mono_push(t, 0, t->batch);
+}
+
+// the mono inputs of a step into the I/O block
+static void stage_mono(ov2_btracker *t, const ov2_btracker::Pending &P)
+{
+    const size_t n = (size_t)P.n_active;
+    memcpy(t->mono.h + t->nl.n_tm, P.time.data(), 8 * n);
+    memcpy(t->mono.h + t->nl.n_id, P.frame_id.data(), 4 * n);
+    memcpy(t->mono.h + t->nl.n_ba, P.localba.data(), 4 * n);
+}
+
+// the device pointers of a mono step (mono_dev.hpp); chain: the step's kernels ran (else every frame is empty)
+static MonoArgs mono_args(ov2_btracker *t, const ov2_btracker::Pending &P, bool chain)
+{
+    const BtMonoLayout &nl = t->nl;
+    const BtPointLayout &pl = t->pl;
+    uint8_t *k = t->pt.k, *m = t->map.k, *q = t->pose.k, *e = t->epi.k, *io = t->mono.k, *r = t->dres, *w = t->dmw;
+    MonoArgs a;
+    a.r_T = (double *)(r + nl.r_T); a.r_st = (ov2_motion_state *)(r + nl.r_st); a.r_kt = (const double *)(r + nl.r_kt);
+    a.r_ki = (const MonoKfInfo *)(r + nl.r_ki); a.hdr = (const FeKfHdr *)t->dfx;
+    a.time = (const double *)(io + nl.n_tm); a.frame_id = (const int *)(io + nl.n_id); a.localba = (const int *)(io + nl.n_ba);
+    a.q_T = (double *)(q + t->ql.q_T); a.m_T = (double *)(m + t->ml.m_T); a.pT = (double *)(io + nl.n_pT);
+    a.sa = (ov2_motion_state *)(io + nl.n_sa); a.rs = io + nl.n_rs;
+    a.n_dev = (const int *)(k + pl.o_n); a.status = k + pl.o_st; a.is3d = m + t->ml.m_3d;
+    a.out_xy = (const float2 *)(k + pl.o_out); a.unpx = (const float2 *)(k + pl.o_unpx); a.bv = (const double *)(k + pl.o_bv);
+    a.lmid = (const int *)(e + t->el.e_lm);
+    a.epi_removed = chain && P.form == STEP_EPI ? e + t->el.e_rm : nullptr;
+    a.pose_removed = q + t->ql.q_rm; a.pose_out = chain ? (const PoseOut *)(q + t->ql.q_out) : nullptr;
+    a.items = (FkfItemD *)(w + nl.w_it); a.c_lmid = (int *)(w + nl.w_lm); a.c_px = (float2 *)(w + nl.w_px); a.c_unpx = (float2 *)(w + nl.w_un);
+    a.c_bv = (double *)(w + nl.w_bv); a.c_is3d = w + nl.w_3d; a.ncur_io = (int *)(io + nl.n_nc); a.su = (ov2_motion_state *)(io + nl.n_su);
+    a.n_max = t->cfg.n_max;
+    return a;
+}
+
+// behind the step's kernels (or, with chain == false, behind k_mono_apply alone): the frame checkNewKfReq sees, the model's update,
+// k_fkf_parallax on that frame against the resident keyframes, and the mono results on their way back
+static int enqueue_mono_tail(ov2_btracker *t, const ov2_btracker::Pending &P, bool chain)
+{
+    const hipStream_t s = t->ctx->stream;
+    const BtMonoLayout &nl = t->nl;
+    const MonoArgs a = mono_args(t, P, chain);
+    int rc = ov2_launch_mono_pack(s, a, P.n_active);
+    if (rc != OV2_OK) return rc;
+    rc = ov2_launch_kf_decision(s, &P.fkf, P.n_active, a.items, a.c_lmid, a.c_px, a.c_unpx, a.c_bv, a.c_is3d,
+                                (const int *)(t->depi + t->eL0.o_kl), (const float2 *)(t->depi + t->eL0.o_ku), (int *)(t->mono.k + nl.n_dec));
+    if (rc != OV2_OK) return rc;
+    return t->mono.download(s, nl.n_in, nl.mono_bytes);
+}
+
+// a mono step in which no item carries a keypoint (not the first frame): the motion model and the decision run all the same
+static int enqueue_mono_empty(ov2_btracker *t, const ov2_btracker::Pending &P)
+{
+    const hipStream_t s = t->ctx->stream;
+    int rc = t->map.upload(s, t->ml.map_bytes);  if (rc) return rc;
+    rc = t->pose.upload(s, t->ql.q_in);  if (rc) return rc;
+    rc = t->mono.upload(s, t->nl.n_in);  if (rc) return rc;
+    rc = ov2_launch_mono_apply(s, mono_args(t, P, false), P.n_active);
+    if (rc != OV2_OK) return rc;
+    return enqueue_mono_tail(t, P, false);
 }
 
 static void stage_points(ov2_btracker *t, int n_active, const float *kps, const float *pri, const uint8_t *has_prior, const int *n_h, int use_prior)
@@ -607,7 +752,7 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     t->img_pitch = bt_img_pitch(cfg->w);
     t->img_bytes = bt_img_bytes(cfg->w, cfg->h);
     t->pl = bt_point_layout(batch, cfg->n_max); t->ml = bt_map_layout(batch, cfg->n_max);
-    t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max);
+    t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max); t->nl = bt_mono_layout(batch, cfg->n_max);
     t->det_in_bytes = bt_det_in_bytes(batch, cfg->n_max);
     hipError_t e = hipSuccess;
     for (int i = 0; i < BT_IMG_SETS && e == hipSuccess; i++) {
@@ -730,7 +875,12 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
 {
     const int n_active = A.n_active;
     const int *n_h = A.n_h;
-    const bool map = A.form >= STEP_MAP, pose = A.form >= STEP_POSE, epi = A.form == STEP_EPI;
+    const bool mono = A.form == STEP_MONO;
+    OV2_REQUIRE(!mono || (A.mp && A.min), OV2_EINVAL, "ov2_btracker_track_mono: NULL params / input");
+    const StepForm form = mono ? (A.mp->doepipolar ? STEP_EPI : STEP_POSE) : A.form;         // the inner step
+    const bool map = form >= STEP_MAP, pose = form >= STEP_POSE, epi = form == STEP_EPI;
+    const ov2_frame_epi_pose_params *epp = mono ? &A.mp->step : A.epp;
+    const ov2_frame_epi_pose_input *ein = mono ? &A.min->step : A.ein;
     OV2_REQUIRE(t && A.img_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
@@ -744,21 +894,36 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
         n_total += n;
     }
-    if (map) OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.wpt_h && A.is3d_h && A.Tcw_h && n_h), OV2_EINVAL, "NULL point buffer");
+    if (map) OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.wpt_h && A.is3d_h && (mono || A.Tcw_h) && n_h), OV2_EINVAL, "NULL point buffer");
     else OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
     const ov2_frame_pose_params *pp = A.pp;
     const ov2_frame_pose_input *pin = A.pin;
     PoseLayout poseL;
     EpifLayout epiL;
-    if (epi) {                                                           // (pp / pin: the pose halves of epp / ein)
-        OV2_REQUIRE(A.epp && A.ein, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
-        pp = &A.epp->pose; pin = &A.ein->pose;
+    if (epi || mono) {                                                   // (pp / pin: the pose halves of epp / ein)
+        OV2_REQUIRE(epp && ein, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
+        pp = &epp->pose; pin = &ein->pose;
     }
-    if (pose) { const int rcp = check_pose(t, A, pp, pin, &poseL);  if (rcp != OV2_OK) return rcp; }
-    if (epi) { const int rce = check_epi(t, A.epp, A.ein, &epiL);  if (rce != OV2_OK) return rce; }
+    if (pose) { const int rcp = check_pose(t, A, pp, pin, &poseL, mono);  if (rcp != OV2_OK) return rcp; }
+    if (epi) { const int rce = check_epi(t, epp, ein, &epiL);  if (rce != OV2_OK) return rce; }
+    if (mono) {
+        // what the mono step refuses of its own.  The predicted pose cannot be checked on the host: the resident pose and state are
+        // finite (the setters refuse anything else, the kernels' results derive from finite ones) and dt > 0, so log and exp are finite
+        OV2_REQUIRE(A.mp->doepipolar == 0 || A.mp->doepipolar == 1, OV2_EINVAL, "doepipolar is not 0 or 1");
+        OV2_REQUIRE(ein->lmid_h, OV2_EINVAL, "ov2_btracker_track_mono: NULL lmid_h");
+        OV2_REQUIRE(A.min->time_h && A.min->frame_id_h, OV2_EINVAL, "ov2_btracker_track_mono: NULL time_h / frame_id_h");
+        OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+        const int rcd = fkf_check_decide(&epp->epi.fkf);  if (rcd != OV2_OK) return rcd;
+        for (int b = 0; b < n_active; b++) {
+            const double tm = A.min->time_h[b], prev = t->res_st.empty() ? -1. : t->res_st[(size_t)b].prev_time;
+            OV2_REQUIRE(std::isfinite(tm), OV2_EINVAL, "time not finite");
+            OV2_REQUIRE(!(prev >= 0. && tm <= prev), OV2_EINVAL, "ov2_btracker_track_mono: time_h is not after the item's prev_time");
+        }
+    }
     for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = t->last_pn[(size_t)b] = 0;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    if (mono) { const int rcm = ensure_mono(t);  if (rcm != OV2_OK) return rcm; }
     int which = 0;
     bool prepared = false;
     t->raw_which = -1;                                                   // staging may rewrite any set
@@ -777,16 +942,25 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     auto commit = [&]() { if (prepared) t->prepq.pop_front(); else t->pre_count++; t->frames++; t->raw_which = which; t->raw_n = n_active; };
     t->cur = (int)(t->frames % BT_SETS);                                 // prev_pyr_.swap(cur_pyr_)  (:1169): frame k lives in set k % BT_SETS
     ov2_btracker::Pending &P = t->pend;
-    P.form = A.form; P.n_active = n_active; P.use_prior = A.klt_use_prior; P.kps = A.kps_xy_h; P.has_prior = A.has_prior_h;
+    P.form = form; P.n_active = n_active; P.use_prior = A.klt_use_prior; P.kps = A.kps_xy_h; P.has_prior = A.has_prior_h;
     P.n.assign((size_t)n_active, 0);
     if (n_h) for (int b = 0; b < n_active; b++) P.n[(size_t)b] = n_h[b];
     if (pose) {
         P.pp = *pp; P.L = poseL;
-        P.Twc.assign(pin->Twc_h, pin->Twc_h + 7 * (size_t)n_active);
+        if (mono) P.Twc.assign(7 * (size_t)n_active, 0.);                // (the predicted poses: _end reads them back)
+        else P.Twc.assign(pin->Twc_h, pin->Twc_h + 7 * (size_t)n_active);
         P.req.assign(pin->p3p_req_h, pin->p3p_req_h + n_active);
         P.seed.assign(pin->seed_h, pin->seed_h + n_active);
     }
-    if (epi) { P.ep = A.epp->epi; P.eL = epiL; }
+    if (epi) { P.ep = epp->epi; P.eL = epiL; }
+    P.mono = mono; P.mono_ran = mono && t->frames > 0;
+    if (mono) {
+        P.fkf = epp->epi.fkf;
+        P.time.assign(A.min->time_h, A.min->time_h + n_active);
+        P.frame_id.assign(A.min->frame_id_h, A.min->frame_id_h + n_active);
+        P.localba.assign((size_t)n_active, 0);
+        if (A.min->localba_is_on_h) for (int b = 0; b < n_active; b++) P.localba[(size_t)b] = A.min->localba_is_on_h[b] ? 1 : 0;
+    }
     // the step proper: the form's blocks staged (and allocated or grown by the first step that needs them), then the enqueue
     auto track = [&]() -> int {
         int r = OV2_OK;
@@ -795,17 +969,28 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
             P.has_prior = t->pt.h + t->pl.o_flg;                         // the flags the device sets: same slots as the caller's array
         }
         if (pose) { r = stage_pose(t, n_active, pp, pin, n_h, poseL);  if (r) return r; }
-        if (epi) {
-            r = ensure_epi(t, &epiL);  if (r) return r;
-            stage_epi(t, n_active, A.ein, n_h);
+        if (epi || mono) {
+            r = ensure_epi(t, epi ? &epiL : nullptr);  if (r) return r;
+            stage_epi(t, n_active, ein, n_h);
         }
+        if (mono) { r = ensure_mono(t);  if (r) return r;  stage_mono(t, P); }
         stage_points(t, n_active, A.kps_xy_h, map ? nullptr : A.prior_xy_h, A.has_prior_h, n_h, A.klt_use_prior);
         r = preprocess();
         return r ? r : enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], P);
     };
     // the first frame (trackMono returns right after preprocessImage) and a step with nothing to track anywhere only pre-process
     const bool tracked = t->frames > 0 && n_total > 0;
-    rc = tracked ? track() : preprocess();
+    // mono, not the first frame, no keypoint anywhere: the motion model and the decision run (the reference runs them too)
+    auto mono_empty = [&]() -> int {
+        int r = stage_map(t, n_active, A.wpt_h, A.is3d_h, nullptr, P.n.data());  if (r) return r;
+        r = stage_pose(t, n_active, pp, pin, P.n.data(), poseL);  if (r) return r;
+        r = ensure_epi(t, nullptr);  if (r) return r;
+        r = ensure_mono(t);  if (r) return r;
+        stage_mono(t, P);
+        r = preprocess();
+        return r ? r : enqueue_mono_empty(t, P);
+    };
+    rc = tracked ? track() : (P.mono_ran ? mono_empty() : preprocess());
     if (rc != OV2_OK) { t->cur = old_cur; return rc; }
     commit();
     P.tracked = tracked; P.on = true;
@@ -1058,8 +1243,10 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
 // both forms of the step's second half.  results != NULL: the step was begun with ov2_btracker_track_frame_pose_begin and its
 // poses are wanted; NULL: the tracking half only (a pose the step computed is dropped)
 // eres != NULL (with results): the step was begun with ov2_btracker_track_frame_epi_pose_begin and the filter's records are wanted too
-static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results,
-                           ov2_epifilter_result *eres)
+// mres != NULL (with results; eres unless the step ran without the filter): the step was begun with ov2_btracker_track_mono_begin;
+// redo / excl: the items the rule re-ran and the slots the filter's second run removed, for mono_finish
+static int track_frame_end_step(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results,
+                                ov2_epifilter_result *eres, const ov2_track_mono_result *mres, std::vector<int> &redo, std::vector<uint8_t> &excl)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     ov2_btracker::Pending &P = t->pend;
@@ -1070,12 +1257,21 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
             OV2_REQUIRE(P.n[(size_t)b] == 0 || results[b].removed, OV2_EINVAL, "NULL result buffer (removed)");
     OV2_REQUIRE(!eres || P.form == STEP_EPI, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose_end: the step was not begun with ov2_btracker_track_frame_epi_pose_begin");
     OV2_REQUIRE(!results || P.form != STEP_EPI || eres, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was begun with ov2_btracker_track_frame_epi_pose_begin");
+    OV2_REQUIRE(!mres || P.mono, OV2_EINVAL, "ov2_btracker_track_mono_end: the step was not begun with ov2_btracker_track_mono_begin");
+    OV2_REQUIRE(!(P.mono && results && !mres), OV2_EINVAL, "the step was begun with ov2_btracker_track_mono_begin: finish it with ov2_btracker_track_mono_end");
     if (eres)
         for (int b = 0; b < P.n_active; b++) {
             OV2_REQUIRE(P.n[(size_t)b] == 0 || eres[b].removed, OV2_EINVAL, "NULL result buffer (removed) of the filter");
             OV2_REQUIRE(!eres[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
         }
     P.on = false;
+    if (P.mono) {                                                        // the predicted poses: what the pose chain started from
+        OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+        if (P.mono_ran) {
+            OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+            memcpy(P.Twc.data(), t->mono.h + t->nl.n_pT, 56 * (size_t)P.n_active);
+        } else memcpy(P.Twc.data(), t->res_T.data(), 56 * (size_t)P.n_active);
+    }
     if (results) { t->lp.open((size_t)t->batch, P.tracked); t->lp_L = P.L; }
     if (eres) { t->le.open((size_t)t->batch, P.tracked); t->le_L = P.eL; }
     if (!P.tracked)                                                      // first frame / nothing tracked: no chain ran
@@ -1112,7 +1308,6 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
         t->last_pn[(size_t)b] = (int)n;
     }
     if (!results) return OV2_OK;
-    std::vector<int> redo;
     const uint8_t *hpose = t->pose.h, *hepi = t->epi.h;
     const BtEpiLayout &el = t->el;
     for (int b = 0; b < P.n_active; b++) {
@@ -1140,9 +1335,112 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
         if (n) memcpy(results[b].removed, hpose + t->ql.q_rm + o, n);
     }
     if (redo.empty()) return OV2_OK;
-    std::vector<uint8_t> excl;
     if (eres) { const int rc = epi_redo(t, redo, out_xy_h, status_h, eres, excl);  if (rc != OV2_OK) return rc; }
     return pose_redo(t, redo, status_h, results, eres ? excl.data() : nullptr);
+}
+
+// The mono half of _end, behind track_frame_end_step.  mres == NULL: the step is dropped (the plain end call) and the resident pose
+// and state go back to what they were.  Else the records of the step; for the items the rule re-ran (redo), updateMotionModel and
+// checkNewKfReq again on the second run's pose and frame -- ov2_motion_update_batch from the state BEFORE the step's update,
+// ov2_kf_decision_batch on the frame built here by k_mono_pack's rule -- and the corrected pose and state back into the resident block.
+static int mono_finish(ov2_btracker *t, const float *out_xy_h, const uint8_t *status_h, const ov2_pose_result *results,
+                       ov2_track_mono_result *mres, const std::vector<int> &redo, const std::vector<uint8_t> &excl)
+{
+    ov2_btracker::Pending &P = t->pend;
+    const BtMonoLayout &nl = t->nl;
+    const size_t nm = (size_t)t->cfg.n_max;
+    if (!mres) return P.mono_ran ? mono_push(t, 0, P.n_active) : OV2_OK;
+    const uint8_t *io = t->mono.h;
+    for (int b = 0; b < P.n_active; b++) {
+        ov2_track_mono_result &r = mres[b];
+        memset(&r, 0, sizeof r);
+        if (!P.mono_ran) {                                               // the tracker's first frame: trackMono :77
+            memcpy(r.Twc_pred, t->res_T.data() + 7 * (size_t)b, 56);
+            r.state = t->res_st[(size_t)b];
+            r.kf.decision = 1; r.kf.reason = OV2_KF_FIRST_FRAME;
+            continue;
+        }
+        memcpy(r.Twc_pred, io + nl.n_pT + 56 * (size_t)b, 56);
+        r.resynced = io[nl.n_rs + (size_t)b];
+        memcpy(&r.state, io + nl.n_su + sizeof(ov2_motion_state) * (size_t)b, sizeof(ov2_motion_state));
+        const int *o = (const int *)(io + nl.n_dec) + FKF_OUT_INTS * (size_t)b;
+        memcpy(&r.kf.parallax, &o[0], 4);
+        r.kf.n = o[1]; r.kf.n_distinct = o[2]; r.kf.n_nonfinite = o[3]; r.kf.noccupcells = o[4]; r.kf.nb3dkps = o[5];
+        r.kf.n_out_of_grid = o[6]; r.kf.decision = o[7]; r.kf.reason = o[8];
+    }
+    if (!P.mono_ran) return OV2_OK;
+    const size_t R = redo.size();
+    if (R) {
+        const EpifLayout &L0 = t->eL0;
+        const uint8_t *kh = t->kf_host.data();
+        const int *lmid_h = (const int *)(t->epi.h + t->el.e_lm);
+        std::vector<std::vector<int>> lmid(R);
+        std::vector<std::vector<float>> px(R), unpx(R);
+        std::vector<std::vector<double>> bv(R);
+        std::vector<std::vector<uint8_t>> d3(R);
+        std::vector<ov2_fkf_item> items(R);
+        std::vector<ov2_motion_state> sa(R), su(R);
+        std::vector<double> Tw(7 * R), tm(R);
+        std::vector<ov2_kf_decision_result> dec(R);
+        for (size_t k = 0; k < R; k++) {
+            const int b = redo[k];
+            const size_t o = (size_t)b * nm;
+            const ov2_pose_result &pr = results[b];
+            const bool reset = pr.action == OV2_POSE_P3P_RESET || pr.action == OV2_POSE_PNP_RESET;          // resetFrame()
+            const int n = reset ? 0 : P.n[(size_t)b];
+            const float *un = (const float *)(t->pt.h + t->pl.o_unpx) + 2 * o;
+            const double *bvs = (const double *)(t->pt.h + t->pl.o_bv) + 3 * o;
+            const uint8_t *f3 = t->map.h + t->ml.m_3d + o;
+            for (int i = 0; i < n; i++)
+                if ((status_h[o + i] & 3) == 1 && !(!excl.empty() && excl[o + i]) && !pr.removed[i]) {
+                    lmid[k].push_back(lmid_h[o + i]);
+                    px[k].push_back(out_xy_h[2 * (o + i)]); px[k].push_back(out_xy_h[2 * (o + i) + 1]);
+                    unpx[k].push_back(un[2 * i]); unpx[k].push_back(un[2 * i + 1]);
+                    for (int c = 0; c < 3; c++) bv[k].push_back(bvs[3 * i + c]);
+                    d3[k].push_back(f3[i] ? 1 : 0);
+                }
+            const int nc = (int)lmid[k].size();
+            const size_t room = (size_t)(nc > 0 ? nc : 1);
+            lmid[k].resize(room); px[k].resize(2 * room); unpx[k].resize(2 * room); bv[k].resize(3 * room); d3[k].resize(room);
+            memcpy(&sa[k], io + nl.n_sa + sizeof(ov2_motion_state) * (size_t)b, sizeof(ov2_motion_state));
+            memcpy(&Tw[7 * k], pr.Twc, 56);
+            tm[k] = P.time[(size_t)b];
+            const FeKfHdr &h = t->kf_hdr[(size_t)b];
+            const MonoKfInfo &ki = t->res_ki[(size_t)b];
+            ov2_fkf_item &q = items[k];
+            memset(&q, 0, sizeof q);
+            q.n_cur = nc; q.cur_lmid = lmid[k].data(); q.cur_px = px[k].data(); q.cur_unpx = unpx[k].data(); q.cur_bv = bv[k].data();
+            q.cur_is3d = d3[k].data(); q.cur_Twc = &Tw[7 * k];
+            q.n_kf = h.n_kf; q.kf_lmid = (const int *)kh + o; q.kf_unpx = (const float *)(kh + (L0.o_ku - L0.o_kl)) + 2 * o; q.kf_Tcw = h.kf_Tcw;
+            q.cur_id = P.frame_id[(size_t)b]; q.kf_id = ki.kf_id; q.cur_time = tm[k]; q.kf_time = t->res_kt[(size_t)b];
+            q.kf_nb3dkps = ki.kf_nb3dkps; q.localba_is_on = P.localba[(size_t)b]; q.noccupcells = -1; q.nb3dkps = -1;
+        }
+        int rc = ov2_motion_update_batch(t->ctx, (int)R, sa.data(), Tw.data(), tm.data(), su.data());
+        if (rc != OV2_OK) return rc;
+        rc = ov2_kf_decision_batch(t->ctx, &P.fkf, (int)R, items.data(), dec.data());
+        if (rc != OV2_OK) return rc;
+        for (size_t k = 0; k < R; k++) { mres[redo[k]].state = su[k]; mres[redo[k]].kf = dec[k]; }
+    }
+    for (int b = 0; b < P.n_active; b++) {
+        if (t->kf_hdr[(size_t)b].n_kf == 0 || !t->res_ki[(size_t)b].has_info) {                          // :994
+            memset(&mres[b].kf, 0, sizeof mres[b].kf);
+            mres[b].kf.reason = OV2_KF_NO_KEYFRAME;
+        }
+        memcpy(t->res_T.data() + 7 * (size_t)b, results[b].Twc, 56);
+        t->res_st[(size_t)b] = mres[b].state;
+    }
+    for (size_t k = 0; k < R; k++) { const int rc = mono_push(t, redo[k], redo[k] + 1);  if (rc != OV2_OK) return rc; }
+    return OV2_OK;
+}
+
+static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results,
+                           ov2_epifilter_result *eres, ov2_track_mono_result *mres = nullptr)
+{
+    std::vector<int> redo;
+    std::vector<uint8_t> excl;
+    const int rc = track_frame_end_step(t, out_xy_h, status_h, p3p_req, results, eres, mres, redo, excl);
+    if (rc != OV2_OK || !t->pend.mono || t->pend.on) return rc;
+    return mono_finish(t, out_xy_h, status_h, results, mres, redo, excl);
 }
 
 extern "C" {
@@ -1265,6 +1563,98 @@ int ov2_btracker_track_frame_epi_pose(ov2_btracker *t, int n_active, const uint8
     if (rc == OV2_OK) rc = ov2_btracker_track_frame_epi_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
     if (rc != OV2_OK) return rc;
     return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results);
+}
+
+// what the five calls around the resident pose, state and keyframe info share: the item, no open step, the buffers
+static int mono_item(ov2_btracker *t, int item, const char *open_msg)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, open_msg);
+    return ensure_mono(t);
+}
+
+int ov2_btracker_set_pose(ov2_btracker *t, int item, const double Twc[7])
+{
+    int rc = mono_item(t, item, "ov2_btracker_set_pose between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    OV2_REQUIRE(Twc, OV2_EINVAL, "NULL pose");
+    for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(Twc[c]), OV2_EINVAL, "pose not finite");
+    memcpy(t->res_T.data() + 7 * (size_t)item, Twc, 56);
+    return mono_push(t, item, item + 1);
+}
+
+int ov2_btracker_get_pose(ov2_btracker *t, int item, double Twc[7])
+{
+    int rc = mono_item(t, item, "ov2_btracker_get_pose between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    OV2_REQUIRE(Twc, OV2_EINVAL, "NULL pose");
+    memcpy(Twc, t->res_T.data() + 7 * (size_t)item, 56);
+    return OV2_OK;
+}
+
+int ov2_btracker_reset_motion(ov2_btracker *t, int item)
+{
+    int rc = mono_item(t, item, "ov2_btracker_reset_motion between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    ov2_motion_state &s = t->res_st[(size_t)item];                      // MotionModel::reset(): prevTwc_ stays
+    s.prev_time = -1.;
+    for (int c = 0; c < 6; c++) s.log_relT[c] = 0.;
+    return mono_push(t, item, item + 1);
+}
+
+int ov2_btracker_get_motion(ov2_btracker *t, int item, ov2_motion_state *state)
+{
+    int rc = mono_item(t, item, "ov2_btracker_get_motion between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    OV2_REQUIRE(state, OV2_EINVAL, "NULL state");
+    *state = t->res_st[(size_t)item];
+    return OV2_OK;
+}
+
+int ov2_btracker_set_keyframe_info(ov2_btracker *t, int item, int kf_id, double kf_time, int kf_nb3dkps)
+{
+    int rc = mono_item(t, item, "ov2_btracker_set_keyframe_info between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    OV2_REQUIRE(std::isfinite(kf_time), OV2_EINVAL, "kf_time not finite");
+    t->res_ki[(size_t)item] = MonoKfInfo{kf_id, kf_nb3dkps, 1, 0};
+    t->res_kt[(size_t)item] = kf_time;
+    return mono_push(t, item, item + 1);
+}
+
+int ov2_btracker_track_mono_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                                  const double *wpt_h, const uint8_t *is3d_h, const int *n_h, int klt_use_prior,
+                                  const ov2_track_mono_params *params, const ov2_track_mono_input *input)
+{
+    StepArgs A;
+    A.form = STEP_MONO; A.n_active = n_active; A.img_h = img_h; A.stride = stride; A.kps_xy_h = kps_xy_h; A.n_h = n_h; A.klt_use_prior = klt_use_prior;
+    A.wpt_h = wpt_h; A.is3d_h = is3d_h; A.mp = params; A.min = input;
+    return track_frame_begin(t, A);
+}
+
+int ov2_btracker_track_mono_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_epifilter_result *epi_results,
+                                ov2_pose_result *pose_results, ov2_track_mono_result *mono_results)
+{
+    OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!t->pend.on || !t->pend.mono || (t->pend.form == STEP_EPI) == (epi_results != nullptr), OV2_EINVAL,
+                "ov2_btracker_track_mono_end: epi_results goes with doepipolar == 1, and only with it");
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results);
+}
+
+int ov2_btracker_track_mono(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, const float *kps_xy_h,
+                            const double *wpt_h, const uint8_t *is3d_h, const int *n_h, int klt_use_prior,
+                            const ov2_track_mono_params *params, const ov2_track_mono_input *input, float *out_xy_h, uint8_t *status_h,
+                            int *p3p_req, ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
+                            ov2_track_mono_result *mono_results)
+{
+    OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
+    OV2_REQUIRE(!params || (params->doepipolar != 0) == (epi_results != nullptr), OV2_EINVAL,
+                "ov2_btracker_track_mono: epi_results goes with doepipolar == 1, and only with it");
+    int rc = check_outputs(t, n_active, n_h, out_xy_h, status_h, pose_results, epi_results);
+    if (rc == OV2_OK) rc = ov2_btracker_track_mono_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, n_h, klt_use_prior, params, input);
+    if (rc != OV2_OK) return rc;
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results);
 }
 
 int ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, int *slot_idx, int *m, int *samples, int *n_rows_used)

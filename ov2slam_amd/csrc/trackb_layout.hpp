@@ -1,5 +1,6 @@
 // trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
-// point block, the map block, the pose block, the epipolar I/O block and the filter's device-only index block, each computed by one
+// point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block and the three blocks of
+// ov2_btracker_track_mono, each computed by one
 // function of (batch, n_max).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
@@ -66,5 +67,33 @@ static inline BtEpiLayout bt_epi_layout(int batch, int n_max)
     L.e_out = L.e_in; L.e_nc = up256(L.e_out + BT_EPIF_OUT_BYTES * B); L.e_rm = up256(L.e_nc + 4 * B);
     L.e_er = up256(L.e_rm + slots); L.e_pc = up256(L.e_er + 4 * slots); L.epi_bytes = up256(L.e_pc + 4 * slots);
     L.x_slot = up256(BT_KF_HDR_BYTES * B); L.x_rank = L.x_slot + 4 * slots; L.fx_bytes = L.x_rank + 4 * slots;
+    return L;
+}
+
+// The blocks of ov2_btracker_track_mono.  I/O block: [time 8][frame_id 4][localba 4 per item] go up (n_in); [predicted Twc 56]
+// [state after apply 112][state after update 112][decision 48 (FKF_OUT_INTS ints)][n_cur 4][resynced 1 per item] come down.
+// Resident block (device only, mirrored on the host): [Twc 56][ov2_motion_state 112][kf_time 8][kf_id, kf_nb3dkps, has_info, pad 16
+// per item].  Work block (device only): [FkfItemD 176 per item][lmid 4][px 8][unpx 8][bv 24][is3d 1 per slot]: the frame
+// checkNewKfReq sees, item b's at b x n_max.
+#define BT_MOTION_STATE_BYTES 112   // sizeof(ov2_motion_state), sizeof(FkfItemD), 4 * FKF_OUT_INTS: trackb.hip asserts all three
+#define BT_FKF_ITEM_BYTES 176
+#define BT_KF_DEC_BYTES 48
+struct BtMonoLayout {
+    size_t n_tm, n_id, n_ba, n_in, n_pT, n_sa, n_su, n_dec, n_nc, n_rs, mono_bytes;
+    size_t r_T, r_st, r_kt, r_ki, res_bytes;
+    size_t w_it, w_lm, w_px, w_un, w_bv, w_3d, work_bytes;
+};
+static inline BtMonoLayout bt_mono_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    BtMonoLayout L;
+    L.n_tm = 0; L.n_id = up256(8 * B); L.n_ba = up256(L.n_id + 4 * B); L.n_in = up256(L.n_ba + 4 * B);
+    L.n_pT = L.n_in; L.n_sa = up256(L.n_pT + 56 * B); L.n_su = up256(L.n_sa + BT_MOTION_STATE_BYTES * B);
+    L.n_dec = up256(L.n_su + BT_MOTION_STATE_BYTES * B); L.n_nc = up256(L.n_dec + BT_KF_DEC_BYTES * B); L.n_rs = up256(L.n_nc + 4 * B);
+    L.mono_bytes = up256(L.n_rs + B);
+    L.r_T = 0; L.r_st = up256(56 * B); L.r_kt = up256(L.r_st + BT_MOTION_STATE_BYTES * B); L.r_ki = up256(L.r_kt + 8 * B);
+    L.res_bytes = up256(L.r_ki + 16 * B);
+    L.w_it = 0; L.w_lm = up256(BT_FKF_ITEM_BYTES * B); L.w_px = up256(L.w_lm + 4 * slots); L.w_un = up256(L.w_px + 8 * slots);
+    L.w_bv = up256(L.w_un + 8 * slots); L.w_3d = up256(L.w_bv + 24 * slots); L.work_bytes = up256(L.w_3d + slots);
     return L;
 }

@@ -761,6 +761,107 @@ class LockstepTracker:
                                                       C.byref(m), tab.ctypes.data_as(C.POINTER(C.c_int)), C.byref(rows)))
         return nc.value, slot[:nc.value].copy(), m.value, tab[:rows.value].copy()
 
+    # ---- trackMono after initialisation in one step (ov2_btracker_track_mono) --------------------------------------------------
+    def setPose(self, item, Twc):
+        """the frame pose of item `item` (pcurframe_->Twc_), resident on the device: the estimator or the loop closer moved the frame.
+        Between steps only."""
+        T = np.ascontiguousarray(Twc, np.float64).reshape(7)
+        L.check(self.lib.ov2_btracker_set_pose(self.h_trk, int(item), _ptr(T)))
+
+    def getPose(self, item):
+        T = np.zeros(7)
+        L.check(self.lib.ov2_btracker_get_pose(self.h_trk, int(item), _ptr(T)))
+        return T
+
+    def resetMotion(self, item):
+        """MotionModel::reset() of item `item`"""
+        L.check(self.lib.ov2_btracker_reset_motion(self.h_trk, int(item)))
+
+    def getMotion(self, item):
+        """the motion state of item `item` as motion.apply takes it"""
+        from . import motion as _motion
+        s = L.MotionState()
+        L.check(self.lib.ov2_btracker_get_motion(self.h_trk, int(item), C.byref(s)))
+        return _motion._state_dict(s)
+
+    def setKeyframeInfo(self, item, kf_id, kf_time, kf_nb3dkps):
+        """id_, img_time_ and nb3dkps_ of the keyframe setKeyframe gave item `item`"""
+        L.check(self.lib.ov2_btracker_set_keyframe_info(self.h_trk, int(item), int(kf_id), float(kf_time), int(kf_nb3dkps)))
+
+    def _mono_args(self, na, nn, params, epi_params, p3p_req, seed, lmid, nbkfs, epi_seed, time, frame_id, localba_is_on, doepipolar,
+                   scale, dop3p, n_rows):
+        ep, ei, keep = self._epi_args(na, nn, params, epi_params, np.zeros((max(1, na), 7)), p3p_req, seed, lmid,
+                                      np.zeros(self.batch, np.int32) if nbkfs is None else nbkfs,
+                                      np.zeros(self.batch, np.uint64) if epi_seed is None else epi_seed, scale, dop3p, n_rows)
+        ei.pose.Twc_h = None                                                      # the pose is resident
+        mp, mi = L.TrackMonoParams(), L.TrackMonoInput()
+        mp.step, mp.doepipolar = ep, int(bool(doepipolar))
+        tm = np.ascontiguousarray(time, np.float64).reshape(-1)
+        fid = np.ascontiguousarray(frame_id, np.int32).reshape(-1)
+        ba = None if localba_is_on is None else np.ascontiguousarray(localba_is_on, np.uint8).reshape(-1)
+        if len(tm) < na or len(fid) < na or (ba is not None and len(ba) < na):
+            raise ValueError("one time, one frame id and one local-BA flag per active item")
+        mi.step = ei
+        mi.time_h = tm.ctypes.data_as(C.POINTER(C.c_double))
+        mi.frame_id_h = fid.ctypes.data_as(C.POINTER(C.c_int))
+        mi.localba_is_on_h = None if ba is None else ba.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._mono_epi = bool(doepipolar)
+        return mp, mi, keep + (tm, fid, ba)
+
+    def _mono_dicts(self, M, na):
+        from . import keyframe as _kf
+        from . import motion as _motion
+        return [dict(Twc_pred=np.array(M[b].Twc_pred[:], np.float64), resynced=int(M[b].resynced), state=_motion._state_dict(M[b].state),
+                     kf=_kf._decision_dict(M[b].kf)) for b in range(na)]
+
+    def _map_args_mono(self, imgs, kps, wpt, is3d, n):
+        return self._map_args(imgs, kps, wpt, is3d, np.zeros((max(1, len(imgs)), 7)), n)
+
+    def trackMono(self, imgs, kps, wpt, is3d, n, params, epi_params, p3p_req, seed, lmid, nbkfs, epi_seed, time, frame_id,
+                  localba_is_on=None, doepipolar=True, scale=None, dop3p=False, n_rows=0, klt_use_prior=True):
+        """VisualFrontEnd::trackMono after initialisation in one enqueue and one synchronisation (ov2_btracker_track_mono): the motion
+        model on the resident pose (setPose / getPose) and state (resetMotion / getMotion), trackFrameEpiPose (doepipolar False:
+        trackFramePose) from the predicted pose, updateMotionModel and checkNewKfReq against the resident keyframe (setKeyframe,
+        setKeyframeInfo).  As trackFrameEpiPose without Tcw and Twc, plus time, frame_id and localba_is_on one per item.
+        -> (out, status bits, p3p_req, epis (None with doepipolar False), poses, monos): monos[b] = dict(Twc_pred (7,), resynced,
+        state (the motion state after the update), kf (as keyframe.kf_decision returns it))."""
+        na, imgs, stride, ptrs, kps, wpt, is3d, _, nn = self._map_args_mono(imgs, kps, wpt, is3d, n)
+        mp, mi, keep = self._mono_args(na, nn, params, epi_params, p3p_req, seed, lmid, nbkfs, epi_seed, time, frame_id, localba_is_on,
+                                       doepipolar, scale, dop3p, n_rows)
+        out, st, p3p = self._outputs(na)
+        R, removed = self._pose_results(na, nn)
+        E, bufs = self._epi_results(na)
+        M = (L.TrackMonoResult * max(1, na))()
+        L.check(self.lib.ov2_btracker_track_mono(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(nn),
+                                                 int(bool(klt_use_prior)), C.byref(mp), C.byref(mi), _ptr(out), _ptr(st), _ptr(p3p),
+                                                 E if doepipolar else None, R, M))
+        return (out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn) if doepipolar else None, self._pose_dicts(R, removed, nn),
+                self._mono_dicts(M, na))
+
+    def trackMonoBegin(self, imgs, kps, wpt, is3d, n, params, epi_params, p3p_req, seed, lmid, nbkfs, epi_seed, time, frame_id,
+                       localba_is_on=None, doepipolar=True, scale=None, dop3p=False, n_rows=0, klt_use_prior=True):
+        """first half of trackMono; trackMonoEnd finishes it (trackFrameEnd gives the tracking half, drops the rest and leaves the
+        resident pose and state as they were)"""
+        na, imgs, stride, ptrs, kps, wpt, is3d, _, nn = self._map_args_mono(imgs, kps, wpt, is3d, n)
+        mp, mi, keep = self._mono_args(na, nn, params, epi_params, p3p_req, seed, lmid, nbkfs, epi_seed, time, frame_id, localba_is_on,
+                                       doepipolar, scale, dop3p, n_rows)
+        L.check(self.lib.ov2_btracker_track_mono_begin(self.h_trk, na, ptrs, stride, _ptr(kps), _ptr(wpt), _ptr(is3d), _ptr(nn),
+                                                       int(bool(klt_use_prior)), C.byref(mp), C.byref(mi)))
+        self._pending = (imgs, kps, wpt, is3d, nn)                                # (kps is re-read by the end half: keep it alive)
+
+    def trackMonoEnd(self):
+        """second half of trackMono -> (out, status bits, p3p_req, epis, poses, monos)"""
+        nn = self._pending[4]
+        na = len(nn)
+        out, st, p3p = self._outputs(na)
+        R, removed = self._pose_results(na, nn)
+        E, bufs = self._epi_results(na)
+        M = (L.TrackMonoResult * max(1, na))()
+        L.check(self.lib.ov2_btracker_track_mono_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p), E if self._mono_epi else None, R, M))
+        self._pending = None
+        return (out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn) if self._mono_epi else None, self._pose_dicts(R, removed, nn),
+                self._mono_dicts(M, na))
+
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
         pri = np.empty((n, 2), np.float32)

@@ -65,5 +65,9 @@ static int (*const check_stereo_priors_batch)(ov2::Context &, const ov2::StereoP
                                               std::vector<std::vector<uint8_t>> &) = &ov2::stereoPriors;
 static auto const check_cell_table = &ov2::detail::buildCellTable;
 static auto const check_pack_klt = &ov2::detail::packKltPriors;
+// the motion model: the reference's three methods
+static int (ov2::MotionModel::*const check_motion_apply)(ov2::Context &, double *, double, double *, bool *) = &ov2::MotionModel::applyMotionModel;
+static int (ov2::MotionModel::*const check_motion_update)(ov2::Context &, const double *, double) = &ov2::MotionModel::updateMotionModel;
+static void (ov2::MotionModel::*const check_motion_reset)() = &ov2::MotionModel::reset;
 
-int main() { return check_klt_priors && check_klt_priors_batch && check_stereo_priors && check_stereo_priors_batch && check_cell_table && check_pack_klt && check_parallax && check_parallax_batch && check_kfreq && check_kfreq_batch && check_epi2d && check_epi2d_batch && check_kf_sort && check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }
+int main() { return check_motion_apply && check_motion_update && check_motion_reset && check_klt_priors && check_klt_priors_batch && check_stereo_priors && check_stereo_priors_batch && check_cell_table && check_pack_klt && check_parallax && check_parallax_batch && check_kfreq && check_kfreq_batch && check_epi2d && check_epi2d_batch && check_kf_sort && check_loopmap && check_loopmap_batch && check_set_loopmap && check_loopmap_order && check_lckf && check_lckf_trk && check_retain_order && check_knn && check_knn_batch && check_ceres_pnp && check_p3p_ransac && check_5pt && check_undist_maps && check_rectify && check_rect_map && check_set_rect ? 0 : 1; }

@@ -555,4 +555,42 @@ inline int computePose(Context &ctx, const ComputePoseParams &params, const std:
     return rc;
 }
 
+// ---- MotionModel (include/visual_front_end.hpp:38-90) on ov2_motion_apply / ov2_motion_update: the reference's three methods, the
+// pose as [t q] in place of a Sophus::SE3d.  The methods return the library's code; a refused call (a non-finite pose, a time that
+// is not after the previous one -- where the reference exits or divides by zero) leaves the pose and the model as they were.
+class MotionModel {
+public:
+    MotionModel() { reset(); }
+    // applyMotionModel(Twc, time): Twc becomes the predicted pose; Tcw (may be NULL) its inverse, resynced (may be NULL) whether
+    // prevTwc_ was moved to the caller's pose
+    int applyMotionModel(Context &ctx, double Twc[7], double time, double *Tcw = nullptr, bool *resynced = nullptr)
+    {
+        ov2_motion_state so;
+        double To[7], Ti[7];
+        uint8_t rs = 0;
+        const int rc = ov2_motion_apply(ctx.get(), &s_, Twc, time, &so, To, Ti, &rs);
+        if (rc != OV2_OK) return rc;
+        s_ = so;
+        for (int k = 0; k < 7; k++) { Twc[k] = To[k]; if (Tcw) Tcw[k] = Ti[k]; }
+        if (resynced) *resynced = rs != 0;
+        return OV2_OK;
+    }
+    int updateMotionModel(Context &ctx, const double Twc[7], double time)
+    {
+        ov2_motion_state so;
+        const int rc = ov2_motion_update(ctx.get(), &s_, Twc, time, &so);
+        if (rc == OV2_OK) s_ = so;
+        return rc;
+    }
+    void reset()
+    {
+        s_.prev_time = -1.;
+        for (int k = 0; k < 6; k++) s_.log_relT[k] = 0.;
+    }
+    const ov2_motion_state &state() const { return s_; }      // prev_time_, prevTwc_, log_relT_
+
+private:
+    ov2_motion_state s_{-1., {0, 0, 0, 0, 0, 0, 1}, {0, 0, 0, 0, 0, 0}};
+};
+
 }  // namespace ov2
