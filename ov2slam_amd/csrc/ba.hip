@@ -1817,8 +1817,8 @@ static int ba_det_setup(ov2_ctx *ctx, BADev &D, BADev &DG, const BAGeom &G)
     OV2_REQUIRE(D.ldim == 1 && !D.big, OV2_EUNSUPPORTED, "OV2_OPT_BA_DETERMINISTIC covers the inverse-depth form on the LDS-resident path only");
     hipStream_t s = ctx->stream;
     const size_t nn = (size_t)D.nfp * D.nfp, ncopy = (size_t)G.det_lin + G.det_po;
-    const size_t b_H = al256(8 * ncopy * nn), b_bf = al256(8 * ncopy * D.nfp), b_c = al256(8 * std::max<size_t>(1, ncopy));
-    const size_t b_G = al256(8 * (size_t)G.ksplit * nn), b_v = al256(8 * (size_t)G.ksplit * D.nfp);
+    const size_t b_H = up256(8 * ncopy * nn), b_bf = up256(8 * ncopy * D.nfp), b_c = up256(8 * std::max<size_t>(1, ncopy));
+    const size_t b_G = up256(8 * (size_t)G.ksplit * nn), b_v = up256(8 * (size_t)G.ksplit * D.nfp);
     const size_t need = b_H + b_bf + b_c + b_G + b_v;
     if (need > ctx->ba_det_bytes) {
         if (ctx->ba_det_pool) { OV2_HIP_CHECK(hipStreamSynchronize(s)); (void)hipFree(ctx->ba_det_pool); ctx->ba_det_pool = nullptr; ctx->ba_det_bytes = 0; }
@@ -2165,16 +2165,16 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
     std::vector<size_t> out_off;
     if (N > 0) {
         // header of the pinned block: look-ahead words, counters, control blocks, device views; then the staging mirrors
-        const size_t hb_flag = 0, hb_cnt = al256(4 * (size_t)N), hb_ctl = hb_cnt + al256(64 * (size_t)N), hb_arr = hb_ctl + al256(sizeof(BACtl) * (size_t)N);
-        out_base = hb_arr + al256(sizeof(BADev) * (size_t)N);
+        const size_t hb_flag = 0, hb_cnt = up256(4 * (size_t)N), hb_ctl = hb_cnt + up256(64 * (size_t)N), hb_arr = hb_ctl + up256(sizeof(BACtl) * (size_t)N);
+        out_base = hb_arr + up256(sizeof(BADev) * (size_t)N);
         out_off.assign(idx.size(), 0);
         for (size_t k = 0; k < idx.size(); k++) {
             const ov2_ba_problem &q = p[idx[k]];
             const size_t nk = (size_t)std::max(0, q.n_kf), nl = (size_t)std::max(1, q.n_lm), nr = (size_t)std::max(0, q.n_res);
             out_off[k] = out_total;
-            out_total += al256(56 * nk) + al256(8 * nl) + al256(nr) + (r[idx[k]].chi2_last_eval ? al256(8 * nr) : 0) + (r[idx[k]].depthpos_last_eval ? al256(nr) : 0);
+            out_total += up256(56 * nk) + up256(8 * nl) + up256(nr) + (r[idx[k]].chi2_last_eval ? up256(8 * nr) : 0) + (r[idx[k]].depthpos_last_eval ? up256(nr) : 0);
         }
-        const size_t header = out_base + al256(out_total);          // (look-ahead words | counters | control blocks | views | results), then the problems' slices
+        const size_t header = out_base + up256(out_total);          // (look-ahead words | counters | control blocks | views | results), then the problems' slices
         size_t host_need = header, dev_need = header;
         for (;;) {
             int rc = ctx->reserve_host(std::max(host_need, ctx->h_scratch_bytes));
@@ -2297,12 +2297,12 @@ static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov
                 const uint8_t *o = hb + out_base + out_off[(size_t)k];
                 const size_t nr = (size_t)D.n_res;
                 if (ri.poses_out) memcpy(ri.poses_out, o, 56 * (size_t)D.n_kf);
-                o += al256(56 * (size_t)D.n_kf);
+                o += up256(56 * (size_t)D.n_kf);
                 if (ri.invdepth_out) memcpy(ri.invdepth_out, o, 8 * (size_t)D.n_lm);
-                o += al256(8 * (size_t)std::max(1, D.n_lm));
+                o += up256(8 * (size_t)std::max(1, D.n_lm));
                 if (ri.bad_obs && nr > 0) memcpy(ri.bad_obs, o, nr);
-                o += al256(nr);
-                if (ri.chi2_last_eval) { if (nr > 0) memcpy(ri.chi2_last_eval, o, 8 * nr); o += al256(8 * nr); }
+                o += up256(nr);
+                if (ri.chi2_last_eval) { if (nr > 0) memcpy(ri.chi2_last_eval, o, 8 * nr); o += up256(8 * nr); }
                 if (ri.depthpos_last_eval && nr > 0) memcpy(ri.depthpos_last_eval, o, nr);
             }
         }

@@ -20,7 +20,6 @@ struct ov2_ba_dev {
     int device = 0;
 };
 
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static void ba_destroy(ov2_ba_dev *dev);
 
 // debug laps of a host entry point (ov2_ctx::debug): "[ov2 <who>] <what>  <ms> ms since entry" on stderr
@@ -183,25 +182,23 @@ static int ba_create(ov2_ctx *ctx, const ov2_ba_problem *p, ov2_ba_dev **out, bo
     // needs from the host goes up in ONE copy instead of eleven (each ~15 us of launch overhead: a third of ba_create on a
     // 69 k-block window)
     const size_t nl = (size_t)std::max(1, p->n_lm), na = (size_t)std::max(1, n_act), nr = (size_t)std::max(1, p->n_res);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
-    const size_t o_pose_col = take(4 * (size_t)p->n_kf), o_lm_ptr = take(4 * (nl + 1)), o_lm_anchor = take(4 * nl), o_lm_auv = take(16 * nl);
-    const size_t o_res_type = take(na), o_res_kf = take(4 * na), o_res_orig = take(4 * na), o_res_uv = take(16 * na), o_res_sigma = take(8 * na);
-    const size_t o_lm_order = take(4 * nl), o_lm_live = take(nl);
-    const size_t o_pose0 = take(56 * (size_t)p->n_kf), o_lam0 = take(8 * nl);      // initial parameters (the batch's reset kernel copies them on the device)
-    const size_t up_bytes = off;                                       // [0, up_bytes) of the pool = the staging buffer
+    StageCursor c(256);
+    const size_t o_pose_col = c.take(4 * (size_t)p->n_kf), o_lm_ptr = c.take(4 * (nl + 1)), o_lm_anchor = c.take(4 * nl), o_lm_auv = c.take(16 * nl);
+    const size_t o_res_type = c.take(na), o_res_kf = c.take(4 * na), o_res_orig = c.take(4 * na), o_res_uv = c.take(16 * na), o_res_sigma = c.take(8 * na);
+    const size_t o_lm_order = c.take(4 * nl), o_lm_live = c.take(nl);
+    const size_t o_pose0 = c.take(56 * (size_t)p->n_kf), o_lam0 = c.take(8 * nl);      // initial parameters (the batch's reset kernel copies them on the device)
+    const size_t up_bytes = c.off;                                       // [0, up_bytes) of the pool = the staging buffer
     uint8_t *hs = nullptr;
     {
         const size_t np_h = (size_t)std::max(1, n_po);
-        size_t hoff = up_bytes;
-        auto htake = [&](size_t bytes) { const size_t o = hoff; hoff += (bytes + 255) & ~(size_t)255; return o; };
-        const size_t h6 = htake(4 * np_h), h7 = htake(4 * np_h), h8 = htake(24 * np_h), h9 = htake(16 * np_h), h10 = htake(8 * np_h);
+        StageCursor hc = c;                                            // the host block goes on behind the staging buffer with sections of its own
+        const size_t h6 = hc.take(4 * np_h), h7 = hc.take(4 * np_h), h8 = hc.take(24 * np_h), h9 = hc.take(16 * np_h), h10 = hc.take(8 * np_h);
         if (ext) {
             std::lock_guard<std::mutex> l(ext->m);
-            if (ext->host_used + hoff > ext->host_cap) { ext->host_used += al256(hoff); return BA_SLICE_FULL; }    // (keeps counting: the caller learns the total)
-            hs = ext->host_base + ext->host_used; ext->host_used += al256(hoff);
+            if (ext->host_used + hc.off > ext->host_cap) { ext->host_used += hc.off; return BA_SLICE_FULL; }    // (keeps counting: the caller learns the total)
+            hs = ext->host_base + ext->host_used; ext->host_used += hc.off;
         } else {
-        const int rch = ctx->reserve_host(hoff);
+        const int rch = ctx->reserve_host(hc.off);
         if (rch != OV2_OK) return rch;
         hs = (uint8_t *)ctx->h_scratch;
         }
@@ -277,30 +274,30 @@ static int ba_create(ov2_ctx *ctx, const ov2_ba_problem *p, ov2_ba_dev **out, bo
     }
     D.n_cw = (int)cw_col.size();
     const size_t ncw = (size_t)std::max(1, D.n_cw);
-    const size_t o_x_pose = take(56 * (size_t)p->n_kf), o_c_pose = take(56 * (size_t)p->n_kf), o_x_RT = take(96 * (size_t)p->n_kf), o_c_RT = take(96 * (size_t)p->n_kf);
-    const size_t o_x_lam = take(8 * nl), o_c_lam = take(8 * nl), o_scale_f = take(8 * (size_t)nfp), o_diag_f = take(8 * (size_t)nfp);
-    const size_t o_scale_l = take(8 * nl), o_diag_l = take(8 * nl), o_ete = take(8 * nl), o_etb = take(8 * nl), o_cl = take(8 * nl), o_ce = take(8 * nl);
-    const size_t o_W = take(D.big ? 256 : 8 * nl * nfp), o_H = take(8 * (size_t)nfp * nfp), o_G = take(8 * (size_t)nfp * nfp), o_S = take(8 * (size_t)nfp * nfp);
-    const size_t o_cww = take(48 * ncw), o_cw_ptr = take(4 * (nl + 1)), o_cw_col = take(4 * ncw), o_cw_lm = take(4 * ncw);
-    const size_t o_res_cw = take(4 * na), o_lm_cwa = take(4 * nl), o_kfl_ptr = take(4 * ((size_t)n_opt + 1)), o_kfl_idx = take(4 * ncw);
-    const size_t o_bf = take(8 * (size_t)nfp), o_v = take(8 * (size_t)nfp), o_yf = take(8 * (size_t)nfp), o_yl = take(8 * nl);
-    const size_t o_Linv = take(8 * (size_t)nfp * 32);
-    const size_t o_chi2 = take(8 * nr), o_dpos = take(nr), o_ctl = take(sizeof(BACtl));
-    const size_t o_res_off = take(na), o_bad_obs = take(nr), o_lba_cnt = take(64), o_part = take(8 * 7 * BA_PART_MAX);
+    const size_t o_x_pose = c.take(56 * (size_t)p->n_kf), o_c_pose = c.take(56 * (size_t)p->n_kf), o_x_RT = c.take(96 * (size_t)p->n_kf), o_c_RT = c.take(96 * (size_t)p->n_kf);
+    const size_t o_x_lam = c.take(8 * nl), o_c_lam = c.take(8 * nl), o_scale_f = c.take(8 * (size_t)nfp), o_diag_f = c.take(8 * (size_t)nfp);
+    const size_t o_scale_l = c.take(8 * nl), o_diag_l = c.take(8 * nl), o_ete = c.take(8 * nl), o_etb = c.take(8 * nl), o_cl = c.take(8 * nl), o_ce = c.take(8 * nl);
+    const size_t o_W = c.take(D.big ? 256 : 8 * nl * nfp), o_H = c.take(8 * (size_t)nfp * nfp), o_G = c.take(8 * (size_t)nfp * nfp), o_S = c.take(8 * (size_t)nfp * nfp);
+    const size_t o_cww = c.take(48 * ncw), o_cw_ptr = c.take(4 * (nl + 1)), o_cw_col = c.take(4 * ncw), o_cw_lm = c.take(4 * ncw);
+    const size_t o_res_cw = c.take(4 * na), o_lm_cwa = c.take(4 * nl), o_kfl_ptr = c.take(4 * ((size_t)n_opt + 1)), o_kfl_idx = c.take(4 * ncw);
+    const size_t o_bf = c.take(8 * (size_t)nfp), o_v = c.take(8 * (size_t)nfp), o_yf = c.take(8 * (size_t)nfp), o_yl = c.take(8 * nl);
+    const size_t o_Linv = c.take(8 * (size_t)nfp * 32);
+    const size_t o_chi2 = c.take(8 * nr), o_dpos = c.take(nr), o_ctl = c.take(sizeof(BACtl));
+    const size_t o_res_off = c.take(na), o_bad_obs = c.take(nr), o_lba_cnt = c.take(64), o_part = c.take(8 * 7 * BA_PART_MAX);
     const size_t npo = (size_t)std::max(1, n_po);
-    const size_t o_po_kf = take(4 * npo), o_po_orig = take(4 * npo), o_po_xyz = take(24 * npo), o_po_uv = take(16 * npo), o_po_sigma = take(8 * npo);
-    dev->pool_bytes = off;
+    const size_t o_po_kf = c.take(4 * npo), o_po_orig = c.take(4 * npo), o_po_xyz = c.take(24 * npo), o_po_uv = c.take(16 * npo), o_po_sigma = c.take(8 * npo);
+    dev->pool_bytes = c.off;
     if (ext) {
         std::lock_guard<std::mutex> l(ext->m);
-        if (ext->dev_used + off > ext->dev_cap) { ext->dev_used += al256(off); delete dev; return BA_SLICE_FULL; }
-        dev->pool = ext->dev_base + ext->dev_used; dev->pool_owned = false; ext->dev_used += al256(off);
-    } else if (transient && off <= ((size_t)64 << 20)) {               // (the context keeps the largest pool it has seen: grow-only scratch)
-        const int rcs = ctx->reserve_device(off);
+        if (ext->dev_used + c.off > ext->dev_cap) { ext->dev_used += up256(c.off); delete dev; return BA_SLICE_FULL; }
+        dev->pool = ext->dev_base + ext->dev_used; dev->pool_owned = false; ext->dev_used += up256(c.off);
+    } else if (transient && c.off <= ((size_t)64 << 20)) {               // (the context keeps the largest pool it has seen: grow-only scratch)
+        const int rcs = ctx->reserve_device(c.off);
         if (rcs != OV2_OK) { delete dev; return rcs; }
         dev->pool = ctx->d_scratch; dev->pool_owned = false;
     } else {
         hipError_t e = hipMalloc(&dev->pool, dev->pool_bytes);
-        if (e != hipSuccess) { delete dev; ov2_set_error("hipMalloc(%zu): %s", off, hipGetErrorString(e)); return OV2_ENOMEM; }
+        if (e != hipSuccess) { delete dev; ov2_set_error("hipMalloc(%zu): %s", c.off, hipGetErrorString(e)); return OV2_ENOMEM; }
     }
     uint8_t *b = (uint8_t *)dev->pool;
     D.pose_col = (int *)(b + o_pose_col); D.lm_ptr = (int *)(b + o_lm_ptr); D.lm_anchor = (int *)(b + o_lm_anchor); D.lm_auv = (double *)(b + o_lm_auv);
@@ -417,21 +414,20 @@ static int xyzba_create(ov2_ctx *ctx, const ov2_xyzba_problem *p, ov2_ba_dev **o
     D.n_kf = p->n_kf; D.n_lm = p->n_pts; D.n_act = n_act; D.nf = nf; D.nfp = nfp; D.n_po = 0; D.ldim = 3;
     D.chol_hbm = chol_hbm; D.lin_waves = lin_waves;
     const size_t nl = (size_t)std::max(1, p->n_pts), na = (size_t)std::max(1, n_act), nr = (size_t)std::max(1, p->n_res);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
-    const size_t o_pose_col = take(4 * (size_t)p->n_kf), o_lm_ptr = take(4 * (nl + 1));
-    const size_t o_res_type = take(na), o_res_kf = take(4 * na), o_res_orig = take(4 * na), o_res_uv = take(16 * na), o_res_sigma = take(8 * na);
-    const size_t o_x_pose = take(56 * (size_t)p->n_kf), o_c_pose = take(56 * (size_t)p->n_kf), o_x_RT = take(96 * (size_t)p->n_kf), o_c_RT = take(96 * (size_t)p->n_kf);
-    const size_t o_x_lam = take(24 * nl), o_c_lam = take(24 * nl), o_scale_f = take(8 * (size_t)nfp), o_diag_f = take(8 * (size_t)nfp);
-    const size_t o_scale_l = take(24 * nl), o_diag_l = take(24 * nl), o_etb = take(24 * nl), o_yl = take(24 * nl), o_ep = take(24 * nl), o_ones = take(24 * nl);
-    const size_t o_ete6 = take(48 * nl), o_minv6 = take(48 * nl);
-    const size_t o_W = take(24 * nl * nfp), o_Wp = take(24 * nl * nfp);
-    const size_t o_H = take(8 * (size_t)nfp * nfp), o_G = take(8 * (size_t)nfp * nfp), o_S = take(8 * (size_t)nfp * nfp);
-    const size_t o_bf = take(8 * (size_t)nfp), o_v = take(8 * (size_t)nfp), o_yf = take(8 * (size_t)nfp), o_Linv = take(8 * (size_t)nfp * 32);
-    const size_t o_chi2 = take(8 * nr), o_dpos = take(nr), o_ctl = take(sizeof(BACtl));
-    dev->pool_bytes = off;
+    StageCursor c(256);
+    const size_t o_pose_col = c.take(4 * (size_t)p->n_kf), o_lm_ptr = c.take(4 * (nl + 1));
+    const size_t o_res_type = c.take(na), o_res_kf = c.take(4 * na), o_res_orig = c.take(4 * na), o_res_uv = c.take(16 * na), o_res_sigma = c.take(8 * na);
+    const size_t o_x_pose = c.take(56 * (size_t)p->n_kf), o_c_pose = c.take(56 * (size_t)p->n_kf), o_x_RT = c.take(96 * (size_t)p->n_kf), o_c_RT = c.take(96 * (size_t)p->n_kf);
+    const size_t o_x_lam = c.take(24 * nl), o_c_lam = c.take(24 * nl), o_scale_f = c.take(8 * (size_t)nfp), o_diag_f = c.take(8 * (size_t)nfp);
+    const size_t o_scale_l = c.take(24 * nl), o_diag_l = c.take(24 * nl), o_etb = c.take(24 * nl), o_yl = c.take(24 * nl), o_ep = c.take(24 * nl), o_ones = c.take(24 * nl);
+    const size_t o_ete6 = c.take(48 * nl), o_minv6 = c.take(48 * nl);
+    const size_t o_W = c.take(24 * nl * nfp), o_Wp = c.take(24 * nl * nfp);
+    const size_t o_H = c.take(8 * (size_t)nfp * nfp), o_G = c.take(8 * (size_t)nfp * nfp), o_S = c.take(8 * (size_t)nfp * nfp);
+    const size_t o_bf = c.take(8 * (size_t)nfp), o_v = c.take(8 * (size_t)nfp), o_yf = c.take(8 * (size_t)nfp), o_Linv = c.take(8 * (size_t)nfp * 32);
+    const size_t o_chi2 = c.take(8 * nr), o_dpos = c.take(nr), o_ctl = c.take(sizeof(BACtl));
+    dev->pool_bytes = c.off;
     hipError_t e = hipMalloc(&dev->pool, dev->pool_bytes);
-    if (e != hipSuccess) { delete dev; ov2_set_error("hipMalloc(%zu): %s", off, hipGetErrorString(e)); return OV2_ENOMEM; }
+    if (e != hipSuccess) { delete dev; ov2_set_error("hipMalloc(%zu): %s", c.off, hipGetErrorString(e)); return OV2_ENOMEM; }
     uint8_t *b = (uint8_t *)dev->pool;
     D.pose_col = (int *)(b + o_pose_col); D.lm_ptr = (int *)(b + o_lm_ptr);
     D.res_type = b + o_res_type; D.res_kf = (int *)(b + o_res_kf); D.res_orig = (int *)(b + o_res_orig); D.res_uv = (double *)(b + o_res_uv); D.res_sigma = (double *)(b + o_res_sigma);

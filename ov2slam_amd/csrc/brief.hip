@@ -143,7 +143,6 @@ static int brief_check_geometry(int w, int h, size_t pitch, int n_items, int cap
     return OV2_OK;
 }
 
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int ov2_brief_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int w, int h, size_t pitch, size_t item_stride, int n_items,
                     const float *xy_h, const int *n_h, int n_h_all, int cap, uint8_t *desc_h, uint8_t *valid_h)

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/ov2slam_hip.h"
+#include "stage.hpp"
 
 #define OV2_MAX_LEVELS 8
 
@@ -94,6 +95,20 @@ struct ov2_ctx {
     // the reverse, synchronous: h rows of w bytes at device pitch src_pitch -> host rows at dst_stride (one contiguous DMA into the
     // pinned staging buffer, then a host-side repack)
     int download_image(uint8_t *dst_h, size_t dst_stride, const void *src_d, size_t src_pitch, size_t w, size_t h);
+};
+// The round trip of a stand-alone call (host conventions), after its input checks: ONE scratch block whose sections
+// (StageCursor, stage.hpp) lie at the same offsets on the device (d) and in the pinned host block (h).  open() sets the device and
+// reserves both grow-only scratches (a block may be shorter on the host: only what travels needs room there); the caller packs the
+// inputs into h, uploads, launches on ctx->stream, downloads, syncs once and scatters from h.  Every step returns an OV2_* code.
+struct Stage {
+    ov2_ctx *ctx = nullptr;
+    uint8_t *h = nullptr, *d = nullptr;
+    int open(ov2_ctx *ctx, size_t dev_bytes, size_t host_bytes);
+    // device [begin, end) from the same host offsets
+    int upload(size_t begin, size_t end) const { OV2_HIP_CHECK(hipMemcpyAsync(d + begin, h + begin, end - begin, hipMemcpyHostToDevice, ctx->stream)); return OV2_OK; }
+    // device [begin, end) to host offset `at`
+    int download(size_t begin, size_t end, size_t at) const { OV2_HIP_CHECK(hipMemcpyAsync(h + at, d + begin, end - begin, hipMemcpyDeviceToHost, ctx->stream)); return OV2_OK; }
+    int sync() const { OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream)); return OV2_OK; }
 };
 #define LK_STAT_SLOTS 256
 #define LK_STAT_STRIDE 16      // unsigned long long per slot (128 B)

@@ -34,6 +34,16 @@ int ov2_ctx::reserve_host(size_t bytes)
     return OV2_OK;
 }
 
+int Stage::open(ov2_ctx *ctx_, size_t dev_bytes, size_t host_bytes)
+{
+    ctx = ctx_;
+    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = ctx->reserve_device(dev_bytes);
+    if (rc == OV2_OK) rc = ctx->reserve_host(host_bytes);
+    h = (uint8_t *)ctx->h_scratch; d = (uint8_t *)ctx->d_scratch;
+    return rc;
+}
+
 // Row-pitched upload through pinned memory: hipMemcpy2DAsync from a pageable image whose width is not a multiple of the pitches
 // (KITTI: 1241-byte rows into a 1248-byte pitch) took 2.8 ms per frame -- 376 row transfers; staged, it is one host-side repack
 // (rows of w bytes, ~25 us) and ONE contiguous DMA.  The staging buffer is refilled only after the previous upload's event.

@@ -4,6 +4,7 @@
 // includes it ahead of the kernels, tests/test_detect_plan.py compiles it alone with g++.
 #pragma once
 #include <stddef.h>
+#include "stage.hpp"
 
 #define DET_MAX_CELL 64
 #define DET_CHUNK 1024     // images per pass of the batch entry points (the response maps of a pass live in the scratch: 1.3 MB per EuRoC image)
@@ -14,8 +15,6 @@
 #define DET_SELECT_STATIC_LDS 256                           // bound on k_grid_select's static LDS (locks, counters); tests/test_detect_cases.py holds the build to it
 #define DET_CAND_BYTES 16                                   // sizeof(CellCand), sizeof(SelectOut): detect.hip asserts both
 #define DET_SELECT_OUT_BYTES 56
-
-static inline size_t det_up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------- k_mineig_strip
 // dynamic LDS of k wavefronts: the blurred bytes of their 64 k columns, and the staged map columns (row pitch 65 floats)
@@ -80,9 +79,9 @@ struct DetScratch { size_t img, map, cur, out, so, cand, free_list, total; };
 static inline DetScratch det_scratch(int w, int h, int cell, int mode, int ncur, bool upload)
 {
     const int ncells = (w / cell) * (h / cell);
-    const size_t map = upload ? det_up256((size_t)w * h) : 0, cur = det_up256(map + det_map_bytes(cell, ncells, mode));
-    const size_t out = det_up256(cur + 8 * (size_t)(ncur > 0 ? ncur : 1)), so = out + 16 * (size_t)ncells;       // (the counters right behind the points: one copy back)
-    const size_t cand = det_up256(so + DET_SELECT_OUT_BYTES), free_list = cand + DET_CAND_BYTES * (size_t)ncells;
+    const size_t map = upload ? up256((size_t)w * h) : 0, cur = up256(map + det_map_bytes(cell, ncells, mode));
+    const size_t out = up256(cur + 8 * (size_t)(ncur > 0 ? ncur : 1)), so = out + 16 * (size_t)ncells;       // (the counters right behind the points: one copy back)
+    const size_t cand = up256(so + DET_SELECT_OUT_BYTES), free_list = cand + DET_CAND_BYTES * (size_t)ncells;
     return {0, map, cur, out, so, cand, free_list, free_list + 4 * ((size_t)ncells + 1)};
 }
 
@@ -94,9 +93,9 @@ struct DetBatchScratch { int sets, chunk; size_t map, cand, free_list, set_bytes
 static inline DetBatchScratch det_batch_scratch(int cell, int ncells, int mode, int items)
 {
     const int sets = items > DET_CHUNK / 2 ? 2 : 1, chunk = sets == 2 ? DET_CHUNK / 2 : items;
-    const size_t cand = det_up256((size_t)chunk * det_map_bytes(cell, ncells, mode)), free_list = cand + (size_t)chunk * ncells * DET_CAND_BYTES;
-    const size_t set_bytes = det_up256(free_list + (size_t)chunk * 4 * ((size_t)ncells + 1)), so = (size_t)sets * set_bytes;
-    const size_t par = det_up256(so + (size_t)items * DET_SELECT_OUT_BYTES);
+    const size_t cand = up256((size_t)chunk * det_map_bytes(cell, ncells, mode)), free_list = cand + (size_t)chunk * ncells * DET_CAND_BYTES;
+    const size_t set_bytes = up256(free_list + (size_t)chunk * 4 * ((size_t)ncells + 1)), so = (size_t)sets * set_bytes;
+    const size_t par = up256(so + (size_t)items * DET_SELECT_OUT_BYTES);
     return {sets, chunk, 0, cand, free_list, set_bytes, so, par, par + (size_t)items * 8};
 }
 

@@ -323,20 +323,16 @@ __global__ __launch_bounds__(64) void k_epif_decide(EpifArgs a)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline size_t epif_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 void epif_layout(size_t n_items, size_t NC, size_t NK, size_t NR, int s_max, EpifLayout *L)
 {
     L->B = n_items; L->NC = NC; L->NK = NK; L->NR = NR; L->s_max = s_max;
-    L->o_it = 0;
-    L->o_lm = epif_al(L->o_it + sizeof(EpifItem) * n_items); L->o_un = epif_al(L->o_lm + 4 * NC); L->o_bv = epif_al(L->o_un + 8 * NC);
-    L->o_3d = epif_al(L->o_bv + 24 * NC); L->o_kl = epif_al(L->o_3d + NC); L->o_ku = epif_al(L->o_kl + 4 * NK);
-    L->o_kb = epif_al(L->o_ku + 8 * NK); L->o_up = epif_al(L->o_kb + 24 * NK);
-    L->o_b1 = L->o_up; L->o_b2 = epif_al(L->o_b1 + 24 * NC); L->o_ol = epif_al(L->o_b2 + 24 * NC); L->o_e5 = epif_al(L->o_ol + 4 * NC);
-    L->o_eo = epif_al(L->o_e5 + sizeof(E5Item) * n_items); L->o_md = epif_al(L->o_eo + sizeof(E5Out) * n_items);
-    L->o_va = epif_al(L->o_md + 96 * NR); L->o_sc = epif_al(L->o_va + NR); L->o_down = epif_al(L->o_sc + 8 * NR);
-    L->o_out = L->o_down; L->o_rm = epif_al(L->o_out + sizeof(EpifOut) * n_items); L->o_pc = epif_al(L->o_rm + NC);
-    L->o_er = epif_al(L->o_pc + 4 * NC); L->o_sm = epif_al(L->o_er + 4 * NC); L->total = epif_al(L->o_sm + 32 * NR);
+    StageCursor c(16);
+    L->o_it = c.take(sizeof(EpifItem) * n_items); L->o_lm = c.take(4 * NC); L->o_un = c.take(8 * NC); L->o_bv = c.take(24 * NC);
+    L->o_3d = c.take(NC); L->o_kl = c.take(4 * NK); L->o_ku = c.take(8 * NK); L->o_kb = c.take(24 * NK);
+    L->o_up = L->o_b1 = c.take(24 * NC); L->o_b2 = c.take(24 * NC); L->o_ol = c.take(4 * NC); L->o_e5 = c.take(sizeof(E5Item) * n_items);
+    L->o_eo = c.take(sizeof(E5Out) * n_items); L->o_md = c.take(96 * NR); L->o_va = c.take(NR); L->o_sc = c.take(8 * NR);
+    L->o_down = L->o_out = c.take(sizeof(EpifOut) * n_items); L->o_rm = c.take(NC); L->o_pc = c.take(4 * NC); L->o_er = c.take(4 * NC);
+    L->o_sm = c.take(32 * NR); L->total = c.off;
 }
 
 int epif_layout_capacity(int n_items, int n_max, int n_rows, EpifLayout *L)
@@ -446,10 +442,9 @@ int ov2_epipolar_filter_batch(ov2_ctx *ctx, const ov2_epifilter_params *params, 
         if (rc) return rc;
     } else epif_layout((size_t)n_items, NC, NK, NR, params->n_rows, &L);
     const size_t down_end = trace ? L.total : L.o_sm;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(L.total);                                        if (rc) return rc;
-    rc = ctx->reserve_host(L.o_up > down_end - L.o_down ? L.o_up : down_end - L.o_down);   if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    Stage st;
+    rc = st.open(ctx, L.total, L.o_up > down_end - L.o_down ? L.o_up : down_end - L.o_down);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t p0 = 0, m0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_epifilter_item &k = items[b];
@@ -476,12 +471,12 @@ int ov2_epipolar_filter_batch(ov2_ctx *ctx, const ov2_epifilter_params *params, 
         }
         p0 += n; m0 += m;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, L.o_up, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, L.o_up);  if (rc) return rc;
     rc = epif_chain_enqueue(ctx->stream, params, L, ds, n_items);
     if (rc) return rc;
     // the staging buffer is free again once the upload has run: the results come down over it
-    OV2_HIP_CHECK(hipMemcpyAsync(hs, ds + L.o_down, down_end - L.o_down, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(L.o_down, down_end, 0);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     auto hd = [&](size_t off) { return (const uint8_t *)hs + (off - L.o_down); };   // where the block's byte `off` came down
     p0 = 0;
     for (int b = 0; b < n_items; b++) {

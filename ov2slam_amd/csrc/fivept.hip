@@ -559,8 +559,6 @@ __global__ __launch_bounds__(64) void k_e5_pick(E5Args a)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline size_t e5_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int e5_enqueue(hipStream_t s, const E5Args &a, int n_items, int s_max)
 {
     if (n_items <= 0) return OV2_OK;
@@ -629,14 +627,14 @@ int ov2_epipolar_ransac_batch(ov2_ctx *ctx, const ov2_epipolar_params *params, i
     // staging: [items 16 B][bv1 24][bv2 24][samples 32] up, [out 128][outliers 4][valid 1][score 8][models 96] down (valid and score
     // only for a trace, models only for a model trace); every section 16-byte aligned
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_b1 = e5_al(o_it + sizeof(E5Item) * B), o_b2 = e5_al(o_b1 + 24 * NP), o_sm = e5_al(o_b2 + 24 * NP);
-    const size_t o_out = e5_al(o_sm + 32 * NR), o_ol = e5_al(o_out + sizeof(E5Out) * B), o_va = e5_al(o_ol + 4 * NP);
-    const size_t o_sc = e5_al(o_va + NR), o_md = e5_al(o_sc + 8 * NR), total = e5_al(o_md + 96 * NR);
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(E5Item) * B), o_b1 = c.take(24 * NP), o_b2 = c.take(24 * NP), o_sm = c.take(32 * NR);
+    const size_t o_out = c.take(sizeof(E5Out) * B), o_ol = c.take(4 * NP), o_va = c.take(NR), o_sc = c.take(8 * NR), o_md = c.take(96 * NR);
+    const size_t total = c.off;
     const size_t down_end = NR == 0 ? o_va : (trace_model ? total : (trace ? o_md : o_va));
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(down_end);     if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    Stage st;
+    int rc = st.open(ctx, total, down_end);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t pt0 = 0, row0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_epipolar_problem &p = problems[b];
@@ -649,7 +647,7 @@ int ov2_epipolar_ransac_batch(ov2_ctx *ctx, const ov2_epipolar_params *params, i
         if (p.n_rows) memcpy(hs + o_sm + 32 * row0, p.samples, 32 * (size_t)p.n_rows);
         pt0 += (size_t)p.n; row0 += (size_t)p.n_rows;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, o_out);  if (rc) return rc;
     E5Args a;
     a.items = (const E5Item *)(ds + o_it); a.bv1 = (const double *)(ds + o_b1); a.bv2 = (const double *)(ds + o_b2);
     a.samples = (const int4 *)(ds + o_sm); a.models = (double *)(ds + o_md); a.valid = ds + o_va; a.score = (double *)(ds + o_sc);
@@ -657,8 +655,8 @@ int ov2_epipolar_ransac_batch(ov2_ctx *ctx, const ov2_epipolar_params *params, i
     a.max_iterations = params->max_iterations; a.threshold = params->threshold; a.probability = params->probability;
     rc = e5_enqueue(ctx->stream, a, n_items, s_max);
     if (rc) return rc;
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, down_end - o_out, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_out, down_end, o_out);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     pt0 = row0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_epipolar_problem &p = problems[b];

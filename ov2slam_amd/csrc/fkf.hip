@@ -238,8 +238,6 @@ int fkf_check_decide(const ov2_fkf_params *params)
     return OV2_OK;
 }
 
-static inline size_t fkf_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // every input check of the three entry points, before the context is looked at; full: the arrays the parallax / decision kernel reads
 int fkf_check_items(int n_items, const ov2_fkf_item *items, bool full, size_t *N, size_t *M, int *n_max)
 {
@@ -275,6 +273,32 @@ static void fkf_fill_item(FkfItemD &d, const ov2_fkf_item &k, size_t p0, size_t 
     if (full) { memcpy(d.cur_Twc, k.cur_Twc, 56); memcpy(d.kf_Tcw, k.kf_Tcw, 56); }
 }
 
+// The item arrays both drivers stage, at their offsets in the host block: the item records, [cur_lmid 4][cur_is3d 1] per current
+// keypoint and [kf_lmid 4][kf_unpx 8] per keyframe keypoint always; cur_px, cur_unpx and cur_bv only where the flag says the form
+// reads them (their offsets are then not looked at).  !is3d: the flags are zero-filled.  full: the records carry the two poses.
+struct FkfIn { size_t o_it, o_lm, o_px, o_un, o_bv, o_3d, o_kl, o_ku; bool full, px, un, bv, is3d; };
+static void fkf_stage_items(uint8_t *hs, const FkfIn &s, int n_items, const ov2_fkf_item *items)
+{
+    size_t p0 = 0, m0 = 0;
+    for (int b = 0; b < n_items; b++) {
+        const ov2_fkf_item &k = items[b];
+        const size_t n = (size_t)k.n_cur, m = (size_t)k.n_kf;
+        fkf_fill_item(*(FkfItemD *)(hs + s.o_it + sizeof(FkfItemD) * b), k, p0, m0, s.full);
+        if (n) {
+            memcpy(hs + s.o_lm + 4 * p0, k.cur_lmid, 4 * n);
+            if (s.px) memcpy(hs + s.o_px + 8 * p0, k.cur_px, 8 * n);
+            if (s.un) memcpy(hs + s.o_un + 8 * p0, k.cur_unpx, 8 * n);
+            if (s.bv) memcpy(hs + s.o_bv + 24 * p0, k.cur_bv, 24 * n);
+            if (s.is3d) memcpy(hs + s.o_3d + p0, k.cur_is3d, n); else memset(hs + s.o_3d + p0, 0, n);
+        }
+        if (m) {
+            memcpy(hs + s.o_kl + 4 * m0, k.kf_lmid, 4 * m);
+            memcpy(hs + s.o_ku + 8 * m0, k.kf_unpx, 8 * m);
+        }
+        p0 += n; m0 += m;
+    }
+}
+
 // results: n_items records of `rec_bytes` (ov2_parallax_result, or ov2_kf_decision_result when decide)
 static int fkf_run(ov2_ctx *ctx, const ov2_fkf_params *params, int n_items, const ov2_fkf_item *items, int unrot, int filter, int stat,
                    bool decide, void *results)
@@ -300,40 +324,24 @@ static int fkf_run(ov2_ctx *ctx, const ov2_fkf_params *params, int n_items, cons
     P.ncellsize = params->ncellsize; P.nbwcells = params->nbwcells; P.nbhcells = params->nbhcells; P.nbmaxkps = params->nbmaxkps;
     P.finit_parallax = params->finit_parallax; P.stereo = params->stereo ? 1 : 0;
     P.unrot = unrot; P.filter = filter; P.stat = stat; P.decide = decide ? 1 : 0;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
     // staging: [items 176 B] [cur_lmid 4][cur_px 8][cur_unpx 8][cur_bv 24][cur_is3d 1] per current keypoint, [kf_lmid 4][kf_unpx 8] per
     // keyframe keypoint -- only the arrays this form reads travel (the flags are zero-filled otherwise) --, then FKF_OUT_INTS ints per item
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_lm = fkf_al(o_it + sizeof(FkfItemD) * B), o_px = fkf_al(o_lm + 4 * N), o_un = fkf_al(o_px + (need_px ? 8 * N : 0));
-    const size_t o_bv = fkf_al(o_un + (unrot ? 0 : 8 * N)), o_3d = fkf_al(o_bv + (unrot ? 24 * N : 0)), o_kl = fkf_al(o_3d + N);
-    const size_t o_ku = fkf_al(o_kl + 4 * M), o_out = fkf_al(o_ku + 8 * M), total = fkf_al(o_out + 4 * FKF_OUT_INTS * B);
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
-    size_t p0 = 0, m0 = 0;
-    for (int b = 0; b < n_items; b++) {
-        const ov2_fkf_item &k = items[b];
-        const size_t n = (size_t)k.n_cur, m = (size_t)k.n_kf;
-        fkf_fill_item(*(FkfItemD *)(hs + o_it + sizeof(FkfItemD) * b), k, p0, m0, true);
-        if (n) {
-            memcpy(hs + o_lm + 4 * p0, k.cur_lmid, 4 * n);
-            if (need_px) memcpy(hs + o_px + 8 * p0, k.cur_px, 8 * n);
-            if (unrot) memcpy(hs + o_bv + 24 * p0, k.cur_bv, 24 * n); else memcpy(hs + o_un + 8 * p0, k.cur_unpx, 8 * n);
-            if (need_3d) memcpy(hs + o_3d + p0, k.cur_is3d, n); else memset(hs + o_3d + p0, 0, n);
-        }
-        if (m) {
-            memcpy(hs + o_kl + 4 * m0, k.kf_lmid, 4 * m);
-            memcpy(hs + o_ku + 8 * m0, k.kf_unpx, 8 * m);
-        }
-        p0 += n; m0 += m;
-    }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(FkfItemD) * B), o_lm = c.take(4 * N), o_px = c.take(need_px ? 8 * N : 0);
+    const size_t o_un = c.take(unrot ? 0 : 8 * N), o_bv = c.take(unrot ? 24 * N : 0), o_3d = c.take(N), o_kl = c.take(4 * M);
+    const size_t o_ku = c.take(8 * M), o_out = c.take(4 * FKF_OUT_INTS * B), total = c.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
+    fkf_stage_items(hs, FkfIn{o_it, o_lm, o_px, o_un, o_bv, o_3d, o_kl, o_ku, true, need_px, !unrot, unrot != 0, need_3d}, n_items, items);
+    rc = st.upload(0, o_out);  if (rc) return rc;
     hipLaunchKernelGGL(k_fkf_parallax, dim3(n_items), dim3(FKF_THREADS), 0, ctx->stream, P, (const FkfItemD *)(ds + o_it),
                        (const int *)(ds + o_lm), (const float2 *)(ds + o_px), (const float2 *)(ds + o_un), (const double *)(ds + o_bv),
                        (const uint8_t *)(ds + o_3d), (const int *)(ds + o_kl), (const float2 *)(ds + o_ku), (int *)(ds + o_out));
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_out, total, o_out);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     for (int b = 0; b < n_items; b++) {
         const int *o = (const int *)(hs + o_out) + FKF_OUT_INTS * (size_t)b;
         if (decide) {
@@ -389,42 +397,26 @@ int ov2_sampson_filter_2d_batch(ov2_ctx *ctx, int n_items, const ov2_fkf_item *i
     OV2_REQUIRE(ctx, OV2_EINVAL, "NULL context");
     for (int b = 0; b < n_items; b++) results[b].n_bad = 0;
     if (n_max == 0) return OV2_OK;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
     // staging: [items 176 B][F 72 B] [cur_lmid 4][cur_unpx 8][cur_is3d 1] per current keypoint, [kf_lmid 4][kf_unpx 8] per keyframe
     // keypoint, then the outputs [err 4][bad 1] per current keypoint
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_f = fkf_al(o_it + sizeof(FkfItemD) * B), o_lm = fkf_al(o_f + 72 * B), o_un = fkf_al(o_lm + 4 * N);
-    const size_t o_3d = fkf_al(o_un + 8 * N), o_kl = fkf_al(o_3d + N), o_ku = fkf_al(o_kl + 4 * M), o_err = fkf_al(o_ku + 8 * M);
-    const size_t o_bad = fkf_al(o_err + 4 * N), total = fkf_al(o_bad + N);
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
-    size_t p0 = 0, m0 = 0;
-    for (int b = 0; b < n_items; b++) {
-        const ov2_fkf_item &k = items[b];
-        const size_t n = (size_t)k.n_cur, m = (size_t)k.n_kf;
-        fkf_fill_item(*(FkfItemD *)(hs + o_it + sizeof(FkfItemD) * b), k, p0, m0, false);
-        memcpy(hs + o_f + 72 * b, Fkfcur + 9 * (size_t)b, 72);
-        if (n) {
-            memcpy(hs + o_lm + 4 * p0, k.cur_lmid, 4 * n);
-            memcpy(hs + o_un + 8 * p0, k.cur_unpx, 8 * n);
-            memcpy(hs + o_3d + p0, k.cur_is3d, n);
-        }
-        if (m) {
-            memcpy(hs + o_kl + 4 * m0, k.kf_lmid, 4 * m);
-            memcpy(hs + o_ku + 8 * m0, k.kf_unpx, 8 * m);
-        }
-        p0 += n; m0 += m;
-    }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_err, hipMemcpyHostToDevice, ctx->stream));
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(FkfItemD) * B), o_f = c.take(72 * B), o_lm = c.take(4 * N), o_un = c.take(8 * N), o_3d = c.take(N);
+    const size_t o_kl = c.take(4 * M), o_ku = c.take(8 * M), o_err = c.take(4 * N), o_bad = c.take(N), total = c.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
+    fkf_stage_items(hs, FkfIn{o_it, o_lm, 0, o_un, 0, o_3d, o_kl, o_ku, false, false, true, false, true}, n_items, items);
+    memcpy(hs + o_f, Fkfcur, 72 * B);
+    rc = st.upload(0, o_err);  if (rc) return rc;
     hipLaunchKernelGGL(k_fkf_sampson, dim3((n_max + FKF_THREADS - 1) / FKF_THREADS, n_items), dim3(FKF_THREADS), 0, ctx->stream,
                        (const FkfItemD *)(ds + o_it), (const double *)(ds + o_f), fransac_err, (const int *)(ds + o_lm),
                        (const float2 *)(ds + o_un), (const uint8_t *)(ds + o_3d), (const int *)(ds + o_kl), (const float2 *)(ds + o_ku),
                        (float *)(ds + o_err), ds + o_bad);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_err, ds + o_err, total - o_err, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    p0 = 0;
+    rc = st.download(o_err, total, o_err);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
+    size_t p0 = 0;
     for (int b = 0; b < n_items; b++) {
         const size_t n = (size_t)items[b].n_cur;
         ov2_sampson2d_result &r = results[b];

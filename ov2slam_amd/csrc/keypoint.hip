@@ -86,20 +86,20 @@ int ov2_compute_keypoints(ov2_ctx *ctx, int model, const double K[4], const doub
     KpCalib c;
     int rc = ov2_kp_calib(model, K, D, nD, iK, c);
     if (rc != OV2_OK) return rc;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    // layout: [bv 24n][px 8n][unpx 8n]
-    const size_t o_bv = 0, o_px = 24 * (size_t)n, o_un = 32 * (size_t)n, total = 40 * (size_t)n;
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    // layout: [bv 24n][px 8n][unpx 8n], packed
+    StageCursor sc(1);
+    const size_t o_bv = sc.take(24 * (size_t)n), o_px = sc.take(8 * (size_t)n), o_un = sc.take(8 * (size_t)n), total = sc.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     memcpy(hs + o_px, px_xy_h, 8 * (size_t)n);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds + o_px, hs + o_px, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(o_px, o_un);  if (rc) return rc;
     hipLaunchKernelGGL(k_compute_keypoints, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, c, (const float2 *)(ds + o_px), n,
                        (float2 *)(ds + o_un), bv_xyz_h ? (double *)(ds + o_bv) : nullptr, (const int *)nullptr);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_un, ds + o_un, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (bv_xyz_h) OV2_HIP_CHECK(hipMemcpyAsync(hs + o_bv, ds + o_bv, 24 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_un, total, o_un);  if (rc) return rc;
+    if (bv_xyz_h) { rc = st.download(o_bv, o_px, o_bv);  if (rc) return rc; }
+    rc = st.sync();  if (rc) return rc;
     memcpy(unpx_xy_h, hs + o_un, 8 * (size_t)n);
     if (bv_xyz_h) memcpy(bv_xyz_h, hs + o_bv, 24 * (size_t)n);
     return OV2_OK;

@@ -115,8 +115,6 @@ __global__ __launch_bounds__(256) void k_knn_merge(KnArgs a, int splits)
     kn_finish(a, (size_t)o, d0, d1, i0, i1);
 }
 
-static inline size_t kn_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items, const ov2_knn_item *items, ov2_knn_result *results)
 {
     // the inputs first, the context last: a malformed input is reported without a device
@@ -148,8 +146,9 @@ int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items,
     // staging: [items 16 B][query 32][train 32], then the outputs [idx 8][dist 8][good 1]; every section 16-byte aligned.  On the
     // device only, behind them: the ranges' candidates [part 16 per range and query row] when the train tiles are split
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_q = kn_al(o_it + sizeof(KnItem) * B), o_t = kn_al(o_q + 32 * NQ), o_out = kn_al(o_t + 32 * NT);
-    const size_t o_d = kn_al(o_out + 8 * NQ), o_g = kn_al(o_d + 8 * NQ), total = kn_al(o_g + NQ);
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(KnItem) * B), o_q = c.take(32 * NQ), o_t = c.take(32 * NT);
+    const size_t o_out = c.take(8 * NQ), o_d = c.take(8 * NQ), o_g = c.take(NQ), total = c.off;
     // Few work-groups and several train tiles: ranges of tiles over grid.z, so that a single call is not one wavefront's walk
     // over all train rows.  A call that fills the device anyway keeps the whole walk in one work-group and needs no merge.
     const int q_tiles = (q_max + KNN_QUERIES - 1) / KNN_QUERIES, t_tiles = t_max > 0 ? (t_max - 1) / KNN_TILE + 1 : 0;
@@ -161,10 +160,9 @@ int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items,
         splits = (t_tiles + chunk_tiles - 1) / chunk_tiles;
     }
     const size_t part_bytes = splits > 1 ? 16 * NQ * (size_t)splits : 0;      // device only, behind the outputs
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = ctx->reserve_device(total + part_bytes);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    Stage st;
+    int rc = st.open(ctx, total + part_bytes, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t q0 = 0, t0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_knn_item &k = items[b];
@@ -175,7 +173,7 @@ int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items,
         q0 += (size_t)k.n_query; t0 += (size_t)k.n_train;
     }
     if (NQ > 0) {
-        OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+        rc = st.upload(0, o_out);  if (rc) return rc;
         KnArgs a;
         a.items = (const KnItem *)(ds + o_it);
         a.query = (const uint4 *)(ds + o_q); a.train = (const uint4 *)(ds + o_t);
@@ -188,8 +186,8 @@ int ov2_knn_match_batch(ov2_ctx *ctx, const ov2_knn_params *params, int n_items,
             hipLaunchKernelGGL(k_knn_merge, dim3((unsigned)((NQ + 255) / 256)), dim3(256), 0, ctx->stream, a, splits);
             OV2_HIP_CHECK(hipGetLastError());
         }
-        OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
-        OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        rc = st.download(o_out, total, o_out);  if (rc) return rc;
+        rc = st.sync();  if (rc) return rc;
     }
     q0 = 0;
     for (int b = 0; b < n_items; b++) {

@@ -276,7 +276,6 @@ __global__ __launch_bounds__(256) void k_lckf_emit(LckfArgs a)
     }
 }
 
-static inline size_t lk_al(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // drawing.cpp Circle(): rows +-dy get half-width dx, rows +-dx get dy (the fill variant's four spans per step)
 static void lckf_halfwidths(signed char *hw, int radius)
@@ -328,8 +327,8 @@ static LckfPlan lckf_plan(const ov2_ctx *ctx, int w, int h, int n_items, int kep
     LckfPlan p;
     p.mpitch = (w + LCKF_TILE_W - 1) / LCKF_TILE_W * LCKF_TILE_W;
     p.mwpr = (w + 31) / 32;
-    const size_t b_mask = lk_al(4 * (size_t)p.mwpr * h), b_hist = 1024, b_map = lk_al((size_t)p.mpitch * h), b_rows = lk_al(16 * (size_t)h);
-    const size_t b_fxy = lk_al(8 * (size_t)kept_cap);
+    const size_t b_mask = up256(4 * (size_t)p.mwpr * h), b_hist = 1024, b_map = up256((size_t)p.mpitch * h), b_rows = up256(16 * (size_t)h);
+    const size_t b_fxy = up256(8 * (size_t)kept_cap);
     p.per_item = b_mask + b_hist + b_map + b_rows + 8 + b_fxy;
     size_t chunk = ((size_t)ctx->lckf_scratch_kb << 10) / p.per_item;
     chunk = chunk < 1 ? 1 : chunk;
@@ -337,7 +336,7 @@ static LckfPlan lckf_plan(const ov2_ctx *ctx, int w, int h, int n_items, int kep
     const size_t c = (size_t)p.chunk;
     // [masks][histograms]: one memset per chunk; then the maps, the row counts, the two small per-item arrays, BRIEF's points
     p.o_mask = 0; p.o_hist = b_mask * c; p.o_map = p.o_hist + b_hist * c; p.o_rows = p.o_map + b_map * c;
-    p.o_th = p.o_rows + b_rows * c; p.o_nb = lk_al(p.o_th + 4 * c); p.o_fxy = lk_al(p.o_nb + 4 * c);
+    p.o_th = p.o_rows + b_rows * c; p.o_nb = up256(p.o_th + 4 * c); p.o_fxy = up256(p.o_nb + 4 * c);
     p.total = p.o_fxy + b_fxy * c;
     return p;
 }
@@ -420,10 +419,10 @@ int ov2_lckf_run_h(ov2_ctx *ctx, const uint8_t *img_h, const uint8_t *img_d, int
     // staging, the same layout on both sides: [n_excl 4][excl 8 per slot] | [counts 16][kept_xy 4][kept_resp 1][kept_valid 1][kept_desc 32]
     // [all_xy 4][all_resp 1] per slot; on the device the host image (if any) ahead of it and the scratch behind
     const size_t B = (size_t)n_items, ks = B * (size_t)kept_cap, as = B * (size_t)all_cap;
-    const size_t o_n = 0, o_ex = lk_al(4 * B), o_out = lk_al(o_ex + 8 * B * (size_t)excl_cap);
-    const size_t o_kxy = lk_al(o_out + 16 * B), o_kr = lk_al(o_kxy + 4 * ks), o_kv = lk_al(o_kr + ks), o_kd = lk_al(o_kv + ks);
-    const size_t o_axy = lk_al(o_kd + 32 * ks), o_ar = lk_al(o_axy + 4 * as), blk = lk_al(o_ar + as);
-    const size_t img_pitch = lk_al((size_t)w), img_bytes = img_h ? lk_al(img_pitch * (size_t)h) : 0;
+    const size_t o_n = 0, o_ex = up256(4 * B), o_out = up256(o_ex + 8 * B * (size_t)excl_cap);
+    const size_t o_kxy = up256(o_out + 16 * B), o_kr = up256(o_kxy + 4 * ks), o_kv = up256(o_kr + ks), o_kd = up256(o_kv + ks);
+    const size_t o_axy = up256(o_kd + 32 * ks), o_ar = up256(o_axy + 4 * as), blk = up256(o_ar + as);
+    const size_t img_pitch = up256((size_t)w), img_bytes = img_h ? up256(img_pitch * (size_t)h) : 0;
     const LckfPlan pl = lckf_plan(ctx, w, h, n_items, kept_cap);
     rc = ctx->reserve_host(blk);                                                  if (rc != OV2_OK) return rc;
     rc = ctx->reserve_device(img_bytes + blk + pl.total);           if (rc != OV2_OK) return rc;

@@ -729,23 +729,23 @@ static int lk_host_call(ov2_ctx *ctx, const ov2_pyr *prev, const ov2_pyr *cur, L
                         long long *stats_h)
 {
     OV2_REQUIRE(prev->d.batch == 1 && cur->d.batch == 1, OV2_EINVAL, "host-buffer LK entry points take batch=1 pyramids");
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    // layout: [kps 8n][priors 8n][err 4n][iters 4n][stats 16][status n]
-    const size_t o_kps = 0, o_pri = 8 * (size_t)n, o_err = 16 * (size_t)n, o_it = 20 * (size_t)n;
-    const size_t o_stats = 24 * (size_t)n, o_st = o_stats + 16, total = o_st + (size_t)n;
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    // layout: [kps 8n][priors 8n][err 4n][iters 4n][stats 16][status n], packed
+    StageCursor c(1);
+    const size_t o_kps = c.take(8 * (size_t)n), o_pri = c.take(8 * (size_t)n), o_err = c.take(4 * (size_t)n), o_it = c.take(4 * (size_t)n);
+    const size_t o_stats = c.take(16), o_st = c.take((size_t)n), total = c.off;
+    Stage st;
+    int rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     memcpy(hs + o_kps, kps_h, 8 * (size_t)n);
     memcpy(hs + o_pri, priors_h, 8 * (size_t)n);
     memset(hs + o_stats, 0, 16);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_err, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(o_kps, o_err);  if (rc) return rc;
     OV2_HIP_CHECK(hipMemsetAsync(ds + o_stats, 0, 16, ctx->stream));
     rc = lk_dispatch(ctx, prev, cur, prm, (const float2 *)(ds + o_kps), (float2 *)(ds + o_pri), ds + o_st,
                      (float *)(ds + o_err), (int *)(ds + o_it), nullptr, (long long *)(ds + o_stats));
     if (rc) return rc;
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_pri, ds + o_pri, total - o_pri, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_pri, total, o_pri);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     memcpy(priors_h, hs + o_pri, 8 * (size_t)n);
     memcpy(status_h, hs + o_st, (size_t)n);
     if (err_h) memcpy(err_h, hs + o_err, 4 * (size_t)n);

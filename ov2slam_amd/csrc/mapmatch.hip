@@ -217,8 +217,6 @@ __global__ __launch_bounds__(256) void k_map_pick(const unsigned long long *__re
     kp_dist[i] = none ? 0.f : (float)(unsigned)(key >> 32);
 }
 
-static inline size_t mt_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // offsets[0 .. n]: starts at 0, never decreases
 static bool mt_offsets_ok(const int *o, int n)
 {
@@ -340,17 +338,16 @@ static int mt_run(ov2_ctx *ctx, const Params *params, int n_items, const Item *i
     // [obs_kf 4, mapper][obs_px 8, mapper][desc 32][kf_Tcw 56, mapper][lm_mp 4][lm_wpt 24][keys 8, all ones], then the outputs
     // [lm_status 1][lm_kp 4][lm_dist 4][lm_projpx 8][kp_lm 4][kp_dist 4]; every section 16-byte aligned, a section of the other mode empty
     const size_t CS = B * (ncells + 1), MS = NMP + B, NKM = LOOP ? NKP : 0, NOM = LOOP ? 0 : NOB;
-    const size_t o_it = 0, o_kpx = mt_al(o_it + sizeof(MapMatchItem) * B), o_kmp = mt_al(o_kpx + 8 * NKP), o_kma = mt_al(o_kmp + 4 * NKP);
-    const size_t o_cs = mt_al(o_kma + NKM), o_ck = mt_al(o_cs + 4 * CS), o_os = mt_al(o_ck + 4 * NCK), o_ds = mt_al(o_os + 4 * MS);
-    const size_t o_oid = mt_al(o_ds + 4 * MS), o_okf = mt_al(o_oid + 4 * NOB), o_opx = mt_al(o_okf + 4 * NOM), o_de = mt_al(o_opx + 8 * NOM);
-    const size_t o_kf = mt_al(o_de + 32 * NDE), o_lmp = mt_al(o_kf + 56 * NKF), o_lw = mt_al(o_lmp + 4 * NLM), o_key = mt_al(o_lw + 24 * NLM);
-    const size_t o_out = mt_al(o_key + 8 * NKP);
-    const size_t o_lk = mt_al(o_out + NLM), o_ld = mt_al(o_lk + 4 * NLM), o_lp = mt_al(o_ld + 4 * NLM), o_kl = mt_al(o_lp + 8 * NLM);
-    const size_t o_kd = mt_al(o_kl + 4 * NKP), total = mt_al(o_kd + 4 * NKP);
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(MapMatchItem) * B), o_kpx = c.take(8 * NKP), o_kmp = c.take(4 * NKP), o_kma = c.take(NKM);
+    const size_t o_cs = c.take(4 * CS), o_ck = c.take(4 * NCK), o_os = c.take(4 * MS), o_ds = c.take(4 * MS), o_oid = c.take(4 * NOB);
+    const size_t o_okf = c.take(4 * NOM), o_opx = c.take(8 * NOM), o_de = c.take(32 * NDE), o_kf = c.take(56 * NKF), o_lmp = c.take(4 * NLM);
+    const size_t o_lw = c.take(24 * NLM), o_key = c.take(8 * NKP);
+    const size_t o_out = c.take(NLM), o_lk = c.take(4 * NLM), o_ld = c.take(4 * NLM), o_lp = c.take(8 * NLM), o_kl = c.take(4 * NKP);
+    const size_t o_kd = c.take(4 * NKP), total = c.off;
+    Stage st;
+    int rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t kp0 = 0, ck0 = 0, mp0 = 0, ob0 = 0, de0 = 0, kf0 = 0, lm0 = 0;
     for (int b = 0; b < n_items; b++) {
         const Item &k = items[b];
@@ -397,7 +394,7 @@ static int mt_run(ov2_ctx *ctx, const Params *params, int n_items, const Item *i
         kp0 += (size_t)k.n_kp; ck0 += n_ck; mp0 += (size_t)k.n_mp; ob0 += n_ob; de0 += n_de; kf0 += n_kf; lm0 += (size_t)k.n_lm;
     }
     memset(hs + o_key, 0xff, 8 * NKP);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, o_out);  if (rc) return rc;
     if (NKP + NLM > 0) {
         a.items = (const MapMatchItem *)(ds + o_it);
         a.kp_px = (const float2 *)(ds + o_kpx); a.kp_mp = (const int *)(ds + o_kmp);
@@ -421,9 +418,9 @@ static int mt_run(ov2_ctx *ctx, const Params *params, int n_items, const Item *i
                                (int *)(ds + o_kl), (float *)(ds + o_kd));
             OV2_HIP_CHECK(hipGetLastError());
         }
-        OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
+        rc = st.download(o_out, total, o_out);  if (rc) return rc;
     }
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.sync();  if (rc) return rc;
     kp0 = lm0 = 0;
     for (int b = 0; b < n_items; b++) {
         const size_t nk = (size_t)items[b].n_kp, nl = (size_t)items[b].n_lm;

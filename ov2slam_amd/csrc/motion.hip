@@ -50,8 +50,6 @@ __global__ __launch_bounds__(MO_THREADS) void k_motion_update(int n, const ov2_m
     state_out[b] = so;
 }
 
-static inline size_t mo_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 static bool mo_finite(const double *v, int n)
 {
     for (int k = 0; k < n; k++)
@@ -86,17 +84,17 @@ static int mo_run(ov2_ctx *ctx, bool apply, int n, const ov2_motion_state *state
     OV2_REQUIRE(ctx, OV2_EINVAL, "NULL context");
     if (n == 0) return OV2_OK;
     const size_t B = (size_t)n;
-    const size_t o_si = 0, o_T = mo_al(o_si + sizeof(ov2_motion_state) * B), o_tm = mo_al(o_T + 56 * B), o_so = mo_al(o_tm + 8 * B);
-    const size_t o_To = mo_al(o_so + sizeof(ov2_motion_state) * B), o_Ti = mo_al(o_To + (apply ? 56 * B : 0));
-    const size_t o_rs = mo_al(o_Ti + (apply ? 56 * B : 0)), total = mo_al(o_rs + (apply ? B : 0));
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor c(16);
+    const size_t o_si = c.take(sizeof(ov2_motion_state) * B), o_T = c.take(56 * B), o_tm = c.take(8 * B);
+    const size_t o_so = c.take(sizeof(ov2_motion_state) * B), o_To = c.take(apply ? 56 * B : 0), o_Ti = c.take(apply ? 56 * B : 0);
+    const size_t o_rs = c.take(apply ? B : 0), total = c.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     memcpy(hs + o_si, state_in, sizeof(ov2_motion_state) * B);
     memcpy(hs + o_T, Twc, 56 * B);
     memcpy(hs + o_tm, time, 8 * B);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_so, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, o_so);  if (rc) return rc;
     const dim3 grid((n + MO_THREADS - 1) / MO_THREADS), block(MO_THREADS);
     if (apply)
         hipLaunchKernelGGL(k_motion_apply, grid, block, 0, ctx->stream, n, (const ov2_motion_state *)(ds + o_si), (const double *)(ds + o_T),
@@ -106,8 +104,8 @@ static int mo_run(ov2_ctx *ctx, bool apply, int n, const ov2_motion_state *state
         hipLaunchKernelGGL(k_motion_update, grid, block, 0, ctx->stream, n, (const ov2_motion_state *)(ds + o_si), (const double *)(ds + o_T),
                            (const double *)(ds + o_tm), (ov2_motion_state *)(ds + o_so));
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_so, ds + o_so, total - o_so, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_so, total, o_so);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     memcpy(state_out, hs + o_so, sizeof(ov2_motion_state) * B);
     if (apply) {
         memcpy(Twc_out, hs + o_To, 56 * B);

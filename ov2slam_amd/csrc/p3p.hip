@@ -438,8 +438,6 @@ __global__ __launch_bounds__(64) void k_p3p_pick(P3Args a)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline size_t p3_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 static inline unsigned long long p3_splitmix64(unsigned long long seed, unsigned long long j)
 {
     unsigned long long z = seed + (j + 1ull) * 0x9E3779B97F4A7C15ull;
@@ -467,9 +465,10 @@ int ov2_p3p_draw_samples(unsigned long long seed, int n, int rows, int *out)
 static void p3p_plan_fill(P3Plan &pl, size_t B, size_t NP, size_t NR, int n_max, int s_max, bool trace)
 {
     pl.B = B; pl.NP = NP; pl.NR = NR; pl.n_max = n_max; pl.s_max = s_max; pl.trace = trace;
-    pl.o_it = 0; pl.o_bv = p3_al(pl.o_it + sizeof(P3Item) * B); pl.o_X = p3_al(pl.o_bv + 24 * NP); pl.o_sm = p3_al(pl.o_X + 24 * NP);
-    pl.o_out = p3_al(pl.o_sm + 16 * NR); pl.o_ol = p3_al(pl.o_out + sizeof(P3Out) * B); pl.o_va = p3_al(pl.o_ol + 4 * NP);
-    pl.o_sc = p3_al(pl.o_va + NR); pl.o_md = p3_al(pl.o_sc + 8 * NR); pl.total = p3_al(pl.o_md + 96 * NR);
+    StageCursor c(16);
+    pl.o_it = c.take(sizeof(P3Item) * B); pl.o_bv = c.take(24 * NP); pl.o_X = c.take(24 * NP); pl.o_sm = c.take(16 * NR);
+    pl.o_out = c.take(sizeof(P3Out) * B); pl.o_ol = c.take(4 * NP); pl.o_va = c.take(NR); pl.o_sc = c.take(8 * NR);
+    pl.o_md = c.take(96 * NR); pl.total = c.off;
 }
 
 int p3p_plan(const ov2_p3p_params *params, int n_items, const ov2_p3p_problem *problems, const ov2_p3p_result *results, P3Plan *plan)
@@ -567,17 +566,16 @@ int ov2_p3p_ransac_batch(ov2_ctx *ctx, const ov2_p3p_params *params, int n_items
     OV2_REQUIRE(ctx, OV2_EINVAL, "NULL context");
     if (n_items == 0) return OV2_OK;
 
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(pl.total);  if (rc) return rc;
-    rc = ctx->reserve_host(pl.o_md);     if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    Stage st;
+    rc = st.open(ctx, pl.total, pl.o_md);  if (rc) return rc;     // (the models stay on the device: the host block ends where they begin)
+    uint8_t *hs = st.h, *ds = st.d;
     p3p_stage(pl, problems, hs);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, pl.o_out, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, pl.o_out);  if (rc) return rc;
     rc = p3p_enqueue(ctx->stream, params, pl, ds);
     if (rc) return rc;
     const size_t down_end = (pl.trace && pl.NR > 0) ? pl.o_md : pl.o_va;
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + pl.o_out, ds + pl.o_out, down_end - pl.o_out, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(pl.o_out, down_end, pl.o_out);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     size_t pt0 = 0, row0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_p3p_problem &p = problems[b];

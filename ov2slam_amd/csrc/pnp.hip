@@ -344,8 +344,6 @@ __global__ __launch_bounds__(64) void k_pose_decide(PoseArgs a)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline size_t pn_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 static int pnp_check_params(const ov2_pnp_params *p)
 {
     OV2_REQUIRE(p, OV2_EINVAL, "NULL params");
@@ -384,6 +382,22 @@ static void pnp_fill_args(PnPArgs &a, const ov2_pnp_params *p)
     for (int c = 0; c < 4; c++) a.calib_l[c] = p->K[c];
 }
 
+// the pose inputs of problem b, whose points start at pt0, into the host block: [item 16][Twc 56] per item, [unpx 16][wpt 24]
+// [sigma 8 = 2^scale] per point.  Both drivers stage them; a PnPItem is a PoseItem whose two flags are 0.
+struct PnpIn { size_t o_it, o_tw, o_px, o_wp, o_sg; };
+static_assert(sizeof(PnPItem) == sizeof(PoseItem), "one item record for both drivers");
+static void pnp_stage_item(uint8_t *hs, const PnpIn &s, int b, const PoseItem &it, const double *Twc, const double *unpx, const double *wpt,
+                           const int *scale)
+{
+    memcpy(hs + s.o_it + sizeof(PoseItem) * b, &it, sizeof(PoseItem));
+    memcpy(hs + s.o_tw + 56 * (size_t)b, Twc, 56);
+    if (it.n == 0) return;
+    memcpy(hs + s.o_px + 16 * (size_t)it.pt0, unpx, 16 * (size_t)it.n);
+    memcpy(hs + s.o_wp + 24 * (size_t)it.pt0, wpt, 24 * (size_t)it.n);
+    double *sg = (double *)(hs + s.o_sg) + it.pt0;
+    for (int i = 0; i < it.n; i++) sg[i] = ldexp(1.0, scale[i]);
+}
+
 static void pnp_store_pass(ov2_pnp_pass &d, int ran, int it, int ns, int term, double ic, double fc)
 {
     d.ran = ran; d.iterations = it; d.num_successful_steps = ns; d.termination = term; d.initial_cost = ic; d.final_cost = fc;
@@ -403,11 +417,11 @@ int pose_layout(int n_items, int n_max, int n_rows, PoseLayout *L)
     const int rc = p3p_plan_capacity(n_items, n_max, n_rows, &L->pl);  if (rc) return rc;
     const size_t B = (size_t)n_items, NP = L->pl.NP;
     L->B = B; L->n_max = n_max; L->n_rows = n_rows;
-    L->o_it = 0; L->o_px = pn_al(L->o_it + sizeof(PoseItem) * B); L->o_sg = pn_al(L->o_px + 16 * NP); L->o_p3 = pn_al(L->o_sg + 8 * NP);
-    L->o_cx = pn_al(L->o_p3 + L->pl.total); L->o_cw = pn_al(L->o_cx + 16 * NP); L->o_cs = pn_al(L->o_cw + 24 * NP); L->o_ix = pn_al(L->o_cs + 8 * NP);
-    L->o_pi = pn_al(L->o_ix + 4 * NP); L->o_q0 = pn_al(L->o_pi + sizeof(PnPItem) * B); L->o_st = pn_al(L->o_q0 + 56 * B);
-    L->o_po = pn_al(L->o_st + 4 * B); L->o_pl = pn_al(L->o_po + sizeof(PnPOut) * B); L->o_rm = pn_al(L->o_pl + 4 * NP);
-    L->total = pn_al(L->o_rm + NP);
+    StageCursor c(16);
+    L->o_it = c.take(sizeof(PoseItem) * B); L->o_px = c.take(16 * NP); L->o_sg = c.take(8 * NP); L->o_p3 = c.take(L->pl.total);
+    L->o_cx = c.take(16 * NP); L->o_cw = c.take(24 * NP); L->o_cs = c.take(8 * NP); L->o_ix = c.take(4 * NP);
+    L->o_pi = c.take(sizeof(PnPItem) * B); L->o_q0 = c.take(56 * B); L->o_st = c.take(4 * B); L->o_po = c.take(sizeof(PnPOut) * B);
+    L->o_pl = c.take(4 * NP); L->o_rm = c.take(NP); L->total = c.off;
     return OV2_OK;
 }
 
@@ -471,35 +485,27 @@ int ov2_ceres_pnp_batch(ov2_ctx *ctx, const ov2_pnp_params *params, int n_items,
 
     // staging: [items 16 B][pose0 56][unpx 16][wpt 24][sigma 8] up, [out 128][outliers 4] down; every section 16-byte aligned
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_p0 = pn_al(o_it + sizeof(PnPItem) * B), o_px = pn_al(o_p0 + 56 * B), o_wp = pn_al(o_px + 16 * NP), o_sg = pn_al(o_wp + 24 * NP);
-    const size_t o_out = pn_al(o_sg + 8 * NP), o_ol = pn_al(o_out + sizeof(PnPOut) * B), total = pn_al(o_ol + 4 * NP);
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(PnPItem) * B), o_p0 = c.take(56 * B), o_px = c.take(16 * NP), o_wp = c.take(24 * NP), o_sg = c.take(8 * NP);
+    const size_t o_out = c.take(sizeof(PnPOut) * B), o_ol = c.take(4 * NP), total = c.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t pt0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_pnp_problem &p = problems[b];
-        const PnPItem it{p.n, (int)pt0, 0, 0};
-        memcpy(hs + o_it + sizeof(PnPItem) * b, &it, sizeof(PnPItem));
-        memcpy(hs + o_p0 + 56 * (size_t)b, p.Twc, 56);
-        if (p.n) {
-            memcpy(hs + o_px + 16 * pt0, p.unpx, 16 * (size_t)p.n);
-            memcpy(hs + o_wp + 24 * pt0, p.wpt, 24 * (size_t)p.n);
-            double *sg = (double *)(hs + o_sg) + pt0;
-            for (int i = 0; i < p.n; i++) sg[i] = ldexp(1.0, p.scale[i]);
-        }
+        pnp_stage_item(hs, PnpIn{o_it, o_p0, o_px, o_wp, o_sg}, b, PoseItem{p.n, (int)pt0, 0, 0}, p.Twc, p.unpx, p.wpt, p.scale);
         pt0 += (size_t)p.n;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, o_out);  if (rc) return rc;
     PnPArgs a;
     pnp_fill_args(a, params);
     a.items = (const PnPItem *)(ds + o_it); a.pose0 = (const double *)(ds + o_p0); a.unpx = (const double *)(ds + o_px);
     a.wpt = (const double *)(ds + o_wp); a.sigma = (const double *)(ds + o_sg); a.out = (PnPOut *)(ds + o_out); a.outliers = (int *)(ds + o_ol);
     hipLaunchKernelGGL(k_pnp_solve, dim3(n_items), dim3(PNP_THREADS), 0, ctx->stream, a);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_out, total, o_out);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     pt0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_pnp_problem &p = problems[b];
@@ -554,31 +560,24 @@ int ov2_compute_pose_batch(ov2_ctx *ctx, const ov2_pose_params *params, int n_it
     // here -- [the rest of the search's block][compacted unpx, wpt, sigma, idx 4][PnP items 16, pose0 56, stage 4, PnP out 128,
     // PnP outliers 4][out 168, removed 1] -- ONE download of the last two
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_tw = pn_al(o_it + sizeof(PoseItem) * B), o_px = pn_al(o_tw + 56 * B), o_wp = pn_al(o_px + 16 * NP), o_sg = pn_al(o_wp + 24 * NP);
-    const size_t o_p3 = pn_al(o_sg + 8 * NP), up_end = o_p3 + (any_p3p ? pl.o_out : 0);
-    const size_t o_cx = pn_al(o_p3 + (any_p3p ? pl.total : 0)), o_cw = pn_al(o_cx + 16 * NP), o_cs = pn_al(o_cw + 24 * NP), o_ix = pn_al(o_cs + 8 * NP);
-    const size_t o_pi = pn_al(o_ix + 4 * NP), o_q0 = pn_al(o_pi + sizeof(PnPItem) * B), o_st = pn_al(o_q0 + 56 * B), o_po = pn_al(o_st + 4 * B);
-    const size_t o_pl = pn_al(o_po + sizeof(PnPOut) * B), o_out = pn_al(o_pl + 4 * NP), o_rm = pn_al(o_out + sizeof(PoseOut) * B), total = pn_al(o_rm + NP);
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(total);                      if (rc) return rc;
-    rc = ctx->reserve_host(up_end + (total - o_out));     if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch, *hd = hs + up_end;   // hd: where [o_out, total) comes down
+    StageCursor c(16);
+    const size_t o_it = c.take(sizeof(PoseItem) * B), o_tw = c.take(56 * B), o_px = c.take(16 * NP), o_wp = c.take(24 * NP), o_sg = c.take(8 * NP);
+    const size_t o_p3 = c.take(any_p3p ? pl.total : 0), up_end = o_p3 + (any_p3p ? pl.o_out : 0);
+    const size_t o_cx = c.take(16 * NP), o_cw = c.take(24 * NP), o_cs = c.take(8 * NP), o_ix = c.take(4 * NP);
+    const size_t o_pi = c.take(sizeof(PnPItem) * B), o_q0 = c.take(56 * B), o_st = c.take(4 * B), o_po = c.take(sizeof(PnPOut) * B);
+    const size_t o_pl = c.take(4 * NP), o_out = c.take(sizeof(PoseOut) * B), o_rm = c.take(NP), total = c.off;
+    Stage st;
+    rc = st.open(ctx, total, up_end + (total - o_out));  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d, *hd = hs + up_end;   // hd: where [o_out, total) comes down
     size_t pt0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_pose_problem &p = problems[b];
-        const PoseItem it{p.n, (int)pt0, p.do_p3p != 0, p.p3p_req != 0};
-        memcpy(hs + o_it + sizeof(PoseItem) * b, &it, sizeof(PoseItem));
-        memcpy(hs + o_tw + 56 * (size_t)b, p.Twc, 56);
-        if (p.n) {
-            memcpy(hs + o_px + 16 * pt0, p.unpx, 16 * (size_t)p.n);
-            memcpy(hs + o_wp + 24 * pt0, p.wpt, 24 * (size_t)p.n);
-            double *sg = (double *)(hs + o_sg) + pt0;
-            for (int i = 0; i < p.n; i++) sg[i] = ldexp(1.0, p.scale[i]);
-        }
+        pnp_stage_item(hs, PnpIn{o_it, o_tw, o_px, o_wp, o_sg}, b, PoseItem{p.n, (int)pt0, p.do_p3p != 0, p.p3p_req != 0}, p.Twc, p.unpx, p.wpt,
+                       p.scale);
         pt0 += (size_t)p.n;
     }
     if (any_p3p) p3p_stage(pl, search.data(), hs + o_p3);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, up_end, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, up_end);  if (rc) return rc;
     if (any_p3p) { rc = p3p_enqueue(ctx->stream, &params->p3p, pl, ds + o_p3);  if (rc) return rc; }
     PoseArgs g;
     g.items = (const PoseItem *)(ds + o_it); g.Twc = (const double *)(ds + o_tw); g.unpx = (const double *)(ds + o_px);
@@ -600,8 +599,8 @@ int ov2_compute_pose_batch(ov2_ctx *ctx, const ov2_pose_params *params, int n_it
     OV2_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_pose_decide, dim3(n_items), dim3(64), 0, ctx->stream, g);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hd, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_out, total, up_end);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     pt0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_pose_problem &p = problems[b];

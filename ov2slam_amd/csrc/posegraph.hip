@@ -639,8 +639,6 @@ __global__ __launch_bounds__(256) void k_pg_apply(PgApply a)
 }
 
 // ---------------------------------------------------------------------------------- host
-static inline size_t pg_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 static bool pg_pose_ok(const double *p)
 {
     for (int k = 0; k < 7; k++) if (!std::isfinite(p[k])) return false;
@@ -749,44 +747,42 @@ int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *
     // arena: [items][out][x of every item] [the other staged arrays] [workspace]; up: everything before the workspace, down: out and x
     const size_t B = (size_t)n_items;
     std::vector<PgItem> items(B);
-    size_t off = pg_al(sizeof(PgItem) * B);
-    const size_t o_out = off;
-    off = pg_al(off + sizeof(PgOut) * B);
-    auto take = [&](size_t bytes) { const size_t o = off; off = pg_al(off + bytes); return (long long)o; };
+    StageCursor c(16);
+    c.take(sizeof(PgItem) * B);
+    const size_t o_out = c.take(sizeof(PgOut) * B);
     bool any = false;
     for (size_t b = 0; b < B; b++) {
         PgItem &it = items[b];
         it.n_poses = p[b].n_poses; it.n_var = H[b].n_var; it.n_act = H[b].n_act; it.n_seg = H[b].n_seg;
-        it.o_x = take(56 * (size_t)it.n_poses);
+        it.o_x = c.take(56 * (size_t)it.n_poses);
         any = any || it.n_act > 0;
     }
-    const size_t down_end = off;
+    const size_t down_end = c.off;
     for (size_t b = 0; b < B; b++) {
         PgItem &it = items[b];
         const size_t NP = (size_t)it.n_poses + 1, NV = (size_t)it.n_var + 2, NE = (size_t)it.n_act + 1;
-        it.o_vidx = take(4 * NP); it.o_ei = take(4 * NE); it.o_ej = take(4 * NE); it.o_eT = take(56 * NE); it.o_esi = take(8 * NE);
-        it.o_incp = take(4 * NV); it.o_inc = take(4 * (H[b].inc.size() + 1)); it.o_seg = take(4 * (2 * (size_t)it.n_seg + NV));
+        it.o_vidx = c.take(4 * NP); it.o_ei = c.take(4 * NE); it.o_ej = c.take(4 * NE); it.o_eT = c.take(56 * NE); it.o_esi = c.take(8 * NE);
+        it.o_incp = c.take(4 * NV); it.o_inc = c.take(4 * (H[b].inc.size() + 1)); it.o_seg = c.take(4 * (2 * (size_t)it.n_seg + NV));
     }
-    const size_t up_end = off;
+    const size_t up_end = c.off;
     for (size_t b = 0; b < B; b++) {
         PgItem &it = items[b];
         const size_t NP = (size_t)it.n_poses + 1, NV = (size_t)it.n_var + 1, NE = (size_t)it.n_act + 1;
-        it.o_cand = take(56 * NP); it.o_r = take(48 * NE); it.o_J = take(576 * NE);
-        it.o_H = take(288 * NV); it.o_C = take(288 * NV); it.o_L = take(288 * NV); it.o_W = take(288 * NV); it.o_G = take(288 * NV); it.o_K = take(288 * NV);
-        it.o_g = take(48 * NV); it.o_b = take(48 * NV); it.o_scale = take(48 * NV); it.o_y = take(48 * NV);
+        it.o_cand = c.take(56 * NP); it.o_r = c.take(48 * NE); it.o_J = c.take(576 * NE);
+        it.o_H = c.take(288 * NV); it.o_C = c.take(288 * NV); it.o_L = c.take(288 * NV); it.o_W = c.take(288 * NV); it.o_G = c.take(288 * NV); it.o_K = c.take(288 * NV);
+        it.o_g = c.take(48 * NV); it.o_b = c.take(48 * NV); it.o_scale = c.take(48 * NV); it.o_y = c.take(48 * NV);
     }
-    const size_t total = off;
+    const size_t total = c.off;
     float ms = 0;
     const uint8_t *hs_c = nullptr;
     const bool trace = n_items == 1 && ctx->ba_trace;      // ov2_pose_graph_solve (a batch call with one item is the same call)
     BAIterRec *trace_d = nullptr;
     ctx->ba_trace_n = 0;                                   // (also when nothing is solved)
     if (any) {
-        OV2_HIP_CHECK(hipSetDevice(ctx->device));
-        rc = ctx->reserve_device(total);  if (rc) return rc;
-        rc = ctx->reserve_host(up_end);   if (rc) return rc;
+        Stage st;
+        rc = st.open(ctx, total, up_end);  if (rc) return rc;      // (the workspace stays on the device)
         rc = ba_trace_begin(ctx, trace, &trace_d);  if (rc) return rc;
-        uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+        uint8_t *hs = st.h, *ds = st.d;
         memset(hs, 0, up_end);
         for (size_t b = 0; b < B; b++) {
             const PgItem &it = items[b];
@@ -806,7 +802,7 @@ int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *
             if (it.n_seg) memcpy(hs + it.o_seg, h.seg.data(), 8 * (size_t)it.n_seg);
             if (it.n_var) memcpy(hs + it.o_seg + 8 * (size_t)it.n_seg, h.vpose.data(), 4 * (size_t)it.n_var);
         }
-        OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, up_end, hipMemcpyHostToDevice, ctx->stream));
+        rc = st.upload(0, up_end);  if (rc) return rc;
         PgArgs a;
         a.arena = ds; a.items = (const PgItem *)ds; a.out = (PgOut *)(ds + o_out);
         a.O = ba_opt_from(*opt); a.initial_radius = opt->initial_radius;
@@ -816,8 +812,8 @@ int ov2_pose_graph_solve_batch(ov2_ctx *ctx, int n_items, const ov2_pg_problem *
         hipLaunchKernelGGL(k_pg_solve, dim3(n_items), dim3(PG_THREADS), 0, ctx->stream, a);
         OV2_HIP_CHECK(hipGetLastError());
         OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[1], ctx->stream));
-        OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, down_end - o_out, hipMemcpyDeviceToHost, ctx->stream));
-        OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        rc = st.download(o_out, down_end, o_out);  if (rc) return rc;
+        rc = st.sync();  if (rc) return rc;
         OV2_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ba_ev[0], ctx->ba_ev[1]));
         hs_c = hs;
     }
@@ -872,18 +868,18 @@ int ov2_pose_graph_apply(ov2_ctx *ctx, int n_win, const double *win_old, const d
     }
     OV2_REQUIRE(ctx, OV2_EINVAL, "NULL context");
     if (n_young + n_pts == 0) return OV2_OK;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
     // staging: [win_old][win_new][young_old][xyz][pt_kf] up, [young_new][xyz_out] down
     const size_t W = 56 * (size_t)n_win, Y = 56 * (size_t)n_young, X = 24 * (size_t)n_pts;
-    const size_t o_wo = 0, o_wn = pg_al(o_wo + W), o_yo = pg_al(o_wn + W), o_x = pg_al(o_yo + Y), o_kf = pg_al(o_x + X);
-    const size_t o_yn = pg_al(o_kf + 4 * (size_t)n_pts), o_xo = pg_al(o_yn + Y), total = pg_al(o_xo + X);
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor c(16);
+    const size_t o_wo = c.take(W), o_wn = c.take(W), o_yo = c.take(Y), o_x = c.take(X), o_kf = c.take(4 * (size_t)n_pts);
+    const size_t o_yn = c.take(Y), o_xo = c.take(X), total = c.off;
+    Stage st;
+    int rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     if (n_win) { memcpy(hs + o_wo, win_old, W); memcpy(hs + o_wn, win_new, W); }
     if (n_young) memcpy(hs + o_yo, young_old, Y);
     if (n_pts) { memcpy(hs + o_x, xyz, X); memcpy(hs + o_kf, pt_kf, 4 * (size_t)n_pts); }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_yn, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, o_yn);  if (rc) return rc;
     PgApply a{};
     a.n_win = n_win; a.n_young = n_young; a.n_pts = n_pts;
     a.win_old = (const double *)(ds + o_wo); a.win_new = (const double *)(ds + o_wn); a.young_old = (const double *)(ds + o_yo);
@@ -892,8 +888,8 @@ int ov2_pose_graph_apply(ov2_ctx *ctx, int n_win, const double *win_old, const d
     const long long lanes = (long long)n_young + n_pts;
     hipLaunchKernelGGL(k_pg_apply, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, ctx->stream, a);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_yn, ds + o_yn, total - o_yn, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_yn, total, o_yn);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     if (n_young) memcpy(young_new, hs + o_yn, Y);
     if (n_pts) memcpy(xyz_out, hs + o_xo, X);
     return OV2_OK;

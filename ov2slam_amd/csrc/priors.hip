@@ -120,8 +120,6 @@ int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double
     return OV2_OK;
 }
 
-static inline size_t pri_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // the camera of either params struct: the model, a coefficient count it takes, a positive image size
 template <class Params>
 static int pri_check_camera(const Params *params)
@@ -175,12 +173,12 @@ static int pri_frame_run(ov2_ctx *ctx, const ov2_klt_priors_params *params, int 
     if (rc) return rc;
     // staging: [items 16 B][Tcw 56 B] per item, [px 8][wpt 24][is3d 1] per keypoint, then the outputs [prior 8][has_prior 1]
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_T = pri_al(o_it + sizeof(PriItemD) * B), o_px = pri_al(o_T + 56 * B), o_w = pri_al(o_px + 8 * N);
-    const size_t o_3d = pri_al(o_w + 24 * N), o_out = pri_al(o_3d + N), o_hp = pri_al(o_out + 8 * N), total = pri_al(o_hp + N);
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor sc(16);
+    const size_t o_it = sc.take(sizeof(PriItemD) * B), o_T = sc.take(56 * B), o_px = sc.take(8 * N), o_w = sc.take(24 * N), o_3d = sc.take(N);
+    const size_t o_out = sc.take(8 * N), o_hp = sc.take(N), total = sc.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t p0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_klt_priors_item &k = items[b];
@@ -196,14 +194,14 @@ static int pri_frame_run(ov2_ctx *ctx, const ov2_klt_priors_params *params, int 
         p0 += n;
     }
     if (n_max > 0) {
-        OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+        rc = st.upload(0, o_out);  if (rc) return rc;
         rc = ov2_launch_prior_frame(ctx->stream, c, params->img_w, params->img_h, params->klt_use_prior, ds + o_it, (const double *)(ds + o_T),
                                     (const float *)(ds + o_px), ds + o_3d, (const double *)(ds + o_w), (float *)(ds + o_out), ds + o_hp,
                                     n_max, n_items);
         if (rc) return rc;
-        OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
+        rc = st.download(o_out, total, o_out);  if (rc) return rc;
     }
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.sync();  if (rc) return rc;
     p0 = 0;
     for (int b = 0; b < n_items; b++) {
         const size_t n = (size_t)items[b].n;
@@ -282,14 +280,13 @@ static int pri_stereo_run(ov2_ctx *ctx, const ov2_stereo_priors_params *params, 
     // staging: [items 16 B][Tcw 56 B] per item, [px 8][unpx 8][bv 24][wpt 24][state 1] per keypoint, [cell_start 4] per cell + 1,
     // [cell_kp 4], then the outputs [prior 8][has_prior 1][skip 1]
     const size_t CS = B * (ncells + 1);
-    const size_t o_it = 0, o_T = pri_al(o_it + sizeof(PriItemD) * B), o_px = pri_al(o_T + 56 * B), o_un = pri_al(o_px + 8 * N);
-    const size_t o_bv = pri_al(o_un + 8 * N), o_w = pri_al(o_bv + 24 * N), o_st = pri_al(o_w + 24 * N), o_cs = pri_al(o_st + N);
-    const size_t o_ck = pri_al(o_cs + 4 * CS), o_out = pri_al(o_ck + 4 * NCK), o_hp = pri_al(o_out + 8 * N), o_sk = pri_al(o_hp + N);
-    const size_t total = pri_al(o_sk + N);
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor sc(16);
+    const size_t o_it = sc.take(sizeof(PriItemD) * B), o_T = sc.take(56 * B), o_px = sc.take(8 * N), o_un = sc.take(8 * N), o_bv = sc.take(24 * N);
+    const size_t o_w = sc.take(24 * N), o_st = sc.take(N), o_cs = sc.take(4 * CS), o_ck = sc.take(4 * NCK);
+    const size_t o_out = sc.take(8 * N), o_hp = sc.take(N), o_sk = sc.take(N), total = sc.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t p0 = 0, ck0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_stereo_priors_item &k = items[b];
@@ -310,16 +307,16 @@ static int pri_stereo_run(ov2_ctx *ctx, const ov2_stereo_priors_params *params, 
         p0 += n; ck0 += n_ck;
     }
     if (n_max > 0) {
-        OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+        rc = st.upload(0, o_out);  if (rc) return rc;
         hipLaunchKernelGGL(k_prior_stereo, dim3((n_max + PRI_THREADS - 1) / PRI_THREADS, n_items), dim3(PRI_THREADS), 0, ctx->stream, c, Tr,
                            params->img_w, params->img_h, (float)params->ncellsize, nbw, nbh, rect ? 1 : 0, (const PriItemD *)(ds + o_it),
                            (const double *)(ds + o_T), (const float2 *)(ds + o_px), (const float2 *)(ds + o_un), (const double *)(ds + o_bv),
                            (const double *)(ds + o_w), (const uint8_t *)(ds + o_st), (const int *)(ds + o_cs), (const int *)(ds + o_ck),
                            (float2 *)(ds + o_out), ds + o_hp, ds + o_sk);
         OV2_HIP_CHECK(hipGetLastError());
-        OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
+        rc = st.download(o_out, total, o_out);  if (rc) return rc;
     }
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.sync();  if (rc) return rc;
     p0 = 0;
     for (int b = 0; b < n_items; b++) {
         const size_t n = (size_t)items[b].n;

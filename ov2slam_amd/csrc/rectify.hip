@@ -132,8 +132,6 @@ int ov2_launch_remap(hipStream_t stream, const ov2_rectmap *m, const uint8_t *sr
     return OV2_OK;
 }
 
-static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 extern "C" {
 

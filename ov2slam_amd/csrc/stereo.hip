@@ -157,23 +157,23 @@ int ov2_line_min_sad(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, in
     OV2_REQUIRE(left->d.lv[level].w == right->d.lv[level].w && left->d.lv[level].h == right->d.lv[level].h, OV2_EINVAL,
                 "left/right level size differs");
     OV2_REQUIRE(nwinsize > 0 && nwinsize <= 9, OV2_EUNSUPPORTED, "getLineMinSAD window up to 9 (the reference uses 7)");
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    // layout: [pts 8n][xprior 4n][l1err 4n], packed
+    StageCursor sc(1);
+    const size_t o_p = sc.take(8 * (size_t)n), o_x = sc.take(4 * (size_t)n), o_l = sc.take(4 * (size_t)n), total = sc.off;
+    Stage st;
+    int rc = st.open(ctx, total, total);  if (rc) return rc;
     if (int rcw = ov2_pyr_wait_ready(ctx, left)) return rcw;       // e.g. the front-end's left pyramid read by the mapper's context
     if (int rcw = ov2_pyr_wait_ready(ctx, right)) return rcw;
-    // layout: [pts 8n][xprior 4n][l1err 4n]
-    const size_t total = 16 * (size_t)n;
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
-    memcpy(hs, pts_xy_h, 8 * (size_t)n);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    uint8_t *hs = st.h, *ds = st.d;
+    memcpy(hs + o_p, pts_xy_h, 8 * (size_t)n);
+    rc = st.upload(o_p, o_x);  if (rc) return rc;
     hipLaunchKernelGGL(k_line_min_sad, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, left->d, right->d, level, nwinsize, go_left ? 1 : 0,
-                       (const float2 *)ds, n, (float *)(ds + 8 * (size_t)n), (float *)(ds + 12 * (size_t)n), (const int *)nullptr);
+                       (const float2 *)(ds + o_p), n, (float *)(ds + o_x), (float *)(ds + o_l), (const int *)nullptr);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + 8 * (size_t)n, ds + 8 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    memcpy(xprior_h, hs + 8 * (size_t)n, 4 * (size_t)n);
-    memcpy(l1err_h, hs + 12 * (size_t)n, 4 * (size_t)n);
+    rc = st.download(o_x, total, o_x);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
+    memcpy(xprior_h, hs + o_x, 4 * (size_t)n);
+    memcpy(l1err_h, hs + o_l, 4 * (size_t)n);
     return OV2_OK;
 }
 
@@ -191,20 +191,21 @@ int ov2_stereo_epipolar_check(ov2_ctx *ctx, int rect, const double Frl[9], int m
     EpiParams E;
     for (int i = 0; i < 9; i++) E.F[i] = Frl ? Frl[i] : 0.;
     E.rect = rect ? 1 : 0;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    // layout: [lunpx 8n][rkps 8n][runpx 8n][err 4n][ok n]
-    const size_t N = (size_t)n, o_l = 0, o_r = 8 * N, o_u = 16 * N, o_e = 24 * N, o_k = 28 * N, total = 29 * N;
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    // layout: [lunpx 8n][rkps 8n][runpx 8n][err 4n][ok n], packed
+    const size_t N = (size_t)n;
+    StageCursor sc(1);
+    const size_t o_l = sc.take(8 * N), o_r = sc.take(8 * N), o_u = sc.take(8 * N), o_e = sc.take(4 * N), o_k = sc.take(N), total = sc.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     memcpy(hs + o_l, lunpx_xy_h, 8 * N);
     memcpy(hs + o_r, rkps_xy_inout_h, 8 * N);
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, 16 * N, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(o_l, o_u);  if (rc) return rc;
     hipLaunchKernelGGL(k_epipolar_check, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, E, c, (const float2 *)(ds + o_l),
                        (float2 *)(ds + o_r), n, (float2 *)(ds + o_u), (float *)(ds + o_e), ds + o_k, (const int *)nullptr);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_r, ds + o_r, total - o_r, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_r, total, o_r);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     memcpy(rkps_xy_inout_h, hs + o_r, 8 * N);
     if (runpx_xy_h) memcpy(runpx_xy_h, hs + o_u, 8 * N);
     if (epi_err_h) memcpy(epi_err_h, hs + o_e, 4 * N);
@@ -233,16 +234,18 @@ int ov2_stereo_match(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, in
     EpiParams E;
     for (int i = 0; i < 9; i++) E.F[i] = Frl ? Frl[i] : 0.;
     E.rect = rect ? 1 : 0;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    // layout: [kps 8n][unpx 8n][pri 8n][pts_top 8n][out 8n][runpx 8n][sadx 4n][l1 4n][err 4n][flags n][st n][ok n], packed
+    const size_t N = (size_t)n;
+    StageCursor sc(1);
+    const size_t o_k = sc.take(8 * N), o_u = sc.take(8 * N), o_p = sc.take(8 * N), o_t = sc.take(8 * N), o_o = sc.take(8 * N), o_r = sc.take(8 * N);
+    const size_t o_s = sc.take(4 * N), o_l = sc.take(4 * N), o_e = sc.take(4 * N), o_f = sc.take(N), o_st = sc.take(N), o_ok = sc.take(N);
+    const size_t total = sc.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
     if (int rcw = ov2_pyr_wait_ready(ctx, left)) return rcw;
     if (int rcw = ov2_pyr_wait_ready(ctx, right)) return rcw;
     const int lvl = nklt_pyr_lvl > left->d.n_levels - 1 ? left->d.n_levels - 1 : (nklt_pyr_lvl < 0 ? 0 : nklt_pyr_lvl);
-    // layout: [kps 8n][unpx 8n][pri 8n][pts_top 8n][out 8n][runpx 8n][sadx 4n][l1 4n][err 4n][flags n][st n][ok n]
-    const size_t N = (size_t)n, o_k = 0, o_u = 8 * N, o_p = 16 * N, o_t = 24 * N, o_o = 32 * N, o_r = 40 * N, o_s = 48 * N, o_l = 52 * N,
-                 o_e = 56 * N, o_f = 60 * N, o_st = 61 * N, o_ok = 62 * N, total = 63 * N;
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    uint8_t *hs = st.h, *ds = st.d;
     memcpy(hs + o_k, kps_px_h, 8 * N);
     memcpy(hs + o_u, kps_unpx_h, 8 * N);
     const float up = (float)(1 << lvl), down = 1.f / up;                  // pow(2, nklt_pyr_lvl) and its inverse (:417-418)
@@ -254,8 +257,8 @@ int ov2_stereo_match(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, in
         ((float *)(hs + o_t))[2 * i] = kps_px_h[2 * i] * down;             // the keypoint on the coarsest level (:427)
         ((float *)(hs + o_t))[2 * i + 1] = kps_px_h[2 * i + 1] * down;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, 32 * N, hipMemcpyHostToDevice, ctx->stream));
-    OV2_HIP_CHECK(hipMemcpyAsync(ds + o_f, hs + o_f, N, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(o_k, o_o);  if (rc) return rc;
+    rc = st.upload(o_f, o_st);  if (rc) return rc;
     const float *sad_d = nullptr;
     if (rect) {
         hipLaunchKernelGGL(k_line_min_sad, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, left->d, right->d, lvl, 7, 1,
@@ -273,9 +276,9 @@ int ov2_stereo_match(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, in
     hipLaunchKernelGGL(k_epipolar_check, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, E, c, (const float2 *)(ds + o_u),
                        (float2 *)(ds + o_o), n, (float2 *)(ds + o_r), (float *)(ds + o_e), ds + o_ok, (const int *)nullptr);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_o, ds + o_o, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_st, ds + o_st, 2 * N, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_o, o_r, o_o);  if (rc) return rc;
+    rc = st.download(o_st, total, o_st);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     for (int i = 0; i < n; i++) {
         const bool tracked = (hs[o_st + i] & 1) != 0;
         stereo_ok_h[i] = (tracked && hs[o_ok + i]) ? 1 : 0;
@@ -309,17 +312,20 @@ int ov2_stereo_match_batch(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *rig
     EpiParams E;
     for (int i = 0; i < 9; i++) E.F[i] = Frl ? Frl[i] : 0.;
     E.rect = rect ? 1 : 0;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    // layout (N = n_items * n_max slots): [kps 8N][unpx 8N][pri 8N][pts_top 8N][flags N][counts 4*items, 256-aligned] | [out 8N][runpx 8N][sadx 4N][l1 4N][err 4N][st N][ok N]
+    // packed but for the counts, which start and end on a multiple of 256
+    const size_t N = (size_t)n_items * n_max;
+    StageCursor sc(1);
+    const size_t o_k = sc.take(8 * N), o_u = sc.take(8 * N), o_p = sc.take(8 * N), o_t = sc.take(8 * N), o_f = sc.take(up256(33 * N) - 32 * N);
+    const size_t o_n = sc.take(up256(4 * (size_t)n_items)), in_bytes = sc.off;
+    const size_t o_o = sc.take(8 * N), o_r = sc.take(8 * N), o_s = sc.take(4 * N), o_l = sc.take(4 * N), o_e = sc.take(4 * N), o_st = sc.take(N);
+    const size_t o_ok = sc.take(N), total = sc.off;
+    Stage st;
+    rc = st.open(ctx, total, total);  if (rc) return rc;
     if (int rcw = ov2_pyr_wait_ready(ctx, left)) return rcw;
     if (int rcw = ov2_pyr_wait_ready(ctx, right)) return rcw;
     const int lvl = nklt_pyr_lvl > left->d.n_levels - 1 ? left->d.n_levels - 1 : (nklt_pyr_lvl < 0 ? 0 : nklt_pyr_lvl);
-    // layout (N = n_items * n_max slots): [kps 8N][unpx 8N][pri 8N][pts_top 8N][flags N][counts 4*items, 256-aligned] | [out 8N][runpx 8N][sadx 4N][l1 4N][err 4N][st N][ok N]
-    const size_t N = (size_t)n_items * n_max, o_k = 0, o_u = 8 * N, o_p = 16 * N, o_t = 24 * N, o_f = 32 * N, o_n = (33 * N + 255) & ~(size_t)255;
-    const size_t in_bytes = (o_n + 4 * (size_t)n_items + 255) & ~(size_t)255;
-    const size_t o_o = in_bytes, o_r = o_o + 8 * N, o_s = o_r + 8 * N, o_l = o_s + 4 * N, o_e = o_l + 4 * N, o_st = o_e + 4 * N, o_ok = o_st + N, total = o_ok + N;
-    rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);    if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    uint8_t *hs = st.h, *ds = st.d;
     const float up = (float)(1 << lvl), down = 1.f / up;                  // pow(2, nklt_pyr_lvl) and its inverse (:417-418)
     for (int b = 0; b < n_items; b++) {
         const size_t o = (size_t)b * n_max, n = (size_t)n_h[b];
@@ -335,7 +341,7 @@ int ov2_stereo_match_batch(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *rig
             ((float *)(hs + o_t))[2 * i + 1] = kps_px_h[2 * i + 1] * down;
         }
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(o_k, in_bytes);  if (rc) return rc;
     const int *n_d = (const int *)(ds + o_n);
     if (rect) hipLaunchKernelGGL(k_line_min_sad, dim3((n_max + 3) / 4, n_items), dim3(256), 0, ctx->stream, left->d, right->d, lvl, 7, 1,
                                  (const float2 *)(ds + o_t), n_max, (float *)(ds + o_s), (float *)(ds + o_l), n_d);
@@ -347,9 +353,9 @@ int ov2_stereo_match_batch(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *rig
     hipLaunchKernelGGL(k_epipolar_check, dim3((n_max + 255) / 256, n_items), dim3(256), 0, ctx->stream, E, c, (const float2 *)(ds + o_u),
                        (float2 *)(ds + o_o), n_max, (float2 *)(ds + o_r), (float *)(ds + o_e), ds + o_ok, n_d);
     OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_o, ds + o_o, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_st, ds + o_st, 2 * N, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_o, o_r, o_o);  if (rc) return rc;
+    rc = st.download(o_st, total, o_st);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     for (int b = 0; b < n_items; b++)
         for (size_t i = (size_t)b * n_max; i < (size_t)b * n_max + (size_t)n_h[b]; i++) {
             const bool tracked = (hs[o_st + i] & 1) != 0;

@@ -248,7 +248,6 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
     OV2_REQUIRE(p->n_kf > 0 && p->n_pts >= 0 && p->n_res >= 0, OV2_EINVAL, "bad problem size");
     OV2_REQUIRE(p->poses && (p->n_pts == 0 || p->xyz), OV2_EINVAL, "NULL parameter array");
     OV2_REQUIRE(p->n_res == 0 || (p->res_type && p->res_kf && p->res_pt && p->res_uv && p->res_sigma), OV2_EINVAL, "NULL residual array");
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
     const int n_kf = p->n_kf, n_pts = p->n_pts, n_res = p->n_res;
     // host: validate, build the point -> active residual CSR (ascending residual index inside a point)
     std::vector<int> pt_ptr((size_t)n_pts + 2, 0), pt_res;
@@ -266,19 +265,17 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
         for (int i = 0; i < n_res; i++) if (!p->res_active || p->res_active[i]) pt_res[fill[p->res_pt[i]]++] = i;
     }
     // one device arena, one H2D
-    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += up8(bytes); return o; };
+    StageCursor c(8);
     const size_t N3 = 3 * (size_t)n_pts + 1, NR = (size_t)n_res + 1;
-    const size_t o_poses = take(56 * (size_t)n_kf), o_x = take(8 * N3), o_uv = take(16 * NR), o_sig = take(8 * NR), o_kf = take(4 * NR);
-    const size_t o_type = take(NR), o_ptr = take(4 * ((size_t)n_pts + 2)), o_pres = take(4 * ((size_t)n_act + 1));
-    const size_t h2d = off;
-    const size_t o_rt = take(96 * (size_t)n_kf), o_cand = take(8 * N3), o_g = take(8 * N3), o_scale = take(8 * N3), o_diag = take(8 * N3), o_y = take(8 * N3);
-    const size_t o_jr = take(64 * ((size_t)n_act + 1));
-    const size_t o_chi2 = take(8 * NR), o_dpos = take(NR), o_out = take(sizeof(SbaOut)), total = off;
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    const size_t o_poses = c.take(56 * (size_t)n_kf), o_x = c.take(8 * N3), o_uv = c.take(16 * NR), o_sig = c.take(8 * NR), o_kf = c.take(4 * NR);
+    const size_t o_type = c.take(NR), o_ptr = c.take(4 * ((size_t)n_pts + 2)), o_pres = c.take(4 * ((size_t)n_act + 1));
+    const size_t h2d = c.off;
+    const size_t o_rt = c.take(96 * (size_t)n_kf), o_cand = c.take(8 * N3), o_g = c.take(8 * N3), o_scale = c.take(8 * N3), o_diag = c.take(8 * N3), o_y = c.take(8 * N3);
+    const size_t o_jr = c.take(64 * ((size_t)n_act + 1));
+    const size_t o_chi2 = c.take(8 * NR), o_dpos = c.take(NR), o_out = c.take(sizeof(SbaOut)), total = c.off;
+    Stage st;
+    int rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     memcpy(hs + o_poses, p->poses, 56 * (size_t)n_kf);
     if (n_pts) memcpy(hs + o_x, p->xyz, 24 * (size_t)n_pts);
     if (n_res) {
@@ -292,8 +289,8 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
         ((double *)(hs + o_chi2))[i] = res->chi2_last_eval ? res->chi2_last_eval[i] : 0.0;
         (hs + o_dpos)[i] = res->depthpos_last_eval ? res->depthpos_last_eval[i] : 0;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, h2d, hipMemcpyHostToDevice, ctx->stream));
-    OV2_HIP_CHECK(hipMemcpyAsync(ds + o_chi2, hs + o_chi2, o_out - o_chi2, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, h2d);  if (rc) return rc;
+    rc = st.upload(o_chi2, o_out);  if (rc) return rc;
     SbaDev D;
     D.n_kf = n_kf; D.n_pts = n_pts; D.n_res = n_res;
     D.poses = (const double *)(ds + o_poses); D.kf_rt = (double *)(ds + o_rt);
@@ -312,9 +309,9 @@ int ov2_structure_ba(ov2_ctx *ctx, const ov2_sba_problem *p, const ov2_ba_option
     hipLaunchKernelGGL(k_structure_ba, dim3(1), dim3(1024), 0, ctx->stream, D);
     OV2_HIP_CHECK(hipGetLastError());
     OV2_HIP_CHECK(hipEventRecord(e1, ctx->stream));
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_x, ds + o_x, 8 * N3, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipMemcpyAsync(hs + o_chi2, ds + o_chi2, total - o_chi2, hipMemcpyDeviceToHost, ctx->stream));
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.download(o_x, o_x + 8 * N3, o_x);  if (rc) return rc;
+    rc = st.download(o_chi2, total, o_chi2);  if (rc) return rc;
+    rc = st.sync();  if (rc) return rc;
     float ms = 0;
     OV2_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     if (res->xyz_out && n_pts) memcpy(res->xyz_out, hs + o_x, 24 * (size_t)n_pts);

@@ -40,7 +40,6 @@ struct ov2_tracker {
     bool graph_ok = false;
 };
 
-static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // preprocessImage body for pyramid `dst` (no swap, no event): frame H2D (+ rectifyImage) + CLAHE / level-0 copy + coarser levels
 static int enqueue_preprocess(ov2_tracker *t, ov2_pyr *dst)

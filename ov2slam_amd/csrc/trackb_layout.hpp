@@ -5,13 +5,11 @@
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
 #include <stddef.h>
+#include "stage.hpp"
 
 #define BT_POSE_OUT_BYTES 168       // sizeof(PoseOut), sizeof(EpifOut), sizeof(FeKfHdr): trackb.hip asserts all three
 #define BT_EPIF_OUT_BYTES 304
 #define BT_KF_HDR_BYTES 120
-
-static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // frames: row pitch and bytes of one item in the staging sets
 static inline size_t bt_img_pitch(int w) { return up16((size_t)w); }

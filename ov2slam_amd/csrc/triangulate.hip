@@ -124,8 +124,6 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_triangulate(TriParams P, const in
     invdepth[i] = inv;
 }
 
-static inline size_t tri_al(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, int n_items, const ov2_tri_keyframe *kfs,
                                    ov2_tri_result *results)
 {
@@ -175,17 +173,16 @@ int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, i
         const TriD3 c{qv.y * uv.z - qv.z * uv.y, qv.z * uv.x - qv.x * uv.z, qv.x * uv.y - qv.y * uv.x};
         P.Trl = TriSE3{TriD3{(p.x + qi.w * uv.x) + c.x, (p.y + qi.w * uv.y) + c.y, (p.z + qi.w * uv.z) + c.z}, qi};
     }
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
     // staging: [items 16B][Twc 56B][source table 112B] [unpx 8][bv 24][runpx 8][rbv 24][src_unpx 8][src_bv 24][src 4][stereo 1] per point,
     // then the outputs [status 1][wpt 24][invdepth 8] per point; every section 16-byte aligned
     const size_t B = (size_t)n_items;
-    const size_t o_it = 0, o_tw = tri_al(o_it + 16 * B), o_st = tri_al(o_tw + 56 * B), o_u = tri_al(o_st + 112 * S);
-    const size_t o_b = tri_al(o_u + 8 * N), o_ru = tri_al(o_b + 24 * N), o_rb = tri_al(o_ru + 8 * N), o_su = tri_al(o_rb + 24 * N);
-    const size_t o_sb = tri_al(o_su + 8 * N), o_s = tri_al(o_sb + 24 * N), o_fl = tri_al(o_s + 4 * N), o_out = tri_al(o_fl + N);
-    const size_t o_w = tri_al(o_out + N), o_inv = tri_al(o_w + 24 * N), total = tri_al(o_inv + 8 * N);
-    int rc = ctx->reserve_device(total);  if (rc) return rc;
-    rc = ctx->reserve_host(total);        if (rc) return rc;
-    uint8_t *hs = (uint8_t *)ctx->h_scratch, *ds = (uint8_t *)ctx->d_scratch;
+    StageCursor c(16);
+    const size_t o_it = c.take(16 * B), o_tw = c.take(56 * B), o_st = c.take(112 * S), o_u = c.take(8 * N), o_b = c.take(24 * N);
+    const size_t o_ru = c.take(8 * N), o_rb = c.take(24 * N), o_su = c.take(8 * N), o_sb = c.take(24 * N), o_s = c.take(4 * N), o_fl = c.take(N);
+    const size_t o_out = c.take(N), o_w = c.take(24 * N), o_inv = c.take(8 * N), total = c.off;
+    Stage st;
+    int rc = st.open(ctx, total, total);  if (rc) return rc;
+    uint8_t *hs = st.h, *ds = st.d;
     size_t p0 = 0, s0 = 0;
     for (int b = 0; b < n_items; b++) {
         const ov2_tri_keyframe &k = kfs[b];
@@ -209,7 +206,7 @@ int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, i
         }
         p0 += n; s0 += m;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, ctx->stream));
+    rc = st.upload(0, o_out);  if (rc) return rc;
     if (n_max > 0) {
         hipLaunchKernelGGL(k_triangulate, dim3((n_max + TRI_BLOCK - 1) / TRI_BLOCK, n_items), dim3(TRI_BLOCK), 0, ctx->stream, P,
                            (const int4 *)(ds + o_it), (const double *)(ds + o_tw), (const double *)(ds + o_st), (const float2 *)(ds + o_u),
@@ -217,9 +214,9 @@ int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, i
                            (const double *)(ds + o_sb), (const int *)(ds + o_s), (const uint8_t *)(ds + o_fl), ds + o_out,
                            (double *)(ds + o_w), (double *)(ds + o_inv));
         OV2_HIP_CHECK(hipGetLastError());
-        OV2_HIP_CHECK(hipMemcpyAsync(hs + o_out, ds + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
+        rc = st.download(o_out, total, o_out);  if (rc) return rc;
     }
-    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    rc = st.sync();  if (rc) return rc;
     p0 = 0;
     for (int b = 0; b < n_items; b++) {
         const size_t n = (size_t)kfs[b].n;

@@ -217,6 +217,19 @@ def test_batch_returns_the_bytes_of_the_single_calls(gpu_ctx):
         for f in ("iterations", "num_successful_steps", "termination", "initial_cost", "final_cost"):
             assert s[f] == x[f] == y[f], f
         assert s["poses"].tobytes() == x["poses"].tobytes() == y["poses"].tobytes()
+    # items with nothing to solve beside one that is solved: no pose at all, one pose (no edge can touch it), 17 poses
+    one = case("far", 17)["prob"]
+    none = dict(poses=np.zeros((0, 7)), pose_const=np.zeros(0, np.uint8), edge_i=np.zeros(0, np.int32), edge_j=np.zeros(0, np.int32),
+                edge_T=np.zeros((0, 7)))
+    lone = dict(none, poses=one["poses"][:1], pose_const=np.zeros(1, np.uint8))
+    for probs in ([none, lone, one], [one, none]):
+        for p, x in zip(probs, O.pose_graph_batch(gpu_ctx, probs, opts)):
+            s = O.pose_graph(gpu_ctx, p, opts)
+            for f in ("iterations", "num_successful_steps", "termination", "initial_cost", "final_cost"):
+                assert s[f] == x[f], f
+            assert s["poses"].tobytes() == x["poses"].tobytes() and len(x["poses"]) == len(p["poses"])
+            if p is not one:
+                assert x["iterations"] == 0 and x["termination"] == R.TERM_FUNCTION_TOL and np.array_equal(x["poses"], p["poses"])
     assert O.pose_graph_batch(gpu_ctx, [], opts) == []
 
 
