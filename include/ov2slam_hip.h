@@ -2133,7 +2133,8 @@ int  ov2_motion_update_batch(ov2_ctx *ctx, int n, const ov2_motion_state *state_
  * in front of the step of f18 (doepipolar: 1) or f16 (doepipolar: 0), and behind it updateMotionModel and checkNewKfReq, one enqueue
  * and one synchronisation.  The caller hands over images, keypoints, map points and a timestamp and gets the tracked frame, the
  * filter's record, the pose and the keyframe request; it does no pose arithmetic.  What remains with it per frame is the map (which
- * slots exist) and createKeyframe.
+ * slots exist) and createKeyframe.  (Since f20 createKeyframe has a lock-step form too: ov2_btracker_create_keyframe, at the end of this
+ * header, takes this step's kf.decision.)
  *
  * RESIDENT ON THE DEVICE per item, mirrored on the host: the frame pose (pcurframe_->Twc_; the identity at first), the
  * ov2_motion_state (reset() at first) and the keyframe's id_, img_time_ and nb3dkps_ next to the keyframe arrays of
@@ -2206,6 +2207,95 @@ int  ov2_btracker_track_mono(ov2_btracker *t, int n_active, const uint8_t *const
                              const ov2_track_mono_params *params, const ov2_track_mono_input *input, float *out_xy_h, uint8_t *status_h,
                              int *p3p_req, ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
                              ov2_track_mono_result *mono_results);
+
+/* MapManager::createKeyframe for the items of a lock-step batch that were asked to become keyframes (f20; src/map_manager.cpp:44-61,
+ * :286-362): what VisualFrontEnd::visualTracking does after trackMono returned true, in ONE enqueue on the context's stream and ONE
+ * synchronisation, with nothing visiting the host in between.  It replaces, per keyframe round, ov2_btracker_describe_brief of the
+ * frame, the occupied-cell count, ov2_btracker_detect_singlescale / _grid_fast, ov2_btracker_describe_brief of the new points,
+ * ov2_compute_keypoints, a sort by lmid on the host and ov2_btracker_set_keyframe + ov2_btracker_set_keyframe_info ONCE PER ITEM --
+ * and returns byte for byte what that route returns and installs (tests/test_gpu_createkf.py; tests/createkf_ref.py is the route).
+ *
+ * input, in slot layout with cfg.n_max slots per item: px_h / lmid_h / is3d_h / n_h are the current frame AFTER all of the step's
+ * removals and after prepareFrame.  prepareFrame's filter (:267-284) walks vgridkps_ in insertion order and needs the map's
+ * observation counts, so it stays with the caller.  make_kf_h: one byte per item, normally mono_results[b].kf.decision.  nlmid_h:
+ * MapManager::nlmid_ per item; nkfid_h / time_h: the id and img_time_ the keyframe gets.  Twc_h: 7 doubles per item, NULL: the
+ * resident pose of f19.  quality_inout (single scale) or fast_th_inout (grid FAST): the per-item adaptive state; the pointer must
+ * stay valid until _end, which updates it.
+ *
+ * Per flagged item, on the device, in the reference's order:
+ *   k_ckf_prepare   (csrc/createkf.hip) noccupcells as Frame::addKeypointToGrid leaves it -- Frame::getKeypointCellIdx on the grid of
+ *                   params, the counting of ov2_kf_decision -- and nb3dkps from is3d; nb2detect = nbmaxkps - noccupcells.
+ *   detection       if nb2detect > 0: detectSingleScale / detectGridFAST on level 0 of the current pyramid with the frame's
+ *                   keypoints as the occupied set -- the three launches of the detectors with cell det_cell, the count left on the
+ *                   device.  An item that is not flagged or has nb2detect <= 0 carries a skip byte: its work-groups leave at once.
+ *   k_ckf_append    addKeypointsToFrame: the new points behind slot n_prev in the detector's output order, lmid = nlmid + k,
+ *                   is3d = 0, colour = level 0 at ((int)y, (int)x).
+ *   computeKeypoint unpx / bv of ALL slots of the new frame (k_compute_keypoints); needs ov2_btracker_set_calibration.
+ *   describeBRIEF   with use_brief != 0: k_brief32 over the n_prev + n_new points on the step's RAW frame, under the conditions of
+ *                   ov2_btracker_describe_brief (an invalid descriptor: 32 zero bytes, valid = 0).  use_brief == 0: no BRIEF runs.
+ *   k_ckf_install   addKeyframe as far as the tracker holds it: lmid / unpx / bv sorted strictly ascending by lmid into the arrays
+ *                   ov2_btracker_set_keyframe writes, the header {n_kf, kf_Twc, its inverse}, {nkfid, nb3dkps, has_info = 1} and
+ *                   time where ov2_btracker_set_keyframe_info writes.  The new frame becomes the item's resident keyframe without
+ *                   leaving the device; _end brings the host mirrors (the 33 % rule's re-run, the get_ calls) to the same state.
+ * The tracker's first frame (n_h = 0 everywhere) runs all of it on empty frames.
+ *
+ * results[b].action:
+ *   OV2_CKF_NOT_REQUESTED  make_kf_h[b] == 0.  Nothing of the item is written but this action: the resident keyframe, its info, the
+ *                          adaptive state and the output slots are untouched.
+ *   OV2_CKF_CREATED        the record is complete; slots [0, n_kf) of out_px_h / out_lmid_h / unpx_h / bv_h (and desc_h / valid_h
+ *                          with use_brief) hold the new frame in slot order, slots [n_prev, n_kf) of color_h the new points' colour.
+ *   OV2_CKF_OVERFLOW       n_prev + n_new > cfg.n_max.   } the record is filled (n_new is the true count), nothing else of the item
+ *   OV2_CKF_DUP_LMID       lmid_h repeats an id.         } is written, the resident keyframe and its info stay as they were; the
+ *                          caller falls back to the separate calls for that item.
+ * The adaptive state is updated from the detector's counters by the reference's rules for every flagged item whose detection ran
+ * (nb2detect > 0, also with OVERFLOW / DUP_LMID) and for no other item.
+ *
+ * OV2_EINVAL, checked on the host before anything is enqueued (the tracker stays where it was): NULL tracker / params / input /
+ * px_h / lmid_h / is3d_h / n_h / make_kf_h / nlmid_h / nkfid_h / time_h / the detector's state array; n_active outside [1, batch] or
+ * beyond the items of the current step; n_h[b] outside [0, cfg.n_max]; a step or another call of this kind open; no current raw
+ * frames; no calibration; a grid ov2_kf_decision refuses or a cell the detectors refuse (OV2_EUNSUPPORTED where they say so);
+ * cfg.n_max > OV2_FKF_MAX_POINTS; on a flagged item lmid_h[i] < 0 or >= nlmid_h[b] (the reference's counter is monotone), a
+ * non-finite time_h / Twc_h; nlmid_h[b] + 2 * cells overflowing int; Twc_h == NULL on a tracker without a resident pose block;
+ * detector OV2_CKF_DET_GFTT (detectGFTT is not fused); a mask_mode the detector refuses.  In _end: no open call, a NULL result array
+ * or output array.  Between _begin and _end the calls that change the tracker's resident state or start a step return OV2_EINVAL. */
+#define OV2_CKF_DET_SINGLESCALE 0
+#define OV2_CKF_DET_GRID_FAST   1
+#define OV2_CKF_DET_GFTT        2
+enum { OV2_CKF_NOT_REQUESTED = 0, OV2_CKF_CREATED = 1, OV2_CKF_OVERFLOW = 2, OV2_CKF_DUP_LMID = 3 };
+typedef struct {
+    int ncellsize, nbwcells, nbhcells, nbmaxkps;   /* the frame's grid, as ov2_fkf_params carries it                          */
+    int detector;                     /* OV2_CKF_DET_*                                                                       */
+    int det_cell;                     /* the detector's cell size (nmaxdist_)                                                */
+    int roi[4];                       /* single scale: x, y, w, h as ov2_detect_singlescale takes it                         */
+    int mask_mode;                    /* grid FAST: OV2_MASK_*                                                               */
+    int do_subpix;
+    int use_brief;                    /* SlamParams::use_brief_                                                              */
+} ov2_create_keyframe_params;
+typedef struct {
+    const float *px_h;                /* 2 per slot                                                                          */
+    const int *lmid_h;                /* 1 per slot                                                                          */
+    const uint8_t *is3d_h;            /* 1 per slot                                                                          */
+    const int *n_h;                   /* 1 per item                                                                          */
+    const uint8_t *make_kf_h;         /* 1 per item                                                                          */
+    const int *nlmid_h;               /* 1 per item: MapManager::nlmid_                                                      */
+    const int *nkfid_h;               /* 1 per item: the keyframe's id                                                       */
+    const double *time_h;             /* 1 per item: img_time_                                                               */
+    const double *Twc_h;              /* 7 per item; NULL: the resident pose                                                 */
+    double *quality_inout;            /* 1 per item, single scale: dmaxquality_                                              */
+    int *fast_th_inout;               /* 1 per item, grid FAST: nfast_th_                                                    */
+} ov2_create_keyframe_input;
+typedef struct {
+    int action;                       /* OV2_CKF_*                                                                           */
+    int n_prev, noccupcells, nb2detect, n_new, n_kf, nb3dkps;
+    int pad;
+} ov2_create_keyframe_result;
+int  ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_create_keyframe_params *params,
+                                        const ov2_create_keyframe_input *input);
+int  ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result *results, float *out_px_h, int *out_lmid_h,
+                                      float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h);
+int  ov2_btracker_create_keyframe(ov2_btracker *t, int n_active, const ov2_create_keyframe_params *params,
+                                  const ov2_create_keyframe_input *input, ov2_create_keyframe_result *results, float *out_px_h,
+                                  int *out_lmid_h, float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h);
 
 #ifdef __cplusplus
 }

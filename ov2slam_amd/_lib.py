@@ -46,6 +46,8 @@ OV2_FKF_AVG, OV2_FKF_MEDIAN, OV2_FKF_AVG_WIDE = 0, 1, 2
 OV2_KF_C0, OV2_KF_C1, OV2_KF_C2, OV2_KF_CX = 1, 2, 4, 8
 OV2_KF_RET_FEW_CELLS, OV2_KF_RET_FEW_3D, OV2_KF_RET_MANY_3D, OV2_KF_RET_TIME, OV2_KF_NONFINITE = 16, 32, 64, 128, 256
 OV2_KF_FIRST_FRAME, OV2_KF_NO_KEYFRAME = 512, 1024      # ov2_btracker_track_mono
+OV2_CKF_DET_SINGLESCALE, OV2_CKF_DET_GRID_FAST, OV2_CKF_DET_GFTT = 0, 1, 2             # ov2_btracker_create_keyframe
+OV2_CKF_NOT_REQUESTED, OV2_CKF_CREATED, OV2_CKF_OVERFLOW, OV2_CKF_DUP_LMID = 0, 1, 2, 3
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -457,6 +459,26 @@ class TrackMonoResult(C.Structure):
     _fields_ = [("Twc_pred", C.c_double * 7), ("resynced", C.c_int), ("state", MotionState), ("kf", KfDecisionResult)]
 
 
+class CreateKeyframeParams(C.Structure):
+    """ov2_create_keyframe_params"""
+    _fields_ = [("ncellsize", C.c_int), ("nbwcells", C.c_int), ("nbhcells", C.c_int), ("nbmaxkps", C.c_int), ("detector", C.c_int),
+                ("det_cell", C.c_int), ("roi", C.c_int * 4), ("mask_mode", C.c_int), ("do_subpix", C.c_int), ("use_brief", C.c_int)]
+
+
+class CreateKeyframeInput(C.Structure):
+    """ov2_create_keyframe_input"""
+    _fields_ = [("px_h", C.POINTER(C.c_float)), ("lmid_h", C.POINTER(C.c_int)), ("is3d_h", C.POINTER(C.c_uint8)), ("n_h", C.POINTER(C.c_int)),
+                ("make_kf_h", C.POINTER(C.c_uint8)), ("nlmid_h", C.POINTER(C.c_int)), ("nkfid_h", C.POINTER(C.c_int)),
+                ("time_h", C.POINTER(C.c_double)), ("Twc_h", C.POINTER(C.c_double)), ("quality_inout", C.POINTER(C.c_double)),
+                ("fast_th_inout", C.POINTER(C.c_int))]
+
+
+class CreateKeyframeResult(C.Structure):
+    """ov2_create_keyframe_result"""
+    _fields_ = [("action", C.c_int), ("n_prev", C.c_int), ("noccupcells", C.c_int), ("nb2detect", C.c_int), ("n_new", C.c_int),
+                ("n_kf", C.c_int), ("nb3dkps", C.c_int), ("pad", C.c_int)]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -673,6 +695,10 @@ SIGNATURES = {
     "ov2_btracker_track_mono_end": (_i, [_vp, _vp, _vp, _vp, C.POINTER(EpifilterResult), C.POINTER(PoseResult), C.POINTER(TrackMonoResult)]),
     "ov2_btracker_track_mono": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(TrackMonoParams), C.POINTER(TrackMonoInput),
                                      _vp, _vp, _vp, C.POINTER(EpifilterResult), C.POINTER(PoseResult), C.POINTER(TrackMonoResult)]),
+    "ov2_btracker_create_keyframe_begin": (_i, [_vp, _i, C.POINTER(CreateKeyframeParams), C.POINTER(CreateKeyframeInput)]),
+    "ov2_btracker_create_keyframe_end": (_i, [_vp, C.POINTER(CreateKeyframeResult), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ov2_btracker_create_keyframe": (_i, [_vp, _i, C.POINTER(CreateKeyframeParams), C.POINTER(CreateKeyframeInput),
+                                          C.POINTER(CreateKeyframeResult), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

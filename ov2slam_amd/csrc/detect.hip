@@ -20,6 +20,7 @@
 //   3. k_corner_subpix : cv::cornerSubPix, one wavefront per point (parallel patch, ordered accumulation).
 #include "common.hpp"
 #include "detect_plan.hpp"        // size constants, launch geometry, LDS bytes, scratch layouts, adaptation rules, geometry check
+#include "detect_dev.hpp"         // CellCand, DetBatch, SelectOut; enqueue_detect for trackb.hip
 #include <limits.h>
 #include <float.h>
 #include <math.h>
@@ -45,23 +46,8 @@ __device__ __forceinline__ int d_reflect101(int p, int len)
 // An exclusion mask only ever removes candidates (masked responses become 0), so when p1 (p2) is positive and its mask bit is
 // still set when the sweep reaches the cell, it IS the masked arg-max -- the sweep then costs two LDS bit tests per cell instead
 // of a load batch and two arg-max passes, and falls back to the full scan otherwise.
-struct CellCand { int p1; float v1; int p2; float v2; };      // p = lx | ly << 16 (cell-local pixel), -1: none
-static_assert(sizeof(CellCand) == DET_CAND_BYTES, "detect_plan.hpp lays out the scratch with this size");
-
-// Batched launches (one image per batch item of a pyramid, ov2_detect_*_batch_d): per-item strides and parameters; everything
-// zero / NULL for a single image.  The cell kernels run ncells work-groups per item, the selection one work-group per item,
-// the sub-pixel refinement a wavefront per (output slot, item).
-struct DetBatch {
-    long long img_stride;      // bytes between the items' images
-    int ncells;                // cells per image
-    int cur_stride;            // float2 entries between the items' current-keypoint lists
-    int out_stride;            // float2 entries between the items' output lists
-    const int *ncur;           // per-item number of current keypoints   (NULL: ncur_all)
-    const float2 *cur;         // item 0's current keypoints (the cell kernels skip occupied cells like the reference's loop does)
-    int ncur_all;              // number of current keypoints when ncur == NULL
-    const int *fast_th;        // per-item FAST threshold                (NULL: the scalar argument)
-    const double *quality;     // per-item quality level                 (NULL: SelectParams::quality)
-};
+// CellCand (p = lx | ly << 16 (cell-local pixel), -1: none), DetBatch and SelectOut: detect_dev.hpp -- the lock-step tracker's
+// createKeyframe (trackb.hip) enqueues the three launches on buffers of its own.
 
 // wave-wide arg-max of (value, smaller index wins ties); all 64 lanes participate
 __device__ __forceinline__ void wave_argmax_f(float &v, int &idx)
@@ -133,6 +119,7 @@ __global__ __launch_bounds__(256) void k_fast_cells(const uint8_t *__restrict__ 
     __shared__ float s_v[4];
     __shared__ int s_i[4];
     const int item = blockIdx.x / B.ncells, cell = blockIdx.x - item * B.ncells;
+    if (B.skip && B.skip[item]) return;                                  // (work-group uniform)
     const int x0 = (cell % nwcells) * cs, y0 = (cell / nwcells) * cs;
     const int npx = cs * cs;
     img += (long long)item * B.img_stride;
@@ -252,6 +239,7 @@ __global__ __launch_bounds__(64) void k_mineig_cells(const uint8_t *__restrict__
     float *lam = (float *)smem;                               // npx, row-major
     uint8_t *blur = (uint8_t *)(lam + npx);                   // npx
     const int item = blockIdx.x / B.ncells, cell = blockIdx.x - item * B.ncells;
+    if (B.skip && B.skip[item]) return;
     const int x0 = (cell % nwcells) * cs, y0 = (cell / nwcells) * cs;
     img += (long long)item * B.img_stride;
     hmap_out += (long long)item * B.ncells * npx;
@@ -403,6 +391,10 @@ __global__ __launch_bounds__(64) void k_free_cells(int cs, int nwcells, DetBatch
     unsigned *occ = (unsigned *)smem;
     const int item = blockIdx.x, lane = threadIdx.x, ncells = B.ncells, nhcells = ncells / nwcells;
     const int occ_words = (ncells + 31) / 32;
+    if (B.skip && B.skip[item]) {                                        // no free cell: the strip kernel's work-groups of the item leave
+        if (lane == 0) free_list[(long long)item * (ncells + 1)] = 0;
+        return;
+    }
     for (int i = lane; i < occ_words; i += 64) occ[i] = 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const int n = B.ncur ? B.ncur[item] : B.ncur_all;
@@ -607,14 +599,6 @@ struct SelectParams {
     double quality;
 };
 
-struct SelectOut {
-    int n;               // points written to out_xy
-    int nboccup, nbempty, nbkps;
-    int nslow, pad_;             // cells of the sweep that needed the full masked scan (a candidate was hit by a neighbour's disc)
-    unsigned long long dbg[4];   // wall_clock64 ticks (100 MHz): init, prologue, sweep, compaction
-};
-static_assert(sizeof(SelectOut) == DET_SELECT_OUT_BYTES, "detect_plan.hpp lays out the scratch with this size");
-
 __device__ __forceinline__ void mask_clear_span(unsigned *mask, int wpr, int y, int xa, int xb)
 {
     // clear bits [xa, xb] of row y (already clipped, xa <= xb)
@@ -725,6 +709,10 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 1 : DET_SEL_MIN_WAVES) void k_grid
         const long long map_items = (long long)item * B.ncells * P.cs * P.cs;
         cur_xy += (long long)item * B.cur_stride; nms_maps += map_items; hmaps += map_items; cand += (long long)item * B.ncells;
         out_xy += (long long)item * B.out_stride; out += item;
+        if (B.skip && B.skip[item]) {                                    // no point, no count: the sub-pixel pass leaves on n == 0
+            if (threadIdx.x < sizeof(SelectOut) / 4) ((int *)out)[threadIdx.x] = 0;
+            return;
+        }
         if (B.ncur) P.ncur = B.ncur[item];
         if (B.quality) P.quality = B.quality[item];
     }
@@ -1332,11 +1320,20 @@ static const DetLimits &det_raise_lds_limits()
 // what det_check_geometry refused, as the entry points report it (OV2_EUNSUPPORTED each)
 static const char *const det_check_msg[] = {"", "cell size must be in [8,64]", "image too large", "image too large for the LDS-resident exclusion mask"};
 
+int det_ready(const ov2_ctx *ctx, int w, int h, int cell, int mode)
+{
+    const DetCheck chk = det_check_geometry(w, h, cell, mode, ctx->det_fast_tie == OV2_FAST_TIE_LIBSTDCXX);
+    OV2_REQUIRE(chk == DET_CHECK_OK, OV2_EUNSUPPORTED, det_check_msg[chk]);
+    OV2_HIP_CHECK(det_raise_lds_limits().err);
+    return OV2_OK;
+}
+
 // The three launches of a detection (response + candidates per cell, selection, sub-pixel refinement) for `items` images
 // that lie `B.img_stride` bytes apart; every pointer addresses item 0.  Asynchronous on `stream`; the context gives the options only.
-static int enqueue_detect(const ov2_ctx *ctx, hipStream_t stream, int mode, const uint8_t *im, int w, int h, int im_stride, int cell, int items, DetBatch B,
-                          int fast_th, int mask_mode, const int roi[4], double quality, int ncur, const float2 *cur_d,
-                          uint8_t *maps_d, CellCand *cand_d, int *free_d, float2 *out_d, SelectOut *so_d, int do_subpix)
+// (Declared in detect_dev.hpp: trackb.hip's createKeyframe enqueues it with a per-item skip byte.)
+int enqueue_detect(const ov2_ctx *ctx, hipStream_t stream, int mode, const uint8_t *im, int w, int h, int im_stride, int cell, int items, DetBatch B,
+                   int fast_th, int mask_mode, const int roi[4], double quality, int ncur, const float2 *cur_d,
+                   uint8_t *maps_d, CellCand *cand_d, int *free_d, float2 *out_d, SelectOut *so_d, int do_subpix)
 {
     const int nw = w / cell, nh = h / cell, ncells = nw * nh;
     int sort_slots = 0;

@@ -27,11 +27,18 @@
 // and the keyframe decision (mono.hip: k_mono_apply in front, k_mono_pack and fkf.hip's k_fkf_parallax behind), the frame pose, the
 // motion state and the keyframe's id / time / nb3dkps resident on the device with host mirrors; byte-equal to ov2_motion_apply_batch,
 // the step, ov2_motion_update_batch and ov2_kf_decision_batch (tests/test_gpu_trackmono.py).
+// ov2_btracker_create_keyframe is MapManager::createKeyframe for the items such a step asked to become keyframes (createkf.hip:
+// k_ckf_prepare in front, k_ckf_append behind the detector's launches, k_ckf_install behind computeKeypoint and BRIEF): the new frame
+// becomes the item's resident keyframe without leaving the device; byte-equal to the separate describe / detect / computeKeypoints
+// calls, a host sort and ov2_btracker_set_keyframe + ov2_btracker_set_keyframe_info per item (tests/test_gpu_createkf.py).
 #include "common.hpp"
 #include "keypoint_dev.hpp"
 #include "pose_dev.hpp"
 #include "frameepi_dev.hpp"
 #include "mono_dev.hpp"
+#include "detect_dev.hpp"
+#include "createkf_dev.hpp"
+#include "fkf_dev.hpp"
 #include "trackb_layout.hpp"
 #include <cmath>
 #include <deque>
@@ -47,6 +54,7 @@ static_assert(sizeof(EpifOut) == BT_EPIF_OUT_BYTES, "trackb_layout.hpp: the epip
 static_assert(sizeof(FeKfHdr) == BT_KF_HDR_BYTES, "trackb_layout.hpp: the index block's header");
 static_assert(sizeof(ov2_motion_state) == BT_MOTION_STATE_BYTES, "trackb_layout.hpp: the mono blocks' state");
 static_assert(sizeof(FkfItemD) == BT_FKF_ITEM_BYTES && 4 * FKF_OUT_INTS == BT_KF_DEC_BYTES, "trackb_layout.hpp: the mono blocks' records");
+static_assert(sizeof(ov2_create_keyframe_result) == BT_CKF_REC_BYTES && sizeof(SelectOut) == BT_CKF_SO_BYTES, "trackb_layout.hpp: the createKeyframe block's records");
 
 // A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
 // (zero copy), or mirrored on the device with a copy up before the kernels and a copy down behind them.
@@ -205,6 +213,15 @@ struct ov2_btracker {
                      std::vector<int> frame_id, localba; } pend;
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
+    // ov2_btracker_create_keyframe, allocated by its first call: the I/O block (pinned, and its device mirror at the same offsets:
+    // BtCkfLayout) and the detector's work block (device only, grow-only: the output lists, then one pass's maps, candidates and
+    // free-cell lists)
+    BtCkfLayout cl;
+    uint8_t *hckf = nullptr, *dckf = nullptr, *dckw = nullptr;
+    size_t ckw_bytes = 0;
+    struct CkfPending { bool on = false, det = false; int n_active = 0, mode = 0, ncells = 0; ov2_create_keyframe_params p;
+                        double *quality = nullptr; int *fast_th = nullptr; std::vector<uint8_t> flag; std::vector<int> nkfid;
+                        std::vector<double> time; } cpend;
 };
 
 static void btracker_free(ov2_btracker *t)
@@ -236,6 +253,9 @@ static void btracker_free(ov2_btracker *t)
     if (t->h_out) (void)hipHostFree(t->h_out);
     if (t->d_out) (void)hipFree(t->d_out);
     if (t->d_roi) (void)hipFree(t->d_roi);
+    if (t->hckf) (void)hipHostFree(t->hckf);
+    if (t->dckf) (void)hipFree(t->dckf);
+    if (t->dckw) (void)hipFree(t->dckw);
     delete t;
 }
 
@@ -753,6 +773,7 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     t->img_bytes = bt_img_bytes(cfg->w, cfg->h);
     t->pl = bt_point_layout(batch, cfg->n_max); t->ml = bt_map_layout(batch, cfg->n_max);
     t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max); t->nl = bt_mono_layout(batch, cfg->n_max);
+    t->cl = bt_ckf_layout(batch, cfg->n_max);
     t->det_in_bytes = bt_det_in_bytes(batch, cfg->n_max);
     hipError_t e = hipSuccess;
     for (int i = 0; i < BT_IMG_SETS && e == hipSuccess; i++) {
@@ -851,7 +872,7 @@ int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(!map || (map->w == t->cfg.w && map->h == t->cfg.h), OV2_EINVAL, "map and tracker differ in size");
     OV2_REQUIRE(!map || map->device == t->ctx->device, OV2_EINVAL, "the map lives on another device");
-    OV2_REQUIRE(t->prepq.empty() && !t->pend.on, OV2_EINVAL, "ov2_btracker_set_rectification between steps only: prepared frames wait or a step is open");
+    OV2_REQUIRE(t->prepq.empty() && !t->pend.on && !t->cpend.on, OV2_EINVAL, "ov2_btracker_set_rectification between steps only: prepared frames wait or a step is open");
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
     OV2_HIP_CHECK(hipStreamSynchronize(t->cs));
     OV2_HIP_CHECK(hipStreamSynchronize(t->ps));
@@ -884,6 +905,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     OV2_REQUIRE(t && A.img_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
+    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(A.stride >= t->cfg.w, OV2_EINVAL, "stride < width");
     const size_t nm = (size_t)t->cfg.n_max;
@@ -1513,7 +1535,7 @@ int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf
         for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(h.kf_Tcw[c]), OV2_EINVAL, "pose not finite (the inverse of kf_Twc)");
     }
     for (size_t i = 0; i < 3 * (size_t)n_kf; i++) OV2_REQUIRE(std::isfinite(kf_bv[i]), OV2_EINVAL, "kf_bv not finite");
-    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_set_keyframe between steps only: a step is open");
+    OV2_REQUIRE(!t->pend.on && !t->cpend.on, OV2_EINVAL, "ov2_btracker_set_keyframe between steps only: a step is open");
     const int rc = ensure_epi(t, nullptr);
     if (rc != OV2_OK) return rc;
     const EpifLayout &L0 = t->eL0;
@@ -1570,7 +1592,7 @@ static int mono_item(ov2_btracker *t, int item, const char *open_msg)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, open_msg);
+    OV2_REQUIRE(!t->pend.on && !t->cpend.on, OV2_EINVAL, open_msg);
     return ensure_mono(t);
 }
 
@@ -1767,6 +1789,264 @@ int ov2_btracker_lckf_prepare(ov2_btracker *t, int n_active, const ov2_lckf_para
     // a later upload of this set on the copy stream orders itself after the reads (the call has synchronised: this costs nothing)
     OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], t->ctx->stream));
     return OV2_OK;
+}
+
+} // extern "C"
+
+// ---- ov2_btracker_create_keyframe ------------------------------------------------------------------------------------------------
+// the detector's work block: every item's output list, then ONE pass's response maps, candidates and free-cell lists (passes of
+// `chunk` items follow each other on the context's stream and share them, as the passes of the batched detectors do)
+struct CkfWork { int chunk, out_cap; size_t o_out, o_map, o_cand, o_free, total; };
+static CkfWork ckf_work(int batch, int cell, int ncells, int mode)
+{
+    CkfWork W;
+    W.chunk = batch < DET_CHUNK / 2 ? batch : DET_CHUNK / 2;
+    W.out_cap = det_out_cap(mode, ncells);
+    StageCursor c(256);
+    W.o_out = c.take(8 * (size_t)W.out_cap * (size_t)batch);
+    W.o_map = c.take((size_t)W.chunk * det_map_bytes(cell, ncells, mode));
+    W.o_cand = c.take((size_t)W.chunk * (size_t)ncells * DET_CAND_BYTES);
+    W.o_free = c.take((size_t)W.chunk * 4 * ((size_t)ncells + 1));
+    W.total = c.off;
+    return W;
+}
+
+// the call's buffers: the I/O block by the first call, the work block grown to `need` bytes
+static int ensure_ckf(ov2_btracker *t, size_t need)
+{
+    const char *who = "ov2_btracker_create_keyframe";
+    if (!t->hckf) {
+        uint8_t *h = nullptr, *d = nullptr;
+        hipError_t e = hipHostMalloc((void **)&h, t->cl.c_down, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&d, t->cl.dev_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(d, 0, t->cl.dev_bytes, t->ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+        if (e != hipSuccess) {
+            if (h) (void)hipHostFree(h);
+            if (d) (void)hipFree(d);
+            (void)hipGetLastError();
+            ov2_set_error("%s: %s", who, hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        memset(h, 0, t->cl.c_down);
+        t->hckf = h; t->dckf = d;
+    }
+    if (need > t->ckw_bytes) {
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (an earlier call's kernels have long finished: its _end waited)
+        if (t->dckw) (void)hipFree(t->dckw);
+        t->dckw = nullptr; t->ckw_bytes = 0;
+        const hipError_t e = hipMalloc((void **)&t->dckw, need);
+        if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("%s: %s", who, hipGetErrorString(e)); return OV2_ENOMEM; }
+        t->ckw_bytes = need;
+    }
+    return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_create_keyframe_params *params,
+                                       const ov2_create_keyframe_input *input)
+{
+    OV2_REQUIRE(t && params && input, OV2_EINVAL, "ov2_btracker_create_keyframe: NULL tracker / params / input");
+    const ov2_create_keyframe_params &p = *params;
+    const ov2_create_keyframe_input &in = *input;
+    OV2_REQUIRE(in.px_h && in.lmid_h && in.is3d_h && in.n_h && in.make_kf_h && in.nlmid_h && in.nkfid_h && in.time_h, OV2_EINVAL,
+                "ov2_btracker_create_keyframe: NULL px_h / lmid_h / is3d_h / n_h / make_kf_h / nlmid_h / nkfid_h / time_h");
+    OV2_REQUIRE(p.detector != OV2_CKF_DET_GFTT, OV2_EINVAL, "ov2_btracker_create_keyframe: detectGFTT is not fused (detector OV2_CKF_DET_GFTT)");
+    OV2_REQUIRE(p.detector == OV2_CKF_DET_SINGLESCALE || p.detector == OV2_CKF_DET_GRID_FAST, OV2_EINVAL, "ov2_btracker_create_keyframe: unknown detector");
+    const int mode = p.detector == OV2_CKF_DET_GRID_FAST ? 0 : 1;
+    OV2_REQUIRE(mode == 0 ? in.fast_th_inout != nullptr : in.quality_inout != nullptr, OV2_EINVAL,
+                "ov2_btracker_create_keyframe: NULL quality_inout (single scale) / fast_th_inout (grid FAST)");
+    OV2_REQUIRE(mode != 0 || p.mask_mode == OV2_MASK_AS_EXECUTED || p.mask_mode == OV2_MASK_INTENDED, OV2_EINVAL, "bad mask_mode");
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
+    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_create_keyframe between steps only: a step is open");
+    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: the previous call has not been finished (ov2_btracker_create_keyframe_end)");
+    OV2_REQUIRE(t->raw_which >= 0, OV2_EINVAL, "ov2_btracker_create_keyframe: no current frames (no step yet, or their staging set was uploaded / prepared again)");
+    OV2_REQUIRE(n_active <= t->raw_n, OV2_EINVAL, "n_active exceeds the items of the current step");
+    OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_create_keyframe: no calibration set on this tracker");
+    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    OV2_REQUIRE(in.Twc_h || t->dres, OV2_EINVAL, "ov2_btracker_create_keyframe: Twc_h == NULL on a tracker without a resident pose (ov2_btracker_set_pose / ov2_btracker_track_mono)");
+    {
+        ov2_fkf_params g;
+        memset(&g, 0, sizeof g);
+        g.ncellsize = p.ncellsize; g.nbwcells = p.nbwcells; g.nbhcells = p.nbhcells; g.nbmaxkps = p.nbmaxkps;
+        const int rcg = fkf_check_decide(&g);  if (rcg != OV2_OK) return rcg;
+    }
+    const ov2_tracker_config &c = t->cfg;
+    OV2_REQUIRE(p.det_cell >= 8, OV2_EINVAL, "the detector's cell size must be at least 8");
+    int rc = det_ready(t->ctx, c.w, c.h, p.det_cell, mode);  if (rc != OV2_OK) return rc;
+    const int ncells = (c.w / p.det_cell) * (c.h / p.det_cell);
+    const size_t nm = (size_t)c.n_max;
+    bool any = false;
+    for (int b = 0; b < n_active; b++) {
+        const int n = in.n_h[b];
+        OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
+        if (!in.make_kf_h[b]) continue;
+        any = true;
+        const int nl = in.nlmid_h[b];
+        OV2_REQUIRE(nl >= 0 && (long long)nl + 2ll * ncells <= 2147483647ll, OV2_EINVAL, "nlmid_h negative, or nlmid_h + the detector's capacity overflows int");
+        for (int i = 0; i < n; i++) {
+            const int lm = in.lmid_h[nm * (size_t)b + (size_t)i];
+            OV2_REQUIRE(lm >= 0 && lm < nl, OV2_EINVAL, "lmid_h outside [0, nlmid_h): the map's id counter is monotone");
+        }
+        OV2_REQUIRE(std::isfinite(in.time_h[b]), OV2_EINVAL, "time not finite");
+        const double *T = in.Twc_h ? in.Twc_h + 7 * (size_t)b : t->res_T.data() + 7 * (size_t)b;
+        double Ti[7];
+        for (int k = 0; k < 7; k++) OV2_REQUIRE(std::isfinite(T[k]), OV2_EINVAL, "pose not finite (Twc_h)");
+        ov2_fe_invert(T, Ti);
+        for (int k = 0; k < 7; k++) OV2_REQUIRE(std::isfinite(Ti[k]), OV2_EINVAL, "pose not finite (the inverse of Twc_h)");
+    }
+    ov2_ctx *ctx = t->ctx;
+    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;
+    rc = ensure_mono(t);  if (rc != OV2_OK) return rc;
+    const bool det_on = ncells > 0;
+    const CkfWork W = ckf_work(t->batch, p.det_cell, det_on ? ncells : 1, mode);
+    rc = ensure_ckf(t, W.total);  if (rc != OV2_OK) return rc;
+    ov2_btracker::CkfPending &P = t->cpend;
+    P.n_active = n_active; P.mode = mode; P.ncells = ncells; P.p = p; P.det = det_on && any;
+    P.quality = in.quality_inout; P.fast_th = in.fast_th_inout;
+    P.flag.assign(in.make_kf_h, in.make_kf_h + n_active);
+    P.nkfid.assign(in.nkfid_h, in.nkfid_h + n_active);
+    P.time.assign(in.time_h, in.time_h + n_active);
+    // ---- the inputs into the pinned block ----
+    const BtCkfLayout &L = t->cl;
+    uint8_t *h = t->hckf, *d = t->dckf;
+    const size_t na = (size_t)n_active;
+    memcpy(h + L.c_n, in.n_h, 4 * na);
+    for (int b = 0; b < n_active; b++) h[L.c_fl + (size_t)b] = in.make_kf_h[b] ? 1 : 0;
+    memcpy(h + L.c_nl, in.nlmid_h, 4 * na);
+    memcpy(h + L.c_id, in.nkfid_h, 4 * na);
+    memcpy(h + L.c_tm, in.time_h, 8 * na);
+    if (in.Twc_h) memcpy(h + L.c_T, in.Twc_h, 56 * na);
+    for (int b = 0; b < n_active; b++) {
+        if (mode == 0) memcpy(h + L.c_par + 4 * (size_t)b, in.fast_th_inout + b, 4);
+        else memcpy(h + L.c_par + 8 * (size_t)b, in.quality_inout + b, 8);
+        const size_t n = in.make_kf_h[b] ? (size_t)in.n_h[b] : 0, o = nm * (size_t)b;
+        if (!n) continue;
+        memcpy(h + L.c_px + 8 * o, in.px_h + 2 * o, 8 * n);
+        memcpy(h + L.c_lm + 4 * o, in.lmid_h + o, 4 * n);
+        memcpy(h + L.c_3d + o, in.is3d_h + o, n);
+    }
+    // ---- the one enqueue ----
+    const hipStream_t s = ctx->stream;
+    const ov2_pyr *pyr = t->pyr[t->cur];
+    rc = ov2_pyr_wait_ready(ctx, pyr);  if (rc != OV2_OK) return rc;
+    const PyrLevelDesc &L0 = pyr->d.lv[0];
+    const uint8_t *im = pyr->d.base + L0.img_roi;
+    OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.c_up, hipMemcpyHostToDevice, s));
+    uint8_t *w = t->dckw;
+    CkfArgs a;
+    a.n = (const int *)(d + L.c_n); a.flag = d + L.c_fl; a.nlmid = (const int *)(d + L.c_nl); a.nkfid = (const int *)(d + L.c_id);
+    a.time = (const double *)(d + L.c_tm); a.Twc = in.Twc_h ? (const double *)(d + L.c_T) : (const double *)(t->dres + t->nl.r_T);
+    a.px = (float2 *)(d + L.c_px); a.lmid = (int *)(d + L.c_lm); a.is3d = d + L.c_3d;
+    a.skip = d + L.w_skip; a.so_n = (const int *)(d + L.c_so); a.so_stride = (int)(sizeof(SelectOut) / sizeof(int));
+    a.det = (const float2 *)(w + W.o_out); a.det_cap = W.out_cap; a.nb = (int *)(d + L.w_nb);
+    a.img = im; a.img_item = (long long)pyr->d.item_stride; a.img_pitch = L0.img_pitch; a.w = L0.w; a.h = L0.h;
+    a.rec = (ov2_create_keyframe_result *)(d + L.c_rec); a.color = d + L.c_col; a.o_hdr = (FeKfHdr *)(d + L.c_hdr); a.perm = (int *)(d + L.c_perm);
+    a.unpx = (const float2 *)(d + L.c_un); a.bv = (const double *)(d + L.c_bv);
+    a.kf_lmid = (int *)(t->depi + t->eL0.o_kl); a.kf_unpx = (float2 *)(t->depi + t->eL0.o_ku); a.kf_bv = (double *)(t->depi + t->eL0.o_kb);
+    a.hdr = (FeKfHdr *)t->dfx; a.r_ki = (MonoKfInfo *)(t->dres + t->nl.r_ki); a.r_kt = (double *)(t->dres + t->nl.r_kt);
+    a.n_max = c.n_max; a.ncellsize = p.ncellsize; a.nbwcells = p.nbwcells; a.nbhcells = p.nbhcells; a.nbmaxkps = p.nbmaxkps; a.det_on = det_on ? 1 : 0;
+    rc = ov2_launch_ckf_prepare(s, a, n_active);  if (rc != OV2_OK) return rc;
+    if (P.det) {
+        // the detectors' three launches per pass, the frame's keypoints as the occupied set, every count left on the device
+        for (int c0 = 0; c0 < n_active; c0 += W.chunk) {
+            const int n = n_active - c0 < W.chunk ? n_active - c0 : W.chunk;
+            DetBatch B = {};
+            B.img_stride = (long long)pyr->d.item_stride; B.cur_stride = c.n_max; B.out_stride = W.out_cap;
+            B.ncur = a.n + c0; B.skip = a.skip + c0;
+            if (mode == 0) B.fast_th = (const int *)(d + L.c_par) + c0; else B.quality = (const double *)(d + L.c_par) + c0;
+            rc = enqueue_detect(ctx, s, mode, im + (long long)c0 * pyr->d.item_stride, L0.w, L0.h, L0.img_pitch, p.det_cell, n, B, 0, p.mask_mode,
+                                mode == 1 ? p.roi : nullptr, 0.0, 0, (const float2 *)a.px + (size_t)c0 * nm, w + W.o_map, (CellCand *)(w + W.o_cand),
+                                (int *)(w + W.o_free), (float2 *)(w + W.o_out) + (size_t)c0 * (size_t)W.out_cap,
+                                (SelectOut *)(d + L.c_so) + c0, p.do_subpix);
+            if (rc != OV2_OK) return rc;
+        }
+    }
+    rc = ov2_launch_ckf_append(s, a, n_active);  if (rc != OV2_OK) return rc;
+    rc = ov2_launch_compute_keypoints(s, t->calib, (const float *)a.px, c.n_max, a.nb, (float *)(d + L.c_un), (double *)(d + L.c_bv), n_active);
+    if (rc != OV2_OK) return rc;
+    if (p.use_brief) {
+        const int which = t->raw_which;
+        rc = ov2_brief_launch_d(ctx, t->dimg[which], c.w, c.h, t->img_pitch, t->img_bytes, n_active, (const float *)a.px, c.n_max, a.nb, 0,
+                                d + L.c_desc, d + L.c_val);
+        if (rc != OV2_OK) return rc;
+        // a later upload of this set on the copy stream orders itself after the reads
+        OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], s));
+    }
+    rc = ov2_launch_ckf_install(s, a, n_active);  if (rc != OV2_OK) return rc;
+    OV2_HIP_CHECK(hipMemcpyAsync(h + L.c_io, d + L.c_io, (p.use_brief ? L.c_down : L.c_desc) - L.c_io, hipMemcpyDeviceToHost, s));
+    P.on = true;
+    return OV2_OK;
+}
+
+int ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result *results, float *out_px_h, int *out_lmid_h,
+                                     float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    ov2_btracker::CkfPending &P = t->cpend;
+    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_create_keyframe_end without ov2_btracker_create_keyframe_begin");
+    OV2_REQUIRE(results && out_px_h && out_lmid_h && unpx_h && bv_h && color_h, OV2_EINVAL, "ov2_btracker_create_keyframe_end: NULL result / output array");
+    OV2_REQUIRE(!P.p.use_brief || (desc_h && valid_h), OV2_EINVAL, "ov2_btracker_create_keyframe_end: NULL desc_h / valid_h with use_brief");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    P.on = false;
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    const BtCkfLayout &L = t->cl;
+    const EpifLayout &E = t->eL0;
+    const uint8_t *h = t->hckf;
+    uint8_t *kh = t->kf_host.data();
+    const size_t nm = (size_t)t->cfg.n_max;
+    for (int b = 0; b < P.n_active; b++) {
+        if (!P.flag[(size_t)b]) { results[b].action = OV2_CKF_NOT_REQUESTED; continue; }
+        ov2_create_keyframe_result &r = results[b];
+        memcpy(&r, h + L.c_rec + sizeof r * (size_t)b, sizeof r);
+        if (P.det && r.nb2detect > 0) {                                     // the detection ran: the reference's adaptation (:546-552 / :418-423)
+            SelectOut so;
+            memcpy(&so, h + L.c_so + sizeof so * (size_t)b, sizeof so);
+            if (P.mode == 0) P.fast_th[b] = det_adapt_fast_th(P.fast_th[b], so.nbkps, so.nbempty);
+            else P.quality[b] = det_adapt_quality(P.quality[b], so.n, P.ncells, so.nboccup);
+        }
+        if (r.action != OV2_CKF_CREATED) continue;
+        const size_t o = nm * (size_t)b, n = (size_t)r.n_kf, n0 = (size_t)r.n_prev;
+        memcpy(out_px_h + 2 * o, h + L.c_px + 8 * o, 8 * n);
+        memcpy(out_lmid_h + o, h + L.c_lm + 4 * o, 4 * n);
+        memcpy(unpx_h + 2 * o, h + L.c_un + 8 * o, 8 * n);
+        memcpy(bv_h + 3 * o, h + L.c_bv + 24 * o, 24 * n);
+        memcpy(color_h + o + n0, h + L.c_col + o + n0, n - n0);
+        if (P.p.use_brief) {
+            memcpy(desc_h + 32 * o, h + L.c_desc + 32 * o, 32 * n);
+            memcpy(valid_h + o, h + L.c_val + o, n);
+        }
+        // the host mirrors, as ov2_btracker_set_keyframe / ov2_btracker_set_keyframe_info leave them
+        const int *perm = (const int *)(h + L.c_perm) + o, *lm = (const int *)(h + L.c_lm) + o;
+        const float *un = (const float *)(h + L.c_un) + 2 * o;
+        const double *bv = (const double *)(h + L.c_bv) + 3 * o;
+        int *kl = (int *)kh + o;
+        float *ku = (float *)(kh + (E.o_ku - E.o_kl)) + 2 * o;
+        double *kb = (double *)(kh + (E.o_kb - E.o_kl)) + 3 * o;
+        for (size_t i = 0; i < n; i++) {
+            const size_t sl = (size_t)perm[i];
+            kl[i] = lm[sl];
+            ku[2 * i] = un[2 * sl]; ku[2 * i + 1] = un[2 * sl + 1];
+            kb[3 * i] = bv[3 * sl]; kb[3 * i + 1] = bv[3 * sl + 1]; kb[3 * i + 2] = bv[3 * sl + 2];
+        }
+        memcpy(&t->kf_hdr[(size_t)b], h + L.c_hdr + sizeof(FeKfHdr) * (size_t)b, sizeof(FeKfHdr));
+        t->res_ki[(size_t)b] = MonoKfInfo{P.nkfid[(size_t)b], r.nb3dkps, 1, 0};
+        t->res_kt[(size_t)b] = P.time[(size_t)b];
+    }
+    return OV2_OK;
+}
+
+int ov2_btracker_create_keyframe(ov2_btracker *t, int n_active, const ov2_create_keyframe_params *params,
+                                 const ov2_create_keyframe_input *input, ov2_create_keyframe_result *results, float *out_px_h,
+                                 int *out_lmid_h, float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h)
+{
+    OV2_REQUIRE(results && out_px_h && out_lmid_h && unpx_h && bv_h && color_h, OV2_EINVAL, "ov2_btracker_create_keyframe: NULL result / output array");
+    OV2_REQUIRE(!params || !params->use_brief || (desc_h && valid_h), OV2_EINVAL, "ov2_btracker_create_keyframe: NULL desc_h / valid_h with use_brief");
+    const int rc = ov2_btracker_create_keyframe_begin(t, n_active, params, input);
+    if (rc != OV2_OK) return rc;
+    return ov2_btracker_create_keyframe_end(t, results, out_px_h, out_lmid_h, unpx_h, bv_h, desc_h, valid_h, color_h);
 }
 
 const ov2_pyr *ov2_btracker_cur_pyr(const ov2_btracker *t) { return t ? t->pyr[t->cur] : nullptr; }

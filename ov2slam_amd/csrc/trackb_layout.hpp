@@ -1,6 +1,6 @@
 // trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
-// point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block and the three blocks of
-// ov2_btracker_track_mono, each computed by one
+// point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block, the three blocks of
+// ov2_btracker_track_mono and the block of ov2_btracker_create_keyframe, each computed by one
 // function of (batch, n_max).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
@@ -93,5 +93,34 @@ static inline BtMonoLayout bt_mono_layout(int batch, int n_max)
     L.res_bytes = up256(L.r_ki + 16 * B);
     L.w_it = 0; L.w_lm = up256(BT_FKF_ITEM_BYTES * B); L.w_px = up256(L.w_lm + 4 * slots); L.w_un = up256(L.w_px + 8 * slots);
     L.w_bv = up256(L.w_un + 8 * slots); L.w_3d = up256(L.w_bv + 24 * slots); L.work_bytes = up256(L.w_3d + slots);
+    return L;
+}
+
+// The block of ov2_btracker_create_keyframe: one pinned host block and its device mirror at the same offsets, ONE copy up ([0, c_up))
+// and ONE copy down ([c_io, c_down) with descriptors, [c_io, c_desc) without).
+//   up only     [n 4][make_kf 1][nlmid 4][nkfid 4][time 8][Twc 56][quality 8 or fast_th 4, in 8 per item][is3d 1 per slot]
+//   up and down [px 8][lmid 4 per slot]: the frame, the new points appended behind slot n on the device
+//   down only   [record 32][SelectOut 56][FeKfHdr 120 per item][unpx 8][bv 24][colour 1][perm 4 (slot of the keyframe's i-th id) per
+//               slot][desc 32][valid 1 per slot]
+//   device only [skip 1][count 4 per item]: the detector's skip byte and the frame's size for computeKeypoint / BRIEF
+#define BT_CKF_REC_BYTES 32          // sizeof(ov2_create_keyframe_result), sizeof(SelectOut): trackb.hip asserts both
+#define BT_CKF_SO_BYTES 56
+struct BtCkfLayout {
+    size_t c_n, c_fl, c_nl, c_id, c_tm, c_T, c_par, c_3d, c_io, c_px, c_lm, c_up;
+    size_t c_rec, c_so, c_hdr, c_un, c_bv, c_col, c_perm, c_desc, c_val, c_down;
+    size_t w_skip, w_nb, dev_bytes;
+};
+static inline BtCkfLayout bt_ckf_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    StageCursor c(256);
+    BtCkfLayout L;
+    L.c_n = c.take(4 * B); L.c_fl = c.take(B); L.c_nl = c.take(4 * B); L.c_id = c.take(4 * B); L.c_tm = c.take(8 * B); L.c_T = c.take(56 * B);
+    L.c_par = c.take(8 * B); L.c_3d = c.take(slots);
+    L.c_io = L.c_px = c.take(8 * slots); L.c_lm = c.take(4 * slots); L.c_up = c.off;
+    L.c_rec = c.take(BT_CKF_REC_BYTES * B); L.c_so = c.take(BT_CKF_SO_BYTES * B); L.c_hdr = c.take(BT_KF_HDR_BYTES * B);
+    L.c_un = c.take(8 * slots); L.c_bv = c.take(24 * slots); L.c_col = c.take(slots); L.c_perm = c.take(4 * slots);
+    L.c_desc = c.take(32 * slots); L.c_val = c.take(slots); L.c_down = c.off;
+    L.w_skip = c.take(B); L.w_nb = c.take(4 * B); L.dev_bytes = c.off;
     return L;
 }

@@ -862,6 +862,100 @@ class LockstepTracker:
         return (out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn) if self._mono_epi else None, self._pose_dicts(R, removed, nn),
                 self._mono_dicts(M, na))
 
+    # ---- createKeyframe for the items a step flagged (ov2_btracker_create_keyframe) ------------------------------------------------
+    def _ckf_args(self, n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc):
+        na = int(n_active)
+        cp = L.CreateKeyframeParams()
+        cp.ncellsize, cp.nbwcells, cp.nbhcells, cp.nbmaxkps = (int(params[k]) for k in ("ncellsize", "nbwcells", "nbhcells", "nbmaxkps"))
+        det = params.get("detector", "singlescale")
+        cp.detector = {"singlescale": L.OV2_CKF_DET_SINGLESCALE, "gridfast": L.OV2_CKF_DET_GRID_FAST, "gftt": L.OV2_CKF_DET_GFTT}.get(det, det)
+        cp.det_cell = int(params["det_cell"])
+        cp.roi = (C.c_int * 4)(*[int(v) for v in params.get("roi", (0, 0, self.w, self.h))])
+        cp.mask_mode = int(params.get("mask_mode", L.OV2_MASK_AS_EXECUTED))
+        cp.do_subpix, cp.use_brief = int(bool(params.get("do_subpix", True))), int(bool(params.get("use_brief", True)))
+        px = np.ascontiguousarray(px, np.float32).reshape(self.batch, self.n_max, 2)
+        lm = np.ascontiguousarray(lmid, np.int32).reshape(self.batch, self.n_max)
+        d3 = np.ascontiguousarray(is3d, np.uint8).reshape(self.batch, self.n_max)
+        nn = np.ascontiguousarray(n, np.int32).reshape(-1)
+        mk = np.ascontiguousarray(make_kf, np.uint8).reshape(-1)
+        nl = np.ascontiguousarray(nlmid, np.int32).reshape(-1)
+        ki = np.ascontiguousarray(nkfid, np.int32).reshape(-1)
+        tm = np.ascontiguousarray(time, np.float64).reshape(-1)
+        if min(len(nn), len(mk), len(nl), len(ki), len(tm)) < na:
+            raise ValueError("one count, flag, nlmid, keyframe id and time per active item")
+        T = None if Twc is None else np.ascontiguousarray(Twc, np.float64).reshape(-1, 7)
+        if T is not None and len(T) < na:
+            raise ValueError("one pose per active item")
+        fast = cp.detector == L.OV2_CKF_DET_GRID_FAST
+        st = np.ascontiguousarray(state, np.int32 if fast else np.float64)
+        assert st is state or np.shares_memory(st, state), "state must be a contiguous int32 (FAST) / float64 (single scale) array (updated in place)"
+        if len(st) < na:
+            raise ValueError("one adaptive state per active item")
+        ci = L.CreateKeyframeInput()
+        ci.px_h = px.ctypes.data_as(C.POINTER(C.c_float))
+        ci.lmid_h = lm.ctypes.data_as(C.POINTER(C.c_int))
+        ci.is3d_h = d3.ctypes.data_as(C.POINTER(C.c_uint8))
+        ci.n_h = nn.ctypes.data_as(C.POINTER(C.c_int))
+        ci.make_kf_h = mk.ctypes.data_as(C.POINTER(C.c_uint8))
+        ci.nlmid_h = nl.ctypes.data_as(C.POINTER(C.c_int))
+        ci.nkfid_h = ki.ctypes.data_as(C.POINTER(C.c_int))
+        ci.time_h = tm.ctypes.data_as(C.POINTER(C.c_double))
+        ci.Twc_h = None if T is None else T.ctypes.data_as(C.POINTER(C.c_double))
+        ci.quality_inout = None if fast else st.ctypes.data_as(C.POINTER(C.c_double))
+        ci.fast_th_inout = st.ctypes.data_as(C.POINTER(C.c_int)) if fast else None
+        return na, cp, ci, (px, lm, d3, nn, mk, nl, ki, tm, T, st)
+
+    def _ckf_outputs(self, na, out):
+        """the arrays _end scatters into (the caller's, so that untouched slots stay what they were, or fresh zeros)"""
+        shapes = dict(px=((self.batch, self.n_max, 2), np.float32), lmid=((self.batch, self.n_max), np.int32),
+                      unpx=((self.batch, self.n_max, 2), np.float32), bv=((self.batch, self.n_max, 3), np.float64),
+                      desc=((self.batch, self.n_max, L.OV2_BRIEF_BYTES), np.uint8), valid=((self.batch, self.n_max), np.uint8),
+                      color=((self.batch, self.n_max), np.uint8))
+        o = {}
+        for k, (shape, dt) in shapes.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dt)
+            elif a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError("out[%r] must be a contiguous %s array of shape %r" % (k, np.dtype(dt).name, shape))
+            o[k] = a
+        return o, (L.CreateKeyframeResult * max(1, na))()
+
+    def _ckf_dicts(self, R, na, o):
+        keys = ("action", "n_prev", "noccupcells", "nb2detect", "n_new", "n_kf", "nb3dkps")
+        return [{k: int(getattr(R[b], k)) for k in keys} for b in range(na)], o
+
+    def createKeyframe(self, n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc=None, out=None):
+        """MapManager::createKeyframe for the items of [0, n_active) with make_kf[b] != 0, in one enqueue and one synchronisation
+        (ov2_btracker_create_keyframe): describeBRIEF, the detector's top-up of the empty cells, addKeypointsToFrame, computeKeypoint and
+        the new frame installed as the item's resident keyframe (setKeyframe + setKeyframeInfo) without leaving the device.
+        px (batch, n_max, 2), lmid / is3d (batch, n_max), n: the current frame after prepareFrame; nlmid, nkfid, time: one per item;
+        params: dict(ncellsize, nbwcells, nbhcells, nbmaxkps, detector "singlescale" | "gridfast", det_cell, roi, mask_mode, do_subpix,
+        use_brief); state: float64 qualities (single scale) or int32 thresholds (FAST), one per item, updated in place; Twc
+        (>= n_active, 7) or None: the resident pose; out: dict of arrays to scatter into (missing ones are zeros).
+        -> (records, out): records[b] = dict(action, n_prev, noccupcells, nb2detect, n_new, n_kf, nb3dkps); out = dict(px, lmid, unpx,
+        bv, desc, valid, color) in slot layout, written for the items with action OV2_CKF_CREATED only."""
+        na, cp, ci, keep = self._ckf_args(n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc)
+        o, R = self._ckf_outputs(na, out)
+        L.check(self.lib.ov2_btracker_create_keyframe(self.h_trk, na, C.byref(cp), C.byref(ci), R, _ptr(o["px"]), _ptr(o["lmid"]), _ptr(o["unpx"]),
+                                                      _ptr(o["bv"]), _ptr(o["desc"]), _ptr(o["valid"]), _ptr(o["color"])))
+        return self._ckf_dicts(R, na, o)
+
+    def createKeyframeBegin(self, n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc=None):
+        """first half of createKeyframe: enqueue and return; createKeyframeEnd finishes it (state is updated there: keep it alive)"""
+        na, cp, ci, keep = self._ckf_args(n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc)
+        L.check(self.lib.ov2_btracker_create_keyframe_begin(self.h_trk, na, C.byref(cp), C.byref(ci)))
+        self._ckf_pending = (na, keep)
+
+    def createKeyframeEnd(self, out=None):
+        """second half of createKeyframe -> (records, out)"""
+        na = self._ckf_pending[0] if getattr(self, "_ckf_pending", None) else 0          # (no open call: the library refuses)
+        o, R = self._ckf_outputs(na, out)
+        L.check(self.lib.ov2_btracker_create_keyframe_end(self.h_trk, R, _ptr(o["px"]), _ptr(o["lmid"]), _ptr(o["unpx"]), _ptr(o["bv"]),
+                                                          _ptr(o["desc"]), _ptr(o["valid"]), _ptr(o["color"])))
+        self._ckf_pending = None
+        return self._ckf_dicts(R, na, o)
+
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
         pri = np.empty((n, 2), np.float32)
