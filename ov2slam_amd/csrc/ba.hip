@@ -1031,7 +1031,7 @@ __global__ __launch_bounds__(256) void k_ba_pose_only(BADev D, BAOpt O, BACtl ct
                     for (int c = 0; c < 7; c++) cp[c] = out[c];
                     d_pose_to_RT(out, s_cRT);
                 }
-                s_flag = valid;
+                s_flag = cl.done ? -1 : valid;                  // (an invalid step that used up the budget ends the solve)
             } else s_flag = -1;
             s_cost = 0;
         }

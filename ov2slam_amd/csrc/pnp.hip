@@ -167,7 +167,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_solve(PnPArgs a)
                         for (int c = 0; c < 7; c++) s_c[c] = o7[c];
                         d_pose_to_RT(o7, s_cRT);
                     }
-                    s_flag = valid;
+                    s_flag = cl.done ? -1 : valid;              // (an invalid step that used up the budget ends the solve)
                 } else s_flag = -1;
             }
             __syncthreads();

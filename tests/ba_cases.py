@@ -246,6 +246,18 @@ def irregular_xyz(seed=1, shuffle=True):
     return shuffle_blocks(pb, seed) if shuffle else pb
 
 
+RECOVERY_XYZ_EMPTY_KF = 6
+
+
+def recovery_xyz(seed=1):
+    """A small 3-D point problem with a free keyframe without blocks and no point of fewer than four blocks (tests/trlm_cases.py):
+    at a trust-region radius of 1e306 the LM diagonal no longer regularises anything, so every 3 x 3 point block has to be
+    positive definite on its own -- a point of one block (irregular_xyz has some) is not -- and the only pivot that fails is the
+    empty keyframe's."""
+    counts = np.random.default_rng(seed).integers(4, 11, 40)
+    return shuffle_blocks(make_xyz_problem(counts, 10, (0,), RECOVERY_XYZ_EMPTY_KF, seed=seed, outlier_frac=0.0), seed)
+
+
 def irregular_structure(seed=1, shuffle=True):
     counts, dead = irregular_xyz_counts(seed)
     pb = make_structure_problem(counts, N_KF, seed=seed, dead=dead)

@@ -20,6 +20,19 @@ CERES_DEFAULTS = dict(gradient_tolerance=1e-10, parameter_tolerance=1e-8, initia
                       max_consecutive_invalid_steps=5)
 
 
+# A finite, accepted initial_radius under which every linear solve fails: diag / radius overflows in float64 (diag >= min_lm_diagonal
+# = 1e-6 against a radius of 1e-310 and below), the first pivot is inf, the step is invalid; the radius goes 1e-310, 5e-311, 1.25e-311,
+# 1.5625e-312, 9.765625e-314 and the fifth invalid step in a row ends the solve.  A FAILED solve (not a step without descent) is
+# Ceres' FAILURE: the input poses come back.  In longdouble the quotient (1e304) is representable and the solve succeeds, so the two
+# precisions do NOT decide alike here: only decisions and copied values are compared on this case.
+DENORMAL_RADIUS = dict(initial_radius=1e-310, min_radius=0.0, function_tolerance=0.0, parameter_tolerance=0.0, gradient_tolerance=0.0)
+DENORMAL_RADIUS_SEED, DENORMAL_RADIUS_N = 105, 5
+
+
+def denormal_radius_scene():
+    return make_local_scene(np.random.default_rng(DENORMAL_RADIUS_SEED), DENORMAL_RADIUS_N)
+
+
 def options(full=False, **kw):
     o = dict(CERES_DEFAULTS)
     o.update(FULL_OPTIONS if full else LOCAL_OPTIONS)
@@ -387,7 +400,8 @@ def solve(prob, opts=None, dt=np.float64):
         cur = dict(iteration=iteration, step_is_valid=0, step_is_successful=0, cost=0.0, cost_change=0.0, gradient_max_norm=f(gmax),
                    step_norm=0.0, relative_decrease=0.0)
         diag = np.clip(H[:, np.arange(6), np.arange(6)], T(o["min_lm_diagonal"]), T(o["max_lm_diagonal"]))
-        D = np.sqrt(diag / radius)
+        with np.errstate(over="ignore"):                           # (a denormal radius: the quotient is inf and the solve fails, DENORMAL_RADIUS)
+            D = np.sqrt(diag / radius)
         A = H.copy()
         A[:, np.arange(6), np.arange(6)] += D * D
         y = block_tridiagonal_solve(A, Cc, b, S.segments)

@@ -24,9 +24,12 @@ optimum only, where the cost is 1e-28), and
 g the specification's gradient J^T r (tangent space, all variable poses) at its own final poses and tol the pose bound above: the
 first-order change of the cost over a box of half-width tol around the specification's solution.
 
-The sub-case "an item with a singular block ends with OV2_TERM_FAILURE" is not here: the factor's Jacobian blocks
-(I -+ J_c / 2) Adj(.) are never singular (the eigenvalues of I -+ hat(omega) / 2 are 1 and 1 -+ i theta / 2) and min_lm_diagonal > 0
-is added on top, so no finite input gives a failed factorisation."""
+OV2_TERM_FAILURE: no finite POSE or MEASUREMENT gives a failed factorisation -- the factor's Jacobian blocks (I -+ J_c / 2) Adj(.)
+are never singular (the eigenvalues of I -+ hat(omega) / 2 are 1 and 1 -+ i theta / 2) and min_lm_diagonal > 0 is added on top -- but
+a finite, accepted initial_radius does: at 1e-310 diag / radius overflows, every pivot is inf and every step invalid
+(posegraph_ref.DENORMAL_RADIUS).  On that case the longdouble specification does not overflow, so the condition above does not
+apply to it and only decisions and copied values are compared: iterations, termination, the trace's flags and radii (halving a
+double is exact), poses_out equal to the input bit for bit."""
 import os
 import subprocess
 
@@ -231,6 +234,64 @@ def test_batch_returns_the_bytes_of_the_single_calls(gpu_ctx):
             if p is not one:
                 assert x["iterations"] == 0 and x["termination"] == R.TERM_FUNCTION_TOL and np.array_equal(x["poses"], p["poses"])
     assert O.pose_graph_batch(gpu_ctx, [], opts) == []
+
+
+DENORMAL_VARIANTS = {"five_invalid": (dict(), "iiiiix", R.TERM_FAILURE, 5),
+                     "budget2": (dict(max_consecutive_invalid_steps=2), "iix", R.TERM_FAILURE, 2),
+                     "min_radius_after_invalid": (dict(min_radius=1e-312), "iiiis", R.TERM_MIN_RADIUS, 4)}
+
+
+def _denormal(ctx, variant, trace=True):
+    """-> (problem, the float64 specification's solve, the device's) under posegraph_ref.DENORMAL_RADIUS"""
+    from ov2slam_amd import optimizer as O
+    kw = dict(R.DENORMAL_RADIUS, **DENORMAL_VARIANTS[variant][0])
+    p = R.denormal_radius_scene()
+    return p, R.solve(p, R.options(**kw)), O.pose_graph(ctx, p, O.pose_graph_options(ctx.lib, **kw), trace=trace)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", sorted(DENORMAL_VARIANTS))
+def test_denormal_radius_fails_every_solve(gpu_ctx, variant):
+    """every linear solve fails: OV2_TERM_FAILURE (the radius floor, where it comes first: MIN_RADIUS) and the input poses"""
+    _, dec, term, its = DENORMAL_VARIANTS[variant]
+    p, want, got = _denormal(gpu_ctx, variant)
+    assert (want["decisions"], want["termination"], want["iterations"]) == (dec, term, its)
+    assert (got["iterations"], got["num_successful_steps"], got["termination"]) == (its, 1, term)
+    assert got["poses"].tobytes() == np.ascontiguousarray(p["poses"], np.float64).tobytes()
+    assert got["initial_cost"] == got["final_cost"] and abs(got["initial_cost"] - want["initial_cost"]) <= 1e-12 * want["initial_cost"]
+    flags = lambda tr: [(t["iteration"], t["step_is_valid"], t["step_is_successful"], t["trust_region_radius"]) for t in tr]
+    assert flags(got["trace"]) == flags(want["trace"]) and len(got["trace"]) == dec.count("i") + (term == R.TERM_MIN_RADIUS)
+    assert all(t["cost"] == got["initial_cost"] and t["cost_change"] == 0 and t["step_norm"] == 0 for t in got["trace"][1:])
+
+
+@pytest.mark.gpu
+def test_failing_item_in_a_batch_leaves_its_neighbours_alone(gpu_ctx):
+    """A batch has ONE option set, and with Jacobi scaling the LM diagonal lies in [min_lm_diagonal, 1): what fails under a radius
+    is decided by the problem's weights.  At initial_radius 5e-312 diag / radius overflows from diag = 9e-4 on: the denormal-radius
+    scene (sigma 1, diag near 1) fails every solve, two scenes whose edges weigh 1e-4 (diag <= 1e-5) do not -- their one step is
+    lost in rounding and the function tolerance ends them, as in the specification.  The batch [scene, failing, scene] returns the
+    bytes of the three single calls, the failing item its input poses."""
+    from ov2slam_amd import optimizer as O
+    kw = dict(R.DENORMAL_RADIUS, initial_radius=5e-312)
+    opts = O.pose_graph_options(gpu_ctx.lib, **kw)
+    weak = lambda q: dict(q, edge_sigma=np.full(len(q["edge_i"]), 1e4))
+    bad = R.denormal_radius_scene()
+    a, c = weak(case("local", 17)["prob"]), weak(case("far", 9)["prob"])
+    probs = [a, bad, c]
+    spec = [R.solve(q, R.options(**kw)) for q in probs]
+    assert [s["decisions"] for s in spec] == ["f", "iiiiix", "f"] and spec[1]["termination"] == R.TERM_FAILURE
+    singles = [O.pose_graph(gpu_ctx, q, opts) for q in probs]
+    batch = O.pose_graph_batch(gpu_ctx, probs, opts)
+    for q, w, s, x in zip(probs, spec, singles, batch):
+        for f in ("iterations", "num_successful_steps", "termination", "initial_cost", "final_cost"):
+            assert s[f] == x[f], f
+        assert s["poses"].tobytes() == x["poses"].tobytes()
+        assert (x["iterations"], x["num_successful_steps"], x["termination"]) == (w["iterations"], w["num_successful_steps"], w["termination"])
+        assert x["poses"].tobytes() == np.ascontiguousarray(q["poses"], np.float64).tobytes()       # (no step is taken in any of them)
+    assert batch[1]["termination"] == R.TERM_FAILURE and batch[0]["termination"] == batch[2]["termination"] == R.TERM_FUNCTION_TOL
+    # and beside items that do move: the failing scene under ordinary options is an ordinary item again
+    moving = O.pose_graph_batch(gpu_ctx, [case("local", 17)["prob"], bad, case("far", 9)["prob"]], O.pose_graph_options(gpu_ctx.lib))
+    assert all(m["termination"] != R.TERM_FAILURE and m["final_cost"] < m["initial_cost"] for m in moving)
 
 
 @pytest.mark.gpu

@@ -200,3 +200,27 @@ def test_specification_solves_a_small_loop():
     far = R.solve(R.make_local_scene(np.random.default_rng(24), 17, loop_far=True))
     assert "r" in far["decisions"]
     assert len(a["trace"]) == a["iterations"]                       # entry 0 + one per iteration, the one that ended inside the loop missing
+
+
+def test_denormal_radius_fails_every_solve():
+    """R.DENORMAL_RADIUS: five invalid steps, TERM_FAILURE, the input poses returned.  This case is EXEMPT from "float64 and longdouble
+    decide alike" (tests/test_gpu_posegraph.py's condition): diag / radius = 1e304 overflows in float64 only, the longdouble run takes
+    ordinary steps.  Only decisions and copied values are compared on it."""
+    p = R.denormal_radius_scene()
+    a = R.solve(p, R.options(**R.DENORMAL_RADIUS))
+    print("float64: %s, %d iterations, termination %d" % (a["decisions"], a["iterations"], a["termination"]))
+    assert a["decisions"] == "iiiiix" and a["termination"] == R.TERM_FAILURE and a["iterations"] == 5 and a["num_successful_steps"] == 1
+    assert np.array_equal(a["poses"], p["poses"]) and a["final_cost"] == a["initial_cost"] > 0
+    assert [t["trust_region_radius"] for t in a["trace"]] == [1e-310, 1e-310 / 2, 1e-310 / 2 / 4, 1e-310 / 2 / 4 / 8, 1e-310 / 2 / 4 / 8 / 16]
+    assert all(not t["step_is_valid"] and t["cost"] == a["initial_cost"] for t in a["trace"][1:])
+    b = R.solve(p, R.options(**R.DENORMAL_RADIUS), dt=np.longdouble)
+    assert "i" not in b["decisions"] and b["termination"] != R.TERM_FAILURE            # (why the case is exempt)
+    # the invalid budget, the radius floor (9.765625e-314 <= 1e-312 after four invalid steps) and the iteration budget inside the run
+    two = R.solve(p, R.options(**dict(R.DENORMAL_RADIUS, max_consecutive_invalid_steps=2)))
+    assert two["decisions"] == "iix" and two["termination"] == R.TERM_FAILURE and two["iterations"] == 2
+    floor = R.solve(p, R.options(**dict(R.DENORMAL_RADIUS, min_radius=1e-312)))
+    assert floor["decisions"] == "iiiis" and floor["termination"] == R.TERM_MIN_RADIUS and floor["iterations"] == 4
+    budget = R.solve(p, R.options(**dict(R.DENORMAL_RADIUS, max_iter=3)))
+    assert budget["decisions"] == "iiim" and budget["termination"] == R.TERM_NO_CONVERGENCE and budget["iterations"] == 3
+    for r in (two, floor, budget):
+        assert np.array_equal(r["poses"], p["poses"]) and r["final_cost"] == r["initial_cost"]

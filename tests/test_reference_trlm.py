@@ -115,6 +115,12 @@ def problems(oracle):
     out.append(("min radius", synth.make_ba_problem(8, 200, 6, stereo=True, seed=6), O(min_radius=2e4), TERM["MIN_RADIUS"], None))
     # motion-only BA (ceresPnP): one pose, pose-only blocks, no landmark columns
     out.append(("pnp", synth.make_pnp_problem(120, seed=2), O(max_iter=10, function_tolerance=1e-6), None, None))
+    # tests/trlm_cases.py: every linear solve fails (diag / radius overflows): five invalid steps end the solve; and a free keyframe
+    # without blocks whose pivot min_lm_diagonal / radius is 0, then a denormal, then 0 again: invalid, success, invalid
+    from tests import trlm_cases as TC
+    for name in ("ba/denormal", "irregular/recover_then_invalid"):
+        c = TC.BY_NAME[name]
+        out.append((name, TC.PROBLEMS[c.problem](), O(**c.options), c.termination, c.pattern))
     return out
 
 
