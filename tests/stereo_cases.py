@@ -6,16 +6,21 @@ A scene is a left / right pair cut from one texture at a horizontal disparity, w
   * keypoints in the interior AND within 28 px of every border, permuted so that both kinds share wavefronts and work-groups: on the
     SAD level the border keypoints walk through getLineMinSAD's `halfwin += ...` adjustments (half window 0, shrunk, grown),
   * 3-D priors on about 35 % of the keypoints, about 30 % of those far off: lost by the one-level pass and retried on the full pyramid.
-All keypoints lie inside the image (the contract of ov2_line_min_sad).  Pinhole only: every comparison against the device is exact."""
+All keypoints lie inside the image (the contract of ov2_line_min_sad).  Under the pinhole model every comparison against the device is
+exact.  fisheye_unrect gives the right camera (and the left) the fisheye model: there the device's undistortion of a right key point
+may differ from the oracle's in the last float bit (tan), so the status of a point whose oracle epipolar distance lies within
+GATE_MARGIN of the gate is left out of the comparison (near_gate); positions and every other status stay exact."""
 import numpy as np
 
 from ov2slam_amd import synth
+from tests.match_ref import FISHEYE4
 
 RADTAN = (-0.05, 0.01, 1e-4, -1e-4)
 F_XTRANS = np.array([[0, 0, 0], [0, 0, -1.0], [0, 1.0, 0]])       # identical pinhole cameras, pure x-translation: rows are epipolar lines
 SAD_WIN = 7                                                        # map_manager.cpp:431
+GATE, GATE_MARGIN = 2.0, 1e-3                                      # map_manager.cpp:568-590: epi_err <= 2 px; see near_gate below
 
-# name -> w, h, disparity, interior / border keypoints, LK windows, nklt_pyr_lvl, rectified, distortion
+# name -> w, h, disparity, interior / border keypoints, LK windows, nklt_pyr_lvl, rectified, distortion, camera model (pinhole if absent)
 SPECS = {
     "euroc_half":        dict(w=376, h=240, disp=12, n_inner=70, n_edge=60, wins=(9,), lvl=3, rect=True, D=None),
     "euroc_half_unrect": dict(w=376, h=240, disp=12, n_inner=70, n_edge=60, wins=(9,), lvl=3, rect=False, D=RADTAN),
@@ -23,6 +28,7 @@ SPECS = {
     "odd_w11_unrect":    dict(w=161, h=121, disp=6, n_inner=40, n_edge=40, wins=(11,), lvl=1, rect=False, D=RADTAN),
     "flat_strip":        dict(w=264, h=100, disp=8, n_inner=50, n_edge=50, wins=(9,), lvl=3, rect=True, D=None),
     "w5_w13":            dict(w=161, h=121, disp=6, n_inner=40, n_edge=40, wins=(5, 13), lvl=3, rect=True, D=None),
+    "fisheye_unrect":    dict(w=161, h=121, disp=6, n_inner=40, n_edge=40, wins=(9,), lvl=1, rect=False, D=FISHEYE4, model="fisheye"),
 }
 NAMES = tuple(SPECS)
 CASE_WINS = tuple((name, win) for name in NAMES for win in SPECS[name]["wins"])
@@ -106,13 +112,34 @@ def case(name, win=None, seed=None, contrast=False):
     K = (0.61 * w, 0.608 * w, 0.488 * w, 0.517 * h)
     iK = np.linalg.inv(np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1.0]]))
     c = dict(name=name, w=w, h=h, disp=s["disp"], left=l, right=r, kps=kps, priors3d=priors_3d(kps, s["disp"], rng), K=K, D=s["D"],
-             rect=s["rect"], Frl=None if s["rect"] else F_XTRANS.copy(), win=win, nklt_pyr_lvl=s["lvl"], _runs={})
-    c["kps_unpx"] = O.compute_keypoints(O.CAM_PINHOLE, K, s["D"], iK, kps)[0]
+             rect=s["rect"], Frl=None if s["rect"] else F_XTRANS.copy(), win=win, nklt_pyr_lvl=s["lvl"], _runs={},
+             model=s.get("model", "pinhole"))
+    c["kps_unpx"] = O.compute_keypoints(_model(O, c), K, s["D"], iK, kps)[0]
     c["opl"], c["opr"] = O.Pyramid(l, win, MAX_LEVEL), O.Pyramid(r, win, MAX_LEVEL)
     assert c["opl"].levels == MAX_LEVEL + 1
     c["ok"], c["right_px"] = oracle_run(c)
+    c["near_gate"] = near_gate(c)
     _cache[key] = c
     return c
+
+
+def _model(O, c):
+    return O.CAM_FISHEYE if c["model"] == "fisheye" else O.CAM_PINHOLE
+
+
+def near_gate(c):
+    """The tracked key points whose status a last-bit difference in the right key point's undistortion could turn: those whose oracle
+    epipolar distance lies within GATE_MARGIN of the gate.  One float ulp on an undistorted pixel below 256 is 3.1e-5 px and the
+    distance moves by at most that much per coordinate, so 1e-3 px is a margin of thirty such steps.  Pinhole: nobody, the undistortion
+    is exact."""
+    from oracle import oracle as O
+    n = len(c["kps"])
+    if c["model"] != "fisheye":
+        return np.zeros(n, bool)
+    tracked = (c["right_px"] != 0).any(axis=1)
+    err = O.stereo_epipolar_check(c["rect"], F_XTRANS if c["Frl"] is None else c["Frl"], _model(O, c), c["K"], c["D"], c["kps_unpx"], c["right_px"])[2]
+    assert np.array_equal(tracked & (err <= GATE), c["ok"])           # the gate as the flow applies it
+    return tracked & (np.abs(err.astype(np.float64) - GATE) <= GATE_MARGIN)
 
 
 def prefix_priors(c, n):
@@ -128,7 +155,7 @@ def oracle_run(c, n=None, nklt_pyr_lvl=None, float_acc=False):
     key = (n, lvl, float_acc)
     if key not in c["_runs"]:
         with O.lk_acc_mode(O.LK_ACC_FLOAT_UI4 if float_acc else O.LK_ACC_INT64):
-            c["_runs"][key] = O.stereo_matching(c["opl"], c["opr"], c["kps"][:n], c["kps_unpx"][:n], O.CAM_PINHOLE, c["K"], c["D"], c["rect"],
+            c["_runs"][key] = O.stereo_matching(c["opl"], c["opr"], c["kps"][:n], c["kps_unpx"][:n], _model(O, c), c["K"], c["D"], c["rect"],
                                                 Frl=c["Frl"], win=c["win"], nklt_pyr_lvl=lvl, priors3d=prefix_priors(c, n))
     return c["_runs"][key]
 

@@ -19,6 +19,7 @@ import pytest
 import ov2slam_amd
 from ov2slam_amd import _lib as L
 from ov2slam_amd import pose
+from tests import camera_cases as CAM
 from tests import createkf_cases as CC
 from tests import createkf_ref as CR
 from tests.match_ref import _inv_act
@@ -64,6 +65,7 @@ def _mono_args(cal, f, kf):
     """a trackMono step on frame f: the keypoints of the keyframes installed last (kf[b] = (px, lmid) or None), map points that project
     onto the true track under the true pose"""
     rng = np.random.default_rng(700 + f)
+    Kc = tuple(float(v) for v in cal.K)
     kps = np.zeros((BATCH, N_MAX, 2), np.float32); wpt = np.zeros((BATCH, N_MAX, 3)); is3d = np.zeros((BATCH, N_MAX), np.uint8)
     lmid = np.zeros((BATCH, N_MAX), np.int32); n = np.zeros(BATCH, np.int32)
     for b in range(BATCH):
@@ -81,9 +83,9 @@ def _mono_args(cal, f, kf):
             wpt[b, i] = _inv_act(T, Pc[i])
         kps[b, :m], lmid[b, :m], n[b] = px, ids, m
         is3d[b, :m] = rng.uniform(size=m) < 0.7
-    fkf = dict(_epi_params(True, False)["fkf"], nbmaxkps=CC.BASE["nbmaxkps"])
+    fkf = dict(_epi_params(True, False, Kc=Kc)["fkf"], nbmaxkps=CC.BASE["nbmaxkps"])
     seeds = lambda: rng.integers(0, 1 << 63, BATCH).astype(np.uint64) * np.uint64(2) + np.uint64(1)
-    return ((_imgs(f), kps, wpt, is3d, n, _params(pose.LMEDS, False), dict(_epi_params(True, False), fkf=fkf), np.zeros(BATCH, np.uint8), seeds(),
+    return ((_imgs(f), kps, wpt, is3d, n, _params(pose.LMEDS, False, Kc), dict(_epi_params(True, False, Kc=Kc), fkf=fkf), np.zeros(BATCH, np.uint8), seeds(),
              lmid, np.full(BATCH, 3, np.int32), seeds(), np.full(BATCH, 10.0 + f * DT + 0.02), np.array([100 * b + f for b in range(BATCH)], np.int32)),
             dict(localba_is_on=np.zeros(BATCH, np.uint8), dop3p=False, n_rows=40))
 
@@ -110,13 +112,14 @@ def _round(ctx, t, cal, ri, detector, how, state):
     return t.createKeyframeEnd(out=_poison())
 
 
-def _play(ctx, detector, how):
+def _play(ctx, detector, how, camera=None):
     """frame 0 and its round, a trackMono step on frame 1, the rounds of frame 1, a trackMono step on frame 2 -- on a fresh tracker,
-    through 'route', 'fused' (the one-call form) or 'halves'.  Computed once and shared; nobody changes a result."""
-    key = (detector, how)
+    through 'route', 'fused' (the one-call form) or 'halves', under the EuRoC calibration or a camera of tests/camera_cases.py.
+    Computed once and shared; nobody changes a result."""
+    key = (detector, how) if camera is None else (detector, how, camera)
     if key in _RUNS:
         return _RUNS[key]
-    cal = _cal(ctx)
+    cal = CAM.calibration(ctx, camera) if camera else _cal(ctx)
     t = _tracker(ctx, cal)
     state = _state0(detector)
     for b in range(BATCH):
@@ -125,7 +128,7 @@ def _play(ctx, detector, how):
     rounds, steps = [], []
     for f in range(CC.NFRAMES):
         if f > 0:
-            t.setPose(f, _invert(_wrong(_invert(_truth(f)[f]), np.random.default_rng(40 + f))))      # item f: the rule fires
+            t.setPose(f, _invert(_wrong(_invert(_truth(f)[f]), np.random.default_rng(40 + f), float(cal.K[0]))))      # item f: the rule fires
         a, kw = _mono_args(cal, f, kf)
         steps.append(_mono_step(t, a, kw))
         for b in range(BATCH):                                         # the estimator puts the frames where they belong
@@ -170,6 +173,35 @@ def test_fused_call_equals_the_route(gpu_ctx, detector):
     A, B = _play(gpu_ctx, detector, "route"), _play(gpu_ctx, detector, "fused")
     _show(detector, A)
     _same_play(A, B, detector)
+
+
+@pytest.mark.parametrize("camera", CAM.ADDED)
+def test_fused_call_equals_the_route_under_added_cameras(gpu_ctx, oracle, camera):
+    """The single-scale play under the added cameras of tests/camera_cases.py: fused against route byte for byte, and every created
+    keyframe's unpx / bv equal ov2_compute_keypoints on its px as bits and the oracle within the camera's bound; the same for
+    lastKeypoints after the trackMono steps in between."""
+    cal = CAM.calibration(gpu_ctx, camera)
+    A, B = _play(gpu_ctx, "singlescale", "route", camera), _play(gpu_ctx, "singlescale", "fused", camera)
+    _show(camera, A)
+    _same_play(A, B, camera)
+    created = 0
+    for r in B["rounds"]:
+        for b, rec in enumerate(r["recs"]):
+            if rec["action"] != L.OV2_CKF_CREATED or not rec["n_kf"]:
+                continue
+            m = rec["n_kf"]
+            px = np.ascontiguousarray(r["out"]["px"][b, :m])
+            su, sb = cal.computeKeypoints(px)
+            assert np.array_equal(r["out"]["unpx"][b, :m].view(np.uint32), su.view(np.uint32)), (r["name"], b)
+            assert np.array_equal(r["out"]["bv"][b, :m].view(np.uint64), sb.view(np.uint64)), (r["name"], b)
+            CAM.assert_keypoints_match_oracle(oracle, camera, px, su, sb)
+            created += 1
+    assert created >= 8
+    for f, s in enumerate(B["steps"]):
+        n = np.array([len(k[0]) for k in s["kp"]])
+        CAM.assert_step_anchor(gpu_ctx, oracle, cal, camera, dict(n=n), s)
+    for f in (1, 2):
+        assert A["steps"][f]["rule"][f], (f, A["steps"][f]["rule"])
 
 
 @pytest.mark.parametrize("detector", ["singlescale", "gridfast"])

@@ -18,6 +18,7 @@ import pytest
 import ov2slam_amd
 from ov2slam_amd import _lib as L
 from ov2slam_amd import keyframe, pose
+from tests import camera_cases as CC
 from tests import fivept_ref as E5
 from tests import frameepi_ref as R
 from tests import framepose_ref as F
@@ -34,8 +35,8 @@ I7 = np.array([0, 0, 0, 0, 0, 0, 1.0])
 EPI_ROWS = 48
 
 
-def _epi_params(stereo, mono, n_rows=EPI_ROWS):
-    return dict(fkf=KF.make_params(K=K, img_w=W, img_h=H, stereo=stereo), max_iterations=100, threshold=E5.threshold_of(3.0, K[0], K[1]),
+def _epi_params(stereo, mono, n_rows=EPI_ROWS, Kc=K):
+    return dict(fkf=KF.make_params(K=Kc, img_w=W, img_h=H, stereo=stereo), max_iterations=100, threshold=E5.threshold_of(3.0, Kc[0], Kc[1]),
                 probability=0.99, fransac_err=3.0, mono=mono, n_rows=n_rows)
 
 
@@ -83,11 +84,11 @@ def _rot_of(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-def _keyframe(rng, T, Pc, ids, pointed, planted, mode):
+def _keyframe(rng, T, Pc, ids, pointed, planted, mode, Kc=K):
     """the cloud Pc (points in the current camera, whose world-to-camera pose is T) seen from the keyframe's camera.  ids: the id of
     the map point each slot REALLY shows; pointed: slot -> the id it carries instead (an entry of the keyframe's own, somewhere in the
     image); planted: slots that must keep their counterpart.  -> dict(lmid ascending, unpx, bv, Twc), at most N_MAX entries"""
-    fx, fy, cx, cy = K
+    fx, fy, cx, cy = Kc
     m = len(Pc)
     same = mode == "same"
     Rrel = np.eye(3) if same else _aa(np.array([0.02, -0.03, 0.01]) * rng.uniform(0.6, 1.4))
@@ -119,6 +120,7 @@ def _inputs(name, cal):
     """the per-step arguments of a sequence (a function of the name alone)"""
     seqs, rng, steps = _seqs(), np.random.default_rng(len(name) + 41), []
     spec, cfg = SPECS[name]
+    Kc = tuple(float(v) for v in cal.K)
     prev_idx = 0
     for f, sp in enumerate(spec):
         cur_idx = prev_idx if sp.get("repeat") else prev_idx + 1
@@ -155,9 +157,9 @@ def _inputs(name, cal):
             nfr = int(round(sp.get("frac", [0] * na)[b] * m))
             for x in list(three[2 * s3:2 * s3 + p3]) + list(rng.permutation(m)[:nfr]):
                 pointed[int(x)] = ids[x] = 100000 + len(pointed)
-            kf = None if mode == "none" else _keyframe(rng, T, Pc, real, pointed, planted, mode)
+            kf = None if mode == "none" else _keyframe(rng, T, Pc, real, pointed, planted, mode, Kc)
             kps[b, :m], is3d[b, :m], lmid[b, :m] = k, d3, ids
-            Tp = _wrong(T, rng) if sp.get("wrong_pose") else _near(T, rng)
+            Tp = _wrong(T, rng, Kc[0]) if sp.get("wrong_pose") else _near(T, rng)
             Tcw[b], Twc[b] = Tp, _invert(Tp)
             kfs.append(kf)
         req = np.zeros(BATCH, np.uint8); req[:na] = sp.get("req", [0] * na)
@@ -167,7 +169,8 @@ def _inputs(name, cal):
                           epi_seed=rng.integers(0, 1 << 63, BATCH).astype(np.uint64) * np.uint64(2) + np.uint64(1),
                           lmid=lmid, nbkfs=nbkfs, keyframes=kfs,
                           scale=rng.integers(0, 4, (BATCH, N_MAX)).astype(np.int32) if sp.get("scale") else None,
-                          params=_params(sp.get("mode", pose.LMEDS), cfg["mono"]), epi_params=_epi_params(cfg["stereo"], cfg["mono"], sp.get("epi_rows", EPI_ROWS)),
+                          params=_params(sp.get("mode", pose.LMEDS), cfg["mono"], Kc),
+                          epi_params=_epi_params(cfg["stereo"], cfg["mono"], sp.get("epi_rows", EPI_ROWS), Kc),
                           dop3p=sp.get("dop3p", False), n_rows=sp.get("n_rows", 0), klt_use_prior=True))
         prev_idx = cur_idx
     return steps
@@ -230,16 +233,18 @@ def _call(t, s, how, ctx):
     return dict(out=out, st=st, rule=rule, poses=poses, inputs=inputs, kp=kp, pr=pr, epis=epis, einputs=einputs)
 
 
-def _play(ctx, name, how):
+def _play(ctx, name, how, camera=None):
     """the sequence `name` on a fresh tracker, through route() ('route'), the one-call fused step ('fused'), its two halves ('halves')
-    or the pose step without the filter ('f16').  Computed once per (name, how) and shared between the tests; nobody changes a result."""
-    if (name, how) not in _RUNS:
-        cal = ov2slam_amd.CameraCalibration(ctx, "pinhole", *K, D=DIST)
+    or the pose step without the filter ('f16'), under the EuRoC calibration or a camera of tests/camera_cases.py.  Computed once per
+    (name, how, camera) and shared between the tests; nobody changes a result."""
+    key = (name, how) if camera is None else (name, how, camera)
+    if key not in _RUNS:
+        cal = CC.calibration(ctx, camera) if camera else ov2slam_amd.CameraCalibration(ctx, "pinhole", *K, D=DIST)
         t = _tracker(ctx, cal)
         _first(t, how if how in ("route", "f16") else "fused")
-        _RUNS[(name, how)] = [_call(t, s, how, ctx) for s in _inputs(name, cal)]
+        _RUNS[key] = [_call(t, s, how, ctx) for s in _inputs(name, cal)]
         t.close()
-    return _RUNS[(name, how)]
+    return _RUNS[key]
 
 
 def _same_epi_step(a, b, where):
@@ -266,6 +271,23 @@ def test_fused_step_equals_the_route(gpu_ctx, name):
     _show(name, A)
     for f, (a, b) in enumerate(zip(A, B)):
         _same_epi_step(a, b, (name, f))
+
+
+@pytest.mark.parametrize("camera", CC.ADDED)
+def test_fused_step_equals_the_route_under_added_cameras(gpu_ctx, oracle, camera):
+    """The stereo sequence under the added cameras of tests/camera_cases.py: fused against route byte for byte, and after every step
+    every item is tied to the reference (camera_cases.assert_step_anchor: lastKeypoints == ov2_compute_keypoints as bits == the
+    oracle within the camera's bound; lastPriors == ov2_klt_priors_batch as bits)."""
+    cal = CC.calibration(gpu_ctx, camera)
+    steps = _inputs("stereo", cal)
+    A, B = _play(gpu_ctx, "stereo", "route", camera), _play(gpu_ctx, "stereo", "fused", camera)
+    _show(camera, A)
+    assert len(A) == len(B) == len(steps)
+    for f, (s, a, b) in enumerate(zip(steps, A, B)):
+        _same_epi_step(a, b, (camera, f))
+        CC.assert_step_anchor(gpu_ctx, oracle, cal, camera, s, b)
+    # the filter still filters and the pose still solves under this camera
+    assert A[0]["epis"][0]["action"] == keyframe.EPIF_FILTERED and A[0]["poses"][0]["action"] == pose.POSE_OK
 
 
 def test_the_route_exercises_what_the_cases_are_for(gpu_ctx):

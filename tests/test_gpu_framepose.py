@@ -11,6 +11,7 @@ import pytest
 import ov2slam_amd
 from ov2slam_amd import _lib as L
 from ov2slam_amd import pose
+from tests import camera_cases as CC
 from tests import framepose_ref as F
 from tests.match_ref import _inv_act, _rand_pose
 from tests.test_gpu_priors_lockstep import BATCH, DIST, H, K, N_MAX, NFRAMES, W, _wrong
@@ -22,9 +23,9 @@ COUNTS = [64, 37, 0]
 I7 = np.array([0, 0, 0, 0, 0, 0, 1.0])
 
 
-def _params(mode=pose.LMEDS, mono=False):
-    return dict(pnp=dict(nmaxiter=5, chi2th=5.9915, use_robust=True, apply_l2_after_robust=True, K=np.array(K)),
-                p3p=dict(mode=mode, max_iterations=40, threshold=pose.threshold(3.0, K[0], K[1]), probability=0.99, boptimize=False), mono=mono)
+def _params(mode=pose.LMEDS, mono=False, Kc=K):
+    return dict(pnp=dict(nmaxiter=5, chi2th=5.9915, use_robust=True, apply_l2_after_robust=True, K=np.array(Kc)),
+                p3p=dict(mode=mode, max_iterations=40, threshold=pose.threshold(3.0, Kc[0], Kc[1]), probability=0.99, boptimize=False), mono=mono)
 
 
 def _invert(T):
@@ -55,7 +56,12 @@ ALT = [dict(counts=[64, 37, 0], dop3p=True, n_rows=40),
        dict(counts=[37, 0, 64], dop3p=True, n_rows=40, mode=pose.RANSAC, mono=True),
        dict(counts=[20, 20, 20], n3d=[3, 4, 5], req=[1, 1, 1], n_rows=40, exact=True),
        dict(counts=[64, 64, 64], req=[0, 1, 0], n_rows=7, scale=True)]
+# fold: one step for the camera fisheye_fold (tests/camera_cases.py).  Half of the key points lie just beyond the radius at which its
+#       undistortion fails and have map points that project next to them (camera_cases.fold_rays), so they track, and the pose set
+#       carries (-1e6, -1e6) pixels and their bearings into P3P (requested on both items) and both PnP passes
+FOLD = [dict(counts=[64, 37, 0], req=[1, 1, 0], n_rows=40, fold=True)]
 SPECS = dict(main=MAIN, alt=ALT)
+CAMERA_SPECS = dict(SPECS, fold=FOLD)
 
 _SEQS, _RUNS = {}, {}
 
@@ -69,7 +75,8 @@ def _seqs():
 def _inputs(name, cal):
     """the per-step arguments of a sequence (a function of the name alone)"""
     seqs, rng, steps = _seqs(), np.random.default_rng(len(name) + 23), []
-    for f, sp in enumerate(SPECS[name]):
+    Kc = tuple(float(v) for v in cal.K)
+    for f, sp in enumerate(CAMERA_SPECS[name]):
         na = len(sp["counts"])
         kps = np.zeros((BATCH, N_MAX, 2), np.float32); wpt = np.zeros((BATCH, N_MAX, 3)); is3d = np.zeros((BATCH, N_MAX), np.uint8)
         Tcw, Twc = np.tile(I7, (BATCH, 1)), np.tile(I7, (BATCH, 1))
@@ -77,6 +84,8 @@ def _inputs(name, cal):
         for b in range(na):
             m = int(n[b])
             k = np.stack([rng.uniform(20, W - 20, m), rng.uniform(20, H - 20, m)], 1).astype(np.float32)
+            if sp.get("fold"):
+                k = CC.fold_ring_points(m, rng)
             true = seqs[b][1](k.astype(np.float64), f, f + 1)
             gt = (true + rng.normal(0, 0.0 if sp.get("exact") else 0.3, (m, 2))).astype(np.float32)
             T = _rand_pose(rng)
@@ -88,18 +97,20 @@ def _inputs(name, cal):
                 bad = np.nonzero(d3)[0][::8]
                 gt[bad, 0] += np.where(gt[bad, 0] < W / 2, 20.0, -20.0).astype(np.float32)
             bv = cal.computeKeypoints(gt)[1] if m else np.zeros((0, 3))
+            if sp.get("fold") and m:
+                bv = CC.fold_rays(gt, bv)
             for i in range(m):
                 wpt[b, i] = _inv_act(T, bv[i] / bv[i][2] * rng.uniform(2, 10))
             kps[b, :m], is3d[b, :m] = k, d3
             Tp = _near(T, rng)
             if sp.get("wrong_pose"):
-                Tp = _wrong(T, rng)
+                Tp = _wrong(T, rng, Kc[0])
             Tcw[b], Twc[b] = Tp, _invert(Tp)
         req = np.zeros(BATCH, np.uint8); req[:na] = sp.get("req", [0] * na)
         steps.append(dict(imgs=[seqs[b][0][f + 1] for b in range(na)], kps=kps, wpt=wpt, is3d=is3d, Tcw=Tcw, n=n, Twc=Twc, p3p_req=req,
                           seed=rng.integers(0, 1 << 63, BATCH).astype(np.uint64) * np.uint64(2) + np.uint64(1),
                           scale=rng.integers(0, 4, (BATCH, N_MAX)).astype(np.int32) if sp.get("scale") else None,
-                          params=_params(sp.get("mode", pose.LMEDS), sp.get("mono", False)), dop3p=sp.get("dop3p", False),
+                          params=_params(sp.get("mode", pose.LMEDS), sp.get("mono", False), Kc), dop3p=sp.get("dop3p", False),
                           n_rows=sp.get("n_rows", 0), klt_use_prior=sp.get("use_prior", True)))
     return steps
 
@@ -138,16 +149,18 @@ def _call(t, s, how, ctx):
     return dict(out=out, st=st, rule=rule, poses=poses, inputs=inputs, kp=kp, pr=pr)
 
 
-def _play(ctx, name, how):
+def _play(ctx, name, how, camera=None):
     """the sequence `name` on a fresh tracker, through route() ('route'), the one-call fused step ('fused') or its two halves
-    ('halves').  Computed once per (name, how) and shared between the tests; nobody changes a result."""
-    if (name, how) not in _RUNS:
-        cal = ov2slam_amd.CameraCalibration(ctx, "pinhole", *K, D=DIST)
+    ('halves'), under the EuRoC calibration or a camera of tests/camera_cases.py.  Computed once per (name, how, camera) and shared
+    between the tests; nobody changes a result."""
+    key = (name, how) if camera is None else (name, how, camera)
+    if key not in _RUNS:
+        cal = CC.calibration(ctx, camera) if camera else ov2slam_amd.CameraCalibration(ctx, "pinhole", *K, D=DIST)
         t = _tracker(ctx, cal)
         _first(t, "route" if how == "route" else "fused")
-        _RUNS[(name, how)] = [_call(t, s, how, ctx) for s in _inputs(name, cal)]
+        _RUNS[key] = [_call(t, s, how, ctx) for s in _inputs(name, cal)]
         t.close()
-    return _RUNS[(name, how)]
+    return _RUNS[key]
 
 
 def _same_step(a, b, where):
@@ -175,6 +188,33 @@ def test_fused_step_equals_the_route(gpu_ctx, name):
                         for p, i in zip(a["poses"], a["inputs"])], "rule", a["rule"].astype(int).tolist())
     for f, (a, b) in enumerate(zip(A, B)):
         _same_step(a, b, (name, f))
+
+
+@pytest.mark.parametrize("camera", CC.ADDED_FOLD)
+def test_fused_step_equals_the_route_under_added_cameras(gpu_ctx, oracle, camera):
+    """The main sequence under the added cameras, and one step under fisheye_fold: fused against route byte for byte as above, and
+    after every step every item is tied to the reference (camera_cases.assert_step_anchor): lastKeypoints equals the stand-alone
+    call on the output positions as bits, that call equals the oracle within the camera's bound, and the priors derived on the
+    device equal ov2_klt_priors_batch as bits."""
+    name = "fold" if camera == "fisheye_fold" else "main"
+    cal = CC.calibration(gpu_ctx, camera)
+    steps = _inputs(name, cal)
+    A, B = _play(gpu_ctx, name, "route", camera), _play(gpu_ctx, name, "fused", camera)
+    assert len(A) == len(B) == len(steps)
+    for f, (s, a, b) in enumerate(zip(steps, A, B)):
+        _same_step(a, b, (camera, name, f))
+        CC.assert_step_anchor(gpu_ctx, oracle, cal, camera, s, b)
+    if camera == "fisheye_fold":
+        # the pose sets of both items hold failed and successful undistortions, the search and both passes ran on them
+        for bi in (0, 1):
+            m, slots, tab = B[0]["inputs"][bi]
+            kind = CC.fisheye_kinds(camera, B[0]["out"][bi][slots])
+            assert (kind != CC.OK).sum() >= 5 and (kind == CC.OK).sum() >= 5, (bi, CC.population(camera, B[0]["out"][bi][slots]))
+            p = B[0]["poses"][bi]
+            assert p["ran_p3p"] and len(tab) == 40
+    else:
+        assert [p["action"] for p in A[0]["poses"]] == [pose.POSE_OK, pose.POSE_OK, pose.TOO_FEW]
+        assert A[2]["rule"].tolist() == [False, True, True]
 
 
 def test_the_route_exercises_what_the_cases_are_for(gpu_ctx):

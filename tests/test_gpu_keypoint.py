@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import ov2slam_amd
+from tests import camera_cases as CC
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +49,27 @@ def test_fisheye(gpu_ctx, oracle):
     assert (u != ru).mean() < 0.01
     same = np.all(u == ru, axis=1)
     assert np.array_equal(b[same], rb[same])
+
+
+@pytest.mark.parametrize("name", ["fisheye_mild", "fisheye_wide", "fisheye_fold"])
+def test_fisheye_failure_branch_clamp_and_tan_bound(gpu_ctx, oracle, name):
+    """The cameras of tests/camera_cases.py that leave the mild regime.  The Newton loop is + - * / in fp64 without contraction: the
+    set of failed points equals the oracle's, their (-1e6, -1e6) pixels and bearings are equal as bits.  A successful point may
+    differ only where tan's last double bit decides the float pixel (the points camera_cases.tan_sensitive names, counted from the
+    reference's own arithmetic), and then by one float ulp; bearings are equal as bits wherever the pixel is."""
+    cal = CC.calibration(gpu_ctx, name)
+    for n in (1, 308, 5000):
+        px = CC.points(n, n)
+        u, b = cal.computeKeypoints(px)
+        kind = CC.fisheye_kinds(name, px)
+        if name == "fisheye_fold" and n > 1:
+            assert CC.fold_populated(px)
+            failed = kind != CC.OK
+            assert (u[failed] == CC.FAIL_PX).all() and np.array_equal(b[failed].view(np.uint64), CC.bearings(name, u[failed]).view(np.uint64))
+        if name == "fisheye_wide" and n > 1:
+            assert CC.fisheye_newton(name, px)["clamped"].any() and (kind == CC.OK).all()
+        differ = CC.assert_keypoints_match_oracle(oracle, name, px, u, b)
+        print("%s n=%d: %d points differ from the oracle, %d are tan-sensitive" % (name, n, differ, CC.tan_sensitive(name, px)[0].sum()))
 
 
 def test_empty_and_errors(gpu_ctx):

@@ -9,6 +9,7 @@ import ov2slam_amd
 from ov2slam_amd import synth, stereo
 from ov2slam_amd import _lib as L
 
+from tests import camera_cases as CC
 from tests.test_gpu_tracker import _sequence, _points, _oracle_frame, _bits, CLIP
 
 pytestmark = pytest.mark.gpu
@@ -29,13 +30,36 @@ def _pack(batch, n_max, per_item):
 @pytest.mark.parametrize("impl", ["wave", "row"])
 @pytest.mark.parametrize("wh,use_clahe", [((752, 480), True), ((1241, 376), True), ((376, 240), False)])
 def test_lockstep_equals_single_trackers(gpu_ctx, oracle, wh, use_clahe, impl):
+    _equals_single_trackers(gpu_ctx, oracle, wh, use_clahe, impl)
+
+
+@pytest.mark.parametrize("camera", CC.ADDED_FOLD)
+def test_lockstep_equals_single_trackers_under_added_cameras(gpu_ctx, oracle, camera):
+    """The 376 x 240 case above under the added cameras of tests/camera_cases.py, with ~400 key points per item (one per 15 px cell).
+    The item stride of the lock-step k_compute_keypoints launch is the thing under test -- with fisheye_fold every item writes
+    failure pixels: after every frame every item's lastKeypoints equals the stand-alone call on its output positions as bits, and
+    that call equals the oracle within the camera's stand-alone bound."""
+    _equals_single_trackers(gpu_ctx, oracle, (CC.W, CC.H), False, "wave", camera=camera)
+
+
+def _keypoints_anchor(oracle, cal, camera, out, got):
+    """lastKeypoints == ov2_compute_keypoints (bits) == the oracle (the camera's stand-alone bound)"""
+    su, sb = cal.computeKeypoints(out)
+    assert np.array_equal(_bits(got[0]), _bits(su)) and np.array_equal(got[1].view(np.uint64), sb.view(np.uint64))
+    CC.assert_keypoints_match_oracle(oracle, camera, out, su, sb)
+    if camera == "fisheye_fold":
+        assert CC.fold_populated(out), CC.population(camera, out)
+
+
+def _equals_single_trackers(gpu_ctx, oracle, wh, use_clahe, impl, camera=None):
     w, h = wh
+    cell = 15 if camera else 35
     batch, n_max, nframes = 5, 640, 6
     with gpu_ctx.options(track_impl=L.OV2_TRACK_IMPL_ROW if impl == "row" else L.OV2_TRACK_IMPL_WAVE):
         seqs = [_sequence(w, h, nframes, seed=40 + b) for b in range(batch)]
         length = [6, 6, 5, 4, 3]                                 # longest first: items drop out from the tail
         rngs = [np.random.default_rng(100 + b) for b in range(batch)]
-        cal = ov2slam_amd.CameraCalibration(gpu_ctx, "pinhole", *K_EUROC, D=D_EUROC)
+        cal = CC.calibration(gpu_ctx, camera) if camera else ov2slam_amd.CameraCalibration(gpu_ctx, "pinhole", *K_EUROC, D=D_EUROC)
         bt = ov2slam_amd.LockstepTracker(gpu_ctx, batch, w, h, use_clahe=use_clahe, fclahe_val=CLIP, nbmaxkps=n_max)
         bt.setCalibration(cal)
         singles = []
@@ -51,7 +75,7 @@ def test_lockstep_equals_single_trackers(gpu_ctx, oracle, wh, use_clahe, impl):
             na = sum(1 for b in range(batch) if length[b] > f + 1)
             per = []
             for b in range(na):
-                k, p, hp_ = _points(w, h, seqs[b][1], f, rngs[b], 1.0, bad_frac=0.25)
+                k, p, hp_ = _points(w, h, seqs[b][1], f, rngs[b], 1.0, bad_frac=0.25, cell=cell)
                 m = len(k) - 7 * b                               # different counts per item
                 per.append((k[:m], p[:m], hp_[:m]))
             if f == 2:
@@ -78,6 +102,8 @@ def test_lockstep_equals_single_trackers(gpu_ctx, oracle, wh, use_clahe, impl):
                     bu, bb = bt.lastKeypoints(b, m)
                     su, sb = singles[b].lastKeypoints(m)
                     assert np.array_equal(_bits(bu), _bits(su)) and np.array_equal(bb.view(np.uint64), sb.view(np.uint64))
+                    if camera:
+                        _keypoints_anchor(oracle, cal, camera, out[b, :m], (bu, bb))
                 for lvl in range(4):
                     gi, _ = bt.cur_item(b).download(lvl)
                     si, _ = singles[b].cur_pyr.download(lvl)
@@ -191,20 +217,37 @@ def test_lockstep_pipeline(gpu_ctx, split):
 def test_lockstep_p3p_rule(gpu_ctx):
     """Priors so wrong in ONE item that fewer than a third survive the 2-level pass: that item's bp3preq_ is raised and its lost
     tracks restart from their keypoints (visual_front_end.cpp:225-230); the other items are untouched."""
-    w, h, batch, n_max = 752, 480, 3, 400
+    _p3p_rule(gpu_ctx, None, 752, 480, True, ov2slam_amd.CameraCalibration(gpu_ctx, "pinhole", *K_EUROC))
+
+
+@pytest.mark.parametrize("camera", CC.ADDED_FOLD)
+def test_lockstep_p3p_rule_under_added_cameras(gpu_ctx, oracle, camera):
+    """The rule on the 376 x 240 frame under the added cameras: the host's re-run (ov2_apply_p3p_rule) of item 1 must undistort with
+    the tracker's model and all of its coefficients.  Every item's lastKeypoints equals the stand-alone call as bits and the oracle
+    within the camera's bound; with fisheye_fold the re-run set holds failed and successful undistortions."""
+    _p3p_rule(gpu_ctx, oracle, CC.W, CC.H, False, CC.calibration(gpu_ctx, camera), camera=camera)
+
+
+def _p3p_rule(gpu_ctx, oracle, w, h, use_clahe, cal, camera=None):
+    batch, n_max, cell = 3, 400, 15 if camera else 35
     seqs = [_sequence(w, h, 2, seed=70 + b) for b in range(batch)]
     rng = np.random.default_rng(9)
-    cal = ov2slam_amd.CameraCalibration(gpu_ctx, "pinhole", *K_EUROC)
-    bt = ov2slam_amd.LockstepTracker(gpu_ctx, batch, w, h, fclahe_val=CLIP, nbmaxkps=n_max)
+    bt = ov2slam_amd.LockstepTracker(gpu_ctx, batch, w, h, use_clahe=use_clahe, fclahe_val=CLIP, nbmaxkps=n_max)
     bt.setCalibration(cal)
     z = np.zeros((batch, n_max, 2), np.float32)
     bt.trackFrame([s[0][0] for s in seqs], z, z, None, np.zeros(batch, np.int32))
-    per = [_points(w, h, seqs[b][1], 0, rng, 1.0, frac_prior=0.8, bad_frac=0.85 if b == 1 else 0.1, bad_sigma=40.0) for b in range(batch)]
+    per = [_points(w, h, seqs[b][1], 0, rng, 1.0, frac_prior=0.8, bad_frac=0.85 if b == 1 else 0.1, bad_sigma=40.0, cell=cell) for b in range(batch)]
     kps, pri, hp, n = _pack(batch, n_max, per)
     out, st, p3p = bt.trackFrame([s[0][1] for s in seqs], kps, pri, hp, n)
     assert list(p3p) == [False, True, False]
     for b in range(batch):
-        t = ov2slam_amd.VisualFrontEndTracker(gpu_ctx, w, h, fclahe_val=CLIP, nbmaxkps=n_max, use_graph=False)
+        if camera:
+            m = int(n[b])
+            _keypoints_anchor(oracle, cal, camera, out[b, :m], bt.lastKeypoints(b, m))
+            if camera == "fisheye_fold" and b == 1:
+                kind = CC.fisheye_kinds(camera, out[b, :m][(st[b, :m] & 2) > 0])
+                assert (kind == CC.OK).sum() >= 20 and (kind != CC.OK).sum() >= 20
+        t = ov2slam_amd.VisualFrontEndTracker(gpu_ctx, w, h, use_clahe=use_clahe, fclahe_val=CLIP, nbmaxkps=n_max, use_graph=False)
         t.setCalibration(cal)
         t.trackFrame(seqs[b][0][0], np.zeros((0, 2), np.float32), np.zeros((0, 2), np.float32), None)
         so, ss, sp = t.trackFrame(seqs[b][0][1], *per[b])

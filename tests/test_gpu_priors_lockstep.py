@@ -9,6 +9,7 @@ import pytest
 import ov2slam_amd
 from ov2slam_amd import _lib as L
 from ov2slam_amd import priors as PR
+from tests import camera_cases as CC
 from tests.match_ref import _inv_act, _rand_pose
 from tests.test_gpu_tracker import _bits, _sequence
 
@@ -22,22 +23,35 @@ LENGTH = [5, 5, 3]                                                # the last ite
 COUNTS = [64, 37, 0]
 
 
-def _wrong(T, rng):
-    """the pose turned by 0.15 rad about y: projections land ~35 px away, mostly still inside the image"""
-    s, c = np.sin(0.075), np.cos(0.075)
+def _wrong(T, rng, fx=K[0]):
+    """the pose turned by 0.15 rad about y (by more for a shorter focal length fx): projections land ~35 px away, mostly still inside
+    the image"""
+    half = 0.075 * (K[0] / fx)                                    # K[0] / K[0] == 1.0: the EuRoC case is what it was
+    s, c = np.sin(half), np.cos(half)
     x, y, z, w = T[3:]
     q = np.array([c * x + s * z, c * y + s * w, c * z - s * x, c * w - s * y])      # (0, s, 0, c) * q
     return np.concatenate([T[:3] + rng.normal(0, 0.05, 3), q / np.linalg.norm(q)])
 
 
 def test_map_form_equals_host_priors(gpu_ctx):
+    _map_form(gpu_ctx, None, None)
+
+
+@pytest.mark.parametrize("camera", CC.ADDED)
+def test_map_form_equals_host_priors_under_added_cameras(gpu_ctx, oracle, camera):
+    """The same sequence under the added cameras of tests/camera_cases.py: the fused prior kernel runs kp_project_dist's rational and
+    fisheye branches, and both trackers' lastKeypoints equal the stand-alone call as bits and the oracle within the camera's bound."""
+    _map_form(gpu_ctx, oracle, camera)
+
+
+def _map_form(gpu_ctx, oracle, camera):
     seqs = [_sequence(W, H, NFRAMES, seed=70 + b) for b in range(BATCH)]
     rng = np.random.default_rng(11)
-    cal = ov2slam_amd.CameraCalibration(gpu_ctx, "pinhole", *K, D=DIST)
+    cal = CC.calibration(gpu_ctx, camera) if camera else ov2slam_amd.CameraCalibration(gpu_ctx, "pinhole", *K, D=DIST)
     A = ov2slam_amd.LockstepTracker(gpu_ctx, BATCH, W, H, use_clahe=False, nbmaxkps=N_MAX)
     B = ov2slam_amd.LockstepTracker(gpu_ctx, BATCH, W, H, use_clahe=False, nbmaxkps=N_MAX)
     A.setCalibration(cal); B.setCalibration(cal)
-    P = dict(model="pinhole", K=K, D=DIST, img_w=W, img_h=H)
+    P = CC.params(camera) if camera else dict(model="pinhole", K=K, D=DIST, img_w=W, img_h=H)
     z2 = np.zeros((BATCH, N_MAX, 2), np.float32)
     first = [seqs[b][0][0] for b in range(BATCH)]
     A.trackFrame(first, z2, z2, None, np.zeros(BATCH, np.int32))
@@ -65,7 +79,7 @@ def test_map_form_equals_host_priors(gpu_ctx):
                 wpt[b, 0] = _inv_act(T, (30.0, 0.0, 1.0))         # one that projects outside: no prior
                 d3[0] = 1
             kps[b, :m], is3d[b, :m] = k, d3
-            Tcw[b] = _wrong(T, rng) if f == 1 else T              # frame 1: the motion model is wrong
+            Tcw[b] = _wrong(T, rng, cal.K[0]) if f == 1 else T    # frame 1: the motion model is wrong
             items.append(dict(Tcw=Tcw[b], px=k, is3d=d3, wpt=wpt[b, :m]))
         imgs = [seqs[b][0][f + 1] for b in range(na)]
         host = PR.klt_priors_batch(gpu_ctx, dict(P, klt_use_prior=use_prior), items)
@@ -84,6 +98,10 @@ def test_map_form_equals_host_priors(gpu_ctx):
             ua, ba = A.lastKeypoints(b, m)
             ub, bb = B.lastKeypoints(b, m)
             assert np.array_equal(_bits(ua), _bits(ub)) and np.array_equal(ba.view(np.uint64), bb.view(np.uint64)), (f, b)
+            if camera and m:
+                su, sb = cal.computeKeypoints(ob[b, :m])
+                assert np.array_equal(_bits(ub), _bits(su)) and np.array_equal(bb.view(np.uint64), sb.view(np.uint64)), (f, b)
+                CC.assert_keypoints_match_oracle(oracle, camera, ob[b, :m], su, sb)
             lp, lh = B.lastPriors(b, m)
             assert np.array_equal(_bits(lp), _bits(host[b]["prior"])) and np.array_equal(lh, host[b]["has_prior"]), (f, b)
             la, lha = A.lastPriors(b, m)

@@ -63,6 +63,36 @@ def test_epipolar_check_bit_exact(gpu_ctx, oracle):
                 assert np.abs(runpx - rr).max() <= 1.3e-4 and np.mean(ok == rok) > 0.995
 
 
+def test_epipolar_check_with_failed_right_undistortions(gpu_ctx, oracle):
+    """Right camera fisheye_fold (tests/camera_cases.py): beyond 103 px from the centre the right key point undistorts to
+    (-1e6, -1e6).  Those pairs are rejected exactly where the oracle rejects them, with the oracle's error as bits; every other pair
+    is exact too unless tan's last bit moves its float pixel."""
+    from tests import camera_cases as CC
+    rng = np.random.default_rng(8)
+    n = 500
+    rk = np.stack([rng.uniform(0, CC.W, n), rng.uniform(0, CC.H, n)], 1).astype(np.float32)
+    assert CC.fold_populated(rk)
+    failed = CC.fisheye_kinds("fisheye_fold", rk) != CC.OK
+    # left points on and about the epipolar line of the right point's undistortion where there is one, anywhere in the frame otherwise
+    lun = np.where(failed[:, None], rk, CC.oracle_keypoints(oracle, "fisheye_fold", rk)[0])
+    lun = (lun + np.stack([rng.uniform(0, 30, n), rng.normal(0, 1.5, n)], 1)).astype(np.float32)
+    sens = CC.tan_sensitive("fisheye_fold", rk)[0]
+    F = np.array([[0, 0, 0], [0, 0, -1.0], [0, 1.0, 0]])          # pure x-translation: rows are epipolar lines
+    cal = CC.calibration(gpu_ctx, "fisheye_fold")
+    for rect in (True, False):
+        out, runpx, err, ok = stereo.epipolar_check(gpu_ctx, rect, F, cal, lun, rk)
+        ro, rr, re, rok = oracle.stereo_epipolar_check(rect, F, cal.model, CC.intrinsics("fisheye_fold"), CC.coeffs("fisheye_fold"), lun, rk)
+        assert np.array_equal((rr == CC.FAIL_PX).all(axis=1), failed) and (runpx[failed] == CC.FAIL_PX).all()
+        assert np.array_equal(ok[failed], rok[failed]) and np.array_equal(err[failed].view(np.uint32), re[failed].view(np.uint32))
+        assert rok[failed].mean() < 0.05
+        assert rok[~failed].any() and not rok[~failed].all()
+        exact = ~sens
+        assert np.array_equal(out, ro)
+        assert np.array_equal(runpx[exact].view(np.uint32), rr[exact].view(np.uint32))
+        assert np.array_equal(err[exact].view(np.uint32), re[exact].view(np.uint32)) and np.array_equal(ok[exact], rok[exact])
+        assert (np.abs(runpx.astype(np.float64) - rr) <= np.spacing(np.abs(rr))).all()
+
+
 def test_stereo_matching_flow(gpu_ctx, oracle):
     """MapManager::stereoMatching data path on a synthetic rectified pair: SAD priors -> two fbKlt passes (3-D-prior failures
     retried from the first call's forward result, map_manager.cpp:533-538) -> gate, against oracle.stereo_matching, which

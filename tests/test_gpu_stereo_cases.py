@@ -2,7 +2,7 @@
 k_track_klt_w in lkw.hip) against oracle.stereo_matching and oracle.line_min_sad on the scenes of tests/stereo_cases.py, whose
 branch population tests/test_stereo_cases.py asserts on the oracle alone.  Everything bit for bit: stereo_ok as booleans, right_px as
 raw float32 bits.  Both tracking kernels, every window instance of the row kernel, both accumulator modes, rectified and
-non-rectified with distortion, partial wavefronts / work-groups, every nklt_pyr_lvl, and the batch form."""
+non-rectified with distortion, a fisheye pair (status left out within 1e-3 px of the gate: stereo_cases.near_gate), partial wavefronts / work-groups, every nklt_pyr_lvl, and the batch form."""
 import numpy as np
 import pytest
 
@@ -25,11 +25,13 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _same(got, want, what):
+def _same(got, want, what, near_gate=None):
+    """near_gate: the key points whose status is left out (stereo_cases.near_gate: the fisheye case alone); positions always count"""
     ok, right = got
     rok, rright = want
     assert ok.shape == rok.shape and right.shape == rright.shape, what
-    bad = np.nonzero((ok != rok) | (_bits(right) != _bits(rright)).any(axis=-1))[0]
+    status = (ok != rok) if near_gate is None else (ok != rok) & ~near_gate
+    bad = np.nonzero(status | (_bits(right) != _bits(rright)).any(axis=-1))[0]
     assert len(bad) == 0, "%s: %d of %d keypoints differ, first %d: ok %s / %s, right %s / %s" % (
         what, len(bad), len(ok), bad[0], ok[bad[0]], rok[bad[0]], right[bad[0]], rright[bad[0]])
 
@@ -47,7 +49,7 @@ class _Rig:
         return self._pyrs[key]
 
     def cal(self, c):
-        return ov2slam_amd.CameraCalibration(self.ctx, "pinhole", *c["K"], D=c["D"])
+        return ov2slam_amd.CameraCalibration(self.ctx, c["model"], *c["K"], D=c["D"])
 
     def run(self, fn, c, n=None, nklt_pyr_lvl=None):
         n = len(c["kps"]) if n is None else n
@@ -73,7 +75,7 @@ def test_fused_form_against_the_oracle(gpu_ctx, oracle, rig, name, win, impl):
     c = SC.case(name, win)
     with gpu_ctx.options(track_impl=TRACK_IMPL[impl]):
         got = rig.run(stereo.stereo_matching_fused, c)
-    _same(got, (c["ok"], c["right_px"]), "%s win %d %s" % (name, win, impl))
+    _same(got, (c["ok"], c["right_px"]), "%s win %d %s" % (name, win, impl), c["near_gate"])
     assert 2 * got[0].sum() >= len(got[0])
 
 
@@ -82,7 +84,7 @@ def test_call_sequence_against_the_oracle(gpu_ctx, oracle, rig, name, win, impl)
     c = SC.case(name, win)
     with gpu_ctx.options(lk_impl=LK_IMPL[impl]):
         got = rig.run(stereo.stereo_matching, c)
-    _same(got, (c["ok"], c["right_px"]), "%s win %d %s" % (name, win, impl))
+    _same(got, (c["ok"], c["right_px"]), "%s win %d %s" % (name, win, impl), c["near_gate"])
 
 
 @pytest.mark.parametrize("name,impl", [("euroc_half", "wave"), ("euroc_half", "row"), ("odd_w7", "row"), ("odd_w11_unrect", "row")])

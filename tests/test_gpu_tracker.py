@@ -7,6 +7,7 @@ import pytest
 
 import ov2slam_amd
 from ov2slam_amd import synth
+from tests import camera_cases as CC
 
 pytestmark = pytest.mark.gpu
 
@@ -45,8 +46,8 @@ def _oracle_frame(O, prev_img, cur_img, kps, pri, hp, use_clahe, w, h, use_prior
     return O.klt_tracking(O.Pyramid(prev_img, 9, 3), O.Pyramid(cur_img, 9, 3), kps, pri, hp, klt_use_prior=use_prior)
 
 
-def _points(w, h, flow, f, rng, prior_sigma, frac_prior=0.7, bad_frac=0.0, bad_sigma=12.0):
-    kps = synth.grid_keypoints(w, h, 35, rng)
+def _points(w, h, flow, f, rng, prior_sigma, frac_prior=0.7, bad_frac=0.0, bad_sigma=12.0, cell=35):
+    kps = synth.grid_keypoints(w, h, cell, rng)
     gt = flow(kps.astype(np.float64), f, f + 1)
     hp = rng.uniform(size=len(kps)) < frac_prior
     pri = np.where(hp[:, None], gt + rng.normal(0, prior_sigma, gt.shape), kps).astype(np.float32)
@@ -227,6 +228,50 @@ def test_tracker_computes_keypoints_in_the_same_enqueue(gpu_ctx, oracle, use_gra
         trk.trackFrame(views[1], np.zeros((0, 2), np.float32), np.zeros((0, 2), np.float32), None)
         with pytest.raises(ov2slam_amd.Ov2Error):
             trk.lastKeypoints(1)
+        trk.close()
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+@pytest.mark.parametrize("camera", CC.NAMES)
+def test_tracker_computes_keypoints_under_every_camera(gpu_ctx, oracle, camera, use_graph):
+    """The test above on the 376 x 240 frame under every camera of tests/camera_cases.py: ov2_tracker_set_calibration must hand the
+    model and all of k[] to the device, for one launch (capacity 512), for chunks (capacity 100, ~400 key points) and in the host's
+    re-run of the p3p rule (ov2_apply_p3p_rule).  lastKeypoints == ov2_compute_keypoints on the output positions as bits (both are
+    device code on the same input), and that call equals the oracle within the stand-alone bound of the camera.  With
+    fisheye_fold the re-run set holds failed and successful undistortions."""
+    w, h = CC.W, CC.H
+    views, flow = _sequence(w, h, 3, seed=21)
+    rng = np.random.default_rng(6)
+
+    def check(trk, cal, out):
+        unpx, bv = trk.lastKeypoints(len(out))
+        su, sb = cal.computeKeypoints(out)
+        assert np.array_equal(_bits(unpx), _bits(su)) and np.array_equal(bv.view(np.uint64), sb.view(np.uint64))
+        CC.assert_keypoints_match_oracle(oracle, camera, out, su, sb)
+        if camera == "fisheye_fold":
+            assert CC.fold_populated(out)
+
+    for cap in (512, 100):
+        trk = ov2slam_amd.VisualFrontEndTracker(gpu_ctx, w, h, use_clahe=False, nbmaxkps=cap, use_graph=use_graph)
+        cal = CC.calibration(gpu_ctx, camera)
+        trk.setCalibration(cal)
+        trk.trackFrame(views[0], np.zeros((0, 2), np.float32), np.zeros((0, 2), np.float32), None)
+        kps, pri, hp = _points(w, h, flow, 0, rng, 1.0, bad_frac=0.25, cell=15)
+        assert len(kps) > 3 * 100
+        out, st, _ = trk.trackFrame(views[1], kps, pri, hp)
+        rout = _oracle_frame(oracle, views[0], views[1], kps, pri, hp, False, w, h)[0]
+        assert np.array_equal(_bits(out), _bits(rout))
+        check(trk, cal, out)
+        # the p3p rule re-runs lost prior tracks from their keypoints on the host's second enqueue
+        kps, pri, hp = _points(w, h, flow, 1, rng, 1.0, frac_prior=0.8, bad_frac=0.95, bad_sigma=60.0, cell=15)
+        out, st, p3p = trk.trackFrame(views[2], kps, pri, hp)
+        assert p3p
+        rerun = (st & 2) > 0
+        assert rerun.sum() > 50
+        check(trk, cal, out)
+        if camera == "fisheye_fold":
+            kind = CC.fisheye_kinds(camera, out[rerun])
+            assert (kind == CC.OK).sum() >= 20 and (kind != CC.OK).sum() >= 20
         trk.close()
 
 

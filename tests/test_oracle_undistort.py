@@ -78,6 +78,36 @@ def test_fisheye_inverts_forward_model(oracle):
     assert np.allclose(c[0], [K[2], K[3]], atol=1e-4)
 
 
+def test_fisheye_failure_branch(oracle):
+    """theta (1 - 0.5 theta^2) peaks at 0.5443: beyond that theta_d the Newton loop has nothing to find.  It either runs out of its
+    10 trips or settles on a negative theta (`theta_flipped`), and undistortImagePoint returns exactly (-1e6, -1e6)
+    (cv::fisheye::undistortPoints, fisheye.cpp: `pu = Vec2d(-1000000.0, -1000000.0)`); the bearing is iK (-1e6, -1e6, 1) normalised."""
+    Kf, kf = (190.0, 190.0, 188.0, 120.0), (-0.5, 0.0, 0.0, 0.0)
+    iK = iK_of(Kf)
+    rng = np.random.default_rng(2)
+    px = np.stack([rng.uniform(0, 376, 2000), rng.uniform(0, 240, 2000)], 1).astype(np.float32)
+    unpx, bv = oracle.compute_keypoints(oracle.CAM_FISHEYE, Kf, kf, iK, px)
+    thd = np.hypot((px[:, 0].astype(np.float64) - Kf[2]) / Kf[0], (px[:, 1].astype(np.float64) - Kf[3]) / Kf[1])
+    peak = np.sqrt(2. / 3.) * (1 - 0.5 * 2. / 3.)
+    failed = (unpx == np.float32(-1e6)).all(axis=1)
+    assert np.array_equal(failed, (unpx == np.float32(-1e6)).any(axis=1))
+    margin = np.abs(thd - peak) > 1e-3                    # at the peak itself Newton's convergence is a matter of rounding
+    assert np.array_equal(failed[margin], (thd > peak)[margin])
+    assert failed.sum() > 500 and (~failed).sum() > 500
+    # the success path still inverts the forward model where the fold is not yet near (d theta_d / d theta = 1 - 1.5 theta^2 > 0.4)
+    good = ~failed & (thd < 0.45)
+    th = np.arctan(np.hypot((unpx[good, 0] - Kf[2]) / Kf[0], (unpx[good, 1] - Kf[3]) / Kf[1]))
+    assert np.abs(th * (1 + kf[0] * th ** 2) - thd[good]).max() < 1e-6
+    b = iK @ np.array([-1e6, -1e6, 1.0])
+    b /= np.linalg.norm(b)
+    assert np.allclose(bv[failed], b, rtol=0, atol=1e-15) and len(np.unique(bv[failed].view(np.uint64), axis=0)) == 1
+    # the restatement of the loop that names the reason (tests/camera_cases.py) agrees on who failed
+    from tests import camera_cases as CC
+    kind = CC.fisheye_kinds("fisheye_fold", px)
+    assert np.array_equal(kind != CC.OK, failed)
+    assert (kind == CC.NOT_CONVERGED).sum() >= 100 and (kind == CC.FLIPPED).sum() >= 30
+
+
 def test_no_distortion_returns_input(oracle):
     px = np.array([[10.5, 20.25], [300.0, 200.0]], np.float32)
     unpx, bv = oracle.compute_keypoints(oracle.CAM_PINHOLE, K, None, iK_of(K), px)

@@ -30,6 +30,12 @@ def test_case_populates_the_branches(oracle, capsys, name, win):
         assert k["retry_distinct"] >= 1                                        # a retry from the 3-D prior itself would show
     assert k["gate_rejected"] >= 10 and 2 * k["ok"] >= n                      # gate
     assert k["untracked"] >= 3                                                # no track
+    # the status of at most 2 % of the points is left out of the device comparison, and under the pinhole model of none
+    assert c["near_gate"].sum() <= (0.02 * n if c["model"] == "fisheye" else 0)
+    if name == "fisheye_unrect":
+        assert c["model"] == "fisheye" and not c["rect"] and np.array_equal(c["Frl"], SC.F_XTRANS) and c["nklt_pyr_lvl"] == 1
+        pin = oracle.compute_keypoints(oracle.CAM_PINHOLE, c["K"], c["D"], np.eye(3), c["kps"])[0]
+        assert np.abs(c["kps_unpx"] - pin).max() > 0.05                       # the fisheye undistortion, not the pinhole one
 
 
 def test_half_window_quirk(oracle):
