@@ -2297,6 +2297,89 @@ int  ov2_btracker_create_keyframe(ov2_btracker *t, int n_active, const ov2_creat
                                   const ov2_create_keyframe_input *input, ov2_create_keyframe_result *results, float *out_px_h,
                                   int *out_lmid_h, float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h);
 
+/* The current frame RESIDENT ON THE DEVICE between the lock-step steps (f21): per item of an ov2_btracker the count n and per slot
+ * px (2 float), lmid, is3d and the 3-D point wpt (3 double), mirrored on the host.  ov2_btracker_track_mono and
+ * ov2_btracker_create_keyframe take the frame from the host at every call, and the caller rebuilds it between two calls by the rule
+ * of k_mono_pack; with the calls below the tracker carries it, and the caller sends up only what the map changed.  The block is
+ * double-buffered per item: a call reads an item's frame from one buffer and writes the next frame into the other, and its _end
+ * decides which holds -- so ov2_btracker_track_frame_end on a resident step leaves the frame as it was before the step.
+ *
+ * ov2_btracker_set_frame    installs item's frame (first install, and the fallback after OV2_CKF_OVERFLOW / OV2_CKF_DUP_LMID or a
+ *                           re-initialisation): one copy up, one synchronisation.
+ * ov2_btracker_get_frame    from_device != 0: the device block copied down (one synchronisation); 0: the mirror.  Any output
+ *                           pointer may be NULL; the arrays hold cfg.n_max slots, [0, *n) are written.  wpt of a slot with
+ *                           is3d == 0 is whatever the slot last carried.
+ * ov2_btracker_update_frame[_batch]   what the map did to the frames since the last step, as a list of ops per item -- the batch
+ *                           form for items [0, n_active) (ops_h[b]: n_ops_h[b] ops; may be NULL where that is 0), the single
+ *                           form for one item:
+ *     OV2_RES_SET_POINT     triangulation, local BA or matchToMap gave or moved the 3-D point: wpt = xyz, is3d = 1
+ *     OV2_RES_UNSET_POINT   is3d = 0 (the point is kept in the slot)
+ *     OV2_RES_REMOVE        removeObsFromCurFrameById, prepareFrame's filter: the slot leaves the frame, the rest close up in slot
+ *                           order
+ *                           An lmid the frame does not hold is skipped and counted (n_missing).  One upload (the ops, packed), one
+ *                           launch (k_res_update, csrc/resident.hip: a work-group per item, the list's ids in LDS), one download (the
+ *                           records) and one synchronisation; the mirror is advanced on the host by the same rule.
+ * ov2_btracker_track_mono_resident[_begin / _end]   ov2_btracker_track_mono on the resident frame: its arguments without kps_xy_h,
+ *                           wpt_h, is3d_h and n_h; input->step.lmid_h and input->step.pose.scale_h must be NULL (every scale is 0).
+ *                           k_res_stage writes the frame where the step's kernels read it -- the per-slot ranges are not copied up
+ *                           --, the step of f19 runs untouched, and k_res_carry behind k_mono_pack writes the next frame by that
+ *                           kernel's rule: the tracked px of the slots with (status & 3) == 1 whose filter byte and pose byte are 0,
+ *                           with their lmid, is3d and wpt, in slot order; none where the pose's action is OV2_POSE_P3P_RESET or
+ *                           OV2_POSE_PNP_RESET.  _end returns what ov2_btracker_track_mono_end returns, in the slot space of the
+ *                           frame BEFORE the step, plus n_before / n_after per item (frame_results, may be NULL); the next frame
+ *                           comes down with the results into the mirror.  Where the 33 % rule fired, _end rebuilds that item's
+ *                           frame on the host from the second run's removals and copies that one item up.  The tracker's first
+ *                           frame and a step with no keypoint anywhere leave every frame as it is; so does any step for the items
+ *                           beyond n_active.  ov2_btracker_track_mono_end finishes a resident step too (without frame_results).
+ * ov2_btracker_create_keyframe with input->px_h == NULL (lmid_h, is3d_h and n_h must then be NULL too) reads the resident frame:
+ *                           k_res_ckf_in fills the call's input ranges on the device, and behind k_ckf_install k_res_adopt makes
+ *                           the frame with the new points appended (is3d = 0, wpt = 0) the resident frame of every
+ *                           OV2_CKF_CREATED item; an item that is NOT_REQUESTED, OVERFLOW or DUP_LMID keeps its frame.  Outputs and
+ *                           the installed keyframe are those of the host form.
+ * ov2_btracker_last_slot_bytes   the bytes of PER-SLOT input (any range whose size goes with n or cfg.n_max: keypoints, points,
+ *                           flags, ids, scales; not images, not per-item scalars) that the last _begin of a step or of
+ *                           create_keyframe wrote for the device: > 0 for the host forms with a non-empty frame, 0 for the
+ *                           resident forms.
+ *
+ * OV2_EINVAL, checked on the host before anything is enqueued: a NULL tracker; an item or n_active out of range; an open step or
+ * an open create_keyframe call (set_frame, get_frame and update_frame alike); cfg.n_max >
+ * OV2_FKF_MAX_POINTS.  set_frame: n outside [0, cfg.n_max]; a NULL array with n > 0; a non-finite px; a non-finite wpt on an is3d
+ * slot; a negative or repeated lmid.  update_frame: n_ops outside [0, cfg.n_max]; a NULL list with n_ops > 0; an unknown op; an
+ * lmid repeated within one item's list; a non-finite xyz on OV2_RES_SET_POINT.  track_mono_resident: everything
+ * ov2_btracker_track_mono refuses of the remaining arguments; a non-NULL lmid_h / scale_h; _end on a step that was not begun with
+ * _resident_begin. */
+#define OV2_RES_SET_POINT   0
+#define OV2_RES_UNSET_POINT 1
+#define OV2_RES_REMOVE      2
+typedef struct {
+    int lmid;                         /* the map point's id                                                                  */
+    int op;                           /* OV2_RES_*                                                                           */
+    double xyz[3];                    /* OV2_RES_SET_POINT: the point in the world frame; else unused                        */
+} ov2_resident_op;
+typedef struct {
+    int n_before, n_after;            /* the frame's size                                                                    */
+    int n_set, n_unset, n_removed;    /* ops applied, by kind                                                                */
+    int n_missing;                    /* ops whose lmid the frame does not hold                                              */
+} ov2_resident_update_result;
+typedef struct {
+    int n_before, n_after;            /* the frame's size before the step and after its removals                             */
+} ov2_resident_step_result;
+int  ov2_btracker_set_frame(ov2_btracker *t, int item, int n, const float *px, const int *lmid, const uint8_t *is3d, const double *wpt);
+int  ov2_btracker_get_frame(ov2_btracker *t, int item, int from_device, int *n, float *px, int *lmid, uint8_t *is3d, double *wpt);
+int  ov2_btracker_update_frame(ov2_btracker *t, int item, int n_ops, const ov2_resident_op *ops, ov2_resident_update_result *result);
+int  ov2_btracker_update_frame_batch(ov2_btracker *t, int n_active, const int *n_ops_h, const ov2_resident_op *const *ops_h,
+                                     ov2_resident_update_result *results);
+int  ov2_btracker_track_mono_resident_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, int klt_use_prior,
+                                            const ov2_track_mono_params *params, const ov2_track_mono_input *input);
+int  ov2_btracker_track_mono_resident_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req,
+                                          ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
+                                          ov2_track_mono_result *mono_results, ov2_resident_step_result *frame_results);
+int  ov2_btracker_track_mono_resident(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, int klt_use_prior,
+                                      const ov2_track_mono_params *params, const ov2_track_mono_input *input, float *out_xy_h,
+                                      uint8_t *status_h, int *p3p_req, ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
+                                      ov2_track_mono_result *mono_results, ov2_resident_step_result *frame_results);
+int  ov2_btracker_last_slot_bytes(const ov2_btracker *t, size_t *h2d);
+
 #ifdef __cplusplus
 }
 #endif

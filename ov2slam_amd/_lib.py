@@ -48,6 +48,7 @@ OV2_KF_RET_FEW_CELLS, OV2_KF_RET_FEW_3D, OV2_KF_RET_MANY_3D, OV2_KF_RET_TIME, OV
 OV2_KF_FIRST_FRAME, OV2_KF_NO_KEYFRAME = 512, 1024      # ov2_btracker_track_mono
 OV2_CKF_DET_SINGLESCALE, OV2_CKF_DET_GRID_FAST, OV2_CKF_DET_GFTT = 0, 1, 2             # ov2_btracker_create_keyframe
 OV2_CKF_NOT_REQUESTED, OV2_CKF_CREATED, OV2_CKF_OVERFLOW, OV2_CKF_DUP_LMID = 0, 1, 2, 3
+OV2_RES_SET_POINT, OV2_RES_UNSET_POINT, OV2_RES_REMOVE = 0, 1, 2                        # ov2_btracker_update_frame
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -479,6 +480,22 @@ class CreateKeyframeResult(C.Structure):
                 ("n_kf", C.c_int), ("nb3dkps", C.c_int), ("pad", C.c_int)]
 
 
+class ResidentOp(C.Structure):
+    """ov2_resident_op"""
+    _fields_ = [("lmid", C.c_int), ("op", C.c_int), ("xyz", C.c_double * 3)]
+
+
+class ResidentUpdateResult(C.Structure):
+    """ov2_resident_update_result"""
+    _fields_ = [("n_before", C.c_int), ("n_after", C.c_int), ("n_set", C.c_int), ("n_unset", C.c_int), ("n_removed", C.c_int),
+                ("n_missing", C.c_int)]
+
+
+class ResidentStepResult(C.Structure):
+    """ov2_resident_step_result"""
+    _fields_ = [("n_before", C.c_int), ("n_after", C.c_int)]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -699,6 +716,17 @@ SIGNATURES = {
     "ov2_btracker_create_keyframe_end": (_i, [_vp, C.POINTER(CreateKeyframeResult), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ov2_btracker_create_keyframe": (_i, [_vp, _i, C.POINTER(CreateKeyframeParams), C.POINTER(CreateKeyframeInput),
                                           C.POINTER(CreateKeyframeResult), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ov2_btracker_set_frame": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "ov2_btracker_get_frame": (_i, [_vp, _i, _i, C.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "ov2_btracker_update_frame": (_i, [_vp, _i, _i, C.POINTER(ResidentOp), C.POINTER(ResidentUpdateResult)]),
+    "ov2_btracker_update_frame_batch": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(C.POINTER(ResidentOp)), C.POINTER(ResidentUpdateResult)]),
+    "ov2_btracker_track_mono_resident_begin": (_i, [_vp, _i, _vp, _i, _i, C.POINTER(TrackMonoParams), C.POINTER(TrackMonoInput)]),
+    "ov2_btracker_track_mono_resident_end": (_i, [_vp, _vp, _vp, _vp, C.POINTER(EpifilterResult), C.POINTER(PoseResult),
+                                                  C.POINTER(TrackMonoResult), C.POINTER(ResidentStepResult)]),
+    "ov2_btracker_track_mono_resident": (_i, [_vp, _i, _vp, _i, _i, C.POINTER(TrackMonoParams), C.POINTER(TrackMonoInput), _vp, _vp, _vp,
+                                              C.POINTER(EpifilterResult), C.POINTER(PoseResult), C.POINTER(TrackMonoResult),
+                                              C.POINTER(ResidentStepResult)]),
+    "ov2_btracker_last_slot_bytes": (_i, [_vp, C.POINTER(C.c_size_t)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

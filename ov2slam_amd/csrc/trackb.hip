@@ -31,6 +31,12 @@
 // k_ckf_prepare in front, k_ckf_append behind the detector's launches, k_ckf_install behind computeKeypoint and BRIEF): the new frame
 // becomes the item's resident keyframe without leaving the device; byte-equal to the separate describe / detect / computeKeypoints
 // calls, a host sort and ov2_btracker_set_keyframe + ov2_btracker_set_keyframe_info per item (tests/test_gpu_createkf.py).
+// The resident frame (ov2_btracker_set_frame / _get_frame / _update_frame, ov2_btracker_track_mono_resident, create_keyframe with
+// px_h == NULL; resident.hip): the current frame of every item -- px, lmid, is3d, wpt per slot -- stays on the device between those
+// calls, in a block of two buffers per item with a pinned mirror of the same layout.  k_res_stage writes it where the step's kernels
+// read their per-slot inputs (which are then not copied up), k_res_carry writes the frame the step leaves by k_mono_pack's rule,
+// k_res_update applies what the map did, k_res_ckf_in / k_res_adopt put create_keyframe on it; byte-equal to the same cycle on frames
+// kept on the host (tests/test_gpu_resident.py; tests/resident_ref.py is that cycle).
 #include "common.hpp"
 #include "keypoint_dev.hpp"
 #include "pose_dev.hpp"
@@ -38,8 +44,10 @@
 #include "mono_dev.hpp"
 #include "detect_dev.hpp"
 #include "createkf_dev.hpp"
+#include "resident_dev.hpp"
 #include "fkf_dev.hpp"
 #include "trackb_layout.hpp"
+#include <algorithm>
 #include <cmath>
 #include <deque>
 #include <new>
@@ -55,6 +63,7 @@ static_assert(sizeof(FeKfHdr) == BT_KF_HDR_BYTES, "trackb_layout.hpp: the index 
 static_assert(sizeof(ov2_motion_state) == BT_MOTION_STATE_BYTES, "trackb_layout.hpp: the mono blocks' state");
 static_assert(sizeof(FkfItemD) == BT_FKF_ITEM_BYTES && 4 * FKF_OUT_INTS == BT_KF_DEC_BYTES, "trackb_layout.hpp: the mono blocks' records");
 static_assert(sizeof(ov2_create_keyframe_result) == BT_CKF_REC_BYTES && sizeof(SelectOut) == BT_CKF_SO_BYTES, "trackb_layout.hpp: the createKeyframe block's records");
+static_assert(sizeof(ov2_resident_op) == BT_RES_OP_BYTES && sizeof(ov2_resident_update_result) == BT_RES_REC_BYTES, "trackb_layout.hpp: the resident frame's records");
 
 // A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
 // (zero copy), or mirrored on the device with a copy up before the kernels and a copy down behind them.
@@ -89,7 +98,12 @@ struct IoBlock {
         h = d = k = nullptr; bytes = 0;
     }
     // [0, n) up, [from, to) down: nothing to do when the kernels work on the pinned block itself
-    int upload(hipStream_t s, size_t n) const { if (d) OV2_HIP_CHECK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)); return OV2_OK; }
+    int upload(hipStream_t s, size_t n) const { return upload(s, 0, n); }
+    int upload(hipStream_t s, size_t from, size_t to) const
+    {
+        if (d && to > from) OV2_HIP_CHECK(hipMemcpyAsync(d + from, h + from, to - from, hipMemcpyHostToDevice, s));
+        return OV2_OK;
+    }
     int download(hipStream_t s, size_t from, size_t to) const
     {
         if (d) OV2_HIP_CHECK(hipMemcpyAsync(h + from, d + from, to - from, hipMemcpyDeviceToHost, s));
@@ -113,6 +127,7 @@ struct StepArgs {
     const ov2_frame_pose_params *pp = nullptr; const ov2_frame_pose_input *pin = nullptr;                  // pose (epi: the pose halves of epp / ein)
     const ov2_frame_epi_pose_params *epp = nullptr; const ov2_frame_epi_pose_input *ein = nullptr;         // epi
     const ov2_track_mono_params *mp = nullptr; const ov2_track_mono_input *min = nullptr;                  // mono (epp / ein: their step halves)
+    bool resident = false;            // mono on the resident frame: n_h holds the mirror's counts, the point arrays are NULL
 };
 
 // ov2_btracker_last_pose_inputs / ov2_btracker_last_epi_inputs: what the last finished step of the kind fed its chain.  Per item the
@@ -210,7 +225,8 @@ struct ov2_btracker {
                      ov2_epifilter_params ep; EpifLayout eL;
                      // mono: the step runs between the motion model and the decision; ran: not the tracker's first frame
                      bool mono = false, mono_ran = false; ov2_fkf_params fkf; std::vector<double> time;
-                     std::vector<int> frame_id, localba; } pend;
+                     std::vector<int> frame_id, localba;
+                     bool resident = false; } pend;       // the frame is the resident one; k_res_carry wrote the next one
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
     // ov2_btracker_create_keyframe, allocated by its first call: the I/O block (pinned, and its device mirror at the same offsets:
@@ -221,7 +237,14 @@ struct ov2_btracker {
     size_t ckw_bytes = 0;
     struct CkfPending { bool on = false, det = false; int n_active = 0, mode = 0, ncells = 0; ov2_create_keyframe_params p;
                         double *quality = nullptr; int *fast_th = nullptr; std::vector<uint8_t> flag; std::vector<int> nkfid;
-                        std::vector<double> time; } cpend;
+                        std::vector<double> time; bool resident = false; } cpend;
+    // the resident frame (f21), allocated by its first use: the frame block (two buffers of `batch` items: BtResLayout) with its
+    // pinned host mirror of the same layout, the control block of a call (pinned, and its device mirror), and per item the buffer
+    // that holds the current frame
+    BtResLayout rl;
+    uint8_t *dfr = nullptr, *hfr = nullptr, *drc = nullptr, *hrc = nullptr;
+    std::vector<uint8_t> res_sel;
+    size_t slot_bytes = 0;            // ov2_btracker_last_slot_bytes
 };
 
 static void btracker_free(ov2_btracker *t)
@@ -256,6 +279,10 @@ static void btracker_free(ov2_btracker *t)
     if (t->hckf) (void)hipHostFree(t->hckf);
     if (t->dckf) (void)hipFree(t->dckf);
     if (t->dckw) (void)hipFree(t->dckw);
+    if (t->dfr) (void)hipFree(t->dfr);
+    if (t->hfr) (void)hipHostFree(t->hfr);
+    if (t->drc) (void)hipFree(t->drc);
+    if (t->hrc) (void)hipHostFree(t->hrc);
     delete t;
 }
 
@@ -289,6 +316,8 @@ static int enqueue_preprocess(ov2_btracker *t, ov2_ctx *on, ov2_pyr *dst, int wh
 
 static MonoArgs mono_args(ov2_btracker *t, const ov2_btracker::Pending &P, bool chain);           // (below, with the mono side's staging)
 static int enqueue_mono_tail(ov2_btracker *t, const ov2_btracker::Pending &P, bool chain);
+static int enqueue_res_stage(ov2_btracker *t, int n_active);                                      // (below: the resident frame)
+static int enqueue_res_carry(ov2_btracker *t, const ov2_btracker::Pending &P);
 
 // kltTracking of items [0, P.n_active) for the step P describes: keypoint block in, the fused LK launch, computeKeypoint, result block out
 // map form: k_prior_frame fills the prior and flag slots from the map side first
@@ -303,15 +332,18 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
     const BtMapLayout &ml = t->ml;
     uint8_t *k = t->pt.k;
     const uint8_t *m = t->map.k;
-    int rc = t->pt.upload(s, pl.in_bytes);  if (rc) return rc;
+    // a resident step sends the blocks' per-item headers only: k_res_stage fills the per-slot ranges behind these uploads
+    const bool res = P.resident;
+    int rc = res ? t->pt.upload(s, 0, pl.o_kps) : t->pt.upload(s, pl.in_bytes);  if (rc) return rc;
     if (P.form >= STEP_MAP) {
-        rc = t->map.upload(s, ml.map_bytes);  if (rc) return rc;
+        rc = res ? t->map.upload(s, 0, ml.m_w) : t->map.upload(s, ml.map_bytes);  if (rc) return rc;
         if (P.mono) {
             // the motion model, behind the uploads of the two blocks it writes into (a mirrored block's upload would overwrite it)
             // and ahead of k_prior_frame; the filter's inputs travel here when the inner step does not take them (lmid is needed)
-            rc = t->pose.upload(s, t->ql.q_in);  if (rc) return rc;
+            rc = res ? t->pose.upload(s, 0, t->ql.q_sc) : t->pose.upload(s, t->ql.q_in);  if (rc) return rc;
             rc = t->mono.upload(s, t->nl.n_in);  if (rc) return rc;
-            if (P.form != STEP_EPI) { rc = t->epi.upload(s, t->el.e_in);  if (rc) return rc; }
+            if (P.form != STEP_EPI) { rc = res ? t->epi.upload(s, t->el.e_nk, t->el.e_in) : t->epi.upload(s, t->el.e_in);  if (rc) return rc; }
+            if (res) { rc = enqueue_res_stage(t, n);  if (rc != OV2_OK) return rc; }
             rc = ov2_launch_mono_apply(s, mono_args(t, P, true), n);
             if (rc != OV2_OK) return rc;
         }
@@ -338,7 +370,7 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
         ov2_fp_hook hook = nullptr;
         if (P.form == STEP_EPI) {                                       // the filter between the select and the pack (frameepi.hip)
             const BtEpiLayout &el = t->el;
-            rc = t->epi.upload(s, el.e_in);  if (rc) return rc;
+            rc = res ? t->epi.upload(s, el.e_nk, el.e_in) : t->epi.upload(s, el.e_in);  if (rc) return rc;
             uint8_t *e = t->epi.k, *d = t->depi;
             const EpifLayout &EL = P.eL;
             FeStep &fe = t->fe;
@@ -370,6 +402,7 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
         rc = t->pose.download(s, ql.q_out, ql.pose_bytes);
         if (rc == OV2_OK && P.form == STEP_EPI) rc = t->epi.download(s, t->el.e_out, t->el.epi_bytes);
         if (rc == OV2_OK && P.mono) rc = enqueue_mono_tail(t, P, true);
+        if (rc == OV2_OK && res) rc = enqueue_res_carry(t, P);
         if (rc != OV2_OK) return rc;
     }
     rc = t->pt.download(s, pl.o_out, pl.blk_bytes);
@@ -434,9 +467,10 @@ static int stage_map(ov2_btracker *t, int n_active, const double *wpt, const uin
     if (Tcw) memcpy(hmap + ml.m_T, Tcw, 56 * (size_t)n_active);      // (mono: k_mono_apply writes the inverse of the predicted pose)
     for (int b = 0; b < n_active; b++) {
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
-        if (!n) continue;
+        if (!n || !wpt) continue;                                        // (a resident step: k_res_stage writes both)
         memcpy(hmap + ml.m_w + 24 * o, wpt + 3 * o, 24 * n);
         memcpy(hmap + ml.m_3d + o, is3d + o, n);
+        t->slot_bytes += 25 * n;
     }
     return OV2_OK;
 }
@@ -473,7 +507,7 @@ static int check_pose(const ov2_btracker *t, const StepArgs &A, const ov2_frame_
 // the pose inputs of a step into hpose (the pose buffers are allocated here by the first pose step, and grown when a step asks for
 // more sample rows than any before it)
 static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params *pp, const ov2_frame_pose_input *in, const int *n_h,
-                      const PoseLayout &L)
+                      const PoseLayout &L, bool resident = false)
 {
     const size_t nm = (size_t)t->cfg.n_max;
     if (!t->pose.h) { const int rc = t->pose.alloc(t->ql.pose_bytes, t->zero_copy, false, "ov2_btracker_track_frame_pose");  if (rc) return rc; }
@@ -495,17 +529,20 @@ static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params
         const int req = in->p3p_req_h[b] != 0;
         fl[b] = (uint8_t)(req | ((req || pp->dop3p) ? 2 : 0));
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
+        if (resident) continue;                                          // (k_res_stage writes the scales: all 0)
         int *sc = (int *)(hpose + ql.q_sc) + o;
         if (in->scale_h) memcpy(sc, in->scale_h + o, 4 * n); else memset(sc, 0, 4 * n);
+        t->slot_bytes += 4 * n;
     }
     return OV2_OK;
 }
 
 // what an epipolar + pose step refuses beyond the pose step's checks; *L: the filter's layout at capacity
-static int check_epi(const ov2_btracker *t, const ov2_frame_epi_pose_params *pp, const ov2_frame_epi_pose_input *in, EpifLayout *L)
+static int check_epi(const ov2_btracker *t, const ov2_frame_epi_pose_params *pp, const ov2_frame_epi_pose_input *in, EpifLayout *L,
+                     bool resident = false)
 {
     OV2_REQUIRE(pp && in, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL params / input");
-    OV2_REQUIRE(in->lmid_h && in->nbkfs_h && in->epi_seed_h, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL lmid_h / nbkfs_h / epi_seed_h");
+    OV2_REQUIRE((resident || in->lmid_h) && in->nbkfs_h && in->epi_seed_h, OV2_EINVAL, "ov2_btracker_track_frame_epi_pose: NULL lmid_h / nbkfs_h / epi_seed_h");
     const int rc = epif_check_params(&pp->epi);  if (rc) return rc;
     OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
     return epif_layout_capacity(t->batch, t->cfg.n_max, pp->epi.n_rows, L);
@@ -561,7 +598,10 @@ static void stage_epi(ov2_btracker *t, int n_active, const ov2_frame_epi_pose_in
 {
     const size_t nm = (size_t)t->cfg.n_max;
     for (int b = 0; b < n_active; b++)
-        if (n_h[b] > 0) memcpy(t->epi.h + t->el.e_lm + 4 * nm * (size_t)b, in->lmid_h + nm * (size_t)b, 4 * (size_t)n_h[b]);
+        if (n_h[b] > 0 && in->lmid_h) {                                   // (NULL: a resident step, k_res_stage writes the ids)
+            memcpy(t->epi.h + t->el.e_lm + 4 * nm * (size_t)b, in->lmid_h + nm * (size_t)b, 4 * (size_t)n_h[b]);
+            t->slot_bytes += 4 * (size_t)n_h[b];
+        }
     if (in->nbkfs_h) memcpy(t->epi.h + t->el.e_nk, in->nbkfs_h, 4 * (size_t)n_active);         // (NULL: mono without the filter)
     if (in->epi_seed_h) memcpy(t->epi.h + t->el.e_sd, in->epi_seed_h, 8 * (size_t)n_active);
 }
@@ -682,14 +722,176 @@ static void stage_points(ov2_btracker *t, int n_active, const float *kps, const 
     for (int b = 0; b < t->batch; b++) nd[b] = b < n_active ? n_h[b] : 0;
     for (int b = 0; b < n_active; b++) {
         const size_t n = (size_t)n_h[b], o = (size_t)b * nm;
-        if (!n) continue;
+        if (!n || !kps) continue;                                        // (NULL: a resident step, k_res_stage writes the keypoints)
         memcpy(hblk + pl.o_kps + 8 * o, kps + 2 * o, 8 * n);
+        t->slot_bytes += 8 * n;
         if (!pri) continue;                                              // the map form: k_prior_frame writes both
         memcpy(hblk + pl.o_pri + 8 * o, pri + 2 * o, 8 * n);
         uint8_t *f = hblk + pl.o_flg + o;
         if (use_prior && has_prior) for (size_t i = 0; i < n; i++) f[i] = has_prior[o + i] ? 1 : 0;
         else memset(f, 0, n);
+        t->slot_bytes += 9 * n;
     }
+}
+
+// ---- the resident frame (f21) ------------------------------------------------------------------------------------------------------
+// item b of the host mirror: its current frame (other == 0) or the buffer its next frame is written into (other == 1)
+struct ResHost { int *n; float *px; int *lmid; uint8_t *is3d; double *wpt; };
+static ResHost res_host(const ov2_btracker *t, int b, int other)
+{
+    const BtResLayout &L = t->rl;
+    uint8_t *p = t->hfr + (size_t)(t->res_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.f_item;
+    return ResHost{(int *)p, (float *)(p + L.f_px), (int *)(p + L.f_lm), p + L.f_3d, (double *)(p + L.f_w)};
+}
+
+static ResFrames res_frames(const ov2_btracker *t)
+{
+    const BtResLayout &L = t->rl;
+    return ResFrames{t->dfr, L.buf_bytes, L.f_item, L.f_px, L.f_lm, L.f_3d, L.f_w, t->drc + L.u_sel, t->cfg.n_max};
+}
+
+// the frame block, its mirror and the control block, allocated by the first use: every frame empty
+static int ensure_res(ov2_btracker *t)
+{
+    if (t->dfr) return OV2_OK;
+    const char *who = "ov2_btracker_set_frame";
+    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const BtResLayout &L = t->rl;
+    uint8_t *df = nullptr, *hf = nullptr, *dc = nullptr, *hc = nullptr;
+    hipError_t e = hipMalloc((void **)&df, L.frame_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&hf, L.frame_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&dc, L.ctl_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&hc, L.ctl_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemsetAsync(df, 0, L.frame_bytes, t->ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dc, 0, L.ctl_bytes, t->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+    if (e != hipSuccess) {
+        if (df) (void)hipFree(df);
+        if (hf) (void)hipHostFree(hf);
+        if (dc) (void)hipFree(dc);
+        if (hc) (void)hipHostFree(hc);
+        (void)hipGetLastError();
+        ov2_set_error("%s: %s", who, hipGetErrorString(e));
+        return OV2_ENOMEM;
+    }
+    memset(hf, 0, L.frame_bytes);
+    memset(hc, 0, L.ctl_bytes);
+    t->dfr = df; t->hfr = hf; t->drc = dc; t->hrc = hc;
+    t->res_sel.assign((size_t)t->batch, 0);
+    return OV2_OK;
+}
+
+// which buffer holds each item's current frame, to the device (one byte per item)
+static int res_push_sel(ov2_btracker *t, hipStream_t s)
+{
+    memcpy(t->hrc + t->rl.u_sel, t->res_sel.data(), (size_t)t->batch);
+    OV2_HIP_CHECK(hipMemcpyAsync(t->drc + t->rl.u_sel, t->hrc + t->rl.u_sel, (size_t)t->batch, hipMemcpyHostToDevice, s));
+    return OV2_OK;
+}
+
+// item b's frame in the mirror (its current one, or with other == 1 the next one) to the same place on the device
+static int res_push_item(ov2_btracker *t, int b, int other, hipStream_t s)
+{
+    const BtResLayout &L = t->rl;
+    const size_t o = (size_t)(t->res_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.f_item;
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dfr + o, t->hfr + o, L.f_item, hipMemcpyHostToDevice, s));
+    return OV2_OK;
+}
+
+// A resident step on mirrored blocks: what _end reads on the host again (the rule's keypoints, the re-run's points, ids and
+// scales) from the mirror into the host halves of the blocks.  Nothing of it is copied up: k_res_stage writes the device halves.
+// (With zero copy the kernel's writes land in these very ranges.)
+static void res_fill_host(ov2_btracker *t, int n_active)
+{
+    const size_t nm = (size_t)t->cfg.n_max;
+    for (int b = 0; b < n_active; b++) {
+        const ResHost f = res_host(t, b, 0);
+        const size_t n = (size_t)*f.n, o = (size_t)b * nm;
+        if (!n) continue;
+        memcpy(t->pt.h + t->pl.o_kps + 8 * o, f.px, 8 * n);
+        memcpy(t->map.h + t->ml.m_w + 24 * o, f.wpt, 24 * n);
+        memcpy(t->map.h + t->ml.m_3d + o, f.is3d, n);
+        memcpy(t->epi.h + t->el.e_lm + 4 * o, f.lmid, 4 * n);
+        memset(t->pose.h + t->ql.q_sc + 4 * o, 0, 4 * n);
+    }
+}
+
+// in front of a resident step's kernels: which buffers are current, then the frames into the step's blocks
+static int enqueue_res_stage(ov2_btracker *t, int n_active)
+{
+    const hipStream_t s = t->ctx->stream;
+    const int rc = res_push_sel(t, s);
+    if (rc != OV2_OK) return rc;
+    ResStageArgs a;
+    a.f = res_frames(t);
+    a.kps = (float2 *)(t->pt.k + t->pl.o_kps); a.wpt = (double *)(t->map.k + t->ml.m_w); a.is3d = t->map.k + t->ml.m_3d;
+    a.lmid = (int *)(t->epi.k + t->el.e_lm); a.scale = (int *)(t->pose.k + t->ql.q_sc);
+    return ov2_launch_res_stage(s, a, n_active);
+}
+
+// behind k_mono_pack: the frame the step leaves into each item's other buffer, and those buffers down into the mirror (one copy
+// per buffer that takes part: the items' frames are contiguous)
+static int enqueue_res_carry(ov2_btracker *t, const ov2_btracker::Pending &P)
+{
+    const hipStream_t s = t->ctx->stream;
+    const MonoArgs m = mono_args(t, P, true);
+    ResCarryArgs a;
+    a.f = res_frames(t);
+    a.n_dev = m.n_dev; a.status = m.status; a.epi_removed = m.epi_removed; a.pose_removed = m.pose_removed; a.pose_out = m.pose_out;
+    a.out_xy = m.out_xy; a.lmid = m.lmid; a.is3d = m.is3d; a.wpt = (const double *)(t->map.k + t->ml.m_w);
+    const int rc = ov2_launch_res_carry(s, a, P.n_active);
+    if (rc != OV2_OK) return rc;
+    const BtResLayout &L = t->rl;
+    for (int buf = 0; buf < 2; buf++) {
+        int lo = -1, hi = -1;
+        for (int b = 0; b < P.n_active; b++)
+            if ((t->res_sel[(size_t)b] ^ 1) == buf) { if (lo < 0) lo = b; hi = b; }
+        if (lo < 0) continue;
+        // (an item in [lo, hi] whose CURRENT frame lies in this buffer is copied too: the mirror holds the same bytes)
+        const size_t o = (size_t)buf * L.buf_bytes + (size_t)lo * L.f_item;
+        OV2_HIP_CHECK(hipMemcpyAsync(t->hfr + o, t->dfr + o, (size_t)(hi - lo + 1) * L.f_item, hipMemcpyDeviceToHost, s));
+    }
+    return OV2_OK;
+}
+
+// The resident half of _end, behind mono_finish (mres != NULL: a dropped step leaves every frame as it was).  The next frames came
+// down with the results; for the items the rule re-ran (redo) the frame is rebuilt here from the second run's removals, by
+// k_mono_pack's rule as mono_finish applies it, and copied up.  Then each item's other buffer becomes its current one.
+static int res_finish(ov2_btracker *t, const float *out_xy_h, const uint8_t *status_h, const ov2_pose_result *results,
+                      const std::vector<int> &redo, const std::vector<uint8_t> &excl, ov2_resident_step_result *fres)
+{
+    const ov2_btracker::Pending &P = t->pend;
+    const size_t nm = (size_t)t->cfg.n_max;
+    if (!P.tracked) {                                                    // the first frame, or no keypoint anywhere: nothing ran
+        for (int b = 0; b < P.n_active && fres; b++) fres[b].n_before = fres[b].n_after = P.n[(size_t)b];
+        return OV2_OK;
+    }
+    for (size_t k = 0; k < redo.size(); k++) {
+        const int b = redo[k];
+        const size_t o = (size_t)b * nm;
+        const ov2_pose_result &pr = results[b];
+        const bool reset = pr.action == OV2_POSE_P3P_RESET || pr.action == OV2_POSE_PNP_RESET;              // resetFrame()
+        const int n = reset ? 0 : P.n[(size_t)b];
+        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
+        int r = 0;
+        for (int i = 0; i < n; i++)
+            if ((status_h[o + i] & 3) == 1 && !(!excl.empty() && excl[o + i]) && !pr.removed[i]) {
+                dst.px[2 * r] = out_xy_h[2 * (o + i)]; dst.px[2 * r + 1] = out_xy_h[2 * (o + i) + 1];
+                dst.lmid[r] = src.lmid[i]; dst.is3d[r] = src.is3d[i] ? 1 : 0;
+                for (int c = 0; c < 3; c++) dst.wpt[3 * r + c] = src.wpt[3 * i + c];
+                r++;
+            }
+        *dst.n = r;
+        const int rc = res_push_item(t, b, 1, t->ctx->stream);
+        if (rc != OV2_OK) return rc;
+    }
+    if (!redo.empty()) OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    for (int b = 0; b < P.n_active; b++) {
+        t->res_sel[(size_t)b] ^= 1;
+        if (fres) { fres[b].n_before = P.n[(size_t)b]; fres[b].n_after = *res_host(t, b, 0).n; }
+    }
+    return OV2_OK;
 }
 
 // mode 0: detectGridFAST, 1: detectSingleScale, 2: detectGFTT (roi_h / roi_stride / gp / nbmax_h; cell unused)
@@ -773,7 +975,7 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     t->img_bytes = bt_img_bytes(cfg->w, cfg->h);
     t->pl = bt_point_layout(batch, cfg->n_max); t->ml = bt_map_layout(batch, cfg->n_max);
     t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max); t->nl = bt_mono_layout(batch, cfg->n_max);
-    t->cl = bt_ckf_layout(batch, cfg->n_max);
+    t->cl = bt_ckf_layout(batch, cfg->n_max); t->rl = bt_res_layout(batch, cfg->n_max);
     t->det_in_bytes = bt_det_in_bytes(batch, cfg->n_max);
     hipError_t e = hipSuccess;
     for (int i = 0; i < BT_IMG_SETS && e == hipSuccess; i++) {
@@ -916,7 +1118,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
         n_total += n;
     }
-    if (map) OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.wpt_h && A.is3d_h && (mono || A.Tcw_h) && n_h), OV2_EINVAL, "NULL point buffer");
+    if (map) OV2_REQUIRE(n_total == 0 || A.resident || (A.kps_xy_h && A.wpt_h && A.is3d_h && (mono || A.Tcw_h) && n_h), OV2_EINVAL, "NULL point buffer");
     else OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
     const ov2_frame_pose_params *pp = A.pp;
     const ov2_frame_pose_input *pin = A.pin;
@@ -927,12 +1129,12 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
         pp = &epp->pose; pin = &ein->pose;
     }
     if (pose) { const int rcp = check_pose(t, A, pp, pin, &poseL, mono);  if (rcp != OV2_OK) return rcp; }
-    if (epi) { const int rce = check_epi(t, epp, ein, &epiL);  if (rce != OV2_OK) return rce; }
+    if (epi) { const int rce = check_epi(t, epp, ein, &epiL, A.resident);  if (rce != OV2_OK) return rce; }
     if (mono) {
         // what the mono step refuses of its own.  The predicted pose cannot be checked on the host: the resident pose and state are
         // finite (the setters refuse anything else, the kernels' results derive from finite ones) and dt > 0, so log and exp are finite
         OV2_REQUIRE(A.mp->doepipolar == 0 || A.mp->doepipolar == 1, OV2_EINVAL, "doepipolar is not 0 or 1");
-        OV2_REQUIRE(ein->lmid_h, OV2_EINVAL, "ov2_btracker_track_mono: NULL lmid_h");
+        OV2_REQUIRE(A.resident || ein->lmid_h, OV2_EINVAL, "ov2_btracker_track_mono: NULL lmid_h");
         OV2_REQUIRE(A.min->time_h && A.min->frame_id_h, OV2_EINVAL, "ov2_btracker_track_mono: NULL time_h / frame_id_h");
         OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
         const int rcd = fkf_check_decide(&epp->epi.fkf);  if (rcd != OV2_OK) return rcd;
@@ -943,6 +1145,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
         }
     }
     for (int b = 0; b < t->batch; b++) t->last_n[(size_t)b] = t->last_pn[(size_t)b] = 0;
+    t->slot_bytes = 0;
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     if (mono) { const int rcm = ensure_mono(t);  if (rcm != OV2_OK) return rcm; }
@@ -976,6 +1179,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     }
     if (epi) { P.ep = epp->epi; P.eL = epiL; }
     P.mono = mono; P.mono_ran = mono && t->frames > 0;
+    P.resident = A.resident;
     if (mono) {
         P.fkf = epp->epi.fkf;
         P.time.assign(A.min->time_h, A.min->time_h + n_active);
@@ -990,13 +1194,18 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
             r = stage_map(t, n_active, A.wpt_h, A.is3d_h, A.Tcw_h, n_h);  if (r) return r;
             P.has_prior = t->pt.h + t->pl.o_flg;                         // the flags the device sets: same slots as the caller's array
         }
-        if (pose) { r = stage_pose(t, n_active, pp, pin, n_h, poseL);  if (r) return r; }
+        if (pose) { r = stage_pose(t, n_active, pp, pin, n_h, poseL, A.resident);  if (r) return r; }
         if (epi || mono) {
             r = ensure_epi(t, epi ? &epiL : nullptr);  if (r) return r;
             stage_epi(t, n_active, ein, n_h);
         }
         if (mono) { r = ensure_mono(t);  if (r) return r;  stage_mono(t, P); }
         stage_points(t, n_active, A.kps_xy_h, map ? nullptr : A.prior_xy_h, A.has_prior_h, n_h, A.klt_use_prior);
+        if (A.resident) {
+            // the frame before the step, as _end reads it on the host: where k_res_stage puts it (zero copy), or from the mirror
+            P.kps = (const float *)(t->pt.h + t->pl.o_kps);
+            if (t->pt.d) res_fill_host(t, n_active);
+        }
         r = preprocess();
         return r ? r : enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], P);
     };
@@ -1456,13 +1665,15 @@ static int mono_finish(ov2_btracker *t, const float *out_xy_h, const uint8_t *st
 }
 
 static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req, ov2_pose_result *results,
-                           ov2_epifilter_result *eres, ov2_track_mono_result *mres = nullptr)
+                           ov2_epifilter_result *eres, ov2_track_mono_result *mres = nullptr, ov2_resident_step_result *fres = nullptr)
 {
     std::vector<int> redo;
     std::vector<uint8_t> excl;
-    const int rc = track_frame_end_step(t, out_xy_h, status_h, p3p_req, results, eres, mres, redo, excl);
+    int rc = track_frame_end_step(t, out_xy_h, status_h, p3p_req, results, eres, mres, redo, excl);
     if (rc != OV2_OK || !t->pend.mono || t->pend.on) return rc;
-    return mono_finish(t, out_xy_h, status_h, results, mres, redo, excl);
+    rc = mono_finish(t, out_xy_h, status_h, results, mres, redo, excl);
+    if (rc != OV2_OK || !t->pend.resident || !mres) return rc;
+    return res_finish(t, out_xy_h, status_h, results, redo, excl, fres);
 }
 
 extern "C" {
@@ -1679,6 +1890,213 @@ int ov2_btracker_track_mono(ov2_btracker *t, int n_active, const uint8_t *const 
     return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results);
 }
 
+// ---- the resident frame (f21): the setters, the getter, the map's ops, and the step on it ----
+// what the calls around the resident frame share: the item, no open step, the buffers
+static int res_entry(ov2_btracker *t, int item0, int n_items, const char *open_msg)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(n_items >= 1 && item0 >= 0 && item0 <= t->batch - n_items, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(!t->pend.on && !t->cpend.on, OV2_EINVAL, open_msg);
+    return ensure_res(t);
+}
+
+int ov2_btracker_set_frame(ov2_btracker *t, int item, int n, const float *px, const int *lmid, const uint8_t *is3d, const double *wpt)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(n >= 0 && n <= t->cfg.n_max, OV2_EINVAL, "ov2_btracker_set_frame: n outside [0, cfg.n_max]");
+    OV2_REQUIRE(n == 0 || (px && lmid && is3d && wpt), OV2_EINVAL, "ov2_btracker_set_frame: NULL array");
+    std::vector<int> ids(lmid, lmid + n);
+    std::sort(ids.begin(), ids.end());
+    for (int i = 0; i < n; i++) {
+        OV2_REQUIRE(std::isfinite(px[2 * i]) && std::isfinite(px[2 * i + 1]), OV2_EINVAL, "ov2_btracker_set_frame: px not finite");
+        OV2_REQUIRE(!is3d[i] || (std::isfinite(wpt[3 * i]) && std::isfinite(wpt[3 * i + 1]) && std::isfinite(wpt[3 * i + 2])), OV2_EINVAL,
+                    "ov2_btracker_set_frame: wpt not finite on a 3-D slot");
+        OV2_REQUIRE(ids[(size_t)i] >= 0 && (i == 0 || ids[(size_t)i - 1] != ids[(size_t)i]), OV2_EINVAL, "ov2_btracker_set_frame: a negative or repeated lmid");
+    }
+    int rc = res_entry(t, item, 1, "ov2_btracker_set_frame between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    const ResHost f = res_host(t, item, 0);
+    *f.n = n;
+    if (n) { memcpy(f.px, px, 8 * (size_t)n); memcpy(f.lmid, lmid, 4 * (size_t)n); memcpy(f.wpt, wpt, 24 * (size_t)n); }
+    for (int i = 0; i < n; i++) f.is3d[i] = is3d[i] ? 1 : 0;
+    rc = res_push_item(t, item, 0, t->ctx->stream);
+    if (rc != OV2_OK) return rc;
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    return OV2_OK;
+}
+
+int ov2_btracker_get_frame(ov2_btracker *t, int item, int from_device, int *n, float *px, int *lmid, uint8_t *is3d, double *wpt)
+{
+    int rc = res_entry(t, item, 1, "ov2_btracker_get_frame between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    const BtResLayout &L = t->rl;
+    const uint8_t *p = (const uint8_t *)res_host(t, item, 0).n;
+    std::vector<uint8_t> dev;
+    if (from_device) {
+        dev.resize(L.f_item);
+        OV2_HIP_CHECK(hipMemcpyAsync(dev.data(), t->dfr + (p - t->hfr), L.f_item, hipMemcpyDeviceToHost, t->ctx->stream));
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+        p = dev.data();
+    }
+    int m;
+    memcpy(&m, p + L.f_n, 4);
+    m = m < 0 ? 0 : (m > t->cfg.n_max ? t->cfg.n_max : m);
+    if (n) *n = m;
+    if (px) memcpy(px, p + L.f_px, 8 * (size_t)m);
+    if (lmid) memcpy(lmid, p + L.f_lm, 4 * (size_t)m);
+    if (is3d) memcpy(is3d, p + L.f_3d, (size_t)m);
+    if (wpt) memcpy(wpt, p + L.f_w, 24 * (size_t)m);
+    return OV2_OK;
+}
+
+} // extern "C"
+
+// items [b0, b0 + nb): the ops checked, packed into the control block, one copy up, k_res_update, the records down; the mirror
+// advanced by the same rule
+static int res_update(ov2_btracker *t, int b0, int nb, const int *n_ops_h, const ov2_resident_op *const *ops_h,
+                      ov2_resident_update_result *results)
+{
+    OV2_REQUIRE(t && n_ops_h && ops_h && results, OV2_EINVAL, "ov2_btracker_update_frame: NULL argument");
+    OV2_REQUIRE(nb >= 1 && b0 >= 0 && b0 <= t->batch - nb, OV2_EINVAL, "batch item out of range");
+    const int nm = t->cfg.n_max;
+    size_t total = 0;
+    std::vector<int> ids;
+    for (int k = 0; k < nb; k++) {
+        const int n = n_ops_h[k];
+        OV2_REQUIRE(n >= 0 && n <= nm, OV2_EINVAL, "ov2_btracker_update_frame: n_ops outside [0, cfg.n_max]");
+        OV2_REQUIRE(n == 0 || ops_h[k], OV2_EINVAL, "ov2_btracker_update_frame: NULL op list");
+        ids.clear();
+        for (int j = 0; j < n; j++) {
+            const ov2_resident_op &q = ops_h[k][j];
+            OV2_REQUIRE(q.op == OV2_RES_SET_POINT || q.op == OV2_RES_UNSET_POINT || q.op == OV2_RES_REMOVE, OV2_EINVAL, "ov2_btracker_update_frame: unknown op");
+            OV2_REQUIRE(q.op != OV2_RES_SET_POINT || (std::isfinite(q.xyz[0]) && std::isfinite(q.xyz[1]) && std::isfinite(q.xyz[2])), OV2_EINVAL,
+                        "ov2_btracker_update_frame: xyz not finite on OV2_RES_SET_POINT");
+            ids.push_back(q.lmid);
+        }
+        std::sort(ids.begin(), ids.end());
+        OV2_REQUIRE(std::adjacent_find(ids.begin(), ids.end()) == ids.end(), OV2_EINVAL, "ov2_btracker_update_frame: an lmid repeated within one item's list");
+        total += (size_t)n;
+    }
+    int rc = res_entry(t, b0, nb, "ov2_btracker_update_frame between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    const BtResLayout &L = t->rl;
+    const hipStream_t s = t->ctx->stream;
+    uint8_t *h = t->hrc, *d = t->drc;
+    memcpy(h + L.u_sel, t->res_sel.data(), (size_t)t->batch);
+    int *nop = (int *)(h + L.u_nop), *off = (int *)(h + L.u_off);
+    ov2_resident_op *ops = (ov2_resident_op *)(h + L.u_ops);
+    size_t at = 0;
+    for (int k = 0; k < nb; k++) {
+        nop[b0 + k] = n_ops_h[k]; off[b0 + k] = (int)at;
+        if (n_ops_h[k]) memcpy(ops + at, ops_h[k], sizeof(ov2_resident_op) * (size_t)n_ops_h[k]);
+        at += (size_t)n_ops_h[k];
+    }
+    OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.u_ops + sizeof(ov2_resident_op) * total, hipMemcpyHostToDevice, s));
+    ResUpdateArgs a;
+    a.f = res_frames(t);
+    a.n_ops = (const int *)(d + L.u_nop); a.op_off = (const int *)(d + L.u_off); a.ops = (const ov2_resident_op *)(d + L.u_ops);
+    a.rec = (ov2_resident_update_result *)(d + L.u_rec);
+    rc = ov2_launch_res_update(s, a, b0, nb, (int)total);
+    if (rc != OV2_OK) return rc;
+    const size_t ro = L.u_rec + sizeof(ov2_resident_update_result) * (size_t)b0;
+    OV2_HIP_CHECK(hipMemcpyAsync(h + ro, d + ro, sizeof(ov2_resident_update_result) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    OV2_HIP_CHECK(hipStreamSynchronize(s));
+    memcpy(results, h + ro, sizeof(ov2_resident_update_result) * (size_t)nb);
+    // the mirror, by the kernel's rule (an id stands once in a frame and once in a list)
+    std::vector<std::pair<int, int>> byid;
+    for (int k = 0; k < nb; k++) {
+        const int b = b0 + k, n_ops = n_ops_h[k];
+        byid.clear();
+        for (int j = 0; j < n_ops; j++) byid.push_back({ops_h[k][j].lmid, j});
+        std::sort(byid.begin(), byid.end());
+        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
+        const int n = *src.n;
+        int r = 0;
+        for (int i = 0; i < n; i++) {
+            const auto it = std::lower_bound(byid.begin(), byid.end(), std::make_pair(src.lmid[i], 0));
+            const ov2_resident_op *q = it != byid.end() && it->first == src.lmid[i] ? &ops_h[k][it->second] : nullptr;
+            if (q && q->op == OV2_RES_REMOVE) continue;
+            dst.px[2 * r] = src.px[2 * i]; dst.px[2 * r + 1] = src.px[2 * i + 1];
+            dst.lmid[r] = src.lmid[i];
+            dst.is3d[r] = q && q->op == OV2_RES_SET_POINT ? 1 : (q && q->op == OV2_RES_UNSET_POINT ? 0 : src.is3d[i]);
+            for (int c = 0; c < 3; c++) dst.wpt[3 * r + c] = q && q->op == OV2_RES_SET_POINT ? q->xyz[c] : src.wpt[3 * i + c];
+            r++;
+        }
+        *dst.n = r;
+        t->res_sel[(size_t)b] ^= 1;
+    }
+    return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_update_frame(ov2_btracker *t, int item, int n_ops, const ov2_resident_op *ops, ov2_resident_update_result *result)
+{
+    return res_update(t, item, 1, &n_ops, &ops, result);
+}
+
+int ov2_btracker_update_frame_batch(ov2_btracker *t, int n_active, const int *n_ops_h, const ov2_resident_op *const *ops_h,
+                                    ov2_resident_update_result *results)
+{
+    return res_update(t, 0, n_active, n_ops_h, ops_h, results);
+}
+
+int ov2_btracker_track_mono_resident_begin(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, int klt_use_prior,
+                                           const ov2_track_mono_params *params, const ov2_track_mono_input *input)
+{
+    OV2_REQUIRE(t && params && input, OV2_EINVAL, "ov2_btracker_track_mono_resident: NULL tracker / params / input");
+    OV2_REQUIRE(!input->step.lmid_h && !input->step.pose.scale_h, OV2_EINVAL,
+                "ov2_btracker_track_mono_resident: lmid_h and scale_h must be NULL (the frame is resident, every scale is 0)");
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
+    const int rc = res_entry(t, 0, n_active, "ov2_btracker_track_frame_begin: a step or an ov2_btracker_create_keyframe call is open");
+    if (rc != OV2_OK) return rc;
+    std::vector<int> n((size_t)n_active);
+    for (int b = 0; b < n_active; b++) n[(size_t)b] = *res_host(t, b, 0).n;
+    StepArgs A;
+    A.form = STEP_MONO; A.resident = true; A.n_active = n_active; A.img_h = img_h; A.stride = stride; A.n_h = n.data();
+    A.klt_use_prior = klt_use_prior; A.mp = params; A.min = input;
+    return track_frame_begin(t, A);
+}
+
+int ov2_btracker_track_mono_resident_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, int *p3p_req,
+                                         ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
+                                         ov2_track_mono_result *mono_results, ov2_resident_step_result *frame_results)
+{
+    OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!t->pend.on || t->pend.resident, OV2_EINVAL,
+                "ov2_btracker_track_mono_resident_end: the step was not begun with ov2_btracker_track_mono_resident_begin");
+    OV2_REQUIRE(!t->pend.on || (t->pend.form == STEP_EPI) == (epi_results != nullptr), OV2_EINVAL,
+                "ov2_btracker_track_mono_end: epi_results goes with doepipolar == 1, and only with it");
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results, frame_results);
+}
+
+int ov2_btracker_track_mono_resident(ov2_btracker *t, int n_active, const uint8_t *const *img_h, int stride, int klt_use_prior,
+                                     const ov2_track_mono_params *params, const ov2_track_mono_input *input, float *out_xy_h,
+                                     uint8_t *status_h, int *p3p_req, ov2_epifilter_result *epi_results, ov2_pose_result *pose_results,
+                                     ov2_track_mono_result *mono_results, ov2_resident_step_result *frame_results)
+{
+    OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
+    OV2_REQUIRE(!params || (params->doepipolar != 0) == (epi_results != nullptr), OV2_EINVAL,
+                "ov2_btracker_track_mono: epi_results goes with doepipolar == 1, and only with it");
+    if (t && t->dfr && n_active >= 1 && n_active <= t->batch && !t->pend.on) {      // the result buffers, against the mirror's counts
+        std::vector<int> n((size_t)n_active);
+        for (int b = 0; b < n_active; b++) n[(size_t)b] = *res_host(t, b, 0).n;
+        const int rc = check_outputs(t, n_active, n.data(), out_xy_h, status_h, pose_results, epi_results);
+        if (rc != OV2_OK) return rc;
+    }
+    const int rc = ov2_btracker_track_mono_resident_begin(t, n_active, img_h, stride, klt_use_prior, params, input);
+    if (rc != OV2_OK) return rc;
+    return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results, frame_results);
+}
+
+int ov2_btracker_last_slot_bytes(const ov2_btracker *t, size_t *h2d)
+{
+    OV2_REQUIRE(t && h2d, OV2_EINVAL, "NULL argument");
+    *h2d = t->slot_bytes;
+    return OV2_OK;
+}
+
 int ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, int *slot_idx, int *m, int *samples, int *n_rows_used)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
@@ -1850,7 +2268,10 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     OV2_REQUIRE(t && params && input, OV2_EINVAL, "ov2_btracker_create_keyframe: NULL tracker / params / input");
     const ov2_create_keyframe_params &p = *params;
     const ov2_create_keyframe_input &in = *input;
-    OV2_REQUIRE(in.px_h && in.lmid_h && in.is3d_h && in.n_h && in.make_kf_h && in.nlmid_h && in.nkfid_h && in.time_h, OV2_EINVAL,
+    const bool resident = !in.px_h;                                      // the frame is the resident one (f21)
+    OV2_REQUIRE(resident ? (!in.lmid_h && !in.is3d_h && !in.n_h) : (in.lmid_h && in.is3d_h && in.n_h), OV2_EINVAL,
+                "ov2_btracker_create_keyframe: px_h / lmid_h / is3d_h / n_h are all NULL (the resident frame) or none is");
+    OV2_REQUIRE(in.make_kf_h && in.nlmid_h && in.nkfid_h && in.time_h, OV2_EINVAL,
                 "ov2_btracker_create_keyframe: NULL px_h / lmid_h / is3d_h / n_h / make_kf_h / nlmid_h / nkfid_h / time_h");
     OV2_REQUIRE(p.detector != OV2_CKF_DET_GFTT, OV2_EINVAL, "ov2_btracker_create_keyframe: detectGFTT is not fused (detector OV2_CKF_DET_GFTT)");
     OV2_REQUIRE(p.detector == OV2_CKF_DET_SINGLESCALE || p.detector == OV2_CKF_DET_GRID_FAST, OV2_EINVAL, "ov2_btracker_create_keyframe: unknown detector");
@@ -1877,16 +2298,23 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     int rc = det_ready(t->ctx, c.w, c.h, p.det_cell, mode);  if (rc != OV2_OK) return rc;
     const int ncells = (c.w / p.det_cell) * (c.h / p.det_cell);
     const size_t nm = (size_t)c.n_max;
+    std::vector<int> n_res;                                              // the resident form: the mirror's counts stand for n_h
+    if (resident) {
+        rc = ensure_res(t);  if (rc != OV2_OK) return rc;
+        for (int b = 0; b < n_active; b++) n_res.push_back(*res_host(t, b, 0).n);
+    }
+    const int *n_h = resident ? n_res.data() : in.n_h;
     bool any = false;
     for (int b = 0; b < n_active; b++) {
-        const int n = in.n_h[b];
+        const int n = n_h[b];
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
         if (!in.make_kf_h[b]) continue;
         any = true;
         const int nl = in.nlmid_h[b];
         OV2_REQUIRE(nl >= 0 && (long long)nl + 2ll * ncells <= 2147483647ll, OV2_EINVAL, "nlmid_h negative, or nlmid_h + the detector's capacity overflows int");
+        const int *lmid = resident ? res_host(t, b, 0).lmid : in.lmid_h + nm * (size_t)b;
         for (int i = 0; i < n; i++) {
-            const int lm = in.lmid_h[nm * (size_t)b + (size_t)i];
+            const int lm = lmid[i];
             OV2_REQUIRE(lm >= 0 && lm < nl, OV2_EINVAL, "lmid_h outside [0, nlmid_h): the map's id counter is monotone");
         }
         OV2_REQUIRE(std::isfinite(in.time_h[b]), OV2_EINVAL, "time not finite");
@@ -1909,11 +2337,13 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     P.flag.assign(in.make_kf_h, in.make_kf_h + n_active);
     P.nkfid.assign(in.nkfid_h, in.nkfid_h + n_active);
     P.time.assign(in.time_h, in.time_h + n_active);
+    P.resident = resident;
+    t->slot_bytes = 0;
     // ---- the inputs into the pinned block ----
     const BtCkfLayout &L = t->cl;
     uint8_t *h = t->hckf, *d = t->dckf;
     const size_t na = (size_t)n_active;
-    memcpy(h + L.c_n, in.n_h, 4 * na);
+    memcpy(h + L.c_n, n_h, 4 * na);
     for (int b = 0; b < n_active; b++) h[L.c_fl + (size_t)b] = in.make_kf_h[b] ? 1 : 0;
     memcpy(h + L.c_nl, in.nlmid_h, 4 * na);
     memcpy(h + L.c_id, in.nkfid_h, 4 * na);
@@ -1922,11 +2352,12 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     for (int b = 0; b < n_active; b++) {
         if (mode == 0) memcpy(h + L.c_par + 4 * (size_t)b, in.fast_th_inout + b, 4);
         else memcpy(h + L.c_par + 8 * (size_t)b, in.quality_inout + b, 8);
-        const size_t n = in.make_kf_h[b] ? (size_t)in.n_h[b] : 0, o = nm * (size_t)b;
+        const size_t n = in.make_kf_h[b] && !resident ? (size_t)in.n_h[b] : 0, o = nm * (size_t)b;
         if (!n) continue;
         memcpy(h + L.c_px + 8 * o, in.px_h + 2 * o, 8 * n);
         memcpy(h + L.c_lm + 4 * o, in.lmid_h + o, 4 * n);
         memcpy(h + L.c_3d + o, in.is3d_h + o, n);
+        t->slot_bytes += 13 * n;
     }
     // ---- the one enqueue ----
     const hipStream_t s = ctx->stream;
@@ -1934,7 +2365,16 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     rc = ov2_pyr_wait_ready(ctx, pyr);  if (rc != OV2_OK) return rc;
     const PyrLevelDesc &L0 = pyr->d.lv[0];
     const uint8_t *im = pyr->d.base + L0.img_roi;
-    OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.c_up, hipMemcpyHostToDevice, s));
+    // (the resident form: the per-item sections only; k_res_ckf_in fills the per-slot ranges on the device)
+    OV2_HIP_CHECK(hipMemcpyAsync(d, h, resident ? L.c_3d : L.c_up, hipMemcpyHostToDevice, s));
+    ResCkfArgs ra;
+    if (resident) {
+        rc = res_push_sel(t, s);  if (rc != OV2_OK) return rc;
+        ra.f = res_frames(t);
+        ra.flag = d + L.c_fl; ra.n = (int *)(d + L.c_n); ra.px = (float2 *)(d + L.c_px); ra.lmid = (int *)(d + L.c_lm); ra.is3d = d + L.c_3d;
+        ra.rec = (const ov2_create_keyframe_result *)(d + L.c_rec);
+        rc = ov2_launch_res_ckf_in(s, ra, n_active);  if (rc != OV2_OK) return rc;
+    }
     uint8_t *w = t->dckw;
     CkfArgs a;
     a.n = (const int *)(d + L.c_n); a.flag = d + L.c_fl; a.nlmid = (const int *)(d + L.c_nl); a.nkfid = (const int *)(d + L.c_id);
@@ -1976,6 +2416,7 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
         OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], s));
     }
     rc = ov2_launch_ckf_install(s, a, n_active);  if (rc != OV2_OK) return rc;
+    if (resident) { rc = ov2_launch_res_adopt(s, ra, n_active);  if (rc != OV2_OK) return rc; }
     OV2_HIP_CHECK(hipMemcpyAsync(h + L.c_io, d + L.c_io, (p.use_brief ? L.c_down : L.c_desc) - L.c_io, hipMemcpyDeviceToHost, s));
     P.on = true;
     return OV2_OK;
@@ -2034,6 +2475,17 @@ int ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result
         memcpy(&t->kf_hdr[(size_t)b], h + L.c_hdr + sizeof(FeKfHdr) * (size_t)b, sizeof(FeKfHdr));
         t->res_ki[(size_t)b] = MonoKfInfo{P.nkfid[(size_t)b], r.nb3dkps, 1, 0};
         t->res_kt[(size_t)b] = P.time[(size_t)b];
+        if (!P.resident) continue;
+        // the resident frame's mirror, as k_res_adopt left the device: the old slots, then the new points without a 3-D point
+        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
+        memcpy(dst.px, h + L.c_px + 8 * o, 8 * n);
+        memcpy(dst.lmid, lm, 4 * n);
+        memcpy(dst.is3d, src.is3d, n0);
+        memcpy(dst.wpt, src.wpt, 24 * n0);
+        memset(dst.is3d + n0, 0, n - n0);
+        memset(dst.wpt + 3 * n0, 0, 24 * (n - n0));
+        *dst.n = (int)n;
+        t->res_sel[(size_t)b] ^= 1;
     }
     return OV2_OK;
 }

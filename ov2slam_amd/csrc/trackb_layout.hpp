@@ -1,6 +1,6 @@
 // trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
 // point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block, the three blocks of
-// ov2_btracker_track_mono and the block of ov2_btracker_create_keyframe, each computed by one
+// ov2_btracker_track_mono, the block of ov2_btracker_create_keyframe and the two blocks of the resident frame, each computed by one
 // function of (batch, n_max).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
@@ -122,5 +122,33 @@ static inline BtCkfLayout bt_ckf_layout(int batch, int n_max)
     L.c_un = c.take(8 * slots); L.c_bv = c.take(24 * slots); L.c_col = c.take(slots); L.c_perm = c.take(4 * slots);
     L.c_desc = c.take(32 * slots); L.c_val = c.take(slots); L.c_down = c.off;
     L.w_skip = c.take(B); L.w_nb = c.take(4 * B); L.dev_bytes = c.off;
+    return L;
+}
+
+// The resident frame (ov2_btracker_set_frame / _update_frame / _track_mono_resident): the current frame of every item, kept on the
+// device from step to step.  ITEM-MAJOR, so that the frames of items [b0, b1) are one contiguous range (one copy per direction):
+//   one item    [n 4, padded to 16][px 8][lmid 4][is3d 1][wpt 24 per slot], f_item bytes (a multiple of 256)
+//   one buffer  batch items; the block holds TWO buffers (a step reads an item's frame from one and writes the next frame into the
+//               other; which one is current is kept per item on the host and travels as one byte per item)
+// The pinned host mirror has the same layout.  The control block of a call (pinned, and its device mirror at the same offsets):
+//   up    [sel 1][n_ops 4][first op 4 per item][ops 32 per slot, PACKED: item b's list starts at its first op]   (u_up at capacity;
+//         an update sends [0, u_ops + 32 x the ops of the call), a step or a create_keyframe call [0, u_nop) only)
+//   down  [record 24 per item]
+#define BT_RES_OP_BYTES 32           // sizeof(ov2_resident_op), sizeof(ov2_resident_update_result): trackb.hip asserts both
+#define BT_RES_REC_BYTES 24
+struct BtResLayout {
+    size_t f_n, f_px, f_lm, f_3d, f_w, f_item, buf_bytes, frame_bytes;
+    size_t u_sel, u_nop, u_off, u_ops, u_up, u_rec, ctl_bytes;
+};
+static inline BtResLayout bt_res_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, nm = (size_t)n_max, slots = nm * B;
+    BtResLayout L;
+    StageCursor f(16);
+    L.f_n = f.take(4); L.f_px = f.take(8 * nm); L.f_lm = f.take(4 * nm); L.f_3d = f.take(nm); L.f_w = f.take(24 * nm);
+    L.f_item = up256(f.off); L.buf_bytes = L.f_item * B; L.frame_bytes = 2 * L.buf_bytes;
+    StageCursor c(256);
+    L.u_sel = c.take(B); L.u_nop = c.take(4 * B); L.u_off = c.take(4 * B); L.u_ops = c.take(BT_RES_OP_BYTES * slots);
+    L.u_up = c.off; L.u_rec = c.take(BT_RES_REC_BYTES * B); L.ctl_bytes = c.off;
     return L;
 }

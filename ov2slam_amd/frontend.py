@@ -790,10 +790,13 @@ class LockstepTracker:
 
     def _mono_args(self, na, nn, params, epi_params, p3p_req, seed, lmid, nbkfs, epi_seed, time, frame_id, localba_is_on, doepipolar,
                    scale, dop3p, n_rows):
-        ep, ei, keep = self._epi_args(na, nn, params, epi_params, np.zeros((max(1, na), 7)), p3p_req, seed, lmid,
+        ep, ei, keep = self._epi_args(na, nn, params, epi_params, np.zeros((max(1, na), 7)), p3p_req, seed,
+                                      np.zeros((self.batch, self.n_max), np.int32) if lmid is None else lmid,
                                       np.zeros(self.batch, np.int32) if nbkfs is None else nbkfs,
                                       np.zeros(self.batch, np.uint64) if epi_seed is None else epi_seed, scale, dop3p, n_rows)
         ei.pose.Twc_h = None                                                      # the pose is resident
+        if lmid is None:
+            ei.lmid_h = None                                                      # ... and so is the frame (trackMonoResident)
         mp, mi = L.TrackMonoParams(), L.TrackMonoInput()
         mp.step, mp.doepipolar = ep, int(bool(doepipolar))
         tm = np.ascontiguousarray(time, np.float64).reshape(-1)
@@ -862,6 +865,110 @@ class LockstepTracker:
         return (out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn) if self._mono_epi else None, self._pose_dicts(R, removed, nn),
                 self._mono_dicts(M, na))
 
+    # ---- the current frame resident on the device between the steps (ov2_btracker_set_frame, ..._track_mono_resident) -------------
+    def setFrame(self, item, px, lmid, is3d, wpt):
+        """installs the current frame of item `item` on the device (ov2_btracker_set_frame): px (n, 2), lmid (n,) distinct and >= 0,
+        is3d (n,), wpt (n, 3), n <= n_max.  The first install, and the fallback where createKeyframe did not create.  Between
+        steps only."""
+        px = np.ascontiguousarray(px, np.float32).reshape(-1, 2)
+        lm = np.ascontiguousarray(lmid, np.int32).reshape(-1)
+        d3 = np.ascontiguousarray(is3d, np.uint8).reshape(-1)
+        w = np.ascontiguousarray(wpt, np.float64).reshape(-1, 3)
+        if not (len(px) == len(lm) == len(d3) == len(w)):
+            raise ValueError("one px, one lmid, one is3d and one wpt per slot")
+        L.check(self.lib.ov2_btracker_set_frame(self.h_trk, int(item), len(lm), _ptr(px), _ptr(lm), _ptr(d3), _ptr(w)))
+
+    def getFrame(self, item, from_device=True):
+        """the resident frame of item `item` -> dict(n, px (n, 2), lmid (n,), is3d (n,), wpt (n, 3)): copied down from the device
+        block, or with from_device False the host mirror.  wpt of a slot that is not 3-D is whatever the slot last carried."""
+        n = C.c_int()
+        px, lm = np.zeros((self.n_max, 2), np.float32), np.zeros(self.n_max, np.int32)
+        d3, w = np.zeros(self.n_max, np.uint8), np.zeros((self.n_max, 3), np.float64)
+        L.check(self.lib.ov2_btracker_get_frame(self.h_trk, int(item), int(bool(from_device)), C.byref(n), _ptr(px), _ptr(lm), _ptr(d3), _ptr(w)))
+        k = n.value
+        return dict(n=k, px=px[:k].copy(), lmid=lm[:k].copy(), is3d=d3[:k].copy(), wpt=w[:k].copy())
+
+    def updateFrame(self, n_active, ops):
+        """what the map did to the resident frames of items [0, n_active) since the last step (ov2_btracker_update_frame_batch), one
+        upload, one launch, one download: ops[b] is a list of (lmid, op, xyz) with op L.OV2_RES_SET_POINT (wpt = xyz, is3d = 1),
+        L.OV2_RES_UNSET_POINT (is3d = 0) or L.OV2_RES_REMOVE (the slot leaves, the rest close up in slot order); xyz may be None
+        where the op does not read it.  An lmid the frame does not hold is counted.
+        -> [dict(n_before, n_after, n_set, n_unset, n_removed, n_missing)] per item"""
+        na = int(n_active)
+        if len(ops) < na:
+            raise ValueError("one op list per active item")
+        lists, cnt = [], np.zeros(max(1, na), np.int32)
+        ptrs = (C.POINTER(L.ResidentOp) * max(1, na))()
+        for b in range(na):
+            arr = (L.ResidentOp * max(1, len(ops[b])))()
+            for j, (lmid, op, xyz) in enumerate(ops[b]):
+                arr[j].lmid, arr[j].op = int(lmid), int(op)
+                arr[j].xyz = (C.c_double * 3)(*([0.0, 0.0, 0.0] if xyz is None else [float(v) for v in xyz]))
+            lists.append(arr)
+            cnt[b] = len(ops[b])
+            ptrs[b] = C.cast(arr, C.POINTER(L.ResidentOp))
+        R = (L.ResidentUpdateResult * max(1, na))()
+        L.check(self.lib.ov2_btracker_update_frame_batch(self.h_trk, na, cnt.ctypes.data_as(C.POINTER(C.c_int)), ptrs, R))
+        return [{k: int(getattr(R[b], k)) for k, _ in L.ResidentUpdateResult._fields_} for b in range(na)]
+
+    def lastSlotBytes(self):
+        """bytes of per-slot input (keypoints, points, flags, ids, scales: anything sized by n or n_max; not images) the last step or
+        createKeyframe call wrote for the device: 0 for the resident forms"""
+        v = C.c_size_t()
+        L.check(self.lib.ov2_btracker_last_slot_bytes(self.h_trk, C.byref(v)))
+        return int(v.value)
+
+    def _resident_args(self, imgs, params, epi_params, p3p_req, seed, nbkfs, epi_seed, time, frame_id, localba_is_on, doepipolar, dop3p,
+                       n_rows):
+        na = len(imgs)
+        imgs, stride, ptrs = self._frames(imgs)
+        mp, mi, keep = self._mono_args(na, None, params, epi_params, p3p_req, seed, None, nbkfs, epi_seed, time, frame_id, localba_is_on,
+                                       doepipolar, None, dop3p, n_rows)
+        return na, imgs, stride, ptrs, mp, mi, keep
+
+    def _resident_results(self, na):
+        out, st, p3p = self._outputs(na)
+        R, removed = self._pose_results(na, None)
+        E, bufs = self._epi_results(na)
+        return out, st, p3p, R, removed, E, bufs, (L.TrackMonoResult * max(1, na))(), (L.ResidentStepResult * max(1, na))()
+
+    def _resident_return(self, na, out, st, p3p, R, removed, E, bufs, M, F, epi):
+        nn = np.array([F[b].n_before for b in range(na)], np.int32)
+        return (out, st, p3p.astype(bool), self._epi_dicts(E, bufs, nn) if epi else None, self._pose_dicts(R, removed, nn),
+                self._mono_dicts(M, na), [dict(n_before=int(F[b].n_before), n_after=int(F[b].n_after)) for b in range(na)])
+
+    def trackMonoResident(self, imgs, params, epi_params, p3p_req, seed, nbkfs, epi_seed, time, frame_id, localba_is_on=None,
+                          doepipolar=True, dop3p=False, n_rows=0, klt_use_prior=True):
+        """trackMono on the resident frames (ov2_btracker_track_mono_resident): as trackMono without kps, wpt, is3d, n, lmid and scale
+        -- the frame of each item is the one setFrame / updateFrame / createKeyframe / the last step left on the device, and the
+        step leaves its successor there: the tracked px of the slots that are tracked and were removed by neither the filter nor the
+        pose, with their lmid, is3d and wpt, in slot order.
+        -> (out, status bits, p3p_req, epis, poses, monos, frames): as trackMono, in the slot space of the frame BEFORE the step;
+        frames[b] = dict(n_before, n_after)."""
+        na, imgs, stride, ptrs, mp, mi, keep = self._resident_args(imgs, params, epi_params, p3p_req, seed, nbkfs, epi_seed, time, frame_id,
+                                                                   localba_is_on, doepipolar, dop3p, n_rows)
+        out, st, p3p, R, removed, E, bufs, M, F = self._resident_results(na)
+        L.check(self.lib.ov2_btracker_track_mono_resident(self.h_trk, na, ptrs, stride, int(bool(klt_use_prior)), C.byref(mp), C.byref(mi),
+                                                          _ptr(out), _ptr(st), _ptr(p3p), E if doepipolar else None, R, M, F))
+        return self._resident_return(na, out, st, p3p, R, removed, E, bufs, M, F, doepipolar)
+
+    def trackMonoResidentBegin(self, imgs, params, epi_params, p3p_req, seed, nbkfs, epi_seed, time, frame_id, localba_is_on=None,
+                               doepipolar=True, dop3p=False, n_rows=0, klt_use_prior=True):
+        """first half of trackMonoResident; trackMonoResidentEnd finishes it (trackFrameEnd gives the tracking half, drops the rest and
+        leaves the resident pose, state and frames as they were)"""
+        na, imgs, stride, ptrs, mp, mi, keep = self._resident_args(imgs, params, epi_params, p3p_req, seed, nbkfs, epi_seed, time, frame_id,
+                                                                   localba_is_on, doepipolar, dop3p, n_rows)
+        L.check(self.lib.ov2_btracker_track_mono_resident_begin(self.h_trk, na, ptrs, stride, int(bool(klt_use_prior)), C.byref(mp), C.byref(mi)))
+        self._pending = (imgs, None, None, None, np.zeros(na, np.int32))
+
+    def trackMonoResidentEnd(self):
+        """second half of trackMonoResident -> (out, status bits, p3p_req, epis, poses, monos, frames)"""
+        na = len(self._pending[4])
+        out, st, p3p, R, removed, E, bufs, M, F = self._resident_results(na)
+        L.check(self.lib.ov2_btracker_track_mono_resident_end(self.h_trk, _ptr(out), _ptr(st), _ptr(p3p), E if self._mono_epi else None, R, M, F))
+        self._pending = None
+        return self._resident_return(na, out, st, p3p, R, removed, E, bufs, M, F, self._mono_epi)
+
     # ---- createKeyframe for the items a step flagged (ov2_btracker_create_keyframe) ------------------------------------------------
     def _ckf_args(self, n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc):
         na = int(n_active)
@@ -873,10 +980,13 @@ class LockstepTracker:
         cp.roi = (C.c_int * 4)(*[int(v) for v in params.get("roi", (0, 0, self.w, self.h))])
         cp.mask_mode = int(params.get("mask_mode", L.OV2_MASK_AS_EXECUTED))
         cp.do_subpix, cp.use_brief = int(bool(params.get("do_subpix", True))), int(bool(params.get("use_brief", True)))
-        px = np.ascontiguousarray(px, np.float32).reshape(self.batch, self.n_max, 2)
-        lm = np.ascontiguousarray(lmid, np.int32).reshape(self.batch, self.n_max)
-        d3 = np.ascontiguousarray(is3d, np.uint8).reshape(self.batch, self.n_max)
-        nn = np.ascontiguousarray(n, np.int32).reshape(-1)
+        resident = px is None                                                     # the frame is the resident one
+        if resident and not (lmid is None and is3d is None and n is None):
+            raise ValueError("px None means the resident frame: lmid, is3d and n must be None too")
+        px = None if resident else np.ascontiguousarray(px, np.float32).reshape(self.batch, self.n_max, 2)
+        lm = None if resident else np.ascontiguousarray(lmid, np.int32).reshape(self.batch, self.n_max)
+        d3 = None if resident else np.ascontiguousarray(is3d, np.uint8).reshape(self.batch, self.n_max)
+        nn = np.zeros(na, np.int32) if resident else np.ascontiguousarray(n, np.int32).reshape(-1)
         mk = np.ascontiguousarray(make_kf, np.uint8).reshape(-1)
         nl = np.ascontiguousarray(nlmid, np.int32).reshape(-1)
         ki = np.ascontiguousarray(nkfid, np.int32).reshape(-1)
@@ -892,10 +1002,10 @@ class LockstepTracker:
         if len(st) < na:
             raise ValueError("one adaptive state per active item")
         ci = L.CreateKeyframeInput()
-        ci.px_h = px.ctypes.data_as(C.POINTER(C.c_float))
-        ci.lmid_h = lm.ctypes.data_as(C.POINTER(C.c_int))
-        ci.is3d_h = d3.ctypes.data_as(C.POINTER(C.c_uint8))
-        ci.n_h = nn.ctypes.data_as(C.POINTER(C.c_int))
+        ci.px_h = None if resident else px.ctypes.data_as(C.POINTER(C.c_float))
+        ci.lmid_h = None if resident else lm.ctypes.data_as(C.POINTER(C.c_int))
+        ci.is3d_h = None if resident else d3.ctypes.data_as(C.POINTER(C.c_uint8))
+        ci.n_h = None if resident else nn.ctypes.data_as(C.POINTER(C.c_int))
         ci.make_kf_h = mk.ctypes.data_as(C.POINTER(C.c_uint8))
         ci.nlmid_h = nl.ctypes.data_as(C.POINTER(C.c_int))
         ci.nkfid_h = ki.ctypes.data_as(C.POINTER(C.c_int))
@@ -933,6 +1043,8 @@ class LockstepTracker:
         params: dict(ncellsize, nbwcells, nbhcells, nbmaxkps, detector "singlescale" | "gridfast", det_cell, roi, mask_mode, do_subpix,
         use_brief); state: float64 qualities (single scale) or int32 thresholds (FAST), one per item, updated in place; Twc
         (>= n_active, 7) or None: the resident pose; out: dict of arrays to scatter into (missing ones are zeros).
+        px None (with lmid, is3d and n None): the frames are the resident ones (setFrame, trackMonoResident); nothing per slot
+        goes up, and the frame with the new points appended (is3d 0, wpt 0) becomes the resident frame of every CREATED item.
         -> (records, out): records[b] = dict(action, n_prev, noccupcells, nb2detect, n_new, n_kf, nb3dkps); out = dict(px, lmid, unpx,
         bv, desc, valid, color) in slot layout, written for the items with action OV2_CKF_CREATED only."""
         na, cp, ci, keep = self._ckf_args(n_active, px, lmid, is3d, n, make_kf, nlmid, nkfid, time, params, state, Twc)
