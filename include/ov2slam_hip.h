@@ -718,7 +718,8 @@ typedef struct {
     double solve_ms[2];          /* device time of each pass                                              */
     int status;                  /* OV2_OK, or this problem's error code (ABI 600).  ov2_local_ba: the value it returns.  ov2_local_ba_batch:
                                     every problem is attempted; r[i].status tells which results are valid and the call returns the
-                                    first non-OK status (OV2_OK when all are)                                                        */
+                                    first non-OK status in problem order (OV2_OK when all are).  The buffers of a problem whose
+                                    input was rejected are not written                                                               */
 } ov2_local_ba_result;
 void ov2_local_ba_default_options(ov2_local_ba_options *o);
 int  ov2_local_ba(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r);
@@ -733,6 +734,9 @@ int  ov2_local_ba(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_opti
  * the batch's pass.  Problems the shared launches do not cover (more optimised keyframes than the LDS-resident path holds,
  * OV2_RES_PNP blocks, no landmarks, OV2_OPT_BA_DETERMINISTIC) are solved one after the other through ov2_local_ba in the same
  * call; *n_batched (or NULL) = how many shared the launches; a failure of one of them (r[i].status) does not stop the others.
+ * Options that disagree (or robust_mono_th <= 0) are an error of the batch: every status is OV2_EINVAL and nothing runs.  A problem
+ * whose input is rejected gets its own code and leaves the shared launches to the others; a failure of the shared launches
+ * themselves (memory, a HIP error) is the status of every problem that shared them, and the problems solved alone still run.
  * max_solver_time_s is ONE host-clock budget for the batch's shared pass (the batch advances iteration by iteration, so a slow
  * window ends the pass for all): a caller that wants the reference's per-problem limit leaves it at 0 here, or calls ov2_local_ba
  * per problem.                                                                                                                 */

@@ -1846,7 +1846,6 @@ static int ba_enqueue_solve(ov2_ctx *ctx, const ov2_ba_dev *dev, BADev D, const 
     if (rc != OV2_OK) return rc;
     // poses -> R | t, scales = 1 (round 1 filled the scales through a host staging vector: three copies and a synchronisation)
     hipLaunchKernelGGL(k_ba_init, dim3(G.init_blocks), dim3(256), 0, s, D);
-    D.bs_blocks = G.bs_blocks; D.cost_blocks = G.cost_blocks; D.lin_blocks = G.lin_blocks;
     // rows of the W^T C W contraction: landmarks, or the 3 pseudo-rows per point of Wp (ldim 3)
     BADev DG = D;
     if (D.ldim == 3) { DG.W = D.Wp; DG.n_lm = 3 * D.n_lm; DG.cl = D.ones; DG.etb = D.ep; }
@@ -1924,6 +1923,14 @@ static int ba_download(hipStream_t s, const ov2_ba_dev *dev, double *poses, doub
     return OV2_OK;
 }
 
+// what a solve adds to the launches' view of a problem: the loss, the clamp of the LM diagonal, and the grids whose per-work-group
+// partial sums the bookkeeping kernels add up (G: the launches' geometry -- the problem's own, or its batch's)
+static void ba_view_for_solve(BADev &D, const ov2_ba_options *o, double huber, const BAGeom &G)
+{
+    D.huber = huber; D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
+    D.bs_blocks = G.bs_blocks; D.cost_blocks = G.cost_blocks; D.lin_blocks = G.lin_blocks;
+}
+
 // keep_state: continue from the parameters and the cached chi2 / depth flags that are on the device (second pass of
 // ov2_local_ba) instead of resetting to the problem's initial values
 static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba_result *r,
@@ -1934,12 +1941,11 @@ static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba
     if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     BADev D = dev->D;
-    D.huber = o->huber_delta;
-    D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
     hipStream_t s = ctx->stream;
     const BAOpt O = ba_opt_from(*o);
     // a problem alone spreads over the whole chip: up to 256 lineariser work-groups, ~1024 for the Schur complement
     const BAGeom G = ba_geom(D, 256, 1024, ctx->ba_schur_chunk);
+    ba_view_for_solve(D, o, o->huber_delta, G);
     // size limits first: nothing is created or enqueued for a problem this path cannot solve
     OV2_REQUIRE(G.lin_lds <= BA_LIN_LDS_MAX, OV2_EUNSUPPORTED, "too many optimised keyframes for the LDS-aggregating lineariser");
     OV2_REQUIRE(G.chol_lds <= BA_CHOL_LDS_MAX, OV2_EUNSUPPORTED, "reduced system too large for the LDS-panel Cholesky");
@@ -1986,342 +1992,7 @@ static int ba_run(ov2_ctx *ctx, ov2_ba_dev *dev, const ov2_ba_options *o, ov2_ba
     return OV2_OK;
 }
 
-// ================================================================================== lock-step batch of local-BA problems
-// BASELINE configs[4]: eleven sequences advance in lock step on one GPU (ov2_btracker_*), their keyframes arrive together -- and
-// eleven estimator threads with a stream each then push ~100 launches per solve through the command processor, where they queue
-// behind each other and behind the front end's (round 5: 5.8 ms of wall clock per 0.9 ms solve, the SLAM thread 1.8x slower).
-// Here the problems of one step share every launch: blockIdx.z = problem, the kernels read their BADev from an array in device
-// memory instead of the kernel arguments, a problem that has converged (or takes no second pass) leaves through the kernels'
-// `if (ctl->done) return`.  The one-work-group kernels (factorisation, bookkeeping) so run on as many CUs as there are problems.
-// The arithmetic of a problem is that of ov2_local_ba (same device functions); grids are the largest any problem of the batch
-// needs, the per-work-group partial sums are added in a different grouping when a problem runs on a larger grid than alone.
-
-// results of the batch into ONE block (poses | inverse depths | outlier verdicts [| chi2] [| depth flags] per problem, 256-byte
-// aligned parts): one download instead of three to five small ones per problem
-__global__ __launch_bounds__(256) void k_ba_gather_B(const BADev *__restrict__ arr)
-{
-    const BADev &D = arr[blockIdx.z];
-    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
-    uint8_t *o = D.out_b;
-    for (long long e = i0; e < 7LL * D.n_kf; e += stride) ((double *)o)[e] = D.x_pose[e];
-    o += (56 * (size_t)D.n_kf + 255) & ~(size_t)255;
-    for (long long e = i0; e < D.n_lm; e += stride) ((double *)o)[e] = D.x_lam[e];
-    o += (8 * (size_t)max(1, D.n_lm) + 255) & ~(size_t)255;
-    for (long long e = i0; e < D.n_res; e += stride) o[e] = D.bad_obs[e];
-    o += ((size_t)D.n_res + 255) & ~(size_t)255;
-    if (D.out_flags & 1) { for (long long e = i0; e < D.n_res; e += stride) ((double *)o)[e] = D.chi2[e]; o += (8 * (size_t)D.n_res + 255) & ~(size_t)255; }
-    if (D.out_flags & 2) for (long long e = i0; e < D.n_res; e += stride) o[e] = D.dpos[e];
-}
-
-struct BABatch {
-    std::vector<ov2_ba_dev *> devs;
-    BADev *h_arr = nullptr, *d_arr = nullptr;           // the problems' device views: pinned staging / device copy
-    BACtl *h_ctl = nullptr, *d_ctl = nullptr;           // control blocks, consecutive (one download per pass)
-    int *h_cnt = nullptr, *d_cnt = nullptr;             // 16 counters per problem (k_ba_mark_outliers)
-    volatile int *h_flag = nullptr;                     // the look-ahead words of k_ba_decide
-    bool lm_live_first = false;                         // second pass: landmarks that lost all their blocks leave the program first
-    ~BABatch() { for (ov2_ba_dev *d : devs) ba_destroy(d); }
-};
-
-// one LM solve of every problem of the batch (ba_run's loop on batched launches); skip[i]: the problem sits this pass out
-static int ba_run_batch(ov2_ctx *ctx, BABatch &B, const ov2_ba_options *o, const double *huber, const uint8_t *skip, bool keep_state, float *ms_out)
-{
-    int rc = ba_check_options(o);
-    if (rc != OV2_OK) return rc;
-    const int N = (int)B.devs.size();
-    hipStream_t s = ctx->stream;
-    const BAOpt O = ba_opt_from(*o);
-    // a single problem spreads over the whole chip for latency (16 landmarks per lineariser work-group, 1024 Schur work-groups); a batch
-    // fills it anyway: ~768 lineariser and ~2048 Schur work-groups over ALL problems -- fewer flushes of the LDS aggregates and fewer
-    // atomic adds into G per problem (eleven windows: 2.31 -> 2.07 ms of device time; tools/r5_ba_batch_grid.sh swept 512 .. 4096 / 1024 .. 16384)
-    const int lin_total = 768, schur_total = 2048;
-    const int lin_cap = std::max(16, std::min(256, (lin_total + N - 1) / N));
-    const int schur_wgs = std::max(64, std::min(1024, (schur_total + N - 1) / N));
-    // grids and LDS bytes: the largest any problem needs; the Schur split is each problem's own (into its view)
-    std::vector<BAGeom> each((size_t)N);
-    for (int i = 0; i < N; i++) each[(size_t)i] = ba_geom(B.devs[(size_t)i]->D, lin_cap, schur_wgs);
-    BAGeom G = each[0];
-    for (int i = 1; i < N; i++) ba_geom_max(G, each[(size_t)i]);
-    OV2_REQUIRE(G.lin_lds <= BA_LIN_LDS_MAX && G.chol_lds <= BA_CHOL_LDS_MAX, OV2_EUNSUPPORTED, "a problem of the batch is too large for the LDS-resident path");
-    rc = ba_raise_lds_limits();
-    if (rc == OV2_OK) rc = ba_events(ctx);
-    if (rc != OV2_OK) return rc;
-    for (int i = 0; i < N; i++) {
-        BADev D = B.devs[(size_t)i]->D;
-        const BAGeom &g = each[(size_t)i];
-        D.huber = huber[i]; D.min_diag = o->min_lm_diagonal; D.max_diag = o->max_lm_diagonal;
-        D.bs_blocks = G.bs_blocks; D.cost_blocks = G.cost_blocks; D.lin_blocks = G.lin_blocks;
-        D.g_ntiles = g.ntiles; D.g_nupper = g.n_upper; D.g_lmps = g.lm_per_split; D.g_ksplit = g.ksplit;
-        D.skip2 = skip && skip[i] ? 1 : 0;
-        D.flag_h = (int *)(B.h_flag + i);
-        D.ctl = B.d_ctl + i; D.lba_cnt = B.d_cnt + 16 * i;
-        B.h_arr[i] = D;
-        B.h_flag[i] = -1;
-    }
-    OV2_HIP_CHECK(hipMemcpyAsync(B.d_arr, B.h_arr, sizeof(BADev) * (size_t)N, hipMemcpyHostToDevice, s));
-    OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[0], s));
-    BACtl c0;
-    ba_ctl_init(c0, o->initial_radius, nullptr);
-    const BADev *A = B.d_arr;
-    const unsigned Z = (unsigned)N;
-    if (B.lm_live_first) {
-        int ll = 1;
-        for (int i = 0; i < N; i++) ll = std::max(ll, std::min(512, (B.devs[(size_t)i]->D.n_lm + 3) / 4));
-        hipLaunchKernelGGL(k_ba_lm_live_B, dim3(ll, 1, Z), dim3(256), 0, s, A);
-    }
-    hipLaunchKernelGGL(k_ba_reset_B, dim3(G.reset_blocks_B, 1, Z), dim3(256), 0, s, A, c0, keep_state ? 1 : 0);
-    hipLaunchKernelGGL(k_ba_init_B, dim3(G.init_blocks, 1, Z), dim3(256), 0, s, A);
-    auto linearize = [&]() { hipLaunchKernelGGL(k_ba_linearize_B, dim3(G.lin_blocks, 1, Z), dim3(256), G.lin_lds, s, A); };
-    auto first_half = [&](int it) {
-        hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O, it);
-        hipLaunchKernelGGL(k_ba_schur_gemm_B, dim3(G.n_upper, G.ksplit, Z), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(k_ba_assemble_B, dim3((G.nf + 255) / 256, G.nf, Z), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(k_ba_cholesky_B, dim3(1, 1, Z), dim3(512), G.chol_lds, s, A);
-    };
-    auto second_half = [&](int it) {
-        hipLaunchKernelGGL(k_ba_backsub_B, dim3(G.bs_blocks, 1, Z), dim3(256), G.bs_lds, s, A);
-        hipLaunchKernelGGL(k_ba_candidate_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O);
-        hipLaunchKernelGGL(k_ba_cost_B, dim3(G.cost_blocks, 1, Z), dim3(256), 0, s, A);
-        hipLaunchKernelGGL(k_ba_decide_B, dim3(1, 1, Z), dim3(1024), 0, s, A, O, it);
-        linearize();
-    };
-    linearize();
-    rc = ba_lm_loop(s, o, O, B.h_flag, N, first_half, second_half,
-                    [&](const BAOpt &Ob) { hipLaunchKernelGGL(k_ba_iter_begin_B, dim3(1, 1, Z), dim3(1024), 0, s, A, Ob, -1); });
-    if (rc != OV2_OK) return rc;
-    OV2_HIP_CHECK(hipEventRecord(ctx->ba_ev[1], s));
-    OV2_HIP_CHECK(hipMemcpyAsync(B.h_ctl, B.d_ctl, sizeof(BACtl) * (size_t)N, hipMemcpyDeviceToHost, s));
-    OV2_HIP_CHECK(hipStreamSynchronize(s));
-    OV2_HIP_CHECK(hipEventElapsedTime(ms_out, ctx->ba_ev[0], ctx->ba_ev[1]));
-    return OV2_OK;
-}
-
-// ---------------------------------------------------------------------------------- the two-pass localBA protocol (single and batch)
-static void local_ba_clear_result(ov2_local_ba_result &r)
-{
-    r.l2_done = 0; r.pass2_error = OV2_OK; r.n_bad_pass1 = 0; r.n_bad_total = 0; r.status = OV2_OK;
-    for (int q = 0; q < 2; q++) { r.iterations[q] = 0; r.num_successful_steps[q] = 0; r.termination[q] = OV2_TERM_NO_CONVERGENCE; r.initial_cost[q] = r.final_cost[q] = 0; r.solve_ms[q] = 0; }
-}
-
-// the summary of a finished pass (q = 0, 1) into its slot
-static void local_ba_store_pass(ov2_local_ba_result &r, int q, const ov2_ba_result &b)
-{
-    r.iterations[q] = b.iterations; r.num_successful_steps[q] = b.num_successful_steps; r.termination[q] = b.termination;
-    r.initial_cost[q] = b.initial_cost; r.final_cost[q] = b.final_cost; r.solve_ms[q] = b.solve_ms;
-}
-static void local_ba_store_pass(ov2_local_ba_result &r, int q, const BACtl &c, float ms)
-{
-    ov2_ba_result b;
-    ba_fill_result(&b, c, ms);
-    local_ba_store_pass(r, q, b);
-}
-
-// Huber's delta of the first pass (<= 0: trivial loss)
-static double local_ba_huber(const ov2_local_ba_options &o) { return o.use_robust_cost ? sqrt(o.robust_mono_th) : -1.0; }
-
-// The decision after the first outlier test (src/optimizer.cpp:603-608): is there a second pass, and with which loss?  stopLocalBA()
-// is evaluated HERE, after the first solve: a keyframe that arrived while pass 1 ran skips pass 2.  The loss is reset to L2 only
-// when both residual lists are still non-empty (mono runs keep Huber!).
-static bool local_ba_second_pass(const ov2_local_ba_options &o, int n_bad, int left_remaining, int right_remaining, double *huber2)
-{
-    const bool stop = o.stop_requested || (o.stop_flag && *o.stop_flag);
-    *huber2 = (left_remaining && right_remaining) ? -1.0 : local_ba_huber(o);
-    return o.apply_l2_after_robust && o.use_robust_cost && !stop && n_bad > 0;
-}
-
-static bool same_solver_options(const ov2_ba_options &a, const ov2_ba_options &b)
-{
-    return a.max_iter == b.max_iter && a.function_tolerance == b.function_tolerance && a.gradient_tolerance == b.gradient_tolerance &&
-           a.parameter_tolerance == b.parameter_tolerance && a.initial_radius == b.initial_radius && a.max_radius == b.max_radius &&
-           a.min_radius == b.min_radius && a.min_lm_diagonal == b.min_lm_diagonal && a.max_lm_diagonal == b.max_lm_diagonal &&
-           a.min_relative_decrease == b.min_relative_decrease && a.jacobi_scaling == b.jacobi_scaling &&
-           a.max_consecutive_invalid_steps == b.max_consecutive_invalid_steps && a.max_solver_time_s == b.max_solver_time_s;
-}
-
-static int local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r, int *n_batched)
-{
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    for (int i = 0; i < n; i++) {
-        OV2_REQUIRE(o[i].robust_mono_th > 0, OV2_EINVAL, "robust_mono_th must be positive");
-        OV2_REQUIRE(o[i].robust_mono_th == o[0].robust_mono_th && o[i].use_robust_cost == o[0].use_robust_cost && o[i].apply_l2_after_robust == o[0].apply_l2_after_robust &&
-                    same_solver_options(o[i].pass1, o[0].pass1) && same_solver_options(o[i].pass2, o[0].pass2), OV2_EINVAL,
-                    "ov2_local_ba_batch: the problems of a batch share the protocol and solver options (only the stop request is per problem)");
-        local_ba_clear_result(r[i]);
-    }
-    // which problems can share launches: inverse-depth problems of the LDS-resident path with landmarks and optimised keyframes
-    std::vector<int> idx;                                   // batch slot -> problem
-    std::vector<uint8_t> alone((size_t)n, 0);
-    for (int i = 0; i < n; i++) {
-        int n_opt = 0;
-        if (p[i].n_kf > 0 && p[i].kf_const) for (int k = 0; k < p[i].n_kf; k++) n_opt += !p[i].kf_const[k];
-        const bool ok = !ctx->ba_deterministic && !ctx->ba_force_large && p[i].n_lm > 0 && p[i].n_res > 0 && n_opt > 0 && ba_small_path(n_opt);
-        if (ok) idx.push_back(i); else alone[(size_t)i] = 1;
-    }
-    BABatch B;
-    int N = (int)idx.size();
-    const BALap lap{"local_ba_batch", ctx->debug != 0};
-    size_t out_base = 0, out_total = 0;                     // the batch's result block (k_ba_gather_B) inside the header
-    std::vector<size_t> out_off;
-    if (N > 0) {
-        // header of the pinned block: look-ahead words, counters, control blocks, device views; then the staging mirrors
-        const size_t hb_flag = 0, hb_cnt = up256(4 * (size_t)N), hb_ctl = hb_cnt + up256(64 * (size_t)N), hb_arr = hb_ctl + up256(sizeof(BACtl) * (size_t)N);
-        out_base = hb_arr + up256(sizeof(BADev) * (size_t)N);
-        out_off.assign(idx.size(), 0);
-        for (size_t k = 0; k < idx.size(); k++) {
-            const ov2_ba_problem &q = p[idx[k]];
-            const size_t nk = (size_t)std::max(0, q.n_kf), nl = (size_t)std::max(1, q.n_lm), nr = (size_t)std::max(0, q.n_res);
-            out_off[k] = out_total;
-            out_total += up256(56 * nk) + up256(8 * nl) + up256(nr) + (r[idx[k]].chi2_last_eval ? up256(8 * nr) : 0) + (r[idx[k]].depthpos_last_eval ? up256(nr) : 0);
-        }
-        const size_t header = out_base + up256(out_total);          // (look-ahead words | counters | control blocks | views | results), then the problems' slices
-        size_t host_need = header, dev_need = header;
-        for (;;) {
-            int rc = ctx->reserve_host(std::max(host_need, ctx->h_scratch_bytes));
-            if (rc == OV2_OK) rc = ctx->reserve_device(std::max(dev_need, ctx->d_scratch_bytes));
-            if (rc != OV2_OK) return rc;
-            uint8_t *hb = (uint8_t *)ctx->h_scratch, *db = (uint8_t *)ctx->d_scratch;
-            B.h_flag = (volatile int *)(hb + hb_flag); B.h_cnt = (int *)(hb + hb_cnt); B.h_ctl = (BACtl *)(hb + hb_ctl); B.h_arr = (BADev *)(hb + hb_arr);
-            B.d_cnt = (int *)(db + hb_cnt); B.d_ctl = (BACtl *)(db + hb_ctl); B.d_arr = (BADev *)(db + hb_arr);
-            BASlice sl;
-            sl.dev_base = db; sl.dev_cap = ctx->d_scratch_bytes; sl.dev_used = header; sl.host_base = hb; sl.host_cap = ctx->h_scratch_bytes; sl.host_used = header;
-            // the host side of a problem (validation, the landmark sort, the staging mirror; ~0.4 ms for a 69 k-block window) on a thread of
-            // its own (sixteen persistent threads of the context) -- on one thread it was more than the batch's device time.  Each thread enqueues its
-            // problem's upload on the context's stream itself (the order of the uploads does not matter).
-            std::vector<ov2_ba_dev *> made(idx.size(), nullptr);
-            std::vector<int> rcs(idx.size(), OV2_OK);
-            std::vector<std::string> errs(idx.size());
-            BAHostPool *hp = idx.size() > 1 ? ba_host_pool_of(ctx) : nullptr;
-            const std::function<void(int)> work = [&](int k) {
-                (void)hipSetDevice(ctx->device);
-                rcs[(size_t)k] = ba_create(ctx, &p[idx[(size_t)k]], &made[(size_t)k], true, &sl);
-                if (rcs[(size_t)k] != OV2_OK && rcs[(size_t)k] != BA_SLICE_FULL) errs[(size_t)k] = ov2_last_error();          // (the message is per thread)
-            };
-            if (hp) hp->run((int)idx.size(), work);
-            else for (size_t k = 0; k < idx.size(); k++) work((int)k);
-            bool full = false;
-            int bad_rc = OV2_OK; size_t bad_k = 0;
-            for (size_t k = 0; k < idx.size(); k++) {
-                if (rcs[k] == BA_SLICE_FULL) full = true;
-                else if (rcs[k] != OV2_OK && bad_rc == OV2_OK) { bad_rc = rcs[k]; bad_k = k; }
-            }
-            if (bad_rc == OV2_OK && !full) {
-                for (size_t k = 0; k < idx.size(); k++) {
-                    made[k]->D.out_b = db + out_base + out_off[k];
-                    made[k]->D.out_flags = (r[idx[k]].chi2_last_eval ? 1 : 0) | (r[idx[k]].depthpos_last_eval ? 2 : 0);
-                }
-                B.devs = made;
-                break;
-            }
-            OV2_HIP_CHECK(hipStreamSynchronize(s));
-            for (ov2_ba_dev *d : made) ba_destroy(d);
-            if (bad_rc != OV2_OK) { ov2_set_error("ov2_local_ba_batch: problem %d: %s", idx[bad_k], errs[bad_k].c_str()); return bad_rc; }
-            // grow-only blocks: twice what this batch would have taken, and start over (the first batches of a run only)
-            host_need = 2 * sl.host_used; dev_need = 2 * sl.dev_used;
-        }
-        // problems that turn out to carry pose-only blocks leave the batch
-        for (size_t k = 0; k < B.devs.size();) {
-            if (B.devs[k]->D.n_po > 0 || B.devs[k]->D.big) { alone[(size_t)idx[k]] = 1; OV2_HIP_CHECK(hipStreamSynchronize(s)); ba_destroy(B.devs[k]); B.devs.erase(B.devs.begin() + (long)k); idx.erase(idx.begin() + (long)k); out_off.erase(out_off.begin() + (long)k); }
-            else k++;
-        }
-        N = (int)idx.size();
-    }
-    if (n_batched) *n_batched = N;
-    lap("sort + upload (ba_create)");
-    if (N > 0) {
-        const ov2_local_ba_options &o0 = o[0];
-        std::vector<double> huber((size_t)N, local_ba_huber(o0));
-        std::vector<uint8_t> skip((size_t)N, 0);
-        OV2_HIP_CHECK(hipMemsetAsync(B.d_cnt, 0, 64 * (size_t)N, s));
-        ov2_ba_options o1 = o0.pass1;
-        float ms = 0;
-        int rc = ba_run_batch(ctx, B, &o1, huber.data(), nullptr, false, &ms);
-        if (rc != OV2_OK) return rc;
-        lap("pass 1");
-        for (int k = 0; k < N; k++) local_ba_store_pass(r[idx[(size_t)k]], 0, B.h_ctl[k], ms);
-        int mk_blocks = 1;
-        for (int k = 0; k < N; k++) mk_blocks = std::max(mk_blocks, std::min(1024, (B.devs[(size_t)k]->D.n_act + 255) / 256));
-        hipLaunchKernelGGL(k_ba_mark_outliers_B, dim3(mk_blocks, 1, (unsigned)N), dim3(256), 0, s, (const BADev *)B.d_arr, o0.robust_mono_th, o0.apply_l2_after_robust ? 1 : 0, (uint8_t *)nullptr);
-        OV2_HIP_CHECK(hipGetLastError());
-        OV2_HIP_CHECK(hipMemcpyAsync(B.h_cnt, B.d_cnt, 64 * (size_t)N, hipMemcpyDeviceToHost, s));
-        for (int k = 0; k < N; k++) {
-            ov2_local_ba_result &ri = r[idx[(size_t)k]];
-            const ov2_ba_dev *dev = B.devs[(size_t)k];
-            if (ri.bad_after_pass1 && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(ri.bad_after_pass1, dev->D.bad_obs, (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
-        }
-        OV2_HIP_CHECK(hipStreamSynchronize(s));
-        lap("outlier test 1");
-        // (only the stop request is per problem: the other options are the batch's)
-        int n_pass2 = 0;
-        std::vector<int> bad1((size_t)N, 0);
-        for (int k = 0; k < N; k++) {
-            ov2_local_ba_result &ri = r[idx[(size_t)k]];
-            const int nbbad = B.h_cnt[16 * k];
-            bad1[(size_t)k] = nbbad; ri.n_bad_pass1 = nbbad; ri.n_bad_total = nbbad;
-            const bool go = local_ba_second_pass(o[idx[(size_t)k]], nbbad, B.h_cnt[16 * k + 1], B.h_cnt[16 * k + 2], &huber[(size_t)k]);
-            skip[(size_t)k] = go ? 0 : 1;
-            n_pass2 += go;
-        }
-        if (n_pass2 > 0) {
-            // (skip2 reaches the device with ba_run_batch's upload of the views: k_ba_lm_live_B runs after it, as part of the reset)
-            OV2_HIP_CHECK(hipMemsetAsync(B.d_cnt, 0, 64 * (size_t)N, s));
-            ov2_ba_options o2 = o0.pass2;
-            B.lm_live_first = true;
-            rc = ba_run_batch(ctx, B, &o2, huber.data(), skip.data(), true, &ms);
-            B.lm_live_first = false;
-            lap("pass 2");
-            if (rc != OV2_OK) {
-                for (int k = 0; k < N; k++) if (!skip[(size_t)k]) r[idx[(size_t)k]].pass2_error = rc;
-            } else {
-                for (int k = 0; k < N; k++) {
-                    if (skip[(size_t)k]) continue;
-                    r[idx[(size_t)k]].l2_done = 1;
-                    local_ba_store_pass(r[idx[(size_t)k]], 1, B.h_ctl[k], ms);
-                }
-                hipLaunchKernelGGL(k_ba_mark_outliers_B, dim3(mk_blocks, 1, (unsigned)N), dim3(256), 0, s, (const BADev *)B.d_arr, o0.robust_mono_th, 0, (uint8_t *)nullptr);
-                OV2_HIP_CHECK(hipGetLastError());
-                OV2_HIP_CHECK(hipMemcpyAsync(B.h_cnt, B.d_cnt, 64 * (size_t)N, hipMemcpyDeviceToHost, s));
-            }
-        }
-        {
-            int gb = 1;
-            for (int k = 0; k < N; k++) gb = std::max(gb, std::min(64, (std::max(B.devs[(size_t)k]->D.n_res, B.devs[(size_t)k]->D.n_lm) + 1023) / 1024));
-            hipLaunchKernelGGL(k_ba_gather_B, dim3(gb, 1, (unsigned)N), dim3(256), 0, s, (const BADev *)B.d_arr);
-            OV2_HIP_CHECK(hipGetLastError());
-            uint8_t *hb = (uint8_t *)ctx->h_scratch, *db = (uint8_t *)ctx->d_scratch;
-            OV2_HIP_CHECK(hipMemcpyAsync(hb + out_base, db + out_base, out_total, hipMemcpyDeviceToHost, s));
-            OV2_HIP_CHECK(hipStreamSynchronize(s));
-            for (int k = 0; k < N; k++) {
-                ov2_local_ba_result &ri = r[idx[(size_t)k]];
-                const BADev &D = B.devs[(size_t)k]->D;
-                const uint8_t *o = hb + out_base + out_off[(size_t)k];
-                const size_t nr = (size_t)D.n_res;
-                if (ri.poses_out) memcpy(ri.poses_out, o, 56 * (size_t)D.n_kf);
-                o += up256(56 * (size_t)D.n_kf);
-                if (ri.invdepth_out) memcpy(ri.invdepth_out, o, 8 * (size_t)D.n_lm);
-                o += up256(8 * (size_t)std::max(1, D.n_lm));
-                if (ri.bad_obs && nr > 0) memcpy(ri.bad_obs, o, nr);
-                o += up256(nr);
-                if (ri.chi2_last_eval) { if (nr > 0) memcpy(ri.chi2_last_eval, o, 8 * nr); o += up256(8 * nr); }
-                if (ri.depthpos_last_eval && nr > 0) memcpy(ri.depthpos_last_eval, o, nr);
-            }
-        }
-        lap("outlier test 2 + download");
-        for (int k = 0; k < N; k++) if (r[idx[(size_t)k]].l2_done) r[idx[(size_t)k]].n_bad_total = bad1[(size_t)k] + B.h_cnt[16 * k];
-        for (ov2_ba_dev *d : B.devs) ba_destroy(d);
-        B.devs.clear();
-    }
-    // what cannot share launches (large windows, pose-only blocks, the deterministic mode): one problem at a time
-    // every one of them is attempted: r[i].status says which results are valid, the call returns the first failure
-    int first_err = OV2_OK;
-    for (int i = 0; i < n; i++) {
-        if (!alone[(size_t)i]) continue;
-        const int rc = ov2_local_ba(ctx, &p[i], &o[i], &r[i]);
-        r[i].status = rc;
-        if (rc != OV2_OK && first_err == OV2_OK) first_err = rc;
-    }
-    return first_err;
-}
+#include "ba_local.hpp"         // the two-pass localBA protocol: one problem (local_ba_one), a lock-step batch (local_ba_batch)
 
 extern "C" {
 
@@ -2381,76 +2052,12 @@ void ov2_local_ba_default_options(ov2_local_ba_options *o)
     o->pass2.max_iter = 10;                                  // :611
 }
 
-// Optimizer::localBA's solve stage (src/optimizer.cpp:436-735) with the problem RESIDENT between the two passes: one
-// counting sort + one upload, the outlier tests and the removal of residual blocks on the device, one download.
-static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r);
 int ov2_local_ba(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r)
 {
     OV2_REQUIRE(ctx && p && o && r, OV2_EINVAL, "NULL argument");
     const int rc = local_ba_one(ctx, p, o, r);
     r->status = rc;
     return rc;
-}
-static int local_ba_one(ov2_ctx *ctx, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r)
-{
-    OV2_REQUIRE(o->robust_mono_th > 0, OV2_EINVAL, "robust_mono_th must be positive");
-    local_ba_clear_result(*r);
-    ov2_ba_dev *dev = nullptr;
-    const BALap lap{"local_ba", ctx->debug != 0};
-    int rc = ba_create(ctx, p, &dev, /*transient*/ true);       // the pool lives in the context's scratch through both passes
-    if (rc != OV2_OK) return rc;
-    lap("sort + upload (ba_create)");
-    struct Guard { ov2_ba_dev *d; ~Guard() { ba_destroy(d); } } guard{dev};
-    if (dev->D.n_po > 0) { ov2_set_error("ov2_local_ba: problems with OV2_RES_PNP blocks go through ov2_ba_solve"); return OV2_EUNSUPPORTED; }
-    BADev &D = dev->D;
-    hipStream_t s = ctx->stream;
-    // pass 1 (:436-485)
-    ov2_ba_options o1 = o->pass1, o2 = o->pass2;
-    o1.huber_delta = local_ba_huber(*o);
-    ov2_ba_result br;
-    memset(&br, 0, sizeof(br));
-    rc = ba_run(ctx, dev, &o1, &br, nullptr, nullptr);
-    if (rc != OV2_OK) return rc;
-    local_ba_store_pass(*r, 0, br);
-    lap("pass 1");
-    // outlier test on the values cached by the last Evaluate of pass 1 (:492-594)
-    rc = ctx->reserve_host(64);
-    if (rc != OV2_OK) return rc;
-    int *cnt_h = (int *)ctx->h_scratch;
-    const int mk_blocks = std::max(1, std::min(1024, (D.n_act + 255) / 256));
-    hipLaunchKernelGGL(k_ba_mark_outliers, dim3(mk_blocks), dim3(256), 0, s, D, o->robust_mono_th, o->apply_l2_after_robust ? 1 : 0, (uint8_t *)nullptr);
-    OV2_HIP_CHECK(hipGetLastError());
-    OV2_HIP_CHECK(hipMemcpyAsync(cnt_h, D.lba_cnt, 16, hipMemcpyDeviceToHost, s));
-    if (r->bad_after_pass1 && dev->n_res > 0) OV2_HIP_CHECK(hipMemcpyAsync(r->bad_after_pass1, D.bad_obs, (size_t)dev->n_res, hipMemcpyDeviceToHost, s));
-    OV2_HIP_CHECK(hipStreamSynchronize(s));
-    lap("outlier test 1");
-    const int nbbad = cnt_h[0];
-    r->n_bad_pass1 = nbbad; r->n_bad_total = nbbad;
-    if (local_ba_second_pass(*o, nbbad, cnt_h[1], cnt_h[2], &o2.huber_delta)) {
-        hipLaunchKernelGGL(k_ba_lm_live, dim3(std::max(1, std::min(512, (D.n_lm + 3) / 4))), dim3(256), 0, s, D);
-        OV2_HIP_CHECK(hipMemsetAsync(D.lba_cnt, 0, 16, s));
-        rc = ba_run(ctx, dev, &o2, &br, nullptr, nullptr, /*keep_state*/ true);
-        if (rc != OV2_OK) {
-            // pass 2 could not run: the device still holds an accepted state (pass 1's, or a later accepted LM step) and the
-            // verdicts of the first test -- hand those back instead of dropping a valid solve
-            r->pass2_error = rc;
-            goto download;
-        }
-        r->l2_done = 1;
-        local_ba_store_pass(*r, 1, br);
-        lap("pass 2");
-        // second outlier test on the residual blocks that are still in the problem (:637-735)
-        hipLaunchKernelGGL(k_ba_mark_outliers, dim3(mk_blocks), dim3(256), 0, s, D, o->robust_mono_th, 0, (uint8_t *)nullptr);
-        OV2_HIP_CHECK(hipGetLastError());
-        OV2_HIP_CHECK(hipMemcpyAsync(cnt_h, D.lba_cnt, 16, hipMemcpyDeviceToHost, s));
-    }
-download:
-    rc = ba_download(s, dev, r->poses_out, r->invdepth_out, r->bad_obs, r->chi2_last_eval, r->depthpos_last_eval);
-    if (rc != OV2_OK) return rc;
-    OV2_HIP_CHECK(hipStreamSynchronize(s));
-    if (r->l2_done) r->n_bad_total = nbbad + cnt_h[0];
-    lap("outlier test 2 + download");
-    return OV2_OK;
 }
 
 int ov2_local_ba_batch(ov2_ctx *ctx, int n, const ov2_ba_problem *p, const ov2_local_ba_options *o, ov2_local_ba_result *r, int *n_batched)

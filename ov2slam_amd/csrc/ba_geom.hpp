@@ -1,10 +1,17 @@
 // ba_geom.hpp -- the ONE place that knows the sizes of the device bundle adjustment: tile and panel constants, the dynamic-LDS
 // byte count of every kernel that carves up dynamic LDS, which path a problem takes, and the grids of the LM loop's launches.
 // Plain C++ (no HIP types, no context): ba.hip includes it ahead of the kernels, tests/cpp/ba_geom_check.cpp builds it alone.
-// A kernel whose LDS layout changes changes its function here, and nothing else on the host.
+// A kernel whose LDS layout changes changes its function here, and nothing else on the host.  The two blocks of a lock-step batch
+// (header, results) are laid out here as well: k_ba_gather_B writes the result block by the function the host reads it by.
 #pragma once
 #include <stddef.h>
 #include <algorithm>
+
+#if defined(__HIPCC__)
+#define BA_HD __host__ __device__
+#else
+#define BA_HD
+#endif
 
 #define BA_TILE 32
 #define BA_MAX_NFP 6144     // 1024 optimised keyframes: H, G, S are dense nfp x nfp doubles (302 MB each at the cap)
@@ -123,4 +130,33 @@ static inline void ba_geom_max(BAGeom &a, const BAGeom &b)
     size_t BAGeom::*const gs[] = {&BAGeom::lin_lds, &BAGeom::po_lds, &BAGeom::ss_lds, &BAGeom::chol_lds, &BAGeom::bs_lds};
     for (auto f : gi) a.*f = std::max(a.*f, b.*f);
     for (auto f : gs) a.*f = std::max(a.*f, b.*f);
+}
+
+// ---------------------------------------------------------------------------------- the blocks of a lock-step batch (ba_local.hpp)
+static inline BA_HD size_t ba_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// one problem's slot of the batch's result block: poses | inverse depths | outlier verdicts [| chi2] [| depth flags], offsets in
+// bytes, 256-byte parts (a problem without landmarks keeps one part of inverse depths); out_flags 1: + chi2, 2: + depth flags --
+// a part that is not there is empty, so its offset is the next part's
+struct BAOutLayout { size_t poses, invdepth, bad_obs, chi2, dpos, total; };
+static inline BA_HD BAOutLayout ba_out_layout(int n_kf, int n_lm, int n_res, int out_flags)
+{
+    const size_t nk = (size_t)(n_kf > 0 ? n_kf : 0), nl = (size_t)(n_lm > 1 ? n_lm : 1), nr = (size_t)(n_res > 0 ? n_res : 0);
+    BAOutLayout L;
+    L.poses = 0; L.invdepth = ba_up256(56 * nk); L.bad_obs = L.invdepth + ba_up256(8 * nl); L.chi2 = L.bad_obs + ba_up256(nr);
+    L.dpos = L.chi2 + ((out_flags & 1) ? ba_up256(8 * nr) : 0);
+    L.total = L.dpos + ((out_flags & 2) ? ba_up256(nr) : 0);
+    return L;
+}
+
+// head of the batch's pinned block and of its device mirror, N problems: look-ahead words (one int each) | 16 int counters each |
+// control blocks | device views; the result block starts at out_base, the problems' slices follow it
+struct BABatchHeader { size_t flag, cnt, ctl, arr, out_base; };
+static inline BABatchHeader ba_batch_header(int N, size_t sizeof_ctl, size_t sizeof_dev)
+{
+    const size_t n = (size_t)N;
+    BABatchHeader h;
+    h.flag = 0; h.cnt = ba_up256(4 * n); h.ctl = h.cnt + ba_up256(64 * n); h.arr = h.ctl + ba_up256(sizeof_ctl * n);
+    h.out_base = h.arr + ba_up256(sizeof_dev * n);
+    return h;
 }

@@ -1,5 +1,6 @@
 // ba_geom_check.cpp -- host-only check of ov2slam_amd/csrc/ba_geom.hpp (tests/test_ba_geom.py builds it with g++ against that header
-// alone): every size the BA host driver hands to a launch, for n_opt = 1 .. 1024.  Prints "FAIL ..." per violated property and the
+// alone): every size the BA host driver hands to a launch, for n_opt = 1 .. 1024, and the layout of a lock-step batch's header
+// and result block.  Prints "FAIL ..." per violated property and the
 // figures the test compares; exit status 1 when anything failed.
 #include "ba_geom.hpp"
 #include <stdio.h>
@@ -32,8 +33,50 @@ static void check_geom(const Sizes &D, const BAGeom &g, int rows)
     CHECK(g.bs_blocks <= 2048 && g.cost_blocks <= 2048, "more partial sums than BA_PART_MAX holds: %d %d", g.bs_blocks, g.cost_blocks);
 }
 
+// the layout of a lock-step batch's blocks against a restatement written out here: the parts in order, each a whole number of
+// 256-byte units that holds its array
+static size_t units(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+static void check_part(const char *what, size_t off, size_t next, size_t bytes, size_t want_off)
+{
+    CHECK(off == want_off, "%s at %zu, expected %zu", what, off, want_off);
+    CHECK(off % 256 == 0 && off + bytes <= next, "%s: %zu bytes at %zu, the next part at %zu", what, bytes, off, next);
+}
+
+static void check_out_layout(int n_kf, int n_lm, int n_res, int flags)
+{
+    const BAOutLayout L = ba_out_layout(n_kf, n_lm, n_res, flags);
+    const size_t nk = (size_t)n_kf, nl = (size_t)n_lm, nr = (size_t)n_res;
+    const size_t b_pose = units(56 * nk), b_lam = n_lm == 0 ? 256 : units(8 * nl), b_bad = units(nr);
+    const size_t b_chi2 = (flags & 1) ? units(8 * nr) : 0, b_dpos = (flags & 2) ? units(nr) : 0;
+    check_part("poses", L.poses, L.invdepth, 56 * nk, 0);
+    check_part("invdepth", L.invdepth, L.bad_obs, 8 * nl, b_pose);
+    check_part("bad_obs", L.bad_obs, L.chi2, nr, b_pose + b_lam);
+    check_part("chi2", L.chi2, L.dpos, (flags & 1) ? 8 * nr : 0, b_pose + b_lam + b_bad);
+    check_part("dpos", L.dpos, L.total, (flags & 2) ? nr : 0, b_pose + b_lam + b_bad + b_chi2);
+    CHECK(L.total == b_pose + b_lam + b_bad + b_chi2 + b_dpos, "total %zu (%d %d %d flags %d)", L.total, n_kf, n_lm, n_res, flags);
+    // the optional parts exist exactly with their flags
+    CHECK((L.dpos - L.chi2 > 0) == ((flags & 1) && n_res > 0) && (L.total - L.dpos > 0) == ((flags & 2) && n_res > 0),
+          "optional parts %zu %zu with flags %d (n_res %d)", L.dpos - L.chi2, L.total - L.dpos, flags, n_res);
+}
+
+static void check_batch_header(int N, size_t sizeof_ctl, size_t sizeof_dev)
+{
+    const BABatchHeader H = ba_batch_header(N, sizeof_ctl, sizeof_dev);
+    const size_t n = (size_t)N;
+    check_part("look-ahead words", H.flag, H.cnt, 4 * n, 0);
+    check_part("counters", H.cnt, H.ctl, 16 * 4 * n, units(4 * n));
+    check_part("control blocks", H.ctl, H.arr, sizeof_ctl * n, units(4 * n) + units(64 * n));
+    check_part("device views", H.arr, H.out_base, sizeof_dev * n, units(4 * n) + units(64 * n) + units(sizeof_ctl * n));
+    CHECK(H.out_base == units(4 * n) + units(64 * n) + units(sizeof_ctl * n) + units(sizeof_dev * n), "out_base %zu (N %d)", H.out_base, N);
+}
+
 int main()
 {
+    static const int out_cases[][3] = {{1, 0, 0}, {1, 1, 1}, {6, 40, 160}, {25, 3000, 69000}};
+    for (auto &c : out_cases) for (int flags = 0; flags < 4; flags++) check_out_layout(c[0], c[1], c[2], flags);
+    for (int N : {1, 11, 4096}) { check_batch_header(N, 200, 1000); check_batch_header(N, 256, 1024); check_batch_header(N, 8, 4); }
+    printf("out_total_25kf_flags3 %zu\n", ba_out_layout(25, 3000, 69000, 3).total);
     int last_small = 0, first_direct = 0, last_w[5] = {0, 0, 0, 0, 0};
     for (int n = 1; n <= 1024; n++) {
         const int nf = 6 * n, nfp = ba_nfp(n);

@@ -132,3 +132,42 @@ def test_batch_reports_a_status_per_problem(gpu_ctx):
     assert [r["status"] for r in res] == [L.OV2_OK, L.OV2_EUNSUPPORTED, L.OV2_OK]
     _same(res[0], ov2slam_amd.Optimizer(gpu_ctx).localBA(small))
     _same(res[2], ov2slam_amd.Optimizer(gpu_ctx).localBA(large), tight=1e-6)
+
+
+def test_batch_status_of_the_shared_part(gpu_ctx):
+    """include/ov2slam_hip.h ov2_local_ba_result::status on the shared-launch path: a problem that ba_create rejects (a residual block
+    that names landmark 10^6) gets its own code and leaves the batch, the others still share launches; the problems that run alone
+    (70 optimised keyframes; OV2_RES_PNP blocks) are still attempted; the buffers of a failed problem keep what the caller put there
+    (localBA_batch allocates zeros, NaN for chi2); the call returns the first failure in problem order."""
+    import ctypes as C
+    from ov2slam_amd import _lib as L
+    from ov2slam_amd.optimizer import pack_problem
+    a = synth.make_ba_problem(6, 40, 4, stereo=False, seed=1)
+    b = synth.make_ba_problem(12, 400, 8, stereo=True, seed=3)
+    bad = dict(b); bad["res_lm"] = b["res_lm"].copy(); bad["res_lm"][0] = 10**6
+    big = synth.make_ba_problem(71, 600, 6, stereo=True, seed=5)
+    pnp = synth.make_pnp_problem(100, seed=2)
+    pbs = [a, bad, big, b, pnp]
+    res, nb = ov2slam_amd.Optimizer(gpu_ctx).localBA_batch(pbs, raise_on_error=False)
+    assert [r["status"] for r in res] == [L.OV2_OK, L.OV2_EINVAL, L.OV2_OK, L.OV2_OK, L.OV2_EUNSUPPORTED]
+    assert nb == 2
+    _same(res[0], ov2slam_amd.Optimizer(gpu_ctx).localBA(a))
+    _same(res[3], ov2slam_amd.Optimizer(gpu_ctx).localBA(b))
+    _same(res[2], ov2slam_amd.Optimizer(gpu_ctx).localBA(big), tight=1e-6)
+    for i in (1, 4):
+        assert not res[i]["poses"].any() and not res[i]["invdepth"].any() and not res[i]["bad_obs"].any() and not res[i]["bad_after_pass1"].any()
+        assert np.isnan(res[i]["chi2"]).all() and not res[i]["depthpos"].any()
+    with pytest.raises(ov2slam_amd.Ov2Error):
+        ov2slam_amd.Optimizer(gpu_ctx).localBA_batch(pbs)
+    # problems that disagree on use_robust_cost: an error of the batch as a whole, every status says so
+    lib = gpu_ctx.lib
+    PA = (L.BAProblem * 2)(); OA = (L.LocalBAOptions * 2)(); RA = (L.LocalBAResult * 2)()
+    keep = [pack_problem(a), pack_problem(b)]
+    for i in range(2):
+        PA[i] = keep[i][0]
+        lib.ov2_local_ba_default_options(C.byref(OA[i]))
+        RA[i].status = 77
+    OA[1].use_robust_cost = 0
+    nbc = C.c_int(-1)
+    assert lib.ov2_local_ba_batch(gpu_ctx.h, 2, PA, OA, RA, C.byref(nbc)) == L.OV2_EINVAL
+    assert [RA[i].status for i in range(2)] == [L.OV2_EINVAL, L.OV2_EINVAL] and nbc.value == 0
