@@ -2384,6 +2384,97 @@ int  ov2_btracker_track_mono_resident(ov2_btracker *t, int n_active, const uint8
                                       ov2_track_mono_result *mono_results, ov2_resident_step_result *frame_results);
 int  ov2_btracker_last_slot_bytes(const ov2_btracker *t, size_t *h2d);
 
+/* The mapper's STEREO block on the resident keyframe (f22): what Mapper::run executes on every new stereo keyframe
+ * (src/mapper.cpp:69-105) -- MapManager::stereoMatching (src/map_manager.cpp:367-611), then Mapper::triangulateStereo
+ * (src/mapper.cpp:346-461) -- for the items ov2_btracker_create_keyframe just turned into keyframes, in ONE enqueue on the context's
+ * stream and ONE synchronisation, byte-equal to the route of separate calls (ov2_btracker_get_frame, ov2_compute_keypoints,
+ * ov2_stereo_priors_batch, ov2_stereo_match_batch, ov2_compute_keypoints of the right camera, ov2_triangulate_keyframe_batch,
+ * ov2_btracker_update_frame_batch, ov2_btracker_set_keyframe_info).  Per item b of [0, n_active) with do_h[b] != 0 whose resident
+ * frame is its resident keyframe, in the reference's order (csrc/stereokf.hip between the existing kernels):
+ *   input      k_skf_input: from the resident frame px, lmid, is3d, wpt and n, from the resident keyframe header its Twc and Tcw as
+ *              k_ckf_install wrote them.  state = is3d: state 2 (a 3-D keypoint whose map point is gone, :415-418) CANNOT OCCUR
+ *              here -- the caller removes such observations with ov2_btracker_update_frame first.  unpx / bv of every slot by the
+ *              left camera of ov2_btracker_set_calibration (the bits of ov2_compute_keypoints), the keypoint on the coarsest
+ *              level, the per-item descriptors of the kernels behind (0 for an item that is not OV2_SKF_DONE).  With rect == 0
+ *              the keypoint grid of Frame::getSurroundingKeypoints: ceil(img_w / ncellsize) x ceil(img_h / ncellsize) cells, a
+ *              keypoint in cell (floorf(px.y / cellsize), floorf(px.x / cellsize)) as k_prior_stereo computes it, a keypoint
+ *              outside the grid in none.  KEYPOINTS INSIDE A CELL STAND IN SLOT ORDER.  The reference's order is vgridkps_
+ *              insertion order, which depends on the frame's history and is not carried by the resident frame: the one
+ *              deviation.  It changes only the summation order of the neighbour-depth prior, a starting point for LK.
+ *   priors     k_prior_stereo (ov2_stereo_priors), then k_skf_seed: prior = has_prior ? prior : px, flag = has_prior != 0
+ *   matching   k_line_min_sad on level nklt_pyr_lvl (rect) or "nothing found", k_track_klt from the tracker's current pyramid into
+ *              `right`, k_epipolar_check with the right camera: the grids and arguments of ov2_stereo_match_batch
+ *   keypoints  k_skf_stereo_kp: stereo_ok = tracked && gate; right_px as ov2_stereo_match_batch returns it ((0, 0) where the
+ *              tracking failed, the corrected row for rect); for stereo_ok slots runpx / rbv by the right camera's computeKeypoint
+ *              on right_px (Frame::computeStereoKeypoint, frame.cpp:405-420); is_stereo = stereo_ok && !is3d (mapper.cpp:383)
+ *   triangulation   k_triangulate with src = -1 everywhere: the stereo pass alone.  Mapper::triangulateTemporal needs the map's
+ *              source keyframes and is OUT OF SCOPE, as are updateMapPoint's other effects and removeStereoKeypointById's
+ *              bookkeeping: the statuses returned are what a caller needs to replay them.
+ *   apply      k_skf_apply: every OV2_TRI_STEREO_OK slot gets is3d = 1 and wpt = the triangulated point, written into the item's
+ *              OTHER frame buffer (_end flips it: a call begun and never ended leaves the frame as it was); kf_nb3dkps of the
+ *              resident keyframe info becomes the number of is3d slots after the call (updateMapPoint -> turnKeypoint3d on the
+ *              keyframe's nb3dkps_, which checkNewKfReq reads).  _end brings the host mirrors of the frame and of the info to the
+ *              same state from the statuses and points that come down anyway.
+ * `right`: a batch pyramid of the right images built by the caller on the tracker's context (ov2_pyr_build_clahe_hb / ov2_pyr_build_h,
+ * as for ov2_stereo_match_batch), at least n_active items, of the tracker's size, window and level count; it may still be building
+ * on that stream.  The tracker owns no right pyramid.  The left camera is that of ov2_btracker_set_calibration.
+ * results[b].action:
+ *   OV2_SKF_NOT_REQUESTED   do_h[b] == 0: nothing of the item is read or written, its work-groups leave at once
+ *   OV2_SKF_NOT_KEYFRAME    the item's resident frame is not its resident keyframe: nothing is written.  The tracker keeps one
+ *                           host byte per item: set by the _end of a resident ov2_btracker_create_keyframe whose action was
+ *                           OV2_CKF_CREATED; cleared by ov2_btracker_set_frame, ov2_btracker_set_keyframe, any resident step's _end
+ *                           that flipped the item, and an ov2_btracker_update_frame that removed a slot
+ *   OV2_SKF_DONE            the record and, in the slot space of the resident frame (cfg.n_max slots per item, [0, n) written),
+ *                           right_px_h (2 float), stereo_ok_h, tri_status_h (OV2_TRI_* bits), wpt_h (3 double), invdepth_h
+ * ov2_btracker_last_slot_bytes reports 0 after this call.  ov2_btracker_get_keyframe_info returns the resident keyframe info of
+ * an item (from_device != 0: copied down, one synchronisation; else the host mirror); any output pointer may be NULL.
+ * OV2_EINVAL, checked on the host before anything is enqueued (the tracker stays where it was): a NULL tracker / params / right /
+ * do_h; n_active outside [1, batch]; `right` with fewer items than n_active or another size, window or level count than the
+ * tracker's pyramid; an open step, create_keyframe call or call of this kind; no calibration; no resident block; cfg.n_max >
+ * OV2_FKF_MAX_POINTS; rect == 0 with ncellsize <= 0 or more than OV2_FKF_MAX_CELLS cells; params->tri.stereo == 0; a non-finite
+ * pose in Tcic0 / tri.Tcic0 / tri.Tlr; the camera checks of ov2_stereo_priors (OV2_EUNSUPPORTED where it says so).  _end: no open
+ * call, a NULL result or output array.  Between _begin and _end the calls that change resident state or start a step return
+ * OV2_EINVAL. */
+#define OV2_SKF_NOT_REQUESTED 0
+#define OV2_SKF_NOT_KEYFRAME  1
+#define OV2_SKF_DONE          2
+typedef struct {
+    int nklt_win_size;                /* ov2_stereo_match_batch: nklt_win_size_                                              */
+    int nklt_pyr_lvl;                 /* ov2_stereo_match_batch: nklt_pyr_lvl_                                               */
+    int max_iter;                     /* ov2_stereo_match_batch: nmax_iter_                                                  */
+    float eps;                        /* ov2_stereo_match_batch: fmax_px_precision_                                          */
+    float nklt_err;                   /* ov2_stereo_match_batch: nklt_err_                                                   */
+    float fmax_fbklt_dist;            /* ov2_stereo_match_batch: fmax_fbklt_dist_                                            */
+    int rect;                         /* ov2_stereo_priors_params.rect / ov2_stereo_match_batch: bdo_stereo_rect_            */
+    double Frl[9];                    /* ov2_stereo_match_batch: the fundamental matrix of the gate (read when rect == 0)    */
+    int model;                        /* ov2_stereo_priors_params / ov2_compute_keypoints: the RIGHT camera's model          */
+    double K[4];                      /* ov2_stereo_priors_params / ov2_compute_keypoints: right fx fy cx cy                 */
+    const double *D;                  /* ov2_stereo_priors_params / ov2_compute_keypoints: right distortion vector, or NULL  */
+    int nD;                           /* ov2_stereo_priors_params / ov2_compute_keypoints: its length (0: none)              */
+    double iK[9];                     /* ov2_compute_keypoints of the right camera: its iK_, row-major                       */
+    double img_w, img_h;              /* ov2_stereo_priors_params: pcalib_rightcam_->img_w_ / img_h_, the size behind the grid */
+    double Tcic0[7];                  /* ov2_stereo_priors_params: pcalib_rightcam_->Tcic0_                                  */
+    int ncellsize;                    /* ov2_stereo_priors_params: Frame::ncellsize_ (read when rect == 0)                   */
+    ov2_tri_params tri;               /* ov2_triangulate_keyframe_batch: its params, as they are (tri.stereo must be set)    */
+} ov2_stereo_keyframe_params;
+typedef struct {
+    int action;                       /* OV2_SKF_*; the other fields are 0 unless OV2_SKF_DONE                               */
+    int n;                            /* the frame's size                                                                    */
+    int n_prior3d, n_prior_nb;        /* ov2_stereo_priors_result: priors of kind 1 / kind 2                                 */
+    int n_stereo_kps;                 /* stereo_ok slots: the reference's nb_stereo_kps_ after stereoMatching                */
+    int n_stereo, n_stereo_good;      /* ov2_tri_result: nbstereo / good of triangulateStereo                                */
+    int nb3dkps;                      /* is3d slots of the frame after the call: the keyframe info's kf_nb3dkps              */
+} ov2_stereo_keyframe_result;
+int  ov2_btracker_stereo_keyframe_begin(ov2_btracker *t, int n_active, const ov2_stereo_keyframe_params *params,
+                                        const ov2_pyr *right, const uint8_t *do_h);
+int  ov2_btracker_stereo_keyframe_end(ov2_btracker *t, ov2_stereo_keyframe_result *results, float *right_px_h,
+                                      uint8_t *stereo_ok_h, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h);
+int  ov2_btracker_stereo_keyframe(ov2_btracker *t, int n_active, const ov2_stereo_keyframe_params *params, const ov2_pyr *right,
+                                  const uint8_t *do_h, ov2_stereo_keyframe_result *results, float *right_px_h,
+                                  uint8_t *stereo_ok_h, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h);
+int  ov2_btracker_get_keyframe_info(ov2_btracker *t, int item, int from_device, int *kf_id, double *kf_time, int *kf_nb3dkps,
+                                    int *has_info);
+
 #ifdef __cplusplus
 }
 #endif

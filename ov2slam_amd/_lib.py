@@ -49,6 +49,7 @@ OV2_KF_FIRST_FRAME, OV2_KF_NO_KEYFRAME = 512, 1024      # ov2_btracker_track_mon
 OV2_CKF_DET_SINGLESCALE, OV2_CKF_DET_GRID_FAST, OV2_CKF_DET_GFTT = 0, 1, 2             # ov2_btracker_create_keyframe
 OV2_CKF_NOT_REQUESTED, OV2_CKF_CREATED, OV2_CKF_OVERFLOW, OV2_CKF_DUP_LMID = 0, 1, 2, 3
 OV2_RES_SET_POINT, OV2_RES_UNSET_POINT, OV2_RES_REMOVE = 0, 1, 2                        # ov2_btracker_update_frame
+OV2_SKF_NOT_REQUESTED, OV2_SKF_NOT_KEYFRAME, OV2_SKF_DONE = 0, 1, 2                     # ov2_btracker_stereo_keyframe
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -496,6 +497,20 @@ class ResidentStepResult(C.Structure):
     _fields_ = [("n_before", C.c_int), ("n_after", C.c_int)]
 
 
+class StereoKeyframeParams(C.Structure):
+    """ov2_stereo_keyframe_params"""
+    _fields_ = [("nklt_win_size", C.c_int), ("nklt_pyr_lvl", C.c_int), ("max_iter", C.c_int), ("eps", C.c_float), ("nklt_err", C.c_float),
+                ("fmax_fbklt_dist", C.c_float), ("rect", C.c_int), ("Frl", C.c_double * 9), ("model", C.c_int), ("K", C.c_double * 4),
+                ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("iK", C.c_double * 9), ("img_w", C.c_double), ("img_h", C.c_double),
+                ("Tcic0", C.c_double * 7), ("ncellsize", C.c_int), ("tri", TriParams)]
+
+
+class StereoKeyframeResult(C.Structure):
+    """ov2_stereo_keyframe_result"""
+    _fields_ = [("action", C.c_int), ("n", C.c_int), ("n_prior3d", C.c_int), ("n_prior_nb", C.c_int), ("n_stereo_kps", C.c_int),
+                ("n_stereo", C.c_int), ("n_stereo_good", C.c_int), ("nb3dkps", C.c_int)]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -727,6 +742,11 @@ SIGNATURES = {
                                               C.POINTER(EpifilterResult), C.POINTER(PoseResult), C.POINTER(TrackMonoResult),
                                               C.POINTER(ResidentStepResult)]),
     "ov2_btracker_last_slot_bytes": (_i, [_vp, C.POINTER(C.c_size_t)]),
+    "ov2_btracker_stereo_keyframe_begin": (_i, [_vp, _i, C.POINTER(StereoKeyframeParams), _vp, _vp]),
+    "ov2_btracker_stereo_keyframe_end": (_i, [_vp, C.POINTER(StereoKeyframeResult), _vp, _vp, _vp, _vp, _vp]),
+    "ov2_btracker_stereo_keyframe": (_i, [_vp, _i, C.POINTER(StereoKeyframeParams), _vp, _vp, C.POINTER(StereoKeyframeResult),
+                                          _vp, _vp, _vp, _vp, _vp]),
+    "ov2_btracker_get_keyframe_info": (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_i), C.POINTER(_i)]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

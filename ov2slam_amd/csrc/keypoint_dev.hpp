@@ -71,6 +71,15 @@ int ov2_launch_compute_keypoints(hipStream_t s, const KpCalib &c, const float *p
 int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double img_h, int use_prior, const void *items_d,
                            const double *Tcw_d, const float *px_d, const uint8_t *is3d_d, const double *wpt_d, float *prior_d,
                            uint8_t *has_prior_d, int n_max, int n_items);
+// priors.hip: k_prior_stereo, and stereo.hip: k_line_min_sad / k_epipolar_check, on device arrays with n_max point slots per item
+int ov2_launch_prior_stereo(hipStream_t s, const KpCalib &c, const double *Tcic0, double img_w, double img_h, int ncellsize, int nbw, int nbh,
+                            int rect, const void *items_d, const double *Tcw_d, const float *px_d, const float *unpx_d, const double *bv_d,
+                            const double *wpt_d, const uint8_t *state_d, const int *cell_start_d, const int *cell_kp_d, float *prior_d,
+                            uint8_t *has_prior_d, uint8_t *skip_d, int n_max, int n_items);
+int ov2_launch_line_min_sad(hipStream_t s, const ov2_pyr *left, const ov2_pyr *right, int level, int nwinsize, int go_left, const float *pts_d,
+                            int n_max, float *xprior_d, float *l1err_d, const int *n_dev, int n_items);
+int ov2_launch_epipolar_check(hipStream_t s, int rect, const double Frl[9], const KpCalib &c, const float *lunpx_d, float *rkps_d, int n_max,
+                              float *runpx_d, float *epi_err_d, uint8_t *ok_d, const int *n_dev, int n_items);
 
 // The forward model: CameraCalibration::projectCamToImageDist (src/camera_calibration.cpp:254-281) of a camera-frame point.
 // x = X / z, y = Y / z in double through invz; without coefficients Point2f(fx x + cx, fy y + cy).  With coefficients x, y are

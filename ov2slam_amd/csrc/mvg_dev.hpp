@@ -12,6 +12,12 @@ struct TriD3 { double x, y, z; };
 struct TriQ { double x, y, z, w; };
 struct TriSE3 { TriD3 t; TriQ q; };      // a pose as held: [tx ty tz qx qy qz qw]
 
+// triangulate.hip: k_triangulate on device arrays (items_d: {first slot, count, first source row, 0} per item)
+int ov2_launch_triangulate(hipStream_t s, const ov2_tri_params *params, const void *items_d, const double *twc_d, const double *srcT_d,
+                           const float *unpx_d, const double *bv_d, const float *runpx_d, const double *rbv_d, const float *src_unpx_d,
+                           const double *src_bv_d, const int *src_d, const uint8_t *is_stereo_d, uint8_t *status_d, double *wpt_d,
+                           double *invdepth_d, int n_max, int n_items);
+
 __device__ __forceinline__ double tri_dot(TriD3 a, TriD3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ TriD3 tri_cross(TriD3 a, TriD3 b)       // Eigen's cross
 {

@@ -120,6 +120,22 @@ int ov2_launch_prior_frame(hipStream_t s, const KpCalib &c, double img_w, double
     return OV2_OK;
 }
 
+// launcher for trackb.hip (ov2_btracker_stereo_keyframe): the stereo form on device arrays with n_max point slots per item
+// (items_d: PriItemD per item, written on the device; Tcic0: 7 doubles; cell_start_d / cell_kp_d unread with rect)
+int ov2_launch_prior_stereo(hipStream_t s, const KpCalib &c, const double *Tcic0, double img_w, double img_h, int ncellsize, int nbw, int nbh,
+                            int rect, const void *items_d, const double *Tcw_d, const float *px_d, const float *unpx_d, const double *bv_d,
+                            const double *wpt_d, const uint8_t *state_d, const int *cell_start_d, const int *cell_kp_d, float *prior_d,
+                            uint8_t *has_prior_d, uint8_t *skip_d, int n_max, int n_items)
+{
+    PriPose Tr;
+    memcpy(Tr.v, Tcic0, 56);
+    hipLaunchKernelGGL(k_prior_stereo, dim3((n_max + PRI_THREADS - 1) / PRI_THREADS, n_items), dim3(PRI_THREADS), 0, s, c, Tr, img_w, img_h,
+                       (float)ncellsize, nbw, nbh, rect ? 1 : 0, (const PriItemD *)items_d, Tcw_d, (const float2 *)px_d, (const float2 *)unpx_d,
+                       bv_d, wpt_d, state_d, cell_start_d, cell_kp_d, (float2 *)prior_d, has_prior_d, skip_d);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
 // the camera of either params struct: the model, a coefficient count it takes, a positive image size
 template <class Params>
 static int pri_check_camera(const Params *params)

@@ -144,6 +144,29 @@ __global__ __launch_bounds__(256) void k_epipolar_check(EpiParams E, KpCalib c, 
     ok[i] = e <= 2.f ? 1 : 0;
 }
 
+// launchers for trackb.hip (ov2_btracker_stereo_keyframe): the two kernels on device arrays with n_max point slots and one n_dev
+// entry per item, the grids of ov2_stereo_match_batch
+int ov2_launch_line_min_sad(hipStream_t s, const ov2_pyr *left, const ov2_pyr *right, int level, int nwinsize, int go_left, const float *pts_d,
+                            int n_max, float *xprior_d, float *l1err_d, const int *n_dev, int n_items)
+{
+    hipLaunchKernelGGL(k_line_min_sad, dim3((n_max + 3) / 4, n_items), dim3(256), 0, s, left->d, right->d, level, nwinsize, go_left ? 1 : 0,
+                       (const float2 *)pts_d, n_max, xprior_d, l1err_d, n_dev);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
+int ov2_launch_epipolar_check(hipStream_t s, int rect, const double Frl[9], const KpCalib &c, const float *lunpx_d, float *rkps_d, int n_max,
+                              float *runpx_d, float *epi_err_d, uint8_t *ok_d, const int *n_dev, int n_items)
+{
+    EpiParams E;
+    for (int i = 0; i < 9; i++) E.F[i] = Frl ? Frl[i] : 0.;
+    E.rect = rect ? 1 : 0;
+    hipLaunchKernelGGL(k_epipolar_check, dim3((n_max + 255) / 256, n_items), dim3(256), 0, s, E, c, (const float2 *)lunpx_d, (float2 *)rkps_d,
+                       n_max, (float2 *)runpx_d, epi_err_d, ok_d, n_dev);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
 extern "C" {
 
 int ov2_line_min_sad(ov2_ctx *ctx, const ov2_pyr *left, const ov2_pyr *right, int level, int nwinsize, int go_left,

@@ -45,6 +45,8 @@
 #include "detect_dev.hpp"
 #include "createkf_dev.hpp"
 #include "resident_dev.hpp"
+#include "stereokf_dev.hpp"
+#include "mvg_dev.hpp"
 #include "fkf_dev.hpp"
 #include "trackb_layout.hpp"
 #include <algorithm>
@@ -63,6 +65,7 @@ static_assert(sizeof(FeKfHdr) == BT_KF_HDR_BYTES, "trackb_layout.hpp: the index 
 static_assert(sizeof(ov2_motion_state) == BT_MOTION_STATE_BYTES, "trackb_layout.hpp: the mono blocks' state");
 static_assert(sizeof(FkfItemD) == BT_FKF_ITEM_BYTES && 4 * FKF_OUT_INTS == BT_KF_DEC_BYTES, "trackb_layout.hpp: the mono blocks' records");
 static_assert(sizeof(ov2_create_keyframe_result) == BT_CKF_REC_BYTES && sizeof(SelectOut) == BT_CKF_SO_BYTES, "trackb_layout.hpp: the createKeyframe block's records");
+static_assert(sizeof(ov2_stereo_keyframe_result) == BT_SKF_REC_BYTES && sizeof(SkfItemD) == 16, "trackb_layout.hpp: the stereo keyframe block's records");
 static_assert(sizeof(ov2_resident_op) == BT_RES_OP_BYTES && sizeof(ov2_resident_update_result) == BT_RES_REC_BYTES, "trackb_layout.hpp: the resident frame's records");
 
 // A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
@@ -245,6 +248,15 @@ struct ov2_btracker {
     uint8_t *dfr = nullptr, *hfr = nullptr, *drc = nullptr, *hrc = nullptr;
     std::vector<uint8_t> res_sel;
     size_t slot_bytes = 0;            // ov2_btracker_last_slot_bytes
+    // ov2_btracker_stereo_keyframe (f22), allocated by its first call: the I/O block (pinned [0, s_down), and its device mirror with the
+    // work ranges behind: BtSkfLayout, regrown when a call's grid has more cells), per item whether its resident frame is its resident
+    // keyframe, and the call between _begin and _end
+    BtSkfLayout sl;
+    int skf_cells = -1;
+    uint8_t *hskf = nullptr, *dskf = nullptr;
+    std::vector<uint8_t> res_iskf;
+    struct SkfPending { bool on = false; int n_active = 0; std::vector<uint8_t> action; } spend;
+    bool open_call() const { return pend.on || cpend.on || spend.on; }
 };
 
 static void btracker_free(ov2_btracker *t)
@@ -283,6 +295,8 @@ static void btracker_free(ov2_btracker *t)
     if (t->hfr) (void)hipHostFree(t->hfr);
     if (t->drc) (void)hipFree(t->drc);
     if (t->hrc) (void)hipHostFree(t->hrc);
+    if (t->hskf) (void)hipHostFree(t->hskf);
+    if (t->dskf) (void)hipFree(t->dskf);
     delete t;
 }
 
@@ -779,6 +793,7 @@ static int ensure_res(ov2_btracker *t)
     memset(hc, 0, L.ctl_bytes);
     t->dfr = df; t->hfr = hf; t->drc = dc; t->hrc = hc;
     t->res_sel.assign((size_t)t->batch, 0);
+    t->res_iskf.assign((size_t)t->batch, 0);
     return OV2_OK;
 }
 
@@ -889,6 +904,7 @@ static int res_finish(ov2_btracker *t, const float *out_xy_h, const uint8_t *sta
     if (!redo.empty()) OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
     for (int b = 0; b < P.n_active; b++) {
         t->res_sel[(size_t)b] ^= 1;
+        t->res_iskf[(size_t)b] = 0;                                      // the frame has moved on from its keyframe
         if (fres) { fres[b].n_before = P.n[(size_t)b]; fres[b].n_after = *res_host(t, b, 0).n; }
     }
     return OV2_OK;
@@ -1074,7 +1090,7 @@ int ov2_btracker_set_rectification(ov2_btracker *t, const ov2_rectmap *map)
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(!map || (map->w == t->cfg.w && map->h == t->cfg.h), OV2_EINVAL, "map and tracker differ in size");
     OV2_REQUIRE(!map || map->device == t->ctx->device, OV2_EINVAL, "the map lives on another device");
-    OV2_REQUIRE(t->prepq.empty() && !t->pend.on && !t->cpend.on, OV2_EINVAL, "ov2_btracker_set_rectification between steps only: prepared frames wait or a step is open");
+    OV2_REQUIRE(t->prepq.empty() && !t->open_call(), OV2_EINVAL, "ov2_btracker_set_rectification between steps only: prepared frames wait or a step is open");
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
     OV2_HIP_CHECK(hipStreamSynchronize(t->cs));
     OV2_HIP_CHECK(hipStreamSynchronize(t->ps));
@@ -1108,6 +1124,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
     OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
+    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(A.stride >= t->cfg.w, OV2_EINVAL, "stride < width");
     const size_t nm = (size_t)t->cfg.n_max;
@@ -1746,7 +1763,7 @@ int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf
         for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(h.kf_Tcw[c]), OV2_EINVAL, "pose not finite (the inverse of kf_Twc)");
     }
     for (size_t i = 0; i < 3 * (size_t)n_kf; i++) OV2_REQUIRE(std::isfinite(kf_bv[i]), OV2_EINVAL, "kf_bv not finite");
-    OV2_REQUIRE(!t->pend.on && !t->cpend.on, OV2_EINVAL, "ov2_btracker_set_keyframe between steps only: a step is open");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_set_keyframe between steps only: a step is open");
     const int rc = ensure_epi(t, nullptr);
     if (rc != OV2_OK) return rc;
     const EpifLayout &L0 = t->eL0;
@@ -1762,6 +1779,7 @@ int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf
         OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kb + 24 * o, kh + (L0.o_kb - L0.o_kl) + 24 * o, 24 * n, hipMemcpyHostToDevice, s));
     }
     t->kf_hdr[(size_t)item] = h;
+    if (!t->res_iskf.empty()) t->res_iskf[(size_t)item] = 0;
     OV2_HIP_CHECK(hipMemcpyAsync(t->dfx + sizeof(FeKfHdr) * (size_t)item, &t->kf_hdr[(size_t)item], sizeof(FeKfHdr), hipMemcpyHostToDevice, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));                              // the host copy may be rewritten by the next call
     return OV2_OK;
@@ -1803,7 +1821,7 @@ static int mono_item(ov2_btracker *t, int item, const char *open_msg)
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(!t->pend.on && !t->cpend.on, OV2_EINVAL, open_msg);
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, open_msg);
     return ensure_mono(t);
 }
 
@@ -1896,7 +1914,7 @@ static int res_entry(ov2_btracker *t, int item0, int n_items, const char *open_m
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     OV2_REQUIRE(n_items >= 1 && item0 >= 0 && item0 <= t->batch - n_items, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(!t->pend.on && !t->cpend.on, OV2_EINVAL, open_msg);
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, open_msg);
     return ensure_res(t);
 }
 
@@ -1916,6 +1934,7 @@ int ov2_btracker_set_frame(ov2_btracker *t, int item, int n, const float *px, co
     int rc = res_entry(t, item, 1, "ov2_btracker_set_frame between steps only: a step is open");
     if (rc != OV2_OK) return rc;
     const ResHost f = res_host(t, item, 0);
+    t->res_iskf[(size_t)item] = 0;
     *f.n = n;
     if (n) { memcpy(f.px, px, 8 * (size_t)n); memcpy(f.lmid, lmid, 4 * (size_t)n); memcpy(f.wpt, wpt, 24 * (size_t)n); }
     for (int i = 0; i < n; i++) f.is3d[i] = is3d[i] ? 1 : 0;
@@ -2024,6 +2043,7 @@ static int res_update(ov2_btracker *t, int b0, int nb, const int *n_ops_h, const
         }
         *dst.n = r;
         t->res_sel[(size_t)b] ^= 1;
+        if (r != n) t->res_iskf[(size_t)b] = 0;                          // a slot left: the frame is no longer the keyframe's
     }
     return OV2_OK;
 }
@@ -2282,6 +2302,7 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_create_keyframe between steps only: a step is open");
     OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: the previous call has not been finished (ov2_btracker_create_keyframe_end)");
+    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
     OV2_REQUIRE(t->raw_which >= 0, OV2_EINVAL, "ov2_btracker_create_keyframe: no current frames (no step yet, or their staging set was uploaded / prepared again)");
     OV2_REQUIRE(n_active <= t->raw_n, OV2_EINVAL, "n_active exceeds the items of the current step");
     OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_create_keyframe: no calibration set on this tracker");
@@ -2475,7 +2496,10 @@ int ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result
         memcpy(&t->kf_hdr[(size_t)b], h + L.c_hdr + sizeof(FeKfHdr) * (size_t)b, sizeof(FeKfHdr));
         t->res_ki[(size_t)b] = MonoKfInfo{P.nkfid[(size_t)b], r.nb3dkps, 1, 0};
         t->res_kt[(size_t)b] = P.time[(size_t)b];
-        if (!P.resident) continue;
+        if (!P.resident) {                                                   // the keyframe is no longer the resident frame, if it was
+            if (!t->res_iskf.empty()) t->res_iskf[(size_t)b] = 0;
+            continue;
+        }
         // the resident frame's mirror, as k_res_adopt left the device: the old slots, then the new points without a 3-D point
         const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
         memcpy(dst.px, h + L.c_px + 8 * o, 8 * n);
@@ -2486,6 +2510,7 @@ int ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result
         memset(dst.wpt + 3 * n0, 0, 24 * (n - n0));
         *dst.n = (int)n;
         t->res_sel[(size_t)b] ^= 1;
+        t->res_iskf[(size_t)b] = 1;                                      // the resident frame IS the resident keyframe
     }
     return OV2_OK;
 }
@@ -2499,6 +2524,245 @@ int ov2_btracker_create_keyframe(ov2_btracker *t, int n_active, const ov2_create
     const int rc = ov2_btracker_create_keyframe_begin(t, n_active, params, input);
     if (rc != OV2_OK) return rc;
     return ov2_btracker_create_keyframe_end(t, results, out_px_h, out_lmid_h, unpx_h, bv_h, desc_h, valid_h, color_h);
+}
+
+} // extern "C"
+
+// ---- ov2_btracker_stereo_keyframe (f22) --------------------------------------------------------------------------------------------
+// the call's buffers: the pinned block by the first call, the device block regrown when the grid has more cells than any before
+static int ensure_skf(ov2_btracker *t, int cells)
+{
+    const char *who = "ov2_btracker_stereo_keyframe";
+    const BtSkfLayout L = bt_skf_layout(t->batch, t->cfg.n_max, cells > t->skf_cells ? cells : t->skf_cells);
+    if (!t->hskf) {
+        uint8_t *h = nullptr;
+        const hipError_t e = hipHostMalloc((void **)&h, L.s_down, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("%s: %s", who, hipGetErrorString(e)); return OV2_ENOMEM; }
+        memset(h, 0, L.s_down);
+        t->hskf = h;
+    }
+    if (cells > t->skf_cells) {
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (an earlier call's kernels have long finished: its _end waited)
+        if (t->dskf) (void)hipFree(t->dskf);
+        t->dskf = nullptr; t->skf_cells = -1;
+        uint8_t *d = nullptr;
+        hipError_t e = hipMalloc((void **)&d, L.dev_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(d, 0, L.dev_bytes, t->ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+        if (e != hipSuccess) {
+            if (d) (void)hipFree(d);
+            (void)hipGetLastError();
+            ov2_set_error("%s: %s", who, hipGetErrorString(e));
+            return OV2_ENOMEM;
+        }
+        t->dskf = d; t->skf_cells = cells; t->sl = L;
+    }
+    return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_stereo_keyframe_begin(ov2_btracker *t, int n_active, const ov2_stereo_keyframe_params *params,
+                                       const ov2_pyr *right, const uint8_t *do_h)
+{
+    OV2_REQUIRE(t && params && right && do_h, OV2_EINVAL, "ov2_btracker_stereo_keyframe: NULL tracker / params / right / do_h");
+    const ov2_stereo_keyframe_params &p = *params;
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
+    OV2_REQUIRE(n_active <= 65535, OV2_EUNSUPPORTED, "more than 65535 items in one call");
+    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe between steps only: a step is open");
+    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
+    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe_begin: the previous call has not been finished (ov2_btracker_stereo_keyframe_end)");
+    OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no calibration set on this tracker");
+    OV2_REQUIRE(t->dfr, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no resident frame on this tracker (ov2_btracker_set_frame)");
+    OV2_REQUIRE(t->frames > 0, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no current frames (no step yet)");
+    const ov2_tracker_config &c = t->cfg;
+    OV2_REQUIRE(c.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    const ov2_pyr *left = t->pyr[t->cur];
+    {
+        const PyrDesc &A = left->d, &R = right->d;
+        bool same = R.n_levels == A.n_levels && R.win == A.win;
+        for (int l = 0; same && l < A.n_levels; l++) same = R.lv[l].w == A.lv[l].w && R.lv[l].h == A.lv[l].h;
+        OV2_REQUIRE(R.batch >= n_active, OV2_EINVAL, "ov2_btracker_stereo_keyframe: the right pyramid has fewer items than n_active");
+        OV2_REQUIRE(same, OV2_EINVAL, "ov2_btracker_stereo_keyframe: the right pyramid differs from the tracker's in size, window or level count");
+        OV2_REQUIRE(p.nklt_win_size == A.win, OV2_EINVAL, "ov2_btracker_stereo_keyframe: nklt_win_size is not the pyramids' window");
+        const int w = p.nklt_win_size;
+        OV2_REQUIRE(w == 5 || w == 7 || w == 9 || w == 11 || w == 13, OV2_EUNSUPPORTED, "LK window has no kernel instance (supported: 5,7,9,11,13; the reference ships 9)");
+    }
+    // the right camera, as ov2_stereo_priors checks it
+    OV2_REQUIRE(p.model == OV2_CAM_PINHOLE || p.model == OV2_CAM_FISHEYE, OV2_EINVAL, "unknown camera model");
+    OV2_REQUIRE(p.nD >= 0 && (p.nD == 0 || p.D), OV2_EINVAL, "bad distortion vector: nD < 0 or D == NULL");
+    OV2_REQUIRE(p.nD == 0 || (p.model == OV2_CAM_FISHEYE ? p.nD == 4 : (p.nD == 4 || p.nD == 5 || p.nD == 8 || p.nD == 12)), OV2_EUNSUPPORTED,
+                "unsupported coefficient count: pinhole takes 0 / 4 / 5 / 8 / 12 distortion coefficients, fisheye 0 / 4");
+    OV2_REQUIRE(p.img_w > 0 && p.img_h > 0, OV2_EINVAL, "img_w / img_h not positive");     // false for NaN too
+    OV2_REQUIRE(p.img_w <= 65536 && p.img_h <= 65536, OV2_EINVAL, "img_w / img_h above 65536");
+    const bool rect = p.rect != 0;
+    int nbw = 0, nbh = 0;
+    if (!rect) {
+        OV2_REQUIRE(p.ncellsize > 0, OV2_EINVAL, "ncellsize not positive");
+        nbw = (int)ceilf((float)p.img_w / (float)p.ncellsize);              // Frame's grid (frame.cpp:41-43)
+        nbh = (int)ceilf((float)p.img_h / (float)p.ncellsize);
+        OV2_REQUIRE((long long)nbw * nbh <= OV2_FKF_MAX_CELLS, OV2_EINVAL, "the keypoint grid has more than OV2_FKF_MAX_CELLS (65536) cells");
+    }
+    const int ncells = nbw * nbh;
+    OV2_REQUIRE(p.tri.stereo != 0, OV2_EINVAL, "ov2_btracker_stereo_keyframe: params->tri.stereo == 0 (triangulateStereo runs in stereo mode only)");
+    for (int k = 0; k < 7; k++)
+        OV2_REQUIRE(std::isfinite(p.Tcic0[k]) && std::isfinite(p.tri.Tcic0[k]) && std::isfinite(p.tri.Tlr[k]), OV2_EINVAL, "pose not finite (Tcic0 / tri.Tcic0 / tri.Tlr)");
+    OV2_REQUIRE((size_t)t->batch * (size_t)c.n_max <= 0x7fffffff && (size_t)t->batch * ((size_t)ncells + 1) <= 0x7fffffff, OV2_EUNSUPPORTED,
+                "more than 2^31 - 1 elements of one kind in one call");
+    KpCalib cr;
+    int rc = ov2_kp_calib(p.model, p.K, p.D, p.nD, p.iK, cr);  if (rc != OV2_OK) return rc;
+    ov2_ctx *ctx = t->ctx;
+    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;
+    rc = ensure_mono(t);  if (rc != OV2_OK) return rc;
+    rc = ensure_skf(t, ncells);  if (rc != OV2_OK) return rc;
+    ov2_btracker::SkfPending &P = t->spend;
+    P.n_active = n_active;
+    P.action.assign((size_t)n_active, OV2_SKF_NOT_REQUESTED);
+    const BtSkfLayout &L = t->sl;
+    uint8_t *h = t->hskf, *d = t->dskf;
+    int n_done = 0;
+    size_t total = 0;
+    for (int b = 0; b < n_active; b++) {
+        const int action = !do_h[b] ? OV2_SKF_NOT_REQUESTED : (t->res_iskf[(size_t)b] ? OV2_SKF_DONE : OV2_SKF_NOT_KEYFRAME);
+        P.action[(size_t)b] = (uint8_t)action;
+        h[L.s_act + (size_t)b] = action == OV2_SKF_DONE ? 1 : 0;
+        if (action != OV2_SKF_DONE) continue;
+        n_done++;
+        total += (size_t)*res_host(t, b, 0).n;
+    }
+    t->slot_bytes = 0;
+    P.on = true;
+    if (!n_done) return OV2_OK;
+    // ---- the one enqueue ----
+    const hipStream_t s = ctx->stream;
+    rc = ov2_pyr_wait_ready(ctx, left);  if (rc != OV2_OK) { P.on = false; return rc; }
+    rc = ov2_pyr_wait_ready(ctx, right);  if (rc != OV2_OK) { P.on = false; return rc; }
+    const int lvl = p.nklt_pyr_lvl > left->d.n_levels - 1 ? left->d.n_levels - 1 : (p.nklt_pyr_lvl < 0 ? 0 : p.nklt_pyr_lvl);
+    const float up = (float)(1 << lvl), down = 1.f / up;                    // pow(2, nklt_pyr_lvl) and its inverse (:417-418)
+    const int nm = c.n_max;
+    SkfArgs a;
+    a.f = res_frames(t);
+    a.act = d + L.s_act; a.hdr = (const FeKfHdr *)t->dfx; a.r_ki = (MonoKfInfo *)(t->dres + t->nl.r_ki);
+    a.left = t->calib; a.right = cr;
+    a.n_max = nm; a.rect = rect ? 1 : 0; a.nbw = nbw; a.nbh = nbh; a.cellsize = (float)p.ncellsize; a.down = down;
+    a.pit = (SkfItemD *)(d + L.w_pit); a.tit = (int4 *)(d + L.w_tit); a.Tcw = (double *)(d + L.w_Tcw); a.Twc = (double *)(d + L.w_Twc);
+    a.nd = (int *)(d + L.w_nd);
+    a.px = (float2 *)(d + L.w_px); a.unpx = (float2 *)(d + L.w_un); a.bv = (double *)(d + L.w_bv); a.fw = (double *)(d + L.w_fw);
+    a.top = (float2 *)(d + L.w_top); a.state = d + L.w_st; a.src = (int *)(d + L.w_src);
+    a.cell_start = (int *)(d + L.w_cs); a.cell_kp = (int *)(d + L.w_ck);
+    a.has_prior = d + L.w_hp; a.flag = d + L.w_fl; a.sadx = (float *)(d + L.w_sx);
+    a.lk_out = (const float2 *)(d + L.w_out); a.lk_st = d + L.w_lk; a.gate_ok = d + L.w_ok;
+    a.runpx = (float2 *)(d + L.w_ru); a.rbv = (double *)(d + L.w_rbv); a.is_stereo = d + L.w_is;
+    a.right_px = (float2 *)(d + L.s_rpx); a.stereo_ok = d + L.s_sok; a.tri_status = d + L.s_tst; a.tri_wpt = (const double *)(d + L.s_wpt);
+    a.rec = (ov2_stereo_keyframe_result *)(d + L.s_rec);
+    rc = [&]() -> int {
+        OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.s_up, hipMemcpyHostToDevice, s));
+        int r = res_push_sel(t, s);  if (r != OV2_OK) return r;
+        r = ov2_launch_skf_input(s, a, n_active);  if (r != OV2_OK) return r;
+        if (total > 0) {
+            const int *n_d = a.nd;
+            r = ov2_launch_prior_stereo(s, cr, p.Tcic0, p.img_w, p.img_h, p.ncellsize, nbw, nbh, a.rect, a.pit, a.Tcw, (const float *)a.px,
+                                        (const float *)a.unpx, a.bv, a.fw, a.state, a.cell_start, a.cell_kp, (float *)(d + L.w_pri), d + L.w_hp,
+                                        d + L.w_sk, nm, n_active);
+            if (r != OV2_OK) return r;
+            r = ov2_launch_skf_seed(s, a, n_active);  if (r != OV2_OK) return r;
+            if (rect) {
+                r = ov2_launch_line_min_sad(s, left, right, lvl, 7, 1, (const float *)a.top, nm, a.sadx, (float *)(d + L.w_l1), n_d, n_active);
+                if (r != OV2_OK) return r;
+            }
+            r = ov2_launch_track_klt(s, left, right, p.nklt_win_size, 1, lvl, p.max_iter, p.eps, p.nklt_err, p.fmax_fbklt_dist, nm, n_d,
+                                     (const float *)a.px, (const float *)(d + L.w_pri), a.flag, (float *)(d + L.w_out), d + L.w_lk, nullptr, a.sadx,
+                                     up, ctx->track_impl, n_active, ctx->lk_acc);
+            if (r != OV2_OK) return r;
+            r = ov2_launch_epipolar_check(s, a.rect, p.Frl, cr, (const float *)a.unpx, (float *)(d + L.w_out), nm, (float *)(d + L.w_gru),
+                                          (float *)(d + L.w_err), d + L.w_ok, n_d, n_active);
+            if (r != OV2_OK) return r;
+            r = ov2_launch_skf_stereo_kp(s, a, n_active);  if (r != OV2_OK) return r;
+            r = ov2_launch_triangulate(s, &p.tri, a.tit, a.Twc, nullptr, (const float *)a.unpx, a.bv, (const float *)a.runpx, a.rbv, nullptr, nullptr,
+                                       a.src, a.is_stereo, d + L.s_tst, (double *)(d + L.s_wpt), (double *)(d + L.s_inv), nm, n_active);
+            if (r != OV2_OK) return r;
+        }
+        r = ov2_launch_skf_apply(s, a, n_active);  if (r != OV2_OK) return r;
+        OV2_HIP_CHECK(hipMemcpyAsync(h + L.s_io, d + L.s_io, L.s_down - L.s_io, hipMemcpyDeviceToHost, s));
+        return OV2_OK;
+    }();
+    if (rc != OV2_OK) { (void)hipStreamSynchronize(s); P.on = false; }      // nothing flips: every frame stays what it was
+    return rc;
+}
+
+int ov2_btracker_stereo_keyframe_end(ov2_btracker *t, ov2_stereo_keyframe_result *results, float *right_px_h,
+                                     uint8_t *stereo_ok_h, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    ov2_btracker::SkfPending &P = t->spend;
+    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe_end without ov2_btracker_stereo_keyframe_begin");
+    OV2_REQUIRE(results && right_px_h && stereo_ok_h && tri_status_h && wpt_h && invdepth_h, OV2_EINVAL,
+                "ov2_btracker_stereo_keyframe_end: NULL result / output array");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    P.on = false;
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    const BtSkfLayout &L = t->sl;
+    const uint8_t *h = t->hskf;
+    const size_t nm = (size_t)t->cfg.n_max;
+    for (int b = 0; b < P.n_active; b++) {
+        ov2_stereo_keyframe_result &r = results[b];
+        memset(&r, 0, sizeof r);
+        r.action = P.action[(size_t)b];
+        if (r.action != OV2_SKF_DONE) continue;
+        memcpy(&r, h + L.s_rec + sizeof r * (size_t)b, sizeof r);
+        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
+        const size_t o = nm * (size_t)b, n = (size_t)*src.n;
+        const uint8_t *st = h + L.s_tst + o;
+        const double *w = (const double *)(h + L.s_wpt) + 3 * o;
+        memcpy(right_px_h + 2 * o, h + L.s_rpx + 8 * o, 8 * n);
+        memcpy(stereo_ok_h + o, h + L.s_sok + o, n);
+        memcpy(tri_status_h + o, st, n);
+        memcpy(wpt_h + 3 * o, w, 24 * n);
+        memcpy(invdepth_h + o, h + L.s_inv + 8 * o, 8 * n);
+        // the host mirrors, as k_skf_apply left the device: the frame with the new points, the keyframe's count of 3-D keypoints
+        memcpy(dst.px, src.px, 8 * n);
+        memcpy(dst.lmid, src.lmid, 4 * n);
+        for (size_t i = 0; i < n; i++) {
+            const bool good = (st[i] & OV2_TRI_STEREO_OK) != 0;
+            dst.is3d[i] = good || src.is3d[i] ? 1 : 0;
+            for (int k = 0; k < 3; k++) dst.wpt[3 * i + k] = good ? w[3 * i + k] : src.wpt[3 * i + k];
+        }
+        *dst.n = (int)n;
+        t->res_sel[(size_t)b] ^= 1;
+        t->res_ki[(size_t)b].kf_nb3dkps = r.nb3dkps;
+    }
+    return OV2_OK;
+}
+
+int ov2_btracker_stereo_keyframe(ov2_btracker *t, int n_active, const ov2_stereo_keyframe_params *params, const ov2_pyr *right,
+                                 const uint8_t *do_h, ov2_stereo_keyframe_result *results, float *right_px_h, uint8_t *stereo_ok_h,
+                                 uint8_t *tri_status_h, double *wpt_h, double *invdepth_h)
+{
+    OV2_REQUIRE(results && right_px_h && stereo_ok_h && tri_status_h && wpt_h && invdepth_h, OV2_EINVAL,
+                "ov2_btracker_stereo_keyframe: NULL result / output array");
+    const int rc = ov2_btracker_stereo_keyframe_begin(t, n_active, params, right, do_h);
+    if (rc != OV2_OK) return rc;
+    return ov2_btracker_stereo_keyframe_end(t, results, right_px_h, stereo_ok_h, tri_status_h, wpt_h, invdepth_h);
+}
+
+int ov2_btracker_get_keyframe_info(ov2_btracker *t, int item, int from_device, int *kf_id, double *kf_time, int *kf_nb3dkps, int *has_info)
+{
+    const int rc = mono_item(t, item, "ov2_btracker_get_keyframe_info between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    MonoKfInfo ki = t->res_ki[(size_t)item];
+    double kt = t->res_kt[(size_t)item];
+    if (from_device) {
+        const hipStream_t s = t->ctx->stream;
+        OV2_HIP_CHECK(hipMemcpyAsync(&ki, t->dres + t->nl.r_ki + sizeof ki * (size_t)item, sizeof ki, hipMemcpyDeviceToHost, s));
+        OV2_HIP_CHECK(hipMemcpyAsync(&kt, t->dres + t->nl.r_kt + sizeof kt * (size_t)item, sizeof kt, hipMemcpyDeviceToHost, s));
+        OV2_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (kf_id) *kf_id = ki.kf_id;
+    if (kf_time) *kf_time = kt;
+    if (kf_nb3dkps) *kf_nb3dkps = ki.kf_nb3dkps;
+    if (has_info) *has_info = ki.has_info;
+    return OV2_OK;
 }
 
 const ov2_pyr *ov2_btracker_cur_pyr(const ov2_btracker *t) { return t ? t->pyr[t->cur] : nullptr; }

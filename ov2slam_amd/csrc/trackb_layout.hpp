@@ -1,7 +1,7 @@
 // trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
 // point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block, the three blocks of
-// ov2_btracker_track_mono, the block of ov2_btracker_create_keyframe and the two blocks of the resident frame, each computed by one
-// function of (batch, n_max).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
+// ov2_btracker_track_mono, the block of ov2_btracker_create_keyframe, the two blocks of the resident frame and the block of
+// ov2_btracker_stereo_keyframe, each computed by one function of (batch, n_max) (the last one: and the grid's cells).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
 #include <stddef.h>
@@ -150,5 +150,40 @@ static inline BtResLayout bt_res_layout(int batch, int n_max)
     StageCursor c(256);
     L.u_sel = c.take(B); L.u_nop = c.take(4 * B); L.u_off = c.take(4 * B); L.u_ops = c.take(BT_RES_OP_BYTES * slots);
     L.u_up = c.off; L.u_rec = c.take(BT_RES_REC_BYTES * B); L.ctl_bytes = c.off;
+    return L;
+}
+
+// The block of ov2_btracker_stereo_keyframe (f22): one pinned host block [0, s_down) and its device mirror at the same offsets,
+// ONE copy up ([0, s_up)) and ONE copy down ([s_io, s_down)); behind s_down the device-only work ranges of the kernels between.
+// `cells` is the grid of Frame::getSurroundingKeypoints (0 for a rectified pair: no grid).
+//   up only     [act 1 per item]: 1 where the item is OV2_SKF_DONE
+//   down only   [record 32 per item][right_px 8][wpt 24][invdepth 8][stereo_ok 1][tri_status 1 per slot]
+//   device only [PriItemD 16][tri item 16][Tcw 56][Twc 56][count 4 per item]
+//               [px 8][unpx 8][bv 24][frame wpt 24][pts_top 8][prior 8][LK out 8][gate runpx 8][runpx 8][rbv 24][src 4][sad x 4]
+//               [sad err 4][gate err 4][state 1][has_prior 1][skip 1][flag 1][LK status 1][gate ok 1][is_stereo 1 per slot]
+//               [cell_start 4 per cell + 1 per item][cell_kp 4 per slot]
+#define BT_SKF_REC_BYTES 32          // sizeof(ov2_stereo_keyframe_result): trackb.hip asserts it
+struct BtSkfLayout {
+    size_t s_act, s_up, s_io, s_rec, s_rpx, s_wpt, s_inv, s_sok, s_tst, s_down;
+    size_t w_pit, w_tit, w_Tcw, w_Twc, w_nd;
+    size_t w_px, w_un, w_bv, w_fw, w_top, w_pri, w_out, w_gru, w_ru, w_rbv, w_src, w_sx, w_l1, w_err;
+    size_t w_st, w_hp, w_sk, w_fl, w_lk, w_ok, w_is, w_cs, w_ck, dev_bytes;
+};
+static inline BtSkfLayout bt_skf_layout(int batch, int n_max, int cells)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    StageCursor c(256);
+    BtSkfLayout L;
+    L.s_act = c.take(B); L.s_up = c.off;
+    L.s_io = L.s_rec = c.take(BT_SKF_REC_BYTES * B); L.s_rpx = c.take(8 * slots); L.s_wpt = c.take(24 * slots); L.s_inv = c.take(8 * slots);
+    L.s_sok = c.take(slots); L.s_tst = c.take(slots); L.s_down = c.off;
+    L.w_pit = c.take(16 * B); L.w_tit = c.take(16 * B); L.w_Tcw = c.take(56 * B); L.w_Twc = c.take(56 * B); L.w_nd = c.take(4 * B);
+    L.w_px = c.take(8 * slots); L.w_un = c.take(8 * slots); L.w_bv = c.take(24 * slots); L.w_fw = c.take(24 * slots);
+    L.w_top = c.take(8 * slots); L.w_pri = c.take(8 * slots); L.w_out = c.take(8 * slots); L.w_gru = c.take(8 * slots);
+    L.w_ru = c.take(8 * slots); L.w_rbv = c.take(24 * slots); L.w_src = c.take(4 * slots); L.w_sx = c.take(4 * slots);
+    L.w_l1 = c.take(4 * slots); L.w_err = c.take(4 * slots);
+    L.w_st = c.take(slots); L.w_hp = c.take(slots); L.w_sk = c.take(slots); L.w_fl = c.take(slots); L.w_lk = c.take(slots);
+    L.w_ok = c.take(slots); L.w_is = c.take(slots);
+    L.w_cs = c.take(4 * ((size_t)cells + 1) * B); L.w_ck = c.take(4 * slots); L.dev_bytes = c.off;
     return L;
 }

@@ -124,6 +124,42 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_triangulate(TriParams P, const in
     invdepth[i] = inv;
 }
 
+// the kernel's parameter block of a call's ov2_tri_params
+static TriParams tri_make_params(const ov2_tri_params *params)
+{
+    TriParams P;
+    P.stereo = params->stereo ? 1 : 0; P.rect = params->rect ? 1 : 0; P.emax = params->fmax_reproj_err;
+    for (int j = 0; j < 4; j++) { P.K[j] = params->K[j]; P.Kr[j] = params->Kr[j]; }
+    for (int j = 0; j < 9; j++) P.iK[j] = params->iK[j];
+    P.Tlr = tri_load(params->Tlr); P.Tcic0 = tri_load(params->Tcic0);
+    {   // Trl = Tlr.inverse() (:379), the same arithmetic as the device's Tcjci, on the host once per call
+        const TriQ q = P.Tlr.q;
+        const double nn = std::sqrt(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
+        const TriQ qi{-q.x / nn, -q.y / nn, -q.z / nn, q.w / nn};
+        const TriD3 p{P.Tlr.t.x * -1., P.Tlr.t.y * -1., P.Tlr.t.z * -1.}, qv{qi.x, qi.y, qi.z};
+        TriD3 uv{qv.y * p.z - qv.z * p.y, qv.z * p.x - qv.x * p.z, qv.x * p.y - qv.y * p.x};
+        uv = TriD3{uv.x + uv.x, uv.y + uv.y, uv.z + uv.z};
+        const TriD3 c{qv.y * uv.z - qv.z * uv.y, qv.z * uv.x - qv.x * uv.z, qv.x * uv.y - qv.y * uv.x};
+        P.Trl = TriSE3{TriD3{(p.x + qi.w * uv.x) + c.x, (p.y + qi.w * uv.y) + c.y, (p.z + qi.w * uv.z) + c.z}, qi};
+    }
+    return P;
+}
+
+// launcher for trackb.hip (ov2_btracker_stereo_keyframe): k_triangulate on device arrays, items_d = {first slot, count, first source
+// row, 0} per item; n_max: the largest count an item may carry
+int ov2_launch_triangulate(hipStream_t s, const ov2_tri_params *params, const void *items_d, const double *twc_d, const double *srcT_d,
+                           const float *unpx_d, const double *bv_d, const float *runpx_d, const double *rbv_d, const float *src_unpx_d,
+                           const double *src_bv_d, const int *src_d, const uint8_t *is_stereo_d, uint8_t *status_d, double *wpt_d,
+                           double *invdepth_d, int n_max, int n_items)
+{
+    const TriParams P = tri_make_params(params);
+    hipLaunchKernelGGL(k_triangulate, dim3((n_max + TRI_BLOCK - 1) / TRI_BLOCK, n_items), dim3(TRI_BLOCK), 0, s, P, (const int4 *)items_d, twc_d,
+                       srcT_d, (const float2 *)unpx_d, bv_d, (const float2 *)runpx_d, rbv_d, (const float2 *)src_unpx_d, src_bv_d, src_d,
+                       is_stereo_d, status_d, wpt_d, invdepth_d);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
 int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, int n_items, const ov2_tri_keyframe *kfs,
                                    ov2_tri_result *results)
 {
@@ -158,21 +194,7 @@ int ov2_triangulate_keyframe_batch(ov2_ctx *ctx, const ov2_tri_params *params, i
         N += (size_t)k.n; S += (size_t)k.n_src;
         n_max = k.n > n_max ? k.n : n_max;
     }
-    TriParams P;
-    P.stereo = params->stereo ? 1 : 0; P.rect = params->rect ? 1 : 0; P.emax = params->fmax_reproj_err;
-    for (int j = 0; j < 4; j++) { P.K[j] = params->K[j]; P.Kr[j] = params->Kr[j]; }
-    for (int j = 0; j < 9; j++) P.iK[j] = params->iK[j];
-    P.Tlr = tri_load(params->Tlr); P.Tcic0 = tri_load(params->Tcic0);
-    {   // Trl = Tlr.inverse() (:379), the same arithmetic as the device's Tcjci, on the host once per call
-        const TriQ q = P.Tlr.q;
-        const double nn = std::sqrt(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-        const TriQ qi{-q.x / nn, -q.y / nn, -q.z / nn, q.w / nn};
-        const TriD3 p{P.Tlr.t.x * -1., P.Tlr.t.y * -1., P.Tlr.t.z * -1.}, qv{qi.x, qi.y, qi.z};
-        TriD3 uv{qv.y * p.z - qv.z * p.y, qv.z * p.x - qv.x * p.z, qv.x * p.y - qv.y * p.x};
-        uv = TriD3{uv.x + uv.x, uv.y + uv.y, uv.z + uv.z};
-        const TriD3 c{qv.y * uv.z - qv.z * uv.y, qv.z * uv.x - qv.x * uv.z, qv.x * uv.y - qv.y * uv.x};
-        P.Trl = TriSE3{TriD3{(p.x + qi.w * uv.x) + c.x, (p.y + qi.w * uv.y) + c.y, (p.z + qi.w * uv.z) + c.z}, qi};
-    }
+    const TriParams P = tri_make_params(params);
     // staging: [items 16B][Twc 56B][source table 112B] [unpx 8][bv 24][runpx 8][rbv 24][src_unpx 8][src_bv 24][src 4][stereo 1] per point,
     // then the outputs [status 1][wpt 24][invdepth 8] per point; every section 16-byte aligned
     const size_t B = (size_t)n_items;

@@ -1068,6 +1068,74 @@ class LockstepTracker:
         self._ckf_pending = None
         return self._ckf_dicts(R, na, o)
 
+    # ---- the mapper's stereo block on the resident keyframe (ov2_btracker_stereo_keyframe) -----------------------------------------
+    def _skf_outputs(self, na, out):
+        """the arrays _end scatters into (the caller's, so that untouched slots stay what they were, or fresh zeros)"""
+        shapes = dict(right_px=((self.batch, self.n_max, 2), np.float32), stereo_ok=((self.batch, self.n_max), np.uint8),
+                      tri_status=((self.batch, self.n_max), np.uint8), wpt=((self.batch, self.n_max, 3), np.float64),
+                      invdepth=((self.batch, self.n_max), np.float64))
+        o = {}
+        for k, (shape, dt) in shapes.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dt)
+            elif a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError("out[%r] must be a contiguous %s array of shape %r" % (k, np.dtype(dt).name, shape))
+            o[k] = a
+        return o, (L.StereoKeyframeResult * max(1, na))()
+
+    def _skf_dicts(self, R, na, o):
+        return [{k: int(getattr(R[b], k)) for k, _ in L.StereoKeyframeResult._fields_} for b in range(na)], o
+
+    @staticmethod
+    def _skf_do(n_active, do):
+        na = int(n_active)
+        d = np.ascontiguousarray(do, np.uint8).reshape(-1)
+        if len(d) < na:
+            raise ValueError("one flag per active item")
+        return na, d
+
+    def stereoKeyframe(self, n_active, right_pyr, do, params, out=None):
+        """MapManager::stereoMatching, then Mapper::triangulateStereo, on the resident keyframe of the items of [0, n_active) with
+        do[b] != 0 (normally: the item's last createKeyframe action was OV2_CKF_CREATED), in one enqueue and one synchronisation
+        (ov2_btracker_stereo_keyframe): the stereo priors, the line search (rect), the tracking from cur_pyr into right_pyr, the
+        epipolar gate, the right camera's computeKeypoint, triangulateStereo; every OV2_TRI_STEREO_OK slot becomes 3-D in the
+        resident frame and the keyframe info's kf_nb3dkps is recounted.  right_pyr: a batch Pyramid of the right images on this
+        tracker's context (it may still be building); params: mapper.stereo_keyframe_params(...); out: dict of arrays to scatter
+        into (missing ones are zeros).  Keypoints of a grid cell stand in slot order (not vgridkps_ insertion order); state 2
+        cannot occur (remove such observations with updateFrame first); triangulateTemporal is not run.
+        -> (records, out): records[b] = dict(action L.OV2_SKF_*, n, n_prior3d, n_prior_nb, n_stereo_kps, n_stereo, n_stereo_good,
+        nb3dkps); out = dict(right_px, stereo_ok, tri_status, wpt, invdepth) in the slot layout of the resident frame, written
+        for the items with action OV2_SKF_DONE only."""
+        na, d = self._skf_do(n_active, do)
+        o, R = self._skf_outputs(na, out)
+        L.check(self.lib.ov2_btracker_stereo_keyframe(self.h_trk, na, C.byref(params), right_pyr.h_pyr, _ptr(d), R, _ptr(o["right_px"]),
+                                                      _ptr(o["stereo_ok"]), _ptr(o["tri_status"]), _ptr(o["wpt"]), _ptr(o["invdepth"])))
+        return self._skf_dicts(R, na, o)
+
+    def stereoKeyframeBegin(self, n_active, right_pyr, do, params):
+        """first half of stereoKeyframe: enqueue and return; stereoKeyframeEnd finishes it"""
+        na, d = self._skf_do(n_active, do)
+        L.check(self.lib.ov2_btracker_stereo_keyframe_begin(self.h_trk, na, C.byref(params), right_pyr.h_pyr, _ptr(d)))
+        self._skf_pending = (na, right_pyr, params)
+
+    def stereoKeyframeEnd(self, out=None):
+        """second half of stereoKeyframe -> (records, out)"""
+        na = self._skf_pending[0] if getattr(self, "_skf_pending", None) else 0          # (no open call: the library refuses)
+        o, R = self._skf_outputs(na, out)
+        L.check(self.lib.ov2_btracker_stereo_keyframe_end(self.h_trk, R, _ptr(o["right_px"]), _ptr(o["stereo_ok"]), _ptr(o["tri_status"]),
+                                                          _ptr(o["wpt"]), _ptr(o["invdepth"])))
+        self._skf_pending = None
+        return self._skf_dicts(R, na, o)
+
+    def getKeyframeInfo(self, item, from_device=False):
+        """the resident keyframe info of item `item` -> dict(kf_id, kf_time, kf_nb3dkps, has_info): the host mirror, or with
+        from_device True copied down from the device block"""
+        i, t, n, hi = C.c_int(), C.c_double(), C.c_int(), C.c_int()
+        L.check(self.lib.ov2_btracker_get_keyframe_info(self.h_trk, int(item), int(bool(from_device)), C.byref(i), C.byref(t), C.byref(n),
+                                                        C.byref(hi)))
+        return dict(kf_id=i.value, kf_time=t.value, kf_nb3dkps=n.value, has_info=hi.value)
+
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
         pri = np.empty((n, 2), np.float32)

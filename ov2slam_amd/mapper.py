@@ -43,6 +43,31 @@ def tri_params(K, iK, Kr, Tlr, Tcic0, *, stereo, rect, fmax_reproj_err):
     return p
 
 
+def stereo_keyframe_params(right_calib, tri, *, img_w, img_h, Tcic0, rect, Frl=None, ncellsize=35, nklt_win_size=9, nklt_pyr_lvl=3,
+                           nmax_iter=30, fmax_px_precision=0.01, nklt_err=30.0, fmax_fbklt_dist=0.5):
+    """ov2_stereo_keyframe_params of LockstepTracker.stereoKeyframe, one struct with the fields of the calls it replaces: the LK
+    settings and Frl of stereo.stereo_match_batch_arrays, the RIGHT camera (a CameraCalibration: model, K, D, iK) with its image size
+    and Tcic0_ as priors.stereo_priors and CameraCalibration.computeKeypoints take them, the Frame's ncellsize_ (read without
+    rectification), and `tri`, the ov2_tri_params of tri_params() (tri.stereo must be set).  The left camera is the tracker's
+    (setCalibration).  The returned struct keeps its distortion array alive."""
+    p = L.StereoKeyframeParams()
+    p.nklt_win_size, p.nklt_pyr_lvl, p.max_iter = int(nklt_win_size), int(nklt_pyr_lvl), int(nmax_iter)
+    p.eps, p.nklt_err, p.fmax_fbklt_dist = float(np.float32(fmax_px_precision)), float(nklt_err), float(fmax_fbklt_dist)
+    p.rect = int(bool(rect))
+    p.Frl[:] = [0.0] * 9 if Frl is None else [float(v) for v in np.asarray(Frl, np.float64).reshape(9)]
+    p.model = right_calib.model
+    p.K[:] = [float(v) for v in right_calib.K]
+    d = np.zeros(0) if right_calib.D is None else np.ascontiguousarray(right_calib.D, np.float64).reshape(-1)
+    p._D = d
+    p.D, p.nD = (d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None), int(d.size)
+    p.iK[:] = [float(v) for v in np.asarray(right_calib.iK, np.float64).reshape(9)]
+    p.img_w, p.img_h = float(img_w), float(img_h)
+    p.Tcic0[:] = [float(v) for v in np.asarray(Tcic0, np.float64).reshape(7)]
+    p.ncellsize = int(ncellsize)
+    p.tri = _as_params(tri)
+    return p
+
+
 def _as_params(params):
     if isinstance(params, L.TriParams):
         return params
