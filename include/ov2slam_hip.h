@@ -2407,9 +2407,10 @@ int  ov2_btracker_last_slot_bytes(const ov2_btracker *t, size_t *h2d);
  *   keypoints  k_skf_stereo_kp: stereo_ok = tracked && gate; right_px as ov2_stereo_match_batch returns it ((0, 0) where the
  *              tracking failed, the corrected row for rect); for stereo_ok slots runpx / rbv by the right camera's computeKeypoint
  *              on right_px (Frame::computeStereoKeypoint, frame.cpp:405-420); is_stereo = stereo_ok && !is3d (mapper.cpp:383)
- *   triangulation   k_triangulate with src = -1 everywhere: the stereo pass alone.  Mapper::triangulateTemporal needs the map's
- *              source keyframes and is OUT OF SCOPE, as are updateMapPoint's other effects and removeStereoKeypointById's
- *              bookkeeping: the statuses returned are what a caller needs to replay them.
+ *   triangulation   k_triangulate with src = -1 everywhere: the stereo pass alone.  Mapper::triangulateTemporal is the call behind
+ *              this one, ov2_btracker_temporal_keyframe (it needs the source keyframes: the tracker's anchor table).
+ *              updateMapPoint's other effects and removeStereoKeypointById's bookkeeping are OUT OF SCOPE: the statuses
+ *              returned are what a caller needs to replay them.
  *   apply      k_skf_apply: every OV2_TRI_STEREO_OK slot gets is3d = 1 and wpt = the triangulated point, written into the item's
  *              OTHER frame buffer (_end flips it: a call begun and never ended leaves the frame as it was); kf_nb3dkps of the
  *              resident keyframe info becomes the number of is3d slots after the call (updateMapPoint -> turnKeypoint3d on the
@@ -2474,6 +2475,97 @@ int  ov2_btracker_stereo_keyframe(ov2_btracker *t, int n_active, const ov2_stere
                                   uint8_t *stereo_ok_h, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h);
 int  ov2_btracker_get_keyframe_info(ov2_btracker *t, int item, int from_device, int *kf_id, double *kf_time, int *kf_nb3dkps,
                                     int *has_info);
+
+/* Mapper::triangulateTemporal on the resident keyframe (f23): what Mapper::run executes on every new keyframe (src/mapper.cpp:107-127;
+ * the function is :191-343) for the items ov2_btracker_create_keyframe just turned into keyframes -- in stereo behind
+ * ov2_btracker_stereo_keyframe, in mono as the only source of 3-D points -- in ONE enqueue on the context's stream and ONE
+ * synchronisation, byte-equal to the route of separate calls (ov2_btracker_get_frame, a walk over the caller's map for src / src_unpx /
+ * src_bv and the source poses, ov2_triangulate_keyframe_batch, ov2_btracker_update_frame_batch, ov2_btracker_set_keyframe,
+ * ov2_btracker_set_keyframe_info).
+ * THE ANCHOR TABLE.  The reference asks its map for the first observing keyframe of a 2-D keypoint (*co_kf_ids.begin(), :262), that
+ * keyframe's keypoint (:292) and pose (:278, :332).  A keypoint that has left the current frame can never again be a 2-D keypoint of a
+ * new keyframe, so the tracker keeps that record only for the keypoints of the item's latest keyframe: per item at most cfg.n_max
+ * records {lmid, row, unpx, bv} ascending by lmid, and at most n_src_max rows {kfid, Twc, Tcw} ascending by kfid, one per keyframe
+ * some record still refers to.  The block is allocated by the first call that needs it (ov2_btracker_reserve_anchors, or the first
+ * ov2_btracker_temporal_keyframe with its params->n_src_max); another n_src_max afterwards is OV2_EINVAL.
+ *   ov2_btracker_set_anchors       installs an item's whole table, as ov2_btracker_set_keyframe installs a keyframe: n records (lmid
+ *                                  strictly ascending, kfid[i] the anchoring keyframe, its unpx (2 float) and bv (3 double)) and
+ *                                  n_rows rows (row_kfid strictly ascending, row_Twc 7 double each; Tcw = fe_invert_hd(Twc), the
+ *                                  arithmetic of ov2_btracker_set_keyframe).  OV2_EINVAL and the state untouched: no block reserved,
+ *                                  n outside [0, cfg.n_max], n_rows outside [0, n_src_max], a NULL array, lmid or row_kfid not
+ *                                  strictly ascending, a kfid[i] not among the rows, a pose or bv that is not finite, an open call.
+ *   ov2_btracker_get_anchors       the table of an item (from_device != 0: copied down, one synchronisation; else the host mirror);
+ *                                  arrays of cfg.n_max records / n_src_max rows, any output pointer may be NULL.
+ *   ov2_btracker_set_anchor_poses[_batch]   (item, kfid, Twc) triples, the poses local BA moved: ONE upload and ONE launch
+ *                                  (k_tkf_set_poses) for the batch, Tcw = fe_invert_hd(Twc).  A kfid that anchors nothing in its item
+ *                                  is counted in *n_ignored and ignored.  OV2_EINVAL: an item out of range, a pose not finite, the
+ *                                  same (item, kfid) twice, more triples than batch x n_src_max, no block, an open call.
+ * THE CALL.  Per item b of [0, n_active) with do_h[b] != 0 whose resident frame is its resident keyframe (csrc/temporalkf.hip):
+ *   anchors    k_tkf_anchor: the item's next table, written into its OTHER buffer.  A keypoint of the resident keyframe whose lmid
+ *              the current table holds inherits that record; any other is new and anchors at this keyframe (kf_id of the resident
+ *              keyframe info) with the kf_unpx / kf_bv k_ckf_install wrote.  Rows that lose their last record go, the others keep their
+ *              order, this keyframe's row (Twc / Tcw of the keyframe header) is appended.  More than n_src_max rows:
+ *              OV2_TKF_SRC_OVERFLOW, and frame, keyframe and anchors stay what they were.  A table whose newest row is this
+ *              keyframe already (a second call on the same keyframe, or ov2_btracker_set_anchors) is taken as it is.
+ *   input      k_tkf_input: a slot of the resident frame is a candidate when the keyframe holds its lmid (the reference's
+ *              getKeypoints2d() of the keyframe), it is not 3-D (:250) and its anchor is another keyframe than this one (:258-266);
+ *              unpx / bv from the keyframe's arrays, src_unpx / src_bv from the anchor.  plm == nullptr (:244) and pkf == nullptr
+ *              (:271) CANNOT OCCUR here: the caller removes such observations with ov2_btracker_update_frame and, after its map
+ *              culled a keyframe, installs the re-anchored table with ov2_btracker_set_anchors.
+ *   triangulation   k_triangulate on the row table with is_stereo = 0 everywhere: the temporal pass alone; params->tri.stereo is
+ *              read for the no-motion skip (:287), the left camera's K from params->tri.
+ *   apply      k_tkf_apply: every OV2_TRI_TEMPORAL_OK slot gets is3d = 1 and wpt, written into the item's OTHER frame buffer;
+ *              kf_nb3dkps of the resident keyframe info is recounted; every OV2_TRI_REMOVE_OBS slot is taken out of the resident
+ *              KEYFRAME (removeMapPointObs(lmid, frame.kfid_): the keyframe is compacted in order and its n_kf lowered), not out
+ *              of the frame, and the anchor table keeps its record: the first observer has not changed.  _end brings every host
+ *              mirror (frame, info, keyframe, anchors) to the same state from what comes down anyway.
+ * ONE DEVIATION: if a caller does not run this call for a keyframe it created, the points first seen there anchor at the next
+ * keyframe for which it does.
+ * results[b].action:
+ *   OV2_TKF_NOT_REQUESTED   do_h[b] == 0: nothing of the item is read or written
+ *   OV2_TKF_NOT_KEYFRAME    the byte and the rules of OV2_SKF_NOT_KEYFRAME; ov2_btracker_stereo_keyframe does not clear the byte
+ *   OV2_TKF_SRC_OVERFLOW    more than n_src_max rows are still referred to: nothing is written
+ *   OV2_TKF_DONE            the record and, in the slot space of the resident frame ([0, n) written), tri_status_h (OV2_TRI_* bits),
+ *                           wpt_h (3 double), invdepth_h and src_kfid_h (the anchoring keyframe of a candidate, else -1): what a
+ *                           caller needs to replay updateMapPoint and removeMapPointObs, and Mapper::run's mono reset test (:129-143)
+ * ov2_btracker_last_slot_bytes reports 0 after this call.  OV2_EINVAL, checked on the host before anything is enqueued (the tracker
+ * stays where it was): a NULL tracker / params / do_h; n_active outside [1, batch]; an open step, create_keyframe, stereo_keyframe
+ * call or call of this kind; no resident block; cfg.n_max > OV2_FKF_MAX_POINTS; n_src_max outside [1, OV2_TKF_MAX_ROWS] or another
+ * one than the block's; a non-finite params->tri.K; an item whose table holds a keyframe newer than its resident keyframe.  _end:
+ * no open call, a NULL result or output array.  Between _begin and _end the calls that change resident state or start a step
+ * return OV2_EINVAL. */
+#define OV2_TKF_MAX_ROWS      256
+#define OV2_TKF_NOT_REQUESTED 0
+#define OV2_TKF_NOT_KEYFRAME  1
+#define OV2_TKF_DONE          2
+#define OV2_TKF_SRC_OVERFLOW  3
+typedef struct {
+    ov2_tri_params tri;               /* ov2_triangulate_keyframe_batch: its params, as they are                             */
+    int n_src_max;                    /* rows of an item's anchor table: the keyframes its keypoints may anchor at            */
+} ov2_temporal_keyframe_params;
+typedef struct {
+    int action;                       /* OV2_TKF_*; the other fields are 0 unless OV2_TKF_DONE                               */
+    int n;                            /* the frame's size                                                                    */
+    int n_candidates, n_temporal_good;   /* ov2_tri_result: candidates / good of triangulateTemporal                         */
+    int n_remove_obs;                 /* OV2_TRI_REMOVE_OBS slots: keypoints taken out of the keyframe                       */
+    int n_no_motion;                  /* OV2_TRI_NO_MOTION slots                                                             */
+    int nb3dkps;                      /* is3d slots of the frame after the call: the keyframe info's kf_nb3dkps              */
+    int n_rows;                       /* rows of the item's anchor table after the call                                      */
+} ov2_temporal_keyframe_result;
+int  ov2_btracker_reserve_anchors(ov2_btracker *t, int n_src_max);
+int  ov2_btracker_set_anchors(ov2_btracker *t, int item, int n, const int *lmid, const int *kfid, const float *unpx, const double *bv,
+                              int n_rows, const int *row_kfid, const double *row_Twc);
+int  ov2_btracker_get_anchors(ov2_btracker *t, int item, int from_device, int *n, int *lmid, int *kfid, float *unpx, double *bv,
+                              int *n_rows, int *row_kfid, double *row_Twc, double *row_Tcw);
+int  ov2_btracker_set_anchor_poses_batch(ov2_btracker *t, int n, const int *item, const int *kfid, const double *Twc, int *n_ignored);
+int  ov2_btracker_set_anchor_poses(ov2_btracker *t, int item, int n, const int *kfid, const double *Twc, int *n_ignored);
+int  ov2_btracker_temporal_keyframe_begin(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params,
+                                          const uint8_t *do_h);
+int  ov2_btracker_temporal_keyframe_end(ov2_btracker *t, ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h,
+                                        double *invdepth_h, int *src_kfid_h);
+int  ov2_btracker_temporal_keyframe(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params, const uint8_t *do_h,
+                                    ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h,
+                                    int *src_kfid_h);
 
 #ifdef __cplusplus
 }

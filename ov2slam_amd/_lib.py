@@ -50,6 +50,8 @@ OV2_CKF_DET_SINGLESCALE, OV2_CKF_DET_GRID_FAST, OV2_CKF_DET_GFTT = 0, 1, 2      
 OV2_CKF_NOT_REQUESTED, OV2_CKF_CREATED, OV2_CKF_OVERFLOW, OV2_CKF_DUP_LMID = 0, 1, 2, 3
 OV2_RES_SET_POINT, OV2_RES_UNSET_POINT, OV2_RES_REMOVE = 0, 1, 2                        # ov2_btracker_update_frame
 OV2_SKF_NOT_REQUESTED, OV2_SKF_NOT_KEYFRAME, OV2_SKF_DONE = 0, 1, 2                     # ov2_btracker_stereo_keyframe
+OV2_TKF_NOT_REQUESTED, OV2_TKF_NOT_KEYFRAME, OV2_TKF_DONE, OV2_TKF_SRC_OVERFLOW = 0, 1, 2, 3   # ov2_btracker_temporal_keyframe
+OV2_TKF_MAX_ROWS = 256
 OV2_P3P_LMEDS, OV2_P3P_RANSAC = 0, 1
 OV2_P3P_TOO_FEW_POINTS, OV2_P3P_NO_MODEL, OV2_P3P_FEW_INLIERS, OV2_P3P_NOT_ORTHOGONAL = 1, 2, 4, 8
 OV2_P3P_MAX_POINTS, OV2_P3P_MAX_ROWS = 2048, 4096
@@ -511,6 +513,17 @@ class StereoKeyframeResult(C.Structure):
                 ("n_stereo", C.c_int), ("n_stereo_good", C.c_int), ("nb3dkps", C.c_int)]
 
 
+class TemporalKeyframeParams(C.Structure):
+    """ov2_temporal_keyframe_params"""
+    _fields_ = [("tri", TriParams), ("n_src_max", C.c_int)]
+
+
+class TemporalKeyframeResult(C.Structure):
+    """ov2_temporal_keyframe_result"""
+    _fields_ = [("action", C.c_int), ("n", C.c_int), ("n_candidates", C.c_int), ("n_temporal_good", C.c_int), ("n_remove_obs", C.c_int),
+                ("n_no_motion", C.c_int), ("nb3dkps", C.c_int), ("n_rows", C.c_int)]
+
+
 class KltPriorsParams(C.Structure):
     """ov2_klt_priors_params"""
     _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.POINTER(C.c_double)), ("nD", C.c_int), ("img_w", C.c_double),
@@ -747,6 +760,15 @@ SIGNATURES = {
     "ov2_btracker_stereo_keyframe": (_i, [_vp, _i, C.POINTER(StereoKeyframeParams), _vp, _vp, C.POINTER(StereoKeyframeResult),
                                           _vp, _vp, _vp, _vp, _vp]),
     "ov2_btracker_get_keyframe_info": (_i, [_vp, _i, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_i), C.POINTER(_i)]),
+    "ov2_btracker_reserve_anchors": (_i, [_vp, _i]),
+    "ov2_btracker_set_anchors": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ov2_btracker_get_anchors": (_i, [_vp, _i, _i, C.POINTER(_i), _vp, _vp, _vp, _vp, C.POINTER(_i), _vp, _vp, _vp]),
+    "ov2_btracker_set_anchor_poses_batch": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(_i)]),
+    "ov2_btracker_set_anchor_poses": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(_i)]),
+    "ov2_btracker_temporal_keyframe_begin": (_i, [_vp, _i, C.POINTER(TemporalKeyframeParams), _vp]),
+    "ov2_btracker_temporal_keyframe_end": (_i, [_vp, C.POINTER(TemporalKeyframeResult), _vp, _vp, _vp, _vp]),
+    "ov2_btracker_temporal_keyframe": (_i, [_vp, _i, C.POINTER(TemporalKeyframeParams), _vp, C.POINTER(TemporalKeyframeResult),
+                                            _vp, _vp, _vp, _vp]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

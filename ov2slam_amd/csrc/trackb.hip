@@ -46,6 +46,7 @@
 #include "createkf_dev.hpp"
 #include "resident_dev.hpp"
 #include "stereokf_dev.hpp"
+#include "temporalkf_dev.hpp"
 #include "mvg_dev.hpp"
 #include "fkf_dev.hpp"
 #include "trackb_layout.hpp"
@@ -66,6 +67,7 @@ static_assert(sizeof(ov2_motion_state) == BT_MOTION_STATE_BYTES, "trackb_layout.
 static_assert(sizeof(FkfItemD) == BT_FKF_ITEM_BYTES && 4 * FKF_OUT_INTS == BT_KF_DEC_BYTES, "trackb_layout.hpp: the mono blocks' records");
 static_assert(sizeof(ov2_create_keyframe_result) == BT_CKF_REC_BYTES && sizeof(SelectOut) == BT_CKF_SO_BYTES, "trackb_layout.hpp: the createKeyframe block's records");
 static_assert(sizeof(ov2_stereo_keyframe_result) == BT_SKF_REC_BYTES && sizeof(SkfItemD) == 16, "trackb_layout.hpp: the stereo keyframe block's records");
+static_assert(sizeof(ov2_temporal_keyframe_result) == BT_TKF_REC_BYTES, "trackb_layout.hpp: the temporal keyframe block's record");
 static_assert(sizeof(ov2_resident_op) == BT_RES_OP_BYTES && sizeof(ov2_resident_update_result) == BT_RES_REC_BYTES, "trackb_layout.hpp: the resident frame's records");
 
 // A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
@@ -256,7 +258,15 @@ struct ov2_btracker {
     uint8_t *hskf = nullptr, *dskf = nullptr;
     std::vector<uint8_t> res_iskf;
     struct SkfPending { bool on = false; int n_active = 0; std::vector<uint8_t> action; } spend;
-    bool open_call() const { return pend.on || cpend.on || spend.on; }
+    // ov2_btracker_temporal_keyframe (f23), allocated by the first call that needs it: the anchor block (two buffers, item-major) and
+    // its pinned mirror, per item the buffer of its current table, the call's I/O block (pinned [0, t_down), and its device mirror with
+    // the work ranges behind), the block of ov2_btracker_set_anchor_poses, and the call between _begin and _end
+    BtTkfLayout tl;
+    int n_src_max = 0;
+    uint8_t *danc = nullptr, *hanc = nullptr, *htkf = nullptr, *dtkf = nullptr, *hap = nullptr, *dap = nullptr;
+    std::vector<uint8_t> anc_sel;
+    struct TkfPending { bool on = false; int n_active = 0; std::vector<uint8_t> action; } tpend;
+    bool open_call() const { return pend.on || cpend.on || spend.on || tpend.on; }
 };
 
 static void btracker_free(ov2_btracker *t)
@@ -297,6 +307,12 @@ static void btracker_free(ov2_btracker *t)
     if (t->hrc) (void)hipHostFree(t->hrc);
     if (t->hskf) (void)hipHostFree(t->hskf);
     if (t->dskf) (void)hipFree(t->dskf);
+    if (t->danc) (void)hipFree(t->danc);
+    if (t->hanc) (void)hipHostFree(t->hanc);
+    if (t->dtkf) (void)hipFree(t->dtkf);
+    if (t->htkf) (void)hipHostFree(t->htkf);
+    if (t->dap) (void)hipFree(t->dap);
+    if (t->hap) (void)hipHostFree(t->hap);
     delete t;
 }
 
@@ -1125,6 +1141,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
     OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
     OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
+    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_temporal_keyframe_begin has not been finished (ov2_btracker_temporal_keyframe_end)");
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(A.stride >= t->cfg.w, OV2_EINVAL, "stride < width");
     const size_t nm = (size_t)t->cfg.n_max;
@@ -2303,6 +2320,7 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_create_keyframe between steps only: a step is open");
     OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: the previous call has not been finished (ov2_btracker_create_keyframe_end)");
     OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
+    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: ov2_btracker_temporal_keyframe_begin has not been finished (ov2_btracker_temporal_keyframe_end)");
     OV2_REQUIRE(t->raw_which >= 0, OV2_EINVAL, "ov2_btracker_create_keyframe: no current frames (no step yet, or their staging set was uploaded / prepared again)");
     OV2_REQUIRE(n_active <= t->raw_n, OV2_EINVAL, "n_active exceeds the items of the current step");
     OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_create_keyframe: no calibration set on this tracker");
@@ -2572,6 +2590,7 @@ int ov2_btracker_stereo_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe between steps only: a step is open");
     OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
     OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe_begin: the previous call has not been finished (ov2_btracker_stereo_keyframe_end)");
+    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe: ov2_btracker_temporal_keyframe_begin has not been finished (ov2_btracker_temporal_keyframe_end)");
     OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no calibration set on this tracker");
     OV2_REQUIRE(t->dfr, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no resident frame on this tracker (ov2_btracker_set_frame)");
     OV2_REQUIRE(t->frames > 0, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no current frames (no step yet)");
@@ -2763,6 +2782,387 @@ int ov2_btracker_get_keyframe_info(ov2_btracker *t, int item, int from_device, i
     if (kf_nb3dkps) *kf_nb3dkps = ki.kf_nb3dkps;
     if (has_info) *has_info = ki.has_info;
     return OV2_OK;
+}
+
+} // extern "C"
+
+// ---- ov2_btracker_temporal_keyframe (f23) and the anchor table -----------------------------------------------------------------------
+// item b of the anchor mirror: its current table (other == 0) or the buffer its next table is written into (other == 1)
+struct AncHost { uint8_t *p; int *n, *lmid, *row; float *unpx; double *bv; int *n_rows, *kfid; double *Twc, *Tcw; };
+static AncHost anc_at(const BtTkfLayout &L, uint8_t *p)
+{
+    return AncHost{p, (int *)(p + L.a_n), (int *)(p + L.a_lm), (int *)(p + L.a_row), (float *)(p + L.a_un), (double *)(p + L.a_bv),
+                   (int *)(p + L.a_nr), (int *)(p + L.a_kf), (double *)(p + L.a_Twc), (double *)(p + L.a_Tcw)};
+}
+static AncHost anc_host(const ov2_btracker *t, int b, int other)
+{
+    const BtTkfLayout &L = t->tl;
+    return anc_at(L, t->hanc + (size_t)(t->anc_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.a_item);
+}
+
+static TkfAnchors tkf_anchors(const ov2_btracker *t)
+{
+    const BtTkfLayout &L = t->tl;
+    return TkfAnchors{t->danc, L.buf_bytes, L.a_item, L.a_lm, L.a_row, L.a_un, L.a_bv, L.a_nr, L.a_kf, L.a_Twc, L.a_Tcw, t->dtkf + L.t_sel,
+                      t->cfg.n_max, t->n_src_max};
+}
+
+// the anchor block, its mirror, the call's blocks and the pose block, allocated by the first call that needs them: every table empty
+static int ensure_tkf(ov2_btracker *t, int n_src_max, const char *who)
+{
+    OV2_REQUIRE(n_src_max >= 1 && n_src_max <= OV2_TKF_MAX_ROWS, OV2_EINVAL, "n_src_max outside [1, OV2_TKF_MAX_ROWS (256)]");
+    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    if (t->danc) {
+        OV2_REQUIRE(n_src_max == t->n_src_max, OV2_EINVAL, "n_src_max differs from the one this tracker's anchor block was allocated with");
+        return OV2_OK;
+    }
+    OV2_REQUIRE((size_t)t->batch * (size_t)t->cfg.n_max <= 0x7fffffff && (size_t)t->batch * (size_t)n_src_max <= 0x7fffffff, OV2_EUNSUPPORTED,
+                "more than 2^31 - 1 elements of one kind in one call");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const BtTkfLayout L = bt_tkf_layout(t->batch, t->cfg.n_max, n_src_max);
+    uint8_t *da = nullptr, *ha = nullptr, *dk = nullptr, *hk = nullptr, *dp = nullptr, *hp = nullptr;
+    const hipStream_t s = t->ctx->stream;
+    hipError_t e = hipMalloc((void **)&da, L.anchor_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&ha, L.anchor_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&dk, L.dev_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&hk, L.t_down, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void **)&dp, L.pose_bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&hp, L.pose_bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemsetAsync(da, 0, L.anchor_bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(dk, 0, L.dev_bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(dp, 0, L.pose_bytes, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        if (da) (void)hipFree(da);
+        if (ha) (void)hipHostFree(ha);
+        if (dk) (void)hipFree(dk);
+        if (hk) (void)hipHostFree(hk);
+        if (dp) (void)hipFree(dp);
+        if (hp) (void)hipHostFree(hp);
+        (void)hipGetLastError();
+        ov2_set_error("%s: %s", who, hipGetErrorString(e));
+        return OV2_ENOMEM;
+    }
+    memset(ha, 0, L.anchor_bytes);
+    memset(hk, 0, L.t_down);
+    memset(hp, 0, L.pose_bytes);
+    t->danc = da; t->hanc = ha; t->dtkf = dk; t->htkf = hk; t->dap = dp; t->hap = hp;
+    t->tl = L; t->n_src_max = n_src_max;
+    t->anc_sel.assign((size_t)t->batch, 0);
+    return OV2_OK;
+}
+
+// what the calls around the anchor table share: the item, no open call, the block
+static int anc_entry(ov2_btracker *t, int item, const char *open_msg)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, open_msg);
+    OV2_REQUIRE(t->danc, OV2_EINVAL, "no anchor block on this tracker (ov2_btracker_reserve_anchors / ov2_btracker_temporal_keyframe)");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_reserve_anchors(ov2_btracker *t, int n_src_max)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_reserve_anchors between steps only: a step is open");
+    return ensure_tkf(t, n_src_max, "ov2_btracker_reserve_anchors");
+}
+
+int ov2_btracker_set_anchors(ov2_btracker *t, int item, int n, const int *lmid, const int *kfid, const float *unpx, const double *bv,
+                             int n_rows, const int *row_kfid, const double *row_Twc)
+{
+    int rc = anc_entry(t, item, "ov2_btracker_set_anchors between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    OV2_REQUIRE(n >= 0 && n <= t->cfg.n_max, OV2_EINVAL, "ov2_btracker_set_anchors: n outside [0, cfg.n_max]");
+    OV2_REQUIRE(n_rows >= 0 && n_rows <= t->n_src_max, OV2_EINVAL, "ov2_btracker_set_anchors: n_rows outside [0, n_src_max]");
+    OV2_REQUIRE(n == 0 || (lmid && kfid && unpx && bv), OV2_EINVAL, "ov2_btracker_set_anchors: NULL array");
+    OV2_REQUIRE(n_rows == 0 || (row_kfid && row_Twc), OV2_EINVAL, "ov2_btracker_set_anchors: NULL array");
+    for (int i = 1; i < n; i++) OV2_REQUIRE(lmid[i - 1] < lmid[i], OV2_EINVAL, "ov2_btracker_set_anchors: lmid unsorted: not strictly ascending");
+    for (int r = 1; r < n_rows; r++) OV2_REQUIRE(row_kfid[r - 1] < row_kfid[r], OV2_EINVAL, "ov2_btracker_set_anchors: row_kfid unsorted: not strictly ascending");
+    std::vector<double> Tcw(7 * (size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(row_Twc[7 * r + c]), OV2_EINVAL, "ov2_btracker_set_anchors: pose not finite (row_Twc)");
+        fe_invert_hd(row_Twc + 7 * r, Tcw.data() + 7 * (size_t)r);
+        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(Tcw[7 * (size_t)r + c]), OV2_EINVAL, "ov2_btracker_set_anchors: pose not finite (the inverse of row_Twc)");
+    }
+    std::vector<int> row((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int *e = std::lower_bound(row_kfid, row_kfid + n_rows, kfid[i]);
+        OV2_REQUIRE(e != row_kfid + n_rows && *e == kfid[i], OV2_EINVAL, "ov2_btracker_set_anchors: a kfid that is not among the rows");
+        row[(size_t)i] = (int)(e - row_kfid);
+        OV2_REQUIRE(std::isfinite(unpx[2 * i]) && std::isfinite(unpx[2 * i + 1]) && std::isfinite(bv[3 * i]) && std::isfinite(bv[3 * i + 1]) &&
+                    std::isfinite(bv[3 * i + 2]), OV2_EINVAL, "ov2_btracker_set_anchors: unpx / bv not finite");
+    }
+    const AncHost a = anc_host(t, item, 0);
+    *a.n = n; *a.n_rows = n_rows;
+    if (n) { memcpy(a.lmid, lmid, 4 * (size_t)n); memcpy(a.row, row.data(), 4 * (size_t)n); memcpy(a.unpx, unpx, 8 * (size_t)n); memcpy(a.bv, bv, 24 * (size_t)n); }
+    if (n_rows) { memcpy(a.kfid, row_kfid, 4 * (size_t)n_rows); memcpy(a.Twc, row_Twc, 56 * (size_t)n_rows); memcpy(a.Tcw, Tcw.data(), 56 * (size_t)n_rows); }
+    const hipStream_t s = t->ctx->stream;
+    OV2_HIP_CHECK(hipMemcpyAsync(t->danc + (a.p - t->hanc), a.p, t->tl.a_item, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipStreamSynchronize(s));
+    return OV2_OK;
+}
+
+int ov2_btracker_get_anchors(ov2_btracker *t, int item, int from_device, int *n, int *lmid, int *kfid, float *unpx, double *bv,
+                             int *n_rows, int *row_kfid, double *row_Twc, double *row_Tcw)
+{
+    int rc = anc_entry(t, item, "ov2_btracker_get_anchors between steps only: a step is open");
+    if (rc != OV2_OK) return rc;
+    const BtTkfLayout &L = t->tl;
+    AncHost a = anc_host(t, item, 0);
+    std::vector<uint8_t> dev;
+    if (from_device) {
+        dev.resize(L.a_item);
+        OV2_HIP_CHECK(hipMemcpyAsync(dev.data(), t->danc + (a.p - t->hanc), L.a_item, hipMemcpyDeviceToHost, t->ctx->stream));
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+        a = anc_at(L, dev.data());
+    }
+    const int m = std::min(std::max(*a.n, 0), t->cfg.n_max), mr = std::min(std::max(*a.n_rows, 0), t->n_src_max);
+    if (n) *n = m;
+    if (n_rows) *n_rows = mr;
+    if (lmid) memcpy(lmid, a.lmid, 4 * (size_t)m);
+    if (unpx) memcpy(unpx, a.unpx, 8 * (size_t)m);
+    if (bv) memcpy(bv, a.bv, 24 * (size_t)m);
+    if (kfid) for (int i = 0; i < m; i++) kfid[i] = (a.row[i] >= 0 && a.row[i] < mr) ? a.kfid[a.row[i]] : -1;
+    if (row_kfid) memcpy(row_kfid, a.kfid, 4 * (size_t)mr);
+    if (row_Twc) memcpy(row_Twc, a.Twc, 56 * (size_t)mr);
+    if (row_Tcw) memcpy(row_Tcw, a.Tcw, 56 * (size_t)mr);
+    return OV2_OK;
+}
+
+int ov2_btracker_set_anchor_poses_batch(ov2_btracker *t, int n, const int *item, const int *kfid, const double *Twc, int *n_ignored)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_set_anchor_poses between steps only: a step is open");
+    OV2_REQUIRE(t->danc, OV2_EINVAL, "no anchor block on this tracker (ov2_btracker_reserve_anchors / ov2_btracker_temporal_keyframe)");
+    OV2_REQUIRE(n >= 0 && (size_t)n <= (size_t)t->batch * (size_t)t->n_src_max, OV2_EINVAL, "ov2_btracker_set_anchor_poses: n outside [0, batch x n_src_max]");
+    OV2_REQUIRE(n == 0 || (item && kfid && Twc), OV2_EINVAL, "ov2_btracker_set_anchor_poses: NULL array");
+    std::vector<std::pair<int, int>> keys((size_t)n);
+    for (int k = 0; k < n; k++) {
+        OV2_REQUIRE(item[k] >= 0 && item[k] < t->batch, OV2_EINVAL, "batch item out of range");
+        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(Twc[7 * (size_t)k + c]), OV2_EINVAL, "ov2_btracker_set_anchor_poses: pose not finite");
+        keys[(size_t)k] = std::make_pair(item[k], kfid[k]);
+    }
+    std::sort(keys.begin(), keys.end());
+    for (int k = 1; k < n; k++) OV2_REQUIRE(keys[(size_t)k - 1] != keys[(size_t)k], OV2_EINVAL, "ov2_btracker_set_anchor_poses: the same (item, kfid) twice");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    // the mirror, and the count of the triples that anchor nothing
+    int ignored = 0;
+    for (int k = 0; k < n; k++) {
+        const AncHost a = anc_host(t, item[k], 0);
+        const int mr = std::min(std::max(*a.n_rows, 0), t->n_src_max);
+        const int *e = std::lower_bound(a.kfid, a.kfid + mr, kfid[k]);
+        if (e == a.kfid + mr || *e != kfid[k]) { ignored++; continue; }
+        const size_t r = (size_t)(e - a.kfid);
+        memcpy(a.Twc + 7 * r, Twc + 7 * (size_t)k, 56);
+        fe_invert_hd(Twc + 7 * (size_t)k, a.Tcw + 7 * r);
+    }
+    if (n_ignored) *n_ignored = ignored;
+    if (n == ignored) return OV2_OK;
+    const BtTkfLayout &L = t->tl;
+    const hipStream_t s = t->ctx->stream;
+    memcpy(t->hap + L.p_item, item, 4 * (size_t)n);
+    memcpy(t->hap + L.p_kfid, kfid, 4 * (size_t)n);
+    memcpy(t->hap + L.p_Twc, Twc, 56 * (size_t)n);
+    memcpy(t->htkf + L.t_sel, t->anc_sel.data(), (size_t)t->batch);
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dtkf + L.t_sel, t->htkf + L.t_sel, (size_t)t->batch, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->dap, t->hap, L.p_Twc + 56 * (size_t)n, hipMemcpyHostToDevice, s));
+    const int rc = ov2_launch_tkf_set_poses(s, tkf_anchors(t), t->batch, n, (const int *)(t->dap + L.p_item), (const int *)(t->dap + L.p_kfid),
+                                            (const double *)(t->dap + L.p_Twc));
+    OV2_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+}
+
+int ov2_btracker_set_anchor_poses(ov2_btracker *t, int item, int n, const int *kfid, const double *Twc, int *n_ignored)
+{
+    OV2_REQUIRE(n >= 0 && n <= OV2_TKF_MAX_ROWS, OV2_EINVAL, "ov2_btracker_set_anchor_poses: n outside [0, OV2_TKF_MAX_ROWS]");
+    const std::vector<int> items((size_t)n, item);
+    return ov2_btracker_set_anchor_poses_batch(t, n, items.data(), kfid, Twc, n_ignored);
+}
+
+int ov2_btracker_temporal_keyframe_begin(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params, const uint8_t *do_h)
+{
+    OV2_REQUIRE(t && params && do_h, OV2_EINVAL, "ov2_btracker_temporal_keyframe: NULL tracker / params / do_h");
+    const ov2_temporal_keyframe_params &p = *params;
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
+    OV2_REQUIRE(n_active <= 65535, OV2_EUNSUPPORTED, "more than 65535 items in one call");
+    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe between steps only: a step is open");
+    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
+    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
+    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe_begin: the previous call has not been finished (ov2_btracker_temporal_keyframe_end)");
+    OV2_REQUIRE(t->dfr, OV2_EINVAL, "ov2_btracker_temporal_keyframe: no resident frame on this tracker (ov2_btracker_set_frame)");
+    const ov2_tracker_config &c = t->cfg;
+    OV2_REQUIRE(c.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    for (int k = 0; k < 4; k++) OV2_REQUIRE(std::isfinite(p.tri.K[k]), OV2_EINVAL, "ov2_btracker_temporal_keyframe: params->tri.K not finite");
+    for (int k = 0; k < 7; k++)
+        OV2_REQUIRE(std::isfinite(p.tri.Tcic0[k]) && std::isfinite(p.tri.Tlr[k]), OV2_EINVAL, "pose not finite (tri.Tcic0 / tri.Tlr)");
+    ov2_ctx *ctx = t->ctx;
+    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = ensure_tkf(t, p.n_src_max, "ov2_btracker_temporal_keyframe");  if (rc != OV2_OK) return rc;
+    rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;
+    rc = ensure_mono(t);  if (rc != OV2_OK) return rc;
+    for (int b = 0; b < n_active; b++) {
+        if (!do_h[b] || !t->res_iskf[(size_t)b]) continue;
+        const AncHost a = anc_host(t, b, 0);
+        const int mr = std::min(std::max(*a.n_rows, 0), t->n_src_max);
+        OV2_REQUIRE(mr == 0 || a.kfid[mr - 1] <= t->res_ki[(size_t)b].kf_id, OV2_EINVAL,
+                    "ov2_btracker_temporal_keyframe: an item's anchor table holds a keyframe newer than its resident keyframe");
+    }
+    ov2_btracker::TkfPending &P = t->tpend;
+    P.n_active = n_active;
+    P.action.assign((size_t)n_active, OV2_TKF_NOT_REQUESTED);
+    const BtTkfLayout &L = t->tl;
+    uint8_t *h = t->htkf, *d = t->dtkf;
+    int n_done = 0;
+    for (int b = 0; b < n_active; b++) {
+        const int action = !do_h[b] ? OV2_TKF_NOT_REQUESTED : (t->res_iskf[(size_t)b] ? OV2_TKF_DONE : OV2_TKF_NOT_KEYFRAME);
+        P.action[(size_t)b] = (uint8_t)action;
+        h[L.t_act + (size_t)b] = action == OV2_TKF_DONE ? 1 : 0;
+        n_done += action == OV2_TKF_DONE ? 1 : 0;
+    }
+    memcpy(h + L.t_sel, t->anc_sel.data(), (size_t)t->batch);
+    t->slot_bytes = 0;
+    P.on = true;
+    if (!n_done) return OV2_OK;
+    // ---- the one enqueue ----
+    const hipStream_t s = ctx->stream;
+    const int nm = c.n_max;
+    TkfArgs a;
+    a.f = res_frames(t);
+    a.anc = tkf_anchors(t);
+    a.act = d + L.t_act; a.hdr = (FeKfHdr *)t->dfx; a.r_ki = (MonoKfInfo *)(t->dres + t->nl.r_ki);
+    a.kf_lmid = (int *)(t->depi + t->eL0.o_kl); a.kf_unpx = (float2 *)(t->depi + t->eL0.o_ku); a.kf_bv = (double *)(t->depi + t->eL0.o_kb);
+    a.n_max = nm;
+    a.tit = (int4 *)(d + L.w_tit); a.Twc = (double *)(d + L.w_Twc); a.ovf = (int *)(d + L.w_ovf); a.srcT = (double *)(d + L.w_srcT);
+    a.unpx = (float2 *)(d + L.w_un); a.bv = (double *)(d + L.w_bv); a.src_unpx = (float2 *)(d + L.w_sun); a.src_bv = (double *)(d + L.w_sbv);
+    a.src = (int *)(d + L.w_src); a.is_stereo = d + L.w_is;
+    a.src_kfid = (int *)(d + L.t_skf); a.tri_status = d + L.t_tst; a.tri_wpt = (const double *)(d + L.t_wpt);
+    a.rec = (ov2_temporal_keyframe_result *)(d + L.t_rec);
+    rc = [&]() -> int {
+        OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.t_up, hipMemcpyHostToDevice, s));
+        int r = res_push_sel(t, s);  if (r != OV2_OK) return r;
+        r = ov2_launch_tkf_anchor(s, a, n_active);  if (r != OV2_OK) return r;
+        r = ov2_launch_tkf_input(s, a, n_active);  if (r != OV2_OK) return r;
+        r = ov2_launch_triangulate(s, &p.tri, a.tit, a.Twc, a.srcT, (const float *)a.unpx, a.bv, nullptr, nullptr, (const float *)a.src_unpx,
+                                   a.src_bv, a.src, a.is_stereo, d + L.t_tst, (double *)(d + L.t_wpt), (double *)(d + L.t_inv), nm, n_active);
+        if (r != OV2_OK) return r;
+        r = ov2_launch_tkf_apply(s, a, n_active);  if (r != OV2_OK) return r;
+        OV2_HIP_CHECK(hipMemcpyAsync(h + L.t_io, d + L.t_io, L.t_down - L.t_io, hipMemcpyDeviceToHost, s));
+        return OV2_OK;
+    }();
+    if (rc != OV2_OK) { (void)hipStreamSynchronize(s); P.on = false; }      // nothing flips: every frame and table stays what it was
+    return rc;
+}
+
+int ov2_btracker_temporal_keyframe_end(ov2_btracker *t, ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h,
+                                       double *invdepth_h, int *src_kfid_h)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    ov2_btracker::TkfPending &P = t->tpend;
+    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe_end without ov2_btracker_temporal_keyframe_begin");
+    OV2_REQUIRE(results && tri_status_h && wpt_h && invdepth_h && src_kfid_h, OV2_EINVAL,
+                "ov2_btracker_temporal_keyframe_end: NULL result / output array");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    P.on = false;
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    const BtTkfLayout &L = t->tl;
+    const EpifLayout &E = t->eL0;
+    const uint8_t *h = t->htkf;
+    uint8_t *kh = t->kf_host.data();
+    const size_t nm = (size_t)t->cfg.n_max;
+    for (int b = 0; b < P.n_active; b++) {
+        ov2_temporal_keyframe_result &r = results[b];
+        memset(&r, 0, sizeof r);
+        r.action = P.action[(size_t)b];
+        if (r.action != OV2_TKF_DONE) continue;
+        memcpy(&r, h + L.t_rec + sizeof r * (size_t)b, sizeof r);
+        if (r.action != OV2_TKF_DONE) continue;                          // OV2_TKF_SRC_OVERFLOW: the device wrote nothing else
+        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
+        const size_t o = nm * (size_t)b, n = (size_t)*src.n;
+        const uint8_t *st = h + L.t_tst + o;
+        const double *w = (const double *)(h + L.t_wpt) + 3 * o;
+        memcpy(tri_status_h + o, st, n);
+        memcpy(wpt_h + 3 * o, w, 24 * n);
+        memcpy(invdepth_h + o, h + L.t_inv + 8 * o, 8 * n);
+        memcpy(src_kfid_h + o, h + L.t_skf + 4 * o, 4 * n);
+        // the anchor mirror, by k_tkf_anchor's rule on the keyframe mirror as it was before the call
+        int *kl = (int *)kh + o;
+        float *ku = (float *)(kh + (E.o_ku - E.o_kl)) + 2 * o;
+        double *kb = (double *)(kh + (E.o_kb - E.o_kl)) + 3 * o;
+        FeKfHdr &hd = t->kf_hdr[(size_t)b];
+        const int n_kf = std::min(std::max(hd.n_kf, 0), (int)nm), kfid = t->res_ki[(size_t)b].kf_id;
+        {
+            const AncHost A = anc_host(t, b, 0), N = anc_host(t, b, 1);
+            const int n_o = std::min(std::max(*A.n, 0), (int)nm), n_ro = std::min(std::max(*A.n_rows, 0), t->n_src_max);
+            if (n_ro > 0 && A.kfid[n_ro - 1] == kfid) {
+                memcpy(N.p, A.p, L.a_item);
+            } else {
+                std::vector<int> jn((size_t)n_kf, -1), ref((size_t)n_ro, 0), nr((size_t)n_ro, 0);
+                for (int i = 0; i < n_kf && n_ro > 0; i++) {
+                    const int *e = std::lower_bound(A.lmid, A.lmid + n_o, kl[i]);
+                    if (e == A.lmid + n_o || *e != kl[i]) continue;
+                    jn[(size_t)i] = (int)(e - A.lmid);
+                    ref[(size_t)std::min(std::max(A.row[e - A.lmid], 0), n_ro - 1)] = 1;
+                }
+                int live = 0;
+                for (int q = 0; q < n_ro; q++) { nr[(size_t)q] = live; live += ref[(size_t)q]; }
+                for (int i = 0; i < n_kf; i++) {
+                    const int j = jn[(size_t)i];
+                    N.lmid[i] = kl[i];
+                    N.row[i] = j >= 0 ? nr[(size_t)std::min(std::max(A.row[j], 0), n_ro - 1)] : live;
+                    memcpy(N.unpx + 2 * i, j >= 0 ? A.unpx + 2 * j : ku + 2 * i, 8);
+                    memcpy(N.bv + 3 * i, j >= 0 ? A.bv + 3 * j : kb + 3 * i, 24);
+                }
+                for (int q = 0; q < n_ro; q++) {
+                    if (!ref[(size_t)q]) continue;
+                    const int x = nr[(size_t)q];
+                    N.kfid[x] = A.kfid[q]; memcpy(N.Twc + 7 * x, A.Twc + 7 * q, 56); memcpy(N.Tcw + 7 * x, A.Tcw + 7 * q, 56);
+                }
+                N.kfid[live] = kfid; memcpy(N.Twc + 7 * live, hd.kf_Twc, 56); memcpy(N.Tcw + 7 * live, hd.kf_Tcw, 56);
+                *N.n = n_kf; *N.n_rows = live + 1;
+            }
+            t->anc_sel[(size_t)b] ^= 1;
+        }
+        // the frame's mirror as k_tkf_apply left the device, and the keyframe's without the OV2_TRI_REMOVE_OBS keypoints
+        memcpy(dst.px, src.px, 8 * n);
+        memcpy(dst.lmid, src.lmid, 4 * n);
+        std::vector<int> gone;
+        for (size_t i = 0; i < n; i++) {
+            const bool good = (st[i] & OV2_TRI_TEMPORAL_OK) != 0;
+            dst.is3d[i] = good || src.is3d[i] ? 1 : 0;
+            for (int k = 0; k < 3; k++) dst.wpt[3 * i + k] = good ? w[3 * i + k] : src.wpt[3 * i + k];
+            if (st[i] & OV2_TRI_REMOVE_OBS) gone.push_back(src.lmid[i]);
+        }
+        *dst.n = (int)n;
+        t->res_sel[(size_t)b] ^= 1;
+        t->res_ki[(size_t)b].kf_nb3dkps = r.nb3dkps;
+        if (!gone.empty()) {
+            std::sort(gone.begin(), gone.end());
+            int m = 0;
+            for (int j = 0; j < n_kf; j++) {
+                if (std::binary_search(gone.begin(), gone.end(), kl[j])) continue;
+                if (m != j) { kl[m] = kl[j]; memcpy(ku + 2 * m, ku + 2 * j, 8); memcpy(kb + 3 * m, kb + 3 * j, 24); }
+                m++;
+            }
+            hd.n_kf = m;
+        }
+    }
+    return OV2_OK;
+}
+
+int ov2_btracker_temporal_keyframe(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params, const uint8_t *do_h,
+                                   ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h,
+                                   int *src_kfid_h)
+{
+    OV2_REQUIRE(results && tri_status_h && wpt_h && invdepth_h && src_kfid_h, OV2_EINVAL,
+                "ov2_btracker_temporal_keyframe: NULL result / output array");
+    const int rc = ov2_btracker_temporal_keyframe_begin(t, n_active, params, do_h);
+    if (rc != OV2_OK) return rc;
+    return ov2_btracker_temporal_keyframe_end(t, results, tri_status_h, wpt_h, invdepth_h, src_kfid_h);
 }
 
 const ov2_pyr *ov2_btracker_cur_pyr(const ov2_btracker *t) { return t ? t->pyr[t->cur] : nullptr; }

@@ -1,7 +1,8 @@
 // trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
 // point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block, the three blocks of
-// ov2_btracker_track_mono, the block of ov2_btracker_create_keyframe, the two blocks of the resident frame and the block of
-// ov2_btracker_stereo_keyframe, each computed by one function of (batch, n_max) (the last one: and the grid's cells).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
+// ov2_btracker_track_mono, the block of ov2_btracker_create_keyframe, the two blocks of the resident frame, the block of
+// ov2_btracker_stereo_keyframe and the blocks of ov2_btracker_temporal_keyframe, each computed by one function of (batch, n_max) (the
+// last two: and the grid's cells / the anchor table's rows).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
 #include <stddef.h>
@@ -185,5 +186,46 @@ static inline BtSkfLayout bt_skf_layout(int batch, int n_max, int cells)
     L.w_st = c.take(slots); L.w_hp = c.take(slots); L.w_sk = c.take(slots); L.w_fl = c.take(slots); L.w_lk = c.take(slots);
     L.w_ok = c.take(slots); L.w_is = c.take(slots);
     L.w_cs = c.take(4 * ((size_t)cells + 1) * B); L.w_ck = c.take(4 * slots); L.dev_bytes = c.off;
+    return L;
+}
+
+// The blocks of ov2_btracker_temporal_keyframe (f23).  The ANCHOR TABLE: per item the first observing keyframe of every keypoint of
+// its latest keyframe, ITEM-MAJOR and double-buffered like the resident frame (a call reads an item's table from one buffer and
+// writes the next one into the other; which one is current is kept per item on the host and travels as one byte per item), with a
+// pinned host mirror of the same layout:
+//   one item    [n 4, padded to 16][lmid 4][row 4][unpx 8][bv 24 per slot, ascending by lmid]
+//               [n_rows 4, padded to 16][kfid 4][Twc 56][Tcw 56 per row, ascending by kfid], a_item bytes (a multiple of 256)
+// The control block of a call: one pinned host block [0, t_down) and its device mirror at the same offsets, ONE copy up ([0, t_up))
+// and ONE copy down ([t_io, t_down)); behind t_down the device-only work ranges of the kernels.
+//   up only     [act 1][asel 1 per item]: 1 where the item is asked and its frame is its keyframe; the buffer of its current table
+//   down only   [record 32 per item][wpt 24][invdepth 8][src_kfid 4][tri_status 1 per slot]
+//   device only [tri item 16][Twc 56][overflow 4 per item][source rows 112 per row (Twc, Tcw)]
+//               [unpx 8][bv 24][src_unpx 8][src_bv 24][src 4][is_stereo 1 per slot]
+// The block of ov2_btracker_set_anchor_poses (pinned, and its device mirror): [item 4][kfid 4][Twc 56 per triple], batch x n_src_max
+// triples at the most.
+#define BT_TKF_REC_BYTES 32          // sizeof(ov2_temporal_keyframe_result): trackb.hip asserts it
+struct BtTkfLayout {
+    size_t a_n, a_lm, a_row, a_un, a_bv, a_nr, a_kf, a_Twc, a_Tcw, a_item, buf_bytes, anchor_bytes;
+    size_t t_act, t_sel, t_up, t_io, t_rec, t_wpt, t_inv, t_skf, t_tst, t_down;
+    size_t w_tit, w_Twc, w_ovf, w_srcT, w_un, w_bv, w_sun, w_sbv, w_src, w_is, dev_bytes;
+    size_t p_item, p_kfid, p_Twc, pose_bytes;
+};
+static inline BtTkfLayout bt_tkf_layout(int batch, int n_max, int n_src_max)
+{
+    const size_t B = (size_t)batch, nm = (size_t)n_max, ns = (size_t)n_src_max, slots = nm * B, rows = ns * B;
+    BtTkfLayout L;
+    StageCursor f(16);
+    L.a_n = f.take(4); L.a_lm = f.take(4 * nm); L.a_row = f.take(4 * nm); L.a_un = f.take(8 * nm); L.a_bv = f.take(24 * nm);
+    L.a_nr = f.take(4); L.a_kf = f.take(4 * ns); L.a_Twc = f.take(56 * ns); L.a_Tcw = f.take(56 * ns);
+    L.a_item = up256(f.off); L.buf_bytes = L.a_item * B; L.anchor_bytes = 2 * L.buf_bytes;
+    StageCursor c(256);
+    L.t_act = c.take(B); L.t_sel = c.take(B); L.t_up = c.off;
+    L.t_io = L.t_rec = c.take(BT_TKF_REC_BYTES * B); L.t_wpt = c.take(24 * slots); L.t_inv = c.take(8 * slots); L.t_skf = c.take(4 * slots);
+    L.t_tst = c.take(slots); L.t_down = c.off;
+    L.w_tit = c.take(16 * B); L.w_Twc = c.take(56 * B); L.w_ovf = c.take(4 * B); L.w_srcT = c.take(112 * rows);
+    L.w_un = c.take(8 * slots); L.w_bv = c.take(24 * slots); L.w_sun = c.take(8 * slots); L.w_sbv = c.take(24 * slots);
+    L.w_src = c.take(4 * slots); L.w_is = c.take(slots); L.dev_bytes = c.off;
+    StageCursor q(256);
+    L.p_item = q.take(4 * rows); L.p_kfid = q.take(4 * rows); L.p_Twc = q.take(56 * rows); L.pose_bytes = q.off;
     return L;
 }

@@ -1136,6 +1136,103 @@ class LockstepTracker:
                                                         C.byref(hi)))
         return dict(kf_id=i.value, kf_time=t.value, kf_nb3dkps=n.value, has_info=hi.value)
 
+    # ---- Mapper::triangulateTemporal on the resident keyframe (ov2_btracker_temporal_keyframe) and the anchor table -----------------
+    def reserveAnchors(self, n_src_max):
+        """allocates the anchor block with n_src_max rows per item (ov2_btracker_reserve_anchors); the first temporalKeyframe does
+        it otherwise.  Another n_src_max afterwards is refused."""
+        L.check(self.lib.ov2_btracker_reserve_anchors(self.h_trk, int(n_src_max)))
+        self._n_src_max = int(n_src_max)
+
+    def setAnchors(self, item, lmid, kfid, unpx, bv, row_kfid, row_Twc):
+        """installs the whole anchor table of item `item` (ov2_btracker_set_anchors), as setKeyframe installs a keyframe: per keypoint
+        of the latest keyframe lmid (n,) strictly ascending, kfid (n,) its first observing keyframe, unpx (n, 2) and bv (n, 3) its
+        keypoint there; per keyframe referred to row_kfid (r,) strictly ascending and row_Twc (r, 7).  After the map culled a
+        keyframe, or for a tracker that joins a running map.  Between steps only."""
+        lm = np.ascontiguousarray(lmid, np.int32).reshape(-1)
+        kf = np.ascontiguousarray(kfid, np.int32).reshape(-1)
+        un = np.ascontiguousarray(unpx, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(bv, np.float64).reshape(-1, 3)
+        rk = np.ascontiguousarray(row_kfid, np.int32).reshape(-1)
+        rT = np.ascontiguousarray(row_Twc, np.float64).reshape(-1, 7)
+        if not (len(lm) == len(kf) == len(un) == len(b)) or len(rk) != len(rT):
+            raise ValueError("one kfid, unpx and bv per lmid, one pose per row")
+        L.check(self.lib.ov2_btracker_set_anchors(self.h_trk, int(item), len(lm), _ptr(lm), _ptr(kf), _ptr(un), _ptr(b), len(rk), _ptr(rk), _ptr(rT)))
+
+    def getAnchors(self, item, from_device=False):
+        """the anchor table of item `item` -> dict(n, lmid (n,), kfid (n,), unpx (n, 2), bv (n, 3), n_rows, row_kfid (r,), row_Twc (r, 7),
+        row_Tcw (r, 7)): the host mirror, or with from_device True copied down from the device block"""
+        ns = getattr(self, "_n_src_max", L.OV2_TKF_MAX_ROWS)
+        n, nr = C.c_int(), C.c_int()
+        lm, kf = np.zeros(self.n_max, np.int32), np.zeros(self.n_max, np.int32)
+        un, b = np.zeros((self.n_max, 2), np.float32), np.zeros((self.n_max, 3), np.float64)
+        rk, rT, rI = np.zeros(ns, np.int32), np.zeros((ns, 7), np.float64), np.zeros((ns, 7), np.float64)
+        L.check(self.lib.ov2_btracker_get_anchors(self.h_trk, int(item), int(bool(from_device)), C.byref(n), _ptr(lm), _ptr(kf), _ptr(un), _ptr(b),
+                                                  C.byref(nr), _ptr(rk), _ptr(rT), _ptr(rI)))
+        k, r = n.value, nr.value
+        return dict(n=k, lmid=lm[:k].copy(), kfid=kf[:k].copy(), unpx=un[:k].copy(), bv=b[:k].copy(), n_rows=r, row_kfid=rk[:r].copy(),
+                    row_Twc=rT[:r].copy(), row_Tcw=rI[:r].copy())
+
+    def setAnchorPoses(self, triples):
+        """the poses local BA moved (ov2_btracker_set_anchor_poses_batch): triples is a list of (item, kfid, Twc (7,)); one upload and
+        one launch for all of them.  -> the number of triples whose kfid anchors nothing in its item (ignored)"""
+        it = np.ascontiguousarray([t[0] for t in triples], np.int32).reshape(-1)
+        kf = np.ascontiguousarray([t[1] for t in triples], np.int32).reshape(-1)
+        T = np.ascontiguousarray([t[2] for t in triples], np.float64).reshape(-1, 7)
+        ign = C.c_int()
+        L.check(self.lib.ov2_btracker_set_anchor_poses_batch(self.h_trk, len(it), _ptr(it), _ptr(kf), _ptr(T), C.byref(ign)))
+        return ign.value
+
+    def _tkf_outputs(self, na, out):
+        """the arrays _end scatters into (the caller's, so that untouched slots stay what they were, or fresh zeros)"""
+        shapes = dict(tri_status=((self.batch, self.n_max), np.uint8), wpt=((self.batch, self.n_max, 3), np.float64),
+                      invdepth=((self.batch, self.n_max), np.float64), src_kfid=((self.batch, self.n_max), np.int32))
+        o = {}
+        for k, (shape, dt) in shapes.items():
+            a = None if out is None else out.get(k)
+            if a is None:
+                a = np.zeros(shape, dt)
+            elif a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError("out[%r] must be a contiguous %s array of shape %r" % (k, np.dtype(dt).name, shape))
+            o[k] = a
+        return o, (L.TemporalKeyframeResult * max(1, na))()
+
+    def _tkf_dicts(self, R, na, o):
+        return [{k: int(getattr(R[b], k)) for k, _ in L.TemporalKeyframeResult._fields_} for b in range(na)], o
+
+    def temporalKeyframe(self, n_active, do, params, out=None):
+        """Mapper::triangulateTemporal on the resident keyframe of the items of [0, n_active) with do[b] != 0 (normally: the item's
+        last createKeyframe action was OV2_CKF_CREATED; in stereo behind stereoKeyframe), in one enqueue and one synchronisation
+        (ov2_btracker_temporal_keyframe): the item's anchor table moves on to this keyframe, every 2-D slot the keyframe holds whose
+        anchor is an earlier keyframe is triangulated against it, every OV2_TRI_TEMPORAL_OK slot becomes 3-D in the resident
+        frame, every OV2_TRI_REMOVE_OBS slot leaves the resident keyframe, kf_nb3dkps is recounted.  params:
+        mapper.temporal_keyframe_params(...); out: dict of arrays to scatter into (missing ones are zeros).  Points first seen at a
+        keyframe for which this call was not run anchor at the next one for which it is.
+        -> (records, out): records[b] = dict(action L.OV2_TKF_*, n, n_candidates, n_temporal_good, n_remove_obs, n_no_motion, nb3dkps,
+        n_rows); out = dict(tri_status, wpt, invdepth, src_kfid) in the slot layout of the resident frame, written for the items with
+        action OV2_TKF_DONE only."""
+        na, d = self._skf_do(n_active, do)
+        o, R = self._tkf_outputs(na, out)
+        L.check(self.lib.ov2_btracker_temporal_keyframe(self.h_trk, na, C.byref(params), _ptr(d), R, _ptr(o["tri_status"]), _ptr(o["wpt"]),
+                                                        _ptr(o["invdepth"]), _ptr(o["src_kfid"])))
+        self._n_src_max = int(params.n_src_max)
+        return self._tkf_dicts(R, na, o)
+
+    def temporalKeyframeBegin(self, n_active, do, params):
+        """first half of temporalKeyframe: enqueue and return; temporalKeyframeEnd finishes it"""
+        na, d = self._skf_do(n_active, do)
+        L.check(self.lib.ov2_btracker_temporal_keyframe_begin(self.h_trk, na, C.byref(params), _ptr(d)))
+        self._n_src_max = int(params.n_src_max)
+        self._tkf_pending = (na, params)
+
+    def temporalKeyframeEnd(self, out=None):
+        """second half of temporalKeyframe -> (records, out)"""
+        na = self._tkf_pending[0] if getattr(self, "_tkf_pending", None) else 0          # (no open call: the library refuses)
+        o, R = self._tkf_outputs(na, out)
+        L.check(self.lib.ov2_btracker_temporal_keyframe_end(self.h_trk, R, _ptr(o["tri_status"]), _ptr(o["wpt"]), _ptr(o["invdepth"]),
+                                                            _ptr(o["src_kfid"])))
+        self._tkf_pending = None
+        return self._tkf_dicts(R, na, o)
+
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
         pri = np.empty((n, 2), np.float32)

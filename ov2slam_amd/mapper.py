@@ -68,6 +68,16 @@ def stereo_keyframe_params(right_calib, tri, *, img_w, img_h, Tcic0, rect, Frl=N
     return p
 
 
+def temporal_keyframe_params(tri, *, n_src_max=16):
+    """ov2_temporal_keyframe_params of LockstepTracker.temporalKeyframe: `tri`, the ov2_tri_params of tri_params() as they are
+    (tri.stereo is read for the no-motion skip; the stereo fields are not read), and n_src_max, the rows of an item's anchor table:
+    the keyframes the keypoints of one keyframe may anchor at (1 .. L.OV2_TKF_MAX_ROWS; fixed by the tracker's first call)."""
+    p = L.TemporalKeyframeParams()
+    p.tri = _as_params(tri)
+    p.n_src_max = int(n_src_max)
+    return p
+
+
 def _as_params(params):
     if isinstance(params, L.TriParams):
         return params
