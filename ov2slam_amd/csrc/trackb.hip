@@ -27,38 +27,19 @@
 // and the keyframe decision (mono.hip: k_mono_apply in front, k_mono_pack and fkf.hip's k_fkf_parallax behind), the frame pose, the
 // motion state and the keyframe's id / time / nb3dkps resident on the device with host mirrors; byte-equal to ov2_motion_apply_batch,
 // the step, ov2_motion_update_batch and ov2_kf_decision_batch (tests/test_gpu_trackmono.py).
-// ov2_btracker_create_keyframe is MapManager::createKeyframe for the items such a step asked to become keyframes (createkf.hip:
-// k_ckf_prepare in front, k_ckf_append behind the detector's launches, k_ckf_install behind computeKeypoint and BRIEF): the new frame
-// becomes the item's resident keyframe without leaving the device; byte-equal to the separate describe / detect / computeKeypoints
-// calls, a host sort and ov2_btracker_set_keyframe + ov2_btracker_set_keyframe_info per item (tests/test_gpu_createkf.py).
+// The keyframe calls on this state (ov2_btracker_create_keyframe, _stereo_keyframe, _temporal_keyframe and the anchor table) are
+// trackb_keyframe.hip; struct ov2_btracker, the block types and the helpers both files use are declared in trackb.hpp.
 // The resident frame (ov2_btracker_set_frame / _get_frame / _update_frame, ov2_btracker_track_mono_resident, create_keyframe with
 // px_h == NULL; resident.hip): the current frame of every item -- px, lmid, is3d, wpt per slot -- stays on the device between those
 // calls, in a block of two buffers per item with a pinned mirror of the same layout.  k_res_stage writes it where the step's kernels
 // read their per-slot inputs (which are then not copied up), k_res_carry writes the frame the step leaves by k_mono_pack's rule,
 // k_res_update applies what the map did, k_res_ckf_in / k_res_adopt put create_keyframe on it; byte-equal to the same cycle on frames
 // kept on the host (tests/test_gpu_resident.py; tests/resident_ref.py is that cycle).
-#include "common.hpp"
-#include "keypoint_dev.hpp"
-#include "pose_dev.hpp"
-#include "frameepi_dev.hpp"
-#include "mono_dev.hpp"
-#include "detect_dev.hpp"
-#include "createkf_dev.hpp"
-#include "resident_dev.hpp"
-#include "stereokf_dev.hpp"
-#include "temporalkf_dev.hpp"
-#include "mvg_dev.hpp"
-#include "fkf_dev.hpp"
-#include "trackb_layout.hpp"
+#include "trackb.hpp"
 #include <algorithm>
 #include <cmath>
-#include <deque>
 #include <new>
 #include <vector>
-
-#define BT_SETS 8       // pyramid sets in rotation: cur, prev, the one being prepared for the next frame, five of slack for the mapper
-                        // context (a keyframe's pyramids outlive it by BT_SETS - 1 steps: the keyframe period of the shipped parameter files)
-#define BT_IMG_SETS 3   // staging sets: frame f (read by its pre-processing), f + 1 (arriving), f + 2 (being filled by the host)
 
 static_assert(sizeof(PoseOut) == BT_POSE_OUT_BYTES, "trackb_layout.hpp: the pose block's record");
 static_assert(sizeof(EpifOut) == BT_EPIF_OUT_BYTES, "trackb_layout.hpp: the epipolar block's record");
@@ -70,58 +51,100 @@ static_assert(sizeof(ov2_stereo_keyframe_result) == BT_SKF_REC_BYTES && sizeof(S
 static_assert(sizeof(ov2_temporal_keyframe_result) == BT_TKF_REC_BYTES, "trackb_layout.hpp: the temporal keyframe block's record");
 static_assert(sizeof(ov2_resident_op) == BT_RES_OP_BYTES && sizeof(ov2_resident_update_result) == BT_RES_REC_BYTES, "trackb_layout.hpp: the resident frame's records");
 
-// A block the host fills and reads and the kernels read and write: pinned + mapped, reached by the kernels through its device alias
-// (zero copy), or mirrored on the device with a copy up before the kernels and a copy down behind them.
-struct IoBlock {
-    uint8_t *h = nullptr, *d = nullptr, *k = nullptr;    // the pinned block; its device mirror (NULL with zero copy); what the kernels dereference
-    size_t bytes = 0;
-    // decide: the tracker's first block takes the alias when there is one and sets zero_copy; the later blocks follow it
-    int alloc(size_t n, bool &zero_copy, bool decide, const char *who)
-    {
-        hipError_t e = hipHostMalloc((void **)&h, n, hipHostMallocMapped);
-        void *alias = nullptr;
-        if (e == hipSuccess && decide) {
-            zero_copy = hipHostGetDevicePointer(&alias, h, 0) == hipSuccess && alias;
-            if (!zero_copy) (void)hipGetLastError();
-        }
-        if (e == hipSuccess && !zero_copy) { e = hipMalloc((void **)&d, n); alias = d; }
-        else if (e == hipSuccess && !decide) e = hipHostGetDevicePointer(&alias, h, 0);
-        if (e != hipSuccess || !alias) {
-            release();
-            (void)hipGetLastError();
-            ov2_set_error("%s: %s", who, hipGetErrorString(e));
-            return OV2_ENOMEM;
-        }
-        memset(h, 0, n);
-        k = (uint8_t *)alias; bytes = n;
-        return OV2_OK;
+// ---- the block types (trackb.hpp) ----
+int IoBlock::alloc(size_t n, bool &zero_copy, bool decide, const char *who)
+{
+    hipError_t e = hipHostMalloc((void **)&h, n, hipHostMallocMapped);
+    void *alias = nullptr;
+    if (e == hipSuccess && decide) {
+        zero_copy = hipHostGetDevicePointer(&alias, h, 0) == hipSuccess && alias;
+        if (!zero_copy) (void)hipGetLastError();
     }
-    void release()
-    {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = k = nullptr; bytes = 0;
+    if (e == hipSuccess && !zero_copy) { e = hipMalloc((void **)&d, n); alias = d; }
+    else if (e == hipSuccess && !decide) e = hipHostGetDevicePointer(&alias, h, 0);
+    if (e != hipSuccess || !alias) {
+        release();
+        (void)hipGetLastError();
+        ov2_set_error("%s: %s", who, hipGetErrorString(e));
+        return OV2_ENOMEM;
     }
-    // [0, n) up, [from, to) down: nothing to do when the kernels work on the pinned block itself
-    int upload(hipStream_t s, size_t n) const { return upload(s, 0, n); }
-    int upload(hipStream_t s, size_t from, size_t to) const
-    {
-        if (d && to > from) OV2_HIP_CHECK(hipMemcpyAsync(d + from, h + from, to - from, hipMemcpyHostToDevice, s));
-        return OV2_OK;
-    }
-    int download(hipStream_t s, size_t from, size_t to) const
-    {
-        if (d) OV2_HIP_CHECK(hipMemcpyAsync(h + from, d + from, to - from, hipMemcpyDeviceToHost, s));
-        return OV2_OK;
-    }
-};
+    memset(h, 0, n);
+    k = (uint8_t *)alias; bytes = n;
+    return OV2_OK;
+}
+void IoBlock::release()
+{
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    h = d = k = nullptr; bytes = 0;
+}
+int IoBlock::upload(hipStream_t s, size_t from, size_t to) const
+{
+    if (d && to > from) OV2_HIP_CHECK(hipMemcpyAsync(d + from, h + from, to - from, hipMemcpyHostToDevice, s));
+    return OV2_OK;
+}
+int IoBlock::download(hipStream_t s, size_t from, size_t to) const
+{
+    if (d) OV2_HIP_CHECK(hipMemcpyAsync(h + from, d + from, to - from, hipMemcpyDeviceToHost, s));
+    return OV2_OK;
+}
+
+int DevBlock::fail(hipError_t e, const char *who)
+{
+    release();
+    (void)hipGetLastError();
+    ov2_set_error("%s: %s", who, hipGetErrorString(e));
+    return OV2_ENOMEM;
+}
+int DevBlock::alloc(size_t host_bytes, size_t n, hipStream_t s, const char *who)
+{
+    release();
+    const hipError_t e = host_bytes ? hipHostMalloc((void **)&h, host_bytes, hipHostMallocDefault) : hipSuccess;
+    if (e != hipSuccess) return fail(e, who);
+    if (h) memset(h, 0, host_bytes);
+    return grow(n, s, who);
+}
+int DevBlock::grow(size_t need, hipStream_t s, const char *who)
+{
+    OV2_HIP_CHECK(hipStreamSynchronize(s));                              // (an earlier call's kernels have long finished: its _end waited)
+    if (d) (void)hipFree(d);
+    d = nullptr; dev_bytes = 0;
+    hipError_t e = hipMalloc((void **)&d, need);
+    if (e == hipSuccess) e = hipMemsetAsync(d, 0, need, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(e, who);
+    dev_bytes = need;
+    return OV2_OK;
+}
+void DevBlock::release()
+{
+    if (h) (void)hipHostFree(h);
+    if (d) (void)hipFree(d);
+    h = d = nullptr; dev_bytes = 0;
+}
+int DevBlock::up(hipStream_t s, size_t from, size_t to) const
+{
+    if (to > from) OV2_HIP_CHECK(hipMemcpyAsync(d + from, h + from, to - from, hipMemcpyHostToDevice, s));
+    return OV2_OK;
+}
+int DevBlock::down(hipStream_t s, size_t from, size_t to) const
+{
+    if (to > from) OV2_HIP_CHECK(hipMemcpyAsync(h + from, d + from, to - from, hipMemcpyDeviceToHost, s));
+    return OV2_OK;
+}
+int alloc_all(std::initializer_list<DevBlockSpec> blocks, hipStream_t s, const char *who)
+{
+    int rc = OV2_OK;
+    for (const DevBlockSpec &q : blocks) if (rc == OV2_OK) rc = q.b->alloc(q.host_bytes, q.dev_bytes, s, who);
+    if (rc != OV2_OK) for (const DevBlockSpec &q : blocks) q.b->release();
+    return rc;
+}
 
 // One step as its _begin call describes it.  Each form includes the one before it: map -- the priors come from the device (wpt_h /
 // is3d_h / Tcw_h; prior_xy_h / has_prior_h are unused); pose -- the pose of ov2_btracker_track_frame_pose follows in the same
 // enqueue; epi -- the filter of ov2_btracker_track_frame_epi_pose runs between the pose's select and its pack.
 // mono -- ov2_btracker_track_mono: the epi form (or, with doepipolar == 0, the pose form) between the motion model and the keyframe
 // decision; track_frame_begin resolves it to that inner form plus Pending::mono.
-enum StepForm { STEP_PLAIN = 0, STEP_MAP, STEP_POSE, STEP_EPI, STEP_MONO };
 struct StepArgs {
     StepForm form = STEP_PLAIN;
     int n_active = 0, stride = 0, klt_use_prior = 0;
@@ -133,140 +156,6 @@ struct StepArgs {
     const ov2_frame_epi_pose_params *epp = nullptr; const ov2_frame_epi_pose_input *ein = nullptr;         // epi
     const ov2_track_mono_params *mp = nullptr; const ov2_track_mono_input *min = nullptr;                  // mono (epp / ein: their step halves)
     bool resident = false;            // mono on the resident frame: n_h holds the mirror's counts, the point arrays are NULL
-};
-
-// ov2_btracker_last_pose_inputs / ov2_btracker_last_epi_inputs: what the last finished step of the kind fed its chain.  Per item the
-// counts (ncur: entries of the slot list -- the filter's packed frame; the pose set, so m again) and, for an item the 33 % rule
-// re-ran (host), the slot list and the table of the second run -- the device block still holds those of the first
-struct LastInputs {
-    bool on = false, chain = false;                  // a step has been finished; its chain ran (not a first frame / nothing tracked)
-    std::vector<int> ncur, m, rows;
-    std::vector<std::vector<int>> slot, samples;
-    std::vector<uint8_t> host;
-    void open(size_t B, bool tracked)
-    {
-        on = true; chain = tracked;
-        ncur.assign(B, 0); m.assign(B, 0); rows.assign(B, 0); host.assign(B, 0); slot.resize(B); samples.resize(B);
-    }
-};
-
-struct ov2_btracker {
-    ov2_ctx *ctx = nullptr;
-    ov2_tracker_config cfg;
-    int batch = 0;
-    // pyramid sets in rotation (cur_pyr_, prev_pyr_, ...): a keyframe's pyramids stay valid for BT_SETS - 1 more steps (BT_SETS - 2
-    // when the next frame is prepared ahead), so the mapper contexts that stereo-match it rarely hold the SLAM thread up (with two
-    // sets 12 % of the lock-step wall clock was that wait)
-    ov2_pyr *pyr[BT_SETS] = {};
-    std::vector<ov2_pyr *> view[BT_SETS];    // batch-1 aliases of the items (stereo matching, the p3p retry, single-item detection)
-    int cur = 0;                       // index of cur_pyr_ (= (frames - 1) % BT_SETS); prev_pyr_ = pyr[(cur + BT_SETS - 1) % BT_SETS]
-    int prev() const { return (cur + BT_SETS - 1) % BT_SETS; }
-    long frames = 0;
-    // frames: pinned staging sets + their device mirrors; a copy stream for uploads and a stream for pre-processing started ahead
-    uint8_t *himg[BT_IMG_SETS] = {nullptr, nullptr, nullptr}, *dimg[BT_IMG_SETS] = {nullptr, nullptr, nullptr};
-    size_t img_pitch = 0, img_bytes = 0;          // per item (trackb_layout.hpp)
-    // ov2_btracker_set_rectification: the uploads of set `which` go to draw[which]; the pre-processing of the set starts with k_remap
-    // draw[which] -> dimg[which], so dimg holds the RECTIFIED frames.  used_ev[which] is recorded behind that pre-processing: it covers
-    // the remap's reads of draw[which] as it covers the reads of dimg[which]
-    const ov2_rectmap *rect = nullptr;
-    uint8_t *draw[BT_IMG_SETS] = {nullptr, nullptr, nullptr};      // allocated by the first ov2_btracker_set_rectification
-    uint8_t *upload_dst(int which) const { return rect ? draw[which] : dimg[which]; }
-    hipStream_t cs = nullptr, ps = nullptr;
-    ov2_ctx side;                                 // what the launchers of clahe.hip / pyramid.hip see when they enqueue on `ps`
-    uint8_t *lut = nullptr;                       // CLAHE tables of a step (the context's scratch is busy with the detector on the main stream)
-    hipEvent_t up_ev[BT_IMG_SETS] = {nullptr, nullptr, nullptr};     // set `which` has arrived in dimg[which] (copy stream)
-    hipEvent_t used_ev[BT_IMG_SETS] = {nullptr, nullptr, nullptr};   // the kernels that read dimg[which] are done (main or prep stream)
-    int up_n[BT_IMG_SETS] = {0, 0, 0};            // items covered by the pending upload of the set (0: none pending)
-    // Frame k lives in pyramid set k % BT_SETS.  pre_count = frames whose preprocessImage has been enqueued (ahead or in order);
-    // frames prepared ahead wait in prepq (at most two: the one about to be tracked and the one after it)
-    struct Prep { int which, n, set; };
-    std::deque<Prep> prepq;
-    long pre_count = 0;
-    // the four blocks the host and the kernels share (IoBlock; their sections: trackb_layout.hpp).  The point block decides zero_copy
-    // for all of them; the map, pose and epipolar blocks are allocated by the first step of their form
-    IoBlock pt, map, pose, epi, mono;
-    bool zero_copy = false;
-    BtPointLayout pl; BtMapLayout ml; BtPoseLayout ql; BtEpiLayout el; BtMonoLayout nl;
-    // ov2_btracker_track_mono: the resident block (frame pose, motion state, keyframe info per item) with its host mirrors, and the
-    // work block of k_mono_pack / k_fkf_parallax (both device only), allocated by the first setter or step of the kind
-    uint8_t *dres = nullptr, *dmw = nullptr;
-    std::vector<double> res_T, res_kt;
-    std::vector<ov2_motion_state> res_st;
-    std::vector<MonoKfInfo> res_ki;
-    bool has_calib = false;
-    KpCalib calib;
-    std::vector<int> last_n;           // per item: keypoints of the last track_frame (0 before / after a call that tracked nothing)
-    std::vector<int> last_pn;          // the same whether or not a calibration is set (ov2_btracker_last_priors)
-    // ov2_btracker_track_frame_pose: the chain's block at capacity and the pack's lists (device only, grow-only; not the context's
-    // scratch, which other calls use on the same stream)
-    uint8_t *dwork = nullptr;
-    size_t work_bytes = 0;
-    LastInputs lp;
-    PoseLayout lp_L;                                  // the chain's layout in the last finished pose step
-    // ov2_btracker_track_frame_epi_pose / ov2_btracker_set_keyframe: the epipolar side, allocated by the first of either.
-    //   depi   the filter's block (EpifLayout at capacity: batch x n_max slots, batch x n_rows rows; device only, grow-only).  Its
-    //          inputs [0, o_up) do not depend on n_rows, so the resident keyframe arrays stay where they are when a step asks for
-    //          more rows and the block is grown (they are then copied again from kf_host).
-    //   dfx    the index block (device only)
-    uint8_t *depi = nullptr, *dfx = nullptr;
-    size_t depi_bytes = 0;
-    EpifLayout eL0;                                   // the layout with no rows: where the keyframe arrays lie
-    std::vector<uint8_t> kf_host;                     // host copy of the block's [o_kl, o_up)
-    std::vector<FeKfHdr> kf_hdr;
-    FeStep fe;                                        // the arguments of the step being enqueued
-    LastInputs le;
-    EpifLayout le_L;                                  // the filter's layout in the last finished epipolar step
-    // keyframe detection: device mirrors of the items' current keypoints and of the detector's output, pinned staging
-    uint8_t *d_det = nullptr, *h_det = nullptr; size_t det_in_bytes = 0;
-    float *d_out = nullptr; uint8_t *h_out = nullptr; int out_cap = 0;
-    uint8_t *d_roi = nullptr;                     // detectGFTT: device copy of the caller's roi mask (w x h, allocated with the first one)
-    // a step between ov2_btracker_track_frame_begin and _end: what _end needs to finish it
-    struct Pending { bool on = false, tracked = false; StepForm form = STEP_PLAIN; int n_active = 0, use_prior = 0;
-                     const float *kps = nullptr; const uint8_t *has_prior = nullptr; std::vector<int> n;
-                     // pose and epi: the settings and the per-item inputs _end needs again (the filter's per-item inputs stay in the
-                     // epipolar block, which the device only reads)
-                     ov2_frame_pose_params pp; PoseLayout L; std::vector<double> Twc; std::vector<uint8_t> req;
-                     std::vector<unsigned long long> seed;
-                     ov2_epifilter_params ep; EpifLayout eL;
-                     // mono: the step runs between the motion model and the decision; ran: not the tracker's first frame
-                     bool mono = false, mono_ran = false; ov2_fkf_params fkf; std::vector<double> time;
-                     std::vector<int> frame_id, localba;
-                     bool resident = false; } pend;       // the frame is the resident one; k_res_carry wrote the next one
-    // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
-    int raw_which = -1, raw_n = 0;
-    // ov2_btracker_create_keyframe, allocated by its first call: the I/O block (pinned, and its device mirror at the same offsets:
-    // BtCkfLayout) and the detector's work block (device only, grow-only: the output lists, then one pass's maps, candidates and
-    // free-cell lists)
-    BtCkfLayout cl;
-    uint8_t *hckf = nullptr, *dckf = nullptr, *dckw = nullptr;
-    size_t ckw_bytes = 0;
-    struct CkfPending { bool on = false, det = false; int n_active = 0, mode = 0, ncells = 0; ov2_create_keyframe_params p;
-                        double *quality = nullptr; int *fast_th = nullptr; std::vector<uint8_t> flag; std::vector<int> nkfid;
-                        std::vector<double> time; bool resident = false; } cpend;
-    // the resident frame (f21), allocated by its first use: the frame block (two buffers of `batch` items: BtResLayout) with its
-    // pinned host mirror of the same layout, the control block of a call (pinned, and its device mirror), and per item the buffer
-    // that holds the current frame
-    BtResLayout rl;
-    uint8_t *dfr = nullptr, *hfr = nullptr, *drc = nullptr, *hrc = nullptr;
-    std::vector<uint8_t> res_sel;
-    size_t slot_bytes = 0;            // ov2_btracker_last_slot_bytes
-    // ov2_btracker_stereo_keyframe (f22), allocated by its first call: the I/O block (pinned [0, s_down), and its device mirror with the
-    // work ranges behind: BtSkfLayout, regrown when a call's grid has more cells), per item whether its resident frame is its resident
-    // keyframe, and the call between _begin and _end
-    BtSkfLayout sl;
-    int skf_cells = -1;
-    uint8_t *hskf = nullptr, *dskf = nullptr;
-    std::vector<uint8_t> res_iskf;
-    struct SkfPending { bool on = false; int n_active = 0; std::vector<uint8_t> action; } spend;
-    // ov2_btracker_temporal_keyframe (f23), allocated by the first call that needs it: the anchor block (two buffers, item-major) and
-    // its pinned mirror, per item the buffer of its current table, the call's I/O block (pinned [0, t_down), and its device mirror with
-    // the work ranges behind), the block of ov2_btracker_set_anchor_poses, and the call between _begin and _end
-    BtTkfLayout tl;
-    int n_src_max = 0;
-    uint8_t *danc = nullptr, *hanc = nullptr, *htkf = nullptr, *dtkf = nullptr, *hap = nullptr, *dap = nullptr;
-    std::vector<uint8_t> anc_sel;
-    struct TkfPending { bool on = false; int n_active = 0; std::vector<uint8_t> action; } tpend;
-    bool open_call() const { return pend.on || cpend.on || spend.on || tpend.on; }
 };
 
 static void btracker_free(ov2_btracker *t)
@@ -288,32 +177,33 @@ static void btracker_free(ov2_btracker *t)
         if (t->draw[i]) (void)hipFree(t->draw[i]);
     }
     for (IoBlock *b : {&t->pt, &t->map, &t->pose, &t->epi, &t->mono}) b->release();
-    if (t->dres) (void)hipFree(t->dres);
-    if (t->dmw) (void)hipFree(t->dmw);
-    if (t->dwork) (void)hipFree(t->dwork);
     if (t->depi) (void)hipFree(t->depi);
-    if (t->dfx) (void)hipFree(t->dfx);
-    if (t->h_det) (void)hipHostFree(t->h_det);
-    if (t->d_det) (void)hipFree(t->d_det);
-    if (t->h_out) (void)hipHostFree(t->h_out);
-    if (t->d_out) (void)hipFree(t->d_out);
-    if (t->d_roi) (void)hipFree(t->d_roi);
-    if (t->hckf) (void)hipHostFree(t->hckf);
-    if (t->dckf) (void)hipFree(t->dckf);
-    if (t->dckw) (void)hipFree(t->dckw);
-    if (t->dfr) (void)hipFree(t->dfr);
-    if (t->hfr) (void)hipHostFree(t->hfr);
-    if (t->drc) (void)hipFree(t->drc);
-    if (t->hrc) (void)hipHostFree(t->hrc);
-    if (t->hskf) (void)hipHostFree(t->hskf);
-    if (t->dskf) (void)hipFree(t->dskf);
-    if (t->danc) (void)hipFree(t->danc);
-    if (t->hanc) (void)hipHostFree(t->hanc);
-    if (t->dtkf) (void)hipFree(t->dtkf);
-    if (t->htkf) (void)hipHostFree(t->htkf);
-    if (t->dap) (void)hipFree(t->dap);
-    if (t->hap) (void)hipHostFree(t->hap);
+    for (DevBlock *b : {&t->res, &t->mw, &t->work, &t->fx, &t->det, &t->out, &t->roi, &t->ckf, &t->ckw, &t->fr, &t->ctl, &t->skf, &t->anc, &t->tkf,
+                        &t->ap})
+        b->release();
     delete t;
+}
+
+// What the _begin of a call of kind `who` refuses: any open call.  name: ov2_btracker_<name>_begin / _end; sign: what this kind's
+// _begin puts in front when ANOTHER kind is open.
+static const struct { const char *name, *sign; } k_calls[] = {
+    {nullptr, nullptr},
+    {"track_frame", "ov2_btracker_track_frame_begin"},
+    {"create_keyframe", "ov2_btracker_create_keyframe_begin"},
+    {"stereo_keyframe", "ov2_btracker_stereo_keyframe"},
+    {"temporal_keyframe", "ov2_btracker_temporal_keyframe"},
+};
+int begin_guard(const ov2_btracker *t, OpenCall who)
+{
+    const OpenCall o = t->open;
+    if (o == CALL_NONE) return OV2_OK;
+    const char *w = k_calls[who].name, *n = k_calls[o].name;
+    if (o == who)
+        ov2_set_error("%s:%d: ov2_btracker_%s_begin: the previous %s has not been finished (ov2_btracker_%s_end)", __FILE__, __LINE__, w,
+                      who == CALL_STEP ? "step" : "call", w);
+    else if (o == CALL_STEP) ov2_set_error("%s:%d: ov2_btracker_%s between steps only: a step is open", __FILE__, __LINE__, w);
+    else ov2_set_error("%s:%d: %s: ov2_btracker_%s_begin has not been finished (ov2_btracker_%s_end)", __FILE__, __LINE__, k_calls[who].sign, n, n);
+    return OV2_EINVAL;
 }
 
 // a pyramid handle that covers items [0, n) of `p` (host-side descriptor copy: the launchers size their grids from d.batch)
@@ -408,10 +298,10 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
             a.n_dev = (const int *)(k + pl.o_n); a.status = k + pl.o_st; a.is3d = m + ml.m_3d;
             a.unpx = (const float2 *)(k + pl.o_unpx); a.bv = (const double *)(k + pl.o_bv);
             a.lmid = (const int *)(e + el.e_lm); a.nbkfs = (const int *)(e + el.e_nk); a.seed = (const unsigned long long *)(e + el.e_sd);
-            a.Twc = (const double *)(q + ql.q_T); a.hdr = (const FeKfHdr *)t->dfx;
+            a.Twc = (const double *)(q + ql.q_T); a.hdr = (const FeKfHdr *)t->fx.d;
             a.items = (EpifItem *)(d + EL.o_it); a.c_lmid = (int *)(d + EL.o_lm); a.c_unpx = (float2 *)(d + EL.o_un);
             a.c_bv = (double *)(d + EL.o_bv); a.c_is3d = d + EL.o_3d;
-            a.slot = (int *)(t->dfx + el.x_slot); a.rank = (int *)(t->dfx + el.x_rank);
+            a.slot = (int *)(t->fx.d + el.x_slot); a.rank = (int *)(t->fx.d + el.x_rank);
             a.out = (const EpifOut *)(d + EL.o_out); a.removed = d + EL.o_rm; a.err = (const float *)(d + EL.o_er);
             a.pair_cur = (const int *)(d + EL.o_pc);
             a.sel = nullptr;
@@ -426,7 +316,7 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
         io.wpt = (const double *)(m + ml.m_w); io.is3d = m + ml.m_3d;
         io.Twc = (const double *)(q + ql.q_T); io.scale = (const int *)(q + ql.q_sc); io.flags = q + ql.q_fl;
         io.seed = (const unsigned long long *)(q + ql.q_seed);
-        io.work = t->dwork; io.out = (PoseOut *)(q + ql.q_out); io.ms = (int *)(q + ql.q_ms); io.removed_slot = q + ql.q_rm;
+        io.work = t->work.d; io.out = (PoseOut *)(q + ql.q_out); io.ms = (int *)(q + ql.q_ms); io.removed_slot = q + ql.q_rm;
         rc = ov2_launch_frame_pose(s, &P.pp.pose, P.L, n, search, io, hook, &t->fe);
         if (rc != OV2_OK) return rc;
         rc = t->pose.download(s, ql.q_out, ql.pose_bytes);
@@ -542,13 +432,9 @@ static int stage_pose(ov2_btracker *t, int n_active, const ov2_frame_pose_params
     const size_t nm = (size_t)t->cfg.n_max;
     if (!t->pose.h) { const int rc = t->pose.alloc(t->ql.pose_bytes, t->zero_copy, false, "ov2_btracker_track_frame_pose");  if (rc) return rc; }
     const size_t need = ov2_frame_pose_work_bytes(L);
-    if (need > t->work_bytes) {
-        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (the previous step's chain has long finished: _end waited for it)
-        if (t->dwork) (void)hipFree(t->dwork);
-        t->dwork = nullptr; t->work_bytes = 0; t->lp.on = false;         // the lists of the last step go with the block
-        const hipError_t e = hipMalloc((void **)&t->dwork, need);
-        if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("ov2_btracker_track_frame_pose: %s", hipGetErrorString(e)); return OV2_ENOMEM; }
-        t->work_bytes = need;
+    if (need > t->work.dev_bytes) {
+        t->lp.on = false;                                                // the lists of the last step go with the block
+        const int rc = t->work.grow(need, t->ctx->stream, "ov2_btracker_track_frame_pose");  if (rc) return rc;
     }
     uint8_t *hpose = t->pose.h;
     const BtPoseLayout &ql = t->ql;
@@ -580,7 +466,7 @@ static int check_epi(const ov2_btracker *t, const ov2_frame_epi_pose_params *pp,
 
 // The epipolar side's buffers (allocated by the first call) and the filter's block, grown to hold layout L.  The keyframe arrays lie
 // in the block's input section, whose offsets do not depend on the rows: a grown block gets them again from the host copy.
-static int ensure_epi(ov2_btracker *t, const EpifLayout *L)
+int ensure_epi(ov2_btracker *t, const EpifLayout *L)
 {
     const char *who = "ov2_btracker_track_frame_epi_pose";
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
@@ -588,18 +474,8 @@ static int ensure_epi(ov2_btracker *t, const EpifLayout *L)
         EpifLayout L0;
         int rc = epif_layout_capacity(t->batch, t->cfg.n_max, 0, &L0);  if (rc) return rc;
         rc = t->epi.alloc(t->el.epi_bytes, t->zero_copy, false, who);  if (rc) return rc;
-        uint8_t *fx = nullptr;
-        hipError_t e = hipMalloc((void **)&fx, t->el.fx_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(fx, 0, t->el.fx_bytes, t->ctx->stream);       // no item has a keyframe yet
-        if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
-        if (e != hipSuccess) {
-            t->epi.release();
-            if (fx) (void)hipFree(fx);
-            (void)hipGetLastError();
-            ov2_set_error("%s: %s", who, hipGetErrorString(e));
-            return OV2_ENOMEM;
-        }
-        t->dfx = fx;
+        rc = t->fx.alloc(0, t->el.fx_bytes, t->ctx->stream, who);           // zeroed: no item has a keyframe yet
+        if (rc) { t->epi.release(); return rc; }
         t->eL0 = L0;
         t->kf_host.assign(L0.o_up - L0.o_kl, 0);
         t->kf_hdr.assign((size_t)t->batch, FeKfHdr());
@@ -623,6 +499,15 @@ static int ensure_epi(ov2_btracker *t, const EpifLayout *L)
     return OV2_OK;
 }
 
+// item b's keyframe arrays in kf_host (the block's [o_kl, o_up) as the layout without rows puts them)
+KfHost kf_host_item(ov2_btracker *t, int b)
+{
+    const EpifLayout &E = t->eL0;
+    uint8_t *kh = t->kf_host.data();
+    const size_t o = (size_t)b * (size_t)t->cfg.n_max;
+    return KfHost{(int *)kh + o, (float *)(kh + (E.o_ku - E.o_kl)) + 2 * o, (double *)(kh + (E.o_kb - E.o_kl)) + 3 * o};
+}
+
 // the filter's inputs of a step into hepi
 static void stage_epi(ov2_btracker *t, int n_active, const ov2_frame_epi_pose_input *in, const int *n_h)
 {
@@ -642,36 +527,25 @@ static int mono_push(ov2_btracker *t, int b0, int b1)
     const BtMonoLayout &nl = t->nl;
     const size_t o = (size_t)b0, n = (size_t)(b1 - b0);
     hipStream_t s = t->ctx->stream;
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_T + 56 * o, t->res_T.data() + 7 * o, 56 * n, hipMemcpyHostToDevice, s));
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_st + sizeof(ov2_motion_state) * o, t->res_st.data() + o, sizeof(ov2_motion_state) * n, hipMemcpyHostToDevice, s));
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_kt + 8 * o, t->res_kt.data() + o, 8 * n, hipMemcpyHostToDevice, s));
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dres + nl.r_ki + sizeof(MonoKfInfo) * o, t->res_ki.data() + o, sizeof(MonoKfInfo) * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->res.d + nl.r_T + 56 * o, t->res_T.data() + 7 * o, 56 * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->res.d + nl.r_st + sizeof(ov2_motion_state) * o, t->res_st.data() + o, sizeof(ov2_motion_state) * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->res.d + nl.r_kt + 8 * o, t->res_kt.data() + o, 8 * n, hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->res.d + nl.r_ki + sizeof(MonoKfInfo) * o, t->res_ki.data() + o, sizeof(MonoKfInfo) * n, hipMemcpyHostToDevice, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));
     return OV2_OK;
 }
 
 // The mono side's buffers, allocated by the first setter or step of the kind: the I/O block, the resident block with its host mirrors
 // (pose: the identity; state: reset(); no keyframe info) and the work block
-static int ensure_mono(ov2_btracker *t)
+int ensure_mono(ov2_btracker *t)
 {
-    if (t->dres) return OV2_OK;
+    if (t->res.d) return OV2_OK;
     const char *who = "ov2_btracker_track_mono";
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
     const size_t B = (size_t)t->batch;
     if (!t->mono.h) { const int rc = t->mono.alloc(t->nl.mono_bytes, t->zero_copy, false, who);  if (rc) return rc; }
-    uint8_t *res = nullptr, *w = nullptr;
-    hipError_t e = hipMalloc((void **)&res, t->nl.res_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&w, t->nl.work_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(res, 0, t->nl.res_bytes, t->ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(w, 0, t->nl.work_bytes, t->ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
-    if (e != hipSuccess) {
-        if (res) (void)hipFree(res);
-        if (w) (void)hipFree(w);
-        (void)hipGetLastError();
-        ov2_set_error("%s: %s", who, hipGetErrorString(e));
-        return OV2_ENOMEM;
-    }
+    const int rc = alloc_all({{&t->res, 0, t->nl.res_bytes}, {&t->mw, 0, t->nl.work_bytes}}, t->ctx->stream, who);
+    if (rc) return rc;
     ov2_motion_state s0;
     memset(&s0, 0, sizeof s0);
     s0.prev_time = -1.; s0.prevTwc[6] = 1.;
@@ -680,8 +554,16 @@ static int ensure_mono(ov2_btracker *t)
     for (size_t b = 0; b < B; b++) t->res_T[7 * b + 6] = 1.;
     t->res_kt.assign(B, 0.);
     t->res_ki.assign(B, MonoKfInfo{0, 0, 0, 0});
-    t->dres = res; t->dmw = w;
     return mono_push(t, 0, t->batch);
+}
+
+// what the five calls around the resident pose, state and keyframe info share: the item, no open step, the buffers
+int mono_item(ov2_btracker *t, int item, const char *open_msg)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, open_msg);
+    return ensure_mono(t);
 }
 
 // the mono inputs of a step into the I/O block
@@ -698,10 +580,10 @@ static MonoArgs mono_args(ov2_btracker *t, const ov2_btracker::Pending &P, bool 
 {
     const BtMonoLayout &nl = t->nl;
     const BtPointLayout &pl = t->pl;
-    uint8_t *k = t->pt.k, *m = t->map.k, *q = t->pose.k, *e = t->epi.k, *io = t->mono.k, *r = t->dres, *w = t->dmw;
+    uint8_t *k = t->pt.k, *m = t->map.k, *q = t->pose.k, *e = t->epi.k, *io = t->mono.k, *r = t->res.d, *w = t->mw.d;
     MonoArgs a;
     a.r_T = (double *)(r + nl.r_T); a.r_st = (ov2_motion_state *)(r + nl.r_st); a.r_kt = (const double *)(r + nl.r_kt);
-    a.r_ki = (const MonoKfInfo *)(r + nl.r_ki); a.hdr = (const FeKfHdr *)t->dfx;
+    a.r_ki = (const MonoKfInfo *)(r + nl.r_ki); a.hdr = (const FeKfHdr *)t->fx.d;
     a.time = (const double *)(io + nl.n_tm); a.frame_id = (const int *)(io + nl.n_id); a.localba = (const int *)(io + nl.n_ba);
     a.q_T = (double *)(q + t->ql.q_T); a.m_T = (double *)(m + t->ml.m_T); a.pT = (double *)(io + nl.n_pT);
     a.sa = (ov2_motion_state *)(io + nl.n_sa); a.rs = io + nl.n_rs;
@@ -765,60 +647,39 @@ static void stage_points(ov2_btracker *t, int n_active, const float *kps, const 
 }
 
 // ---- the resident frame (f21) ------------------------------------------------------------------------------------------------------
-// item b of the host mirror: its current frame (other == 0) or the buffer its next frame is written into (other == 1)
-struct ResHost { int *n; float *px; int *lmid; uint8_t *is3d; double *wpt; };
-static ResHost res_host(const ov2_btracker *t, int b, int other)
+ResHost res_host(const ov2_btracker *t, int b, int other)
 {
     const BtResLayout &L = t->rl;
-    uint8_t *p = t->hfr + (size_t)(t->res_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.f_item;
+    uint8_t *p = t->fr.h + (size_t)(t->res_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.f_item;
     return ResHost{(int *)p, (float *)(p + L.f_px), (int *)(p + L.f_lm), p + L.f_3d, (double *)(p + L.f_w)};
 }
 
-static ResFrames res_frames(const ov2_btracker *t)
+ResFrames res_frames(const ov2_btracker *t)
 {
     const BtResLayout &L = t->rl;
-    return ResFrames{t->dfr, L.buf_bytes, L.f_item, L.f_px, L.f_lm, L.f_3d, L.f_w, t->drc + L.u_sel, t->cfg.n_max};
+    return ResFrames{t->fr.d, L.buf_bytes, L.f_item, L.f_px, L.f_lm, L.f_3d, L.f_w, t->ctl.d + L.u_sel, t->cfg.n_max};
 }
 
 // the frame block, its mirror and the control block, allocated by the first use: every frame empty
-static int ensure_res(ov2_btracker *t)
+int ensure_res(ov2_btracker *t)
 {
-    if (t->dfr) return OV2_OK;
+    if (t->fr.d) return OV2_OK;
     const char *who = "ov2_btracker_set_frame";
     OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
     OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
     const BtResLayout &L = t->rl;
-    uint8_t *df = nullptr, *hf = nullptr, *dc = nullptr, *hc = nullptr;
-    hipError_t e = hipMalloc((void **)&df, L.frame_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&hf, L.frame_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&dc, L.ctl_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&hc, L.ctl_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemsetAsync(df, 0, L.frame_bytes, t->ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dc, 0, L.ctl_bytes, t->ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
-    if (e != hipSuccess) {
-        if (df) (void)hipFree(df);
-        if (hf) (void)hipHostFree(hf);
-        if (dc) (void)hipFree(dc);
-        if (hc) (void)hipHostFree(hc);
-        (void)hipGetLastError();
-        ov2_set_error("%s: %s", who, hipGetErrorString(e));
-        return OV2_ENOMEM;
-    }
-    memset(hf, 0, L.frame_bytes);
-    memset(hc, 0, L.ctl_bytes);
-    t->dfr = df; t->hfr = hf; t->drc = dc; t->hrc = hc;
+    const int rc = alloc_all({{&t->fr, L.frame_bytes, L.frame_bytes}, {&t->ctl, L.ctl_bytes, L.ctl_bytes}}, t->ctx->stream, who);
+    if (rc) return rc;
     t->res_sel.assign((size_t)t->batch, 0);
     t->res_iskf.assign((size_t)t->batch, 0);
     return OV2_OK;
 }
 
 // which buffer holds each item's current frame, to the device (one byte per item)
-static int res_push_sel(ov2_btracker *t, hipStream_t s)
+int res_push_sel(ov2_btracker *t, hipStream_t s)
 {
-    memcpy(t->hrc + t->rl.u_sel, t->res_sel.data(), (size_t)t->batch);
-    OV2_HIP_CHECK(hipMemcpyAsync(t->drc + t->rl.u_sel, t->hrc + t->rl.u_sel, (size_t)t->batch, hipMemcpyHostToDevice, s));
-    return OV2_OK;
+    memcpy(t->ctl.h + t->rl.u_sel, t->res_sel.data(), (size_t)t->batch);
+    return t->ctl.up(s, t->rl.u_sel, t->rl.u_sel + (size_t)t->batch);
 }
 
 // item b's frame in the mirror (its current one, or with other == 1 the next one) to the same place on the device
@@ -826,8 +687,7 @@ static int res_push_item(ov2_btracker *t, int b, int other, hipStream_t s)
 {
     const BtResLayout &L = t->rl;
     const size_t o = (size_t)(t->res_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.f_item;
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dfr + o, t->hfr + o, L.f_item, hipMemcpyHostToDevice, s));
-    return OV2_OK;
+    return t->fr.up(s, o, o + L.f_item);
 }
 
 // A resident step on mirrored blocks: what _end reads on the host again (the rule's keypoints, the re-run's points, ids and
@@ -881,7 +741,7 @@ static int enqueue_res_carry(ov2_btracker *t, const ov2_btracker::Pending &P)
         if (lo < 0) continue;
         // (an item in [lo, hi] whose CURRENT frame lies in this buffer is copied too: the mirror holds the same bytes)
         const size_t o = (size_t)buf * L.buf_bytes + (size_t)lo * L.f_item;
-        OV2_HIP_CHECK(hipMemcpyAsync(t->hfr + o, t->dfr + o, (size_t)(hi - lo + 1) * L.f_item, hipMemcpyDeviceToHost, s));
+        const int rcd = t->fr.down(s, o, o + (size_t)(hi - lo + 1) * L.f_item);  if (rcd != OV2_OK) return rcd;
     }
     return OV2_OK;
 }
@@ -939,42 +799,39 @@ static int detect_common(ov2_btracker *t, int mode, int n_active, int cell, cons
     ov2_ctx *ctx = t->ctx;
     OV2_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t nm = (size_t)t->cfg.n_max, o_cur = up256(4 * (size_t)t->batch);
-    int *nh = (int *)t->h_det;
+    int *nh = (int *)t->det.h;
     for (int b = 0; b < n_active; b++) {
         const int n = ncur_h ? ncur_h[b] : 0;
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm && (n == 0 || cur_xy_h), OV2_EINVAL, "bad current keypoints");
         nh[b] = n;
-        if (n) memcpy(t->h_det + o_cur + 8 * nm * b, cur_xy_h + 2 * nm * b, 8 * (size_t)n);
+        if (n) memcpy(t->det.h + o_cur + 8 * nm * b, cur_xy_h + 2 * nm * b, 8 * (size_t)n);
     }
     if (out_cap > t->out_cap) {                                          // grow-only result mirrors
         OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (t->d_out) (void)hipFree(t->d_out);
-        if (t->h_out) (void)hipHostFree(t->h_out);
-        t->d_out = nullptr; t->h_out = nullptr; t->out_cap = 0;
-        OV2_HIP_CHECK(hipMalloc((void **)&t->d_out, 8 * (size_t)out_cap * t->batch));
-        OV2_HIP_CHECK(hipHostMalloc((void **)&t->h_out, 8 * (size_t)out_cap * t->batch, hipHostMallocDefault));
+        t->out_cap = 0;
+        const int rca = t->out.alloc(8 * (size_t)out_cap * t->batch, 8 * (size_t)out_cap * t->batch, ctx->stream, "ov2_btracker_detect");
+        if (rca) return rca;
         t->out_cap = out_cap;
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(t->d_det, t->h_det, o_cur + 8 * nm * (size_t)n_active, hipMemcpyHostToDevice, ctx->stream));
+    int rc = t->det.up(ctx->stream, 0, o_cur + 8 * nm * (size_t)n_active);  if (rc != OV2_OK) return rc;
     const ov2_pyr q = prefix_of(t->pyr[t->cur], n_active);
-    const float *cur_d = (const float *)(t->d_det + o_cur);
-    const int *ncur_d = (const int *)t->d_det;
+    const float *cur_d = (const float *)(t->det.d + o_cur);
+    const int *ncur_d = (const int *)t->det.d;
     if (mode == 2 && roi_h) {
         OV2_REQUIRE(roi_stride >= t->cfg.w, OV2_EINVAL, "roi stride < width");
-        if (!t->d_roi) OV2_HIP_CHECK(hipMalloc((void **)&t->d_roi, (size_t)t->cfg.w * t->cfg.h));
-        OV2_HIP_CHECK(hipMemcpy2DAsync(t->d_roi, (size_t)t->cfg.w, roi_h, (size_t)roi_stride, (size_t)t->cfg.w, (size_t)t->cfg.h,
+        if (!t->roi.d) { const int rca = t->roi.alloc(0, (size_t)t->cfg.w * t->cfg.h, ctx->stream, "ov2_btracker_detect_gftt");  if (rca) return rca; }
+        OV2_HIP_CHECK(hipMemcpy2DAsync(t->roi.d, (size_t)t->cfg.w, roi_h, (size_t)roi_stride, (size_t)t->cfg.w, (size_t)t->cfg.h,
                                        hipMemcpyHostToDevice, ctx->stream));
     }
-    int rc;
-    if (mode == 2) rc = ov2_detect_gftt_batch_d(ctx, &q, roi_h ? t->d_roi : nullptr, t->cfg.w, gp, cur_d, (int)nm, ncur_d, nbmax_h, do_subpix,
-                                                t->d_out, t->out_cap, out_n_h);
-    else if (mode == 0) rc = ov2_detect_grid_fast_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, fast_th_inout, mask_mode, do_subpix, t->d_out, t->out_cap, out_n_h);
-    else rc = ov2_detect_singlescale_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, roi, quality_inout, do_subpix, t->d_out, t->out_cap, out_n_h);
+    if (mode == 2) rc = ov2_detect_gftt_batch_d(ctx, &q, roi_h ? t->roi.d : nullptr, t->cfg.w, gp, cur_d, (int)nm, ncur_d, nbmax_h, do_subpix,
+                                                (float *)t->out.d, t->out_cap, out_n_h);
+    else if (mode == 0) rc = ov2_detect_grid_fast_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, fast_th_inout, mask_mode, do_subpix, (float *)t->out.d, t->out_cap, out_n_h);
+    else rc = ov2_detect_singlescale_batch_d(ctx, &q, cell, cur_d, (int)nm, ncur_d, roi, quality_inout, do_subpix, (float *)t->out.d, t->out_cap, out_n_h);
     if (rc != OV2_OK) return rc;
-    OV2_HIP_CHECK(hipMemcpyAsync(t->h_out, t->d_out, 8 * (size_t)t->out_cap * n_active, hipMemcpyDeviceToHost, ctx->stream));
+    rc = t->out.down(ctx->stream, 0, 8 * (size_t)t->out_cap * n_active);  if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < n_active; b++)
-        if (out_n_h[b] > 0) memcpy(out_xy_h + 2 * (size_t)out_cap * b, t->h_out + 8 * (size_t)t->out_cap * b, 8 * (size_t)out_n_h[b]);
+        if (out_n_h[b] > 0) memcpy(out_xy_h + 2 * (size_t)out_cap * b, t->out.h + 8 * (size_t)t->out_cap * b, 8 * (size_t)out_n_h[b]);
     return OV2_OK;
 }
 
@@ -1008,7 +865,6 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     t->pl = bt_point_layout(batch, cfg->n_max); t->ml = bt_map_layout(batch, cfg->n_max);
     t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max); t->nl = bt_mono_layout(batch, cfg->n_max);
     t->cl = bt_ckf_layout(batch, cfg->n_max); t->rl = bt_res_layout(batch, cfg->n_max);
-    t->det_in_bytes = bt_det_in_bytes(batch, cfg->n_max);
     hipError_t e = hipSuccess;
     for (int i = 0; i < BT_IMG_SETS && e == hipSuccess; i++) {
         e = hipHostMalloc((void **)&t->himg[i], t->img_bytes * batch + 256, hipHostMallocDefault);
@@ -1028,11 +884,10 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     // the kernels read / write the pinned point block through its device alias (no staging copies); a device mirror is the fallback
     if (e == hipSuccess && (rc = t->pt.alloc(t->pl.blk_bytes, t->zero_copy, true, "ov2_btracker_create")) != OV2_OK) { btracker_free(t); return rc; }
     if (e == hipSuccess && t->pt.d) e = hipMemsetAsync(t->pt.d, 0, t->pl.blk_bytes, ctx->stream);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&t->h_det, t->det_in_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&t->d_det, t->det_in_bytes);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { ov2_set_error("ov2_btracker_create: %s", hipGetErrorString(e)); btracker_free(t); return OV2_ENOMEM; }
-    memset(t->h_det, 0, t->det_in_bytes);
+    const size_t det_in = bt_det_in_bytes(batch, cfg->n_max);
+    if ((rc = t->det.alloc(det_in, det_in, ctx->stream, "ov2_btracker_create")) != OV2_OK) { btracker_free(t); return rc; }
     t->side.device = ctx->device; t->side.stream = t->ps; t->side.owns_stream = false;
     *out = t;
     return OV2_OK;
@@ -1138,10 +993,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     const ov2_frame_epi_pose_input *ein = mono ? &A.min->step : A.ein;
     OV2_REQUIRE(t && A.img_h, OV2_EINVAL, "NULL argument");
     OV2_REQUIRE(!map || t->has_calib, OV2_EINVAL, "ov2_btracker_track_frame_map: no calibration set on this tracker");
-    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: the previous step has not been finished (ov2_btracker_track_frame_end)");
-    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
-    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
-    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_track_frame_begin: ov2_btracker_temporal_keyframe_begin has not been finished (ov2_btracker_temporal_keyframe_end)");
+    { const int rco = begin_guard(t, CALL_STEP);  if (rco != OV2_OK) return rco; }
     OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
     OV2_REQUIRE(A.stride >= t->cfg.w, OV2_EINVAL, "stride < width");
     const size_t nm = (size_t)t->cfg.n_max;
@@ -1258,7 +1110,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     rc = tracked ? track() : (P.mono_ran ? mono_empty() : preprocess());
     if (rc != OV2_OK) { t->cur = old_cur; return rc; }
     commit();
-    P.tracked = tracked; P.on = true;
+    P.tracked = tracked; t->open = CALL_STEP;
     return OV2_OK;
 }
 
@@ -1433,8 +1285,6 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
     const ov2_btracker::Pending &P = t->pend;
     const size_t nm = (size_t)t->cfg.n_max, R = redo.size();
     const int n_rows = P.ep.n_rows;
-    const EpifLayout &L0 = t->eL0;
-    const uint8_t *kh = t->kf_host.data();
     const int *lmid_h = (const int *)(t->epi.h + t->el.e_lm), *nbkfs_h = (const int *)(t->epi.h + t->el.e_nk);    // as the step staged them
     const unsigned long long *seed_h = (const unsigned long long *)(t->epi.h + t->el.e_sd);
     std::vector<std::vector<int>> lmid(R), pair(R);
@@ -1469,13 +1319,14 @@ static int epi_redo(ov2_btracker *t, const std::vector<int> &redo, const float *
         std::vector<int> &tab = t->le.samples[(size_t)b];
         tab.assign(8 * (size_t)(n_rows > 0 ? n_rows : 1), -1);
         const FeKfHdr &h = t->kf_hdr[(size_t)b];
+        const KfHost kf = kf_host_item(t, b);
         ov2_epifilter_item &q = items[k];
         memset(&q, 0, sizeof q);
         q.fkf.n_cur = nc; q.fkf.cur_lmid = lmid[k].data(); q.fkf.cur_px = px[k].data(); q.fkf.cur_unpx = unpx[k].data();
         q.fkf.cur_bv = bv[k].data(); q.fkf.cur_is3d = d3[k].data(); q.fkf.cur_Twc = P.Twc.data() + 7 * (size_t)b;
-        q.fkf.n_kf = h.n_kf; q.fkf.kf_lmid = (const int *)kh + o; q.fkf.kf_unpx = (const float *)(kh + (L0.o_ku - L0.o_kl)) + 2 * o;
+        q.fkf.n_kf = h.n_kf; q.fkf.kf_lmid = kf.lmid; q.fkf.kf_unpx = kf.unpx;
         q.fkf.kf_Tcw = h.kf_Tcw; q.fkf.noccupcells = -1; q.fkf.nb3dkps = -1;
-        q.kf_bv = (const double *)(kh + (L0.o_kb - L0.o_kl)) + 3 * o; q.kf_Twc = h.kf_Twc; q.nbkfs = nbkfs_h[b]; q.seed = seed_h[b];
+        q.kf_bv = kf.bv; q.kf_Twc = h.kf_Twc; q.nbkfs = nbkfs_h[b]; q.seed = seed_h[b];
         ov2_epifilter_result &r = rs[k];
         memset(&r, 0, sizeof r);
         r.removed = rm[k].data(); r.pair_cur = pair[k].data(); r.err = err[k].data(); r.trace_samples = n_rows > 0 ? tab.data() : nullptr;
@@ -1515,7 +1366,7 @@ static int track_frame_end_step(ov2_btracker *t, float *out_xy_h, uint8_t *statu
 {
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
     ov2_btracker::Pending &P = t->pend;
-    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_track_frame_end without ov2_btracker_track_frame_begin");
+    OV2_REQUIRE(t->open == CALL_STEP, OV2_EINVAL, "ov2_btracker_track_frame_end without ov2_btracker_track_frame_begin");
     OV2_REQUIRE(!results || P.form >= STEP_POSE, OV2_EINVAL, "ov2_btracker_track_frame_pose_end: the step was not begun with ov2_btracker_track_frame_pose_begin");
     if (results)
         for (int b = 0; b < P.n_active; b++)
@@ -1529,7 +1380,7 @@ static int track_frame_end_step(ov2_btracker *t, float *out_xy_h, uint8_t *statu
             OV2_REQUIRE(P.n[(size_t)b] == 0 || eres[b].removed, OV2_EINVAL, "NULL result buffer (removed) of the filter");
             OV2_REQUIRE(!eres[b].trace_samples, OV2_EINVAL, "trace_samples must be NULL in a step: ov2_btracker_last_epi_inputs fetches the table");
         }
-    P.on = false;
+    t->open = CALL_NONE;
     if (P.mono) {                                                        // the predicted poses: what the pose chain started from
         OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
         if (P.mono_ran) {
@@ -1636,8 +1487,6 @@ static int mono_finish(ov2_btracker *t, const float *out_xy_h, const uint8_t *st
     if (!P.mono_ran) return OV2_OK;
     const size_t R = redo.size();
     if (R) {
-        const EpifLayout &L0 = t->eL0;
-        const uint8_t *kh = t->kf_host.data();
         const int *lmid_h = (const int *)(t->epi.h + t->el.e_lm);
         std::vector<std::vector<int>> lmid(R);
         std::vector<std::vector<float>> px(R), unpx(R);
@@ -1676,7 +1525,7 @@ static int mono_finish(ov2_btracker *t, const float *out_xy_h, const uint8_t *st
             memset(&q, 0, sizeof q);
             q.n_cur = nc; q.cur_lmid = lmid[k].data(); q.cur_px = px[k].data(); q.cur_unpx = unpx[k].data(); q.cur_bv = bv[k].data();
             q.cur_is3d = d3[k].data(); q.cur_Twc = &Tw[7 * k];
-            q.n_kf = h.n_kf; q.kf_lmid = (const int *)kh + o; q.kf_unpx = (const float *)(kh + (L0.o_ku - L0.o_kl)) + 2 * o; q.kf_Tcw = h.kf_Tcw;
+            q.n_kf = h.n_kf; q.kf_lmid = kf_host_item(t, b).lmid; q.kf_unpx = kf_host_item(t, b).unpx; q.kf_Tcw = h.kf_Tcw;
             q.cur_id = P.frame_id[(size_t)b]; q.kf_id = ki.kf_id; q.cur_time = tm[k]; q.kf_time = t->res_kt[(size_t)b];
             q.kf_nb3dkps = ki.kf_nb3dkps; q.localba_is_on = P.localba[(size_t)b]; q.noccupcells = -1; q.nb3dkps = -1;
         }
@@ -1704,7 +1553,7 @@ static int track_frame_end(ov2_btracker *t, float *out_xy_h, uint8_t *status_h, 
     std::vector<int> redo;
     std::vector<uint8_t> excl;
     int rc = track_frame_end_step(t, out_xy_h, status_h, p3p_req, results, eres, mres, redo, excl);
-    if (rc != OV2_OK || !t->pend.mono || t->pend.on) return rc;
+    if (rc != OV2_OK || !t->pend.mono || t->open == CALL_STEP) return rc;
     rc = mono_finish(t, out_xy_h, status_h, results, mres, redo, excl);
     if (rc != OV2_OK || !t->pend.resident || !mres) return rc;
     return res_finish(t, out_xy_h, status_h, results, redo, excl, fres);
@@ -1754,7 +1603,7 @@ int ov2_btracker_last_pose_inputs(const ov2_btracker *t, int item, int *m, int *
     if (m) *m = t->lp.m[b];
     if (n_rows_used) *n_rows_used = t->lp.rows[b];
     const PoseLayout &L = t->lp_L;
-    const uint8_t *w = t->lp.chain ? t->dwork : nullptr;
+    const uint8_t *w = t->lp.chain ? t->work.d : nullptr;
     return last_inputs_fetch(t, t->lp, b, slot_idx, samples, w ? w + ov2_frame_pose_slot_offset(L) + 4 * b * (size_t)L.n_max : nullptr,
                              w ? w + L.o_p3 + L.pl.o_sm + 16 * b * (size_t)L.n_rows : nullptr, 16);
 }
@@ -1785,19 +1634,19 @@ int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf
     if (rc != OV2_OK) return rc;
     const EpifLayout &L0 = t->eL0;
     const size_t o = (size_t)item * (size_t)t->cfg.n_max, n = (size_t)n_kf;
-    uint8_t *kh = t->kf_host.data();
+    const KfHost kf = kf_host_item(t, item);
     hipStream_t s = t->ctx->stream;
     if (n) {
-        memcpy(kh + 4 * o, kf_lmid, 4 * n);
-        memcpy(kh + (L0.o_ku - L0.o_kl) + 8 * o, kf_unpx, 8 * n);
-        memcpy(kh + (L0.o_kb - L0.o_kl) + 24 * o, kf_bv, 24 * n);
-        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kl + 4 * o, kh + 4 * o, 4 * n, hipMemcpyHostToDevice, s));
-        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_ku + 8 * o, kh + (L0.o_ku - L0.o_kl) + 8 * o, 8 * n, hipMemcpyHostToDevice, s));
-        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kb + 24 * o, kh + (L0.o_kb - L0.o_kl) + 24 * o, 24 * n, hipMemcpyHostToDevice, s));
+        memcpy(kf.lmid, kf_lmid, 4 * n);
+        memcpy(kf.unpx, kf_unpx, 8 * n);
+        memcpy(kf.bv, kf_bv, 24 * n);
+        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kl + 4 * o, kf.lmid, 4 * n, hipMemcpyHostToDevice, s));
+        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_ku + 8 * o, kf.unpx, 8 * n, hipMemcpyHostToDevice, s));
+        OV2_HIP_CHECK(hipMemcpyAsync(t->depi + L0.o_kb + 24 * o, kf.bv, 24 * n, hipMemcpyHostToDevice, s));
     }
     t->kf_hdr[(size_t)item] = h;
     if (!t->res_iskf.empty()) t->res_iskf[(size_t)item] = 0;
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dfx + sizeof(FeKfHdr) * (size_t)item, &t->kf_hdr[(size_t)item], sizeof(FeKfHdr), hipMemcpyHostToDevice, s));
+    OV2_HIP_CHECK(hipMemcpyAsync(t->fx.d + sizeof(FeKfHdr) * (size_t)item, &t->kf_hdr[(size_t)item], sizeof(FeKfHdr), hipMemcpyHostToDevice, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));                              // the host copy may be rewritten by the next call
     return OV2_OK;
 }
@@ -1831,15 +1680,6 @@ int ov2_btracker_track_frame_epi_pose(ov2_btracker *t, int n_active, const uint8
     if (rc == OV2_OK) rc = ov2_btracker_track_frame_epi_pose_begin(t, n_active, img_h, stride, kps_xy_h, wpt_h, is3d_h, Tcw_h, n_h, klt_use_prior, params, input);
     if (rc != OV2_OK) return rc;
     return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results);
-}
-
-// what the five calls around the resident pose, state and keyframe info share: the item, no open step, the buffers
-static int mono_item(ov2_btracker *t, int item, const char *open_msg)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, open_msg);
-    return ensure_mono(t);
 }
 
 int ov2_btracker_set_pose(ov2_btracker *t, int item, const double Twc[7])
@@ -1905,7 +1745,7 @@ int ov2_btracker_track_mono_end(ov2_btracker *t, float *out_xy_h, uint8_t *statu
 {
     OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    OV2_REQUIRE(!t->pend.on || !t->pend.mono || (t->pend.form == STEP_EPI) == (epi_results != nullptr), OV2_EINVAL,
+    OV2_REQUIRE(t->open != CALL_STEP || !t->pend.mono || (t->pend.form == STEP_EPI) == (epi_results != nullptr), OV2_EINVAL,
                 "ov2_btracker_track_mono_end: epi_results goes with doepipolar == 1, and only with it");
     return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results);
 }
@@ -1970,7 +1810,7 @@ int ov2_btracker_get_frame(ov2_btracker *t, int item, int from_device, int *n, f
     std::vector<uint8_t> dev;
     if (from_device) {
         dev.resize(L.f_item);
-        OV2_HIP_CHECK(hipMemcpyAsync(dev.data(), t->dfr + (p - t->hfr), L.f_item, hipMemcpyDeviceToHost, t->ctx->stream));
+        OV2_HIP_CHECK(hipMemcpyAsync(dev.data(), t->fr.d + (p - t->fr.h), L.f_item, hipMemcpyDeviceToHost, t->ctx->stream));
         OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
         p = dev.data();
     }
@@ -2017,7 +1857,7 @@ static int res_update(ov2_btracker *t, int b0, int nb, const int *n_ops_h, const
     if (rc != OV2_OK) return rc;
     const BtResLayout &L = t->rl;
     const hipStream_t s = t->ctx->stream;
-    uint8_t *h = t->hrc, *d = t->drc;
+    uint8_t *h = t->ctl.h, *d = t->ctl.d;
     memcpy(h + L.u_sel, t->res_sel.data(), (size_t)t->batch);
     int *nop = (int *)(h + L.u_nop), *off = (int *)(h + L.u_off);
     ov2_resident_op *ops = (ov2_resident_op *)(h + L.u_ops);
@@ -2027,7 +1867,7 @@ static int res_update(ov2_btracker *t, int b0, int nb, const int *n_ops_h, const
         if (n_ops_h[k]) memcpy(ops + at, ops_h[k], sizeof(ov2_resident_op) * (size_t)n_ops_h[k]);
         at += (size_t)n_ops_h[k];
     }
-    OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.u_ops + sizeof(ov2_resident_op) * total, hipMemcpyHostToDevice, s));
+    rc = t->ctl.up(s, 0, L.u_ops + sizeof(ov2_resident_op) * total);  if (rc != OV2_OK) return rc;
     ResUpdateArgs a;
     a.f = res_frames(t);
     a.n_ops = (const int *)(d + L.u_nop); a.op_off = (const int *)(d + L.u_off); a.ops = (const ov2_resident_op *)(d + L.u_ops);
@@ -2035,7 +1875,7 @@ static int res_update(ov2_btracker *t, int b0, int nb, const int *n_ops_h, const
     rc = ov2_launch_res_update(s, a, b0, nb, (int)total);
     if (rc != OV2_OK) return rc;
     const size_t ro = L.u_rec + sizeof(ov2_resident_update_result) * (size_t)b0;
-    OV2_HIP_CHECK(hipMemcpyAsync(h + ro, d + ro, sizeof(ov2_resident_update_result) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    rc = t->ctl.down(s, ro, ro + sizeof(ov2_resident_update_result) * (size_t)nb);  if (rc != OV2_OK) return rc;
     OV2_HIP_CHECK(hipStreamSynchronize(s));
     memcpy(results, h + ro, sizeof(ov2_resident_update_result) * (size_t)nb);
     // the mirror, by the kernel's rule (an id stands once in a frame and once in a list)
@@ -2101,9 +1941,9 @@ int ov2_btracker_track_mono_resident_end(ov2_btracker *t, float *out_xy_h, uint8
 {
     OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
     OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    OV2_REQUIRE(!t->pend.on || t->pend.resident, OV2_EINVAL,
+    OV2_REQUIRE(t->open != CALL_STEP || t->pend.resident, OV2_EINVAL,
                 "ov2_btracker_track_mono_resident_end: the step was not begun with ov2_btracker_track_mono_resident_begin");
-    OV2_REQUIRE(!t->pend.on || (t->pend.form == STEP_EPI) == (epi_results != nullptr), OV2_EINVAL,
+    OV2_REQUIRE(t->open != CALL_STEP || (t->pend.form == STEP_EPI) == (epi_results != nullptr), OV2_EINVAL,
                 "ov2_btracker_track_mono_end: epi_results goes with doepipolar == 1, and only with it");
     return track_frame_end(t, out_xy_h, status_h, p3p_req, pose_results, epi_results, mono_results, frame_results);
 }
@@ -2116,7 +1956,7 @@ int ov2_btracker_track_mono_resident(ov2_btracker *t, int n_active, const uint8_
     OV2_REQUIRE(pose_results && mono_results, OV2_EINVAL, "NULL result array");
     OV2_REQUIRE(!params || (params->doepipolar != 0) == (epi_results != nullptr), OV2_EINVAL,
                 "ov2_btracker_track_mono: epi_results goes with doepipolar == 1, and only with it");
-    if (t && t->dfr && n_active >= 1 && n_active <= t->batch && !t->pend.on) {      // the result buffers, against the mirror's counts
+    if (t && t->fr.d && n_active >= 1 && n_active <= t->batch && t->open != CALL_STEP) {      // the result buffers, against the mirror's counts
         std::vector<int> n((size_t)n_active);
         for (int b = 0; b < n_active; b++) n[(size_t)b] = *res_host(t, b, 0).n;
         const int rc = check_outputs(t, n_active, n.data(), out_xy_h, status_h, pose_results, epi_results);
@@ -2145,7 +1985,7 @@ int ov2_btracker_last_epi_inputs(const ov2_btracker *t, int item, int *n_cur, in
     if (n_rows_used) *n_rows_used = t->le.rows[b];
     const EpifLayout &L = t->le_L;
     const bool dev = t->le.chain;
-    return last_inputs_fetch(t, t->le, b, slot_idx, samples, dev ? t->dfx + t->el.x_slot + 4 * b * (size_t)t->cfg.n_max : nullptr,
+    return last_inputs_fetch(t, t->le, b, slot_idx, samples, dev ? t->fx.d + t->el.x_slot + 4 * b * (size_t)t->cfg.n_max : nullptr,
                              dev ? t->depi + L.o_sm + 32 * b * (size_t)L.s_max : nullptr, 32);
 }
 
@@ -2244,925 +2084,6 @@ int ov2_btracker_lckf_prepare(ov2_btracker *t, int n_active, const ov2_lckf_para
     // a later upload of this set on the copy stream orders itself after the reads (the call has synchronised: this costs nothing)
     OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], t->ctx->stream));
     return OV2_OK;
-}
-
-} // extern "C"
-
-// ---- ov2_btracker_create_keyframe ------------------------------------------------------------------------------------------------
-// the detector's work block: every item's output list, then ONE pass's response maps, candidates and free-cell lists (passes of
-// `chunk` items follow each other on the context's stream and share them, as the passes of the batched detectors do)
-struct CkfWork { int chunk, out_cap; size_t o_out, o_map, o_cand, o_free, total; };
-static CkfWork ckf_work(int batch, int cell, int ncells, int mode)
-{
-    CkfWork W;
-    W.chunk = batch < DET_CHUNK / 2 ? batch : DET_CHUNK / 2;
-    W.out_cap = det_out_cap(mode, ncells);
-    StageCursor c(256);
-    W.o_out = c.take(8 * (size_t)W.out_cap * (size_t)batch);
-    W.o_map = c.take((size_t)W.chunk * det_map_bytes(cell, ncells, mode));
-    W.o_cand = c.take((size_t)W.chunk * (size_t)ncells * DET_CAND_BYTES);
-    W.o_free = c.take((size_t)W.chunk * 4 * ((size_t)ncells + 1));
-    W.total = c.off;
-    return W;
-}
-
-// the call's buffers: the I/O block by the first call, the work block grown to `need` bytes
-static int ensure_ckf(ov2_btracker *t, size_t need)
-{
-    const char *who = "ov2_btracker_create_keyframe";
-    if (!t->hckf) {
-        uint8_t *h = nullptr, *d = nullptr;
-        hipError_t e = hipHostMalloc((void **)&h, t->cl.c_down, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&d, t->cl.dev_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(d, 0, t->cl.dev_bytes, t->ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
-        if (e != hipSuccess) {
-            if (h) (void)hipHostFree(h);
-            if (d) (void)hipFree(d);
-            (void)hipGetLastError();
-            ov2_set_error("%s: %s", who, hipGetErrorString(e));
-            return OV2_ENOMEM;
-        }
-        memset(h, 0, t->cl.c_down);
-        t->hckf = h; t->dckf = d;
-    }
-    if (need > t->ckw_bytes) {
-        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (an earlier call's kernels have long finished: its _end waited)
-        if (t->dckw) (void)hipFree(t->dckw);
-        t->dckw = nullptr; t->ckw_bytes = 0;
-        const hipError_t e = hipMalloc((void **)&t->dckw, need);
-        if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("%s: %s", who, hipGetErrorString(e)); return OV2_ENOMEM; }
-        t->ckw_bytes = need;
-    }
-    return OV2_OK;
-}
-
-extern "C" {
-
-int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_create_keyframe_params *params,
-                                       const ov2_create_keyframe_input *input)
-{
-    OV2_REQUIRE(t && params && input, OV2_EINVAL, "ov2_btracker_create_keyframe: NULL tracker / params / input");
-    const ov2_create_keyframe_params &p = *params;
-    const ov2_create_keyframe_input &in = *input;
-    const bool resident = !in.px_h;                                      // the frame is the resident one (f21)
-    OV2_REQUIRE(resident ? (!in.lmid_h && !in.is3d_h && !in.n_h) : (in.lmid_h && in.is3d_h && in.n_h), OV2_EINVAL,
-                "ov2_btracker_create_keyframe: px_h / lmid_h / is3d_h / n_h are all NULL (the resident frame) or none is");
-    OV2_REQUIRE(in.make_kf_h && in.nlmid_h && in.nkfid_h && in.time_h, OV2_EINVAL,
-                "ov2_btracker_create_keyframe: NULL px_h / lmid_h / is3d_h / n_h / make_kf_h / nlmid_h / nkfid_h / time_h");
-    OV2_REQUIRE(p.detector != OV2_CKF_DET_GFTT, OV2_EINVAL, "ov2_btracker_create_keyframe: detectGFTT is not fused (detector OV2_CKF_DET_GFTT)");
-    OV2_REQUIRE(p.detector == OV2_CKF_DET_SINGLESCALE || p.detector == OV2_CKF_DET_GRID_FAST, OV2_EINVAL, "ov2_btracker_create_keyframe: unknown detector");
-    const int mode = p.detector == OV2_CKF_DET_GRID_FAST ? 0 : 1;
-    OV2_REQUIRE(mode == 0 ? in.fast_th_inout != nullptr : in.quality_inout != nullptr, OV2_EINVAL,
-                "ov2_btracker_create_keyframe: NULL quality_inout (single scale) / fast_th_inout (grid FAST)");
-    OV2_REQUIRE(mode != 0 || p.mask_mode == OV2_MASK_AS_EXECUTED || p.mask_mode == OV2_MASK_INTENDED, OV2_EINVAL, "bad mask_mode");
-    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
-    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_create_keyframe between steps only: a step is open");
-    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: the previous call has not been finished (ov2_btracker_create_keyframe_end)");
-    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
-    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_create_keyframe_begin: ov2_btracker_temporal_keyframe_begin has not been finished (ov2_btracker_temporal_keyframe_end)");
-    OV2_REQUIRE(t->raw_which >= 0, OV2_EINVAL, "ov2_btracker_create_keyframe: no current frames (no step yet, or their staging set was uploaded / prepared again)");
-    OV2_REQUIRE(n_active <= t->raw_n, OV2_EINVAL, "n_active exceeds the items of the current step");
-    OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_create_keyframe: no calibration set on this tracker");
-    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
-    OV2_REQUIRE(in.Twc_h || t->dres, OV2_EINVAL, "ov2_btracker_create_keyframe: Twc_h == NULL on a tracker without a resident pose (ov2_btracker_set_pose / ov2_btracker_track_mono)");
-    {
-        ov2_fkf_params g;
-        memset(&g, 0, sizeof g);
-        g.ncellsize = p.ncellsize; g.nbwcells = p.nbwcells; g.nbhcells = p.nbhcells; g.nbmaxkps = p.nbmaxkps;
-        const int rcg = fkf_check_decide(&g);  if (rcg != OV2_OK) return rcg;
-    }
-    const ov2_tracker_config &c = t->cfg;
-    OV2_REQUIRE(p.det_cell >= 8, OV2_EINVAL, "the detector's cell size must be at least 8");
-    int rc = det_ready(t->ctx, c.w, c.h, p.det_cell, mode);  if (rc != OV2_OK) return rc;
-    const int ncells = (c.w / p.det_cell) * (c.h / p.det_cell);
-    const size_t nm = (size_t)c.n_max;
-    std::vector<int> n_res;                                              // the resident form: the mirror's counts stand for n_h
-    if (resident) {
-        rc = ensure_res(t);  if (rc != OV2_OK) return rc;
-        for (int b = 0; b < n_active; b++) n_res.push_back(*res_host(t, b, 0).n);
-    }
-    const int *n_h = resident ? n_res.data() : in.n_h;
-    bool any = false;
-    for (int b = 0; b < n_active; b++) {
-        const int n = n_h[b];
-        OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
-        if (!in.make_kf_h[b]) continue;
-        any = true;
-        const int nl = in.nlmid_h[b];
-        OV2_REQUIRE(nl >= 0 && (long long)nl + 2ll * ncells <= 2147483647ll, OV2_EINVAL, "nlmid_h negative, or nlmid_h + the detector's capacity overflows int");
-        const int *lmid = resident ? res_host(t, b, 0).lmid : in.lmid_h + nm * (size_t)b;
-        for (int i = 0; i < n; i++) {
-            const int lm = lmid[i];
-            OV2_REQUIRE(lm >= 0 && lm < nl, OV2_EINVAL, "lmid_h outside [0, nlmid_h): the map's id counter is monotone");
-        }
-        OV2_REQUIRE(std::isfinite(in.time_h[b]), OV2_EINVAL, "time not finite");
-        const double *T = in.Twc_h ? in.Twc_h + 7 * (size_t)b : t->res_T.data() + 7 * (size_t)b;
-        double Ti[7];
-        for (int k = 0; k < 7; k++) OV2_REQUIRE(std::isfinite(T[k]), OV2_EINVAL, "pose not finite (Twc_h)");
-        ov2_fe_invert(T, Ti);
-        for (int k = 0; k < 7; k++) OV2_REQUIRE(std::isfinite(Ti[k]), OV2_EINVAL, "pose not finite (the inverse of Twc_h)");
-    }
-    ov2_ctx *ctx = t->ctx;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;
-    rc = ensure_mono(t);  if (rc != OV2_OK) return rc;
-    const bool det_on = ncells > 0;
-    const CkfWork W = ckf_work(t->batch, p.det_cell, det_on ? ncells : 1, mode);
-    rc = ensure_ckf(t, W.total);  if (rc != OV2_OK) return rc;
-    ov2_btracker::CkfPending &P = t->cpend;
-    P.n_active = n_active; P.mode = mode; P.ncells = ncells; P.p = p; P.det = det_on && any;
-    P.quality = in.quality_inout; P.fast_th = in.fast_th_inout;
-    P.flag.assign(in.make_kf_h, in.make_kf_h + n_active);
-    P.nkfid.assign(in.nkfid_h, in.nkfid_h + n_active);
-    P.time.assign(in.time_h, in.time_h + n_active);
-    P.resident = resident;
-    t->slot_bytes = 0;
-    // ---- the inputs into the pinned block ----
-    const BtCkfLayout &L = t->cl;
-    uint8_t *h = t->hckf, *d = t->dckf;
-    const size_t na = (size_t)n_active;
-    memcpy(h + L.c_n, n_h, 4 * na);
-    for (int b = 0; b < n_active; b++) h[L.c_fl + (size_t)b] = in.make_kf_h[b] ? 1 : 0;
-    memcpy(h + L.c_nl, in.nlmid_h, 4 * na);
-    memcpy(h + L.c_id, in.nkfid_h, 4 * na);
-    memcpy(h + L.c_tm, in.time_h, 8 * na);
-    if (in.Twc_h) memcpy(h + L.c_T, in.Twc_h, 56 * na);
-    for (int b = 0; b < n_active; b++) {
-        if (mode == 0) memcpy(h + L.c_par + 4 * (size_t)b, in.fast_th_inout + b, 4);
-        else memcpy(h + L.c_par + 8 * (size_t)b, in.quality_inout + b, 8);
-        const size_t n = in.make_kf_h[b] && !resident ? (size_t)in.n_h[b] : 0, o = nm * (size_t)b;
-        if (!n) continue;
-        memcpy(h + L.c_px + 8 * o, in.px_h + 2 * o, 8 * n);
-        memcpy(h + L.c_lm + 4 * o, in.lmid_h + o, 4 * n);
-        memcpy(h + L.c_3d + o, in.is3d_h + o, n);
-        t->slot_bytes += 13 * n;
-    }
-    // ---- the one enqueue ----
-    const hipStream_t s = ctx->stream;
-    const ov2_pyr *pyr = t->pyr[t->cur];
-    rc = ov2_pyr_wait_ready(ctx, pyr);  if (rc != OV2_OK) return rc;
-    const PyrLevelDesc &L0 = pyr->d.lv[0];
-    const uint8_t *im = pyr->d.base + L0.img_roi;
-    // (the resident form: the per-item sections only; k_res_ckf_in fills the per-slot ranges on the device)
-    OV2_HIP_CHECK(hipMemcpyAsync(d, h, resident ? L.c_3d : L.c_up, hipMemcpyHostToDevice, s));
-    ResCkfArgs ra;
-    if (resident) {
-        rc = res_push_sel(t, s);  if (rc != OV2_OK) return rc;
-        ra.f = res_frames(t);
-        ra.flag = d + L.c_fl; ra.n = (int *)(d + L.c_n); ra.px = (float2 *)(d + L.c_px); ra.lmid = (int *)(d + L.c_lm); ra.is3d = d + L.c_3d;
-        ra.rec = (const ov2_create_keyframe_result *)(d + L.c_rec);
-        rc = ov2_launch_res_ckf_in(s, ra, n_active);  if (rc != OV2_OK) return rc;
-    }
-    uint8_t *w = t->dckw;
-    CkfArgs a;
-    a.n = (const int *)(d + L.c_n); a.flag = d + L.c_fl; a.nlmid = (const int *)(d + L.c_nl); a.nkfid = (const int *)(d + L.c_id);
-    a.time = (const double *)(d + L.c_tm); a.Twc = in.Twc_h ? (const double *)(d + L.c_T) : (const double *)(t->dres + t->nl.r_T);
-    a.px = (float2 *)(d + L.c_px); a.lmid = (int *)(d + L.c_lm); a.is3d = d + L.c_3d;
-    a.skip = d + L.w_skip; a.so_n = (const int *)(d + L.c_so); a.so_stride = (int)(sizeof(SelectOut) / sizeof(int));
-    a.det = (const float2 *)(w + W.o_out); a.det_cap = W.out_cap; a.nb = (int *)(d + L.w_nb);
-    a.img = im; a.img_item = (long long)pyr->d.item_stride; a.img_pitch = L0.img_pitch; a.w = L0.w; a.h = L0.h;
-    a.rec = (ov2_create_keyframe_result *)(d + L.c_rec); a.color = d + L.c_col; a.o_hdr = (FeKfHdr *)(d + L.c_hdr); a.perm = (int *)(d + L.c_perm);
-    a.unpx = (const float2 *)(d + L.c_un); a.bv = (const double *)(d + L.c_bv);
-    a.kf_lmid = (int *)(t->depi + t->eL0.o_kl); a.kf_unpx = (float2 *)(t->depi + t->eL0.o_ku); a.kf_bv = (double *)(t->depi + t->eL0.o_kb);
-    a.hdr = (FeKfHdr *)t->dfx; a.r_ki = (MonoKfInfo *)(t->dres + t->nl.r_ki); a.r_kt = (double *)(t->dres + t->nl.r_kt);
-    a.n_max = c.n_max; a.ncellsize = p.ncellsize; a.nbwcells = p.nbwcells; a.nbhcells = p.nbhcells; a.nbmaxkps = p.nbmaxkps; a.det_on = det_on ? 1 : 0;
-    rc = ov2_launch_ckf_prepare(s, a, n_active);  if (rc != OV2_OK) return rc;
-    if (P.det) {
-        // the detectors' three launches per pass, the frame's keypoints as the occupied set, every count left on the device
-        for (int c0 = 0; c0 < n_active; c0 += W.chunk) {
-            const int n = n_active - c0 < W.chunk ? n_active - c0 : W.chunk;
-            DetBatch B = {};
-            B.img_stride = (long long)pyr->d.item_stride; B.cur_stride = c.n_max; B.out_stride = W.out_cap;
-            B.ncur = a.n + c0; B.skip = a.skip + c0;
-            if (mode == 0) B.fast_th = (const int *)(d + L.c_par) + c0; else B.quality = (const double *)(d + L.c_par) + c0;
-            rc = enqueue_detect(ctx, s, mode, im + (long long)c0 * pyr->d.item_stride, L0.w, L0.h, L0.img_pitch, p.det_cell, n, B, 0, p.mask_mode,
-                                mode == 1 ? p.roi : nullptr, 0.0, 0, (const float2 *)a.px + (size_t)c0 * nm, w + W.o_map, (CellCand *)(w + W.o_cand),
-                                (int *)(w + W.o_free), (float2 *)(w + W.o_out) + (size_t)c0 * (size_t)W.out_cap,
-                                (SelectOut *)(d + L.c_so) + c0, p.do_subpix);
-            if (rc != OV2_OK) return rc;
-        }
-    }
-    rc = ov2_launch_ckf_append(s, a, n_active);  if (rc != OV2_OK) return rc;
-    rc = ov2_launch_compute_keypoints(s, t->calib, (const float *)a.px, c.n_max, a.nb, (float *)(d + L.c_un), (double *)(d + L.c_bv), n_active);
-    if (rc != OV2_OK) return rc;
-    if (p.use_brief) {
-        const int which = t->raw_which;
-        rc = ov2_brief_launch_d(ctx, t->dimg[which], c.w, c.h, t->img_pitch, t->img_bytes, n_active, (const float *)a.px, c.n_max, a.nb, 0,
-                                d + L.c_desc, d + L.c_val);
-        if (rc != OV2_OK) return rc;
-        // a later upload of this set on the copy stream orders itself after the reads
-        OV2_HIP_CHECK(hipEventRecord(t->used_ev[which], s));
-    }
-    rc = ov2_launch_ckf_install(s, a, n_active);  if (rc != OV2_OK) return rc;
-    if (resident) { rc = ov2_launch_res_adopt(s, ra, n_active);  if (rc != OV2_OK) return rc; }
-    OV2_HIP_CHECK(hipMemcpyAsync(h + L.c_io, d + L.c_io, (p.use_brief ? L.c_down : L.c_desc) - L.c_io, hipMemcpyDeviceToHost, s));
-    P.on = true;
-    return OV2_OK;
-}
-
-int ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result *results, float *out_px_h, int *out_lmid_h,
-                                     float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    ov2_btracker::CkfPending &P = t->cpend;
-    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_create_keyframe_end without ov2_btracker_create_keyframe_begin");
-    OV2_REQUIRE(results && out_px_h && out_lmid_h && unpx_h && bv_h && color_h, OV2_EINVAL, "ov2_btracker_create_keyframe_end: NULL result / output array");
-    OV2_REQUIRE(!P.p.use_brief || (desc_h && valid_h), OV2_EINVAL, "ov2_btracker_create_keyframe_end: NULL desc_h / valid_h with use_brief");
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    P.on = false;
-    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-    const BtCkfLayout &L = t->cl;
-    const EpifLayout &E = t->eL0;
-    const uint8_t *h = t->hckf;
-    uint8_t *kh = t->kf_host.data();
-    const size_t nm = (size_t)t->cfg.n_max;
-    for (int b = 0; b < P.n_active; b++) {
-        if (!P.flag[(size_t)b]) { results[b].action = OV2_CKF_NOT_REQUESTED; continue; }
-        ov2_create_keyframe_result &r = results[b];
-        memcpy(&r, h + L.c_rec + sizeof r * (size_t)b, sizeof r);
-        if (P.det && r.nb2detect > 0) {                                     // the detection ran: the reference's adaptation (:546-552 / :418-423)
-            SelectOut so;
-            memcpy(&so, h + L.c_so + sizeof so * (size_t)b, sizeof so);
-            if (P.mode == 0) P.fast_th[b] = det_adapt_fast_th(P.fast_th[b], so.nbkps, so.nbempty);
-            else P.quality[b] = det_adapt_quality(P.quality[b], so.n, P.ncells, so.nboccup);
-        }
-        if (r.action != OV2_CKF_CREATED) continue;
-        const size_t o = nm * (size_t)b, n = (size_t)r.n_kf, n0 = (size_t)r.n_prev;
-        memcpy(out_px_h + 2 * o, h + L.c_px + 8 * o, 8 * n);
-        memcpy(out_lmid_h + o, h + L.c_lm + 4 * o, 4 * n);
-        memcpy(unpx_h + 2 * o, h + L.c_un + 8 * o, 8 * n);
-        memcpy(bv_h + 3 * o, h + L.c_bv + 24 * o, 24 * n);
-        memcpy(color_h + o + n0, h + L.c_col + o + n0, n - n0);
-        if (P.p.use_brief) {
-            memcpy(desc_h + 32 * o, h + L.c_desc + 32 * o, 32 * n);
-            memcpy(valid_h + o, h + L.c_val + o, n);
-        }
-        // the host mirrors, as ov2_btracker_set_keyframe / ov2_btracker_set_keyframe_info leave them
-        const int *perm = (const int *)(h + L.c_perm) + o, *lm = (const int *)(h + L.c_lm) + o;
-        const float *un = (const float *)(h + L.c_un) + 2 * o;
-        const double *bv = (const double *)(h + L.c_bv) + 3 * o;
-        int *kl = (int *)kh + o;
-        float *ku = (float *)(kh + (E.o_ku - E.o_kl)) + 2 * o;
-        double *kb = (double *)(kh + (E.o_kb - E.o_kl)) + 3 * o;
-        for (size_t i = 0; i < n; i++) {
-            const size_t sl = (size_t)perm[i];
-            kl[i] = lm[sl];
-            ku[2 * i] = un[2 * sl]; ku[2 * i + 1] = un[2 * sl + 1];
-            kb[3 * i] = bv[3 * sl]; kb[3 * i + 1] = bv[3 * sl + 1]; kb[3 * i + 2] = bv[3 * sl + 2];
-        }
-        memcpy(&t->kf_hdr[(size_t)b], h + L.c_hdr + sizeof(FeKfHdr) * (size_t)b, sizeof(FeKfHdr));
-        t->res_ki[(size_t)b] = MonoKfInfo{P.nkfid[(size_t)b], r.nb3dkps, 1, 0};
-        t->res_kt[(size_t)b] = P.time[(size_t)b];
-        if (!P.resident) {                                                   // the keyframe is no longer the resident frame, if it was
-            if (!t->res_iskf.empty()) t->res_iskf[(size_t)b] = 0;
-            continue;
-        }
-        // the resident frame's mirror, as k_res_adopt left the device: the old slots, then the new points without a 3-D point
-        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
-        memcpy(dst.px, h + L.c_px + 8 * o, 8 * n);
-        memcpy(dst.lmid, lm, 4 * n);
-        memcpy(dst.is3d, src.is3d, n0);
-        memcpy(dst.wpt, src.wpt, 24 * n0);
-        memset(dst.is3d + n0, 0, n - n0);
-        memset(dst.wpt + 3 * n0, 0, 24 * (n - n0));
-        *dst.n = (int)n;
-        t->res_sel[(size_t)b] ^= 1;
-        t->res_iskf[(size_t)b] = 1;                                      // the resident frame IS the resident keyframe
-    }
-    return OV2_OK;
-}
-
-int ov2_btracker_create_keyframe(ov2_btracker *t, int n_active, const ov2_create_keyframe_params *params,
-                                 const ov2_create_keyframe_input *input, ov2_create_keyframe_result *results, float *out_px_h,
-                                 int *out_lmid_h, float *unpx_h, double *bv_h, uint8_t *desc_h, uint8_t *valid_h, uint8_t *color_h)
-{
-    OV2_REQUIRE(results && out_px_h && out_lmid_h && unpx_h && bv_h && color_h, OV2_EINVAL, "ov2_btracker_create_keyframe: NULL result / output array");
-    OV2_REQUIRE(!params || !params->use_brief || (desc_h && valid_h), OV2_EINVAL, "ov2_btracker_create_keyframe: NULL desc_h / valid_h with use_brief");
-    const int rc = ov2_btracker_create_keyframe_begin(t, n_active, params, input);
-    if (rc != OV2_OK) return rc;
-    return ov2_btracker_create_keyframe_end(t, results, out_px_h, out_lmid_h, unpx_h, bv_h, desc_h, valid_h, color_h);
-}
-
-} // extern "C"
-
-// ---- ov2_btracker_stereo_keyframe (f22) --------------------------------------------------------------------------------------------
-// the call's buffers: the pinned block by the first call, the device block regrown when the grid has more cells than any before
-static int ensure_skf(ov2_btracker *t, int cells)
-{
-    const char *who = "ov2_btracker_stereo_keyframe";
-    const BtSkfLayout L = bt_skf_layout(t->batch, t->cfg.n_max, cells > t->skf_cells ? cells : t->skf_cells);
-    if (!t->hskf) {
-        uint8_t *h = nullptr;
-        const hipError_t e = hipHostMalloc((void **)&h, L.s_down, hipHostMallocDefault);
-        if (e != hipSuccess) { (void)hipGetLastError(); ov2_set_error("%s: %s", who, hipGetErrorString(e)); return OV2_ENOMEM; }
-        memset(h, 0, L.s_down);
-        t->hskf = h;
-    }
-    if (cells > t->skf_cells) {
-        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));              // (an earlier call's kernels have long finished: its _end waited)
-        if (t->dskf) (void)hipFree(t->dskf);
-        t->dskf = nullptr; t->skf_cells = -1;
-        uint8_t *d = nullptr;
-        hipError_t e = hipMalloc((void **)&d, L.dev_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(d, 0, L.dev_bytes, t->ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
-        if (e != hipSuccess) {
-            if (d) (void)hipFree(d);
-            (void)hipGetLastError();
-            ov2_set_error("%s: %s", who, hipGetErrorString(e));
-            return OV2_ENOMEM;
-        }
-        t->dskf = d; t->skf_cells = cells; t->sl = L;
-    }
-    return OV2_OK;
-}
-
-extern "C" {
-
-int ov2_btracker_stereo_keyframe_begin(ov2_btracker *t, int n_active, const ov2_stereo_keyframe_params *params,
-                                       const ov2_pyr *right, const uint8_t *do_h)
-{
-    OV2_REQUIRE(t && params && right && do_h, OV2_EINVAL, "ov2_btracker_stereo_keyframe: NULL tracker / params / right / do_h");
-    const ov2_stereo_keyframe_params &p = *params;
-    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
-    OV2_REQUIRE(n_active <= 65535, OV2_EUNSUPPORTED, "more than 65535 items in one call");
-    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe between steps only: a step is open");
-    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
-    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe_begin: the previous call has not been finished (ov2_btracker_stereo_keyframe_end)");
-    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe: ov2_btracker_temporal_keyframe_begin has not been finished (ov2_btracker_temporal_keyframe_end)");
-    OV2_REQUIRE(t->has_calib, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no calibration set on this tracker");
-    OV2_REQUIRE(t->dfr, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no resident frame on this tracker (ov2_btracker_set_frame)");
-    OV2_REQUIRE(t->frames > 0, OV2_EINVAL, "ov2_btracker_stereo_keyframe: no current frames (no step yet)");
-    const ov2_tracker_config &c = t->cfg;
-    OV2_REQUIRE(c.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
-    const ov2_pyr *left = t->pyr[t->cur];
-    {
-        const PyrDesc &A = left->d, &R = right->d;
-        bool same = R.n_levels == A.n_levels && R.win == A.win;
-        for (int l = 0; same && l < A.n_levels; l++) same = R.lv[l].w == A.lv[l].w && R.lv[l].h == A.lv[l].h;
-        OV2_REQUIRE(R.batch >= n_active, OV2_EINVAL, "ov2_btracker_stereo_keyframe: the right pyramid has fewer items than n_active");
-        OV2_REQUIRE(same, OV2_EINVAL, "ov2_btracker_stereo_keyframe: the right pyramid differs from the tracker's in size, window or level count");
-        OV2_REQUIRE(p.nklt_win_size == A.win, OV2_EINVAL, "ov2_btracker_stereo_keyframe: nklt_win_size is not the pyramids' window");
-        const int w = p.nklt_win_size;
-        OV2_REQUIRE(w == 5 || w == 7 || w == 9 || w == 11 || w == 13, OV2_EUNSUPPORTED, "LK window has no kernel instance (supported: 5,7,9,11,13; the reference ships 9)");
-    }
-    // the right camera, as ov2_stereo_priors checks it
-    OV2_REQUIRE(p.model == OV2_CAM_PINHOLE || p.model == OV2_CAM_FISHEYE, OV2_EINVAL, "unknown camera model");
-    OV2_REQUIRE(p.nD >= 0 && (p.nD == 0 || p.D), OV2_EINVAL, "bad distortion vector: nD < 0 or D == NULL");
-    OV2_REQUIRE(p.nD == 0 || (p.model == OV2_CAM_FISHEYE ? p.nD == 4 : (p.nD == 4 || p.nD == 5 || p.nD == 8 || p.nD == 12)), OV2_EUNSUPPORTED,
-                "unsupported coefficient count: pinhole takes 0 / 4 / 5 / 8 / 12 distortion coefficients, fisheye 0 / 4");
-    OV2_REQUIRE(p.img_w > 0 && p.img_h > 0, OV2_EINVAL, "img_w / img_h not positive");     // false for NaN too
-    OV2_REQUIRE(p.img_w <= 65536 && p.img_h <= 65536, OV2_EINVAL, "img_w / img_h above 65536");
-    const bool rect = p.rect != 0;
-    int nbw = 0, nbh = 0;
-    if (!rect) {
-        OV2_REQUIRE(p.ncellsize > 0, OV2_EINVAL, "ncellsize not positive");
-        nbw = (int)ceilf((float)p.img_w / (float)p.ncellsize);              // Frame's grid (frame.cpp:41-43)
-        nbh = (int)ceilf((float)p.img_h / (float)p.ncellsize);
-        OV2_REQUIRE((long long)nbw * nbh <= OV2_FKF_MAX_CELLS, OV2_EINVAL, "the keypoint grid has more than OV2_FKF_MAX_CELLS (65536) cells");
-    }
-    const int ncells = nbw * nbh;
-    OV2_REQUIRE(p.tri.stereo != 0, OV2_EINVAL, "ov2_btracker_stereo_keyframe: params->tri.stereo == 0 (triangulateStereo runs in stereo mode only)");
-    for (int k = 0; k < 7; k++)
-        OV2_REQUIRE(std::isfinite(p.Tcic0[k]) && std::isfinite(p.tri.Tcic0[k]) && std::isfinite(p.tri.Tlr[k]), OV2_EINVAL, "pose not finite (Tcic0 / tri.Tcic0 / tri.Tlr)");
-    OV2_REQUIRE((size_t)t->batch * (size_t)c.n_max <= 0x7fffffff && (size_t)t->batch * ((size_t)ncells + 1) <= 0x7fffffff, OV2_EUNSUPPORTED,
-                "more than 2^31 - 1 elements of one kind in one call");
-    KpCalib cr;
-    int rc = ov2_kp_calib(p.model, p.K, p.D, p.nD, p.iK, cr);  if (rc != OV2_OK) return rc;
-    ov2_ctx *ctx = t->ctx;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;
-    rc = ensure_mono(t);  if (rc != OV2_OK) return rc;
-    rc = ensure_skf(t, ncells);  if (rc != OV2_OK) return rc;
-    ov2_btracker::SkfPending &P = t->spend;
-    P.n_active = n_active;
-    P.action.assign((size_t)n_active, OV2_SKF_NOT_REQUESTED);
-    const BtSkfLayout &L = t->sl;
-    uint8_t *h = t->hskf, *d = t->dskf;
-    int n_done = 0;
-    size_t total = 0;
-    for (int b = 0; b < n_active; b++) {
-        const int action = !do_h[b] ? OV2_SKF_NOT_REQUESTED : (t->res_iskf[(size_t)b] ? OV2_SKF_DONE : OV2_SKF_NOT_KEYFRAME);
-        P.action[(size_t)b] = (uint8_t)action;
-        h[L.s_act + (size_t)b] = action == OV2_SKF_DONE ? 1 : 0;
-        if (action != OV2_SKF_DONE) continue;
-        n_done++;
-        total += (size_t)*res_host(t, b, 0).n;
-    }
-    t->slot_bytes = 0;
-    P.on = true;
-    if (!n_done) return OV2_OK;
-    // ---- the one enqueue ----
-    const hipStream_t s = ctx->stream;
-    rc = ov2_pyr_wait_ready(ctx, left);  if (rc != OV2_OK) { P.on = false; return rc; }
-    rc = ov2_pyr_wait_ready(ctx, right);  if (rc != OV2_OK) { P.on = false; return rc; }
-    const int lvl = p.nklt_pyr_lvl > left->d.n_levels - 1 ? left->d.n_levels - 1 : (p.nklt_pyr_lvl < 0 ? 0 : p.nklt_pyr_lvl);
-    const float up = (float)(1 << lvl), down = 1.f / up;                    // pow(2, nklt_pyr_lvl) and its inverse (:417-418)
-    const int nm = c.n_max;
-    SkfArgs a;
-    a.f = res_frames(t);
-    a.act = d + L.s_act; a.hdr = (const FeKfHdr *)t->dfx; a.r_ki = (MonoKfInfo *)(t->dres + t->nl.r_ki);
-    a.left = t->calib; a.right = cr;
-    a.n_max = nm; a.rect = rect ? 1 : 0; a.nbw = nbw; a.nbh = nbh; a.cellsize = (float)p.ncellsize; a.down = down;
-    a.pit = (SkfItemD *)(d + L.w_pit); a.tit = (int4 *)(d + L.w_tit); a.Tcw = (double *)(d + L.w_Tcw); a.Twc = (double *)(d + L.w_Twc);
-    a.nd = (int *)(d + L.w_nd);
-    a.px = (float2 *)(d + L.w_px); a.unpx = (float2 *)(d + L.w_un); a.bv = (double *)(d + L.w_bv); a.fw = (double *)(d + L.w_fw);
-    a.top = (float2 *)(d + L.w_top); a.state = d + L.w_st; a.src = (int *)(d + L.w_src);
-    a.cell_start = (int *)(d + L.w_cs); a.cell_kp = (int *)(d + L.w_ck);
-    a.has_prior = d + L.w_hp; a.flag = d + L.w_fl; a.sadx = (float *)(d + L.w_sx);
-    a.lk_out = (const float2 *)(d + L.w_out); a.lk_st = d + L.w_lk; a.gate_ok = d + L.w_ok;
-    a.runpx = (float2 *)(d + L.w_ru); a.rbv = (double *)(d + L.w_rbv); a.is_stereo = d + L.w_is;
-    a.right_px = (float2 *)(d + L.s_rpx); a.stereo_ok = d + L.s_sok; a.tri_status = d + L.s_tst; a.tri_wpt = (const double *)(d + L.s_wpt);
-    a.rec = (ov2_stereo_keyframe_result *)(d + L.s_rec);
-    rc = [&]() -> int {
-        OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.s_up, hipMemcpyHostToDevice, s));
-        int r = res_push_sel(t, s);  if (r != OV2_OK) return r;
-        r = ov2_launch_skf_input(s, a, n_active);  if (r != OV2_OK) return r;
-        if (total > 0) {
-            const int *n_d = a.nd;
-            r = ov2_launch_prior_stereo(s, cr, p.Tcic0, p.img_w, p.img_h, p.ncellsize, nbw, nbh, a.rect, a.pit, a.Tcw, (const float *)a.px,
-                                        (const float *)a.unpx, a.bv, a.fw, a.state, a.cell_start, a.cell_kp, (float *)(d + L.w_pri), d + L.w_hp,
-                                        d + L.w_sk, nm, n_active);
-            if (r != OV2_OK) return r;
-            r = ov2_launch_skf_seed(s, a, n_active);  if (r != OV2_OK) return r;
-            if (rect) {
-                r = ov2_launch_line_min_sad(s, left, right, lvl, 7, 1, (const float *)a.top, nm, a.sadx, (float *)(d + L.w_l1), n_d, n_active);
-                if (r != OV2_OK) return r;
-            }
-            r = ov2_launch_track_klt(s, left, right, p.nklt_win_size, 1, lvl, p.max_iter, p.eps, p.nklt_err, p.fmax_fbklt_dist, nm, n_d,
-                                     (const float *)a.px, (const float *)(d + L.w_pri), a.flag, (float *)(d + L.w_out), d + L.w_lk, nullptr, a.sadx,
-                                     up, ctx->track_impl, n_active, ctx->lk_acc);
-            if (r != OV2_OK) return r;
-            r = ov2_launch_epipolar_check(s, a.rect, p.Frl, cr, (const float *)a.unpx, (float *)(d + L.w_out), nm, (float *)(d + L.w_gru),
-                                          (float *)(d + L.w_err), d + L.w_ok, n_d, n_active);
-            if (r != OV2_OK) return r;
-            r = ov2_launch_skf_stereo_kp(s, a, n_active);  if (r != OV2_OK) return r;
-            r = ov2_launch_triangulate(s, &p.tri, a.tit, a.Twc, nullptr, (const float *)a.unpx, a.bv, (const float *)a.runpx, a.rbv, nullptr, nullptr,
-                                       a.src, a.is_stereo, d + L.s_tst, (double *)(d + L.s_wpt), (double *)(d + L.s_inv), nm, n_active);
-            if (r != OV2_OK) return r;
-        }
-        r = ov2_launch_skf_apply(s, a, n_active);  if (r != OV2_OK) return r;
-        OV2_HIP_CHECK(hipMemcpyAsync(h + L.s_io, d + L.s_io, L.s_down - L.s_io, hipMemcpyDeviceToHost, s));
-        return OV2_OK;
-    }();
-    if (rc != OV2_OK) { (void)hipStreamSynchronize(s); P.on = false; }      // nothing flips: every frame stays what it was
-    return rc;
-}
-
-int ov2_btracker_stereo_keyframe_end(ov2_btracker *t, ov2_stereo_keyframe_result *results, float *right_px_h,
-                                     uint8_t *stereo_ok_h, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    ov2_btracker::SkfPending &P = t->spend;
-    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_stereo_keyframe_end without ov2_btracker_stereo_keyframe_begin");
-    OV2_REQUIRE(results && right_px_h && stereo_ok_h && tri_status_h && wpt_h && invdepth_h, OV2_EINVAL,
-                "ov2_btracker_stereo_keyframe_end: NULL result / output array");
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    P.on = false;
-    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-    const BtSkfLayout &L = t->sl;
-    const uint8_t *h = t->hskf;
-    const size_t nm = (size_t)t->cfg.n_max;
-    for (int b = 0; b < P.n_active; b++) {
-        ov2_stereo_keyframe_result &r = results[b];
-        memset(&r, 0, sizeof r);
-        r.action = P.action[(size_t)b];
-        if (r.action != OV2_SKF_DONE) continue;
-        memcpy(&r, h + L.s_rec + sizeof r * (size_t)b, sizeof r);
-        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
-        const size_t o = nm * (size_t)b, n = (size_t)*src.n;
-        const uint8_t *st = h + L.s_tst + o;
-        const double *w = (const double *)(h + L.s_wpt) + 3 * o;
-        memcpy(right_px_h + 2 * o, h + L.s_rpx + 8 * o, 8 * n);
-        memcpy(stereo_ok_h + o, h + L.s_sok + o, n);
-        memcpy(tri_status_h + o, st, n);
-        memcpy(wpt_h + 3 * o, w, 24 * n);
-        memcpy(invdepth_h + o, h + L.s_inv + 8 * o, 8 * n);
-        // the host mirrors, as k_skf_apply left the device: the frame with the new points, the keyframe's count of 3-D keypoints
-        memcpy(dst.px, src.px, 8 * n);
-        memcpy(dst.lmid, src.lmid, 4 * n);
-        for (size_t i = 0; i < n; i++) {
-            const bool good = (st[i] & OV2_TRI_STEREO_OK) != 0;
-            dst.is3d[i] = good || src.is3d[i] ? 1 : 0;
-            for (int k = 0; k < 3; k++) dst.wpt[3 * i + k] = good ? w[3 * i + k] : src.wpt[3 * i + k];
-        }
-        *dst.n = (int)n;
-        t->res_sel[(size_t)b] ^= 1;
-        t->res_ki[(size_t)b].kf_nb3dkps = r.nb3dkps;
-    }
-    return OV2_OK;
-}
-
-int ov2_btracker_stereo_keyframe(ov2_btracker *t, int n_active, const ov2_stereo_keyframe_params *params, const ov2_pyr *right,
-                                 const uint8_t *do_h, ov2_stereo_keyframe_result *results, float *right_px_h, uint8_t *stereo_ok_h,
-                                 uint8_t *tri_status_h, double *wpt_h, double *invdepth_h)
-{
-    OV2_REQUIRE(results && right_px_h && stereo_ok_h && tri_status_h && wpt_h && invdepth_h, OV2_EINVAL,
-                "ov2_btracker_stereo_keyframe: NULL result / output array");
-    const int rc = ov2_btracker_stereo_keyframe_begin(t, n_active, params, right, do_h);
-    if (rc != OV2_OK) return rc;
-    return ov2_btracker_stereo_keyframe_end(t, results, right_px_h, stereo_ok_h, tri_status_h, wpt_h, invdepth_h);
-}
-
-int ov2_btracker_get_keyframe_info(ov2_btracker *t, int item, int from_device, int *kf_id, double *kf_time, int *kf_nb3dkps, int *has_info)
-{
-    const int rc = mono_item(t, item, "ov2_btracker_get_keyframe_info between steps only: a step is open");
-    if (rc != OV2_OK) return rc;
-    MonoKfInfo ki = t->res_ki[(size_t)item];
-    double kt = t->res_kt[(size_t)item];
-    if (from_device) {
-        const hipStream_t s = t->ctx->stream;
-        OV2_HIP_CHECK(hipMemcpyAsync(&ki, t->dres + t->nl.r_ki + sizeof ki * (size_t)item, sizeof ki, hipMemcpyDeviceToHost, s));
-        OV2_HIP_CHECK(hipMemcpyAsync(&kt, t->dres + t->nl.r_kt + sizeof kt * (size_t)item, sizeof kt, hipMemcpyDeviceToHost, s));
-        OV2_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    if (kf_id) *kf_id = ki.kf_id;
-    if (kf_time) *kf_time = kt;
-    if (kf_nb3dkps) *kf_nb3dkps = ki.kf_nb3dkps;
-    if (has_info) *has_info = ki.has_info;
-    return OV2_OK;
-}
-
-} // extern "C"
-
-// ---- ov2_btracker_temporal_keyframe (f23) and the anchor table -----------------------------------------------------------------------
-// item b of the anchor mirror: its current table (other == 0) or the buffer its next table is written into (other == 1)
-struct AncHost { uint8_t *p; int *n, *lmid, *row; float *unpx; double *bv; int *n_rows, *kfid; double *Twc, *Tcw; };
-static AncHost anc_at(const BtTkfLayout &L, uint8_t *p)
-{
-    return AncHost{p, (int *)(p + L.a_n), (int *)(p + L.a_lm), (int *)(p + L.a_row), (float *)(p + L.a_un), (double *)(p + L.a_bv),
-                   (int *)(p + L.a_nr), (int *)(p + L.a_kf), (double *)(p + L.a_Twc), (double *)(p + L.a_Tcw)};
-}
-static AncHost anc_host(const ov2_btracker *t, int b, int other)
-{
-    const BtTkfLayout &L = t->tl;
-    return anc_at(L, t->hanc + (size_t)(t->anc_sel[(size_t)b] ^ other) * L.buf_bytes + (size_t)b * L.a_item);
-}
-
-static TkfAnchors tkf_anchors(const ov2_btracker *t)
-{
-    const BtTkfLayout &L = t->tl;
-    return TkfAnchors{t->danc, L.buf_bytes, L.a_item, L.a_lm, L.a_row, L.a_un, L.a_bv, L.a_nr, L.a_kf, L.a_Twc, L.a_Tcw, t->dtkf + L.t_sel,
-                      t->cfg.n_max, t->n_src_max};
-}
-
-// the anchor block, its mirror, the call's blocks and the pose block, allocated by the first call that needs them: every table empty
-static int ensure_tkf(ov2_btracker *t, int n_src_max, const char *who)
-{
-    OV2_REQUIRE(n_src_max >= 1 && n_src_max <= OV2_TKF_MAX_ROWS, OV2_EINVAL, "n_src_max outside [1, OV2_TKF_MAX_ROWS (256)]");
-    OV2_REQUIRE(t->cfg.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
-    if (t->danc) {
-        OV2_REQUIRE(n_src_max == t->n_src_max, OV2_EINVAL, "n_src_max differs from the one this tracker's anchor block was allocated with");
-        return OV2_OK;
-    }
-    OV2_REQUIRE((size_t)t->batch * (size_t)t->cfg.n_max <= 0x7fffffff && (size_t)t->batch * (size_t)n_src_max <= 0x7fffffff, OV2_EUNSUPPORTED,
-                "more than 2^31 - 1 elements of one kind in one call");
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    const BtTkfLayout L = bt_tkf_layout(t->batch, t->cfg.n_max, n_src_max);
-    uint8_t *da = nullptr, *ha = nullptr, *dk = nullptr, *hk = nullptr, *dp = nullptr, *hp = nullptr;
-    const hipStream_t s = t->ctx->stream;
-    hipError_t e = hipMalloc((void **)&da, L.anchor_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&ha, L.anchor_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&dk, L.dev_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&hk, L.t_down, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&dp, L.pose_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&hp, L.pose_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemsetAsync(da, 0, L.anchor_bytes, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dk, 0, L.dev_bytes, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dp, 0, L.pose_bytes, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        if (da) (void)hipFree(da);
-        if (ha) (void)hipHostFree(ha);
-        if (dk) (void)hipFree(dk);
-        if (hk) (void)hipHostFree(hk);
-        if (dp) (void)hipFree(dp);
-        if (hp) (void)hipHostFree(hp);
-        (void)hipGetLastError();
-        ov2_set_error("%s: %s", who, hipGetErrorString(e));
-        return OV2_ENOMEM;
-    }
-    memset(ha, 0, L.anchor_bytes);
-    memset(hk, 0, L.t_down);
-    memset(hp, 0, L.pose_bytes);
-    t->danc = da; t->hanc = ha; t->dtkf = dk; t->htkf = hk; t->dap = dp; t->hap = hp;
-    t->tl = L; t->n_src_max = n_src_max;
-    t->anc_sel.assign((size_t)t->batch, 0);
-    return OV2_OK;
-}
-
-// what the calls around the anchor table share: the item, no open call, the block
-static int anc_entry(ov2_btracker *t, int item, const char *open_msg)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
-    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, open_msg);
-    OV2_REQUIRE(t->danc, OV2_EINVAL, "no anchor block on this tracker (ov2_btracker_reserve_anchors / ov2_btracker_temporal_keyframe)");
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    return OV2_OK;
-}
-
-extern "C" {
-
-int ov2_btracker_reserve_anchors(ov2_btracker *t, int n_src_max)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_reserve_anchors between steps only: a step is open");
-    return ensure_tkf(t, n_src_max, "ov2_btracker_reserve_anchors");
-}
-
-int ov2_btracker_set_anchors(ov2_btracker *t, int item, int n, const int *lmid, const int *kfid, const float *unpx, const double *bv,
-                             int n_rows, const int *row_kfid, const double *row_Twc)
-{
-    int rc = anc_entry(t, item, "ov2_btracker_set_anchors between steps only: a step is open");
-    if (rc != OV2_OK) return rc;
-    OV2_REQUIRE(n >= 0 && n <= t->cfg.n_max, OV2_EINVAL, "ov2_btracker_set_anchors: n outside [0, cfg.n_max]");
-    OV2_REQUIRE(n_rows >= 0 && n_rows <= t->n_src_max, OV2_EINVAL, "ov2_btracker_set_anchors: n_rows outside [0, n_src_max]");
-    OV2_REQUIRE(n == 0 || (lmid && kfid && unpx && bv), OV2_EINVAL, "ov2_btracker_set_anchors: NULL array");
-    OV2_REQUIRE(n_rows == 0 || (row_kfid && row_Twc), OV2_EINVAL, "ov2_btracker_set_anchors: NULL array");
-    for (int i = 1; i < n; i++) OV2_REQUIRE(lmid[i - 1] < lmid[i], OV2_EINVAL, "ov2_btracker_set_anchors: lmid unsorted: not strictly ascending");
-    for (int r = 1; r < n_rows; r++) OV2_REQUIRE(row_kfid[r - 1] < row_kfid[r], OV2_EINVAL, "ov2_btracker_set_anchors: row_kfid unsorted: not strictly ascending");
-    std::vector<double> Tcw(7 * (size_t)n_rows);
-    for (int r = 0; r < n_rows; r++) {
-        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(row_Twc[7 * r + c]), OV2_EINVAL, "ov2_btracker_set_anchors: pose not finite (row_Twc)");
-        fe_invert_hd(row_Twc + 7 * r, Tcw.data() + 7 * (size_t)r);
-        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(Tcw[7 * (size_t)r + c]), OV2_EINVAL, "ov2_btracker_set_anchors: pose not finite (the inverse of row_Twc)");
-    }
-    std::vector<int> row((size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int *e = std::lower_bound(row_kfid, row_kfid + n_rows, kfid[i]);
-        OV2_REQUIRE(e != row_kfid + n_rows && *e == kfid[i], OV2_EINVAL, "ov2_btracker_set_anchors: a kfid that is not among the rows");
-        row[(size_t)i] = (int)(e - row_kfid);
-        OV2_REQUIRE(std::isfinite(unpx[2 * i]) && std::isfinite(unpx[2 * i + 1]) && std::isfinite(bv[3 * i]) && std::isfinite(bv[3 * i + 1]) &&
-                    std::isfinite(bv[3 * i + 2]), OV2_EINVAL, "ov2_btracker_set_anchors: unpx / bv not finite");
-    }
-    const AncHost a = anc_host(t, item, 0);
-    *a.n = n; *a.n_rows = n_rows;
-    if (n) { memcpy(a.lmid, lmid, 4 * (size_t)n); memcpy(a.row, row.data(), 4 * (size_t)n); memcpy(a.unpx, unpx, 8 * (size_t)n); memcpy(a.bv, bv, 24 * (size_t)n); }
-    if (n_rows) { memcpy(a.kfid, row_kfid, 4 * (size_t)n_rows); memcpy(a.Twc, row_Twc, 56 * (size_t)n_rows); memcpy(a.Tcw, Tcw.data(), 56 * (size_t)n_rows); }
-    const hipStream_t s = t->ctx->stream;
-    OV2_HIP_CHECK(hipMemcpyAsync(t->danc + (a.p - t->hanc), a.p, t->tl.a_item, hipMemcpyHostToDevice, s));
-    OV2_HIP_CHECK(hipStreamSynchronize(s));
-    return OV2_OK;
-}
-
-int ov2_btracker_get_anchors(ov2_btracker *t, int item, int from_device, int *n, int *lmid, int *kfid, float *unpx, double *bv,
-                             int *n_rows, int *row_kfid, double *row_Twc, double *row_Tcw)
-{
-    int rc = anc_entry(t, item, "ov2_btracker_get_anchors between steps only: a step is open");
-    if (rc != OV2_OK) return rc;
-    const BtTkfLayout &L = t->tl;
-    AncHost a = anc_host(t, item, 0);
-    std::vector<uint8_t> dev;
-    if (from_device) {
-        dev.resize(L.a_item);
-        OV2_HIP_CHECK(hipMemcpyAsync(dev.data(), t->danc + (a.p - t->hanc), L.a_item, hipMemcpyDeviceToHost, t->ctx->stream));
-        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-        a = anc_at(L, dev.data());
-    }
-    const int m = std::min(std::max(*a.n, 0), t->cfg.n_max), mr = std::min(std::max(*a.n_rows, 0), t->n_src_max);
-    if (n) *n = m;
-    if (n_rows) *n_rows = mr;
-    if (lmid) memcpy(lmid, a.lmid, 4 * (size_t)m);
-    if (unpx) memcpy(unpx, a.unpx, 8 * (size_t)m);
-    if (bv) memcpy(bv, a.bv, 24 * (size_t)m);
-    if (kfid) for (int i = 0; i < m; i++) kfid[i] = (a.row[i] >= 0 && a.row[i] < mr) ? a.kfid[a.row[i]] : -1;
-    if (row_kfid) memcpy(row_kfid, a.kfid, 4 * (size_t)mr);
-    if (row_Twc) memcpy(row_Twc, a.Twc, 56 * (size_t)mr);
-    if (row_Tcw) memcpy(row_Tcw, a.Tcw, 56 * (size_t)mr);
-    return OV2_OK;
-}
-
-int ov2_btracker_set_anchor_poses_batch(ov2_btracker *t, int n, const int *item, const int *kfid, const double *Twc, int *n_ignored)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_set_anchor_poses between steps only: a step is open");
-    OV2_REQUIRE(t->danc, OV2_EINVAL, "no anchor block on this tracker (ov2_btracker_reserve_anchors / ov2_btracker_temporal_keyframe)");
-    OV2_REQUIRE(n >= 0 && (size_t)n <= (size_t)t->batch * (size_t)t->n_src_max, OV2_EINVAL, "ov2_btracker_set_anchor_poses: n outside [0, batch x n_src_max]");
-    OV2_REQUIRE(n == 0 || (item && kfid && Twc), OV2_EINVAL, "ov2_btracker_set_anchor_poses: NULL array");
-    std::vector<std::pair<int, int>> keys((size_t)n);
-    for (int k = 0; k < n; k++) {
-        OV2_REQUIRE(item[k] >= 0 && item[k] < t->batch, OV2_EINVAL, "batch item out of range");
-        for (int c = 0; c < 7; c++) OV2_REQUIRE(std::isfinite(Twc[7 * (size_t)k + c]), OV2_EINVAL, "ov2_btracker_set_anchor_poses: pose not finite");
-        keys[(size_t)k] = std::make_pair(item[k], kfid[k]);
-    }
-    std::sort(keys.begin(), keys.end());
-    for (int k = 1; k < n; k++) OV2_REQUIRE(keys[(size_t)k - 1] != keys[(size_t)k], OV2_EINVAL, "ov2_btracker_set_anchor_poses: the same (item, kfid) twice");
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    // the mirror, and the count of the triples that anchor nothing
-    int ignored = 0;
-    for (int k = 0; k < n; k++) {
-        const AncHost a = anc_host(t, item[k], 0);
-        const int mr = std::min(std::max(*a.n_rows, 0), t->n_src_max);
-        const int *e = std::lower_bound(a.kfid, a.kfid + mr, kfid[k]);
-        if (e == a.kfid + mr || *e != kfid[k]) { ignored++; continue; }
-        const size_t r = (size_t)(e - a.kfid);
-        memcpy(a.Twc + 7 * r, Twc + 7 * (size_t)k, 56);
-        fe_invert_hd(Twc + 7 * (size_t)k, a.Tcw + 7 * r);
-    }
-    if (n_ignored) *n_ignored = ignored;
-    if (n == ignored) return OV2_OK;
-    const BtTkfLayout &L = t->tl;
-    const hipStream_t s = t->ctx->stream;
-    memcpy(t->hap + L.p_item, item, 4 * (size_t)n);
-    memcpy(t->hap + L.p_kfid, kfid, 4 * (size_t)n);
-    memcpy(t->hap + L.p_Twc, Twc, 56 * (size_t)n);
-    memcpy(t->htkf + L.t_sel, t->anc_sel.data(), (size_t)t->batch);
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dtkf + L.t_sel, t->htkf + L.t_sel, (size_t)t->batch, hipMemcpyHostToDevice, s));
-    OV2_HIP_CHECK(hipMemcpyAsync(t->dap, t->hap, L.p_Twc + 56 * (size_t)n, hipMemcpyHostToDevice, s));
-    const int rc = ov2_launch_tkf_set_poses(s, tkf_anchors(t), t->batch, n, (const int *)(t->dap + L.p_item), (const int *)(t->dap + L.p_kfid),
-                                            (const double *)(t->dap + L.p_Twc));
-    OV2_HIP_CHECK(hipStreamSynchronize(s));
-    return rc;
-}
-
-int ov2_btracker_set_anchor_poses(ov2_btracker *t, int item, int n, const int *kfid, const double *Twc, int *n_ignored)
-{
-    OV2_REQUIRE(n >= 0 && n <= OV2_TKF_MAX_ROWS, OV2_EINVAL, "ov2_btracker_set_anchor_poses: n outside [0, OV2_TKF_MAX_ROWS]");
-    const std::vector<int> items((size_t)n, item);
-    return ov2_btracker_set_anchor_poses_batch(t, n, items.data(), kfid, Twc, n_ignored);
-}
-
-int ov2_btracker_temporal_keyframe_begin(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params, const uint8_t *do_h)
-{
-    OV2_REQUIRE(t && params && do_h, OV2_EINVAL, "ov2_btracker_temporal_keyframe: NULL tracker / params / do_h");
-    const ov2_temporal_keyframe_params &p = *params;
-    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
-    OV2_REQUIRE(n_active <= 65535, OV2_EUNSUPPORTED, "more than 65535 items in one call");
-    OV2_REQUIRE(!t->pend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe between steps only: a step is open");
-    OV2_REQUIRE(!t->cpend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe: ov2_btracker_create_keyframe_begin has not been finished (ov2_btracker_create_keyframe_end)");
-    OV2_REQUIRE(!t->spend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe: ov2_btracker_stereo_keyframe_begin has not been finished (ov2_btracker_stereo_keyframe_end)");
-    OV2_REQUIRE(!t->tpend.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe_begin: the previous call has not been finished (ov2_btracker_temporal_keyframe_end)");
-    OV2_REQUIRE(t->dfr, OV2_EINVAL, "ov2_btracker_temporal_keyframe: no resident frame on this tracker (ov2_btracker_set_frame)");
-    const ov2_tracker_config &c = t->cfg;
-    OV2_REQUIRE(c.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
-    for (int k = 0; k < 4; k++) OV2_REQUIRE(std::isfinite(p.tri.K[k]), OV2_EINVAL, "ov2_btracker_temporal_keyframe: params->tri.K not finite");
-    for (int k = 0; k < 7; k++)
-        OV2_REQUIRE(std::isfinite(p.tri.Tcic0[k]) && std::isfinite(p.tri.Tlr[k]), OV2_EINVAL, "pose not finite (tri.Tcic0 / tri.Tlr)");
-    ov2_ctx *ctx = t->ctx;
-    OV2_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = ensure_tkf(t, p.n_src_max, "ov2_btracker_temporal_keyframe");  if (rc != OV2_OK) return rc;
-    rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;
-    rc = ensure_mono(t);  if (rc != OV2_OK) return rc;
-    for (int b = 0; b < n_active; b++) {
-        if (!do_h[b] || !t->res_iskf[(size_t)b]) continue;
-        const AncHost a = anc_host(t, b, 0);
-        const int mr = std::min(std::max(*a.n_rows, 0), t->n_src_max);
-        OV2_REQUIRE(mr == 0 || a.kfid[mr - 1] <= t->res_ki[(size_t)b].kf_id, OV2_EINVAL,
-                    "ov2_btracker_temporal_keyframe: an item's anchor table holds a keyframe newer than its resident keyframe");
-    }
-    ov2_btracker::TkfPending &P = t->tpend;
-    P.n_active = n_active;
-    P.action.assign((size_t)n_active, OV2_TKF_NOT_REQUESTED);
-    const BtTkfLayout &L = t->tl;
-    uint8_t *h = t->htkf, *d = t->dtkf;
-    int n_done = 0;
-    for (int b = 0; b < n_active; b++) {
-        const int action = !do_h[b] ? OV2_TKF_NOT_REQUESTED : (t->res_iskf[(size_t)b] ? OV2_TKF_DONE : OV2_TKF_NOT_KEYFRAME);
-        P.action[(size_t)b] = (uint8_t)action;
-        h[L.t_act + (size_t)b] = action == OV2_TKF_DONE ? 1 : 0;
-        n_done += action == OV2_TKF_DONE ? 1 : 0;
-    }
-    memcpy(h + L.t_sel, t->anc_sel.data(), (size_t)t->batch);
-    t->slot_bytes = 0;
-    P.on = true;
-    if (!n_done) return OV2_OK;
-    // ---- the one enqueue ----
-    const hipStream_t s = ctx->stream;
-    const int nm = c.n_max;
-    TkfArgs a;
-    a.f = res_frames(t);
-    a.anc = tkf_anchors(t);
-    a.act = d + L.t_act; a.hdr = (FeKfHdr *)t->dfx; a.r_ki = (MonoKfInfo *)(t->dres + t->nl.r_ki);
-    a.kf_lmid = (int *)(t->depi + t->eL0.o_kl); a.kf_unpx = (float2 *)(t->depi + t->eL0.o_ku); a.kf_bv = (double *)(t->depi + t->eL0.o_kb);
-    a.n_max = nm;
-    a.tit = (int4 *)(d + L.w_tit); a.Twc = (double *)(d + L.w_Twc); a.ovf = (int *)(d + L.w_ovf); a.srcT = (double *)(d + L.w_srcT);
-    a.unpx = (float2 *)(d + L.w_un); a.bv = (double *)(d + L.w_bv); a.src_unpx = (float2 *)(d + L.w_sun); a.src_bv = (double *)(d + L.w_sbv);
-    a.src = (int *)(d + L.w_src); a.is_stereo = d + L.w_is;
-    a.src_kfid = (int *)(d + L.t_skf); a.tri_status = d + L.t_tst; a.tri_wpt = (const double *)(d + L.t_wpt);
-    a.rec = (ov2_temporal_keyframe_result *)(d + L.t_rec);
-    rc = [&]() -> int {
-        OV2_HIP_CHECK(hipMemcpyAsync(d, h, L.t_up, hipMemcpyHostToDevice, s));
-        int r = res_push_sel(t, s);  if (r != OV2_OK) return r;
-        r = ov2_launch_tkf_anchor(s, a, n_active);  if (r != OV2_OK) return r;
-        r = ov2_launch_tkf_input(s, a, n_active);  if (r != OV2_OK) return r;
-        r = ov2_launch_triangulate(s, &p.tri, a.tit, a.Twc, a.srcT, (const float *)a.unpx, a.bv, nullptr, nullptr, (const float *)a.src_unpx,
-                                   a.src_bv, a.src, a.is_stereo, d + L.t_tst, (double *)(d + L.t_wpt), (double *)(d + L.t_inv), nm, n_active);
-        if (r != OV2_OK) return r;
-        r = ov2_launch_tkf_apply(s, a, n_active);  if (r != OV2_OK) return r;
-        OV2_HIP_CHECK(hipMemcpyAsync(h + L.t_io, d + L.t_io, L.t_down - L.t_io, hipMemcpyDeviceToHost, s));
-        return OV2_OK;
-    }();
-    if (rc != OV2_OK) { (void)hipStreamSynchronize(s); P.on = false; }      // nothing flips: every frame and table stays what it was
-    return rc;
-}
-
-int ov2_btracker_temporal_keyframe_end(ov2_btracker *t, ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h,
-                                       double *invdepth_h, int *src_kfid_h)
-{
-    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
-    ov2_btracker::TkfPending &P = t->tpend;
-    OV2_REQUIRE(P.on, OV2_EINVAL, "ov2_btracker_temporal_keyframe_end without ov2_btracker_temporal_keyframe_begin");
-    OV2_REQUIRE(results && tri_status_h && wpt_h && invdepth_h && src_kfid_h, OV2_EINVAL,
-                "ov2_btracker_temporal_keyframe_end: NULL result / output array");
-    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
-    P.on = false;
-    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
-    const BtTkfLayout &L = t->tl;
-    const EpifLayout &E = t->eL0;
-    const uint8_t *h = t->htkf;
-    uint8_t *kh = t->kf_host.data();
-    const size_t nm = (size_t)t->cfg.n_max;
-    for (int b = 0; b < P.n_active; b++) {
-        ov2_temporal_keyframe_result &r = results[b];
-        memset(&r, 0, sizeof r);
-        r.action = P.action[(size_t)b];
-        if (r.action != OV2_TKF_DONE) continue;
-        memcpy(&r, h + L.t_rec + sizeof r * (size_t)b, sizeof r);
-        if (r.action != OV2_TKF_DONE) continue;                          // OV2_TKF_SRC_OVERFLOW: the device wrote nothing else
-        const ResHost src = res_host(t, b, 0), dst = res_host(t, b, 1);
-        const size_t o = nm * (size_t)b, n = (size_t)*src.n;
-        const uint8_t *st = h + L.t_tst + o;
-        const double *w = (const double *)(h + L.t_wpt) + 3 * o;
-        memcpy(tri_status_h + o, st, n);
-        memcpy(wpt_h + 3 * o, w, 24 * n);
-        memcpy(invdepth_h + o, h + L.t_inv + 8 * o, 8 * n);
-        memcpy(src_kfid_h + o, h + L.t_skf + 4 * o, 4 * n);
-        // the anchor mirror, by k_tkf_anchor's rule on the keyframe mirror as it was before the call
-        int *kl = (int *)kh + o;
-        float *ku = (float *)(kh + (E.o_ku - E.o_kl)) + 2 * o;
-        double *kb = (double *)(kh + (E.o_kb - E.o_kl)) + 3 * o;
-        FeKfHdr &hd = t->kf_hdr[(size_t)b];
-        const int n_kf = std::min(std::max(hd.n_kf, 0), (int)nm), kfid = t->res_ki[(size_t)b].kf_id;
-        {
-            const AncHost A = anc_host(t, b, 0), N = anc_host(t, b, 1);
-            const int n_o = std::min(std::max(*A.n, 0), (int)nm), n_ro = std::min(std::max(*A.n_rows, 0), t->n_src_max);
-            if (n_ro > 0 && A.kfid[n_ro - 1] == kfid) {
-                memcpy(N.p, A.p, L.a_item);
-            } else {
-                std::vector<int> jn((size_t)n_kf, -1), ref((size_t)n_ro, 0), nr((size_t)n_ro, 0);
-                for (int i = 0; i < n_kf && n_ro > 0; i++) {
-                    const int *e = std::lower_bound(A.lmid, A.lmid + n_o, kl[i]);
-                    if (e == A.lmid + n_o || *e != kl[i]) continue;
-                    jn[(size_t)i] = (int)(e - A.lmid);
-                    ref[(size_t)std::min(std::max(A.row[e - A.lmid], 0), n_ro - 1)] = 1;
-                }
-                int live = 0;
-                for (int q = 0; q < n_ro; q++) { nr[(size_t)q] = live; live += ref[(size_t)q]; }
-                for (int i = 0; i < n_kf; i++) {
-                    const int j = jn[(size_t)i];
-                    N.lmid[i] = kl[i];
-                    N.row[i] = j >= 0 ? nr[(size_t)std::min(std::max(A.row[j], 0), n_ro - 1)] : live;
-                    memcpy(N.unpx + 2 * i, j >= 0 ? A.unpx + 2 * j : ku + 2 * i, 8);
-                    memcpy(N.bv + 3 * i, j >= 0 ? A.bv + 3 * j : kb + 3 * i, 24);
-                }
-                for (int q = 0; q < n_ro; q++) {
-                    if (!ref[(size_t)q]) continue;
-                    const int x = nr[(size_t)q];
-                    N.kfid[x] = A.kfid[q]; memcpy(N.Twc + 7 * x, A.Twc + 7 * q, 56); memcpy(N.Tcw + 7 * x, A.Tcw + 7 * q, 56);
-                }
-                N.kfid[live] = kfid; memcpy(N.Twc + 7 * live, hd.kf_Twc, 56); memcpy(N.Tcw + 7 * live, hd.kf_Tcw, 56);
-                *N.n = n_kf; *N.n_rows = live + 1;
-            }
-            t->anc_sel[(size_t)b] ^= 1;
-        }
-        // the frame's mirror as k_tkf_apply left the device, and the keyframe's without the OV2_TRI_REMOVE_OBS keypoints
-        memcpy(dst.px, src.px, 8 * n);
-        memcpy(dst.lmid, src.lmid, 4 * n);
-        std::vector<int> gone;
-        for (size_t i = 0; i < n; i++) {
-            const bool good = (st[i] & OV2_TRI_TEMPORAL_OK) != 0;
-            dst.is3d[i] = good || src.is3d[i] ? 1 : 0;
-            for (int k = 0; k < 3; k++) dst.wpt[3 * i + k] = good ? w[3 * i + k] : src.wpt[3 * i + k];
-            if (st[i] & OV2_TRI_REMOVE_OBS) gone.push_back(src.lmid[i]);
-        }
-        *dst.n = (int)n;
-        t->res_sel[(size_t)b] ^= 1;
-        t->res_ki[(size_t)b].kf_nb3dkps = r.nb3dkps;
-        if (!gone.empty()) {
-            std::sort(gone.begin(), gone.end());
-            int m = 0;
-            for (int j = 0; j < n_kf; j++) {
-                if (std::binary_search(gone.begin(), gone.end(), kl[j])) continue;
-                if (m != j) { kl[m] = kl[j]; memcpy(ku + 2 * m, ku + 2 * j, 8); memcpy(kb + 3 * m, kb + 3 * j, 24); }
-                m++;
-            }
-            hd.n_kf = m;
-        }
-    }
-    return OV2_OK;
-}
-
-int ov2_btracker_temporal_keyframe(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params, const uint8_t *do_h,
-                                   ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h,
-                                   int *src_kfid_h)
-{
-    OV2_REQUIRE(results && tri_status_h && wpt_h && invdepth_h && src_kfid_h, OV2_EINVAL,
-                "ov2_btracker_temporal_keyframe: NULL result / output array");
-    const int rc = ov2_btracker_temporal_keyframe_begin(t, n_active, params, do_h);
-    if (rc != OV2_OK) return rc;
-    return ov2_btracker_temporal_keyframe_end(t, results, tri_status_h, wpt_h, invdepth_h, src_kfid_h);
 }
 
 const ov2_pyr *ov2_btracker_cur_pyr(const ov2_btracker *t) { return t ? t->pyr[t->cur] : nullptr; }

@@ -1,4 +1,4 @@
-"""ov2_btracker_create_keyframe (csrc/trackb.hip, csrc/createkf.hip: MapManager::createKeyframe for the flagged items of a lock-step
+"""ov2_btracker_create_keyframe (csrc/trackb_keyframe.hip, csrc/createkf.hip: MapManager::createKeyframe for the flagged items of a lock-step
 batch in one enqueue) against the route of separate calls it replaces (tests/createkf_ref.py: route).  Tracker A plays the rounds of
 tests/createkf_cases.py through route(), tracker B through the fused call, on the same frames; EVERY comparison is on raw bytes: both
 sides run the same device code on the same inputs, so equality is the requirement, not a tolerance.  Compared per round: the records,
@@ -22,6 +22,7 @@ from ov2slam_amd import pose
 from tests import camera_cases as CAM
 from tests import createkf_cases as CC
 from tests import createkf_ref as CR
+from tests import resident_ref as RR
 from tests.match_ref import _inv_act
 from tests.test_gpu_frameepi import _epi_params
 from tests.test_gpu_framepose import _invert, _params
@@ -353,3 +354,63 @@ def test_rejected_calls_leave_the_tracker_usable(gpu_ctx):
                            x["n"], x["make_kf"], x["nlmid"], x["nkfid"], x["time"], p, _state0("singlescale"), Twc=x["Twc"])
     assert err.value.code == L.OV2_EINVAL and "OV2_FKF_MAX_POINTS" in str(err.value)
     big.close()
+
+
+def _ckf_work_bytes(det_cell):
+    """the single-scale detector's work block of a call (csrc: ckf_work): every item's output list, then one pass's response maps,
+    candidates and free-cell lists, each range rounded up to 256 bytes"""
+    up = lambda v: (v + 255) // 256 * 256
+    nc = (W // det_cell) * (H // det_cell)
+    return up(8 * 2 * nc * BATCH) + up(BATCH * nc * det_cell * det_cell * 4) + up(BATCH * nc * 16) + up(BATCH * 4 * (nc + 1))
+
+
+def _views(t):
+    return dict(device=[RR.frame_bytes(t.getFrame(b, True)) for b in range(BATCH)], mirror=[RR.frame_bytes(t.getFrame(b, False)) for b in range(BATCH)],
+                info_device=[t.getKeyframeInfo(b, True) for b in range(BATCH)], info_mirror=[t.getKeyframeInfo(b, False) for b in range(BATCH)])
+
+
+def _grow_play(ctx, small_first):
+    """frame 0, [a call that flags nobody with a detector cell of 64: the work block at its size], round 0 of the scenario, and a
+    trackMono step on frame 1 that reads the keyframes the round installed"""
+    cal = _cal(ctx)
+    t = _tracker(ctx, cal)
+    for b in range(BATCH):
+        t.setPose(b, _truth(b)[0])
+    a, kw = _mono_args(cal, 0, [None] * BATCH)
+    _mono_step(t, a, kw)
+    for b in range(BATCH):
+        t.setPose(b, _truth(b)[0])
+    state = _state0("singlescale")
+    if small_first:
+        x, p = CC.round_inputs(0), dict(CC.round_params(CC.ROUNDS[0], "singlescale"), det_cell=64)
+        before, out = _views(t), _poison()
+        recs, out = t.createKeyframe(4, x["px"], x["lmid"], x["is3d"], x["n"], np.zeros(BATCH, np.uint8), x["nlmid"], x["nkfid"], x["time"], p,
+                                     state, Twc=x["Twc"], out=out)
+        assert [r["action"] for r in recs] == [L.OV2_CKF_NOT_REQUESTED] * 4
+        assert state.tobytes() == _state0("singlescale").tobytes() and all(out[k].tobytes() == v.tobytes() for k, v in _poison().items())
+        assert _views(t) == before
+    recs, out = _round(ctx, t, cal, 0, "singlescale", "fused", state)
+    res = dict(recs=recs, out=out, state=state.copy(), views=_views(t))
+    kf = [(out["px"][b, :r["n_kf"]].copy(), out["lmid"][b, :r["n_kf"]].copy()) if r["action"] == L.OV2_CKF_CREATED else None for b, r in enumerate(recs)]
+    t.setPose(1, _invert(_wrong(_invert(_truth(1)[1]), np.random.default_rng(41), float(cal.K[0]))))          # item 1: the rule fires
+    a, kw = _mono_args(cal, 1, kf)
+    res["step"] = _mono_step(t, a, kw)
+    res["views_after"] = _views(t)
+    t.close()
+    return res
+
+
+def test_a_grown_work_block_changes_nothing(gpu_ctx):
+    """The detector's work block is grow-only.  Tracker A's first call flags nobody and asks for a detector cell of 64, whose work block
+    is smaller than the scenario's: it changes nothing (records, outputs, adaptive state, frames, keyframe info) and A's scenario round
+    then grows the block.  Tracker B plays the round alone on a block allocated at that size.  Records, every output array, the adaptive
+    state, the frames and the keyframe info from the device and from the mirror, and the trackMono step that reads the installed
+    keyframes (the rule fires on item 1: the host re-run reads their mirror) are byte-equal."""
+    assert 0 < _ckf_work_bytes(64) < _ckf_work_bytes(CC.BASE["det_cell"])
+    A, B = _grow_play(gpu_ctx, True), _grow_play(gpu_ctx, False)
+    _same_round(A, B, "grown work block")
+    assert [r["action"] for r in A["recs"]] == [L.OV2_CKF_CREATED] * 4 and all(r["n_new"] > 0 for r in A["recs"])
+    assert A["views"] == B["views"] and A["views"]["info_device"] == A["views"]["info_mirror"]
+    _same_mono_step(A["step"], B["step"], "the step after the grown block")
+    assert A["step"]["rule"][1]
+    assert A["views_after"] == B["views_after"]

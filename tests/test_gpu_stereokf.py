@@ -1,4 +1,4 @@
-"""ov2_btracker_stereo_keyframe (scope row f22; csrc/stereokf.hip, csrc/trackb.hip): the mapper's stereo block on the resident keyframe
+"""ov2_btracker_stereo_keyframe (scope row f22; csrc/stereokf.hip, csrc/trackb_keyframe.hip): the mapper's stereo block on the resident keyframe
 in one lock-step call, against the route of separate calls it replaces (tests/stereokf_ref.py: route).  Tracker A plays the scenario
 through the route, tracker B through the new call; EVERY comparison is on raw bytes: both sides run the same device code on the same
 inputs, so equality is the requirement, not a tolerance, and no point is left out.  Compared after every call: every field of every
@@ -395,3 +395,56 @@ def _changed(ctx, S, **kw):
         else:
             setattr(tgt, f, v)
     return p
+
+
+def _regrow_play(ctx, name, one_cell_first):
+    """the scenario up to its keyframes, [a call that asks nobody on a grid of one cell: the block at that size], the scenario's call
+    (11 x 7 cells) and a call on a coarser grid (6 x 4 cells) -> one entry per stereo call: records, outputs, the four views"""
+    s = _Side(ctx, name, "B", "one")
+    S, cfg, B, t = s.S, s.cfg, s.B, s.t
+    items = S["items"]
+    for b in range(B):
+        t.setPose(b, items[b]["Twc"])
+        s.set_frame(b, items[b]["frame"])
+    s.step([it["left"] for it in items], 0, "first_frame")
+    nbw, nbh = _grid(cfg)
+    s.ckf([1] * B, nbw * nbh, 0, "ckf_main")
+    log = []
+
+    def call(do, params):
+        recs, out = t.stereoKeyframe(B, s.rp, do, params, out=R.empty_out(B, N_MAX, POISON))
+        log.append(dict(recs=recs, out=out, views=s.views(), slot_bytes=t.lastSlotBytes()))
+        return log[-1]
+
+    if one_cell_first:
+        before = s.views()
+        e = call([0] * B, _changed(ctx, S, ncellsize=4 * cfg["w"]))
+        assert [r["action"] for r in e["recs"]] == [NOT_REQUESTED] * B and e["views"] == before
+        assert all((a.view(np.uint8) == POISON).all() for a in e["out"].values())
+        log.clear()
+    call([1] * B, s.skp)
+    call([1] * B, _changed(ctx, S, ncellsize=2 * CELL))
+    t.close()
+    s.rp.close()
+    return log
+
+
+def test_a_regrown_block_changes_nothing(gpu_ctx):
+    """The call's device block is regrown, with a new layout, when a call's grid has more cells than any before.  Tracker A's first
+    call asks nobody on a grid of one cell (the block at that size; nothing changes), its second is the scenario's call (77 cells: the
+    block is regrown), its third has a coarser grid (24 cells: the block stays).  Tracker B makes the two real calls only.  Every
+    record, every output array and the frame and the keyframe info, from the device and from the mirror, are byte-equal."""
+    name = "unrect-radtan"
+    cfg = R.CONFIGS[name]
+    assert int(np.ceil(cfg["w"] / (4 * cfg["w"]))) * int(np.ceil(cfg["h"] / (4 * cfg["w"]))) == 1
+    assert 1 < int(np.ceil(cfg["w"] / (2 * CELL))) * int(np.ceil(cfg["h"] / (2 * CELL))) < _grid(cfg)[0] * _grid(cfg)[1]
+    A, B = _regrow_play(gpu_ctx, name, True), _regrow_play(gpu_ctx, name, False)
+    assert len(A) == len(B) == 2
+    for i, (a, b) in enumerate(zip(A, B)):
+        assert a["recs"] == b["recs"], (i, a["recs"], b["recs"])
+        assert all(r["action"] == DONE for r in a["recs"]) and a["slot_bytes"] == b["slot_bytes"] == 0
+        for k in a["out"]:
+            assert a["out"][k].tobytes() == b["out"][k].tobytes(), (i, k)
+        assert a["views"] == b["views"], i
+        assert a["views"]["device"] == a["views"]["mirror"] and a["views"]["info_device"] == a["views"]["info_mirror"], i
+    assert sum(r["n_stereo_good"] for r in A[0]["recs"]) >= 5 and sum(r["n_prior_nb"] for r in A[0]["recs"]) >= 10

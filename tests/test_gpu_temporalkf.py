@@ -1,4 +1,4 @@
-"""ov2_btracker_temporal_keyframe (scope row f23; csrc/temporalkf.hip, csrc/trackb.hip): Mapper::triangulateTemporal on the resident
+"""ov2_btracker_temporal_keyframe (scope row f23; csrc/temporalkf.hip, csrc/trackb_keyframe.hip): Mapper::triangulateTemporal on the resident
 keyframe in one lock-step call, against the route of separate calls it replaces (tests/temporalkf_ref.py: route, with the host anchor
 walk).  Tracker A plays the script through the route, tracker B through the new call, once as one call and once as two halves.  EVERY
 comparison is on raw bytes: both sides run the same device arithmetic on the same inputs, so equality is the requirement, not a tolerance.
