@@ -178,6 +178,10 @@ int  ov2_pyr_download(ov2_ctx *ctx, const ov2_pyr *p, int b, int level, uint8_t 
 int  ov2_pyr_download_padded(ov2_ctx *ctx, const ov2_pyr *p, int b, int level, uint8_t *img_h, int16_t *deriv_h);
 /* algorithmic HBM bytes of one build of one image (SURVEY.md 8d "B_pyr")       */
 size_t ov2_pyr_algorithmic_bytes(const ov2_pyr *p);
+/* One batch item as it lies in device memory: every level with its borders and the alignment slack between them,
+ * ov2_pyr_item_bytes(p) bytes (the stride between items).  For comparing pyramids byte by byte (tests). */
+size_t ov2_pyr_item_bytes(const ov2_pyr *p);
+int  ov2_pyr_download_item(ov2_ctx *ctx, const ov2_pyr *p, int b, uint8_t *bytes_h);
 
 /* ---- CLAHE ----------------------------------------------------------
  * Replaces cv::CLAHE::apply(img_raw, cur_img_) -- src/visual_front_end.cpp:1159 (left image, every
@@ -2566,6 +2570,52 @@ int  ov2_btracker_temporal_keyframe_end(ov2_btracker *t, ov2_temporal_keyframe_r
 int  ov2_btracker_temporal_keyframe(ov2_btracker *t, int n_active, const ov2_temporal_keyframe_params *params, const uint8_t *do_h,
                                     ov2_temporal_keyframe_result *results, uint8_t *tri_status_h, double *wpt_h, double *invdepth_h,
                                     int *src_kfid_h);
+
+/* ---- the lock-step step from the keyframe: VisualFrontEnd::kltTrackingFromKF (src/visual_front_end.cpp:278-442) -----------------
+ * With btrack_keyframetoframe the reference tracks every frame from the LAST KEYFRAME: the template pyramid is kf_pyr_, a copy of
+ * the current pyramid taken when the keyframe was created (:52-54), and the source point of a keypoint is the keyframe's px_ of
+ * its lmid_ (:336, :346).  ov2_btracker_set_track_from_keyframe(t, 1) puts the step forms that carry lmid --
+ * ov2_btracker_track_frame_epi_pose, ov2_btracker_track_mono, ov2_btracker_track_mono_resident -- into that mode; everything behind
+ * the tracking stage (computeKeypoint, the filter, the pose chain, the mono tail, the resident frame) runs as before.  It differs
+ * from kltTracking in what changes bits:
+ *   source      the keyframe's pyramid (the tracker's KEYFRAME STORE: one more pyramid set of `batch` items outside the rotation) and
+ *               the keyframe's px of the slot's lmid (the KEYFRAME-PX TABLE: per item [lmid ascending][px], a snapshot taken when the
+ *               keyframe was created and only ever looked up by lmid)
+ *   membership  a slot whose lmid the item's resident keyframe (ov2_btracker_set_keyframe / _create_keyframe, compacted by
+ *               ov2_btracker_temporal_keyframe) no longer holds, or the px table never held, is not tracked: status 4 (bit 2, "not
+ *               in the keyframe"), out_xy = its input px.  Every stage behind tests bit 0 or (status & 3) == 1 and treats it as a
+ *               lost track, which is what the reference does with it (:316-320, :348-351); it takes no part in the 33 % rule
+ *   priors      a slot without a 3-D prior starts from the frame's own px (:343-345), not from its source point
+ *   retry       a 3-D-prior slot the one-level pass lost is retried on the full pyramid from the frame's own px (:386), not from
+ *               the first pass's forward result; status bit 1 as before
+ *   33 % rule   counted over the slots that entered the prior pass.  When it fires, `vpriors = vkps` (:395-400) resets every prior
+ *               of the second call: each slot whose result comes from that call (no prior, or bit 1 set) is run again from the
+ *               keyframe's item on the full pyramid with prior = the keyframe's px; good prior-pass tracks are kept.  p3p_req and
+ *               the re-run of the chains behind follow as in the other mode
+ * ov2_btracker_last_priors returns the flag byte the join left: bit 0 the slot entered the prior pass, bit 1 (value 2) it was
+ * skipped.
+ *
+ * ov2_btracker_set_track_from_keyframe   between steps only.  The first `on` allocates the store (OV2_ENOMEM leaves the tracker as it
+ *     was, mode off).  While on: the step forms without lmid (ov2_btracker_track_frame, _map, _pose) return OV2_EINVAL; a step in
+ *     which an active item carries keypoints but has no adopted keyframe pyramid returns OV2_EINVAL before anything is enqueued (the
+ *     reference's `pkf == nullptr` return); ov2_btracker_create_keyframe (both forms) adopts the current pyramid item and installs the
+ *     px table of every OV2_CKF_CREATED item in its own enqueue.  While off every call enqueues exactly what it did before; the store
+ *     and its contents stay, but an item whose keyframe is replaced while the mode is off (ov2_btracker_create_keyframe creates it,
+ *     or ov2_btracker_set_keyframe sets it) loses its adopted pyramid: the store's belongs to the keyframe before, and a step with the
+ *     mode on again refuses the item until a pyramid is adopted.  With the mode on, ov2_btracker_set_keyframe leaves the adoption as it
+ *     is: the caller that builds keyframes on the host follows it with ov2_btracker_set_keyframe_px and
+ *     ov2_btracker_adopt_keyframe_pyramid.
+ * The calls below need the store (OV2_EINVAL before the first `on`) and run between steps only:
+ * ov2_btracker_adopt_keyframe_pyramid    the current pyramid item of every item b < n_active with do_h[b] != 0 becomes its keyframe
+ *     pyramid (one copy kernel, one synchronisation): for callers that build keyframes on the host
+ * ov2_btracker_set_keyframe_px           the px table of one item: n <= cfg.n_max entries, lmid strictly ascending, px finite
+ * ov2_btracker_get_keyframe_px           the table back, from the host mirror or (from_device != 0) from the device
+ * ov2_btracker_kf_item                   item `item` of the store as a batch-1 view (owned by the tracker; NULL without a store)     */
+int  ov2_btracker_set_track_from_keyframe(ov2_btracker *t, int on);
+int  ov2_btracker_adopt_keyframe_pyramid(ov2_btracker *t, int n_active, const uint8_t *do_h);
+int  ov2_btracker_set_keyframe_px(ov2_btracker *t, int item, int n, const int *lmid, const float *px);
+int  ov2_btracker_get_keyframe_px(ov2_btracker *t, int item, int from_device, int *n, int *lmid, float *px);
+const ov2_pyr *ov2_btracker_kf_item(const ov2_btracker *t, int item);
 
 #ifdef __cplusplus
 }

@@ -769,6 +769,13 @@ SIGNATURES = {
     "ov2_btracker_temporal_keyframe_end": (_i, [_vp, C.POINTER(TemporalKeyframeResult), _vp, _vp, _vp, _vp]),
     "ov2_btracker_temporal_keyframe": (_i, [_vp, _i, C.POINTER(TemporalKeyframeParams), _vp, C.POINTER(TemporalKeyframeResult),
                                             _vp, _vp, _vp, _vp]),
+    "ov2_pyr_item_bytes": (C.c_size_t, [_vp]),
+    "ov2_pyr_download_item": (_i, [_vp, _vp, _i, _vp]),
+    "ov2_btracker_set_track_from_keyframe": (_i, [_vp, _i]),
+    "ov2_btracker_adopt_keyframe_pyramid": (_i, [_vp, _i, _vp]),
+    "ov2_btracker_set_keyframe_px": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ov2_btracker_get_keyframe_px": (_i, [_vp, _i, _i, C.POINTER(_i), _vp, _vp]),
+    "ov2_btracker_kf_item": (_vp, [_vp, _i]),
 }
 
 OV2_ABI_VERSION = 600          # include/ov2slam_hip.h

@@ -179,6 +179,12 @@ int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur,
                          int track_impl = OV2_TRACK_IMPL_WAVE,
                          int items = 1,    // items > 1 (trackb.hip): batch items [0, items) of both pyramids, n_max point slots and one n_dev entry per item
                          int lk_acc = OV2_LK_ACC_INT64);   // OV2_OPT_LK_ACC   // items > 1 (trackb.hip): batch items [0, items) of both pyramids, n_max point slots and one n_dev entry per item
+// fused VisualFrontEnd::kltTrackingFromKF launch (lk.hip): kf is the keyframe's pyramid, kps the keyframe's px, a lost prior track is
+// retried from retry_prior, flag bit 1 skips a slot (status 4); the kernel choice is ov2_launch_track_klt's
+int ov2_launch_track_klt_kf(hipStream_t s, const ov2_pyr *kf, const ov2_pyr *cur, int win, int lvl_prior, int lvl_full,
+                            int max_iter, float eps, float err_th, float fb_dist, int n_max, const int *n_dev,
+                            const float *kps, const float *priors, const float *retry_prior, const uint8_t *flags, float *out_xy,
+                            uint8_t *status, int *iters, int track_impl = OV2_TRACK_IMPL_WAVE, int items = 1, int lk_acc = OV2_LK_ACC_INT64);
 // The cross-keypoint rule of visual_front_end.cpp:225-230 over the n results of one frame (track.hip; both trackers call it): when
 // fewer than 33 % of the prior tracks are good, the lost ones are run again from their keypoints between the two pyramids (one item
 // each), out_xy / status take the new results and *p3p_req (may be NULL) is set.  calib != NULL: unpx (2 per keypoint) and bv (3 per

@@ -563,6 +563,53 @@ __global__ __launch_bounds__(64) void k_track_klt(PyrDesc P, PyrDesc C, LKParams
     }
 }
 
+// VisualFrontEnd::kltTrackingFromKF (src/visual_front_end.cpp:278-442) in ONE launch, the row-per-lane form of k_track_klt_kf_w
+// (lkw.hip states the contract): P is the keyframe's pyramid, kps the keyframe's px, a lost prior track is retried from
+// retry_prior (the frame's current px, :386), flag bit 1 skips the slot with status 4.
+template <int WIN, bool FACC>
+__global__ __launch_bounds__(64) void k_track_klt_kf(PyrDesc P, PyrDesc C, LKParams prm, int lvl_prior, int lvl_full,
+                                                     const int *__restrict__ n_dev, const float2 *__restrict__ kps,
+                                                     const float2 *__restrict__ priors, const float2 *__restrict__ retry_prior,
+                                                     const uint8_t *__restrict__ flags, float2 *__restrict__ out_xy,
+                                                     uint8_t *__restrict__ status, int *__restrict__ iters_out)
+{
+    const int item = blockIdx.y;
+    const int n = n_dev ? n_dev[item] : prm.n_max;
+    const int r = threadIdx.x & 15;
+    const int il = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4);
+    if (il >= n) return;
+    const int i = item * prm.n_max + il;
+    const uint8_t *pb = P.base + (long long)item * P.item_stride, *cb = C.base + (long long)item * C.item_stride;
+    const float2 kp = kps[i];
+    const int fl = flags[i];
+    if (fl & 2) {                                                         // whole 16-lane rows take the same side
+        if (r == 0) {
+            out_xy[i] = kp;
+            status[i] = 4;
+            if (iters_out) iters_out[i] = 0;
+        }
+        return;
+    }
+    float2 pr = priors[i];
+    const bool has_prior = (fl & 1) != 0;
+    int max_level = has_prior ? lvl_prior : lvl_full;
+    int ok = 0, retried = 0, iters = 0;
+    float fx = 0.f, fy = 0.f;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        LKPointState st;
+        ok = fb_track_point<WIN, FACC>(pb, cb, P, C, prm, max_level, kp, pr, r, fx, fy, st);
+        iters += st.iters;
+        if (ok || !has_prior || attempt == 1) break;
+        pr = retry_prior[i];                                              // visual_front_end.cpp:386
+        max_level = lvl_full; retried = 1;
+    }
+    if (r == 0) {
+        out_xy[i] = make_float2(fx, fy);
+        status[i] = (uint8_t)(ok | (retried << 1));
+        if (iters_out) iters_out[i] = iters;
+    }
+}
+
 // folds (and clears) the per-slot partial sums of one LK launch into the caller's {iterations, patch builds}
 __global__ __launch_bounds__(LK_STAT_SLOTS) void k_lk_stats_fold(unsigned long long *__restrict__ slots, long long *__restrict__ stats)
 {
@@ -666,6 +713,20 @@ static LKParams make_params(const ov2_pyr *pyr, int win, int max_level, int max_
     return prm;
 }
 
+// what the two fused launchers below share: the geometry check, the parameter block and the two level counts (lf: the full pyramid,
+// clamped to the levels there are like feature_tracker.cpp:50-52; lp: the prior pass)
+static int track_klt_setup(const ov2_pyr *prev, const ov2_pyr *cur, int win, int lvl_prior, int lvl_full, int max_iter, float eps, float err_th,
+                           float fb_dist, int n_max, int items, LKParams &prm, int &lp, int &lf)
+{
+    const PyrDesc &P = prev->d, &C = cur->d;
+    OV2_REQUIRE(P.n_levels == C.n_levels && items >= 1 && P.batch >= items && C.batch >= items && P.win == C.win && win == P.win, OV2_EINVAL,
+                "tracker pyramids differ in geometry");
+    prm = make_params(prev, win, lvl_full, max_iter, eps, OV2_LK_USE_INITIAL_FLOW | OV2_LK_GET_MIN_EIGENVALS, err_th, fb_dist, 1, n_max);
+    lf = prm.max_level;
+    lp = lvl_prior > P.n_levels - 1 ? P.n_levels - 1 : (lvl_prior < 0 ? 0 : lvl_prior);
+    return OV2_OK;
+}
+
 // launcher of the fused kltTracking kernel (used by track.hip); all pointers are device memory, *n_dev <= n_max
 int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur, int win, int lvl_prior, int lvl_full,
                          int max_iter, float eps, float err_th, float fb_dist, int n_max, const int *n_dev,
@@ -673,12 +734,9 @@ int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur,
                          const float *sad_x, float sad_up, int track_impl, int items, int lk_acc)
 {
     const PyrDesc &P = prev->d, &C = cur->d;
-    OV2_REQUIRE(P.n_levels == C.n_levels && items >= 1 && P.batch >= items && C.batch >= items && P.win == C.win && win == P.win, OV2_EINVAL,
-                "tracker pyramids differ in geometry");
-    LKParams prm = make_params(prev, win, lvl_full, max_iter, eps, OV2_LK_USE_INITIAL_FLOW | OV2_LK_GET_MIN_EIGENVALS,
-                               err_th, fb_dist, 1, n_max);
-    const int lf = prm.max_level;                                  // clamped to the pyramid like feature_tracker.cpp:50-52
-    const int lp = lvl_prior > P.n_levels - 1 ? P.n_levels - 1 : (lvl_prior < 0 ? 0 : lvl_prior);
+    LKParams prm;
+    int lp, lf;
+    if (int rc = track_klt_setup(prev, cur, win, lvl_prior, lvl_full, max_iter, eps, err_th, fb_dist, n_max, items, prm, lp, lf)) return rc;
     // window 9 (the reference's): the wavefront-per-keypoint kernel (lkw.hip) -- the 81 window pixels over all 64 lanes, the next
     // level's search block requested while the current level iterates.  Other windows (and OV2_OPT_TRACK_IMPL = ROW): the
     // row-per-lane kernel, four keypoints per wavefront
@@ -701,6 +759,40 @@ int ov2_launch_track_klt(hipStream_t s, const ov2_pyr *prev, const ov2_pyr *cur,
         return OV2_EUNSUPPORTED;
     }
 #undef OV2_TK
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
+// launcher of the fused kltTrackingFromKF kernel (trackb.hip): ov2_launch_track_klt's choice of kernel -- window 9 takes the wave
+// kernel, other windows and OV2_TRACK_IMPL_ROW the row kernel; kf: the keyframe store's pyramids
+int ov2_launch_track_klt_kf(hipStream_t s, const ov2_pyr *kf, const ov2_pyr *cur, int win, int lvl_prior, int lvl_full,
+                            int max_iter, float eps, float err_th, float fb_dist, int n_max, const int *n_dev,
+                            const float *kps, const float *priors, const float *retry_prior, const uint8_t *flags, float *out_xy,
+                            uint8_t *status, int *iters, int track_impl, int items, int lk_acc)
+{
+    const PyrDesc &P = kf->d, &C = cur->d;
+    LKParams prm;
+    int lp, lf;
+    if (int rc = track_klt_setup(kf, cur, win, lvl_prior, lvl_full, max_iter, eps, err_th, fb_dist, n_max, items, prm, lp, lf)) return rc;
+    if (win == 9 && track_impl == OV2_TRACK_IMPL_WAVE)
+        return ov2_launch_track_klt_kf_w(s, P, C, prm, lp, lf, n_max, n_dev, kps, priors, retry_prior, flags, out_xy, status, iters, items, lk_acc);
+    constexpr int kpw = 4;
+    dim3 grid((n_max + kpw - 1) / kpw, items), block(16 * kpw);
+#define OV2_TKF(W) do { if (lk_acc == OV2_LK_ACC_FLOAT_UI4) hipLaunchKernelGGL((k_track_klt_kf<W, true>), grid, block, 0, s, P, C, prm, lp, lf, n_dev, (const float2 *)kps, \
+                                      (const float2 *)priors, (const float2 *)retry_prior, flags, (float2 *)out_xy, status, iters); \
+                        else hipLaunchKernelGGL((k_track_klt_kf<W, false>), grid, block, 0, s, P, C, prm, lp, lf, n_dev, (const float2 *)kps, \
+                                      (const float2 *)priors, (const float2 *)retry_prior, flags, (float2 *)out_xy, status, iters); } while (0)
+    switch (win) {
+    case 5:  OV2_TKF(5); break;
+    case 7:  OV2_TKF(7); break;
+    case 9:  OV2_TKF(9); break;
+    case 11: OV2_TKF(11); break;
+    case 13: OV2_TKF(13); break;
+    default:
+        ov2_set_error("LK window %d has no kernel instance (supported: 5,7,9,11,13; the reference ships 9)", win);
+        return OV2_EUNSUPPORTED;
+    }
+#undef OV2_TKF
     OV2_HIP_CHECK(hipGetLastError());
     return OV2_OK;
 }

@@ -16,3 +16,7 @@ struct LKParams {
 int ov2_launch_track_klt_w(hipStream_t s, const PyrDesc &P, const PyrDesc &C, const LKParams &prm, int lp, int lf, int n_max, const int *n_dev,
                            const float *kps, const float *priors, const uint8_t *flags, float *out_xy, uint8_t *status, int *iters,
                            const float *sad_x, float sad_up, int items = 1, int lk_acc = OV2_LK_ACC_INT64);
+// the from-keyframe sibling (VisualFrontEnd::kltTrackingFromKF): plus retry_prior, flag bit 1 = the slot is skipped (status 4)
+int ov2_launch_track_klt_kf_w(hipStream_t s, const PyrDesc &P, const PyrDesc &C, const LKParams &prm, int lp, int lf, int n_max, const int *n_dev,
+                              const float *kps, const float *priors, const float *retry_prior, const uint8_t *flags, float *out_xy,
+                              uint8_t *status, int *iters, int items = 1, int lk_acc = OV2_LK_ACC_INT64);

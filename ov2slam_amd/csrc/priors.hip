@@ -43,6 +43,8 @@ __global__ __launch_bounds__(PRI_THREADS) void k_prior_frame(KpCalib c, double i
         const float2 pr = kp_project_dist(c, cam.x, cam.y, cam.z);                 // :165
         if (pri_in_image(pr, img_w, img_h)) { out = pr; hp = 1; }                  // :168
     }
+    // (kltkf.hip's k_kf_join and the from-keyframe tracking kernels rely on exactly this for a slot without a projection, klt_use_prior
+    // == 0 included: prior = the frame's own px and flag 0 -- kltTrackingFromKF starts such a slot there, visual_front_end.cpp:343-345)
     prior[g] = out;
     has_prior[g] = hp;
 }

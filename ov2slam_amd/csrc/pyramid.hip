@@ -496,6 +496,19 @@ int ov2_pyr_download_padded(ov2_ctx *ctx, const ov2_pyr *p, int b, int level, ui
     return pyr_download_impl(ctx, p, b, level, img_h, deriv_h, 1);
 }
 
+size_t ov2_pyr_item_bytes(const ov2_pyr *p) { return p ? (size_t)p->d.item_stride : 0; }
+
+int ov2_pyr_download_item(ov2_ctx *ctx, const ov2_pyr *p, int b, uint8_t *bytes_h)
+{
+    OV2_REQUIRE(ctx && p && bytes_h, OV2_EINVAL, "NULL argument");
+    OV2_REQUIRE(b >= 0 && b < p->d.batch, OV2_EINVAL, "bad batch index");
+    OV2_HIP_CHECK(hipSetDevice(ctx->device));
+    if (int rcw = ov2_pyr_wait_ready(ctx, p)) return rcw;
+    OV2_HIP_CHECK(hipMemcpyAsync(bytes_h, p->d.base + (long long)b * p->d.item_stride, (size_t)p->d.item_stride, hipMemcpyDeviceToHost, ctx->stream));
+    OV2_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return OV2_OK;
+}
+
 size_t ov2_pyr_algorithmic_bytes(const ov2_pyr *p)
 {
     if (!p) return 0;

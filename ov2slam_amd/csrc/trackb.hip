@@ -176,10 +176,12 @@ static void btracker_free(ov2_btracker *t)
         if (t->dimg[i]) (void)hipFree(t->dimg[i]);
         if (t->draw[i]) (void)hipFree(t->draw[i]);
     }
+    for (ov2_pyr *v : t->kf_view) ov2_pyr_destroy(v);
+    ov2_pyr_destroy(t->kf_store);
     for (IoBlock *b : {&t->pt, &t->map, &t->pose, &t->epi, &t->mono}) b->release();
     if (t->depi) (void)hipFree(t->depi);
     for (DevBlock *b : {&t->res, &t->mw, &t->work, &t->fx, &t->det, &t->out, &t->roi, &t->ckf, &t->ckw, &t->fr, &t->ctl, &t->skf, &t->anc, &t->tkf,
-                        &t->ap})
+                        &t->ap, &t->kfpx})
         b->release();
     delete t;
 }
@@ -272,9 +274,25 @@ static int enqueue_klt(ov2_btracker *t, const ov2_pyr *prev, const ov2_pyr *cur,
                                     k + pl.o_flg, c.n_max, n);
         if (rc != OV2_OK) return rc;
     }
-    rc = ov2_launch_track_klt(s, prev, cur, c.win, c.prior_pyr_lvl, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist,
-                              c.n_max, (const int *)(k + pl.o_n), (const float *)(k + pl.o_kps), (const float *)(k + pl.o_pri),
-                              k + pl.o_flg, (float *)(k + pl.o_out), k + pl.o_st, nullptr, nullptr, 0.f, ctx->track_impl, n, ctx->lk_acc);
+    if (P.from_kf) {
+        // kltTrackingFromKF: `prev` is the keyframe store.  k_kf_join puts the keyframe's px where the tracking kernel reads its source
+        // points and flags the slots the keyframe no longer holds; the frame's own px is the retry prior (visual_front_end.cpp:386)
+        const BtEpiLayout &el = t->el;
+        if (!res && P.form == STEP_EPI) { rc = t->epi.upload(s, el.e_lm, el.e_nk);  if (rc) return rc; }     // the ids, ahead of the filter's upload
+        KfJoinArgs j;
+        j.tab = kfpx_table(t);
+        j.n_dev = (const int *)(k + pl.o_n); j.lmid = (const int *)(t->epi.k + el.e_lm);
+        j.hdr = (const FeKfHdr *)t->fx.d; j.kf_lmid = (const int *)(t->depi + t->eL0.o_kl);
+        j.kps = (const float2 *)(k + pl.o_kps); j.src = (float2 *)(t->kfpx.d + t->kl.w_src); j.flags = k + pl.o_flg;
+        rc = ov2_launch_kf_join(s, j, n);
+        if (rc != OV2_OK) return rc;
+        rc = ov2_launch_track_klt_kf(s, prev, cur, c.win, c.prior_pyr_lvl, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist, c.n_max,
+                                     j.n_dev, (const float *)j.src, (const float *)(k + pl.o_pri), (const float *)(k + pl.o_kps), k + pl.o_flg,
+                                     (float *)(k + pl.o_out), k + pl.o_st, nullptr, ctx->track_impl, n, ctx->lk_acc);
+    } else
+        rc = ov2_launch_track_klt(s, prev, cur, c.win, c.prior_pyr_lvl, c.nklt_pyr_lvl, c.max_iter, c.eps, c.err_th, c.fb_dist,
+                                  c.n_max, (const int *)(k + pl.o_n), (const float *)(k + pl.o_kps), (const float *)(k + pl.o_pri),
+                                  k + pl.o_flg, (float *)(k + pl.o_out), k + pl.o_st, nullptr, nullptr, 0.f, ctx->track_impl, n, ctx->lk_acc);
     if (rc != OV2_OK) return rc;
     if (t->has_calib) {
         rc = ov2_launch_compute_keypoints(s, t->calib, (const float *)(k + pl.o_out), c.n_max, (const int *)(k + pl.o_n),
@@ -506,6 +524,11 @@ KfHost kf_host_item(ov2_btracker *t, int b)
     uint8_t *kh = t->kf_host.data();
     const size_t o = (size_t)b * (size_t)t->cfg.n_max;
     return KfHost{(int *)kh + o, (float *)(kh + (E.o_ku - E.o_kl)) + 2 * o, (double *)(kh + (E.o_kb - E.o_kl)) + 3 * o};
+}
+
+KfPxTable kfpx_table(const ov2_btracker *t)
+{
+    return KfPxTable{t->kfpx.d, t->kl.k_item, t->kl.k_lm, t->kl.k_px, t->cfg.n_max};
 }
 
 // the filter's inputs of a step into hepi
@@ -864,7 +887,7 @@ int ov2_btracker_create(ov2_ctx *ctx, const ov2_tracker_config *cfg, int batch, 
     t->img_bytes = bt_img_bytes(cfg->w, cfg->h);
     t->pl = bt_point_layout(batch, cfg->n_max); t->ml = bt_map_layout(batch, cfg->n_max);
     t->ql = bt_pose_layout(batch, cfg->n_max); t->el = bt_epi_layout(batch, cfg->n_max); t->nl = bt_mono_layout(batch, cfg->n_max);
-    t->cl = bt_ckf_layout(batch, cfg->n_max); t->rl = bt_res_layout(batch, cfg->n_max);
+    t->cl = bt_ckf_layout(batch, cfg->n_max); t->rl = bt_res_layout(batch, cfg->n_max); t->kl = bt_kfpx_layout(batch, cfg->n_max);
     hipError_t e = hipSuccess;
     for (int i = 0; i < BT_IMG_SETS && e == hipSuccess; i++) {
         e = hipHostMalloc((void **)&t->himg[i], t->img_bytes * batch + 256, hipHostMallocDefault);
@@ -1004,6 +1027,14 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
         OV2_REQUIRE(n >= 0 && (size_t)n <= nm, OV2_EINVAL, "an item carries more keypoints than cfg.n_max slots");
         n_total += n;
     }
+    if (t->from_kf) {
+        // kltTrackingFromKF joins the frame with its keyframe by lmid, and tracks from the keyframe's pyramid (the reference's
+        // `pkf == nullptr` early return, visual_front_end.cpp:308-310, is a refusal here)
+        OV2_REQUIRE(epi || mono, OV2_EINVAL, "the tracker tracks from the keyframe (ov2_btracker_set_track_from_keyframe): this form of the step carries no lmid");
+        for (int b = 0; b < n_active && t->frames > 0; b++)
+            OV2_REQUIRE(!(n_h && n_h[b] > 0) || t->kf_has_pyr[(size_t)b], OV2_EINVAL,
+                        "the tracker tracks from the keyframe: an item with keypoints has no adopted keyframe pyramid");
+    }
     if (map) OV2_REQUIRE(n_total == 0 || A.resident || (A.kps_xy_h && A.wpt_h && A.is3d_h && (mono || A.Tcw_h) && n_h), OV2_EINVAL, "NULL point buffer");
     else OV2_REQUIRE(n_total == 0 || (A.kps_xy_h && A.prior_xy_h && n_h), OV2_EINVAL, "NULL point buffer");
     const ov2_frame_pose_params *pp = A.pp;
@@ -1066,6 +1097,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
     if (epi) { P.ep = epp->epi; P.eL = epiL; }
     P.mono = mono; P.mono_ran = mono && t->frames > 0;
     P.resident = A.resident;
+    P.from_kf = t->from_kf;
     if (mono) {
         P.fkf = epp->epi.fkf;
         P.time.assign(A.min->time_h, A.min->time_h + n_active);
@@ -1093,7 +1125,7 @@ static int track_frame_begin(ov2_btracker *t, const StepArgs &A)
             if (t->pt.d) res_fill_host(t, n_active);
         }
         r = preprocess();
-        return r ? r : enqueue_klt(t, t->pyr[t->prev()], t->pyr[t->cur], P);
+        return r ? r : enqueue_klt(t, P.from_kf ? t->kf_store : t->pyr[t->prev()], t->pyr[t->cur], P);
     };
     // the first frame (trackMono returns right after preprocessImage) and a step with nothing to track anywhere only pre-process
     const bool tracked = t->frames > 0 && n_total > 0;
@@ -1416,8 +1448,14 @@ static int track_frame_end_step(ov2_btracker *t, float *out_xy_h, uint8_t *statu
         // the rule on the item's views; the re-derived unpx / bv go to the item's rows of the point block
         const P3pRuleFrame f = {P.kps + 2 * o, P.has_prior ? P.has_prior + o : nullptr, P.use_prior, (int)n, out_xy_h + 2 * o, status_h + o,
                                 (float *)(hblk + pl.o_unpx) + 2 * o, (double *)(hblk + pl.o_bv) + 3 * o};
-        const int rc = ov2_apply_p3p_rule(ctx, t->cfg, t->view[t->prev()][b], t->view[t->cur][b], t->has_calib ? &t->calib : nullptr, f,
-                                          &rule[(size_t)b]);
+        int rc;
+        if (P.from_kf) {
+            const uint8_t *tab = t->kfpx.h + (size_t)b * t->kl.k_item;
+            const KfRuleFrame g = {(const int *)(t->epi.h + t->el.e_lm) + o, (const int *)(tab + t->kl.k_lm), (const float *)(tab + t->kl.k_px),
+                                   *(const int *)tab, P.has_prior + o, (int)n, f.out_xy, f.status, f.unpx, f.bv};
+            rc = ov2_apply_p3p_rule_kf(ctx, t->cfg, t->kf_view[(size_t)b], t->view[t->cur][b], t->has_calib ? &t->calib : nullptr, g, &rule[(size_t)b]);
+        } else
+            rc = ov2_apply_p3p_rule(ctx, t->cfg, t->view[t->prev()][b], t->view[t->cur][b], t->has_calib ? &t->calib : nullptr, f, &rule[(size_t)b]);
         if (rc != OV2_OK) return rc;
         if (p3p_req) p3p_req[b] = rule[(size_t)b];
         if (t->has_calib) t->last_n[(size_t)b] = (int)n;
@@ -1646,6 +1684,7 @@ int ov2_btracker_set_keyframe(ov2_btracker *t, int item, int n_kf, const int *kf
     }
     t->kf_hdr[(size_t)item] = h;
     if (!t->res_iskf.empty()) t->res_iskf[(size_t)item] = 0;
+    if (!t->from_kf && !t->kf_has_pyr.empty()) t->kf_has_pyr[(size_t)item] = 0;      // a keyframe set with the mode off: the store's is stale
     OV2_HIP_CHECK(hipMemcpyAsync(t->fx.d + sizeof(FeKfHdr) * (size_t)item, &t->kf_hdr[(size_t)item], sizeof(FeKfHdr), hipMemcpyHostToDevice, s));
     OV2_HIP_CHECK(hipStreamSynchronize(s));                              // the host copy may be rewritten by the next call
     return OV2_OK;

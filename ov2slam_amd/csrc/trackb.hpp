@@ -14,6 +14,7 @@
 #include "temporalkf_dev.hpp"
 #include "mvg_dev.hpp"
 #include "fkf_dev.hpp"
+#include "kltkf_dev.hpp"
 #include "trackb_layout.hpp"
 #include <deque>
 #include <initializer_list>
@@ -160,7 +161,8 @@ struct ov2_btracker {
                      // mono: the step runs between the motion model and the decision; ran: not the tracker's first frame
                      bool mono = false, mono_ran = false; ov2_fkf_params fkf; std::vector<double> time;
                      std::vector<int> frame_id, localba;
-                     bool resident = false; } pend;       // the frame is the resident one; k_res_carry wrote the next one
+                     bool resident = false;               // the frame is the resident one; k_res_carry wrote the next one
+                     bool from_kf = false; } pend;        // the step tracked from the keyframe store (kltTrackingFromKF)
     // the raw frames of the current step: items [0, raw_n) of dimg[raw_which], until that set is uploaded / prepared again (describeBRIEF)
     int raw_which = -1, raw_n = 0;
     // ov2_btracker_create_keyframe, allocated by its first call: the I/O block (pinned, and its device mirror at the same offsets:
@@ -170,7 +172,7 @@ struct ov2_btracker {
     DevBlock ckf, ckw;
     struct CkfPending { bool det = false; int n_active = 0, mode = 0, ncells = 0; ov2_create_keyframe_params p;
                         double *quality = nullptr; int *fast_th = nullptr; std::vector<uint8_t> flag; std::vector<int> nkfid;
-                        std::vector<double> time; bool resident = false; } cpend;
+                        std::vector<double> time; bool resident = false, from_kf = false; } cpend;
     // the resident frame (f21), allocated by its first use: the frame block (two buffers of `batch` items: BtResLayout) with its
     // pinned host mirror of the same layout, the control block of a call (pinned, and its device mirror), and per item the buffer
     // that holds the current frame
@@ -194,6 +196,15 @@ struct ov2_btracker {
     DevBlock anc, tkf, ap;
     std::vector<uint8_t> anc_sel;
     struct TkfPending { int n_active = 0; std::vector<uint8_t> action; } tpend;
+    // the from-keyframe mode (ov2_btracker_set_track_from_keyframe; kltkf.hip), allocated by its first `on`: the keyframe store -- one
+    // more pyramid set of `batch` items outside the rotation, with its item views -- the keyframe-px table with its pinned mirror
+    // (BtKfPxLayout), and per item whether a pyramid has been adopted
+    bool from_kf = false;
+    ov2_pyr *kf_store = nullptr;
+    std::vector<ov2_pyr *> kf_view;
+    BtKfPxLayout kl;
+    DevBlock kfpx;
+    std::vector<uint8_t> kf_has_pyr;
     // the call between a _begin and its _end: at most one at a time (begin_guard)
     OpenCall open = CALL_NONE;
     bool open_call() const { return open != CALL_NONE; }
@@ -213,3 +224,4 @@ int res_push_sel(ov2_btracker *t, hipStream_t s);                // which buffer
 // item b's keyframe arrays in kf_host (the block's [o_kl, o_up) as the layout without rows puts them)
 struct KfHost { int *lmid; float *unpx; double *bv; };
 KfHost kf_host_item(ov2_btracker *t, int b);
+KfPxTable kfpx_table(const ov2_btracker *t);                     // the device view of the keyframe-px table

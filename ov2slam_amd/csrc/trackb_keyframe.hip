@@ -134,6 +134,7 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
     P.nkfid.assign(in.nkfid_h, in.nkfid_h + n_active);
     P.time.assign(in.time_h, in.time_h + n_active);
     P.resident = resident;
+    P.from_kf = t->from_kf;
     t->slot_bytes = 0;
     // ---- the inputs into the pinned block ----
     const BtCkfLayout &L = t->cl;
@@ -216,6 +217,14 @@ int ov2_btracker_create_keyframe_begin(ov2_btracker *t, int n_active, const ov2_
         }
         r = ov2_launch_ckf_install(s, a, n_active);  if (r != OV2_OK) return r;
         if (resident) { r = ov2_launch_res_adopt(s, ra, n_active);  if (r != OV2_OK) return r; }
+        if (P.from_kf) {
+            // kf_pyr_ = cur_pyr_ (visual_front_end.cpp:52-54) and the keyframe's px_ of every CREATED item, in the same enqueue
+            KfPxInstallArgs ka;
+            ka.tab = kfpx_table(t);
+            ka.make_kf = a.flag; ka.rec = a.rec; ka.px = a.px; ka.lmid = a.lmid; ka.perm = a.perm; ka.adopt = t->kfpx.d + t->kl.k_flag;
+            r = ov2_launch_kfpx_install(s, ka, n_active);  if (r != OV2_OK) return r;
+            r = ov2_launch_kfpyr_adopt(s, pyr->d, t->kf_store->d, ka.adopt, n_active);  if (r != OV2_OK) return r;
+        }
         return t->ckf.down(s, L.c_io, p.use_brief ? L.c_down : L.c_desc);
     }();
     if (rc != OV2_OK) { (void)hipStreamSynchronize(s); return rc; }      // the call stays closed, like its siblings'
@@ -272,6 +281,18 @@ int ov2_btracker_create_keyframe_end(ov2_btracker *t, ov2_create_keyframe_result
         memcpy(&t->kf_hdr[(size_t)b], h + L.c_hdr + sizeof(FeKfHdr) * (size_t)b, sizeof(FeKfHdr));
         t->res_ki[(size_t)b] = MonoKfInfo{P.nkfid[(size_t)b], r.nb3dkps, 1, 0};
         t->res_kt[(size_t)b] = P.time[(size_t)b];
+        if (P.from_kf) {                                                     // the px table's mirror, as k_kfpx_install left the device
+            uint8_t *tab = t->kfpx.h + (size_t)b * t->kl.k_item;
+            int *tl = (int *)(tab + t->kl.k_lm);
+            float *tp = (float *)(tab + t->kl.k_px);
+            const float *px = (const float *)(h + L.c_px) + 2 * o;
+            for (size_t i = 0; i < n; i++) {
+                const size_t sl = (size_t)perm[i];
+                tl[i] = lm[sl]; tp[2 * i] = px[2 * sl]; tp[2 * i + 1] = px[2 * sl + 1];
+            }
+            *(int *)tab = (int)n;
+            t->kf_has_pyr[(size_t)b] = 1;
+        } else if (!t->kf_has_pyr.empty()) t->kf_has_pyr[(size_t)b] = 0;    // a keyframe created with the mode off: the store's is stale
         if (!P.resident) {                                                   // the keyframe is no longer the resident frame, if it was
             if (!t->res_iskf.empty()) t->res_iskf[(size_t)b] = 0;
             continue;
@@ -300,6 +321,131 @@ int ov2_btracker_create_keyframe(ov2_btracker *t, int n_active, const ov2_create
     const int rc = ov2_btracker_create_keyframe_begin(t, n_active, params, input);
     if (rc != OV2_OK) return rc;
     return ov2_btracker_create_keyframe_end(t, results, out_px_h, out_lmid_h, unpx_h, bv_h, desc_h, valid_h, color_h);
+}
+
+} // extern "C"
+
+// ---- the from-keyframe mode: the keyframe store (kltkf.hip) ---------------------------------------------------------------------
+static void kf_store_release(ov2_btracker *t)
+{
+    for (ov2_pyr *v : t->kf_view) ov2_pyr_destroy(v);
+    t->kf_view.clear();
+    ov2_pyr_destroy(t->kf_store);
+    t->kf_store = nullptr;
+    t->kfpx.release();
+}
+
+// the store, allocated by the first `on`: all of it or nothing
+static int ensure_kf_store(ov2_btracker *t)
+{
+    if (t->kf_store) return OV2_OK;
+    const char *who = "ov2_btracker_set_track_from_keyframe";
+    const ov2_tracker_config &c = t->cfg;
+    OV2_REQUIRE(c.n_max <= OV2_FKF_MAX_POINTS, OV2_EINVAL, "capacity: cfg.n_max exceeds OV2_FKF_MAX_POINTS (2048) keypoints of one frame");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    int rc = ov2_pyr_create(t->ctx, c.w, c.h, c.win, c.nklt_pyr_lvl, t->batch, &t->kf_store);
+    for (int b = 0; b < t->batch && rc == OV2_OK; b++) {
+        ov2_pyr *v = nullptr;
+        rc = ov2_pyr_item_view(t->kf_store, b, &v);
+        if (rc == OV2_OK) t->kf_view.push_back(v);
+    }
+    if (rc == OV2_OK) rc = t->kfpx.alloc(t->kl.host_bytes, t->kl.dev_bytes, t->ctx->stream, who);
+    if (rc != OV2_OK) {
+        (void)hipGetLastError();
+        kf_store_release(t);
+        return rc;
+    }
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));                 // the store's zero fill
+    t->kf_has_pyr.assign((size_t)t->batch, 0);
+    return OV2_OK;
+}
+
+extern "C" {
+
+int ov2_btracker_set_track_from_keyframe(ov2_btracker *t, int on)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_set_track_from_keyframe between steps only: a step or a keyframe call is open");
+    if (on) {
+        int rc = ensure_epi(t, nullptr);  if (rc != OV2_OK) return rc;       // the resident keyframe's lists: membership
+        rc = ensure_kf_store(t);  if (rc != OV2_OK) return rc;
+    }
+    t->from_kf = on != 0;
+    return OV2_OK;
+}
+
+int ov2_btracker_adopt_keyframe_pyramid(ov2_btracker *t, int n_active, const uint8_t *do_h)
+{
+    OV2_REQUIRE(t && do_h, OV2_EINVAL, "ov2_btracker_adopt_keyframe_pyramid: NULL tracker / do_h");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_adopt_keyframe_pyramid between steps only: a step or a keyframe call is open");
+    OV2_REQUIRE(t->kf_store, OV2_EINVAL, "ov2_btracker_adopt_keyframe_pyramid: no keyframe store (ov2_btracker_set_track_from_keyframe)");
+    OV2_REQUIRE(n_active >= 1 && n_active <= t->batch, OV2_EINVAL, "n_active out of range");
+    OV2_REQUIRE(t->frames > 0, OV2_EINVAL, "ov2_btracker_adopt_keyframe_pyramid: no current frames (no step yet)");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const hipStream_t s = t->ctx->stream;
+    const ov2_pyr *pyr = t->pyr[t->cur];
+    int rc = ov2_pyr_wait_ready(t->ctx, pyr);  if (rc != OV2_OK) return rc;
+    const size_t o = t->kl.k_flag;
+    for (int b = 0; b < n_active; b++) t->kfpx.h[o + (size_t)b] = do_h[b] ? 1 : 0;
+    rc = t->kfpx.up(s, o, o + (size_t)n_active);  if (rc != OV2_OK) return rc;
+    rc = ov2_launch_kfpyr_adopt(s, pyr->d, t->kf_store->d, t->kfpx.d + o, n_active);  if (rc != OV2_OK) return rc;
+    OV2_HIP_CHECK(hipStreamSynchronize(s));
+    for (int b = 0; b < n_active; b++) if (do_h[b]) t->kf_has_pyr[(size_t)b] = 1;
+    return OV2_OK;
+}
+
+int ov2_btracker_set_keyframe_px(ov2_btracker *t, int item, int n, const int *lmid, const float *px)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(n >= 0 && n <= t->cfg.n_max, OV2_EINVAL, "ov2_btracker_set_keyframe_px: n outside [0, cfg.n_max]");
+    OV2_REQUIRE(n == 0 || (lmid && px), OV2_EINVAL, "ov2_btracker_set_keyframe_px: NULL array");
+    for (int i = 0; i < n; i++) {
+        OV2_REQUIRE(i == 0 || lmid[i - 1] < lmid[i], OV2_EINVAL, "ov2_btracker_set_keyframe_px: lmid unsorted or repeated: not strictly ascending");
+        OV2_REQUIRE(std::isfinite(px[2 * i]) && std::isfinite(px[2 * i + 1]), OV2_EINVAL, "ov2_btracker_set_keyframe_px: px not finite");
+    }
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_set_keyframe_px between steps only: a step or a keyframe call is open");
+    OV2_REQUIRE(t->kf_store, OV2_EINVAL, "ov2_btracker_set_keyframe_px: no keyframe store (ov2_btracker_set_track_from_keyframe)");
+    OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+    const BtKfPxLayout &K = t->kl;
+    const size_t o = (size_t)item * K.k_item;
+    uint8_t *tab = t->kfpx.h + o;
+    *(int *)tab = n;
+    if (n) { memcpy(tab + K.k_lm, lmid, 4 * (size_t)n); memcpy(tab + K.k_px, px, 8 * (size_t)n); }
+    const int rc = t->kfpx.up(t->ctx->stream, o, o + K.k_item);  if (rc != OV2_OK) return rc;
+    OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+    return OV2_OK;
+}
+
+int ov2_btracker_get_keyframe_px(ov2_btracker *t, int item, int from_device, int *n, int *lmid, float *px)
+{
+    OV2_REQUIRE(t, OV2_EINVAL, "NULL tracker");
+    OV2_REQUIRE(item >= 0 && item < t->batch, OV2_EINVAL, "batch item out of range");
+    OV2_REQUIRE(!t->open_call(), OV2_EINVAL, "ov2_btracker_get_keyframe_px between steps only: a step or a keyframe call is open");
+    OV2_REQUIRE(t->kf_store, OV2_EINVAL, "ov2_btracker_get_keyframe_px: no keyframe store (ov2_btracker_set_track_from_keyframe)");
+    const BtKfPxLayout &K = t->kl;
+    const size_t o = (size_t)item * K.k_item;
+    const uint8_t *p = t->kfpx.h + o;
+    std::vector<uint8_t> dev;
+    if (from_device) {
+        OV2_HIP_CHECK(hipSetDevice(t->ctx->device));
+        dev.resize(K.k_item);
+        OV2_HIP_CHECK(hipMemcpyAsync(dev.data(), t->kfpx.d + o, K.k_item, hipMemcpyDeviceToHost, t->ctx->stream));
+        OV2_HIP_CHECK(hipStreamSynchronize(t->ctx->stream));
+        p = dev.data();
+    }
+    int m;
+    memcpy(&m, p, 4);
+    m = m < 0 ? 0 : (m > t->cfg.n_max ? t->cfg.n_max : m);
+    if (n) *n = m;
+    if (lmid) memcpy(lmid, p + K.k_lm, 4 * (size_t)m);
+    if (px) memcpy(px, p + K.k_px, 8 * (size_t)m);
+    return OV2_OK;
+}
+
+const ov2_pyr *ov2_btracker_kf_item(const ov2_btracker *t, int item)
+{
+    return t && t->kf_store && item >= 0 && item < t->batch ? t->kf_view[(size_t)item] : nullptr;
 }
 
 } // extern "C"

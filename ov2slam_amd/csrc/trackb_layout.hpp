@@ -229,3 +229,22 @@ static inline BtTkfLayout bt_tkf_layout(int batch, int n_max, int n_src_max)
     L.p_item = q.take(4 * rows); L.p_kfid = q.take(4 * rows); L.p_Twc = q.take(56 * rows); L.pose_bytes = q.off;
     return L;
 }
+
+// The keyframe store of the from-keyframe mode (ov2_btracker_set_track_from_keyframe).  The KEYFRAME-PX TABLE: per item the distorted
+// px of every keypoint its keyframe had when it was created, ITEM-MAJOR like the resident frame, with a pinned host mirror of the same
+// layout.  A snapshot that is only ever looked up by lmid: membership is the resident keyframe's own list.
+//   one item    [n 4, padded to 16][lmid 4][px 8 per slot, ascending by lmid], k_item bytes (a multiple of 256)
+// Behind the table, in the same block: [adopt flag 1 per item] (pinned too: ov2_btracker_adopt_keyframe_pyramid sends it up) and,
+// device only, the source point of every slot of a step [src 8 per slot] (k_kf_join writes it, the tracking kernel reads it).
+struct BtKfPxLayout { size_t k_n, k_lm, k_px, k_item, table_bytes, k_flag, host_bytes, w_src, dev_bytes; };
+static inline BtKfPxLayout bt_kfpx_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, nm = (size_t)n_max, slots = nm * B;
+    BtKfPxLayout L;
+    StageCursor f(16);
+    L.k_n = f.take(4); L.k_lm = f.take(4 * nm); L.k_px = f.take(8 * nm);
+    L.k_item = up256(f.off); L.table_bytes = L.k_item * B;
+    L.k_flag = L.table_bytes; L.host_bytes = up256(L.k_flag + B);
+    L.w_src = L.host_bytes; L.dev_bytes = up256(L.w_src + 8 * slots);
+    return L;
+}

@@ -200,6 +200,12 @@ class Pyramid:
         L.check(fn(self.ctx.h, self.h_pyr, b, level, _ptr(img), _ptr(der)))
         return img, der
 
+    def download_item(self, b=0):
+        """item b as it lies in device memory (every level, its borders, the slack between them): a uint8 array of the item stride"""
+        raw = np.empty(int(self.lib.ov2_pyr_item_bytes(self.h_pyr)), np.uint8)
+        L.check(self.lib.ov2_pyr_download_item(self.ctx.h, self.h_pyr, int(b), _ptr(raw)))
+        return raw
+
     @property
     def algorithmic_bytes(self):
         return self.lib.ov2_pyr_algorithmic_bytes(self.h_pyr)
@@ -353,6 +359,7 @@ class _PyrView:
     levels = Pyramid.levels
     level_size = Pyramid.level_size
     download = Pyramid.download
+    download_item = Pyramid.download_item
 
 
 class VisualFrontEndTracker:
@@ -1314,6 +1321,43 @@ class LockstepTracker:
 
     def prev_item(self, item):
         return _PyrView(self.ctx, C.c_void_p(self.lib.ov2_btracker_prev_item(self.h_trk, int(item))), self.w, self.h, self.win)
+
+    # ---- tracking from the keyframe: VisualFrontEnd::kltTrackingFromKF (ov2_btracker_set_track_from_keyframe) ----------------------
+    def setTrackFromKeyframe(self, on=True):
+        """btrack_keyframetoframe: while on, trackFrameEpiPose, trackMono and trackMonoResident track every frame from the item's last
+        keyframe -- its pyramid in the tracker's keyframe store, its px from the keyframe-px table, joined by lmid -- instead of the
+        previous frame, and createKeyframe adopts the pyramid and installs the table of every item it creates.  status 4 marks a
+        slot the keyframe no longer holds.  The first call allocates the store.  Between steps only."""
+        L.check(self.lib.ov2_btracker_set_track_from_keyframe(self.h_trk, 1 if on else 0))
+
+    def adoptKeyframePyramid(self, n_active, do):
+        """the current pyramid of every item b < n_active with do[b] becomes its keyframe pyramid (ov2_btracker_adopt_keyframe_pyramid):
+        for keyframes built on the host.  Between steps only."""
+        d = np.zeros(max(1, int(n_active)), np.uint8)
+        d[:int(n_active)] = np.asarray(do, np.uint8).reshape(-1)[:int(n_active)] != 0
+        L.check(self.lib.ov2_btracker_adopt_keyframe_pyramid(self.h_trk, int(n_active), _ptr(d)))
+
+    def setKeyframePx(self, item, lmid, px):
+        """the keyframe-px table of item `item` (ov2_btracker_set_keyframe_px): lmid (n,) strictly ascending, px (n, 2) finite, the
+        keyframe's distorted pixel of every id."""
+        lm = np.ascontiguousarray(lmid, np.int32).reshape(-1)
+        px = np.ascontiguousarray(px, np.float32).reshape(-1, 2)
+        if len(lm) != len(px):
+            raise ValueError("one px per lmid")
+        L.check(self.lib.ov2_btracker_set_keyframe_px(self.h_trk, int(item), len(lm), _ptr(lm), _ptr(px)))
+
+    def getKeyframePx(self, item, from_device=True):
+        """the keyframe-px table of item `item` -> dict(n, lmid (n,), px (n, 2)), from the device or the host mirror"""
+        n = C.c_int()
+        lm, px = np.zeros(self.n_max, np.int32), np.zeros((self.n_max, 2), np.float32)
+        L.check(self.lib.ov2_btracker_get_keyframe_px(self.h_trk, int(item), int(bool(from_device)), C.byref(n), _ptr(lm), _ptr(px)))
+        k = n.value
+        return dict(n=k, lmid=lm[:k].copy(), px=px[:k].copy())
+
+    def kf_item(self, item):
+        """item `item` of the keyframe store as a batch-1 pyramid view (None before the first setTrackFromKeyframe)"""
+        h = self.lib.ov2_btracker_kf_item(self.h_trk, int(item))
+        return _PyrView(self.ctx, C.c_void_p(h), self.w, self.h, self.win) if h else None
 
     def close(self):
         if getattr(self, "h_trk", None):
