@@ -8,6 +8,7 @@
 //   k_clahe_apply : 4 pixels per thread (dword load/store), bilinear blend of the four tile LUTs
 #include "common.hpp"
 #include "xcd_map.hpp"
+#include "clahe_plan.hpp"
 #include <math.h>
 #include <mutex>
 #include <type_traits>
@@ -32,6 +33,7 @@ struct ClaheParams {
                          // into ~60 short row bands so that it does not run on 10 CUs only -- latency)
     // strip kernel (k_clahe_apply_pyr): column strips per image, level 1 of the pyramid next to the level-0 destination
     int nstrips, nlut;   // nlut: LUT wavefronts of the fused form
+    int row_hist;        // fused form: the histograms in the row form (clahe_plan.hpp)
     long long l1_delta;  // byte offset of level 1's ROI pixel (0, 0) from the dst ROI pointer
     int l1_pitch, l1_w, l1_h;
 };
@@ -61,15 +63,52 @@ __device__ __forceinline__ void clahe_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#define CH_WAVE_DW 256               // dwords of a one-copy histogram
-#define CH_CSTRIDE 264               // dwords between the copies of a multi-copy histogram: bin b of copy c sits in LDS bank (b + 8 c) % 64
-#define CH_NCOPY 4                   // copies of the wavefronts that histogram most tiles (k_clahe_lut; the LUT wavefronts of the fused kernel)
-                                     // (other copy counts: profiles/r5_clahe_histogram_variants.txt)
-#define CH_MULTI_DW (CH_NCOPY * CH_CSTRIDE)
+// (CH_WAVE_DW, CH_CSTRIDE, CH_NCOPY, CH_MULTI_DW: clahe_plan.hpp)
 typedef uint32_t c_u32x4 __attribute__((ext_vector_type(4)));
 
 template <int CTRL>
 __device__ __forceinline__ int c_dpp0(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }   // out-of-row sources read 0
+
+// Clip, redistribution, inclusive scan and LUT of ONE tile from its histogram: the lane holds bins 4 lane .. 4 lane + 3 in hv and
+// gets its four LUT bytes.  One copy for both forms of the histogram (clahe_lut_tiles, clahe_lut_row_hist).
+__device__ __forceinline__ uint32_t clahe_lut_tail(const ClaheParams &P, int lane, int (&hv)[4])
+{
+    const int sub = lane >> 4;
+    if (P.clip > 0) {
+        int over = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { over += max(hv[k] - P.clip, 0); hv[k] = min(hv[k], P.clip); }
+        over += c_dpp0<0xB1>(over); over += c_dpp0<0x4E>(over); over += c_dpp0<0x124>(over); over += c_dpp0<0x128>(over);   // row totals
+        const int clipped = __builtin_amdgcn_readlane(over, 0) + __builtin_amdgcn_readlane(over, 16) +
+                            __builtin_amdgcn_readlane(over, 32) + __builtin_amdgcn_readlane(over, 48);
+        const int batch = clipped >> 8, residual = clipped & 255;
+        // serial loop `for (i = 0; i < 256 && residual > 0; i += step, residual--) hist[i]++` : bin gets +1 iff
+        // bin % step == 0 && bin / step < residual, step = max(256 / residual, 1)
+        int step = residual ? (int)(256.0f / (float)residual) : 1;          // exact: |256 - r n| >= 1
+        int q = (int)((float)(4 * lane) / (float)step), r = 4 * lane - q * step;    // exact for the same reason
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            hv[k] += batch + ((residual != 0 && r == 0 && q < residual) ? 1 : 0);
+            r++;
+            if (r == step) { r = 0; q++; }
+        }
+    }
+    // inclusive scan over the 256 bins: in-lane prefix, DPP scan inside the 16-lane rows, row offsets by readlane
+    hv[1] += hv[0]; hv[2] += hv[1]; hv[3] += hv[2];
+    int v = hv[3];
+    v += c_dpp0<0x111>(v); v += c_dpp0<0x112>(v); v += c_dpp0<0x114>(v); v += c_dpp0<0x118>(v);      // row_shr:1,2,4,8 (zero fill)
+    const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31), r2 = __builtin_amdgcn_readlane(v, 47);
+    const int rowoff = sub == 0 ? 0 : (sub == 1 ? r0 : (sub == 2 ? r0 + r1 : r0 + r1 + r2));
+    const int base = v + rowoff - hv[3];
+    uint32_t packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int r = __float2int_rn((float)(hv[k] + base) * P.lut_scale);   // saturate_cast<uchar>(float)
+        r = r < 0 ? 0 : (r > 255 ? 255 : r);
+        packed |= (uint32_t)r << (8 * k);
+    }
+    return packed;
+}
 
 // The tiles t, t + tstride, .. < t_end of ONE image, by one wavefront with its own 256-bin histogram `hw` in LDS; store_lut(t, packed)
 // receives the lane's four LUT bytes (bins 4 lane .. 4 lane + 3) of tile t.  Shared by k_clahe_lut (LUTs to HBM) and the fused
@@ -209,40 +248,104 @@ __device__ __forceinline__ void clahe_lut_tiles(const ClaheParams &P, const uint
             histogram(tn);
             if (tn + tstride < ntiles && tile_fast(tn + tstride)) tile_load(tn + tstride, cur, cur_ph);
         }
-        if (P.clip > 0) {
-            int over = 0;
+        const uint32_t packed = clahe_lut_tail(P, lane, hv);
+        store_lut(t, packed);
+    }
+}
+
+// ---- row form of the fused kernel's histograms (clahe_plan.hpp: ov2_clahe_row_form) ------------------------------------------
+// The tile form above spends a third of its ds_adds and three quarters of its loads on empty lanes at EuRoC's 51 x 54 tiles (16 lanes
+// for a 51-byte tile row, 64 candidate rows for 54).  Here a wavefront walks WHOLE image rows of a row of tiles: a lane owns 12
+// consecutive bytes of the row (one 12-byte load per lane and row, 192 dwords per trip, wider rows in further trips), so every
+// ds_add spans all tiles of the row -- 646 instead of 960 per row of tiles, 54 loads instead of 240.  All histograms of the row of
+// tiles are live at once: 16-bit counters, tiles 2 p and 2 p + 1 in the halves of the dwords of pair block p (CH_CSTRIDE dwords
+// apart: equal grey levels of different pairs fall into different banks).  A tile's padded pixels number tw * th < 65536, so no
+// half overflows into the other.
+// What a byte adds and where is a lane constant: the pair block of its tile and 0 / 1 / 2 in that tile's half -- 0 outside the
+// image or owned by the lane before, 2 for a column that also stands for a REFLECT_101 column right of the image (clahe_lut_tiles:
+// tile_fast; the plan guarantees that those columns lie in the last tile).  A lane whose 12 bytes would end beyond the row's last
+// dword loads the row's last 12 bytes instead and counts only the bytes that are its own.  A row that also stands for a padded
+// row below the image is added twice (wave-uniform).
+typedef uint32_t c_u32x3 __attribute__((ext_vector_type(3)));
+#define CH_ROW_AHEAD 4               // rows in flight per lane
+
+struct ClaheRowLane {
+    uint32_t off;                    // byte offset of the lane's 12 bytes in an image row
+    uint32_t base[12], val[12];      // per byte: LDS byte offset of its tile's pair block, weight in the tile's half of the dword
+    bool mine;                       // some byte has a weight
+};
+
+__device__ __forceinline__ void clahe_row_lane(const ClaheParams &P, int lane, int chunk, ClaheRowLane &K)
+{
+    const int x0 = 4 * (CH_ROW_CHUNK_DW * chunk + 3 * lane);
+    const int xs = min(x0, 4 * ((P.w + 3) >> 2) - 12);              // (w >= 64: host-checked)
+    const int dbl_lo = 2 * P.w - 2 - P.tiles_x * P.tw;              // columns in (dbl_lo, w - 2] also stand for a padded column
+    K.off = (uint32_t)xs;
+    K.mine = false;
+    int t = xs / P.tw, r = xs - t * P.tw;
 #pragma unroll
-            for (int k = 0; k < 4; k++) { over += max(hv[k] - P.clip, 0); hv[k] = min(hv[k], P.clip); }
-            over += c_dpp0<0xB1>(over); over += c_dpp0<0x4E>(over); over += c_dpp0<0x124>(over); over += c_dpp0<0x128>(over);   // row totals
-            const int clipped = __builtin_amdgcn_readlane(over, 0) + __builtin_amdgcn_readlane(over, 16) +
-                                __builtin_amdgcn_readlane(over, 32) + __builtin_amdgcn_readlane(over, 48);
-            const int batch = clipped >> 8, residual = clipped & 255;
-            // serial loop `for (i = 0; i < 256 && residual > 0; i += step, residual--) hist[i]++` : bin gets +1 iff
-            // bin % step == 0 && bin / step < residual, step = max(256 / residual, 1)
-            int step = residual ? (int)(256.0f / (float)residual) : 1;          // exact: |256 - r n| >= 1
-            int q = (int)((float)(4 * lane) / (float)step), r = 4 * lane - q * step;    // exact for the same reason
+    for (int k = 0; k < 12; k++) {
+        const int x = xs + k, tc = min(t, P.tiles_x - 1);
+        const uint32_t wgt = (x >= x0 && x < P.w) ? ((x > dbl_lo && x <= P.w - 2) ? 2u : 1u) : 0u;
+        K.base[k] = (uint32_t)(tc >> 1) * (CH_CSTRIDE * 4u);
+        K.val[k] = wgt << (16 * (tc & 1));
+        K.mine = K.mine || wgt != 0;
+        if (++r == P.tw) { r = 0; t++; }
+    }
+}
+
+// The image rows ybeg + row0, + rowstep, .. of tile row ty into the (cleared) pair blocks.  The lane constants are formed here, once
+// per call and chunk (~150 instructions against the ~2000 of a row of tiles): kept across the LUT wavefront's table builds they
+// cost the kernel two spilled registers.
+// (img: buffer descriptor of the image -- the row is its scalar offset, the lane's column its 32-bit offset, as in the strips' loads)
+__device__ __forceinline__ void clahe_lut_row_hist(const ClaheParams &P, __amdgpu_buffer_rsrc_t img, uint32_t *pairs, int lane, int ty, int row0, int rowstep)
+{
+    const int ybeg = ty * P.th, yend = min(ybeg + P.th, P.h);       // (ybeg < h: the plan's vertical condition)
+    const int dbl_lo = 2 * P.h - 2 - (ybeg + P.th);                 // rows in (dbl_lo, h - 2] also stand for a padded row
+    const int nchunks = (((P.w + 3) >> 2) + CH_ROW_CHUNK_DW - 1) / CH_ROW_CHUNK_DW;
+    for (int c = 0; c < nchunks; c++) {
+        ClaheRowLane K;
+        clahe_row_lane(P, lane, c, K);
+        auto load = [&](int y) {                                       // rows beyond the tile row: its last row again, never added
+            return __builtin_amdgcn_raw_buffer_load_b96(img, (int)K.off, min(y, yend - 1) * P.stride, 0);
+        };
+        auto add = [&](const uint32_t (&a)[12]) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                hv[k] += batch + ((residual != 0 && r == 0 && q < residual) ? 1 : 0);
-                r++;
-                if (r == step) { r = 0; q++; }
+            for (int k = 0; k < 12; k++) atomicAdd((uint32_t *)((unsigned char *)pairs + a[k]), K.val[k]);
+        };
+        // one register set: a row's LDS addresses are formed, the row CH_ROW_AHEAD further down is requested into its registers,
+        // then its ds_adds are issued
+        c_u32x3 cur[CH_ROW_AHEAD];
+        int y = ybeg + row0;
+#pragma unroll
+        for (int u = 0; u < CH_ROW_AHEAD; u++) cur[u] = load(y + u * rowstep);
+#pragma nounroll
+        for (; y < yend; y += CH_ROW_AHEAD * rowstep) {
+#pragma unroll
+            for (int u = 0; u < CH_ROW_AHEAD; u++) {
+                const int yy = y + u * rowstep;
+                uint32_t a[12];
+#pragma unroll
+                for (int k = 0; k < 12; k++) a[k] = K.base[k] + 4u * ((cur[u][k >> 2] >> (8 * (k & 3))) & 0xFFu);
+                cur[u] = load(yy + CH_ROW_AHEAD * rowstep);
+                if (yy < yend && K.mine) {
+                    add(a);
+                    if (yy > dbl_lo && yy <= P.h - 2) add(a);
+                }
             }
         }
-        // inclusive scan over the 256 bins: in-lane prefix, DPP scan inside the 16-lane rows, row offsets by readlane
-        hv[1] += hv[0]; hv[2] += hv[1]; hv[3] += hv[2];
-        int v = hv[3];
-        v += c_dpp0<0x111>(v); v += c_dpp0<0x112>(v); v += c_dpp0<0x114>(v); v += c_dpp0<0x118>(v);      // row_shr:1,2,4,8 (zero fill)
-        const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31), r2 = __builtin_amdgcn_readlane(v, 47);
-        const int rowoff = sub == 0 ? 0 : (sub == 1 ? r0 : (sub == 2 ? r0 + r1 : r0 + r1 + r2));
-        const int base = v + rowoff - hv[3];
-        uint32_t packed = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            int r = __float2int_rn((float)(hv[k] + base) * P.lut_scale);   // saturate_cast<uchar>(float)
-            r = r < 0 ? 0 : (r > 255 ? 255 : r);
-            packed |= (uint32_t)r << (8 * k);
-        }
-        store_lut(t, packed);
+    }
+}
+
+// Clip / scan / LUT of the tiles tx0, tx0 + txstep, .. of a row of tiles from its pair blocks; store_lut(tx, packed) as in clahe_lut_tiles
+template <class StoreLut>
+__device__ __forceinline__ void clahe_lut_row_tails(const ClaheParams &P, const uint32_t *pairs, int lane, int tx0, int txstep, StoreLut store_lut)
+{
+#pragma nounroll
+    for (int tx = tx0; tx < P.tiles_x; tx += txstep) {
+        const c_u32x4 q = *(const c_u32x4 *)(pairs + (tx >> 1) * CH_CSTRIDE + 4 * lane) >> (uint32_t)(16 * (tx & 1));
+        int hv[4] = {(int)(q.x & 0xFFFFu), (int)(q.y & 0xFFFFu), (int)(q.z & 0xFFFFu), (int)(q.w & 0xFFFFu)};
+        store_lut(tx, clahe_lut_tail(P, lane, hv));
     }
 }
 
@@ -451,7 +554,8 @@ enum { CS_MID = 0, CS_EDGE = 1, CS_ANY = 2 };      // what a strip holds of the 
 template <int E> using cs_tag = std::integral_constant<int, E>;
 // UNAL: w % 4 != 0 or an odd level-1 width (the generic right edge); false keeps the w % 4 == 0 instance free of its per-lane
 // selectors (they cost three spilled registers at this kernel's 80-VGPR budget)
-// FUSED (round 4): the work-group has one more wavefront, which computes the tile LUTs (clahe_lut_tiles: histogram, clip, scan) of the
+// FUSED (round 4): the work-group has one more wavefront, which computes the tile LUTs (histogram, clip, scan; clahe_lut_row_hist +
+// clahe_lut_row_tails where clahe_plan.hpp allows the row form -- EuRoC --, clahe_lut_tiles otherwise) of the
 // NEXT row of tiles while the strips walk the current row of cells -- the LDS-atomic-bound half of CLAHE runs beside the store- and
 // latency-bound half on the same CU, the LUTs never leave LDS (a ring of two rows of tiles), the source rows are fetched from HBM once
 // (the strips find them in L2 half a tile later), and k_clahe_lut's launch is gone.  The first row of tiles is shared by all wavefronts
@@ -467,7 +571,7 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
     // everything else is wave-private
     const int b = blockIdx.x, s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, ndw = (P.w + 3) >> 2, wr = UNAL ? (P.w & 3) : 0;
-    // FUSED: this wavefront's histogram -- one copy for the strips (they histogram the first row of tiles only), CH_NCOPY for the LUT wavefronts
+    // FUSED, tile form: this wavefront's histogram -- one copy for the strips (they histogram the first row of tiles only), CH_NCOPY for the LUT wavefronts
     uint32_t *hist_w = (uint32_t *)(ring + (size_t)2 * P.tiles_x * 256) + (s < P.nstrips ? s * CH_WAVE_DW : P.nstrips * CH_WAVE_DW + (s - P.nstrips) * CH_MULTI_DW);
     const int hist_copies = s < P.nstrips ? 1 : CH_NCOPY;
     auto lut_row = [&](int ty, int tx0, int txstep) {                   // FUSED: LUTs of the tiles tx0, tx0 + txstep, .. of tile row ty
@@ -499,7 +603,37 @@ __global__ __launch_bounds__(64 * (CS_MAX_STRIPS + 2), 6) void k_clahe_apply_pyr
         }
         __syncthreads();
     };
-    if (FUSED) {
+    if (FUSED && P.row_hist) {
+        // row form: the pair blocks of ONE row of tiles, shared by the work-group for the first row of tiles (image row r to
+        // wavefront r mod n, tile t's clip / scan / LUT to wavefront t mod n), then the LUT wavefront's own
+        uint32_t *pairs = (uint32_t *)(ring + (size_t)2 * P.tiles_x * 256);
+        const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void *)(src + (long long)b * P.src_item_stride), 0, 0x7fffffff, 0x00020000);
+        const int npair_q = ov2_clahe_pair_blocks(P.tiles_x) * (CH_CSTRIDE / 4), nw = P.nstrips + P.nlut;
+        auto tails = [&](int ty, int tx0, int txstep) {
+            uint8_t *slot = ring + (size_t)(ty & 1) * P.tiles_x * 256 + 4 * lane;
+            clahe_lut_row_tails(P, pairs, lane, tx0, txstep, [&](int tx, uint32_t packed) { *(uint32_t *)(slot + (size_t)tx * 256) = packed; });
+        };
+        for (int q = threadIdx.x; q < npair_q; q += blockDim.x) ((c_u32x4 *)pairs)[q] = (c_u32x4)(0u);
+        __syncthreads();
+        clahe_lut_row_hist(P, img, pairs, lane, 0, s, nw);
+        __syncthreads();
+        tails(0, s, nw);
+        if (s >= P.nstrips) {                                           // the LUT wavefront, as in the tile form below
+            const int n_cell_rows = cell_row(P.h - 1) + 1;
+            __builtin_amdgcn_s_setprio(CS_LUT_PRIO);
+            for (int c = 0; c < n_cell_rows; c++) {
+                build(c);                                               // (the strips have read the pair blocks of row 0 before its barriers)
+                if (c + 1 < P.tiles_y) {
+                    for (int q = lane; q < npair_q; q += 64) ((c_u32x4 *)pairs)[q] = (c_u32x4)(0u);
+                    clahe_wave_sync();
+                    clahe_lut_row_hist(P, img, pairs, lane, c + 1, 0, 1);
+                    clahe_wave_sync();                                  // the atomics have landed
+                    tails(c + 1, 0, 1);
+                }
+            }
+            return;
+        }
+    } else if (FUSED) {
         lut_row(0, s, P.nstrips + P.nlut);                              // the first row of tiles: all wavefronts
         if (s >= P.nstrips) {                                           // the LUT wavefront: one row of tiles ahead of the strips
             const int n_cell_rows = cell_row(P.h - 1) + 1;              // (the strips stage every row of cells once, in order)
@@ -760,11 +894,9 @@ int ov2_launch_clahe(ov2_ctx *ctx, const uint8_t *src_d, int w, int h, int strid
     OV2_HIP_CHECK(attr_err);
     ClaheParams P;
     P.border = border;
-    P.nstrips = 0; P.nlut = 0; P.l1_delta = 0; P.l1_pitch = P.l1_w = P.l1_h = 0;
-    int ew = w, eh = h;
-    if (!(w % tiles_x == 0 && h % tiles_y == 0)) { ew = w + (tiles_x - w % tiles_x); eh = h + (tiles_y - h % tiles_y); }
+    P.nstrips = 0; P.nlut = 0; P.row_hist = 0; P.l1_delta = 0; P.l1_pitch = P.l1_w = P.l1_h = 0;
     P.w = w; P.h = h; P.stride = stride; P.tiles_x = tiles_x; P.tiles_y = tiles_y;
-    P.tw = ew / tiles_x; P.th = eh / tiles_y;
+    ov2_clahe_tile_size(w, h, tiles_x, tiles_y, &P.tw, &P.th);
     const int total = P.tw * P.th;
     P.lut_scale = (float)(256 - 1) / (float)total;
     P.clip = 0;
@@ -808,7 +940,10 @@ int ov2_launch_clahe(ov2_ctx *ctx, const uint8_t *src_d, int w, int h, int strid
             const bool fused = (ctx->clahe_strips == 2 || (ctx->clahe_strips < 0 && tiles_x <= 16 * nlut)) && (unal || src_al);
             if (fused) {
                 P.nlut = nlut;
-                const size_t lds = (size_t)(tiles_x + 1) * 1024 + (size_t)2 * tiles_x * 256 + ((size_t)nstrips * CH_WAVE_DW + (size_t)P.nlut * CH_MULTI_DW) * 4;
+                // the histograms of the LUT computation: whole rows into 16-bit pair blocks where the plan allows, else per tile
+                const bool row_form = ov2_clahe_row_form(w, h, tiles_x, tiles_y, src_al, nstrips, nlut);
+                P.row_hist = row_form ? 1 : 0;
+                const size_t lds = (size_t)ov2_clahe_lds_fused(row_form, tiles_x, nstrips, nlut);
                 hipLaunchKernelGGL((unal ? k_clahe_apply_pyr<true, true> : k_clahe_apply_pyr<false, true>), dim3(batch), dim3(64 * (nstrips + P.nlut)), lds, ctx->stream, P, src_d, lut_d, dst_d);
             } else {
                 launch_lut();

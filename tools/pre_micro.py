@@ -16,7 +16,7 @@ S = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 strips = int(sys.argv[3]) if len(sys.argv) > 3 else -1
 if len(sys.argv) > 4 and sys.argv[4] == "kitti": bench.W, bench.H = 1241, 376        # configs[2]
-views, _, _ = bench.make_inputs(S, 1234)
+views = bench.make_inputs(1, 1234)[0][0]                                  # the first view set: (NF + 1, H, W)
 dev = torch.device("cuda", 0)
 stream = torch.cuda.current_stream()
 ctx = ov2slam_amd.Context(0, stream=stream.cuda_stream)
