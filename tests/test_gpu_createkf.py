@@ -293,10 +293,10 @@ def test_rejected_calls_leave_the_tracker_usable(gpu_ctx):
     for b in range(BATCH):
         t.setPose(b, _truth(b)[0])
     refused(t, L.OV2_EINVAL, "n_active", n_active=0)
-    na, cp, ci, keep = t._ckf_args(4, x["px"], x["lmid"], x["is3d"], x["n"], x["make_kf"], x["nlmid"], x["nkfid"], x["time"], p,
+    c = t._marshal_create_keyframe(4, x["px"], x["lmid"], x["is3d"], x["n"], x["make_kf"], x["nlmid"], x["nkfid"], x["time"], p,
                                    _state0("singlescale"), x["Twc"])
-    assert t.lib.ov2_btracker_create_keyframe_begin(t.h_trk, BATCH + 1, C.byref(cp), C.byref(ci)) == L.OV2_EINVAL
-    assert b"n_active" in t.lib.ov2_last_error() and keep[-1].tobytes() == _state0("singlescale").tobytes()
+    assert t.lib.ov2_btracker_create_keyframe_begin(t.h_trk, BATCH + 1, *c.args[1:]) == L.OV2_EINVAL
+    assert b"n_active" in t.lib.ov2_last_error() and c.keep["state"].tobytes() == _state0("singlescale").tobytes()
     for bad in (-1, N_MAX + 1):
         n = x["n"].copy(); n[1] = bad
         refused(t, L.OV2_EINVAL, "cfg.n_max slots", n=n)

@@ -17,7 +17,7 @@ import pytest
 
 import ov2slam_amd
 from ov2slam_amd import _lib as L
-from ov2slam_amd import keyframe, pose
+from ov2slam_amd import keyframe, lockstep, pose
 from tests import camera_cases as CC
 from tests import fivept_ref as E5
 from tests import frameepi_ref as R
@@ -451,18 +451,16 @@ def test_rejected_calls_leave_outputs_and_tracker_untouched(gpu_ctx):
             t.trackFrameEpiPose(*a, e[0], ep, *e[2:], **dict(kw, **k))
         assert err.value.code == L.OV2_EINVAL, ep
     # NULL lmid_h / nbkfs_h / epi_seed_h through the C ABI, with poisoned outputs: nothing is written
-    na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = t._map_args(*a)
     for field in ("lmid_h", "nbkfs_h", "epi_seed_h"):
-        ep, ei, keep = t._epi_args(na, nn, *e, None, False, 0)
-        setattr(ei, field, None)
+        c = t._marshal_track_frame_epi_pose(*a, *e)
+        setattr(c.inputs, field, None)
+        na = c.na
         out = np.full((BATCH, N_MAX, 2), 7.5, np.float32); st = np.full((BATCH, N_MAX), 0x6E, np.uint8); p3p = np.full(na, 0x6E6E, np.int32)
-        Rp, removed = t._pose_results(na, nn)
-        Re, bufs = t._epi_results(na)
+        res = lockstep._Results(t, "track_frame_epi_pose", c)
+        Rp, removed, Re, bufs = res.R, res.removed, res.E, res.bufs
         removed[...] = 0x6E; bufs["removed"][...] = 0x6E
         before = bytes(C.string_at(C.byref(Rp), C.sizeof(Rp))) + bytes(C.string_at(C.byref(Re), C.sizeof(Re)))
-        rc = t.lib.ov2_btracker_track_frame_epi_pose(t.h_trk, na, ptrs, stride, kps.ctypes.data, wpt.ctypes.data, is3d.ctypes.data,
-                                                     Tcw.ctypes.data, nn.ctypes.data, 1, C.byref(ep), C.byref(ei), out.ctypes.data,
-                                                     st.ctypes.data, p3p.ctypes.data, Re, Rp)
+        rc = t.lib.ov2_btracker_track_frame_epi_pose(t.h_trk, *c.args, out.ctypes.data, st.ctypes.data, p3p.ctypes.data, Re, Rp)
         assert rc == L.OV2_EINVAL and b"NULL" in t.lib.ov2_last_error(), field
         assert (out == 7.5).all() and (st == 0x6E).all() and (p3p == 0x6E6E).all() and (removed == 0x6E).all() and (bufs["removed"] == 0x6E).all()
         assert bytes(C.string_at(C.byref(Rp), C.sizeof(Rp))) + bytes(C.string_at(C.byref(Re), C.sizeof(Re))) == before
@@ -473,8 +471,8 @@ def test_rejected_calls_leave_outputs_and_tracker_untouched(gpu_ctx):
         t.setKeyframe(0, kf["lmid"], kf["unpx"], kf["bv"], kf["Twc"])
     assert err.value.code == L.OV2_EINVAL and "open" in str(err.value)
     # ... and a trace_samples pointer is refused by the end half, which leaves the step open
-    Rp, removed = t._pose_results(na, nn)
-    Re, bufs = t._epi_results(na)
+    res = lockstep._Results(t, "track_frame_epi_pose", c)
+    Rp, Re = res.R, res.E
     tab = np.zeros((EPI_ROWS, 8), np.int32)
     Re[0].trace_samples = tab.ctypes.data_as(C.POINTER(C.c_int))
     out = np.zeros((BATCH, N_MAX, 2), np.float32); st = np.zeros((BATCH, N_MAX), np.uint8); p3p = np.zeros(na, np.int32)

@@ -10,7 +10,7 @@ import pytest
 
 import ov2slam_amd
 from ov2slam_amd import _lib as L
-from ov2slam_amd import pose
+from ov2slam_amd import lockstep, pose
 from tests import camera_cases as CC
 from tests import framepose_ref as F
 from tests.match_ref import _inv_act, _rand_pose
@@ -324,15 +324,15 @@ def test_rejected_calls_leave_outputs_and_tracker_untouched(gpu_ctx):
                              s["p3p_req"], s["seed"], scale=kw.get("scale"), n_rows=kw.get("n_rows", 0))
         assert e.value.code == L.OV2_EINVAL, kw.keys()
     # NULL Twc_h through the C ABI, with poisoned outputs: nothing is written
-    na, imgs, stride, ptrs, kps, wpt, is3d, Tcw, nn = t._map_args(*a)
-    fp, fi, keep = t._pose_args(na, nn, s["params"], s["Twc"], s["p3p_req"], s["seed"], None, False, 0)
-    fi.Twc_h = None
+    c = t._marshal_track_frame_pose(*a, s["params"], s["Twc"], s["p3p_req"], s["seed"])
+    c.inputs.Twc_h = None
+    na = c.na
     out = np.full((BATCH, N_MAX, 2), 7.5, np.float32); st = np.full((BATCH, N_MAX), 0x6E, np.uint8); p3p = np.full(na, 0x6E6E, np.int32)
-    R, removed = t._pose_results(na, nn)
+    res = lockstep._Results(t, "track_frame_pose", c)
+    R, removed = res.R, res.removed
     removed[...] = 0x6E
     before = bytes(C.string_at(C.byref(R), C.sizeof(R)))
-    rc = t.lib.ov2_btracker_track_frame_pose(t.h_trk, na, ptrs, stride, kps.ctypes.data, wpt.ctypes.data, is3d.ctypes.data, Tcw.ctypes.data,
-                                             nn.ctypes.data, 1, C.byref(fp), C.byref(fi), out.ctypes.data, st.ctypes.data, p3p.ctypes.data, R)
+    rc = t.lib.ov2_btracker_track_frame_pose(t.h_trk, *c.args, out.ctypes.data, st.ctypes.data, p3p.ctypes.data, R)
     assert rc == L.OV2_EINVAL and b"NULL" in t.lib.ov2_last_error()
     assert (out == 7.5).all() and (st == 0x6E).all() and (p3p == 0x6E6E).all() and (removed == 0x6E).all()
     assert bytes(C.string_at(C.byref(R), C.sizeof(R))) == before

@@ -537,11 +537,10 @@ def test_refusals_the_dropped_step_and_the_host_forms(gpu_ctx):
     assert [t.getFrame(b, True)["n"] for b in range(BATCH)] == [60] * 4      # the first frame leaves the frames alone
     t.updateFrame(BATCH, _set_ops(side, 1, BATCH))
     a1, _ = args(1)
-    mp, mi, keep = t._mono_args(BATCH, None, a1[0], a1[1], a1[2], a1[3], None, a1[4], a1[5], a1[6], a1[7], None, True, None, False, 0)
+    c = t._marshal_track_mono_resident(_imgs(1), *a1)
     lm = np.zeros((BATCH, N_MAX), np.int32)
-    mi.step.lmid_h = lm.ctypes.data_as(type(mi.step.lmid_h))
-    imgs, stride, ptrs = t._frames(_imgs(1))
-    assert t.lib.ov2_btracker_track_mono_resident_begin(t.h_trk, BATCH, ptrs, stride, 1, mp, mi) == L.OV2_EINVAL
+    c.inputs.step.lmid_h = lm.ctypes.data_as(type(c.inputs.step.lmid_h))
+    assert t.lib.ov2_btracker_track_mono_resident_begin(t.h_trk, *c.args) == L.OV2_EINVAL
     assert b"lmid_h and scale_h must be NULL" in t.lib.ov2_last_error()
     views = side.views()
     pose0, state0 = side.poses().tobytes(), [R.state_bytes(s) for s in side.states()]

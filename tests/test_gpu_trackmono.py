@@ -18,7 +18,7 @@ import pytest
 
 import ov2slam_amd
 from ov2slam_amd import _lib as L
-from ov2slam_amd import keyframe, motion, pose
+from ov2slam_amd import keyframe, lockstep, motion, pose
 from tests import camera_cases as CC
 from tests import motion_ref as M
 from tests import trackmono_ref as R
@@ -349,19 +349,17 @@ def test_rejected_calls_leave_everything_untouched(gpu_ctx):
     _prepare(t, None, steps[1], True)
     before = (np.array([t.getPose(b) for b in range(BATCH)]).tobytes(), [R.state_bytes(t.getMotion(b)) for b in range(BATCH)])
     # through the C ABI with poisoned outputs: a non-NULL Twc_h, NULL time_h / frame_id_h / lmid_h, a bad grid, a non-finite time
-    na, imgs, stride, ptrs, kps, wpt, is3d, _, nn = t._map_args_mono(*a1[:5])
-
     def refused(change, words):
-        mp, mi, keep = t._mono_args(na, nn, *a1[5:], steps[1]["ba"], True, None, False, 0)
-        change(mp, mi)
+        c = t._marshal_track_mono(*a1, localba_is_on=steps[1]["ba"])
+        change(c.params, c.inputs)
+        na = c.na
         out = np.full((BATCH, N_MAX, 2), 7.5, np.float32); st = np.full((BATCH, N_MAX), 0x6E, np.uint8); p3p = np.full(na, 0x6E6E, np.int32)
-        Rp, removed = t._pose_results(na, nn)
-        Re, bufs = t._epi_results(na)
+        res = lockstep._Results(t, "track_mono", c)
+        Rp, Re = res.R, res.E
         Mr = (L.TrackMonoResult * na)()
         C.memset(Mr, 0x6E, C.sizeof(Mr))
         keepb = bytes(C.string_at(C.byref(Rp), C.sizeof(Rp))) + bytes(C.string_at(C.byref(Re), C.sizeof(Re))) + bytes(Mr)
-        rc = t.lib.ov2_btracker_track_mono(t.h_trk, na, ptrs, stride, kps.ctypes.data, wpt.ctypes.data, is3d.ctypes.data, nn.ctypes.data, 1,
-                                           C.byref(mp), C.byref(mi), out.ctypes.data, st.ctypes.data, p3p.ctypes.data, Re, Rp, Mr)
+        rc = t.lib.ov2_btracker_track_mono(t.h_trk, *c.args, out.ctypes.data, st.ctypes.data, p3p.ctypes.data, Re, Rp, Mr)
         assert rc == L.OV2_EINVAL and words in t.lib.ov2_last_error(), (words, t.lib.ov2_last_error())
         assert (out == 7.5).all() and (st == 0x6E).all() and (p3p == 0x6E6E).all()
         assert bytes(C.string_at(C.byref(Rp), C.sizeof(Rp))) + bytes(C.string_at(C.byref(Re), C.sizeof(Re))) + bytes(Mr) == keepb
@@ -382,7 +380,6 @@ def test_rejected_calls_leave_everything_untouched(gpu_ctx):
     before = (np.array([t.getPose(b) for b in range(BATCH)]).tobytes(), [R.state_bytes(t.getMotion(b)) for b in range(BATCH)])
     a2, kw2 = _args(steps[2])
     _prepare(t, None, steps[2], True)
-    na, imgs, stride, ptrs, kps, wpt, is3d, _, nn = t._map_args_mono(*a2[:5])
     a1 = a2
     old_t = np.full(BATCH, 10.0 + DT)
     refused(lambda mp, mi: setattr(mi, "time_h", old_t.ctypes.data_as(C.POINTER(C.c_double))), b"not after")
