@@ -1832,6 +1832,102 @@ int ov2_epipolar_filter(ov2_ctx *ctx, const ov2_epifilter_params *params, const 
 int ov2_epipolar_filter_batch(ov2_ctx *ctx, const ov2_epifilter_params *params, int n_items, const ov2_epifilter_item *items,
                               ov2_epifilter_result *results);
 
+/* ---- mono initialisation (monoinit.hip): trackMono's un-initialised branch, src/visual_front_end.cpp:98-113, with
+ * VisualFrontEnd::checkReadyForInit, :855-984 -------------------------------------------------------------------------------------
+ * The whole decision "can this mono system initialise from the previous keyframe and this frame" as ONE device chain: the count of
+ * 2-D keypoints, the plain median parallax, the join against the keyframe, the rotation-compensated average parallax in the
+ * arithmetic of :908-913, the 5-point search over a sample table drawn on the device, the removals and the initial pose.  One upload,
+ * six launches (k_fkf_parallax, k_minit_gather, k_e5_solve, k_e5_score, k_e5_pick, k_minit_decide), one download, ONE synchronisation
+ * per call.  The frame's keypoints are taken in array order (the iteration order of pcurframe_->mapkps_, as ov2_epipolar_filter).
+ *
+ *   :100   nb2dkps = #(cur_is3d == 0); nb2dkps < min_2d_kps: OV2_MINIT_RESET (breset_req_).  Nothing else runs: every other field
+ *          of the record is 0 (best_row -1), nothing is removed.  min_2d_kps is the reference's literal 50; 0 disables the test.
+ *   :857   p0 IS ov2_parallax(unrot = 0, OV2_FKF_ALL, OV2_FKF_MEDIAN) bit for bit -- the median of the DISTINCT float parallaxes,
+ *          0 when nothing joins, NaN when one of them is not finite -- reported with its n / n_distinct / n_nonfinite.
+ *   :861   the gate is (double)p0 > (double)finit_parallax (strict: equality does not pass, nor does NaN); failing it:
+ *          OV2_MINIT_LOW_PARALLAX.
+ *   :873   n_cur < 8: OV2_MINIT_TOO_FEW_KPS.
+ *   :887   Rkfcur = toRotationMatrix(kf_Tcw.q) * toRotationMatrix(cur_Twc.q), as ov2_parallax(unrot = 1).
+ *   :893   the join of ov2_epipolar_filter without its 3-D restriction: EVERY current keypoint in array order, its counterpart by
+ *          binary search in the strictly ascending kf_lmid, a keypoint without one is skipped.  Match k (k < m) is current keypoint
+ *          pair_cur[k] and keyframe slot j: bv1[k] = kf_bv[j], bv2[k] = cur_bv[pair_cur[k]].
+ *   :908   the parallax of a match is NOT the distance of ov2_parallax(unrot = 1) (projectCamToImage multiplies by 1 / z and adds
+ *          the principal point; this line multiplies by the matrix K and divides):
+ *            rotbv = Rkfcur bv, each coefficient the serial sum (r0 x + r1 y) + r2 z;
+ *            u = K rotbv with K = [fx 0 cx; 0 fy cy; 0 0 1] as a full 3 x 3 by 3 coefficient product, zero entries included:
+ *                u.x = (fx x + 0 y) + cx z,  u.y = (0 x + fy y) + cy z,  u.z = (0 x + 0 y) + 1 z;
+ *            rotpx = ((float)(u.x / u.z), (float)(u.y / u.z));
+ *            d = cv::norm(rotpx - kf_unpx): the difference in float, then sqrt((double)dx dx + (double)dy dy).
+ *          The sum is OV2_FKF_AVG_WIDE's: sum = (float)((double)sum + d), serial in array order.  This form is restated from the
+ *          reference's source, not pinned against an Eigen build.
+ *   :917   m < 8: OV2_MINIT_TOO_FEW_MATCHES (p1 is reported as 0: the reference returns before it divides).
+ *   :923   p1 = sum / (float)m;  p1 < finit_parallax (float against float, strict: equality passes, and so does NaN):
+ *          OV2_MINIT_LOW_ROT_PARALLAX.
+ *   :945   the search IS ov2_epipolar_ransac on the packed bearings with the table of ov2_epipolar_draw_samples(seed, m, n_rows),
+ *          drawn on the device as in ov2_epipolar_filter.  Any OV2_EPI_* bit in its status (fewer than 10 inliers included):
+ *          OV2_MINIT_NO_MODEL, nothing is removed.
+ *   :962   removed[pair_cur[outliers[k]]] = 1 for every outlier.  There is no 50 % rule here.
+ *   :968   t = tkfc / |tkfc| (the norm as sqrt((x x + y y) + z z), a division per component, as Twc_model of ov2_epipolar_filter),
+ *          then t * 0.25 per component.  Twc_init = [t, q], q the quaternion of ov2_pose_from_model(model) (Frame::setTwc(R, t):
+ *          setRotationMatrix, then the translation).  OV2_MINIT_READY.
+ *
+ * The one deviation.  The reference calls the search with do_optimize = true.  That changes only Rwc / twc, never the outlier list
+ * (src/multi_view_geometry.cpp:669-693), so every action and every removal above is the reference's.  The REFINED model is not
+ * available (OpenGV's non-linear refinement has no device form; epi.boptimize must be 0): Twc_init comes from the UNREFINED model and
+ * the record says so with pose_refined = 0.  This is NOT the reference's pose until a refinement exists.
+ *
+ * A field that a return above comes before is 0 (best_row -1): p0 and its counts are set unless the action is OV2_MINIT_RESET; m
+ * from :917 on; p1 from :923 on; the search's fields where it ran; model / Twc_init / n_removed with OV2_MINIT_READY (model also
+ * with OV2_MINIT_NO_MODEL, as the search left it).  `removed` is always written (n_cur bytes).
+ *
+ * Capacity: OV2_FKF_MAX_POINTS keypoints on either side, OV2_EPI_MAX_ROWS rows, 65535 items.  OV2_EINVAL, all of it checked on the
+ * host before the context is touched (a rejected call writes nothing): everything ov2_epipolar_filter_batch refuses for the same
+ * fields (NULL arguments or arrays with a non-zero count -- cur_px included, the item is ov2_parallax's --, negative counts, kf_lmid
+ * not strictly ascending, threshold, probability, max_iterations, boptimize != 0, a NULL kf_bv with n_kf > 0, a NULL `removed` with
+ * n_cur > 0, bearings, poses or K that are not finite, n_rows outside [0, OV2_EPI_MAX_ROWS], n_cur / n_kf beyond OV2_FKF_MAX_POINTS,
+ * more than 65535 items), min_2d_kps < 0, a finit_parallax that is not finite. */
+enum {
+    OV2_MINIT_RESET = 0, OV2_MINIT_LOW_PARALLAX = 1, OV2_MINIT_TOO_FEW_KPS = 2, OV2_MINIT_TOO_FEW_MATCHES = 3,
+    OV2_MINIT_LOW_ROT_PARALLAX = 4, OV2_MINIT_NO_MODEL = 5, OV2_MINIT_READY = 6,
+    OV2_MINIT_NOT_REQUESTED = 7, OV2_MINIT_NO_KEYFRAME = 8       /* ov2_btracker_mono_init only */
+};
+typedef struct {
+    ov2_fkf_params fkf;          /* K and finit_parallax are read                                                            */
+    ov2_epipolar_params epi;     /* nransac_iter_, the bearing threshold of fransac_err_, 0.99; boptimize must be 0          */
+    int n_rows;                  /* rows of the sample table drawn per item that searches                                    */
+    int min_2d_kps;              /* :100, the reference's literal 50; 0: no such test                                        */
+} ov2_mono_init_params;
+typedef struct {
+    ov2_fkf_item fkf;            /* the item of ov2_parallax                                                                 */
+    const double *kf_bv;         /* 3 n_kf: the keyframe's Keypoint::bv_, in the order of kf_lmid                            */
+    unsigned long long seed;     /* of the sample table                                                                      */
+} ov2_mono_init_item;
+typedef struct {
+    int action;                  /* OV2_MINIT_*                                                                              */
+    int nb2dkps;                 /* :100                                                                                     */
+    float p0;                    /* :857                                                                                     */
+    int p0_n, p0_n_distinct, p0_n_nonfinite;   /* as ov2_parallax_result                                                     */
+    int m;                       /* matches that entered the search                                                          */
+    float p1;                    /* :923                                                                                     */
+    int status, best_row, iterations, rows_consumed;   /* the search's, as ov2_epipolar_result; 0 / -1 / 0 / 0 when it did not run */
+    double score;
+    int n_inliers, n_outliers;
+    double model[12];            /* Rkfc row-major, tkfc; zeros without a model                                              */
+    int n_removed;
+    int pose_refined;            /* always 0: Twc_init is the pose of the UNREFINED model (see above)                        */
+    double Twc_init[7];          /* OV2_MINIT_READY: [0.25 tkfc / |tkfc|, q(Rkfc)]; zeros otherwise                          */
+    uint8_t *removed;            /* n_cur bytes: 0 kept, 1 removed as a RANSAC outlier                                       */
+    int *pair_cur;               /* optional (NULL or n_cur ints of room): the current index of packed match k, k < m        */
+    int *trace_samples;          /* optional diagnostic (NULL or 8 n_rows): the table the device drew; untouched without a search */
+} ov2_mono_init_result;
+/* The three pointers of the result are INPUTS of the call, read on entry, as those of ov2_epifilter_result. */
+/* one frame: the batch form with one item, through the same code path */
+int ov2_mono_init(ov2_ctx *ctx, const ov2_mono_init_params *params, const ov2_mono_init_item *item, ov2_mono_init_result *result);
+/* the frames of a lock-step batch with shared params (the item is a grid axis: each kernel is launched once).  Per item the result
+ * equals ov2_mono_init on that item bit for bit; sizes may differ, empty frames and empty keyframes are allowed. */
+int ov2_mono_init_batch(ov2_ctx *ctx, const ov2_mono_init_params *params, int n_items, const ov2_mono_init_item *items,
+                        ov2_mono_init_result *results);
+
 /* ---- tracking priors (priors.hip): where the reference derives the priors that its KLT calls start from ----------------------
  *   ov2_klt_priors      VisualFrontEnd::kltTracking (src/visual_front_end.cpp:156-184): the map point of every 3-D keypoint
  *                       projected with the predicted pose (Frame::projWorldToImageDist, Frame::isInImage)
@@ -2616,6 +2712,40 @@ int  ov2_btracker_adopt_keyframe_pyramid(ov2_btracker *t, int n_active, const ui
 int  ov2_btracker_set_keyframe_px(ov2_btracker *t, int item, int n, const int *lmid, const float *px);
 int  ov2_btracker_get_keyframe_px(ov2_btracker *t, int item, int from_device, int *n, int *lmid, float *px);
 const ov2_pyr *ov2_btracker_kf_item(const ov2_btracker *t, int item);
+
+/* ---- mono initialisation on the resident frame and keyframe (f25): trackMono's un-initialised branch, :98-113 ----------------------
+ * ov2_mono_init (above) on the state an ov2_btracker keeps on the device, for the items b < n_active with do_h[b] != 0, in ONE enqueue
+ * and ONE synchronisation, without a per-slot byte going up (ov2_btracker_last_slot_bytes gives 0).  It runs right after the
+ * ov2_btracker_track_mono_resident step of an item that has not been initialised yet: such an item passes through that step
+ * harmlessly (no 3-D keypoints: computePose gives OV2_POSE_TOO_FEW, the filter does not refine, the 33 % rule counts nothing) and its
+ * caller ignores the step's keyframe decision.
+ *   input    by kernels: lmid / is3d / px of the resident frame's slots in slot order, unpx / bv from px with the tracker's calibration
+ *            (k_compute_keypoints: Frame::computeKeypoint), cur_Twc the resident pose, kf_lmid / kf_unpx / kf_bv / kf_Tcw the resident
+ *            keyframe (ov2_btracker_set_keyframe, ov2_btracker_create_keyframe); seed_h[b] is the item's seed.
+ *   chain    that of ov2_mono_init_batch on a block of the tracker's at capacity; the record of a requested item equals, bit for bit,
+ *            what ov2_mono_init returns for those inputs.  removed_h holds cfg.n_max bytes per item, item b's at b * cfg.n_max (the
+ *            record's `removed` points there; pair_cur and trace_samples are NULL).
+ *   apply    OV2_MINIT_READY: the removed slots leave the resident frame by the rule of OV2_RES_REMOVE (the rest close up in slot
+ *            order; the frame is then no longer its keyframe's), and the resident pose becomes Twc_init -- the pose of the UNREFINED
+ *            model, see ov2_mono_init.  Any other action leaves frame and pose alone.  EVERY requested item that ran, whatever its
+ *            action: the resident motion state becomes MotionModel::reset()'s (prev_time = -1, log_relT = 0, prevTwc stays).  The
+ *            reference never reaches updateMotionModel before initialisation (:107 and :111 return first), while the step that ran
+ *            for this item did update the state; without the reset the next step would resync and then store a velocity where the
+ *            reference stores none.  _end brings the host mirrors (frame, pose, motion) to the same state.
+ *   OV2_MINIT_NOT_REQUESTED   do_h[b] == 0: nothing of the item is read or written.
+ *   OV2_MINIT_NO_KEYFRAME     the item has no resident keyframe (or an empty one) or no keyframe info (ov2_btracker_set_keyframe_info,
+ *                             ov2_btracker_create_keyframe): the reference's pkf == nullptr return (:866); nothing changes.
+ * OV2_EINVAL before anything is enqueued, the tracker staying where it was: NULL arguments, n_active outside [1, batch], any open
+ * call, no resident frame (ov2_btracker_set_frame), no calibration, cfg.n_max outside [1, OV2_FKF_MAX_POINTS], more than 65535 items,
+ * and what ov2_mono_init refuses in its params.  Between _begin and _end the calls that change resident state or start a step return
+ * OV2_EINVAL.  The kernels are launched over the items up to the last one that runs.  A HIP error while enqueueing (OV2_EHIP) closes
+ * the call; the host mirrors have not moved then, but if the failure came behind the apply kernel the device already holds the new
+ * pose and motion state of the requested items: re-install them (ov2_btracker_set_pose, ov2_btracker_reset_motion) or drop the tracker. */
+int  ov2_btracker_mono_init_begin(ov2_btracker *t, int n_active, const ov2_mono_init_params *params, const uint8_t *do_h,
+                                  const unsigned long long *seed_h);
+int  ov2_btracker_mono_init_end(ov2_btracker *t, ov2_mono_init_result *results, uint8_t *removed_h);
+int  ov2_btracker_mono_init(ov2_btracker *t, int n_active, const ov2_mono_init_params *params, const uint8_t *do_h,
+                            const unsigned long long *seed_h, ov2_mono_init_result *results, uint8_t *removed_h);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,8 @@ OV2_POSE_TOO_FEW, OV2_POSE_OK, OV2_POSE_PNP_REQ_P3P, OV2_POSE_P3P_RESET, OV2_POS
 OV2_EPI_TOO_FEW_POINTS, OV2_EPI_NO_MODEL, OV2_EPI_FEW_INLIERS = 1, 2, 4
 OV2_EPI_MAX_POINTS, OV2_EPI_MAX_ROWS = 2048, 4096
 OV2_EPIF_TOO_FEW_KPS, OV2_EPIF_LOW_PARALLAX, OV2_EPIF_NO_MODEL, OV2_EPIF_DEGENERATE, OV2_EPIF_FILTERED = 0, 1, 2, 3, 4
+(OV2_MINIT_RESET, OV2_MINIT_LOW_PARALLAX, OV2_MINIT_TOO_FEW_KPS, OV2_MINIT_TOO_FEW_MATCHES, OV2_MINIT_LOW_ROT_PARALLAX,
+ OV2_MINIT_NO_MODEL, OV2_MINIT_READY, OV2_MINIT_NOT_REQUESTED, OV2_MINIT_NO_KEYFRAME) = range(9)
 OV2_PG_MAX_POSES, OV2_PG_MAX_EDGES = 16384, 32768
 OV2_TERM_NO_CONVERGENCE, OV2_TERM_FUNCTION_TOL, OV2_TERM_PARAMETER_TOL, OV2_TERM_GRADIENT_TOL = 0, 1, 2, 3
 OV2_TERM_MIN_RADIUS, OV2_TERM_INVALID_STEPS, OV2_TERM_FAILURE = 4, 5, 6
@@ -431,6 +433,26 @@ class EpifilterResult(C.Structure):
                 ("pose_from_model", C.c_int), ("Twc_model", C.c_double * 7), ("trace_samples", C.POINTER(C.c_int))]
 
 
+class MonoInitParams(C.Structure):
+    """ov2_mono_init_params"""
+    _fields_ = [("fkf", FkfParams), ("epi", EpipolarParams), ("n_rows", C.c_int), ("min_2d_kps", C.c_int)]
+
+
+class MonoInitItem(C.Structure):
+    """ov2_mono_init_item"""
+    _fields_ = [("fkf", FkfItem), ("kf_bv", C.POINTER(C.c_double)), ("seed", C.c_ulonglong)]
+
+
+class MonoInitResult(C.Structure):
+    """ov2_mono_init_result"""
+    _fields_ = [("action", C.c_int), ("nb2dkps", C.c_int), ("p0", C.c_float), ("p0_n", C.c_int), ("p0_n_distinct", C.c_int),
+                ("p0_n_nonfinite", C.c_int), ("m", C.c_int), ("p1", C.c_float), ("status", C.c_int), ("best_row", C.c_int),
+                ("iterations", C.c_int), ("rows_consumed", C.c_int), ("score", C.c_double), ("n_inliers", C.c_int),
+                ("n_outliers", C.c_int), ("model", C.c_double * 12), ("n_removed", C.c_int), ("pose_refined", C.c_int),
+                ("Twc_init", C.c_double * 7), ("removed", C.POINTER(C.c_uint8)), ("pair_cur", C.POINTER(C.c_int)),
+                ("trace_samples", C.POINTER(C.c_int))]
+
+
 class FrameEpiPoseParams(C.Structure):
     """ov2_frame_epi_pose_params"""
     _fields_ = [("pose", FramePoseParams), ("epi", EpifilterParams)]
@@ -705,6 +727,11 @@ SIGNATURES = {
     "ov2_sampson_filter_2d_batch": (_i, [_vp, _i, C.POINTER(FkfItem), C.POINTER(_d), _f, C.POINTER(Sampson2dResult)]),
     "ov2_epipolar_filter": (_i, [_vp, C.POINTER(EpifilterParams), C.POINTER(EpifilterItem), C.POINTER(EpifilterResult)]),
     "ov2_epipolar_filter_batch": (_i, [_vp, C.POINTER(EpifilterParams), _i, C.POINTER(EpifilterItem), C.POINTER(EpifilterResult)]),
+    "ov2_mono_init": (_i, [_vp, C.POINTER(MonoInitParams), C.POINTER(MonoInitItem), C.POINTER(MonoInitResult)]),
+    "ov2_mono_init_batch": (_i, [_vp, C.POINTER(MonoInitParams), _i, C.POINTER(MonoInitItem), C.POINTER(MonoInitResult)]),
+    "ov2_btracker_mono_init_begin": (_i, [_vp, _i, C.POINTER(MonoInitParams), _vp, _vp]),
+    "ov2_btracker_mono_init_end": (_i, [_vp, C.POINTER(MonoInitResult), _vp]),
+    "ov2_btracker_mono_init": (_i, [_vp, _i, C.POINTER(MonoInitParams), _vp, _vp, C.POINTER(MonoInitResult), _vp]),
     "ov2_klt_priors": (_i, [_vp, C.POINTER(KltPriorsParams), C.POINTER(KltPriorsItem), C.POINTER(KltPriorsResult)]),
     "ov2_klt_priors_batch": (_i, [_vp, C.POINTER(KltPriorsParams), _i, C.POINTER(KltPriorsItem), C.POINTER(KltPriorsResult)]),
     "ov2_stereo_priors": (_i, [_vp, C.POINTER(StereoPriorsParams), C.POINTER(StereoPriorsItem), C.POINTER(StereoPriorsResult)]),

@@ -45,3 +45,112 @@ int epif_check_params(const ov2_epifilter_params *params);
 // The chain on items [0, n_items) of the block `ds`: the gather (join, parallax, gate, packed bearings, E5Item, sample table), the
 // three launches of the search, the decision.  No synchronisation; the results are left at [o_down, total).
 int epif_chain_enqueue(hipStream_t s, const ov2_epifilter_params *params, const EpifLayout &L, uint8_t *ds, int n_items);
+
+// ---- device: what the two gather kernels share (k_epif_gather here, k_minit_gather in monoinit.hip) ----------------------------------
+#pragma clang fp contract(off)
+
+#define EPIF_THREADS 256               // four wavefronts per item
+#define EPIF_WIN 2048                  // stream positions per window of the draw (8.5 KB of LDS)
+
+__device__ __forceinline__ int epif_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the row that starts at position p of the window v[0, W): its eight distinct values and the draws it consumed, 0 when the window
+// ends before the row is full
+__device__ __forceinline__ int epif_row_walk(const unsigned short *v, int p, int W, int (&row)[8])
+{
+    int k = 0, c = 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) row[q] = -1;
+    while (k < 8 && p + c < W) {
+        const int x = v[p + c];
+        c++;
+        bool dup = false;
+#pragma unroll
+        for (int q = 0; q < 8; q++) dup = dup || row[q] == x;      // empty slots hold -1
+        if (dup) continue;
+#pragma unroll
+        for (int q = 0; q < 8; q++) row[q] = q == k ? x : row[q];
+        k++;
+    }
+    return k == 8 ? c : 0;
+}
+
+// The table of ov2_epipolar_draw_samples(seed, m, S) into tab (two int4 per row), by the EPIF_THREADS lanes of one work-group (t: the
+// lane's index in it; every lane calls, m >= 8 and S >= 1 are uniform).  Draw j is splitmix64(seed, j) % m; a slot that repeats an
+// earlier slot of its row is drawn again.  A row always starts from an empty state, so "the row that starts at stream position p
+// consumes cnt(p) draws" is a function of p alone: a window of the stream is evaluated for every p by lanes, the row starts are then the
+// chain 0, cnt(0), cnt(0) + cnt(cnt(0)), ... (dependent LDS reads, eight rows per read), and the rows are filled by lanes again.
+// LDS, all of it the caller's and free for the taking once the work-group has passed a barrier behind its last use: s_a (2 EPIF_WIN
+// unsigned shorts: the window and its counts), s_c (3 EPIF_WIN: the counts over 2, 4 and 8 rows), s_start (EPIF_WIN / 8).
+__device__ __forceinline__ void epif_draw_table(unsigned long long seed, int m, int S, int4 *tab, unsigned short *s_a, unsigned short *s_c,
+                                                unsigned short *s_start, int t)
+{
+    unsigned short *s_v = s_a, *s_cnt = s_v + EPIF_WIN;
+    const unsigned um = (unsigned)m, c32 = (0xffffffffu % um + 1u) % um;       // 2^32 mod m
+    int r = 0;
+    unsigned long long j0 = 0;
+    bool whole = false;                                            // the last window was a short one and held no whole row
+    for (int win = 0; win <= 2 * S && r < S; win++) {              // a window completes a row, or is evaluated again as a whole one, or ends the loop
+        int W = 16 * (S - r) + 64;                                 // a few rows left need no whole window: an estimate, not a bound
+        W = (whole || W > EPIF_WIN) ? EPIF_WIN : W;
+        for (int p = t; p < W; p += EPIF_THREADS) {                // z % m through 32-bit halves: m < 2^11, so nothing overflows
+            const unsigned long long z = e5_splitmix64(seed, j0 + (unsigned long long)p);
+            const unsigned hi = (unsigned)(z >> 32), lo = (unsigned)z;
+            s_v[p] = (unsigned short)(((hi % um) * c32 + lo % um) % um);
+        }
+        __syncthreads();
+        for (int p = t; p < W; p += EPIF_THREADS) {
+            int row[8];
+            s_cnt[p] = (unsigned short)epif_row_walk(s_v, p, W, row);
+        }
+        __syncthreads();
+        // the counts over 2, 4 and 8 consecutive rows (0 where one of them runs past the window), so that the chain below makes
+        // one dependent read per EIGHT rows
+        for (int lv = 0; lv < 3; lv++) {
+            const unsigned short *src = lv == 0 ? s_cnt : s_c + (lv - 1) * EPIF_WIN;
+            unsigned short *dst = s_c + lv * EPIF_WIN;
+            for (int p = t; p < W; p += EPIF_THREADS) {
+                const int c = src[p], q = p + c;
+                const int c2 = (c != 0 && q < W) ? src[q] : 0;
+                dst[p] = (unsigned short)(c2 != 0 ? c + c2 : 0);
+            }
+            __syncthreads();
+        }
+        const unsigned short *s_c8 = s_c + 2 * EPIF_WIN;
+        int ng = 0, pos = 0;                                       // uniform: every lane reads the same words
+        while (pos < W && r + 8 * (ng + 1) <= S) {
+            const int c = s_c8[pos];
+            if (c == 0) break;                                     // fewer than eight whole rows are left in the window
+            if (t == 0) s_start[ng] = (unsigned short)pos;
+            ng++; pos += c;
+        }
+        if (t == 0) s_start[ng] = (unsigned short)pos;             // the tail: up to seven rows, one read each
+        int nt = 0;
+        while (pos < W && r + 8 * ng + nt < S && nt < 8) {
+            const int c = s_cnt[pos];
+            if (c == 0) break;                                     // the row runs past the window
+            nt++; pos += c;
+        }
+        const int nr = 8 * ng + nt;
+        __syncthreads();
+        if (nr == 0) {
+            if (W == EPIF_WIN) break;                              // a row of more than EPIF_WIN draws: see the header
+            whole = true;                                          // the short window was the estimate's fault: the same positions again,
+            continue;                                              // as a whole window (the barrier above covers the rewrite of s_v)
+        }
+        whole = false;
+        for (int q = t; q < nr; q += EPIF_THREADS) {
+            int row[8], p = s_start[q >> 3];
+            for (int k = 0; k < (q & 7); k++) p += s_cnt[p];
+            epif_row_walk(s_v, p, W, row);
+            tab[2 * (r + q)] = make_int4(row[0], row[1], row[2], row[3]);
+            tab[2 * (r + q) + 1] = make_int4(row[4], row[5], row[6], row[7]);
+        }
+        r += nr; j0 += (unsigned long long)pos;
+        __syncthreads();                                           // s_v and s_start are rewritten by the next window
+    }
+    for (int rr = r + t; rr < S; rr += EPIF_THREADS) {             // the bound was met: rows the search skips
+        tab[2 * rr] = make_int4(-1, -1, -1, -1);
+        tab[2 * rr + 1] = make_int4(-1, -1, -1, -1);
+    }
+}

@@ -229,6 +229,23 @@ int ov2_launch_kf_decision(hipStream_t s, const ov2_fkf_params *params, int n_it
     return OV2_OK;
 }
 
+// k_fkf_parallax in the form of ov2_parallax_batch(unrot, filter, stat) on a caller-owned device block: monoinit.hip puts it ahead of
+// its own kernels.  cur_unpx is read without unrot, cur_bv with it; the grid fields of params are not read.
+int ov2_launch_parallax(hipStream_t s, const ov2_fkf_params *params, int unrot, int filter, int stat, int n_items, const FkfItemD *items_d,
+                        const int *cur_lmid, const float2 *cur_unpx, const double *cur_bv, const uint8_t *cur_is3d, const int *kf_lmid,
+                        const float2 *kf_unpx, int *out_d)
+{
+    FkfParamsD P;
+    for (int j = 0; j < 4; j++) P.K[j] = params->K[j];
+    P.ncellsize = params->ncellsize; P.nbwcells = params->nbwcells; P.nbhcells = params->nbhcells; P.nbmaxkps = params->nbmaxkps;
+    P.finit_parallax = params->finit_parallax; P.stereo = params->stereo ? 1 : 0;
+    P.unrot = unrot; P.filter = filter; P.stat = stat; P.decide = 0;
+    hipLaunchKernelGGL(k_fkf_parallax, dim3(n_items), dim3(FKF_THREADS), 0, s, P, items_d, cur_lmid, (const float2 *)nullptr, cur_unpx,
+                       cur_bv, cur_is3d, kf_lmid, kf_unpx, out_d);
+    OV2_HIP_CHECK(hipGetLastError());
+    return OV2_OK;
+}
+
 int fkf_check_decide(const ov2_fkf_params *params)
 {
     OV2_REQUIRE(params->ncellsize > 0 && params->nbwcells > 0 && params->nbhcells > 0, OV2_EINVAL,

@@ -74,3 +74,8 @@ int fkf_check_decide(const ov2_fkf_params *params);
 int ov2_launch_kf_decision(hipStream_t s, const ov2_fkf_params *params, int n_items, const FkfItemD *items_d, const int *cur_lmid,
                            const float2 *cur_px, const float2 *cur_unpx, const double *cur_bv, const uint8_t *cur_is3d, const int *kf_lmid,
                            const float2 *kf_unpx, int *out_d);
+// k_fkf_parallax in the form of ov2_parallax_batch(unrot, filter, stat) on a caller-owned device block (fkf.hip): out_d gets the
+// parallax bits, n, n_distinct and n_nonfinite of every item
+int ov2_launch_parallax(hipStream_t s, const ov2_fkf_params *params, int unrot, int filter, int stat, int n_items, const FkfItemD *items_d,
+                        const int *cur_lmid, const float2 *cur_unpx, const double *cur_bv, const uint8_t *cur_is3d, const int *kf_lmid,
+                        const float2 *kf_unpx, int *out_d);

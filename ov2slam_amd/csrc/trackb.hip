@@ -49,6 +49,7 @@ static_assert(sizeof(FkfItemD) == BT_FKF_ITEM_BYTES && 4 * FKF_OUT_INTS == BT_KF
 static_assert(sizeof(ov2_create_keyframe_result) == BT_CKF_REC_BYTES && sizeof(SelectOut) == BT_CKF_SO_BYTES, "trackb_layout.hpp: the createKeyframe block's records");
 static_assert(sizeof(ov2_stereo_keyframe_result) == BT_SKF_REC_BYTES && sizeof(SkfItemD) == 16, "trackb_layout.hpp: the stereo keyframe block's records");
 static_assert(sizeof(ov2_temporal_keyframe_result) == BT_TKF_REC_BYTES, "trackb_layout.hpp: the temporal keyframe block's record");
+static_assert(sizeof(MinitOut) == BT_MINIT_REC_BYTES, "trackb_layout.hpp: the mono initialisation block's record");
 static_assert(sizeof(ov2_resident_op) == BT_RES_OP_BYTES && sizeof(ov2_resident_update_result) == BT_RES_REC_BYTES, "trackb_layout.hpp: the resident frame's records");
 
 // ---- the block types (trackb.hpp) ----
@@ -181,7 +182,7 @@ static void btracker_free(ov2_btracker *t)
     for (IoBlock *b : {&t->pt, &t->map, &t->pose, &t->epi, &t->mono}) b->release();
     if (t->depi) (void)hipFree(t->depi);
     for (DevBlock *b : {&t->res, &t->mw, &t->work, &t->fx, &t->det, &t->out, &t->roi, &t->ckf, &t->ckw, &t->fr, &t->ctl, &t->skf, &t->anc, &t->tkf,
-                        &t->ap, &t->kfpx})
+                        &t->ap, &t->kfpx, &t->mi})
         b->release();
     delete t;
 }
@@ -194,6 +195,7 @@ static const struct { const char *name, *sign; } k_calls[] = {
     {"create_keyframe", "ov2_btracker_create_keyframe_begin"},
     {"stereo_keyframe", "ov2_btracker_stereo_keyframe"},
     {"temporal_keyframe", "ov2_btracker_temporal_keyframe"},
+    {"mono_init", "ov2_btracker_mono_init"},
 };
 int begin_guard(const ov2_btracker *t, OpenCall who)
 {

@@ -15,6 +15,7 @@
 #include "mvg_dev.hpp"
 #include "fkf_dev.hpp"
 #include "kltkf_dev.hpp"
+#include "monoinit_dev.hpp"
 #include "trackb_layout.hpp"
 #include <deque>
 #include <initializer_list>
@@ -78,7 +79,7 @@ struct LastInputs {
 };
 
 // the calls that stay open between a _begin and its _end
-enum OpenCall { CALL_NONE = 0, CALL_STEP, CALL_CKF, CALL_SKF, CALL_TKF };
+enum OpenCall { CALL_NONE = 0, CALL_STEP, CALL_CKF, CALL_SKF, CALL_TKF, CALL_MINIT };
 
 struct ov2_btracker {
     ov2_ctx *ctx = nullptr;
@@ -205,6 +206,12 @@ struct ov2_btracker {
     BtKfPxLayout kl;
     DevBlock kfpx;
     std::vector<uint8_t> kf_has_pyr;
+    // ov2_btracker_mono_init (f25), allocated by its first call: the I/O block (pinned [0, i_down), and its device mirror with the
+    // chain's block behind: BtMinitLayout, regrown when a call draws more rows), and the call between _begin and _end
+    BtMinitLayout il;
+    int mi_rows = -1;
+    DevBlock mi;
+    struct MinitPending { int n_active = 0; std::vector<uint8_t> action; } ipend;
     // the call between a _begin and its _end: at most one at a time (begin_guard)
     OpenCall open = CALL_NONE;
     bool open_call() const { return open != CALL_NONE; }

@@ -1,8 +1,8 @@
 // trackb_layout.hpp -- the ONE place that knows where things lie in the lock-step tracker's host-visible blocks (trackb.hip): the
 // point block, the map block, the pose block, the epipolar I/O block, the filter's device-only index block, the three blocks of
 // ov2_btracker_track_mono, the block of ov2_btracker_create_keyframe, the two blocks of the resident frame, the block of
-// ov2_btracker_stereo_keyframe and the blocks of ov2_btracker_temporal_keyframe, each computed by one function of (batch, n_max) (the
-// last two: and the grid's cells / the anchor table's rows).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
+// ov2_btracker_stereo_keyframe, the blocks of ov2_btracker_temporal_keyframe and the block of ov2_btracker_mono_init, each computed
+// by one function of (batch, n_max) (stereo_keyframe and temporal_keyframe: and the grid's cells / the anchor table's rows).  Plain C++ (no HIP types, no context): trackb.hip includes it, tests/test_lockstep_layout.py compiles
 // it alone with g++ and checks every offset.  `slots` below is batch x n_max; a section start is a multiple of 256 unless noted.
 #pragma once
 #include <stddef.h>
@@ -227,6 +227,26 @@ static inline BtTkfLayout bt_tkf_layout(int batch, int n_max, int n_src_max)
     L.w_src = c.take(4 * slots); L.w_is = c.take(slots); L.dev_bytes = c.off;
     StageCursor q(256);
     L.p_item = q.take(4 * rows); L.p_kfid = q.take(4 * rows); L.p_Twc = q.take(56 * rows); L.pose_bytes = q.off;
+    return L;
+}
+
+// The block of ov2_btracker_mono_init (f25): one pinned host block [0, i_down) and its device mirror at the same offsets, ONE copy up
+// ([0, i_up)) and ONE copy down ([i_io, i_down)); behind i_down the device-only ranges: what k_minit_input leaves for
+// Frame::computeKeypoint, then (at w_chain) the chain's own block -- monoinit_dev.hpp: MinitLayout at capacity, batch x n_max slots and
+// batch x n_rows rows, so its size follows the rows of the call and the device half is grown when a call asks for more.
+//   up only     [act 1][seed 8 per item]: 1 where the item is requested and has a resident keyframe with its info
+//   down only   [record 224 per item][removed 1 per slot]
+//   device only [count 4 per item][px 8 per slot][the chain's block]
+#define BT_MINIT_REC_BYTES 224       // sizeof(MinitOut): trackb.hip asserts it
+struct BtMinitLayout { size_t i_act, i_seed, i_up, i_io, i_rec, i_rm, i_down, w_nd, w_px, w_chain; };
+static inline BtMinitLayout bt_minit_layout(int batch, int n_max)
+{
+    const size_t B = (size_t)batch, slots = (size_t)n_max * B;
+    StageCursor c(256);
+    BtMinitLayout L;
+    L.i_act = c.take(B); L.i_seed = c.take(8 * B); L.i_up = c.off;
+    L.i_io = L.i_rec = c.take(BT_MINIT_REC_BYTES * B); L.i_rm = c.take(slots); L.i_down = c.off;
+    L.w_nd = c.take(4 * B); L.w_px = c.take(8 * slots); L.w_chain = c.off;
     return L;
 }
 

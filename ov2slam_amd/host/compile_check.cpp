@@ -53,6 +53,10 @@ static auto const check_kf_sort = &ov2::detail::sortKeyframeByLmid;
 static int (*const check_epif)(ov2::Context &, const ov2::EpipolarFilterParams &, const ov2::EpipolarFilterInput &, ov2::EpipolarFilterOutput &) = &ov2::epipolar2d2dFiltering;
 static int (*const check_epif_batch)(ov2::Context &, const ov2::EpipolarFilterParams &, const std::vector<ov2::EpipolarFilterInput> &,
                                      std::vector<ov2::EpipolarFilterOutput> &) = &ov2::epipolar2d2dFiltering;
+// trackMono's un-initialised branch (checkReadyForInit) as one device chain, single and batch
+static int (*const check_minit)(ov2::Context &, const ov2::MonoInitParams &, const ov2::MonoInitInput &, ov2::MonoInitOutput &) = &ov2::checkReadyForInit;
+static int (*const check_minit_batch)(ov2::Context &, const ov2::MonoInitParams &, const std::vector<ov2::MonoInitInput> &,
+                                      std::vector<ov2::MonoInitOutput> &) = &ov2::checkReadyForInit;
 // the tracking priors: kltPriors / stereoPriors, single and batch, and their host-only helpers
 static int (*const check_klt_priors)(ov2::Context &, const ov2::ProjectionCamera &, bool, const ov2::KltPriorsInput &, std::vector<ov2::Point2f> &,
                                      std::vector<uint8_t> &) = &ov2::kltPriors;

@@ -395,6 +395,98 @@ inline int epipolar2d2dFiltering(Context &ctx, const EpipolarFilterParams &param
     return OV2_OK;
 }
 
+// ---- trackMono's un-initialised branch (:98-113) with checkReadyForInit (:855-984) as one device chain on ov2_mono_init: the count
+// of 2-D keypoints, the plain median parallax, the join, the rotation-compensated parallax of :908-913, the 5-point search over a
+// table drawn on the device from `seed`, the removals and the initial pose.  The frame is a FrameVsKeyframe plus the keyframe's
+// bearings.  out.r.action says which return the reference takes (OV2_MINIT_RESET: breset_req_ = true; OV2_MINIT_READY: true; any other:
+// false).  vremove: the lmids the reference hands to removeObsFromCurFrameById (:962-965), in its order.  out.r.Twc_init (where
+// OV2_MINIT_READY) is the pose of the UNREFINED model: the reference refines it first (OpenGV, not provided; out.r.pose_refined is
+// 0), so it is NOT the reference's pose until a refinement exists.
+struct MonoInitParams {
+    KfReqParams kf;                                           // K and finit_parallax are read
+    int nransac_iter = 100;                                   // SlamParams: nransac_iter_, fransac_err_
+    float fransac_err = 3.f;
+    double threshold = 0.;                                    // 0: 2 (1 - cos(atan(fransac_err / focal))) from K, as the reference
+    double probability = 0.99;
+    int n_rows = 200;                                         // rows of the sample table per frame
+    int min_2d_kps = 50;                                      // :100
+};
+struct MonoInitInput {
+    FrameVsKeyframe f;
+    std::vector<double> kf_bv;                                // pkf's Keypoint::bv_, 3 doubles each, in the order of f.kf_lmid
+    unsigned long long seed = 0;
+};
+struct MonoInitOutput {
+    ov2_mono_init_result r;
+    std::vector<uint8_t> removed;
+    std::vector<int> pair_cur;
+    std::vector<int> vremove;
+};
+namespace detail {
+struct MinitPacked { FkfPacked fkf; std::vector<double> kf_bv; ov2_mono_init_item item; };
+inline bool packMinit(const MonoInitInput &in, MinitPacked &p, MonoInitOutput &out)
+{
+    const size_t n = in.f.cur_lmid.size();
+    if (!packFkf(in.f, p.fkf, &in.kf_bv, &p.kf_bv)) return false;          // one sort: ids, pixels and bearings together
+    static const double none_d[3] = {0., 0., 0.};
+    p.item.fkf = p.fkf.item;
+    p.item.kf_bv = p.kf_bv.empty() ? none_d : p.kf_bv.data();
+    p.item.seed = in.seed;
+    out.removed.assign(n ? n : 1, 0); out.pair_cur.assign(n ? n : 1, 0); out.vremove.clear();
+    out.r = ov2_mono_init_result{};
+    out.r.removed = out.removed.data(); out.r.pair_cur = out.pair_cur.data();
+    return true;
+}
+inline ov2_mono_init_params minitParams(const MonoInitParams &c)
+{
+    ov2_mono_init_params p{};
+    p.fkf = fkfParams(c.kf);
+    p.epi.max_iterations = c.nransac_iter; p.epi.probability = c.probability; p.epi.boptimize = 0;
+    if (c.threshold > 0.) p.epi.threshold = c.threshold;
+    else {                                                    // src/multi_view_geometry.cpp:640-641
+        const float focal = (float)((double)((float)c.kf.K[0] + (float)c.kf.K[1]) / 2.);
+        p.epi.threshold = 2.0 * (1.0 - std::cos(std::atan((double)(c.fransac_err / focal))));
+    }
+    p.n_rows = c.n_rows; p.min_2d_kps = c.min_2d_kps;
+    return p;
+}
+inline void finishMinit(const MonoInitInput &in, MonoInitOutput &out)
+{
+    out.removed.resize(in.f.cur_lmid.size());
+    out.pair_cur.resize((size_t)(out.r.m > 0 ? out.r.m : 0));
+    for (int idx : out.pair_cur) if (out.removed[(size_t)idx] == 1) out.vremove.push_back(in.f.cur_lmid[(size_t)idx]);
+    out.r.removed = out.removed.data(); out.r.pair_cur = out.pair_cur.data();
+}
+}  // namespace detail
+
+inline int checkReadyForInit(Context &ctx, const MonoInitParams &params, const MonoInitInput &in, MonoInitOutput &out)
+{
+    detail::MinitPacked p;
+    if (!detail::packMinit(in, p, out)) return OV2_EINVAL;
+    const ov2_mono_init_params mp = detail::minitParams(params);
+    const int rc = ov2_mono_init(ctx.get(), &mp, &p.item, &out.r);
+    if (rc != OV2_OK) return rc;
+    detail::finishMinit(in, out);
+    return OV2_OK;
+}
+// the frames of a lock-step batch in one chain
+inline int checkReadyForInit(Context &ctx, const MonoInitParams &params, const std::vector<MonoInitInput> &ins, std::vector<MonoInitOutput> &outs)
+{
+    std::vector<detail::MinitPacked> packed(ins.size());
+    std::vector<ov2_mono_init_item> items(ins.size());
+    std::vector<ov2_mono_init_result> rs(ins.size());
+    outs.assign(ins.size(), MonoInitOutput());
+    for (size_t b = 0; b < ins.size(); b++) {
+        if (!detail::packMinit(ins[b], packed[b], outs[b])) return OV2_EINVAL;
+        items[b] = packed[b].item; rs[b] = outs[b].r;
+    }
+    const ov2_mono_init_params mp = detail::minitParams(params);
+    const int rc = ov2_mono_init_batch(ctx.get(), &mp, (int)ins.size(), items.data(), rs.data());
+    if (rc != OV2_OK) return rc;
+    for (size_t b = 0; b < ins.size(); b++) { outs[b].r = rs[b]; detail::finishMinit(ins[b], outs[b]); }
+    return OV2_OK;
+}
+
 // ---- the priors of kltTracking (:156-184) on ov2_klt_priors: every 3-D keypoint's map point projected with the predicted pose
 // (projWorldToImageDist), a prior where it lands in the image (isInImage) and kp.px_ otherwise.  The caller hands over the
 // keypoints in the iteration order of pcurframe_->mapkps_ with the map point of each 3-D one (pmap_->map_plms_.at(lmid)->getPoint();

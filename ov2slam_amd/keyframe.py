@@ -5,6 +5,8 @@ of the C ABI (ov2_parallax / ov2_kf_decision / ov2_sampson_filter_2d and their b
     kf_decision         VisualFrontEnd::checkNewKfReq (:986-1061)
     sampson_filter_2d   the Sampson pass over the 2-D keypoints after the 5-point search (:610-652)
     epipolar_filter     VisualFrontEnd::epipolar2d2dFiltering (:440-656) as one device chain (ov2_epipolar_filter, csrc/epifilter.hip)
+    mono_init           trackMono's un-initialised branch (:98-113) with checkReadyForInit (:855-984) as one device chain
+                        (ov2_mono_init, csrc/monoinit.hip)
 
 An item is a dict named like the fields of ov2_fkf_item (the counts follow from the array lengths): cur_lmid (n,), cur_px (n,2),
 cur_unpx (n,2), cur_bv (n,3), cur_is3d (n,), cur_Twc (7,), kf_lmid (m,) strictly ascending, kf_unpx (m,2), kf_Tcw (7,), and the
@@ -20,6 +22,10 @@ ALL, ONLY_2D, ONLY_3D = L.OV2_FKF_ALL, L.OV2_FKF_ONLY_2D, L.OV2_FKF_ONLY_3D
 AVG, MEDIAN, AVG_WIDE = L.OV2_FKF_AVG, L.OV2_FKF_MEDIAN, L.OV2_FKF_AVG_WIDE
 EPIF_TOO_FEW_KPS, EPIF_LOW_PARALLAX, EPIF_NO_MODEL, EPIF_DEGENERATE, EPIF_FILTERED = (
     L.OV2_EPIF_TOO_FEW_KPS, L.OV2_EPIF_LOW_PARALLAX, L.OV2_EPIF_NO_MODEL, L.OV2_EPIF_DEGENERATE, L.OV2_EPIF_FILTERED)
+(MINIT_RESET, MINIT_LOW_PARALLAX, MINIT_TOO_FEW_KPS, MINIT_TOO_FEW_MATCHES, MINIT_LOW_ROT_PARALLAX, MINIT_NO_MODEL, MINIT_READY,
+ MINIT_NOT_REQUESTED, MINIT_NO_KEYFRAME) = (
+    L.OV2_MINIT_RESET, L.OV2_MINIT_LOW_PARALLAX, L.OV2_MINIT_TOO_FEW_KPS, L.OV2_MINIT_TOO_FEW_MATCHES, L.OV2_MINIT_LOW_ROT_PARALLAX,
+    L.OV2_MINIT_NO_MODEL, L.OV2_MINIT_READY, L.OV2_MINIT_NOT_REQUESTED, L.OV2_MINIT_NO_KEYFRAME)
 
 _FKF_FIELDS = (("cur_lmid", np.int32, C.c_int, 1), ("cur_px", np.float32, C.c_float, 2), ("cur_unpx", np.float32, C.c_float, 2),
                ("cur_bv", np.float64, C.c_double, 3), ("cur_is3d", np.uint8, C.c_uint8, 1), ("kf_lmid", np.int32, C.c_int, 1),
@@ -250,3 +256,100 @@ def epipolar_filter_batch(ctx, params, items, *, trace_samples=False):
         outs.append(out)
     L.check(ctx.lib.ov2_epipolar_filter_batch(ctx.h, C.byref(p), len(items), S, R))
     return [_epifilter_dict(R[b], outs[b]) for b in range(len(items))]
+
+
+# ---- mono initialisation ------------------------------------------------------------------------------------------------------------
+def mono_init_params(fkf, *, max_iterations, threshold, n_rows, min_2d_kps=50, probability=0.99, boptimize=False):
+    """ov2_mono_init_params: the ov2_fkf_params (or the dict of them; K and finit_parallax are read), the search's nransac_iter_ and
+    bearing threshold, the rows of the sample table drawn per item and the 2-D keypoint count below which trackMono asks for a reset
+    (the reference's literal 50; 0: no such test)"""
+    p = L.MonoInitParams()
+    p.fkf = _as_fkf_params(fkf)
+    p.epi.max_iterations, p.epi.threshold, p.epi.probability = int(max_iterations), float(threshold), float(probability)
+    p.epi.boptimize = int(bool(boptimize))
+    p.n_rows, p.min_2d_kps = int(n_rows), int(min_2d_kps)
+    return p
+
+
+def _as_mono_init_params(params):
+    if isinstance(params, L.MonoInitParams):
+        return params
+    return mono_init_params(params["fkf"], max_iterations=params["max_iterations"], threshold=params["threshold"],
+                            n_rows=params["n_rows"], min_2d_kps=params.get("min_2d_kps", 50),
+                            probability=params.get("probability", 0.99), boptimize=params.get("boptimize", False))
+
+
+def _mono_init_item(item):
+    """(ov2_mono_init_item, the arrays it points into): the ov2_fkf_item dict plus kf_bv (m, 3) and seed"""
+    s = L.MonoInitItem()
+    s.fkf, keep = _fkf_item(item)
+    a = item.get("kf_bv")
+    a = np.zeros(0, np.float64) if a is None else np.ascontiguousarray(a, np.float64)
+    if a.size != 3 * s.fkf.n_kf:
+        raise ValueError("frame versus keyframe: kf_bv has %d elements, not 3 per keypoint" % a.size)
+    keep["kf_bv"] = a
+    s.kf_bv = a.ctypes.data_as(C.POINTER(C.c_double))
+    s.seed = int(item.get("seed", 0)) & ((1 << 64) - 1)
+    return s, keep
+
+
+def _mono_init_result(n, n_rows, trace):
+    out = dict(removed=np.zeros(n, np.uint8), pair_cur=np.zeros(n, np.int32))
+    r = L.MonoInitResult()
+    r.removed = out["removed"].ctypes.data_as(C.POINTER(C.c_uint8))
+    r.pair_cur = out["pair_cur"].ctypes.data_as(C.POINTER(C.c_int))
+    if trace:
+        out["samples"] = np.full((n_rows, 8), -1, np.int32)
+        r.trace_samples = out["samples"].ctypes.data_as(C.POINTER(C.c_int))
+    return r, out
+
+
+def _mono_init_record(r):
+    """the scalar and fixed-size fields of an ov2_mono_init_result"""
+    return _mono_init_fields(r, {})
+
+
+def _mono_init_dict(r, out):
+    _mono_init_fields(r, out)
+    out["pair_cur"] = out["pair_cur"][:max(r.m, 0)]
+    if "samples" in out and not (MINIT_NO_MODEL <= r.action <= MINIT_READY and out["samples"].shape[0] > 0):
+        out["samples"] = None                                      # no table was drawn
+    return out
+
+
+def _mono_init_fields(r, out):
+    out.update(action=r.action, nb2dkps=r.nb2dkps, p0=np.float32(r.p0), p0_n=r.p0_n, p0_n_distinct=r.p0_n_distinct,
+               p0_n_nonfinite=r.p0_n_nonfinite, m=r.m, p1=np.float32(r.p1), status=r.status, best_row=r.best_row,
+               iterations=r.iterations, rows_consumed=r.rows_consumed, score=np.float64(r.score), n_inliers=r.n_inliers,
+               n_outliers=r.n_outliers, model=np.array(r.model[:], np.float64), n_removed=r.n_removed, pose_refined=r.pose_refined,
+               Twc_init=np.array(r.Twc_init[:], np.float64))
+    return out
+
+
+def mono_init(ctx, params, item, *, trace_samples=False):
+    """ov2_mono_init: the mono initialisation test of one frame against its keyframe.  Returns a dict named like
+    ov2_mono_init_result: action (MINIT_*), nb2dkps, p0 (np.float32) with p0_n / p0_n_distinct / p0_n_nonfinite, m, p1 (np.float32),
+    the search's status / best_row / iterations / rows_consumed / score / n_inliers / n_outliers / model (12,), n_removed, removed
+    (n,) uint8, pair_cur (m,), Twc_init (7,) -- the pose of the UNREFINED model, pose_refined = 0 --; with trace_samples the table
+    the device drew (n_rows, 8), None where the item did not search."""
+    p = _as_mono_init_params(params)
+    s, keep = _mono_init_item(item)
+    r, out = _mono_init_result(s.fkf.n_cur, p.n_rows, trace_samples)
+    L.check(ctx.lib.ov2_mono_init(ctx.h, C.byref(p), C.byref(s), C.byref(r)))
+    return _mono_init_dict(r, out)
+
+
+def mono_init_batch(ctx, params, items, *, trace_samples=False):
+    """ov2_mono_init_batch: the frames of a lock-step batch in one chain (shared params); one dict per item"""
+    p = _as_mono_init_params(params)
+    items = list(items)
+    S = (L.MonoInitItem * max(1, len(items)))()
+    R = (L.MonoInitResult * max(1, len(items)))()
+    keep, outs = [], []
+    for b, it in enumerate(items):
+        S[b], k = _mono_init_item(it)
+        R[b], out = _mono_init_result(S[b].fkf.n_cur, p.n_rows, trace_samples)
+        keep.append(k)
+        outs.append(out)
+    L.check(ctx.lib.ov2_mono_init_batch(ctx.h, C.byref(p), len(items), S, R))
+    return [_mono_init_dict(R[b], outs[b]) for b in range(len(items))]

@@ -1,6 +1,6 @@
 """LockstepTracker: `batch` camera streams in lock-step on top of ov2_btracker_* (include/ov2slam_hip.h, csrc/trackb.hip).
 
-Every lock-step call family of the C ABI (track_frame ... temporal_keyframe) comes as three entry points -- the whole call, _begin
+Every lock-step call family of the C ABI (track_frame ... temporal_keyframe, mono_init) comes as three entry points -- the whole call, _begin
 and _end --, and the argument list of the whole call is _begin's followed by _end's.  The binding has one path for all of them:
 
     _marshal_<family>(public arguments) -> _Call      what _begin takes, and every array and struct those arguments point at
@@ -68,6 +68,8 @@ class _Results:
                                  invdepth=((), np.float64))),
         "temporal_keyframe": (L.TemporalKeyframeResult, tuple(k for k, _ in L.TemporalKeyframeResult._fields_),
                               dict(tri_status=((), np.uint8), wpt=((3,), np.float64), invdepth=((), np.float64), src_kfid=((), np.int32))),
+        # (keys None: the record holds floats and arrays, keyframe._mono_init_record reads it)
+        "mono_init": (L.MonoInitResult, None, dict(removed=((), np.uint8))),
     }
 
     def __init__(self, trk, family, call, out=None):
@@ -110,6 +112,8 @@ class _Results:
         from . import pose as _pose
         na, nn = self.na, self.nn
         if self.family in self.KEYFRAME:
+            if self.keys is None:
+                return [_kf._mono_init_record(self.R[b]) for b in range(na)], self.out
             return [{k: int(getattr(self.R[b], k)) for k in self.keys} for b in range(na)], self.out
         res = (self.out, self.st, self.p3p.astype(bool))
         if "F" in self.parts:
@@ -377,6 +381,16 @@ class LockstepTracker:
         if len(d) < na:
             raise ValueError("one flag per active item")
         return _Call("temporal_keyframe", na, (na, C.byref(params), _ptr(d)), params=params, do=d)
+
+    def _marshal_mono_init(self, n_active, do, seed, params):
+        from . import keyframe as _kf
+        c = self._marshal_temporal_keyframe(n_active, do, _kf._as_mono_init_params(params))
+        sd = np.ascontiguousarray(seed, np.uint64).reshape(-1)
+        if len(sd) < c.na:
+            raise ValueError("one seed per active item")
+        c.family, c.args = "mono_init", c.args + (_ptr(sd),)
+        c.keep.update(seed=sd)
+        return c
 
     # ---- the lock-step calls ------------------------------------------------------------------------------------------------------------
     def trackFrame(self, imgs, kps, pri, hasprior, n, klt_use_prior=True):
@@ -723,6 +737,25 @@ class LockstepTracker:
     def temporalKeyframeEnd(self, out=None):
         """second half of temporalKeyframe -> (records, out)"""
         return self._end("temporal_keyframe", out)
+
+    # ---- trackMono's un-initialised branch on the resident frame and keyframe (ov2_btracker_mono_init) ----------------------------------
+    def monoInit(self, n_active, do, seed, params, out=None):
+        """checkReadyForInit for the items with do[b] != 0, right after their trackMonoResident step, on the resident frame, pose and
+        keyframe (ov2_btracker_mono_init): one enqueue, no per-slot byte goes up.  Where the action is MINIT_READY the removed slots
+        leave the resident frame and the resident pose becomes Twc_init (the pose of the UNREFINED model: pose_refined = 0); the
+        motion state of every item that ran is reset.  seed: one per item, of the sample table; params:
+        keyframe.mono_init_params(...) or the dict of them; out: dict with `removed` to scatter into (missing: zeros).
+        -> (records, out): records[b] is the dict of keyframe.mono_init without its arrays (action L.OV2_MINIT_*, NOT_REQUESTED and
+        NO_KEYFRAME among them); out["removed"] (batch, n_max) uint8"""
+        return self._whole(self._marshal_mono_init(n_active, do, seed, params), out)
+
+    def monoInitBegin(self, n_active, do, seed, params):
+        """first half of monoInit: enqueue and return; monoInitEnd finishes it"""
+        self._begin(self._marshal_mono_init(n_active, do, seed, params))
+
+    def monoInitEnd(self, out=None):
+        """second half of monoInit -> (records, out)"""
+        return self._end("mono_init", out)
 
     def lastPriors(self, item, n):
         """(prior (n, 2) float32, has_prior (n,) uint8) of item `item` as the last step used them"""
